@@ -19,16 +19,20 @@ Inputs (`--input`): the reference's damped sine (data.py:8-22; SURVEY 8(d)'s gen
 or SURVEY 8(d)'s band-limited random walk; parameters by the reference's initialisation rules (model.py:36-39, 49, 218-219) with
 train.py:41-43 hyper-parameters, seed 0 (D > 64: SURVEY 8(d)'s scaled R_in, which keeps 1 + e x / A positive).
 
+A plain run sets up, warms up, times the K steps, writes `--dump-outputs DIR` if given (the last timed step's per-clip losses,
+gradient sums, losses, variables and Adam slots as DIR/<name>.npy) and prints the record; `roofline` and `cpu_baseline` are null.
+Everything below that is not the headline's own figure runs only with `--full`, after the timed region.
+
 Output (rank 0).  The LAST stdout line is the contract's record: ONE compact JSON object (< 4 KB; `HEADLINE_LIMIT`) with
-metric / value / config, `roofline` for the dominant kernel (the longer of the two scan launches: `achieved` / `frac` are the
-contract's ALGORITHMIC flops -- SURVEY 8(d): 24 D^2 forward, 56 D^2 backward per clip-sample -- over the launch time measured with
-HIP events on the launch stream), `cpu_baseline` (the plain-C restatement oracle/cmps_oracle.c timed on this host's cores on a
-bounded sample) and `parity_in_bench` (the GPU results on that same sample against the oracle's, outside the timed region).
-Everything else goes out EARLIER, one JSON object per line, each of the form {"detail": name, "data": ...} (never a top-level
-"metric" key), and as sidecar files under gpurun_out/bench_detail/ when that directory can be written: `roofline_detail` (per-kernel
-/ per-pipe records, executed split, step traffic), `precision_ab` (the arithmetic modes of the rank-1 gradient sums side by side),
-`reference_style` (numpy restatement timings), `other_config:<name>` (BASELINE configs[0] shape, [1], [4] in float32 and as named,
-a few steps each with their own parity check; the headline keeps a one-line summary of each).
+metric / value / ms_per_step / config and, with --full, `roofline` for the dominant kernel (the longer of the two scan launches:
+`achieved` / `frac` are the contract's ALGORITHMIC flops -- SURVEY 8(d): 24 D^2 forward, 56 D^2 backward per clip-sample -- over the
+launch time measured with HIP events on the launch stream), `cpu_baseline` (the plain-C restatement oracle/cmps_oracle.c timed on
+this host's cores on a bounded sample) and `parity_in_bench` (the GPU results on that same sample against the oracle's).
+With --full everything else goes out EARLIER, one JSON object per line, each of the form {"detail": name, "data": ...} (never a
+top-level "metric" key), and as sidecar files under DETAIL_DIR (CMPS_BENCH_DETAIL_DIR) when that directory can be written:
+`roofline_detail` (per-kernel / per-pipe records, executed split, step traffic), `precision_ab` (the arithmetic modes of the rank-1
+gradient sums side by side), `reference_style` (numpy restatement timings), `other_config:<name>` (BASELINE configs[0] shape, [1],
+[4] in float32 and as named, a few steps each with their own parity check; the headline keeps a one-line summary of each).
 """
 from __future__ import annotations
 
@@ -76,9 +80,15 @@ def parse_args(argv=None):
                         "0.1 cumsum(N(0,1)) / sqrt(T) clipped")
     p.add_argument("--host-optimizer", action="store_true",
                    help="chain rule + Adam in numpy on the host (D2H of the gradient sums every step) instead of cmps_psi_apply_step")
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--no-precision-ab", action="store_true")
-    p.add_argument("--no-other-configs", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="after the headline, also measure and check what it does not need: per-kernel times and the roofline, the CPU "
+                        "baseline and the in-bench parity, the precision A/B, the numpy restatement timings, the other BASELINE configs "
+                        "and (N > 1) the replica check")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step computed as DIR/<name>.npy (rank 0)")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline, parity or precision A/B")
+    p.add_argument("--no-precision-ab", action="store_true", help="with --full: no precision A/B")
+    p.add_argument("--no-other-configs", action="store_true", help="with --full: no other BASELINE configs")
     p.add_argument("--cpu-clips", type=int, default=0, help="clips in the CPU sample (0 = 8 per thread)")
     p.add_argument("--spawn", action="store_true", help="go through the child-process launcher even at --gpus 1")
     p.add_argument("--launcher-selftest", action="store_true",
@@ -760,6 +770,27 @@ class Run:
                 "against": "oracle/cmps_oracle.c float32 (parity UNPINNED: no reference-held vectors exist)"}
 
 
+def dump_outputs(run, out_dir):
+    """What the last timed step computed, as its caller reads it: that step's per-clip losses and gradient sums (this rank's scan), its
+    model and total loss, and the variables and Adam slots it left behind (model.variables brings the device-resident state back).
+    All float32 except the host optimiser's losses (float64); D = 128 at batch 512 is about 0.5 MB."""
+    from audio_mps_amd.train import VAR_ORDER
+    arrays = {"loss_per_clip": run.backend._loss.cpu().numpy(), "grad_sums": run.backend._grad.cpu().numpy()}
+    if run.host_optimizer:
+        h = run.trainer.history[-1]
+        arrays["losses"] = np.array([h["model_loss"], h["total_loss"]], dtype=np.float64)
+    else:
+        arrays["losses"] = run.trainer._dev["losses"].cpu().numpy()
+    variables = run.model.variables
+    for k in VAR_ORDER:
+        arrays["var_" + k] = np.asarray(variables[k], dtype=np.float32)
+        arrays["adam_m_" + k] = np.asarray(run.trainer.opt.m[k], dtype=np.float32)
+        arrays["adam_v_" + k] = np.asarray(run.trainer.opt.v[k], dtype=np.float32)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def dtype_label(variant, D, rank1, wide_chain=1):
     """The arithmetic the path computes in (a label, not a precision claim); `arithmetic_note` has the long form."""
     if variant == V_PAIR:
@@ -857,12 +888,14 @@ def worker(ARGS):
     r = run.timed(ARGS.steps, ARGS.warmup)
     if not np.isfinite(r["last"]):
         raise SystemExit(f"non-finite loss {r['last']}")
+    if ARGS.dump_outputs and rank == 0:
+        dump_outputs(run, ARGS.dump_outputs)                     # before --full's extra steps move the state on
     allreduce_us = dp.collective_us()                            # mean HIP-event time of the collective (None at N = 1)
-    ktimes = run.kernel_pass(3) if (rank == 0 and world == 1) else None      # per-kernel durations, outside the timed region
+    ktimes = run.kernel_pass(3) if (ARGS.full and rank == 0 and world == 1) else None      # per-kernel durations, outside the timed region
     per_rank_ms = dp.gather_floats(1e3 * r["local"] / ARGS.steps)
     # the data-parallel invariant: after the same all-reduced sums every rank holds bit-identical variables and Adam slots
     replicas_ok = None
-    if world > 1 and not ARGS.host_optimizer:
+    if ARGS.full and world > 1 and not ARGS.host_optimizer:
         st = run.trainer._dev
         replicas_ok = all(dp.replicas_identical(st[k]) for k in ("vars", "m", "v"))
     rccl_world = dp.measured_world_size()                        # dist.get_world_size() after a GPU all-reduce of ones
@@ -877,8 +910,10 @@ def worker(ARGS):
         cfg_name = BASELINE_CONFIGS.get((D, T, B), "custom shape")
         if world > 1 and (D, T, B) == (32, 16000, 1024):
             cfg_name = "BASELINE configs[3] (configs[2] per GPU)" if world == 8 else f"BASELINE configs[2] per GPU x {world}"
-        roof = roofline_record(D, T, B, variant, rank1, r["t_fwd"], r["t_bwd"], ms_per_step, ktimes, wide_chain)
-        details.append(emit_detail("roofline_detail", roof))
+        roof = None
+        if ARGS.full:
+            roof = roofline_record(D, T, B, variant, rank1, r["t_fwd"], r["t_bwd"], ms_per_step, ktimes, wide_chain)
+            details.append(emit_detail("roofline_detail", roof))
         settings = collective_settings()
         out = {
             "metric": f"audio samples/sec (fwd+bwd) at D={D}, T={T}",
@@ -908,8 +943,8 @@ def worker(ARGS):
         if ARGS.rehearse_on_one_gpu:
             out["rehearsal"] = "all ranks share cuda:0 and reduce over gloo on the host: NOT a scaling measurement"
 
-    # ---- outside the timed region: CPU baseline, parity of this very workload, precision A/B, the other configs (rank 0, N = 1) ----
-    if rank == 0 and world == 1 and not ARGS.no_cpu_baseline:
+    # ---- --full, outside the timed region: CPU baseline, parity of this very workload, precision A/B, the other configs (rank 0, N = 1) ----
+    if rank == 0 and world == 1 and ARGS.full and not ARGS.no_cpu_baseline:
         run.trainer.sync_to_host()                               # the oracle sees the variables the timed steps left behind
         cb, sample, ref = cpu_baseline(run.model, D, T, ARGS.input, seed=run.seed, clips_arg=ARGS.cpu_clips)
         out["cpu_baseline"] = cb

@@ -4,7 +4,7 @@ kernel: the A/B tool for a change to ONE kernel of a multi-kernel step.  usage: 
 a diagnostic library build)"""
 import json, os, subprocess, sys
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-cmd = [sys.executable, os.path.join(root, "bench.py"), "--no-cpu-baseline", "--no-other-configs", "--no-precision-ab", "--steps", "5", "--warmup", "2"] + sys.argv[1:]
+cmd = [sys.executable, os.path.join(root, "bench.py"), "--full", "--no-cpu-baseline", "--no-other-configs", "--no-precision-ab", "--steps", "5", "--warmup", "2"] + sys.argv[1:]
 out = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, text=True, check=True).stdout
 seen = {}
 for line in out.splitlines():

@@ -9,7 +9,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/prof_$TAG
 rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-ARGS="--steps 5 --warmup 2 --no-cpu-baseline --no-other-configs --bond-dim $D --T $T --batch-per-gpu $B $*"
+ARGS="--steps 5 --warmup 2 --full --no-cpu-baseline --no-other-configs --bond-dim $D --T $T --batch-per-gpu $B $*"
 echo "python3 bench.py $ARGS" > $OUT/command.txt
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $ROOT/bench.py $ARGS > $OUT/trace.log 2>&1
 for C in FETCH_SIZE WRITE_SIZE \
