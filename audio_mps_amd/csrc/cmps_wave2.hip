@@ -6,9 +6,9 @@
 // the stash row, the loss).  k_fwd_wave runs the second one step late inside the same wave; here it runs in a second
 // wave that shares the SIMDs with the chain waves and fills their idle issue slots:
 //
-//   chain wave (waves 0-3 of the workgroup, raised priority): per step two interleaved mat-vec chains, one wave
-//     reduction, the rotation; writes y_k (256 B, split layout) into a ring in LDS; per 32-step chunk publishes
-//     `prod` = chunks written and stores the chunk's |y_k|^2 row.
+//   chain wave (waves 0-3 of the workgroup, raised priority): per step one mat-vec chain and the rotation of the
+//     UN-normalised state z_k; writes z_k (256 B, split layout) into a ring in LDS; per 32-step chunk one power-of-two
+//     rescale and publishes `prod` = chunks written.  The loss wave turns the rows into y_k = c_k z_k.
 //   loss wave (waves 4-7): nothing waits for it, so it works a whole 32-step chunk at a time ON THE MATRIX CORES: the 32 rows
 //     y_k of the chunk form Y [32 steps x 64 reals], and H Y^T is one real GEMM Y W (W = the 64 x 64 real form of
 //     H = R + R^dagger) = 2 tiles x 4 k-steps of v_mfma_f32_32x32x16_bf16.  Both operands are split EXACTLY into three bf16
@@ -25,7 +25,8 @@
 // Synchronisation is two LDS counters per clip and NO barrier: the ring holds two chunks; the loss wave starts chunk
 // c when prod >= c + 1, the chain wave starts chunk c (c >= 2) when cons >= c - 1.  LDS operations of one wave
 // complete in order, so a counter write issued after the chunk's data is visible after it.
-// Same arithmetic as k_fwd_wave (cmps_wave.hip), same stash layouts; the reverse sweep is unchanged.
+// Same arithmetic as k_fwd_wave (cmps_wave.hip) up to rounding, same stash layouts; the reverse sweep is unchanged.  Since round 6 the chain
+// carries the UN-normalised state z_k and the loss wave normalises the rows it reads.
 #include "cmps_wave_util.h"
 
 namespace cmps {
@@ -102,23 +103,6 @@ template <int N>
 __device__ __forceinline__ void lds_wait_hi_t_after(v4f (&o)[8], v2f& t, v2f& dep) {
     asm volatile("s_waitcnt lgkmcnt(%6)" : "+v"(o[4]), "+v"(o[5]), "+v"(o[6]), "+v"(o[7]), "+v"(t), "+v"(dep) : "n"(N) : "memory");
 }
-// vec[lane sel] = val (both wave-uniform): v_writelane_b32 takes its lane select from M0 when the value already occupies the
-// one SGPR operand slot; M0 is reserved by the compiler, so it is saved and restored around the instruction
-__device__ __forceinline__ void write_lane(float& vec, float val, int sel) {
-    unsigned keep;
-    asm("s_mov_b32 %1, m0\n\ts_mov_b32 m0, %3\n\tv_writelane_b32 %0, %2, m0\n\ts_mov_b32 m0, %1"
-        : "+v"(vec), "=&s"(keep) : "s"(val), "s"(sel));
-}
-template <int SEL>
-__device__ __forceinline__ void write_lane_c(float& vec, float val) {      // vec[lane SEL] = val, SEL a compile-time constant
-    asm("v_writelane_b32 %0, %1, %2" : "+v"(vec) : "s"(val), "n"(SEL));
-}
-__device__ __forceinline__ float vmax_s(float s, float c) {     // one v_max_f32 (fmaxf adds a canonicalising second one)
-    float r;
-    asm("v_max_f32 %0, %1, %2" : "=v"(r) : "s"(s), "v"(c));
-    return r;
-}
-
 }  // namespace
 
 // Diagnostic builds only (scripts/ablate.py passes -DCMPS_DIAG -DCMPS_DIAG_NO_LOSS / -DCMPS_DIAG_NO_CHAIN; results are wrong,
@@ -154,6 +138,8 @@ __global__ __launch_bounds__(128 * WAVES, 1) void k_fwd_wave2(Dev P, const float
     __shared__ __attribute__((aligned(16))) float ring[WAVES][RING][RLD];   // y_k, n = 2 i + {re, im}, rows padded (RLD)
     __shared__ __attribute__((aligned(16))) float pe[WAVES][CH2 * PE2_LD]; // y_k[n] (H y_k)[n], [step][column]
     __shared__ int flags[WAVES][2];                                         // [clip][0: prod, 1: cons]
+    __shared__ float esc[WAVES][4];                                         // 4^-e of the rescale entering chunk c, slot c & 3
+    __shared__ __attribute__((aligned(16))) float cst[WAVES][CH2];          // loss wave: c_k of the chunk's rows (C/D layout reads)
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int w = wv & (WAVES - 1), role = wv / WAVES;
     const int i = lane & 31, h = lane >> 5;
@@ -197,11 +183,12 @@ __global__ __launch_bounds__(128 * WAVES, 1) void k_fwd_wave2(Dev P, const float
         float u = hb ? p0.y : p0.x;
         v4f qu[8];
         v2f rho;
-        // The normalisation is linear, so it is applied AFTER the mat-vec: the wave broadcasts ut = rho_{k-1} y_{k-1}
-        // (un-normalised), y_k = inv_{k-1} (ut + M_k ut) with inv_{k-1} = rsqrt(max(|y_{k-1}|^2, 1e-12)), and the
-        // reduction of |y_{k-1}|^2 rides inside the FMA blocks of step k instead of sitting on the serial chain.
-        float xsq = lane == 0 ? 1.f : 0.f;      // "|y_{-1}|^2" = 1: psi_0 arrives normalised
-        float nvec = 1.f;
+        // The normalisation is linear, so the chain does not apply it at all: it carries the un-normalised product
+        // z_k = zt_k + M_k zt_k, zt_k = rho_{k-1} z_{k-1} (zt_0 = psi_0), and the loss wave turns the rows back into
+        // y_k = c_k z_k (c_k from |z_{k-1}|^2, see there).  What keeps z in fp32 range is one exact power-of-two rescale
+        // 2^-e per chunk, entering the next chunk: e from |z|^2 of step CH2 - 3, whose wave reduction rides inside the FMA
+        // blocks of step CH2 - 2 (the only step with one); 4^-e goes to the loss wave through esc[].
+        float xsq = 0.f, mlate = 1.f;
         float sv = LEGACY ? P.dt * (xa1 - xa0) : (xa1 - xa0) / A;   // model.py:263, 303: s_k = x_k / A, one step per lane (legacy: dt x_k)
         // M_k = Q + s_k R (model.py:308-313 with the two products merged): one packed FMA per complex entry
 #define FORM_M(S_)                                                                                            \
@@ -231,12 +218,10 @@ __global__ __launch_bounds__(128 * WAVES, 1) void k_fwd_wave2(Dev P, const float
                 const int kk_ = (KK);                                                                         \
                 lds_wait_lo<5>(qu);                                                                           \
                 v2f am;                                                                                       \
-                float nprev;                                                                                  \
-                mv1r_lo(MM, qu, am, xsq);                                                                     \
+                mv1_lo(MM, qu, am);                                                                           \
                 lds_wait_hi_t_after<0>(qu, rho, am);                                                          \
-                mv1r_hi(MM, qu, am, xsq, nprev);                          /* nprev = |y_{k-1}|^2 */           \
-                const float inv = __builtin_amdgcn_rsqf(vmax_s(nprev, 1e-12f));  /* model.py:332 */           \
-                const float y = inv * (u + swapadd(am.x, am.y));                                              \
+                mv1_hi(MM, qu, am);                                                                           \
+                const float y = u + swapadd_after_asm(am.x, am.y);        /* z_k */                           \
                 lds_write32(ay, y);                                                                           \
                 ay += RROWB;                                                                                  \
                 const float yo = osig_of(y, hb);                                                              \
@@ -245,8 +230,6 @@ __global__ __launch_bounds__(128 * WAVES, 1) void k_fwd_wave2(Dev P, const float
                 const int kn = kk_ + 1 < CH2 ? kk_ + 1 : 0;               /* chunk end: a dummy, retired below */ \
                 bcast_issue_tab(aUw, aUr, u, aRho + kn * 256, qu, rho);                                       \
                 FORM_M(rdlane(sv, kn))                                    /* in the shadow of the broadcast */ \
-                xsq = y * y;                                                                                  \
-                write_lane(nvec, nprev, (kk_ - 1) & (CH2 - 1));                                               \
             }
             // a full chunk runs unrolled with compile-time step numbers: every LDS offset is an immediate, the lane selects of
             // v_readlane / v_writelane are constants (no M0 save / restore), no loop bookkeeping on the serial chain
@@ -254,25 +237,26 @@ __global__ __launch_bounds__(128 * WAVES, 1) void k_fwd_wave2(Dev P, const float
             {                                                                                                 \
                 lds_wait_lo<5>(qu);                                                                           \
                 v2f am;                                                                                       \
-                float nprev;                                                                                  \
-                mv1r_lo(MM, qu, am, xsq);                                                                     \
-                lds_wait_hi_t_after<0>(qu, rho, am);                                                          \
-                mv1r_hi(MM, qu, am, xsq, nprev);                                                              \
-                const float inv = __builtin_amdgcn_rsqf(vmax_s(nprev, 1e-12f));                               \
-                const float y = inv * (u + swapadd(am.x, am.y));                                              \
+                if constexpr ((KK) == CH2 - 2) {                          /* mlate = |z_{CH2-3}|^2 */         \
+                    mv1r_lo(MM, qu, am, xsq);                                                                 \
+                    lds_wait_hi_t_after<0>(qu, rho, am);                                                      \
+                    mv1r_hi(MM, qu, am, xsq, mlate);                                                          \
+                } else {                                                                                      \
+                    mv1_lo(MM, qu, am);                                                                       \
+                    lds_wait_hi_t_after<0>(qu, rho, am);                                                      \
+                    mv1_hi(MM, qu, am);                                                                       \
+                }                                                                                             \
+                const float y = u + swapadd_after_asm(am.x, am.y);                                            \
                 lds_write32_imm<(KK) * RROWB>(ay, y);                                                         \
                 const float yo = osig_of(y, hb);                                                              \
                 const v2f un = cmul2(mk2(y, yo), rho);                                                        \
                 u = un.x;                                                                                     \
                 bcast_issue_tab_off<(((KK) + 1) & (CH2 - 1)) * 256>(aUw, aUr, u, aRho, qu, rho);              \
                 FORM_M(rdlane(sv, ((KK) + 1) & (CH2 - 1)))                                                    \
-                xsq = y * y;                                                                                  \
-                write_lane_c<((KK) + CH2 - 1) & (CH2 - 1)>(nvec, nprev);                                      \
+                if constexpr ((KK) == CH2 - 3) xsq = y * y;                                                   \
             }
             if (cnt == CH2) {
-                CHAIN_STEPC(0)
-                if (SAVE && c > 0 && lane < CH2) sc[(size_t)((c - 1) >> 1) * 128 + ((c - 1) & 1) * CH2 + lane] = nvec;
-                CHAIN_STEPC(1) CHAIN_STEPC(2) CHAIN_STEPC(3) CHAIN_STEPC(4) CHAIN_STEPC(5) CHAIN_STEPC(6) CHAIN_STEPC(7)
+                CHAIN_STEPC(0) CHAIN_STEPC(1) CHAIN_STEPC(2) CHAIN_STEPC(3) CHAIN_STEPC(4) CHAIN_STEPC(5) CHAIN_STEPC(6) CHAIN_STEPC(7)
                 stage_commit<4>(nxt, lane, sr);                        // (requested eight steps ago)
                 stage_load<4>(rho4, cn * CH2 + 16, N, lane, sr);       // rows 16 .. 31
                 CHAIN_STEPC(8) CHAIN_STEPC(9) CHAIN_STEPC(10) CHAIN_STEPC(11) CHAIN_STEPC(12) CHAIN_STEPC(13) CHAIN_STEPC(14)
@@ -282,15 +266,18 @@ __global__ __launch_bounds__(128 * WAVES, 1) void k_fwd_wave2(Dev P, const float
                 CHAIN_STEPC(24) CHAIN_STEPC(25) CHAIN_STEPC(26) CHAIN_STEPC(27) CHAIN_STEPC(28)
                 CHAIN_STEPC(29) CHAIN_STEPC(30) CHAIN_STEPC(31)
             } else {                                                   // the clip's last, partial chunk (nothing follows it)
-                CHAIN_STEP(0)
-                if (SAVE && c > 0 && lane < CH2) sc[(size_t)((c - 1) >> 1) * 128 + ((c - 1) & 1) * CH2 + lane] = nvec;
-                for (int kk = 1; kk < cnt; ++kk) CHAIN_STEP(kk)
+                for (int kk = 0; kk < cnt; ++kk) CHAIN_STEP(kk)
             }
 #undef CHAIN_STEPC
 #undef CHAIN_STEP
             lds_wait_hi_t<0>(qu, rho);                                 // everything of this chunk has landed
             flag_store(aProd, c + 1, lane);                            // publish (ordered behind the chunk's y rows)
-            if (c + 1 < NC2) {
+            if (c + 1 < NC2) {                                         // (chunk c was full: mlate is this chunk's)
+                // rescale: |z|^2 -> [1, 4) near the chunk end.  e in [-60, 60] keeps 4^-e a normal float (m = 0, inf, NaN: clamped)
+                int e = ((int)((__float_as_uint(mlate) >> 23) & 0xFFu) - 127) >> 1;
+                e = e > 60 ? 60 : e < -60 ? -60 : e;
+                u *= __uint_as_float((unsigned)(127 - e) << 23);
+                if (lane == 0) esc[w][(c + 1) & 3] = __uint_as_float((unsigned)(127 - 2 * e) << 23);   // the loss wave is at chunk >= c - 1
                 aRho = lds_addr(&stR[w][(c + 1) & 1][0]) + i * 8;     // both halves of the next chunk are in place
                 sv = LEGACY ? P.dt * (xa1 - xa0) : (xa1 - xa0) / A;    // the next chunk's s_k
                 FORM_M(rdlane(sv, 0))                                  // the last in-loop FORM_M used the stale lane 0
@@ -298,12 +285,6 @@ __global__ __launch_bounds__(128 * WAVES, 1) void k_fwd_wave2(Dev P, const float
             }
         }
 #undef FORM_M
-        if (SAVE) {                                                    // |y_{N-1}|^2 closes the last row
-            const float nlast = sum64(xsq);
-            const int cl = NC2 - 1;
-            write_lane(nvec, nlast, (N - 1) & (CH2 - 1));
-            if (lane < CH2) sc[(size_t)(cl >> 1) * 128 + (cl & 1) * CH2 + lane] = nvec;
-        }
         return;
     }
 
@@ -398,6 +379,7 @@ __global__ __launch_bounds__(128 * WAVES, 1) void k_fwd_wave2(Dev P, const float
     float2* st = SAVE ? reinterpret_cast<float2*>(P.hst + (size_t)b * N * 128) : nullptr;   // rows of 64 (y[n], (H y)[n]) pairs
     float loss = 0.f;
     float f_below = 2.0f * P.R[0].x, n_below = 1.f;                    // LEGACY: y^dagger H y and |y|^2 of the step below the chunk (psi_0 = e_0)
+    float m_below = 1.f, g_carry = 1.f;                                // |z|^2 of the step below the chunk (|psi_0|^2 = 1), g of the chunk's first step
     for (int c = 0; c < NC2; ++c) {
         const int kbeg = c * CH2;
         const int cnt = (N - kbeg) < CH2 ? (N - kbeg) : CH2;
@@ -407,6 +389,47 @@ __global__ __launch_bounds__(128 * WAVES, 1) void k_fwd_wave2(Dev P, const float
         if (!DIAG_NO_CHAIN)
             while (flag_load(aProd) < c + 1) __builtin_amdgcn_s_sleep(8);     // a chunk takes ~20000 cycles: poll rarely
         const float* rh = ringw + (c & 1) * (CH2 * RLD);               // this chunk's 32 rows (rows >= cnt: stale, ignored below)
+        // The rows are the chain's z_k; today's y_k = c_k z_k.  With m_k = |z_k|^2 and mt_k = |zt_k|^2 = m_{k-1} (times the chunk's 4^-e
+        // on its first row; |rho| = 1 enters neither: model.py takes the norm before the rotation), the reference's
+        // u_k = rho y_{k-1} / sqrt(max(n_{k-1}, 1e-12)) has |u_k|^2 = g_k = n_{k-1} / max(n_{k-1}, 1e-12) (1 but after a clip), so
+        // c_k = sqrt(g_k / mt_k) and n_k = |y_k|^2 = c_k^2 m_k.  Lane (crow, chk) holds half of row crow in the A-operand layout below.
+        float4 F[4][2];
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) {
+            F[ks][0] = *reinterpret_cast<const float4*>(rh + crow * RLD + 16 * ks + 8 * chk);
+            F[ks][1] = *reinterpret_cast<const float4*>(rh + crow * RLD + 16 * ks + 8 * chk + 4);
+        }
+        float ck, nk;
+        {
+            v2f s2 = mk2(0.f, 0.f);
+#pragma unroll
+            for (int ks = 0; ks < 4; ++ks)
+#pragma unroll
+                for (int hf = 0; hf < 2; ++hf) {
+                    const v2f a = mk2(F[ks][hf].x, F[ks][hf].y), b2 = mk2(F[ks][hf].z, F[ks][hf].w);
+                    s2 = __builtin_elementwise_fma(a, a, s2);
+                    s2 = __builtin_elementwise_fma(b2, b2, s2);
+                }
+            const float mk = swapadd(s2.x + s2.y, s2.x + s2.y);            // m_k of row crow (both halves)
+            float mt = __shfl_up(mk, 1, 64);
+            if (crow == 0) mt = c ? m_below * esc[w][c & 3] : m_below;
+            m_below = rdlane(mk, CH2 - 1);                                  // (a partial chunk is the clip's last)
+            ck = __builtin_amdgcn_rsqf(mt);                                 // g_k = 1
+            nk = ck * ck * mk;
+            if (g_carry != 1.f || __ballot(crow < cnt && !(nk >= 1e-12f))) {
+                // the 1e-12 floor clipped (model.py:331-334), or a zero state: g_k step by step (rare; uniform branch)
+                float g = g_carry;
+                for (int j = 0; j < cnt; ++j) {
+                    const float mtj = rdlane(mt, j), mj = rdlane(mk, j);
+                    const float cj = mtj > 0.f ? sqrtf(g) * __builtin_amdgcn_rsqf(mtj) : 0.f;
+                    const float nj = cj * cj * mj;
+                    if (crow == j) { ck = cj; nk = nj; }
+                    g = nj >= 1e-12f ? 1.f : nj / 1e-12f;
+                }
+                g_carry = g;
+            }
+        }
+        if (lane < CH2) cst[w][lane] = ck;
         v16f acc0 = {}, acc1 = {};
         float sY = 1.f, unsc = 1.f;
         if constexpr (HF16) {
@@ -422,14 +445,15 @@ __global__ __launch_bounds__(128 * WAVES, 1) void k_fwd_wave2(Dev P, const float
         }
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) {
-            const float4 f0 = *reinterpret_cast<const float4*>(rh + crow * RLD + 16 * ks + 8 * chk);
-            const float4 f1 = *reinterpret_cast<const float4*>(rh + crow * RLD + 16 * ks + 8 * chk + 4);
+            float4 f0 = F[ks][0], f1 = F[ks][1];
             if constexpr (HF16) {
+                // the operand is y_k sY = z_k (c_k sY): c_k enters the split's one multiply (the bound above is one of |y_k|)
+                const float scA = ck * sY;
                 unsigned AH[4], AL[4];
-                split2h_scaled(mk2(f0.x, f0.y), sY, AH[0], AL[0]);
-                split2h_scaled(mk2(f0.z, f0.w), sY, AH[1], AL[1]);
-                split2h_scaled(mk2(f1.x, f1.y), sY, AH[2], AL[2]);
-                split2h_scaled(mk2(f1.z, f1.w), sY, AH[3], AL[3]);
+                split2h_scaled(mk2(f0.x, f0.y), scA, AH[0], AL[0]);
+                split2h_scaled(mk2(f0.z, f0.w), scA, AH[1], AL[1]);
+                split2h_scaled(mk2(f1.x, f1.y), scA, AH[2], AL[2]);
+                split2h_scaled(mk2(f1.z, f1.w), scA, AH[3], AL[3]);
 #define MF3(ACC, T_)                                                                                           \
                 ACC = __builtin_amdgcn_mfma_f32_32x32x16_f16(fragh(AH), fragh(WH[T_][ks]), ACC, 0, 0, 0);      \
                 ACC = __builtin_amdgcn_mfma_f32_32x32x16_f16(fragh(AH), fragh(WL[T_][ks]), ACC, 0, 0, 0);      \
@@ -438,6 +462,7 @@ __global__ __launch_bounds__(128 * WAVES, 1) void k_fwd_wave2(Dev P, const float
                 MF3(acc1, 1)
 #undef MF3
             } else {
+            f0.x *= ck; f0.y *= ck; f0.z *= ck; f0.w *= ck; f1.x *= ck; f1.y *= ck; f1.z *= ck; f1.w *= ck;   // y_k
             unsigned AH[4], AM[4], AL[4];
             split3(f0.x, f0.y, AH[0], AM[0], AL[0]);
             split3(f0.z, f0.w, AH[1], AM[1], AL[1]);
@@ -463,13 +488,19 @@ __global__ __launch_bounds__(128 * WAVES, 1) void k_fwd_wave2(Dev P, const float
                 acc0[r] = a.x; acc0[r + 1] = a.y; acc1[r] = b2.x; acc1[r + 1] = b2.y;
             }
         }
-        // y_k[n] in the C/D layout, products y (H y), stash rows
+        // y_k[n] in the C/D layout (c_k of the register's step from cst: steps 8 G + 4 chk + 0..3 in one read), products y (H y), stash rows
         float yc0[16], yc1[16], pr[16];
+        __builtin_amdgcn_wave_barrier();
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int stp = (r & 3) + 8 * (r >> 2) + 4 * chk;
-            yc0[r] = rh[stp * RLD + crow];
-            yc1[r] = rh[stp * RLD + 32 + crow];
+        for (int g4 = 0; g4 < 4; ++g4) {
+            const float4 cg = *reinterpret_cast<const float4*>(&cst[w][8 * g4 + 4 * chk]);
+            const float cr[4] = {cg.x, cg.y, cg.z, cg.w};
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int r = 4 * g4 + q, stp = q + 8 * g4 + 4 * chk;
+                yc0[r] = cr[q] * rh[stp * RLD + crow];
+                yc1[r] = cr[q] * rh[stp * RLD + 32 + crow];
+            }
         }
 #pragma unroll
         for (int r = 0; r < 16; ++r) pr[r] = yc0[r] * acc0[r] + yc1[r] * acc1[r];
@@ -562,7 +593,10 @@ __global__ __launch_bounds__(128 * WAVES, 1) void k_fwd_wave2(Dev P, const float
         } else {
             for (int j = 0; j < cnt; ++j) loss += rdlane(lv, j);
         }
-        if (SAVE && lane < CH2) sc[(size_t)(c >> 1) * 128 + 64 + (c & 1) * CH2 + lane] = evec;
+        if (SAVE && lane < CH2) {
+            sc[(size_t)(c >> 1) * 128 + (c & 1) * CH2 + lane] = nk;                // n_k = |y_k|^2
+            sc[(size_t)(c >> 1) * 128 + 64 + (c & 1) * CH2 + lane] = evec;
+        }
     }
     if (lane == 0) loss_out[b] = loss;
 }
