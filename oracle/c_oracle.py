@@ -18,10 +18,25 @@ _LIB_PATH = os.path.join(_HERE, "_build", "liboracle.so")
 _lib = None
 
 
+_DTYPES = {"f32": np.float32, "f64": np.float64, "f64t32": np.float64}
+
+
+def _stale() -> bool:
+    """liboracle.so is missing, older than its sources, or lacks one of the entry points (a library built
+    before the f64t32 object existed)."""
+    if not os.path.exists(_LIB_PATH):
+        return True
+    mtime = os.path.getmtime(_LIB_PATH)
+    if any(mtime < os.path.getmtime(os.path.join(_HERE, f)) for f in ("cmps_oracle.c", "Makefile")):
+        return True
+    with open(_LIB_PATH, "rb") as fh:
+        blob = fh.read()
+    return any(("cmps_oracle_psi_" + d).encode() not in blob for d in _DTYPES)
+
+
 def build(force: bool = False) -> str:
     """Compile oracle/cmps_oracle.c with gcc (oracle/Makefile)."""
-    if force or not os.path.exists(_LIB_PATH) or (
-            os.path.getmtime(_LIB_PATH) < os.path.getmtime(os.path.join(_HERE, "cmps_oracle.c"))):
+    if force or _stale():
         subprocess.run(["make", "-C", _HERE] + (["-B"] if force else []), check=True,
                        stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
     return _LIB_PATH
@@ -32,8 +47,9 @@ def _load():
     if _lib is None:
         build()
         _lib = ctypes.CDLL(_LIB_PATH)
-        for name, real in (("cmps_oracle_psi_f32", ctypes.c_float), ("cmps_oracle_psi_f64", ctypes.c_double)):
-            fn = getattr(_lib, name)
+        for d, real in _DTYPES.items():
+            real = ctypes.c_float if real is np.float32 else ctypes.c_double
+            fn = getattr(_lib, "cmps_oracle_psi_" + d)
             p = ctypes.c_void_p
             fn.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, p, p, p, p, p, p, real,
                            ctypes.c_double, ctypes.c_double, p, p, p, ctypes.c_int]
@@ -47,10 +63,12 @@ def grad_size(D: int) -> int:
 
 def psi_scan(data, R, freqs, psi0, A, delta_t, sigma, dtype="f32", want_grad=False,
              want_states=False, nthreads=0):
-    """Returns dict(loss_per_clip [B], grad (flat sums, see cmps_oracle.c) or None, states or None)."""
-    real = np.float32 if dtype == "f32" else np.float64
+    """Returns dict(loss_per_clip [B], grad (flat sums, see cmps_oracle.c) or None, states or None).
+    dtype: "f32" (the reference's precision), "f64" (its float64 twin, float64 time grid too) or "f64t32"
+    (float64 arithmetic on the float32 time grid; parameters in double like "f64")."""
+    real = _DTYPES[dtype]
     lib = _load()
-    fn = lib.cmps_oracle_psi_f32 if dtype == "f32" else lib.cmps_oracle_psi_f64
+    fn = getattr(lib, "cmps_oracle_psi_" + dtype)
     data = np.ascontiguousarray(data, dtype=real)
     B, T = data.shape
     R = np.asarray(R)

@@ -26,7 +26,13 @@
  * in the working precision over time, then summed over clips in double in clip order (TF sums the
  * batch inside its fp32 matmul-gradient kernels in an unknowable order).
  *
- * The file is compiled twice: REAL = float (the stand-in for "TF CPU") and REAL = double (twin).
+ * The file is compiled three times: REAL = float (the stand-in for "TF CPU"), REAL = double (twin), and
+ * REAL = double with TREAL = float ("f64t32"): the float64 evaluation of the float32 problem.  TREAL is the type
+ * of the time accumulator and of dt; in f64t32 the float32 constants of the reference (dt = tf.constant(delta_t,
+ * tf.float32), model.py:16, and -delta_t * sigma^2 cast to complex64, model.py:312) enter as their float32
+ * values and t follows the float32 sequence t += dt (model.py:281), while everything else is double.  That is
+ * the time grid the HIP kernels follow (k_ttable), so the distance of any float32 evaluation from f64t32 is
+ * rounding alone.
  */
 #include <math.h>
 #include <stdlib.h>
@@ -38,6 +44,9 @@
 #ifndef REAL
 #define REAL float
 #define SUFFIX f32
+#endif
+#ifndef TREAL
+#define TREAL REAL
 #endif
 
 #define CAT_(a, b) a##_##b
@@ -53,7 +62,7 @@ static inline REAL r_hypot(REAL x, REAL y) { return sizeof(REAL) == 4 ? (REAL)hy
 typedef struct {
     int D;
     const REAL *Rre, *Rim, *f;
-    REAL A, ccre; /* ccre = (REAL)(-delta_t * sigma^2), formed in double then cast (model.py:312) */
+    REAL A, ccre; /* ccre = (REAL)(TREAL)(-delta_t * sigma^2), formed in double then cast (model.py:312) */
     /* scratch, each D long (re, im) */
     REAL *phr, *phi, *Ur, *Ui, *Vr, *Vi, *Wr, *Wi, *dr, *di, *ppr, *ppi, *Upr, *Upi, *RVr, *RVi;
     /* per-step scalars */
@@ -165,8 +174,8 @@ int FN(cmps_oracle_psi)(int B, int T, int D, const REAL* data, const REAL* R_re,
                         int nthreads) {
     const int N = T - 1;
     const int G = 2 * D * D + 3 * D + 2;
-    const REAL dt = (REAL)delta_t;                          /* model.py:16 */
-    const REAL ccre = (REAL)(-delta_t * sigma * sigma);
+    const TREAL dt = (TREAL)delta_t;                        /* model.py:16 */
+    const REAL ccre = (REAL)(TREAL)(-delta_t * sigma * sigma);
     int fail = 0;
     double* gsum = NULL;
     REAL* gclip = NULL;
@@ -197,7 +206,8 @@ int FN(cmps_oracle_psi)(int B, int T, int D, const REAL* data, const REAL* R_re,
         REAL *psr = cur, *psi_ = cur + D;
         for (int d = 0; d < D; ++d) { psr[d] = psi0_re[d]; psi_[d] = psi0_im[d]; }   /* :260 */
         const REAL* xrow = data + (size_t)b * T;
-        REAL loss = 0, t = 0;                                /* :266 */
+        REAL loss = 0;
+        TREAL t = 0;                                         /* :266 */
         for (int k = 0; k < N; ++k) {                        /* :265 foldl */
             if (tape) {
                 memcpy(tape + (size_t)k * 2 * D, psr, D * sizeof(REAL));

@@ -48,11 +48,27 @@ class HParams:
 
 
 def _dt(dtype):
+    """Working dtypes.  "f64t32" is float64 arithmetic on the float32 time grid: the reference's float32
+    constants (dt, model.py:16; -delta_t * sigma^2, model.py:312 and :184) enter as their float32 values and
+    t accumulates in float32 (model.py:281), everything else is float64.  The HIP kernels follow the float32
+    time sequence, so the distance of a float32 evaluation from "f64t32" is rounding alone, while its
+    distance from "f64" also holds the time-grid mismatch, which grows with T."""
     if dtype == "f32":
         return np.float32, np.complex64
-    if dtype == "f64":
+    if dtype in ("f64", "f64t32"):
         return np.float64, np.complex128
     raise ValueError(dtype)
+
+
+def _treal(dtype):
+    """dtype of the time accumulator t and of dt."""
+    return np.float64 if dtype == "f64" else np.float32
+
+
+def _c32(x, dtype):
+    """A Python-float constant that the reference turns into a float32 (or complex64) value: in "f64t32" it
+    enters as that float32 value, otherwise unchanged (the working dtype rounds it)."""
+    return float(np.float32(x)) if dtype == "f64t32" else x
 
 
 # --------------------------------------------------------------------------------------------
@@ -178,7 +194,7 @@ def update_ancilla_psi(psi, signal, t, R, freqs, A, hp: HParams, dtype="f32"):
     Rdag = np.conj(R.T)                                           # :308
     RUpsi = (Upsi @ R.T).astype(cplx)                             # :309  einsum('bc,ac->ab')
     RdagRUpsi = (RUpsi @ Rdag.T).astype(cplx)                     # :310
-    cc = cplx(-hp.delta_t * hp.sigma ** 2)                        # python float64 product, then cast
+    cc = cplx(_c32(-hp.delta_t * hp.sigma ** 2, dtype))          # python float64 product, then cast
     delta_Upsi = cc * RdagRUpsi / cplx(2.0)                       # :312
     delta_Upsi = delta_Upsi + s[:, None] * RUpsi                  # :313
     delta_psi = phases * delta_Upsi                               # :315
@@ -210,12 +226,13 @@ def time_table(delta_t, N, dtype="f32"):
     """t_0 = 0, t_{k+1} = t_k + dt accumulated sequentially in the working dtype
     (model.py:16 ``self.dt = tf.constant(delta_t, tf.float32)``; :266 initial 0.; :281 ``t += self.dt``)."""
     real, _ = _dt(dtype)
+    treal = _treal(dtype)
     t = np.empty(N + 1, dtype=real)
-    acc = real(0)
-    dt = real(delta_t)
+    acc = treal(0)
+    dt = treal(delta_t)
     for k in range(N + 1):
         t[k] = acc
-        acc = real(acc + dt)
+        acc = treal(acc + dt)
     return t
 
 
@@ -231,15 +248,15 @@ def psi_loss_per_clip(hp: HParams, var: Variables, data, dtype="f32", return_sta
     incs = (data[:, 1:] - data[:, :-1]).astype(real)              # model.py:263
     psi = np.tile(psi_0(var, dtype)[None, :], (B, 1)).astype(cplx)  # :260
     loss = np.zeros(B, dtype=real)
-    t = real(0)
-    dt = real(hp.delta_t)
+    t = _treal(dtype)(0)
+    dt = _treal(dtype)(hp.delta_t)
     states = [] if return_states else None
     for k in range(T - 1):                                        # tf.foldl, :265
         x = incs[:, k]
         psi = update_ancilla_psi(psi, x, t, R, freqs, A, hp, dtype)          # :278
         loss = (loss + inc_loss_psi(psi, x, t, R, freqs, A, dtype)).astype(real)  # :279
         psi = normalize_psi(psi, axis=1, dtype=dtype)                          # :280
-        t = real(t + dt)                                                       # :281
+        t = _treal(dtype)(t + dt)                                              # :281
         if return_states:
             states.append(psi)
     if return_states:
@@ -300,13 +317,14 @@ def psi_loss_and_grads(hp: HParams, var: Variables, data, dtype="f32", with_reg=
     R, freqs, c_r, c_h = effective_params(hp, var, dtype)
     A = real(var.A)
     Rdag_T = np.conj(R)                       # adjoint(R) transposed
-    cc = cplx(-hp.delta_t * hp.sigma ** 2)
+    cc = cplx(_c32(-hp.delta_t * hp.sigma ** 2, dtype))
     incs = (data[:, 1:] - data[:, :-1]).astype(real)
     p0 = psi_0(var, dtype)
     psi = np.tile(p0[None, :], (B, 1)).astype(cplx)
     loss = np.zeros(B, dtype=real)
-    t = real(0)
-    dt = real(hp.delta_t)
+    treal = _treal(dtype)
+    t = treal(0)
+    dt = treal(hp.delta_t)
     tape_psi = np.empty((N, B, D), dtype=cplx)
     tape_t = np.empty(N, dtype=real)
     # ---------------- forward (identical op order to psi_loss_per_clip) ----------------
@@ -317,7 +335,7 @@ def psi_loss_and_grads(hp: HParams, var: Variables, data, dtype="f32", with_reg=
         psi = update_ancilla_psi(psi, x, t, R, freqs, A, hp, dtype)
         loss = (loss + inc_loss_psi(psi, x, t, R, freqs, A, dtype)).astype(real)
         psi = normalize_psi(psi, axis=1, dtype=dtype)
-        t = real(t + dt)
+        t = treal(t + dt)
     # ---------------- reverse ----------------
     g = np.zeros((B, D), dtype=cplx)          # cotangent of the carried (normalised) psi
     lbar = real(1) / real(B)                  # d mean / d loss_b
@@ -601,8 +619,9 @@ def _rho_step(rho, x, t, R, freqs, A, hp, dtype):
     Rt = (ph[:, None] * R * np.conj(ph)[None, :]).astype(cplx)                     # :179 einsum('a,ab,b->ab')
     RRd = (np.conj(Rt.T) @ Rt).astype(cplx)                                        # :180
     # :184  `- 0.5 * RR_dag * self.delta_t * self.sigma**2`: three successive complex64 products, left to right
-    damp = (((cplx(-0.5) * RRd).astype(cplx) * cplx(hp.delta_t)).astype(cplx) * cplx(hp.sigma ** 2)).astype(cplx)
-    c = cplx(cplx(-0.5) * cplx(hp.delta_t) * cplx(hp.sigma ** 2))                  # the same factor, for the adjoint
+    dtc, s2c = cplx(_c32(hp.delta_t, dtype)), cplx(_c32(hp.sigma ** 2, dtype))
+    damp = (((cplx(-0.5) * RRd).astype(cplx) * dtc).astype(cplx) * s2c).astype(cplx)
+    c = cplx(cplx(-0.5) * dtc * s2c)                                               # the same factor, for the adjoint
     U = (np.eye(R.shape[0], dtype=cplx)[None] + (damp[None] + s[:, None, None] * Rt[None])).astype(cplx)
     new_rho = np.matmul(np.matmul(U, rho).astype(cplx), np.conj(np.transpose(U, (0, 2, 1)))).astype(cplx)   # :186 U rho U^dagger
     X = (Rt + np.conj(Rt.T)).astype(cplx)                                          # :193-194
@@ -622,13 +641,13 @@ def rho_loss_per_clip(hp: HParams, var: Variables, Wx, Wy, data, dtype="f32", re
     rho = np.tile(rho_0(Wx, Wy, dtype)[None], (B, 1, 1))
     incs = (data[:, 1:] - data[:, :-1]).astype(real)
     loss = np.zeros(B, dtype=real)
-    t = real(0)
+    t = _treal(dtype)(0)
     states = []
     for k in range(T - 1):
         st = _rho_step(rho, incs[:, k], t, R, freqs, A, hp, dtype)
         loss = (loss + (-np.log(real(1) + st["z"]))).astype(real)
         rho = (st["new_rho"] * (real(1) / st["m"]).astype(cplx)[:, None, None]).astype(cplx)    # :201-203
-        t = real(t + real(hp.delta_t))
+        t = _treal(dtype)(t + _treal(dtype)(hp.delta_t))
         if return_states:
             states.append(rho)
     return (loss, np.stack(states, axis=1)) if return_states else loss
@@ -650,14 +669,15 @@ def rho_loss_and_grads(hp: HParams, var: Variables, Wx, Wy, data, dtype="f32"):
     rho = np.tile((r0 / tr0)[None], (B, 1, 1)).astype(cplx)
     incs = (data[:, 1:] - data[:, :-1]).astype(real)
     loss = np.zeros(B, dtype=real)
-    t = real(0)
+    treal = _treal(dtype)
+    t = treal(0)
     tape = []
     for k in range(N):
         tape.append((rho, t))
         st = _rho_step(rho, incs[:, k], t, R, freqs, A, hp, dtype)
         loss = (loss + (-np.log(real(1) + st["z"]))).astype(real)
         rho = (st["new_rho"] * (real(1) / st["m"]).astype(cplx)[:, None, None]).astype(cplx)
-        t = real(t + real(hp.delta_t))
+        t = treal(t + treal(hp.delta_t))
     G = np.zeros((B, D, D), dtype=cplx)          # cotangent of the carried rho
     Rbar = np.zeros((D, D), dtype=cplx)
     fbar = np.zeros(D, dtype=real)

@@ -8,7 +8,7 @@ import pytest
 
 from oracle import cmps_oracle as O
 from oracle import c_oracle as C
-from _util import c_oracle_run, make_audio, rel_inf
+from _util import c_oracle_run, elastic_check, make_audio, rel_inf, strict_grad_sums
 
 pytestmark = pytest.mark.gpu
 
@@ -30,12 +30,14 @@ def _model(T, B, seed, sigma=1e-4, rscale=None, audio_scale=None, **hpkw):
     return m, audio
 
 
-def _check(m, audio, f64_bar=False):
+def _check(m, audio, elastic_bar=False):
+    """HIP against the float32 oracle.  elastic_bar: the gradient bar widens to 3 x the float32 oracle's own rounding distance
+    (from f64t32, float64 on the float32 time grid the kernels follow) where that is above GRAD_RTOL."""
     from audio_mps_amd.scan import unpack_grad
     be = m._get_backend()
     be.kernel_events(True)
     per = m.loss_per_clip()
-    flat, B = m.grad_sums()
+    flat, B = strict_grad_sums(m)
     names = set(be.kernel_times())
     be.kernel_events(False)
     assert "k_fwd_wave2" in names, names
@@ -46,10 +48,15 @@ def _check(m, audio, f64_bar=False):
     err = np.max(np.abs(per - ref["loss_per_clip"]) / np.maximum(np.abs(ref["loss_per_clip"]), 1.0))
     assert err <= LOSS_RTOL, f"loss rel err {err}"
     g, gr = unpack_grad(flat, 32), C.unpack_grad(ref["grad"], 32)
-    g64 = C.unpack_grad(c_oracle_run(m, audio, "f64")["grad"], 32) if f64_bar else None
+    if elastic_bar:
+        gt = C.unpack_grad(c_oracle_run(m, audio, "f64t32")["grad"], 32)
+        g64 = C.unpack_grad(c_oracle_run(m, audio, "f64")["grad"], 32)
     for k in ("Rbar", "fbar", "psi0bar", "Abar"):
-        bar = max(GRAD_RTOL, 3 * rel_inf(gr[k], g64[k])) if f64_bar else GRAD_RTOL
-        assert rel_inf(g[k], gr[k]) <= bar, (k, rel_inf(g[k], gr[k]), bar)
+        e = rel_inf(g[k], gr[k])
+        if elastic_bar:
+            elastic_check(k, e, max(GRAD_RTOL, 3 * rel_inf(gr[k], gt[k])), e, max(GRAD_RTOL, 3 * rel_inf(gr[k], g64[k])))
+        else:
+            assert e <= GRAD_RTOL, (k, e, GRAD_RTOL)
     return per
 
 
@@ -67,7 +74,7 @@ def test_norm_drift_through_rescales(T, B, sigma, rscale, audio_scale, A):
     """Visible dissipator / large R / large increments: |z_k| drifts over many chunks and the chain rescales it by powers of two."""
     kw = {"A": A} if A is not None else {}
     m, audio = _model(T, B, seed=T + B, sigma=sigma, rscale=rscale, audio_scale=audio_scale, **kw)
-    _check(m, audio, f64_bar=True)
+    _check(m, audio, elastic_bar=True)
 
 
 def test_normalisation_floor_clips():

@@ -12,7 +12,8 @@ import pytest
 
 from oracle import cmps_oracle as O
 from oracle import c_oracle as C
-from _util import c_oracle_run, make_audio, oracle_hparams, oracle_variables, rel_inf
+from _util import (c_oracle_run, make_audio, oracle_hparams, oracle_variables, rel_inf, strict_grad_sums,
+                   strict_loss_and_grads)
 
 pytestmark = pytest.mark.gpu
 PAIR = 3
@@ -35,7 +36,7 @@ def test_pair_matches_bf16_oracle_and_float32(D, T, B):
     m, audio = _pair_model(T, B, D=D)
     assert m._get_backend().variant == PAIR
     per = m.loss_per_clip()
-    flat, _ = m.grad_sums()
+    flat, _ = strict_grad_sums(m)
     g = unpack_grad(flat.cpu().numpy(), D)
     em = O.psi_bf16_scan(oracle_hparams(m.hparams), oracle_variables(m), audio, want_grad=True)
     ref = c_oracle_run(m, audio, "f32", want_grad=True)
@@ -62,7 +63,7 @@ def test_pair_qbar_sums_visible_at_large_sigma(D, T, rs, sigma):
     m.variables["Rx"] *= np.float32(rs)
     m.variables["Ry"] *= np.float32(rs)
     per = m.loss_per_clip(audio)
-    g = unpack_grad(m.grad_sums(audio)[0].cpu().numpy(), D)
+    g = unpack_grad(strict_grad_sums(m, audio)[0].cpu().numpy(), D)
     em = O.psi_bf16_scan(oracle_hparams(m.hparams), oracle_variables(m), audio, want_grad=True)
     ref = c_oracle_run(m, audio, "f32", want_grad=True)
     gr = C.unpack_grad(ref["grad"], D)
@@ -93,8 +94,8 @@ def test_pair_agrees_with_block_variant_at_reduced_c5():
         blk.variables[k] = m.variables[k].copy()
     a, b = m.loss_per_clip(), blk.loss_per_clip()
     assert np.max(np.abs(a - b) / np.maximum(np.abs(b), 1.0)) <= 2e-3
-    la, ga = m.loss_and_grads()
-    lb, gb = blk.loss_and_grads()
+    la, ga = strict_loss_and_grads(m)
+    lb, gb = strict_loss_and_grads(blk)
     assert abs(float(la) - float(lb)) <= 2e-3 * max(1.0, abs(float(lb)))
     for k in ga:
         assert rel_inf(ga[k], gb[k]) <= 5e-2, k
@@ -139,7 +140,7 @@ def test_config5_full_length_reduced_batch():
     from audio_mps_amd.scan import unpack_grad
     m, audio = _pair_model(16000, 4, seed=2)
     per = m.loss_per_clip()
-    flat, _ = m.grad_sums()
+    flat, _ = strict_grad_sums(m)
     g = unpack_grad(flat.cpu().numpy(), 128)
     ref = c_oracle_run(m, audio, "f32", want_grad=True, nthreads=4)
     gr = C.unpack_grad(ref["grad"], 128)
@@ -157,14 +158,14 @@ def test_config5_full_size_properties():
     from audio_mps_amd.scan import unpack_grad
     m, audio = _pair_model(16000, 512, seed=4)
     per = m.loss_per_clip()
-    flat, _ = m.grad_sums()
+    flat, _ = strict_grad_sums(m)
     g = unpack_grad(flat.cpu().numpy(), 128)
     assert np.all(np.isfinite(per)) and np.all(np.isfinite(flat.cpu().numpy()))
     assert abs(g["loss_sum"] - float(np.sum(per, dtype=np.float64))) <= 1e-4 * abs(g["loss_sum"])
     perm = np.random.default_rng(0).permutation(512)
     per2 = m.loss_per_clip(audio[perm])
     np.testing.assert_allclose(per2, per[perm], rtol=1e-6, atol=1e-6)
-    flat2, _ = m.grad_sums(audio[perm])
+    flat2, _ = strict_grad_sums(m, audio[perm])
     g2 = unpack_grad(flat2.cpu().numpy(), 128)
     for k in ("Rbar", "fbar", "psi0bar", "Abar"):
         assert rel_inf(g2[k], g[k]) <= 1e-4, k

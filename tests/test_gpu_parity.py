@@ -18,7 +18,7 @@ import torch
 from oracle import cmps_oracle as O
 from oracle import c_oracle as C
 from _util import (c_oracle_run, golden_names, load_golden, make_audio, model_from_golden, oracle_hparams,
-                   oracle_variables, rel_inf)
+                   oracle_variables, rel_inf, strict_grad_sums, strict_loss_and_grads, elastic_check)
 
 pytestmark = pytest.mark.gpu
 
@@ -47,7 +47,7 @@ def _check_against_oracle(m, audio, nthreads=0, loss_rtol=LOSS_RTOL, grad_rtol=G
     from audio_mps_amd.scan import unpack_grad
     D = m.bond_d
     per = m.loss_per_clip()
-    flat, B = m.grad_sums()
+    flat, B = strict_grad_sums(m)
     flat = flat.cpu().numpy()
     ref = c_oracle_run(m, audio, "f32", nthreads=nthreads)
     assert np.all(np.isfinite(per))
@@ -74,7 +74,7 @@ def test_golden(name, variant):
     per = m.loss_per_clip()
     scale = np.maximum(np.abs(g["loss_per_clip_f32"]), 1.0)
     assert np.max(np.abs(per - g["loss_per_clip_f32"]) / scale) <= LOSS_RTOL
-    loss, grads = m.loss_and_grads()
+    loss, grads = strict_loss_and_grads(m)
     assert abs(float(loss) - float(g["loss_f32"])) <= LOSS_RTOL * max(1.0, abs(float(g["loss_f32"])))
     for k in O.Variables.NAMES:
         assert rel_inf(grads[k], g[f"grad_{k}_f32"]) <= GRAD_RTOL, k
@@ -136,8 +136,8 @@ def test_wave16_matches_wave32():
     assert m1._get_backend().variant == WAVE and m2._get_backend().variant == WAVE32
     p1, p2 = m1.loss_per_clip(), m2.loss_per_clip()
     assert np.max(np.abs(p1 - p2) / np.maximum(np.abs(p2), 1.0)) <= LOSS_RTOL
-    f1 = m1.grad_sums()[0].cpu().numpy()
-    f2 = m2.grad_sums()[0].cpu().numpy()
+    f1 = strict_grad_sums(m1)[0].cpu().numpy()
+    f2 = strict_grad_sums(m2)[0].cpu().numpy()
     assert rel_inf(f1[:2 * 16 * 16], f2[:2 * 16 * 16]) <= GRAD_RTOL
     assert rel_inf(f1[2 * 16 * 16:], f2[2 * 16 * 16:]) <= GRAD_RTOL
     s1, s2 = m1.psi_evolve_with_data(), m2.psi_evolve_with_data()
@@ -187,7 +187,7 @@ def test_rank1_modes_order_of_accuracy():
     flats = {}
     for mode in (0, 1, 2, 3):
         be.set_rank1(mode)
-        flats[mode] = m.grad_sums()[0].cpu().numpy().astype(np.float64)[:2 * 32 * 32]
+        flats[mode] = strict_grad_sums(m)[0].cpu().numpy().astype(np.float64)[:2 * 32 * 32]
     e2 = rel_inf(flats[1], flats[0])
     e3 = rel_inf(flats[2], flats[0])
     e16 = rel_inf(flats[3], flats[0])
@@ -202,26 +202,28 @@ def test_rank1_modes_order_of_accuracy():
 def test_qbar_sums_visible_at_large_sigma(D, T):
     """With train.py's sigma = 1e-4 the term Q = -(dt sigma^2 / 2) R^dagger R is below float32 resolution and errors in Qbar = sum ybar u^dagger
     never reach the R gradient.  sigma = 0.36 with a large R makes them visible: every arithmetic of the rank-1 sums must then sit at
-    the float32 oracle's own distance from float64.  (Round 4: hipcc put a v_pk_fma_f32 one instruction in front of the v_mfma_f32_32x32x2_f32
+    the float32 oracle's own rounding distance (from f64t32: float64 on the float32 time grid the kernels follow).  (Round 4: hipcc put a v_pk_fma_f32 one instruction in front of the v_mfma_f32_32x32x2_f32
     that reads its result in the steps updated immediately -- every step of EXACT_F32, the steps above the first aligned octet otherwise --
     and the matrix core used the previous step's u_k: Rbar off by 3e-4 ... 3e-3 here, unnoticed at small sigma.  DESIGN 4.3e.)"""
     from audio_mps_amd import HParams, PsiCMPS
     from audio_mps_amd.scan import HipScan, unpack_grad
     hp = HParams(minibatch_size=5, bond_dim=D, sigma=0.36, A=66.0)
     audio = (make_audio(5, T, hp.delta_t, 3) * np.float32(0.09)).astype(np.float32)
-    g64 = own = None
+    gt = g64 = None
     for variant in (WAVE, 4):                               # 16-row layout below D = 17 / 32-row layout; the 32-row layout for every D
         for mode in (0, 1, 2, 3):
             m = PsiCMPS(hp, data_iterator=audio, seed=7, backend=HipScan(D, variant=variant, rank1=mode))
             m.variables["Rx"] *= np.float32(0.69)
             m.variables["Ry"] *= np.float32(0.69)
-            g = unpack_grad(m.grad_sums()[0].cpu().numpy(), D)
-            if g64 is None:
+            g = unpack_grad(strict_grad_sums(m)[0].cpu().numpy(), D)
+            if gt is None:
+                g32 = C.unpack_grad(c_oracle_run(m, audio, "f32")["grad"], D)
+                gt = C.unpack_grad(c_oracle_run(m, audio, "f64t32")["grad"], D)
                 g64 = C.unpack_grad(c_oracle_run(m, audio, "f64")["grad"], D)
-                own = {k: rel_inf(C.unpack_grad(c_oracle_run(m, audio, "f32")["grad"], D)[k], g64[k]) for k in ("Rbar", "fbar", "psi0bar")}
             for k in ("Rbar", "fbar", "psi0bar"):
-                bar = 3 * own[k] + (3e-5 if mode == 1 else 3e-6)         # BF16X2 carries 16 operand bits
-                assert rel_inf(g[k], g64[k]) <= bar, (variant, mode, k, rel_inf(g[k], g64[k]), own[k])
+                floor = 3e-5 if mode == 1 else 3e-6                      # BF16X2 carries 16 operand bits
+                elastic_check(f"variant {variant} mode {mode} {k}", rel_inf(g[k], gt[k]), 3 * rel_inf(g32[k], gt[k]) + floor,
+                              rel_inf(g[k], g64[k]), 3 * rel_inf(g32[k], g64[k]) + floor)
 
 
 @pytest.mark.parametrize("D", [17, 24, 32])
@@ -245,13 +247,13 @@ def test_rank1_f16x2_scale_jumps(D):
     be.set_rank1(3)
     ref = c_oracle_run(m, audio, "f32")
     assert np.all(np.isfinite(ref["loss_per_clip"]))
-    flat = m.grad_sums(audio)[0].cpu().numpy()
+    flat = strict_grad_sums(m, audio)[0].cpu().numpy()
     assert np.all(np.isfinite(flat))
     g, gr = unpack_grad(flat, D), C.unpack_grad(ref["grad"], D)
     for k in ("Rbar", "fbar", "psi0bar", "Abar"):
         assert rel_inf(g[k], gr[k]) <= GRAD_RTOL, k
     be.set_rank1(2)
-    g3 = unpack_grad(m.grad_sums(audio)[0].cpu().numpy(), D)
+    g3 = unpack_grad(strict_grad_sums(m, audio)[0].cpu().numpy(), D)
     assert rel_inf(g["Rbar"], g3["Rbar"]) <= 2e-5
 
 
@@ -276,12 +278,12 @@ def test_two_wave_reverse_scan_matches_oracle_and_one_wave(D, T, B, sigma, rscal
     assert be._lib.cmps_get_option(be._h, _capi.CMPS_OPT_BWD_WAVES) == 2          # the default since round 5
     _capi.check(be._h, be._lib.cmps_set_option(be._h, _capi.CMPS_OPT_BWD_WAVES, 1))
     be.kernel_events(True)
-    g1 = unpack_grad(m.grad_sums(audio)[0].cpu().numpy(), D)
+    g1 = unpack_grad(strict_grad_sums(m, audio)[0].cpu().numpy(), D)
     assert "k_bwd_wave" in set(be.kernel_times())
     be.kernel_events(False)
     _capi.check(be._h, be._lib.cmps_set_option(be._h, _capi.CMPS_OPT_BWD_WAVES, 2))
     be.kernel_events(True)
-    flat = m.grad_sums(audio)[0].cpu().numpy()
+    flat = strict_grad_sums(m, audio)[0].cpu().numpy()
     names = set(be.kernel_times())
     be.kernel_events(False)
     assert "k_bwd_wave2w" in names, names
@@ -289,11 +291,12 @@ def test_two_wave_reverse_scan_matches_oracle_and_one_wave(D, T, B, sigma, rscal
     g2 = unpack_grad(flat, D)
     ref = c_oracle_run(m, audio, "f32")
     gr = C.unpack_grad(ref["grad"], D)
+    gt = C.unpack_grad(c_oracle_run(m, audio, "f64t32")["grad"], D)
     g64 = C.unpack_grad(c_oracle_run(m, audio, "f64")["grad"], D)
     for k in ("Rbar", "fbar", "psi0bar", "Abar"):
-        own = rel_inf(gr[k], g64[k])
-        assert rel_inf(g2[k], gr[k]) <= max(GRAD_RTOL, 3 * own), (k, rel_inf(g2[k], gr[k]), own)
-        assert rel_inf(g2[k], g1[k]) <= max(GRAD_RTOL, 3 * own), (k, rel_inf(g2[k], g1[k]))
+        bar, bar64 = max(GRAD_RTOL, 3 * rel_inf(gr[k], gt[k])), max(GRAD_RTOL, 3 * rel_inf(gr[k], g64[k]))
+        elastic_check(f"{k} vs oracle", rel_inf(g2[k], gr[k]), bar, rel_inf(g2[k], gr[k]), bar64)
+        elastic_check(f"{k} vs one wave", rel_inf(g2[k], g1[k]), bar, rel_inf(g2[k], g1[k]), bar64)
 
 
 def test_f16_range_tripwire_and_fallback():
@@ -335,6 +338,13 @@ def test_f16_range_tripwire_and_fallback():
     g = unpack_grad(flat.cpu().numpy(), D)
     for k in ("Rbar", "fbar", "psi0bar", "Abar"):
         assert rel_inf(g[k], gr[k]) <= GRAD_RTOL, k
+    # what every other test calls instead of grad_sums / loss_and_grads: the same fallback is a failure there
+    for strict in (lambda: strict_grad_sums(m, audio), lambda: strict_loss_and_grads(m, audio)):
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            with pytest.raises(AssertionError, match="fp16-range fallback"):
+                strict()
+    assert be.f16_fallbacks == 3
     # the device-resident optimiser step skips such a step: variables untouched, total loss NaN as the marker
     tr = Trainer(m, m.hparams, device_step=True)
     st = tr._device_state()
@@ -370,8 +380,8 @@ def test_variants_agree():
     m2, _ = _model(32, 1500, 9, BLOCK, seed=5)
     p1, p2 = m1.loss_per_clip(), m2.loss_per_clip()
     assert np.max(np.abs(p1 - p2) / np.maximum(np.abs(p2), 1.0)) <= LOSS_RTOL
-    f1 = m1.grad_sums()[0].cpu().numpy()
-    f2 = m2.grad_sums()[0].cpu().numpy()
+    f1 = strict_grad_sums(m1)[0].cpu().numpy()
+    f2 = strict_grad_sums(m2)[0].cpu().numpy()
     assert rel_inf(f1[:2 * 32 * 32], f2[:2 * 32 * 32]) <= GRAD_RTOL
 
 
@@ -390,9 +400,9 @@ def test_full_size_properties():
     # (1) determinism / independence of clips: identical clips give bit-identical losses wherever they sit
     np.testing.assert_array_equal(per.reshape(B // 64, 64), np.tile(per[:64], (B // 64, 1)))
     # (2) the reduced loss and gradient SUMS are additive over a split of the batch
-    full = m.grad_sums(audio)[0].cpu().numpy().astype(np.float64)
-    h1 = m.grad_sums(audio[:512])[0].cpu().numpy().astype(np.float64)
-    h2 = m.grad_sums(audio[512:])[0].cpu().numpy().astype(np.float64)
+    full = strict_grad_sums(m, audio)[0].cpu().numpy().astype(np.float64)
+    h1 = strict_grad_sums(m, audio[:512])[0].cpu().numpy().astype(np.float64)
+    h2 = strict_grad_sums(m, audio[512:])[0].cpu().numpy().astype(np.float64)
     assert rel_inf(h1 + h2, full) <= 2e-5
     assert abs(full[-1] - per.astype(np.float64).sum()) <= 1e-5 * abs(full[-1])
     # (3) against the oracle on the 64 distinct clips
@@ -403,7 +413,7 @@ def test_full_size_properties():
 def test_gradient_is_directional_derivative():
     """d/deps loss(R + eps dR) from two forward scans == <grad, dR> from the reverse scan (fp32, loose)."""
     m, audio = _model(16, 400, 8, WAVE, seed=21)
-    loss0, grads = m.loss_and_grads()
+    loss0, grads = strict_loss_and_grads(m)
     rng = np.random.default_rng(0)
     d = {k: rng.standard_normal(np.shape(v)).astype(np.float32) for k, v in m.variables.items()}
     eps = 1e-3
@@ -556,7 +566,7 @@ def test_normalisation_floor_branch(variant):
     assert np.all(np.isfinite(ref["loss_per_clip"])) and np.all(np.isfinite(per))
     assert np.max(np.abs(per - ref["loss_per_clip"])) <= 1e-5 * max(1.0, np.max(np.abs(ref["loss_per_clip"])))
     from audio_mps_amd.scan import unpack_grad
-    flat = m.grad_sums(audio)[0].cpu().numpy()
+    flat = strict_grad_sums(m, audio)[0].cpu().numpy()
     g, gr = unpack_grad(flat, 2), C.unpack_grad(ref["grad"], 2)
     for k in ("Rbar", "fbar", "psi0bar", "Abar"):
         assert rel_inf(g[k], gr[k]) <= 1e-3, k
@@ -569,7 +579,7 @@ def test_more_clips_than_simds():
     ref = c_oracle_run(m, audio, "f32", want_grad=True, nthreads=16)
     assert np.max(np.abs(per - ref["loss_per_clip"]) / np.maximum(np.abs(ref["loss_per_clip"]), 1.0)) <= LOSS_RTOL
     from audio_mps_amd.scan import unpack_grad
-    g, gr = unpack_grad(m.grad_sums()[0].cpu().numpy(), 32), C.unpack_grad(ref["grad"], 32)
+    g, gr = unpack_grad(strict_grad_sums(m)[0].cpu().numpy(), 32), C.unpack_grad(ref["grad"], 32)
     for k in ("Rbar", "fbar", "psi0bar", "Abar"):
         assert rel_inf(g[k], gr[k]) <= GRAD_RTOL, k
 

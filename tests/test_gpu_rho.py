@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 from oracle import cmps_oracle as O
-from _util import make_audio, rel_inf
+from _util import elastic_check, make_audio, rel_inf
 
 pytestmark = pytest.mark.gpu
 
@@ -100,6 +100,18 @@ def test_sampling_two_level_system():
 # ---------------------------------------------------------------------------------------------------
 # parity with the oracle
 # ---------------------------------------------------------------------------------------------------
+def _rho_ref64(ohp, ov, Wx, Wy, audio, dtype):
+    return O.rho_loss_and_grads(ohp, ov.astype(np.float64), Wx.astype(np.float64), Wy.astype(np.float64), audio, dtype)
+
+
+def _check_elastic(grads, ref, reft, ref64, keys, label="", extra=0.0):
+    """|hip - f64t32| <= max(GRAD_RTOL, 3 |oracle_f32 - f64t32|) + extra per tensor (f64t32: float64 on the float32 time grid the
+    kernels follow, so the bar is the float32 oracle's rounding alone); the f64-anchored bar of earlier rounds stays where it is tighter."""
+    for k in keys:
+        elastic_check(f"{label}{k}", rel_inf(grads[k], reft[k]), max(GRAD_RTOL, 3 * rel_inf(ref[k], reft[k])) + extra,
+                      rel_inf(grads[k], ref64[k]), max(GRAD_RTOL, 3 * rel_inf(ref[k], ref64[k])) + extra)
+
+
 @pytest.mark.parametrize("D,T,B,rank,sigma,rscale", [
     (4, 256, 8, None, 1e-4, None),       # BASELINE C1 shape
     (7, 256, 8, None, 1e-4, None),       # the reference tests' shape
@@ -119,17 +131,14 @@ def test_rho_loss_and_gradients_match_oracle(D, T, B, rank, sigma, rscale):
     m, audio = _rho_model(D, T, B, rank=rank, sigma=sigma, seed=D + T, rscale=rscale)
     ohp, ov, Wx, Wy = _oracle_side(m)
     ref = O.rho_loss_and_grads(ohp, ov, Wx, Wy, audio, "f32")
-    ref64 = O.rho_loss_and_grads(ohp, ov.astype(np.float64), Wx.astype(np.float64), Wy.astype(np.float64), audio, "f64")
+    reft, ref64 = (_rho_ref64(ohp, ov, Wx, Wy, audio, d) for d in ("f64t32", "f64"))
     per = m.loss_per_clip()
     err = np.max(np.abs(per - ref["per_clip"]) / np.maximum(np.abs(ref["per_clip"]), 1.0))
     assert err <= LOSS_RTOL, f"loss rel err {err}"
     loss, grads = m.loss_and_grads()
     assert abs(float(loss) - float(ref["loss"])) <= LOSS_RTOL * max(abs(float(ref["loss"])), 1.0)
-    for k in ("A", "Rx", "Ry", "freqs", "Wx", "Wy"):
-        # the float32 oracle's own gradient error (vs float64) bounds what can be asked of the kernels
-        own = rel_inf(ref[k], ref64[k])
-        e = rel_inf(grads[k], ref64[k])
-        assert e <= max(GRAD_RTOL, 3 * own), f"{k}: rel err {e} (oracle f32 vs f64: {own})"
+    # the float32 oracle's own rounding error (vs f64t32) bounds what can be asked of the kernels
+    _check_elastic(grads, ref, reft, ref64, ("A", "Rx", "Ry", "freqs", "Wx", "Wy"))
 
 
 def test_rank_one_rho_reproduces_the_pure_state_path():
@@ -281,12 +290,9 @@ def test_rho_wide_kernels_match_oracle_and_general_kernels(D, rank, T, B, sigma,
     assert {"k_fwd_wide_rho", "k_bwd_wide", "k_grad_gemm", "k_rho_merge_e"} <= names, names       # the wide path really ran
     ohp, ov, Wx, Wy = _oracle_side(m)
     ref = O.rho_loss_and_grads(ohp, ov, Wx, Wy, audio, "f32")
-    ref64 = O.rho_loss_and_grads(ohp, ov.astype(np.float64), Wx.astype(np.float64), Wy.astype(np.float64), audio, "f64")
+    reft, ref64 = (_rho_ref64(ohp, ov, Wx, Wy, audio, d) for d in ("f64t32", "f64"))
     assert abs(float(loss) - float(ref["loss"])) <= LOSS_RTOL * max(abs(float(ref["loss"])), 1.0)
-    for k in ("A", "Rx", "Ry", "freqs", "Wx", "Wy"):
-        own = rel_inf(ref[k], ref64[k])
-        e = rel_inf(grads[k], ref64[k])
-        assert e <= max(GRAD_RTOL, 3 * own), f"{k}: rel err {e} (oracle f32 vs f64: {own})"
+    _check_elastic(grads, ref, reft, ref64, ("A", "Rx", "Ry", "freqs", "Wx", "Wy"))
     blk = RhoCMPS(m.hparams, data_iterator=audio, seed=1, backend=HipScan(D, variant=1))
     for k in m.variables:
         blk.variables[k] = m.variables[k].copy()
@@ -311,7 +317,7 @@ def test_rho_reverse_on_virtual_clips_matches_gemm_reverse_and_oracle(D, rank, T
     be = m._get_backend()
     ohp, ov, Wx, Wy = _oracle_side(m)
     ref = O.rho_loss_and_grads(ohp, ov, Wx, Wy, audio, "f32")
-    ref64 = O.rho_loss_and_grads(ohp, ov.astype(np.float64), Wx.astype(np.float64), Wy.astype(np.float64), audio, "f64")
+    reft, ref64 = (_rho_ref64(ohp, ov, Wx, Wy, audio, d) for d in ("f64t32", "f64"))
     assert be._lib.cmps_get_option(be._h, _capi.CMPS_OPT_RHO_BWD) == _capi.CMPS_RHO_BWD_VIRTUAL
     be.kernel_events(True)
     loss, gv = m.loss_and_grads()
@@ -324,20 +330,18 @@ def test_rho_reverse_on_virtual_clips_matches_gemm_reverse_and_oracle(D, rank, T
     assert "k_bwd_wave" in set(be.kernel_times())
     be.kernel_events(False)
     _capi.check(be._h, be._lib.cmps_set_option(be._h, _capi.CMPS_OPT_BWD_WAVES, 2))
-    for k in ("A", "Rx", "Ry", "freqs", "Wx", "Wy"):
-        assert rel_inf(g1[k], ref64[k]) <= max(GRAD_RTOL, 3 * rel_inf(ref[k], ref64[k])), ("one wave", k)
+    _check_elastic(g1, ref, reft, ref64, ("A", "Rx", "Ry", "freqs", "Wx", "Wy"), "one wave ")
     _capi.check(be._h, be._lib.cmps_set_option(be._h, _capi.CMPS_OPT_RHO_BWD, _capi.CMPS_RHO_BWD_GEMM))
     _, gg_ = m.loss_and_grads()
     _capi.check(be._h, be._lib.cmps_set_option(be._h, _capi.CMPS_OPT_RHO_BWD, _capi.CMPS_RHO_BWD_VIRTUAL))
+    _check_elastic(gv, ref, reft, ref64, ("A", "Rx", "Ry", "freqs", "Wx", "Wy"), "virtual ")
     for k in ("A", "Rx", "Ry", "freqs", "Wx", "Wy"):
-        own = rel_inf(ref[k], ref64[k])
-        assert rel_inf(gv[k], ref64[k]) <= max(GRAD_RTOL, 3 * own), (k, rel_inf(gv[k], ref64[k]), own)
-        assert rel_inf(gv[k], gg_[k]) <= max(GRAD_RTOL, 3 * own), (k, rel_inf(gv[k], gg_[k]))
+        bar, bar64 = max(GRAD_RTOL, 3 * rel_inf(ref[k], reft[k])), max(GRAD_RTOL, 3 * rel_inf(ref[k], ref64[k]))
+        elastic_check(f"virtual vs gemm {k}", rel_inf(gv[k], gg_[k]), bar, rel_inf(gv[k], gg_[k]), bar64)
     for mode in (0, 1, 2):
         be.set_rank1(mode)
         _, gm = m.loss_and_grads()
-        for k in ("Rx", "Ry", "Wx", "Wy"):
-            assert rel_inf(gm[k], ref64[k]) <= max(GRAD_RTOL, 3 * rel_inf(ref[k], ref64[k])) + (3e-5 if mode == 1 else 0.0), (mode, k)
+        _check_elastic(gm, ref, reft, ref64, ("Rx", "Ry", "Wx", "Wy"), f"rank1 mode {mode} ", 3e-5 if mode == 1 else 0.0)
 
 
 def test_rho_wide_rank_scaling_and_batch_order():

@@ -76,6 +76,8 @@ def test_device_step_matches_host_trainer(D, given):
     assert "losses_dev" in out and out["losses_dev"].is_cuda and out["global_step"] == 21
     # checkpoint of the device-resident state -> a host-path trainer continues the same trajectory
     assert float(out["losses_dev"].cpu()[1]) == pytest.approx(t_host.step()["total_loss"], rel=1e-6, abs=1e-6)
+    # the host trainer's gradients (PsiCMPS.grad_sums) were the kernel's throughout, never the BF16X3 / VALU re-run's
+    assert m_host._get_backend().f16_fallbacks == 0
 
 
 def test_empty_shard_contributes_zeros():

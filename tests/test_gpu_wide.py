@@ -6,7 +6,7 @@ so the bars are the ones of the D <= 32 kernels (tests/test_gpu_parity.py):
 import numpy as np
 import pytest
 
-from _util import c_oracle_run, make_audio, rel_inf
+from _util import c_oracle_run, elastic_check, make_audio, rel_inf, strict_grad_sums
 from test_gpu_parity import BLOCK, GRAD_RTOL, LOSS_RTOL, _check_against_oracle, _model
 
 pytestmark = pytest.mark.gpu
@@ -38,14 +38,15 @@ def test_qbar_sums_visible_at_large_sigma(D, T, rs):
     sigma = 1 cases above scale R by 0.1, which hides Qbar).  sigma = 0.36, A = 66, quiet audio and a large R make
     Q = -(delta_t sigma^2 / 2) R^dagger R (/root/reference/model.py:312) carry 14 ... 50 % of the R gradient (oracle, sigma = 0.36 against
     1e-4), so a wrong Qbar = sum ybar u^dagger cannot hide.  Every chain form (VALU, MFMA, MFMA forward only) and every GEMM arithmetic
-    against the float64 oracle, the bar being the float32 oracle's own distance from it (x 3) plus the arithmetic's operand bits."""
+    against f64t32 (float64 on the float32 time grid the kernels follow), the bar being the float32 oracle's own distance from it (x 3)
+    plus the arithmetic's operand bits."""
     from audio_mps_amd import HParams, PsiCMPS
     from audio_mps_amd.scan import HipScan, unpack_grad
     from oracle import c_oracle as C
     B = 3
     hp = HParams(minibatch_size=B, bond_dim=D, sigma=0.36, A=66.0)
     audio = (make_audio(B, T, hp.delta_t, 3) * np.float32(0.09)).astype(np.float32)
-    g64 = own = ref32 = None
+    gt = g64 = ref32 = None
     for chain in (0, 1, 2):
         for mode in (1, 2, 3):
             be = HipScan(D, rank1=mode)
@@ -55,17 +56,18 @@ def test_qbar_sums_visible_at_large_sigma(D, T, rs):
             m.variables["Rx"] *= np.float32(rs)
             m.variables["Ry"] *= np.float32(rs)
             per = m.loss_per_clip()
-            g = unpack_grad(m.grad_sums()[0].cpu().numpy(), D)
-            if g64 is None:
+            g = unpack_grad(strict_grad_sums(m)[0].cpu().numpy(), D)
+            if gt is None:
+                gt = C.unpack_grad(c_oracle_run(m, audio, "f64t32")["grad"], D)
                 g64 = C.unpack_grad(c_oracle_run(m, audio, "f64")["grad"], D)
                 ref32 = c_oracle_run(m, audio, "f32")
                 g32 = C.unpack_grad(ref32["grad"], D)
-                own = {k: rel_inf(g32[k], g64[k]) for k in ("Rbar", "fbar", "psi0bar", "Abar")}
                 assert np.all(np.isfinite(ref32["loss_per_clip"]))
             assert np.max(np.abs(per - ref32["loss_per_clip"]) / np.maximum(np.abs(ref32["loss_per_clip"]), 1.0)) <= LOSS_RTOL
             for k in ("Rbar", "fbar", "psi0bar", "Abar"):
-                bar = 3 * own[k] + (3e-5 if mode == 1 else 1e-5)        # BF16X2 carries 16 operand bits
-                assert rel_inf(g[k], g64[k]) <= bar, (chain, mode, k, rel_inf(g[k], g64[k]), own[k])
+                floor = 3e-5 if mode == 1 else 1e-5                      # BF16X2 carries 16 operand bits
+                elastic_check(f"chain {chain} mode {mode} {k}", rel_inf(g[k], gt[k]), 3 * rel_inf(g32[k], gt[k]) + floor,
+                              rel_inf(g[k], g64[k]), 3 * rel_inf(g32[k], g64[k]) + floor)
 
 
 def test_auto_selects_wide_above_32():
@@ -96,14 +98,14 @@ def test_config5_float32_full_size_properties():
     from audio_mps_amd.scan import unpack_grad
     m, audio = _wide_model(128, 16000, 512, seed=4)
     per = m.loss_per_clip()
-    flat, _ = m.grad_sums()
+    flat, _ = strict_grad_sums(m)
     g = unpack_grad(flat.cpu().numpy(), 128)
     assert np.all(np.isfinite(per)) and np.all(np.isfinite(flat.cpu().numpy()))
     assert abs(g["loss_sum"] - float(np.sum(per, dtype=np.float64))) <= 1e-5 * max(abs(g["loss_sum"]), 1.0)
     perm = np.random.default_rng(0).permutation(512)
     per2 = m.loss_per_clip(audio[perm])
     np.testing.assert_array_equal(per2, per[perm])
-    flat2, _ = m.grad_sums(audio[perm])
+    flat2, _ = strict_grad_sums(m, audio[perm])
     g2 = unpack_grad(flat2.cpu().numpy(), 128)
     for k in ("Rbar", "fbar", "psi0bar", "Abar"):
         assert rel_inf(g2[k], g[k]) <= 1e-5, k
@@ -117,7 +119,7 @@ def test_wide_matches_block(D):
     mb, _ = _wide_model(D, 500, 5, seed=D, variant=BLOCK)
     pw, pb = mw.loss_per_clip(), mb.loss_per_clip()
     assert np.max(np.abs(pw - pb) / np.maximum(np.abs(pb), 1.0)) <= LOSS_RTOL
-    fw, fb = mw.grad_sums()[0].cpu().numpy(), mb.grad_sums()[0].cpu().numpy()
+    fw, fb = strict_grad_sums(mw)[0].cpu().numpy(), strict_grad_sums(mb)[0].cpu().numpy()
     assert rel_inf(fw[:2 * D * D], fb[:2 * D * D]) <= GRAD_RTOL
     assert rel_inf(fw[2 * D * D:2 * D * D + D], fb[2 * D * D:2 * D * D + D]) <= GRAD_RTOL
     sw, sb = mw.psi_evolve_with_data(), mb.psi_evolve_with_data()
@@ -134,7 +136,7 @@ def test_rank1_option_two_pieces():
     m2, _ = _wide_model(64, 400, 4, seed=9)
     m2._get_backend().set_rank1(1)
     _check_against_oracle(m2, audio)
-    f3, f2 = m3.grad_sums()[0].cpu().numpy(), m2.grad_sums()[0].cpu().numpy()
+    f3, f2 = strict_grad_sums(m3)[0].cpu().numpy(), strict_grad_sums(m2)[0].cpu().numpy()
     assert not np.array_equal(f3[:2 * 64 * 64], f2[:2 * 64 * 64])
     assert rel_inf(f2[:2 * 64 * 64], f3[:2 * 64 * 64]) <= GRAD_RTOL
 
@@ -153,15 +155,15 @@ def test_rank1_option_f16x2(D, T, B, sigma):
     _, flat_default = _check_against_oracle(m, audio)
     be.set_rank1(3)
     assert be.rank1 == 3 and be.effective_rank1 == 3
-    np.testing.assert_array_equal(m.grad_sums()[0].cpu().numpy(), flat_default)
+    np.testing.assert_array_equal(strict_grad_sums(m)[0].cpu().numpy(), flat_default)
     be.set_rank1(2)                                               # three bf16 pieces stay selectable
     _check_against_oracle(m, audio)
-    assert not np.array_equal(m.grad_sums()[0].cpu().numpy()[:2 * D * D], flat_default[:2 * D * D])
+    assert not np.array_equal(strict_grad_sums(m)[0].cpu().numpy()[:2 * D * D], flat_default[:2 * D * D])
 
 
 def test_rank1_f16x2_accuracy_class():
-    """The gate VERDICT r3 item 3 put on the fp16 split: on the gradient GEMM's sums its distance to the float64 restatement is at
-    most 4 x BF16X3's, and it sits at least 8 x closer to BF16X3 than BF16X2 does (all three share every other instruction, so the
+    """The gate VERDICT r3 item 3 put on the fp16 split: on the gradient GEMM's sums its distance to the float64 restatement of the
+    float32 time grid (f64t32, so that no mode's distance is padded by the f64 twin's different time grid) is at most 4 x BF16X3's, and it sits at least 8 x closer to BF16X3 than BF16X2 does (all three share every other instruction, so the
     differences isolate the product arithmetic).  Short clips: with few accumulations per sum the product arithmetic is what shows
     (at T >= 2000 float32 accumulation noise of ~1e-5, common to all modes, covers it: scripts/rank1_accuracy_wide.py).  Small and
     large amplitudes exercise the power-of-two operand scales."""
@@ -171,16 +173,18 @@ def test_rank1_f16x2_accuracy_class():
     for D, T, B, amp in ((128, 33, 2, 1.0), (128, 9, 3, 1e-3), (64, 33, 2, 4.0), (96, 129, 4, 1.0), (128, 33, 2, 1e-6)):
         m, audio = _wide_model(D, T, B, seed=T + B)
         audio = (audio * np.float32(amp)).astype(np.float32)
-        ref = C.unpack_grad(c_oracle_run(m, audio, "f64", nthreads=8)["grad"], D)["Rbar"]
+        ref = C.unpack_grad(c_oracle_run(m, audio, "f64t32", nthreads=8)["grad"], D)["Rbar"]
+        ref64 = C.unpack_grad(c_oracle_run(m, audio, "f64", nthreads=8)["grad"], D)["Rbar"]
         out = {}
         for mode in (1, 2, 3):
             m._get_backend().set_rank1(mode)
-            out[mode] = unpack_grad(m.grad_sums(audio)[0].cpu().numpy(), D)["Rbar"].astype(np.complex128)
+            out[mode] = unpack_grad(strict_grad_sums(m, audio)[0].cpu().numpy(), D)["Rbar"].astype(np.complex128)
         assert all(np.all(np.isfinite(v)) for v in out.values()) and np.all(np.isfinite(ref))
         e = {mode: rel_inf(out[mode], ref) for mode in out}
+        e64 = {mode: rel_inf(out[mode], ref64) for mode in out}
         d2, d3 = rel_inf(out[1], out[2]), rel_inf(out[3], out[2])
-        print(f"D {D} T {T} amp {amp}: vs float64  bf16x2 {e[1]:.2e}  bf16x3 {e[2]:.2e}  f16x2 {e[3]:.2e};  to bf16x3: bf16x2 {d2:.2e}  f16x2 {d3:.2e}")
-        assert e[3] <= 4 * e[2], (D, T, amp, e)
+        print(f"D {D} T {T} amp {amp}: vs f64t32  bf16x2 {e[1]:.2e}  bf16x3 {e[2]:.2e}  f16x2 {e[3]:.2e};  to bf16x3: bf16x2 {d2:.2e}  f16x2 {d3:.2e}")
+        elastic_check(f"D {D} T {T} amp {amp} f16x2 vs 4 x bf16x3", e[3], 4 * e[2], e64[3], 4 * e64[2])
         assert 8 * d3 <= d2, (D, T, amp, d2, d3)
 
 
@@ -259,7 +263,7 @@ def test_mfma_chain_long_clip_and_states():
     m2, audio2 = _mfma_chain_model(96, 400, 3, seed=8)
     mv, _ = _wide_model(96, 400, 3, seed=8)
     mv._get_backend().set_wide_chain(0)
-    m2.grad_sums(); mv.grad_sums()
+    strict_grad_sums(m2); strict_grad_sums(mv)
     s2, sv = m2.psi_evolve_with_data(), mv.psi_evolve_with_data()
     assert s2.shape == sv.shape and np.max(np.abs(s2 - sv)) < 1e-5
     pm, pv = m2.loss_per_clip(), mv.loss_per_clip()           # (the forward-only path is the VALU kernel in both)
@@ -289,7 +293,7 @@ def test_mfma_chain_vector_scale_jumps():
     audio[3, 250:] *= np.float32(100.0)
     ref = c_oracle_run(m, audio, "f32")
     assert np.all(np.isfinite(ref["loss_per_clip"]))
-    flat = m.grad_sums(audio)[0].cpu().numpy()
+    flat = strict_grad_sums(m, audio)[0].cpu().numpy()
     assert np.all(np.isfinite(flat))
     g, gr = unpack_grad(flat, 128), C.unpack_grad(ref["grad"], 128)
     assert abs(g["loss_sum"] - gr["loss_sum"]) <= LOSS_RTOL * max(abs(gr["loss_sum"]), 4.0)
@@ -307,7 +311,7 @@ def test_mfma_chain_operand_scales():
             continue
         from audio_mps_amd.scan import unpack_grad
         from oracle import c_oracle as C
-        flat = m.grad_sums(audio)[0].cpu().numpy()
+        flat = strict_grad_sums(m, audio)[0].cpu().numpy()
         g, gr = unpack_grad(flat, 128), C.unpack_grad(ref["grad"], 128)
         assert abs(g["loss_sum"] - gr["loss_sum"]) <= LOSS_RTOL * max(abs(gr["loss_sum"]), 2.0), (rscale, amp)
         for k in ("Rbar", "fbar", "psi0bar", "Abar"):
@@ -316,11 +320,11 @@ def test_mfma_chain_operand_scales():
 
 def test_bit_reproducible():
     m, audio = _wide_model(96, 300, 5, seed=4)
-    a = m.grad_sums()[0].cpu().numpy().copy()
+    a = strict_grad_sums(m)[0].cpu().numpy().copy()
     pa = m.loss_per_clip().copy()
     for _ in range(3):
         m2, _ = _wide_model(96, 300, 5, seed=4)
-        np.testing.assert_array_equal(m2.grad_sums()[0].cpu().numpy(), a)
+        np.testing.assert_array_equal(strict_grad_sums(m2)[0].cpu().numpy(), a)
         np.testing.assert_array_equal(m2.loss_per_clip(), pa)
 
 
@@ -336,5 +340,5 @@ def test_normalisation_floor_branch():
     m.variables["psi_y"] *= np.float32(0)
     per = m.loss_per_clip()
     assert np.all(per == 0.0)
-    flat = m.grad_sums()[0].cpu().numpy()
+    flat = strict_grad_sums(m)[0].cpu().numpy()
     assert np.all(np.isfinite(flat))

@@ -68,7 +68,7 @@ def test_c_oracle_matches_numpy_oracle(D, T, B, sigma):
         var.Rx *= 0.1
         var.Ry *= 0.1
     data = O.damped_sine(B, T, hp.delta_t, seed=D + 1)
-    for dtype, tol in (("f32", 2e-5), ("f64", 1e-9)):
+    for dtype, tol in (("f32", 2e-5), ("f64", 1e-9), ("f64t32", 1e-9)):
         v = var if dtype == "f32" else var.astype(np.float64)
         g = O.psi_loss_and_grads(hp, v, data, dtype)
         R, f, _, _ = O.effective_params(hp, v, dtype)
@@ -80,6 +80,77 @@ def test_c_oracle_matches_numpy_oracle(D, T, B, sigma):
             assert rel_inf(np.asarray(cg[k]) / B, g.eff[k]) < 20 * tol, k
         _, states = O.psi_loss_per_clip(hp, v, data, dtype, return_states=True)
         assert np.abs(c["states"] - states).max() < 50 * tol
+
+
+# ---------------------------------------------------------------------------------------------------
+# the f64t32 anchor: float64 arithmetic on the float32 time grid (the problem the kernels evaluate)
+# ---------------------------------------------------------------------------------------------------
+def _c_grads(hp, var, data, dtype, nthreads=0):
+    v = var if dtype == "f32" else var.astype(np.float64)
+    R, f, _, _ = O.effective_params(hp, v, dtype)
+    out = C.psi_scan(data, R, f, O.psi_0(v, dtype), float(v.A), hp.delta_t, hp.sigma, dtype, want_grad=True,
+                     nthreads=nthreads)
+    return out["loss_per_clip"], C.unpack_grad(out["grad"], hp.bond_dim)
+
+
+def test_liboracle_exports_the_f64t32_anchor():
+    import ctypes
+    lib = ctypes.CDLL(C.build())
+    for d in ("f32", "f64", "f64t32"):
+        assert hasattr(lib, "cmps_oracle_psi_" + d), d
+
+
+def test_f64t32_equals_f64_on_an_exact_float32_grid():
+    """With delta_t = 2^-14 and sigma = 2^-7 every t_k = k 2^-14, dt and -dt sigma^2 = -2^-28 are exact float32
+    values: f64t32 and f64 then evaluate the same numbers, so the time grid and those constants are the only
+    difference between the two modes.  C and numpy, psi and rho."""
+    hp = O.HParams(minibatch_size=3, bond_dim=6, delta_t=2.0 ** -14, sigma=2.0 ** -7)
+    var = O.init_variables(hp, seed=11)
+    data = make_audio(3, 300, hp.delta_t, 4)
+    l64, g64 = _c_grads(hp, var, data, "f64")
+    lt, gt = _c_grads(hp, var, data, "f64t32")
+    assert np.max(np.abs(lt - l64)) <= 1e-12 * max(1.0, np.max(np.abs(l64)))
+    for k in ("Rbar", "fbar", "psi0bar", "Abar"):
+        assert rel_inf(gt[k], g64[k]) <= 1e-12, k
+    v64 = var.astype(np.float64)
+    n64, nt = O.psi_loss_and_grads(hp, v64, data[:, :120], "f64"), O.psi_loss_and_grads(hp, v64, data[:, :120], "f64t32")
+    assert rel_inf(nt.per_clip, n64.per_clip) <= 1e-12
+    for k in ("Rbar", "fbar", "psi0bar"):
+        assert rel_inf(nt.eff[k], n64.eff[k]) <= 1e-12, k
+    hp.initial_rank = 3
+    Wx, Wy = (w.astype(np.float64) for w in O.rho_init_W(hp, seed=2))
+    r64 = O.rho_loss_and_grads(hp, v64, Wx, Wy, data[:, :80], "f64")
+    rt = O.rho_loss_and_grads(hp, v64, Wx, Wy, data[:, :80], "f64t32")
+    assert rel_inf(rt["per_clip"], r64["per_clip"]) <= 1e-12
+    for k in ("Rx", "Ry", "freqs", "Wx", "Wy"):
+        assert rel_inf(rt[k], r64[k]) <= 1e-12, k
+    np.testing.assert_array_equal(O.time_table(hp.delta_t, 299, "f64t32"), O.time_table(hp.delta_t, 299, "f64"))
+
+
+def test_f64t32_follows_the_float32_time_grid():
+    """On the default grid (delta_t = 1/16000 is not a float32 value) f64t32's times are exactly the float32
+    sequence t += dt, and they are not f64's."""
+    hp = O.HParams(minibatch_size=2, bond_dim=4)
+    np.testing.assert_array_equal(O.time_table(hp.delta_t, 3000, "f64t32"),
+                                  O.time_table(hp.delta_t, 3000, "f32").astype(np.float64))
+    assert not np.array_equal(O.time_table(hp.delta_t, 3000, "f64"), O.time_table(hp.delta_t, 3000, "f64t32"))
+
+
+def test_f32_oracle_is_far_closer_to_f64t32_than_to_f64_at_c3_length():
+    """Why the anchor exists.  At D = 32, T = 16000 (the C3 clip length), 8 clips, the float32 restatement's fbar is
+    >= 100x closer to f64t32 than to f64: its distance from f64 is mostly the time-grid mismatch (the float32 `t += dt`
+    drifts from k dt), not rounding, so a bar built from it would be loose by that factor."""
+    hp = O.HParams(minibatch_size=8, bond_dim=32)
+    var = O.init_variables(hp, seed=0)
+    data = make_audio(8, 16000, hp.delta_t, 0)
+    _, g32 = _c_grads(hp, var, data, "f32")
+    _, g64 = _c_grads(hp, var, data, "f64")
+    _, gt = _c_grads(hp, var, data, "f64t32")
+    for k in ("Rbar", "fbar", "psi0bar"):
+        print(f"{k}: f32 vs f64 {rel_inf(g32[k], g64[k]):.2e}, vs f64t32 {rel_inf(g32[k], gt[k]):.2e}")
+    assert rel_inf(g32["fbar"], g64["fbar"]) >= 100 * rel_inf(g32["fbar"], gt["fbar"])
+    # the rounding distance itself is small: what a float32 evaluation of this problem can be asked for
+    assert rel_inf(g32["fbar"], gt["fbar"]) <= 1e-4
 
 
 def test_float64_gradients_match_finite_differences():
