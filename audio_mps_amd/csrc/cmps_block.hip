@@ -9,25 +9,9 @@
 //     n = max(|y|^2, 1e-12);  u_{k+1} = rho_k * y / sqrt(n)              model.py:331-334 (+ phases :305)
 //
 // where u_k = psi_k * conj(phases_k) is the reference's `Upsi` and rho_k = phases_k conj(phases_{k+1}).
-#include "cmps_internal.h"
+#include "cmps_lane_util.h"
 
 namespace cmps {
-
-// Sum over the workgroup, result to every thread; fixed order (deterministic).  Two barriers.
-template <int NT>
-__device__ __forceinline__ float block_sum(float v, float* red) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    constexpr int NW = NT / 64;
-    if constexpr (NW == 1) return v;
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float s = 0.f;
-#pragma unroll
-    for (int w = 0; w < NW; ++w) s += red[w];
-    __syncthreads();
-    return s;
-}
 
 // ------------------------------------------------------------------------------------------------
 // forward
@@ -364,19 +348,19 @@ __global__ void k_states(Dev P, float* __restrict__ psi_out) {
     const bool act = i < D;
     float2 y = make_float2(0.f, 0.f);
     if (act) {
-        if (P.stash_layout == 1) {   // 16-row wave layout: 64 lanes x (y own, H y own); re on lane i, im on lane i + 32
+        if (P.stash_layout == STASH_WAVE16) {   // 16-row wave layout: 64 lanes x (y own, H y own); re on lane i, im on lane i + 32
             const float* r = P.hst + row * 128;
             y = make_float2(r[2 * i], r[2 * (i + 32)]);
-        } else if (P.stash_layout == 3) {   // 32-row wave layout: 64 (y[n], (H y)[n]) pairs, n = 2 i + {re, im}
+        } else if (P.stash_layout == STASH_WAVE32) {   // 32-row wave layout: 64 (y[n], (H y)[n]) pairs, n = 2 i + {re, im}
             const float* r = P.hst + row * 128;
             y = make_float2(r[4 * i], r[4 * i + 2]);
-        } else if (P.stash_layout == 4) {
+        } else if (P.stash_layout == STASH_WIDE) {
             // wide variant (cmps_wide.hip): per pair and step [y | H y][wave][lane], lane = 8 q + i, q = (row half, component, clip)
             const int b = (int)(row / N);
             const float* r = reinterpret_cast<const float*>(P.stash) + (((size_t)(b >> 1) * N + k) * 2) * 4 * DP
                              + (i >> 4) * 64 + (i & 7) + 8 * (((i >> 3) & 1) * 4 + (b & 1));
             y = make_float2(r[0], r[16]);
-        } else if (P.stash_layout == 2) {
+        } else if (P.stash_layout == STASH_PAIR) {
             // pair variant (cmps_pair.hip): per pair and step [y | H y][clip][re | im][DP] float32
             const int b = (int)(row / N);
             const float* r = reinterpret_cast<const float*>(P.stash) + ((((size_t)(b >> 1) * N + k) * 2 + 0) * 2 + (b & 1)) * 2 * DP;

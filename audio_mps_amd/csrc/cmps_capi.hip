@@ -88,6 +88,48 @@ int wave_rank1(int mode) {
     if (mode == CMPS_RANK1_DEFAULT) return CMPS_RANK1_F16X2;
     return mode == CMPS_RANK1_EXACT_F32 || mode == CMPS_RANK1_BF16X2 || mode == CMPS_RANK1_F16X2 ? mode : CMPS_RANK1_BF16X3;
 }
+// the same option where there is only an fp16 and a bf16 form (loss products, samplers, the legacy gradient GEMM): true for two fp16 pieces
+bool rank1_f16(int mode) { return mode == CMPS_RANK1_DEFAULT || mode == CMPS_RANK1_F16X2; }
+// ... and as the wide kernels' gradient GEMM takes it: -2 two fp16 pieces, 2 two bf16 pieces, 3 three bf16 pieces
+int rank1_wide_pieces(int mode) { return rank1_f16(mode) ? -2 : mode == CMPS_RANK1_BF16X2 ? 2 : 3; }
+
+// The sections of a workspace as the kernels see them: everything a Dev takes from the Layout alone.  The callers add what is their
+// own (the scalars; the time table, which the legacy mode does not have).
+Dev bind_workspace(const Layout& L, char* ws) {
+    const bool train = (L.flags & CMPS_WS_TRAIN) != 0, big = train && L.D > 32;
+    Dev P{};
+    P.D = L.D; P.DP = L.DP; P.B = L.B; P.T = L.T; P.N = L.N;
+    P.R = reinterpret_cast<float2*>(ws + L.off_R);
+    P.RT = reinterpret_cast<float2*>(ws + L.off_RT);
+    P.Q = reinterpret_cast<float2*>(ws + L.off_Q);
+    P.QT = reinterpret_cast<float2*>(ws + L.off_QT);
+    P.psi0 = reinterpret_cast<float2*>(ws + L.off_psi0);
+    P.freqs = reinterpret_cast<float*>(ws + L.off_freqs);
+    P.qflag = reinterpret_cast<unsigned*>(ws + L.off_qflag);
+    P.dtk = reinterpret_cast<float*>(ws + L.off_dtk);
+    P.rho = reinterpret_cast<float2*>(ws + L.off_rho);
+    P.stash = train ? reinterpret_cast<float2*>(ws + L.off_stash) : nullptr;
+    P.hst = train ? reinterpret_cast<float*>(ws + L.off_hst) : nullptr;
+    P.scal = train ? reinterpret_cast<float*>(ws + L.off_scal) : nullptr;
+    P.gops = big ? static_cast<void*>(ws + L.off_gops) : nullptr;
+    P.opmax = big ? reinterpret_cast<float*>(ws + L.off_opmax) : nullptr;
+    P.slabs = train ? reinterpret_cast<float*>(ws + L.off_slabs) : nullptr;
+    P.sums = train ? reinterpret_cast<float*>(ws + L.off_sums) : nullptr;
+    P.status = train ? reinterpret_cast<unsigned*>(ws + L.off_status) : nullptr;
+    P.slab_floats = L.slab_floats;
+    return P;
+}
+
+// the end of a reverse pass whose slabs hold one PAIR of clips each (pair and wide kernels): reduce over (B + 1) / 2 slabs, closing terms
+hipError_t reduce_pairs_finalize(Dev P, int abar_fix, const float* loss, float* grad_out, hipStream_t s) {
+    Dev Pp = P;
+    Pp.B = (P.B + 1) / 2;
+    KScope ks("reduce + finalize", s);
+    hipError_t e = launch_reduce_only(Pp, s);
+    P.abar_fix = abar_fix;
+    if (e == hipSuccess) e = launch_finalize_only(P, loss, grad_out, s);
+    return e;
+}
 
 }  // namespace
 
@@ -203,27 +245,8 @@ static int set_params_impl(cmps_handle_t h, const float* R_re_dev, const float* 
     if (((uintptr_t)workspace_dev & 255) != 0)
         return fail(h, CMPS_ERR_WORKSPACE, "cmps_set_params: workspace must be 256-byte aligned");
     char* ws = static_cast<char*>(workspace_dev);
-    Dev P{};
-    P.D = L.D; P.DP = L.DP; P.B = B_max; P.T = T; P.N = L.N;
-    P.R = reinterpret_cast<float2*>(ws + L.off_R);
-    P.RT = reinterpret_cast<float2*>(ws + L.off_RT);
-    P.Q = reinterpret_cast<float2*>(ws + L.off_Q);
-    P.QT = reinterpret_cast<float2*>(ws + L.off_QT);
-    P.psi0 = reinterpret_cast<float2*>(ws + L.off_psi0);
-    P.freqs = reinterpret_cast<float*>(ws + L.off_freqs);
-    P.qflag = reinterpret_cast<unsigned*>(ws + L.off_qflag);
+    Dev P = bind_workspace(L, ws);
     P.ttab = reinterpret_cast<float*>(ws + L.off_ttab);
-    P.dtk = reinterpret_cast<float*>(ws + L.off_dtk);
-    P.rho = reinterpret_cast<float2*>(ws + L.off_rho);
-    P.stash = (flags & CMPS_WS_TRAIN) ? reinterpret_cast<float2*>(ws + L.off_stash) : nullptr;
-    P.hst = (flags & CMPS_WS_TRAIN) ? reinterpret_cast<float*>(ws + L.off_hst) : nullptr;
-    P.scal = (flags & CMPS_WS_TRAIN) ? reinterpret_cast<float*>(ws + L.off_scal) : nullptr;
-    P.gops = ((flags & CMPS_WS_TRAIN) && L.D > 32) ? static_cast<void*>(ws + L.off_gops) : nullptr;
-    P.opmax = ((flags & CMPS_WS_TRAIN) && L.D > 32) ? reinterpret_cast<float*>(ws + L.off_opmax) : nullptr;
-    P.slabs = (flags & CMPS_WS_TRAIN) ? reinterpret_cast<float*>(ws + L.off_slabs) : nullptr;
-    P.sums = (flags & CMPS_WS_TRAIN) ? reinterpret_cast<float*>(ws + L.off_sums) : nullptr;
-    P.status = (flags & CMPS_WS_TRAIN) ? reinterpret_cast<unsigned*>(ws + L.off_status) : nullptr;
-    P.slab_floats = L.slab_floats;
     P.A = A;
     P.Adev = A_dev;
     // model.py:312: `- self.delta_t * self.sigma**2` is a Python float (double), cast to complex64,
@@ -303,32 +326,26 @@ int cmps_psi_loss_fwd(cmps_handle_t h, const float* audio_dev, int B, int T, flo
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int variant = resolve_variant(h);
     KBind kb(h);
+    // the kernel family, named by the stash layout it writes
+    const bool wave = variant == CMPS_VARIANT_WAVE || variant == CMPS_VARIANT_WAVE32;
+    const int family = variant == CMPS_VARIANT_WAVE && h->D <= 16 ? STASH_WAVE16 : wave ? STASH_WAVE32
+                     : variant == CMPS_VARIANT_PAIR ? STASH_PAIR : variant == CMPS_VARIANT_WIDE ? STASH_WIDE : STASH_BLOCK;
+    const bool save = save_for_bwd != 0, f16 = rank1_f16(h->rank1_mode);
     hipError_t e;
-    if (variant == CMPS_VARIANT_WAVE && h->D <= 16) {
-        KScope ks("k_fwd_wave16", s);
-        e = launch_fwd_wave16(P, audio_dev, loss_dev, save_for_bwd != 0, s);
-    } else if (variant == CMPS_VARIANT_WAVE || variant == CMPS_VARIANT_WAVE32) {
-        KScope ks("k_fwd_wave2", s);
-        // the loss product's pieces follow CMPS_OPT_RANK1 like the reverse scan's rank-1 sums: two fp16 pieces for F16X2 / DEFAULT
-        e = launch_fwd_wave2(P, audio_dev, loss_dev, save_for_bwd != 0, wave_rank1(h->rank1_mode) == CMPS_RANK1_F16X2, s);
-    } else if (variant == CMPS_VARIANT_PAIR) {
-        KScope ks("k_fwd_pair", s);
-        e = launch_fwd_pair(P, audio_dev, loss_dev, save_for_bwd != 0, s);
-    } else if (variant == CMPS_VARIANT_WIDE) {
-        // k_fwd_wide, k_hy_wide, k_loss_wide (scopes inside); the loss product's pieces follow CMPS_OPT_RANK1 like the gradient GEMM's
-        e = launch_fwd_wide(P, audio_dev, loss_dev, save_for_bwd != 0,
-                            h->rank1_mode == CMPS_RANK1_DEFAULT || h->rank1_mode == CMPS_RANK1_F16X2, h->wide_chain != CMPS_WIDE_CHAIN_VALU, s);
-    } else {
-        KScope ks("k_fwd_block", s);
-        e = launch_fwd_block(P, audio_dev, loss_dev, save_for_bwd != 0, s);
+    switch (family) {
+    case STASH_WAVE16: { KScope ks("k_fwd_wave16", s); e = launch_fwd_wave16(P, audio_dev, loss_dev, save, s); } break;
+    // the loss product's pieces follow CMPS_OPT_RANK1 like the reverse scan's rank-1 sums: two fp16 pieces for F16X2 / DEFAULT
+    case STASH_WAVE32: { KScope ks("k_fwd_wave2", s); e = launch_fwd_wave2(P, audio_dev, loss_dev, save, f16, s); } break;
+    case STASH_PAIR: { KScope ks("k_fwd_pair", s); e = launch_fwd_pair(P, audio_dev, loss_dev, save, s); } break;
+    // k_fwd_wide, k_hy_wide, k_loss_wide (scopes inside); the loss product's pieces follow CMPS_OPT_RANK1 like the gradient GEMM's
+    case STASH_WIDE: e = launch_fwd_wide(P, audio_dev, loss_dev, save, f16, h->wide_chain != CMPS_WIDE_CHAIN_VALU, s); break;
+    default: { KScope ks("k_fwd_block", s); e = launch_fwd_block(P, audio_dev, loss_dev, save, s); } break;
     }
     if (e != hipSuccess) return fail_hip(h, e, "cmps_psi_loss_fwd");
     h->fwd_saved = save_for_bwd != 0;
     h->saved_B = B; h->saved_T = T; h->saved_audio = audio_dev; h->saved_loss = loss_dev;
     h->saved_variant = variant;
-    h->P.stash_layout = (variant == CMPS_VARIANT_WAVE && h->D <= 16) ? 1
-                      : (variant == CMPS_VARIANT_WAVE || variant == CMPS_VARIANT_WAVE32) ? 3
-                      : (variant == CMPS_VARIANT_PAIR ? 2 : variant == CMPS_VARIANT_WIDE ? 4 : 0);
+    h->P.stash_layout = family;
     return CMPS_OK;
 }
 
@@ -351,11 +368,7 @@ int cmps_psi_loss_bwd(cmps_handle_t h, const float* audio_dev, int B, int T, flo
         { KScope ks("k_bwd_pair", s); e = launch_bwd_pair(P, audio_dev, s); }
         if (e == hipSuccess) { KScope ks("k_grad_gemm<1>", s); e = launch_grad_pair(P, audio_dev, s); }
         if (e != hipSuccess) return fail_hip(h, e, "cmps_psi_loss_bwd (pair scan)");
-        Dev Pp = P;
-        Pp.B = (B + 1) / 2;
-        KScope ks("reduce + finalize", s);
-        e = launch_reduce_only(Pp, s);
-        if (e == hipSuccess) e = launch_finalize_only(P, h->saved_loss, grad_dev, s);
+        e = reduce_pairs_finalize(P, 0, h->saved_loss, grad_dev, s);
         if (e != hipSuccess) return fail_hip(h, e, "cmps_psi_loss_bwd (pair reduce)");
         return CMPS_OK;
     }
@@ -365,17 +378,13 @@ int cmps_psi_loss_bwd(cmps_handle_t h, const float* audio_dev, int B, int T, flo
         if (h->wide_chain == CMPS_WIDE_CHAIN_MFMA) { KScope ks("k_bwd_chain16", s); e = launch_bwd_chain16(P, audio_dev, s); }
         else { KScope ks("k_bwd_wide", s); e = launch_bwd_wide(P, audio_dev, s); }
         if (e == hipSuccess) {
-            const int rm = h->rank1_mode == CMPS_RANK1_DEFAULT ? CMPS_RANK1_F16X2 : h->rank1_mode;
-            KScope ks(rm == CMPS_RANK1_F16X2 ? "k_grad_gemm<f16x2>" : rm == CMPS_RANK1_BF16X2 ? "k_grad_gemm<2>" : "k_grad_gemm<3>", s);
-            e = launch_grad_wide(P, audio_dev, rm == CMPS_RANK1_F16X2 ? -2 : rm == CMPS_RANK1_BF16X2 ? 2 : 3, s);
+            const int pieces = rank1_wide_pieces(h->rank1_mode);
+            KScope ks(pieces == -2 ? "k_grad_gemm<f16x2>" : pieces == 2 ? "k_grad_gemm<2>" : "k_grad_gemm<3>", s);
+            e = launch_grad_wide(P, audio_dev, pieces, s);
         }
         if (e != hipSuccess) return fail_hip(h, e, "cmps_psi_loss_bwd (wide scan)");
-        Dev Pp = P;
-        Pp.B = (B + 1) / 2;
-        KScope ks("reduce + finalize", s);
-        e = launch_reduce_only(Pp, s);
-        P.abar_fix = 1;              // the merged mat-vec: k_finalize removes the Q part of sum Re(u^dagger (Q + s R^dagger) ybar)
-        if (e == hipSuccess) e = launch_finalize_only(P, h->saved_loss, grad_dev, s);
+        // abar_fix: the merged mat-vec, k_finalize removes the Q part of sum Re(u^dagger (Q + s R^dagger) ybar)
+        e = reduce_pairs_finalize(P, 1, h->saved_loss, grad_dev, s);
         if (e != hipSuccess) return fail_hip(h, e, "cmps_psi_loss_bwd (wide reduce)");
         return CMPS_OK;
     }
@@ -383,7 +392,7 @@ int cmps_psi_loss_bwd(cmps_handle_t h, const float* audio_dev, int B, int T, flo
     const bool w16 = h->saved_variant == CMPS_VARIANT_WAVE && h->D <= 16;
     hipError_t e;
     {
-        const bool two = wave && !w16 && h->bwd_waves == 2 && wave_rank1(h->rank1_mode) == CMPS_RANK1_F16X2 && h->f16_shift == 0;
+        const bool two = wave && !w16 && h->bwd_waves == 2 && rank1_f16(h->rank1_mode) && h->f16_shift == 0;
         KScope ks(!wave ? "k_bwd_block" : w16 ? "k_bwd_wave16" : two ? "k_bwd_wave2w" : "k_bwd_wave", s);
         e = !wave ? launch_bwd_block(P, audio_dev, s) : w16 ? launch_bwd_wave16(P, audio_dev, s)
           : two ? launch_bwd_wave2w(P, audio_dev, s) : launch_bwd_wave(P, audio_dev, wave_rank1(h->rank1_mode), s);
@@ -472,29 +481,10 @@ int cmps_legacy_set_params(cmps_handle_t h, const float* R_dev, const float* Q_r
     if (((uintptr_t)workspace_dev & 255) != 0)
         return fail(h, CMPS_ERR_WORKSPACE, "cmps_legacy_set_params: workspace must be 256-byte aligned");
     char* ws = static_cast<char*>(workspace_dev);
-    Dev P{};
-    P.D = L.D; P.DP = L.DP; P.B = B_max; P.T = T; P.N = L.N;
-    P.R = reinterpret_cast<float2*>(ws + L.off_R);
-    P.RT = reinterpret_cast<float2*>(ws + L.off_RT);
-    P.Q = reinterpret_cast<float2*>(ws + L.off_Q);
-    P.QT = reinterpret_cast<float2*>(ws + L.off_QT);
-    P.stash = (flags & CMPS_WS_TRAIN) ? reinterpret_cast<float2*>(ws + L.off_stash) : nullptr;
-    P.hst = (flags & CMPS_WS_TRAIN) ? reinterpret_cast<float*>(ws + L.off_hst) : nullptr;
-    P.scal = (flags & CMPS_WS_TRAIN) ? reinterpret_cast<float*>(ws + L.off_scal) : nullptr;
-    P.slabs = (flags & CMPS_WS_TRAIN) ? reinterpret_cast<float*>(ws + L.off_slabs) : nullptr;
-    P.sums = (flags & CMPS_WS_TRAIN) ? reinterpret_cast<float*>(ws + L.off_sums) : nullptr;
-    P.status = (flags & CMPS_WS_TRAIN) ? reinterpret_cast<unsigned*>(ws + L.off_status) : nullptr;
-    P.gops = ((flags & CMPS_WS_TRAIN) && L.D > 32) ? static_cast<void*>(ws + L.off_gops) : nullptr;      // the wide kernels' ybar rows
-    P.opmax = ((flags & CMPS_WS_TRAIN) && L.D > 32) ? reinterpret_cast<float*>(ws + L.off_opmax) : nullptr;
-    P.freqs = reinterpret_cast<float*>(ws + L.off_freqs);
-    P.qflag = reinterpret_cast<unsigned*>(ws + L.off_qflag);
-    P.slab_floats = L.slab_floats;
+    // psi0 / dtk / rho: the tables of the pure-state wave kernels, which the D <= 32 legacy kernels share (cmps_wave2.hip /
+    // cmps_wave.hip, LEGACY): rotation rho = 1, psi_0 = e_0, no time table
+    Dev P = bind_workspace(L, ws);
     P.dt = (float)delta_t;
-    // the tables of the pure-state wave kernels, which the D <= 32 legacy kernels share (cmps_wave2.hip / cmps_wave.hip, LEGACY):
-    // rotation rho = 1, psi_0 = e_0, no time table
-    P.psi0 = reinterpret_cast<float2*>(ws + L.off_psi0);
-    P.dtk = reinterpret_cast<float*>(ws + L.off_dtk);
-    P.rho = reinterpret_cast<float2*>(ws + L.off_rho);
     P.A = 1.0f;
     hipError_t e = launch_pack_legacy(P, R_dev, Q_re_dev, Q_im_dev, const_cast<float2*>(P.R), const_cast<float2*>(P.RT),
                                       const_cast<float2*>(P.Q), const_cast<float2*>(P.QT), static_cast<hipStream_t>(stream));
@@ -524,7 +514,7 @@ int cmps_legacy_loss_fwd(cmps_handle_t h, const float* audio_dev, int B, int T, 
     // (cmps_wide.hip; round 5); CMPS_VARIANT_BLOCK: the general one-workgroup-per-clip kernels (cmps_legacy.hip), the cross-check
     const bool wave = h->D <= 32 && h->variant_req != CMPS_VARIANT_BLOCK;
     const bool wide = h->D > 32 && h->variant_req != CMPS_VARIANT_BLOCK;
-    const bool f16 = h->rank1_mode == CMPS_RANK1_DEFAULT || h->rank1_mode == CMPS_RANK1_F16X2;
+    const bool f16 = rank1_f16(h->rank1_mode);
     KBind kb(h);
     hipError_t e = wave ? launch_fwd_legacy_wave(P, audio_dev, loss_dev, save_for_bwd != 0, static_cast<hipStream_t>(stream))
                  : wide ? launch_fwd_wide_legacy(P, audio_dev, loss_dev, save_for_bwd != 0, f16, static_cast<hipStream_t>(stream))
@@ -554,7 +544,7 @@ int cmps_legacy_loss_bwd(cmps_handle_t h, const float* audio_dev, int B, int T, 
         { KScope ks("k_bwd_wide<legacy>", s); e = launch_bwd_wide_legacy(P, audio_dev, s); }
         if (e == hipSuccess) {
             KScope ks("k_grad_gemm<legacy>", s);
-            e = launch_grad_wide_legacy(P, audio_dev, h->rank1_mode == CMPS_RANK1_DEFAULT || h->rank1_mode == CMPS_RANK1_F16X2, s);
+            e = launch_grad_wide_legacy(P, audio_dev, rank1_f16(h->rank1_mode), s);
         }
         Pr.B = (B + 1) / 2;
     } else {
@@ -601,7 +591,7 @@ int cmps_rho_set_state(cmps_handle_t h, const float* phi_re_dev, const float* ph
     W.stash = train ? reinterpret_cast<float2*>(ws + RL.off_stash) : nullptr;
     W.scal = train ? reinterpret_cast<float*>(ws + RL.off_scal) : nullptr;
     W.p1 = (train && h->D <= 32) ? reinterpret_cast<float*>(ws + RL.off_p1) : nullptr;
-    W.stash_layout = 0;
+    W.stash_layout = RHO_STASH_BLOCK;
     W.cols = rD > RHO_LDS_COLS_MAX ? reinterpret_cast<float2*>(ws + RL.off_cols) : nullptr;
     W.cols_blocks = B_max;
     W.slabs = train ? reinterpret_cast<float*>(ws + RL.off_slabs) : nullptr;
@@ -654,7 +644,7 @@ int cmps_rho_loss_fwd(cmps_handle_t h, const float* audio_dev, int B, int T, flo
     // 32 < D <= 128, training forward (round 5): the columns as virtual clips of the wide kernels (cmps_wide.hip), when the rho workspace
     // has the sections for it (cmps_rho_workspace_bytes: CMPS_WS_TRAIN and the column vectors fit the LDS); else the general kernels
     const bool wide = h->D > 32 && h->W.vrank > 0 && save_for_bwd != 0 && h->variant_req != CMPS_VARIANT_BLOCK;
-    const bool f16 = h->rank1_mode == CMPS_RANK1_DEFAULT || h->rank1_mode == CMPS_RANK1_F16X2;
+    const bool f16 = rank1_f16(h->rank1_mode);
     hipStream_t s = static_cast<hipStream_t>(stream);
     KBind kb(h);
     hipError_t e = wide ? launch_fwd_rho_wide(P, h->W, audio_dev, loss_dev, f16, s)
@@ -662,7 +652,7 @@ int cmps_rho_loss_fwd(cmps_handle_t h, const float* audio_dev, int B, int T, flo
                  : wave ? launch_fwd_rho_wave(P, h->W, audio_dev, loss_dev, save_for_bwd != 0, s)
                         : launch_fwd_rho(P, h->W, audio_dev, loss_dev, save_for_bwd != 0, s);
     if (e != hipSuccess) return fail_hip(h, e, "cmps_rho_loss_fwd");
-    h->W.stash_layout = wide ? 3 : mfma ? 2 : (wave ? 1 : 0);
+    h->W.stash_layout = wide ? RHO_STASH_WIDE : mfma ? RHO_STASH_MFMA : wave ? RHO_STASH_WAVE : RHO_STASH_BLOCK;
     h->rho_fwd_grad1 = mfma && !h->rho_virtual_bwd;               // the forward's part of Rbar exists (k_bwd_rho_mfma needs it)
     h->rho_saved = h->rho_bwd_ok = save_for_bwd != 0;
     h->rho_saved_B = B; h->rho_saved_steps = T - 1;
@@ -682,25 +672,23 @@ int cmps_rho_loss_bwd(cmps_handle_t h, const float* audio_dev, int B, int T, flo
     P.slabs = h->W.slabs; P.sums = h->W.sums; P.slab_floats = h->W.slab_floats;   // the reduction runs on the rho slabs
     hipStream_t s = static_cast<hipStream_t>(stream);
     KBind kb(h);
-    if (h->W.stash_layout == 3) {                                 // the wide kernels on virtual clips: reverse chain, GEMM, reduction, closing terms
-        const int rm = h->rank1_mode == CMPS_RANK1_DEFAULT ? CMPS_RANK1_F16X2 : h->rank1_mode;
-        const hipError_t ew = launch_bwd_rho_wide(P, h->W, h->saved_loss, grad_dev,
-                                                  rm == CMPS_RANK1_F16X2 ? -2 : rm == CMPS_RANK1_BF16X2 ? 2 : 3, s);
+    if (h->W.stash_layout == RHO_STASH_WIDE) {                                 // the wide kernels on virtual clips: reverse chain, GEMM, reduction, closing terms
+        const hipError_t ew = launch_bwd_rho_wide(P, h->W, h->saved_loss, grad_dev, rank1_wide_pieces(h->rank1_mode), s);
         if (ew != hipSuccess) return fail_hip(h, ew, "cmps_rho_loss_bwd (wide)");
         return CMPS_OK;
     }
-    if (h->W.stash_layout == 2 && !h->rho_virtual_bwd && !h->rho_fwd_grad1)
+    if (h->W.stash_layout == RHO_STASH_MFMA && !h->rho_virtual_bwd && !h->rho_fwd_grad1)
         return fail(h, CMPS_ERR_STATE, "cmps_rho_loss_bwd: CMPS_OPT_RHO_BWD changed between the forward and the reverse call");
-    if (h->W.stash_layout == 2 && h->rho_virtual_bwd) {
+    if (h->W.stash_layout == RHO_STASH_MFMA && h->rho_virtual_bwd) {
         // the row-array forward's rows through the pure-state wave reverse scan, one virtual clip per column (cmps_rho_wave.hip)
         const hipError_t ew = launch_bwd_rho_virtual_wave(P, h->W, audio_dev, h->saved_loss, grad_dev, wave_rank1(h->rank1_mode), h->bwd_waves, s);
         if (ew != hipSuccess) return fail_hip(h, ew, "cmps_rho_loss_bwd (virtual clips)");
         return CMPS_OK;
     }
-    hipError_t e = h->W.stash_layout == 2 ? launch_bwd_rho_mfma(P, h->W, audio_dev, s)
-                 : h->W.stash_layout == 1 ? launch_bwd_rho_wave(P, h->W, audio_dev, s) : launch_bwd_rho(P, h->W, audio_dev, s);
+    hipError_t e = h->W.stash_layout == RHO_STASH_MFMA ? launch_bwd_rho_mfma(P, h->W, audio_dev, s)
+                 : h->W.stash_layout == RHO_STASH_WAVE ? launch_bwd_rho_wave(P, h->W, audio_dev, s) : launch_bwd_rho(P, h->W, audio_dev, s);
     if (e != hipSuccess) return fail_hip(h, e, "cmps_rho_loss_bwd (scan)");
-    P.abar_fix = h->W.stash_layout == 2 ? 1 : 0;   // the MFMA scan sums Re(u^dagger (Q + s R^dagger) ybar); k_finalize removes the Q part
+    P.abar_fix = h->W.stash_layout == RHO_STASH_MFMA ? 1 : 0;   // the MFMA scan sums Re(u^dagger (Q + s R^dagger) ybar); k_finalize removes the Q part
     e = launch_reduce_finalize(P, h->saved_loss, grad_dev, s);
     if (e == hipSuccess) e = launch_finalize_rho(P, h->W, grad_dev, s);
     if (e != hipSuccess) return fail_hip(h, e, "cmps_rho_loss_bwd (reduce)");
@@ -736,11 +724,11 @@ int cmps_rho_sample(cmps_handle_t h, const float* noise_dev, int n, int length, 
     // general workgroup-per-path kernel (cross-check; 93 us per step at rank 32 against 2 us)
     const bool mfma = mfma_sampler;
     hipError_t e = mfma ? launch_sample_rho_mfma(h->P, h->W, noise_dev, n, length, out_dev, save_states != 0,
-                                                 h->rank1_mode == CMPS_RANK1_DEFAULT || h->rank1_mode == CMPS_RANK1_F16X2, static_cast<hipStream_t>(stream))
+                                                 rank1_f16(h->rank1_mode), static_cast<hipStream_t>(stream))
                         : launch_sample_rho(h->P, h->W, noise_dev, n, length, out_dev, save_states != 0, static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return fail_hip(h, e, "cmps_rho_sample");
     h->rho_saved = save_states != 0;
-    h->W.stash_layout = mfma ? 2 : 0;
+    h->W.stash_layout = mfma ? RHO_STASH_MFMA : RHO_STASH_BLOCK;
     h->rho_bwd_ok = false;
     h->rho_saved_B = n; h->rho_saved_steps = length;
     return CMPS_OK;

@@ -33,16 +33,10 @@
 #pragma once
 #include <type_traits>
 
-#include "cmps_internal.h"
+#include "cmps_lane_util.h"
 
 namespace cmps {
 namespace gg {
-
-typedef float v4 __attribute__((ext_vector_type(4)));
-typedef unsigned u4 __attribute__((ext_vector_type(4)));
-typedef short bf8 __attribute__((ext_vector_type(8)));
-typedef float f16 __attribute__((ext_vector_type(16)));
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 
 constexpr int CH = 64;       // steps per chunk of per-step scalars (the forward's scal rows)
 
@@ -53,35 +47,10 @@ __device__ __forceinline__ void static_for(F&& f) {
         static_for<I + 1, E>(f);
     }
 }
-__device__ __forceinline__ unsigned pack_hi16(unsigned lo_word, unsigned hi_word) {   // (lo_word >> 16) | (hi_word & 0xFFFF0000)
-    return __builtin_amdgcn_perm(hi_word, lo_word, 0x07060302u);
-}
-__device__ __forceinline__ unsigned cvt_pk_bf16(float lo, float hi) {                  // round to nearest even, (lo, hi) packed
-    unsigned r;
-    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
-    return r;
-}
-__device__ __forceinline__ unsigned cvt_pk_f16(float lo, float hi) {                   // round to nearest even, (lo, hi) packed
-    unsigned r;
-    asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
-    return r;
-}
 template <bool F16>
-__device__ __forceinline__ f16 mma(bf8 a, bf8 b, f16 c) {
+__device__ __forceinline__ v16f mma(s16x8 a, s16x8 b, v16f c) {
     if constexpr (F16) return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h8, a), __builtin_bit_cast(h8, b), c, 0, 0, 0);
     else return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-// the largest power of two S with bound S < 2^target (bound = m 2^e, 1/2 <= m < 1); exponent clamped so that S and 1 / S are normal
-__device__ __forceinline__ float pow2_scale(float bound, int target) {
-    const int e = (int)((__float_as_uint(bound) >> 23) & 0xFFu) - 126;
-    int se = target - e;
-    se = se > 60 ? 60 : se < -60 ? -60 : se;
-    return __uint_as_float((unsigned)(127 + se) << 23);
-}
-__device__ __forceinline__ bf8 xor_bits(bf8 v, unsigned mask) {
-    u4 t = __builtin_bit_cast(u4, v);
-    t = u4{t.x ^ mask, t.y ^ mask, t.z ^ mask, t.w ^ mask};
-    return __builtin_bit_cast(bf8, t);
 }
 
 // groups of a unit: (LDS sub-array of the A pieces, of the B pieces).  NPC > 1: piece pairs, b = NPC - 1 .. 0, a = NPC - 1 - b .. 0;
@@ -128,9 +97,9 @@ __global__ __launch_bounds__(2 * PD, 1) void k_grad_gemm(Dev P, const float* __r
     constexpr int NM = NG * 6 * PWV;                              // MFMAs per unit
     // the two operand buffers are two distinct arrays (and the unit loop is unrolled by two): no aliasing between the build's
     // stores and the reads of the unit being multiplied
-    __shared__ __attribute__((aligned(16))) u4 opsA[NARR * OPS];
-    __shared__ __attribute__((aligned(16))) u4 opsB[NARR * OPS];
-    __shared__ __attribute__((aligned(16))) v4 tab[2 * CH * 2];   // [2][CH][2]: (s w, inv, w, te w) per (chunk parity, step, clip)
+    __shared__ __attribute__((aligned(16))) v4u opsA[NARR * OPS];
+    __shared__ __attribute__((aligned(16))) v4u opsB[NARR * OPS];
+    __shared__ __attribute__((aligned(16))) v4f tab[2 * CH * 2];   // [2][CH][2]: (s w, inv, w, te w) per (chunk parity, step, clip)
     const int tid = threadIdx.x;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int N = P.N, T = P.T, NC = (N + CH - 1) / CH, NU = (N + GU - 1) / GU;
@@ -175,23 +144,23 @@ __global__ __launch_bounds__(2 * PD, 1) void k_grad_gemm(Dev P, const float* __r
             m_t = fmaxf(m_t, __shfl_xor(m_t, off, 64));
             m_n = fmaxf(m_n, __shfl_xor(m_n, off, 64));
         }
-        if (lane == 0) tab[w] = v4{m_s, m_t, m_n, 0.f};
+        if (lane == 0) tab[w] = v4f{m_s, m_t, m_n, 0.f};
         __syncthreads();
 #pragma unroll
         for (int ww = 0; ww < PWV; ++ww) {
-            const v4 t = tab[ww];
+            const v4f t = tab[ww];
             m_s = fmaxf(m_s, t.x); m_t = fmaxf(m_t, t.y); m_n = fmaxf(m_n, t.z);
         }
         __syncthreads();
         const float ymax = P.opmax[blockIdx.x];
         auto uni = [](float x) { return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(x))); };
-        sR = uni(pow2_scale(fmaxf(m_t, m_s * ymax), 15));
-        sQ = uni(pow2_scale(ymax, 15));
-        sB = uni(pow2_scale(sqrtf(m_n), 13));                     // |u| <= 1 <= max |y|
+        sR = uni(pow2_below(fmaxf(m_t, m_s * ymax), 15));
+        sQ = uni(pow2_below(ymax, 15));
+        sB = uni(pow2_below(sqrtf(m_n), 13));                     // |u| <= 1 <= max |y|
         ps0.x *= sB; ps0.y *= sB;
     }
 
-    f16 Rre[PWV], Rim[PWV], Qre[PWV], Qim[PWV];
+    v16f Rre[PWV], Rim[PWV], Qre[PWV], Qim[PWV];
 #pragma unroll
     for (int cb = 0; cb < PWV; ++cb)
 #pragma unroll
@@ -214,10 +183,10 @@ __global__ __launch_bounds__(2 * PD, 1) void k_grad_gemm(Dev P, const float* __r
             const bool on = in && (cl == 0 || two);
             if constexpr (LEGACY)
                 tab[((cj & 1) * CH + st) * 2 + cl] =
-                    v4{on ? (P.dt * inc) * sR : 0.f, ROWS::rsq(fmaxf(nv, 1e-12f)) * sB, on ? sQ : 0.f, on ? (2.0f * (ev - inc)) * sR : 0.f};
+                    v4f{on ? (P.dt * inc) * sR : 0.f, ROWS::rsq(fmaxf(nv, 1e-12f)) * sB, on ? sQ : 0.f, on ? (2.0f * (ev - inc)) * sR : 0.f};
             else
             tab[((cj & 1) * CH + st) * 2 + cl] =
-                v4{on ? (inc / A) * sR : 0.f, ROWS::rsq(fmaxf(nv, 1e-12f)) * sB, on ? sQ : 0.f, on ? (2.0f * (zbar * inc / A)) * sR : 0.f};
+                v4f{on ? (inc / A) * sR : 0.f, ROWS::rsq(fmaxf(nv, 1e-12f)) * sB, on ? sQ : 0.f, on ? (2.0f * (zbar * inc / A)) * sR : 0.f};
         }
     };
     // raw rows of one unit: y_{kb-1 .. kb+GU-1}, ybar_{kb .. kb+GU-1} (both components), rho_{kb-1 .. kb+GU-2}; fetched one unit
@@ -253,28 +222,28 @@ __global__ __launch_bounds__(2 * PD, 1) void k_grad_gemm(Dev P, const float* __r
     };
 
     // one unit: the MFMAs of unit u from RD (MAC), the operands of unit u + 1 into WR, the raw rows of unit u + 2
-    auto run_unit = [&](auto mac_c, const u4* RD, u4* WR, int u) {
+    auto run_unit = [&](auto mac_c, const v4u* RD, v4u* WR, int u) {
         constexpr bool MAC = decltype(mac_c)::value;
         constexpr int NX = NPC == 1 ? 10 : F16 ? 40 : 60;         // split / pack / store slices per sub-unit
         constexpr int BLK = 16 + NLD + NX;                        // slices per sub-unit: math | loads | split, pack, store
         constexpr int NS = 1 + NSUB * BLK;                        // + the table slice
         const int kb = GU * (u + 1);                              // first step of the unit being built
         const int kl = GU * (u + 2);                              // ... of the unit being fetched
-        v4 sk[GU];
+        v4f sk[GU];
         float invp0 = 1.f;
         float val[2][GU][5];                                      // te y, s ybar, ybar, y, u per (component, step)
         float t1 = 0.f, t2 = 0.f;
         float sv[2][3];                                           // (x, x - hi, x - hi - mid) of the two steps being packed
         unsigned w0[3] = {0u, 0u, 0u};
         unsigned hp0 = 0u, lp0 = 0u, hp1 = 0u;                   // fp16 pieces of the operand being packed: steps (0, 1) and the hi piece of (2, 3)
-        bf8 Areg[6], By[PWV], Bu[PWV];
+        s16x8 Areg[6], By[PWV], Bu[PWV];
         auto a_off = [&](int ap) { return (ap < 2 ? 0 : ap < 4 ? 4 * PD : 2 * PD) + ((ap & 1) ? a_im_off : a_re_off); };
-        auto read_a = [&](int ap, int arr) { Areg[ap] = __builtin_bit_cast(bf8, RD[(size_t)arr * OPS + a_off(ap)]); };
+        auto read_a = [&](int ap, int arr) { Areg[ap] = __builtin_bit_cast(s16x8, RD[(size_t)arr * OPS + a_off(ap)]); };
         auto fix_a = [&](int ap) { Areg[ap] = xor_bits(Areg[ap], imask); };
         auto slice = [&](auto ic) {
             constexpr int I = decltype(ic)::value;
             if constexpr (I == 0) {                               // the unit's table rows (its steps lie in one chunk)
-                const v4* tb = tab + (((kb / CH) & 1) * CH + (kb & (CH - 1))) * 2 + pclip;
+                const v4f* tb = tab + (((kb / CH) & 1) * CH + (kb & (CH - 1))) * 2 + pclip;
 #pragma unroll
                 for (int j = 0; j < GU; ++j) sk[j] = tb[2 * j];
                 const int km = kb > 0 ? kb - 1 : 0;
@@ -313,7 +282,6 @@ __global__ __launch_bounds__(2 * PD, 1) void k_grad_gemm(Dev P, const float* __r
                     if constexpr (F16) {
                         // two slices per pair of steps: hi piece + residuals | lo piece (and, behind the second pair, the two 8-byte stores)
                         constexpr int xf = r - 16 - NLD, cf = xf / 20, of = (xf / 4) % 5, jpf = (xf / 2) % 2, partf = xf % 2;
-                        typedef _Float16 h2 __attribute__((ext_vector_type(2)));
                         if constexpr (partf == 0) {
                             const float v0 = val[cf][4 * s + 2 * jpf][of], v1 = val[cf][4 * s + 2 * jpf + 1][of];
                             const unsigned hp = cvt_pk_f16(v0, v1);
@@ -366,11 +334,11 @@ __global__ __launch_bounds__(2 * PD, 1) void k_grad_gemm(Dev P, const float* __r
             constexpr int a0 = grp_a<NPC>(0), bb0 = grp_b<NPC>(0);
             read_a(0, a0);
 #pragma unroll
-            for (int cb = 0; cb < PWV; ++cb) By[cb] = __builtin_bit_cast(bf8, RD[(size_t)bb0 * OPS + b_off + 32 * cb]);
+            for (int cb = 0; cb < PWV; ++cb) By[cb] = __builtin_bit_cast(s16x8, RD[(size_t)bb0 * OPS + b_off + 32 * cb]);
             read_a(1, a0);
             read_a(2, a0);
 #pragma unroll
-            for (int cb = 0; cb < PWV; ++cb) Bu[cb] = __builtin_bit_cast(bf8, RD[(size_t)bb0 * OPS + b_off + 2 * PD + 32 * cb]);
+            for (int cb = 0; cb < PWV; ++cb) Bu[cb] = __builtin_bit_cast(s16x8, RD[(size_t)bb0 * OPS + b_off + 2 * PD + 32 * cb]);
             read_a(3, a0);
             read_a(4, a0);
             read_a(5, a0);
@@ -401,8 +369,8 @@ __global__ __launch_bounds__(2 * PD, 1) void k_grad_gemm(Dev P, const float* __r
                 }
                 if constexpr (ng < NG && grp_last_of_b<NPC>(g)) {                              // last group of these B pieces: next ones
                     constexpr int nb = grp_b<NPC>(ng < NG ? ng : 0);
-                    if constexpr (ap == 1) By[cb] = __builtin_bit_cast(bf8, RD[(size_t)nb * OPS + b_off + 32 * cb]);
-                    if constexpr (ap == 5) Bu[cb] = __builtin_bit_cast(bf8, RD[(size_t)nb * OPS + b_off + 2 * PD + 32 * cb]);
+                    if constexpr (ap == 1) By[cb] = __builtin_bit_cast(s16x8, RD[(size_t)nb * OPS + b_off + 32 * cb]);
+                    if constexpr (ap == 5) Bu[cb] = __builtin_bit_cast(s16x8, RD[(size_t)nb * OPS + b_off + 2 * PD + 32 * cb]);
                 }
                 __builtin_amdgcn_sched_barrier(0);
 #if !(defined(CMPS_DIAG) && defined(WABL_GRAD_NO_SLICES))          // diagnostic builds only (results are wrong): the MFMA stream alone

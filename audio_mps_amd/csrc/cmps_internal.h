@@ -120,6 +120,15 @@ inline Layout make_layout(int D, int B, int T, int flags) {
     return L;
 }
 
+// Which family's forward wrote the stash (Dev::stash_layout): plain ints, so that the field and the kernels' comparisons stay what they were
+enum StashLayout : int {
+    STASH_BLOCK = 0,     // stash [B][N][DP] float2 (cmps_block.hip)
+    STASH_WAVE16 = 1,    // hst rows in lane order (cmps_wave16.hip)
+    STASH_PAIR = 2,      // pair rows (cmps_pair.hip)
+    STASH_WAVE32 = 3,    // hst rows of (y[n], (H y)[n]) pairs, n = 2 i + {re, im} (cmps_wave2.hip)
+    STASH_WIDE = 4,      // wide rows (cmps_wide.hip): [pair][step][y | H y][wave][lane] float
+};
+
 // Device-side view handed to the kernels by value.
 struct Dev {
     int D, DP, B, T, N;
@@ -135,9 +144,7 @@ struct Dev {
     const float2* rho;   // [N][DP]
     float2* stash;       // [B][N][DP]
     float* hst;          // [B][N][64][2] (wave variant)
-    int stash_layout;    // 0: stash [B][N][DP] float2 (block variant)  1: hst rows in lane order (cmps_wave16.hip)
-                         // 2: pair rows (cmps_pair.hip)  3: hst rows of (y[n], (H y)[n]) pairs, n = 2 i + {re, im} (cmps_wave2.hip)
-                         // 4: wide rows (cmps_wide.hip): [pair][step][y | H y][wave][lane] float
+    int stash_layout;    // a StashLayout: STASH_BLOCK reads `stash`, the STASH_WAVE* layouts `hst`, STASH_PAIR / STASH_WIDE their rows in `stash`
     float* scal;         // [B][NC][2][64]
     void* gops;          // ybar rows for the gradient GEMM (see the layout comment), D > 32 only
     float* opmax;        // [pairs] max |ybar| over the pair's steps and rows (written by k_bwd_wide), D > 32 only
@@ -239,11 +246,17 @@ inline RhoLayout make_rho_layout(int D, int rank, int B, int T, int flags) {
     return L;
 }
 
+// Which forward (or sampler) wrote the rho stash (RhoDev::stash_layout)
+enum RhoStashLayout : int {
+    RHO_STASH_BLOCK = 0,   // [B][N][rank][DP] float2 (cmps_rho.hip)
+    RHO_STASH_WAVE = 1,    // [B][N][rank][64] (y own, H y own) (cmps_rho_wave.hip)
+    RHO_STASH_MFMA = 2,    // [B][N][rank][64] pairs (y[n], (H y)[n]), n = 2 i + {re, im} (cmps_rho_mfma.hip)
+    RHO_STASH_WIDE = 3,    // the wide kernels' rows, one vector per PAIR of columns: vstash [(b vrank + a) / 2][N][y | H y][4 DP] (cmps_wide.hip)
+};
+
 struct RhoDev {
     int rank;
-    int stash_layout;    // 0: [B][N][rank][DP] float2 (cmps_rho.hip)  1: [B][N][rank][64] (y own, H y own) (cmps_rho_wave.hip)
-                         // 2: [B][N][rank][64] pairs (y[n], (H y)[n]), n = 2 i + {re, im} (cmps_rho_mfma.hip)
-                         // 3: the wide kernels' rows, one vector per PAIR of columns: vstash [(b vrank + a) / 2][N][y | H y][4 DP] (cmps_wide.hip)
+    int stash_layout;    // a RhoStashLayout
     float* wslabs; float* wsums;   // D <= 32: the wave reverse scan's slabs, one per (clip, column), and their reduction buffer
     int vrank;           // rank rounded up to even when the wide path's sections exist (else 0)
     float2* vphi;        // [vrank][DP]

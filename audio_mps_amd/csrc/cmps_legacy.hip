@@ -10,24 +10,9 @@
 //   ybar = (g - yhat Re(yhat^dagger g)) / sqrt(n);  ebar = e - x
 //   vbar = dt x ybar + 2 ebar psi;   Qbar += ybar psi^dagger;   Rbar_c += vbar psi^dagger
 //   g    = ybar + Q^dagger ybar + 2 ebar R psi + R^dagger vbar
-#include "cmps_internal.h"
+#include "cmps_lane_util.h"
 
 namespace cmps {
-
-template <int NT>
-__device__ __forceinline__ float lblock_sum(float v, float* red) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    constexpr int NW = NT / 64;
-    if constexpr (NW == 1) return v;
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float s = 0.f;
-#pragma unroll
-    for (int w = 0; w < NW; ++w) s += red[w];
-    __syncthreads();
-    return s;
-}
 
 // body(j, M1[j][t], M2[j][t]) for j = 0 .. D-1 in order, the matrix elements (L2 resident above D = 32) fetched a block of rows ahead
 // of their use (round 4, as rho_jloop in cmps_rho.hip): one L2 round trip per block of 8 rows instead of one per row
@@ -91,11 +76,11 @@ __global__ __launch_bounds__(NT) void k_fwd_legacy(Dev P, const float* __restric
                 q = cfma(m2, pj, q);
             });
         }
-        const float e = 2.0f * lblock_sum<NT>(act ? (psi.x * v.x + psi.y * v.y) : 0.f, red);
+        const float e = 2.0f * block_sum<NT>(act ? (psi.x * v.x + psi.y * v.y) : 0.f, red);
         const float d = x - e;
         loss += d * d / 2.0f;
         const float2 y = make_float2(psi.x + q.x + c * v.x, psi.y + q.y + c * v.y);
-        const float n = lblock_sum<NT>(act ? (y.x * y.x + y.y * y.y) : 0.f, red);
+        const float n = block_sum<NT>(act ? (y.x * y.x + y.y * y.y) : 0.f, red);
         const float inv = 1.0f / sqrtf(fmaxf(n, 1e-12f));
         psi = act ? cscale(inv, y) : make_float2(0.f, 0.f);
         __syncthreads();
@@ -134,12 +119,12 @@ __global__ __launch_bounds__(NT) void k_bwd_legacy(Dev P, const float* __restric
                 q = cfma(m2, pj, q);
             });
         }
-        const float e = 2.0f * lblock_sum<NT>(act ? (p.x * v.x + p.y * v.y) : 0.f, red);
+        const float e = 2.0f * block_sum<NT>(act ? (p.x * v.x + p.y * v.y) : 0.f, red);
         const float2 y = make_float2(p.x + q.x + c * v.x, p.y + q.y + c * v.y);
-        const float n = lblock_sum<NT>(act ? (y.x * y.x + y.y * y.y) : 0.f, red);
+        const float n = block_sum<NT>(act ? (y.x * y.x + y.y * y.y) : 0.f, red);
         const float inv = 1.0f / sqrtf(fmaxf(n, 1e-12f));
         const float2 yhat = cscale(inv, y);
-        const float dot = lblock_sum<NT>(act ? (yhat.x * g.x + yhat.y * g.y) : 0.f, red);
+        const float dot = block_sum<NT>(act ? (yhat.x * g.x + yhat.y * g.y) : 0.f, red);
         float2 ybar;
         if (n > 1e-12f)
             ybar = make_float2((g.x - yhat.x * dot) * inv, (g.y - yhat.y * dot) * inv);

@@ -28,7 +28,6 @@
 //   Per step: 4 D / 16 MFMAs on the chain (R ut, Q ut; 512 matrix-pipe cycles at D = 128), ONE workgroup barrier.
 //   The identity part of y = ut + Q ut + s R ut stays float32; only the small correction goes through bf16.
 // Arithmetic restated (with the same rounding points) by oracle/cmps_oracle.py::psi_bf16_scan.
-#include "cmps_internal.h"
 #include "cmps_grad_gemm.h"
 
 namespace cmps {
@@ -39,23 +38,10 @@ constexpr int PCH = 64;      // steps per chunk of per-step scalars
 // Everything below is templated on the padded bond dimension D (64, 96 or 128): D / 32 waves own 32 rows each, a mat-vec pair is
 // 4 D / 16 MFMA instructions per wave, a broadcast vector is D / 16 16-byte reads per lane.
 
-typedef float f4 __attribute__((ext_vector_type(4)));
-typedef float f2 __attribute__((ext_vector_type(2)));
-typedef unsigned u4 __attribute__((ext_vector_type(4)));
-
 __device__ __forceinline__ unsigned short bf16_rne(float f) {
     unsigned u = __float_as_uint(f);
     u += 0x7FFFu + ((u >> 16) & 1u);
     return (unsigned short)(u >> 16);
-}
-// (lo, hi) -> packed bf16x2, round to nearest even
-__device__ __forceinline__ unsigned pk_bf16(float lo, float hi) {
-    unsigned r;
-    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
-    return r;
-}
-__device__ __forceinline__ float rdl(float v, int lane) {
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
 }
 // workgroup barrier that orders LDS traffic only: __syncthreads() also drains vmcnt, i.e. waits every step for the
 // stash row's store to reach L2 (~1.5 us; measured: it was 80 % of the step)
@@ -66,23 +52,8 @@ __device__ __forceinline__ void lds_barrier() {
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 #endif
 }
-// sum over the two lane halves, both operands (see cmps_wave_util.h::swapadd); the loss waves' row halves
-__device__ __forceinline__ float half_add(float a0, float a1) {
-    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(a0), __float_as_uint(a1), false, false);
-    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
 template <int CTRL>
 __device__ __forceinline__ unsigned dpp_movu(unsigned x) { return (unsigned)__builtin_amdgcn_update_dpp(0, (int)x, CTRL, 0xf, 0xf, true); }
-template <int CTRL>
-__device__ __forceinline__ float dpp_mov(float x) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), CTRL, 0xf, 0xf, true));
-}
-// the value the lane 16 away holds (the Re <-> Im partner of the same row and clip): v_permlane16_swap of x with itself leaves
-// the even rows' values in r[0] and the odd rows' values in r[1], in both rows of a pair
-__device__ __forceinline__ float partner16(float x, bool odd) {
-    const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-    return __uint_as_float(odd ? r[0] : r[1]);
-}
 // sum over the 16 lanes of a row (one clip, one component); every lane receives the total
 __device__ __forceinline__ float row_sum16(float x) {
     x += dpp_mov<0x128>(x);       // row_ror:8
@@ -92,13 +63,13 @@ __device__ __forceinline__ float row_sum16(float x) {
     return x;
 }
 template <int W>
-__device__ __forceinline__ float sum4(const float __attribute__((ext_vector_type(4))) & t) {   // the first W entries
+__device__ __forceinline__ float sum4(const v4f& t) {   // the first W entries
     if constexpr (W == 4) return (t.x + t.y) + (t.z + t.w);
     else if constexpr (W == 3) return (t.x + t.y) + t.z;
     else return t.x + t.y;
 }
 // sum over the two clips (lanes l and l ^ 32), in every lane
-__device__ __forceinline__ float both_clips(float x) { return half_add(x, x); }
+__device__ __forceinline__ float both_clips(float x) { return swap32_add(x, x); }
 
 // LDS image of one broadcast vector for both clips: arrays re | im | -im | dummy, each [2 clips][D] bf16.
 // Rows are padded by 32 B: the sixteen distinct 16-byte pieces a ds_read_b128 of the A operand touches -- four forms (four
@@ -113,7 +84,7 @@ struct PairLds {
 template <int W>
 __device__ __forceinline__ float sum_waves(const float* p) {          // p[0..W-1], 16-byte aligned
     if constexpr (W == 4) {
-        const f4 t = *reinterpret_cast<const f4*>(p);
+        const v4f t = *reinterpret_cast<const v4f*>(p);
         return (t.x + t.y) + (t.z + t.w);
     } else if constexpr (W == 3) {
         const float2 t = *reinterpret_cast<const float2*>(p);
@@ -176,7 +147,7 @@ __device__ __forceinline__ ChainLane<PD / 32> chain_lane(int w, int lane, unsign
 // rows ia, ia + 1 are adjacent: one packed 4-byte store per array
 template <int KH>
 __device__ __forceinline__ void write_vec(unsigned char* base, const ChainLane<KH>& g, float xa, float xb) {
-    const unsigned pk = pk_bf16(xa, xb);
+    const unsigned pk = cvt_pk_bf16(xa, xb);
     *reinterpret_cast<unsigned*>(base + g.wr1) = pk;
     *reinterpret_cast<unsigned*>(base + g.wr2) = pk ^ 0x80008000u;
 }
@@ -184,7 +155,7 @@ __device__ __forceinline__ void write_vec(unsigned char* base, const ChainLane<K
 // B fragments of one matrix for this lane in the wave's K-step order: frag[tile * KS + tau] (M_re half) and frag[tile * KS + KH + tau]
 // (M_im half) = 8 bf16 = columns 32 ((tau + w) % KH) + 8 kg .. + 7 of that half in row ia + tile; elem(tile, half, col) is the float32 entry
 template <int PD, bool AGPR, typename F>
-__device__ __forceinline__ void load_frags(u4 (&frag)[PD / 8], int w, int kg, F&& elem) {
+__device__ __forceinline__ void load_frags(v4u (&frag)[PD / 8], int w, int kg, F&& elem) {
     constexpr int KS = PD / 16, KH = PD / 32;
 #pragma unroll
     for (int tile = 0; tile < 2; ++tile)
@@ -195,7 +166,7 @@ __device__ __forceinline__ void load_frags(u4 (&frag)[PD / 8], int w, int kg, F&
 #pragma unroll
             for (int e = 0; e < 4; ++e)
                 v[e] = (unsigned)bf16_rne(elem(tile, half, col0 + 2 * e)) | ((unsigned)bf16_rne(elem(tile, half, col0 + 2 * e + 1)) << 16);
-            frag[tile * KS + t] = u4{v[0], v[1], v[2], v[3]};
+            frag[tile * KS + t] = v4u{v[0], v[1], v[2], v[3]};
             // into its registers now: the loads of all fragments in flight at once would be the kernel's register peak
             if constexpr (AGPR) asm volatile("" : "+a"(frag[tile * KS + t]));
             else asm volatile("" : "+v"(frag[tile * KS + t]));
@@ -211,18 +182,18 @@ __device__ __forceinline__ void load_frags(u4 (&frag)[PD / 8], int w, int kg, F&
 // operations of a wave complete in order, so whatever else is in flight only makes a counted wait stricter) ----
 // the wave's own K-steps (tau = 0), read back right behind its own stores of image parity `POFF / stride`
 template <int POFF>
-__device__ __forceinline__ void rd_own(unsigned lo0, unsigned hi0, u4& vlo, u4& vhi) {
+__device__ __forceinline__ void rd_own(unsigned lo0, unsigned hi0, v4u& vlo, v4u& vhi) {
     asm volatile("ds_read_b128 %0, %2 offset:%4\n\tds_read_b128 %1, %3 offset:%4"
                  : "=&v"(vlo), "=&v"(vhi) : "v"(lo0), "v"(hi0), "n"(POFF) : "memory");
 }
 // two 16-byte table rows (x0, x1: per-step scalars, rho rows, norm partials) and then the K-steps tau = 1 .. KH - 1 of both halves:
 // 2 + 2 (KH - 1) reads; v[tau - 1] / v[KH - 1 + tau - 1]
 template <int KH, int POFF, bool TABLES_LAST>
-__device__ __forceinline__ void rd_rest(unsigned ax0, unsigned ax1, const unsigned (&lo)[KH], const unsigned (&hi)[KH], f4& x0, f4& x1,
-                                        u4 (&v)[2 * KH - 2]) {
+__device__ __forceinline__ void rd_rest(unsigned ax0, unsigned ax1, const unsigned (&lo)[KH], const unsigned (&hi)[KH], v4f& x0, v4f& x1,
+                                        v4u (&v)[2 * KH - 2]) {
 #if defined(CMPS_DIAG) && defined(PABL_NO_READS)      // diagnostic builds only (scripts/ablate.py): the table rows only
     asm volatile("ds_read_b128 %0, %2\n\tds_read_b128 %1, %3" : "=&v"(x0), "=&v"(x1) : "v"(ax0), "v"(ax1) : "memory");
-    for (int i = 0; i < 2 * KH - 2; ++i) { v[i] = u4{lo[0], hi[0], ax0, ax1}; asm volatile("" : "+v"(v[i])); }
+    for (int i = 0; i < 2 * KH - 2; ++i) { v[i] = v4u{lo[0], hi[0], ax0, ax1}; asm volatile("" : "+v"(v[i])); }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     return;
 #endif
@@ -266,7 +237,7 @@ __device__ __forceinline__ void rd_rest(unsigned ax0, unsigned ax1, const unsign
 }
 // wait until at most W LDS operations are outstanding; the named registers are the reads this makes available
 template <int W>
-__device__ __forceinline__ void lds_wait2(f4& a, f4& b) {
+__device__ __forceinline__ void lds_wait2(v4f& a, v4f& b) {
     asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(a), "+v"(b) : "n"(W) : "memory");
 }
 // One K-step: the A operand v against the fragments of two matrices x two tiles.  The MFMAs are compiler builtins: hipcc then places
@@ -280,22 +251,21 @@ __device__ __forceinline__ void lds_wait2(f4& a, f4& b) {
 // selects the AGPR form, whose accumulators the tail has to read back with v_accvgpr_read, and the fixed 128 / 128 split spilled);
 // the reverse scan (one wave per SIMD, 512 registers) pins them in AGPRs (load_frags<.., true>: gfx950 MFMAs read A / B operands
 // from either file) and reads the eight accumulator values it needs back once per step.
-typedef short bf8 __attribute__((ext_vector_type(8)));
 template <int W, bool FIRST>
-__device__ __forceinline__ void kstep(const u4& fa0, const u4& fa1, const u4& fb0, const u4& fb1, u4& v, f4& a0, f4& a1, f4& b0, f4& b1) {
+__device__ __forceinline__ void kstep(const v4u& fa0, const v4u& fa1, const v4u& fb0, const v4u& fb1, v4u& v, v4f& a0, v4f& a1, v4f& b0, v4f& b1) {
     asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(v) : "n"(W) : "memory");
-    if constexpr (FIRST) { a0 = f4{0.f, 0.f, 0.f, 0.f}; a1 = a0; b0 = a0; b1 = a0; }
-    const bf8 av = __builtin_bit_cast(bf8, v);
+    if constexpr (FIRST) { a0 = v4f{0.f, 0.f, 0.f, 0.f}; a1 = a0; b0 = a0; b1 = a0; }
+    const s16x8 av = __builtin_bit_cast(s16x8, v);
 #if defined(CMPS_DIAG) && defined(PABL_NO_MFMA)       // diagnostic builds only (scripts/ablate.py)
     a0[0] += __uint_as_float(v.x); a1[0] += __uint_as_float(fa1.x); b0[0] += __uint_as_float(fb0.x); b1[0] += __uint_as_float(fb1.x + fa0.x);
 #else
-    a0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, __builtin_bit_cast(bf8, fa0), a0, 0, 0, 0);
-    b0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, __builtin_bit_cast(bf8, fb0), b0, 0, 0, 0);
+    a0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, __builtin_bit_cast(s16x8, fa0), a0, 0, 0, 0);
+    b0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, __builtin_bit_cast(s16x8, fb0), b0, 0, 0, 0);
 #if defined(CMPS_DIAG) && defined(PABL_HALF_MFMA)     // diagnostic builds only: tile 0 alone (what an MFMA costs in place: the difference, / 16)
     a1[0] += __uint_as_float(fa1.x); b1[0] += __uint_as_float(fb1.x);
 #else
-    a1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, __builtin_bit_cast(bf8, fa1), a1, 0, 0, 0);
-    b1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, __builtin_bit_cast(bf8, fb1), b1, 0, 0, 0);
+    a1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, __builtin_bit_cast(s16x8, fa1), a1, 0, 0, 0);
+    b1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, __builtin_bit_cast(s16x8, fb1), b1, 0, 0, 0);
 #endif
 #endif
 }
@@ -323,7 +293,7 @@ __device__ __forceinline__ void mfma_valu_pipeline() {
     }
 }
 template <int PD, int I, int XTRA, typename Piece>
-__device__ __forceinline__ void ksteps_rest(const u4 (&FA)[PD / 8], const u4 (&FB)[PD / 8], u4 (&v)[PD / 16 - 2], f4& a0, f4& a1, f4& b0, f4& b1,
+__device__ __forceinline__ void ksteps_rest(const v4u (&FA)[PD / 8], const v4u (&FB)[PD / 8], v4u (&v)[PD / 16 - 2], v4f& a0, v4f& a1, v4f& b0, v4f& b1,
                                             Piece&& piece) {
     constexpr int KS = PD / 16, KH = PD / 32, NR = KS - 2;     // NR reads of the rest: lo tau = 1 .. KH - 1, then hi tau = 1 .. KH - 1
     if constexpr (I < NR) {
@@ -341,7 +311,7 @@ __device__ __forceinline__ void ksteps_rest(const u4 (&FA)[PD / 8], const u4 (&F
 // read number IDX of a step's LDS read sequence (the order the counted waits of matvec2 assume): the two table rows first or last,
 // the other waves' K ranges (M_re half tau = 1 .. KH - 1, then the M_im half) in between
 template <int KH, int POFF, bool TABLES_LAST, int IDX>
-__device__ __forceinline__ void rd_seq(unsigned ax0, unsigned ax1, const unsigned (&lo)[KH], const unsigned (&hi)[KH], f4& x0, f4& x1, u4 (&v)[2 * KH - 2]) {
+__device__ __forceinline__ void rd_seq(unsigned ax0, unsigned ax1, const unsigned (&lo)[KH], const unsigned (&hi)[KH], v4f& x0, v4f& x1, v4u (&v)[2 * KH - 2]) {
     constexpr int NV = 2 * KH - 2;
     constexpr int vi = TABLES_LAST ? IDX : IDX - 2;             // index into v, or a table row outside [0, NV)
     if constexpr (IDX >= NV + 2) {
@@ -358,33 +328,33 @@ __device__ __forceinline__ void rd_seq(unsigned ax0, unsigned ax1, const unsigne
 // burst in front of the own K-steps the 2 KH reads took ~25 cycles apiece with the matrix pipe idle (measured on k_fwd_chain16,
 // profiles/r4_c5wide_chain16_ablations.log)
 template <bool FIRST, typename Rd>
-__device__ __forceinline__ void kstep_own(const u4& fa0, const u4& fa1, const u4& fb0, const u4& fb1, u4& v, f4& a0, f4& a1, f4& b0, f4& b1, Rd&& rd) {
+__device__ __forceinline__ void kstep_own(const v4u& fa0, const v4u& fa1, const v4u& fb0, const v4u& fb1, v4u& v, v4f& a0, v4f& a1, v4f& b0, v4f& b1, Rd&& rd) {
     // The operand was read in the previous step's tail (rd_own, asm) and has landed by the barrier's lgkmcnt(0) -- but the compiler only
     // sees a register defined by that asm: without this statement (asm volatile statements keep their order, the barrier is one) it is
     // free to issue the MFMAs that read it ABOVE the barrier.  (The first interleaved version had dropped the no-op wait that did this
     // job in kstep<>: intermittent garbage in tests/test_gpu_pair.py, about every second run.)
     asm volatile("" : "+v"(v) :: "memory");
-    if constexpr (FIRST) { a0 = f4{0.f, 0.f, 0.f, 0.f}; a1 = a0; b0 = a0; b1 = a0; }
-    const bf8 av = __builtin_bit_cast(bf8, v);
+    if constexpr (FIRST) { a0 = v4f{0.f, 0.f, 0.f, 0.f}; a1 = a0; b0 = a0; b1 = a0; }
+    const s16x8 av = __builtin_bit_cast(s16x8, v);
 #if defined(CMPS_DIAG) && defined(PABL_NO_MFMA)       // diagnostic builds only (scripts/ablate.py)
     a0[0] += __uint_as_float(v.x); a1[0] += __uint_as_float(fa1.x); b0[0] += __uint_as_float(fb0.x); b1[0] += __uint_as_float(fb1.x + fa0.x);
     rd(ic<0>{}); rd(ic<1>{}); rd(ic<2>{}); rd(ic<3>{});
 #else
-    a0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, __builtin_bit_cast(bf8, fa0), a0, 0, 0, 0);
+    a0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, __builtin_bit_cast(s16x8, fa0), a0, 0, 0, 0);
     __builtin_amdgcn_sched_barrier(0); rd(ic<0>{}); __builtin_amdgcn_sched_barrier(0);
-    b0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, __builtin_bit_cast(bf8, fb0), b0, 0, 0, 0);
+    b0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, __builtin_bit_cast(s16x8, fb0), b0, 0, 0, 0);
     __builtin_amdgcn_sched_barrier(0); rd(ic<1>{}); __builtin_amdgcn_sched_barrier(0);
-    a1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, __builtin_bit_cast(bf8, fa1), a1, 0, 0, 0);
+    a1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, __builtin_bit_cast(s16x8, fa1), a1, 0, 0, 0);
     __builtin_amdgcn_sched_barrier(0); rd(ic<2>{}); __builtin_amdgcn_sched_barrier(0);
-    b1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, __builtin_bit_cast(bf8, fb1), b1, 0, 0, 0);
+    b1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, __builtin_bit_cast(s16x8, fb1), b1, 0, 0, 0);
     __builtin_amdgcn_sched_barrier(0); rd(ic<3>{}); __builtin_amdgcn_sched_barrier(0);
 #endif
 }
 template <int PD, int POFF, bool TABLES_LAST, typename Piece>
-__device__ __forceinline__ void matvec2(const u4 (&FA)[PD / 8], const u4 (&FB)[PD / 8], const ChainLane<PD / 32>& g, unsigned ax0, unsigned ax1,
-                                        u4& vlo, u4& vhi, f4& x0, f4& x1, f4& a0, f4& a1, f4& b0, f4& b1, Piece&& piece) {
+__device__ __forceinline__ void matvec2(const v4u (&FA)[PD / 8], const v4u (&FB)[PD / 8], const ChainLane<PD / 32>& g, unsigned ax0, unsigned ax1,
+                                        v4u& vlo, v4u& vhi, v4f& x0, v4f& x1, v4f& a0, v4f& a1, v4f& b0, v4f& b1, Piece&& piece) {
     constexpr int KS = PD / 16, KH = PD / 32;
-    u4 v[KS - 2];
+    v4u v[KS - 2];
 #if defined(CMPS_DIAG) && (defined(PABL_NO_READS) || defined(PABL_READ_BURST))     // diagnostic / A/B builds: all reads in front of the own K-steps (rounds 1-3 and the first round-4 form)
     rd_rest<KH, POFF, TABLES_LAST>(ax0, ax1, g.lo, g.hi, x0, x1, v);
     __builtin_amdgcn_sched_barrier(0);
@@ -470,8 +440,6 @@ struct FwdRing {
     __attribute__((aligned(16))) float sinc[2][2][PCH];                // [chunk parity][clip][step]: s_k = x_k / A of a 64-step chunk (loss wave 0 -> chain waves)
 };
 
-typedef float f16t __attribute__((ext_vector_type(16)));
-
 // float index of (pair, step, y / H y, clip, component, row) in the pair stash
 template <int PD>
 __device__ __forceinline__ size_t pair_stash_index(size_t pair, int N, int step, int yh, int clip, int comp, int row) {
@@ -505,7 +473,7 @@ __global__ __launch_bounds__(4 * PD, 1) void k_fwd_pair(Dev P, const float* __re
         // ================================================================== chain waves
         __builtin_amdgcn_s_setprio(3);      // both kinds share a SIMD's matrix pipe: the serial chain goes first
         constexpr int KH = PD / 32, VEC = PairLds<PD>::VEC_BYTES;
-        u4 FR[PD / 8], FQ[PD / 8];
+        v4u FR[PD / 8], FQ[PD / 8];
         {
             const int row0 = 32 * w + 2 * (lane & 15);                 // rows ia (tile 0) and ia + 1 (tile 1)
             const float2* Rrow = P.R + (size_t)row0 * PD;
@@ -528,9 +496,9 @@ __global__ __launch_bounds__(4 * PD, 1) void k_fwd_pair(Dev P, const float* __re
         const unsigned a_rho = lds_addr_of(&RS.row[0][0][ia]);        // + 8 PD (32 buffer + row)
         const float2 pa = P.psi0[ia], pb = P.psi0[ib];
         // ut_0 = psi_0 (both clips): (own component, a copy of the partner's -- kept in step by the MFMAs' register 1)
-        f2 ua = odd ? f2{pa.y, pa.x} : f2{pa.x, pa.y}, ub = odd ? f2{pb.y, pb.x} : f2{pb.x, pb.y};
+        v2f ua = odd ? v2f{pa.y, pa.x} : v2f{pa.x, pa.y}, ub = odd ? v2f{pb.y, pb.x} : v2f{pb.x, pb.y};
         float sv0 = 0.f, sv1 = 0.f;                                   // s = x / A of the current 64 steps, lane <-> step
-        u4 vlo, vhi;                                                  // the wave's own K-steps of the image the next step multiplies
+        v4u vlo, vhi;                                                  // the wave's own K-steps of the image the next step multiplies
         write_vec(L.vec[0], g, ua.x, ub.x);
         rd_own<0>(g.lo[0], g.hi[0], vlo, vhi);
         rho_stage<PD>(P, RS, 0, 0, 64 * w + lane_c);
@@ -569,7 +537,7 @@ __global__ __launch_bounds__(4 * PD, 1) void k_fwd_pair(Dev P, const float* __re
             const int nslot = (J) > 0 ? hb_ * FB + (J) - 1 : (hb_ ^ 1) * FB + FB - 1;                                      \
             const unsigned ax0 = a_nrm + 32 * nslot;                                                                       \
             const unsigned ax1 = a_rho + 8 * PD * (((bt / (RCH / FB)) & 1) * RCH + (bt & (RCH / FB - 1)) * FB + (J));       \
-            f4 xn, rh, cR0, cR1, cQ0, cQ1;                                                                                 \
+            v4f xn, rh, cR0, cR1, cQ0, cQ1;                                                                                 \
             float inv, s;                                                                                                  \
             PAIR_FSTAMP_A();                                                                                               \
             matvec2<PD, p * VEC, false>(FR, FQ, g, ax0, ax1, vlo, vhi, xn, rh, cR0, cR1, cQ0, cQ1, [&](auto pc) {                 \
@@ -577,7 +545,7 @@ __global__ __launch_bounds__(4 * PD, 1) void k_fwd_pair(Dev P, const float* __re
                     inv = __builtin_amdgcn_rsqf(fmaxf(sum4<PWV>(xn), 1e-12f));           /* model.py:332 */                \
                     if ((J) == 0 && bt == 0) inv = 1.f;                                                                    \
                     const int kl = (bt & (PCH / FB - 1)) * FB + (J);                                                       \
-                    const float s0 = rdl(sv0, kl), s1 = rdl(sv1, kl);  /* (both read: a readlane inside a select becomes a branch) */ \
+                    const float s0 = rdlane(sv0, kl), s1 = rdlane(sv1, kl);  /* (both read: a readlane inside a select becomes a branch) */ \
                     s = q ? s1 : s0;                                                                                       \
                     PAIR_PIN2(inv, s);                                                                                     \
                 }                                                                                                          \
@@ -585,22 +553,22 @@ __global__ __launch_bounds__(4 * PD, 1) void k_fwd_pair(Dev P, const float* __re
             PAIR_FSTAMP_B();                                                                                               \
             /* y_k, rows ia / ib: own component (register 0) and the partner's (register 1), as explicit (own, partner) pairs: the tail  \
                runs when the matrix pipe is idle, where packed float32 VALU halves its instruction count */                        \
-            const f2 ya = inv * (ua + (f2{cQ0[0], cQ0[1]} + s * f2{cR0[0], cR0[1]}));                                       \
-            const f2 yb = inv * (ub + (f2{cQ1[0], cQ1[1]} + s * f2{cR1[0], cR1[1]}));                                       \
+            const v2f ya = inv * (ua + (v2f{cQ0[0], cQ0[1]} + s * v2f{cR0[0], cR0[1]}));                                       \
+            const v2f yb = inv * (ub + (v2f{cQ1[0], cQ1[1]} + s * v2f{cR1[0], cR1[1]}));                                       \
             const float yna = ya.x, ynb = yb.x;                                                                            \
             /* Two chains start at y and both end in an LDS store the barrier waits for: ut_{k+1} = rho_k y_k -> bf16 image, and    \
                |y_k|^2 -> four dependent DPP adds -> norm partial.  Written out turn by turn (scheduling barriers), the second      \
                runs in the first one's dependency gaps; left to the scheduler it came behind it. */                                \
-            const f2 n2 = ya * ya + yb * yb;                                                                               \
+            const v2f n2 = ya * ya + yb * yb;                                                                               \
             float nn = n2.x + n2.y;                                                                                        \
-            const f2 ta = f2{sg * rh.y, -(sg * rh.y)} * __builtin_shufflevector(ya, ya, 1, 0);                              \
-            const f2 tb = f2{sg * rh.w, -(sg * rh.w)} * __builtin_shufflevector(yb, yb, 1, 0);                              \
+            const v2f ta = v2f{sg * rh.y, -(sg * rh.y)} * __builtin_shufflevector(ya, ya, 1, 0);                              \
+            const v2f tb = v2f{sg * rh.w, -(sg * rh.w)} * __builtin_shufflevector(yb, yb, 1, 0);                              \
             __builtin_amdgcn_sched_barrier(0);                                                                             \
             nn += dpp_mov<0x128>(nn);                                  /* row_ror:8 */                                     \
             ua = rh.x * ya + ta;   ub = rh.z * yb + tb;               /* ut_{k+1} = rho_k y_k (un-normalised), own and partner */ \
             __builtin_amdgcn_sched_barrier(0);                                                                             \
             nn += dpp_mov<0x124>(nn);                                  /* row_ror:4 */                                     \
-            const unsigned pku = pk_bf16(ua.x, ub.x);                                                                      \
+            const unsigned pku = cvt_pk_bf16(ua.x, ub.x);                                                                      \
             __builtin_amdgcn_sched_barrier(0);                                                                             \
             nn += dpp_mov<0x122>(nn);                                  /* row_ror:2 */                                     \
             *reinterpret_cast<unsigned*>(L.vec[p ^ 1] + g.wr1) = pku;                                                      \
@@ -608,7 +576,7 @@ __global__ __launch_bounds__(4 * PD, 1) void k_fwd_pair(Dev P, const float* __re
             rd_own<(p ^ 1) * VEC>(g.lo[0], g.hi[0], vlo, vhi);         /* (same wave, in order: no wait between store and read) */ \
             __builtin_amdgcn_sched_barrier(0);                                                                             \
             nn += dpp_mov<0x121>(nn);                                  /* row_ror:1: the clip's total over this wave's rows */ \
-            const unsigned pky = pk_bf16(yna, ynb);                                                                        \
+            const unsigned pky = cvt_pk_bf16(yna, ynb);                                                                        \
             __builtin_amdgcn_sched_barrier(0);                                                                             \
             if (lane_c == 0 || lane_c == 32) RG.nrm[hb_ * FB + (J)][q][w] = nn;                                           \
             {   /* y_k for the loss waves: bf16 images and float32 */                                                      \
@@ -645,7 +613,7 @@ __global__ __launch_bounds__(4 * PD, 1) void k_fwd_pair(Dev P, const float* __re
     const int n = lane & 31, hk = lane >> 5;
     const int comp = n >> 4, sb = (n >> 1) & (FB - 1), clip = n & 1;   // the column of this lane: (component, step in batch, clip)
     constexpr int KS = PD / 16, KT = 2 * KS;                            // MFMAs per batch: H_re [y_re | y_im] and H_im [-y_im | y_re]
-    u4 FHre[KS], FHim[KS];                                             // H = R + R^dagger, rows 32 w + n, K = 16 t + 8 hk ..
+    v4u FHre[KS], FHim[KS];                                             // H = R + R^dagger, rows 32 w + n, K = 16 t + 8 hk ..
     {
         const float2* Rrow = P.R + (size_t)(32 * w + n) * PD;
         const float2* RTrow = P.RT + (size_t)(32 * w + n) * PD;       // RT[i][j] = R[j][i]
@@ -658,8 +626,8 @@ __global__ __launch_bounds__(4 * PD, 1) void k_fwd_pair(Dev P, const float* __re
                 rr[e] = (unsigned)bf16_rne(Rrow[j0].x + RTrow[j0].x) | ((unsigned)bf16_rne(Rrow[j0 + 1].x + RTrow[j0 + 1].x) << 16);
                 ii[e] = (unsigned)bf16_rne(Rrow[j0].y - RTrow[j0].y) | ((unsigned)bf16_rne(Rrow[j0 + 1].y - RTrow[j0 + 1].y) << 16);
             }
-            FHre[t] = u4{rr[0], rr[1], rr[2], rr[3]};
-            FHim[t] = u4{ii[0], ii[1], ii[2], ii[3]};
+            FHre[t] = v4u{rr[0], rr[1], rr[2], rr[3]};
+            FHim[t] = v4u{ii[0], ii[1], ii[2], ii[3]};
             // one fragment pair at a time ("memory": the loads of the next pair stay behind this point): with all 64 row loads in
             // flight the prologue was the kernel's register peak, and the allocator then kept fragments in scratch memory for the
             // whole loop (reloaded behind s_waitcnt vmcnt(0) in every step: 2 ms of the round-4 forward until this was found)
@@ -675,8 +643,8 @@ __global__ __launch_bounds__(4 * PD, 1) void k_fwd_pair(Dev P, const float* __re
     const float* xr_c = clip ? xr1 : xr0;
     const bool clip_live = clip == 0 || two;
     float loss0 = 0.f, loss1 = 0.f;
-    f16t acc, accE;                                                    // the tile being accumulated / the finished tile of the batch before
-    f4 yv[4];                                                          // y (float32) of this lane's column: rows 32 w + 8 g + 4 hk ..+3
+    v16f acc, accE;                                                    // the tile being accumulated / the finished tile of the batch before
+    v4f yv[4];                                                          // y (float32) of this lane's column: rows 32 w + 8 g + 4 hk ..+3
     float epE = 0.f, xp0 = 0.f, xp1 = 0.f;
     __syncthreads();
     // Batch bt of the loop: multiplies batch pb = bt - 1 (two MFMAs per step), reads its float32 y (steps 0-3) and stores it
@@ -704,9 +672,9 @@ __global__ __launch_bounds__(4 * PD, 1) void k_fwd_pair(Dev P, const float* __re
         const unsigned char* fslot = &RG.f[(pb & 1) * FB + sb][0][0][0];
         const int step_b = FB * pb + sb, step_e = FB * pe + sb;       // this lane's step in either batch
 #if defined(CMPS_DIAG) && defined(PABL_LOSS_NO_READS)     // diagnostic builds only (scripts/ablate.py)
-#define PAIR_LOSS_BV(p) u4{(unsigned)(uintptr_t)(p), 1u, 2u, 3u}
+#define PAIR_LOSS_BV(p) v4u{(unsigned)(uintptr_t)(p), 1u, 2u, 3u}
 #else
-#define PAIR_LOSS_BV(p) (*reinterpret_cast<const u4*>(p))
+#define PAIR_LOSS_BV(p) (*reinterpret_cast<const v4u*>(p))
 #endif
 #define PAIR_LOSS_STEP(J)                                                                                                  \
         {                                                                                                                  \
@@ -714,7 +682,7 @@ __global__ __launch_bounds__(4 * PD, 1) void k_fwd_pair(Dev P, const float* __re
                 if (((J) & 1) == 0 && SAVE && step_e < N) {          /* H y of batch pe: ONE 16-byte store per lane and step (J = 0, 2, 4, 6) -- */ \
                     constexpr int g = (J) / 2;                         /* four in one step made that step the slowest of the batch, and every    */ \
                     float* hp = stash + pair_stash_index<PD>(blockIdx.x, N, step_e, 1, clip, comp, 32 * w + 4 * hk);   /* barrier waits for the slowest wave */ \
-                    *reinterpret_cast<f4*>(hp + 8 * g) = f4{accE[4 * g], accE[4 * g + 1], accE[4 * g + 2], accE[4 * g + 3]}; \
+                    *reinterpret_cast<v4f*>(hp + 8 * g) = v4f{accE[4 * g], accE[4 * g + 1], accE[4 * g + 2], accE[4 * g + 3]}; \
                 }                                                                                                          \
                 if ((J) == 1) {                                      /* the two audio samples of this lane's step, four steps before their use */ \
                     const bool in = step_e < N;                                                                            \
@@ -722,7 +690,7 @@ __global__ __launch_bounds__(4 * PD, 1) void k_fwd_pair(Dev P, const float* __re
                     xp1 = (in && step_e + 1 < T) ? xr_c[step_e + 1] : 0.f;                                                 \
                 }                                                                                                          \
                 if ((J) == 1) {                                                                                            \
-                    float ep = half_add(epE, epE);                     /* + the other row half */                          \
+                    float ep = swap32_add(epE, epE);                     /* + the other row half */                          \
                     const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(ep), __float_as_uint(ep), false, false); \
                     ep = __uint_as_float(r[0]) + __uint_as_float(r[1]);              /* + the other component */            \
                     if (lane < 2 * FB) RG.ee[pe & 1][lane][w] = ep;                                                        \
@@ -734,21 +702,21 @@ __global__ __launch_bounds__(4 * PD, 1) void k_fwd_pair(Dev P, const float* __re
                     if (SAVE && w == 0 && lane < 2 * FB && in && clip_live)                                                 \
                         sc_c[(size_t)(step_e / PCH) * 128 + 64 + (step_e & (PCH - 1))] = e;                               \
                     _Pragma("unroll") for (int jj = 0; jj < FB; ++jj) {  /* model.py:279: sequential in time */             \
-                        loss0 += rdl(lv, 2 * jj);                                                                          \
-                        loss1 += rdl(lv, 2 * jj + 1);                                                                      \
+                        loss0 += rdlane(lv, 2 * jj);                                                                          \
+                        loss1 += rdlane(lv, 2 * jj + 1);                                                                      \
                     }                                                                                                      \
                 }                                                                                                          \
             }                                                                                                              \
             if (mul) {                                                                                                     \
-                if ((J) < 4) yv[(J) & 3] = *reinterpret_cast<const f4*>(fslot + of + 32 * ((J) & 3));                      \
+                if ((J) < 4) yv[(J) & 3] = *reinterpret_cast<const v4f*>(fslot + of + 32 * ((J) & 3));                      \
                 if (((J) & 1) == 1 && SAVE && step_b < N) {          /* y of batch pb (the repeated clip of an odd batch too): one store per */ \
                     constexpr int g = (J) / 2;                         /* lane at J = 1, 3, 5, 7 (yv[g] was read at J = g)                     */ \
                     float* yp = stash + pair_stash_index<PD>(blockIdx.x, N, step_b, 0, clip, comp, 32 * w + 4 * hk);       \
-                    *reinterpret_cast<f4*>(yp + 8 * g) = yv[g];                                                            \
+                    *reinterpret_cast<v4f*>(yp + 8 * g) = yv[g];                                                            \
                 }                                                                                                          \
                 if ((J) == 4 && SAVE && step_b < N && w == 0 && lane < 2 * FB && clip_live)                                 \
                     sc_c[(size_t)(step_b / PCH) * 128 + (step_b & (PCH - 1))] = sum_waves<PWV>(&RG.nrm[(pb & 1) * FB + sb][clip][0]); \
-                u4 bvs[(KT + FB - 1) / FB];                                                                                \
+                v4u bvs[(KT + FB - 1) / FB];                                                                                \
                 _Pragma("unroll") for (int t = (J) * KT / FB; t < ((J) + 1) * KT / FB; ++t)                                \
                     bvs[t - (J) * KT / FB] = PAIR_LOSS_BV(bslot + (t < KS ? ob1 : ob2) + 32 * (t < KS ? t : t - KS));      \
                 if constexpr (LOSS_SLEEP > 0) {                      /* the MFMAs go to the matrix pipe when the chain is in its tail */ \
@@ -757,7 +725,7 @@ __global__ __launch_bounds__(4 * PD, 1) void k_fwd_pair(Dev P, const float* __re
                 }                                                                                                          \
                 _Pragma("unroll") for (int t = (J) * KT / FB; t < ((J) + 1) * KT / FB; ++t) {                              \
                     const int tt = t < KS ? t : t - KS;                                                                    \
-                    const u4 bv = bvs[t - (J) * KT / FB];                                                                  \
+                    const v4u bv = bvs[t - (J) * KT / FB];                                                                  \
                     /* asm (fixed issue points); no AGPR operand anywhere in this kernel: see kstep */                           \
                     if (t == 0)                                                                                            \
                         asm volatile(PAIR_LASM("v_mfma_f32_32x32x16_bf16 %0, %1, %2, 0") : "=&v"(acc) : "v"(FHre[0]), "v"(bv));     \
@@ -822,14 +790,12 @@ hipError_t launch_fwd_pair(const Dev& P, const float* audio, float* loss, bool s
 // ------------------------------------------------------------------------------------------------
 namespace {
 
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 
 // (a, b) -> packed hi pieces and packed lo pieces
 __device__ __forceinline__ void split_f16x2(float a, float b, unsigned& hi, unsigned& lo) {
-    typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-    hi = gg::cvt_pk_f16(a, b);
+    hi = cvt_pk_f16(a, b);
     const h2 h = __builtin_bit_cast(h2, hi);
-    lo = gg::cvt_pk_f16(a - (float)h.x, b - (float)h.y);
+    lo = cvt_pk_f16(a - (float)h.x, b - (float)h.y);
 }
 
 template <int D>
@@ -842,7 +808,7 @@ struct Chain16Lds {
 
 // hi / lo fragments of one matrix (see load_frags), entries scaled by `scale`
 template <int PD, bool PIN_LO = true, typename F>
-__device__ __forceinline__ void load_frags_f16(u4 (&fh)[PD / 8], u4 (&fl)[PD / 8], int w, int kg, float scale, F&& elem) {
+__device__ __forceinline__ void load_frags_f16(v4u (&fh)[PD / 8], v4u (&fl)[PD / 8], int w, int kg, float scale, F&& elem) {
     constexpr int KS = PD / 16, KH = PD / 32;
 #pragma unroll
     for (int tile = 0; tile < 2; ++tile)
@@ -853,8 +819,8 @@ __device__ __forceinline__ void load_frags_f16(u4 (&fh)[PD / 8], u4 (&fl)[PD / 8
 #pragma unroll
             for (int e = 0; e < 4; ++e)
                 split_f16x2(elem(tile, half, col0 + 2 * e) * scale, elem(tile, half, col0 + 2 * e + 1) * scale, vh[e], vl[e]);
-            fh[tile * KS + t] = u4{vh[0], vh[1], vh[2], vh[3]};
-            fl[tile * KS + t] = u4{vl[0], vl[1], vl[2], vl[3]};
+            fh[tile * KS + t] = v4u{vh[0], vh[1], vh[2], vh[3]};
+            fl[tile * KS + t] = v4u{vl[0], vl[1], vl[2], vl[3]};
             if constexpr (PIN_LO) asm volatile("" : "+a"(fh[tile * KS + t]), "+a"(fl[tile * KS + t]) :: "memory");
             else asm volatile("" : "+a"(fh[tile * KS + t]) :: "memory");
         }
@@ -866,10 +832,10 @@ struct NoSlot { template <typename I> __device__ __forceinline__ void operator()
 // instance); stacked it is 8 (6) -- v R_hi and v R_lo give hi hi' + lo hi' + hi lo' (+ lo lo', 2^-22 of the product: kept, it costs nothing) in registers
 // 0 + 2 (own form) and 1 + 3 (partner) of the accumulator -- and one operand read instead of two.
 template <int W, bool FIRST, bool QLITE = false, bool PIPE = false, typename Slot = NoSlot>
-__device__ __forceinline__ void kstep_st(const u4& rh0, const u4& rl0, const u4& rh1, const u4& rl1, const u4& qh0, const u4& ql0, const u4& qh1,
-                                         const u4& ql1, u4& v, f4& aR0, f4& aR1, f4& aQ0, f4& aQ1, Slot&& slot = NoSlot{}) {
+__device__ __forceinline__ void kstep_st(const v4u& rh0, const v4u& rl0, const v4u& rh1, const v4u& rl1, const v4u& qh0, const v4u& ql0, const v4u& qh1,
+                                         const v4u& ql1, v4u& v, v4f& aR0, v4f& aR1, v4f& aQ0, v4f& aQ1, Slot&& slot = NoSlot{}) {
     asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(v) : "n"(W) : "memory");
-    if constexpr (FIRST) { aR0 = f4{0.f, 0.f, 0.f, 0.f}; aR1 = aR0; aQ0 = aR0; aQ1 = aR0; }
+    if constexpr (FIRST) { aR0 = v4f{0.f, 0.f, 0.f, 0.f}; aR1 = aR0; aQ0 = aR0; aQ1 = aR0; }
     const h8 a = __builtin_bit_cast(h8, v);
 #define C16_MMA(ACC, B) ACC = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, __builtin_bit_cast(h8, B), ACC, 0, 0, 0)
     if constexpr (PIPE) {               // the reverse scan: the slots' code first, then the MFMAs, interleaved 1 MFMA : 2 VALU by a sched_group_barrier pipeline instead of walls around every slot (-0.6 ms of 16.7 at C5 in round 4; no gain for the forward, whose slots hold LDS reads only)
@@ -891,16 +857,12 @@ __device__ __forceinline__ void kstep_st(const u4& rh0, const u4& rl0, const u4&
 #undef C16_MMA
 }
 // own + partner sums of a stacked accumulator: (hi-piece rows) + (lo-piece rows)
-__device__ __forceinline__ f2 st_sum(const f4& c) { return f2{c[0], c[1]} + f2{c[2], c[3]}; }
+__device__ __forceinline__ v2f st_sum(const v4f& c) { return v2f{c[0], c[1]} + v2f{c[2], c[3]}; }
 
 // single 16-byte LDS reads (asm volatile statements keep their order; the data is valid after a matching counted wait)
 template <int OFF, typename V>
 __device__ __forceinline__ void rd128(unsigned addr, V& v) {
     asm volatile("ds_read_b128 %0, %1 offset:%2" : "=&v"(v) : "v"(addr), "n"(OFF) : "memory");
-}
-__device__ __forceinline__ float gg_rsq_newton(float m) {      // as cmps_wide.hip::rsq_newton (the family's reverse scan and GEMM recompute it)
-    const float r = __builtin_amdgcn_rsqf(m);
-    return r * (1.5f - 0.5f * m * r * r);
 }
 
 // float offset of (row, component, clip) inside a vector of the wide family's stash (cmps_wide.hip: lane order of its chain kernels)
@@ -959,22 +921,22 @@ __global__ __launch_bounds__(2 * PD, 1) void k_fwd_chain16(Dev P, const float* _
         }
         __syncthreads();
         auto uni = [](float x) { return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(x))); };
-        sR = uni(gg::pow2_scale(mR, 15));
-        sQ = uni(gg::pow2_scale(mQ, 15));
-        sV = uni(gg::pow2_scale(1.01f * (1.0f + sqrtf(fQ) + ms * sqrtf(fR)), 13));
+        sR = uni(pow2_below(mR, 15));
+        sQ = uni(pow2_below(mQ, 15));
+        sV = uni(pow2_below(1.01f * (1.0f + sqrtf(fQ) + ms * sqrtf(fR)), 13));
     }
     const float iRV = (1.0f / sR) * (1.0f / sV), iQV = (1.0f / sQ) * (1.0f / sV);    // exact: powers of two
 
-    u4 FRh[PD / 8], FRl[PD / 8], FQh[PD / 8], FQl[QLITE ? 1 : PD / 8];
+    v4u FRh[PD / 8], FRl[PD / 8], FQh[PD / 8], FQl[QLITE ? 1 : PD / 8];
     {
         const int row0 = 32 * w + 2 * (lane & 15);
         const float2* Rrow = P.R + (size_t)row0 * PD;
         const float2* Qrow = P.Q + (size_t)row0 * PD;
         load_frags_f16<PD>(FRh, FRl, w, lane >> 4, sR, [&](int tile, int half, int c) { return half ? Rrow[tile * PD + c].y : Rrow[tile * PD + c].x; });
         if constexpr (QLITE) {
-            u4 dump[PD / 8];
+            v4u dump[PD / 8];
             load_frags_f16<PD, false>(FQh, dump, w, lane >> 4, sQ, [&](int tile, int half, int c) { return half ? Qrow[tile * PD + c].y : Qrow[tile * PD + c].x; });
-            FQl[0] = u4{0u, 0u, 0u, 0u};
+            FQl[0] = v4u{0u, 0u, 0u, 0u};
         } else {
             load_frags_f16<PD>(FQh, FQl, w, lane >> 4, sQ, [&](int tile, int half, int c) { return half ? Qrow[tile * PD + c].y : Qrow[tile * PD + c].x; });
         }
@@ -988,11 +950,11 @@ __global__ __launch_bounds__(2 * PD, 1) void k_fwd_chain16(Dev P, const float* _
     const unsigned a_nrm = lds_addr_of(&L.nrm[0][0][0]);             // + 32 parity: (clip 0 row, clip 1 row)
     const unsigned a_rho = lds_addr_of(&RS.row[0][0][ia]);            // + 8 PD (32 buffer + row)
     const float2 pa = P.psi0[ia], pb = P.psi0[ib];
-    f2 ua = odd ? f2{pa.y, pa.x} : f2{pa.x, pa.y}, ub = odd ? f2{pb.y, pb.x} : f2{pb.x, pb.y};
+    v2f ua = odd ? v2f{pa.y, pa.x} : v2f{pa.x, pa.y}, ub = odd ? v2f{pb.y, pb.x} : v2f{pb.x, pb.y};
     float sv0 = 0.f, sv1 = 0.f;
     float nbuf0 = 0.f, nbuf1 = 0.f;                                   // wave 0: |y_k|^2 of the current 64-step chunk, lane <-> step
     float* stash = reinterpret_cast<float*>(P.stash) + (size_t)blockIdx.x * N * (8 * PD) + wide_pos(ia, odd ? 1 : 0, q);
-    u4 o0, o1;                                                        // the wave's own K-steps: [K half] (both pieces stacked in the A rows)
+    v4u o0, o1;                                                        // the wave's own K-steps: [K half] (both pieces stacked in the A rows)
     float n0p = 1.f, n1p = 1.f;                                       // |y|^2 of both clips as the last step's tail read them
     // |y_kn|^2 rows of the scalar stash (wave 0; lane <-> step, one row of 64 steps per chunk), a step late and off the chain's tail
     auto book = [&](int kn) {
@@ -1046,8 +1008,8 @@ __global__ __launch_bounds__(2 * PD, 1) void k_fwd_chain16(Dev P, const float* _
         if (p == 0 && (k & (RCH - 1)) == 0) rho_stage<PD>(P, RS, k / RCH + 1, (k / RCH + 1) & 1, 64 * w + lane_c);          \
         const unsigned ax0 = a_nrm + 32 * p;                                                                               \
         const unsigned ax2 = a_rho + 8 * PD * (((k / RCH) & 1) * RCH + (k & (RCH - 1)));                                   \
-        f4 xn0, xn1, rh, cR0, cR1, cQ0, cQ1;                                                                               \
-        u4 v[2 * KH - 2];                                                                                                  \
+        v4f xn0, xn1, rh, cR0, cR1, cQ0, cQ1;                                                                               \
+        v4u v[2 * KH - 2];                                                                                                  \
         /* the step's LDS reads (the other waves' K ranges, both pieces; three table rows) are issued two per K-step behind pairs of    \
            MFMAs, two K-steps ahead of their use: the four waves' 60 KB per step then pass the LDS (128 B / clk) spread over the step  \
            instead of in one burst behind the barrier (which took ~390 cycles with the matrix pipe idle, ~200 even when interleaved    \
@@ -1081,16 +1043,16 @@ __global__ __launch_bounds__(2 * PD, 1) void k_fwd_chain16(Dev P, const float* _
         C16_STAMP_DEP(3, cQ1[1])                                                                                           \
         const float n0 = sum4<PWV>(xn0), n1 = sum4<PWV>(xn1);                                                              \
         const float nq = q ? n1 : n0;                                                                                      \
-        float inv = gg_rsq_newton(fmaxf(nq, 1e-12f));                                    /* model.py:332 */                \
+        float inv = rsq_newton(fmaxf(nq, 1e-12f));                                    /* model.py:332 */                \
         if (k == 0) inv = 1.f;                                                                                             \
-        const float s0 = rdl(sv0, k & (PCH - 1)), s1 = rdl(sv1, k & (PCH - 1));                                            \
+        const float s0 = rdlane(sv0, k & (PCH - 1)), s1 = rdlane(sv1, k & (PCH - 1));                                            \
         const float sr = (q ? s1 : s0) * iRV;                                                                              \
-        const f2 ya = inv * (ua + (st_sum(cQ0) * iQV + sr * st_sum(cR0)));                                                  \
-        const f2 yb = inv * (ub + (st_sum(cQ1) * iQV + sr * st_sum(cR1)));                                                  \
-        const f2 n2 = ya * ya + yb * yb;                                                                                   \
+        const v2f ya = inv * (ua + (st_sum(cQ0) * iQV + sr * st_sum(cR0)));                                                  \
+        const v2f yb = inv * (ub + (st_sum(cQ1) * iQV + sr * st_sum(cR1)));                                                  \
+        const v2f n2 = ya * ya + yb * yb;                                                                                   \
         float nn = n2.x + n2.y;                                                                                            \
-        const f2 ta = f2{sg * rh.y, -(sg * rh.y)} * __builtin_shufflevector(ya, ya, 1, 0);                                  \
-        const f2 tb = f2{sg * rh.w, -(sg * rh.w)} * __builtin_shufflevector(yb, yb, 1, 0);                                  \
+        const v2f ta = v2f{sg * rh.y, -(sg * rh.y)} * __builtin_shufflevector(ya, ya, 1, 0);                                  \
+        const v2f tb = v2f{sg * rh.w, -(sg * rh.w)} * __builtin_shufflevector(yb, yb, 1, 0);                                  \
         ua = rh.x * ya + ta;   ub = rh.z * yb + tb;                   /* ut_{k+1} = rho_k y_k (un-normalised), own and partner */ \
         write_image(p ^ 1, ua.x, ub.x);                                                                                    \
         rd_own<(p ^ 1) * 2 * VEC>(g.lo[0], g.hi[0], o0, o1);          /* (same wave, in order: no wait between store and read) */ \
@@ -1160,7 +1122,7 @@ namespace {
 // per-step scalars of one clip: (s, inv, ok, te | rad, xa = -x/A^2, dt, -)
 template <int W>
 struct StepTab {
-    __attribute__((aligned(16))) f4 row[W][2][PCH][2][2];              // [wave][chunk parity][step][clip][half]
+    __attribute__((aligned(16))) v4f row[W][2][PCH][2][2];              // [wave][chunk parity][step][clip][half]
 };
 
 constexpr int GB = 8;          // steps per block of the unrolled sweep
@@ -1188,7 +1150,7 @@ __global__ __launch_bounds__(2 * PD, 1) void k_bwd_pair(Dev P, const float* __re
     const int b0 = 2 * blockIdx.x, b1 = (b0 + 1 < P.B) ? b0 + 1 : b0;
     const bool two = b1 != b0;
 
-    u4 FQ[PD / 8], FD[PD / 8];                                        // Q (Hermitian) and R^dagger
+    v4u FQ[PD / 8], FD[PD / 8];                                        // Q (Hermitian) and R^dagger
     {
         const int row0 = 32 * w + 2 * (lane0 & 15);                    // rows ia (tile 0) and ia + 1 (tile 1)
         const float2* Qrow = P.Q + (size_t)row0 * PD;
@@ -1233,7 +1195,7 @@ __global__ __launch_bounds__(2 * PD, 1) void k_bwd_pair(Dev P, const float* __re
             const float z = ex / A;
             const float zbar = -1.0f / (1.0f + z);
             const float te = 2.0f * (zbar * inc / A);
-            f4 r0, r1;
+            v4f r0, r1;
             r0.x = inc / A;
             r0.y = 1.0f / sqrtf(fmaxf(nv, 1e-12f));
             r0.z = nv > 1e-12f ? 1.f : 0.f;
@@ -1264,9 +1226,9 @@ __global__ __launch_bounds__(2 * PD, 1) void k_bwd_pair(Dev P, const float* __re
     float una = 0.f, unb = 0.f, puna = 0.f, punb = 0.f; // u_{k+1} = rho_k yhat_k, own and partner component (carried: it is u_k of the step before)
     float facca = 0.f, faccb = 0.f, accS = 0.f;
     float sda = 0.f, sdb = 0.f, ssy = 0.f;              // (R^dagger ybar) rows and the -x / A^2 factor of the step before: its Abar term is added a step late
-    u4 vlo, vhi;                                        // the wave's own K-steps of ybar_k, read back before the barrier
+    v4u vlo, vhi;                                        // the wave's own K-steps of ybar_k, read back before the barrier
     float4 rh, rhp;                             // rho_k and rho_{k-1}, rows ia | ib
-    f4 S0, S1, SP0, SP1;                        // scalar rows of steps k and k - 1 (fetched two steps ahead, behind the MFMAs)
+    v4f S0, S1, SP0, SP1;                        // scalar rows of steps k and k - 1 (fetched two steps ahead, behind the MFMAs)
     float c3a, c3b;                             // te_k (H y_k) - ok_k yhat_k rad_{k+1} inv_k
     auto rho_rows = [&](int k) { return *reinterpret_cast<const float4*>(&RS.row[(k / RCH) & 1][k & (RCH - 1)][ia]); };
     auto tab_row = [&](int k, int half) { return TB.row[w][(k / PCH) & 1][k & (PCH - 1)][q][half]; };
@@ -1342,7 +1304,7 @@ __global__ __launch_bounds__(2 * PD, 1) void k_bwd_pair(Dev P, const float* __re
         if ((k & (RCH - 1)) == RCH - 1 && k != N - 1 && k >= RCH)                   /* entering rho chunk k / RCH: fetch the one below */ \
             rho_stage<PD>(P, RS, k / RCH - 1, (k / RCH - 1) & 1, 64 * w + lane);                                                   \
         float4 nrh;                                                                                                                \
-        f4 nS0, nS1;                                                                                                               \
+        v4f nS0, nS1;                                                                                                               \
         PAIR_STAMP(0);                                                                                                             \
         /* ---- the chain ---- */                                                                                                  \
         const float hba = rh.x * ga - sgn * rh.y * pga;              /* conj(rho_k) g */                                           \
@@ -1367,7 +1329,7 @@ __global__ __launch_bounds__(2 * PD, 1) void k_bwd_pair(Dev P, const float* __re
         __builtin_amdgcn_sched_barrier(0);                                                                                         \
         lds_barrier();                                                                                                             \
         PAIR_STAMP(4);                                                                                                             \
-        f4 cQ0, cQ1, cD0, cD1;                                                                                                     \
+        v4f cQ0, cQ1, cD0, cD1;                                                                                                     \
         float uka, ukb, puka, pukb, ypa, ypb, pypa, pypb;                                                                          \
         const unsigned ax0 = a_tab + 64 * (((km2 / PCH) & 1) * PCH + (km2 & (PCH - 1)));                                           \
         matvec2<PD, p * VEC, PAIR_BWD_TABLES_LAST>(FQ, FD, g, ax0, ax0 + 16, vlo, vhi, nS0, nS1, cQ0, cQ1, cD0, cD1, [&](auto pc) {                      \
@@ -1408,8 +1370,8 @@ __global__ __launch_bounds__(2 * PD, 1) void k_bwd_pair(Dev P, const float* __re
         PAIR_STAMP(12);                                                                                                            \
         if (k == 0) { uka = ps0a; ukb = ps0b; puka = pps0a; pukb = pps0b; }         /* u_0 = psi_0 */                              \
         {   /* g = ybar + Q ybar + s R^dagger ybar, (own, partner) pairs: packed float32 (the matrix pipe is idle here) */          \
-            const f2 Ga = (f2{yba, pyba} + f2{cQ0[0], cQ0[1]}) + S0.x * f2{cD0[0], cD0[1]};                                        \
-            const f2 Gb = (f2{ybb, pybb} + f2{cQ1[0], cQ1[1]}) + S0.x * f2{cD1[0], cD1[1]};                                        \
+            const v2f Ga = (v2f{yba, pyba} + v2f{cQ0[0], cQ0[1]}) + S0.x * v2f{cD0[0], cD0[1]};                                        \
+            const v2f Gb = (v2f{ybb, pybb} + v2f{cQ1[0], cQ1[1]}) + S0.x * v2f{cD1[0], cD1[1]};                                        \
             ga = Ga.x; pga = Ga.y; gb = Gb.x; pgb = Gb.y;                                                                          \
         }                                                                                                                          \
         sda = cD0[0]; sdb = cD1[0]; ssy = S1.y;                                                                                    \
@@ -1551,22 +1513,22 @@ __global__ __launch_bounds__(2 * PD, 1) void k_bwd_chain16(Dev P, const float* _
         }
         __syncthreads();
         auto uni = [](float x) { return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(x))); };
-        sQ = uni(gg::pow2_scale(mQ, 15));
-        sD = uni(gg::pow2_scale(mD, 15));
+        sQ = uni(pow2_below(mQ, 15));
+        sD = uni(pow2_below(mD, 15));
         Qinf = uni(1.001f * rQ); Dinf = uni(1.001f * rD); Hinf = uni(1.001f * rH);
     }
     const float iQ = 1.0f / sQ, iD = 1.0f / sD;
 
-    u4 FQh[PD / 8], FQl[QLITE ? 1 : PD / 8], FDh[PD / 8], FDl[PD / 8];  // Q (Hermitian) and R^dagger
+    v4u FQh[PD / 8], FQl[QLITE ? 1 : PD / 8], FDh[PD / 8], FDl[PD / 8];  // Q (Hermitian) and R^dagger
     {
         const int row0 = 32 * w + 2 * (lane0 & 15);
         const float2* Qrow = P.Q + (size_t)row0 * PD;
         const float2* RTrow = P.RT + (size_t)row0 * PD;                // R^dagger[i][j] = conj(RT[i][j])
         load_frags_f16<PD>(FDh, FDl, w, lane0 >> 4, sD, [&](int tile, int half, int c) { return half ? -RTrow[tile * PD + c].y : RTrow[tile * PD + c].x; });
         if constexpr (QLITE) {
-            u4 dump[PD / 8];
+            v4u dump[PD / 8];
             load_frags_f16<PD, false>(FQh, dump, w, lane0 >> 4, sQ, [&](int tile, int half, int c) { return half ? Qrow[tile * PD + c].y : Qrow[tile * PD + c].x; });
-            FQl[0] = u4{0u, 0u, 0u, 0u};
+            FQl[0] = v4u{0u, 0u, 0u, 0u};
         } else {
             load_frags_f16<PD>(FQh, FQl, w, lane0 >> 4, sQ, [&](int tile, int half, int c) { return half ? Qrow[tile * PD + c].y : Qrow[tile * PD + c].x; });
         }
@@ -1607,9 +1569,9 @@ __global__ __launch_bounds__(2 * PD, 1) void k_bwd_chain16(Dev P, const float* _
             const float ex = ev * inc;
             const float z = ex / A;
             const float zbar = -1.0f / (1.0f + z);
-            f4 r0, r1;
+            v4f r0, r1;
             r0.x = inc / A;
-            r0.y = gg_rsq_newton(fmaxf(nv, 1e-12f));
+            r0.y = rsq_newton(fmaxf(nv, 1e-12f));
             r0.z = nv > 1e-12f ? 1.f : 0.f;
             r0.w = 2.0f * (zbar * inc / A);
             r1.x = r0.w * ev;
@@ -1618,7 +1580,7 @@ __global__ __launch_bounds__(2 * PD, 1) void k_bwd_chain16(Dev P, const float* _
             // lane above, or the chunk built before this one)
             float s_up = __shfl_down(r0.x, 1, 64), rad_up = __shfl_down(r1.x, 1, 64);
             if (lane == PCH - 1) { s_up = qq ? s_ab1 : s_ab0; rad_up = qq ? rad_ab1 : rad_ab0; }
-            if (qq) { s_ab1 = rdl(r0.x, 0); rad_ab1 = rdl(r1.x, 0); } else { s_ab0 = rdl(r0.x, 0); rad_ab0 = rdl(r1.x, 0); }
+            if (qq) { s_ab1 = rdlane(r0.x, 0); rad_ab1 = rdlane(r1.x, 0); } else { s_ab0 = rdlane(r0.x, 0); rad_ab0 = rdlane(r1.x, 0); }
             r1.z = fabsf(r0.w) * Hinf * (1.001f * sqrtf(fmaxf(nv, 1e-12f))) + fabsf(rad_up) * r0.z * r0.y;      // c_j >= |c3_j|
             r1.w = r0.y * fmaf(fabsf(s_up), gr1, gr0);                                                        // a_j
             TB.row[w][cj & 1][lane][qq][0] = r0;
@@ -1636,23 +1598,22 @@ __global__ __launch_bounds__(2 * PD, 1) void k_bwd_chain16(Dev P, const float* _
     if (threadIdx.x < 32) reinterpret_cast<unsigned*>(ymx_tab)[threadIdx.x] = 0u;
     __syncthreads();
 
-    f2 ga = f2{0.f, 0.f}, gb = ga;                      // g: cotangent of u_{k+1}, (own component, the partner's: MFMA register 1)
-    f2 una = ga, unb = ga;                              // u_{k+1} = rho_k yhat_k, (own, partner)
+    v2f ga = v2f{0.f, 0.f}, gb = ga;                      // g: cotangent of u_{k+1}, (own component, the partner's: MFMA register 1)
+    v2f una = ga, unb = ga;                              // u_{k+1} = rho_k yhat_k, (own, partner)
     float facca = 0.f, faccb = 0.f, accS = 0.f;
     unsigned ymxb = 0u;                                 // max |ybar| of this lane over the clip (float bits), for the gradient GEMM's scale
     float sda = 0.f, sdb = 0.f;                         // ((Q + s R^dagger) ybar) rows of the step before: its Abar term is added a step late
-    u4 o0, o1;                                          // the wave's own K-steps: [K half] (both pieces stacked in the A rows)
+    v4u o0, o1;                                          // the wave's own K-steps: [K half] (both pieces stacked in the A rows)
     float4 rh, rhp;
-    f4 S0, S1, SP0, SP1;
+    v4f S0, S1, SP0, SP1;
     float c3a, c3b;                                     // te_k (H y_k) - ok_k yhat_k rad_{k+1} inv_k
     float sS = 1.f, iS = 1.f;                           // the vector's scale of the step about to run, and its inverse
     auto rho_rows = [&](int k) { return *reinterpret_cast<const float4*>(&RS.row[(k / RCH) & 1][k & (RCH - 1)][ia]); };
     auto tab_row = [&](int k, int half) { return TB.row[w][(k / PCH) & 1][k & (PCH - 1)][q][half]; };
-    typedef unsigned u2b __attribute__((ext_vector_type(2)));
     auto row_at = [&](int k) {
         const int kc = k > 0 ? k : 0;
-        const u2b y = __builtin_amdgcn_raw_buffer_load_b64(rs_st, voff, kc * (8 * PD * 4), 0);
-        const u2b h = __builtin_amdgcn_raw_buffer_load_b64(rs_st, voff + 4 * PD * 4, kc * (8 * PD * 4), 0);
+        const v2u y = __builtin_amdgcn_raw_buffer_load_b64(rs_st, voff, kc * (8 * PD * 4), 0);
+        const v2u h = __builtin_amdgcn_raw_buffer_load_b64(rs_st, voff + 4 * PD * 4, kc * (8 * PD * 4), 0);
         return make_float4(__uint_as_float(y.x), __uint_as_float(y.y), __uint_as_float(h.x), __uint_as_float(h.y));
     };
     float4 ring0, ring1, ring2, ring3, ring4, ring5, ring6, ring7;
@@ -1676,11 +1637,11 @@ __global__ __launch_bounds__(2 * PD, 1) void k_bwd_chain16(Dev P, const float* _
         const float4 cur = row_at(k0);
         c3a = S0.w * cur.z;                             // rad_N = 0
         c3b = S0.w * cur.w;
-        sS = gg::pow2_scale(S1.z, 15);                  // ybar_{N-1} = c3_{N-1} (g = 0): its bound c_{N-1} (rad_N = 0)
+        sS = pow2_below(S1.z, 15);                  // ybar_{N-1} = c3_{N-1} (g = 0): its bound c_{N-1} (rad_N = 0)
         iS = __uint_as_float(0x7F000000u - __float_as_uint(sS));
     }
     const float2 psa = P.psi0[ia], psb = P.psi0[ib];
-    const f2 ps0a = odd ? f2{psa.y, psa.x} : f2{psa.x, psa.y}, ps0b = odd ? f2{psb.y, psb.x} : f2{psb.x, psb.y};   // u_0 = psi_0 (own, partner)
+    const v2f ps0a = odd ? v2f{psa.y, psa.x} : v2f{psa.x, psa.y}, ps0b = odd ? v2f{psb.y, psb.x} : v2f{psb.x, psb.y};   // u_0 = psi_0 (own, partner)
     const unsigned a_tab = lds_addr_of(&TB.row[w][0][0][q][0]);
     const unsigned a_ym = lds_addr_of(&ymx_tab[0][q][0][0]);        // + 64 parity: this clip's eight entries
     auto write_image = [&](int par, float xa, float xb) {
@@ -1725,19 +1686,19 @@ __global__ __launch_bounds__(2 * PD, 1) void k_bwd_chain16(Dev P, const float* _
         __builtin_amdgcn_sched_barrier(0);                                                                                         \
         C16_STAMP(1)                                                                                                               \
         /* ---- behind the stores: ybar out (for the gradient GEMM) ---- */                                                        \
-        __builtin_amdgcn_raw_buffer_store_b64(u2b{__float_as_uint(yba), __float_as_uint(ybb)}, rs_yb, voff, k * (4 * PD * 4), 0);   \
-        const f2 una_ = una, unb_ = unb, ga_ = ga, gb_ = gb;                                                                       \
+        __builtin_amdgcn_raw_buffer_store_b64(v2u{__float_as_uint(yba), __float_as_uint(ybb)}, rs_yb, voff, k * (4 * PD * 4), 0);   \
+        const v2f una_ = una, unb_ = unb, ga_ = ga, gb_ = gb;                                                                       \
         unsigned mbits = max(__float_as_uint(yba) & 0x7FFFFFFFu, __float_as_uint(ybb) & 0x7FFFFFFFu);     /* max |ybar| as float bits */ \
         __builtin_amdgcn_sched_barrier(0);                                                                                         \
         C16_STAMP_DEP(2, mbits)                                                                                                    \
         lds_barrier();                                                                                                             \
         C16_STAMP(3)                                                                                                               \
-        f4 cQ0, cQ1, cD0, cD1, nS0, nS1;                                                                                           \
-        u4 v[2 * KH - 2];                                                                                                          \
+        v4f cQ0, cQ1, cD0, cD1, nS0, nS1;                                                                                           \
+        v4u v[2 * KH - 2];                                                                                                          \
         float4 nrh;                                                                                                                \
-        f2 uka, ukb;                                                                                                               \
+        v2f uka, ukb;                                                                                                               \
         float ypa, ypb, pypa, pypb, pyba, pybb, sSn;                                                                         \
-        u4 ym[2];                                                                                                                  \
+        v4u ym[2];                                                                                                                  \
         const unsigned ax0 = a_tab + 64 * (((km2 / PCH) & 1) * PCH + (km2 & (PCH - 1)));                                           \
         const float invp = SP0.y;                                                                                                  \
         auto slot = [&](auto kidx_c, auto sl_c) {                                                                                  \
@@ -1754,12 +1715,12 @@ __global__ __launch_bounds__(2 * PD, 1) void k_bwd_chain16(Dev P, const float* _
             if constexpr (kidx == 0 && sl == 5) { pypb = partner16(ypb, odd); PAIR_PIN1(pypb); }                                   \
             if constexpr (kidx == 1 && sl == 1) {                                                                                  \
                 const float ria = sgn * rhp.y;                                                                                     \
-                uka = f2{rhp.x * ypa + ria * pypa, rhp.x * pypa - ria * ypa};                                                      \
+                uka = v2f{rhp.x * ypa + ria * pypa, rhp.x * pypa - ria * ypa};                                                      \
                 PAIR_PIN1(uka);                                                                                                    \
             }                                                                                                                      \
             if constexpr (kidx == 1 && sl == 3) {                                                                                  \
                 const float rib = sgn * rhp.w;                                                                                     \
-                ukb = f2{rhp.z * ypb + rib * pypb, rhp.z * pypb - rib * ypb};                                                      \
+                ukb = v2f{rhp.z * ypb + rib * pypb, rhp.z * pypb - rib * ypb};                                                      \
                 PAIR_PIN1(ukb);                                                                                                    \
             }                                                                                                                      \
             if constexpr (kidx == 1 && sl == 5) {                    /* the g-independent part of ybar_{k-1} and its bound */      \
@@ -1798,7 +1759,7 @@ __global__ __launch_bounds__(2 * PD, 1) void k_bwd_chain16(Dev P, const float* _
                 if constexpr (PWV > 2) mb = max(mb, max(ym[1].x, ym[1].y));                                                        \
                 if constexpr (PWV > 3) mb = max(mb, max(ym[1].z, ym[1].w));                                                        \
                 const float bnd = fmaf(SP1.w, fmaf(S1.w, __uint_as_float(mb), S1.z), SP1.z);    /* a_{k-1} (a_k Y_{k+1} + c_k) + c_{k-1} */ \
-                sSn = gg::pow2_scale(bnd, 15);                                                                                     \
+                sSn = pow2_below(bnd, 15);                                                                                     \
                 PAIR_PIN1(sSn);                                                                                                    \
             }                                                                                                                      \
         };                                                                                                                         \
@@ -1821,10 +1782,10 @@ __global__ __launch_bounds__(2 * PD, 1) void k_bwd_chain16(Dev P, const float* _
         if (k == 0) { uka = ps0a; ukb = ps0b; }                      /* u_0 = psi_0 */                                             \
         {   /* g = ybar + (Q + s R^dagger) ybar, (own, partner) pairs; the accumulators carry the scales sQ sS and sD sS */           \
             const float cq = iQ * iS, cd = S0.x * (iD * iS);                                                                       \
-            const f2 da = st_sum(cQ0) * cq + cd * st_sum(cD0);                                                                     \
-            const f2 db = st_sum(cQ1) * cq + cd * st_sum(cD1);                                                                     \
-            ga = f2{yba, pyba} + da;                                                                                               \
-            gb = f2{ybb, pybb} + db;                                                                                               \
+            const v2f da = st_sum(cQ0) * cq + cd * st_sum(cD0);                                                                     \
+            const v2f db = st_sum(cQ1) * cq + cd * st_sum(cD1);                                                                     \
+            ga = v2f{yba, pyba} + da;                                                                                               \
+            gb = v2f{ybb, pybb} + db;                                                                                               \
             sda = da.x; sdb = db.x;                                                                                                \
         }                                                                                                                          \
         sS = sSn;                                                                                                                  \

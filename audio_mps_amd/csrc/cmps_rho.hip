@@ -15,24 +15,9 @@
 //     yhb_a = conj(rho_k) g_a;  dot = sum_a Re(yhat_a^dagger yhb_a);  ybar_a = (yhb_a - yhat_a dot)/sqrt(n) + 2 ebar H y_a
 //     Rbar += 2 ebar sum_a y_a y_a^dagger + s sum_a ybar_a u_a^dagger;   Qbar += sum_a ybar_a u_a^dagger
 //     g_a  = ybar_a + Q ybar_a + s R^dagger ybar_a;   fbar += dt_k sum_a Im(g_a conj(u_a(k+1)))
-#include "cmps_internal.h"
+#include "cmps_lane_util.h"
 
 namespace cmps {
-
-template <int NT>
-__device__ __forceinline__ float rblock_sum(float v, float* red) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    constexpr int NW = NT / 64;
-    if constexpr (NW == 1) return v;
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float s = 0.f;
-#pragma unroll
-    for (int w = 0; w < NW; ++w) s += red[w];
-    __syncthreads();
-    return s;
-}
 
 // ------------------------------------------------------------------------------------------------
 // forward: RhoCMPS._build_loss_rho (model.py:133-144)
@@ -156,8 +141,8 @@ __global__ __launch_bounds__(NT) void k_fwd_rho(Dev P, RhoDev W, const float* __
                     }
             }
         }
-        const float e = rblock_sum<NT>(pe, red);                  // Re tr(x rho'), :195-196
-        const float n = rblock_sum<NT>(pn, red);                  // tr rho', :200
+        const float e = block_sum<NT>(pe, red);                  // Re tr(x rho'), :195-196
+        const float n = block_sum<NT>(pn, red);                  // tr rho', :200
         loss += -logf(1.0f + (e * x) / dev_A(P));                      // :166, 155
         const float sc = sqrtf(1.0f / fmaxf(n, 1e-12f));          // :201 (columns scale with the square root)
         if (act) {
@@ -208,7 +193,7 @@ __global__ __launch_bounds__(NT) void k_bwd_rho(Dev P, RhoDev W, const float* __
                 pn += y.x * y.x + y.y * y.y;
             }
         }
-        const float nraw = rblock_sum<NT>(pn, red);
+        const float nraw = block_sum<NT>(pn, red);
         const float inv = sqrtf(1.0f / fmaxf(nraw, 1e-12f));
         float pd = 0.f;
         if (act) {
@@ -223,7 +208,7 @@ __global__ __launch_bounds__(NT) void k_bwd_rho(Dev P, RhoDev W, const float* __
                 YB[a * D + t] = yhb;
             }
         }
-        const float dot = rblock_sum<NT>(pd, red);
+        const float dot = block_sum<NT>(pd, red);
         __syncthreads();
         float pe = 0.f;
         if (mact) {
@@ -252,7 +237,7 @@ __global__ __launch_bounds__(NT) void k_bwd_rho(Dev P, RhoDev W, const float* __
                     }
             }
         }
-        const float e = rblock_sum<NT>(pe, red);
+        const float e = block_sum<NT>(pe, red);
         const float ex = e * x;
         const float z = ex / dev_A(P);
         const float zbar = -1.0f / (1.0f + z);
@@ -283,7 +268,7 @@ __global__ __launch_bounds__(NT) void k_bwd_rho(Dev P, RhoDev W, const float* __
             }
         }
         if (k > 0) {
-            const float nprev = rblock_sum<NT>(pnp, red);
+            const float nprev = block_sum<NT>(pnp, red);
             const float invp = sqrtf(1.0f / fmaxf(nprev, 1e-12f));
             if (act) {
                 const float2 rhop = P.rho[(size_t)(k - 1) * DP + t];
@@ -319,7 +304,7 @@ __global__ __launch_bounds__(NT) void k_bwd_rho(Dev P, RhoDev W, const float* __
                     }
             }
         }
-        const float sbar = rblock_sum<NT>(ps, red);
+        const float sbar = block_sum<NT>(ps, red);
         Abar += sbar * (-x / (dev_A(P) * dev_A(P)));
 #pragma unroll
         for (int m = 0; m < EPT; ++m) {
@@ -399,14 +384,14 @@ __global__ __launch_bounds__(256) void k_states_rho(Dev P, RhoDev W, int steps, 
     const float2* st = W.stash + row * r * DP;
     const float* stw = reinterpret_cast<const float*>(W.stash) + row * r * 128;   // wave layout: [rank][64] (y own, H y own)
     auto ldY = [&](int a, int d) {
-        if (W.stash_layout == 3) {                          // the wide kernels' rows (cmps_wide.hip): one vector per pair of columns, lane order
+        if (W.stash_layout == RHO_STASH_WIDE) {                          // the wide kernels' rows (cmps_wide.hip): one vector per pair of columns, lane order
             const size_t vp = ((row / steps) * W.vrank + a) >> 1;
             const float* base = W.vstash + ((vp * steps + k) * 2) * (size_t)(4 * DP);
             const int p0 = 64 * (d >> 4) + 8 * ((((d & 15) >> 3) << 2) | (a & 1)) + (d & 7);
             return make_float2(base[p0], base[p0 + 16]);    // component bit = q bit 1 = + 16 lanes
         }
-        return W.stash_layout == 1 ? make_float2(stw[(a * 64 + d) * 2], stw[(a * 64 + d + 32) * 2])
-             : W.stash_layout == 2 ? make_float2(stw[(a * 64 + 2 * d) * 2], stw[(a * 64 + 2 * d + 1) * 2]) : st[a * DP + d];
+        return W.stash_layout == RHO_STASH_WAVE ? make_float2(stw[(a * 64 + d) * 2], stw[(a * 64 + d + 32) * 2])
+             : W.stash_layout == RHO_STASH_MFMA ? make_float2(stw[(a * 64 + 2 * d) * 2], stw[(a * 64 + 2 * d + 1) * 2]) : st[a * DP + d];
     };
     float pn = 0.f;
     for (int idx = t; idx < r * D; idx += 256) {
@@ -421,7 +406,7 @@ __global__ __launch_bounds__(256) void k_states_rho(Dev P, RhoDev W, int steps, 
         sincosf(th, &sn, &cs);
         ph[t] = make_float2(cs, sn);
     }
-    const float n = rblock_sum<256>(pn, red);
+    const float n = block_sum<256>(pn, red);
     const float inv = 1.0f / fmaxf(n, 1e-12f);
     __syncthreads();
     float pp = 0.f;
@@ -441,7 +426,7 @@ __global__ __launch_bounds__(256) void k_states_rho(Dev P, RhoDev W, int steps, 
             rho_out[(row * D * D + idx) * 2 + 1] = w.y;
         }
     }
-    const float pur = rblock_sum<256>(pp, red);
+    const float pur = block_sum<256>(pp, red);
     if (purity_out && t == 0) purity_out[row] = pur;
 }
 
@@ -533,7 +518,7 @@ __global__ __launch_bounds__(NT) void k_sample_rho(Dev P, RhoDev W, const float*
                 Wb[a * D + t] = cadd(u, q);
             }
         }
-        const float e = 2.0f * rblock_sum<NT>(pe, red);                            // Re tr((Rt + Rt^dagger) rho), :189-196
+        const float e = 2.0f * block_sum<NT>(pe, red);                            // Re tr((Rt + Rt^dagger) rho), :189-196
         const float inc = e * P.dt + noise[(size_t)b * length + k];                // :162
         samp += inc;                                                               // :163
         const float s = inc / dev_A(P);                                                 // :164, 175
@@ -547,7 +532,7 @@ __global__ __launch_bounds__(NT) void k_sample_rho(Dev P, RhoDev W, const float*
                 if (save) st[((size_t)k * r + a) * DP + t] = y;
             }
         }
-        const float n = rblock_sum<NT>(pn, red);
+        const float n = block_sum<NT>(pn, red);
         const float sc = sqrtf(1.0f / fmaxf(n, 1e-12f));                           // :165
         __syncthreads();
         if (act) {

@@ -11,7 +11,7 @@
 // e = sum_a y_a . (H y_a) and n = tr rho' = sum_a |y_a|^2 are whole-array sums; the rotation u_a' = rho_k (.) y_a / sqrt(n)
 // is lane-local in the C/D layout (a component's partner sits in the neighbouring lane: one DPP move).
 // One wavefront per clip; the row arrays live in LDS between steps (padded rows: conflict-free 32-row reads).
-// Stash (layout 2): per (step, column a < rank) one 512-B row of 64 pairs (y_a[n], (H y_a)[n]).
+// Stash (RHO_STASH_MFMA): per (step, column a < rank) one 512-B row of 64 pairs (y_a[n], (H y_a)[n]).
 #include "cmps_wave_util.h"
 
 namespace cmps {
@@ -20,17 +20,7 @@ namespace {
 
 constexpr int RRLD = 68;      // floats per row of the LDS row arrays: 64 + 4 of padding
 
-// exact three-way bf16 split of two floats (even element in the low half of every packed word)
-__device__ __forceinline__ void split3(float fe, float fo, unsigned& H, unsigned& M, unsigned& L) {
-    const unsigned xe = __float_as_uint(fe), xo = __float_as_uint(fo);
-    H = __builtin_amdgcn_perm(xo, xe, 0x07060302u);
-    const float re = fe - __uint_as_float(xe & 0xFFFF0000u), ro = fo - __uint_as_float(xo & 0xFFFF0000u);
-    const unsigned me = __float_as_uint(re), mo = __float_as_uint(ro);
-    M = __builtin_amdgcn_perm(mo, me, 0x07060302u);
-    const float le = re - __uint_as_float(me & 0xFFFF0000u), lo = ro - __uint_as_float(mo & 0xFFFF0000u);
-    L = __builtin_amdgcn_perm(__float_as_uint(lo), __float_as_uint(le), 0x07060302u);   // <= 8 bits left: exact
-}
-__device__ __forceinline__ bf8 frag4(const unsigned (&f)[4]) { return __builtin_bit_cast(bf8, v4u{f[0], f[1], f[2], f[3]}); }
+__device__ __forceinline__ bf16x8 frag4(const unsigned (&f)[4]) { return __builtin_bit_cast(bf16x8, v4u{f[0], f[1], f[2], f[3]}); }
 
 // acc += A B over the six piece pairs (hi,hi) (hi,mid) (mid,hi) (hi,lo) (lo,hi) (mid,mid)
 __device__ __forceinline__ void mfma6(v16f& acc, const unsigned (&AH)[4], const unsigned (&AM)[4], const unsigned (&AL)[4],
@@ -47,15 +37,13 @@ __device__ __forceinline__ void mfma6(v16f& acc, const unsigned (&AH)[4], const 
 // on v_mfma_f32_32x32x16_f16 instead of three bf16 pieces and six: the accuracy class of the split above at half the MFMAs and
 // 6 instead of 11 VALU per pair of values (cmps_grad_gemm.h).  fp16 has 5 exponent bits: the caller scales every
 // operand class by a power of two from a guaranteed bound and unscales the accumulators.
-typedef _Float16 hf8r __attribute__((ext_vector_type(8)));
 __device__ __forceinline__ void split2h(float fe, float fo, unsigned& H, unsigned& L) {
-    typedef _Float16 h2 __attribute__((ext_vector_type(2)));
     const h2 hh = h2{(_Float16)fe, (_Float16)fo};
     H = __builtin_bit_cast(unsigned, hh);
     const float re = fe - (float)hh.x, ro = fo - (float)hh.y;
     L = __builtin_bit_cast(unsigned, h2{(_Float16)re, (_Float16)ro});
 }
-__device__ __forceinline__ hf8r frag4h(const unsigned (&f)[4]) { return __builtin_bit_cast(hf8r, v4u{f[0], f[1], f[2], f[3]}); }
+__device__ __forceinline__ h8 frag4h(const unsigned (&f)[4]) { return __builtin_bit_cast(h8, v4u{f[0], f[1], f[2], f[3]}); }
 // acc += A B over the piece pairs (hi,hi) (hi,lo) (lo,hi)
 __device__ __forceinline__ void mfma3(v16f& acc, const unsigned (&AH)[4], const unsigned (&AL)[4], const unsigned (&BH)[4], const unsigned (&BL)[4]) {
     acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(frag4h(AH), frag4h(BH), acc, 0, 0, 0);
@@ -66,12 +54,7 @@ __device__ __forceinline__ void pieces8h(const float (&x)[16], int s2, float sc,
 #pragma unroll
     for (int e2 = 0; e2 < 4; ++e2) split2h(x[8 * s2 + 2 * e2] * sc, x[8 * s2 + 2 * e2 + 1] * sc, H[e2], L[e2]);
 }
-// the largest power of two S with bound S < 2^target (exponent clamped: S and 1 / S stay normal); 1 / S for such an S
-__device__ __forceinline__ float pow2_below(float bound, int target) {
-    int se = target - ((int)((__float_as_uint(bound) >> 23) & 0xFFu) - 126);
-    se = se > 60 ? 60 : se < -60 ? -60 : se;
-    return __uint_as_float((unsigned)(127 + se) << 23);
-}
+// 1 / S for a power of two S as pow2_below (cmps_lane_util.h) returns it
 __device__ __forceinline__ float pow2_recip(float s) { return __uint_as_float(0x7F000000u - __float_as_uint(s)); }
 __device__ __forceinline__ float max64(float x) {
 #pragma unroll
@@ -86,11 +69,9 @@ __device__ __forceinline__ float wform(float2 mij, int cp, int cc) { return cp =
 // pieces of eight registers x[8 s2 .. 8 s2 + 7] of a C/D tile as the K-fragment of k-step s2
 __device__ __forceinline__ void pieces8(const float (&x)[16], int s2, unsigned (&H)[4], unsigned (&M)[4], unsigned (&L)[4]) {
 #pragma unroll
-    for (int e2 = 0; e2 < 4; ++e2) split3(x[8 * s2 + 2 * e2], x[8 * s2 + 2 * e2 + 1], H[e2], M[e2], L[e2]);
+    for (int e2 = 0; e2 < 4; ++e2) split3_pk(x[8 * s2 + 2 * e2], x[8 * s2 + 2 * e2 + 1], H[e2], M[e2], L[e2]);
 }
-__device__ __forceinline__ float dpp_nb(float x) {      // the value of lane n ^ 1
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0xB1, 0xf, 0xf, true));
-}
+__device__ __forceinline__ float dpp_nb(float x) { return dpp_mov<0xB1>(x); }      // the value of lane n ^ 1
 
 }  // namespace
 
@@ -129,7 +110,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_fwd_rho_mfma(Dev P, RhoDev W,
             }
             if constexpr (!F16) {
 #pragma unroll
-                for (int e2 = 0; e2 < 4; ++e2) split3(wh[2 * e2], wh[2 * e2 + 1], HH[t][ks][e2], HM[t][ks][e2], HL[t][ks][e2]);
+                for (int e2 = 0; e2 < 4; ++e2) split3_pk(wh[2 * e2], wh[2 * e2 + 1], HH[t][ks][e2], HM[t][ks][e2], HL[t][ks][e2]);
             } else {
 #pragma unroll
                 for (int e = 0; e < 8; ++e) HWraw[t][ks][e] = wh[e];
@@ -218,10 +199,10 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_fwd_rho_mfma(Dev P, RhoDev W,
                     split2h(f1.x * sU, f1.y * sU, AH[2], AL[2]);
                     split2h(f1.z * sU, f1.w * sU, AH[3], AL[3]);
                 } else {
-                    split3(f0.x, f0.y, AH[0], AM[0], AL[0]);
-                    split3(f0.z, f0.w, AH[1], AM[1], AL[1]);
-                    split3(f1.x, f1.y, AH[2], AM[2], AL[2]);
-                    split3(f1.z, f1.w, AH[3], AM[3], AL[3]);
+                    split3_pk(f0.x, f0.y, AH[0], AM[0], AL[0]);
+                    split3_pk(f0.z, f0.w, AH[1], AM[1], AL[1]);
+                    split3_pk(f1.x, f1.y, AH[2], AM[2], AL[2]);
+                    split3_pk(f1.z, f1.w, AH[3], AM[3], AL[3]);
                 }
 #pragma unroll
                 for (int t = 0; t < 2; ++t) {
@@ -230,7 +211,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_fwd_rho_mfma(Dev P, RhoDev W,
                     for (int e2 = 0; e2 < 4; ++e2) {
                         const float we = fmaf(s, WR[t][ks][2 * e2], WQ[t][ks][2 * e2]), wo = fmaf(s, WR[t][ks][2 * e2 + 1], WQ[t][ks][2 * e2 + 1]);
                         if constexpr (F16) split2h(we, wo, BH[e2], BL[e2]);       // (W_Q, W_R carry the scale sW)
-                        else split3(we, wo, BH[e2], BM[e2], BL[e2]);
+                        else split3_pk(we, wo, BH[e2], BM[e2], BL[e2]);
                     }
                     if constexpr (F16) mfma3(t ? a1 : a0, AH, AL, BH, BL);
                     else mfma6(t ? a1 : a0, AH, AM, AL, BH, BM, BL);
@@ -264,10 +245,10 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_fwd_rho_mfma(Dev P, RhoDev W,
                     mfma3(h0, AH, AL, HH[0][ks], HL[0][ks]);
                     mfma3(h1, AH, AL, HH[1][ks], HL[1][ks]);
                 } else {
-                    split3(f0.x, f0.y, AH[0], AM[0], AL[0]);
-                    split3(f0.z, f0.w, AH[1], AM[1], AL[1]);
-                    split3(f1.x, f1.y, AH[2], AM[2], AL[2]);
-                    split3(f1.z, f1.w, AH[3], AM[3], AL[3]);
+                    split3_pk(f0.x, f0.y, AH[0], AM[0], AL[0]);
+                    split3_pk(f0.z, f0.w, AH[1], AM[1], AL[1]);
+                    split3_pk(f1.x, f1.y, AH[2], AM[2], AL[2]);
+                    split3_pk(f1.z, f1.w, AH[3], AM[3], AL[3]);
                     mfma6(h0, AH, AM, AL, HH[0][ks], HM[0][ks], HL[0][ks]);
                     mfma6(h1, AH, AM, AL, HH[1][ks], HM[1][ks], HL[1][ks]);
                 }
@@ -497,17 +478,17 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_bwd_rho_mfma(Dev P, RhoDev W,
                 const float4 f0 = *reinterpret_cast<const float4*>(Bw + col * RRLD + 16 * ks + 8 * hk);
                 const float4 f1 = *reinterpret_cast<const float4*>(Bw + col * RRLD + 16 * ks + 8 * hk + 4);
                 unsigned AH[4], AM[4], AL[4];
-                split3(f0.x, f0.y, AH[0], AM[0], AL[0]);
-                split3(f0.z, f0.w, AH[1], AM[1], AL[1]);
-                split3(f1.x, f1.y, AH[2], AM[2], AL[2]);
-                split3(f1.z, f1.w, AH[3], AM[3], AL[3]);
+                split3_pk(f0.x, f0.y, AH[0], AM[0], AL[0]);
+                split3_pk(f0.z, f0.w, AH[1], AM[1], AL[1]);
+                split3_pk(f1.x, f1.y, AH[2], AM[2], AL[2]);
+                split3_pk(f1.z, f1.w, AH[3], AM[3], AL[3]);
 #pragma unroll
                 for (int t = 0; t < 2; ++t) {
                     unsigned BH[4], BM[4], BL[4];
 #pragma unroll
                     for (int e2 = 0; e2 < 4; ++e2) {
                         const int v = (t * 4 + ks) * 8 + 2 * e2;
-                        split3(fmaf(s, WDs[v * 64 + lane], WQs[v * 64 + lane]),
+                        split3_pk(fmaf(s, WDs[v * 64 + lane], WQs[v * 64 + lane]),
                                fmaf(s, WDs[(v + 1) * 64 + lane], WQs[(v + 1) * 64 + lane]), BH[e2], BM[e2], BL[e2]);
                     }
                     mfma6(t ? m1 : m0, AH, AM, AL, BH, BM, BL);
@@ -547,10 +528,10 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_bwd_rho_mfma(Dev P, RhoDev W,
                     const int ra = (qa & 3) + 8 * (qa >> 2) + 4 * hk, rb = (qb & 3) + 8 * (qb >> 2) + 4 * hk;
                     const float a0 = Bw[ra * RRLD + col], b0 = Bw[rb * RRLD + col];
                     const float a1 = Bw[ra * RRLD + 32 + col], b1 = Bw[rb * RRLD + 32 + col];
-                    split3(a0, b0, YH[0][e2], YM[0][e2], YL[0][e2]);
-                    split3(a1, b1, YH[1][e2], YM[1][e2], YL[1][e2]);
-                    split3(s * a0, s * b0, SH[0][e2], SM[0][e2], SL[0][e2]);
-                    split3(s * a1, s * b1, SH[1][e2], SM[1][e2], SL[1][e2]);
+                    split3_pk(a0, b0, YH[0][e2], YM[0][e2], YL[0][e2]);
+                    split3_pk(a1, b1, YH[1][e2], YM[1][e2], YL[1][e2]);
+                    split3_pk(s * a0, s * b0, SH[0][e2], SM[0][e2], SL[0][e2]);
+                    split3_pk(s * a1, s * b1, SH[1][e2], SM[1][e2], SL[1][e2]);
                 }
 #pragma unroll
                 for (int tb = 0; tb < 2; ++tb) {
@@ -595,7 +576,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_bwd_rho_mfma(Dev P, RhoDev W,
             }
     // fbar_i: sum over the rows of this lane (both halves) and over the lane pair of component i
     {
-        const float f0 = swapadd(facc0, facc0), f1 = swapadd(facc1, facc1);           // + the other half's rows
+        const float f0 = swap32_add(facc0, facc0), f1 = swap32_add(facc1, facc1);           // + the other half's rows
         const float t0 = f0 + dpp_nb(f0), t1 = f1 + dpp_nb(f1);
         if (hk == 0 && (col & 1) == 0) {
             slab[4 * DD + (col >> 1)] = t0;
@@ -621,7 +602,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_bwd_rho_mfma(Dev P, RhoDev W,
 // path.  The sample needs the expectation BEFORE the update, so a step is  V = U W_R  and  QU = U W_Q  (constant operands:
 // their bf16 pieces are split once), then  e = 2 sum U . V  (= Re tr((R + R^dagger) rho), :189-196),  inc = e dt + noise,
 // s = inc / A,  Y = (U + QU) + s V,  n = sum Y^2,  U' = rho_k (.) Y / sqrt(n).  Noise is [n_paths][length] (one 64-step chunk
-// per lane load), the waveform is written back the same way.  Stash (save): layout 2 rows of (y[n], 0).
+// per lane load), the waveform is written back the same way.  Stash (save): RHO_STASH_MFMA rows of (y[n], 0).
 // ------------------------------------------------------------------------------------------------
 template <bool SAVE, bool F16>
 __global__ __launch_bounds__(64 * WAVES, 1) void k_sample_rho_mfma(Dev P, RhoDev W, const float* __restrict__ noise, int n_paths,
@@ -667,8 +648,8 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_sample_rho_mfma(Dev P, RhoDev
                     split2h(wr[2 * e2] * sR, wr[2 * e2 + 1] * sR, RH[t][ks][e2], RL[t][ks][e2]);
                     split2h(wq[2 * e2] * sQ, wq[2 * e2 + 1] * sQ, QH[t][ks][e2], QL[t][ks][e2]);
                 } else {
-                    split3(wr[2 * e2], wr[2 * e2 + 1], RH[t][ks][e2], RM[t][ks][e2], RL[t][ks][e2]);
-                    split3(wq[2 * e2], wq[2 * e2 + 1], QH[t][ks][e2], QM[t][ks][e2], QL[t][ks][e2]);
+                    split3_pk(wr[2 * e2], wr[2 * e2 + 1], RH[t][ks][e2], RM[t][ks][e2], RL[t][ks][e2]);
+                    split3_pk(wq[2 * e2], wq[2 * e2 + 1], QH[t][ks][e2], QM[t][ks][e2], QL[t][ks][e2]);
                 }
             }
         }
@@ -710,10 +691,10 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_sample_rho_mfma(Dev P, RhoDev
                     mfma3(q0, AH, AL, QH[0][ks], QL[0][ks]);
                     mfma3(q1, AH, AL, QH[1][ks], QL[1][ks]);
                 } else {
-                    split3(f0.x, f0.y, AH[0], AM[0], AL[0]);
-                    split3(f0.z, f0.w, AH[1], AM[1], AL[1]);
-                    split3(f1.x, f1.y, AH[2], AM[2], AL[2]);
-                    split3(f1.z, f1.w, AH[3], AM[3], AL[3]);
+                    split3_pk(f0.x, f0.y, AH[0], AM[0], AL[0]);
+                    split3_pk(f0.z, f0.w, AH[1], AM[1], AL[1]);
+                    split3_pk(f1.x, f1.y, AH[2], AM[2], AL[2]);
+                    split3_pk(f1.z, f1.w, AH[3], AM[3], AL[3]);
                     mfma6(v0, AH, AM, AL, RH[0][ks], RM[0][ks], RL[0][ks]);
                     mfma6(v1, AH, AM, AL, RH[1][ks], RM[1][ks], RL[1][ks]);
                     mfma6(q0, AH, AM, AL, QH[0][ks], QM[0][ks], QL[0][ks]);

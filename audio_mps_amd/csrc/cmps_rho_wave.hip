@@ -83,12 +83,12 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_fwd_rho_wave(Dev P, RhoDev W,
                 mv2_lo(MR, MQ, q, av, aq);
                 mv2_hi(MR, MQ, q, av, aq);
                 const v2f wp = aq + s * av;
-                const float y = u + swapadd(wp.x, wp.y);         // column of U rho U^dagger, :186
+                const float y = u + swap32_add(wp.x, wp.y);         // column of U rho U^dagger, :186
                 Yb[w][a][lane] = y;
                 accn += y * y;
                 bcast(aUw, aUr, y, q);
                 const v2f ah = mv1(MH, q);
-                const float hs = swapadd(ah.x, ah.y);            // ((Rt + Rt^dagger) y_a), :193-194
+                const float hs = swap32_add(ah.x, ah.y);            // ((Rt + Rt^dagger) y_a), :193-194
                 acce += y * hs;
                 if (SAVE) st[((size_t)(kbeg + kk) * r + a) * 64] = make_float2(y, hs);
             }
@@ -138,9 +138,9 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_bwd_rho_wave(Dev P, RhoDev W,
     const unsigned aBw = lds_addr(&bcB[w][0]) + i * 8 + h * 4, aBr = lds_addr(&bcB[w][0]) + h * 128;
     const float4* rho4 = reinterpret_cast<const float4*>(P.rho);
     const float* xrow = audio + (size_t)b * T;
-    // stash rows of 64 pairs (y, H y): in lane order (layout 1, k_fwd_rho_wave) or per real component n = 2 i + {re, im}
-    // (layout 2, k_fwd_rho_mfma)
-    const float2* st = reinterpret_cast<const float2*>(W.stash) + (size_t)b * N * r * 64 + (W.stash_layout == 2 ? 2 * i + h : lane);
+    // stash rows of 64 pairs (y, H y): in lane order (RHO_STASH_WAVE, k_fwd_rho_wave) or per real component n = 2 i + {re, im}
+    // (RHO_STASH_MFMA, k_fwd_rho_mfma)
+    const float2* st = reinterpret_cast<const float2*>(W.stash) + (size_t)b * N * r * 64 + (W.stash_layout == RHO_STASH_MFMA ? 2 * i + h : lane);
     const float* sc = W.scal + (size_t)b * NC * 128;
     const float A = dev_A(P);
     for (int a = 0; a < r; ++a) G[w][a][lane] = 0.f;
@@ -204,7 +204,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_bwd_rho_wave(Dev P, RhoDev W,
                 v2f ad, aq;
                 mv2_lo(MD, MQ, q, ad, aq);
                 mv2_hi(MD, MQ, q, ad, aq);
-                const float d = swapadd(ad.x, ad.y), bq = swapadd(aq.x, aq.y);
+                const float d = swap32_add(ad.x, ad.y), bq = swap32_add(aq.x, aq.y);
                 // u_a(k) = rho_{k-1} y_a(k-1) / sqrt(tr)  (the initial column at k = 0)
                 float uk, uko;
                 if (k > 0) {
@@ -246,7 +246,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_bwd_rho_wave(Dev P, RhoDev W,
         slab[2 * DD + o] = Qre[rr];
         slab[3 * DD + o] = -Qim[rr];
     }
-    const float ftot = swapadd(facc, facc);
+    const float ftot = swap32_add(facc, facc);
     if (!hb) slab[4 * DD + i] = ftot;
     float* tail = slab + 4 * DD + 3 * DPW + 2;
     for (int a = 0; a < r; ++a) tail[(hb ? r + a : a) * DPW + i] = G[w][a][lane];
@@ -270,7 +270,7 @@ hipError_t launch_bwd_rho_wave(const Dev& P, const RhoDev& W, const float* audio
 }
 
 // ------------------------------------------------------------------------------------------------
-// Round 5: the reverse sweep of the row-array forward (k_fwd_rho_mfma, stash layout 2) as the PURE-STATE wave reverse scan on virtual
+// Round 5: the reverse sweep of the row-array forward (k_fwd_rho_mfma, RHO_STASH_MFMA) as the PURE-STATE wave reverse scan on virtual
 // clips.  Given the clip's per-step scalars (tr rho'_k, e_k: RhoDev::scal) the cotangents of the columns do not couple -- the
 // normalisation adjoint's radial part is te_{k+1} e_{k+1} for every column (Euler, as in k_bwd_wave) -- so column a of clip b is clip
 // b rank + a of k_bwd_wave (cmps_wave.hip; Dev::phi0 switches the indexing), whose cost is linear in the rank and whose rank-1 sums
@@ -300,7 +300,7 @@ hipError_t launch_bwd_rho_virtual_wave(const Dev& P, const RhoDev& W, const floa
     V.B = P.B * W.rank;
     V.hst = reinterpret_cast<float*>(W.stash);
     V.stash = W.stash;
-    V.stash_layout = 3;
+    V.stash_layout = STASH_WAVE32;
     V.scal = W.scal;
     V.slabs = W.wslabs;
     V.sums = W.wsums;

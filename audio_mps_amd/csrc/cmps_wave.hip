@@ -157,7 +157,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_bwd_wave(Dev P, const float* 
         const int idx = c * CH + lane;
         const float inc = ra1 - ra0;
         const float nv = rnv, ev = rev;
-        const float invv = rsq_nr(fmaxf(nv, 1e-12f));
+        const float invv = rsq_newton(fmaxf(nv, 1e-12f));
         const float invokv = nv > 1e-12f ? invv : 0.f;
         if constexpr (LEGACY) {
             const float tev = idx < N ? 2.0f * (ev - inc) : 0.f;              // te_k = 2 ebar_k, ebar_k = e_k - x_k
@@ -313,7 +313,6 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_bwd_wave(Dev P, const float* 
     float fsave[7], hold_e[7], hold_o[7];
     auto split_pair = [&](int v, int reg, float ve, float vo) {
         if constexpr (RANK1 == 3) {
-            typedef _Float16 h2 __attribute__((ext_vector_type(2)));
             const float sc2 = (v == 0 || v == 2) ? sR : v == 1 ? sQ : SB16;
             const float te_ = ve * sc2, to_ = vo * sc2;
             unsigned hi, lo;
@@ -339,7 +338,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_bwd_wave(Dev P, const float* 
             // at most 8 significand bits are left: the truncation to bf16 is exact
             fL[v][reg] = __builtin_amdgcn_perm(__float_as_uint(l3.y), __float_as_uint(l3.x), 0x07060302u);
         } else {
-            fL[v][reg] = __builtin_bit_cast(unsigned, __builtin_convertvector(lo, bf2));
+            fL[v][reg] = __builtin_bit_cast(unsigned, __builtin_convertvector(lo, bf16x2));
         }
     };
     // Slots 7 and 6 of an octet are held raw and split only at slot 4: fragment register 3 of the PREVIOUS octet then stays
@@ -373,12 +372,11 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_bwd_wave(Dev P, const float* 
         for (int r = 0; r < 4; ++r) { fH[v][r] = 0u; fL[v][r] = 0u; if constexpr (RANK1 == 2) fM[v][r] = 0u; }
     }
     constexpr int PER_PAIR = RANK1 == 2 ? 6 : 3, UNITS = 6 * PER_PAIR, PER_HOOK = RANK1 == 2 ? 2 : 1;
-    typedef _Float16 hf8 __attribute__((ext_vector_type(8)));
     // hook points of a step: A-points 0..5 (both modes) and B-points 0..5 (BF16X3 only): point q = 0..17 over the three steps
     // issues unit q (BF16X2) or unit 2 q at the A-point and unit 2 q + 1 at the B-point (BF16X3): never two MFMAs in a row
     auto mf_unit = [&](auto usel) {
         constexpr int U = decltype(usel)::value, PR = U / PER_PAIR, K = U % PER_PAIR;
-        auto frag = [&](const unsigned (&f)[4]) { return __builtin_bit_cast(bf8, v4u{f[0], f[1], f[2], f[3]}); };
+        auto frag = [&](const unsigned (&f)[4]) { return __builtin_bit_cast(bf16x8, v4u{f[0], f[1], f[2], f[3]}); };
         auto piece = [&](auto which, int idx) -> const unsigned (&)[4] {        // 0 hi, 1 second 8 bits, 2 third 8 bits
             constexpr int W = decltype(which)::value;
             if constexpr (W == 0) return fH[idx];
@@ -390,8 +388,8 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_bwd_wave(Dev P, const float* 
         constexpr int WB = K == 0 ? 0 : K == 1 ? 1 : K == 2 ? 0 : K == 3 ? 2 : K == 4 ? 0 : 1;
         auto mf = [&](v16f& acc, int ia, int ib) {
             if constexpr (RANK1 == 3)
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(hf8, frag(piece(std::integral_constant<int, WA>{}, ia))),
-                                                             __builtin_bit_cast(hf8, frag(piece(std::integral_constant<int, WB>{}, ib))), acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h8, frag(piece(std::integral_constant<int, WA>{}, ia))),
+                                                             __builtin_bit_cast(h8, frag(piece(std::integral_constant<int, WB>{}, ib))), acc, 0, 0, 0);
             else
                 acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag(piece(std::integral_constant<int, WA>{}, ia)),
                                                               frag(piece(std::integral_constant<int, WB>{}, ib)), acc, 0, 0, 0);
@@ -596,7 +594,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_bwd_wave(Dev P, const float* 
     const float sumS = sum64(accS);
     const float sumA = av == 0 ? sum64(accA) : 0.f;        // (z = e x / A belongs to the clip: counted with its first column)
     // fbar_i = sum_k dtk Im(g conj(u)) = sum over both halves of g_osig * u_own (the sign lives in osig)
-    const float ftot = swapadd(facc, facc);               // half 0: f(h=0) + f(h=1)
+    const float ftot = swap32_add(facc, facc);               // half 0: f(h=0) + f(h=1)
     slab[4 * DD + (hb ? 2 * DPW : DPW) + i] = g;          // cotangent of psi_0: re in [DPW, 2DPW), im in [2DPW, 3DPW)
     if (!hb) slab[4 * DD + i] = ftot;
     if (lane == 0) {
@@ -700,8 +698,8 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_sample_wave(Dev P, const floa
             mv2r_lo(MR, MQ, qu, av, aq, xsq);
             lds_wait_hi_t<0>(qu, rho);
             mv2r_hi(MR, MQ, qu, av, aq, xsq, nprev);                 // nprev = |y_{k-1}|^2
-            const float vs = swapadd(av.x, av.y), qs = swapadd(aq.x, aq.y);
-            const float inv = rsq_nr(fmaxf(nprev, 1e-12f));          // :289 of the step before
+            const float vs = swap32_add(av.x, av.y), qs = swap32_add(aq.x, aq.y);
+            const float inv = rsq_newton(fmaxf(nprev, 1e-12f));          // :289 of the step before
             const float e = 2.0f * (sum64(u * vs) * inv) * inv;      // _expectation on the normalised state (model.py:319-325)
             const float inc = e * dt + rdlane(nz, kk);               // model.py:286
             samp += inc;                                             // :287

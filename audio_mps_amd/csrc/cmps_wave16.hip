@@ -31,20 +31,9 @@ constexpr int BROW = 256;          // reverse ring: bytes of one row (64 floats)
 constexpr int BSLOT = 3 * BROW;    // ybar | yhat | u_k of one step
 constexpr int BHALF = 8 * BSLOT;   // one octet
 
-typedef float v4acc __attribute__((ext_vector_type(4)));
-
 #ifndef POLL_SLEEP
 #define POLL_SLEEP 1
 #endif
-
-__device__ __forceinline__ int flag_load16(unsigned addr) {
-    int v;
-    asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(addr) : "memory");
-    return __builtin_amdgcn_readfirstlane(v);
-}
-__device__ __forceinline__ void flag_store16(unsigned addr, int v, int lane) {
-    if (lane == 0) asm volatile("ds_write_b32 %0, %1" : : "v"(addr), "v"(v) : "memory");
-}
 
 // ---- 16-row mat-vec: this quarter's four columns, one chain of 8 packed FMAs ----
 __device__ __forceinline__ v2f mv16(const v2f (&M)[4], const v4f (&q)[2]) {
@@ -226,7 +215,7 @@ __global__ __launch_bounds__(128, 1) void k_fwd_wave16(Dev P, const float* __res
                 xa1 = idx + 1 < T ? xrow[idx + 1] : 0.f;
             }
             if (c >= 2)                                               // the ring half about to be overwritten
-                while (flag_load16(aCons) < c - 1) __builtin_amdgcn_s_sleep(POLL_SLEEP);
+                while (flag_load(aCons) < c - 1) __builtin_amdgcn_s_sleep(POLL_SLEEP);
             unsigned ay = aYw + (c & 1) * (CH16 * 128);
             for (int kk = 0; kk < cnt; ++kk) {
                 wait16_t<0>(qu, rho);
@@ -262,7 +251,7 @@ __global__ __launch_bounds__(128, 1) void k_fwd_wave16(Dev P, const float* __res
             tC = 0;                                                    // the chunk hand-over is not a step
 #endif
             wait16_t<0>(qu, rho);                                      // everything of this chunk has landed
-            flag_store16(aProd, c + 1, lane);                          // publish (ordered behind the chunk's y rows)
+            flag_store(aProd, c + 1, lane);                          // publish (ordered behind the chunk's y rows)
             if (c + 1 < NC2) {
                 stage_commit<4>(stR, lane, sr);
                 sv = (xa1 - xa0) / A;
@@ -309,7 +298,7 @@ __global__ __launch_bounds__(128, 1) void k_fwd_wave16(Dev P, const float* __res
         const int idx = kbeg + lane;
         const float x0 = idx < T ? xrow[idx] : 0.f;
         const float x1 = idx + 1 < T ? xrow[idx + 1] : 0.f;
-        while (flag_load16(aProd) < c + 1) __builtin_amdgcn_s_sleep(POLL_SLEEP);
+        while (flag_load(aProd) < c + 1) __builtin_amdgcn_s_sleep(POLL_SLEEP);
         const unsigned off = (c & 1) * (CH16 * 128);
         const int last = cnt - 1;
         rows16_own(aYr + off, aYo + off, qa, ya);
@@ -330,7 +319,7 @@ __global__ __launch_bounds__(128, 1) void k_fwd_wave16(Dev P, const float* __res
         }
 #undef LOSS16_STEP
         wait16_own<0>(qa, ya);
-        flag_store16(aCons, c + 1, lane);                              // every ring read has landed: the half is free
+        flag_store(aCons, c + 1, lane);                              // every ring read has landed: the half is free
         // e_k = 1/2 the sum over the 64 lanes of the stored products (every component is held twice)
         float evec;
         {
@@ -346,7 +335,7 @@ __global__ __launch_bounds__(128, 1) void k_fwd_wave16(Dev P, const float* __res
                 a3 += col[(l + 3) * PE16_LD];
             }
             const float part = (a0 + a1) + (a2 + a3);
-            evec = 0.5f * swapadd(part, part);
+            evec = 0.5f * swap32_add(part, part);
         }
         const float incv = x1 - x0;
         const float z = (evec * incv) / A;                             // model.py:294 operation order
@@ -412,7 +401,7 @@ __global__ __launch_bounds__(128, 1) void k_bwd_wave16(Dev P, const float* __res
             const float inc = ra1 - ra0;
             const float svv = inc / A;
             const float nv = rnv, ev = rev;
-            const float invv = rsq_nr(fmaxf(nv, 1e-12f));
+            const float invv = rsq_newton(fmaxf(nv, 1e-12f));
             const float invokv = nv > 1e-12f ? invv : 0.f;
             const float ex = ev * inc;                      // model.py:294 operation order
             const float z = ex / A;
@@ -564,10 +553,10 @@ __global__ __launch_bounds__(128, 1) void k_bwd_wave16(Dev P, const float* __res
                     BWD16_STEP(0, aW, aR, aL)
                 }
                 wait16<0>(qc);
-                flag_store16(aProd, otop - oup + 1, lane);
+                flag_store(aProd, otop - oup + 1, lane);
                 const int qd = otop - oup + 1;
                 if (qd >= 2)
-                    while (flag_load16(aCons) < qd - 1) __builtin_amdgcn_s_sleep(POLL_SLEEP);
+                    while (flag_load(aCons) < qd - 1) __builtin_amdgcn_s_sleep(POLL_SLEEP);
                 const unsigned aW = aWb + hd, aR = aRb + hd, aL = aLb + hd;
                 BWD16_STEP(7, aW, aR, aL) BWD16_STEP(6, aW, aR, aL) BWD16_STEP(5, aW, aR, aL) BWD16_STEP(4, aW, aR, aL)
                 BWD16_STEP(3, aW, aR, aL) BWD16_STEP(2, aW, aR, aL) BWD16_STEP(1, aW, aR, aL)
@@ -579,7 +568,7 @@ __global__ __launch_bounds__(128, 1) void k_bwd_wave16(Dev P, const float* __res
         {   // step 0: u_0 = psi_0; slot 0 of octet 0
             S = chain_step(S, u0, std::false_type{}, true, std::integral_constant<int, 0>{}, aWb, aRb, aLb);
             wait16<0>(qc);
-            flag_store16(aProd, otop + 1, lane);
+            flag_store(aProd, otop + 1, lane);
         }
 #if W16_ON
         if (blockIdx.x == 0 && lane == 0) {
@@ -592,7 +581,7 @@ __global__ __launch_bounds__(128, 1) void k_bwd_wave16(Dev P, const float* __res
 #endif
         const float sumS = 0.5f * sum64(accS);                // every component is held twice
         const float sumA = sum64(accA);                       // one step per lane: no duplication
-        const float ftot = swapadd(facc, facc);               // half 0: f(Re lane) + f(Im lane)
+        const float ftot = swap32_add(facc, facc);               // half 0: f(Re lane) + f(Im lane)
         if ((q & 1) == 0) {
             slab[4 * DD + (hb ? 2 * SD : SD) + i] = g;        // cotangent of psi_0
             if (!hb) slab[4 * DD + i] = ftot;
@@ -608,7 +597,7 @@ __global__ __launch_bounds__(128, 1) void k_bwd_wave16(Dev P, const float* __res
     // Rbar += 2 ebar y y^dagger + s ybar u^dagger ;  Qbar += ybar u^dagger as exact fp32 16x16x4 MFMAs: lane (i, q) feeds
     // A[i][k = q] / B[k = q][j = i]; k = q is {re, im} (q & 2: the split16 layout) x {step k, step k-1} (q & 1: the two holders
     // of a component carry the two steps of a pair).  Re(a b^dagger): B = b; Im(a b^dagger): B = -b_osig (sign at the end).
-    v4acc Rre = {}, Rim = {}, Qre = {}, Qim = {};
+    v4f Rre = {}, Rim = {}, Qre = {}, Qim = {};
     {
         float ra0 = 0.f, ra1 = 0.f, rnv = 1.f, rev = 0.f, sv = 0.f, tenv = 0.f;
         auto scal_load = [&](int c) {
@@ -641,7 +630,7 @@ __global__ __launch_bounds__(128, 1) void k_bwd_wave16(Dev P, const float* __res
                 scal_commit(cc);
                 if (cc > 0) scal_load(cc - 1);
             }
-            while (flag_load16(aProd) < otop - o + 1) __builtin_amdgcn_s_sleep(POLL_SLEEP);
+            while (flag_load(aProd) < otop - o + 1) __builtin_amdgcn_s_sleep(POLL_SLEEP);
             const unsigned aRd = aRing + (o & 1) * BHALF + lane * 4, aRd0 = aRing + (o & 1) * BHALF + i * 8 + hq * 4;
             const int kb = (o * 8) & 63;
             ring16_read3<7 * BSLOT>(aRd0, aRd, yb, yh, uk);
@@ -670,7 +659,7 @@ __global__ __launch_bounds__(128, 1) void k_bwd_wave16(Dev P, const float* __res
             GRAD16_STEP(3, yb, yh, uk, ybn, yhn, ukn) GRAD16_STEP(2, ybn, yhn, ukn, yb, yh, uk)
             GRAD16_STEP(1, yb, yh, uk, ybn, yhn, ukn) GRAD16_STEP(0, ybn, yhn, ukn, yb, yh, uk)
 #undef GRAD16_STEP
-            flag_store16(aCons, otop - o + 1, lane);
+            flag_store(aCons, otop - o + 1, lane);
         }
     }
 #pragma unroll

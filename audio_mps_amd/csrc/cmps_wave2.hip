@@ -40,17 +40,6 @@ constexpr int RLD = 68;          // floats per ring row: 64 (y_k as n = 2 i + {r
 constexpr int PE2_LD = 36;       // row stride (floats) of the loss wave's product buffer [step][column]: 16-B aligned rows, the
                                  // 32 rows read at one offset fall into distinct banks
 
-// progress counters in LDS, accessed with explicit DS instructions (a `volatile int*` cast would decay to a generic
-// pointer: flat accesses plus a vmcnt(0) wait that also drains the stash stores)
-__device__ __forceinline__ int flag_load(unsigned addr) {
-    int v;
-    asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(addr) : "memory");
-    return __builtin_amdgcn_readfirstlane(v);
-}
-__device__ __forceinline__ void flag_store(unsigned addr, int v, int lane) {
-    if (lane == 0) asm volatile("ds_write_b32 %0, %1" : : "v"(addr), "v"(v) : "memory");
-}
-
 // this half's 16 entries of a ring row and the lane's own value
 __device__ __forceinline__ void rows_own_issue(unsigned rd, unsigned own, v4f (&o)[8], float& mine) {
     asm volatile("ds_read_b128 %0, %9\n\tds_read_b128 %1, %9 offset:16\n\t"
@@ -291,25 +280,13 @@ __global__ __launch_bounds__(128 * WAVES, 1) void k_fwd_wave2(Dev P, const float
     // ---------------------------------------------------------------------- loss wave
     if (DIAG_NO_LOSS) return;
     __builtin_amdgcn_s_setprio(0);
-    // exact three-way bf16 split of two floats (even element in the low half of every packed word)
-    auto split3 = [](float fe, float fo, unsigned& H, unsigned& M, unsigned& L) {
-        const unsigned xe = __float_as_uint(fe), xo = __float_as_uint(fo);
-        H = __builtin_amdgcn_perm(xo, xe, 0x07060302u);
-        const float re = fe - __uint_as_float(xe & 0xFFFF0000u), ro = fo - __uint_as_float(xo & 0xFFFF0000u);
-        const unsigned me = __float_as_uint(re), mo = __float_as_uint(ro);
-        M = __builtin_amdgcn_perm(mo, me, 0x07060302u);
-        const float le = re - __uint_as_float(me & 0xFFFF0000u), lo = ro - __uint_as_float(mo & 0xFFFF0000u);
-        L = __builtin_amdgcn_perm(__float_as_uint(lo), __float_as_uint(le), 0x07060302u);   // <= 8 bits left: exact
-    };
-    auto frag = [](const unsigned (&f)[4]) { return __builtin_bit_cast(bf8, v4u{f[0], f[1], f[2], f[3]}); };
+    auto frag = [](const unsigned (&f)[4]) { return __builtin_bit_cast(bf16x8, v4u{f[0], f[1], f[2], f[3]}); };
     // B operand: W[m][n], the real 64 x 64 form of H = R + R^dagger acting on (re, im)-interleaved vectors,
     //   (H y)[n = 2 i + c] = sum_m y[m = 2 j + c'] W[m][n]:  W = Hr_ij for c' = c,  -Hi_ij for (c', c) = (1, 0),  +Hi_ij for (0, 1).
     // Lane (col = lane & 31, hk = lane >> 5) holds W[16 s + 8 hk + e][32 t + col], e = 0..7, for tile t and k-step s.
-    typedef _Float16 hf8 __attribute__((ext_vector_type(8)));
-    typedef _Float16 hf2 __attribute__((ext_vector_type(2)));
     auto split2h = [](float fe, float fo, unsigned& H, unsigned& L) {           // two fp16 pieces, round to nearest (11 + 1 + 11 + 1 bits)
-        const hf2 hh = {(_Float16)fe, (_Float16)fo};                            // plain casts: hipcc must see who produces an MFMA operand
-        const hf2 ll = {(_Float16)(fe - (float)hh.x), (_Float16)(fo - (float)hh.y)};
+        const h2 hh = {(_Float16)fe, (_Float16)fo};                            // plain casts: hipcc must see who produces an MFMA operand
+        const h2 ll = {(_Float16)(fe - (float)hh.x), (_Float16)(fo - (float)hh.y)};
         H = __builtin_bit_cast(unsigned, hh);
         L = __builtin_bit_cast(unsigned, ll);
     };
@@ -318,16 +295,16 @@ __global__ __launch_bounds__(128 * WAVES, 1) void k_fwd_wave2(Dev P, const float
     // an MFMA directly, so the hazard of DESIGN 4.3e cannot arise.
     auto split2h_scaled = [](v2f p, float sc, unsigned& H, unsigned& L) {
         const v2f t = p * mk2(sc, sc);
-        const hf2 hh = {(_Float16)t.x, (_Float16)t.y};
+        const h2 hh = {(_Float16)t.x, (_Float16)t.y};
         H = __builtin_bit_cast(unsigned, hh);
         float re, ro;
         asm("v_fma_mix_f32 %0, %2, %4, -%5 op_sel:[0,0,0] op_sel_hi:[0,0,1]\n\t"
             "v_fma_mix_f32 %1, %3, %4, -%5 op_sel:[0,0,1] op_sel_hi:[0,0,1]"
             : "=&v"(re), "=&v"(ro) : "v"(p.x), "v"(p.y), "v"(sc), "v"(H));
-        const hf2 ll = {(_Float16)re, (_Float16)ro};
+        const h2 ll = {(_Float16)re, (_Float16)ro};
         L = __builtin_bit_cast(unsigned, ll);
     };
-    auto fragh = [](const unsigned (&f)[4]) { return __builtin_bit_cast(hf8, v4u{f[0], f[1], f[2], f[3]}); };
+    auto fragh = [](const unsigned (&f)[4]) { return __builtin_bit_cast(h8, v4u{f[0], f[1], f[2], f[3]}); };
     unsigned WH[2][4][4], WM[HF16 ? 1 : 2][HF16 ? 1 : 4][4], WL[2][4][4];
     float sW = 1.f, Qn = 0.f, Rn = 0.f;              // HF16: scale of W; Frobenius norms of Q and R (the bound of |y_k|)
     {
@@ -366,7 +343,7 @@ __global__ __launch_bounds__(128 * WAVES, 1) void k_fwd_wave2(Dev P, const float
 #pragma unroll
                 for (int e2 = 0; e2 < 4; ++e2) {
                     if constexpr (HF16) split2h(wv[2 * e2] * sW, wv[2 * e2 + 1] * sW, WH[t][ks][e2], WL[t][ks][e2]);
-                    else split3(wv[2 * e2], wv[2 * e2 + 1], WH[t][ks][e2], WM[t][ks][e2], WL[t][ks][e2]);
+                    else split3_pk(wv[2 * e2], wv[2 * e2 + 1], WH[t][ks][e2], WM[t][ks][e2], WL[t][ks][e2]);
                 }
             }
         }
@@ -410,7 +387,7 @@ __global__ __launch_bounds__(128 * WAVES, 1) void k_fwd_wave2(Dev P, const float
                     s2 = __builtin_elementwise_fma(a, a, s2);
                     s2 = __builtin_elementwise_fma(b2, b2, s2);
                 }
-            const float mk = swapadd(s2.x + s2.y, s2.x + s2.y);            // m_k of row crow (both halves)
+            const float mk = swap32_add(s2.x + s2.y, s2.x + s2.y);            // m_k of row crow (both halves)
             float mt = __shfl_up(mk, 1, 64);
             if (crow == 0) mt = c ? m_below * esc[w][c & 3] : m_below;
             m_below = rdlane(mk, CH2 - 1);                                  // (a partial chunk is the clip's last)
@@ -464,10 +441,10 @@ __global__ __launch_bounds__(128 * WAVES, 1) void k_fwd_wave2(Dev P, const float
             } else {
             f0.x *= ck; f0.y *= ck; f0.z *= ck; f0.w *= ck; f1.x *= ck; f1.y *= ck; f1.z *= ck; f1.w *= ck;   // y_k
             unsigned AH[4], AM[4], AL[4];
-            split3(f0.x, f0.y, AH[0], AM[0], AL[0]);
-            split3(f0.z, f0.w, AH[1], AM[1], AL[1]);
-            split3(f1.x, f1.y, AH[2], AM[2], AL[2]);
-            split3(f1.z, f1.w, AH[3], AM[3], AL[3]);
+            split3_pk(f0.x, f0.y, AH[0], AM[0], AL[0]);
+            split3_pk(f0.z, f0.w, AH[1], AM[1], AL[1]);
+            split3_pk(f1.x, f1.y, AH[2], AM[2], AL[2]);
+            split3_pk(f1.z, f1.w, AH[3], AM[3], AL[3]);
 #define MF6(ACC, T_)                                                                                           \
             ACC = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag(AH), frag(WH[T_][ks]), ACC, 0, 0, 0);           \
             ACC = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag(AH), frag(WM[HF16 ? 0 : T_][HF16 ? 0 : ks]), ACC, 0, 0, 0);           \
@@ -556,7 +533,7 @@ __global__ __launch_bounds__(128 * WAVES, 1) void k_fwd_wave2(Dev P, const float
             const float4 q0 = rowp[0], q1 = rowp[1], q2 = rowp[2], q3 = rowp[3];
             const float part = ((q0.x + q0.y) + (q0.z + q0.w)) + ((q1.x + q1.y) + (q1.z + q1.w)) +
                                (((q2.x + q2.y) + (q2.z + q2.w)) + ((q3.x + q3.y) + (q3.z + q3.w)));
-            evec = swapadd(part, part);
+            evec = swap32_add(part, part);
         }
         __builtin_amdgcn_wave_barrier();
         const float incv = x1 - x0;
@@ -572,7 +549,7 @@ __global__ __launch_bounds__(128 * WAVES, 1) void k_fwd_wave2(Dev P, const float
                 const float4 q0 = rowp[0], q1 = rowp[1], q2 = rowp[2], q3 = rowp[3];
                 const float part = ((q0.x + q0.y) + (q0.z + q0.w)) + ((q1.x + q1.y) + (q1.z + q1.w)) +
                                    (((q2.x + q2.y) + (q2.z + q2.w)) + ((q3.x + q3.y) + (q3.z + q3.w)));
-                nvec2 = swapadd(part, part);
+                nvec2 = swap32_add(part, part);
             }
             __builtin_amdgcn_wave_barrier();
             float fb = __shfl_up(evec, 1, 64), nb = __shfl_up(nvec2, 1, 64);       // lanes k and k + 32 both hold step k

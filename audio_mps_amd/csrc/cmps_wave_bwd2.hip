@@ -41,11 +41,7 @@ constexpr int RING_HALF = 3 * RING_VAL;        // (ybar, yhat, u) of one octet
 constexpr int SPIN_MAX = 1 << 22;              // bound of every wait loop
 constexpr int MT = 4;                          // entries of M_{k-1} formed in the tail of step k (chain_step: inside its two lane exchanges)
 
-__device__ __forceinline__ int flag_load2(unsigned addr) {
-    int v;
-    asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(addr) : "memory");
-    return __builtin_amdgcn_readfirstlane(v);
-}
+// the counter store of this kernel (flag_load: cmps_lane_util.h): all lanes store
 __device__ __forceinline__ void flag_store2(unsigned addr_l, int v) {       // addr_l: the flag in lane 0, a sink word in the other lanes
     asm volatile("ds_write_b32 %0, %1" : : "v"(addr_l), "v"(v) : "memory");
 }
@@ -170,7 +166,7 @@ __global__ __launch_bounds__(128 * WAVES, 1) void k_bwd_wave2w(Dev P, const floa
             const int idx = c * CH + lane;
             const float inc = ra1 - ra0;
             const float nv = rnv, ev = rev;
-            const float invv = rsq_nr(fmaxf(nv, 1e-12f));
+            const float invv = rsq_newton(fmaxf(nv, 1e-12f));
             const float invokv = nv > 1e-12f ? invv : 0.f;
             const float sv = inc / A;
             const float ex = ev * inc;                      // model.py:294 operation order
@@ -276,7 +272,7 @@ __global__ __launch_bounds__(128 * WAVES, 1) void k_bwd_wave2w(Dev P, const floa
             // the tail is one dependency chain with two lane exchanges in it (VALU write -> permlane read: wait states the compiler fills
             // with s_nop): MT entries of the NEXT step's matrix go there (the mat-vec above has consumed this step's)
             const v2f sn2 = __builtin_shufflevector(c0_j, c0_j, 0, 1);     // (s, dtk) of the next step's row: only the low half is read
-            float sx = am.x, sy = am.y;                                    // swapadd (cmps_wave_util.h)
+            float sx = am.x, sy = am.y;                                    // swap32_add (cmps_lane_util.h)
             swap_fill(sx, sy, MM[12], MRd[12], MQ[12], MM[13], MRd[13], MQ[13], sn2);
             const float md = sx + sy;
             accS += md * uk;
@@ -300,7 +296,7 @@ __global__ __launch_bounds__(128 * WAVES, 1) void k_bwd_wave2w(Dev P, const floa
             asm volatile("s_nop 0\n\tv_readfirstlane_b32 %0, %1" : "=s"(seen) : "v"(cons_seen));
             if (o >= 2 && seen < o - 1) {
                 int spin = 0;
-                while (flag_load2(aCons) < o - 1 && ++spin < SPIN_MAX) __builtin_amdgcn_s_sleep(1);
+                while (flag_load(aCons) < o - 1 && ++spin < SPIN_MAX) __builtin_amdgcn_s_sleep(1);
             }
         };
         auto publish = [&]() {
@@ -376,7 +372,7 @@ __global__ __launch_bounds__(128 * WAVES, 1) void k_bwd_wave2w(Dev P, const floa
         // ---------------- the chain wave's part of the slab: f | psi0bar | A ----------------
         const float sumS = sum64(accS);
         const float sumA = av == 0 ? sum64(accA) : 0.f;        // (z = e x / A belongs to the clip: counted with its first column)
-        const float ftot = swapadd(facc, facc);               // half 0: f(h=0) + f(h=1)
+        const float ftot = swap32_add(facc, facc);               // half 0: f(h=0) + f(h=1)
         slab[4 * DD + (hb ? 2 * DPW : DPW) + i] = g;          // cotangent of psi_0: re in [DPW, 2DPW), im in [2DPW, 3DPW)
         if (!hb) slab[4 * DD + i] = ftot;
         if (lane == 0) {
@@ -388,8 +384,6 @@ __global__ __launch_bounds__(128 * WAVES, 1) void k_bwd_wave2w(Dev P, const floa
 
     // ====================================================================== gradient wave
     __builtin_amdgcn_s_setprio(0);      // (equal or swapped priorities: no gain, profiles/r5_c3_ab_two_wave.log)
-    typedef _Float16 hf8 __attribute__((ext_vector_type(8)));
-    typedef _Float16 hf2 __attribute__((ext_vector_type(2)));
     v16f Rre = {}, Rim = {}, Qre = {}, Qim = {};
     constexpr float SB16 = 8192.f;                  // the unit vectors yhat, u: |.| <= 1
     float sR = 1.f, sQ = 1.f;                       // current scales of (a1 | a2) and of ybar (wave-uniform powers of two)
@@ -404,7 +398,7 @@ __global__ __launch_bounds__(128 * WAVES, 1) void k_bwd_wave2w(Dev P, const floa
     for (int o = 0; o < n_oct; ++o) {
         {
             int spin = 0;
-            while (flag_load2(aProd) < o + 1 && ++spin < SPIN_MAX) __builtin_amdgcn_s_sleep(2);
+            while (flag_load(aProd) < o + 1 && ++spin < SPIN_MAX) __builtin_amdgcn_s_sleep(2);
         }
         const unsigned ab = aRing0 + (unsigned)(o & 1) * RING_HALF, ap = aPart + (unsigned)(o & 1) * RING_HALF;
         // the octet's steps: slot t <-> step ktop - t (slots outside [0, N - 1] hold zero operands: any finite scalar will do)
@@ -462,13 +456,13 @@ __global__ __launch_bounds__(128 * WAVES, 1) void k_bwd_wave2w(Dev P, const floa
         // half read in place; the asm results feed a compiler-visible conversion, never an MFMA directly: DESIGN 4.3e)
         auto split_pair = [&](int v, int reg, float ve, float vo, float sc2) {
             const v2f t = mk2(ve, vo) * mk2(sc2, sc2);
-            const hf2 hh = {(_Float16)t.x, (_Float16)t.y};
+            const h2 hh = {(_Float16)t.x, (_Float16)t.y};
             const unsigned H = __builtin_bit_cast(unsigned, hh);
             float re, ro;
             asm("v_fma_mix_f32 %0, %2, %4, -%5 op_sel:[0,0,0] op_sel_hi:[0,0,1]\n\t"
                 "v_fma_mix_f32 %1, %3, %4, -%5 op_sel:[0,0,1] op_sel_hi:[0,0,1]"
                 : "=&v"(re), "=&v"(ro) : "v"(ve), "v"(vo), "v"(sc2), "v"(H));
-            const hf2 ll = {(_Float16)re, (_Float16)ro};
+            const h2 ll = {(_Float16)re, (_Float16)ro};
             fH[v][reg] = H;
             fL[v][reg] = __builtin_bit_cast(unsigned, ll);
         };
@@ -483,7 +477,7 @@ __global__ __launch_bounds__(128 * WAVES, 1) void k_bwd_wave2w(Dev P, const floa
             split_pair(5, r, uu[2 * r], uu[2 * r + 1], SB16);
             split_pair(6, r, uq[2 * r], uq[2 * r + 1], sgB);
         }
-        auto frag = [&](const unsigned (&f)[4]) { return __builtin_bit_cast(hf8, v4u{f[0], f[1], f[2], f[3]}); };
+        auto frag = [&](const unsigned (&f)[4]) { return __builtin_bit_cast(h8, v4u{f[0], f[1], f[2], f[3]}); };
         auto mf3 = [&](v16f& acc, int ia, int ib) {  // hi hi' + hi lo' + lo hi'
             acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(frag(fH[ia]), frag(fH[ib]), acc, 0, 0, 0);
             acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(frag(fH[ia]), frag(fL[ib]), acc, 0, 0, 0);

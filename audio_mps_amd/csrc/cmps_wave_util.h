@@ -4,7 +4,7 @@
 #pragma once
 #include <type_traits>
 
-#include "cmps_internal.h"
+#include "cmps_lane_util.h"
 
 namespace cmps {
 
@@ -16,17 +16,7 @@ constexpr int CH = 64;     // steps per chunk of per-step scalars (one step per 
 constexpr int PE_LD = 65;  // row stride (floats) of the forward's per-lane product buffer: conflict-free both ways
 constexpr int CHB = 32;    // steps per staged chunk in the reverse sweep (three tables share the LDS)
 
-typedef float v2f __attribute__((ext_vector_type(2)));
-typedef float v4f __attribute__((ext_vector_type(4)));
-typedef float v16f __attribute__((ext_vector_type(16)));
-typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
-typedef unsigned v4u __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ v2f mk2(float a, float b) { v2f r; r.x = a; r.y = b; return r; }
 __device__ __forceinline__ v2f ld2(const float2* p) { const float2 t = *p; return mk2(t.x, t.y); }
-__device__ __forceinline__ v2f lo2(v4f q) { return __builtin_shufflevector(q, q, 0, 1); }
-__device__ __forceinline__ v2f hi2(v4f q) { return __builtin_shufflevector(q, q, 2, 3); }
 
 __device__ __forceinline__ unsigned lds_addr(const void* p) {
     return (unsigned)(uintptr_t)(__attribute__((address_space(3))) const void*)p;
@@ -131,16 +121,8 @@ __device__ __forceinline__ void mv2_hi(const v2f (&MA)[16], const v2f (&MB)[16],
           "v"(lo2(q[7])), "v"(hi2(q[7])));
 }
 
-__device__ __forceinline__ float rdlane(float v, int lane) {
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
-}
-
-// ---- cross-half: (partial.x, partial.y) of both halves -> split-layout total ----
-__device__ __forceinline__ float swapadd(float px, float py) {
-    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(px), __float_as_uint(py), false, false);
-    return __uint_as_float(r[0]) + __uint_as_float(r[1]);     // half 0: sum of x's; half 1: sum of y's
-}
-// The same directly behind an asm block that wrote px / py (the mat-vec chains): hipcc's hazard recogniser does not see VALU writes inside
+// ---- cross-half: (partial.x, partial.y) of both halves -> split-layout total (half 0: sum of x's; half 1: sum of y's) is swap32_add
+// (cmps_lane_util.h).  The same directly behind an asm block that wrote px / py (the mat-vec chains): hipcc's hazard recogniser does not see VALU writes inside
 // inline asm and left ONE instruction between the chain's last v_pk_fma_f32 and the exchange in k_bwd_wave / k_fwd_wave16, where its own
 // code keeps two wait states (s_nop 1) -- found by scripts/check_mfma_hazards.py's round-5 check.  No wrong result was ever observed (a
 // lone wave issues every ~5 cycles), but the distance is now written out.
@@ -157,7 +139,7 @@ __device__ __forceinline__ float osig_of(float x, bool hbit) {
 // ---- wave reduction ----
 template <int CTRL>
 __device__ __forceinline__ float dpp_add_row(float x) {
-    return x + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), CTRL, 0xf, 0xf, true));
+    return x + dpp_mov<CTRL>(x);
 }
 __device__ __forceinline__ float sum64(float x) {   // sum over all 64 lanes, uniform (SGPR) result
     x = dpp_add_row<0xB1>(x);    // quad_perm [1,0,3,2]
@@ -169,11 +151,6 @@ __device__ __forceinline__ float sum64(float x) {   // sum over all 64 lanes, un
     asm("s_nop 1\n\tv_add_f32_dpp %0, %0, %0 row_bcast:15 row_mask:0xa bank_mask:0xf\n\t"
         "s_nop 1\n\tv_add_f32_dpp %0, %0, %0 row_bcast:31 row_mask:0xc bank_mask:0xf" : "+v"(x));
     return rdlane(x, 63);
-}
-
-__device__ __forceinline__ float rsq_nr(float m) {   // 1/sqrt(m): v_rsq_f32 + one Newton step
-    const float r = __builtin_amdgcn_rsqf(m);
-    return r * (1.5f - 0.5f * m * r * r);
 }
 
 // ---- LDS traffic of the inner loops, hidden from hipcc's waitcnt bookkeeping on purpose ----

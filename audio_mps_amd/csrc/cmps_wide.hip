@@ -27,48 +27,20 @@
 //                         are accumulated in fp32 (24 operand bits: what is dropped is <= 2^-23 |a||b|), the same
 //                         fp32-faithful product as CMPS_RANK1_BF16X3 of the D <= 32 kernels; CMPS_RANK1_BF16X2 keeps two
 //                         pieces / three products (16 operand bits).
-// Stash (Dev::stash, layout 4): [pair][step][y | H y][wave][lane] float32 (4 PD floats per vector: the lane order above);
+// Stash (Dev::stash, STASH_WIDE): [pair][step][y | H y][wave][lane] float32 (4 PD floats per vector: the lane order above);
 // ybar: the same vector shape per (pair, step) in Dev::gops.
-#include "cmps_internal.h"
 #include "cmps_grad_gemm.h"
 
 namespace cmps {
 
 namespace {
 
-typedef float v2f __attribute__((ext_vector_type(2)));
-typedef float v4f __attribute__((ext_vector_type(4)));
-typedef unsigned u4w __attribute__((ext_vector_type(4)));
-typedef unsigned u2w __attribute__((ext_vector_type(2)));
-typedef short bf8w __attribute__((ext_vector_type(8)));
-typedef float f16w __attribute__((ext_vector_type(16)));
-
 constexpr int WCH = 64;      // steps per chunk of per-step scalars (one step per lane)
 
-__device__ __forceinline__ v2f mkv2(float a, float b) { v2f r; r.x = a; r.y = b; return r; }
-__device__ __forceinline__ v2f lo_of(v4f q) { return __builtin_shufflevector(q, q, 0, 1); }
-__device__ __forceinline__ v2f hi_of(v4f q) { return __builtin_shufflevector(q, q, 2, 3); }
-__device__ __forceinline__ float wrdl(float v, int lane) {
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
-}
-template <int CTRL>
-__device__ __forceinline__ float wdpp(float x) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), CTRL, 0xf, 0xf, true));
-}
-// lanes l and l ^ 32: lower lanes receive x + x', upper lanes y + y'
-__device__ __forceinline__ float swap32_add(float x, float y) {
-    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(y), false, false);
-    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
 // lanes l and l ^ 16: even 16-lane rows receive x + x', odd rows y + y'
 __device__ __forceinline__ float swap16_add(float x, float y) {
     const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(y), false, false);
     return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-// the value of lane l ^ 16
-__device__ __forceinline__ float partner16(float x, bool odd_row) {
-    const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-    return odd_row ? __uint_as_float(r[0]) : __uint_as_float(r[1]);
 }
 // partial sums of the eight K slices (two rows x {re, im} x packed clips) -> this lane's own (row, component, clip)
 __device__ __forceinline__ float reduce_slices(v2f re0, v2f im0, v2f re1, v2f im1, bool clip1) {
@@ -76,20 +48,16 @@ __device__ __forceinline__ float reduce_slices(v2f re0, v2f im0, v2f re1, v2f im
     const float ti0 = swap32_add(im0.x, im1.x), ti1 = swap32_add(im0.y, im1.y);
     const float c0 = swap16_add(tr0, ti0), c1 = swap16_add(tr1, ti1);                 // component select (q bit 1)
     const float keep = clip1 ? c1 : c0, give = clip1 ? c0 : c1;                       // clip select (q bit 0)
-    return keep + wdpp<0x128>(give);                                                  // row_ror:8: lane l ^ 8
+    return keep + dpp_mov<0x128>(give);                                                  // row_ror:8: lane l ^ 8
 }
 // sum over the lanes of this wave that carry the same clip (q & 1); every lane receives its clip's total
 __device__ __forceinline__ float clip_wave_sum(float x) {
-    x += wdpp<0xB1>(x);           // quad_perm [1,0,3,2]
-    x += wdpp<0x4E>(x);           // quad_perm [2,3,0,1]
-    x += wdpp<0x141>(x);          // row_half_mirror: the other quad of this 8-lane group
+    x += dpp_mov<0xB1>(x);           // quad_perm [1,0,3,2]
+    x += dpp_mov<0x4E>(x);           // quad_perm [2,3,0,1]
+    x += dpp_mov<0x141>(x);          // row_half_mirror: the other quad of this 8-lane group
     x = swap16_add(x, x);
     x = swap32_add(x, x);
     return x;
-}
-__device__ __forceinline__ float rsq_newton(float m) {   // 1 / sqrt(m): v_rsq_f32 + one Newton step (same in all three kernels)
-    const float r = __builtin_amdgcn_rsqf(m);
-    return r * (1.5f - 0.5f * m * r * r);
 }
 __device__ __forceinline__ void wide_barrier() {          // orders LDS traffic only (__syncthreads() would also drain the stash stores)
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
@@ -161,8 +129,8 @@ __device__ __forceinline__ void col_pair_plain(v2f& aRe0, v2f& aIm0, v2f& aRe1, 
         "v_pk_fma_f32 %1, %5, %10, %1 op_sel:[1,0,0]\n\t"
         "v_pk_fma_f32 %3, %7, %10, %3 op_sel:[1,0,0]"
         : "+v"(aRe0), "+v"(aIm0), "+v"(aRe1), "+v"(aIm1)
-        : "v"(lo_of(h0)), "v"(hi_of(h0)), "v"(lo_of(h1)), "v"(hi_of(h1)), "v"(lo_of(ya)), "v"(hi_of(ya)), "v"(lo_of(yb)),
-          "v"(hi_of(yb)));
+        : "v"(lo2(h0)), "v"(hi2(h0)), "v"(lo2(h1)), "v"(hi2(h1)), "v"(lo2(ya)), "v"(hi2(ya)), "v"(lo2(yb)),
+          "v"(hi2(yb)));
 }
 
 template <int PD>
@@ -199,13 +167,6 @@ __device__ __forceinline__ void split3(float x, unsigned& h, unsigned& m, unsign
     m = __float_as_uint(r1) & 0xFFFF0000u;
     const float r2 = r1 - __uint_as_float(m);
     l = __float_as_uint(r2);                        // <= 8 significant bits: exact in bf16 (the low half is zero)
-}
-__device__ __forceinline__ unsigned pack_hi16(unsigned lo_word, unsigned hi_word) {   // (lo_word >> 16) | (hi_word & 0xFFFF0000)
-    return __builtin_amdgcn_perm(hi_word, lo_word, 0x07060302u);
-}
-__device__ __forceinline__ bf8w piece_bits(u4w v, unsigned mask) {
-    u4w t = {v.x ^ mask, v.y ^ mask, v.z ^ mask, v.w ^ mask};
-    return __builtin_bit_cast(bf8w, t);
 }
 
 
@@ -271,8 +232,8 @@ __global__ __launch_bounds__(4 * PD) void k_fwd_wide(Dev P, const float* __restr
         for (int j = 0; j < KC; ++j) {
             const float2 a = P.R[(size_t)ra * PD + c0 + j], b = P.R[(size_t)rb * PD + c0 + j];
             const float2 c = P.Q[(size_t)ra * PD + c0 + j], d = P.Q[(size_t)rb * PD + c0 + j];
-            MR[0][j] = mkv2(a.x, a.y); MR[1][j] = mkv2(b.x, b.y);
-            MQ[0][j] = mkv2(c.x, c.y); MQ[1][j] = mkv2(d.x, d.y);
+            MR[0][j] = mk2(a.x, a.y); MR[1][j] = mk2(b.x, b.y);
+            MQ[0][j] = mk2(c.x, c.y); MQ[1][j] = mk2(d.x, d.y);
         }
         // H = R + R^dagger in lane order: float4 number rs KC/2 + jp of this lane = H[row_rs][c0 + 2 jp], H[row_rs][c0 + 2 jp + 1]
 #pragma unroll
@@ -331,16 +292,16 @@ __global__ __launch_bounds__(4 * PD) void k_fwd_wide(Dev P, const float* __restr
             }
         }
         const float inv = k >= 1 ? rsq_newton(fmaxf(clip1 ? n1 : n0, 1e-12f)) : 1.f;      // model.py:332
-        v2f cRe0 = mkv2(0.f, 0.f), cIm0 = cRe0, cRe1 = cRe0, cIm1 = cRe0;
+        v2f cRe0 = mk2(0.f, 0.f), cIm0 = cRe0, cRe1 = cRe0, cIm1 = cRe0;
         v2f hRe0 = cRe0, hIm0 = cRe0, hRe1 = cRe0, hIm1 = cRe0;
         if (chain) {
             const int kl = k & (WCH - 1);
-            const v2f s2 = mkv2(wrdl(sv0, kl), wrdl(sv1, kl));
+            const v2f s2 = mk2(rdlane(sv0, kl), rdlane(sv1, kl));
             const v4f* uv = uvec + p * VEC4 + rd4;
 #pragma unroll
             for (int j = 0; j < KC; ++j) {
                 const v4f x = uv[j];
-                col_merged(cRe0, cIm0, cRe1, cIm1, MR[0][j], MQ[0][j], MR[1][j], MQ[1][j], s2, lo_of(x), hi_of(x));
+                col_merged(cRe0, cIm0, cRe1, cIm1, MR[0][j], MQ[0][j], MR[1][j], MQ[1][j], s2, lo2(x), hi2(x));
             }
         }
         if (lossmv) {                                             // H y_{k-1}
@@ -390,7 +351,7 @@ __global__ __launch_bounds__(4 * PD) void k_fwd_wide(Dev P, const float* __restr
                     if constexpr (LEGACY) {                       // the expectation on the normalised state of the step below (graph.pbtxt:11857-12819)
                         float f0 = __shfl_up(ebuf0, 1, 64), f1 = __shfl_up(ebuf1, 1, 64), m0 = __shfl_up(nbuf0, 1, 64), m1 = __shfl_up(nbuf1, 1, 64);
                         if (lane == 0) { f0 = fbel0; f1 = fbel1; m0 = nbel0; m1 = nbel1; }
-                        fbel0 = wrdl(ebuf0, WCH - 1); fbel1 = wrdl(ebuf1, WCH - 1); nbel0 = wrdl(nbuf0, WCH - 1); nbel1 = wrdl(nbuf1, WCH - 1);
+                        fbel0 = rdlane(ebuf0, WCH - 1); fbel1 = rdlane(ebuf1, WCH - 1); nbel0 = rdlane(nbuf0, WCH - 1); nbel1 = rdlane(nbuf1, WCH - 1);
                         const float v0 = 1.0f / sqrtf(fmaxf(m0, 1e-12f)), v1 = 1.0f / sqrtf(fmaxf(m1, 1e-12f));
                         const float d0 = i0 - (f0 * v0) * v0, d1 = i1 - (f1 * v1) * v1;
                         l0 = in ? d0 * d0 / 2.0f : 0.f;
@@ -401,8 +362,8 @@ __global__ __launch_bounds__(4 * PD) void k_fwd_wide(Dev P, const float* __restr
                     }
 #pragma unroll
                     for (int j = 0; j < WCH; ++j) {               // model.py:279: sequential in time
-                        loss0 += wrdl(l0, j);
-                        loss1 += wrdl(l1, j);
+                        loss0 += rdlane(l0, j);
+                        loss1 += rdlane(l1, j);
                     }
                 }
             }
@@ -460,8 +421,8 @@ __global__ __launch_bounds__(4 * PD) void k_fwd_wide_rho(Dev P, const float* __r
         for (int j = 0; j < KC; ++j) {
             const float2 a = P.R[(size_t)ra * PD + c0 + j], bb = P.R[(size_t)rb * PD + c0 + j];
             const float2 c = P.Q[(size_t)ra * PD + c0 + j], d = P.Q[(size_t)rb * PD + c0 + j];
-            MR[0][j] = mkv2(a.x, a.y); MR[1][j] = mkv2(bb.x, bb.y);
-            MQ[0][j] = mkv2(c.x, c.y); MQ[1][j] = mkv2(d.x, d.y);
+            MR[0][j] = mk2(a.x, a.y); MR[1][j] = mk2(bb.x, bb.y);
+            MQ[0][j] = mk2(c.x, c.y); MQ[1][j] = mk2(d.x, d.y);
         }
     }
     const int own_f = vec_float_index<PD>(row, comp, clip);
@@ -492,8 +453,8 @@ __global__ __launch_bounds__(4 * PD) void k_fwd_wide_rho(Dev P, const float* __r
         }
         const float inv = k >= 1 ? rsq_newton(fmaxf(n, 1e-12f)) : 1.f;       // model.py:198-203 (sqrt of the trace: columns, not the matrix)
         if (chain) {
-            const float sk = wrdl(sv, k & (WCH - 1));
-            const v2f s2 = mkv2(sk, sk);
+            const float sk = rdlane(sv, k & (WCH - 1));
+            const v2f s2 = mk2(sk, sk);
             v2f MM[2][KC];                                        // M_k = Q + s_k R: once per step, shared by every column of the clip
 #pragma unroll
             for (int j = 0; j < KC; ++j) {
@@ -503,11 +464,11 @@ __global__ __launch_bounds__(4 * PD) void k_fwd_wide_rho(Dev P, const float* __r
             float nacc = 0.f;
             for (int cp = 0; cp < npairs; ++cp) {
                 const v4f* uv = uvec + ((size_t)p * npairs + cp) * VEC4;
-                v2f cRe0 = mkv2(0.f, 0.f), cIm0 = cRe0, cRe1 = cRe0, cIm1 = cRe0;
+                v2f cRe0 = mk2(0.f, 0.f), cIm0 = cRe0, cRe1 = cRe0, cIm1 = cRe0;
 #pragma unroll
                 for (int j = 0; j < KC; ++j) {
                     const v4f x = uv[rd4 + j];
-                    col_single(cRe0, cIm0, cRe1, cIm1, MM[0][j], MM[1][j], lo_of(x), hi_of(x));
+                    col_single(cRe0, cIm0, cRe1, cIm1, MM[0][j], MM[1][j], lo2(x), hi2(x));
                 }
                 const float ut = reinterpret_cast<const float*>(uv)[own_f];
                 const float acc = reduce_slices(cRe0, cIm0, cRe1, cIm1, clip1);
@@ -519,7 +480,7 @@ __global__ __launch_bounds__(4 * PD) void k_fwd_wide_rho(Dev P, const float* __r
                     rho_k.x * y + (im_lane ? rho_k.y : -rho_k.y) * py;       // ut_{k+1} = rho_k y_k (un-normalised)
             }
             float nn = clip_wave_sum(nacc);
-            nn += wdpp<0x128>(nn);                                // + the columns of the other parity (lane ^ 8)
+            nn += dpp_mov<0x128>(nn);                                // + the columns of the other parity (lane ^ 8)
             if (lane == 0) nrm[(p ^ 1) * NW + w] = nn;
         }
         if (w == 0 && k >= 1) {                                   // tr rho'_{k-1} rows of the per-clip scalar stash
@@ -610,8 +571,8 @@ __global__ __launch_bounds__(4 * PD) void k_sample_wide(Dev P, const float* __re
         for (int j = 0; j < KC; ++j) {
             const float2 a = P.R[(size_t)ra * PD + c0 + j], b = P.R[(size_t)rb * PD + c0 + j];
             const float2 c = P.Q[(size_t)ra * PD + c0 + j], d = P.Q[(size_t)rb * PD + c0 + j];
-            MR[0][j] = mkv2(a.x, a.y); MR[1][j] = mkv2(b.x, b.y);
-            MQ[0][j] = mkv2(c.x, c.y); MQ[1][j] = mkv2(d.x, d.y);
+            MR[0][j] = mk2(a.x, a.y); MR[1][j] = mk2(b.x, b.y);
+            MQ[0][j] = mk2(c.x, c.y); MQ[1][j] = mk2(d.x, d.y);
         }
     }
     const int own_f = vec_float_index<PD>(row, comp, clip);
@@ -643,13 +604,13 @@ __global__ __launch_bounds__(4 * PD) void k_sample_wide(Dev P, const float* __re
             }
         }
         const float inv = k >= 1 ? rsq_newton(fmaxf(clip1 ? n1 : n0, 1e-12f)) : 1.f;      // model.py:289 of the step before
-        v2f rRe0 = mkv2(0.f, 0.f), rIm0 = rRe0, rRe1 = rRe0, rIm1 = rRe0;
+        v2f rRe0 = mk2(0.f, 0.f), rIm0 = rRe0, rRe1 = rRe0, rIm1 = rRe0;
         v2f qRe0 = rRe0, qIm0 = rRe0, qRe1 = rRe0, qIm1 = rRe0;
         const v4f* uv = uvec + p * VEC4 + rd4;
 #pragma unroll
         for (int j = 0; j < KC; ++j) {
             const v4f x = uv[j];
-            col_two(rRe0, rIm0, rRe1, rIm1, qRe0, qIm0, qRe1, qIm1, MR[0][j], MQ[0][j], MR[1][j], MQ[1][j], lo_of(x), hi_of(x));
+            col_two(rRe0, rIm0, rRe1, rIm1, qRe0, qIm0, qRe1, qIm1, MR[0][j], MQ[0][j], MR[1][j], MQ[1][j], lo2(x), hi2(x));
         }
         const float vs = reduce_slices(rRe0, rIm0, rRe1, rIm1, clip1);      // (R ut), (Q ut): this lane's (row, component, path)
         const float qs = reduce_slices(qRe0, qIm0, qRe1, qIm1, clip1);
@@ -663,7 +624,7 @@ __global__ __launch_bounds__(4 * PD) void k_sample_wide(Dev P, const float* __re
             e0 += t.x; e1 += t.y;
         }
         const float e = 2.0f * ((clip1 ? e1 : e0) * inv) * inv;   // _expectation on the normalised state (model.py:319-325)
-        const float inc = e * dt + (clip1 ? wrdl(nz1, kl) : wrdl(nz0, kl));   // model.py:286
+        const float inc = e * dt + (clip1 ? rdlane(nz1, kl) : rdlane(nz0, kl));   // model.py:286
         samp += inc;                                              // :287
         const float s = inc / A;                                  // :288 -> :303
         const float y = inv * (ut + (qs + s * vs));
@@ -748,7 +709,7 @@ __global__ __launch_bounds__(2 * PD, 1) void k_hy_wide(Dev P) {
     const float sgn = cf ? -1.f : 1.f;
 
     // ---- A operand: row 32 w + mr of [H_re | -H_im], K values 16 t + 8 mh .. + 7, three bf16 pieces (two fp16 pieces) ----
-    bf8w Ah[KT], Am[F16 ? 1 : KT], Al[KT];
+    s16x8 Ah[KT], Am[F16 ? 1 : KT], Al[KT];
     float sH = 1.f, sB = 1.f;
     if constexpr (F16) {
         const int row = 32 * w + mr;
@@ -773,8 +734,8 @@ __global__ __launch_bounds__(2 * PD, 1) void k_hy_wide(Dev P) {
         for (int ww = 0; ww < PWV; ++ww) { mH = fmaxf(mH, eacc[2 * ww]); mN = fmaxf(mN, eacc[2 * ww + 1]); }
         __syncthreads();
         auto uni = [](float x) { return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(x))); };
-        sH = uni(gg::pow2_scale(mH, 15));
-        sB = uni(gg::pow2_scale(sqrtf(mN), 13));
+        sH = uni(pow2_below(mH, 15));
+        sB = uni(pow2_below(sqrtf(mN), 13));
 #pragma unroll
         for (int t = 0; t < KT; ++t) {
             unsigned ph[4], pl[4];
@@ -787,13 +748,12 @@ __global__ __launch_bounds__(2 * PD, 1) void k_hy_wide(Dev P) {
                     const float2 r = P.R[(size_t)row * PD + j], rt = P.RT[(size_t)row * PD + j];
                     v[i] = (part == 0 ? r.x + rt.x : -(r.y - rt.y)) * sH;
                 }
-                typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-                ph[e >> 1] = gg::cvt_pk_f16(v[0], v[1]);
+                ph[e >> 1] = cvt_pk_f16(v[0], v[1]);
                 const h2 hh = __builtin_bit_cast(h2, ph[e >> 1]);
-                pl[e >> 1] = gg::cvt_pk_f16(v[0] - (float)hh.x, v[1] - (float)hh.y);
+                pl[e >> 1] = cvt_pk_f16(v[0] - (float)hh.x, v[1] - (float)hh.y);
             }
-            Ah[t] = __builtin_bit_cast(bf8w, u4w{ph[0], ph[1], ph[2], ph[3]});
-            Al[t] = __builtin_bit_cast(bf8w, u4w{pl[0], pl[1], pl[2], pl[3]});
+            Ah[t] = __builtin_bit_cast(s16x8, v4u{ph[0], ph[1], ph[2], ph[3]});
+            Al[t] = __builtin_bit_cast(s16x8, v4u{pl[0], pl[1], pl[2], pl[3]});
         }
     } else {
         const int row = 32 * w + mr;
@@ -815,9 +775,9 @@ __global__ __launch_bounds__(2 * PD, 1) void k_hy_wide(Dev P) {
                     ph[e >> 1] = h; pm[e >> 1] = m; pl[e >> 1] = l;
                 }
             }
-            Ah[t] = __builtin_bit_cast(bf8w, u4w{ph[0], ph[1], ph[2], ph[3]});
-            Am[t] = __builtin_bit_cast(bf8w, u4w{pm[0], pm[1], pm[2], pm[3]});
-            Al[t] = __builtin_bit_cast(bf8w, u4w{pl[0], pl[1], pl[2], pl[3]});
+            Ah[t] = __builtin_bit_cast(s16x8, v4u{ph[0], ph[1], ph[2], ph[3]});
+            Am[t] = __builtin_bit_cast(s16x8, v4u{pm[0], pm[1], pm[2], pm[3]});
+            Al[t] = __builtin_bit_cast(s16x8, v4u{pl[0], pl[1], pl[2], pl[3]});
         }
     }
     // ---- build / write-out role: positions 2 tid and 2 tid + 1 of a stash vector: two adjacent rows of one (component, clip) ----
@@ -846,9 +806,8 @@ __global__ __launch_bounds__(2 * PD, 1) void k_hy_wide(Dev P) {
             const bool in = k_lo + HU * u + j < k_hi;
             sv0 = in ? Y[j].x : 0.f; sv1 = in ? Y[j].y : 0.f;
             if constexpr (F16) {
-                typedef _Float16 h2 __attribute__((ext_vector_type(2)));
                 const float t0 = sv0 * sB, t1 = sv1 * sB;
-                sh[0] = gg::cvt_pk_f16(t0, t1);
+                sh[0] = cvt_pk_f16(t0, t1);
                 const h2 hh = __builtin_bit_cast(h2, sh[0]);
                 sr0 = t0 - (float)hh.x;
                 sr1 = t1 - (float)hh.y;
@@ -857,7 +816,7 @@ __global__ __launch_bounds__(2 * PD, 1) void k_hy_wide(Dev P) {
                 sr1 = sv1 - __uint_as_float(__float_as_uint(sv1) & 0xFFFF0000u);
             }
         } else if (part == 1 && F16) {
-            sh[1] = gg::cvt_pk_f16(sr0, sr1);
+            sh[1] = cvt_pk_f16(sr0, sr1);
         } else if (part == 1) {
             const float q0 = sr0 - __uint_as_float(__float_as_uint(sr0) & 0xFFFF0000u);
             const float q1 = sr1 - __uint_as_float(__float_as_uint(sr1) & 0xFFFF0000u);
@@ -875,7 +834,7 @@ __global__ __launch_bounds__(2 * PD, 1) void k_hy_wide(Dev P) {
     };
 
     // one unit.  PAR = u & 1 (static: accumulator pair and LDS buffers of the stages), u3 = u % 3.
-    f16w acc0[2], acc1[2];                                         // [unit parity]: K half 0 (H_re), K half 1 (-H_im)
+    v16f acc0[2], acc1[2];                                         // [unit parity]: K half 0 (H_re), K half 1 (-H_im)
     float ep_run = 0.f;
     float4 hv = make_float4(0.f, 0.f, 0.f, 0.f);
     const float usc = (1.0f / sH) * (1.0f / sB), usgn = sgn * usc;   // exact powers of two (1 without the fp16 scales)
@@ -890,14 +849,14 @@ __global__ __launch_bounds__(2 * PD, 1) void k_hy_wide(Dev P) {
         float* hr = hf + (size_t)(1 - PAR) * FBUF + rowi * FROW + 32 * w + 4 * mh;
         const int kw = k_lo + HU * (u - 2);                        // first step of the unit being written out
         const float* hb = hf + (size_t)PAR * FBUF;
-        bf8w Bq[2][3];
+        s16x8 Bq[2][3];
         auto read_b = [&](int t, int buf) {
             const int part = (16 * t) / PD, j0 = (16 * t) % PD + 8 * mh;
             const int comp = part == 0 ? cf : 1 - cf;              // Re form: [y_re; y_im]; Im form: [y_im; y_re] (sign: see the epilogue)
             const unsigned char* src = pb + hy_slot((cs * 2 + cc) * 2 + comp) * PROW + j0 * 2;
-            Bq[buf][0] = __builtin_bit_cast(bf8w, *reinterpret_cast<const u4w*>(src));
-            Bq[buf][1] = __builtin_bit_cast(bf8w, *reinterpret_cast<const u4w*>(src + PIECE));
-            if constexpr (!F16) Bq[buf][2] = __builtin_bit_cast(bf8w, *reinterpret_cast<const u4w*>(src + 2 * PIECE));
+            Bq[buf][0] = __builtin_bit_cast(s16x8, *reinterpret_cast<const v4u*>(src));
+            Bq[buf][1] = __builtin_bit_cast(s16x8, *reinterpret_cast<const v4u*>(src + PIECE));
+            if constexpr (!F16) Bq[buf][2] = __builtin_bit_cast(s16x8, *reinterpret_cast<const v4u*>(src + 2 * PIECE));
         };
         auto slice = [&](auto ic) {
             constexpr int I = decltype(ic)::value;
@@ -906,7 +865,7 @@ __global__ __launch_bounds__(2 * PD, 1) void k_hy_wide(Dev P) {
                     constexpr int j = I;
                     const float2 v = *reinterpret_cast<const float2*>(&hb[hy_slot((j * 2 + pclip) * 2 + pcomp) * FROW + prow]);
                     const bool ok = u >= 2 && kw + j < k_hi;
-                    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u2w, v), rs_st, ok ? voff_h : 0x7fffffff,
+                    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(v2u, v), rs_st, ok ? voff_h : 0x7fffffff,
                                                           ok ? (kw + j) * (8 * PD * 4) : 0, 0);
                 } else {
                     const int j = (tid >> 1) & 7, cl = tid & 1, k = kw + j;
@@ -936,7 +895,7 @@ __global__ __launch_bounds__(2 * PD, 1) void k_hy_wide(Dev P) {
                     }
                 } else {
                     float ep = swap32_add(ep_run, ep_run);        // + the other row half
-                    ep += wdpp<0xB1>(ep);                         // + the other component (column ^ 1)
+                    ep += dpp_mov<0xB1>(ep);                         // + the other component (column ^ 1)
                     if (mh == 0 && cf == 0) eacc[((1 - PAR) * PWV + w) * 16 + (mr >> 1)] = ep;
                 }
             } else if constexpr (I < S_F0) {                      // unit u + 1: pieces and float32 rows from the fetched rows
@@ -956,10 +915,10 @@ __global__ __launch_bounds__(2 * PD, 1) void k_hy_wide(Dev P) {
                 constexpr int kt = t / NPR, pr = t % NPR, buf = kt & 1;
                 if constexpr (pr == 0 && kt + 1 < KT) read_b(kt + 1, 1 - buf);
                 // piece products a + b <= 2: lo hi', hi lo', mid mid', mid hi', hi mid', hi hi'  (fp16: lo hi', hi lo', hi hi')
-                const bf8w av = pr == 0 ? Al[kt] : (!F16 && (pr == 2 || pr == 3)) ? Am[F16 ? 0 : kt] : Ah[kt];
-                const bf8w bv = F16 ? (pr == 1 ? Bq[buf][1] : Bq[buf][0])
+                const s16x8 av = pr == 0 ? Al[kt] : (!F16 && (pr == 2 || pr == 3)) ? Am[F16 ? 0 : kt] : Ah[kt];
+                const s16x8 bv = F16 ? (pr == 1 ? Bq[buf][1] : Bq[buf][0])
                                     : (pr == 1 ? Bq[buf][2] : (pr == 2 || pr == 4) ? Bq[buf][1] : Bq[buf][0]);
-                constexpr f16w zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+                constexpr v16f zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
                 if constexpr (kt < KT / 2) acc0[PAR] = gg::mma<F16>(av, bv, t == 0 ? zero : acc0[PAR]);
                 else acc1[PAR] = gg::mma<F16>(av, bv, t == NPR * (KT / 2) ? zero : acc1[PAR]);
                 __builtin_amdgcn_sched_barrier(0);
@@ -1020,8 +979,8 @@ __global__ __launch_bounds__(64) void k_loss_wide(Dev P, const float* __restrict
             // (:12685-12819); the e row is REPLACED by the legacy e_k (what the reverse scan and the gradient GEMM read), as the wave kernels do
             float fb = __shfl_up(e, 1, 64), nb = __shfl_up(nv, 1, 64);
             if (lane == 0) { fb = f_below; nb = n_below; }
-            f_below = wrdl(e, WCH - 1);
-            n_below = wrdl(nv, WCH - 1);
+            f_below = rdlane(e, WCH - 1);
+            n_below = rdlane(nv, WCH - 1);
             const float invb = 1.0f / sqrtf(fmaxf(nb, 1e-12f));       // graph.pbtxt:14350-14594
             e = (fb * invb) * invb;
             if (in) sc[(size_t)c * 128 + 64 + lane] = e;
@@ -1031,7 +990,7 @@ __global__ __launch_bounds__(64) void k_loss_wide(Dev P, const float* __restrict
             lv = in ? -logf(1.0f + (e * inc) / A) : 0.f;
         }
 #pragma unroll
-        for (int j = 0; j < WCH; ++j) loss += wrdl(lv, j);
+        for (int j = 0; j < WCH; ++j) loss += rdlane(lv, j);
     }
     if (lane == 0) loss_out[b] = loss;
 }
@@ -1078,12 +1037,12 @@ __global__ __launch_bounds__(4 * PD) void k_bwd_wide(Dev P, const float* __restr
             const float2 a = P.RT[(size_t)ra * PD + c0 + j], b = P.RT[(size_t)rb * PD + c0 + j];   // R^dagger[i][j] = conj(RT[i][j])
             if constexpr (LEGACY) {                               // Q^dagger[i][j] = conj(QT[i][j])
                 const float2 c = P.QT[(size_t)ra * PD + c0 + j], d = P.QT[(size_t)rb * PD + c0 + j];
-                MQ[0][j] = mkv2(c.x, -c.y); MQ[1][j] = mkv2(d.x, -d.y);
+                MQ[0][j] = mk2(c.x, -c.y); MQ[1][j] = mk2(d.x, -d.y);
             } else {
                 const float2 c = P.Q[(size_t)ra * PD + c0 + j], d = P.Q[(size_t)rb * PD + c0 + j];
-                MQ[0][j] = mkv2(c.x, c.y); MQ[1][j] = mkv2(d.x, d.y);
+                MQ[0][j] = mk2(c.x, c.y); MQ[1][j] = mk2(d.x, d.y);
             }
-            MD[0][j] = mkv2(a.x, -a.y); MD[1][j] = mkv2(b.x, -b.y);
+            MD[0][j] = mk2(a.x, -a.y); MD[1][j] = mk2(b.x, -b.y);
         }
     }
     const int own_f = vec_float_index<PD>(row, comp, clip);
@@ -1112,7 +1071,7 @@ __global__ __launch_bounds__(4 * PD) void k_bwd_wide(Dev P, const float* __restr
                 const float tev = in ? 2.0f * (ev - inc) : 0.f;   // te_k = 2 ebar_k, ebar_k = e_k - x_k (the e rows hold the legacy e_k: k_loss_wide)
                 float ten = __shfl_down(tev, 1, 64);               // te_{k+1}
                 if (lane == 63) ten = qq ? te_above1 : te_above0;
-                if (qq) te_above1 = wrdl(tev, 0); else te_above0 = wrdl(tev, 0);
+                if (qq) te_above1 = rdlane(tev, 0); else te_above0 = rdlane(tev, 0);
                 r.s = P.dt * inc;
                 r.inv = rsq_newton(fmaxf(nv, 1e-12f));
                 r.ok = nv > 1e-12f ? 1.f : 0.f;
@@ -1179,13 +1138,13 @@ __global__ __launch_bounds__(4 * PD) void k_bwd_wide(Dev P, const float* __restr
         wide_barrier();
         const int kl = k & (WCH - 1);
         const bool par = ((k / WCH) & 1) != 0;
-        const v2f s2 = mkv2(wrdl(par ? svB0 : svA0, kl), wrdl(par ? svB1 : svA1, kl));
-        v2f dRe0 = mkv2(0.f, 0.f), dIm0 = dRe0, dRe1 = dRe0, dIm1 = dRe0;
+        const v2f s2 = mk2(rdlane(par ? svB0 : svA0, kl), rdlane(par ? svB1 : svA1, kl));
+        v2f dRe0 = mk2(0.f, 0.f), dIm0 = dRe0, dRe1 = dRe0, dIm1 = dRe0;
         const v4f* yv = vec[p] + rd4;
 #pragma unroll
         for (int j = 0; j < KC; ++j) {
             const v4f x = yv[j];
-            col_merged(dRe0, dIm0, dRe1, dIm1, MD[0][j], MQ[0][j], MD[1][j], MQ[1][j], s2, lo_of(x), hi_of(x));
+            col_merged(dRe0, dIm0, dRe1, dIm1, MD[0][j], MQ[0][j], MD[1][j], MQ[1][j], s2, lo2(x), hi2(x));
         }
         // ---- off the chain ----
         facc += S1.y * (im_lane ? -pg : pg) * unext;              // dt_k Im(g conj(u_{k+1})): re lanes g_im u_re, im lanes -g_re u_im
@@ -1216,8 +1175,8 @@ __global__ __launch_bounds__(4 * PD) void k_bwd_wide(Dev P, const float* __restr
     constexpr int DD = PD * PD;
     {
         float f = facc * wq, g0 = g * wq;
-        f += wdpp<0x128>(f);                                      // + the other clip (lane ^ 8)
-        g0 += wdpp<0x128>(g0);
+        f += dpp_mov<0x128>(f);                                      // + the other clip (lane ^ 8)
+        g0 += dpp_mov<0x128>(g0);
         const float ft = f + partner16(f, im_lane);               // + the other component's share
         if (!clip1) {
             if (!im_lane) slab[4 * DD + row] = ft;
@@ -1398,7 +1357,7 @@ static Dev rho_virtual_dev(const Dev& P, const RhoDev& W) {
     V.B = P.B * W.vrank;
     V.stash = reinterpret_cast<float2*>(W.vstash);
     V.hst = W.vstash;
-    V.stash_layout = 4;
+    V.stash_layout = STASH_WIDE;
     V.scal = W.vscal;
     V.gops = W.vgops;
     V.opmax = W.vopmax;

@@ -50,8 +50,8 @@ enum {
  * kernels above that.  Both follow the reference's float32 / complex64 arithmetic (model.py:300-325) in this sense:
  *   - state, identity part of every update, normalisation, loss and every accumulation are float32;
  *   - D <= 32: the mat-vec on the serial chain is an fp32 FMA chain.  The two products nothing waits for run on the matrix
- *     cores with split operands and fp32 accumulation: the loss product H y (three bf16 pieces, six products) and the rank-1
- *     gradient sums (CMPS_OPT_RANK1; default two scaled fp16 pieces, three products);
+ *     cores with split operands and fp32 accumulation: the loss product H y and the rank-1 gradient sums
+ *     (both follow CMPS_OPT_RANK1; default two scaled fp16 pieces, three products);
  *   - 32 < D <= 128: the mat-vecs of both serial chains, H y and the gradient GEMM all run on the matrix cores with two
  *     scaled fp16 pieces per operand (CMPS_OPT_WIDE_CHAIN, CMPS_OPT_RANK1 select the fp32-VALU / bf16-piece forms).
  * Split products carry 22-24 operand bits: within float32 rounding of an fp32 FMA chain, not bit-identical to it.
