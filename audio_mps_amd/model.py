@@ -18,6 +18,9 @@ from typing import Callable, Dict, Optional
 
 import numpy as np
 
+from . import layout
+from .layout import EffectiveParams, unpack_grad
+
 VARIABLE_NAMES = ("A", "Rx", "Ry", "freqs", "psi_x", "psi_y")
 
 
@@ -79,6 +82,49 @@ def _normalize_psi_host(p: np.ndarray) -> np.ndarray:
 
 
 # --------------------------------------------------------------------------------------------------
+class _ScanModel:
+    """What every model class needs to run a scan on its backend.  Expects ``bond_d``, ``data_iterator``, ``_backend``, ``_last`` and
+    the subclass's ``_prepare(B, T, train)`` (upload the parameters, return the backend), ``grad_sums`` and ``chain_rule``."""
+
+    def _get_backend(self):
+        if self._backend is None:
+            from .scan import HipScan   # raises if libcmps.so or the GPU is missing: no fallback
+            self._backend = HipScan(self.bond_d)
+        return self._backend
+
+    def _batch(self, data=None):
+        data = self.data_iterator if data is None else data
+        if callable(data):
+            data = data()
+        return data
+
+    def _to_device(self, data):
+        import torch
+        be = self._get_backend()
+        dev = getattr(be, "device", None)
+        if isinstance(data, torch.Tensor):
+            t = data.to(dtype=torch.float32)
+            if dev is not None:
+                t = t.to(dev)
+            return t.contiguous()
+        t = torch.from_numpy(np.ascontiguousarray(data, dtype=np.float32))
+        return t.to(dev) if dev is not None else t
+
+    def _scan(self, data, train: bool):
+        """(backend holding the current parameters, the batch on its device, B, T): the start of every scan method."""
+        audio = self._to_device(self._batch(data))
+        B, T = audio.shape
+        return self._prepare(B, T, train), audio, B, T
+
+    def loss_and_grads(self, data=None, with_reg: bool = False):
+        """(loss, {variable: gradient}) of mean_b loss_b (+ train.py's regularisers if with_reg): what
+        ``AdamOptimizer.minimize`` obtains from TF (train.py:89)."""
+        flat, B = self.grad_sums(data)
+        host = flat.detach().cpu().numpy() if hasattr(flat, "detach") else np.asarray(flat)
+        self._last = host
+        return self.chain_rule(host, B, with_reg=with_reg)
+
+
 class _VarDict(dict):
     """model.variables: a plain dict whose item assignment invalidates a live device-resident copy of the variables (see CMPS.variables)."""
 
@@ -87,18 +133,21 @@ class _VarDict(dict):
         self._model = model
 
     def __setitem__(self, key, value):
-        owner = self._model._owner() if hasattr(self._model, "_device_owner") else None
-        if owner is not None and getattr(owner, "_dev", None) is not None and not getattr(owner, "_syncing_back", False):
+        owner = self._model._owner()
+        if owner is not None and owner._dev is not None and not owner._syncing_back:
             owner.drop_device_state()              # device -> host for everything else, then forget the device copy
         super().__setitem__(key, value)
 
 
-class CMPS:
+class CMPS(_ScanModel):
     """Continuous Matrix Product State: the trainable variables and the effective parameters
     (model.py:5-52).  ``self.R`` (complex64 [D,D], diagonal removed as at model.py:42), ``self.freqs``,
     ``self.A``, ``self.sigma`` are the attributes train.py:55-75 reads."""
 
     def __init__(self, hparams, data_iterator=None, freqs_in=None, R_in=None, seed: int = 0):
+        self._device_owner = None      # a Trainer whose device-resident optimiser state is newer than self._variables (see `variables`)
+        self._backend = None           # the scan implementation (the subclasses' `backend` argument); None: a HipScan on first use
+        self._last = None              # the flat gradient sums of the last loss_and_grads (host copy)
         self.hparams = hparams
         self.bond_d = int(hparams.bond_dim)
         self.batch_size = hparams.minibatch_size
@@ -110,9 +159,7 @@ class CMPS:
         self.data_iterator = data_iterator
         D = self.bond_d
         rng = np.random.default_rng(seed)
-        self._device_owner = None
         self._variables: Dict[str, np.ndarray] = _VarDict(self)
-        self._device_owner = None      # a Trainer whose device-resident optimiser state is newer than self._variables (see `variables`)
         self.variables["A"] = np.asarray(np.float32(hparams.A))   # model.py:19
         # --- R (model.py:31-42)
         if R_in is not None:
@@ -176,32 +223,30 @@ class CMPS:
     def freqsc(self) -> np.ndarray:
         return self.freqs.astype(np.complex64)                    # model.py:52
 
-    # ---- backend plumbing (shared by PsiCMPS and RhoCMPS) ----
-    _backend = None
+    _LOSS_LINE = None              # where the reference's subclass defines `loss` (cited by its AttributeError)
 
-    def _get_backend(self):
-        if self._backend is None:
-            from .scan import HipScan   # raises if libcmps.so or the GPU is missing: no fallback
-            self._backend = HipScan(self.bond_d)
-        return self._backend
+    @property
+    def loss(self) -> np.float32:
+        """``.loss`` of the reference (PsiCMPS model.py:224-225, 267; RhoCMPS :69-70, 144): mean over the batch of the per-clip loss."""
+        if self.data_iterator is None:
+            raise AttributeError(f"loss: the model was built without a data_iterator (model.py:{self._LOSS_LINE})")
+        return np.float32(np.mean(self.loss_per_clip(), dtype=np.float32))
 
-    def _batch(self, data=None):
-        data = self.data_iterator if data is None else data
-        if callable(data):
-            data = data()
-        return data
+    def _effective(self, psi0) -> EffectiveParams:
+        return EffectiveParams(R=self.R, freqs=self.freqs, psi0=psi0, A=float(self.A),
+                               sigma=float(self.sigma), delta_t=float(self.delta_t))
 
-    def _to_device(self, data):
-        import torch
-        be = self._get_backend()
-        dev = getattr(be, "device", None)
-        if isinstance(data, torch.Tensor):
-            t = data.to(dtype=torch.float32)
-            if dev is not None:
-                t = t.to(dev)
-            return t.contiguous()
-        t = torch.from_numpy(np.ascontiguousarray(data, dtype=np.float32))
-        return t.to(dev) if dev is not None else t
+    def _noise(self, num_samples, length, temp, seed, noise):
+        """The sampler's Gaussian noise [length, num_samples] (stddev sigma * sqrt(temp * delta_t), model.py:246 / :88, 96, 106):
+        drawn on the host with a numpy Generator (``seed``), or ``noise`` as passed in, like the reference's tensor."""
+        if noise is None:
+            rng = np.random.default_rng(seed)
+            std = float(self.sigma) * math.sqrt(temp * float(self.delta_t))
+            noise = (std * rng.standard_normal((length, num_samples))).astype(np.float32)
+        noise = np.asarray(noise, dtype=np.float32)
+        if noise.shape != (length, num_samples):
+            raise ValueError(f"noise must be [{length}, {num_samples}]")
+        return noise
 
     def _chain_common(self, Rbar, fbar, Abar, loss, with_reg: bool):
         """Adjoint of model.py:36-42 (scaling + the row-broadcast diagonal removal) and :49 for batch-mean cotangents of
@@ -233,6 +278,8 @@ class PsiCMPS(CMPS):
     the same two methods to exercise the host logic without a GPU.
     """
 
+    _LOSS_LINE = 224
+
     def __init__(self, hparams, psi_in=None, *args, backend=None, **kwargs):
         super().__init__(hparams, *args, **kwargs)
         D = self.bond_d
@@ -249,7 +296,6 @@ class PsiCMPS(CMPS):
             self.variables["psi_x"] = self._rng.uniform(-lim, lim, D).astype(np.float32)
             self.variables["psi_y"] = self._rng.uniform(-lim, lim, D).astype(np.float32)
         self._backend = backend
-        self._last = None
 
     # ---- attributes of the reference object ----
     @property
@@ -257,42 +303,30 @@ class PsiCMPS(CMPS):
         p = (self.variables["psi_x"] + 1j * self.variables["psi_y"]).astype(np.complex64)   # model.py:221
         return _normalize_psi_host(p)                                                        # model.py:222
 
-    @property
-    def loss(self) -> np.float32:
-        """PsiCMPS.loss (model.py:224-225, 267): mean over the batch of the per-clip loss."""
-        if self.data_iterator is None:
-            raise AttributeError("loss: the model was built without a data_iterator (model.py:224)")
-        per_clip = self.loss_per_clip()
-        return np.float32(np.mean(per_clip, dtype=np.float32))
-
     # ---- backend plumbing ----
     def effective_params(self):
-        from .scan import EffectiveParams
-        return EffectiveParams(R=self.R, freqs=self.freqs, psi0=self.psi_0, A=float(self.A),
-                               sigma=float(self.sigma), delta_t=float(self.delta_t))
+        return self._effective(self.psi_0)
+
+    def _prepare(self, B, T, train):
+        be = self._get_backend()
+        be.set_params(self.effective_params(), B, T, train=train)
+        return be
 
     # ---- the hot path ----
     def loss_per_clip(self, data=None) -> np.ndarray:
         """The fold carry ``loss`` [B] of model.py:265-266 (forward only)."""
-        audio = self._to_device(self._batch(data))
-        B, T = audio.shape
-        be = self._get_backend()
-        be.set_params(self.effective_params(), B, T, train=False)
+        be, audio, _, _ = self._scan(data, train=False)
         return be.forward(audio, save_for_bwd=False).detach().cpu().numpy()
 
     def flat_size(self) -> int:
         """Length of the buffer grad_sums() returns (cmps_psi_loss_bwd's layout): what an empty shard adds to the all-reduce as zeros."""
-        from .scan import grad_size
-        return grad_size(self.bond_d)
+        return layout.grad_size(self.bond_d)
 
     def grad_sums(self, data=None):
         """Forward + reverse scan on this process's clips.  Returns (flat device/host buffer of SUMS over
         clips as laid out by cmps_psi_loss_bwd, number of clips).  Used by loss_and_grads and by the
         data-parallel trainer, which all-reduces the buffer before the chain rule."""
-        audio = self._to_device(self._batch(data))
-        B, T = audio.shape
-        be = self._get_backend()
-        be.set_params(self.effective_params(), B, T, train=True)
+        be, audio, B, _ = self._scan(data, train=True)
         _, grad = be.loss_and_grad_sums(audio, check=True)       # fp16-range check + documented fallback (include/cmps.h)
         return grad, B
 
@@ -300,16 +334,10 @@ class PsiCMPS(CMPS):
         """Effective-parameter gradient sums -> (mean loss, gradients w.r.t. the raw variables).
         Adjoint of model.py:36-42 (scaling + the row-broadcast diagonal removal), :49, :221-222, and
         optionally the regularisers of train.py:55-60."""
-        from .scan import unpack_grad
-        D = self.bond_d
-        g = unpack_grad(np.asarray(flat_sums, dtype=np.float64), D)
+        g = unpack_grad(np.asarray(flat_sums, dtype=np.float64), self.bond_d)
         invB = 1.0 / float(global_batch)
-        Rbar = g["Rbar"] * invB
-        fbar = g["fbar"] * invB
         p0bar = g["psi0bar"] * invB
-        Abar = g["Abar"] * invB
-        loss = g["loss_sum"] * invB
-        loss, grads = self._chain_common(Rbar, fbar, Abar, loss, with_reg)
+        loss, grads = self._chain_common(g["Rbar"] * invB, g["fbar"] * invB, g["Abar"] * invB, g["loss_sum"] * invB, with_reg)
         p = (self.variables["psi_x"].astype(np.float64) + 1j * self.variables["psi_y"].astype(np.float64))
         ss = float(np.sum(np.abs(p) ** 2))
         m = max(ss, 1e-12)
@@ -322,28 +350,15 @@ class PsiCMPS(CMPS):
         grads["psi_y"] = pbar.imag.astype(np.float32)
         return np.float32(loss), grads
 
-    def loss_and_grads(self, data=None, with_reg: bool = False):
-        """(loss, {variable: gradient}) of mean_b loss_b (+ train.py's regularisers if with_reg): what
-        ``AdamOptimizer.minimize`` obtains from TF (train.py:89)."""
-        flat, B = self.grad_sums(data)
-        host = flat.detach().cpu().numpy() if hasattr(flat, "detach") else np.asarray(flat)
-        self._last = host
-        return self.chain_rule(host, B, with_reg=with_reg)
-
     # ---- other reference methods on this class ----
     def _update_ancilla_psi(self, psi, signal, t):
         """model.py:300-317 for a batch of states (used by the reference's testTrivialUpdateOfAncilla)."""
-        be = self._get_backend()
         psi = np.asarray(psi, dtype=np.complex64)
-        be.set_params(self.effective_params(), psi.shape[0], 2, train=False)
-        return be.update_ancilla(psi, np.asarray(signal, dtype=np.float32), float(t))
+        return self._prepare(psi.shape[0], 2, train=False).update_ancilla(psi, np.asarray(signal, dtype=np.float32), float(t))
 
     def psi_evolve_with_data(self, data=None) -> np.ndarray:
         """model.py:231-240: the normalised state after every step, [B, T-1, D]."""
-        audio = self._to_device(self._batch(data))
-        B, T = audio.shape
-        be = self._get_backend()
-        be.set_params(self.effective_params(), B, T, train=True)
+        be, audio, _, _ = self._scan(data, train=True)
         be.forward(audio, save_for_bwd=True)
         return be.states()
 
@@ -351,16 +366,8 @@ class PsiCMPS(CMPS):
         """model.py:242-251: waveforms [num_samples, length] = A * running sum of the sampled increments.
         The Gaussian noise (stddev sigma * sqrt(temp * delta_t), model.py:246) is drawn on the host with a numpy
         Generator (``seed``), or passed in as ``noise`` [length, num_samples] like the reference's tensor."""
-        if noise is None:
-            rng = np.random.default_rng(seed)
-            std = float(self.sigma) * math.sqrt(temp * float(self.delta_t))
-            noise = (std * rng.standard_normal((length, num_samples))).astype(np.float32)
-        noise = np.asarray(noise, dtype=np.float32)
-        if noise.shape != (length, num_samples):
-            raise ValueError(f"noise must be [{length}, {num_samples}]")
-        be = self._get_backend()
-        be.set_params(self.effective_params(), num_samples, length + 1, train=False)
-        return be.sample(noise)
+        noise = self._noise(num_samples, length, temp, seed, noise)
+        return self._prepare(num_samples, length + 1, train=False).sample(noise)
 
 
 # --------------------------------------------------------------------------------------------------
@@ -373,6 +380,7 @@ class RhoCMPS(CMPS):
     ``rho_evolve_with_sampling``, ``purity``, ``sample``, ``_update_ancilla_rho``."""
 
     VARIABLE_NAMES = ("A", "Rx", "Ry", "freqs", "Wx", "Wy")
+    _LOSS_LINE = 69
 
     def __init__(self, hparams, W_in=None, *args, backend=None, **kwargs):
         super().__init__(hparams, *args, **kwargs)
@@ -391,7 +399,6 @@ class RhoCMPS(CMPS):
             self.variables["Wx"] = self._rng.uniform(-lim, lim, (self.rank_rho_0, D)).astype(np.float32)
             self.variables["Wy"] = self._rng.uniform(-lim, lim, (self.rank_rho_0, D)).astype(np.float32)
         self._backend = backend
-        self._last = None
 
     # ---- attributes of the reference object ----
     @property
@@ -410,19 +417,10 @@ class RhoCMPS(CMPS):
         t0 = float(np.sum(np.abs(W) ** 2))
         return (np.conj(W) / math.sqrt(t0)).astype(np.complex64)
 
-    @property
-    def loss(self) -> np.float32:
-        """RhoCMPS.loss (model.py:69-70, 144): mean over the batch of the per-clip loss."""
-        if self.data_iterator is None:
-            raise AttributeError("loss: the model was built without a data_iterator (model.py:69)")
-        return np.float32(np.mean(self.loss_per_clip(), dtype=np.float32))
-
     def effective_params(self):
-        from .scan import EffectiveParams
         e0 = np.zeros(self.bond_d, dtype=np.complex64)
         e0[0] = 1                                                  # the pure-state psi_0 slot is unused on this path
-        return EffectiveParams(R=self.R, freqs=self.freqs, psi0=e0, A=float(self.A),
-                               sigma=float(self.sigma), delta_t=float(self.delta_t))
+        return self._effective(e0)
 
     def _prepare(self, B, T, train):
         be = self._get_backend()
@@ -432,36 +430,26 @@ class RhoCMPS(CMPS):
 
     # ---- the scan ----
     def loss_per_clip(self, data=None) -> np.ndarray:
-        audio = self._to_device(self._batch(data))
-        B, T = audio.shape
-        be = self._prepare(B, T, train=False)
+        be, audio, _, _ = self._scan(data, train=False)
         return be.rho_forward(audio, save_for_bwd=False).detach().cpu().numpy()
 
     def flat_size(self) -> int:
         """Length of the buffer grad_sums() returns: the pure-state layout followed by the 2 rank D column cotangents
         (include/cmps.h: cmps_rho_loss_bwd)."""
-        from .scan import grad_size
-        return grad_size(self.bond_d) + 2 * self.rank_rho_0 * self.bond_d
+        return layout.grad_size(self.bond_d, self.rank_rho_0)
 
     def grad_sums(self, data=None):
         """(flat buffer of SUMS over this process's clips as laid out by cmps_rho_loss_bwd, number of clips)."""
-        audio = self._to_device(self._batch(data))
-        B, T = audio.shape
-        be = self._prepare(B, T, train=True)
+        be, audio, B, _ = self._scan(data, train=True)
         _, grad = be.rho_loss_and_grad_sums(audio)
         return grad, B
 
     def chain_rule(self, flat_sums: np.ndarray, global_batch: int, with_reg: bool = False):
         """Effective-parameter gradient sums -> (mean loss, gradients w.r.t. A, Rx, Ry, freqs, Wx, Wy)."""
-        from .scan import unpack_grad, grad_size
-        D, r = self.bond_d, self.rank_rho_0
-        flat = np.asarray(flat_sums, dtype=np.float64)
-        g = unpack_grad(flat, D)
+        g = unpack_grad(np.asarray(flat_sums, dtype=np.float64), self.bond_d, self.rank_rho_0)
         invB = 1.0 / float(global_batch)
-        loss, grads = self._chain_common(g["Rbar"] * invB, g["fbar"] * invB, g["Abar"] * invB, g["loss_sum"] * invB,
-                                         with_reg)
-        tail = flat[grad_size(D):grad_size(D) + 2 * r * D]
-        phibar = (tail[:r * D] + 1j * tail[r * D:]).reshape(r, D) * invB
+        loss, grads = self._chain_common(g["Rbar"] * invB, g["fbar"] * invB, g["Abar"] * invB, g["loss_sum"] * invB, with_reg)
+        phibar = g["phibar"] * invB
         # phi = p / |p|, p = conj(W) (all rank * D entries as one vector), then W = conj(p)        adjoint of :128-130
         W = self.W.astype(np.complex128)
         nrm = math.sqrt(float(np.sum(np.abs(W) ** 2)))
@@ -471,37 +459,19 @@ class RhoCMPS(CMPS):
         grads["Wy"] = (-pbar.imag).astype(np.float32)
         return np.float32(loss), grads
 
-    def loss_and_grads(self, data=None, with_reg: bool = False):
-        flat, B = self.grad_sums(data)
-        host = flat.detach().cpu().numpy() if hasattr(flat, "detach") else np.asarray(flat)
-        self._last = host
-        return self.chain_rule(host, B, with_reg=with_reg)
-
     # ---- other reference methods on this class ----
     def _update_ancilla_rho(self, rho, signal, t):
         """model.py:172-187 for a batch of density matrices [B, D, D]."""
         be = self._get_backend()
         rho = np.asarray(rho, dtype=np.complex64)
-        be.set_params(self.effective_params(), rho.shape[0], 2, train=False)
+        be.set_params(self.effective_params(), rho.shape[0], 2, train=False)      # (needs no cmps_rho_set_state)
         return be.rho_update_ancilla(rho, np.asarray(signal, dtype=np.float32), float(t))
 
     def rho_evolve_with_data(self, data=None) -> np.ndarray:
         """model.py:76-84: the normalised rho after every step, [B, T-1, D, D]."""
-        audio = self._to_device(self._batch(data))
-        B, T = audio.shape
-        be = self._prepare(B, T, train=True)
+        be, audio, B, T = self._scan(data, train=True)
         be.rho_forward(audio, save_for_bwd=True)
         return be.rho_states(B, T - 1, want_rho=True)
-
-    def _noise(self, num_samples, length, temp, seed, noise):
-        if noise is None:
-            rng = np.random.default_rng(seed)
-            std = float(self.sigma) * math.sqrt(temp * float(self.delta_t))                        # :88, 96, 106
-            noise = (std * rng.standard_normal((length, num_samples))).astype(np.float32)
-        noise = np.asarray(noise, dtype=np.float32)
-        if noise.shape != (length, num_samples):
-            raise ValueError(f"noise must be [{length}, {num_samples}]")
-        return noise
 
     def _sample_scan(self, num_samples, length, temp, seed, noise, save_states):
         noise = self._noise(num_samples, length, temp, seed, noise)
@@ -523,7 +493,7 @@ class RhoCMPS(CMPS):
         return be.rho_states(num_samples, length, want_rho=False, want_purity=True)
 
 
-class LegacyAudioMPS:
+class LegacyAudioMPS(_ScanModel):
     """The legacy ``AudioMPS`` arithmetic (reconstructed from logging/graph.pbtxt): real
     variables H, R [D,D] (glorot-uniform), H_s = tril(H) + tril(H)^T, psi_0 = e_0,
     loss = mean_b sum_k (x_k - 2 Re<psi|R|psi>)^2 / 2 evaluated BEFORE the update,
@@ -543,12 +513,7 @@ class LegacyAudioMPS:
             "H": rng.uniform(-lim, lim, (self.bond_d, self.bond_d)).astype(np.float32),
             "R": rng.uniform(-lim, lim, (self.bond_d, self.bond_d)).astype(np.float32)}
         self._backend = backend
-
-    def _get_backend(self):
-        if self._backend is None:
-            from .scan import HipScan
-            self._backend = HipScan(self.bond_d)
-        return self._backend
+        self._last = None
 
     @property
     def H_s(self) -> np.ndarray:
@@ -562,19 +527,13 @@ class LegacyAudioMPS:
         return ((np.complex64(-1j) * self.H_s.astype(np.complex64) - (RtR / np.float32(2)).astype(np.complex64))
                 * np.complex64(np.float32(self.delta_t))).astype(np.complex64)
 
-    def _audio(self, data):
-        import torch
-        data = self.data_iterator if data is None else data
-        if callable(data):
-            data = data()
+    def _prepare(self, B, T, train):
         be = self._get_backend()
-        t = data if isinstance(data, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(data, dtype=np.float32))
-        return t.to(be.device, dtype=torch.float32).contiguous()
+        be.legacy_set_params(self.variables["R"], self.Q, self.delta_t, B, T, train=train)
+        return be
 
     def loss_per_clip(self, data=None) -> np.ndarray:
-        audio = self._audio(data)
-        be = self._get_backend()
-        be.legacy_set_params(self.variables["R"], self.Q, self.delta_t, audio.shape[0], audio.shape[1], train=False)
+        be, audio, _, _ = self._scan(data, train=False)
         return be.legacy_forward(audio).detach().cpu().numpy()
 
     @property
@@ -583,23 +542,17 @@ class LegacyAudioMPS:
 
     def flat_size(self) -> int:
         """Length of the buffer grad_sums() returns (cmps_legacy_loss_bwd's layout)."""
-        return 3 * self.bond_d * self.bond_d + 1
+        return layout.size(layout.legacy_grad_fields(self.bond_d))
 
     def grad_sums(self, data=None):
-        audio = self._audio(data)
-        be = self._get_backend()
-        be.legacy_set_params(self.variables["R"], self.Q, self.delta_t, audio.shape[0], audio.shape[1], train=True)
+        be, audio, B, _ = self._scan(data, train=True)
         be.legacy_forward(audio, save_for_bwd=True)
-        return be.legacy_backward(), audio.shape[0]
+        return be.legacy_backward(), B
 
     def chain_rule(self, flat_sums, global_batch: int, with_reg: bool = False):
         """(dQ, dR_direct) sums -> gradients w.r.t. H and R  (adjoint of Q = dt (-i H_s - R^T R / 2), H_s = L + L^T)."""
-        D = self.bond_d
-        g = np.asarray(flat_sums, dtype=np.float64) / float(global_batch)
-        DD = D * D
-        Qbar = (g[:DD] + 1j * g[DD:2 * DD]).reshape(D, D)
-        Rdir = g[2 * DD:3 * DD].reshape(D, D)
-        loss = g[3 * DD]
+        g = layout.unpack(layout.legacy_grad_fields(self.bond_d), np.asarray(flat_sums, dtype=np.float64) / float(global_batch))
+        Qbar, Rdir, loss = layout.join(g, "Q"), g["R"], g["loss_sum"]
         dt = float(np.float32(self.delta_t))
         R = self.variables["R"].astype(np.float64)
         Hs_bar = -dt * Qbar.imag
@@ -607,10 +560,6 @@ class LegacyAudioMPS:
         gR = Rdir + R @ (M_bar + M_bar.T)
         gH = np.tril(Hs_bar + Hs_bar.T)
         return np.float32(loss), {"H": gH.astype(np.float32), "R": gR.astype(np.float32)}
-
-    def loss_and_grads(self, data=None, with_reg: bool = False):
-        flat, B = self.grad_sums(data)
-        return self.chain_rule(flat.detach().cpu().numpy(), B)
 
 
 class AudioMPS(PsiCMPS):

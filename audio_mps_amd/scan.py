@@ -8,41 +8,24 @@ from __future__ import annotations
 
 import ctypes
 import os
-from dataclasses import dataclass
 from typing import Optional
 
 import numpy as np
 import torch
 
-from . import _capi
+from . import _capi, layout
+from .layout import EffectiveParams, grad_size, unpack_grad  # noqa: F401  (their historical home: tests and scripts import them from here)
 
 
-@dataclass
-class EffectiveParams:
-    """What CMPS.__init__ / PsiCMPS.__init__ hand to the scan (model.py:41-52, 221-222)."""
-    R: np.ndarray        # [D, D] complex64, after the diagonal removal of model.py:42
-    freqs: np.ndarray    # [D] float32
-    psi0: np.ndarray     # [D] complex64, normalised
-    A: float
-    sigma: float
-    delta_t: float
+def _to_interleaved(z: np.ndarray, device) -> torch.Tensor:
+    """Complex host array [...] -> float32 device tensor [..., 2] (re, im): the ABI's layout of states and matrices."""
+    inter = np.stack([z.real, z.imag], axis=-1).astype(np.float32)
+    return torch.from_numpy(np.ascontiguousarray(inter)).to(device)
 
 
-def grad_size(D: int) -> int:
-    return 2 * D * D + 3 * D + 2
-
-
-def unpack_grad(flat, D: int):
-    """Flat buffer of cmps_psi_loss_bwd -> dict (sums over clips)."""
-    g = np.asarray(flat)
-    DD = D * D
-    return {
-        "Rbar": (g[:DD] + 1j * g[DD:2 * DD]).reshape(D, D),
-        "fbar": g[2 * DD:2 * DD + D],
-        "psi0bar": g[2 * DD + D:2 * DD + 2 * D] + 1j * g[2 * DD + 2 * D:2 * DD + 3 * D],
-        "Abar": g[2 * DD + 3 * D],
-        "loss_sum": g[2 * DD + 3 * D + 1],
-    }
+def _from_interleaved(t: torch.Tensor) -> np.ndarray:
+    o = t.cpu().numpy()
+    return (o[..., 0] + 1j * o[..., 1]).astype(np.complex64)
 
 
 class HipScan:
@@ -52,6 +35,7 @@ class HipScan:
 
     def __init__(self, D: int, device: Optional[torch.device] = None, variant: int = _capi.CMPS_VARIANT_AUTO,
                  rank1: Optional[int] = None):
+        self._h = None                # (first: __del__ runs even when a line below raises)
         self._lib = _capi.load()
         if not torch.cuda.is_available():
             raise RuntimeError("HipScan needs a GPU (torch.cuda.is_available() is False); there is no CPU fallback")
@@ -67,22 +51,28 @@ class HipScan:
             self.set_rank1(rank1)
         if os.environ.get("CMPS_BWD_WAVES"):            # diagnostic (like CMPS_LIB): A/B of the one- and two-wave reverse scans without code changes
             _capi.check(self._h, self._lib.cmps_set_option(self._h, _capi.CMPS_OPT_BWD_WAVES, int(os.environ["CMPS_BWD_WAVES"])))
-        self._ws = None
-        self._ws_key = None
-        self._param_buf = torch.empty(2 * D * D + 3 * D, dtype=torch.float32, device=self.device)
-        self._param_host = torch.empty(2 * D * D + 3 * D, dtype=torch.float32).pin_memory()
+        self._mode = "psi"            # which arithmetic the handle was last configured for: set_params* -> "psi", legacy_set_params -> "legacy"
+        self._ws = {"main": None, "rho": None}        # caller-owned workspaces of the C ABI, keyed by the shape they were sized for
+        self._ws_key = {"main": None, "rho": None}
+        self._ws_fresh = False        # the main workspace was (re)allocated since the last set_params*: its cached tables are gone
+        self._n_params = layout.size(layout.param_fields(self.D))
+        self._param_buf = torch.empty(self._n_params, dtype=torch.float32, device=self.device)
+        self._param_host = torch.empty(self._n_params, dtype=torch.float32).pin_memory()
         self._param_evt = None
-        self._B = self._T = 0
+        self._legacy_buf = self._phi_buf = None       # the last legacy_set_params / rho_set_state upload (kept alive for the stream)
+        self._opt_scratch = None
+        self._B = self._T = self._rho_rank = 0
         self._audio = None
         self._loss = None
         self._grad = torch.empty(grad_size(D), dtype=torch.float32, device=self.device)
+        self._legacy_grad = self._rho_grad = None
         self.f16_fallbacks = 0        # loss_and_grad_sums(check=True) re-runs that cmps_psi_grad_status asked for
         self.timing = None            # a list: forward() / backward() then append HIP-event pairs around their launches (bench.py)
 
     # ------------------------------------------------------------------
     def __del__(self):
         try:
-            if getattr(self, "_h", None):
+            if self._h:
                 self._lib.cmps_destroy(self._h)
                 self._h = None
         except Exception:
@@ -115,7 +105,7 @@ class HipScan:
         exact fp32, two bf16 pieces, two fp16 pieces (also for DEFAULT) and three bf16 pieces.  (The 16-row kernels of D <= 16 always
         use exact fp32 MFMAs and the legacy mode maps the fp16 form to three bf16 pieces: this property describes the 32-row kernel.)"""
         mode, wide = self.rank1, self.variant == _capi.CMPS_VARIANT_WIDE
-        if getattr(self, "_legacy_buf", None) is not None and not wide:        # a handle in legacy mode (legacy_set_params): the wave
+        if self._mode == "legacy" and not wide:        # a handle in legacy mode (legacy_set_params): the wave
             # reverse scan's legacy instance has no fp16 form -- F16X2 / DEFAULT run three bf16 pieces (include/cmps.h's table)
             return mode if mode in (_capi.CMPS_RANK1_EXACT_F32, _capi.CMPS_RANK1_BF16X2) else _capi.CMPS_RANK1_BF16X3
         if wide:
@@ -131,7 +121,6 @@ class HipScan:
 
     def kernel_times(self) -> dict:
         """cmps_kernel_times: {kernel name: (summed ms, launches)} since the last call, in first-launch order (synchronises)."""
-        import ctypes
         cap = 32
         names = ctypes.create_string_buffer(2048)
         ms = (ctypes.c_float * cap)()
@@ -145,77 +134,79 @@ class HipScan:
     def _stream(self):
         return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
-    def workspace_bytes(self, B: int, T: int, train: bool) -> int:
-        return int(self._lib.cmps_workspace_bytes(self.D, B, T, _capi.CMPS_WS_TRAIN if train else _capi.CMPS_WS_FWD_ONLY))
+    @staticmethod
+    def _ws_flags(train: bool, fresh: bool = True) -> int:
+        """The `flags` word of cmps_*workspace_bytes / cmps_*set_*.  fresh=False: this object owns the workspace and has not touched it
+        since its previous set_params* -- keep the time table (CMPS_WS_REUSE_TABLES; without it every table is rebuilt)."""
+        flags = _capi.CMPS_WS_TRAIN if train else _capi.CMPS_WS_FWD_ONLY
+        return flags if fresh else flags | _capi.CMPS_WS_REUSE_TABLES
 
-    def _ensure_ws(self, B: int, T: int, train: bool):
-        key = (B, T, train)
-        if self._ws_key != key:
-            nbytes = self.workspace_bytes(B, T, train)
+    def workspace_bytes(self, B: int, T: int, train: bool) -> int:
+        return int(self._lib.cmps_workspace_bytes(self.D, B, T, self._ws_flags(train)))
+
+    def _workspace(self, B: int, T: int, train: bool, rank: Optional[int] = None):
+        """(256-byte aligned address, usable bytes) of the main workspace (rank None) or of the rho workspace of `rank` columns,
+        (re)allocated when the shape it was sized for changes."""
+        which, key = ("main" if rank is None else "rho"), (rank, B, T, train)
+        if self._ws_key[which] != key:
+            nbytes = self.workspace_bytes(B, T, train) if rank is None else \
+                int(self._lib.cmps_rho_workspace_bytes(self.D, rank, B, T, self._ws_flags(train)))
             if nbytes == 0:
-                raise ValueError(f"invalid shape for the scan: D={self.D}, B={B}, T={T}")
-            self._ws = None
-            self._ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=self.device)
-            self._ws_key = key
-            self._ws_fresh = True         # the allocator may hand back the old address: the cached tables are gone
-        base = self._ws.data_ptr()
-        return (base + 255) // 256 * 256, self._ws.numel() - 256
+                what = "scan" if rank is None else f"rho scan (rank={rank})"
+                raise ValueError(f"invalid shape for the {what}: D={self.D}, B={B}, T={T}")
+            self._ws[which] = None        # (free before allocating)
+            self._ws[which] = torch.empty(nbytes + 256, dtype=torch.uint8, device=self.device)
+            self._ws_key[which] = key
+            if rank is None:
+                self._ws_fresh = True     # the allocator may hand back the old address: the cached tables are gone
+        ws = self._ws[which]
+        return (ws.data_ptr() + 255) // 256 * 256, ws.numel() - 256
+
+    def _psi_workspace(self, B: int, T: int, train: bool):
+        """set_params*: (flags, address, bytes) of the main workspace, as the C ABI takes them."""
+        ws_ptr, ws_bytes = self._workspace(B, T, train)
+        flags = self._ws_flags(train, self._ws_fresh)
+        self._ws_fresh = False
+        return flags, ws_ptr, ws_bytes
+
+    def _upload(self, fields, values):
+        """Pack `values` as the layout `fields` -> (device tensor, address of every field)."""
+        buf = torch.from_numpy(layout.pack(fields, values)).to(self.device)
+        return buf, layout.pointers(buf.data_ptr(), fields)
 
     # ------------------------------------------------------------------
     def set_params(self, p: EffectiveParams, B: int, T: int, train: bool = True):
         """cmps_set_params: upload the effective parameters and rebuild the derived tables."""
         D = self.D
-        R = np.asarray(p.R)
-        if R.shape != (D, D):
+        if np.shape(p.R) != (D, D):
             raise ValueError(f"R must be [{D},{D}]")
         if self._param_evt is not None:
             self._param_evt.synchronize()  # the previous upload must have left the pinned buffer
-        host = self._param_host.numpy()
-        DD = D * D
-        host[:DD] = R.real.astype(np.float32).ravel()
-        host[DD:2 * DD] = R.imag.astype(np.float32).ravel()
-        host[2 * DD:2 * DD + D] = np.asarray(p.freqs, dtype=np.float32)
-        psi0 = np.asarray(p.psi0)
-        host[2 * DD + D:2 * DD + 2 * D] = psi0.real.astype(np.float32)
-        host[2 * DD + 2 * D:2 * DD + 3 * D] = psi0.imag.astype(np.float32)
+        fields = layout.param_fields(D)
+        layout.pack(fields, {**layout.split("R", p.R), "freqs": p.freqs, **layout.split("psi0", p.psi0)}, out=self._param_host.numpy())
         self._param_buf.copy_(self._param_host, non_blocking=True)
         self._param_evt = torch.cuda.Event()
         self._param_evt.record(torch.cuda.current_stream(self.device))
-        ws_ptr, ws_bytes = self._ensure_ws(B, T, train)
-        base = self._param_buf.data_ptr()
-        f4 = 4
-        flags = _capi.CMPS_WS_TRAIN if train else _capi.CMPS_WS_FWD_ONLY
-        if getattr(self, "_ws_fresh", False):
-            self._ws_fresh = False              # (re)allocated since the last call: every table is rebuilt (the library's default)
-        else:
-            flags |= _capi.CMPS_WS_REUSE_TABLES  # this object owns the workspace and has not touched it: keep the time table
         _capi.check(self._h, self._lib.cmps_set_params(
-            self._h, base, base + DD * f4, base + 2 * DD * f4, base + (2 * DD + D) * f4,
-            base + (2 * DD + 2 * D) * f4, float(p.A), float(p.sigma), float(p.delta_t), int(T), int(B),
-            flags, ws_ptr, ws_bytes, self._stream()))
-        self._B, self._T, self._train = B, T, train
+            self._h, *layout.pointers(self._param_buf.data_ptr(), fields), float(p.A), float(p.sigma), float(p.delta_t), int(T), int(B),
+            *self._psi_workspace(B, T, train), self._stream()))
+        self._B, self._T, self._mode = B, T, "psi"
 
     def set_params_dev(self, params: torch.Tensor, sigma: float, delta_t: float, B: int, T: int, train: bool = True):
         """cmps_set_params_dev: the effective parameters (A included) are read from the device buffer `params`
         [2 D^2 + 3 D + 1] that cmps_psi_apply_step wrote -- no host copy, no synchronisation."""
-        if not (params.is_cuda and params.dtype == torch.float32 and params.numel() == 2 * self.D * self.D + 3 * self.D + 1):
+        if not (params.is_cuda and params.dtype == torch.float32 and params.numel() == self._n_params + 1):
             raise ValueError("params must be a float32 CUDA tensor of 2 D^2 + 3 D + 1 elements")
-        ws_ptr, ws_bytes = self._ensure_ws(B, T, train)
-        flags = _capi.CMPS_WS_TRAIN if train else _capi.CMPS_WS_FWD_ONLY
-        if getattr(self, "_ws_fresh", False):
-            self._ws_fresh = False              # (re)allocated since the last call: every table is rebuilt (the library's default)
-        else:
-            flags |= _capi.CMPS_WS_REUSE_TABLES  # this object owns the workspace and has not touched it: keep the time table
         _capi.check(self._h, self._lib.cmps_set_params_dev(self._h, params.data_ptr(), float(sigma), float(delta_t), int(T), int(B),
-                                                           flags, ws_ptr, ws_bytes, self._stream()))
-        self._B, self._T, self._train = B, T, train
+                                                           *self._psi_workspace(B, T, train), self._stream()))
+        self._B, self._T, self._mode = B, T, "psi"
 
     def apply_step(self, vars_: torch.Tensor, m: torch.Tensor, v: torch.Tensor, grad_sums: Optional[torch.Tensor], global_batch: int,
                    lr_t: float, beta1: float, beta2: float, eps: float, h_reg: float, r_reg: float, c_r: float, c_h: float,
                    with_reg: bool, params: torch.Tensor, losses: torch.Tensor):
         """cmps_psi_apply_step: chain rule + regularisers + Adam + next effective parameters, on the device (grad_sums None: only
         the effective parameters of `vars_`)."""
-        if getattr(self, "_opt_scratch", None) is None:
+        if self._opt_scratch is None:
             n = int(self._lib.cmps_apply_step_scratch_bytes(self.D))
             self._opt_scratch = torch.empty((n + 7) // 8, dtype=torch.float64, device=self.device)
         _capi.check(self._h, self._lib.cmps_psi_apply_step(
@@ -232,17 +223,38 @@ class HipScan:
             raise ValueError(f"audio shape {tuple(audio.shape)} does not fit set_params(B={self._B}, T={self._T})")
         return B, T
 
-    def forward(self, audio: torch.Tensor, save_for_bwd: bool = False) -> torch.Tensor:
-        """Per-clip loss [B] (device tensor): cmps_psi_loss_fwd."""
+    def _forward(self, fn, audio: torch.Tensor, save_for_bwd: bool, timed: bool = False) -> torch.Tensor:
+        """The one forward driver: `fn` is cmps_{psi,legacy,rho}_loss_fwd.  Returns this object's per-clip loss tensor [B]."""
         B, T = self._check_audio(audio)
         if self._loss is None or self._loss.numel() != B:
             self._loss = torch.empty(B, dtype=torch.float32, device=self.device)
-        ev = self._event_pair()
-        _capi.check(self._h, self._lib.cmps_psi_loss_fwd(
-            self._h, audio.data_ptr(), B, T, self._loss.data_ptr(), 1 if save_for_bwd else 0, self._stream()))
+        ev = self._event_pair() if timed else None
+        _capi.check(self._h, fn(self._h, audio.data_ptr(), B, T, self._loss.data_ptr(), 1 if save_for_bwd else 0, self._stream()))
         self._event_close("fwd", ev)
         self._audio = audio
         return self._loss
+
+    def _backward(self, fn, grad: Optional[torch.Tensor], n: int, who: str = "", timed: bool = False) -> torch.Tensor:
+        """The one backward driver: `fn` is cmps_{psi,legacy,rho}_loss_bwd, `grad` the caller's buffer for its `n` gradient sums
+        (replaced when it does not fit), which is returned."""
+        audio = self._audio
+        if audio is None:
+            raise RuntimeError(f"{who}backward() needs {who}forward(save_for_bwd=True) first")
+        B, T = audio.shape
+        if grad is None or grad.numel() != n:
+            grad = torch.empty(n, dtype=torch.float32, device=self.device)
+        ev = self._event_pair() if timed else None
+        _capi.check(self._h, fn(self._h, audio.data_ptr(), B, T, grad.data_ptr(), self._stream()))
+        self._event_close("bwd", ev)
+        return grad
+
+    def forward(self, audio: torch.Tensor, save_for_bwd: bool = False) -> torch.Tensor:
+        """Per-clip loss [B] (device tensor): cmps_psi_loss_fwd."""
+        return self._forward(self._lib.cmps_psi_loss_fwd, audio, save_for_bwd, timed=True)
+
+    def backward(self) -> torch.Tensor:
+        """Flat gradient sums [2D^2+3D+2] (device tensor): cmps_psi_loss_bwd after forward(save_for_bwd=True)."""
+        return self._backward(self._lib.cmps_psi_loss_bwd, self._grad, self._grad.numel(), timed=True)
 
     # HIP events on the stream the kernels are launched on (torch's current stream is the one handed to the C ABI); they are read
     # only after the caller has synchronised (timing_ms), so recording them never stalls the host
@@ -265,18 +277,6 @@ class HipScan:
         for what, e0, e1 in self.timing or []:
             out[what].append(e0.elapsed_time(e1))
         return out
-
-    def backward(self) -> torch.Tensor:
-        """Flat gradient sums [2D^2+3D+2] (device tensor): cmps_psi_loss_bwd after forward(save_for_bwd=True)."""
-        audio = self._audio
-        if audio is None:
-            raise RuntimeError("backward() needs forward(save_for_bwd=True) first")
-        B, T = audio.shape
-        ev = self._event_pair()
-        _capi.check(self._h, self._lib.cmps_psi_loss_bwd(
-            self._h, audio.data_ptr(), B, T, self._grad.data_ptr(), self._stream()))
-        self._event_close("bwd", ev)
-        return self._grad
 
     def grad_status(self):
         """cmps_psi_grad_status: (code, sticky flags).  Waits for the stream.  code = CMPS_ERR_F16_RANGE when the last backward()
@@ -314,20 +314,29 @@ class HipScan:
         return loss, grad
 
     # ------------------------------------------------------------------
-    def update_ancilla(self, psi: np.ndarray, signal: np.ndarray, t: float) -> np.ndarray:
-        """PsiCMPS._update_ancilla_psi for a batch of states (host arrays in, host array out)."""
-        psi = np.asarray(psi, dtype=np.complex64)
-        B, D = psi.shape
-        if D != self.D:
-            raise ValueError("psi has the wrong bond dimension")
-        inter = np.stack([psi.real, psi.imag], axis=-1).astype(np.float32)
-        d_in = torch.from_numpy(np.ascontiguousarray(inter)).to(self.device)
+    def _ancilla(self, fn, what: str, x: np.ndarray, signal: np.ndarray, t: float) -> np.ndarray:
+        """One update step of a batch of states [B, D] / matrices [B, D, D] (host in, host out): `fn` is cmps_{psi,rho}_update_ancilla."""
+        x = np.asarray(x, dtype=np.complex64)
+        if x.shape[1:] != (self.D,) * (1 if what == "psi" else 2):
+            raise ValueError(f"{what} has the wrong bond dimension")
+        d_in = _to_interleaved(x, self.device)
         d_sig = torch.from_numpy(np.ascontiguousarray(signal, dtype=np.float32)).to(self.device)
         d_out = torch.empty_like(d_in)
-        _capi.check(self._h, self._lib.cmps_psi_update_ancilla(
-            self._h, d_in.data_ptr(), d_sig.data_ptr(), float(t), B, d_out.data_ptr(), self._stream()))
-        o = d_out.cpu().numpy()
-        return (o[..., 0] + 1j * o[..., 1]).astype(np.complex64)
+        _capi.check(self._h, fn(self._h, d_in.data_ptr(), d_sig.data_ptr(), float(t), x.shape[0], d_out.data_ptr(), self._stream()))
+        return _from_interleaved(d_out)
+
+    def _sample(self, fn, noise: np.ndarray, *flags) -> np.ndarray:
+        """Pre-drawn noise [length, n] (the reference's layout) up, waveforms [n, length] down: `fn` is cmps_{psi,rho}_sample."""
+        noise = np.asarray(noise, dtype=np.float32)
+        length, n = noise.shape
+        d_noise = torch.from_numpy(np.ascontiguousarray(noise.T)).to(self.device)
+        d_out = torch.empty((n, length), dtype=torch.float32, device=self.device)
+        _capi.check(self._h, fn(self._h, d_noise.data_ptr(), n, length, d_out.data_ptr(), *flags, self._stream()))
+        return d_out.cpu().numpy()
+
+    def update_ancilla(self, psi: np.ndarray, signal: np.ndarray, t: float) -> np.ndarray:
+        """PsiCMPS._update_ancilla_psi for a batch of states (host arrays in, host array out)."""
+        return self._ancilla(self._lib.cmps_psi_update_ancilla, "psi", psi, signal, t)
 
     def states(self) -> np.ndarray:
         """Normalised lab-frame psi after every step, [B, T-1, D] complex64 (psi_evolve_with_data)."""
@@ -337,59 +346,34 @@ class HipScan:
         B, T = audio.shape
         out = torch.empty((B, T - 1, self.D, 2), dtype=torch.float32, device=self.device)
         _capi.check(self._h, self._lib.cmps_psi_states(self._h, B, T, out.data_ptr(), self._stream()))
-        o = out.cpu().numpy()
-        return (o[..., 0] + 1j * o[..., 1]).astype(np.complex64)
+        return _from_interleaved(out)
 
     def sample(self, noise: np.ndarray) -> np.ndarray:
         """PsiCMPS.sample for pre-drawn noise [length, n] (the reference's layout) -> waveforms [n, length]."""
-        noise = np.asarray(noise, dtype=np.float32)
-        length, n = noise.shape
-        d_noise = torch.from_numpy(np.ascontiguousarray(noise.T)).to(self.device)
-        d_out = torch.empty((n, length), dtype=torch.float32, device=self.device)
-        _capi.check(self._h, self._lib.cmps_psi_sample(self._h, d_noise.data_ptr(), n, length, d_out.data_ptr(),
-                                                       self._stream()))
-        return d_out.cpu().numpy()
+        return self._sample(self._lib.cmps_psi_sample, noise)
 
     # ------------------------------------------------------------------
     # legacy AudioMPS arithmetic (SURVEY 8f rank 2)
     # ------------------------------------------------------------------
     def legacy_set_params(self, R: np.ndarray, Q: np.ndarray, delta_t: float, B: int, T: int, train: bool = True):
-        D = self.D
-        DD = D * D
-        buf = torch.from_numpy(np.concatenate([np.asarray(R, dtype=np.float32).ravel(),
-                                               np.asarray(Q).real.astype(np.float32).ravel(),
-                                               np.asarray(Q).imag.astype(np.float32).ravel()])).to(self.device)
-        self._legacy_buf = buf
-        ws_ptr, ws_bytes = self._ensure_ws(B, T, train)
-        base = buf.data_ptr()
+        self._legacy_buf, ptrs = self._upload(layout.legacy_param_fields(self.D), {"R": R, **layout.split("Q", Q)})
         _capi.check(self._h, self._lib.cmps_legacy_set_params(
-            self._h, base, base + DD * 4, base + 2 * DD * 4, float(delta_t), int(T), int(B),
-            _capi.CMPS_WS_TRAIN if train else _capi.CMPS_WS_FWD_ONLY, ws_ptr, ws_bytes, self._stream()))
-        self._B, self._T, self._train = B, T, train
+            self._h, *ptrs, float(delta_t), int(T), int(B), self._ws_flags(train), *self._workspace(B, T, train), self._stream()))
+        self._B, self._T, self._mode = B, T, "legacy"
 
     def legacy_forward(self, audio: torch.Tensor, save_for_bwd: bool = False) -> torch.Tensor:
-        B, T = self._check_audio(audio)
-        if self._loss is None or self._loss.numel() != B:
-            self._loss = torch.empty(B, dtype=torch.float32, device=self.device)
-        _capi.check(self._h, self._lib.cmps_legacy_loss_fwd(
-            self._h, audio.data_ptr(), B, T, self._loss.data_ptr(), 1 if save_for_bwd else 0, self._stream()))
-        self._audio = audio
-        return self._loss
+        return self._forward(self._lib.cmps_legacy_loss_fwd, audio, save_for_bwd)
 
     def legacy_backward(self) -> torch.Tensor:
-        audio = self._audio
-        B, T = audio.shape
-        if getattr(self, "_legacy_grad", None) is None:
-            self._legacy_grad = torch.empty(3 * self.D * self.D + 1, dtype=torch.float32, device=self.device)
-        _capi.check(self._h, self._lib.cmps_legacy_loss_bwd(
-            self._h, audio.data_ptr(), B, T, self._legacy_grad.data_ptr(), self._stream()))
+        self._legacy_grad = self._backward(self._lib.cmps_legacy_loss_bwd, self._legacy_grad,
+                                           layout.size(layout.legacy_grad_fields(self.D)), "legacy_")
         return self._legacy_grad
 
     # ------------------------------------------------------------------
     # RhoCMPS (SURVEY 8f rank 3): the density matrix carried as its `rank` columns
     # ------------------------------------------------------------------
     def rho_grad_size(self, rank: int) -> int:
-        return grad_size(self.D) + 2 * rank * self.D
+        return grad_size(self.D, rank)
 
     def rho_set_state(self, phi: np.ndarray, B: int, T: int, train: bool = True):
         """cmps_rho_set_state: phi [rank, D] complex, rho_0 = sum_a phi_a phi_a^dagger.  After set_params."""
@@ -397,42 +381,17 @@ class HipScan:
         r, D = phi.shape
         if D != self.D:
             raise ValueError("phi has the wrong bond dimension")
-        flags = _capi.CMPS_WS_TRAIN if train else _capi.CMPS_WS_FWD_ONLY
-        nbytes = int(self._lib.cmps_rho_workspace_bytes(D, r, B, T, flags))
-        if nbytes == 0:
-            raise ValueError(f"invalid shape for the rho scan: D={D}, rank={r}, B={B}, T={T}")
-        key = (r, B, T, train)
-        if getattr(self, "_rho_ws_key", None) != key:
-            self._rho_ws = None
-            self._rho_ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=self.device)
-            self._rho_ws_key = key
-        base = (self._rho_ws.data_ptr() + 255) // 256 * 256
-        host = np.concatenate([phi.real.astype(np.float32).ravel(), phi.imag.astype(np.float32).ravel()])
-        self._phi_buf = torch.from_numpy(host).to(self.device)
-        pb = self._phi_buf.data_ptr()
+        ws_ptr, ws_bytes = self._workspace(B, T, train, rank=r)
+        self._phi_buf, ptrs = self._upload(layout.phi_fields(D, r), layout.split("phi", phi))
         _capi.check(self._h, self._lib.cmps_rho_set_state(
-            self._h, pb, pb + r * D * 4, r, int(T), int(B), flags, base, self._rho_ws.numel() - 256, self._stream()))
-        self._rho_rank, self._rho_B, self._rho_T = r, B, T
+            self._h, *ptrs, r, int(T), int(B), self._ws_flags(train), ws_ptr, ws_bytes, self._stream()))
+        self._rho_rank = r
 
     def rho_forward(self, audio: torch.Tensor, save_for_bwd: bool = False) -> torch.Tensor:
-        B, T = self._check_audio(audio)
-        if self._loss is None or self._loss.numel() != B:
-            self._loss = torch.empty(B, dtype=torch.float32, device=self.device)
-        _capi.check(self._h, self._lib.cmps_rho_loss_fwd(
-            self._h, audio.data_ptr(), B, T, self._loss.data_ptr(), 1 if save_for_bwd else 0, self._stream()))
-        self._audio = audio
-        return self._loss
+        return self._forward(self._lib.cmps_rho_loss_fwd, audio, save_for_bwd)
 
     def rho_backward(self) -> torch.Tensor:
-        audio = self._audio
-        if audio is None:
-            raise RuntimeError("rho_backward() needs rho_forward(save_for_bwd=True) first")
-        B, T = audio.shape
-        n = self.rho_grad_size(self._rho_rank)
-        if getattr(self, "_rho_grad", None) is None or self._rho_grad.numel() != n:
-            self._rho_grad = torch.empty(n, dtype=torch.float32, device=self.device)
-        _capi.check(self._h, self._lib.cmps_rho_loss_bwd(
-            self._h, audio.data_ptr(), B, T, self._rho_grad.data_ptr(), self._stream()))
+        self._rho_grad = self._backward(self._lib.cmps_rho_loss_bwd, self._rho_grad, self.rho_grad_size(self._rho_rank), "rho_")
         return self._rho_grad
 
     def rho_loss_and_grad_sums(self, audio: torch.Tensor):
@@ -441,28 +400,11 @@ class HipScan:
 
     def rho_update_ancilla(self, rho: np.ndarray, signal: np.ndarray, t: float) -> np.ndarray:
         """RhoCMPS._update_ancilla_rho for a batch of matrices [B, D, D] (host in, host out)."""
-        rho = np.asarray(rho, dtype=np.complex64)
-        B, D, D2 = rho.shape
-        if D != self.D or D2 != self.D:
-            raise ValueError("rho has the wrong bond dimension")
-        inter = np.stack([rho.real, rho.imag], axis=-1).astype(np.float32)
-        d_in = torch.from_numpy(np.ascontiguousarray(inter)).to(self.device)
-        d_sig = torch.from_numpy(np.ascontiguousarray(signal, dtype=np.float32)).to(self.device)
-        d_out = torch.empty_like(d_in)
-        _capi.check(self._h, self._lib.cmps_rho_update_ancilla(
-            self._h, d_in.data_ptr(), d_sig.data_ptr(), float(t), B, d_out.data_ptr(), self._stream()))
-        o = d_out.cpu().numpy()
-        return (o[..., 0] + 1j * o[..., 1]).astype(np.complex64)
+        return self._ancilla(self._lib.cmps_rho_update_ancilla, "rho", rho, signal, t)
 
     def rho_sample(self, noise: np.ndarray, save_states: bool = False) -> np.ndarray:
         """RhoCMPS.sample for pre-drawn noise [length, n] -> waveforms [n, length]."""
-        noise = np.asarray(noise, dtype=np.float32)
-        length, n = noise.shape
-        d_noise = torch.from_numpy(np.ascontiguousarray(noise.T)).to(self.device)
-        d_out = torch.empty((n, length), dtype=torch.float32, device=self.device)
-        _capi.check(self._h, self._lib.cmps_rho_sample(self._h, d_noise.data_ptr(), n, length, d_out.data_ptr(),
-                                                       1 if save_states else 0, self._stream()))
-        return d_out.cpu().numpy()
+        return self._sample(self._lib.cmps_rho_sample, noise, 1 if save_states else 0)
 
     def rho_states(self, B: int, steps: int, want_rho: bool = True, want_purity: bool = False):
         """Lab-frame rho [B, steps, D, D] and/or purity [B, steps] of the last saved scan."""
@@ -472,10 +414,5 @@ class HipScan:
         _capi.check(self._h, self._lib.cmps_rho_states(
             self._h, B, steps, d_rho.data_ptr() if want_rho else None, d_pur.data_ptr() if want_purity else None,
             self._stream()))
-        out = []
-        if want_rho:
-            o = d_rho.cpu().numpy()
-            out.append((o[..., 0] + 1j * o[..., 1]).astype(np.complex64))
-        if want_purity:
-            out.append(d_pur.cpu().numpy())
+        out = ([_from_interleaved(d_rho)] if want_rho else []) + ([d_pur.cpu().numpy()] if want_purity else [])
         return out[0] if len(out) == 1 else tuple(out)

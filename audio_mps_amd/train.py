@@ -18,10 +18,14 @@ import argparse
 import math
 import os
 import time
+import weakref
+from collections import deque
 from typing import Dict, Optional
 
 import numpy as np
 
+from . import layout
+from .layout import VAR_ORDER  # noqa: F401  (bench.py imports it from here)
 from .model import HParams, PsiCMPS, RhoCMPS
 from .parallel import DataParallel
 
@@ -58,9 +62,6 @@ class AdamOptimizer:
         self.v = {k[2:]: np.asarray(v) for k, v in sd.items() if k.startswith("v/")}
 
 
-VAR_ORDER = ("A", "Rx", "Ry", "freqs", "psi_x", "psi_y")      # layout of the device-resident variable / Adam-slot buffers (include/cmps.h)
-
-
 class Trainer:
     """One optimiser step = parameter tables, forward scan, reverse scan, (all-reduce), chain rule, Adam.
 
@@ -74,7 +75,6 @@ class Trainer:
     HISTORY = 4096                # step records kept (a long run must not grow without bound)
 
     def __init__(self, model: PsiCMPS, hparams: HParams, dp: Optional[DataParallel] = None, device_step: bool = False):
-        from collections import deque
         self.model = model
         self.hparams = hparams
         self.dp = dp if dp is not None else DataParallel()
@@ -82,7 +82,10 @@ class Trainer:
         self.global_step = 0
         self.history = deque(maxlen=self.HISTORY)   # the dict of every step (the scalar summaries of train.py:62-66)
         self.device_step = bool(device_step)
-        self._dev = None
+        self._dev = None              # device-resident step: {"vars", "m", "v", "params", "losses"} device tensors (_device_state)
+        self._dirty = False           # a device step has run since the last sync: the host copies are stale
+        self._syncing = False         # inside _lazy_sync (sync_to_host reads model.variables, which calls _lazy_sync)
+        self._syncing_back = False    # inside sync_to_host: assigning model.variables must not drop the state being read
         if self.device_step and not isinstance(model, PsiCMPS):
             raise ValueError("device_step: the device-resident optimiser step exists for PsiCMPS (the hot path) only")
 
@@ -92,7 +95,6 @@ class Trainer:
         with fewer clips than ranks) skips the scan and contributes zeros to the all-reduce."""
         if self.device_step:
             return self._step_device(data, sync, global_batch)
-        D = self.model.bond_d
         if data is not None and not callable(data) and len(data) == 0:
             import torch
             # sized from the MODEL (RhoCMPS appends its column cotangents: a shorter buffer here would be a size mismatch in the
@@ -106,9 +108,7 @@ class Trainer:
         if global_batch is not None:
             b_global = int(global_batch)
         total, grads = self.model.chain_rule(host, max(b_global, 1), with_reg=True)       # train.py:55-60
-        # sum_b loss_b sits at the end of the pure-state layout (2 D^2 + 3 D + 2 floats); RhoCMPS appends the column
-        # cotangents behind it (include/cmps.h: cmps_rho_loss_bwd)
-        model_loss = host[2 * D * D + 3 * D + 1] / max(b_global, 1)
+        model_loss = layout.unpack_grad(host, self.model.bond_d)["loss_sum"] / max(b_global, 1)    # (RhoCMPS's tail sits behind it)
         self.opt.apply_gradients(self.model.variables, grads)                     # train.py:89
         self.global_step += 1
         out = {"model_loss": float(model_loss), "total_loss": float(total), "global_step": self.global_step,
@@ -121,26 +121,22 @@ class Trainer:
         if self._dev is None:
             import torch
             be = self.model._get_backend()
-            D = self.model.bond_d
-            V = 2 * D * D + 3 * D + 1
-            host = np.concatenate([np.asarray(self.model.variables[k], dtype=np.float32).ravel() for k in VAR_ORDER])
-            st = {"vars": torch.from_numpy(host).to(be.device)}
-            for slot, src in (("m", self.opt.m), ("v", self.opt.v)):
-                h = np.concatenate([np.asarray(src.get(k, np.zeros_like(self.model.variables[k])), dtype=np.float32).ravel()
-                                    for k in VAR_ORDER])
-                st[slot] = torch.from_numpy(h).to(be.device)
-            st["params"] = torch.empty(V, dtype=torch.float32, device=be.device)
+            D, variables = self.model.bond_d, self.model.variables
+            fields = layout.var_fields(D)
+            zeros = {k: np.zeros_like(variables[k]) for k in VAR_ORDER}       # (a missing Adam slot starts at zero)
+            st = {slot: torch.from_numpy(layout.pack(fields, {**zeros, **src})).to(be.device)
+                  for slot, src in (("vars", variables), ("m", self.opt.m), ("v", self.opt.v))}
+            st["params"] = torch.empty(layout.size(layout.param_fields(D, with_A=True)), dtype=torch.float32, device=be.device)
             st["losses"] = torch.zeros(2, dtype=torch.float32, device=be.device)
             self._dev = st
             self._dirty = False
-            import weakref
             self.model._device_owner = weakref.ref(self)           # model.variables now syncs lazily from the device state
             self._apply(None, 1)                                   # effective parameters of the current variables
         return self._dev
 
     def _lazy_sync(self):
         """Called by model.variables: device state -> host copies if a device step has run since the last sync."""
-        if self._dev is not None and getattr(self, "_dirty", False) and not getattr(self, "_syncing", False):
+        if self._dev is not None and self._dirty and not self._syncing:
             self._syncing = True
             try:
                 self.sync_to_host()
@@ -158,7 +154,6 @@ class Trainer:
         m = self.model
         st = self._device_state()
         be = m._get_backend()
-        D = m.bond_d
         audio = m._to_device(m._batch(data))
         b_local, T = audio.shape
         if b_local > 0:
@@ -166,7 +161,7 @@ class Trainer:
             be.forward(audio, save_for_bwd=True)
             flat = be.backward()
         else:
-            flat = torch.zeros(2 * D * D + 3 * D + 2, dtype=torch.float32, device=be.device)
+            flat = torch.zeros(m.flat_size(), dtype=torch.float32, device=be.device)
         if global_batch is None:                                   # known without communication: the reference's batch is the global one
             global_batch = b_local if self.dp.world_size == 1 else int(self.hparams.minibatch_size)
         self.dp.allreduce_device(flat)
@@ -201,16 +196,11 @@ class Trainer:
             self._syncing_back = False
 
     def _sync_to_host(self):
-        D = self.model.bond_d
-        shapes = {"A": (), "Rx": (D, D), "Ry": (D, D), "freqs": (D,), "psi_x": (D,), "psi_y": (D,)}
+        fields = layout.var_fields(self.model.bond_d)
         self._dirty = False
         for name, dst in (("vars", self.model._variables), ("m", self.opt.m), ("v", self.opt.v)):
-            flat = self._dev[name].cpu().numpy()
-            o = 0
-            for k in VAR_ORDER:
-                n = int(np.prod(shapes[k])) if shapes[k] else 1
-                dst[k] = np.asarray(flat[o:o + n].reshape(shapes[k]), dtype=np.float32).copy()
-                o += n
+            for k, a in layout.unpack(fields, self._dev[name].cpu().numpy()).items():
+                dst[k] = np.asarray(a, dtype=np.float32).copy()
 
     # -- checkpoint / resume (train.py:93: save_checkpoint_secs=60, automatic restore from logdir) --
     def save(self, path: str):
