@@ -13,6 +13,18 @@ using namespace cmps;
 
 namespace cmps { thread_local KTimer* g_ktimer = nullptr; }
 
+// What the last forward (or the rho sampler) left in the stash of ONE workspace: the reverse and the states entries of that workspace check
+// their arguments against it and read its layout.  The main workspace (psi and legacy entries) and the rho workspace have one each.
+struct Saved {
+    bool valid = false;            // the stash holds the rows of B clips x `steps` steps
+    int B = 0, steps = 0;
+    const float* audio = nullptr;
+    float* loss = nullptr;
+    int layout = 0;                // the StashLayout (main workspace) / RhoStashLayout (rho workspace) that was written
+    bool bwd_ok = false;           // rho: written by cmps_rho_loss_fwd (not by the sampler), a reverse pass may follow
+    bool grad1 = false;            // rho: the GEMM forward accumulated RhoDev::p1
+};
+
 struct cmps_handle_s {
     int D = 0;
     int variant_req = CMPS_VARIANT_AUTO;
@@ -20,16 +32,12 @@ struct cmps_handle_s {
     int wide_chain = CMPS_WIDE_CHAIN_MFMA;
     int f16_shift = 0;         // CMPS_OPT_F16_SCALE_SHIFT (diagnostic)
     int bwd_waves = 2;             // CMPS_OPT_BWD_WAVES
-    bool rho_fwd_grad1 = false;    // the last GEMM forward accumulated RhoDev::p1
     bool rho_virtual_bwd = true;   // CMPS_OPT_RHO_BWD: the RhoCMPS GEMM forward's reverse sweep on virtual clips of k_bwd_wave (else k_bwd_rho_mfma)
     bool params_set = false;
     bool legacy = false;       // the tables currently hold the legacy AudioMPS arithmetic (cmps_legacy_set_params)
-    bool fwd_saved = false;
-    int saved_B = 0, saved_T = 0, saved_variant = 0;
-    const float* saved_audio = nullptr;
-    float* saved_loss = nullptr;
+    Saved main, rho;           // the stash of the main workspace (cmps_psi_* / cmps_legacy_* entries) and of the rho workspace
     Layout L{};
-    Dev P{};
+    Dev P{};                   // (stash_layout stays 0 here: main_dev() fills it from `main` for the kernels that read the stash)
     char* ws = nullptr;
     // time-table cache key: the table is rebuilt only when (workspace, N, dt) changes
     char* tt_ws = nullptr;
@@ -37,9 +45,7 @@ struct cmps_handle_s {
     float tt_dt = 0.f;
     // RhoCMPS state (cmps_rho_set_state)
     bool rho_set = false;
-    bool rho_saved = false;       // the rho stash holds the columns of rho_saved_B x rho_saved_steps steps
-    bool rho_bwd_ok = false;      // ... written by cmps_rho_loss_fwd (not by the sampler)
-    int rho_B = 0, rho_T = 0, rho_flags = 0, rho_saved_B = 0, rho_saved_steps = 0;
+    int rho_B = 0, rho_T = 0, rho_flags = 0;
     RhoLayout RL{};
     RhoDev W{};
     cmps::KTimer* ktimer = nullptr;   // non-null: CMPS_OPT_KERNEL_EVENTS is on
@@ -48,7 +54,7 @@ struct cmps_handle_s {
 
 namespace {
 
-int fail(cmps_handle_t h, int code, const char* msg) {
+int fail(cmps_handle_t h, int code, const std::string& msg) {
     if (h) h->err = msg;
     return code;
 }
@@ -118,6 +124,40 @@ Dev bind_workspace(const Layout& L, char* ws) {
     P.status = train ? reinterpret_cast<unsigned*>(ws + L.off_status) : nullptr;
     P.slab_floats = L.slab_floats;
     return P;
+}
+
+// The Dev / RhoDev of a call that reads a stash: B clips, the layout from the workspace's record
+Dev main_dev(const cmps_handle_s* h, int B) {
+    Dev P = h->P;
+    P.B = B;
+    P.stash_layout = h->main.layout;
+    return P;
+}
+RhoDev rho_dev(const cmps_handle_s* h) {
+    RhoDev W = h->W;
+    W.stash_layout = h->rho.layout;
+    return W;
+}
+
+// The argument checks of every *_loss_fwd entry (h non-null): `ready` is the entry's call-order condition, T_set / B_max / ws_flags what
+// `setter` was given.  CMPS_OK, or the code to return with the message set.
+int check_fwd(cmps_handle_t h, const char* who, bool ready, const char* setter, const void* audio, const void* loss, int B, int T,
+              int T_set, int B_max, int save, int ws_flags) {
+    const std::string w(who);
+    if (!ready) return fail(h, CMPS_ERR_STATE, w + ": call " + setter + " first");
+    if (!audio || !loss) return fail(h, CMPS_ERR_BAD_ARG, w + ": null pointer");
+    if (T != T_set) return fail(h, CMPS_ERR_BAD_ARG, w + ": T differs from " + setter);
+    if (B < 1 || B > B_max) return fail(h, CMPS_ERR_BAD_ARG, w + ": B outside [1, B_max] of " + setter);
+    if (save && !(ws_flags & CMPS_WS_TRAIN)) return fail(h, CMPS_ERR_WORKSPACE, w + ": save_for_bwd needs a CMPS_WS_TRAIN workspace in " + setter);
+    return CMPS_OK;
+}
+// ... and of every *_loss_bwd entry, against the record S of the forward `fwd` it follows
+int check_bwd(cmps_handle_t h, const char* who, bool ready, const char* fwd, const Saved& S, const void* audio, const void* grad, int B, int T) {
+    const std::string w(who);
+    if (!ready || !S.valid) return fail(h, CMPS_ERR_STATE, w + ": needs " + fwd + "(save_for_bwd=1) first");
+    if (!audio || !grad) return fail(h, CMPS_ERR_BAD_ARG, w + ": null pointer");
+    if (B != S.B || T != S.steps + 1 || audio != S.audio) return fail(h, CMPS_ERR_STATE, w + ": audio / B / T differ from the forward call");
+    return CMPS_OK;
 }
 
 // the end of a reverse pass whose slabs hold one PAIR of clips each (pair and wide kernels): reduce over (B + 1) / 2 slabs, closing terms
@@ -270,9 +310,9 @@ static int set_params_impl(cmps_handle_t h, const float* R_re_dev, const float* 
     h->L = L; h->P = P; h->ws = ws;
     h->params_set = true;
     h->legacy = false;
-    h->fwd_saved = false;
+    h->main.valid = false;
     h->rho_set = false;               // the columns of rho_0 are handed over again after every parameter change
-    h->rho_saved = false;
+    h->rho.valid = false;
     return CMPS_OK;
 }
 
@@ -315,12 +355,8 @@ int cmps_psi_apply_step(cmps_handle_t h, float* vars_dev, float* adam_m_dev, flo
 int cmps_psi_loss_fwd(cmps_handle_t h, const float* audio_dev, int B, int T, float* loss_dev,
                       int save_for_bwd, void* stream) {
     if (!h) return CMPS_ERR_BAD_ARG;
-    if (!h->params_set || h->legacy) return fail(h, CMPS_ERR_STATE, "cmps_psi_loss_fwd: call cmps_set_params first");
-    if (!audio_dev || !loss_dev) return fail(h, CMPS_ERR_BAD_ARG, "cmps_psi_loss_fwd: null pointer");
-    if (T != h->L.T) return fail(h, CMPS_ERR_BAD_ARG, "cmps_psi_loss_fwd: T differs from cmps_set_params");
-    if (B < 1 || B > h->L.B) return fail(h, CMPS_ERR_BAD_ARG, "cmps_psi_loss_fwd: B outside [1, B_max]");
-    if (save_for_bwd && !(h->L.flags & CMPS_WS_TRAIN))
-        return fail(h, CMPS_ERR_WORKSPACE, "cmps_psi_loss_fwd: save_for_bwd needs a CMPS_WS_TRAIN workspace");
+    if (const int rc = check_fwd(h, "cmps_psi_loss_fwd", h->params_set && !h->legacy, "cmps_set_params", audio_dev, loss_dev, B, T,
+                                 h->L.T, h->L.B, save_for_bwd, h->L.flags)) return rc;
     Dev P = h->P;
     P.B = B;
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -342,37 +378,32 @@ int cmps_psi_loss_fwd(cmps_handle_t h, const float* audio_dev, int B, int T, flo
     default: { KScope ks("k_fwd_block", s); e = launch_fwd_block(P, audio_dev, loss_dev, save, s); } break;
     }
     if (e != hipSuccess) return fail_hip(h, e, "cmps_psi_loss_fwd");
-    h->fwd_saved = save_for_bwd != 0;
-    h->saved_B = B; h->saved_T = T; h->saved_audio = audio_dev; h->saved_loss = loss_dev;
-    h->saved_variant = variant;
-    h->P.stash_layout = family;
+    h->main = Saved{save, B, T - 1, audio_dev, loss_dev, family};
     return CMPS_OK;
 }
 
 int cmps_psi_loss_bwd(cmps_handle_t h, const float* audio_dev, int B, int T, float* grad_dev, void* stream) {
     if (!h) return CMPS_ERR_BAD_ARG;
-    if (!h->params_set || !h->fwd_saved || h->legacy)
-        return fail(h, CMPS_ERR_STATE, "cmps_psi_loss_bwd: needs cmps_psi_loss_fwd(save_for_bwd=1) first");
-    if (!audio_dev || !grad_dev) return fail(h, CMPS_ERR_BAD_ARG, "cmps_psi_loss_bwd: null pointer");
-    if (B != h->saved_B || T != h->saved_T || audio_dev != h->saved_audio)
-        return fail(h, CMPS_ERR_STATE, "cmps_psi_loss_bwd: audio / B / T differ from the forward call");
-    Dev P = h->P;
-    P.B = B;
+    if (const int rc = check_bwd(h, "cmps_psi_loss_bwd", h->params_set && !h->legacy, "cmps_psi_loss_fwd", h->main, audio_dev, grad_dev, B, T))
+        return rc;
+    Dev P = main_dev(h, B);
     P.f16_shift = h->f16_shift;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    // the stash layout belongs to the variant that wrote it
+    // the reverse kernels belong to the family whose forward wrote the stash
+    const int layout = h->main.layout;
+    float* const loss = h->main.loss;
     KBind kb(h);
-    if (h->saved_variant == CMPS_VARIANT_PAIR) {
+    if (layout == STASH_PAIR) {
         // reverse scan, then the gradient GEMM over the rows both scans left behind; one slab per PAIR of clips
         hipError_t e;
         { KScope ks("k_bwd_pair", s); e = launch_bwd_pair(P, audio_dev, s); }
         if (e == hipSuccess) { KScope ks("k_grad_gemm<1>", s); e = launch_grad_pair(P, audio_dev, s); }
         if (e != hipSuccess) return fail_hip(h, e, "cmps_psi_loss_bwd (pair scan)");
-        e = reduce_pairs_finalize(P, 0, h->saved_loss, grad_dev, s);
+        e = reduce_pairs_finalize(P, 0, loss, grad_dev, s);
         if (e != hipSuccess) return fail_hip(h, e, "cmps_psi_loss_bwd (pair reduce)");
         return CMPS_OK;
     }
-    if (h->saved_variant == CMPS_VARIANT_WIDE) {
+    if (layout == STASH_WIDE) {
         // float32 reverse scan, then the gradient GEMM (operands split into bf16 pieces on the fly); one slab per PAIR of clips
         hipError_t e;
         if (h->wide_chain == CMPS_WIDE_CHAIN_MFMA) { KScope ks("k_bwd_chain16", s); e = launch_bwd_chain16(P, audio_dev, s); }
@@ -384,12 +415,11 @@ int cmps_psi_loss_bwd(cmps_handle_t h, const float* audio_dev, int B, int T, flo
         }
         if (e != hipSuccess) return fail_hip(h, e, "cmps_psi_loss_bwd (wide scan)");
         // abar_fix: the merged mat-vec, k_finalize removes the Q part of sum Re(u^dagger (Q + s R^dagger) ybar)
-        e = reduce_pairs_finalize(P, 1, h->saved_loss, grad_dev, s);
+        e = reduce_pairs_finalize(P, 1, loss, grad_dev, s);
         if (e != hipSuccess) return fail_hip(h, e, "cmps_psi_loss_bwd (wide reduce)");
         return CMPS_OK;
     }
-    const bool wave = h->saved_variant == CMPS_VARIANT_WAVE || h->saved_variant == CMPS_VARIANT_WAVE32;
-    const bool w16 = h->saved_variant == CMPS_VARIANT_WAVE && h->D <= 16;
+    const bool w16 = layout == STASH_WAVE16, wave = w16 || layout == STASH_WAVE32;
     hipError_t e;
     {
         const bool two = wave && !w16 && h->bwd_waves == 2 && rank1_f16(h->rank1_mode) && h->f16_shift == 0;
@@ -400,7 +430,7 @@ int cmps_psi_loss_bwd(cmps_handle_t h, const float* audio_dev, int B, int T, flo
     if (e != hipSuccess) return fail_hip(h, e, "cmps_psi_loss_bwd (scan)");
     P.abar_fix = wave ? 1 : 0;
     KScope ks("reduce + finalize", s);
-    e = launch_reduce_finalize(P, h->saved_loss, grad_dev, s);
+    e = launch_reduce_finalize(P, loss, grad_dev, s);
     if (e != hipSuccess) return fail_hip(h, e, "cmps_psi_loss_bwd (reduce)");
     return CMPS_OK;
 }
@@ -439,11 +469,13 @@ int cmps_psi_update_ancilla(cmps_handle_t h, const float* psi_in_dev, const floa
 
 int cmps_psi_states(cmps_handle_t h, int B, int T, float* psi_out_dev, void* stream) {
     if (!h) return CMPS_ERR_BAD_ARG;
-    if (!h->params_set || !h->fwd_saved)
+    if (h->legacy)               // (k_states rotates into the lab frame with freqs and the time table; neither exists after cmps_legacy_set_params)
+        return fail(h, CMPS_ERR_STATE, "cmps_psi_states: not available in legacy mode (no time table for the lab-frame phases)");
+    if (!h->params_set || !h->main.valid)
         return fail(h, CMPS_ERR_STATE, "cmps_psi_states: needs cmps_psi_loss_fwd(save_for_bwd=1) first");
-    if (!psi_out_dev || B != h->saved_B || T != h->saved_T)
+    if (!psi_out_dev || B != h->main.B || T != h->main.steps + 1)
         return fail(h, CMPS_ERR_BAD_ARG, "cmps_psi_states: bad argument");
-    hipError_t e = launch_states(h->P, B, psi_out_dev, static_cast<hipStream_t>(stream));
+    hipError_t e = launch_states(main_dev(h, B), B, psi_out_dev, static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return fail_hip(h, e, "cmps_psi_states");
     return CMPS_OK;
 }
@@ -495,7 +527,7 @@ int cmps_legacy_set_params(cmps_handle_t h, const float* R_dev, const float* Q_r
     h->tt_ws = nullptr;               // the time table of the PsiCMPS mode is no longer valid for this workspace
     h->params_set = true;
     h->legacy = true;
-    h->fwd_saved = false;
+    h->main.valid = false;
     h->rho_set = false;
     return CMPS_OK;
 }
@@ -503,11 +535,8 @@ int cmps_legacy_set_params(cmps_handle_t h, const float* R_dev, const float* Q_r
 int cmps_legacy_loss_fwd(cmps_handle_t h, const float* audio_dev, int B, int T, float* loss_dev, int save_for_bwd,
                          void* stream) {
     if (!h) return CMPS_ERR_BAD_ARG;
-    if (!h->params_set || !h->legacy) return fail(h, CMPS_ERR_STATE, "cmps_legacy_loss_fwd: call cmps_legacy_set_params first");
-    if (!audio_dev || !loss_dev) return fail(h, CMPS_ERR_BAD_ARG, "cmps_legacy_loss_fwd: null pointer");
-    if (T != h->L.T || B < 1 || B > h->L.B) return fail(h, CMPS_ERR_BAD_ARG, "cmps_legacy_loss_fwd: shape differs from set_params");
-    if (save_for_bwd && !(h->L.flags & CMPS_WS_TRAIN))
-        return fail(h, CMPS_ERR_WORKSPACE, "cmps_legacy_loss_fwd: save_for_bwd needs a CMPS_WS_TRAIN workspace");
+    if (const int rc = check_fwd(h, "cmps_legacy_loss_fwd", h->params_set && h->legacy, "cmps_legacy_set_params", audio_dev, loss_dev, B, T,
+                                 h->L.T, h->L.B, save_for_bwd, h->L.flags)) return rc;
     Dev P = h->P;
     P.B = B;
     // D <= 32: the pure-state wave kernels in LEGACY mode (cmps_wave2.hip, cmps_wave.hip); above: the wide kernels in LEGACY mode
@@ -520,26 +549,21 @@ int cmps_legacy_loss_fwd(cmps_handle_t h, const float* audio_dev, int B, int T, 
                  : wide ? launch_fwd_wide_legacy(P, audio_dev, loss_dev, save_for_bwd != 0, f16, static_cast<hipStream_t>(stream))
                         : launch_fwd_legacy(P, audio_dev, loss_dev, save_for_bwd != 0, static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return fail_hip(h, e, "cmps_legacy_loss_fwd");
-    h->saved_variant = wave ? CMPS_VARIANT_WAVE : wide ? CMPS_VARIANT_WIDE : CMPS_VARIANT_BLOCK;
-    h->fwd_saved = save_for_bwd != 0;
-    h->saved_B = B; h->saved_T = T; h->saved_audio = audio_dev; h->saved_loss = loss_dev;
+    // the rows as the forward wrote them: the wave kernel's (y, H y) pairs, the wide kernels' rows, or k_fwd_legacy's [B][N][DP] float2
+    h->main = Saved{save_for_bwd != 0, B, T - 1, audio_dev, loss_dev, wave ? STASH_WAVE32 : wide ? STASH_WIDE : STASH_BLOCK};
     return CMPS_OK;
 }
 
 int cmps_legacy_loss_bwd(cmps_handle_t h, const float* audio_dev, int B, int T, float* grad_dev, void* stream) {
     if (!h) return CMPS_ERR_BAD_ARG;
-    if (!h->params_set || !h->legacy || !h->fwd_saved)
-        return fail(h, CMPS_ERR_STATE, "cmps_legacy_loss_bwd: needs cmps_legacy_loss_fwd(save_for_bwd=1) first");
-    if (!audio_dev || !grad_dev) return fail(h, CMPS_ERR_BAD_ARG, "cmps_legacy_loss_bwd: null pointer");
-    if (B != h->saved_B || T != h->saved_T || audio_dev != h->saved_audio)
-        return fail(h, CMPS_ERR_STATE, "cmps_legacy_loss_bwd: audio / B / T differ from the forward call");
-    Dev P = h->P;
-    P.B = B;
+    if (const int rc = check_bwd(h, "cmps_legacy_loss_bwd", h->params_set && h->legacy, "cmps_legacy_loss_fwd", h->main, audio_dev, grad_dev, B, T))
+        return rc;
+    Dev P = main_dev(h, B);
     hipStream_t s = static_cast<hipStream_t>(stream);
     KBind kb(h);
     hipError_t e;
     Dev Pr = P;                                                    // what the slab reduction runs over
-    if (h->saved_variant == CMPS_VARIANT_WIDE) {
+    if (h->main.layout == STASH_WIDE) {
         // reverse chain, then the gradient GEMM over the rows both scans left behind; one slab per PAIR of clips
         { KScope ks("k_bwd_wide<legacy>", s); e = launch_bwd_wide_legacy(P, audio_dev, s); }
         if (e == hipSuccess) {
@@ -548,11 +572,11 @@ int cmps_legacy_loss_bwd(cmps_handle_t h, const float* audio_dev, int B, int T, 
         }
         Pr.B = (B + 1) / 2;
     } else {
-        e = h->saved_variant == CMPS_VARIANT_WAVE ? launch_bwd_legacy_wave(P, audio_dev, wave_rank1(h->rank1_mode), s) : launch_bwd_legacy(P, audio_dev, s);
+        e = h->main.layout == STASH_WAVE32 ? launch_bwd_legacy_wave(P, audio_dev, wave_rank1(h->rank1_mode), s) : launch_bwd_legacy(P, audio_dev, s);
     }
     if (e != hipSuccess) return fail_hip(h, e, "cmps_legacy_loss_bwd (scan)");
     e = launch_reduce_only(Pr, s);
-    if (e == hipSuccess) e = launch_finalize_legacy(P, h->saved_loss, grad_dev, s);
+    if (e == hipSuccess) e = launch_finalize_legacy(P, h->main.loss, grad_dev, s);
     if (e != hipSuccess) return fail_hip(h, e, "cmps_legacy_loss_bwd (reduce)");
     return CMPS_OK;
 }
@@ -591,7 +615,7 @@ int cmps_rho_set_state(cmps_handle_t h, const float* phi_re_dev, const float* ph
     W.stash = train ? reinterpret_cast<float2*>(ws + RL.off_stash) : nullptr;
     W.scal = train ? reinterpret_cast<float*>(ws + RL.off_scal) : nullptr;
     W.p1 = (train && h->D <= 32) ? reinterpret_cast<float*>(ws + RL.off_p1) : nullptr;
-    W.stash_layout = RHO_STASH_BLOCK;
+    W.stash_layout = RHO_STASH_BLOCK;                            // (stays: rho_dev() fills it from the record for the kernels that read the stash)
     W.cols = rD > RHO_LDS_COLS_MAX ? reinterpret_cast<float2*>(ws + RL.off_cols) : nullptr;
     W.cols_blocks = B_max;
     W.slabs = train ? reinterpret_cast<float*>(ws + RL.off_slabs) : nullptr;
@@ -618,21 +642,15 @@ int cmps_rho_set_state(cmps_handle_t h, const float* phi_re_dev, const float* ph
     h->RL = RL; h->W = W;
     h->rho_B = B_max; h->rho_T = T; h->rho_flags = flags;
     h->rho_set = true;
-    h->rho_saved = false;
-    h->rho_bwd_ok = false;
+    h->rho.valid = h->rho.bwd_ok = false;
     return CMPS_OK;
 }
 
 int cmps_rho_loss_fwd(cmps_handle_t h, const float* audio_dev, int B, int T, float* loss_dev, int save_for_bwd,
                       void* stream) {
     if (!h) return CMPS_ERR_BAD_ARG;
-    if (!h->params_set || h->legacy || !h->rho_set)
-        return fail(h, CMPS_ERR_STATE, "cmps_rho_loss_fwd: call cmps_set_params and cmps_rho_set_state first");
-    if (!audio_dev || !loss_dev) return fail(h, CMPS_ERR_BAD_ARG, "cmps_rho_loss_fwd: null pointer");
-    if (T != h->rho_T) return fail(h, CMPS_ERR_BAD_ARG, "cmps_rho_loss_fwd: T differs from cmps_rho_set_state");
-    if (B < 1 || B > h->rho_B) return fail(h, CMPS_ERR_BAD_ARG, "cmps_rho_loss_fwd: B outside [1, B_max]");
-    if (save_for_bwd && !(h->rho_flags & CMPS_WS_TRAIN))
-        return fail(h, CMPS_ERR_WORKSPACE, "cmps_rho_loss_fwd: save_for_bwd needs a CMPS_WS_TRAIN rho workspace");
+    if (const int rc = check_fwd(h, "cmps_rho_loss_fwd", h->params_set && !h->legacy && h->rho_set, "cmps_rho_set_state (after cmps_set_params)",
+                                 audio_dev, loss_dev, B, T, h->rho_T, h->rho_B, save_for_bwd, h->rho_flags)) return rc;
     Dev P = h->P;
     P.B = B; P.T = T; P.N = T - 1;
     // D <= 32 (and rank <= 32): one wavefront per clip, unless the block variant was asked for -- the forward as row-array
@@ -652,45 +670,43 @@ int cmps_rho_loss_fwd(cmps_handle_t h, const float* audio_dev, int B, int T, flo
                  : wave ? launch_fwd_rho_wave(P, h->W, audio_dev, loss_dev, save_for_bwd != 0, s)
                         : launch_fwd_rho(P, h->W, audio_dev, loss_dev, save_for_bwd != 0, s);
     if (e != hipSuccess) return fail_hip(h, e, "cmps_rho_loss_fwd");
-    h->W.stash_layout = wide ? RHO_STASH_WIDE : mfma ? RHO_STASH_MFMA : wave ? RHO_STASH_WAVE : RHO_STASH_BLOCK;
-    h->rho_fwd_grad1 = mfma && !h->rho_virtual_bwd;               // the forward's part of Rbar exists (k_bwd_rho_mfma needs it)
-    h->rho_saved = h->rho_bwd_ok = save_for_bwd != 0;
-    h->rho_saved_B = B; h->rho_saved_steps = T - 1;
-    h->saved_audio = audio_dev; h->saved_loss = loss_dev;
+    const bool save = save_for_bwd != 0;
+    h->rho = Saved{save, B, T - 1, audio_dev, loss_dev, wide ? RHO_STASH_WIDE : mfma ? RHO_STASH_MFMA : wave ? RHO_STASH_WAVE : RHO_STASH_BLOCK,
+                   save, mfma && !h->rho_virtual_bwd};      // grad1: the forward's part of Rbar exists (k_bwd_rho_mfma needs it)
     return CMPS_OK;
 }
 
 int cmps_rho_loss_bwd(cmps_handle_t h, const float* audio_dev, int B, int T, float* grad_dev, void* stream) {
     if (!h) return CMPS_ERR_BAD_ARG;
-    if (!h->params_set || !h->rho_set || !h->rho_saved || !h->rho_bwd_ok)
-        return fail(h, CMPS_ERR_STATE, "cmps_rho_loss_bwd: needs cmps_rho_loss_fwd(save_for_bwd=1) first");
-    if (!audio_dev || !grad_dev) return fail(h, CMPS_ERR_BAD_ARG, "cmps_rho_loss_bwd: null pointer");
-    if (B != h->rho_saved_B || T - 1 != h->rho_saved_steps || audio_dev != h->saved_audio)
-        return fail(h, CMPS_ERR_STATE, "cmps_rho_loss_bwd: audio / B / T differ from the forward call");
+    if (const int rc = check_bwd(h, "cmps_rho_loss_bwd", h->params_set && h->rho_set && h->rho.bwd_ok, "cmps_rho_loss_fwd", h->rho, audio_dev, grad_dev,
+                                 B, T)) return rc;
     Dev P = h->P;
     P.B = B; P.T = T; P.N = T - 1;
-    P.slabs = h->W.slabs; P.sums = h->W.sums; P.slab_floats = h->W.slab_floats;   // the reduction runs on the rho slabs
+    const RhoDev W = rho_dev(h);
+    const int layout = h->rho.layout;
+    float* const loss = h->rho.loss;
+    P.slabs = W.slabs; P.sums = W.sums; P.slab_floats = W.slab_floats;   // the reduction runs on the rho slabs
     hipStream_t s = static_cast<hipStream_t>(stream);
     KBind kb(h);
-    if (h->W.stash_layout == RHO_STASH_WIDE) {                                 // the wide kernels on virtual clips: reverse chain, GEMM, reduction, closing terms
-        const hipError_t ew = launch_bwd_rho_wide(P, h->W, h->saved_loss, grad_dev, rank1_wide_pieces(h->rank1_mode), s);
+    if (layout == RHO_STASH_WIDE) {                                 // the wide kernels on virtual clips: reverse chain, GEMM, reduction, closing terms
+        const hipError_t ew = launch_bwd_rho_wide(P, W, loss, grad_dev, rank1_wide_pieces(h->rank1_mode), s);
         if (ew != hipSuccess) return fail_hip(h, ew, "cmps_rho_loss_bwd (wide)");
         return CMPS_OK;
     }
-    if (h->W.stash_layout == RHO_STASH_MFMA && !h->rho_virtual_bwd && !h->rho_fwd_grad1)
+    if (layout == RHO_STASH_MFMA && !h->rho_virtual_bwd && !h->rho.grad1)
         return fail(h, CMPS_ERR_STATE, "cmps_rho_loss_bwd: CMPS_OPT_RHO_BWD changed between the forward and the reverse call");
-    if (h->W.stash_layout == RHO_STASH_MFMA && h->rho_virtual_bwd) {
+    if (layout == RHO_STASH_MFMA && h->rho_virtual_bwd) {
         // the row-array forward's rows through the pure-state wave reverse scan, one virtual clip per column (cmps_rho_wave.hip)
-        const hipError_t ew = launch_bwd_rho_virtual_wave(P, h->W, audio_dev, h->saved_loss, grad_dev, wave_rank1(h->rank1_mode), h->bwd_waves, s);
+        const hipError_t ew = launch_bwd_rho_virtual_wave(P, W, audio_dev, loss, grad_dev, wave_rank1(h->rank1_mode), h->bwd_waves, s);
         if (ew != hipSuccess) return fail_hip(h, ew, "cmps_rho_loss_bwd (virtual clips)");
         return CMPS_OK;
     }
-    hipError_t e = h->W.stash_layout == RHO_STASH_MFMA ? launch_bwd_rho_mfma(P, h->W, audio_dev, s)
-                 : h->W.stash_layout == RHO_STASH_WAVE ? launch_bwd_rho_wave(P, h->W, audio_dev, s) : launch_bwd_rho(P, h->W, audio_dev, s);
+    hipError_t e = layout == RHO_STASH_MFMA ? launch_bwd_rho_mfma(P, W, audio_dev, s)
+                 : layout == RHO_STASH_WAVE ? launch_bwd_rho_wave(P, W, audio_dev, s) : launch_bwd_rho(P, W, audio_dev, s);
     if (e != hipSuccess) return fail_hip(h, e, "cmps_rho_loss_bwd (scan)");
-    P.abar_fix = h->W.stash_layout == RHO_STASH_MFMA ? 1 : 0;   // the MFMA scan sums Re(u^dagger (Q + s R^dagger) ybar); k_finalize removes the Q part
-    e = launch_reduce_finalize(P, h->saved_loss, grad_dev, s);
-    if (e == hipSuccess) e = launch_finalize_rho(P, h->W, grad_dev, s);
+    P.abar_fix = layout == RHO_STASH_MFMA ? 1 : 0;   // the MFMA scan sums Re(u^dagger (Q + s R^dagger) ybar); k_finalize removes the Q part
+    e = launch_reduce_finalize(P, loss, grad_dev, s);
+    if (e == hipSuccess) e = launch_finalize_rho(P, W, grad_dev, s);
     if (e != hipSuccess) return fail_hip(h, e, "cmps_rho_loss_bwd (reduce)");
     return CMPS_OK;
 }
@@ -727,20 +743,17 @@ int cmps_rho_sample(cmps_handle_t h, const float* noise_dev, int n, int length, 
                                                  rank1_f16(h->rank1_mode), static_cast<hipStream_t>(stream))
                         : launch_sample_rho(h->P, h->W, noise_dev, n, length, out_dev, save_states != 0, static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return fail_hip(h, e, "cmps_rho_sample");
-    h->rho_saved = save_states != 0;
-    h->W.stash_layout = mfma ? RHO_STASH_MFMA : RHO_STASH_BLOCK;
-    h->rho_bwd_ok = false;
-    h->rho_saved_B = n; h->rho_saved_steps = length;
+    h->rho = Saved{save_states != 0, n, length, nullptr, nullptr, mfma ? RHO_STASH_MFMA : RHO_STASH_BLOCK};   // (no reverse pass after a sampler)
     return CMPS_OK;
 }
 
 int cmps_rho_states(cmps_handle_t h, int B, int steps, float* rho_out_dev, float* purity_out_dev, void* stream) {
     if (!h) return CMPS_ERR_BAD_ARG;
-    if (!h->params_set || !h->rho_set || !h->rho_saved)
+    if (!h->params_set || !h->rho_set || !h->rho.valid)
         return fail(h, CMPS_ERR_STATE, "cmps_rho_states: needs cmps_rho_loss_fwd(save_for_bwd=1) or cmps_rho_sample(save_states=1) first");
-    if (B != h->rho_saved_B || steps != h->rho_saved_steps || (!rho_out_dev && !purity_out_dev))
+    if (B != h->rho.B || steps != h->rho.steps || (!rho_out_dev && !purity_out_dev))
         return fail(h, CMPS_ERR_BAD_ARG, "cmps_rho_states: bad argument");
-    hipError_t e = launch_states_rho(h->P, h->W, B, steps, rho_out_dev, purity_out_dev, static_cast<hipStream_t>(stream));
+    hipError_t e = launch_states_rho(h->P, rho_dev(h), B, steps, rho_out_dev, purity_out_dev, static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return fail_hip(h, e, "cmps_rho_states");
     return CMPS_OK;
 }

@@ -4,6 +4,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 namespace cmps {
@@ -62,12 +64,20 @@ struct Layout {
     int D, DP, B, T, N, flags;
     size_t off_R, off_RT, off_Q, off_QT, off_psi0, off_freqs, off_qflag, off_ttab, off_dtk, off_rho, off_rfix,
         off_stash, off_hst, off_scal, off_slabs, off_sums, off_gops, off_opmax, off_status, total;
-    size_t slab_floats;  // 4*DP*DP + 3*DP + 2
+    size_t slab_floats;  // psi_slab_floats(DP)
 };
 
 inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 inline int padded_D(int D) { return (D + 31) / 32 * 32; }   // zero padding to the next multiple of 32 (32, 64, 96, 128)
+
+constexpr int WS_TRAIN = 1;   // CMPS_WS_TRAIN (include/cmps.h): the workspace has the stash, the slabs and the reduction buffers
+// floats of a pure-state gradient slab: Rbar and Qbar as re | im planes [DP][DP], then f | psi0bar_re | psi0bar_im [DP] each, A, one spare
+inline size_t psi_slab_floats(size_t DP) { return 4 * DP * DP + 3 * DP + 2; }
+// bytes of a `sums` section for slabs of `slab` floats: the reduced slab (padded to the next 64 floats) + [32][slab] double first-pass partials
+inline size_t sums_bytes(size_t slab) { return (slab + 64) * sizeof(float) + 32 * slab * sizeof(double); }
+// bytes of a `scal` section: per clip and 64-step chunk two rows of 64 floats, one step per lane
+inline size_t scal_bytes(size_t B, size_t N) { return B * ((N + 63) / 64) * 128 * sizeof(float); }
 
 inline Layout make_layout(int D, int B, int T, int flags) {
     Layout L{};
@@ -87,7 +97,7 @@ inline Layout make_layout(int D, int B, int T, int flags) {
     L.off_dtk = o;   o = align256(o + (N + 64) * sizeof(float));
     L.off_rho = o;   o = align256(o + (N + 1) * DP * sizeof(float2));
     L.off_rfix = o;  o = align256(o + ((N + 63) / 64) * DP * 2 * sizeof(double2));
-    L.slab_floats = 4 * DP * DP + 3 * DP + 2;
+    L.slab_floats = psi_slab_floats(DP);
     L.off_stash = o;
     L.off_hst = o;
     L.off_scal = o;
@@ -96,7 +106,7 @@ inline Layout make_layout(int D, int B, int T, int flags) {
     L.off_gops = o;
     L.off_opmax = o;
     L.off_status = o;
-    if (flags & 1) {
+    if (flags & WS_TRAIN) {
         // the two variants never run on the same stash: their layouts share one region
         // D > 32: the pair kernels (D = 128) keep (y, H y) per step, 16 B per component; the block kernels use half of it
         size_t stash_bytes = D > 32 ? (size_t)((B + 1) / 2 * 2) * N * DP * sizeof(float2) * 2   // whole pairs
@@ -104,9 +114,9 @@ inline Layout make_layout(int D, int B, int T, int flags) {
         if (D <= 32 && stash_bytes < (size_t)B * N * 128 * sizeof(float)) stash_bytes = (size_t)B * N * 128 * sizeof(float);
         L.off_hst = L.off_stash;
         o = align256(o + stash_bytes);
-        L.off_scal = o;  o = align256(o + (size_t)B * ((N + 63) / 64) * 128 * sizeof(float));
+        L.off_scal = o;  o = align256(o + scal_bytes(B, N));
         L.off_slabs = o; o = align256(o + (size_t)B * L.slab_floats * sizeof(float));
-        L.off_sums = o;  o = align256(o + (L.slab_floats + 64) * sizeof(float) + 32 * L.slab_floats * sizeof(double));
+        L.off_sums = o;  o = align256(o + sums_bytes(L.slab_floats));
         L.off_gops = o;
         // ybar rows: exactly [pairs][N][4 DP] floats (k_grad_gemm clamps every row it requests to the pair's range and its buffer
         // descriptors end at the last row; round 3's 32 rows of slack behind the section had no reader left -- ADVICE r3)
@@ -188,7 +198,7 @@ inline size_t rho_wide_lds(int D, int rank) {
     const size_t PD = (size_t)padded_D(D), vr = (size_t)((rank + 1) / 2 * 2);
     return 2 * (vr / 2) * (8 * (PD / 8 + 1)) * 16 + 2 * (PD / 16) * sizeof(float) + 64;
 }
-inline bool rho_wide_ok(int D, int rank, int flags) { return D > 32 && D <= 128 && (flags & 1) && rho_wide_lds(D, rank) <= 120 * 1024; }
+inline bool rho_wide_ok(int D, int rank, int flags) { return D > 32 && D <= 128 && (flags & WS_TRAIN) && rho_wide_lds(D, rank) <= 120 * 1024; }
 
 // rank * D above which the block kernels' column arrays (4 rank D complex numbers in the reverse scan) no longer fit into 160 KB of
 // LDS and live in the workspace instead (RhoDev::cols): the reference's default rank = D (model.py:62-65) from D = 72 upwards
@@ -204,23 +214,23 @@ inline RhoLayout make_rho_layout(int D, int rank, int B, int T, int flags) {
     RhoLayout L{};
     const size_t DP = (size_t)padded_D(D), N = (size_t)(T - 1), r = (size_t)rank;
     L.rank = rank;
-    L.slab_floats = 4 * DP * DP + 3 * DP + 2 + 2 * r * DP;
+    L.slab_floats = psi_slab_floats(DP) + 2 * r * DP;
     size_t o = 0;
     L.off_phi0 = o; o = align256(o + r * DP * sizeof(float2));
     L.off_stash = L.off_scal = L.off_slabs = L.off_sums = o;
-    if (flags & 1) {
+    if (flags & WS_TRAIN) {
         // D <= 32: the wave kernels keep (y_a own, (H y_a) own) per lane, 512 B per column and step
         L.off_stash = o; o = align256(o + (size_t)B * N * r * DP * sizeof(float2) * (D <= 32 ? 2 : 1));
-        L.off_scal = o;  o = align256(o + (size_t)B * ((N + 63) / 64) * 128 * sizeof(float));
+        L.off_scal = o;  o = align256(o + scal_bytes(B, N));
         L.off_slabs = o; o = align256(o + (size_t)B * L.slab_floats * sizeof(float));
-        L.off_sums = o;  o = align256(o + (L.slab_floats + 64) * sizeof(float) + 32 * L.slab_floats * sizeof(double));
+        L.off_sums = o;  o = align256(o + sums_bytes(L.slab_floats));
         // D <= 32: sum_k 2 ebar_k Y^T Y (real 64 x 64 form, four C/D tiles per clip), accumulated by k_fwd_rho_mfma for the reverse scan
         L.off_p1 = o;    if (D <= 32) o = align256(o + (size_t)B * 4096 * sizeof(float));
         L.off_wslabs = L.off_wsums = o;
         if (D <= 32) {
-            const size_t psl = 4 * DP * DP + 3 * DP + 2;
+            const size_t psl = psi_slab_floats(DP);
             L.off_wslabs = o; o = align256(o + (size_t)B * r * psl * sizeof(float));
-            L.off_wsums = o;  o = align256(o + (psl + 64) * sizeof(float) + 32 * psl * sizeof(double));
+            L.off_wsums = o;  o = align256(o + sums_bytes(psl));
         }
     }
     // column arrays of the block kernels when they do not fit into LDS: [B][4][rank][D] float2 (forward 2, sampler 3, reverse 4)
@@ -228,17 +238,17 @@ inline RhoLayout make_rho_layout(int D, int rank, int B, int T, int flags) {
     if (r * (size_t)D > RHO_LDS_COLS_MAX) o = align256(o + (size_t)B * 4 * r * D * sizeof(float2));
     L.vrank = 0;
     if (rho_wide_ok(D, rank, flags)) {
-        const size_t vr = (size_t)((rank + 1) / 2 * 2), vB = (size_t)B * vr, vp = vB / 2, NC = (N + 63) / 64;
+        const size_t vr = (size_t)((rank + 1) / 2 * 2), vB = (size_t)B * vr, vp = vB / 2;
         L.vrank = (int)vr;
-        L.vslab_floats = 4 * DP * DP + 3 * DP + 2;
+        L.vslab_floats = psi_slab_floats(DP);
         L.off_vphi = o;   o = align256(o + vr * DP * sizeof(float2));
         L.off_vstash = o; o = align256(o + vp * N * 8 * DP * sizeof(float));         // [virtual pair][step][y | H y][4 DP]
         L.off_vgops = o;  o = align256(o + vp * N * 4 * DP * sizeof(float));         // ybar rows
         L.off_vopmax = o; o = align256(o + vp * sizeof(float));
-        L.off_vscal = o;  o = align256(o + vB * NC * 128 * sizeof(float));           // (|y|^2 of the clip, e of the clip) per virtual clip
-        L.off_rscal = o;  o = align256(o + (size_t)B * NC * 128 * sizeof(float));    // the same per real clip
+        L.off_vscal = o;  o = align256(o + scal_bytes(vB, N));                       // (|y|^2 of the clip, e of the clip) per virtual clip
+        L.off_rscal = o;  o = align256(o + scal_bytes(B, N));                        // the same per real clip
         L.off_vslabs = o; o = align256(o + vp * L.vslab_floats * sizeof(float));
-        L.off_vsums = o;  o = align256(o + (L.vslab_floats + 64) * sizeof(float) + 32 * L.vslab_floats * sizeof(double));
+        L.off_vsums = o;  o = align256(o + sums_bytes(L.vslab_floats));
         L.off_vaudio = o; o = align256(o + vB * (size_t)T * sizeof(float));
         L.off_gphi = o;   o = align256(o + vB * 2 * DP * sizeof(float));
     }
@@ -272,6 +282,21 @@ struct RhoDev {
     float* sums;         // [slab]
     size_t slab_floats;
 };
+
+// ---- host-side dispatch of a run-time value to a template argument, written once for every launcher ----
+// f(std::integral_constant<int, PD>{}) for the padded bond dimension of the MFMA / wide kernels (64, 96 or 128)
+template <typename F>
+inline hipError_t dispatch_pd(int DP, F&& f) {
+    if (DP == 128) return f(std::integral_constant<int, 128>{});
+    if (DP == 96) return f(std::integral_constant<int, 96>{});
+    if (DP == 64) return f(std::integral_constant<int, 64>{});
+    return hipErrorInvalidValue;
+}
+// f(std::true_type{}) or f(std::false_type{})
+template <typename F>
+inline hipError_t dispatch_bool(bool b, F&& f) {
+    return b ? f(std::true_type{}) : f(std::false_type{});
+}
 
 // ---- launchers (each returns the hipError_t of its launches) ----
 hipError_t launch_pack_phi(const Dev& P, const RhoDev& W, const float* re, const float* im, hipStream_t s);

@@ -760,19 +760,13 @@ __global__ __launch_bounds__(4 * PD, 1) void k_fwd_pair(Dev P, const float* __re
 
 hipError_t launch_fwd_pair(const Dev& P, const float* audio, float* loss, bool save, hipStream_t s) {
     const unsigned nb = (unsigned)((P.B + 1) / 2);
-    if (P.DP == 128) {
-        if (save) hipLaunchKernelGGL((k_fwd_pair<128, true>), dim3(nb), dim3(512), 0, s, P, audio, loss);
-        else hipLaunchKernelGGL((k_fwd_pair<128, false>), dim3(nb), dim3(512), 0, s, P, audio, loss);
-    } else if (P.DP == 96) {
-        if (save) hipLaunchKernelGGL((k_fwd_pair<96, true>), dim3(nb), dim3(384), 0, s, P, audio, loss);
-        else hipLaunchKernelGGL((k_fwd_pair<96, false>), dim3(nb), dim3(384), 0, s, P, audio, loss);
-    } else if (P.DP == 64) {
-        if (save) hipLaunchKernelGGL((k_fwd_pair<64, true>), dim3(nb), dim3(256), 0, s, P, audio, loss);
-        else hipLaunchKernelGGL((k_fwd_pair<64, false>), dim3(nb), dim3(256), 0, s, P, audio, loss);
-    } else {
-        return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return dispatch_pd(P.DP, [&](auto pd) {
+        return dispatch_bool(save, [&](auto sv) {
+            constexpr int PD = decltype(pd)::value;
+            hipLaunchKernelGGL((k_fwd_pair<PD, decltype(sv)::value>), dim3(nb), dim3(4 * PD), 0, s, P, audio, loss);
+            return hipGetLastError();
+        });
+    });
 }
 
 
@@ -1085,19 +1079,12 @@ __global__ __launch_bounds__(2 * PD, 1) void k_fwd_chain16(Dev P, const float* _
 
 hipError_t launch_fwd_chain16(const Dev& P, const float* audio, hipStream_t s) {
     const unsigned nb = (unsigned)((P.B + 1) / 2);
-    if (P.DP == 128) {
-        hipLaunchKernelGGL((k_fwd_chain16<128, true>), dim3(nb), dim3(256), 0, s, P, audio);
-        hipLaunchKernelGGL((k_fwd_chain16<128, false>), dim3(nb), dim3(256), 0, s, P, audio);
-    } else if (P.DP == 96) {
-        hipLaunchKernelGGL((k_fwd_chain16<96, true>), dim3(nb), dim3(192), 0, s, P, audio);
-        hipLaunchKernelGGL((k_fwd_chain16<96, false>), dim3(nb), dim3(192), 0, s, P, audio);
-    } else if (P.DP == 64) {
-        hipLaunchKernelGGL((k_fwd_chain16<64, true>), dim3(nb), dim3(128), 0, s, P, audio);
-        hipLaunchKernelGGL((k_fwd_chain16<64, false>), dim3(nb), dim3(128), 0, s, P, audio);
-    } else {
-        return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return dispatch_pd(P.DP, [&](auto pd) {                          // both instances: each workgroup of one of them returns at once (Dev::qflag)
+        constexpr int PD = decltype(pd)::value;
+        hipLaunchKernelGGL((k_fwd_chain16<PD, true>), dim3(nb), dim3(2 * PD), 0, s, P, audio);
+        hipLaunchKernelGGL((k_fwd_chain16<PD, false>), dim3(nb), dim3(2 * PD), 0, s, P, audio);
+        return hipGetLastError();
+    });
 }
 
 }  // namespace cmps
@@ -1868,28 +1855,21 @@ __global__ __launch_bounds__(2 * PD, 1) void k_bwd_chain16(Dev P, const float* _
 
 hipError_t launch_bwd_chain16(const Dev& P, const float* audio, hipStream_t s) {
     const unsigned nb = (unsigned)((P.B + 1) / 2);
-    if (P.DP == 128) {
-        hipLaunchKernelGGL((k_bwd_chain16<128, true>), dim3(nb), dim3(256), 0, s, P, audio);
-        hipLaunchKernelGGL((k_bwd_chain16<128, false>), dim3(nb), dim3(256), 0, s, P, audio);
-    } else if (P.DP == 96) {
-        hipLaunchKernelGGL((k_bwd_chain16<96, true>), dim3(nb), dim3(192), 0, s, P, audio);
-        hipLaunchKernelGGL((k_bwd_chain16<96, false>), dim3(nb), dim3(192), 0, s, P, audio);
-    } else if (P.DP == 64) {
-        hipLaunchKernelGGL((k_bwd_chain16<64, true>), dim3(nb), dim3(128), 0, s, P, audio);
-        hipLaunchKernelGGL((k_bwd_chain16<64, false>), dim3(nb), dim3(128), 0, s, P, audio);
-    } else {
-        return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return dispatch_pd(P.DP, [&](auto pd) {
+        constexpr int PD = decltype(pd)::value;
+        hipLaunchKernelGGL((k_bwd_chain16<PD, true>), dim3(nb), dim3(2 * PD), 0, s, P, audio);
+        hipLaunchKernelGGL((k_bwd_chain16<PD, false>), dim3(nb), dim3(2 * PD), 0, s, P, audio);
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_bwd_pair(const Dev& P, const float* audio, hipStream_t s) {
     const unsigned nb = (unsigned)((P.B + 1) / 2);
-    if (P.DP == 128) hipLaunchKernelGGL(k_bwd_pair<128>, dim3(nb), dim3(256), 0, s, P, audio);
-    else if (P.DP == 96) hipLaunchKernelGGL(k_bwd_pair<96>, dim3(nb), dim3(192), 0, s, P, audio);
-    else if (P.DP == 64) hipLaunchKernelGGL(k_bwd_pair<64>, dim3(nb), dim3(128), 0, s, P, audio);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
+    return dispatch_pd(P.DP, [&](auto pd) {
+        constexpr int PD = decltype(pd)::value;
+        hipLaunchKernelGGL(k_bwd_pair<PD>, dim3(nb), dim3(2 * PD), 0, s, P, audio);
+        return hipGetLastError();
+    });
 }
 
 }  // namespace cmps
@@ -1909,11 +1889,11 @@ struct PairRows {
 
 hipError_t launch_grad_pair(const Dev& P, const float* audio, hipStream_t s) {
     const unsigned nb = (unsigned)((P.B + 1) / 2);
-    if (P.DP == 128) hipLaunchKernelGGL((k_grad_gemm<128, 1, PairRows<128>>), dim3(nb), dim3(256), 0, s, P, audio);
-    else if (P.DP == 96) hipLaunchKernelGGL((k_grad_gemm<96, 1, PairRows<96>>), dim3(nb), dim3(192), 0, s, P, audio);
-    else if (P.DP == 64) hipLaunchKernelGGL((k_grad_gemm<64, 1, PairRows<64>>), dim3(nb), dim3(128), 0, s, P, audio);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
+    return dispatch_pd(P.DP, [&](auto pd) {
+        constexpr int PD = decltype(pd)::value;
+        hipLaunchKernelGGL((k_grad_gemm<PD, 1, PairRows<PD>>), dim3(nb), dim3(2 * PD), 0, s, P, audio);
+        return hipGetLastError();
+    });
 }
 
 }  // namespace cmps

@@ -768,11 +768,12 @@ hipError_t launch_fwd_rho_mfma(const Dev& P, const RhoDev& W, const float* audio
 hipError_t launch_sample_rho_mfma(const Dev& P, const RhoDev& W, const float* noise, int n, int length, float* out, bool save,
                                   bool f16, hipStream_t s) {
     const unsigned nb = (unsigned)((n + WAVES - 1) / WAVES);
-    if (save && f16) hipLaunchKernelGGL((k_sample_rho_mfma<true, true>), dim3(nb), dim3(64 * WAVES), 0, s, P, W, noise, n, length, out);
-    else if (save) hipLaunchKernelGGL((k_sample_rho_mfma<true, false>), dim3(nb), dim3(64 * WAVES), 0, s, P, W, noise, n, length, out);
-    else if (f16) hipLaunchKernelGGL((k_sample_rho_mfma<false, true>), dim3(nb), dim3(64 * WAVES), 0, s, P, W, noise, n, length, out);
-    else hipLaunchKernelGGL((k_sample_rho_mfma<false, false>), dim3(nb), dim3(64 * WAVES), 0, s, P, W, noise, n, length, out);
-    return hipGetLastError();
+    return dispatch_bool(save, [&](auto sv) {
+        return dispatch_bool(f16, [&](auto hf) {
+            hipLaunchKernelGGL((k_sample_rho_mfma<decltype(sv)::value, decltype(hf)::value>), dim3(nb), dim3(64 * WAVES), 0, s, P, W, noise, n, length, out);
+            return hipGetLastError();
+        });
+    });
 }
 
 hipError_t launch_bwd_rho_mfma(const Dev& P, const RhoDev& W, const float* audio, hipStream_t s) {

@@ -304,7 +304,7 @@ hipError_t launch_bwd_rho_virtual_wave(const Dev& P, const RhoDev& W, const floa
     V.scal = W.scal;
     V.slabs = W.wslabs;
     V.sums = W.wsums;
-    V.slab_floats = (size_t)4 * P.DP * P.DP + 3 * P.DP + 2;
+    V.slab_floats = psi_slab_floats((size_t)P.DP);
     V.phi0 = W.phi0;
     V.phi_rank = W.rank;
     V.gphi = nullptr;

@@ -580,15 +580,12 @@ __global__ __launch_bounds__(128 * WAVES, 1) void k_fwd_wave2(Dev P, const float
 
 hipError_t launch_fwd_wave2(const Dev& P, const float* audio, float* loss, bool save, bool hf16, hipStream_t s) {
     const unsigned nb = (unsigned)((P.B + WAVES - 1) / WAVES);
-    if (save && hf16)
-        hipLaunchKernelGGL((k_fwd_wave2<true, false, true>), dim3(nb), dim3(128 * WAVES), 0, s, P, audio, loss);
-    else if (save)
-        hipLaunchKernelGGL((k_fwd_wave2<true, false, false>), dim3(nb), dim3(128 * WAVES), 0, s, P, audio, loss);
-    else if (hf16)
-        hipLaunchKernelGGL((k_fwd_wave2<false, false, true>), dim3(nb), dim3(128 * WAVES), 0, s, P, audio, loss);
-    else
-        hipLaunchKernelGGL((k_fwd_wave2<false, false, false>), dim3(nb), dim3(128 * WAVES), 0, s, P, audio, loss);
-    return hipGetLastError();
+    return dispatch_bool(save, [&](auto sv) {
+        return dispatch_bool(hf16, [&](auto hf) {
+            hipLaunchKernelGGL((k_fwd_wave2<decltype(sv)::value, false, decltype(hf)::value>), dim3(nb), dim3(128 * WAVES), 0, s, P, audio, loss);
+            return hipGetLastError();
+        });
+    });
 }
 
 hipError_t launch_fwd_legacy_wave(const Dev& P, const float* audio, float* loss, bool save, hipStream_t s) {

@@ -1234,15 +1234,29 @@ static hipError_t wide_lds_attr(K kernel, size_t shm) {
     return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
 }
 
+// k_hy_wide with two fp16 pieces (hy_f16) or three bf16 pieces: its LDS attribute, and its launch over `pairs` pairs of clips
+template <int PD>
+static hipError_t hy_wide_lds_attr(bool hy_f16) {
+    return dispatch_bool(hy_f16, [](auto f16) { return wide_lds_attr(k_hy_wide<PD, decltype(f16)::value>, HyGeom<PD>::LDS); });
+}
+template <int PD>
+static void launch_hy_wide(const Dev& P, unsigned pairs, bool hy_f16, hipStream_t s) {
+    const dim3 grid(pairs, (unsigned)((P.N + HCHUNK - 1) / HCHUNK));
+    (void)dispatch_bool(hy_f16, [&](auto f16) {
+        hipLaunchKernelGGL((k_hy_wide<PD, decltype(f16)::value>), grid, dim3(2 * PD), HyGeom<PD>::LDS, s, P);
+        return hipSuccess;
+    });
+}
+
 template <int PD, bool LEGACY = false>
 static hipError_t fwd_wide_t(const Dev& P, const float* audio, float* loss, bool save, bool hy_f16, bool chain_mfma, hipStream_t s) {
     const unsigned nb = (unsigned)((P.B + 1) / 2);
     hipError_t e;
     if (save) {
         // the serial chain, then H y / e_k for all (clip, step) pairs as one GEMM launch, then the sequential loss sums
-        const size_t shm = WideGeom<PD>::FWD_LDS_CHAIN, shm_hy = HyGeom<PD>::LDS;
+        const size_t shm = WideGeom<PD>::FWD_LDS_CHAIN;
         e = wide_lds_attr(k_fwd_wide<PD, true, LEGACY>, shm);
-        if (e == hipSuccess) e = hy_f16 ? wide_lds_attr(k_hy_wide<PD, true>, shm_hy) : wide_lds_attr(k_hy_wide<PD, false>, shm_hy);
+        if (e == hipSuccess) e = hy_wide_lds_attr<PD>(hy_f16);
         if (e != hipSuccess) return e;
         if (chain_mfma && !LEGACY) {
             KScope ks("k_fwd_chain16", s);
@@ -1253,9 +1267,7 @@ static hipError_t fwd_wide_t(const Dev& P, const float* audio, float* loss, bool
         }
         {
             KScope ks(hy_f16 ? "k_hy_wide<f16x2>" : "k_hy_wide<3>", s);
-            const dim3 grid(nb, (unsigned)((P.N + HCHUNK - 1) / HCHUNK));
-            if (hy_f16) hipLaunchKernelGGL((k_hy_wide<PD, true>), grid, dim3(2 * PD), shm_hy, s, P);
-            else hipLaunchKernelGGL((k_hy_wide<PD, false>), grid, dim3(2 * PD), shm_hy, s, P);
+            launch_hy_wide<PD>(P, nb, hy_f16, s);
         }
         { KScope ks("k_loss_wide", s); hipLaunchKernelGGL(k_loss_wide<LEGACY>, dim3((unsigned)P.B), dim3(64), 0, s, P, audio, loss); }
     } else {
@@ -1270,82 +1282,54 @@ static hipError_t fwd_wide_t(const Dev& P, const float* audio, float* loss, bool
 
 // the legacy AudioMPS arithmetic on the wide kernels (32 < D <= 128): the fp32 VALU chain kernels in their LEGACY mode + the same GEMMs
 hipError_t launch_fwd_wide_legacy(const Dev& P, const float* audio, float* loss, bool save, bool hy_f16, hipStream_t s) {
-    if (P.DP == 128) return fwd_wide_t<128, true>(P, audio, loss, save, hy_f16, false, s);
-    if (P.DP == 96) return fwd_wide_t<96, true>(P, audio, loss, save, hy_f16, false, s);
-    if (P.DP == 64) return fwd_wide_t<64, true>(P, audio, loss, save, hy_f16, false, s);
-    return hipErrorInvalidValue;
+    return dispatch_pd(P.DP, [&](auto pd) { return fwd_wide_t<decltype(pd)::value, true>(P, audio, loss, save, hy_f16, false, s); });
 }
 
-hipError_t launch_bwd_wide_legacy(const Dev& P, const float* audio, hipStream_t s) {
+template <bool LEGACY>
+static hipError_t bwd_wide_t(const Dev& P, const float* audio, hipStream_t s) {
     const unsigned nb = (unsigned)((P.B + 1) / 2);
-    if (P.DP == 128) hipLaunchKernelGGL((k_bwd_wide<128, true>), dim3(nb), dim3(512), 0, s, P, audio);
-    else if (P.DP == 96) hipLaunchKernelGGL((k_bwd_wide<96, true>), dim3(nb), dim3(384), 0, s, P, audio);
-    else if (P.DP == 64) hipLaunchKernelGGL((k_bwd_wide<64, true>), dim3(nb), dim3(256), 0, s, P, audio);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
+    return dispatch_pd(P.DP, [&](auto pd) {
+        constexpr int PD = decltype(pd)::value;
+        hipLaunchKernelGGL((k_bwd_wide<PD, LEGACY>), dim3(nb), dim3(4 * PD), 0, s, P, audio);
+        return hipGetLastError();
+    });
 }
+
+hipError_t launch_bwd_wide_legacy(const Dev& P, const float* audio, hipStream_t s) { return bwd_wide_t<true>(P, audio, s); }
 
 hipError_t launch_fwd_wide(const Dev& P, const float* audio, float* loss, bool save, bool hy_f16, bool chain_mfma, hipStream_t s) {
-    if (P.DP == 128) return fwd_wide_t<128>(P, audio, loss, save, hy_f16, chain_mfma, s);
-    if (P.DP == 96) return fwd_wide_t<96>(P, audio, loss, save, hy_f16, chain_mfma, s);
-    if (P.DP == 64) return fwd_wide_t<64>(P, audio, loss, save, hy_f16, chain_mfma, s);
-    return hipErrorInvalidValue;
+    return dispatch_pd(P.DP, [&](auto pd) { return fwd_wide_t<decltype(pd)::value>(P, audio, loss, save, hy_f16, chain_mfma, s); });
 }
 
 hipError_t launch_sample_wide(const Dev& P, const float* noise, int n, int length, float* out, hipStream_t s) {
     const unsigned nb = (unsigned)((n + 1) / 2);
-    if (P.DP == 128) hipLaunchKernelGGL(k_sample_wide<128>, dim3(nb), dim3(512), 0, s, P, noise, n, length, out);
-    else if (P.DP == 96) hipLaunchKernelGGL(k_sample_wide<96>, dim3(nb), dim3(384), 0, s, P, noise, n, length, out);
-    else if (P.DP == 64) hipLaunchKernelGGL(k_sample_wide<64>, dim3(nb), dim3(256), 0, s, P, noise, n, length, out);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
+    return dispatch_pd(P.DP, [&](auto pd) {
+        constexpr int PD = decltype(pd)::value;
+        hipLaunchKernelGGL(k_sample_wide<PD>, dim3(nb), dim3(4 * PD), 0, s, P, noise, n, length, out);
+        return hipGetLastError();
+    });
 }
 
-hipError_t launch_bwd_wide(const Dev& P, const float* audio, hipStream_t s) {
-    const unsigned nb = (unsigned)((P.B + 1) / 2);
-    if (P.DP == 128) hipLaunchKernelGGL(k_bwd_wide<128>, dim3(nb), dim3(512), 0, s, P, audio);
-    else if (P.DP == 96) hipLaunchKernelGGL(k_bwd_wide<96>, dim3(nb), dim3(384), 0, s, P, audio);
-    else if (P.DP == 64) hipLaunchKernelGGL(k_bwd_wide<64>, dim3(nb), dim3(256), 0, s, P, audio);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
-}
+hipError_t launch_bwd_wide(const Dev& P, const float* audio, hipStream_t s) { return bwd_wide_t<false>(P, audio, s); }
 
-template <int PD, int NPC, bool F16 = false, bool LEGACY = false>
+template <int NPC, bool F16 = false, bool LEGACY = false>
 static hipError_t grad_wide_t(const Dev& P, const float* audio, hipStream_t s) {
     const unsigned nb = (unsigned)((P.B + 1) / 2);
-    hipLaunchKernelGGL((k_grad_gemm<PD, NPC, WideRows<PD>, F16, LEGACY>), dim3(nb), dim3(2 * PD), 0, s, P, audio);   // static LDS: 2 x NPC x 160 PD + 4 KB
-    return hipGetLastError();
+    return dispatch_pd(P.DP, [&](auto pd) {
+        constexpr int PD = decltype(pd)::value;
+        hipLaunchKernelGGL((k_grad_gemm<PD, NPC, WideRows<PD>, F16, LEGACY>), dim3(nb), dim3(2 * PD), 0, s, P, audio);   // static LDS: 2 x NPC x 160 PD + 4 KB
+        return hipGetLastError();
+    });
 }
 
 // legacy mode: two fp16 pieces (CMPS_RANK1_F16X2 / DEFAULT) or three bf16 pieces (every other value)
 hipError_t launch_grad_wide_legacy(const Dev& P, const float* audio, bool f16, hipStream_t s) {
-    if (f16) {
-        if (P.DP == 128) return grad_wide_t<128, 2, true, true>(P, audio, s);
-        if (P.DP == 96) return grad_wide_t<96, 2, true, true>(P, audio, s);
-        if (P.DP == 64) return grad_wide_t<64, 2, true, true>(P, audio, s);
-    } else {
-        if (P.DP == 128) return grad_wide_t<128, 3, false, true>(P, audio, s);
-        if (P.DP == 96) return grad_wide_t<96, 3, false, true>(P, audio, s);
-        if (P.DP == 64) return grad_wide_t<64, 3, false, true>(P, audio, s);
-    }
-    return hipErrorInvalidValue;
+    return f16 ? grad_wide_t<2, true, true>(P, audio, s) : grad_wide_t<3, false, true>(P, audio, s);
 }
 
 hipError_t launch_grad_wide(const Dev& P, const float* audio, int pieces, hipStream_t s) {
-    if (pieces == -2) {                                           // two fp16 pieces (CMPS_RANK1_F16X2)
-        if (P.DP == 128) return grad_wide_t<128, 2, true>(P, audio, s);
-        if (P.DP == 96) return grad_wide_t<96, 2, true>(P, audio, s);
-        if (P.DP == 64) return grad_wide_t<64, 2, true>(P, audio, s);
-    } else if (pieces == 3) {
-        if (P.DP == 128) return grad_wide_t<128, 3>(P, audio, s);
-        if (P.DP == 96) return grad_wide_t<96, 3>(P, audio, s);
-        if (P.DP == 64) return grad_wide_t<64, 3>(P, audio, s);
-    } else {
-        if (P.DP == 128) return grad_wide_t<128, 2>(P, audio, s);
-        if (P.DP == 96) return grad_wide_t<96, 2>(P, audio, s);
-        if (P.DP == 64) return grad_wide_t<64, 2>(P, audio, s);
-    }
-    return hipErrorInvalidValue;
+    if (pieces == -2) return grad_wide_t<2, true>(P, audio, s);   // two fp16 pieces (CMPS_RANK1_F16X2)
+    return pieces == 3 ? grad_wide_t<3>(P, audio, s) : grad_wide_t<2>(P, audio, s);
 }
 
 // ------------------------------------------------------------------------------------------------------------------------
@@ -1374,9 +1358,9 @@ static Dev rho_virtual_dev(const Dev& P, const RhoDev& W) {
 template <int PD>
 static hipError_t fwd_rho_wide_t(const Dev& P, const RhoDev& W, const float* audio, float* loss, bool hy_f16, hipStream_t s) {
     const int npairs = W.vrank / 2, NC = (P.N + WCH - 1) / WCH;
-    const size_t shm = rho_wide_lds(P.D, W.rank), shm_hy = HyGeom<PD>::LDS;
+    const size_t shm = rho_wide_lds(P.D, W.rank);
     hipError_t e = wide_lds_attr(k_fwd_wide_rho<PD>, shm);
-    if (e == hipSuccess) e = hy_f16 ? wide_lds_attr(k_hy_wide<PD, true>, shm_hy) : wide_lds_attr(k_hy_wide<PD, false>, shm_hy);
+    if (e == hipSuccess) e = hy_wide_lds_attr<PD>(hy_f16);
     if (e != hipSuccess) return e;
     Dev V = rho_virtual_dev(P, W);
     {
@@ -1388,9 +1372,7 @@ static hipError_t fwd_rho_wide_t(const Dev& P, const RhoDev& W, const float* aud
     { KScope ks("k_rho_spread_n", s); hipLaunchKernelGGL(k_rho_spread_n, dim3((unsigned)V.B, (unsigned)NC), dim3(64), 0, s, W.rscal, W.vscal, NC, W.vrank); }
     {
         KScope ks(hy_f16 ? "k_hy_wide<f16x2>" : "k_hy_wide<3>", s);
-        const dim3 grid((unsigned)(V.B / 2), (unsigned)((P.N + HCHUNK - 1) / HCHUNK));
-        if (hy_f16) hipLaunchKernelGGL((k_hy_wide<PD, true>), grid, dim3(2 * PD), shm_hy, s, V);
-        else hipLaunchKernelGGL((k_hy_wide<PD, false>), grid, dim3(2 * PD), shm_hy, s, V);
+        launch_hy_wide<PD>(V, (unsigned)(V.B / 2), hy_f16, s);
     }
     { KScope ks("k_rho_merge_e", s); hipLaunchKernelGGL(k_rho_merge_e, dim3((unsigned)P.B, (unsigned)NC), dim3(64), 0, s, W.rscal, W.vscal, NC, W.vrank); }
     {
@@ -1403,10 +1385,7 @@ static hipError_t fwd_rho_wide_t(const Dev& P, const RhoDev& W, const float* aud
 }
 
 hipError_t launch_fwd_rho_wide(const Dev& P, const RhoDev& W, const float* audio, float* loss, bool hy_f16, hipStream_t s) {
-    if (P.DP == 128) return fwd_rho_wide_t<128>(P, W, audio, loss, hy_f16, s);
-    if (P.DP == 96) return fwd_rho_wide_t<96>(P, W, audio, loss, hy_f16, s);
-    if (P.DP == 64) return fwd_rho_wide_t<64>(P, W, audio, loss, hy_f16, s);
-    return hipErrorInvalidValue;
+    return dispatch_pd(P.DP, [&](auto pd) { return fwd_rho_wide_t<decltype(pd)::value>(P, W, audio, loss, hy_f16, s); });
 }
 
 // reverse chain + gradient GEMM on the virtual clips, the common reduction, the closing terms (k_finalize), the columns' cotangents.

@@ -63,7 +63,8 @@ class HipScan:
         self._opt_scratch = None
         self._B = self._T = self._rho_rank = 0
         self._audio = None
-        self._loss = None
+        self._loss = self._rho_loss = None            # per-clip losses of the main workspace's forwards (psi, legacy) and of rho_forward: each
+        #                                               reverse pass reads the loss buffer of its own forward (the handle's two records)
         self._grad = torch.empty(grad_size(D), dtype=torch.float32, device=self.device)
         self._legacy_grad = self._rho_grad = None
         self.f16_fallbacks = 0        # loss_and_grad_sums(check=True) re-runs that cmps_psi_grad_status asked for
@@ -223,16 +224,18 @@ class HipScan:
             raise ValueError(f"audio shape {tuple(audio.shape)} does not fit set_params(B={self._B}, T={self._T})")
         return B, T
 
-    def _forward(self, fn, audio: torch.Tensor, save_for_bwd: bool, timed: bool = False) -> torch.Tensor:
-        """The one forward driver: `fn` is cmps_{psi,legacy,rho}_loss_fwd.  Returns this object's per-clip loss tensor [B]."""
+    def _forward(self, fn, audio: torch.Tensor, save_for_bwd: bool, timed: bool = False, slot: str = "_loss") -> torch.Tensor:
+        """The one forward driver: `fn` is cmps_{psi,legacy,rho}_loss_fwd.  Returns this object's per-clip loss tensor [B] (`slot`)."""
         B, T = self._check_audio(audio)
-        if self._loss is None or self._loss.numel() != B:
-            self._loss = torch.empty(B, dtype=torch.float32, device=self.device)
+        loss = getattr(self, slot)
+        if loss is None or loss.numel() != B:
+            loss = torch.empty(B, dtype=torch.float32, device=self.device)
+            setattr(self, slot, loss)
         ev = self._event_pair() if timed else None
-        _capi.check(self._h, fn(self._h, audio.data_ptr(), B, T, self._loss.data_ptr(), 1 if save_for_bwd else 0, self._stream()))
+        _capi.check(self._h, fn(self._h, audio.data_ptr(), B, T, loss.data_ptr(), 1 if save_for_bwd else 0, self._stream()))
         self._event_close("fwd", ev)
         self._audio = audio
-        return self._loss
+        return loss
 
     def _backward(self, fn, grad: Optional[torch.Tensor], n: int, who: str = "", timed: bool = False) -> torch.Tensor:
         """The one backward driver: `fn` is cmps_{psi,legacy,rho}_loss_bwd, `grad` the caller's buffer for its `n` gradient sums
@@ -388,7 +391,7 @@ class HipScan:
         self._rho_rank = r
 
     def rho_forward(self, audio: torch.Tensor, save_for_bwd: bool = False) -> torch.Tensor:
-        return self._forward(self._lib.cmps_rho_loss_fwd, audio, save_for_bwd)
+        return self._forward(self._lib.cmps_rho_loss_fwd, audio, save_for_bwd, slot="_rho_loss")
 
     def rho_backward(self) -> torch.Tensor:
         self._rho_grad = self._backward(self._lib.cmps_rho_loss_bwd, self._rho_grad, self.rho_grad_size(self._rho_rank), "rho_")

@@ -259,6 +259,7 @@ int cmps_psi_update_ancilla(cmps_handle_t h, const float* psi_in_dev, const floa
  * Replaces: PsiCMPS.psi_evolve_with_data (model.py:231-240): the normalised lab-frame state after
  * every step, psi_out_dev [B*(T-1)*D*2] interleaved (re, im), reconstructed from the stash written by
  * cmps_psi_loss_fwd(..., save_for_bwd=1).
+ * In legacy mode (after cmps_legacy_set_params) it returns CMPS_ERR_STATE: the lab-frame phases need the time table, which that mode does not have.
  */
 int cmps_psi_states(cmps_handle_t h, int B, int T, float* psi_out_dev, void* stream);
 

@@ -24,4 +24,4 @@ f, bw = [], []
 for r in range(4):
     ev[0].record(); rb.rho_forward(d_a, save_for_bwd=True); ev[1].record(); rb.rho_backward(); ev[2].record(); torch.cuda.synchronize()
     if r: f.append(ev[0].elapsed_time(ev[1])); bw.append(ev[1].elapsed_time(ev[2]))
-print(f"D {D} rank {rank} T {T} B {B} variant {variant}: fwd {np.median(f):.3f} ms  bwd {np.median(bw):.3f} ms  loss {float(rb._loss.mean()):.6f}")
+print(f"D {D} rank {rank} T {T} B {B} variant {variant}: fwd {np.median(f):.3f} ms  bwd {np.median(bw):.3f} ms  loss {float(rb._rho_loss.mean()):.6f}")

@@ -79,6 +79,21 @@ def test_workspace_bytes(hip_lib):
     assert stash < trn < stash * 1.05                     # the per-step state stash dominates (8.4 GB at C3)
 
 
+def test_workspace_bytes_match_recorded_layouts(hip_lib):
+    """tests/golden/workspace_bytes.json: cmps_workspace_bytes and cmps_rho_workspace_bytes over D x B x T x flags (x rank), recorded from
+    the library before make_layout / make_rho_layout took their section sizes from one place each.  Every total stays byte-identical."""
+    import json
+    with open(os.path.join(ROOT, "tests", "golden", "workspace_bytes.json")) as f:
+        gold = json.load(f)
+    main, rho = gold["workspace"], gold["rho_workspace"]
+    assert len(main) == 9 * 3 * 3 * 2 and len(rho) >= 4 * len(main)
+    assert {r[0] for r in main} == {1, 16, 17, 32, 33, 64, 72, 96, 128} and {r[3] for r in main} == {0, 1}
+    for D, B, T, flags, nbytes in main:
+        assert hip_lib.cmps_workspace_bytes(D, B, T, flags) == nbytes > 0, (D, B, T, flags)
+    for D, rank, B, T, flags, nbytes in rho:
+        assert hip_lib.cmps_rho_workspace_bytes(D, rank, B, T, flags) == nbytes > 0, (D, rank, B, T, flags)
+
+
 def test_workspace_bytes_pair_variant(hip_lib):
     """32 < D <= 128 with CMPS_WS_TRAIN: the stash of (y, H y) in float32 plus the reverse scan's ybar rows (float32), from which the
     gradient GEMM builds its operands -- include/cmps.h / cmps_internal.h::make_layout (round 2: five bf16 operand arrays, 21 GB)."""

@@ -674,6 +674,24 @@ def test_legacy_wave_and_block_kernels_agree(T):
         assert rel_inf(ga[k], gb[k]) <= GRAD_RTOL, k
 
 
+@pytest.mark.parametrize("D", [12, 40])                          # the wave kernels' rows, the wide kernels' rows
+def test_states_is_a_call_order_error_in_legacy_mode(D):
+    """cmps_psi_states rotates the stash into the lab frame with freqs and the time table, which a handle in legacy mode does not have:
+    after legacy_forward(save) it returns CMPS_ERR_STATE (include/cmps.h) and launches nothing; the reverse pass still follows."""
+    from audio_mps_amd import LegacyAudioMPS, _capi
+    B, T, dt = 3, 70, 0.004
+    audio = make_audio(B, T, dt, D, noise=0.05)
+    m = LegacyAudioMPS(D, dt, B, data_iterator=audio, seed=4)
+    be = m._get_backend()
+    be.legacy_set_params(m.variables["R"], m.Q, m.delta_t, B, T, train=True)
+    loss = be.legacy_forward(torch.from_numpy(audio).to(be.device), save_for_bwd=True)
+    with pytest.raises(_capi.CmpsError) as ei:
+        be.states()
+    assert ei.value.code == _capi.CMPS_ERR_STATE
+    grad = be.legacy_backward()
+    assert torch.isfinite(loss).all() and torch.isfinite(grad).all()
+
+
 def test_legacy_full_size_properties():
     """The legacy arithmetic at the shape of scripts/bench_next_rows.py (D=32, T=4000, 1024 clips = one clip per SIMD): finite
     results, the reported loss is the mean of the per-clip losses, and the clip order does not matter (per-clip losses permute

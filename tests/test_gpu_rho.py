@@ -458,3 +458,38 @@ def test_rho_entries_after_set_params_dev(D, rank):
     assert np.all(np.isfinite(loss)) and np.all(np.isfinite(grad))
     np.testing.assert_allclose(loss, ref_loss, rtol=1e-6, atol=1e-6)
     np.testing.assert_allclose(grad, ref_grad, rtol=1e-5, atol=1e-6 * np.max(np.abs(ref_grad)))
+
+
+def test_psi_and_rho_saved_forwards_keep_separate_records():
+    """The handle keeps one saved-forward record per workspace.  A RhoCMPS call between a pure-state forward(save) and its backward()
+    (and the other way round) touches neither the other stash nor the other record: the gradient sums -- the loss slot included -- are
+    bit-identical to the uninterrupted pair of calls.  (One record for both used to hand k_finalize the other forward's loss buffer.)"""
+    D, rank, T, B = 24, 12, 130, 5
+    m, audio = _rho_model(D, T, B, rank=rank)
+    be = m._get_backend()
+    d_audio = m._to_device(audio)
+    be.set_params(m.effective_params(), B, T, train=True)
+    be.rho_set_state(m.columns(), B, T, train=True)
+
+    def bits(t):
+        a = t.cpu().numpy().copy()
+        assert np.all(np.isfinite(a))
+        return a.view(np.uint32)
+
+    be.forward(d_audio, save_for_bwd=True)
+    g1 = bits(be.backward())
+    be.forward(d_audio, save_for_bwd=True)
+    be.rho_forward(d_audio, save_for_bwd=True)
+    assert np.array_equal(bits(be.backward()), g1)
+    be.forward(d_audio, save_for_bwd=True)
+    be.rho_forward(d_audio)                                   # a forward that saves nothing invalidates only its own record
+    assert np.array_equal(bits(be.backward()), g1)
+    # the mirror: pure-state forwards between rho_forward(save) and rho_backward()
+    be.rho_forward(d_audio, save_for_bwd=True)
+    r1 = bits(be.rho_backward())
+    be.rho_forward(d_audio, save_for_bwd=True)
+    be.forward(d_audio, save_for_bwd=True)
+    assert np.array_equal(bits(be.rho_backward()), r1)
+    be.rho_forward(d_audio, save_for_bwd=True)
+    be.forward(d_audio)
+    assert np.array_equal(bits(be.rho_backward()), r1)
