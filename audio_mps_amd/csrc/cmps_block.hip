@@ -9,7 +9,7 @@
 //     n = max(|y|^2, 1e-12);  u_{k+1} = rho_k * y / sqrt(n)              model.py:331-334 (+ phases :305)
 //
 // where u_k = psi_k * conj(phases_k) is the reference's `Upsi` and rho_k = phases_k conj(phases_{k+1}).
-#include "cmps_lane_util.h"
+#include "cmps_block_util.h"
 
 namespace cmps {
 
@@ -160,22 +160,17 @@ __global__ __launch_bounds__(NT) void k_bwd_block(Dev P, const float* __restrict
         const float sbar = block_sum<NT>(act ? (d.x * uk.x + d.y * uk.y) : 0.f, red);
         Abar += sbar * (-x / (A * A));
         const float te = 2.0f * ebar;
-#pragma unroll
-        for (int m = 0; m < EPT; ++m) {
-            const int idx = t + m * NT;
-            if (idx < D * D) {
-                const int i = idx / D, j = idx % D;
-                const float2 yi = sy[i], yj = sy[j], ybi = syb[i], uj = su[j];
-                // yi * conj(yj)
-                const float2 o1 = make_float2(yi.x * yj.x + yi.y * yj.y, yi.y * yj.x - yi.x * yj.y);
-                // ybi * conj(uj)
-                const float2 o2 = make_float2(ybi.x * uj.x + ybi.y * uj.y, ybi.y * uj.x - ybi.x * uj.y);
-                Rb[m].x += te * o1.x + s * o2.x;
-                Rb[m].y += te * o1.y + s * o2.y;
-                Qb[m].x += o2.x;
-                Qb[m].y += o2.y;
-            }
-        }
+        for_owned<NT, EPT>(D, [&](int m, int i, int j) {
+            const float2 yi = sy[i], yj = sy[j], ybi = syb[i], uj = su[j];
+            // yi * conj(yj)
+            const float2 o1 = make_float2(yi.x * yj.x + yi.y * yj.y, yi.y * yj.x - yi.x * yj.y);
+            // ybi * conj(uj)
+            const float2 o2 = make_float2(ybi.x * uj.x + ybi.y * uj.y, ybi.y * uj.x - ybi.x * uj.y);
+            Rb[m].x += te * o1.x + s * o2.x;
+            Rb[m].y += te * o1.y + s * o2.y;
+            Qb[m].x += o2.x;
+            Qb[m].y += o2.y;
+        });
         __syncthreads();
         g = make_float2(ybar.x + bq.x + s * d.x, ybar.y + bq.y + s * d.y);
         y = yprev; nraw = nprev; inv = invp; yhat = yhatp; unext = uk;
@@ -185,17 +180,7 @@ __global__ __launch_bounds__(NT) void k_bwd_block(Dev P, const float* __restrict
     const int DD = DP * DP;
     for (int idx = t; idx < DD; idx += NT) slab[idx] = slab[DD + idx] = slab[2 * DD + idx] = slab[3 * DD + idx] = 0.f;
     __syncthreads();
-#pragma unroll
-    for (int m = 0; m < EPT; ++m) {
-        const int idx = t + m * NT;
-        if (idx < D * D) {
-            const int i = idx / D, j = idx % D, o = i * DP + j;
-            slab[o] = Rb[m].x;
-            slab[DD + o] = Rb[m].y;
-            slab[2 * DD + o] = Qb[m].x;
-            slab[3 * DD + o] = Qb[m].y;
-        }
-    }
+    store_rq_planes<NT, EPT>(slab, DD, D, DP, Rb, Qb);
     if (t < DP) {
         slab[4 * DD + t] = act ? facc : 0.f;
         slab[4 * DD + DP + t] = act ? g.x : 0.f;
@@ -291,10 +276,7 @@ __global__ void k_finalize(Dev P, const float* __restrict__ sums, const float* _
         }
     }
     if (blockIdx.x == 0 && threadIdx.x < 64) {      // sum_b loss_b: one wave, strided partials then a fixed-order tree
-        double ls = 0.0;
-        for (int b = threadIdx.x; b < P.B; b += 64) ls += (double)loss[b];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) ls += __shfl_xor(ls, off, 64);
+        const double ls = loss_sum_wave(loss, P.B);
         if (threadIdx.x == 0) {
             grad_out[2 * D * D + 3 * D + 1] = (float)ls;
             if (!isfinite((float)ls)) flag(2u);
@@ -317,10 +299,7 @@ __global__ void k_update_ancilla(Dev P, const float* __restrict__ psi_in,
     float2 psi = make_float2(0.f, 0.f), ph = make_float2(1.f, 0.f), u = psi;
     if (act) {
         psi = make_float2(psi_in[((size_t)b * D + i) * 2], psi_in[((size_t)b * D + i) * 2 + 1]);
-        const float th = __fmul_rn(P.freqs[i], t);                     // :305
-        float sn, cs;
-        sincosf(th, &sn, &cs);
-        ph = make_float2(cs, sn);
+        ph = phase(P.freqs[i], t);                                     // :305
         u = cmul_conj_a(ph, psi);                                      // :306
         su[i] = u;
     }
@@ -380,10 +359,7 @@ __global__ void k_states(Dev P, float* __restrict__ psi_out) {
     }
     if (act) {
         const float inv = 1.0f / sqrtf(fmaxf(n, 1e-12f));
-        const float th = __fmul_rn(P.freqs[i], P.ttab[k]);
-        float sn, cs;
-        sincosf(th, &sn, &cs);
-        const float2 o = cmul(make_float2(cs, sn), cscale(inv, y));
+        const float2 o = cmul(phase(P.freqs[i], P.ttab[k]), cscale(inv, y));
         psi_out[(row * D + i) * 2] = o.x;
         psi_out[(row * D + i) * 2 + 1] = o.y;
     }
@@ -431,26 +407,22 @@ __global__ __launch_bounds__(NT) void k_sample_block(Dev P, const float* __restr
 // ------------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------------
-static inline int round64(int d) { return (d + 63) / 64 * 64; }
-
 hipError_t launch_fwd_block(const Dev& P, const float* audio, float* loss, bool save, hipStream_t s) {
     const size_t shm = (size_t)2 * P.D * sizeof(float2) + 64;
-    if (P.D <= 64)
-        hipLaunchKernelGGL(k_fwd_block<64>, dim3(P.B), dim3(64), shm, s, P, audio, loss, save ? 1 : 0);
-    else
-        hipLaunchKernelGGL(k_fwd_block<128>, dim3(P.B), dim3(128), shm, s, P, audio, loss, save ? 1 : 0);
-    return hipGetLastError();
+    return dispatch_block_nt(P.D, [&](auto nt) {
+        constexpr int NT = decltype(nt)::value;
+        hipLaunchKernelGGL(k_fwd_block<NT>, dim3(P.B), dim3(NT), shm, s, P, audio, loss, save ? 1 : 0);
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_bwd_block(const Dev& P, const float* audio, hipStream_t s) {
     const size_t shm = (size_t)3 * P.D * sizeof(float2) + 128;
-    if (P.D <= 32)
-        hipLaunchKernelGGL((k_bwd_block<64, 16>), dim3(P.B), dim3(64), shm, s, P, audio);
-    else if (P.D <= 64)
-        hipLaunchKernelGGL((k_bwd_block<256, 16>), dim3(P.B), dim3(256), shm, s, P, audio);
-    else
-        hipLaunchKernelGGL((k_bwd_block<1024, 16>), dim3(P.B), dim3(1024), shm, s, P, audio);
-    return hipGetLastError();
+    return dispatch_block_bwd(P.D, [&](auto nt) {
+        constexpr int NT = decltype(nt)::value;
+        hipLaunchKernelGGL((k_bwd_block<NT, BLOCK_EPT>), dim3(P.B), dim3(NT), shm, s, P, audio);
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_reduce_only(const Dev& P, hipStream_t s) {
@@ -483,21 +455,21 @@ hipError_t launch_finalize_only(const Dev& P, const float* loss, float* grad_out
 hipError_t launch_update_ancilla(const Dev& P, const float* psi_in, const float* signal, float t,
                                  int B, float* psi_out, hipStream_t s) {
     const size_t shm = (size_t)2 * P.D * sizeof(float2);
-    hipLaunchKernelGGL(k_update_ancilla, dim3(B), dim3(round64(P.D)), shm, s, P, psi_in, signal, t, psi_out);
+    hipLaunchKernelGGL(k_update_ancilla, dim3(B), dim3(round_up64(P.D)), shm, s, P, psi_in, signal, t, psi_out);
     return hipGetLastError();
 }
 
 hipError_t launch_sample_block(const Dev& P, const float* noise, int n, int length, float* out, hipStream_t s) {
     const size_t shm = (size_t)P.D * sizeof(float2) + 64;
-    if (P.D <= 64)
-        hipLaunchKernelGGL(k_sample_block<64>, dim3(n), dim3(64), shm, s, P, noise, length, out);
-    else
-        hipLaunchKernelGGL(k_sample_block<128>, dim3(n), dim3(128), shm, s, P, noise, length, out);
-    return hipGetLastError();
+    return dispatch_block_nt(P.D, [&](auto nt) {
+        constexpr int NT = decltype(nt)::value;
+        hipLaunchKernelGGL(k_sample_block<NT>, dim3(n), dim3(NT), shm, s, P, noise, length, out);
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_states(const Dev& P, int B, float* psi_out, hipStream_t s) {
-    hipLaunchKernelGGL(k_states, dim3((unsigned)((size_t)B * P.N)), dim3(round64(P.D)), 0, s, P, psi_out);
+    hipLaunchKernelGGL(k_states, dim3((unsigned)((size_t)B * P.N)), dim3(round_up64(P.D)), 0, s, P, psi_out);
     return hipGetLastError();
 }
 

@@ -297,6 +297,36 @@ template <typename F>
 inline hipError_t dispatch_bool(bool b, F&& f) {
     return b ? f(std::true_type{}) : f(std::false_type{});
 }
+// f(std::integral_constant<int, NT>{}): threads per workgroup of the block-per-clip forward scans and samplers (one per component)
+template <typename F>
+inline hipError_t dispatch_block_nt(int D, F&& f) {
+    if (D <= 64) return f(std::integral_constant<int, 64>{});
+    return f(std::integral_constant<int, 128>{});
+}
+// the same for the block-per-clip reverse scans, whose threads each own BLOCK_EPT elements of Rbar and Qbar (NT * BLOCK_EPT >= D * D)
+constexpr int BLOCK_EPT = 16;
+template <typename F>
+inline hipError_t dispatch_block_bwd(int D, F&& f) {
+    if (D <= 32) return f(std::integral_constant<int, 64>{});
+    if (D <= 64) return f(std::integral_constant<int, 256>{});
+    return f(std::integral_constant<int, 1024>{});
+}
+// f(std::integral_constant<int, MODE>{}) for the rank-1 sums of k_bwd_wave (CMPS_RANK1_*: 0, 1, 3; every other value runs 2)
+template <typename F>
+inline hipError_t dispatch_rank1(int mode, F&& f) {
+    if (mode == 0) return f(std::integral_constant<int, 0>{});
+    if (mode == 1) return f(std::integral_constant<int, 1>{});
+    if (mode == 3) return f(std::integral_constant<int, 3>{});
+    return f(std::integral_constant<int, 2>{});
+}
+
+// a kernel's dynamic LDS above the 64 KB every kernel may ask for without saying so
+template <typename K>
+inline hipError_t lds_attr(K kernel, size_t shm) {
+    if (shm <= 64 * 1024) return hipSuccess;
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
+}
+inline int round_up64(int d) { return (d + 63) / 64 * 64; }   // whole waves for d threads
 
 // ---- launchers (each returns the hipError_t of its launches) ----
 hipError_t launch_pack_phi(const Dev& P, const RhoDev& W, const float* re, const float* im, hipStream_t s);

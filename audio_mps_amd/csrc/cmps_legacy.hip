@@ -10,45 +10,9 @@
 //   ybar = (g - yhat Re(yhat^dagger g)) / sqrt(n);  ebar = e - x
 //   vbar = dt x ybar + 2 ebar psi;   Qbar += ybar psi^dagger;   Rbar_c += vbar psi^dagger
 //   g    = ybar + Q^dagger ybar + 2 ebar R psi + R^dagger vbar
-#include "cmps_lane_util.h"
+#include "cmps_block_util.h"
 
 namespace cmps {
-
-// body(j, M1[j][t], M2[j][t]) for j = 0 .. D-1 in order, the matrix elements (L2 resident above D = 32) fetched a block of rows ahead
-// of their use (round 4, as rho_jloop in cmps_rho.hip): one L2 round trip per block of 8 rows instead of one per row
-template <class Body>
-__device__ __forceinline__ void leg_jloop(const float2* __restrict__ M1, const float2* __restrict__ M2, int D, int DP, int t, Body body) {
-    constexpr int JB = 8;
-    float2 n1[JB], n2[JB];
-#pragma unroll
-    for (int jj = 0; jj < JB; ++jj) {
-        const int j = jj < D ? jj : D - 1;
-        n1[jj] = M1[j * DP + t];
-        n2[jj] = M2[j * DP + t];
-    }
-    for (int j0 = 0; j0 < D; j0 += JB) {
-        float2 c1[JB], c2[JB];
-#pragma unroll
-        for (int jj = 0; jj < JB; ++jj) { c1[jj] = n1[jj]; c2[jj] = n2[jj]; }
-        if (j0 + JB < D) {
-#pragma unroll
-            for (int jj = 0; jj < JB; ++jj) {
-                int j = j0 + JB + jj;
-                j = j < D ? j : D - 1;
-                n1[jj] = M1[j * DP + t];
-                n2[jj] = M2[j * DP + t];
-            }
-        }
-        if (j0 + JB <= D) {
-#pragma unroll
-            for (int jj = 0; jj < JB; ++jj) body(j0 + jj, c1[jj], c2[jj]);
-        } else {
-#pragma unroll
-            for (int jj = 0; jj < JB; ++jj)
-                if (j0 + jj < D) body(j0 + jj, c1[jj], c2[jj]);
-        }
-    }
-}
 
 template <int NT>
 __global__ __launch_bounds__(NT) void k_fwd_legacy(Dev P, const float* __restrict__ audio,
@@ -70,7 +34,7 @@ __global__ __launch_bounds__(NT) void k_fwd_legacy(Dev P, const float* __restric
         __syncthreads();
         float2 v = make_float2(0.f, 0.f), q = make_float2(0.f, 0.f);
         if (act) {
-            leg_jloop(P.RT, P.QT, D, DP, t, [&](int j, float2 m1, float2 m2) {
+            jloop2(P.RT, P.QT, D, DP, t, [&](int j, float2 m1, float2 m2) {
                 const float2 pj = su[j];
                 v = cfma(m1, pj, v);
                 q = cfma(m2, pj, q);
@@ -113,7 +77,7 @@ __global__ __launch_bounds__(NT) void k_bwd_legacy(Dev P, const float* __restric
         __syncthreads();
         float2 v = zero, q = zero;
         if (act) {
-            leg_jloop(P.RT, P.QT, D, DP, t, [&](int j, float2 m1, float2 m2) {
+            jloop2(P.RT, P.QT, D, DP, t, [&](int j, float2 m1, float2 m2) {
                 const float2 pj = sp[j];
                 v = cfma(m1, pj, v);
                 q = cfma(m2, pj, q);
@@ -136,23 +100,18 @@ __global__ __launch_bounds__(NT) void k_bwd_legacy(Dev P, const float* __restric
         __syncthreads();
         float2 a = zero, r = zero;
         if (act) {
-            leg_jloop(P.Q, P.R, D, DP, t, [&](int j, float2 m1, float2 m2) {
+            jloop2(P.Q, P.R, D, DP, t, [&](int j, float2 m1, float2 m2) {
                 a = cfma_conj_a(m1, syb[j], a);     // (Q^dagger ybar)_t
                 r = cfma_conj_a(m2, svb[j], r);     // (R^dagger vbar)_t
             });
         }
-#pragma unroll
-        for (int m = 0; m < EPT; ++m) {
-            const int idx = t + m * NT;
-            if (idx < D * D) {
-                const int i = idx / D, j = idx % D;
-                const float2 ybi = syb[i], vbi = svb[i], pj = sp[j];
-                Qb[m].x += ybi.x * pj.x + ybi.y * pj.y;
-                Qb[m].y += ybi.y * pj.x - ybi.x * pj.y;
-                Rb[m].x += vbi.x * pj.x + vbi.y * pj.y;
-                Rb[m].y += vbi.y * pj.x - vbi.x * pj.y;
-            }
-        }
+        for_owned<NT, EPT>(D, [&](int m, int i, int j) {
+            const float2 ybi = syb[i], vbi = svb[i], pj = sp[j];
+            Qb[m].x += ybi.x * pj.x + ybi.y * pj.y;
+            Qb[m].y += ybi.y * pj.x - ybi.x * pj.y;
+            Rb[m].x += vbi.x * pj.x + vbi.y * pj.y;
+            Rb[m].y += vbi.y * pj.x - vbi.x * pj.y;
+        });
         __syncthreads();
         g = make_float2(ybar.x + a.x + te * v.x + r.x, ybar.y + a.y + te * v.y + r.y);
     }
@@ -160,17 +119,7 @@ __global__ __launch_bounds__(NT) void k_bwd_legacy(Dev P, const float* __restric
     const int DD = DP * DP;
     for (int idx = t; idx < (int)P.slab_floats; idx += NT) slab[idx] = 0.f;
     __syncthreads();
-#pragma unroll
-    for (int m = 0; m < EPT; ++m) {
-        const int idx = t + m * NT;
-        if (idx < D * D) {
-            const int i = idx / D, j = idx % D, o = i * DP + j;
-            slab[o] = Rb[m].x;
-            slab[DD + o] = Rb[m].y;
-            slab[2 * DD + o] = Qb[m].x;
-            slab[3 * DD + o] = Qb[m].y;
-        }
-    }
+    store_rq_planes<NT, EPT>(slab, DD, D, DP, Rb, Qb);
 }
 
 // pack R (real), Q (complex) and their transposes into the DP-strided tables
@@ -199,10 +148,7 @@ __global__ void k_finalize_legacy(Dev P, const float* __restrict__ sums, const f
         grad_out[2 * D * D + idx] = sums[o];
     }
     if (blockIdx.x == 0 && threadIdx.x < 64) {
-        double ls = 0.0;
-        for (int b = threadIdx.x; b < P.B; b += 64) ls += (double)loss[b];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) ls += __shfl_xor(ls, off, 64);
+        const double ls = loss_sum_wave(loss, P.B);
         if (threadIdx.x == 0) grad_out[3 * D * D] = (float)ls;
     }
 }
@@ -229,22 +175,20 @@ hipError_t launch_pack_legacy(const Dev& P, const float* Rr, const float* Qre, c
 
 hipError_t launch_fwd_legacy(const Dev& P, const float* audio, float* loss, bool save, hipStream_t s) {
     const size_t shm = (size_t)P.D * sizeof(float2) + 64;
-    if (P.D <= 64)
-        hipLaunchKernelGGL(k_fwd_legacy<64>, dim3(P.B), dim3(64), shm, s, P, audio, loss, save ? 1 : 0);
-    else
-        hipLaunchKernelGGL(k_fwd_legacy<128>, dim3(P.B), dim3(128), shm, s, P, audio, loss, save ? 1 : 0);
-    return hipGetLastError();
+    return dispatch_block_nt(P.D, [&](auto nt) {
+        constexpr int NT = decltype(nt)::value;
+        hipLaunchKernelGGL(k_fwd_legacy<NT>, dim3(P.B), dim3(NT), shm, s, P, audio, loss, save ? 1 : 0);
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_bwd_legacy(const Dev& P, const float* audio, hipStream_t s) {
     const size_t shm = (size_t)3 * P.D * sizeof(float2) + 128;
-    if (P.D <= 32)
-        hipLaunchKernelGGL((k_bwd_legacy<64, 16>), dim3(P.B), dim3(64), shm, s, P, audio);
-    else if (P.D <= 64)
-        hipLaunchKernelGGL((k_bwd_legacy<256, 16>), dim3(P.B), dim3(256), shm, s, P, audio);
-    else
-        hipLaunchKernelGGL((k_bwd_legacy<1024, 16>), dim3(P.B), dim3(1024), shm, s, P, audio);
-    return hipGetLastError();
+    return dispatch_block_bwd(P.D, [&](auto nt) {
+        constexpr int NT = decltype(nt)::value;
+        hipLaunchKernelGGL((k_bwd_legacy<NT, BLOCK_EPT>), dim3(P.B), dim3(NT), shm, s, P, audio);
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_finalize_legacy(const Dev& P, const float* loss, float* grad_out, hipStream_t s) {

@@ -15,50 +15,13 @@
 //     yhb_a = conj(rho_k) g_a;  dot = sum_a Re(yhat_a^dagger yhb_a);  ybar_a = (yhb_a - yhat_a dot)/sqrt(n) + 2 ebar H y_a
 //     Rbar += 2 ebar sum_a y_a y_a^dagger + s sum_a ybar_a u_a^dagger;   Qbar += sum_a ybar_a u_a^dagger
 //     g_a  = ybar_a + Q ybar_a + s R^dagger ybar_a;   fbar += dt_k sum_a Im(g_a conj(u_a(k+1)))
-#include "cmps_lane_util.h"
+#include "cmps_block_util.h"
 
 namespace cmps {
 
 // ------------------------------------------------------------------------------------------------
 // forward: RhoCMPS._build_loss_rho (model.py:133-144)
 // ------------------------------------------------------------------------------------------------
-constexpr int RHO_JB = 8;      // matrix rows fetched ahead per block
-
-// body(j, M1[j][tt], M2[j][tt]) for j = 0 .. D-1 in order, the matrix elements (L2 resident: three D x D tables do not fit L1 above
-// D = 32) fetched a block of RHO_JB rows ahead of their use: one L2 round trip per block instead of one per row
-template <class Body>
-__device__ __forceinline__ void rho_jloop(const float2* __restrict__ M1, const float2* __restrict__ M2, int D, int DP, int tt, Body body) {
-    float2 n1[RHO_JB], n2[RHO_JB];
-#pragma unroll
-    for (int jj = 0; jj < RHO_JB; ++jj) {
-        const int j = jj < D ? jj : D - 1;
-        n1[jj] = M1[j * DP + tt];
-        n2[jj] = M2[j * DP + tt];
-    }
-    for (int j0 = 0; j0 < D; j0 += RHO_JB) {
-        float2 c1[RHO_JB], c2[RHO_JB];
-#pragma unroll
-        for (int jj = 0; jj < RHO_JB; ++jj) { c1[jj] = n1[jj]; c2[jj] = n2[jj]; }
-        if (j0 + RHO_JB < D) {
-#pragma unroll
-            for (int jj = 0; jj < RHO_JB; ++jj) {
-                int j = j0 + RHO_JB + jj;
-                j = j < D ? j : D - 1;
-                n1[jj] = M1[j * DP + tt];
-                n2[jj] = M2[j * DP + tt];
-            }
-        }
-        if (j0 + RHO_JB <= D) {
-#pragma unroll
-            for (int jj = 0; jj < RHO_JB; ++jj) body(j0 + jj, c1[jj], c2[jj]);
-        } else {
-#pragma unroll
-            for (int jj = 0; jj < RHO_JB; ++jj)
-                if (j0 + jj < D) body(j0 + jj, c1[jj], c2[jj]);
-        }
-    }
-}
-
 template <int NT, int CW>
 __global__ __launch_bounds__(NT) void k_fwd_rho(Dev P, RhoDev W, const float* __restrict__ audio,
                                                 float* __restrict__ loss_out, int save, float2* gcols) {
@@ -94,7 +57,7 @@ __global__ __launch_bounds__(NT) void k_fwd_rho(Dev P, RhoDev W, const float* __
                 float2 v[CW], q[CW];
 #pragma unroll
                 for (int c = 0; c < CW; ++c) v[c] = q[c] = make_float2(0.f, 0.f);
-                rho_jloop(P.RT, P.Q, D, DP, tt, [&](int j, float2 m1, float2 m2) {
+                jloop2(P.RT, P.Q, D, DP, tt, [&](int j, float2 m1, float2 m2) {
 #pragma unroll
                     for (int c = 0; c < CW; ++c) {
                         const float2 uj = cur[co[c] + j];
@@ -124,7 +87,7 @@ __global__ __launch_bounds__(NT) void k_fwd_rho(Dev P, RhoDev W, const float* __
                 float2 hy[CW];
 #pragma unroll
                 for (int c = 0; c < CW; ++c) hy[c] = make_float2(0.f, 0.f);
-                rho_jloop(P.RT, P.R, D, DP, tt, [&](int j, float2 m1, float2 m2) {
+                jloop2(P.RT, P.R, D, DP, tt, [&](int j, float2 m1, float2 m2) {
 #pragma unroll
                     for (int c = 0; c < CW; ++c) {
                         const float2 yj = nxt[co[c] + j];
@@ -220,7 +183,7 @@ __global__ __launch_bounds__(NT) void k_bwd_rho(Dev P, RhoDev W, const float* __
                 float2 hy[CW];
 #pragma unroll
                 for (int c = 0; c < CW; ++c) hy[c] = zero;
-                rho_jloop(P.RT, P.R, D, DP, tt, [&](int j, float2 m1, float2 m2) {
+                jloop2(P.RT, P.R, D, DP, tt, [&](int j, float2 m1, float2 m2) {
 #pragma unroll
                     for (int c = 0; c < CW; ++c) {
                         const float2 yj = Y[co[c] + j];
@@ -286,7 +249,7 @@ __global__ __launch_bounds__(NT) void k_bwd_rho(Dev P, RhoDev W, const float* __
                 float2 bq[CW], d[CW];
 #pragma unroll
                 for (int c = 0; c < CW; ++c) bq[c] = d[c] = zero;
-                rho_jloop(P.Q, P.R, D, DP, tt, [&](int j, float2 m1, float2 m2) {
+                jloop2(P.Q, P.R, D, DP, tt, [&](int j, float2 m1, float2 m2) {
 #pragma unroll
                     for (int c = 0; c < CW; ++c) {
                         const float2 yj = YB[co[c] + j];
@@ -306,25 +269,20 @@ __global__ __launch_bounds__(NT) void k_bwd_rho(Dev P, RhoDev W, const float* __
         }
         const float sbar = block_sum<NT>(ps, red);
         Abar += sbar * (-x / (dev_A(P) * dev_A(P)));
-#pragma unroll
-        for (int m = 0; m < EPT; ++m) {
-            const int idx = t + m * NT;
-            if (idx < D * D) {
-                const int i = idx / D, j = idx % D;
-                float2 o1 = zero, o2 = zero;
-                for (int a = 0; a < r; ++a) {
-                    const float2 yi = Y[a * D + i], yj = Y[a * D + j], ybi = YB[a * D + i], uj = U[a * D + j];
-                    o1.x += yi.x * yj.x + yi.y * yj.y;
-                    o1.y += yi.y * yj.x - yi.x * yj.y;
-                    o2.x += ybi.x * uj.x + ybi.y * uj.y;
-                    o2.y += ybi.y * uj.x - ybi.x * uj.y;
-                }
-                Rb[m].x += te * o1.x + s * o2.x;
-                Rb[m].y += te * o1.y + s * o2.y;
-                Qb[m].x += o2.x;
-                Qb[m].y += o2.y;
+        for_owned<NT, EPT>(D, [&](int m, int i, int j) {
+            float2 o1 = zero, o2 = zero;
+            for (int a = 0; a < r; ++a) {
+                const float2 yi = Y[a * D + i], yj = Y[a * D + j], ybi = YB[a * D + i], uj = U[a * D + j];
+                o1.x += yi.x * yj.x + yi.y * yj.y;
+                o1.y += yi.y * yj.x - yi.x * yj.y;
+                o2.x += ybi.x * uj.x + ybi.y * uj.y;
+                o2.y += ybi.y * uj.x - ybi.x * uj.y;
             }
-        }
+            Rb[m].x += te * o1.x + s * o2.x;
+            Rb[m].y += te * o1.y + s * o2.y;
+            Qb[m].x += o2.x;
+            Qb[m].y += o2.y;
+        });
         __syncthreads();
     }
     // slab: the pure-state layout (psi_0 slots zero) followed by the cotangents of the r initial columns
@@ -332,17 +290,7 @@ __global__ __launch_bounds__(NT) void k_bwd_rho(Dev P, RhoDev W, const float* __
     const int DD = DP * DP;
     for (int idx = t; idx < (int)W.slab_floats; idx += NT) slab[idx] = 0.f;
     __syncthreads();
-#pragma unroll
-    for (int m = 0; m < EPT; ++m) {
-        const int idx = t + m * NT;
-        if (idx < D * D) {
-            const int i = idx / D, j = idx % D, o = i * DP + j;
-            slab[o] = Rb[m].x;
-            slab[DD + o] = Rb[m].y;
-            slab[2 * DD + o] = Qb[m].x;
-            slab[3 * DD + o] = Qb[m].y;
-        }
-    }
+    store_rq_planes<NT, EPT>(slab, DD, D, DP, Rb, Qb);
     if (act) {
         slab[4 * DD + t] = facc;
         float* tail = slab + 4 * DD + 3 * DP + 2;
@@ -400,12 +348,7 @@ __global__ __launch_bounds__(256) void k_states_rho(Dev P, RhoDev W, int steps, 
         if (!direct) Y[idx] = y;
         pn += y.x * y.x + y.y * y.y;
     }
-    if (t < D) {
-        const float th = __fmul_rn(P.freqs[t], P.ttab[k]);
-        float sn, cs;
-        sincosf(th, &sn, &cs);
-        ph[t] = make_float2(cs, sn);
-    }
+    if (t < D) ph[t] = phase(P.freqs[t], P.ttab[k]);
     const float n = block_sum<256>(pn, red);
     const float inv = 1.0f / fmaxf(n, 1e-12f);
     __syncthreads();
@@ -444,12 +387,7 @@ __global__ void k_update_ancilla_rho(Dev P, const float* __restrict__ rho_in, co
     const int b = blockIdx.x / D, i = blockIdx.x % D, t = threadIdx.x;
     const bool act = t < D;
     const float s = signal[b] / dev_A(P);
-    if (act) {
-        const float th = __fmul_rn(P.freqs[t], tt);
-        float sn, cs;
-        sincosf(th, &sn, &cs);
-        ph[t] = make_float2(cs, sn);
-    }
+    if (act) ph[t] = phase(P.freqs[t], tt);
     __syncthreads();
     auto Uel = [&](int a, int c) {
         const float2 q = P.Q[c * DP + a];           // Q[a][c] = conj(Q[c][a])
@@ -555,12 +493,6 @@ __global__ void k_pack_phi(int D, int DP, int r, const float* __restrict__ re, c
 // ------------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------------
-template <typename K>
-static hipError_t want_lds(K kernel, size_t shm) {
-    if (shm <= 64 * 1024) return hipSuccess;
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-}
-
 hipError_t launch_pack_phi(const Dev& P, const RhoDev& W, const float* re, const float* im, hipStream_t s) {
     const int n = W.rank * P.DP;
     hipLaunchKernelGGL(k_pack_phi, dim3((n + 255) / 256), dim3(256), 0, s, P.D, P.DP, W.rank, re, im,
@@ -569,8 +501,8 @@ hipError_t launch_pack_phi(const Dev& P, const RhoDev& W, const float* re, const
 }
 
 // beyond RHO_LDS_MAX (cmps_internal.h: rho_cols_spill) the column arrays go to RhoDev::cols (the workspace)
-static float2* cols_if_needed(const RhoDev& W, size_t want_lds_bytes, size_t& shm, int blocks) {
-    if (want_lds_bytes <= RHO_LDS_MAX) { shm = want_lds_bytes; return nullptr; }
+static float2* cols_if_needed(const RhoDev& W, size_t lds_bytes, size_t& shm, int blocks) {
+    if (lds_bytes <= RHO_LDS_MAX) { shm = lds_bytes; return nullptr; }
     shm = 1024;                                   // reduction scratch (and the phases of k_states_rho) only
     return (W.cols && blocks <= W.cols_blocks) ? W.cols : reinterpret_cast<float2*>(1);   // 1: "needed but not provided"
 }
@@ -578,14 +510,14 @@ static float2* cols_if_needed(const RhoDev& W, size_t want_lds_bytes, size_t& sh
 // columns per mat-vec chunk (accumulators in registers): 8 when every column group has at least 8 columns, else 4
 template <int NT, int CW>
 static hipError_t run_fwd_rho(const Dev& P, const RhoDev& W, const float* audio, float* loss, bool save, float2* g, size_t shm, hipStream_t s) {
-    hipError_t e = want_lds(k_fwd_rho<NT, CW>, shm);
+    hipError_t e = lds_attr(k_fwd_rho<NT, CW>, shm);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL((k_fwd_rho<NT, CW>), dim3(P.B), dim3(NT), shm, s, P, W, audio, loss, save ? 1 : 0, g);
     return hipGetLastError();
 }
 template <int NT, int EPT, int CW>
 static hipError_t run_bwd_rho(const Dev& P, const RhoDev& W, const float* audio, float2* g, size_t shm, hipStream_t s) {
-    hipError_t e = want_lds(k_bwd_rho<NT, EPT, CW>, shm);
+    hipError_t e = lds_attr(k_bwd_rho<NT, EPT, CW>, shm);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL((k_bwd_rho<NT, EPT, CW>), dim3(P.B), dim3(NT), shm, s, P, W, audio, g);
     return hipGetLastError();
@@ -605,9 +537,12 @@ hipError_t launch_bwd_rho(const Dev& P, const RhoDev& W, const float* audio, hip
     size_t shm;
     float2* g = cols_if_needed(W, (size_t)4 * W.rank * P.D * sizeof(float2) + 128, shm, P.B);
     if (g == reinterpret_cast<float2*>(1)) return hipErrorInvalidValue;
-    if (P.D <= 32) return W.rank >= 8 ? run_bwd_rho<64, 16, 8>(P, W, audio, g, shm, s) : run_bwd_rho<64, 16, 4>(P, W, audio, g, shm, s);
-    if (P.D <= 64) return W.rank >= 32 ? run_bwd_rho<256, 16, 8>(P, W, audio, g, shm, s) : run_bwd_rho<256, 16, 4>(P, W, audio, g, shm, s);
-    return W.rank >= 64 ? run_bwd_rho<1024, 16, 8>(P, W, audio, g, shm, s) : run_bwd_rho<1024, 16, 4>(P, W, audio, g, shm, s);   // eight groups
+    return dispatch_block_bwd(P.D, [&](auto nt) {
+        constexpr int NT = decltype(nt)::value, GROUPS = NT == 64 ? 1 : NT == 256 ? 4 : 8;   // column groups: NT / 64 up to D = 64, NT / 128 above
+        return dispatch_bool(W.rank >= 8 * GROUPS, [&](auto cw8) {
+            return run_bwd_rho<NT, BLOCK_EPT, decltype(cw8)::value ? 8 : 4>(P, W, audio, g, shm, s);
+        });
+    });
 }
 
 hipError_t launch_finalize_rho(const Dev& P, const RhoDev& W, float* grad_out, hipStream_t s) {
@@ -620,7 +555,7 @@ hipError_t launch_states_rho(const Dev& P, const RhoDev& W, int B, int steps, fl
     size_t shm = ((size_t)W.rank * P.D + P.D) * sizeof(float2) + 128;
     const int direct = shm > RHO_LDS_MAX ? 1 : 0;
     if (direct) shm = (size_t)P.D * sizeof(float2) + 128;
-    hipError_t e = want_lds(k_states_rho, shm);
+    hipError_t e = lds_attr(k_states_rho, shm);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_states_rho, dim3((unsigned)((size_t)B * steps)), dim3(256), shm, s, P, W, steps, rho_out, purity_out, direct);
     return hipGetLastError();
@@ -629,8 +564,7 @@ hipError_t launch_states_rho(const Dev& P, const RhoDev& W, int B, int steps, fl
 hipError_t launch_update_ancilla_rho(const Dev& P, const float* rho_in, const float* signal, float t, int B,
                                      float* rho_out, hipStream_t s) {
     const size_t shm = (size_t)3 * P.D * sizeof(float2);
-    const int nt = (P.D + 63) / 64 * 64;
-    hipLaunchKernelGGL(k_update_ancilla_rho, dim3((unsigned)(B * P.D)), dim3(nt), shm, s, P, rho_in, signal, t, rho_out);
+    hipLaunchKernelGGL(k_update_ancilla_rho, dim3((unsigned)(B * P.D)), dim3(round_up64(P.D)), shm, s, P, rho_in, signal, t, rho_out);
     return hipGetLastError();
 }
 
@@ -639,15 +573,13 @@ hipError_t launch_sample_rho(const Dev& P, const RhoDev& W, const float* noise, 
     size_t shm;
     float2* g = cols_if_needed(W, (size_t)3 * W.rank * P.D * sizeof(float2) + 128, shm, n);
     if (g == reinterpret_cast<float2*>(1)) return hipErrorInvalidValue;
-    hipError_t e;
-    if (P.D <= 64) {
-        if ((e = want_lds(k_sample_rho<64>, shm)) != hipSuccess) return e;
-        hipLaunchKernelGGL(k_sample_rho<64>, dim3(n), dim3(64), shm, s, P, W, noise, length, out, save ? 1 : 0, g);
-    } else {
-        if ((e = want_lds(k_sample_rho<128>, shm)) != hipSuccess) return e;
-        hipLaunchKernelGGL(k_sample_rho<128>, dim3(n), dim3(128), shm, s, P, W, noise, length, out, save ? 1 : 0, g);
-    }
-    return hipGetLastError();
+    return dispatch_block_nt(P.D, [&](auto nt) {
+        constexpr int NT = decltype(nt)::value;
+        const hipError_t e = lds_attr(k_sample_rho<NT>, shm);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(k_sample_rho<NT>, dim3(n), dim3(NT), shm, s, P, W, noise, length, out, save ? 1 : 0, g);
+        return hipGetLastError();
+    });
 }
 
 }  // namespace cmps

@@ -723,26 +723,19 @@ hipError_t launch_sample_wave(const Dev& P, const float* noise, int n, int lengt
 
 hipError_t launch_bwd_legacy_wave(const Dev& P, const float* audio, int rank1_mode, hipStream_t s) {
     const unsigned nb = (unsigned)((P.B + WAVES - 1) / WAVES);
-    if (rank1_mode == 0)
-        hipLaunchKernelGGL((k_bwd_wave<0, true>), dim3(nb), dim3(64 * WAVES), 0, s, P, audio);
-    else if (rank1_mode == 1)
-        hipLaunchKernelGGL((k_bwd_wave<1, true>), dim3(nb), dim3(64 * WAVES), 0, s, P, audio);
-    else
-        hipLaunchKernelGGL((k_bwd_wave<2, true>), dim3(nb), dim3(64 * WAVES), 0, s, P, audio);
-    return hipGetLastError();
+    return dispatch_rank1(rank1_mode, [&](auto mode) {
+        constexpr int M = decltype(mode)::value == 3 ? 2 : decltype(mode)::value;    // the legacy scan has no instance 3: mode 3 runs 2
+        hipLaunchKernelGGL((k_bwd_wave<M, true>), dim3(nb), dim3(64 * WAVES), 0, s, P, audio);
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_bwd_wave(const Dev& P, const float* audio, int rank1_mode, hipStream_t s) {
     const unsigned nb = (unsigned)((P.B + WAVES - 1) / WAVES);
-    if (rank1_mode == 0)
-        hipLaunchKernelGGL(k_bwd_wave<0>, dim3(nb), dim3(64 * WAVES), 0, s, P, audio);
-    else if (rank1_mode == 1)
-        hipLaunchKernelGGL(k_bwd_wave<1>, dim3(nb), dim3(64 * WAVES), 0, s, P, audio);
-    else if (rank1_mode == 3)
-        hipLaunchKernelGGL(k_bwd_wave<3>, dim3(nb), dim3(64 * WAVES), 0, s, P, audio);
-    else
-        hipLaunchKernelGGL(k_bwd_wave<2>, dim3(nb), dim3(64 * WAVES), 0, s, P, audio);
-    return hipGetLastError();
+    return dispatch_rank1(rank1_mode, [&](auto mode) {
+        hipLaunchKernelGGL(k_bwd_wave<decltype(mode)::value>, dim3(nb), dim3(64 * WAVES), 0, s, P, audio);
+        return hipGetLastError();
+    });
 }
 
 }  // namespace cmps

@@ -1228,16 +1228,10 @@ struct WideRows {
 // ------------------------------------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------------------------------------
-template <typename K>
-static hipError_t wide_lds_attr(K kernel, size_t shm) {
-    if (shm <= 64 * 1024) return hipSuccess;
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-}
-
 // k_hy_wide with two fp16 pieces (hy_f16) or three bf16 pieces: its LDS attribute, and its launch over `pairs` pairs of clips
 template <int PD>
 static hipError_t hy_wide_lds_attr(bool hy_f16) {
-    return dispatch_bool(hy_f16, [](auto f16) { return wide_lds_attr(k_hy_wide<PD, decltype(f16)::value>, HyGeom<PD>::LDS); });
+    return dispatch_bool(hy_f16, [](auto f16) { return lds_attr(k_hy_wide<PD, decltype(f16)::value>, HyGeom<PD>::LDS); });
 }
 template <int PD>
 static void launch_hy_wide(const Dev& P, unsigned pairs, bool hy_f16, hipStream_t s) {
@@ -1255,7 +1249,7 @@ static hipError_t fwd_wide_t(const Dev& P, const float* audio, float* loss, bool
     if (save) {
         // the serial chain, then H y / e_k for all (clip, step) pairs as one GEMM launch, then the sequential loss sums
         const size_t shm = WideGeom<PD>::FWD_LDS_CHAIN;
-        e = wide_lds_attr(k_fwd_wide<PD, true, LEGACY>, shm);
+        e = lds_attr(k_fwd_wide<PD, true, LEGACY>, shm);
         if (e == hipSuccess) e = hy_wide_lds_attr<PD>(hy_f16);
         if (e != hipSuccess) return e;
         if (chain_mfma && !LEGACY) {
@@ -1272,7 +1266,7 @@ static hipError_t fwd_wide_t(const Dev& P, const float* audio, float* loss, bool
         { KScope ks("k_loss_wide", s); hipLaunchKernelGGL(k_loss_wide<LEGACY>, dim3((unsigned)P.B), dim3(64), 0, s, P, audio, loss); }
     } else {
         const size_t shm = WideGeom<PD>::FWD_LDS;
-        e = wide_lds_attr(k_fwd_wide<PD, false, LEGACY>, shm);
+        e = lds_attr(k_fwd_wide<PD, false, LEGACY>, shm);
         if (e != hipSuccess) return e;
         KScope ks("k_fwd_wide", s);
         hipLaunchKernelGGL((k_fwd_wide<PD, false, LEGACY>), dim3(nb), dim3(4 * PD), shm, s, P, audio, loss);
@@ -1359,7 +1353,7 @@ template <int PD>
 static hipError_t fwd_rho_wide_t(const Dev& P, const RhoDev& W, const float* audio, float* loss, bool hy_f16, hipStream_t s) {
     const int npairs = W.vrank / 2, NC = (P.N + WCH - 1) / WCH;
     const size_t shm = rho_wide_lds(P.D, W.rank);
-    hipError_t e = wide_lds_attr(k_fwd_wide_rho<PD>, shm);
+    hipError_t e = lds_attr(k_fwd_wide_rho<PD>, shm);
     if (e == hipSuccess) e = hy_wide_lds_attr<PD>(hy_f16);
     if (e != hipSuccess) return e;
     Dev V = rho_virtual_dev(P, W);
