@@ -369,9 +369,13 @@ __global__ void k_states(Dev P, float* __restrict__ psi_out) {
 // ------------------------------------------------------------------------------------------------
 // PsiCMPS.sample (model.py:242-251, 284-291), general D: one workgroup per sample path.
 // ------------------------------------------------------------------------------------------------
-template <int NT>
-__global__ __launch_bounds__(NT) void k_sample_block(Dev P, const float* __restrict__ noise, int length,
-                                                     float* __restrict__ out) {
+// PRIMED (cmps_psi_sample_primed): PF = prime_T - 1 teacher-forced steps (increment prime[k + 1] - prime[k], model.py:263; running sum
+// 0; e_k dt to pred[b][k] when asked) in front of the `length` sampled ones, which read noise[b][k - PF] and write out[b][k - PF]; table
+// row k throughout.  The unprimed instance (cmps_psi_sample) ignores its last four
+// arguments and is the kernel as it was (profiles/primed_sampler_isa_identity.log).
+template <int NT, bool PRIMED>
+__global__ __launch_bounds__(NT) void k_sample_block(Dev P, const float* __restrict__ noise, int length, float* __restrict__ out,
+                                                     const float* __restrict__ prime, int prime_stride, int PF, float* __restrict__ pred) {
     extern __shared__ float2 sh[];
     const int D = P.D, DP = P.DP;
     float2* su = sh;
@@ -380,7 +384,9 @@ __global__ __launch_bounds__(NT) void k_sample_block(Dev P, const float* __restr
     const bool act = t < D;
     float2 u = act ? P.psi0[t] : make_float2(0.f, 0.f);
     float samp = 0.f;
-    for (int k = 0; k < length; ++k) {
+    const int nsteps = PRIMED ? PF + length : length;
+    const float* prow = PRIMED ? prime + (size_t)b * prime_stride : nullptr;      // (prime_stride 0: one clip shared by all paths)
+    for (int k = 0; k < nsteps; ++k) {
         if (act) su[t] = u;
         __syncthreads();
         float2 v = make_float2(0.f, 0.f), q = make_float2(0.f, 0.f);
@@ -392,14 +398,28 @@ __global__ __launch_bounds__(NT) void k_sample_block(Dev P, const float* __restr
             }
         }
         const float e = 2.0f * block_sum<NT>(act ? (u.x * v.x + u.y * v.y) : 0.f, red);   // model.py:319-325
-        const float inc = e * P.dt + noise[(size_t)b * length + k];                        // :286
-        samp += inc;                                                                       // :287
+        float inc;
+        const bool forced = PRIMED && k < PF;
+        if constexpr (PRIMED) {
+            inc = forced ? prow[k + 1] - prow[k] : e * P.dt + noise[(size_t)b * length + (k - PF)];
+            samp = forced ? 0.f : samp + inc;
+        } else {
+            inc = e * P.dt + noise[(size_t)b * length + k];                                // :286
+            samp += inc;                                                                   // :287
+        }
         const float s = inc / dev_A(P);                                                         // :288, :303
         const float2 y = make_float2(u.x + q.x + s * v.x, u.y + q.y + s * v.y);
         const float n = block_sum<NT>(act ? (y.x * y.x + y.y * y.y) : 0.f, red);
         const float inv = 1.0f / sqrtf(fmaxf(n, 1e-12f));                                  // :289
         if (act) u = cmul(P.rho[(size_t)k * DP + t], cscale(inv, y));
-        if (t == 0) out[(size_t)b * length + k] = dev_A(P) * samp;                              // :251
+        if constexpr (PRIMED) {
+            if (t == 0) {
+                if (!forced) out[(size_t)b * length + (k - PF)] = dev_A(P) * samp;
+                else if (pred) pred[(size_t)b * PF + k] = e * P.dt;
+            }
+        } else {
+            if (t == 0) out[(size_t)b * length + k] = dev_A(P) * samp;                          // :251
+        }
         __syncthreads();
     }
 }
@@ -463,7 +483,17 @@ hipError_t launch_sample_block(const Dev& P, const float* noise, int n, int leng
     const size_t shm = (size_t)P.D * sizeof(float2) + 64;
     return dispatch_block_nt(P.D, [&](auto nt) {
         constexpr int NT = decltype(nt)::value;
-        hipLaunchKernelGGL(k_sample_block<NT>, dim3(n), dim3(NT), shm, s, P, noise, length, out);
+        hipLaunchKernelGGL((k_sample_block<NT, false>), dim3(n), dim3(NT), shm, s, P, noise, length, out, (const float*)nullptr, 0, 0, (float*)nullptr);
+        return hipGetLastError();
+    });
+}
+
+hipError_t launch_sample_block_primed(const Dev& P, const float* prime, int prime_stride, int PF, const float* noise, int n, int length,
+                                      float* out, float* pred, hipStream_t s) {
+    const size_t shm = (size_t)P.D * sizeof(float2) + 64;
+    return dispatch_block_nt(P.D, [&](auto nt) {
+        constexpr int NT = decltype(nt)::value;
+        hipLaunchKernelGGL((k_sample_block<NT, true>), dim3(n), dim3(NT), shm, s, P, noise, length, out, prime, prime_stride, PF, pred);
         return hipGetLastError();
     });
 }

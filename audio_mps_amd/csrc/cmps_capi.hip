@@ -99,6 +99,16 @@ bool rank1_f16(int mode) { return mode == CMPS_RANK1_DEFAULT || mode == CMPS_RAN
 // ... and as the wide kernels' gradient GEMM takes it: -2 two fp16 pieces, 2 two bf16 pieces, 3 three bf16 pieces
 int rank1_wide_pieces(int mode) { return rank1_f16(mode) ? -2 : mode == CMPS_RANK1_BF16X2 ? 2 : 3; }
 
+// The pure-state sampler kernel of a handle (cmps_psi_sample and cmps_psi_sample_primed): wave-per-path for D <= 32, the wide chain's
+// sampling mode for 32 < D <= 128 (float32; also what the bf16 pair variant samples with: sampling has no reduced-precision form),
+// the block kernel otherwise
+enum { SAMPLER_BLOCK, SAMPLER_WAVE, SAMPLER_WIDE };
+int sampler_family(const cmps_handle_s* h) {
+    const int sv = resolve_variant(h);
+    return (sv == CMPS_VARIANT_WAVE || sv == CMPS_VARIANT_WAVE32) ? SAMPLER_WAVE
+         : (sv == CMPS_VARIANT_WIDE || sv == CMPS_VARIANT_PAIR)   ? SAMPLER_WIDE : SAMPLER_BLOCK;
+}
+
 // The sections of a workspace as the kernels see them: everything a Dev takes from the Layout alone.  The callers add what is their
 // own (the scalars; the time table, which the legacy mode does not have).
 Dev bind_workspace(const Layout& L, char* ws) {
@@ -175,7 +185,7 @@ hipError_t reduce_pairs_finalize(Dev P, int abar_fix, const float* loss, float* 
 
 extern "C" {
 
-int cmps_version(void) { return 300; }
+int cmps_version(void) { return 400; }
 
 int cmps_create(int D, cmps_handle_t* out) {
     if (!out) return CMPS_ERR_BAD_ARG;
@@ -488,13 +498,42 @@ int cmps_psi_sample(cmps_handle_t h, const float* noise_dev, int n, int length, 
     if (length > h->L.N)
         return fail(h, CMPS_ERR_BAD_ARG, "cmps_psi_sample: length exceeds T - 1 of cmps_set_params (the per-step tables)");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const int sv = resolve_variant(h);
-    // wave-per-path kernel for D <= 32, the wide chain's sampling mode for 32 < D <= 128 (float32; also what the bf16 pair variant
-    // samples with: sampling has no reduced-precision form), the block kernel otherwise
-    hipError_t e = (sv == CMPS_VARIANT_WAVE || sv == CMPS_VARIANT_WAVE32) ? launch_sample_wave(h->P, noise_dev, n, length, out_dev, s)
-                   : (sv == CMPS_VARIANT_WIDE || sv == CMPS_VARIANT_PAIR)  ? launch_sample_wide(h->P, noise_dev, n, length, out_dev, s)
-                                                                           : launch_sample_block(h->P, noise_dev, n, length, out_dev, s);
+    const int family = sampler_family(h);
+    KBind kb(h);
+    KScope ks(family == SAMPLER_WAVE ? "k_sample_wave" : family == SAMPLER_WIDE ? "k_sample_wide" : "k_sample_block", s);
+    hipError_t e = family == SAMPLER_WAVE ? launch_sample_wave(h->P, noise_dev, n, length, out_dev, s)
+                 : family == SAMPLER_WIDE ? launch_sample_wide(h->P, noise_dev, n, length, out_dev, s)
+                                          : launch_sample_block(h->P, noise_dev, n, length, out_dev, s);
     if (e != hipSuccess) return fail_hip(h, e, "cmps_psi_sample");
+    return CMPS_OK;
+}
+
+int cmps_psi_sample_primed(cmps_handle_t h, const float* prime_dev, int n_prime, int prime_T, const float* noise_dev, int n, int length,
+                           float* out_dev, float* pred_dev, void* stream) {
+    if (!h) return CMPS_ERR_BAD_ARG;
+    if (!h->params_set || h->legacy)       // (the legacy tables carry no rotation and another step: nothing here would mean PsiCMPS.sample)
+        return fail(h, CMPS_ERR_STATE, "cmps_psi_sample_primed: call cmps_set_params first (not available in legacy mode)");
+    if (!prime_dev || !noise_dev || !out_dev) return fail(h, CMPS_ERR_BAD_ARG, "cmps_psi_sample_primed: null pointer");
+    if (n < 1 || length < 1) return fail(h, CMPS_ERR_BAD_ARG, "cmps_psi_sample_primed: need n >= 1 and length >= 1");
+    if (prime_T < 2) return fail(h, CMPS_ERR_BAD_ARG, "cmps_psi_sample_primed: need prime_T >= 2 (one increment at least)");
+    if (n_prime != 1 && n_prime != n)
+        return fail(h, CMPS_ERR_BAD_ARG, "cmps_psi_sample_primed: n_prime must be n, or 1 for one clip shared by every path");
+    const int PF = prime_T - 1;                                  // teacher-forced steps
+    if ((long long)PF + length > h->L.N) {                        // one table row per step, forced or sampled
+        char buf[200];
+        snprintf(buf, sizeof buf, "cmps_psi_sample_primed: prime_T + length = %lld exceeds T = %d of cmps_set_params (the per-step tables): "
+                 "needs T >= %lld", (long long)prime_T + length, h->L.T, (long long)prime_T + length);
+        return fail(h, CMPS_ERR_BAD_ARG, buf);
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int family = sampler_family(h);                         // exactly cmps_psi_sample's choice
+    const int stride = n_prime == 1 ? 0 : prime_T;
+    KBind kb(h);
+    KScope ks(family == SAMPLER_WAVE ? "k_sample_wave_primed" : family == SAMPLER_WIDE ? "k_sample_wide_primed" : "k_sample_block_primed", s);
+    hipError_t e = family == SAMPLER_WAVE ? launch_sample_wave_primed(h->P, prime_dev, stride, PF, noise_dev, n, length, out_dev, pred_dev, s)
+                 : family == SAMPLER_WIDE ? launch_sample_wide_primed(h->P, prime_dev, stride, PF, noise_dev, n, length, out_dev, pred_dev, s)
+                                          : launch_sample_block_primed(h->P, prime_dev, stride, PF, noise_dev, n, length, out_dev, pred_dev, s);
+    if (e != hipSuccess) return fail_hip(h, e, "cmps_psi_sample_primed");
     return CMPS_OK;
 }
 

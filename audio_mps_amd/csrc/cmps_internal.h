@@ -389,6 +389,14 @@ hipError_t launch_finalize_legacy(const Dev& P, const float* loss, float* grad_o
 hipError_t launch_sample_wave(const Dev& P, const float* noise, int n, int length, float* out, hipStream_t s);
 hipError_t launch_sample_wide(const Dev& P, const float* noise, int n, int length, float* out, hipStream_t s);
 hipError_t launch_sample_block(const Dev& P, const float* noise, int n, int length, float* out, hipStream_t s);
+// cmps_psi_sample_primed: PF = prime_T - 1 teacher-forced steps on prime[path * prime_stride + k] (prime_stride 0: one shared clip), then
+// `length` sampled steps; pred [n][PF] may be null
+hipError_t launch_sample_wave_primed(const Dev& P, const float* prime, int prime_stride, int PF, const float* noise, int n, int length,
+                                     float* out, float* pred, hipStream_t s);
+hipError_t launch_sample_wide_primed(const Dev& P, const float* prime, int prime_stride, int PF, const float* noise, int n, int length,
+                                     float* out, float* pred, hipStream_t s);
+hipError_t launch_sample_block_primed(const Dev& P, const float* prime, int prime_stride, int PF, const float* noise, int n, int length,
+                                      float* out, float* pred, hipStream_t s);
 
 size_t apply_step_scratch_bytes(int D);
 hipError_t launch_apply_step(int D, bool apply, double inv_batch, double lr_t, double beta1, double beta2, double eps, double h_reg,

@@ -655,8 +655,17 @@ __device__ __forceinline__ void mv2r_hi(const v2f (&MA)[16], const v2f (&MB)[16]
 // inside the FMA blocks of step k (as in the forward scan, cmps_wave2.hip): with inv = rsqrt(max(|y_{k-1}|^2, 1e-12)),
 //   e = 2 inv^2 Re(ut^dagger R ut),   y_k = inv (ut + Q ut + s R ut),
 // and only the expectation's reduction is left on the serial chain.
-__global__ __launch_bounds__(64 * WAVES, 1) void k_sample_wave(Dev P, const float* __restrict__ noise, int n_paths,
-                                                               int length, float* __restrict__ out) {
+// PRIMED (cmps_psi_sample_primed): the scan runs over PF + length steps on table rows 0 .. PF + length - 1.  The first PF = prime_T - 1 steps
+// are teacher-forced -- the increment is the clip's difference prime[k + 1] - prime[k] (model.py:263) instead of e dt + noise, the
+// running sum stays 0, and e_k dt (the model's expected increment, model.py:286 without its noise) goes to pred[b][k] when asked for;
+// the `length` steps behind them are the sampler's own, with noise[b][k - PF] and out[b][k - PF].  The chunk load builds one "given"
+// value per lane (step): the prime difference below PF, the noise from PF on, so the step itself only adds a wave-uniform compare.
+// The unprimed instance (cmps_psi_sample) ignores its last four arguments and is the kernel as it was
+// (profiles/primed_sampler_isa_identity.log).
+template <bool PRIMED>
+__global__ __launch_bounds__(64 * WAVES, 1) void k_sample_wave(Dev P, const float* __restrict__ noise, int n_paths, int length,
+                                                               float* __restrict__ out, const float* __restrict__ prime,
+                                                               int prime_stride, int PF, float* __restrict__ pred) {
     __shared__ __attribute__((aligned(16))) float4 stR[WAVES][CH * 16];
     __shared__ __attribute__((aligned(16))) float2 bcU[WAVES][DPW];
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -664,7 +673,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_sample_wave(Dev P, const floa
     const bool hb = h != 0;
     const int b = blockIdx.x * WAVES + w;
     if (b >= n_paths) return;
-    const int N = length, NC = (N + CH - 1) / CH;
+    const int N = PRIMED ? PF + length : length, NC = (N + CH - 1) / CH;
     v2f MR[16], MQ[16];
 #pragma unroll
     for (int m = 0; m < 16; ++m) {
@@ -676,6 +685,8 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_sample_wave(Dev P, const floa
     const float4* rho4 = reinterpret_cast<const float4*>(P.rho);
     const float* nrow = noise + (size_t)b * length;
     float* orow = out + (size_t)b * length;
+    const float* prow = PRIMED ? prime + (size_t)b * prime_stride : nullptr;      // (prime_stride 0: one clip shared by all paths)
+    float* drow = PRIMED && pred ? pred + (size_t)b * PF : nullptr;
     const float A = dev_A(P), dt = P.dt;
     const float2 p0 = P.psi0[i];
     float u = hb ? p0.y : p0.x;
@@ -687,9 +698,15 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_sample_wave(Dev P, const floa
         const int kbeg = c * CH;
         const int cnt = (N - kbeg) < CH ? (N - kbeg) : CH;
         stage_load<16>(rho4, kbeg, P.N, lane, sr);
-        const float nz = kbeg + lane < N ? nrow[kbeg + lane] : 0.f;
+        float given;                                     // what this lane's step is handed: its noise, or (PRIMED, below PF) the clip's increment
+        if constexpr (PRIMED) {
+            const int k = kbeg + lane;
+            given = k < PF ? prow[k + 1] - prow[k] : k < N ? nrow[k - PF] : 0.f;
+        } else {
+            given = kbeg + lane < N ? nrow[kbeg + lane] : 0.f;
+        }
         stage_commit<16>(stR[w], lane, sr);
-        float svec = 0.f;
+        float svec = 0.f, pvec = 0.f;
         for (int kk = 0; kk < cnt; ++kk) {
             bcast_issue_tab(aUw, aUr, u, aRho + kk * 256, qu, rho);
             lds_wait_lo<5>(qu);
@@ -701,8 +718,17 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_sample_wave(Dev P, const floa
             const float vs = swap32_add(av.x, av.y), qs = swap32_add(aq.x, aq.y);
             const float inv = rsq_newton(fmaxf(nprev, 1e-12f));          // :289 of the step before
             const float e = 2.0f * (sum64(u * vs) * inv) * inv;      // _expectation on the normalised state (model.py:319-325)
-            const float inc = e * dt + rdlane(nz, kk);               // model.py:286
-            samp += inc;                                             // :287
+            float inc;
+            if constexpr (PRIMED) {
+                const bool forced = kbeg + kk < PF;                  // wave-uniform
+                const float edt = e * dt;
+                inc = forced ? rdlane(given, kk) : edt + rdlane(given, kk);
+                samp = forced ? 0.f : samp + inc;
+                pvec = (lane == kk) ? edt : pvec;
+            } else {
+                inc = e * dt + rdlane(given, kk);                      // model.py:286
+                samp += inc;                                         // :287
+            }
             svec = (lane == kk) ? samp : svec;
             const float s = inc / A;                                 // :288 -> :303
             const float y = inv * (u + (qs + s * vs));
@@ -711,13 +737,28 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_sample_wave(Dev P, const floa
             u = un.x;
             xsq = y * y;
         }
-        if (lane < cnt) orow[kbeg + lane] = A * svec;                // model.py:251
+        if constexpr (PRIMED) {
+            const int k = kbeg + lane;                               // table index; out is shifted by PF, pred is not
+            if (lane < cnt) {
+                if (k >= PF) orow[k - PF] = A * svec;
+                else if (drow) drow[k] = pvec;
+            }
+        } else {
+            if (lane < cnt) orow[kbeg + lane] = A * svec;            // model.py:251
+        }
     }
 }
 
 hipError_t launch_sample_wave(const Dev& P, const float* noise, int n, int length, float* out, hipStream_t s) {
     const unsigned nb = (unsigned)((n + WAVES - 1) / WAVES);
-    hipLaunchKernelGGL(k_sample_wave, dim3(nb), dim3(64 * WAVES), 0, s, P, noise, n, length, out);
+    hipLaunchKernelGGL(k_sample_wave<false>, dim3(nb), dim3(64 * WAVES), 0, s, P, noise, n, length, out, (const float*)nullptr, 0, 0, (float*)nullptr);
+    return hipGetLastError();
+}
+
+hipError_t launch_sample_wave_primed(const Dev& P, const float* prime, int prime_stride, int PF, const float* noise, int n, int length,
+                                     float* out, float* pred, hipStream_t s) {
+    const unsigned nb = (unsigned)((n + WAVES - 1) / WAVES);
+    hipLaunchKernelGGL(k_sample_wave<true>, dim3(nb), dim3(64 * WAVES), 0, s, P, noise, n, length, out, prime, prime_stride, PF, pred);
     return hipGetLastError();
 }
 

@@ -543,9 +543,16 @@ __global__ void k_rho_phi_reduce(const float* __restrict__ gphi, int B, int vran
 // R ut and Q ut stay separate (the increment that scales R ut depends on <R>), and the expectation needs one more exchange across
 // the waves: two LDS-only barriers per step instead of one.
 // ------------------------------------------------------------------------------------------------------------------------
-template <int PD>
+// PRIMED (cmps_psi_sample_primed): PF = prime_T - 1 teacher-forced steps in front of the `length` sampled ones, one scan over table rows
+// 0 .. PF + length - 1.  A forced step takes its increment from the clip (prime[k + 1] - prime[k], model.py:263), leaves the running sum
+// at 0 and, when asked, stores e_k dt to pred[path][k]; a sampled step k reads noise[path][k - PF] and writes out[path][k - PF].  The
+// per-lane "given" value of a 64-step chunk is built at chunk load (the difference below PF, the noise from PF on), so a step only adds
+// the uniform compare k < PF.  The unprimed instance (cmps_psi_sample) ignores its last four arguments and is the kernel as it was
+// (profiles/primed_sampler_isa_identity.log).
+template <int PD, bool PRIMED>
 __global__ __launch_bounds__(4 * PD) void k_sample_wide(Dev P, const float* __restrict__ noise, int n_paths, int length,
-                                                        float* __restrict__ out) {
+                                                        float* __restrict__ out, const float* __restrict__ prime, int prime_stride,
+                                                        int PF, float* __restrict__ pred) {
     using G = WideGeom<PD>;
     constexpr int NW = G::NW, KC = G::KC, VSL = G::VSL, VEC4 = G::VEC4;
     __shared__ __attribute__((aligned(16))) v4f uvec[2 * VEC4];
@@ -561,6 +568,10 @@ __global__ __launch_bounds__(4 * PD) void k_sample_wide(Dev P, const float* __re
     const float* nr0 = noise + (size_t)b0 * length;
     const float* nr1 = noise + (size_t)b1 * length;
     float* orow = out + (size_t)(clip1 ? b1 : b0) * length;
+    const float* pr0 = PRIMED ? prime + (size_t)b0 * prime_stride : nullptr;   // (prime_stride 0: one clip shared by all paths)
+    const float* pr1 = PRIMED ? prime + (size_t)b1 * prime_stride : nullptr;
+    float* drow = PRIMED && pred ? pred + (size_t)(clip1 ? b1 : b0) * PF : nullptr;
+    const int nsteps = PRIMED ? PF + length : length;
     const bool writer = w == 0 && i == 0 && q < 2 && (!clip1 || two);
     const float A = dev_A(P), dt = P.dt;
 
@@ -580,17 +591,22 @@ __global__ __launch_bounds__(4 * PD) void k_sample_wide(Dev P, const float* __re
     const float2 p0 = P.psi0[row];
     float ut = im_lane ? p0.y : p0.x;
     reinterpret_cast<float*>(uvec)[own_f] = ut;
-    float nz0 = 0.f, nz1 = 0.f;                                   // noise of the current 64 steps, lane <-> step
+    float gv0 = 0.f, gv1 = 0.f;                                   // what the current 64 steps are handed, lane <-> step: noise (PRIMED, below PF: the clip's increments)
     float samp = 0.f;                                             // model.py:244 batch_zeros (this lane's path)
     float2 rho_next = P.rho[row];
     __syncthreads();
 
-    for (int k = 0; k < length; ++k) {
+    for (int k = 0; k < nsteps; ++k) {
         const int p = k & 1, kl = k & (WCH - 1);
         if (kl == 0) {
             const int idx = k + lane;
-            nz0 = idx < length ? nr0[idx] : 0.f;
-            nz1 = idx < length ? nr1[idx] : 0.f;
+            if constexpr (PRIMED) {
+                gv0 = idx < PF ? pr0[idx + 1] - pr0[idx] : idx < nsteps ? nr0[idx - PF] : 0.f;
+                gv1 = idx < PF ? pr1[idx + 1] - pr1[idx] : idx < nsteps ? nr1[idx - PF] : 0.f;
+            } else {
+                gv0 = idx < length ? nr0[idx] : 0.f;
+                gv1 = idx < length ? nr1[idx] : 0.f;
+            }
         }
         const float2 rho_k = rho_next;
         if (k + 1 < P.N) rho_next = P.rho[(size_t)(k + 1) * PD + row];
@@ -624,8 +640,16 @@ __global__ __launch_bounds__(4 * PD) void k_sample_wide(Dev P, const float* __re
             e0 += t.x; e1 += t.y;
         }
         const float e = 2.0f * ((clip1 ? e1 : e0) * inv) * inv;   // _expectation on the normalised state (model.py:319-325)
-        const float inc = e * dt + (clip1 ? rdlane(nz1, kl) : rdlane(nz0, kl));   // model.py:286
-        samp += inc;                                              // :287
+        float inc;
+        const bool forced = PRIMED && k < PF;                     // uniform
+        if constexpr (PRIMED) {
+            const float given = clip1 ? rdlane(gv1, kl) : rdlane(gv0, kl);
+            inc = forced ? given : e * dt + given;
+            samp = forced ? 0.f : samp + inc;
+        } else {
+            inc = e * dt + (clip1 ? rdlane(gv1, kl) : rdlane(gv0, kl));   // model.py:286
+            samp += inc;                                          // :287
+        }
         const float s = inc / A;                                  // :288 -> :303
         const float y = inv * (ut + (qs + s * vs));
         const float nn = clip_wave_sum(y * y);
@@ -633,7 +657,14 @@ __global__ __launch_bounds__(4 * PD) void k_sample_wide(Dev P, const float* __re
         const float py = partner16(y, im_lane);
         ut = rho_k.x * y + (im_lane ? rho_k.y : -rho_k.y) * py;   // rho_k y_k, normalised in the next step
         reinterpret_cast<float*>(uvec + (p ^ 1) * VEC4)[own_f] = ut;
-        if (writer) orow[k] = A * samp;                           // model.py:251
+        if constexpr (PRIMED) {
+            if (writer) {                                         // table index k; out is shifted by PF, pred is not
+                if (!forced) orow[k - PF] = A * samp;
+                else if (drow) drow[k] = e * dt;
+            }
+        } else {
+            if (writer) orow[k] = A * samp;                       // model.py:251
+        }
         wide_barrier();
     }
 }
@@ -1299,7 +1330,17 @@ hipError_t launch_sample_wide(const Dev& P, const float* noise, int n, int lengt
     const unsigned nb = (unsigned)((n + 1) / 2);
     return dispatch_pd(P.DP, [&](auto pd) {
         constexpr int PD = decltype(pd)::value;
-        hipLaunchKernelGGL(k_sample_wide<PD>, dim3(nb), dim3(4 * PD), 0, s, P, noise, n, length, out);
+        hipLaunchKernelGGL((k_sample_wide<PD, false>), dim3(nb), dim3(4 * PD), 0, s, P, noise, n, length, out, (const float*)nullptr, 0, 0, (float*)nullptr);
+        return hipGetLastError();
+    });
+}
+
+hipError_t launch_sample_wide_primed(const Dev& P, const float* prime, int prime_stride, int PF, const float* noise, int n, int length,
+                                     float* out, float* pred, hipStream_t s) {
+    const unsigned nb = (unsigned)((n + 1) / 2);
+    return dispatch_pd(P.DP, [&](auto pd) {
+        constexpr int PD = decltype(pd)::value;
+        hipLaunchKernelGGL((k_sample_wide<PD, true>), dim3(nb), dim3(4 * PD), 0, s, P, noise, n, length, out, prime, prime_stride, PF, pred);
         return hipGetLastError();
     });
 }

@@ -362,12 +362,58 @@ class PsiCMPS(CMPS):
         be.forward(audio, save_for_bwd=True)
         return be.states()
 
-    def sample(self, num_samples, length, temp=1, seed=None, noise=None):
+    def sample(self, num_samples, length, temp=1, seed=None, noise=None, prime=None, return_pred=False):
         """model.py:242-251: waveforms [num_samples, length] = A * running sum of the sampled increments.
         The Gaussian noise (stddev sigma * sqrt(temp * delta_t), model.py:246) is drawn on the host with a numpy
-        Generator (``seed``), or passed in as ``noise`` [length, num_samples] like the reference's tensor."""
+        Generator (``seed``), or passed in as ``noise`` [length, num_samples] like the reference's tensor.
+
+        ``prime`` (no reference counterpart): a clip [T'], [1, T'] (shared by all paths) or [num_samples, T'] the state is first
+        teacher-forced on -- T' - 1 steps of _psi_update (model.py:269-274) on its increments -- before the ``length`` sampled
+        steps follow in the same scan (cmps_psi_sample_primed).  The return value keeps the reference's convention: A * running
+        sum of the SAMPLED increments, zero at the hand-over (``continue_clip`` returns the clip's own units).  ``return_pred``
+        adds the model's expected increment of every forced step, [num_samples, T' - 1]."""
         noise = self._noise(num_samples, length, temp, seed, noise)
-        return self._prepare(num_samples, length + 1, train=False).sample(noise)
+        if prime is None:
+            if return_pred:
+                raise ValueError("return_pred needs a prime: the predictions belong to the teacher-forced steps")
+            return self._prepare(num_samples, length + 1, train=False).sample(noise)
+        prime = self._prime(prime, num_samples)
+        be = self._prepare(num_samples, prime.shape[1] + length, train=False)    # one table row per step, forced or sampled
+        return be.sample_primed(prime, noise, want_pred=bool(return_pred))
+
+    @staticmethod
+    def _prime(prime, num_samples) -> np.ndarray:
+        """A prime as the backend takes it: float32 [1, T'] (shared by every path) or [num_samples, T'], T' >= 2."""
+        if hasattr(prime, "detach"):
+            prime = prime.detach().cpu().numpy()
+        prime = np.asarray(prime, dtype=np.float32)
+        if prime.ndim == 1:
+            prime = prime[None, :]
+        if prime.ndim != 2 or prime.shape[0] not in (1, num_samples):
+            raise ValueError(f"prime must be [T'], [1, T'] or [{num_samples}, T'], not {prime.shape}")
+        if prime.shape[1] < 2:
+            raise ValueError("prime needs two samples at least (one increment)")
+        return np.ascontiguousarray(prime)
+
+    def continue_clip(self, prime, num_samples, length, temp=1, seed=None, noise=None) -> np.ndarray:
+        """The continuation of ``prime`` in the clip's own units, [num_samples, length]: the array to plot or write behind the clip.
+        The model's waveform is A * (running sum of increments) and the data enter as increments / A (model.py:303), so the
+        sampled sum is divided by A and starts from the clip's last sample."""
+        prime = self._prime(prime, num_samples)
+        out = self.sample(num_samples, length, temp=temp, seed=seed, noise=noise, prime=prime)
+        return (prime[..., -1:] + out / self.A).astype(np.float32)
+
+    def predict_increments(self, data=None) -> np.ndarray:
+        """Teacher-forced one-step predictions [B, T - 1] for a batch [B, T] (default: the model's data_iterator): entry k is the
+        model's expected increment 2 Re<psi|R|psi> delta_t at t_k, given the clip up to sample k -- to compare with
+        data[:, k + 1] - data[:, k].  Runs the primed sampler with one sampled step and discards it."""
+        data = self._batch(data)
+        if data is None:
+            raise ValueError("predict_increments needs a batch (data, or the model's data_iterator)")
+        B = int(np.shape(data)[0])
+        prime = self._prime(data, B)
+        be = self._prepare(B, prime.shape[1] + 1, train=False)
+        return be.sample_primed(prime, np.zeros((1, B), dtype=np.float32), want_pred=True)[1]
 
 
 # --------------------------------------------------------------------------------------------------

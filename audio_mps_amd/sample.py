@@ -1,0 +1,125 @@
+"""Sampler for a trained model: the reference's sample.py, which declares its flags (sample.py:10-14) and leaves ``main`` empty.
+
+  flags              sample.py:10-14     --sample_duration, --sample_rate, --modeldir (same names, same defaults)
+  model              train.py:49-53      PsiCMPS(hparams), its variables read from the checkpoint Trainer.save writes
+  waveform           model.py:242-251    model.sample(num_samples, sample_duration, temp) / A, in the data's units
+
+``--prime FILE`` (a 16-bit mono .wav, or a .npy array [T'], [1, T'] or [num_samples, T']) continues a clip instead: the state is
+teacher-forced on the clip and the sampler carries on from there (PsiCMPS.continue_clip, cmps_psi_sample_primed); the written
+waveform is the clip followed by its continuation.  Writes ``sample_<i>.wav`` (16-bit PCM mono at --sample_rate, clipped to
+[-1, 1)) and ``samples.npy`` (float32 [num_samples, samples], unclipped) into --out_dir.
+Run:  python -m audio_mps_amd.sample --modeldir=LOGDIR --sample_duration=16000 --prime=clip.wav
+"""
+from __future__ import annotations
+
+import argparse
+import math
+import os
+import wave
+
+import numpy as np
+
+from .model import HParams, PsiCMPS
+
+CKPT_NAME = "model.ckpt.npz"          # what train.main saves into its logdir
+
+
+def read_wav(path: str):
+    """(float32 samples in [-1, 1), sample rate) of a 16-bit mono PCM file: int16 / 32768.  Anything else is an error."""
+    with wave.open(path, "rb") as w:
+        ch, width, rate, frames, comp = w.getnchannels(), w.getsampwidth(), w.getframerate(), w.getnframes(), w.getcomptype()
+        if ch != 1 or width != 2 or comp != "NONE":
+            raise ValueError(f"{path}: need 16-bit mono PCM, found {ch} channel(s), {8 * width}-bit samples, compression {comp}")
+        raw = w.readframes(frames)
+    return (np.frombuffer(raw, dtype="<i2").astype(np.float32) / np.float32(32768)), rate
+
+
+def write_wav(path: str, x, rate: int):
+    """16-bit mono PCM at ``rate``: round(x * 32768) clipped to the int16 range, i.e. x clipped to [-1, 1)."""
+    x = np.asarray(x, dtype=np.float64).reshape(-1)
+    pcm = np.clip(np.rint(x * 32768.0), -32768, 32767).astype("<i2")
+    with wave.open(path, "wb") as w:
+        w.setnchannels(1)
+        w.setsampwidth(2)
+        w.setframerate(int(rate))
+        w.writeframes(pcm.tobytes())
+
+
+def load_prime(path: str, sample_rate: int) -> np.ndarray:
+    """The clip to continue: .npy (float array [T'], [1, T'] or [n, T'], the data's units) or .wav (16-bit mono at --sample_rate)."""
+    if path.lower().endswith(".npy"):
+        return np.asarray(np.load(path), dtype=np.float32)
+    if path.lower().endswith(".wav"):
+        x, rate = read_wav(path)
+        if rate != sample_rate:
+            raise ValueError(f"{path}: sampled at {rate} Hz, the model runs at --sample_rate {sample_rate} Hz")
+        return x
+    raise ValueError(f"--prime {path}: need a .wav or .npy file")
+
+
+def load_variables(modeldir: str) -> dict:
+    """The ``model/*`` entries of a checkpoint written by Trainer.save; ``modeldir`` is the directory holding it, or the file."""
+    path = os.path.join(modeldir, CKPT_NAME) if os.path.isdir(modeldir) else modeldir
+    if not os.path.exists(path):
+        raise FileNotFoundError(f"no checkpoint at {path} (--modeldir: a directory holding {CKPT_NAME}, or the file itself)")
+    with np.load(path) as z:
+        out = {k[len("model/"):]: np.asarray(z[k], dtype=np.float32) for k in z.files if k.startswith("model/")}
+    if not out:
+        raise ValueError(f"{path} holds no model/* variables")
+    return out
+
+
+def build_parser():
+    p = argparse.ArgumentParser(description="Sample from a trained PsiCMPS on MI355X, or continue a clip (audio-mps sample.py, filled in)")
+    p.add_argument("--sample_duration", type=int, default=2 ** 16, help="samples to generate (as integer)")      # sample.py:10
+    p.add_argument("--sample_rate", type=int, default=16000)                                                      # sample.py:11
+    p.add_argument("--modeldir", default="./data", help=f"directory holding {CKPT_NAME}, or the checkpoint file")  # sample.py:14
+    p.add_argument("--hparams", default="", help="as for training (r_reg, h_reg, sigma, delta_t must be the training run's; "
+                   "bond_dim is read from the checkpoint)")
+    p.add_argument("--num_samples", type=int, default=1)
+    p.add_argument("--temp", type=float, default=1.0, help="noise temperature (model.py:246)")
+    p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--prime", default=None, metavar="FILE", help=".wav (16-bit mono) or .npy clip to continue")
+    p.add_argument("--out_dir", default="./samples")
+    p.add_argument("--kernel_variant", type=int, default=0, help="as in audio_mps_amd.train")
+    return p
+
+
+def main(argv=None, backend=None):
+    """Returns the waveforms [num_samples, samples] it wrote.  ``backend``: a scan backend to use instead of HipScan (CPU tests of the
+    host logic inject one; the product always builds a HipScan and fails loudly without a GPU)."""
+    args = build_parser().parse_args(argv)
+    if args.sample_duration < 1 or args.num_samples < 1:
+        raise ValueError("--sample_duration and --num_samples must be positive")
+    variables = load_variables(args.modeldir)
+    if "Wx" in variables or "psi_x" not in variables:
+        raise ValueError("the checkpoint is not a PsiCMPS one (rho_mps checkpoints cannot be primed or sampled here)")
+    hp = HParams(delta_t=1.0 / args.sample_rate, h_reg=200.0 / (math.pi * args.sample_rate) ** 2)       # train.py:41-43
+    hp.bond_dim = int(variables["psi_x"].shape[0])
+    hp.parse(args.hparams)
+    if backend is None:
+        from .scan import HipScan
+        backend = HipScan(hp.bond_dim, variant=args.kernel_variant)
+    model = PsiCMPS(hp, seed=args.seed, backend=backend)
+    for k in model.variables:
+        if variables[k].shape != model.variables[k].shape:
+            raise ValueError(f"checkpoint variable {k} has shape {variables[k].shape}, bond_dim={hp.bond_dim} needs {model.variables[k].shape}")
+        model.variables[k] = variables[k]
+    n, length = args.num_samples, args.sample_duration
+    if args.prime is None:
+        waves = model.sample(n, length, temp=args.temp, seed=args.seed) / model.A
+    else:
+        prime = PsiCMPS._prime(load_prime(args.prime, args.sample_rate), n)
+        cont = model.continue_clip(prime, n, length, temp=args.temp, seed=args.seed)
+        waves = np.concatenate([np.broadcast_to(prime, (n, prime.shape[1])), cont], axis=1)
+    waves = np.ascontiguousarray(waves, dtype=np.float32)
+    os.makedirs(args.out_dir, exist_ok=True)
+    np.save(os.path.join(args.out_dir, "samples.npy"), waves)
+    for i in range(n):
+        write_wav(os.path.join(args.out_dir, f"sample_{i}.wav"), waves[i], args.sample_rate)
+    print(f"wrote {n} waveform(s) of {waves.shape[1]} samples to {args.out_dir}")
+    return waves
+
+
+if __name__ == "__main__":
+    main()

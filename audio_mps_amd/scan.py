@@ -116,8 +116,8 @@ class HipScan:
         return mode if mode in (_capi.CMPS_RANK1_EXACT_F32, _capi.CMPS_RANK1_BF16X2, _capi.CMPS_RANK1_F16X2) else _capi.CMPS_RANK1_BF16X3
 
     def kernel_events(self, on: bool):
-        """cmps_set_option(CMPS_OPT_KERNEL_EVENTS): bracket every kernel of forward() / backward() with HIP events (a measurement aid,
-        used by bench.py outside its timed region)."""
+        """cmps_set_option(CMPS_OPT_KERNEL_EVENTS): bracket every kernel of forward() / backward() and of sample() / sample_primed() with HIP
+        events (a measurement aid, used by bench.py outside its timed region)."""
         _capi.check(self._h, self._lib.cmps_set_option(self._h, _capi.CMPS_OPT_KERNEL_EVENTS, 1 if on else 0))
 
     def kernel_times(self) -> dict:
@@ -354,6 +354,26 @@ class HipScan:
     def sample(self, noise: np.ndarray) -> np.ndarray:
         """PsiCMPS.sample for pre-drawn noise [length, n] (the reference's layout) -> waveforms [n, length]."""
         return self._sample(self._lib.cmps_psi_sample, noise)
+
+    def sample_primed(self, prime: np.ndarray, noise: np.ndarray, want_pred: bool = False):
+        """cmps_psi_sample_primed: teacher-force the clips ``prime`` [n_prime, prime_T] (n_prime = n, or 1 for one clip shared by every
+        path), then sample ``length`` steps with the pre-drawn ``noise`` [length, n] (the reference's layout, as `sample` takes it).
+        Returns out [n, length] = A * running sum of the sampled increments (zero at the hand-over), or (out, pred [n, prime_T - 1])
+        with want_pred: the model's expected increment of every forced step.  After set_params with T >= prime_T + length."""
+        prime = np.array(prime, dtype=np.float32, order="C")          # (a copy: torch wants a writable array)
+        noise = np.asarray(noise, dtype=np.float32)
+        if prime.ndim != 2 or noise.ndim != 2:
+            raise ValueError("prime must be [n_prime, prime_T] and noise [length, n]")
+        (n_prime, prime_T), (length, n) = prime.shape, noise.shape
+        d_prime = torch.from_numpy(prime).to(self.device)
+        d_noise = torch.from_numpy(np.array(noise.T, order="C")).to(self.device)
+        d_out = torch.empty((n, length), dtype=torch.float32, device=self.device)
+        d_pred = torch.empty((n, max(prime_T - 1, 0)), dtype=torch.float32, device=self.device) if want_pred else None
+        _capi.check(self._h, self._lib.cmps_psi_sample_primed(
+            self._h, d_prime.data_ptr(), n_prime, prime_T, d_noise.data_ptr(), n, length, d_out.data_ptr(),
+            d_pred.data_ptr() if want_pred else None, self._stream()))
+        out = d_out.cpu().numpy()
+        return (out, d_pred.cpu().numpy()) if want_pred else out
 
     # ------------------------------------------------------------------
     # legacy AudioMPS arithmetic (SURVEY 8f rank 2)

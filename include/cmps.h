@@ -84,7 +84,7 @@ enum {
     CMPS_OPT_F16_SCALE_SHIFT = 4 /* DIAGNOSTIC, default 0: added to the exponent of every data-dependent fp16 scale of the wave reverse
                         * scan's F16X2 arithmetic (range -40 .. 40).  A positive value pushes the pieces out of fp16 range on purpose:
                         * how tests/test_gpu_parity.py provokes CMPS_ERR_F16_RANGE.  No reference counterpart. */,
-    CMPS_OPT_KERNEL_EVENTS = 2 /* 1: every kernel cmps_psi_loss_fwd / _bwd launch is bracketed by two HIP events on the caller's stream
+    CMPS_OPT_KERNEL_EVENTS = 2 /* 1: every kernel cmps_psi_loss_fwd / _bwd, cmps_psi_sample and cmps_psi_sample_primed launch is bracketed by two HIP events on the caller's stream
                         * (read and reset with cmps_kernel_times); 0 (default): nothing is recorded.  A measurement aid -- the reference
                         * has no counterpart (no tracing / profiling hooks); bench.py uses it OUTSIDE its timed region to price
                         * each kernel of a multi-kernel family against the pipe it runs on */
@@ -271,6 +271,29 @@ int cmps_psi_states(cmps_handle_t h, int B, int T, float* psi_out_dev, void* str
  * Needs cmps_set_params with T >= length + 1 (the per-step time/phase tables); any workspace flags.
  */
 int cmps_psi_sample(cmps_handle_t h, const float* noise_dev, int n, int length, float* out_dev, void* stream);
+
+/*
+ * PsiCMPS.sample (model.py:242-251) continued from a clip: P = prime_T - 1 teacher-forced steps of _psi_update
+ * (model.py:269-274) on the increments of prime_dev, then `length` steps of _psi_and_sample_update (:284-291).
+ * The reference has no such method (its sample.py is an empty stub); both halves are its own steps, run as ONE scan over the
+ * steps k = 0 .. P + length - 1 on table row k, so the time grid t_k and the rotating frame run through the hand-over unbroken.
+ *   forced step, k < P:   increment = prime[b'][k + 1] - prime[b'][k] in float32 (the subtraction of model.py:263), b' = b, or 0 when
+ *                         one clip is shared;  the running sum stays 0;  pred[b][k] = 2 Re<psi|R|psi> * delta_t on the normalised
+ *                         state at t_k, BEFORE the step sees the data: the model's expected increment, the expression the sampler
+ *                         adds its noise to at model.py:286.
+ *   sampled step, k >= P: exactly the step of cmps_psi_sample with noise[b][k - P];  out[b][k - P] = A * (running sum of the
+ *                         sampled increments, starting from zero at k = P).
+ * So out_dev is what cmps_psi_sample would return had it started from the primed state at t_P; in the clip's own units the
+ * continuation is prime[b'][prime_T - 1] + out[b][:] / A.
+ * prime_dev [n_prime * prime_T] row-major clips, n_prime == n, or n_prime == 1 for one clip shared by every path; prime_T >= 2.
+ * noise_dev [n * length], out_dev [n * length] as in cmps_psi_sample; pred_dev [n * (prime_T - 1)] row-major [path][step], or NULL.
+ * Needs cmps_set_params* with T >= prime_T + length (one row of the per-step tables per step, forced or sampled), otherwise
+ * CMPS_ERR_BAD_ARG with a message naming the needed T; null pointers, n < 1, length < 1, prime_T < 2 and n_prime not in {1, n} are
+ * CMPS_ERR_BAD_ARG; before cmps_set_params and in legacy mode CMPS_ERR_STATE.  The kernel is chosen exactly as in cmps_psi_sample.
+ */
+int cmps_psi_sample_primed(cmps_handle_t h, const float* prime_dev, int n_prime, int prime_T,
+                           const float* noise_dev, int n, int length,
+                           float* out_dev, float* pred_dev, void* stream);
 
 /*
  * Legacy `AudioMPS` arithmetic (the model training_estimators.py:43-45 was written for; its class body is gone from

@@ -1,14 +1,18 @@
 #!/usr/bin/env python3
 """Device code of every kernel translation unit, one source tree against another: normalised gfx950 assembly, line count and SHA-256.
 
-usage: python scripts/isa_identity.py PARENT [CHANGE] [--jobs N] [--keep DIR]
+usage: python scripts/isa_identity.py PARENT [CHANGE] [--jobs N] [--keep DIR] [--kernels REGEX]
 
 PARENT and CHANGE are checkouts of this repository (CHANGE defaults to the tree this script is in); a PARENT that is no directory
 is taken as a git revision of this repository and exported to a temporary directory.  Every source of build.py::SOURCES except
 cmps_capi.hip (host code only) is compiled device-only with build.py's flags, its EXTRA_FLAGS included, and the two sources with
 diagnostic blocks once more under their diagnostic flag sets.  The only normalisation is the __hip_cuid_<hash> symbol, which is
 a hash of the source path.  Whole files are hashed and compared; a refactor that moves force-inlined device code, or rewrites host
-code only, expects every row "identical".  Needs hipcc, no GPU.  --keep DIR leaves the .s files in DIR/parent and DIR/change."""
+code only, expects every row "identical".  Needs hipcc, no GPU.  --keep DIR leaves the .s files in DIR/parent and DIR/change.
+--kernels REGEX adds one row per kernel whose (mangled) symbol matches, in the translation units that differ: the kernel's body
+(its label to its end label) and its .amdhsa_kernel descriptor block, compared as text with the kernel's own symbol and the
+function index of its labels normalised -- for a change that adds kernels or instances to a file and must leave the existing ones
+alone.  Kernels are paired by demangled name, template arguments `false` dropped."""
 import argparse
 import hashlib
 import importlib.util
@@ -54,7 +58,35 @@ def assemble(tree, src, extra, keep, label):
         os.makedirs(keep, exist_ok=True)
         with open(os.path.join(keep, label.replace(" [diag]", ".diag") + ".s"), "w") as f:
             f.write(text)
-    return text.count("\n"), hashlib.sha256(text.encode()).hexdigest()
+    return text.count("\n"), hashlib.sha256(text.encode()).hexdigest(), text
+
+
+def kernel_key(sym):
+    """What identifies a kernel across the two trees: its demangled name without return type and arguments, and without template
+    arguments `false` (a kernel that gained a bool template parameter keeps its key in the instance that passes false)."""
+    import shutil
+    filt = shutil.which("c++filt") or shutil.which("llvm-cxxfilt")
+    if not filt:
+        raise RuntimeError("--kernels needs c++filt (or llvm-cxxfilt) to pair the kernels of the two trees")
+    name = subprocess.run([filt, sym], stdout=subprocess.PIPE, text=True, check=True).stdout.strip()
+    name = re.sub(r"^void ", "", name.split("(")[0]).replace(" ", "")
+    args = [x for x in re.sub(r"^[^<]*<?|>$", "", name).split(",") if x and x != "false"] if "<" in name else []
+    return name.split("<")[0] + ("<" + ",".join(args) + ">" if args else "")
+
+
+def kernels_of(text, pattern):
+    """{key: (symbol, body + descriptor block)} of the kernels of an assembly file whose symbol matches `pattern`, the kernel's own
+    symbol replaced by a placeholder"""
+    out = {}
+    for sym in re.findall(r"^\s*\.amdhsa_kernel\s+(\S+)", text, flags=re.M):
+        if not re.search(pattern, sym):
+            continue
+        body = re.search(r"^%s:.*?^\.Lfunc_end\d+:" % re.escape(sym), text, flags=re.M | re.S)
+        desc = re.search(r"^\s*\.amdhsa_kernel\s+%s\n.*?\.end_amdhsa_kernel" % re.escape(sym), text, flags=re.M | re.S)
+        both = (body.group(0) if body else "") + "\n" + (desc.group(0) if desc else "")
+        both = re.sub(r"(BB|func_end)\d+", r"\1N", both.replace(sym, "KERNEL"))      # (labels carry the function's index in its file)
+        out[kernel_key(sym)] = (sym, both)
+    return out
 
 
 def main():
@@ -63,6 +95,7 @@ def main():
     ap.add_argument("change", nargs="?", default=ROOT)
     ap.add_argument("--jobs", type=int, default=min(8, os.cpu_count() or 2))
     ap.add_argument("--keep")
+    ap.add_argument("--kernels", help="regular expression on kernel symbols: compare these kernels one by one in the files that differ")
     a = ap.parse_args()
     with tempfile.TemporaryDirectory() as tmp:
         parent = a.parent
@@ -81,9 +114,36 @@ def main():
         if isinstance(p, str) or isinstance(c, str):
             print(f"{lab:28s} parent: {p if isinstance(p, str) else 'ok'}; change: {c if isinstance(c, str) else 'ok'}")
             continue
-        same += p == c
-        print(f"{lab:28s} {p[0]:8d} {c[0]:8d}  {p[1]}  {c[1]}  {'identical' if p == c else 'DIFFERENT'}")
+        same += p[:2] == c[:2]
+        print(f"{lab:28s} {p[0]:8d} {c[0]:8d}  {p[1]}  {c[1]}  {'identical' if p[:2] == c[:2] else 'DIFFERENT'}")
     print(f"\n{same} of {len(todo)} identical ({len(todo) - len(DIAG)} translation units, {len(DIAG)} diagnostic flag sets)")
+    if a.kernels:
+        ksame = ktotal = 0
+        print(f"\nkernels matching /{a.kernels}/ in the translation units that differ")
+        print(f"{'translation unit':20s} {'lines(P)':>8s} {'lines(C)':>8s}  {'verdict':22s} kernel")
+        for (lab, _, _), p, c in zip(todo, rp, rc):
+            if isinstance(p, str) or isinstance(c, str) or p[:2] == c[:2]:
+                continue
+            kp, kc = kernels_of(p[2], a.kernels), kernels_of(c[2], a.kernels)
+            for key in sorted(set(kp) | set(kc)):
+                tp, tc = kp.get(key, (None, None))[1], kc.get(key, (None, None))[1]
+                verdict = "only in change" if tp is None else "only in parent" if tc is None else "identical" if tp == tc else "DIFFERENT"
+                extra = []
+                if verdict == "DIFFERENT":
+                    # every instruction the same and only directives apart (the kernel-argument segment grew, or the kernel became a
+                    # template instance and moved to its own section): say so, and which
+                    lp, lc = tp.split("\n"), tc.split("\n")
+                    if len(lp) == len(lc):
+                        extra = [(x.strip(), y.strip()) for x, y in zip(lp, lc) if x != y]
+                        if all(re.match(r"\.(amdhsa_kernarg_size|text|section)\b", x) and re.match(r"\.(amdhsa_kernarg_size|text|section)\b", y) for x, y in extra):
+                            verdict = "same instructions"
+                ktotal += tp is not None
+                ksame += verdict in ("identical", "same instructions")
+                print(f"{lab:20s} {tp.count(chr(10)) if tp else 0:8d} {tc.count(chr(10)) if tc else 0:8d}  {verdict:22s} {key}")
+                for x, y in sorted(set(extra)) if verdict == "same instructions" else []:
+                    print(f"{'':40s}    directive: {x}  ->  {y}")
+        print(f"\n{ksame} of {ktotal} kernels of the parent with identical instructions")
+        return 0 if ksame == ktotal else 1
     return 0 if same == len(todo) else 1
 
 
