@@ -185,7 +185,7 @@ hipError_t reduce_pairs_finalize(Dev P, int abar_fix, const float* loss, float* 
 
 extern "C" {
 
-int cmps_version(void) { return 400; }
+int cmps_version(void) { return 500; }
 
 int cmps_create(int D, cmps_handle_t* out) {
     if (!out) return CMPS_ERR_BAD_ARG;
@@ -359,6 +359,30 @@ int cmps_psi_apply_step(cmps_handle_t h, float* vars_dev, float* adam_m_dev, flo
                                            c_h, with_reg != 0, vars_dev, adam_m_dev, adam_v_dev, grad_sums_dev, params_dev, losses_dev,
                                            static_cast<double*>(scratch_dev), static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return fail_hip(h, e, "cmps_psi_apply_step");
+    return CMPS_OK;
+}
+
+size_t cmps_rho_apply_step_scratch_bytes(int D, int rank) {
+    return (D < 1 || D > 128 || rank < 1 || rank > 128) ? 0 : rho_apply_step_scratch_bytes(D, rank);
+}
+
+int cmps_rho_apply_step(cmps_handle_t h, float* vars_dev, float* adam_m_dev, float* adam_v_dev, const float* grad_sums_dev,
+                        int rank, double global_batch, double lr_t, double beta1, double beta2, double epsilon, double h_reg,
+                        double r_reg, double c_r, double c_h, int with_reg, float* params_dev, float* phi_dev, float* losses_dev,
+                        void* scratch_dev, void* stream) {
+    if (!h) return CMPS_ERR_BAD_ARG;
+    if (!vars_dev || !params_dev || !phi_dev)
+        return fail(h, CMPS_ERR_BAD_ARG, "cmps_rho_apply_step: null variable / parameter / column buffer");
+    if (rank < 1 || rank > 128) return fail(h, CMPS_ERR_BAD_ARG, "cmps_rho_apply_step: rank outside [1, 128]");
+    const bool apply = grad_sums_dev != nullptr;
+    if (apply && (!adam_m_dev || !adam_v_dev || !losses_dev || !scratch_dev || !(global_batch > 0.0)))
+        return fail(h, CMPS_ERR_BAD_ARG, "cmps_rho_apply_step: an update needs the Adam slots, losses_dev, scratch_dev and a positive batch");
+    if (((uintptr_t)scratch_dev & 7) != 0) return fail(h, CMPS_ERR_BAD_ARG, "cmps_rho_apply_step: scratch_dev must be 8-byte aligned");
+    const hipError_t e = launch_rho_apply_step(h->D, rank, apply, apply ? 1.0 / global_batch : 0.0, lr_t, beta1, beta2, epsilon, h_reg,
+                                               r_reg, c_r, c_h, with_reg != 0, vars_dev, adam_m_dev, adam_v_dev, grad_sums_dev,
+                                               params_dev, phi_dev, losses_dev, static_cast<double*>(scratch_dev),
+                                               static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail_hip(h, e, "cmps_rho_apply_step");
     return CMPS_OK;
 }
 

@@ -402,6 +402,12 @@ size_t apply_step_scratch_bytes(int D);
 hipError_t launch_apply_step(int D, bool apply, double inv_batch, double lr_t, double beta1, double beta2, double eps, double h_reg,
                              double r_reg, double c_r, double c_h, bool with_reg, float* vars, float* am, float* av,
                              const float* grad_sums, float* params_out, float* losses_out, double* scratch, hipStream_t s);
+// cmps_rho_apply_step: the same step for RhoCMPS's variables (Wx, Wy [rank, D] in place of psi_x, psi_y); phi_out = the next columns
+size_t rho_apply_step_scratch_bytes(int D, int rank);
+hipError_t launch_rho_apply_step(int D, int rank, bool apply, double inv_batch, double lr_t, double beta1, double beta2, double eps,
+                                 double h_reg, double r_reg, double c_r, double c_h, bool with_reg, float* vars, float* am, float* av,
+                                 const float* grad_sums, float* params_out, float* phi_out, float* losses_out, double* scratch,
+                                 hipStream_t s);
 
 // model.A (model.py:19) as the kernels see it: a launch argument, or -- device-resident training -- a word of device memory
 __device__ __forceinline__ float dev_A(const Dev& P) { return P.Adev ? *P.Adev : P.A; }

@@ -11,6 +11,7 @@ import numpy as np
 
 FLOAT_BYTES = 4
 VAR_ORDER = ("A", "Rx", "Ry", "freqs", "psi_x", "psi_y")      # the device-resident variable / Adam-slot buffers (cmps_psi_apply_step)
+RHO_VAR_ORDER = ("A", "Rx", "Ry", "freqs", "Wx", "Wy")        # ... of cmps_rho_apply_step
 
 
 @dataclass
@@ -49,9 +50,14 @@ def legacy_grad_fields(D: int):
     return (("Q_re", (D, D)), ("Q_im", (D, D)), ("R", (D, D)), ("loss_sum", ()))
 
 
-def var_fields(D: int):
-    shapes = {"A": (), "Rx": (D, D), "Ry": (D, D), "freqs": (D,), "psi_x": (D,), "psi_y": (D,)}
-    return tuple((k, shapes[k]) for k in VAR_ORDER)
+def var_order(rank: int = 0):
+    return RHO_VAR_ORDER if rank else VAR_ORDER
+
+
+def var_fields(D: int, rank: int = 0):
+    """The variable / Adam-slot buffer of cmps_psi_apply_step; rank > 0: of cmps_rho_apply_step (Wx, Wy [rank, D] in place of psi_x, psi_y)."""
+    shapes = {"A": (), "Rx": (D, D), "Ry": (D, D), "freqs": (D,), "psi_x": (D,), "psi_y": (D,), "Wx": (rank, D), "Wy": (rank, D)}
+    return tuple((k, shapes[k]) for k in var_order(rank))
 
 
 def size(fields) -> int:

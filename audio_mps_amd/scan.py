@@ -60,7 +60,7 @@ class HipScan:
         self._param_host = torch.empty(self._n_params, dtype=torch.float32).pin_memory()
         self._param_evt = None
         self._legacy_buf = self._phi_buf = None       # the last legacy_set_params / rho_set_state upload (kept alive for the stream)
-        self._opt_scratch = None
+        self._opt_scratch = self._rho_opt_scratch = None
         self._B = self._T = self._rho_rank = 0
         self._audio = None
         self._loss = self._rho_loss = None            # per-clip losses of the main workspace's forwards (psi, legacy) and of rho_forward: each
@@ -214,6 +214,25 @@ class HipScan:
             self._h, vars_.data_ptr(), m.data_ptr(), v.data_ptr(), grad_sums.data_ptr() if grad_sums is not None else None,
             float(max(global_batch, 1)), float(lr_t), float(beta1), float(beta2), float(eps), float(h_reg), float(r_reg), float(c_r),
             float(c_h), 1 if with_reg else 0, params.data_ptr(), losses.data_ptr(), self._opt_scratch.data_ptr(), self._stream()))
+
+    def rho_apply_step(self, vars_: torch.Tensor, m: torch.Tensor, v: torch.Tensor, grad_sums: Optional[torch.Tensor], rank: int,
+                       global_batch: int, lr_t: float, beta1: float, beta2: float, eps: float, h_reg: float, r_reg: float, c_r: float,
+                       c_h: float, with_reg: bool, params: torch.Tensor, phi: torch.Tensor, losses: torch.Tensor):
+        """cmps_rho_apply_step: apply_step for RhoCMPS's variables (Wx, Wy [rank, D]); `phi` [2 rank D] receives the next columns
+        (the input of rho_set_state_dev)."""
+        key = (self.D, int(rank))
+        if self._rho_opt_scratch is None or self._rho_opt_scratch[0] != key:
+            n = int(self._lib.cmps_rho_apply_step_scratch_bytes(self.D, int(rank)))
+            if n == 0:
+                raise ValueError(f"invalid shape for the rho optimiser step: D={self.D}, rank={rank}")
+            self._rho_opt_scratch = (key, torch.empty((n + 7) // 8, dtype=torch.float64, device=self.device))
+        if phi.numel() != 2 * int(rank) * self.D:
+            raise ValueError("phi must have 2 rank D elements")
+        _capi.check(self._h, self._lib.cmps_rho_apply_step(
+            self._h, vars_.data_ptr(), m.data_ptr(), v.data_ptr(), grad_sums.data_ptr() if grad_sums is not None else None, int(rank),
+            float(max(global_batch, 1)), float(lr_t), float(beta1), float(beta2), float(eps), float(h_reg), float(r_reg), float(c_r),
+            float(c_h), 1 if with_reg else 0, params.data_ptr(), phi.data_ptr(), losses.data_ptr(),
+            self._rho_opt_scratch[1].data_ptr(), self._stream()))
 
     def _check_audio(self, audio: torch.Tensor):
         if not (isinstance(audio, torch.Tensor) and audio.is_cuda and audio.dtype == torch.float32
@@ -408,6 +427,19 @@ class HipScan:
         self._phi_buf, ptrs = self._upload(layout.phi_fields(D, r), layout.split("phi", phi))
         _capi.check(self._h, self._lib.cmps_rho_set_state(
             self._h, *ptrs, r, int(T), int(B), self._ws_flags(train), ws_ptr, ws_bytes, self._stream()))
+        self._rho_rank = r
+
+    def rho_set_state_dev(self, phi: torch.Tensor, rank: int, B: int, T: int, train: bool = True):
+        """cmps_rho_set_state with the columns read from the device buffer `phi` = phi_re [rank D] | phi_im [rank D] that
+        cmps_rho_apply_step wrote -- no upload, no synchronisation.  After set_params*."""
+        r, D = int(rank), self.D
+        if not (phi.is_cuda and phi.dtype == torch.float32 and phi.is_contiguous() and phi.numel() == 2 * r * D):
+            raise ValueError("phi must be a contiguous float32 CUDA tensor of 2 rank D elements")
+        ws_ptr, ws_bytes = self._workspace(B, T, train, rank=r)
+        self._phi_buf = phi
+        _capi.check(self._h, self._lib.cmps_rho_set_state(
+            self._h, *layout.pointers(phi.data_ptr(), layout.phi_fields(D, r)), r, int(T), int(B), self._ws_flags(train), ws_ptr, ws_bytes,
+            self._stream()))
         self._rho_rank = r
 
     def rho_forward(self, audio: torch.Tensor, save_for_bwd: bool = False) -> torch.Tensor:

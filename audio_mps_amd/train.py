@@ -67,8 +67,9 @@ class Trainer:
 
     ``device_step=False``: the gradient sums come to the host, chain rule (model.chain_rule) and Adam (AdamOptimizer) run in
     numpy, the parameters are uploaded again -- the tested reference implementation of the optimiser half.
-    ``device_step=True`` (PsiCMPS on the HIP backend): variables, Adam slots and effective parameters live on the GPU and
-    cmps_psi_apply_step does the optimiser half there; a step issues no device -> host copy.  ``step`` then returns the
+    ``device_step=True`` (PsiCMPS or RhoCMPS on the HIP backend): variables, Adam slots and effective parameters (for RhoCMPS the
+    columns of rho_0 as well) live on the GPU and cmps_psi_apply_step / cmps_rho_apply_step does the optimiser half there; a step
+    issues no device -> host copy.  ``step`` then returns the
     losses as a 2-element device tensor under "losses_dev" unless ``sync=True``; ``sync_to_host()`` brings variables and
     Adam state back (checkpoints, sampling, inspection)."""
 
@@ -82,12 +83,12 @@ class Trainer:
         self.global_step = 0
         self.history = deque(maxlen=self.HISTORY)   # the dict of every step (the scalar summaries of train.py:62-66)
         self.device_step = bool(device_step)
-        self._dev = None              # device-resident step: {"vars", "m", "v", "params", "losses"} device tensors (_device_state)
+        self._dev = None              # device-resident step: {"vars", "m", "v", "params", "losses"} (RhoCMPS: + "phi") device tensors (_device_state)
         self._dirty = False           # a device step has run since the last sync: the host copies are stale
         self._syncing = False         # inside _lazy_sync (sync_to_host reads model.variables, which calls _lazy_sync)
         self._syncing_back = False    # inside sync_to_host: assigning model.variables must not drop the state being read
-        if self.device_step and not isinstance(model, PsiCMPS):
-            raise ValueError("device_step: the device-resident optimiser step exists for PsiCMPS (the hot path) only")
+        if self.device_step and not isinstance(model, (PsiCMPS, RhoCMPS)):
+            raise ValueError("device_step: the device-resident optimiser step exists for PsiCMPS or RhoCMPS")
 
     # -- host reference path ----------------------------------------------------------------------
     def step(self, data=None, sync: bool = True, global_batch: Optional[int] = None) -> dict:
@@ -117,17 +118,23 @@ class Trainer:
         return out
 
     # -- device-resident path ---------------------------------------------------------------------
+    def _rank(self) -> int:
+        """0 for PsiCMPS; RhoCMPS: the number of columns of rho_0 (selects the variable layout and the rho entry points)."""
+        return int(self.model.rank_rho_0) if isinstance(self.model, RhoCMPS) else 0
+
     def _device_state(self):
         if self._dev is None:
             import torch
             be = self.model._get_backend()
-            D, variables = self.model.bond_d, self.model.variables
-            fields = layout.var_fields(D)
-            zeros = {k: np.zeros_like(variables[k]) for k in VAR_ORDER}       # (a missing Adam slot starts at zero)
+            D, rank, variables = self.model.bond_d, self._rank(), self.model.variables
+            fields = layout.var_fields(D, rank)
+            zeros = {k: np.zeros_like(variables[k]) for k in layout.var_order(rank)}     # (a missing Adam slot starts at zero)
             st = {slot: torch.from_numpy(layout.pack(fields, {**zeros, **src})).to(be.device)
                   for slot, src in (("vars", variables), ("m", self.opt.m), ("v", self.opt.v))}
             st["params"] = torch.empty(layout.size(layout.param_fields(D, with_A=True)), dtype=torch.float32, device=be.device)
             st["losses"] = torch.zeros(2, dtype=torch.float32, device=be.device)
+            if rank:
+                st["phi"] = torch.empty(layout.size(layout.phi_fields(D, rank)), dtype=torch.float32, device=be.device)
             self._dev = st
             self._dirty = False
             self.model._device_owner = weakref.ref(self)           # model.variables now syncs lazily from the device state
@@ -146,8 +153,13 @@ class Trainer:
     def _apply(self, grad_sums, global_batch):
         st, m, o = self._dev, self.model, self.opt
         lr_t = o.lr * math.sqrt(1.0 - o.b2 ** max(o.t, 1)) / (1.0 - o.b1 ** max(o.t, 1))
-        m._get_backend().apply_step(st["vars"], st["m"], st["v"], grad_sums, global_batch, lr_t, o.b1, o.b2, o.eps,
-                                    m.h_reg, m.r_reg, float(m._c_r), float(m._c_h), True, st["params"], st["losses"])
+        be, rank = m._get_backend(), self._rank()
+        if rank:
+            be.rho_apply_step(st["vars"], st["m"], st["v"], grad_sums, rank, global_batch, lr_t, o.b1, o.b2, o.eps,
+                              m.h_reg, m.r_reg, float(m._c_r), float(m._c_h), True, st["params"], st["phi"], st["losses"])
+        else:
+            be.apply_step(st["vars"], st["m"], st["v"], grad_sums, global_batch, lr_t, o.b1, o.b2, o.eps,
+                          m.h_reg, m.r_reg, float(m._c_r), float(m._c_h), True, st["params"], st["losses"])
 
     def _step_device(self, data, sync, global_batch):
         import torch
@@ -156,7 +168,13 @@ class Trainer:
         be = m._get_backend()
         audio = m._to_device(m._batch(data))
         b_local, T = audio.shape
-        if b_local > 0:
+        rank = self._rank()
+        if b_local > 0 and rank:                                   # (RhoCMPS._prepare: the main workspace holds the tables only)
+            be.set_params_dev(st["params"], m.sigma, m.delta_t, b_local, T, train=False)
+            be.rho_set_state_dev(st["phi"], rank, b_local, T, train=True)
+            be.rho_forward(audio, save_for_bwd=True)
+            flat = be.rho_backward()
+        elif b_local > 0:
             be.set_params_dev(st["params"], m.sigma, m.delta_t, b_local, T, train=True)
             be.forward(audio, save_for_bwd=True)
             flat = be.backward()
@@ -196,7 +214,7 @@ class Trainer:
             self._syncing_back = False
 
     def _sync_to_host(self):
-        fields = layout.var_fields(self.model.bond_d)
+        fields = layout.var_fields(self.model.bond_d, self._rank())
         self._dirty = False
         for name, dst in (("vars", self.model._variables), ("m", self.opt.m), ("v", self.opt.v)):
             for k, a in layout.unpack(fields, self._dev[name].cpu().numpy()).items():
@@ -246,7 +264,7 @@ def build_parser():
                         "3 MFMA pair kernels (32 < D <= 128, bf16 mat-vec operands), 5 float32 wide kernels (32 < D <= 128)")
     p.add_argument("--host_optimizer", action="store_true",
                    help="chain rule and Adam in numpy on the host (the reference implementation of the optimiser half) instead of "
-                        "the device-resident step (cmps_psi_apply_step)")
+                        "the device-resident step (cmps_psi_apply_step / cmps_rho_apply_step)")
     return p
 
 
@@ -270,7 +288,7 @@ def main(argv=None, backend=None):
     start, count = dp.shard(hp.minibatch_size)
     cls = RhoCMPS if args.mps_model == "rho_mps" else PsiCMPS                                   # train.py:50-53
     model = cls(hp, seed=args.seed, backend=backend)
-    device_step = (cls is PsiCMPS and not args.host_optimizer and type(backend).__name__ == "HipScan")
+    device_step = (not args.host_optimizer and type(backend).__name__ == "HipScan")
     trainer = Trainer(model, hp, dp, device_step=device_step)
     logdir = f"{args.logdir}/{args.dataset}/{hp.bond_dim}_{hp.delta_t}_{hp.minibatch_size}"    # train.py:94
     ckpt = os.path.join(logdir, "model.ckpt.npz")

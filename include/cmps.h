@@ -357,6 +357,30 @@ int cmps_rho_sample(cmps_handle_t h, const float* noise_dev, int n, int length, 
 int cmps_rho_states(cmps_handle_t h, int B, int steps, float* rho_out_dev, float* purity_out_dev, void* stream);
 
 /*
+ * Replaces: the optimiser half of a RhoCMPS training step -- tf.train.AdamOptimizer(learning_rate).minimize(total_loss)
+ * (train.py:88-89) with the regularisers of train.py:55-60, i.e. the chain rule from the effective parameters and the columns of
+ * rho_0 back to the trainable variables (adjoint of model.py:36-42, 49, 119-132), the Adam update, and the next step's effective
+ * parameters and columns (model.py:36-42, 49, 119-132).  cmps_psi_apply_step for the density-matrix model: everything not named
+ * here (lr_t, c_r, c_h, with_reg, losses_dev, the skipped step) is as described there.
+ *   vars_dev, adam_m_dev, adam_v_dev [2 D^2 + D + 1 + 2 rank D]: A | Rx [D*D] | Ry [D*D] | freqs [D] | Wx [rank*D] | Wy [rank*D]
+ *     (in / out; W row-major [a][d] as the reference's variables, model.py:121-127)
+ *   grad_sums_dev [2 D^2 + 3 D + 2 + 2 rank D]: the buffer of cmps_rho_loss_bwd, summed over all ranks (its two unused psi_0 blocks
+ *     are not read).  NULL: no update -- only params_dev and phi_dev are computed from vars_dev (the first step).
+ *     A non-finite entry in its gradient part (the column cotangents included) next to a finite loss sum skips the update:
+ *     variables and Adam slots stay as they are, losses_dev[1] = NaN, params_dev / phi_dev are written from the unchanged variables.
+ *   params_dev [2 D^2 + 3 D + 1]: out, the input of cmps_set_params_dev; its psi_0 slot is written as e_0 (unused on this path).
+ *   phi_dev [2 rank D]: out, phi_re [rank*D] | phi_im [rank*D], phi_a = conj(W[a, :]) / sqrt(tr W^dagger W): the two pointers
+ *     cmps_rho_set_state takes.  There is no floor on the trace (the reference has none, model.py:130).
+ *   scratch_dev: cmps_rho_apply_step_scratch_bytes(D, rank) bytes (0 for D or rank outside [1, 128]), 8-byte aligned.
+ * One small kernel on `stream`; nothing is copied to the host.
+ */
+size_t cmps_rho_apply_step_scratch_bytes(int D, int rank);
+int cmps_rho_apply_step(cmps_handle_t h, float* vars_dev, float* adam_m_dev, float* adam_v_dev, const float* grad_sums_dev,
+                        int rank, double global_batch, double lr_t, double beta1, double beta2, double epsilon, double h_reg,
+                        double r_reg, double c_r, double c_h, int with_reg, float* params_dev, float* phi_dev, float* losses_dev,
+                        void* scratch_dev, void* stream);
+
+/*
  * Host utility (no GPU involved): CRC-32C (Castagnoli, reflected polynomial 0x82F63B78) of `n` bytes, continuing from
  * `crc_in` (0 to start).  TFRecord framing stores it masked (((crc >> 15) | (crc << 17)) + 0xa282ead8) behind the length
  * and behind the payload of every record; the reference reads those files with tf.data.TFRecordDataset (data.py:29,
