@@ -785,6 +785,32 @@ int cmps_rho_update_ancilla(cmps_handle_t h, const float* rho_in_dev, const floa
     return CMPS_OK;
 }
 
+// What cmps_rho_sample and cmps_rho_sample_primed do behind their own argument checks: the workspace checks, the kernel choice, the launch
+// and the record for cmps_rho_states.  PR.prime == nullptr: unprimed; the scan has PR.PF + length steps.
+static int rho_sample_run(cmps_handle_t h, const char* who, const PrimeDev& PR, const float* noise_dev, int n, int length, float* out_dev,
+                          int save_states, void* stream) {
+    const std::string w(who);
+    const int steps = PR.PF + length;
+    // D <= 32 (rank <= 32): the row-array GEMM sampler, one wavefront per path (cmps_rho_mfma.hip); CMPS_VARIANT_BLOCK keeps the
+    // general workgroup-per-path kernel (cross-check; 93 us per step at rank 32 against 2 us)
+    const bool mfma = h->D <= 32 && h->W.rank <= 32 && h->variant_req != CMPS_VARIANT_BLOCK;
+    // (only when the SAMPLER's three column arrays exceed the LDS: the workspace section exists from a smaller rank * D on, for the
+    // reverse scan's four -- ADVICE r3)
+    if (!mfma && rho_cols_spill(3, h->W.rank, h->P.D) && n > h->rho_B)
+        return fail(h, CMPS_ERR_WORKSPACE, w + ": at this rank * D the columns live in the workspace: n must not exceed B_max");
+    if (save_states && (!(h->rho_flags & CMPS_WS_TRAIN) || (size_t)n * steps > (size_t)h->rho_B * (h->rho_T - 1)))
+        return fail(h, CMPS_ERR_WORKSPACE, w + ": save_states needs a CMPS_WS_TRAIN rho workspace with B_max*(T-1) >= n*" +
+                                               (PR.prime ? "(prime_T-1+length)" : "length"));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    KBind kb(PR.prime ? h : nullptr);                            // (cmps_rho_sample records no kernel events, as before)
+    KScope ks(mfma ? "k_sample_rho_mfma_primed" : "k_sample_rho_primed", s);
+    const hipError_t e = mfma ? launch_sample_rho_mfma(h->P, h->W, noise_dev, n, length, out_dev, save_states != 0, rank1_f16(h->rank1_mode), PR, s)
+                              : launch_sample_rho(h->P, h->W, noise_dev, n, length, out_dev, save_states != 0, PR, s);
+    if (e != hipSuccess) return fail_hip(h, e, who);
+    h->rho = Saved{save_states != 0, n, steps, nullptr, nullptr, mfma ? RHO_STASH_MFMA : RHO_STASH_BLOCK};   // (no reverse pass after a sampler)
+    return CMPS_OK;
+}
+
 int cmps_rho_sample(cmps_handle_t h, const float* noise_dev, int n, int length, float* out_dev, int save_states,
                     void* stream) {
     if (!h) return CMPS_ERR_BAD_ARG;
@@ -792,22 +818,28 @@ int cmps_rho_sample(cmps_handle_t h, const float* noise_dev, int n, int length, 
         return fail(h, CMPS_ERR_STATE, "cmps_rho_sample: call cmps_set_params and cmps_rho_set_state first");
     if (!noise_dev || !out_dev || n < 1 || length < 1) return fail(h, CMPS_ERR_BAD_ARG, "cmps_rho_sample: bad argument");
     if (length > h->L.N) return fail(h, CMPS_ERR_BAD_ARG, "cmps_rho_sample: length exceeds T - 1 of cmps_set_params");
-    // (only when the SAMPLER's three column arrays exceed the LDS: the workspace section exists from a smaller rank * D on, for the
-    // reverse scan's four -- ADVICE r3)
-    const bool mfma_sampler = h->D <= 32 && h->W.rank <= 32 && h->variant_req != CMPS_VARIANT_BLOCK;
-    if (!mfma_sampler && rho_cols_spill(3, h->W.rank, h->P.D) && n > h->rho_B)
-        return fail(h, CMPS_ERR_WORKSPACE, "cmps_rho_sample: at this rank * D the columns live in the workspace: n must not exceed B_max");
-    if (save_states && (!(h->rho_flags & CMPS_WS_TRAIN) || (size_t)n * length > (size_t)h->rho_B * (h->rho_T - 1)))
-        return fail(h, CMPS_ERR_WORKSPACE, "cmps_rho_sample: save_states needs a CMPS_WS_TRAIN rho workspace with B_max*(T-1) >= n*length");
-    // D <= 32 (rank <= 32): the row-array GEMM sampler, one wavefront per path (cmps_rho_mfma.hip); CMPS_VARIANT_BLOCK keeps the
-    // general workgroup-per-path kernel (cross-check; 93 us per step at rank 32 against 2 us)
-    const bool mfma = mfma_sampler;
-    hipError_t e = mfma ? launch_sample_rho_mfma(h->P, h->W, noise_dev, n, length, out_dev, save_states != 0,
-                                                 rank1_f16(h->rank1_mode), static_cast<hipStream_t>(stream))
-                        : launch_sample_rho(h->P, h->W, noise_dev, n, length, out_dev, save_states != 0, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return fail_hip(h, e, "cmps_rho_sample");
-    h->rho = Saved{save_states != 0, n, length, nullptr, nullptr, mfma ? RHO_STASH_MFMA : RHO_STASH_BLOCK};   // (no reverse pass after a sampler)
-    return CMPS_OK;
+    return rho_sample_run(h, "cmps_rho_sample", PrimeDev{nullptr, 0, 0, nullptr}, noise_dev, n, length, out_dev, save_states, stream);
+}
+
+int cmps_rho_sample_primed(cmps_handle_t h, const float* prime_dev, int n_prime, int prime_T, const float* noise_dev, int n, int length,
+                           float* out_dev, float* pred_dev, int save_states, void* stream) {
+    if (!h) return CMPS_ERR_BAD_ARG;
+    if (!h->params_set || h->legacy || !h->rho_set)
+        return fail(h, CMPS_ERR_STATE, "cmps_rho_sample_primed: call cmps_set_params and cmps_rho_set_state first (not available in legacy mode)");
+    if (!prime_dev || !noise_dev || !out_dev) return fail(h, CMPS_ERR_BAD_ARG, "cmps_rho_sample_primed: null pointer");
+    if (n < 1 || length < 1) return fail(h, CMPS_ERR_BAD_ARG, "cmps_rho_sample_primed: need n >= 1 and length >= 1");
+    if (prime_T < 2) return fail(h, CMPS_ERR_BAD_ARG, "cmps_rho_sample_primed: need prime_T >= 2 (one increment at least)");
+    if (n_prime != 1 && n_prime != n)
+        return fail(h, CMPS_ERR_BAD_ARG, "cmps_rho_sample_primed: n_prime must be n, or 1 for one clip shared by every path");
+    const int PF = prime_T - 1;                                  // teacher-forced steps
+    if ((long long)PF + length > h->L.N) {                        // one table row per step, forced or sampled
+        char buf[200];
+        snprintf(buf, sizeof buf, "cmps_rho_sample_primed: prime_T + length = %lld exceeds T = %d of cmps_set_params (the per-step tables): "
+                 "needs T >= %lld", (long long)prime_T + length, h->L.T, (long long)prime_T + length);
+        return fail(h, CMPS_ERR_BAD_ARG, buf);
+    }
+    return rho_sample_run(h, "cmps_rho_sample_primed", PrimeDev{prime_dev, n_prime == 1 ? 0 : prime_T, PF, pred_dev}, noise_dev, n, length,
+                          out_dev, save_states, stream);
 }
 
 int cmps_rho_states(cmps_handle_t h, int B, int steps, float* rho_out_dev, float* purity_out_dev, void* stream) {

@@ -337,8 +337,15 @@ hipError_t launch_states_rho(const Dev& P, const RhoDev& W, int B, int steps, fl
                              hipStream_t s);
 hipError_t launch_update_ancilla_rho(const Dev& P, const float* rho_in, const float* signal, float t, int B,
                                      float* rho_out, hipStream_t s);
+// cmps_rho_sample_primed: PF = prime_T - 1 teacher-forced steps on prime[path * stride + k] (stride 0: one shared clip) in front of the
+// `length` sampled ones; pred [n][PF] may be null.  prime == nullptr: the unprimed sampler (cmps_rho_sample), which reads none of this
+struct PrimeDev {
+    const float* prime;
+    int stride, PF;
+    float* pred;
+};
 hipError_t launch_sample_rho(const Dev& P, const RhoDev& W, const float* noise, int n, int length, float* out,
-                             bool save, hipStream_t s);
+                             bool save, const PrimeDev& PR, hipStream_t s);
 hipError_t launch_fwd_legacy_wave(const Dev& P, const float* audio, float* loss, bool save, hipStream_t s);
 hipError_t launch_bwd_legacy_wave(const Dev& P, const float* audio, int rank1_mode, hipStream_t s);
 hipError_t launch_legacy_tables(const Dev& P, float2* psi0, float* dtk, float2* rho, hipStream_t s);
@@ -346,7 +353,7 @@ hipError_t launch_fwd_rho_wave(const Dev& P, const RhoDev& W, const float* audio
 hipError_t launch_fwd_rho_mfma(const Dev& P, const RhoDev& W, const float* audio, float* loss, bool save, bool f16, bool grad1, hipStream_t s);
 hipError_t launch_bwd_rho_mfma(const Dev& P, const RhoDev& W, const float* audio, hipStream_t s);
 hipError_t launch_sample_rho_mfma(const Dev& P, const RhoDev& W, const float* noise, int n, int length, float* out, bool save,
-                                  bool f16, hipStream_t s);
+                                  bool f16, const PrimeDev& PR, hipStream_t s);
 hipError_t launch_bwd_rho_wave(const Dev& P, const RhoDev& W, const float* audio, hipStream_t s);
 hipError_t launch_prep(const Dev& P, const float* R_re, const float* R_im, const float* freqs,
                        const float* psi0_re, const float* psi0_im, float dt, bool rebuild_ttab,

@@ -421,10 +421,14 @@ __global__ void k_update_ancilla_rho(Dev P, const float* __restrict__ rho_in, co
 
 // ------------------------------------------------------------------------------------------------
 // RhoCMPS.sample / rho_evolve_with_sampling / purity (model.py:86-116, 160-167)
+// PRIMED (cmps_rho_sample_primed): PF = prime_T - 1 teacher-forced steps (increment prime[k + 1] - prime[k], model.py:138; running sum 0;
+// e dt, taken before the update, to pred[b][k] when asked) in front of the `length` sampled ones, which read noise[b][k - PF] and write
+// out[b][k - PF]; table row and stash row k throughout.  The unprimed instance (cmps_rho_sample) ignores its last argument and is the
+// kernel as it was (profiles/rho_primed_isa_identity.log).
 // ------------------------------------------------------------------------------------------------
-template <int NT>
+template <int NT, bool PRIMED>
 __global__ __launch_bounds__(NT) void k_sample_rho(Dev P, RhoDev W, const float* __restrict__ noise, int length,
-                                                   float* __restrict__ out, int save, float2* gcols) {
+                                                   float* __restrict__ out, int save, float2* gcols, PrimeDev PR) {
     extern __shared__ float2 sh[];
     const int D = P.D, DP = P.DP, r = W.rank, rD = r * D;
     float2* base = gcols ? gcols + (size_t)blockIdx.x * 4 * rD : sh;
@@ -434,11 +438,13 @@ __global__ __launch_bounds__(NT) void k_sample_rho(Dev P, RhoDev W, const float*
     float* red = reinterpret_cast<float*>(gcols ? sh : sh + 3 * rD);
     const int b = blockIdx.x, t = threadIdx.x;
     const bool act = t < D;
-    float2* st = save ? W.stash + (size_t)b * length * r * DP : nullptr;
+    const int PF = PRIMED ? PR.PF : 0, nsteps = PF + length;        // (unprimed: nsteps = length)
+    const float* prow = PRIMED ? PR.prime + (size_t)b * PR.stride : nullptr;      // (stride 0: one clip shared by all paths)
+    float2* st = save ? W.stash + (size_t)b * nsteps * r * DP : nullptr;
     if (act)
         for (int a = 0; a < r; ++a) S[a * D + t] = W.phi0[a * DP + t];
     float samp = 0.f;
-    for (int k = 0; k < length; ++k) {
+    for (int k = 0; k < nsteps; ++k) {
         __syncthreads();
         float pe = 0.f;
         if (act) {
@@ -457,8 +463,15 @@ __global__ __launch_bounds__(NT) void k_sample_rho(Dev P, RhoDev W, const float*
             }
         }
         const float e = 2.0f * block_sum<NT>(pe, red);                            // Re tr((Rt + Rt^dagger) rho), :189-196
-        const float inc = e * P.dt + noise[(size_t)b * length + k];                // :162
-        samp += inc;                                                               // :163
+        float inc;
+        const bool forced = PRIMED && k < PF;
+        if constexpr (PRIMED) {
+            inc = forced ? prow[k + 1] - prow[k] : e * P.dt + noise[(size_t)b * length + (k - PF)];
+            samp = forced ? 0.f : samp + inc;
+        } else {
+            inc = e * P.dt + noise[(size_t)b * length + k];                        // :162
+            samp += inc;                                                           // :163
+        }
         const float s = inc / dev_A(P);                                                 // :164, 175
         float pn = 0.f;
         if (act) {
@@ -477,7 +490,14 @@ __global__ __launch_bounds__(NT) void k_sample_rho(Dev P, RhoDev W, const float*
             const float2 rho = P.rho[(size_t)k * DP + t];
             for (int a = 0; a < r; ++a) S[a * D + t] = cmul(rho, cscale(sc, Wb[a * D + t]));
         }
-        if (t == 0) out[(size_t)b * length + k] = dev_A(P) * samp;                      // :116
+        if constexpr (PRIMED) {
+            if (t == 0) {
+                if (!forced) out[(size_t)b * length + (k - PF)] = dev_A(P) * samp;
+                else if (PR.pred) PR.pred[(size_t)b * PF + k] = e * P.dt;
+            }
+        } else {
+            if (t == 0) out[(size_t)b * length + k] = dev_A(P) * samp;                  // :116
+        }
     }
 }
 
@@ -569,16 +589,19 @@ hipError_t launch_update_ancilla_rho(const Dev& P, const float* rho_in, const fl
 }
 
 hipError_t launch_sample_rho(const Dev& P, const RhoDev& W, const float* noise, int n, int length, float* out,
-                             bool save, hipStream_t s) {
+                             bool save, const PrimeDev& PR, hipStream_t s) {
     size_t shm;
     float2* g = cols_if_needed(W, (size_t)3 * W.rank * P.D * sizeof(float2) + 128, shm, n);
     if (g == reinterpret_cast<float2*>(1)) return hipErrorInvalidValue;
     return dispatch_block_nt(P.D, [&](auto nt) {
         constexpr int NT = decltype(nt)::value;
-        const hipError_t e = lds_attr(k_sample_rho<NT>, shm);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k_sample_rho<NT>, dim3(n), dim3(NT), shm, s, P, W, noise, length, out, save ? 1 : 0, g);
-        return hipGetLastError();
+        return dispatch_bool(PR.prime != nullptr, [&](auto pm) {
+            constexpr bool PM = decltype(pm)::value;
+            const hipError_t e = lds_attr(k_sample_rho<NT, PM>, shm);
+            if (e != hipSuccess) return e;
+            hipLaunchKernelGGL((k_sample_rho<NT, PM>), dim3(n), dim3(NT), shm, s, P, W, noise, length, out, save ? 1 : 0, g, PR);
+            return hipGetLastError();
+        });
     });
 }
 

@@ -603,10 +603,19 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_bwd_rho_mfma(Dev P, RhoDev W,
 // their bf16 pieces are split once), then  e = 2 sum U . V  (= Re tr((R + R^dagger) rho), :189-196),  inc = e dt + noise,
 // s = inc / A,  Y = (U + QU) + s V,  n = sum Y^2,  U' = rho_k (.) Y / sqrt(n).  Noise is [n_paths][length] (one 64-step chunk
 // per lane load), the waveform is written back the same way.  Stash (save): RHO_STASH_MFMA rows of (y[n], 0).
+// PRIMED (cmps_rho_sample_primed): the scan runs over PF + length steps on table rows 0 .. PF + length - 1 (and, SAVE, over as many stash
+// rows per path).  The first PF = prime_T - 1 steps are teacher-forced: the increment is the clip's difference prime[k + 1] - prime[k]
+// (model.py:138) instead of e dt + noise, the running sum stays 0, and e dt -- Re tr((Rt + Rt^dagger) rho) delta_t on the normalised state
+// BEFORE the update, the expression of :162 without its noise -- goes to pred[b][k] when asked for; the `length` steps behind them are the
+// sampler's own, with noise[b][k - PF] and out[b][k - PF].  The chunk load hands every lane (step) one value, the clip's difference below
+// PF and the noise from PF on, and every lane writes one value back, so a step adds the wave-uniform compare k < PF and three selects on
+// it.  The fp16 x 2 form needs no new scale for a clip however loud: the fixed scales cover U (unit trace) and the constant W_R, W_Q, and
+// the data-dependent s = inc / A multiplies the float32 accumulators behind the MFMAs -- it never meets an fp16 piece.
+// The unprimed instance (cmps_rho_sample) ignores its last argument and is the kernel as it was (profiles/rho_primed_isa_identity.log).
 // ------------------------------------------------------------------------------------------------
-template <bool SAVE, bool F16>
+template <bool SAVE, bool F16, bool PRIMED>
 __global__ __launch_bounds__(64 * WAVES, 1) void k_sample_rho_mfma(Dev P, RhoDev W, const float* __restrict__ noise, int n_paths,
-                                                                   int length, float* __restrict__ out) {
+                                                                   int length, float* __restrict__ out, PrimeDev PR) {
     __shared__ __attribute__((aligned(16))) float Urow[WAVES][32 * RRLD];
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int b = blockIdx.x * WAVES + w;
@@ -664,13 +673,22 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_sample_rho_mfma(Dev P, RhoDev
     }
     const float* nrow = noise + (size_t)b * length;
     float* orow = out + (size_t)b * length;
-    float2* st = SAVE ? reinterpret_cast<float2*>(W.stash) + (size_t)b * length * r * 64 : nullptr;
+    const int PF = PRIMED ? PR.PF : 0, nsteps = PF + length;        // (unprimed: nsteps = length)
+    const float* prow = PRIMED ? PR.prime + (size_t)b * PR.stride : nullptr;      // (stride 0: one clip shared by all paths)
+    float* drow = PRIMED && PR.pred ? PR.pred + (size_t)b * PF : nullptr;
+    float2* st = SAVE ? reinterpret_cast<float2*>(W.stash) + (size_t)b * nsteps * r * 64 : nullptr;
     const float A = dev_A(P);
     const float sgn = (col & 1) ? 1.f : -1.f;                        // Im lanes add rho_y * partner, Re lanes subtract it
     float samp = 0.f;
-    for (int kbeg = 0; kbeg < length; kbeg += CH) {
-        const int cnt = (length - kbeg) < CH ? (length - kbeg) : CH;
-        const float nzv = kbeg + lane < length ? nrow[kbeg + lane] : 0.f;
+    for (int kbeg = 0; kbeg < nsteps; kbeg += CH) {
+        const int cnt = (nsteps - kbeg) < CH ? (nsteps - kbeg) : CH;
+        float nzv;                                                   // what this lane's step is handed: its noise, or (PRIMED, below PF) the clip's increment
+        if constexpr (PRIMED) {
+            const int kl = kbeg + lane;
+            nzv = kl < PF ? prow[kl + 1] - prow[kl] : kl < nsteps ? nrow[kl - PF] : 0.f;
+        } else {
+            nzv = kbeg + lane < length ? nrow[kbeg + lane] : 0.f;
+        }
         float outv = 0.f;
         for (int kk = 0; kk < cnt; ++kk) {
             const int k = kbeg + kk;
@@ -717,8 +735,17 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_sample_rho_mfma(Dev P, RhoDev
                 acce = fmaf(u1[q], v1[q], acce);
             }
             const float e = 2.0f * sum64(acce);                      // Re tr((Rt + Rt^dagger) rho), :189-196
-            const float inc = e * P.dt + rdlane(nzv, kk);            // :162
-            samp += inc;                                             // :163
+            float inc;
+            if constexpr (PRIMED) {
+                const bool forced = k < PF;                          // wave-uniform
+                const float edt = e * P.dt, given = rdlane(nzv, kk);
+                inc = forced ? given : edt + given;
+                samp = forced ? 0.f : samp + inc;
+                outv = lane == kk ? (forced ? edt : A * samp) : outv;
+            } else {
+                inc = e * P.dt + rdlane(nzv, kk);                    // :162
+                samp += inc;                                         // :163
+            }
             const float s = inc / A;                                 // :164, 175
             float y0[16], y1[16];
             float accn = 0.f;
@@ -748,9 +775,17 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_sample_rho_mfma(Dev P, RhoDev
                 U[row * RRLD + col] = fmaf(sgn * rh0.y, dpp_nb(t0), rh0.x * t0);
                 U[row * RRLD + 32 + col] = fmaf(sgn * rh1.y, dpp_nb(t1), rh1.x * t1);
             }
-            outv = lane == kk ? A * samp : outv;                     // :116
+            if constexpr (!PRIMED) outv = lane == kk ? A * samp : outv;      // :116
         }
-        if (kbeg + lane < length) orow[kbeg + lane] = outv;
+        if constexpr (PRIMED) {
+            const int kl = kbeg + lane;                              // table index; out is shifted by PF, pred is not
+            if (lane < cnt) {
+                if (kl >= PF) orow[kl - PF] = outv;
+                else if (drow) drow[kl] = outv;
+            }
+        } else {
+            if (kbeg + lane < length) orow[kbeg + lane] = outv;
+        }
     }
 }
 
@@ -766,12 +801,15 @@ hipError_t launch_fwd_rho_mfma(const Dev& P, const RhoDev& W, const float* audio
 }
 
 hipError_t launch_sample_rho_mfma(const Dev& P, const RhoDev& W, const float* noise, int n, int length, float* out, bool save,
-                                  bool f16, hipStream_t s) {
+                                  bool f16, const PrimeDev& PR, hipStream_t s) {
     const unsigned nb = (unsigned)((n + WAVES - 1) / WAVES);
     return dispatch_bool(save, [&](auto sv) {
         return dispatch_bool(f16, [&](auto hf) {
-            hipLaunchKernelGGL((k_sample_rho_mfma<decltype(sv)::value, decltype(hf)::value>), dim3(nb), dim3(64 * WAVES), 0, s, P, W, noise, n, length, out);
-            return hipGetLastError();
+            return dispatch_bool(PR.prime != nullptr, [&](auto pm) {
+                hipLaunchKernelGGL((k_sample_rho_mfma<decltype(sv)::value, decltype(hf)::value, decltype(pm)::value>), dim3(nb), dim3(64 * WAVES),
+                                   0, s, P, W, noise, n, length, out, PR);
+                return hipGetLastError();
+            });
         });
     });
 }

@@ -248,6 +248,45 @@ class CMPS(_ScanModel):
             raise ValueError(f"noise must be [{length}, {num_samples}]")
         return noise
 
+    # ---- primed sampling: units and shapes around the subclass's sample(prime=...) and its backend entry ----
+    def _sample_primed(self, be, prime, noise, want_pred):
+        """The backend's primed sampler for this model, (out, pred) with want_pred: HipScan.sample_primed / rho_sample_primed."""
+        raise NotImplementedError
+
+    @staticmethod
+    def _prime(prime, num_samples) -> np.ndarray:
+        """A prime as the backend takes it: float32 [1, T'] (shared by every path) or [num_samples, T'], T' >= 2."""
+        if hasattr(prime, "detach"):
+            prime = prime.detach().cpu().numpy()
+        prime = np.asarray(prime, dtype=np.float32)
+        if prime.ndim == 1:
+            prime = prime[None, :]
+        if prime.ndim != 2 or prime.shape[0] not in (1, num_samples):
+            raise ValueError(f"prime must be [T'], [1, T'] or [{num_samples}, T'], not {prime.shape}")
+        if prime.shape[1] < 2:
+            raise ValueError("prime needs two samples at least (one increment)")
+        return np.ascontiguousarray(prime)
+
+    def continue_clip(self, prime, num_samples, length, temp=1, seed=None, noise=None) -> np.ndarray:
+        """The continuation of ``prime`` in the clip's own units, [num_samples, length]: the array to plot or write behind the clip.
+        The model's waveform is A * (running sum of increments) and the data enter as increments / A (model.py:303, :175), so the
+        sampled sum is divided by A and starts from the clip's last sample."""
+        prime = self._prime(prime, num_samples)
+        out = self.sample(num_samples, length, temp=temp, seed=seed, noise=noise, prime=prime)
+        return (prime[..., -1:] + out / self.A).astype(np.float32)
+
+    def predict_increments(self, data=None) -> np.ndarray:
+        """Teacher-forced one-step predictions [B, T - 1] for a batch [B, T] (default: the model's data_iterator): entry k is the
+        model's expected increment (2 Re<psi|R|psi> delta_t, or Re tr((Rt + Rt^dagger) rho) delta_t) at t_k, given the clip up to sample
+        k -- to compare with data[:, k + 1] - data[:, k].  Runs the primed sampler with one sampled step and discards it."""
+        data = self._batch(data)
+        if data is None:
+            raise ValueError("predict_increments needs a batch (data, or the model's data_iterator)")
+        B = int(np.shape(data)[0])
+        prime = self._prime(data, B)
+        be = self._prepare(B, prime.shape[1] + 1, train=False)
+        return self._sample_primed(be, prime, np.zeros((1, B), dtype=np.float32), True)[1]
+
     def _chain_common(self, Rbar, fbar, Abar, loss, with_reg: bool):
         """Adjoint of model.py:36-42 (scaling + the row-broadcast diagonal removal) and :49 for batch-mean cotangents of
         the effective R, freqs, A; optionally the regularisers of train.py:55-60."""
@@ -379,41 +418,10 @@ class PsiCMPS(CMPS):
             return self._prepare(num_samples, length + 1, train=False).sample(noise)
         prime = self._prime(prime, num_samples)
         be = self._prepare(num_samples, prime.shape[1] + length, train=False)    # one table row per step, forced or sampled
-        return be.sample_primed(prime, noise, want_pred=bool(return_pred))
+        return self._sample_primed(be, prime, noise, bool(return_pred))
 
-    @staticmethod
-    def _prime(prime, num_samples) -> np.ndarray:
-        """A prime as the backend takes it: float32 [1, T'] (shared by every path) or [num_samples, T'], T' >= 2."""
-        if hasattr(prime, "detach"):
-            prime = prime.detach().cpu().numpy()
-        prime = np.asarray(prime, dtype=np.float32)
-        if prime.ndim == 1:
-            prime = prime[None, :]
-        if prime.ndim != 2 or prime.shape[0] not in (1, num_samples):
-            raise ValueError(f"prime must be [T'], [1, T'] or [{num_samples}, T'], not {prime.shape}")
-        if prime.shape[1] < 2:
-            raise ValueError("prime needs two samples at least (one increment)")
-        return np.ascontiguousarray(prime)
-
-    def continue_clip(self, prime, num_samples, length, temp=1, seed=None, noise=None) -> np.ndarray:
-        """The continuation of ``prime`` in the clip's own units, [num_samples, length]: the array to plot or write behind the clip.
-        The model's waveform is A * (running sum of increments) and the data enter as increments / A (model.py:303), so the
-        sampled sum is divided by A and starts from the clip's last sample."""
-        prime = self._prime(prime, num_samples)
-        out = self.sample(num_samples, length, temp=temp, seed=seed, noise=noise, prime=prime)
-        return (prime[..., -1:] + out / self.A).astype(np.float32)
-
-    def predict_increments(self, data=None) -> np.ndarray:
-        """Teacher-forced one-step predictions [B, T - 1] for a batch [B, T] (default: the model's data_iterator): entry k is the
-        model's expected increment 2 Re<psi|R|psi> delta_t at t_k, given the clip up to sample k -- to compare with
-        data[:, k + 1] - data[:, k].  Runs the primed sampler with one sampled step and discards it."""
-        data = self._batch(data)
-        if data is None:
-            raise ValueError("predict_increments needs a batch (data, or the model's data_iterator)")
-        B = int(np.shape(data)[0])
-        prime = self._prime(data, B)
-        be = self._prepare(B, prime.shape[1] + 1, train=False)
-        return be.sample_primed(prime, np.zeros((1, B), dtype=np.float32), want_pred=True)[1]
+    def _sample_primed(self, be, prime, noise, want_pred):
+        return be.sample_primed(prime, noise, want_pred=want_pred)
 
 
 # --------------------------------------------------------------------------------------------------
@@ -519,24 +527,39 @@ class RhoCMPS(CMPS):
         be.rho_forward(audio, save_for_bwd=True)
         return be.rho_states(B, T - 1, want_rho=True)
 
-    def _sample_scan(self, num_samples, length, temp, seed, noise, save_states):
+    def _sample_primed(self, be, prime, noise, want_pred, save_states=False):
+        return be.rho_sample_primed(prime, noise, want_pred=want_pred, save_states=save_states)
+
+    def _sample_scan(self, num_samples, length, temp, seed, noise, save_states, prime=None, want_pred=False):
+        """(backend, what its sampler returned, steps of the scan): unprimed, or (``prime``) P = T' - 1 forced steps in front."""
         noise = self._noise(num_samples, length, temp, seed, noise)
-        be = self._prepare(num_samples, length + 1, train=save_states)
-        return be, be.rho_sample(noise, save_states=save_states)
+        if prime is None:
+            be = self._prepare(num_samples, length + 1, train=save_states)
+            return be, be.rho_sample(noise, save_states=save_states), length
+        prime = self._prime(prime, num_samples)
+        be = self._prepare(num_samples, prime.shape[1] + length, train=save_states)      # one table row per step, forced or sampled
+        return be, self._sample_primed(be, prime, noise, want_pred, save_states), prime.shape[1] - 1 + length
 
-    def sample(self, num_samples, length, temp=1, seed=None, noise=None):
-        """model.py:103-116: waveforms [num_samples, length] = A * running sum of the sampled increments."""
-        return self._sample_scan(num_samples, length, temp, seed, noise, False)[1]
+    def sample(self, num_samples, length, temp=1, seed=None, noise=None, prime=None, return_pred=False):
+        """model.py:103-116: waveforms [num_samples, length] = A * running sum of the sampled increments.
 
-    def rho_evolve_with_sampling(self, num_samples, length, temp=1, seed=None, noise=None) -> np.ndarray:
-        """model.py:86-92: rho after every sampled step, [num_samples, length, D, D]."""
-        be, _ = self._sample_scan(num_samples, length, temp, seed, noise, True)
-        return be.rho_states(num_samples, length, want_rho=True)
+        ``prime`` / ``return_pred`` as in PsiCMPS.sample: the state is first teacher-forced on the clip -- T' - 1 steps of _rho_update
+        (model.py:144-150) on its increments -- and the ``length`` sampled steps follow in the same scan (cmps_rho_sample_primed);
+        ``return_pred`` adds Re tr((Rt + Rt^dagger) rho) delta_t before every forced step, [num_samples, T' - 1]."""
+        if prime is None and return_pred:
+            raise ValueError("return_pred needs a prime: the predictions belong to the teacher-forced steps")
+        return self._sample_scan(num_samples, length, temp, seed, noise, False, prime, bool(return_pred))[1]
 
-    def purity(self, num_samples, length, temp=1, seed=None, noise=None) -> np.ndarray:
-        """model.py:94-101: tr rho^2 along sampled paths, [num_samples, length]."""
-        be, _ = self._sample_scan(num_samples, length, temp, seed, noise, True)
-        return be.rho_states(num_samples, length, want_rho=False, want_purity=True)
+    def rho_evolve_with_sampling(self, num_samples, length, temp=1, seed=None, noise=None, prime=None) -> np.ndarray:
+        """model.py:86-92: rho after every sampled step, [num_samples, length, D, D]; with ``prime`` [num_samples, P + length, D, D], the
+        P = T' - 1 teacher-forced steps first."""
+        be, _, steps = self._sample_scan(num_samples, length, temp, seed, noise, True, prime)
+        return be.rho_states(num_samples, steps, want_rho=True)
+
+    def purity(self, num_samples, length, temp=1, seed=None, noise=None, prime=None) -> np.ndarray:
+        """model.py:94-101: tr rho^2 along sampled paths, [num_samples, length]; with ``prime`` [num_samples, P + length], forced steps first."""
+        be, _, steps = self._sample_scan(num_samples, length, temp, seed, noise, True, prime)
+        return be.rho_states(num_samples, steps, want_rho=False, want_purity=True)
 
 
 class LegacyAudioMPS(_ScanModel):

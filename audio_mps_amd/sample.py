@@ -1,11 +1,12 @@
 """Sampler for a trained model: the reference's sample.py, which declares its flags (sample.py:10-14) and leaves ``main`` empty.
 
   flags              sample.py:10-14     --sample_duration, --sample_rate, --modeldir (same names, same defaults)
-  model              train.py:49-53      PsiCMPS(hparams), its variables read from the checkpoint Trainer.save writes
-  waveform           model.py:242-251    model.sample(num_samples, sample_duration, temp) / A, in the data's units
+  model              train.py:49-53      PsiCMPS(hparams) or, for a checkpoint holding Wx / Wy (--mps_model rho_mps), RhoCMPS(hparams); its
+                                         variables read from the checkpoint Trainer.save writes
+  waveform           model.py:242-251    model.sample(num_samples, sample_duration, temp) / A, in the data's units (RhoCMPS: :103-116)
 
 ``--prime FILE`` (a 16-bit mono .wav, or a .npy array [T'], [1, T'] or [num_samples, T']) continues a clip instead: the state is
-teacher-forced on the clip and the sampler carries on from there (PsiCMPS.continue_clip, cmps_psi_sample_primed); the written
+teacher-forced on the clip and the sampler carries on from there (continue_clip; cmps_psi_sample_primed / cmps_rho_sample_primed); the written
 waveform is the clip followed by its continuation.  Writes ``sample_<i>.wav`` (16-bit PCM mono at --sample_rate, clipped to
 [-1, 1)) and ``samples.npy`` (float32 [num_samples, samples], unclipped) into --out_dir.
 Run:  python -m audio_mps_amd.sample --modeldir=LOGDIR --sample_duration=16000 --prime=clip.wav
@@ -19,7 +20,7 @@ import wave
 
 import numpy as np
 
-from .model import HParams, PsiCMPS
+from .model import CMPS, HParams, PsiCMPS, RhoCMPS
 
 CKPT_NAME = "model.ckpt.npz"          # what train.main saves into its logdir
 
@@ -70,12 +71,12 @@ def load_variables(modeldir: str) -> dict:
 
 
 def build_parser():
-    p = argparse.ArgumentParser(description="Sample from a trained PsiCMPS on MI355X, or continue a clip (audio-mps sample.py, filled in)")
+    p = argparse.ArgumentParser(description="Sample from a trained PsiCMPS or RhoCMPS on MI355X, or continue a clip (audio-mps sample.py, filled in)")
     p.add_argument("--sample_duration", type=int, default=2 ** 16, help="samples to generate (as integer)")      # sample.py:10
     p.add_argument("--sample_rate", type=int, default=16000)                                                      # sample.py:11
     p.add_argument("--modeldir", default="./data", help=f"directory holding {CKPT_NAME}, or the checkpoint file")  # sample.py:14
     p.add_argument("--hparams", default="", help="as for training (r_reg, h_reg, sigma, delta_t must be the training run's; "
-                   "bond_dim is read from the checkpoint)")
+                   "bond_dim and initial_rank are read from the checkpoint)")
     p.add_argument("--num_samples", type=int, default=1)
     p.add_argument("--temp", type=float, default=1.0, help="noise temperature (model.py:246)")
     p.add_argument("--seed", type=int, default=0)
@@ -92,15 +93,19 @@ def main(argv=None, backend=None):
     if args.sample_duration < 1 or args.num_samples < 1:
         raise ValueError("--sample_duration and --num_samples must be positive")
     variables = load_variables(args.modeldir)
-    if "Wx" in variables or "psi_x" not in variables:
-        raise ValueError("the checkpoint is not a PsiCMPS one (rho_mps checkpoints cannot be primed or sampled here)")
+    rho = "Wx" in variables and "Wy" in variables             # a RhoCMPS checkpoint (train.py --mps_model rho_mps)
+    if not rho and "psi_x" not in variables:
+        raise ValueError("the checkpoint holds neither psi_x (PsiCMPS) nor Wx / Wy (RhoCMPS)")
     hp = HParams(delta_t=1.0 / args.sample_rate, h_reg=200.0 / (math.pi * args.sample_rate) ** 2)       # train.py:41-43
-    hp.bond_dim = int(variables["psi_x"].shape[0])
+    if rho:
+        hp.initial_rank, hp.bond_dim = (int(x) for x in variables["Wx"].shape)
+    else:
+        hp.bond_dim = int(variables["psi_x"].shape[0])
     hp.parse(args.hparams)
     if backend is None:
         from .scan import HipScan
         backend = HipScan(hp.bond_dim, variant=args.kernel_variant)
-    model = PsiCMPS(hp, seed=args.seed, backend=backend)
+    model = (RhoCMPS if rho else PsiCMPS)(hp, seed=args.seed, backend=backend)
     for k in model.variables:
         if variables[k].shape != model.variables[k].shape:
             raise ValueError(f"checkpoint variable {k} has shape {variables[k].shape}, bond_dim={hp.bond_dim} needs {model.variables[k].shape}")
@@ -109,7 +114,7 @@ def main(argv=None, backend=None):
     if args.prime is None:
         waves = model.sample(n, length, temp=args.temp, seed=args.seed) / model.A
     else:
-        prime = PsiCMPS._prime(load_prime(args.prime, args.sample_rate), n)
+        prime = CMPS._prime(load_prime(args.prime, args.sample_rate), n)
         cont = model.continue_clip(prime, n, length, temp=args.temp, seed=args.seed)
         waves = np.concatenate([np.broadcast_to(prime, (n, prime.shape[1])), cont], axis=1)
     waves = np.ascontiguousarray(waves, dtype=np.float32)

@@ -116,7 +116,7 @@ class HipScan:
         return mode if mode in (_capi.CMPS_RANK1_EXACT_F32, _capi.CMPS_RANK1_BF16X2, _capi.CMPS_RANK1_F16X2) else _capi.CMPS_RANK1_BF16X3
 
     def kernel_events(self, on: bool):
-        """cmps_set_option(CMPS_OPT_KERNEL_EVENTS): bracket every kernel of forward() / backward() and of sample() / sample_primed() with HIP
+        """cmps_set_option(CMPS_OPT_KERNEL_EVENTS): bracket every kernel of forward() / backward() and of sample() / sample_primed() / rho_sample_primed() with HIP
         events (a measurement aid, used by bench.py outside its timed region)."""
         _capi.check(self._h, self._lib.cmps_set_option(self._h, _capi.CMPS_OPT_KERNEL_EVENTS, 1 if on else 0))
 
@@ -374,11 +374,9 @@ class HipScan:
         """PsiCMPS.sample for pre-drawn noise [length, n] (the reference's layout) -> waveforms [n, length]."""
         return self._sample(self._lib.cmps_psi_sample, noise)
 
-    def sample_primed(self, prime: np.ndarray, noise: np.ndarray, want_pred: bool = False):
-        """cmps_psi_sample_primed: teacher-force the clips ``prime`` [n_prime, prime_T] (n_prime = n, or 1 for one clip shared by every
-        path), then sample ``length`` steps with the pre-drawn ``noise`` [length, n] (the reference's layout, as `sample` takes it).
-        Returns out [n, length] = A * running sum of the sampled increments (zero at the hand-over), or (out, pred [n, prime_T - 1])
-        with want_pred: the model's expected increment of every forced step.  After set_params with T >= prime_T + length."""
+    def _sample_primed(self, fn, prime: np.ndarray, noise: np.ndarray, want_pred: bool, *flags):
+        """Clips [n_prime, prime_T] and pre-drawn noise [length, n] (the reference's layout) up, waveforms [n, length] and, with want_pred,
+        the forced steps' predictions [n, prime_T - 1] down: `fn` is cmps_{psi,rho}_sample_primed."""
         prime = np.array(prime, dtype=np.float32, order="C")          # (a copy: torch wants a writable array)
         noise = np.asarray(noise, dtype=np.float32)
         if prime.ndim != 2 or noise.ndim != 2:
@@ -388,11 +386,17 @@ class HipScan:
         d_noise = torch.from_numpy(np.array(noise.T, order="C")).to(self.device)
         d_out = torch.empty((n, length), dtype=torch.float32, device=self.device)
         d_pred = torch.empty((n, max(prime_T - 1, 0)), dtype=torch.float32, device=self.device) if want_pred else None
-        _capi.check(self._h, self._lib.cmps_psi_sample_primed(
-            self._h, d_prime.data_ptr(), n_prime, prime_T, d_noise.data_ptr(), n, length, d_out.data_ptr(),
-            d_pred.data_ptr() if want_pred else None, self._stream()))
+        _capi.check(self._h, fn(self._h, d_prime.data_ptr(), n_prime, prime_T, d_noise.data_ptr(), n, length, d_out.data_ptr(),
+                                d_pred.data_ptr() if want_pred else None, *flags, self._stream()))
         out = d_out.cpu().numpy()
         return (out, d_pred.cpu().numpy()) if want_pred else out
+
+    def sample_primed(self, prime: np.ndarray, noise: np.ndarray, want_pred: bool = False):
+        """cmps_psi_sample_primed: teacher-force the clips ``prime`` [n_prime, prime_T] (n_prime = n, or 1 for one clip shared by every
+        path), then sample ``length`` steps with the pre-drawn ``noise`` [length, n] (the reference's layout, as `sample` takes it).
+        Returns out [n, length] = A * running sum of the sampled increments (zero at the hand-over), or (out, pred [n, prime_T - 1])
+        with want_pred: the model's expected increment of every forced step.  After set_params with T >= prime_T + length."""
+        return self._sample_primed(self._lib.cmps_psi_sample_primed, prime, noise, want_pred)
 
     # ------------------------------------------------------------------
     # legacy AudioMPS arithmetic (SURVEY 8f rank 2)
@@ -460,6 +464,11 @@ class HipScan:
     def rho_sample(self, noise: np.ndarray, save_states: bool = False) -> np.ndarray:
         """RhoCMPS.sample for pre-drawn noise [length, n] -> waveforms [n, length]."""
         return self._sample(self._lib.cmps_rho_sample, noise, 1 if save_states else 0)
+
+    def rho_sample_primed(self, prime: np.ndarray, noise: np.ndarray, want_pred: bool = False, save_states: bool = False):
+        """cmps_rho_sample_primed: `sample_primed` for RhoCMPS, from the columns of rho_set_state.  save_states keeps the columns of all
+        prime_T - 1 + length steps for rho_states (a train=True rho workspace with T >= prime_T + length)."""
+        return self._sample_primed(self._lib.cmps_rho_sample_primed, prime, noise, want_pred, 1 if save_states else 0)
 
     def rho_states(self, B: int, steps: int, want_rho: bool = True, want_purity: bool = False):
         """Lab-frame rho [B, steps, D, D] and/or purity [B, steps] of the last saved scan."""

@@ -84,7 +84,7 @@ enum {
     CMPS_OPT_F16_SCALE_SHIFT = 4 /* DIAGNOSTIC, default 0: added to the exponent of every data-dependent fp16 scale of the wave reverse
                         * scan's F16X2 arithmetic (range -40 .. 40).  A positive value pushes the pieces out of fp16 range on purpose:
                         * how tests/test_gpu_parity.py provokes CMPS_ERR_F16_RANGE.  No reference counterpart. */,
-    CMPS_OPT_KERNEL_EVENTS = 2 /* 1: every kernel cmps_psi_loss_fwd / _bwd, cmps_psi_sample and cmps_psi_sample_primed launch is bracketed by two HIP events on the caller's stream
+    CMPS_OPT_KERNEL_EVENTS = 2 /* 1: every kernel cmps_psi_loss_fwd / _bwd, cmps_psi_sample, cmps_psi_sample_primed and cmps_rho_sample_primed launch is bracketed by two HIP events on the caller's stream
                         * (read and reset with cmps_kernel_times); 0 (default): nothing is recorded.  A measurement aid -- the reference
                         * has no counterpart (no tracing / profiling hooks); bench.py uses it OUTSIDE its timed region to price
                         * each kernel of a multi-kernel family against the pipe it runs on */
@@ -341,7 +341,7 @@ int cmps_legacy_loss_bwd(cmps_handle_t h, const float* audio_dev, int B, int T, 
  *   T >= length + 1) for cmps_rho_states.  Kernel selection follows cmps_set_variant like the loss entries: D <= 32 and
  *   rank <= 32 run the row-array GEMM kernels (one wavefront per clip / path), CMPS_VARIANT_BLOCK the general ones.
  * cmps_rho_states: lab-frame normalised rho after every step of the last cmps_rho_loss_fwd(save_for_bwd=1) or
- *   cmps_rho_sample(save_states=1): rho_out_dev [B*steps*D*D*2] (rho_evolve_with_data, model.py:76-84 /
+ *   cmps_rho_sample / cmps_rho_sample_primed(save_states=1): rho_out_dev [B*steps*D*D*2] (rho_evolve_with_data, model.py:76-84 /
  *   rho_evolve_with_sampling, :86-92) and/or purity_out_dev [B*steps] = tr rho^2 (:94-101); either may be NULL.
  */
 size_t cmps_rho_workspace_bytes(int D, int rank, int B, int T, int flags);
@@ -355,6 +355,32 @@ int cmps_rho_update_ancilla(cmps_handle_t h, const float* rho_in_dev, const floa
 int cmps_rho_sample(cmps_handle_t h, const float* noise_dev, int n, int length, float* out_dev, int save_states,
                     void* stream);
 int cmps_rho_states(cmps_handle_t h, int B, int steps, float* rho_out_dev, float* purity_out_dev, void* stream);
+
+/*
+ * RhoCMPS.sample (model.py:103-116) continued from a clip: cmps_psi_sample_primed for the density-matrix model, with the same
+ * conventions.  P = prime_T - 1 teacher-forced steps of _rho_update (model.py:144-150) on the increments of prime_dev, then `length`
+ * steps of _rho_and_sample_update (:160-167), as ONE scan over the steps k = 0 .. P + length - 1 on table row k from the `rank` columns
+ * of cmps_rho_set_state, so the time grid t_k and the rotating frame run through the hand-over unbroken.
+ *   forced step, k < P:   increment = prime[b'][k + 1] - prime[b'][k] in float32 (the subtraction of model.py:138), b' = b, or 0 when
+ *                         one clip is shared;  the running sum stays 0;  pred[b][k] = Re tr((Rt + Rt^dagger) rho) * delta_t on the
+ *                         normalised state at t_k, BEFORE the step sees the data: the expression the sampler adds its noise to at
+ *                         model.py:162;  the update is the sampler's own with the given increment.
+ *   sampled step, k >= P: exactly the step of cmps_rho_sample with noise[b][k - P];  out[b][k - P] = A * (running sum of the
+ *                         sampled increments, starting from zero at k = P).
+ * prime_dev [n_prime * prime_T] row-major clips, n_prime == n, or n_prime == 1 for one clip shared by every path; prime_T >= 2.
+ * noise_dev [n * length], out_dev [n * length] as in cmps_rho_sample; pred_dev [n * (prime_T - 1)] row-major [path][step], or NULL.
+ * save_states != 0 keeps the columns of ALL P + length steps, forced ones first (needs a CMPS_WS_TRAIN rho workspace with
+ * B_max * (T - 1) >= n * (P + length)): cmps_rho_states(h, n, P + length, ...) then returns rho and purity across the hand-over.
+ * Needs cmps_set_params* with T >= prime_T + length (one row of the per-step tables per step, forced or sampled), otherwise
+ * CMPS_ERR_BAD_ARG with a message naming the needed T; null prime_dev / noise_dev / out_dev, n < 1, length < 1, prime_T < 2 and
+ * n_prime not in {1, n} are CMPS_ERR_BAD_ARG; before cmps_set_params or cmps_rho_set_state and in legacy mode CMPS_ERR_STATE;
+ * CMPS_ERR_WORKSPACE as for cmps_rho_sample (columns in the workspace and n > B_max; save_states without the rows for it).
+ * The kernel is chosen exactly as in cmps_rho_sample; with CMPS_OPT_KERNEL_EVENTS its time is recorded as k_sample_rho_mfma_primed /
+ * k_sample_rho_primed.
+ */
+int cmps_rho_sample_primed(cmps_handle_t h, const float* prime_dev, int n_prime, int prime_T,
+                           const float* noise_dev, int n, int length,
+                           float* out_dev, float* pred_dev, int save_states, void* stream);
 
 /*
  * Replaces: the optimiser half of a RhoCMPS training step -- tf.train.AdamOptimizer(learning_rate).minimize(total_loss)

@@ -12,7 +12,7 @@ code only, expects every row "identical".  Needs hipcc, no GPU.  --keep DIR leav
 --kernels REGEX adds one row per kernel whose (mangled) symbol matches, in the translation units that differ: the kernel's body
 (its label to its end label) and its .amdhsa_kernel descriptor block, compared as text with the kernel's own symbol and the
 function index of its labels normalised -- for a change that adds kernels or instances to a file and must leave the existing ones
-alone.  Kernels are paired by demangled name, template arguments `false` dropped."""
+alone.  Kernels are paired by demangled name, trailing template arguments `false` dropped."""
 import argparse
 import hashlib
 import importlib.util
@@ -62,15 +62,17 @@ def assemble(tree, src, extra, keep, label):
 
 
 def kernel_key(sym):
-    """What identifies a kernel across the two trees: its demangled name without return type and arguments, and without template
-    arguments `false` (a kernel that gained a bool template parameter keeps its key in the instance that passes false)."""
+    """What identifies a kernel across the two trees: its demangled name without return type and arguments, and without TRAILING template
+    arguments `false` (a kernel that gained a bool template parameter at the end keeps its key in the instance that passes false)."""
     import shutil
     filt = shutil.which("c++filt") or shutil.which("llvm-cxxfilt")
     if not filt:
         raise RuntimeError("--kernels needs c++filt (or llvm-cxxfilt) to pair the kernels of the two trees")
     name = subprocess.run([filt, sym], stdout=subprocess.PIPE, text=True, check=True).stdout.strip()
     name = re.sub(r"^void ", "", name.split("(")[0]).replace(" ", "")
-    args = [x for x in re.sub(r"^[^<]*<?|>$", "", name).split(",") if x and x != "false"] if "<" in name else []
+    args = [x for x in re.sub(r"^[^<]*<?|>$", "", name).split(",") if x] if "<" in name else []
+    while args and args[-1] == "false":
+        args.pop()
     return name.split("<")[0] + ("<" + ",".join(args) + ">" if args else "")
 
 
@@ -85,6 +87,7 @@ def kernels_of(text, pattern):
         desc = re.search(r"^\s*\.amdhsa_kernel\s+%s\n.*?\.end_amdhsa_kernel" % re.escape(sym), text, flags=re.M | re.S)
         both = (body.group(0) if body else "") + "\n" + (desc.group(0) if desc else "")
         both = re.sub(r"(BB|func_end)\d+", r"\1N", both.replace(sym, "KERNEL"))      # (labels carry the function's index in its file)
+        both = re.sub(r"[ \t]+;", " ;", both)                                          # (... and their comments are aligned behind them)
         out[kernel_key(sym)] = (sym, both)
     return out
 
