@@ -373,9 +373,14 @@ __global__ void k_states(Dev P, float* __restrict__ psi_out) {
 // 0; e_k dt to pred[b][k] when asked) in front of the `length` sampled ones, which read noise[b][k - PF] and write out[b][k - PF]; table
 // row k throughout.  The unprimed instance (cmps_psi_sample) ignores its last four
 // arguments and is the kernel as it was (profiles/primed_sampler_isa_identity.log).
-template <int NT, bool PRIMED>
+// STREAM (cmps_psi_stream): the primed scan as one segment of a longer one -- PF or length may be 0, step k of the launch runs on table
+// row ST.k0 + k, and u and the running sum come from the path's record when ST.in is set and go to it behind the last step when ST.out is.
+// The other instances ignore ST and are the kernels they were (profiles/stream_sampler_isa_identity.log).
+template <int NT, bool PRIMED, bool STREAM = false>
 __global__ __launch_bounds__(NT) void k_sample_block(Dev P, const float* __restrict__ noise, int length, float* __restrict__ out,
-                                                     const float* __restrict__ prime, int prime_stride, int PF, float* __restrict__ pred) {
+                                                     const float* __restrict__ prime, int prime_stride, int PF, float* __restrict__ pred,
+                                                     StreamDev ST) {
+    static_assert(PRIMED || !STREAM, "a stream segment is a primed scan");
     extern __shared__ float2 sh[];
     const int D = P.D, DP = P.DP;
     float2* su = sh;
@@ -386,6 +391,13 @@ __global__ __launch_bounds__(NT) void k_sample_block(Dev P, const float* __restr
     float samp = 0.f;
     const int nsteps = PRIMED ? PF + length : length;
     const float* prow = PRIMED ? prime + (size_t)b * prime_stride : nullptr;      // (prime_stride 0: one clip shared by all paths)
+    if constexpr (STREAM) {
+        if (ST.in) {
+            const float* rec = ST.in + (size_t)b * ST.rec;
+            if (act) u = make_float2(rec[2 * t], rec[2 * t + 1]);
+            samp = rec[2 * D];
+        }
+    }
     for (int k = 0; k < nsteps; ++k) {
         if (act) su[t] = u;
         __syncthreads();
@@ -411,7 +423,7 @@ __global__ __launch_bounds__(NT) void k_sample_block(Dev P, const float* __restr
         const float2 y = make_float2(u.x + q.x + s * v.x, u.y + q.y + s * v.y);
         const float n = block_sum<NT>(act ? (y.x * y.x + y.y * y.y) : 0.f, red);
         const float inv = 1.0f / sqrtf(fmaxf(n, 1e-12f));                                  // :289
-        if (act) u = cmul(P.rho[(size_t)k * DP + t], cscale(inv, y));
+        if (act) u = cmul(P.rho[(size_t)(STREAM ? ST.k0 + k : k) * DP + t], cscale(inv, y));
         if constexpr (PRIMED) {
             if (t == 0) {
                 if (!forced) out[(size_t)b * length + (k - PF)] = dev_A(P) * samp;
@@ -421,6 +433,13 @@ __global__ __launch_bounds__(NT) void k_sample_block(Dev P, const float* __restr
             if (t == 0) out[(size_t)b * length + k] = dev_A(P) * samp;                          // :251
         }
         __syncthreads();
+    }
+    if constexpr (STREAM) {
+        if (ST.out) {
+            float* rec = ST.out + (size_t)b * ST.rec;
+            if (act) { rec[2 * t] = u.x; rec[2 * t + 1] = u.y; }
+            if (t == 0) rec[2 * D] = samp;
+        }
     }
 }
 
@@ -483,7 +502,8 @@ hipError_t launch_sample_block(const Dev& P, const float* noise, int n, int leng
     const size_t shm = (size_t)P.D * sizeof(float2) + 64;
     return dispatch_block_nt(P.D, [&](auto nt) {
         constexpr int NT = decltype(nt)::value;
-        hipLaunchKernelGGL((k_sample_block<NT, false>), dim3(n), dim3(NT), shm, s, P, noise, length, out, (const float*)nullptr, 0, 0, (float*)nullptr);
+        hipLaunchKernelGGL((k_sample_block<NT, false>), dim3(n), dim3(NT), shm, s, P, noise, length, out, (const float*)nullptr, 0, 0, (float*)nullptr,
+                           StreamDev{});
         return hipGetLastError();
     });
 }
@@ -493,7 +513,17 @@ hipError_t launch_sample_block_primed(const Dev& P, const float* prime, int prim
     const size_t shm = (size_t)P.D * sizeof(float2) + 64;
     return dispatch_block_nt(P.D, [&](auto nt) {
         constexpr int NT = decltype(nt)::value;
-        hipLaunchKernelGGL((k_sample_block<NT, true>), dim3(n), dim3(NT), shm, s, P, noise, length, out, prime, prime_stride, PF, pred);
+        hipLaunchKernelGGL((k_sample_block<NT, true>), dim3(n), dim3(NT), shm, s, P, noise, length, out, prime, prime_stride, PF, pred, StreamDev{});
+        return hipGetLastError();
+    });
+}
+
+hipError_t launch_sample_block_stream(const Dev& P, const StreamDev& ST, const float* audio, int audio_stride, int PF, const float* noise, int n,
+                                      int length, float* out, float* pred, hipStream_t s) {
+    const size_t shm = (size_t)P.D * sizeof(float2) + 64;
+    return dispatch_block_nt(P.D, [&](auto nt) {
+        constexpr int NT = decltype(nt)::value;
+        hipLaunchKernelGGL((k_sample_block<NT, true, true>), dim3(n), dim3(NT), shm, s, P, noise, length, out, audio, audio_stride, PF, pred, ST);
         return hipGetLastError();
     });
 }

@@ -514,6 +514,54 @@ int cmps_psi_states(cmps_handle_t h, int B, int T, float* psi_out_dev, void* str
     return CMPS_OK;
 }
 
+// What cmps_psi_sample, cmps_psi_sample_primed and cmps_psi_stream share behind their own argument checks.
+// One row of the per-step tables per step, forced or sampled: the rows below `end` must exist (`what` names end + 1 in the caller's terms)
+static int psi_check_rows(cmps_handle_t h, const char* who, const char* what, long long end) {
+    if (end <= h->L.N) return CMPS_OK;
+    char buf[240];
+    snprintf(buf, sizeof buf, "%s: %s = %lld exceeds T = %d of cmps_set_params (the per-step tables): needs T >= %lld", who, what, end + 1,
+             h->L.T, end + 1);
+    return fail(h, CMPS_ERR_BAD_ARG, buf);
+}
+// a clip per path, or one clip shared by every path
+static int psi_check_clips(cmps_handle_t h, const char* who, const char* name, int n_clips, int n) {
+    if (n_clips == 1 || n_clips == n) return CMPS_OK;
+    return fail(h, CMPS_ERR_BAD_ARG, std::string(who) + ": " + name + " must be n, or 1 for one clip shared by every path");
+}
+// floats of one stream-state record of the handle's sampler family
+static int stream_rec_floats(const cmps_handle_s* h) {
+    const int family = sampler_family(h);
+    return family == SAMPLER_WAVE ? STREAM_REC_WAVE : family == SAMPLER_WIDE ? stream_rec_wide(padded_D(h->D)) : stream_rec_block(h->D);
+}
+// The kernel choice and the launch.  clips == nullptr and ST == nullptr: the unprimed sampler; ST == nullptr: the primed one (`forced`
+// teacher-forced steps on clips[path * clip_stride + k]); else one segment of a stream.
+static int psi_sample_launch(cmps_handle_t h, const char* who, const float* clips, int clip_stride, int forced, const float* noise_dev, int n,
+                      int length, float* out_dev, float* pred_dev, const StreamDev* ST, void* stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int family = sampler_family(h);
+    static const char* const names[3][3] = {{"k_sample_block", "k_sample_block_primed", "k_sample_block_stream"},
+                                            {"k_sample_wave", "k_sample_wave_primed", "k_sample_wave_stream"},
+                                            {"k_sample_wide", "k_sample_wide_primed", "k_sample_wide_stream"}};
+    const int mode = ST ? 2 : clips ? 1 : 0;
+    KBind kb(h);
+    KScope ks(names[family][mode], s);
+    hipError_t e;
+    if (mode == 0)
+        e = family == SAMPLER_WAVE ? launch_sample_wave(h->P, noise_dev, n, length, out_dev, s)
+          : family == SAMPLER_WIDE ? launch_sample_wide(h->P, noise_dev, n, length, out_dev, s)
+                                   : launch_sample_block(h->P, noise_dev, n, length, out_dev, s);
+    else if (mode == 1)
+        e = family == SAMPLER_WAVE ? launch_sample_wave_primed(h->P, clips, clip_stride, forced, noise_dev, n, length, out_dev, pred_dev, s)
+          : family == SAMPLER_WIDE ? launch_sample_wide_primed(h->P, clips, clip_stride, forced, noise_dev, n, length, out_dev, pred_dev, s)
+                                   : launch_sample_block_primed(h->P, clips, clip_stride, forced, noise_dev, n, length, out_dev, pred_dev, s);
+    else
+        e = family == SAMPLER_WAVE ? launch_sample_wave_stream(h->P, *ST, clips, clip_stride, forced, noise_dev, n, length, out_dev, pred_dev, s)
+          : family == SAMPLER_WIDE ? launch_sample_wide_stream(h->P, *ST, clips, clip_stride, forced, noise_dev, n, length, out_dev, pred_dev, s)
+                                   : launch_sample_block_stream(h->P, *ST, clips, clip_stride, forced, noise_dev, n, length, out_dev, pred_dev, s);
+    if (e != hipSuccess) return fail_hip(h, e, who);
+    return CMPS_OK;
+}
+
 int cmps_psi_sample(cmps_handle_t h, const float* noise_dev, int n, int length, float* out_dev, void* stream) {
     if (!h) return CMPS_ERR_BAD_ARG;
     if (!h->params_set) return fail(h, CMPS_ERR_STATE, "cmps_psi_sample: call cmps_set_params first");
@@ -521,15 +569,7 @@ int cmps_psi_sample(cmps_handle_t h, const float* noise_dev, int n, int length, 
         return fail(h, CMPS_ERR_BAD_ARG, "cmps_psi_sample: bad argument");
     if (length > h->L.N)
         return fail(h, CMPS_ERR_BAD_ARG, "cmps_psi_sample: length exceeds T - 1 of cmps_set_params (the per-step tables)");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int family = sampler_family(h);
-    KBind kb(h);
-    KScope ks(family == SAMPLER_WAVE ? "k_sample_wave" : family == SAMPLER_WIDE ? "k_sample_wide" : "k_sample_block", s);
-    hipError_t e = family == SAMPLER_WAVE ? launch_sample_wave(h->P, noise_dev, n, length, out_dev, s)
-                 : family == SAMPLER_WIDE ? launch_sample_wide(h->P, noise_dev, n, length, out_dev, s)
-                                          : launch_sample_block(h->P, noise_dev, n, length, out_dev, s);
-    if (e != hipSuccess) return fail_hip(h, e, "cmps_psi_sample");
-    return CMPS_OK;
+    return psi_sample_launch(h, "cmps_psi_sample", nullptr, 0, 0, noise_dev, n, length, out_dev, nullptr, nullptr, stream);
 }
 
 int cmps_psi_sample_primed(cmps_handle_t h, const float* prime_dev, int n_prime, int prime_T, const float* noise_dev, int n, int length,
@@ -540,25 +580,34 @@ int cmps_psi_sample_primed(cmps_handle_t h, const float* prime_dev, int n_prime,
     if (!prime_dev || !noise_dev || !out_dev) return fail(h, CMPS_ERR_BAD_ARG, "cmps_psi_sample_primed: null pointer");
     if (n < 1 || length < 1) return fail(h, CMPS_ERR_BAD_ARG, "cmps_psi_sample_primed: need n >= 1 and length >= 1");
     if (prime_T < 2) return fail(h, CMPS_ERR_BAD_ARG, "cmps_psi_sample_primed: need prime_T >= 2 (one increment at least)");
-    if (n_prime != 1 && n_prime != n)
-        return fail(h, CMPS_ERR_BAD_ARG, "cmps_psi_sample_primed: n_prime must be n, or 1 for one clip shared by every path");
+    if (int c = psi_check_clips(h, "cmps_psi_sample_primed", "n_prime", n_prime, n)) return c;
     const int PF = prime_T - 1;                                  // teacher-forced steps
-    if ((long long)PF + length > h->L.N) {                        // one table row per step, forced or sampled
-        char buf[200];
-        snprintf(buf, sizeof buf, "cmps_psi_sample_primed: prime_T + length = %lld exceeds T = %d of cmps_set_params (the per-step tables): "
-                 "needs T >= %lld", (long long)prime_T + length, h->L.T, (long long)prime_T + length);
-        return fail(h, CMPS_ERR_BAD_ARG, buf);
-    }
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int family = sampler_family(h);                         // exactly cmps_psi_sample's choice
-    const int stride = n_prime == 1 ? 0 : prime_T;
-    KBind kb(h);
-    KScope ks(family == SAMPLER_WAVE ? "k_sample_wave_primed" : family == SAMPLER_WIDE ? "k_sample_wide_primed" : "k_sample_block_primed", s);
-    hipError_t e = family == SAMPLER_WAVE ? launch_sample_wave_primed(h->P, prime_dev, stride, PF, noise_dev, n, length, out_dev, pred_dev, s)
-                 : family == SAMPLER_WIDE ? launch_sample_wide_primed(h->P, prime_dev, stride, PF, noise_dev, n, length, out_dev, pred_dev, s)
-                                          : launch_sample_block_primed(h->P, prime_dev, stride, PF, noise_dev, n, length, out_dev, pred_dev, s);
-    if (e != hipSuccess) return fail_hip(h, e, "cmps_psi_sample_primed");
-    return CMPS_OK;
+    if (int c = psi_check_rows(h, "cmps_psi_sample_primed", "prime_T + length", (long long)PF + length)) return c;
+    return psi_sample_launch(h, "cmps_psi_sample_primed", prime_dev, n_prime == 1 ? 0 : prime_T, PF, noise_dev, n, length, out_dev, pred_dev,
+                             nullptr, stream);
+}
+
+size_t cmps_psi_stream_state_bytes(cmps_handle_t h, int n) {
+    if (!h || n < 1) return 0;
+    return (size_t)n * stream_rec_floats(h) * sizeof(float);
+}
+
+int cmps_psi_stream(cmps_handle_t h, const void* state_in_dev, void* state_out_dev, int k0, const float* audio_dev, int n_audio, int forced,
+                    const float* noise_dev, int length, int n, float* out_dev, float* pred_dev, void* stream) {
+    if (!h) return CMPS_ERR_BAD_ARG;
+    if (!h->params_set || h->legacy)
+        return fail(h, CMPS_ERR_STATE, "cmps_psi_stream: call cmps_set_params first (not available in legacy mode)");
+    if (n < 1 || forced < 0 || length < 0 || (long long)forced + length < 1 || k0 < 0)
+        return fail(h, CMPS_ERR_BAD_ARG, "cmps_psi_stream: need n >= 1, forced >= 0, length >= 0, forced + length >= 1 and k0 >= 0");
+    if ((state_in_dev == nullptr) != (k0 == 0))
+        return fail(h, CMPS_ERR_BAD_ARG, "cmps_psi_stream: state_in_dev is NULL exactly at the start of a stream (k0 == 0)");
+    if (forced > 0 && !audio_dev) return fail(h, CMPS_ERR_BAD_ARG, "cmps_psi_stream: forced > 0 needs audio_dev");
+    if (length > 0 && (!noise_dev || !out_dev)) return fail(h, CMPS_ERR_BAD_ARG, "cmps_psi_stream: length > 0 needs noise_dev and out_dev");
+    if (int c = psi_check_clips(h, "cmps_psi_stream", "n_audio", n_audio, n)) return c;
+    if (int c = psi_check_rows(h, "cmps_psi_stream", "k0 + forced + length + 1", (long long)k0 + forced + length)) return c;
+    const StreamDev ST{static_cast<const float*>(state_in_dev), static_cast<float*>(state_out_dev), k0, stream_rec_floats(h)};
+    return psi_sample_launch(h, "cmps_psi_stream", audio_dev, n_audio == 1 ? 0 : forced + 1, forced, noise_dev, n, length, out_dev, pred_dev,
+                             &ST, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------

@@ -404,6 +404,26 @@ hipError_t launch_sample_wide_primed(const Dev& P, const float* prime, int prime
                                      float* out, float* pred, hipStream_t s);
 hipError_t launch_sample_block_primed(const Dev& P, const float* prime, int prime_stride, int PF, const float* noise, int n, int length,
                                       float* out, float* pred, hipStream_t s);
+// cmps_psi_stream: one segment of a resumable scan.  The primed arguments with PF = forced (either count may be 0, not both), on table
+// rows k0 .. k0 + PF + length - 1; the state a kernel carries from one step into the next is read from `in` (null: the start of a scan,
+// psi_0) and written to `out` (null: not kept), `rec` floats per path.  in == out is allowed: a path reads its record before it writes it.
+struct StreamDev {
+    const float* in;
+    float* out;
+    int k0;
+    int rec;
+};
+// floats of one path's record, a multiple of 4: wave u, |y|^2 partial per lane, running sum | wide ut [2 DP], |y|^2 partial per wave
+// [DP / 16], running sum | block u [2 D], running sum
+constexpr int STREAM_REC_WAVE = 132;
+inline int stream_rec_wide(int DP) { return (2 * DP + DP / 16 + 1 + 3) / 4 * 4; }
+inline int stream_rec_block(int D) { return (2 * D + 1 + 3) / 4 * 4; }
+hipError_t launch_sample_wave_stream(const Dev& P, const StreamDev& ST, const float* audio, int audio_stride, int PF, const float* noise, int n,
+                                     int length, float* out, float* pred, hipStream_t s);
+hipError_t launch_sample_wide_stream(const Dev& P, const StreamDev& ST, const float* audio, int audio_stride, int PF, const float* noise, int n,
+                                     int length, float* out, float* pred, hipStream_t s);
+hipError_t launch_sample_block_stream(const Dev& P, const StreamDev& ST, const float* audio, int audio_stride, int PF, const float* noise, int n,
+                                      int length, float* out, float* pred, hipStream_t s);
 
 size_t apply_step_scratch_bytes(int D);
 hipError_t launch_apply_step(int D, bool apply, double inv_batch, double lr_t, double beta1, double beta2, double eps, double h_reg,

@@ -662,10 +662,16 @@ __device__ __forceinline__ void mv2r_hi(const v2f (&MA)[16], const v2f (&MB)[16]
 // value per lane (step): the prime difference below PF, the noise from PF on, so the step itself only adds a wave-uniform compare.
 // The unprimed instance (cmps_psi_sample) ignores its last four arguments and is the kernel as it was
 // (profiles/primed_sampler_isa_identity.log).
-template <bool PRIMED>
+// STREAM (cmps_psi_stream): the primed scan as one segment of a longer one -- PF or length may be 0, the steps run on table rows ST.k0 ..,
+// and what the loop carries from one step into the next (per lane u and the |y|^2 partial xsq, and the running sum) is loaded from the
+// path's record when ST.in is set and stored to it behind the last step when ST.out is.  The record holds the carried values themselves and
+// the chunks are staged from the segment's first row, so where a run is cut changes no bit of it.  The other instances ignore ST and are
+// the kernels they were (profiles/stream_sampler_isa_identity.log).
+template <bool PRIMED, bool STREAM = false>
 __global__ __launch_bounds__(64 * WAVES, 1) void k_sample_wave(Dev P, const float* __restrict__ noise, int n_paths, int length,
                                                                float* __restrict__ out, const float* __restrict__ prime,
-                                                               int prime_stride, int PF, float* __restrict__ pred) {
+                                                               int prime_stride, int PF, float* __restrict__ pred, StreamDev ST) {
+    static_assert(PRIMED || !STREAM, "a stream segment is a primed scan");
     __shared__ __attribute__((aligned(16))) float4 stR[WAVES][CH * 16];
     __shared__ __attribute__((aligned(16))) float2 bcU[WAVES][DPW];
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -692,12 +698,20 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_sample_wave(Dev P, const floa
     float u = hb ? p0.y : p0.x;
     float xsq = lane == 0 ? 1.f : 0.f;                   // "|y_{-1}|^2" = 1: psi_0 arrives normalised
     float samp = 0.f;                                    // model.py:244 batch_zeros
+    if constexpr (STREAM) {
+        if (ST.in) {                                     // resume: the values the loop below left behind the previous segment's last step
+            const float* rec = ST.in + (size_t)b * ST.rec;
+            u = rec[lane];
+            xsq = rec[64 + lane];
+            samp = rec[128];
+        }
+    }
     v4f sr[16], qu[8];
     v2f rho;
     for (int c = 0; c < NC; ++c) {
         const int kbeg = c * CH;
         const int cnt = (N - kbeg) < CH ? (N - kbeg) : CH;
-        stage_load<16>(rho4, kbeg, P.N, lane, sr);
+        stage_load<16>(rho4, STREAM ? ST.k0 + kbeg : kbeg, P.N, lane, sr);       // (kbeg, k below: steps of this launch; table rows from k0)
         float given;                                     // what this lane's step is handed: its noise, or (PRIMED, below PF) the clip's increment
         if constexpr (PRIMED) {
             const int k = kbeg + lane;
@@ -747,18 +761,34 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_sample_wave(Dev P, const floa
             if (lane < cnt) orow[kbeg + lane] = A * svec;            // model.py:251
         }
     }
+    if constexpr (STREAM) {
+        if (ST.out) {
+            float* rec = ST.out + (size_t)b * ST.rec;
+            rec[lane] = u;
+            rec[64 + lane] = xsq;
+            if (lane == 0) rec[128] = samp;
+        }
+    }
 }
 
 hipError_t launch_sample_wave(const Dev& P, const float* noise, int n, int length, float* out, hipStream_t s) {
     const unsigned nb = (unsigned)((n + WAVES - 1) / WAVES);
-    hipLaunchKernelGGL(k_sample_wave<false>, dim3(nb), dim3(64 * WAVES), 0, s, P, noise, n, length, out, (const float*)nullptr, 0, 0, (float*)nullptr);
+    hipLaunchKernelGGL(k_sample_wave<false>, dim3(nb), dim3(64 * WAVES), 0, s, P, noise, n, length, out, (const float*)nullptr, 0, 0, (float*)nullptr,
+                       StreamDev{});
     return hipGetLastError();
 }
 
 hipError_t launch_sample_wave_primed(const Dev& P, const float* prime, int prime_stride, int PF, const float* noise, int n, int length,
                                      float* out, float* pred, hipStream_t s) {
     const unsigned nb = (unsigned)((n + WAVES - 1) / WAVES);
-    hipLaunchKernelGGL(k_sample_wave<true>, dim3(nb), dim3(64 * WAVES), 0, s, P, noise, n, length, out, prime, prime_stride, PF, pred);
+    hipLaunchKernelGGL(k_sample_wave<true>, dim3(nb), dim3(64 * WAVES), 0, s, P, noise, n, length, out, prime, prime_stride, PF, pred, StreamDev{});
+    return hipGetLastError();
+}
+
+hipError_t launch_sample_wave_stream(const Dev& P, const StreamDev& ST, const float* audio, int audio_stride, int PF, const float* noise, int n,
+                                     int length, float* out, float* pred, hipStream_t s) {
+    const unsigned nb = (unsigned)((n + WAVES - 1) / WAVES);
+    hipLaunchKernelGGL((k_sample_wave<true, true>), dim3(nb), dim3(64 * WAVES), 0, s, P, noise, n, length, out, audio, audio_stride, PF, pred, ST);
     return hipGetLastError();
 }
 

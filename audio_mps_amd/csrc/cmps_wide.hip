@@ -549,10 +549,17 @@ __global__ void k_rho_phi_reduce(const float* __restrict__ gphi, int B, int vran
 // per-lane "given" value of a 64-step chunk is built at chunk load (the difference below PF, the noise from PF on), so a step only adds
 // the uniform compare k < PF.  The unprimed instance (cmps_psi_sample) ignores its last four arguments and is the kernel as it was
 // (profiles/primed_sampler_isa_identity.log).
-template <int PD, bool PRIMED>
+// STREAM (cmps_psi_stream): the primed scan as one segment of a longer one -- PF or length may be 0, step k of the launch runs on table
+// row ST.k0 + k.  With ST.in the launch enters its first step as the unsplit loop would enter step k0: the lane's ut (also into the
+// broadcast vector), the NW partial sums of |y|^2 into the nrm slot that step reads, the running sum, rho_next of row k0; behind the last
+// step the same values go to ST.out (the ping-pong parity is the launch's own: the slot only names where the values sit).  The record
+// holds the carried values themselves, so where a run is cut changes no bit of it.  An odd count's repeated last path stores nothing.
+// The other instances ignore ST and are the kernels they were (profiles/stream_sampler_isa_identity.log).
+template <int PD, bool PRIMED, bool STREAM = false>
 __global__ __launch_bounds__(4 * PD) void k_sample_wide(Dev P, const float* __restrict__ noise, int n_paths, int length,
                                                         float* __restrict__ out, const float* __restrict__ prime, int prime_stride,
-                                                        int PF, float* __restrict__ pred) {
+                                                        int PF, float* __restrict__ pred, StreamDev ST) {
+    static_assert(PRIMED || !STREAM, "a stream segment is a primed scan");
     using G = WideGeom<PD>;
     constexpr int NW = G::NW, KC = G::KC, VSL = G::VSL, VEC4 = G::VEC4;
     __shared__ __attribute__((aligned(16))) v4f uvec[2 * VEC4];
@@ -594,6 +601,19 @@ __global__ __launch_bounds__(4 * PD) void k_sample_wide(Dev P, const float* __re
     float gv0 = 0.f, gv1 = 0.f;                                   // what the current 64 steps are handed, lane <-> step: noise (PRIMED, below PF: the clip's increments)
     float samp = 0.f;                                             // model.py:244 batch_zeros (this lane's path)
     float2 rho_next = P.rho[row];
+    [[maybe_unused]] bool resumed = false;                        // STREAM: the launch continues a scan (uniform)
+    [[maybe_unused]] float nn_last = 0.f;                         // STREAM: the partial sum of |y|^2 the last step handed on
+    if constexpr (STREAM) {
+        rho_next = P.rho[(size_t)ST.k0 * PD + row];
+        resumed = ST.in != nullptr;
+        if (resumed) {
+            const float* rec = ST.in + (size_t)(clip1 ? b1 : b0) * ST.rec;
+            ut = rec[comp * PD + row];
+            reinterpret_cast<float*>(uvec)[own_f] = ut;
+            if (i == 0 && q < 2) nrm[w * 2 + clip] = rec[2 * PD + w];
+            samp = rec[2 * PD + NW];
+        }
+    }
     __syncthreads();
 
     for (int k = 0; k < nsteps; ++k) {
@@ -609,9 +629,13 @@ __global__ __launch_bounds__(4 * PD) void k_sample_wide(Dev P, const float* __re
             }
         }
         const float2 rho_k = rho_next;
-        if (k + 1 < P.N) rho_next = P.rho[(size_t)(k + 1) * PD + row];
+        if constexpr (STREAM) {                                   // (k: step of this launch; table row ST.k0 + k)
+            if (ST.k0 + k + 1 < P.N) rho_next = P.rho[(size_t)(ST.k0 + k + 1) * PD + row];
+        } else {
+            if (k + 1 < P.N) rho_next = P.rho[(size_t)(k + 1) * PD + row];
+        }
         float n0 = 1.f, n1 = 1.f;
-        if (k >= 1) {
+        if (k >= 1 || resumed) {                                  // (the first step of a scan takes psi_0 as it is: "|y_{-1}|^2" = 1)
             n0 = n1 = 0.f;
 #pragma unroll
             for (int ww = 0; ww < NW; ++ww) {
@@ -619,7 +643,7 @@ __global__ __launch_bounds__(4 * PD) void k_sample_wide(Dev P, const float* __re
                 n0 += t.x; n1 += t.y;
             }
         }
-        const float inv = k >= 1 ? rsq_newton(fmaxf(clip1 ? n1 : n0, 1e-12f)) : 1.f;      // model.py:289 of the step before
+        const float inv = (k >= 1 || resumed) ? rsq_newton(fmaxf(clip1 ? n1 : n0, 1e-12f)) : 1.f;      // model.py:289 of the step before
         v2f rRe0 = mk2(0.f, 0.f), rIm0 = rRe0, rRe1 = rRe0, rIm1 = rRe0;
         v2f qRe0 = rRe0, qIm0 = rRe0, qRe1 = rRe0, qIm1 = rRe0;
         const v4f* uv = uvec + p * VEC4 + rd4;
@@ -654,6 +678,7 @@ __global__ __launch_bounds__(4 * PD) void k_sample_wide(Dev P, const float* __re
         const float y = inv * (ut + (qs + s * vs));
         const float nn = clip_wave_sum(y * y);
         if (i == 0 && q < 2) nrm[((p ^ 1) * NW + w) * 2 + clip] = nn;
+        if constexpr (STREAM) nn_last = nn;
         const float py = partner16(y, im_lane);
         ut = rho_k.x * y + (im_lane ? rho_k.y : -rho_k.y) * py;   // rho_k y_k, normalised in the next step
         reinterpret_cast<float*>(uvec + (p ^ 1) * VEC4)[own_f] = ut;
@@ -666,6 +691,14 @@ __global__ __launch_bounds__(4 * PD) void k_sample_wide(Dev P, const float* __re
             if (writer) orow[k] = A * samp;                       // model.py:251
         }
         wide_barrier();
+    }
+    if constexpr (STREAM) {
+        if (ST.out && (!clip1 || two)) {
+            float* rec = ST.out + (size_t)(clip1 ? b1 : b0) * ST.rec;
+            rec[comp * PD + row] = ut;
+            if (i == 0 && q < 2) rec[2 * PD + w] = nn_last;
+            if (writer) rec[2 * PD + NW] = samp;
+        }
     }
 }
 
@@ -1330,7 +1363,8 @@ hipError_t launch_sample_wide(const Dev& P, const float* noise, int n, int lengt
     const unsigned nb = (unsigned)((n + 1) / 2);
     return dispatch_pd(P.DP, [&](auto pd) {
         constexpr int PD = decltype(pd)::value;
-        hipLaunchKernelGGL((k_sample_wide<PD, false>), dim3(nb), dim3(4 * PD), 0, s, P, noise, n, length, out, (const float*)nullptr, 0, 0, (float*)nullptr);
+        hipLaunchKernelGGL((k_sample_wide<PD, false>), dim3(nb), dim3(4 * PD), 0, s, P, noise, n, length, out, (const float*)nullptr, 0, 0, (float*)nullptr,
+                           StreamDev{});
         return hipGetLastError();
     });
 }
@@ -1340,7 +1374,17 @@ hipError_t launch_sample_wide_primed(const Dev& P, const float* prime, int prime
     const unsigned nb = (unsigned)((n + 1) / 2);
     return dispatch_pd(P.DP, [&](auto pd) {
         constexpr int PD = decltype(pd)::value;
-        hipLaunchKernelGGL((k_sample_wide<PD, true>), dim3(nb), dim3(4 * PD), 0, s, P, noise, n, length, out, prime, prime_stride, PF, pred);
+        hipLaunchKernelGGL((k_sample_wide<PD, true>), dim3(nb), dim3(4 * PD), 0, s, P, noise, n, length, out, prime, prime_stride, PF, pred, StreamDev{});
+        return hipGetLastError();
+    });
+}
+
+hipError_t launch_sample_wide_stream(const Dev& P, const StreamDev& ST, const float* audio, int audio_stride, int PF, const float* noise, int n,
+                                     int length, float* out, float* pred, hipStream_t s) {
+    const unsigned nb = (unsigned)((n + 1) / 2);
+    return dispatch_pd(P.DP, [&](auto pd) {
+        constexpr int PD = decltype(pd)::value;
+        hipLaunchKernelGGL((k_sample_wide<PD, true, true>), dim3(nb), dim3(4 * PD), 0, s, P, noise, n, length, out, audio, audio_stride, PF, pred, ST);
         return hipGetLastError();
     });
 }

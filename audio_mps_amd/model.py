@@ -423,6 +423,14 @@ class PsiCMPS(CMPS):
     def _sample_primed(self, be, prime, noise, want_pred):
         return be.sample_primed(prime, noise, want_pred=want_pred)
 
+    def open_stream(self, num_paths, max_steps, temp=1, seed=None):
+        """A resumable sampler of ``num_paths`` paths (no reference counterpart; audio_mps_amd/stream.py, cmps_psi_stream): follow an
+        incoming signal block by block, generate in segments, or alternate.  Prepares the backend once with T = max_steps + 1 -- the
+        only sizing decision, 8 DP bytes of phase table per step; running past ``max_steps`` raises ValueError.  The model's variables
+        are read here: a stream keeps the parameters it was opened with."""
+        from .stream import SampleStream
+        return SampleStream(self, num_paths, max_steps, temp=temp, seed=seed)
+
 
 # --------------------------------------------------------------------------------------------------
 class RhoCMPS(CMPS):

@@ -1,0 +1,115 @@
+"""A resumable PsiCMPS sampler: follow an incoming signal and generate audio in segments (cmps_psi_stream).
+
+The reference samples a whole waveform in one tf.scan (model.py:242-251) and has nothing that carries on.  A ``SampleStream`` keeps what
+the sampler kernel carries between two steps on the device, so a scan can be continued, can alternate between teacher-forced blocks
+(``follow``) and sampled ones (``generate``), and can follow only.  Cutting a run into segments changes no bit of it.
+
+    st = model.open_stream(num_paths=4, max_steps=3 * 16000, seed=0)
+    pred = st.follow(block)             # [4, steps]: the model's expected increment before every followed sample
+    wave = st.generate(16000)           # [4, 16000] in the clip's own units, continuing the followed signal
+    wave2 = st.generate(16000)          # ... and on from there
+"""
+from __future__ import annotations
+
+import math
+
+import numpy as np
+
+
+class SampleStream:
+    """Returned by ``PsiCMPS.open_stream``.  ``position`` is the number of steps taken (the next table row), ``max_steps`` the number the
+    stream was sized for, ``last`` the last sample per path [num_paths] (None while the stream has seen no audio and generated nothing)."""
+
+    def __init__(self, model, num_paths: int, max_steps: int, temp=1, seed=None):
+        if num_paths < 1 or max_steps < 1:
+            raise ValueError("open_stream needs num_paths >= 1 and max_steps >= 1")
+        self.num_paths, self.max_steps = int(num_paths), int(max_steps)
+        self.position = 0
+        self.last = None
+        self._A = np.float32(model.A)
+        self._std = float(model.sigma) * math.sqrt(temp * float(model.delta_t))      # CMPS._noise
+        self._rng = np.random.default_rng(seed)
+        self._be = model._prepare(self.num_paths, self.max_steps + 1, train=False)    # T = max_steps + 1: one table row per step
+        self._state = self._be.stream_state(self.num_paths)
+        self._level = None             # inside a sampled run: the level it began at
+
+    # ------------------------------------------------------------------
+    def _launch(self, steps, audio, noise, want_pred):
+        if self.position + steps > self.max_steps:
+            raise ValueError(f"the stream was opened for max_steps={self.max_steps}: {self.position} taken, {steps} more asked for")
+        out, pred = self._be.stream(self._state if self.position else None, self._state, self.position, audio, noise, want_pred,
+                                    n=self.num_paths)
+        self.position += steps
+        return out, pred
+
+    def _block(self, block) -> np.ndarray:
+        if hasattr(block, "detach"):
+            block = block.detach().cpu().numpy()
+        block = np.asarray(block, dtype=np.float32)
+        if block.ndim == 1:
+            block = block[None, :]
+        if block.ndim != 2 or block.shape[0] not in (1, self.num_paths) or block.shape[1] < 1:
+            raise ValueError(f"a block must be [m], [1, m] or [{self.num_paths}, m] with m >= 1, not {block.shape}")
+        return block
+
+    def follow(self, block, anchor: bool = False) -> np.ndarray:
+        """Teacher-force the stream on ``block`` ([num_paths, m], or [m] / [1, m] for one signal shared by every path; the clip's own
+        units).  On a stream that has seen no audio the block's first sample is the anchor X_0 and makes no step; later blocks make one
+        step per sample, the first one from the stream's last sample.  ``anchor=True`` re-anchors on ``block[..., 0]`` without a step
+        (to resume behind a generated gap without showing the model the jump).  Returns the model's expected increment before every
+        step, [num_paths, steps]."""
+        block = self._block(block)
+        n = self.num_paths
+        if anchor or self.last is None:
+            audio = block
+        elif block.shape[0] == 1 and np.all(self.last == self.last[0]):
+            audio = np.concatenate([self.last[:1, None], block], axis=1)
+        else:
+            audio = np.concatenate([self.last[:, None], np.broadcast_to(block, (n, block.shape[1]))], axis=1)
+        steps = audio.shape[1] - 1
+        pred = np.empty((n, 0), dtype=np.float32)
+        if steps:
+            _, pred = self._launch(steps, np.ascontiguousarray(audio), None, True)
+        self.last = np.array(np.broadcast_to(block[:, -1], (n,)), dtype=np.float32)
+        self._level = None
+        return pred
+
+    def generate(self, length: int, noise=None) -> np.ndarray:
+        """Sample ``length`` steps: [num_paths, length] in the clip's own units = the level when the sampled run began (0 on a fresh
+        stream, model.py:244; else the last followed sample) + the running sum of the sampled increments, which the kernel state
+        carries, so consecutive calls continue one waveform.  The noise [length, num_paths] comes from the stream's own Generator
+        (stddev sigma sqrt(temp delta_t), as CMPS._noise), or is passed in."""
+        length, n = int(length), self.num_paths
+        if length < 1:
+            raise ValueError("generate needs length >= 1")
+        if self.position + length > self.max_steps:                  # (before the draw: a refused call leaves the Generator alone)
+            raise ValueError(f"the stream was opened for max_steps={self.max_steps}: {self.position} taken, {length} more asked for")
+        if noise is None:
+            noise = (self._std * self._rng.standard_normal((length, n))).astype(np.float32)
+        noise = np.asarray(noise, dtype=np.float32)
+        if noise.shape != (length, n):
+            raise ValueError(f"noise must be [{length}, {n}]")
+        if self._level is None:
+            self._level = np.zeros(n, dtype=np.float32) if self.last is None else self.last.copy()
+        out, _ = self._launch(length, None, noise, False)
+        wave = (self._level[:, None] + out / self._A).astype(np.float32)
+        self.last = wave[:, -1].copy()
+        return wave
+
+    def fill_gaps(self, clip, known) -> np.ndarray:
+        """``clip`` [T] or [num_paths, T] with a boolean mask ``known`` [T]: runs of True are followed, runs of False generated, and each
+        known run behind a gap is re-anchored on its first sample.  Returns [num_paths, T]: the clip where it is known, the model's
+        waveform in the gaps."""
+        clip = self._block(clip)
+        known = np.asarray(known, dtype=bool)
+        if known.shape != (clip.shape[1],):
+            raise ValueError(f"known must be a boolean mask [{clip.shape[1]}]")
+        T, n = clip.shape[1], self.num_paths
+        wave = np.array(np.broadcast_to(clip, (n, T)), dtype=np.float32)
+        edges = [0] + [k for k in range(1, T) if known[k] != known[k - 1]] + [T]
+        for a, b in zip(edges[:-1], edges[1:]):
+            if known[a]:
+                self.follow(clip[:, a:b], anchor=a > 0)
+            else:
+                wave[:, a:b] = self.generate(b - a)
+        return wave

@@ -84,7 +84,7 @@ enum {
     CMPS_OPT_F16_SCALE_SHIFT = 4 /* DIAGNOSTIC, default 0: added to the exponent of every data-dependent fp16 scale of the wave reverse
                         * scan's F16X2 arithmetic (range -40 .. 40).  A positive value pushes the pieces out of fp16 range on purpose:
                         * how tests/test_gpu_parity.py provokes CMPS_ERR_F16_RANGE.  No reference counterpart. */,
-    CMPS_OPT_KERNEL_EVENTS = 2 /* 1: every kernel cmps_psi_loss_fwd / _bwd, cmps_psi_sample, cmps_psi_sample_primed and cmps_rho_sample_primed launch is bracketed by two HIP events on the caller's stream
+    CMPS_OPT_KERNEL_EVENTS = 2 /* 1: every kernel cmps_psi_loss_fwd / _bwd, cmps_psi_sample, cmps_psi_sample_primed, cmps_psi_stream and cmps_rho_sample_primed launch is bracketed by two HIP events on the caller's stream
                         * (read and reset with cmps_kernel_times); 0 (default): nothing is recorded.  A measurement aid -- the reference
                         * has no counterpart (no tracing / profiling hooks); bench.py uses it OUTSIDE its timed region to price
                         * each kernel of a multi-kernel family against the pipe it runs on */
@@ -294,6 +294,40 @@ int cmps_psi_sample(cmps_handle_t h, const float* noise_dev, int n, int length, 
 int cmps_psi_sample_primed(cmps_handle_t h, const float* prime_dev, int n_prime, int prime_T,
                            const float* noise_dev, int n, int length,
                            float* out_dev, float* pred_dev, void* stream);
+
+/*
+ * One segment of a resumable PsiCMPS.sample scan: `forced` steps of _psi_update (model.py:269-274) on the increments of audio_dev, then
+ * `length` steps of _psi_and_sample_update (:284-291), on table rows k0 .. k0 + forced + length - 1.  Either count may be 0, not both.
+ * The reference has no such method; the steps are cmps_psi_sample_primed's, and what a sampler kernel carries from one step into the
+ * next leaves the kernel between two calls, so a scan can be carried on (another second behind what was generated, the next block of an
+ * incoming signal), can alternate between following and generating (filling a gap), and can follow only (length == 0).
+ *   forced step j < forced:  increment = audio[b'][j + 1] - audio[b'][j] in float32 (model.py:263), b' = b, or 0 when one signal is
+ *                            shared;  the running sum is reset to 0;  pred[b][j] = 2 Re<psi|R|psi> * delta_t before the step.
+ *   sampled step j >= forced: increment = expectation * delta_t + noise[b][j - forced];  the running sum continues (from state_in_dev's,
+ *                            0 at the start of a stream or behind a forced step);  out[b][j - forced] = A * running sum.
+ * audio_dev [n_audio * (forced + 1)] row-major, n_audio == n, or 1: shared.  audio_dev[b'][0] is the sample BEFORE the segment's first
+ * forced step: consecutive blocks of a signal overlap by one sample, so the subtraction of model.py:263 happens here as everywhere else.
+ * noise_dev [n * length], out_dev [n * length] row-major [path][step]; pred_dev [n * forced] or NULL.
+ * State: cmps_psi_stream_state_bytes(h, n) bytes of caller-owned device memory, n records (a multiple of 16 bytes; 0 for a null handle
+ * or n < 1).  A record is opaque and belongs to the handle's D and to the sampler kernel its variant resolves to (as cmps_psi_sample
+ * chooses it); it holds the carried values themselves, which makes a cut exact: a scan run as one call or in any number of segments
+ * gives the same bits in out, pred and the final record.
+ *   state_in_dev == NULL  <=>  k0 == 0: the start of a stream (psi_0, running sum 0); anything else is CMPS_ERR_BAD_ARG.
+ *   state_out_dev may be NULL (the last segment) and may equal state_in_dev (a path reads its record before it writes it).
+ * Parameters, T, variant and n are the caller's to keep fixed over a stream.  The exact split holds for tables built by equal
+ * cmps_set_params* calls; calling it again with the same arguments between two segments is allowed and changes nothing.  A different T
+ * moves the drift-corrected last row of the final 64-step chunk of the phase table, i.e. rounding only.
+ * CMPS_ERR_BAD_ARG: n < 1, forced < 0, length < 0, forced + length < 1, k0 < 0; audio_dev == NULL with forced > 0; noise_dev or out_dev
+ * == NULL with length > 0; n_audio not in {1, n}; k0 + forced + length > T - 1 of cmps_set_params*, with a message naming the needed
+ * T >= k0 + forced + length + 1.  CMPS_ERR_STATE before cmps_set_params and in legacy mode.
+ * Asynchronous on `stream`; never synchronises, allocates nothing.  With CMPS_OPT_KERNEL_EVENTS the launch is recorded as
+ * k_sample_wave_stream, k_sample_wide_stream or k_sample_block_stream.
+ */
+size_t cmps_psi_stream_state_bytes(cmps_handle_t h, int n);
+int cmps_psi_stream(cmps_handle_t h, const void* state_in_dev, void* state_out_dev, int k0,
+                    const float* audio_dev, int n_audio, int forced,
+                    const float* noise_dev, int length,
+                    int n, float* out_dev, float* pred_dev, void* stream);
 
 /*
  * Legacy `AudioMPS` arithmetic (the model training_estimators.py:43-45 was written for; its class body is gone from
