@@ -23,6 +23,7 @@ struct Saved {
     int layout = 0;                // the StashLayout (main workspace) / RhoStashLayout (rho workspace) that was written
     bool bwd_ok = false;           // rho: written by cmps_rho_loss_fwd (not by the sampler), a reverse pass may follow
     bool grad1 = false;            // rho: the GEMM forward accumulated RhoDev::p1
+    int k0 = 0;                    // rho: the table row of the first saved step (a cmps_rho_stream segment; else 0)
 };
 
 struct cmps_handle_s {
@@ -514,9 +515,10 @@ int cmps_psi_states(cmps_handle_t h, int B, int T, float* psi_out_dev, void* str
     return CMPS_OK;
 }
 
-// What cmps_psi_sample, cmps_psi_sample_primed and cmps_psi_stream share behind their own argument checks.
+// What cmps_psi_sample, cmps_psi_sample_primed and cmps_psi_stream share behind their own argument checks (the two checks also with
+// their RhoCMPS counterparts).
 // One row of the per-step tables per step, forced or sampled: the rows below `end` must exist (`what` names end + 1 in the caller's terms)
-static int psi_check_rows(cmps_handle_t h, const char* who, const char* what, long long end) {
+static int sample_check_rows(cmps_handle_t h, const char* who, const char* what, long long end) {
     if (end <= h->L.N) return CMPS_OK;
     char buf[240];
     snprintf(buf, sizeof buf, "%s: %s = %lld exceeds T = %d of cmps_set_params (the per-step tables): needs T >= %lld", who, what, end + 1,
@@ -524,7 +526,7 @@ static int psi_check_rows(cmps_handle_t h, const char* who, const char* what, lo
     return fail(h, CMPS_ERR_BAD_ARG, buf);
 }
 // a clip per path, or one clip shared by every path
-static int psi_check_clips(cmps_handle_t h, const char* who, const char* name, int n_clips, int n) {
+static int sample_check_clips(cmps_handle_t h, const char* who, const char* name, int n_clips, int n) {
     if (n_clips == 1 || n_clips == n) return CMPS_OK;
     return fail(h, CMPS_ERR_BAD_ARG, std::string(who) + ": " + name + " must be n, or 1 for one clip shared by every path");
 }
@@ -580,9 +582,9 @@ int cmps_psi_sample_primed(cmps_handle_t h, const float* prime_dev, int n_prime,
     if (!prime_dev || !noise_dev || !out_dev) return fail(h, CMPS_ERR_BAD_ARG, "cmps_psi_sample_primed: null pointer");
     if (n < 1 || length < 1) return fail(h, CMPS_ERR_BAD_ARG, "cmps_psi_sample_primed: need n >= 1 and length >= 1");
     if (prime_T < 2) return fail(h, CMPS_ERR_BAD_ARG, "cmps_psi_sample_primed: need prime_T >= 2 (one increment at least)");
-    if (int c = psi_check_clips(h, "cmps_psi_sample_primed", "n_prime", n_prime, n)) return c;
+    if (int c = sample_check_clips(h, "cmps_psi_sample_primed", "n_prime", n_prime, n)) return c;
     const int PF = prime_T - 1;                                  // teacher-forced steps
-    if (int c = psi_check_rows(h, "cmps_psi_sample_primed", "prime_T + length", (long long)PF + length)) return c;
+    if (int c = sample_check_rows(h, "cmps_psi_sample_primed", "prime_T + length", (long long)PF + length)) return c;
     return psi_sample_launch(h, "cmps_psi_sample_primed", prime_dev, n_prime == 1 ? 0 : prime_T, PF, noise_dev, n, length, out_dev, pred_dev,
                              nullptr, stream);
 }
@@ -603,8 +605,8 @@ int cmps_psi_stream(cmps_handle_t h, const void* state_in_dev, void* state_out_d
         return fail(h, CMPS_ERR_BAD_ARG, "cmps_psi_stream: state_in_dev is NULL exactly at the start of a stream (k0 == 0)");
     if (forced > 0 && !audio_dev) return fail(h, CMPS_ERR_BAD_ARG, "cmps_psi_stream: forced > 0 needs audio_dev");
     if (length > 0 && (!noise_dev || !out_dev)) return fail(h, CMPS_ERR_BAD_ARG, "cmps_psi_stream: length > 0 needs noise_dev and out_dev");
-    if (int c = psi_check_clips(h, "cmps_psi_stream", "n_audio", n_audio, n)) return c;
-    if (int c = psi_check_rows(h, "cmps_psi_stream", "k0 + forced + length + 1", (long long)k0 + forced + length)) return c;
+    if (int c = sample_check_clips(h, "cmps_psi_stream", "n_audio", n_audio, n)) return c;
+    if (int c = sample_check_rows(h, "cmps_psi_stream", "k0 + forced + length + 1", (long long)k0 + forced + length)) return c;
     const StreamDev ST{static_cast<const float*>(state_in_dev), static_cast<float*>(state_out_dev), k0, stream_rec_floats(h)};
     return psi_sample_launch(h, "cmps_psi_stream", audio_dev, n_audio == 1 ? 0 : forced + 1, forced, noise_dev, n, length, out_dev, pred_dev,
                              &ST, stream);
@@ -834,29 +836,38 @@ int cmps_rho_update_ancilla(cmps_handle_t h, const float* rho_in_dev, const floa
     return CMPS_OK;
 }
 
-// What cmps_rho_sample and cmps_rho_sample_primed do behind their own argument checks: the workspace checks, the kernel choice, the launch
-// and the record for cmps_rho_states.  PR.prime == nullptr: unprimed; the scan has PR.PF + length steps.
-static int rho_sample_run(cmps_handle_t h, const char* who, const PrimeDev& PR, const float* noise_dev, int n, int length, float* out_dev,
-                          int save_states, void* stream) {
+// The RhoCMPS sampler kernel of a handle (after cmps_rho_set_state).  D <= 32 (rank <= 32): the row-array GEMM sampler, one wavefront
+// per path (cmps_rho_mfma.hip); CMPS_VARIANT_BLOCK keeps the general workgroup-per-path kernel (cross-check; 93 us per step at rank 32
+// against 2 us)
+static bool rho_sampler_mfma(const cmps_handle_s* h) { return h->D <= 32 && h->W.rank <= 32 && h->variant_req != CMPS_VARIANT_BLOCK; }
+// floats of one stream-state record of that kernel
+static int rho_stream_rec_floats(const cmps_handle_s* h) {
+    return rho_sampler_mfma(h) ? stream_rec_rho_mfma(h->W.rank) : stream_rec_rho(h->W.rank, h->D);
+}
+
+// What cmps_rho_sample, cmps_rho_sample_primed and cmps_rho_stream do behind their own argument checks: the workspace checks, the kernel
+// choice, the launch and the record for cmps_rho_states.  ST == nullptr and PR.prime == nullptr: unprimed; ST == nullptr: primed; else one
+// segment of a stream.  The scan has PR.PF + length steps.
+static int rho_sample_run(cmps_handle_t h, const char* who, const PrimeDev& PR, const StreamDev* ST, const float* noise_dev, int n, int length,
+                          float* out_dev, int save_states, void* stream) {
     const std::string w(who);
     const int steps = PR.PF + length;
-    // D <= 32 (rank <= 32): the row-array GEMM sampler, one wavefront per path (cmps_rho_mfma.hip); CMPS_VARIANT_BLOCK keeps the
-    // general workgroup-per-path kernel (cross-check; 93 us per step at rank 32 against 2 us)
-    const bool mfma = h->D <= 32 && h->W.rank <= 32 && h->variant_req != CMPS_VARIANT_BLOCK;
+    const bool mfma = rho_sampler_mfma(h);
     // (only when the SAMPLER's three column arrays exceed the LDS: the workspace section exists from a smaller rank * D on, for the
     // reverse scan's four -- ADVICE r3)
     if (!mfma && rho_cols_spill(3, h->W.rank, h->P.D) && n > h->rho_B)
         return fail(h, CMPS_ERR_WORKSPACE, w + ": at this rank * D the columns live in the workspace: n must not exceed B_max");
     if (save_states && (!(h->rho_flags & CMPS_WS_TRAIN) || (size_t)n * steps > (size_t)h->rho_B * (h->rho_T - 1)))
         return fail(h, CMPS_ERR_WORKSPACE, w + ": save_states needs a CMPS_WS_TRAIN rho workspace with B_max*(T-1) >= n*" +
-                                               (PR.prime ? "(prime_T-1+length)" : "length"));
+                                               (ST ? "(forced+length)" : PR.prime ? "(prime_T-1+length)" : "length"));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    KBind kb(PR.prime ? h : nullptr);                            // (cmps_rho_sample records no kernel events, as before)
-    KScope ks(mfma ? "k_sample_rho_mfma_primed" : "k_sample_rho_primed", s);
-    const hipError_t e = mfma ? launch_sample_rho_mfma(h->P, h->W, noise_dev, n, length, out_dev, save_states != 0, rank1_f16(h->rank1_mode), PR, s)
-                              : launch_sample_rho(h->P, h->W, noise_dev, n, length, out_dev, save_states != 0, PR, s);
+    KBind kb(ST || PR.prime ? h : nullptr);                      // (cmps_rho_sample records no kernel events, as before)
+    KScope ks(ST ? (mfma ? "k_sample_rho_mfma_stream" : "k_sample_rho_stream") : (mfma ? "k_sample_rho_mfma_primed" : "k_sample_rho_primed"), s);
+    const hipError_t e = mfma ? launch_sample_rho_mfma(h->P, h->W, noise_dev, n, length, out_dev, save_states != 0, rank1_f16(h->rank1_mode), PR, ST, s)
+                              : launch_sample_rho(h->P, h->W, noise_dev, n, length, out_dev, save_states != 0, PR, ST, s);
     if (e != hipSuccess) return fail_hip(h, e, who);
     h->rho = Saved{save_states != 0, n, steps, nullptr, nullptr, mfma ? RHO_STASH_MFMA : RHO_STASH_BLOCK};   // (no reverse pass after a sampler)
+    h->rho.k0 = ST ? ST->k0 : 0;                                 // cmps_rho_states: the phases of the saved steps are ttab[k0 + k]
     return CMPS_OK;
 }
 
@@ -867,7 +878,7 @@ int cmps_rho_sample(cmps_handle_t h, const float* noise_dev, int n, int length, 
         return fail(h, CMPS_ERR_STATE, "cmps_rho_sample: call cmps_set_params and cmps_rho_set_state first");
     if (!noise_dev || !out_dev || n < 1 || length < 1) return fail(h, CMPS_ERR_BAD_ARG, "cmps_rho_sample: bad argument");
     if (length > h->L.N) return fail(h, CMPS_ERR_BAD_ARG, "cmps_rho_sample: length exceeds T - 1 of cmps_set_params");
-    return rho_sample_run(h, "cmps_rho_sample", PrimeDev{nullptr, 0, 0, nullptr}, noise_dev, n, length, out_dev, save_states, stream);
+    return rho_sample_run(h, "cmps_rho_sample", PrimeDev{nullptr, 0, 0, nullptr}, nullptr, noise_dev, n, length, out_dev, save_states, stream);
 }
 
 int cmps_rho_sample_primed(cmps_handle_t h, const float* prime_dev, int n_prime, int prime_T, const float* noise_dev, int n, int length,
@@ -878,16 +889,33 @@ int cmps_rho_sample_primed(cmps_handle_t h, const float* prime_dev, int n_prime,
     if (!prime_dev || !noise_dev || !out_dev) return fail(h, CMPS_ERR_BAD_ARG, "cmps_rho_sample_primed: null pointer");
     if (n < 1 || length < 1) return fail(h, CMPS_ERR_BAD_ARG, "cmps_rho_sample_primed: need n >= 1 and length >= 1");
     if (prime_T < 2) return fail(h, CMPS_ERR_BAD_ARG, "cmps_rho_sample_primed: need prime_T >= 2 (one increment at least)");
-    if (n_prime != 1 && n_prime != n)
-        return fail(h, CMPS_ERR_BAD_ARG, "cmps_rho_sample_primed: n_prime must be n, or 1 for one clip shared by every path");
+    if (int c = sample_check_clips(h, "cmps_rho_sample_primed", "n_prime", n_prime, n)) return c;
     const int PF = prime_T - 1;                                  // teacher-forced steps
-    if ((long long)PF + length > h->L.N) {                        // one table row per step, forced or sampled
-        char buf[200];
-        snprintf(buf, sizeof buf, "cmps_rho_sample_primed: prime_T + length = %lld exceeds T = %d of cmps_set_params (the per-step tables): "
-                 "needs T >= %lld", (long long)prime_T + length, h->L.T, (long long)prime_T + length);
-        return fail(h, CMPS_ERR_BAD_ARG, buf);
-    }
-    return rho_sample_run(h, "cmps_rho_sample_primed", PrimeDev{prime_dev, n_prime == 1 ? 0 : prime_T, PF, pred_dev}, noise_dev, n, length,
+    if (int c = sample_check_rows(h, "cmps_rho_sample_primed", "prime_T + length", (long long)PF + length)) return c;
+    return rho_sample_run(h, "cmps_rho_sample_primed", PrimeDev{prime_dev, n_prime == 1 ? 0 : prime_T, PF, pred_dev}, nullptr, noise_dev, n,
+                          length, out_dev, save_states, stream);
+}
+
+size_t cmps_rho_stream_state_bytes(cmps_handle_t h, int n) {
+    if (!h || n < 1 || !h->rho_set) return 0;
+    return (size_t)n * rho_stream_rec_floats(h) * sizeof(float);
+}
+
+int cmps_rho_stream(cmps_handle_t h, const void* state_in_dev, void* state_out_dev, int k0, const float* audio_dev, int n_audio, int forced,
+                    const float* noise_dev, int length, int n, float* out_dev, float* pred_dev, int save_states, void* stream) {
+    if (!h) return CMPS_ERR_BAD_ARG;
+    if (!h->params_set || h->legacy || !h->rho_set)
+        return fail(h, CMPS_ERR_STATE, "cmps_rho_stream: call cmps_set_params and cmps_rho_set_state first (not available in legacy mode)");
+    if (n < 1 || forced < 0 || length < 0 || (long long)forced + length < 1 || k0 < 0)
+        return fail(h, CMPS_ERR_BAD_ARG, "cmps_rho_stream: need n >= 1, forced >= 0, length >= 0, forced + length >= 1 and k0 >= 0");
+    if ((state_in_dev == nullptr) != (k0 == 0))
+        return fail(h, CMPS_ERR_BAD_ARG, "cmps_rho_stream: state_in_dev is NULL exactly at the start of a stream (k0 == 0)");
+    if (forced > 0 && !audio_dev) return fail(h, CMPS_ERR_BAD_ARG, "cmps_rho_stream: forced > 0 needs audio_dev");
+    if (length > 0 && (!noise_dev || !out_dev)) return fail(h, CMPS_ERR_BAD_ARG, "cmps_rho_stream: length > 0 needs noise_dev and out_dev");
+    if (int c = sample_check_clips(h, "cmps_rho_stream", "n_audio", n_audio, n)) return c;
+    if (int c = sample_check_rows(h, "cmps_rho_stream", "k0 + forced + length + 1", (long long)k0 + forced + length)) return c;
+    const StreamDev ST{static_cast<const float*>(state_in_dev), static_cast<float*>(state_out_dev), k0, rho_stream_rec_floats(h)};
+    return rho_sample_run(h, "cmps_rho_stream", PrimeDev{audio_dev, n_audio == 1 ? 0 : forced + 1, forced, pred_dev}, &ST, noise_dev, n, length,
                           out_dev, save_states, stream);
 }
 
@@ -897,7 +925,9 @@ int cmps_rho_states(cmps_handle_t h, int B, int steps, float* rho_out_dev, float
         return fail(h, CMPS_ERR_STATE, "cmps_rho_states: needs cmps_rho_loss_fwd(save_for_bwd=1) or cmps_rho_sample(save_states=1) first");
     if (B != h->rho.B || steps != h->rho.steps || (!rho_out_dev && !purity_out_dev))
         return fail(h, CMPS_ERR_BAD_ARG, "cmps_rho_states: bad argument");
-    hipError_t e = launch_states_rho(h->P, rho_dev(h), B, steps, rho_out_dev, purity_out_dev, static_cast<hipStream_t>(stream));
+    Dev P = h->P;
+    P.ttab += h->rho.k0;                                         // (a stream segment's step k was taken at t_{k0 + k})
+    hipError_t e = launch_states_rho(P, rho_dev(h), B, steps, rho_out_dev, purity_out_dev, static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return fail_hip(h, e, "cmps_rho_states");
     return CMPS_OK;
 }

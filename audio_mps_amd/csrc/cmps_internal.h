@@ -344,8 +344,23 @@ struct PrimeDev {
     int stride, PF;
     float* pred;
 };
+// cmps_psi_stream / cmps_rho_stream: one segment of a resumable scan.  The primed arguments with PF = forced (either count may be 0, not
+// both), on table rows k0 .. k0 + PF + length - 1; the state a kernel carries from one step into the next is read from `in` (null: the
+// start of a scan, psi_0 or the columns of cmps_rho_set_state) and written to `out` (null: not kept), `rec` floats per path.  in == out is
+// allowed: a path reads its record before it writes it.
+struct StreamDev {
+    const float* in;
+    float* out;
+    int k0;
+    int rec;
+};
+// floats of one path's record of the RhoCMPS samplers, a multiple of 4: k_sample_rho_mfma the rows a < rank of U [rank][64], running sum |
+// k_sample_rho the columns S [rank][D] float2, running sum
+inline int stream_rec_rho_mfma(int rank) { return 64 * rank + 4; }
+inline int stream_rec_rho(int rank, int D) { return (2 * rank * D + 1 + 3) / 4 * 4; }
+// ST == nullptr: cmps_rho_sample / cmps_rho_sample_primed; else a stream segment (PR.prime may then be null: PR.PF == 0)
 hipError_t launch_sample_rho(const Dev& P, const RhoDev& W, const float* noise, int n, int length, float* out,
-                             bool save, const PrimeDev& PR, hipStream_t s);
+                             bool save, const PrimeDev& PR, const StreamDev* ST, hipStream_t s);
 hipError_t launch_fwd_legacy_wave(const Dev& P, const float* audio, float* loss, bool save, hipStream_t s);
 hipError_t launch_bwd_legacy_wave(const Dev& P, const float* audio, int rank1_mode, hipStream_t s);
 hipError_t launch_legacy_tables(const Dev& P, float2* psi0, float* dtk, float2* rho, hipStream_t s);
@@ -353,7 +368,7 @@ hipError_t launch_fwd_rho_wave(const Dev& P, const RhoDev& W, const float* audio
 hipError_t launch_fwd_rho_mfma(const Dev& P, const RhoDev& W, const float* audio, float* loss, bool save, bool f16, bool grad1, hipStream_t s);
 hipError_t launch_bwd_rho_mfma(const Dev& P, const RhoDev& W, const float* audio, hipStream_t s);
 hipError_t launch_sample_rho_mfma(const Dev& P, const RhoDev& W, const float* noise, int n, int length, float* out, bool save,
-                                  bool f16, const PrimeDev& PR, hipStream_t s);
+                                  bool f16, const PrimeDev& PR, const StreamDev* ST, hipStream_t s);
 hipError_t launch_bwd_rho_wave(const Dev& P, const RhoDev& W, const float* audio, hipStream_t s);
 hipError_t launch_prep(const Dev& P, const float* R_re, const float* R_im, const float* freqs,
                        const float* psi0_re, const float* psi0_im, float dt, bool rebuild_ttab,
@@ -404,15 +419,7 @@ hipError_t launch_sample_wide_primed(const Dev& P, const float* prime, int prime
                                      float* out, float* pred, hipStream_t s);
 hipError_t launch_sample_block_primed(const Dev& P, const float* prime, int prime_stride, int PF, const float* noise, int n, int length,
                                       float* out, float* pred, hipStream_t s);
-// cmps_psi_stream: one segment of a resumable scan.  The primed arguments with PF = forced (either count may be 0, not both), on table
-// rows k0 .. k0 + PF + length - 1; the state a kernel carries from one step into the next is read from `in` (null: the start of a scan,
-// psi_0) and written to `out` (null: not kept), `rec` floats per path.  in == out is allowed: a path reads its record before it writes it.
-struct StreamDev {
-    const float* in;
-    float* out;
-    int k0;
-    int rec;
-};
+// cmps_psi_stream: the primed arguments and a StreamDev (above)
 // floats of one path's record, a multiple of 4: wave u, |y|^2 partial per lane, running sum | wide ut [2 DP], |y|^2 partial per wave
 // [DP / 16], running sum | block u [2 D], running sum
 constexpr int STREAM_REC_WAVE = 132;

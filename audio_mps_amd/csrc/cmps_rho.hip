@@ -425,10 +425,16 @@ __global__ void k_update_ancilla_rho(Dev P, const float* __restrict__ rho_in, co
 // e dt, taken before the update, to pred[b][k] when asked) in front of the `length` sampled ones, which read noise[b][k - PF] and write
 // out[b][k - PF]; table row and stash row k throughout.  The unprimed instance (cmps_rho_sample) ignores its last argument and is the
 // kernel as it was (profiles/rho_primed_isa_identity.log).
+// STREAM (cmps_rho_stream): the primed scan as one segment of a longer one -- PF or length may be 0, step k of the launch runs on table
+// row ST.k0 + k (noise, out, pred and the stash rows keep the segment's own k), and the columns S (in whichever home they have) and the
+// running sum come from the path's record when ST.in is set and go to it behind the last step when ST.out is.  Thread t moves the
+// components t of all columns, the ones it alone writes in a step.  The other instances ignore ST and are the kernels they were
+// (profiles/rho_stream_isa_identity.log).
 // ------------------------------------------------------------------------------------------------
-template <int NT, bool PRIMED>
+template <int NT, bool PRIMED, bool STREAM = false>
 __global__ __launch_bounds__(NT) void k_sample_rho(Dev P, RhoDev W, const float* __restrict__ noise, int length,
-                                                   float* __restrict__ out, int save, float2* gcols, PrimeDev PR) {
+                                                   float* __restrict__ out, int save, float2* gcols, PrimeDev PR, StreamDev ST) {
+    static_assert(PRIMED || !STREAM, "a stream segment is a primed scan");
     extern __shared__ float2 sh[];
     const int D = P.D, DP = P.DP, r = W.rank, rD = r * D;
     float2* base = gcols ? gcols + (size_t)blockIdx.x * 4 * rD : sh;
@@ -441,9 +447,17 @@ __global__ __launch_bounds__(NT) void k_sample_rho(Dev P, RhoDev W, const float*
     const int PF = PRIMED ? PR.PF : 0, nsteps = PF + length;        // (unprimed: nsteps = length)
     const float* prow = PRIMED ? PR.prime + (size_t)b * PR.stride : nullptr;      // (stride 0: one clip shared by all paths)
     float2* st = save ? W.stash + (size_t)b * nsteps * r * DP : nullptr;
-    if (act)
-        for (int a = 0; a < r; ++a) S[a * D + t] = W.phi0[a * DP + t];
     float samp = 0.f;
+    const float2* rin = nullptr;                                    // (STREAM) this path's record to carry on from
+    if constexpr (STREAM) rin = ST.in ? reinterpret_cast<const float2*>(ST.in + (size_t)b * ST.rec) : nullptr;
+    if (STREAM && rin) {
+        if (act)
+            for (int a = 0; a < r; ++a) S[a * D + t] = rin[a * D + t];
+        samp = ST.in[(size_t)b * ST.rec + 2 * rD];
+    } else {
+        if (act)
+            for (int a = 0; a < r; ++a) S[a * D + t] = W.phi0[a * DP + t];
+    }
     for (int k = 0; k < nsteps; ++k) {
         __syncthreads();
         float pe = 0.f;
@@ -487,7 +501,7 @@ __global__ __launch_bounds__(NT) void k_sample_rho(Dev P, RhoDev W, const float*
         const float sc = sqrtf(1.0f / fmaxf(n, 1e-12f));                           // :165
         __syncthreads();
         if (act) {
-            const float2 rho = P.rho[(size_t)k * DP + t];
+            const float2 rho = P.rho[(size_t)(STREAM ? ST.k0 + k : k) * DP + t];
             for (int a = 0; a < r; ++a) S[a * D + t] = cmul(rho, cscale(sc, Wb[a * D + t]));
         }
         if constexpr (PRIMED) {
@@ -497,6 +511,14 @@ __global__ __launch_bounds__(NT) void k_sample_rho(Dev P, RhoDev W, const float*
             }
         } else {
             if (t == 0) out[(size_t)b * length + k] = dev_A(P) * samp;                  // :116
+        }
+    }
+    if constexpr (STREAM) {
+        if (ST.out) {                                               // (in == out: thread t read these components before the first step)
+            float* rec = ST.out + (size_t)b * ST.rec;
+            if (act)
+                for (int a = 0; a < r; ++a) reinterpret_cast<float2*>(rec)[a * D + t] = S[a * D + t];
+            if (t == 0) rec[2 * rD] = samp;
         }
     }
 }
@@ -589,17 +611,23 @@ hipError_t launch_update_ancilla_rho(const Dev& P, const float* rho_in, const fl
 }
 
 hipError_t launch_sample_rho(const Dev& P, const RhoDev& W, const float* noise, int n, int length, float* out,
-                             bool save, const PrimeDev& PR, hipStream_t s) {
+                             bool save, const PrimeDev& PR, const StreamDev* ST, hipStream_t s) {
     size_t shm;
     float2* g = cols_if_needed(W, (size_t)3 * W.rank * P.D * sizeof(float2) + 128, shm, n);
     if (g == reinterpret_cast<float2*>(1)) return hipErrorInvalidValue;
     return dispatch_block_nt(P.D, [&](auto nt) {
         constexpr int NT = decltype(nt)::value;
+        if (ST) {
+            const hipError_t e = lds_attr(k_sample_rho<NT, true, true>, shm);
+            if (e != hipSuccess) return e;
+            hipLaunchKernelGGL((k_sample_rho<NT, true, true>), dim3(n), dim3(NT), shm, s, P, W, noise, length, out, save ? 1 : 0, g, PR, *ST);
+            return hipGetLastError();
+        }
         return dispatch_bool(PR.prime != nullptr, [&](auto pm) {
             constexpr bool PM = decltype(pm)::value;
             const hipError_t e = lds_attr(k_sample_rho<NT, PM>, shm);
             if (e != hipSuccess) return e;
-            hipLaunchKernelGGL((k_sample_rho<NT, PM>), dim3(n), dim3(NT), shm, s, P, W, noise, length, out, save ? 1 : 0, g, PR);
+            hipLaunchKernelGGL((k_sample_rho<NT, PM>), dim3(n), dim3(NT), shm, s, P, W, noise, length, out, save ? 1 : 0, g, PR, StreamDev{});
             return hipGetLastError();
         });
     });

@@ -612,10 +612,17 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_bwd_rho_mfma(Dev P, RhoDev W,
 // it.  The fp16 x 2 form needs no new scale for a clip however loud: the fixed scales cover U (unit trace) and the constant W_R, W_Q, and
 // the data-dependent s = inc / A multiplies the float32 accumulators behind the MFMAs -- it never meets an fp16 piece.
 // The unprimed instance (cmps_rho_sample) ignores its last argument and is the kernel as it was (profiles/rho_primed_isa_identity.log).
+// STREAM (cmps_rho_stream): the primed scan as one segment of a longer one -- PF or length may be 0, step k of the launch runs on table
+// row ST.k0 + k (noise, out, pred and the stash rows keep the segment's own k, and so does the chunk load: a step knows its place in a
+// chunk only through lane selects), and the rows a < rank of U and the running sum come from the path's record when ST.in is set and go
+// to it behind the last step when ST.out is.  The record holds the float32 rows themselves (the rows from rank on are zero and stay
+// zero), so the fp16 x 2 form needs no scale here either.  The other instances ignore ST and are the kernels they were
+// (profiles/rho_stream_isa_identity.log).
 // ------------------------------------------------------------------------------------------------
-template <bool SAVE, bool F16, bool PRIMED>
+template <bool SAVE, bool F16, bool PRIMED, bool STREAM = false>
 __global__ __launch_bounds__(64 * WAVES, 1) void k_sample_rho_mfma(Dev P, RhoDev W, const float* __restrict__ noise, int n_paths,
-                                                                   int length, float* __restrict__ out, PrimeDev PR) {
+                                                                   int length, float* __restrict__ out, PrimeDev PR, StreamDev ST) {
+    static_assert(PRIMED || !STREAM, "a stream segment is a primed scan");
     __shared__ __attribute__((aligned(16))) float Urow[WAVES][32 * RRLD];
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int b = blockIdx.x * WAVES + w;
@@ -663,11 +670,17 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_sample_rho_mfma(Dev P, RhoDev
             }
         }
     }
+    const float* rin = nullptr;                                      // (STREAM) this path's record to carry on from
+    if constexpr (STREAM) rin = ST.in ? ST.in + (size_t)b * ST.rec : nullptr;
     for (int a = 0; a < 32; ++a) {                                   // rows a < rank of U = phi_a (model.py:127-136), the rest zero
         float v = 0.f;
         if (a < r) {
-            const float2 p = W.phi0[a * DPW + (lane >> 1)];
-            v = (lane & 1) ? p.y : p.x;
+            if (STREAM && rin) {
+                v = rin[a * 64 + lane];
+            } else {
+                const float2 p = W.phi0[a * DPW + (lane >> 1)];
+                v = (lane & 1) ? p.y : p.x;
+            }
         }
         U[a * RRLD + lane] = v;
     }
@@ -680,6 +693,9 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_sample_rho_mfma(Dev P, RhoDev
     const float A = dev_A(P);
     const float sgn = (col & 1) ? 1.f : -1.f;                        // Im lanes add rho_y * partner, Re lanes subtract it
     float samp = 0.f;
+    if constexpr (STREAM) {
+        if (rin) samp = rin[64 * r];
+    }
     for (int kbeg = 0; kbeg < nsteps; kbeg += CH) {
         const int cnt = (nsteps - kbeg) < CH ? (nsteps - kbeg) : CH;
         float nzv;                                                   // what this lane's step is handed: its noise, or (PRIMED, below PF) the clip's increment
@@ -692,7 +708,8 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_sample_rho_mfma(Dev P, RhoDev
         float outv = 0.f;
         for (int kk = 0; kk < cnt; ++kk) {
             const int k = kbeg + kk;
-            const float2 rh0 = P.rho[(size_t)k * DPW + (col >> 1)], rh1 = P.rho[(size_t)k * DPW + 16 + (col >> 1)];
+            const size_t kt = STREAM ? (size_t)ST.k0 + k : (size_t)k;       // table row
+            const float2 rh0 = P.rho[kt * DPW + (col >> 1)], rh1 = P.rho[kt * DPW + 16 + (col >> 1)];
             v16f v0 = {}, v1 = {}, q0 = {}, q1 = {};
 #pragma unroll
             for (int ks = 0; ks < 4; ++ks) {
@@ -787,6 +804,13 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_sample_rho_mfma(Dev P, RhoDev
             if (kbeg + lane < length) orow[kbeg + lane] = outv;
         }
     }
+    if constexpr (STREAM) {
+        if (ST.out) {                                                // (in == out: this wave read its record before the first step)
+            float* rec = ST.out + (size_t)b * ST.rec;
+            for (int a = 0; a < r; ++a) rec[a * 64 + lane] = U[a * RRLD + lane];
+            if (lane == 0) rec[64 * r] = samp;
+        }
+    }
 }
 
 hipError_t launch_fwd_rho_mfma(const Dev& P, const RhoDev& W, const float* audio, float* loss, bool save, bool f16, bool grad1, hipStream_t s) {
@@ -801,13 +825,18 @@ hipError_t launch_fwd_rho_mfma(const Dev& P, const RhoDev& W, const float* audio
 }
 
 hipError_t launch_sample_rho_mfma(const Dev& P, const RhoDev& W, const float* noise, int n, int length, float* out, bool save,
-                                  bool f16, const PrimeDev& PR, hipStream_t s) {
+                                  bool f16, const PrimeDev& PR, const StreamDev* ST, hipStream_t s) {
     const unsigned nb = (unsigned)((n + WAVES - 1) / WAVES);
     return dispatch_bool(save, [&](auto sv) {
         return dispatch_bool(f16, [&](auto hf) {
+            constexpr bool SV = decltype(sv)::value, HF = decltype(hf)::value;
+            if (ST) {
+                hipLaunchKernelGGL((k_sample_rho_mfma<SV, HF, true, true>), dim3(nb), dim3(64 * WAVES), 0, s, P, W, noise, n, length, out, PR, *ST);
+                return hipGetLastError();
+            }
             return dispatch_bool(PR.prime != nullptr, [&](auto pm) {
-                hipLaunchKernelGGL((k_sample_rho_mfma<decltype(sv)::value, decltype(hf)::value, decltype(pm)::value>), dim3(nb), dim3(64 * WAVES),
-                                   0, s, P, W, noise, n, length, out, PR);
+                hipLaunchKernelGGL((k_sample_rho_mfma<SV, HF, decltype(pm)::value>), dim3(nb), dim3(64 * WAVES), 0, s, P, W, noise, n, length, out,
+                                   PR, StreamDev{});
                 return hipGetLastError();
             });
         });

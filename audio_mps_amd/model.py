@@ -253,6 +253,24 @@ class CMPS(_ScanModel):
         """The backend's primed sampler for this model, (out, pred) with want_pred: HipScan.sample_primed / rho_sample_primed."""
         raise NotImplementedError
 
+    # ---- resumable sampling (audio_mps_amd/stream.py) ----
+    def _stream_entries(self, be):
+        """The backend's resumable sampler for this model, (state allocator, segment entry): HipScan.stream_state / stream, or
+        rho_stream_state / rho_stream."""
+        raise NotImplementedError
+
+    def _prepare_stream(self, num_paths, max_steps, keep_states=0):
+        """The backend as a stream needs it: T = max_steps + 1, one table row per step."""
+        return self._prepare(num_paths, max_steps + 1, train=False)
+
+    def open_stream(self, num_paths, max_steps, temp=1, seed=None):
+        """A resumable sampler of ``num_paths`` paths (no reference counterpart; audio_mps_amd/stream.py, cmps_psi_stream /
+        cmps_rho_stream): follow an incoming signal block by block, generate in segments, or alternate.  Prepares the backend once with
+        T = max_steps + 1 -- the only sizing decision, 8 DP bytes of phase table per step; running past ``max_steps`` raises ValueError.
+        The model's variables are read here: a stream keeps the parameters it was opened with."""
+        from .stream import SampleStream
+        return SampleStream(self, num_paths, max_steps, temp=temp, seed=seed)
+
     @staticmethod
     def _prime(prime, num_samples) -> np.ndarray:
         """A prime as the backend takes it: float32 [1, T'] (shared by every path) or [num_samples, T'], T' >= 2."""
@@ -423,13 +441,8 @@ class PsiCMPS(CMPS):
     def _sample_primed(self, be, prime, noise, want_pred):
         return be.sample_primed(prime, noise, want_pred=want_pred)
 
-    def open_stream(self, num_paths, max_steps, temp=1, seed=None):
-        """A resumable sampler of ``num_paths`` paths (no reference counterpart; audio_mps_amd/stream.py, cmps_psi_stream): follow an
-        incoming signal block by block, generate in segments, or alternate.  Prepares the backend once with T = max_steps + 1 -- the
-        only sizing decision, 8 DP bytes of phase table per step; running past ``max_steps`` raises ValueError.  The model's variables
-        are read here: a stream keeps the parameters it was opened with."""
-        from .stream import SampleStream
-        return SampleStream(self, num_paths, max_steps, temp=temp, seed=seed)
+    def _stream_entries(self, be):
+        return be.stream_state, be.stream
 
 
 # --------------------------------------------------------------------------------------------------
@@ -537,6 +550,28 @@ class RhoCMPS(CMPS):
 
     def _sample_primed(self, be, prime, noise, want_pred, save_states=False):
         return be.rho_sample_primed(prime, noise, want_pred=want_pred, save_states=save_states)
+
+    def _stream_entries(self, be):
+        return be.rho_stream_state, be.rho_stream
+
+    def _prepare_stream(self, num_paths, max_steps, keep_states=0):
+        if not keep_states:
+            return super()._prepare_stream(num_paths, max_steps)
+        be = self._get_backend()
+        be.set_params(self.effective_params(), num_paths, max_steps + 1, train=False)
+        be.rho_set_state(self.columns(), num_paths, keep_states + 1, train=True)     # (its T is the stash's capacity, not the tables')
+        return be
+
+    def open_stream(self, num_paths, max_steps, temp=1, seed=None, keep_states=0):
+        """CMPS.open_stream, from rho_0.  ``keep_states = S > 0`` also keeps the columns of every follow / generate call of at most S
+        steps (a longer one raises ValueError), so that ``st.states()`` [num_paths, steps, D, D] and ``st.purity()`` [num_paths, steps]
+        return the lab-frame rho and tr rho^2 after every step of the last call: rho along a run of any length from a stash that holds
+        S steps (num_paths * S * rank * D' * 8 bytes) instead of the whole run."""
+        from .stream import SampleStream
+        keep_states = int(keep_states)
+        if keep_states < 0:
+            raise ValueError("keep_states must not be negative")
+        return SampleStream(self, num_paths, max_steps, temp=temp, seed=seed, keep_states=min(keep_states, int(max_steps)))
 
     def _sample_scan(self, num_samples, length, temp, seed, noise, save_states, prime=None, want_pred=False):
         """(backend, what its sampler returned, steps of the scan): unprimed, or (``prime``) P = T' - 1 forced steps in front."""

@@ -9,7 +9,7 @@
 teacher-forced on the clip and the sampler carries on from there (continue_clip; cmps_psi_sample_primed / cmps_rho_sample_primed); the written
 waveform is the clip followed by its continuation.  Writes ``sample_<i>.wav`` (16-bit PCM mono at --sample_rate, clipped to
 [-1, 1)) and ``samples.npy`` (float32 [num_samples, samples], unclipped) into --out_dir.
-``--segment S`` (PsiCMPS) runs the same job through a resumable stream (model.open_stream; cmps_psi_stream) in segments of S steps: the
+``--segment S`` runs the same job through a resumable stream (model.open_stream; cmps_psi_stream / cmps_rho_stream) in segments of S steps: the
 prime, if given, is followed, then the waveform is generated; the files and the return value are the same.
 Run:  python -m audio_mps_amd.sample --modeldir=LOGDIR --sample_duration=16000 --prime=clip.wav
 """
@@ -83,7 +83,7 @@ def build_parser():
     p.add_argument("--temp", type=float, default=1.0, help="noise temperature (model.py:246)")
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--prime", default=None, metavar="FILE", help=".wav (16-bit mono) or .npy clip to continue")
-    p.add_argument("--segment", type=int, default=None, metavar="S", help="run through a resumable stream in segments of S steps (PsiCMPS)")
+    p.add_argument("--segment", type=int, default=None, metavar="S", help="run through a resumable stream in segments of S steps")
     p.add_argument("--out_dir", default="./samples")
     p.add_argument("--kernel_variant", type=int, default=0, help="as in audio_mps_amd.train")
     return p
@@ -134,8 +134,6 @@ def main(argv=None, backend=None):
     if args.segment is not None:
         if args.segment < 1:
             raise ValueError("--segment must be positive")
-        if rho:
-            raise ValueError("--segment needs a PsiCMPS checkpoint: RhoCMPS has no resumable sampler")
         waves = _segmented(model, args, n, length)
     elif args.prime is None:
         waves = model.sample(n, length, temp=args.temp, seed=args.seed) / model.A

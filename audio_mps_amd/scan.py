@@ -116,7 +116,7 @@ class HipScan:
         return mode if mode in (_capi.CMPS_RANK1_EXACT_F32, _capi.CMPS_RANK1_BF16X2, _capi.CMPS_RANK1_F16X2) else _capi.CMPS_RANK1_BF16X3
 
     def kernel_events(self, on: bool):
-        """cmps_set_option(CMPS_OPT_KERNEL_EVENTS): bracket every kernel of forward() / backward() and of sample() / sample_primed() / stream() / rho_sample_primed() with HIP
+        """cmps_set_option(CMPS_OPT_KERNEL_EVENTS): bracket every kernel of forward() / backward() and of sample() / sample_primed() / stream() / rho_sample_primed() / rho_stream() with HIP
         events (a measurement aid, used by bench.py outside its timed region)."""
         _capi.check(self._h, self._lib.cmps_set_option(self._h, _capi.CMPS_OPT_KERNEL_EVENTS, 1 if on else 0))
 
@@ -398,21 +398,16 @@ class HipScan:
         with want_pred: the model's expected increment of every forced step.  After set_params with T >= prime_T + length."""
         return self._sample_primed(self._lib.cmps_psi_sample_primed, prime, noise, want_pred)
 
-    def stream_state(self, n: int) -> torch.Tensor:
-        """Device memory for the stream-state records of ``n`` paths (cmps_psi_stream_state_bytes): opaque bytes, valid for this
-        object's D and variant."""
-        nbytes = int(self._lib.cmps_psi_stream_state_bytes(self._h, int(n)))
+    def _stream_state(self, bytes_fn, n: int, hint: str = "") -> torch.Tensor:
+        """Device memory for the stream-state records of ``n`` paths: `bytes_fn` is cmps_{psi,rho}_stream_state_bytes."""
+        nbytes = int(bytes_fn(self._h, int(n)))
         if nbytes == 0:
-            raise ValueError(f"invalid path count for a stream: n={n}")
+            raise ValueError(f"invalid path count for a stream: n={n}" + hint)
         return torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
 
-    def stream(self, state_in: Optional[torch.Tensor], state_out: Optional[torch.Tensor], k0: int, audio, noise, want_pred: bool = False,
-               n: Optional[int] = None):
-        """cmps_psi_stream, one segment of a resumable scan on table rows k0 ..: ``audio`` [n_audio, forced + 1] (n_audio = n, or 1: one
-        signal shared by every path; its first column is the sample before the segment's first forced step) or None, then ``noise``
-        [length, n] (the reference's layout) or None.  ``state_in`` is None exactly at k0 = 0, ``state_out`` may be None or ``state_in``
-        (tensors of `stream_state`).  Returns (out [n, length], pred [n, forced] with want_pred, else None).  The path count is taken from
-        the noise, else from a state tensor, else from ``n`` or the audio's rows."""
+    def _stream_call(self, fn, bytes_fn, state_in, state_out, k0, audio, noise, want_pred, n, *flags):
+        """One segment: the signal block [n_audio, forced + 1] and the noise [length, n] up, (out [n, length], pred [n, forced] or None)
+        down.  `fn` / `bytes_fn` are cmps_{psi,rho}_stream / _stream_state_bytes, `flags` what `fn` takes behind pred_dev."""
         forced = length = 0
         d_audio = d_noise = d_out = d_pred = None
         n_audio = 1
@@ -428,11 +423,11 @@ class HipScan:
             n_audio, forced = audio.shape[0], audio.shape[1] - 1
         if n is None:
             st = state_out if state_out is not None else state_in
-            n = st.numel() // int(self._lib.cmps_psi_stream_state_bytes(self._h, 1)) if st is not None else n_audio
+            n = st.numel() // int(bytes_fn(self._h, 1)) if st is not None else n_audio
         n = int(n)
         for st in (state_in, state_out):
             if st is not None and not (st.is_cuda and st.dtype == torch.uint8 and st.is_contiguous()
-                                       and st.numel() == int(self._lib.cmps_psi_stream_state_bytes(self._h, n))):
+                                       and st.numel() == int(bytes_fn(self._h, n))):
                 raise ValueError(f"a stream state must be the tensor stream_state({n}) returned")
         if forced > 0:
             d_audio = torch.from_numpy(audio).to(self.device)
@@ -442,9 +437,24 @@ class HipScan:
         if want_pred:
             d_pred = torch.empty((n, forced), dtype=torch.float32, device=self.device)
         ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None   # noqa: E731
-        _capi.check(self._h, self._lib.cmps_psi_stream(self._h, ptr(state_in), ptr(state_out), int(k0), ptr(d_audio), n_audio, forced,
-                                                       ptr(d_noise), length, n, ptr(d_out), ptr(d_pred), self._stream()))
+        _capi.check(self._h, fn(self._h, ptr(state_in), ptr(state_out), int(k0), ptr(d_audio), n_audio, forced, ptr(d_noise), length, n,
+                                ptr(d_out), ptr(d_pred), *flags, self._stream()))
         return d_out.cpu().numpy(), (d_pred.cpu().numpy() if want_pred else None)
+
+    def stream_state(self, n: int) -> torch.Tensor:
+        """Device memory for the stream-state records of ``n`` paths (cmps_psi_stream_state_bytes): opaque bytes, valid for this
+        object's D and variant."""
+        return self._stream_state(self._lib.cmps_psi_stream_state_bytes, n)
+
+    def stream(self, state_in: Optional[torch.Tensor], state_out: Optional[torch.Tensor], k0: int, audio, noise, want_pred: bool = False,
+               n: Optional[int] = None):
+        """cmps_psi_stream, one segment of a resumable scan on table rows k0 ..: ``audio`` [n_audio, forced + 1] (n_audio = n, or 1: one
+        signal shared by every path; its first column is the sample before the segment's first forced step) or None, then ``noise``
+        [length, n] (the reference's layout) or None.  ``state_in`` is None exactly at k0 = 0, ``state_out`` may be None or ``state_in``
+        (tensors of `stream_state`).  Returns (out [n, length], pred [n, forced] with want_pred, else None).  The path count is taken from
+        the noise, else from a state tensor, else from ``n`` or the audio's rows."""
+        return self._stream_call(self._lib.cmps_psi_stream, self._lib.cmps_psi_stream_state_bytes, state_in, state_out, k0, audio, noise,
+                                 want_pred, n)
 
     # ------------------------------------------------------------------
     # legacy AudioMPS arithmetic (SURVEY 8f rank 2)
@@ -517,6 +527,19 @@ class HipScan:
         """cmps_rho_sample_primed: `sample_primed` for RhoCMPS, from the columns of rho_set_state.  save_states keeps the columns of all
         prime_T - 1 + length steps for rho_states (a train=True rho workspace with T >= prime_T + length)."""
         return self._sample_primed(self._lib.cmps_rho_sample_primed, prime, noise, want_pred, 1 if save_states else 0)
+
+    def rho_stream_state(self, n: int) -> torch.Tensor:
+        """`stream_state` for RhoCMPS (cmps_rho_stream_state_bytes): valid for this object's D and variant and the rank of rho_set_state,
+        which must have been called."""
+        return self._stream_state(self._lib.cmps_rho_stream_state_bytes, n, " (or rho_set_state has not been called)")
+
+    def rho_stream(self, state_in: Optional[torch.Tensor], state_out: Optional[torch.Tensor], k0: int, audio, noise, want_pred: bool = False,
+                   n: Optional[int] = None, save_states: bool = False):
+        """cmps_rho_stream: `stream` for RhoCMPS, from the columns of rho_set_state (states of `rho_stream_state`).  save_states keeps the
+        columns of this segment's steps for rho_states(n, forced + length): a train=True rho workspace whose T - 1 is at least that many
+        steps; the rho workspace's T is a stash capacity only and may be smaller than set_params's."""
+        return self._stream_call(self._lib.cmps_rho_stream, self._lib.cmps_rho_stream_state_bytes, state_in, state_out, k0, audio, noise,
+                                 want_pred, n, 1 if save_states else 0)
 
     def rho_states(self, B: int, steps: int, want_rho: bool = True, want_purity: bool = False):
         """Lab-frame rho [B, steps, D, D] and/or purity [B, steps] of the last saved scan."""

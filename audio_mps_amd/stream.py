@@ -1,4 +1,4 @@
-"""A resumable PsiCMPS sampler: follow an incoming signal and generate audio in segments (cmps_psi_stream).
+"""A resumable sampler for PsiCMPS and RhoCMPS: follow an incoming signal and generate audio in segments (cmps_psi_stream, cmps_rho_stream).
 
 The reference samples a whole waveform in one tf.scan (model.py:242-251) and has nothing that carries on.  A ``SampleStream`` keeps what
 the sampler kernel carries between two steps on the device, so a scan can be continued, can alternate between teacher-forced blocks
@@ -8,6 +8,9 @@ the sampler kernel carries between two steps on the device, so a scan can be con
     pred = st.follow(block)             # [4, steps]: the model's expected increment before every followed sample
     wave = st.generate(16000)           # [4, 16000] in the clip's own units, continuing the followed signal
     wave2 = st.generate(16000)          # ... and on from there
+
+A RhoCMPS stream opened with ``keep_states=S`` also returns rho and the purity after every step of the last call (``st.states()``,
+``st.purity()``), from a stash that holds S steps however long the run is.
 """
 from __future__ import annotations
 
@@ -17,30 +20,51 @@ import numpy as np
 
 
 class SampleStream:
-    """Returned by ``PsiCMPS.open_stream``.  ``position`` is the number of steps taken (the next table row), ``max_steps`` the number the
+    """Returned by ``PsiCMPS.open_stream`` / ``RhoCMPS.open_stream``.  ``position`` is the number of steps taken (the next table row), ``max_steps`` the number the
     stream was sized for, ``last`` the last sample per path [num_paths] (None while the stream has seen no audio and generated nothing)."""
 
-    def __init__(self, model, num_paths: int, max_steps: int, temp=1, seed=None):
+    def __init__(self, model, num_paths: int, max_steps: int, temp=1, seed=None, keep_states: int = 0):
         if num_paths < 1 or max_steps < 1:
             raise ValueError("open_stream needs num_paths >= 1 and max_steps >= 1")
-        self.num_paths, self.max_steps = int(num_paths), int(max_steps)
+        self.num_paths, self.max_steps, self.keep_states = int(num_paths), int(max_steps), int(keep_states)
+        self._saved = None             # steps of the last call whose columns the backend kept (keep_states)
         self.position = 0
         self.last = None
         self._A = np.float32(model.A)
         self._std = float(model.sigma) * math.sqrt(temp * float(model.delta_t))      # CMPS._noise
         self._rng = np.random.default_rng(seed)
-        self._be = model._prepare(self.num_paths, self.max_steps + 1, train=False)    # T = max_steps + 1: one table row per step
-        self._state = self._be.stream_state(self.num_paths)
+        self._be = model._prepare_stream(self.num_paths, self.max_steps, self.keep_states)   # T = max_steps + 1: one table row per step
+        new_state, self._segment = model._stream_entries(self._be)
+        self._state = new_state(self.num_paths)
         self._level = None             # inside a sampled run: the level it began at
 
     # ------------------------------------------------------------------
     def _launch(self, steps, audio, noise, want_pred):
         if self.position + steps > self.max_steps:
             raise ValueError(f"the stream was opened for max_steps={self.max_steps}: {self.position} taken, {steps} more asked for")
-        out, pred = self._be.stream(self._state if self.position else None, self._state, self.position, audio, noise, want_pred,
-                                    n=self.num_paths)
+        if self.keep_states and steps > self.keep_states:
+            raise ValueError(f"the stream was opened with keep_states={self.keep_states}: a call of {steps} steps does not fit")
+        keep = {"save_states": True} if self.keep_states else {}
+        out, pred = self._segment(self._state if self.position else None, self._state, self.position, audio, noise, want_pred,
+                                  n=self.num_paths, **keep)
         self.position += steps
+        self._saved = steps if self.keep_states else None
         return out, pred
+
+    def _kept(self, want_rho):
+        if not self.keep_states:
+            raise ValueError("states() / purity() need a RhoCMPS stream opened with keep_states")
+        if not self._saved:
+            raise ValueError("states() / purity() return the steps of the last follow / generate call: none has made a step yet")
+        return self._be.rho_states(self.num_paths, self._saved, want_rho=want_rho, want_purity=not want_rho)
+
+    def states(self) -> np.ndarray:
+        """Lab-frame rho after every step of the last follow / generate call, [num_paths, steps, D, D] (keep_states streams)."""
+        return self._kept(True)
+
+    def purity(self) -> np.ndarray:
+        """tr rho^2 after every step of the last follow / generate call, [num_paths, steps] (keep_states streams)."""
+        return self._kept(False)
 
     def _block(self, block) -> np.ndarray:
         if hasattr(block, "detach"):

@@ -84,7 +84,7 @@ enum {
     CMPS_OPT_F16_SCALE_SHIFT = 4 /* DIAGNOSTIC, default 0: added to the exponent of every data-dependent fp16 scale of the wave reverse
                         * scan's F16X2 arithmetic (range -40 .. 40).  A positive value pushes the pieces out of fp16 range on purpose:
                         * how tests/test_gpu_parity.py provokes CMPS_ERR_F16_RANGE.  No reference counterpart. */,
-    CMPS_OPT_KERNEL_EVENTS = 2 /* 1: every kernel cmps_psi_loss_fwd / _bwd, cmps_psi_sample, cmps_psi_sample_primed, cmps_psi_stream and cmps_rho_sample_primed launch is bracketed by two HIP events on the caller's stream
+    CMPS_OPT_KERNEL_EVENTS = 2 /* 1: every kernel cmps_psi_loss_fwd / _bwd, cmps_psi_sample, cmps_psi_sample_primed, cmps_psi_stream, cmps_rho_sample_primed and cmps_rho_stream launch is bracketed by two HIP events on the caller's stream
                         * (read and reset with cmps_kernel_times); 0 (default): nothing is recorded.  A measurement aid -- the reference
                         * has no counterpart (no tracing / profiling hooks); bench.py uses it OUTSIDE its timed region to price
                         * each kernel of a multi-kernel family against the pipe it runs on */
@@ -375,7 +375,7 @@ int cmps_legacy_loss_bwd(cmps_handle_t h, const float* audio_dev, int B, int T, 
  *   T >= length + 1) for cmps_rho_states.  Kernel selection follows cmps_set_variant like the loss entries: D <= 32 and
  *   rank <= 32 run the row-array GEMM kernels (one wavefront per clip / path), CMPS_VARIANT_BLOCK the general ones.
  * cmps_rho_states: lab-frame normalised rho after every step of the last cmps_rho_loss_fwd(save_for_bwd=1) or
- *   cmps_rho_sample / cmps_rho_sample_primed(save_states=1): rho_out_dev [B*steps*D*D*2] (rho_evolve_with_data, model.py:76-84 /
+ *   cmps_rho_sample / cmps_rho_sample_primed / cmps_rho_stream(save_states=1): rho_out_dev [B*steps*D*D*2] (rho_evolve_with_data, model.py:76-84 /
  *   rho_evolve_with_sampling, :86-92) and/or purity_out_dev [B*steps] = tr rho^2 (:94-101); either may be NULL.
  */
 size_t cmps_rho_workspace_bytes(int D, int rank, int B, int T, int flags);
@@ -415,6 +415,43 @@ int cmps_rho_states(cmps_handle_t h, int B, int steps, float* rho_out_dev, float
 int cmps_rho_sample_primed(cmps_handle_t h, const float* prime_dev, int n_prime, int prime_T,
                            const float* noise_dev, int n, int length,
                            float* out_dev, float* pred_dev, int save_states, void* stream);
+
+/*
+ * One segment of a resumable RhoCMPS.sample scan: cmps_psi_stream for the density-matrix model, with the same step conventions.  `forced`
+ * steps of _rho_update (model.py:144-150) on the increments of audio_dev, then `length` steps of _rho_and_sample_update (:160-167), on table
+ * rows k0 .. k0 + forced + length - 1.  Either count may be 0, not both.  The steps are cmps_rho_sample_primed's (pred[b][j] =
+ * Re tr((Rt + Rt^dagger) rho) * delta_t before forced step j; a forced step resets the running sum to 0, a sampled step continues it from
+ * state_in_dev's), and what the sampler kernel carries from one step into the next leaves the kernel between two calls.
+ * audio_dev [n_audio * (forced + 1)] row-major, n_audio == n, or 1: shared; audio_dev[b'][0] is the sample BEFORE the segment's first forced
+ * step (consecutive blocks overlap by one sample).  noise_dev [n * length], out_dev [n * length] row-major [path][step] of the SEGMENT;
+ * pred_dev [n * forced] or NULL.
+ * State: cmps_rho_stream_state_bytes(h, n) bytes of caller-owned device memory, n records (a multiple of 16 bytes; 0 for a null handle,
+ * n < 1 or before cmps_rho_set_state).  A record is opaque and belongs to the handle's D, to the rank of cmps_rho_set_state and to the
+ * sampler kernel the variant resolves to (as cmps_rho_sample chooses it): the float32 rows of the row-array kernel (256 rank + 16 bytes),
+ * or the columns of the block kernel (8 rank D + 4 bytes, rounded up to 16), and the running sum.  It holds the carried values themselves,
+ * which makes a cut exact: a scan run as one call or in any number of segments gives the same bits in out, pred, the saved columns and
+ * the final record.
+ *   state_in_dev == NULL  <=>  k0 == 0: the start of a stream (the columns of cmps_rho_set_state, running sum 0); anything else is
+ *   CMPS_ERR_BAD_ARG.  state_out_dev may be NULL (the last segment) and may equal state_in_dev (a path reads its record before it
+ *   writes it).
+ * save_states != 0 keeps the columns of THIS segment's forced + length steps in stash rows 0 ..: needs a CMPS_WS_TRAIN rho workspace with
+ * B_max * (T_rho - 1) >= n * (forced + length), B_max and T_rho those of cmps_rho_set_state -- whose T is independent of cmps_set_params'
+ * (it must not exceed it) and is only a stash capacity: a long run needs rows for one segment, not for the run.
+ * cmps_rho_states(h, n, forced + length, ...) then returns the segment's lab-frame rho and purity, with the phases of t_{k0 + k}.
+ * Parameters, T, the columns, variant and n are the caller's to keep fixed over a stream; calling cmps_set_params* and
+ * cmps_rho_set_state again with the same arguments between two segments is allowed and changes nothing.
+ * CMPS_ERR_BAD_ARG: n < 1, forced < 0, length < 0, forced + length < 1, k0 < 0; audio_dev == NULL with forced > 0; noise_dev or out_dev
+ * == NULL with length > 0; n_audio not in {1, n}; k0 + forced + length > T - 1 of cmps_set_params*, with a message naming the needed
+ * T >= k0 + forced + length + 1.  CMPS_ERR_STATE before cmps_set_params* or cmps_rho_set_state and in legacy mode.  CMPS_ERR_WORKSPACE
+ * as for cmps_rho_sample_primed (columns in the workspace and n > B_max; save_states without the rows for it).
+ * Asynchronous on `stream`; never synchronises, allocates nothing.  With CMPS_OPT_KERNEL_EVENTS the launch is recorded as
+ * k_sample_rho_mfma_stream or k_sample_rho_stream.
+ */
+size_t cmps_rho_stream_state_bytes(cmps_handle_t h, int n);
+int cmps_rho_stream(cmps_handle_t h, const void* state_in_dev, void* state_out_dev, int k0,
+                    const float* audio_dev, int n_audio, int forced,
+                    const float* noise_dev, int length,
+                    int n, float* out_dev, float* pred_dev, int save_states, void* stream);
 
 /*
  * Replaces: the optimiser half of a RhoCMPS training step -- tf.train.AdamOptimizer(learning_rate).minimize(total_loss)
