@@ -313,7 +313,10 @@ static int set_params_impl(cmps_handle_t h, const float* R_re_dev, const float* 
                                const_cast<float*>(P.freqs), const_cast<float2*>(P.rho),
                                reinterpret_cast<double2*>(ws + L.off_rfix), static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return fail_hip(h, e, "cmps_set_params");
-    if (P.status && (fresh || h->ws != ws)) {        // a workspace this handle cannot vouch for: the flag words start at zero
+    // a workspace this handle cannot vouch for, or flag words that moved: the layout puts them behind the stash and the slabs, so with
+    // CMPS_WS_REUSE_TABLES and another T, B_max or TRAIN flag (or after the legacy mode) their address holds something else -- the flag
+    // words start at zero
+    if (P.status && (fresh || h->ws != ws || h->legacy || !h->params_set || h->P.status != P.status)) {
         e = hipMemsetAsync(P.status, 0, 2 * sizeof(unsigned), static_cast<hipStream_t>(stream));
         if (e != hipSuccess) return fail_hip(h, e, "cmps_set_params (status words)");
     }

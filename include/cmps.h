@@ -311,7 +311,8 @@ int cmps_psi_sample_primed(cmps_handle_t h, const float* prime_dev, int n_prime,
  * State: cmps_psi_stream_state_bytes(h, n) bytes of caller-owned device memory, n records (a multiple of 16 bytes; 0 for a null handle
  * or n < 1).  A record is opaque and belongs to the handle's D and to the sampler kernel its variant resolves to (as cmps_psi_sample
  * chooses it); it holds the carried values themselves, which makes a cut exact: a scan run as one call or in any number of segments
- * gives the same bits in out, pred and the final record.
+ * gives the same bits in out, pred and the final record.  (The carried values fill a record from its first byte; the up to 12 bytes
+ * that round it up to a multiple of 16 are never written and keep what the caller's memory held.  The same holds for cmps_rho_stream.)
  *   state_in_dev == NULL  <=>  k0 == 0: the start of a stream (psi_0, running sum 0); anything else is CMPS_ERR_BAD_ARG.
  *   state_out_dev may be NULL (the last segment) and may equal state_in_dev (a path reads its record before it writes it).
  * Parameters, T, variant and n are the caller's to keep fixed over a stream.  The exact split holds for tables built by equal
