@@ -52,7 +52,7 @@ SYMBOLS = (
     "cmps_get_variant", "cmps_set_option", "cmps_get_option", "cmps_kernel_times", "cmps_workspace_bytes", "cmps_set_params", "cmps_set_params_dev",
     "cmps_apply_step_scratch_bytes", "cmps_psi_apply_step", "cmps_psi_loss_fwd",
     "cmps_psi_loss_bwd", "cmps_psi_grad_status", "cmps_psi_update_ancilla", "cmps_psi_states", "cmps_psi_sample",
-    "cmps_psi_sample_primed", "cmps_psi_stream_state_bytes", "cmps_psi_stream",
+    "cmps_psi_sample_primed", "cmps_psi_stream_state_bytes", "cmps_psi_stream", "cmps_psi_stream_score",
     "cmps_legacy_set_params", "cmps_legacy_loss_fwd", "cmps_legacy_loss_bwd",
     "cmps_rho_workspace_bytes", "cmps_rho_set_state", "cmps_rho_loss_fwd", "cmps_rho_loss_bwd",
     "cmps_rho_update_ancilla", "cmps_rho_sample", "cmps_rho_sample_primed", "cmps_rho_stream_state_bytes", "cmps_rho_stream", "cmps_rho_states",
@@ -117,6 +117,8 @@ def _declare(lib):
     lib.cmps_psi_stream_state_bytes.restype = c_size_t
     lib.cmps_psi_stream.argtypes = [vp, vp, vp, c_int, vp, c_int, c_int, vp, c_int, c_int, vp, vp, vp]
     lib.cmps_psi_stream.restype = c_int
+    lib.cmps_psi_stream_score.argtypes = [vp, vp, vp, c_int, vp, c_int, c_int, c_int, vp, vp, vp, vp]
+    lib.cmps_psi_stream_score.restype = c_int
     lib.cmps_legacy_set_params.argtypes = [vp, vp, vp, vp, c_double, c_int, c_int, c_int, vp, c_size_t, vp]
     lib.cmps_legacy_set_params.restype = c_int
     lib.cmps_legacy_loss_fwd.argtypes = [vp, vp, c_int, c_int, vp, c_int, vp]

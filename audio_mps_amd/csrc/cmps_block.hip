@@ -376,15 +376,21 @@ __global__ void k_states(Dev P, float* __restrict__ psi_out) {
 // STREAM (cmps_psi_stream): the primed scan as one segment of a longer one -- PF or length may be 0, step k of the launch runs on table
 // row ST.k0 + k, and u and the running sum come from the path's record when ST.in is set and go to it behind the last step when ST.out is.
 // The other instances ignore ST and are the kernels they were (profiles/stream_sampler_isa_identity.log).
-template <int NT, bool PRIMED, bool STREAM = false>
+// SCORE (cmps_psi_stream_score): a stream segment of forced steps that also gives every step's loss increment (model.py:276-282, 293-294):
+// behind y_k one more LDS pass, R y_k from RT and a second vector sy, e' = 2 Re(y_k^dagger R y_k), z = (e' x) / A, lv = -log(1 + z) as in
+// k_fwd_block above; lv is added to the running loss (SC.loss[b]: read on a resumed scan, written behind the last step) and stored to
+// SC.nll[b][k] when set.  u and the running sum are untouched.  The other instances are the kernels they were
+// (profiles/stream_score_isa_identity.log).
+template <int NT, bool PRIMED, bool STREAM = false, bool SCORE = false>
 __global__ __launch_bounds__(NT) void k_sample_block(Dev P, const float* __restrict__ noise, int length, float* __restrict__ out,
                                                      const float* __restrict__ prime, int prime_stride, int PF, float* __restrict__ pred,
-                                                     StreamDev ST) {
+                                                     StreamDev ST, ScoreDev SC) {
     static_assert(PRIMED || !STREAM, "a stream segment is a primed scan");
+    static_assert(STREAM || !SCORE, "a scored segment is a stream segment");
     extern __shared__ float2 sh[];
     const int D = P.D, DP = P.DP;
     float2* su = sh;
-    float* red = reinterpret_cast<float*>(sh + D);
+    float* red = reinterpret_cast<float*>(sh + (SCORE ? 2 * D : D));   // (SCORE: y_k sits at sh + D)
     const int b = blockIdx.x, t = threadIdx.x;
     const bool act = t < D;
     float2 u = act ? P.psi0[t] : make_float2(0.f, 0.f);
@@ -397,6 +403,10 @@ __global__ __launch_bounds__(NT) void k_sample_block(Dev P, const float* __restr
             if (act) u = make_float2(rec[2 * t], rec[2 * t + 1]);
             samp = rec[2 * D];
         }
+    }
+    [[maybe_unused]] float loss = 0.f;                                            // SCORE: the path's running loss (model.py:279)
+    if constexpr (SCORE) {
+        if (ST.in) loss = SC.loss[b];
     }
     for (int k = 0; k < nsteps; ++k) {
         if (act) su[t] = u;
@@ -424,6 +434,26 @@ __global__ __launch_bounds__(NT) void k_sample_block(Dev P, const float* __restr
         const float n = block_sum<NT>(act ? (y.x * y.x + y.y * y.y) : 0.f, red);
         const float inv = 1.0f / sqrtf(fmaxf(n, 1e-12f));                                  // :289
         if (act) u = cmul(P.rho[(size_t)(STREAM ? ST.k0 + k : k) * DP + t], cscale(inv, y));
+        if constexpr (SCORE) {                                                             // (every step of a scored segment is forced)
+            float2* sy = sh + D;
+            // y_k and the increment reach the score lines as copies the optimiser cannot see through.  With a second visible use of y the
+            // compiler is free to contract the chain's plain C++ sums (u . v of the expectation, u + Q u + s R u, |y|^2) into other FMA
+            // pairs than in the stream instance -- written without the copies, pred came out one digit off; behind the empty asm the chain sees y used as there, and
+            // tests/test_gpu_stream_score.py::test_scoring_perturbs_nothing holds the two instances to the same bits.
+            float2 ys = y;
+            float xs = inc;
+            asm volatile("" : "+v"(ys.x), "+v"(ys.y), "+v"(xs));
+            if (act) sy[t] = ys;
+            __syncthreads();
+            float2 r = make_float2(0.f, 0.f);
+            if (act)
+                for (int j = 0; j < D; ++j) r = cfma(P.RT[j * DP + t], sy[j], r);
+            const float e2 = 2.0f * block_sum<NT>(act ? (ys.x * r.x + ys.y * r.y) : 0.f, red);   // model.py:325 on y_k, frame of t_k
+            const float z = (e2 * xs) / dev_A(P);                                          // :294
+            const float lv = -logf(1.0f + z);
+            loss += lv;                                                                    // :279
+            if (t == 0 && SC.nll) SC.nll[(size_t)b * PF + k] = lv;
+        }
         if constexpr (PRIMED) {
             if (t == 0) {
                 if (!forced) out[(size_t)b * length + (k - PF)] = dev_A(P) * samp;
@@ -433,6 +463,9 @@ __global__ __launch_bounds__(NT) void k_sample_block(Dev P, const float* __restr
             if (t == 0) out[(size_t)b * length + k] = dev_A(P) * samp;                          // :251
         }
         __syncthreads();
+    }
+    if constexpr (SCORE) {
+        if (t == 0) SC.loss[b] = loss;
     }
     if constexpr (STREAM) {
         if (ST.out) {
@@ -503,7 +536,7 @@ hipError_t launch_sample_block(const Dev& P, const float* noise, int n, int leng
     return dispatch_block_nt(P.D, [&](auto nt) {
         constexpr int NT = decltype(nt)::value;
         hipLaunchKernelGGL((k_sample_block<NT, false>), dim3(n), dim3(NT), shm, s, P, noise, length, out, (const float*)nullptr, 0, 0, (float*)nullptr,
-                           StreamDev{});
+                           StreamDev{}, ScoreDev{});
         return hipGetLastError();
     });
 }
@@ -513,7 +546,7 @@ hipError_t launch_sample_block_primed(const Dev& P, const float* prime, int prim
     const size_t shm = (size_t)P.D * sizeof(float2) + 64;
     return dispatch_block_nt(P.D, [&](auto nt) {
         constexpr int NT = decltype(nt)::value;
-        hipLaunchKernelGGL((k_sample_block<NT, true>), dim3(n), dim3(NT), shm, s, P, noise, length, out, prime, prime_stride, PF, pred, StreamDev{});
+        hipLaunchKernelGGL((k_sample_block<NT, true>), dim3(n), dim3(NT), shm, s, P, noise, length, out, prime, prime_stride, PF, pred, StreamDev{}, ScoreDev{});
         return hipGetLastError();
     });
 }
@@ -523,7 +556,18 @@ hipError_t launch_sample_block_stream(const Dev& P, const StreamDev& ST, const f
     const size_t shm = (size_t)P.D * sizeof(float2) + 64;
     return dispatch_block_nt(P.D, [&](auto nt) {
         constexpr int NT = decltype(nt)::value;
-        hipLaunchKernelGGL((k_sample_block<NT, true, true>), dim3(n), dim3(NT), shm, s, P, noise, length, out, audio, audio_stride, PF, pred, ST);
+        hipLaunchKernelGGL((k_sample_block<NT, true, true>), dim3(n), dim3(NT), shm, s, P, noise, length, out, audio, audio_stride, PF, pred, ST, ScoreDev{});
+        return hipGetLastError();
+    });
+}
+
+hipError_t launch_sample_block_score(const Dev& P, const StreamDev& ST, const ScoreDev& SC, const float* audio, int audio_stride, int PF, int n, float* pred,
+                                     hipStream_t s) {
+    const size_t shm = (size_t)2 * P.D * sizeof(float2) + 64;
+    return dispatch_block_nt(P.D, [&](auto nt) {
+        constexpr int NT = decltype(nt)::value;
+        hipLaunchKernelGGL((k_sample_block<NT, true, true, true>), dim3(n), dim3(NT), shm, s, P, (const float*)nullptr, 0, (float*)nullptr, audio,
+                           audio_stride, PF, pred, ST, SC);
         return hipGetLastError();
     });
 }

@@ -539,15 +539,15 @@ static int stream_rec_floats(const cmps_handle_s* h) {
     return family == SAMPLER_WAVE ? STREAM_REC_WAVE : family == SAMPLER_WIDE ? stream_rec_wide(padded_D(h->D)) : stream_rec_block(h->D);
 }
 // The kernel choice and the launch.  clips == nullptr and ST == nullptr: the unprimed sampler; ST == nullptr: the primed one (`forced`
-// teacher-forced steps on clips[path * clip_stride + k]); else one segment of a stream.
+// teacher-forced steps on clips[path * clip_stride + k]); else one segment of a stream, scored when SC is set.
 static int psi_sample_launch(cmps_handle_t h, const char* who, const float* clips, int clip_stride, int forced, const float* noise_dev, int n,
-                      int length, float* out_dev, float* pred_dev, const StreamDev* ST, void* stream) {
+                      int length, float* out_dev, float* pred_dev, const StreamDev* ST, void* stream, const ScoreDev* SC = nullptr) {
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int family = sampler_family(h);
-    static const char* const names[3][3] = {{"k_sample_block", "k_sample_block_primed", "k_sample_block_stream"},
-                                            {"k_sample_wave", "k_sample_wave_primed", "k_sample_wave_stream"},
-                                            {"k_sample_wide", "k_sample_wide_primed", "k_sample_wide_stream"}};
-    const int mode = ST ? 2 : clips ? 1 : 0;
+    static const char* const names[3][4] = {{"k_sample_block", "k_sample_block_primed", "k_sample_block_stream", "k_sample_block_score"},
+                                            {"k_sample_wave", "k_sample_wave_primed", "k_sample_wave_stream", "k_sample_wave_score"},
+                                            {"k_sample_wide", "k_sample_wide_primed", "k_sample_wide_stream", "k_sample_wide_score"}};
+    const int mode = ST ? (SC ? 3 : 2) : clips ? 1 : 0;
     KBind kb(h);
     KScope ks(names[family][mode], s);
     hipError_t e;
@@ -559,6 +559,10 @@ static int psi_sample_launch(cmps_handle_t h, const char* who, const float* clip
         e = family == SAMPLER_WAVE ? launch_sample_wave_primed(h->P, clips, clip_stride, forced, noise_dev, n, length, out_dev, pred_dev, s)
           : family == SAMPLER_WIDE ? launch_sample_wide_primed(h->P, clips, clip_stride, forced, noise_dev, n, length, out_dev, pred_dev, s)
                                    : launch_sample_block_primed(h->P, clips, clip_stride, forced, noise_dev, n, length, out_dev, pred_dev, s);
+    else if (mode == 3)
+        e = family == SAMPLER_WAVE ? launch_sample_wave_score(h->P, *ST, *SC, clips, clip_stride, forced, n, pred_dev, s)
+          : family == SAMPLER_WIDE ? launch_sample_wide_score(h->P, *ST, *SC, clips, clip_stride, forced, n, pred_dev, s)
+                                   : launch_sample_block_score(h->P, *ST, *SC, clips, clip_stride, forced, n, pred_dev, s);
     else
         e = family == SAMPLER_WAVE ? launch_sample_wave_stream(h->P, *ST, clips, clip_stride, forced, noise_dev, n, length, out_dev, pred_dev, s)
           : family == SAMPLER_WIDE ? launch_sample_wide_stream(h->P, *ST, clips, clip_stride, forced, noise_dev, n, length, out_dev, pred_dev, s)
@@ -613,6 +617,24 @@ int cmps_psi_stream(cmps_handle_t h, const void* state_in_dev, void* state_out_d
     const StreamDev ST{static_cast<const float*>(state_in_dev), static_cast<float*>(state_out_dev), k0, stream_rec_floats(h)};
     return psi_sample_launch(h, "cmps_psi_stream", audio_dev, n_audio == 1 ? 0 : forced + 1, forced, noise_dev, n, length, out_dev, pred_dev,
                              &ST, stream);
+}
+
+int cmps_psi_stream_score(cmps_handle_t h, const void* state_in_dev, void* state_out_dev, int k0, const float* audio_dev, int n_audio, int forced,
+                          int n, float* nll_dev, float* loss_dev, float* pred_dev, void* stream) {
+    if (!h) return CMPS_ERR_BAD_ARG;
+    if (!h->params_set || h->legacy)
+        return fail(h, CMPS_ERR_STATE, "cmps_psi_stream_score: call cmps_set_params first (not available in legacy mode)");
+    if (n < 1 || forced < 1 || k0 < 0) return fail(h, CMPS_ERR_BAD_ARG, "cmps_psi_stream_score: need n >= 1, forced >= 1 and k0 >= 0");
+    if ((state_in_dev == nullptr) != (k0 == 0))
+        return fail(h, CMPS_ERR_BAD_ARG, "cmps_psi_stream_score: state_in_dev is NULL exactly at the start of a stream (k0 == 0)");
+    if (!audio_dev) return fail(h, CMPS_ERR_BAD_ARG, "cmps_psi_stream_score: needs audio_dev");
+    if (!loss_dev) return fail(h, CMPS_ERR_BAD_ARG, "cmps_psi_stream_score: needs loss_dev (the running loss per path)");
+    if (int c = sample_check_clips(h, "cmps_psi_stream_score", "n_audio", n_audio, n)) return c;
+    if (int c = sample_check_rows(h, "cmps_psi_stream_score", "k0 + forced + 1", (long long)k0 + forced)) return c;
+    const StreamDev ST{static_cast<const float*>(state_in_dev), static_cast<float*>(state_out_dev), k0, stream_rec_floats(h)};
+    const ScoreDev SC{nll_dev, loss_dev};
+    return psi_sample_launch(h, "cmps_psi_stream_score", audio_dev, n_audio == 1 ? 0 : forced + 1, forced, nullptr, n, 0, nullptr, pred_dev, &ST,
+                             stream, &SC);
 }
 
 // ---------------------------------------------------------------------------------------------------

@@ -431,6 +431,17 @@ hipError_t launch_sample_wide_stream(const Dev& P, const StreamDev& ST, const fl
                                      int length, float* out, float* pred, hipStream_t s);
 hipError_t launch_sample_block_stream(const Dev& P, const StreamDev& ST, const float* audio, int audio_stride, int PF, const float* noise, int n,
                                       int length, float* out, float* pred, hipStream_t s);
+// cmps_psi_stream_score: a stream segment of PF forced steps that also gives the loss increment of every step
+struct ScoreDev {
+    float* nll;       // every step's loss increment [path][step], or null
+    float* loss;      // the running loss per path: read when the segment resumes a scan (StreamDev::in set), written behind the last step
+};
+hipError_t launch_sample_wave_score(const Dev& P, const StreamDev& ST, const ScoreDev& SC, const float* audio, int audio_stride, int PF, int n, float* pred,
+                                    hipStream_t s);
+hipError_t launch_sample_wide_score(const Dev& P, const StreamDev& ST, const ScoreDev& SC, const float* audio, int audio_stride, int PF, int n, float* pred,
+                                    hipStream_t s);
+hipError_t launch_sample_block_score(const Dev& P, const StreamDev& ST, const ScoreDev& SC, const float* audio, int audio_stride, int PF, int n, float* pred,
+                                     hipStream_t s);
 
 size_t apply_step_scratch_bytes(int D);
 hipError_t launch_apply_step(int D, bool apply, double inv_batch, double lr_t, double beta1, double beta2, double eps, double h_reg,

@@ -667,11 +667,19 @@ __device__ __forceinline__ void mv2r_hi(const v2f (&MA)[16], const v2f (&MB)[16]
 // path's record when ST.in is set and stored to it behind the last step when ST.out is.  The record holds the carried values themselves and
 // the chunks are staged from the segment's first row, so where a run is cut changes no bit of it.  The other instances ignore ST and are
 // the kernels they were (profiles/stream_sampler_isa_identity.log).
-template <bool PRIMED, bool STREAM = false>
+// SCORE (cmps_psi_stream_score): a stream segment of forced steps that also gives the loss increment of every step (model.py:276-282,
+// 293-294).  Behind y_k, before it is rotated into rho_k y_k, the wave broadcasts y_k once more, applies the register-resident R to it and
+// reduces e' = 2 Re(y_k^dagger R y_k); e' is parked one step per lane, and behind the chunk z = (e' x) / A, lv = -log(1 + z) are formed for
+// 64 steps at once and added to the running loss in step order (the forward scan's order, cmps_wave2.hip).  Nothing of this feeds u, xsq
+// or the running sum: they keep the stream instance's bits.  The running loss comes from SC.loss[b] on a resumed scan (else 0) and goes
+// back to it behind the last step; lv goes to SC.nll[b][k] when set.  The other instances are the kernels they were
+// (profiles/stream_score_isa_identity.log).
+template <bool PRIMED, bool STREAM = false, bool SCORE = false>
 __global__ __launch_bounds__(64 * WAVES, 1) void k_sample_wave(Dev P, const float* __restrict__ noise, int n_paths, int length,
                                                                float* __restrict__ out, const float* __restrict__ prime,
-                                                               int prime_stride, int PF, float* __restrict__ pred, StreamDev ST) {
+                                                               int prime_stride, int PF, float* __restrict__ pred, StreamDev ST, ScoreDev SC) {
     static_assert(PRIMED || !STREAM, "a stream segment is a primed scan");
+    static_assert(STREAM || !SCORE, "a scored segment is a stream segment");
     __shared__ __attribute__((aligned(16))) float4 stR[WAVES][CH * 16];
     __shared__ __attribute__((aligned(16))) float2 bcU[WAVES][DPW];
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -706,6 +714,12 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_sample_wave(Dev P, const floa
             samp = rec[128];
         }
     }
+    [[maybe_unused]] float loss = 0.f;                   // SCORE: the path's running loss (model.py:279)
+    [[maybe_unused]] float* lrow = nullptr;
+    if constexpr (SCORE) {
+        if (ST.in) loss = SC.loss[b];
+        if (SC.nll) lrow = SC.nll + (size_t)b * PF;
+    }
     v4f sr[16], qu[8];
     v2f rho;
     for (int c = 0; c < NC; ++c) {
@@ -721,6 +735,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_sample_wave(Dev P, const floa
         }
         stage_commit<16>(stR[w], lane, sr);
         float svec = 0.f, pvec = 0.f;
+        [[maybe_unused]] float evec = 0.f;               // SCORE: e' of this lane's step
         for (int kk = 0; kk < cnt; ++kk) {
             bcast_issue_tab(aUw, aUr, u, aRho + kk * 256, qu, rho);
             lds_wait_lo<5>(qu);
@@ -746,6 +761,14 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_sample_wave(Dev P, const floa
             svec = (lane == kk) ? samp : svec;
             const float s = inc / A;                                 // :288 -> :303
             const float y = inv * (u + (qs + s * vs));
+            if constexpr (SCORE) {                                   // e' = 2 Re(y_k^dagger R y_k) in the frame of t_k (model.py:293, 319-325)
+                bcast_issue(aUw, aUr, y, qu);
+                lds_wait<0>(qu);
+                const v2f ar = mv1(MR, qu);
+                const float rs = swapadd_after_asm(ar.x, ar.y);
+                const float e2 = 2.0f * sum64(y * rs);
+                evec = (lane == kk) ? e2 : evec;
+            }
             const float yo = osig_of(y, hb);
             const v2f un = cmul2(mk2(y, yo), rho);                   // rho_k y_k, normalised in the next step
             u = un.x;
@@ -760,6 +783,15 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_sample_wave(Dev P, const floa
         } else {
             if (lane < cnt) orow[kbeg + lane] = A * svec;            // model.py:251
         }
+        if constexpr (SCORE) {                                       // (every step of a scored segment is forced: `given` is its increment)
+            const float z = (evec * given) / A;                      // model.py:294 operation order
+            const float lv = -logf(1.0f + z);
+            for (int j = 0; j < cnt; ++j) loss += rdlane(lv, j);     // :279, sequential in time
+            if (lrow && lane < cnt) lrow[kbeg + lane] = lv;
+        }
+    }
+    if constexpr (SCORE) {
+        if (lane == 0) SC.loss[b] = loss;
     }
     if constexpr (STREAM) {
         if (ST.out) {
@@ -774,21 +806,29 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_sample_wave(Dev P, const floa
 hipError_t launch_sample_wave(const Dev& P, const float* noise, int n, int length, float* out, hipStream_t s) {
     const unsigned nb = (unsigned)((n + WAVES - 1) / WAVES);
     hipLaunchKernelGGL(k_sample_wave<false>, dim3(nb), dim3(64 * WAVES), 0, s, P, noise, n, length, out, (const float*)nullptr, 0, 0, (float*)nullptr,
-                       StreamDev{});
+                       StreamDev{}, ScoreDev{});
     return hipGetLastError();
 }
 
 hipError_t launch_sample_wave_primed(const Dev& P, const float* prime, int prime_stride, int PF, const float* noise, int n, int length,
                                      float* out, float* pred, hipStream_t s) {
     const unsigned nb = (unsigned)((n + WAVES - 1) / WAVES);
-    hipLaunchKernelGGL(k_sample_wave<true>, dim3(nb), dim3(64 * WAVES), 0, s, P, noise, n, length, out, prime, prime_stride, PF, pred, StreamDev{});
+    hipLaunchKernelGGL(k_sample_wave<true>, dim3(nb), dim3(64 * WAVES), 0, s, P, noise, n, length, out, prime, prime_stride, PF, pred, StreamDev{}, ScoreDev{});
     return hipGetLastError();
 }
 
 hipError_t launch_sample_wave_stream(const Dev& P, const StreamDev& ST, const float* audio, int audio_stride, int PF, const float* noise, int n,
                                      int length, float* out, float* pred, hipStream_t s) {
     const unsigned nb = (unsigned)((n + WAVES - 1) / WAVES);
-    hipLaunchKernelGGL((k_sample_wave<true, true>), dim3(nb), dim3(64 * WAVES), 0, s, P, noise, n, length, out, audio, audio_stride, PF, pred, ST);
+    hipLaunchKernelGGL((k_sample_wave<true, true>), dim3(nb), dim3(64 * WAVES), 0, s, P, noise, n, length, out, audio, audio_stride, PF, pred, ST, ScoreDev{});
+    return hipGetLastError();
+}
+
+hipError_t launch_sample_wave_score(const Dev& P, const StreamDev& ST, const ScoreDev& SC, const float* audio, int audio_stride, int PF, int n, float* pred,
+                                    hipStream_t s) {
+    const unsigned nb = (unsigned)((n + WAVES - 1) / WAVES);
+    hipLaunchKernelGGL((k_sample_wave<true, true, true>), dim3(nb), dim3(64 * WAVES), 0, s, P, (const float*)nullptr, n, 0, (float*)nullptr, audio,
+                       audio_stride, PF, pred, ST, SC);
     return hipGetLastError();
 }
 

@@ -555,11 +555,20 @@ __global__ void k_rho_phi_reduce(const float* __restrict__ gphi, int B, int vran
 // step the same values go to ST.out (the ping-pong parity is the launch's own: the slot only names where the values sit).  The record
 // holds the carried values themselves, so where a run is cut changes no bit of it.  An odd count's repeated last path stores nothing.
 // The other instances ignore ST and are the kernels they were (profiles/stream_sampler_isa_identity.log).
-template <int PD, bool PRIMED, bool STREAM = false>
+// SCORE (cmps_psi_stream_score): a stream segment of forced steps that also gives every step's loss increment (model.py:276-282, 293-294).
+// Behind the step's first barrier every wave has read the broadcast slot of ut_k, so y_k is written into that slot; one more barrier, the
+// resident R applied to it (col_single: no Q), the same slice reduction, and the per-wave partials of Re(y_k^dagger R y_k) go to a slot of
+// their own that is summed behind the step's closing barrier: e' = 2 Re(y_k^dagger R y_k), z = (e' x) / A, lv = -log(1 + z), added to
+// the path's running loss (SC.loss: read on a resumed scan, written behind the last step) and stored to SC.nll[path][k] when set.
+// (`ee2`, 8 bytes per wave, is declared where it is used, in the scored branch of the step loop, so that the other instances' LDS is
+// untouched.)  One barrier, one mat-vec and one exchange more per step; ut, the |y|^2 partials and the running sum are untouched.  The other instances
+// are the kernels they were (profiles/stream_score_isa_identity.log).
+template <int PD, bool PRIMED, bool STREAM = false, bool SCORE = false>
 __global__ __launch_bounds__(4 * PD) void k_sample_wide(Dev P, const float* __restrict__ noise, int n_paths, int length,
                                                         float* __restrict__ out, const float* __restrict__ prime, int prime_stride,
-                                                        int PF, float* __restrict__ pred, StreamDev ST) {
+                                                        int PF, float* __restrict__ pred, StreamDev ST, ScoreDev SC) {
     static_assert(PRIMED || !STREAM, "a stream segment is a primed scan");
+    static_assert(STREAM || !SCORE, "a scored segment is a stream segment");
     using G = WideGeom<PD>;
     constexpr int NW = G::NW, KC = G::KC, VSL = G::VSL, VEC4 = G::VEC4;
     __shared__ __attribute__((aligned(16))) v4f uvec[2 * VEC4];
@@ -613,6 +622,12 @@ __global__ __launch_bounds__(4 * PD) void k_sample_wide(Dev P, const float* __re
             if (i == 0 && q < 2) nrm[w * 2 + clip] = rec[2 * PD + w];
             samp = rec[2 * PD + NW];
         }
+    }
+    [[maybe_unused]] float loss = 0.f;                            // SCORE: the running loss of this lane's path (model.py:279)
+    [[maybe_unused]] float* lrow = nullptr;
+    if constexpr (SCORE) {
+        if (resumed) loss = SC.loss[clip1 ? b1 : b0];
+        if (SC.nll) lrow = SC.nll + (size_t)(clip1 ? b1 : b0) * PF;
     }
     __syncthreads();
 
@@ -690,7 +705,37 @@ __global__ __launch_bounds__(4 * PD) void k_sample_wide(Dev P, const float* __re
         } else {
             if (writer) orow[k] = A * samp;                       // model.py:251
         }
-        wide_barrier();
+        if constexpr (SCORE) {                                    // (every step of a scored segment is forced: inc is the clip's increment)
+            __shared__ __attribute__((aligned(8))) float ee2[NW * 2];
+            reinterpret_cast<float*>(uvec + p * VEC4)[own_f] = y;     // slot p: every wave has read ut_k from it before the barrier above
+            wide_barrier();
+            v2f sRe0 = mk2(0.f, 0.f), sIm0 = sRe0, sRe1 = sRe0, sIm1 = sRe0;
+#pragma unroll
+            for (int j = 0; j < KC; ++j) {
+                const v4f x = uv[j];
+                col_single(sRe0, sIm0, sRe1, sIm1, MR[0][j], MR[1][j], lo2(x), hi2(x));
+            }
+            const float rs = reduce_slices(sRe0, sIm0, sRe1, sIm1, clip1);      // (R y_k): this lane's (row, component, path)
+            const float ep2 = clip_wave_sum(y * rs);
+            if (i == 0 && q < 2) ee2[w * 2 + clip] = ep2;
+            wide_barrier();                                       // the step's closing barrier: slot p is free for ut_{k+2}
+            float f0 = 0.f, f1 = 0.f;
+#pragma unroll
+            for (int ww = 0; ww < NW; ++ww) {                     // (ee2 is next written behind two barriers of the next step)
+                const float2 t = *reinterpret_cast<const float2*>(&ee2[ww * 2]);
+                f0 += t.x; f1 += t.y;
+            }
+            const float e2 = 2.0f * (clip1 ? f1 : f0);            // 2 Re(y_k^dagger R y_k), frame of t_k (model.py:293, 319-325)
+            const float z = (e2 * inc) / A;                       // :294
+            const float lv = -logf(1.0f + z);
+            loss += lv;                                           // :279
+            if (writer && lrow) lrow[k] = lv;
+        } else {
+            wide_barrier();
+        }
+    }
+    if constexpr (SCORE) {
+        if (writer) SC.loss[clip1 ? b1 : b0] = loss;
     }
     if constexpr (STREAM) {
         if (ST.out && (!clip1 || two)) {
@@ -1364,7 +1409,7 @@ hipError_t launch_sample_wide(const Dev& P, const float* noise, int n, int lengt
     return dispatch_pd(P.DP, [&](auto pd) {
         constexpr int PD = decltype(pd)::value;
         hipLaunchKernelGGL((k_sample_wide<PD, false>), dim3(nb), dim3(4 * PD), 0, s, P, noise, n, length, out, (const float*)nullptr, 0, 0, (float*)nullptr,
-                           StreamDev{});
+                           StreamDev{}, ScoreDev{});
         return hipGetLastError();
     });
 }
@@ -1374,7 +1419,7 @@ hipError_t launch_sample_wide_primed(const Dev& P, const float* prime, int prime
     const unsigned nb = (unsigned)((n + 1) / 2);
     return dispatch_pd(P.DP, [&](auto pd) {
         constexpr int PD = decltype(pd)::value;
-        hipLaunchKernelGGL((k_sample_wide<PD, true>), dim3(nb), dim3(4 * PD), 0, s, P, noise, n, length, out, prime, prime_stride, PF, pred, StreamDev{});
+        hipLaunchKernelGGL((k_sample_wide<PD, true>), dim3(nb), dim3(4 * PD), 0, s, P, noise, n, length, out, prime, prime_stride, PF, pred, StreamDev{}, ScoreDev{});
         return hipGetLastError();
     });
 }
@@ -1384,7 +1429,18 @@ hipError_t launch_sample_wide_stream(const Dev& P, const StreamDev& ST, const fl
     const unsigned nb = (unsigned)((n + 1) / 2);
     return dispatch_pd(P.DP, [&](auto pd) {
         constexpr int PD = decltype(pd)::value;
-        hipLaunchKernelGGL((k_sample_wide<PD, true, true>), dim3(nb), dim3(4 * PD), 0, s, P, noise, n, length, out, audio, audio_stride, PF, pred, ST);
+        hipLaunchKernelGGL((k_sample_wide<PD, true, true>), dim3(nb), dim3(4 * PD), 0, s, P, noise, n, length, out, audio, audio_stride, PF, pred, ST, ScoreDev{});
+        return hipGetLastError();
+    });
+}
+
+hipError_t launch_sample_wide_score(const Dev& P, const StreamDev& ST, const ScoreDev& SC, const float* audio, int audio_stride, int PF, int n, float* pred,
+                                    hipStream_t s) {
+    const unsigned nb = (unsigned)((n + 1) / 2);
+    return dispatch_pd(P.DP, [&](auto pd) {
+        constexpr int PD = decltype(pd)::value;
+        hipLaunchKernelGGL((k_sample_wide<PD, true, true, true>), dim3(nb), dim3(4 * PD), 0, s, P, (const float*)nullptr, n, 0, (float*)nullptr, audio,
+                           audio_stride, PF, pred, ST, SC);
         return hipGetLastError();
     });
 }

@@ -259,6 +259,11 @@ class CMPS(_ScanModel):
         rho_stream_state / rho_stream."""
         raise NotImplementedError
 
+    def _stream_score_entry(self, be):
+        """The backend's scored segment entry for this model (HipScan.stream_score).  PsiCMPS only: cmps_rho_stream_score does not exist."""
+        raise ValueError(f"scoring a stream is PsiCMPS-only: {type(self).__name__} has no scored sampler (cmps_psi_stream_score has no "
+                         "RhoCMPS counterpart yet)")
+
     def _prepare_stream(self, num_paths, max_steps, keep_states=0):
         """The backend as a stream needs it: T = max_steps + 1, one table row per step."""
         return self._prepare(num_paths, max_steps + 1, train=False)
@@ -443,6 +448,29 @@ class PsiCMPS(CMPS):
 
     def _stream_entries(self, be):
         return be.stream_state, be.stream
+
+    def _stream_score_entry(self, be):
+        return be.stream_score
+
+    def nll_per_step(self, data=None, segment=None) -> np.ndarray:
+        """The fold's increment of every step, [B, T - 1]: -log(1 + e' x / A) of model.py:276-282, 293-294 (the reference only returns
+        their sum).  One scored stream over the batch (cmps_psi_stream_score), cut into segments of ``segment`` steps when given -- the
+        cut changes no bit.  Row sums are ``loss_per_clip`` to float32 rounding."""
+        data = self._batch(data)
+        if hasattr(data, "detach"):
+            data = data.detach().cpu().numpy()
+        data = np.asarray(data, dtype=np.float32)
+        if data.ndim != 2 or data.shape[1] < 2:
+            raise ValueError("data must be [B, T] with T >= 2")
+        B, N = data.shape[0], data.shape[1] - 1
+        S = N if segment is None else int(segment)
+        if S < 1:
+            raise ValueError("segment must be positive")
+        st = self.open_stream(B, N)
+        parts = [st.score(data[:, :S + 1])]                           # the anchor and S steps
+        for a in range(S + 1, N + 1, S):
+            parts.append(st.score(data[:, a:a + S]))
+        return np.concatenate(parts, axis=1)
 
 
 # --------------------------------------------------------------------------------------------------

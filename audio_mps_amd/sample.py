@@ -11,6 +11,10 @@ waveform is the clip followed by its continuation.  Writes ``sample_<i>.wav`` (1
 [-1, 1)) and ``samples.npy`` (float32 [num_samples, samples], unclipped) into --out_dir.
 ``--segment S`` runs the same job through a resumable stream (model.open_stream; cmps_psi_stream / cmps_rho_stream) in segments of S steps: the
 prime, if given, is followed, then the waveform is generated; the files and the return value are the same.
+``--score FILE`` (PsiCMPS; a clip as --prime reads it) samples nothing: the clip is followed and scored through a stream
+(SampleStream.score; cmps_psi_stream_score), in segments of --segment steps when given.  Writes ``nll.npy`` (float32 [clips, T' - 1]: the
+negative log-likelihood of every sample, model.py:293-294) and ``pred.npy`` (the model's expected increments) into --out_dir and prints
+the total and the mean per sample; returns the nll array.
 Run:  python -m audio_mps_amd.sample --modeldir=LOGDIR --sample_duration=16000 --prime=clip.wav
 """
 from __future__ import annotations
@@ -83,6 +87,7 @@ def build_parser():
     p.add_argument("--temp", type=float, default=1.0, help="noise temperature (model.py:246)")
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--prime", default=None, metavar="FILE", help=".wav (16-bit mono) or .npy clip to continue")
+    p.add_argument("--score", default=None, metavar="FILE", help=".wav (16-bit mono) or .npy clip to follow and score instead of sampling (PsiCMPS)")
     p.add_argument("--segment", type=int, default=None, metavar="S", help="run through a resumable stream in segments of S steps")
     p.add_argument("--out_dir", default="./samples")
     p.add_argument("--kernel_variant", type=int, default=0, help="as in audio_mps_amd.train")
@@ -104,6 +109,29 @@ def _segmented(model, args, n, length):
     for a in range(0, length, S):
         parts.append(st.generate(min(S, length - a)))
     return np.concatenate(parts, axis=1)
+
+
+def _scored(model, args):
+    """--score: the clip followed and scored through a SampleStream, whole or in segments of --segment steps; writes nll.npy / pred.npy."""
+    clip = load_prime(args.score, args.sample_rate)
+    clip = clip[None, :] if clip.ndim == 1 else clip
+    if clip.ndim != 2 or clip.shape[1] < 2:
+        raise ValueError(f"--score {args.score}: need [T'] or [n, T'] with two samples at least (one increment), not {clip.shape}")
+    n, N = clip.shape[0], clip.shape[1] - 1
+    S = N if args.segment is None else args.segment
+    st = model.open_stream(n, N)
+    nll, pred = [st.score(clip[:, :S + 1])], [st.last_pred]       # the anchor and S steps
+    for a in range(S + 1, N + 1, S):
+        nll.append(st.score(clip[:, a:a + S]))
+        pred.append(st.last_pred)
+    nll = np.ascontiguousarray(np.concatenate(nll, axis=1), dtype=np.float32)
+    pred = np.ascontiguousarray(np.concatenate(pred, axis=1), dtype=np.float32)
+    os.makedirs(args.out_dir, exist_ok=True)
+    np.save(os.path.join(args.out_dir, "nll.npy"), nll)
+    np.save(os.path.join(args.out_dir, "pred.npy"), pred)
+    total = float(np.sum(st.total_nll, dtype=np.float64))
+    print(f"scored {n} clip(s) of {N} steps: total nll {total:.6g}, mean per sample {total / (n * N):.6g}; wrote nll.npy and pred.npy to {args.out_dir}")
+    return nll
 
 
 def main(argv=None, backend=None):
@@ -131,9 +159,15 @@ def main(argv=None, backend=None):
             raise ValueError(f"checkpoint variable {k} has shape {variables[k].shape}, bond_dim={hp.bond_dim} needs {model.variables[k].shape}")
         model.variables[k] = variables[k]
     n, length = args.num_samples, args.sample_duration
+    if args.segment is not None and args.segment < 1:
+        raise ValueError("--segment must be positive")
+    if args.score is not None:
+        if args.prime is not None:
+            raise ValueError("--score follows and scores its clip and samples nothing: it does not go with --prime")
+        if rho:
+            raise ValueError("--score needs a PsiCMPS checkpoint: scoring a stream is PsiCMPS-only (RhoCMPS has no scored sampler yet)")
+        return _scored(model, args)
     if args.segment is not None:
-        if args.segment < 1:
-            raise ValueError("--segment must be positive")
         waves = _segmented(model, args, n, length)
     elif args.prime is None:
         waves = model.sample(n, length, temp=args.temp, seed=args.seed) / model.A

@@ -116,7 +116,7 @@ class HipScan:
         return mode if mode in (_capi.CMPS_RANK1_EXACT_F32, _capi.CMPS_RANK1_BF16X2, _capi.CMPS_RANK1_F16X2) else _capi.CMPS_RANK1_BF16X3
 
     def kernel_events(self, on: bool):
-        """cmps_set_option(CMPS_OPT_KERNEL_EVENTS): bracket every kernel of forward() / backward() and of sample() / sample_primed() / stream() / rho_sample_primed() / rho_stream() with HIP
+        """cmps_set_option(CMPS_OPT_KERNEL_EVENTS): bracket every kernel of forward() / backward() and of sample() / sample_primed() / stream() / stream_score() / rho_sample_primed() / rho_stream() with HIP
         events (a measurement aid, used by bench.py outside its timed region)."""
         _capi.check(self._h, self._lib.cmps_set_option(self._h, _capi.CMPS_OPT_KERNEL_EVENTS, 1 if on else 0))
 
@@ -455,6 +455,40 @@ class HipScan:
         the noise, else from a state tensor, else from ``n`` or the audio's rows."""
         return self._stream_call(self._lib.cmps_psi_stream, self._lib.cmps_psi_stream_state_bytes, state_in, state_out, k0, audio, noise,
                                  want_pred, n)
+
+    def stream_score(self, state_in: Optional[torch.Tensor], state_out: Optional[torch.Tensor], k0: int, audio, want_nll: bool = True,
+                     want_pred: bool = False, n: Optional[int] = None, loss=None):
+        """cmps_psi_stream_score, one scored segment of a resumable scan on table rows k0 ..: `stream`'s forced steps on ``audio``
+        [n_audio, forced + 1] (forced >= 1) that also give the loss increment of every step.  ``loss`` [n] is the running loss to
+        continue (not read at k0 = 0).  ``loss=None`` on a resumed segment (k0 > 0) starts the total again from zero: the caller keeps
+        the total, the state record does not.  Returns (nll [n, forced] with want_nll else None, the running loss [n] behind the
+        segment, pred [n, forced] with want_pred else None).  The states are `stream`'s: a scan may alternate between the two."""
+        audio = np.array(audio, dtype=np.float32, order="C")           # (a copy: torch wants a writable array)
+        if audio.ndim != 2 or audio.shape[1] < 2:
+            raise ValueError("audio must be [n_audio, forced + 1] with forced >= 1")
+        n_audio, forced = audio.shape[0], audio.shape[1] - 1
+        if n is None:
+            st = state_out if state_out is not None else state_in
+            n = st.numel() // int(self._lib.cmps_psi_stream_state_bytes(self._h, 1)) if st is not None else n_audio
+        n = int(n)
+        for st in (state_in, state_out):
+            if st is not None and not (st.is_cuda and st.dtype == torch.uint8 and st.is_contiguous()
+                                       and st.numel() == int(self._lib.cmps_psi_stream_state_bytes(self._h, n))):
+                raise ValueError(f"a stream state must be the tensor stream_state({n}) returned")
+        if loss is None:
+            d_loss = torch.zeros(n, dtype=torch.float32, device=self.device)
+        else:
+            loss = np.array(loss, dtype=np.float32, order="C")
+            if loss.shape != (n,):
+                raise ValueError(f"loss must be [{n}]")
+            d_loss = torch.from_numpy(loss).to(self.device)
+        d_audio = torch.from_numpy(audio).to(self.device)
+        d_nll = torch.empty((n, forced), dtype=torch.float32, device=self.device) if want_nll else None
+        d_pred = torch.empty((n, forced), dtype=torch.float32, device=self.device) if want_pred else None
+        ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None   # noqa: E731
+        _capi.check(self._h, self._lib.cmps_psi_stream_score(self._h, ptr(state_in), ptr(state_out), int(k0), ptr(d_audio), n_audio, forced, n,
+                                                             ptr(d_nll), ptr(d_loss), ptr(d_pred), self._stream()))
+        return (d_nll.cpu().numpy() if want_nll else None), d_loss.cpu().numpy(), (d_pred.cpu().numpy() if want_pred else None)
 
     # ------------------------------------------------------------------
     # legacy AudioMPS arithmetic (SURVEY 8f rank 2)

@@ -6,6 +6,7 @@ the sampler kernel carries between two steps on the device, so a scan can be con
 
     st = model.open_stream(num_paths=4, max_steps=3 * 16000, seed=0)
     pred = st.follow(block)             # [4, steps]: the model's expected increment before every followed sample
+    nll = st.score(block2)              # [4, steps]: follow, and how likely every sample was (PsiCMPS); st.total_nll sums them
     wave = st.generate(16000)           # [4, 16000] in the clip's own units, continuing the followed signal
     wave2 = st.generate(16000)          # ... and on from there
 
@@ -37,6 +38,9 @@ class SampleStream:
         new_state, self._segment = model._stream_entries(self._be)
         self._state = new_state(self.num_paths)
         self._level = None             # inside a sampled run: the level it began at
+        self._model = model
+        self.total_nll = np.zeros(self.num_paths, dtype=np.float32)   # the fold carry of the scored steps so far (model.py:279)
+        self.last_pred = None          # the predictions of the last score call
 
     # ------------------------------------------------------------------
     def _launch(self, steps, audio, noise, want_pred):
@@ -76,12 +80,8 @@ class SampleStream:
             raise ValueError(f"a block must be [m], [1, m] or [{self.num_paths}, m] with m >= 1, not {block.shape}")
         return block
 
-    def follow(self, block, anchor: bool = False) -> np.ndarray:
-        """Teacher-force the stream on ``block`` ([num_paths, m], or [m] / [1, m] for one signal shared by every path; the clip's own
-        units).  On a stream that has seen no audio the block's first sample is the anchor X_0 and makes no step; later blocks make one
-        step per sample, the first one from the stream's last sample.  ``anchor=True`` re-anchors on ``block[..., 0]`` without a step
-        (to resume behind a generated gap without showing the model the jump).  Returns the model's expected increment before every
-        step, [num_paths, steps]."""
+    def _anchored(self, block, anchor):
+        """(block, the audio of a forced call [n_audio, steps + 1]): the block behind the sample it continues from, follow's rule."""
         block = self._block(block)
         n = self.num_paths
         if anchor or self.last is None:
@@ -90,6 +90,40 @@ class SampleStream:
             audio = np.concatenate([self.last[:1, None], block], axis=1)
         else:
             audio = np.concatenate([self.last[:, None], np.broadcast_to(block, (n, block.shape[1]))], axis=1)
+        return block, audio
+
+    def score(self, block, anchor: bool = False) -> np.ndarray:
+        """``follow`` that also says how likely the block was (PsiCMPS; cmps_psi_stream_score): same arguments, anchoring rule and
+        bookkeeping, returns the negative log-likelihood of every step, [num_paths, steps] = -log(1 + e' x / A) of model.py:293-294,
+        and adds them to ``total_nll`` [num_paths] in step order (the fold carry of model.py:279; over a whole clip from a fresh
+        stream: ``loss_per_clip``).  The predictions ``follow`` would have returned are in ``last_pred``.  Scoring changes nothing the
+        stream carries: ``follow``, ``score`` and ``generate`` alternate freely, and unscored steps leave ``total_nll`` as it is."""
+        entry = self._model._stream_score_entry(self._be)
+        block, audio = self._anchored(block, anchor)
+        n, steps = self.num_paths, audio.shape[1] - 1
+        nll = np.empty((n, 0), dtype=np.float32)
+        pred = np.empty((n, 0), dtype=np.float32)
+        if steps:
+            if self.position + steps > self.max_steps:
+                raise ValueError(f"the stream was opened for max_steps={self.max_steps}: {self.position} taken, {steps} more asked for")
+            nll, total, pred = entry(self._state if self.position else None, self._state, self.position, np.ascontiguousarray(audio),
+                                     want_nll=True, want_pred=True, n=n, loss=self.total_nll)
+            self.total_nll = np.asarray(total, dtype=np.float32)
+            self.position += steps
+            self._saved = None
+        self.last_pred = pred
+        self.last = np.array(np.broadcast_to(block[:, -1], (n,)), dtype=np.float32)
+        self._level = None
+        return nll
+
+    def follow(self, block, anchor: bool = False) -> np.ndarray:
+        """Teacher-force the stream on ``block`` ([num_paths, m], or [m] / [1, m] for one signal shared by every path; the clip's own
+        units).  On a stream that has seen no audio the block's first sample is the anchor X_0 and makes no step; later blocks make one
+        step per sample, the first one from the stream's last sample.  ``anchor=True`` re-anchors on ``block[..., 0]`` without a step
+        (to resume behind a generated gap without showing the model the jump).  Returns the model's expected increment before every
+        step, [num_paths, steps]."""
+        block, audio = self._anchored(block, anchor)
+        n = self.num_paths
         steps = audio.shape[1] - 1
         pred = np.empty((n, 0), dtype=np.float32)
         if steps:

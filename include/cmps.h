@@ -84,7 +84,7 @@ enum {
     CMPS_OPT_F16_SCALE_SHIFT = 4 /* DIAGNOSTIC, default 0: added to the exponent of every data-dependent fp16 scale of the wave reverse
                         * scan's F16X2 arithmetic (range -40 .. 40).  A positive value pushes the pieces out of fp16 range on purpose:
                         * how tests/test_gpu_parity.py provokes CMPS_ERR_F16_RANGE.  No reference counterpart. */,
-    CMPS_OPT_KERNEL_EVENTS = 2 /* 1: every kernel cmps_psi_loss_fwd / _bwd, cmps_psi_sample, cmps_psi_sample_primed, cmps_psi_stream, cmps_rho_sample_primed and cmps_rho_stream launch is bracketed by two HIP events on the caller's stream
+    CMPS_OPT_KERNEL_EVENTS = 2 /* 1: every kernel cmps_psi_loss_fwd / _bwd, cmps_psi_sample, cmps_psi_sample_primed, cmps_psi_stream, cmps_psi_stream_score, cmps_rho_sample_primed and cmps_rho_stream launch is bracketed by two HIP events on the caller's stream
                         * (read and reset with cmps_kernel_times); 0 (default): nothing is recorded.  A measurement aid -- the reference
                         * has no counterpart (no tracing / profiling hooks); bench.py uses it OUTSIDE its timed region to price
                         * each kernel of a multi-kernel family against the pipe it runs on */
@@ -329,6 +329,32 @@ int cmps_psi_stream(cmps_handle_t h, const void* state_in_dev, void* state_out_d
                     const float* audio_dev, int n_audio, int forced,
                     const float* noise_dev, int length,
                     int n, float* out_dev, float* pred_dev, void* stream);
+
+/*
+ * One scored segment of a resumable scan: `forced` steps of cmps_psi_stream (forced steps only, same conventions: audio_dev
+ * [n_audio, forced + 1] with the one-sample overlap, n_audio in {1, n}, state_in_dev == NULL <=> k0 == 0, state_out_dev NULL or equal to
+ * state_in_dev, table rows k0 .. k0 + forced - 1) that also give the loss increment of every step (model.py:276-282, 293-294):
+ *   step j:  y_j = u + Q u + s R u on the normalised state u, s = x_j / A, x_j = audio[b'][j + 1] - audio[b'][j]  (the followed step);
+ *            e'  = 2 Re(y_j^dagger R y_j) in float32 on the updated, UN-normalised state, still in the frame of t_j;
+ *            z   = (e' * x_j) / A;   nll[b][j] = -logf(1.0f + z)   -- the operation order of cmps_psi_loss_fwd (model.py:294);
+ *            loss[b] += nll[b][j], sequentially in step order in float32 (model.py:279).
+ * pred_dev[b][j] holds 2 Re<u|R|u> * delta_t on the state BEFORE the step; the increment needs its own product R y_j (another state,
+ * another frame than the next step's rho_j y_j), which is what this entry adds to a followed step.  Nothing of it feeds the chain:
+ * pred and the state record carry the bits cmps_psi_stream gives on the same steps, the record is the one
+ * cmps_psi_stream_state_bytes describes, and a stream may alternate between this entry and cmps_psi_stream freely.
+ * nll_dev [n * forced] row-major [path][step], or NULL.  loss_dev [n], required: the running loss lives with the caller, not in the
+ * record.  At the start of a stream (state_in_dev == NULL) it is not read and is written from 0; otherwise it is loaded once, continued,
+ * and stored once behind the last step.  Cut anywhere, nll, loss, pred and the final record keep their bits; over a whole clip from
+ * k0 = 0 loss is the clip's cmps_psi_loss_fwd to rounding.  Where 1 + z <= 0 the NaN / Inf of the logarithm propagates into nll and
+ * loss, as in the loss entries.
+ * CMPS_ERR_BAD_ARG: cmps_psi_stream's (with length = 0), and forced < 1 or loss_dev == NULL; k0 + forced > T - 1 with a message naming
+ * the needed T >= k0 + forced + 1.  CMPS_ERR_STATE before cmps_set_params* and in legacy mode.
+ * Asynchronous on `stream`; never synchronises, allocates nothing.  The kernel is chosen as cmps_psi_sample chooses it; with
+ * CMPS_OPT_KERNEL_EVENTS the launch is recorded as k_sample_wave_score, k_sample_wide_score or k_sample_block_score.
+ */
+int cmps_psi_stream_score(cmps_handle_t h, const void* state_in_dev, void* state_out_dev, int k0,
+                          const float* audio_dev, int n_audio, int forced, int n,
+                          float* nll_dev, float* loss_dev, float* pred_dev, void* stream);
 
 /*
  * Legacy `AudioMPS` arithmetic (the model training_estimators.py:43-45 was written for; its class body is gone from
