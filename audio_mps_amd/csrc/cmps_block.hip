@@ -531,44 +531,15 @@ hipError_t launch_update_ancilla(const Dev& P, const float* psi_in, const float*
     return hipGetLastError();
 }
 
-hipError_t launch_sample_block(const Dev& P, const float* noise, int n, int length, float* out, hipStream_t s) {
-    const size_t shm = (size_t)P.D * sizeof(float2) + 64;
+hipError_t launch_sample_block(const Dev& P, const SampleDev& S, hipStream_t s) {
     return dispatch_block_nt(P.D, [&](auto nt) {
-        constexpr int NT = decltype(nt)::value;
-        hipLaunchKernelGGL((k_sample_block<NT, false>), dim3(n), dim3(NT), shm, s, P, noise, length, out, (const float*)nullptr, 0, 0, (float*)nullptr,
-                           StreamDev{}, ScoreDev{});
-        return hipGetLastError();
-    });
-}
-
-hipError_t launch_sample_block_primed(const Dev& P, const float* prime, int prime_stride, int PF, const float* noise, int n, int length,
-                                      float* out, float* pred, hipStream_t s) {
-    const size_t shm = (size_t)P.D * sizeof(float2) + 64;
-    return dispatch_block_nt(P.D, [&](auto nt) {
-        constexpr int NT = decltype(nt)::value;
-        hipLaunchKernelGGL((k_sample_block<NT, true>), dim3(n), dim3(NT), shm, s, P, noise, length, out, prime, prime_stride, PF, pred, StreamDev{}, ScoreDev{});
-        return hipGetLastError();
-    });
-}
-
-hipError_t launch_sample_block_stream(const Dev& P, const StreamDev& ST, const float* audio, int audio_stride, int PF, const float* noise, int n,
-                                      int length, float* out, float* pred, hipStream_t s) {
-    const size_t shm = (size_t)P.D * sizeof(float2) + 64;
-    return dispatch_block_nt(P.D, [&](auto nt) {
-        constexpr int NT = decltype(nt)::value;
-        hipLaunchKernelGGL((k_sample_block<NT, true, true>), dim3(n), dim3(NT), shm, s, P, noise, length, out, audio, audio_stride, PF, pred, ST, ScoreDev{});
-        return hipGetLastError();
-    });
-}
-
-hipError_t launch_sample_block_score(const Dev& P, const StreamDev& ST, const ScoreDev& SC, const float* audio, int audio_stride, int PF, int n, float* pred,
-                                     hipStream_t s) {
-    const size_t shm = (size_t)2 * P.D * sizeof(float2) + 64;
-    return dispatch_block_nt(P.D, [&](auto nt) {
-        constexpr int NT = decltype(nt)::value;
-        hipLaunchKernelGGL((k_sample_block<NT, true, true, true>), dim3(n), dim3(NT), shm, s, P, (const float*)nullptr, 0, (float*)nullptr, audio,
-                           audio_stride, PF, pred, ST, SC);
-        return hipGetLastError();
+        return dispatch_sample_mode(sample_mode(S), [&](auto mode) {
+            constexpr int NT = decltype(nt)::value, M = decltype(mode)::value;
+            const size_t shm = (size_t)(M == SAMPLE_SCORE ? 2 : 1) * P.D * sizeof(float2) + 64;      // (SCORE: y_k behind u)
+            hipLaunchKernelGGL((k_sample_block<NT, M >= SAMPLE_PRIMED, M >= SAMPLE_STREAM, M == SAMPLE_SCORE>), dim3(S.n), dim3(NT), shm, s, P, S.noise,
+                               S.length, S.out, S.PR.prime, S.PR.stride, S.PR.PF, S.PR.pred, stream_of(S), score_of(S));
+            return hipGetLastError();
+        });
     });
 }
 

@@ -538,35 +538,50 @@ static int stream_rec_floats(const cmps_handle_s* h) {
     const int family = sampler_family(h);
     return family == SAMPLER_WAVE ? STREAM_REC_WAVE : family == SAMPLER_WIDE ? stream_rec_wide(padded_D(h->D)) : stream_rec_block(h->D);
 }
-// The kernel choice and the launch.  clips == nullptr and ST == nullptr: the unprimed sampler; ST == nullptr: the primed one (`forced`
-// teacher-forced steps on clips[path * clip_stride + k]); else one segment of a stream, scored when SC is set.
-static int psi_sample_launch(cmps_handle_t h, const char* who, const float* clips, int clip_stride, int forced, const float* noise_dev, int n,
-                      int length, float* out_dev, float* pred_dev, const StreamDev* ST, void* stream, const ScoreDev* SC = nullptr) {
+// What cmps_{psi,rho}_sample_primed check behind their state check, and the launch record of the call
+static int primed_args(cmps_handle_t h, const char* who, const float* prime_dev, int n_prime, int prime_T, const float* noise_dev, int n, int length,
+                       float* out_dev, float* pred_dev, SampleDev& S) {
+    const std::string w(who);
+    if (!prime_dev || !noise_dev || !out_dev) return fail(h, CMPS_ERR_BAD_ARG, w + ": null pointer");
+    if (n < 1 || length < 1) return fail(h, CMPS_ERR_BAD_ARG, w + ": need n >= 1 and length >= 1");
+    if (prime_T < 2) return fail(h, CMPS_ERR_BAD_ARG, w + ": need prime_T >= 2 (one increment at least)");
+    if (int c = sample_check_clips(h, who, "n_prime", n_prime, n)) return c;
+    const int PF = prime_T - 1;                                  // teacher-forced steps
+    if (int c = sample_check_rows(h, who, "prime_T + length", (long long)PF + length)) return c;
+    S = SampleDev{noise_dev, n, length, out_dev, PrimeDev{prime_dev, n_prime == 1 ? 0 : prime_T, PF, pred_dev}, nullptr, nullptr};
+    return CMPS_OK;
+}
+// The same for cmps_{psi,rho}_stream (`rec`: floats of one state record); ST is the caller's, S points to it.  cmps_psi_stream_score, whose
+// messages and stricter lines are its own, shares the state rule
+static int stream_check_state(cmps_handle_t h, const char* who, const void* state_in_dev, int k0) {
+    if ((state_in_dev == nullptr) == (k0 == 0)) return CMPS_OK;
+    return fail(h, CMPS_ERR_BAD_ARG, std::string(who) + ": state_in_dev is NULL exactly at the start of a stream (k0 == 0)");
+}
+static int stream_args(cmps_handle_t h, const char* who, const void* state_in_dev, void* state_out_dev, int k0, const float* audio_dev, int n_audio,
+                       int forced, const float* noise_dev, int length, int n, float* out_dev, float* pred_dev, int rec, StreamDev& ST, SampleDev& S) {
+    const std::string w(who);
+    if (n < 1 || forced < 0 || length < 0 || (long long)forced + length < 1 || k0 < 0)
+        return fail(h, CMPS_ERR_BAD_ARG, w + ": need n >= 1, forced >= 0, length >= 0, forced + length >= 1 and k0 >= 0");
+    if (int c = stream_check_state(h, who, state_in_dev, k0)) return c;
+    if (forced > 0 && !audio_dev) return fail(h, CMPS_ERR_BAD_ARG, w + ": forced > 0 needs audio_dev");
+    if (length > 0 && (!noise_dev || !out_dev)) return fail(h, CMPS_ERR_BAD_ARG, w + ": length > 0 needs noise_dev and out_dev");
+    if (int c = sample_check_clips(h, who, "n_audio", n_audio, n)) return c;
+    if (int c = sample_check_rows(h, who, "k0 + forced + length + 1", (long long)k0 + forced + length)) return c;
+    ST = StreamDev{static_cast<const float*>(state_in_dev), static_cast<float*>(state_out_dev), k0, rec};
+    S = SampleDev{noise_dev, n, length, out_dev, PrimeDev{audio_dev, n_audio == 1 ? 0 : forced + 1, forced, pred_dev}, &ST, nullptr};
+    return CMPS_OK;
+}
+// The kernel choice and the launch of one SampleDev
+static int psi_sample_launch(cmps_handle_t h, const char* who, const SampleDev& S, void* stream) {
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int family = sampler_family(h);
     static const char* const names[3][4] = {{"k_sample_block", "k_sample_block_primed", "k_sample_block_stream", "k_sample_block_score"},
                                             {"k_sample_wave", "k_sample_wave_primed", "k_sample_wave_stream", "k_sample_wave_score"},
-                                            {"k_sample_wide", "k_sample_wide_primed", "k_sample_wide_stream", "k_sample_wide_score"}};
-    const int mode = ST ? (SC ? 3 : 2) : clips ? 1 : 0;
+                                            {"k_sample_wide", "k_sample_wide_primed", "k_sample_wide_stream", "k_sample_wide_score"}};   // [family][SampleMode]
     KBind kb(h);
-    KScope ks(names[family][mode], s);
-    hipError_t e;
-    if (mode == 0)
-        e = family == SAMPLER_WAVE ? launch_sample_wave(h->P, noise_dev, n, length, out_dev, s)
-          : family == SAMPLER_WIDE ? launch_sample_wide(h->P, noise_dev, n, length, out_dev, s)
-                                   : launch_sample_block(h->P, noise_dev, n, length, out_dev, s);
-    else if (mode == 1)
-        e = family == SAMPLER_WAVE ? launch_sample_wave_primed(h->P, clips, clip_stride, forced, noise_dev, n, length, out_dev, pred_dev, s)
-          : family == SAMPLER_WIDE ? launch_sample_wide_primed(h->P, clips, clip_stride, forced, noise_dev, n, length, out_dev, pred_dev, s)
-                                   : launch_sample_block_primed(h->P, clips, clip_stride, forced, noise_dev, n, length, out_dev, pred_dev, s);
-    else if (mode == 3)
-        e = family == SAMPLER_WAVE ? launch_sample_wave_score(h->P, *ST, *SC, clips, clip_stride, forced, n, pred_dev, s)
-          : family == SAMPLER_WIDE ? launch_sample_wide_score(h->P, *ST, *SC, clips, clip_stride, forced, n, pred_dev, s)
-                                   : launch_sample_block_score(h->P, *ST, *SC, clips, clip_stride, forced, n, pred_dev, s);
-    else
-        e = family == SAMPLER_WAVE ? launch_sample_wave_stream(h->P, *ST, clips, clip_stride, forced, noise_dev, n, length, out_dev, pred_dev, s)
-          : family == SAMPLER_WIDE ? launch_sample_wide_stream(h->P, *ST, clips, clip_stride, forced, noise_dev, n, length, out_dev, pred_dev, s)
-                                   : launch_sample_block_stream(h->P, *ST, clips, clip_stride, forced, noise_dev, n, length, out_dev, pred_dev, s);
+    KScope ks(names[family][sample_mode(S)], s);
+    const hipError_t e = family == SAMPLER_WAVE ? launch_sample_wave(h->P, S, s)
+                       : family == SAMPLER_WIDE ? launch_sample_wide(h->P, S, s) : launch_sample_block(h->P, S, s);
     if (e != hipSuccess) return fail_hip(h, e, who);
     return CMPS_OK;
 }
@@ -578,7 +593,7 @@ int cmps_psi_sample(cmps_handle_t h, const float* noise_dev, int n, int length, 
         return fail(h, CMPS_ERR_BAD_ARG, "cmps_psi_sample: bad argument");
     if (length > h->L.N)
         return fail(h, CMPS_ERR_BAD_ARG, "cmps_psi_sample: length exceeds T - 1 of cmps_set_params (the per-step tables)");
-    return psi_sample_launch(h, "cmps_psi_sample", nullptr, 0, 0, noise_dev, n, length, out_dev, nullptr, nullptr, stream);
+    return psi_sample_launch(h, "cmps_psi_sample", SampleDev{noise_dev, n, length, out_dev, PrimeDev{}, nullptr, nullptr}, stream);
 }
 
 int cmps_psi_sample_primed(cmps_handle_t h, const float* prime_dev, int n_prime, int prime_T, const float* noise_dev, int n, int length,
@@ -586,14 +601,9 @@ int cmps_psi_sample_primed(cmps_handle_t h, const float* prime_dev, int n_prime,
     if (!h) return CMPS_ERR_BAD_ARG;
     if (!h->params_set || h->legacy)       // (the legacy tables carry no rotation and another step: nothing here would mean PsiCMPS.sample)
         return fail(h, CMPS_ERR_STATE, "cmps_psi_sample_primed: call cmps_set_params first (not available in legacy mode)");
-    if (!prime_dev || !noise_dev || !out_dev) return fail(h, CMPS_ERR_BAD_ARG, "cmps_psi_sample_primed: null pointer");
-    if (n < 1 || length < 1) return fail(h, CMPS_ERR_BAD_ARG, "cmps_psi_sample_primed: need n >= 1 and length >= 1");
-    if (prime_T < 2) return fail(h, CMPS_ERR_BAD_ARG, "cmps_psi_sample_primed: need prime_T >= 2 (one increment at least)");
-    if (int c = sample_check_clips(h, "cmps_psi_sample_primed", "n_prime", n_prime, n)) return c;
-    const int PF = prime_T - 1;                                  // teacher-forced steps
-    if (int c = sample_check_rows(h, "cmps_psi_sample_primed", "prime_T + length", (long long)PF + length)) return c;
-    return psi_sample_launch(h, "cmps_psi_sample_primed", prime_dev, n_prime == 1 ? 0 : prime_T, PF, noise_dev, n, length, out_dev, pred_dev,
-                             nullptr, stream);
+    SampleDev S;
+    if (int c = primed_args(h, "cmps_psi_sample_primed", prime_dev, n_prime, prime_T, noise_dev, n, length, out_dev, pred_dev, S)) return c;
+    return psi_sample_launch(h, "cmps_psi_sample_primed", S, stream);
 }
 
 size_t cmps_psi_stream_state_bytes(cmps_handle_t h, int n) {
@@ -606,17 +616,12 @@ int cmps_psi_stream(cmps_handle_t h, const void* state_in_dev, void* state_out_d
     if (!h) return CMPS_ERR_BAD_ARG;
     if (!h->params_set || h->legacy)
         return fail(h, CMPS_ERR_STATE, "cmps_psi_stream: call cmps_set_params first (not available in legacy mode)");
-    if (n < 1 || forced < 0 || length < 0 || (long long)forced + length < 1 || k0 < 0)
-        return fail(h, CMPS_ERR_BAD_ARG, "cmps_psi_stream: need n >= 1, forced >= 0, length >= 0, forced + length >= 1 and k0 >= 0");
-    if ((state_in_dev == nullptr) != (k0 == 0))
-        return fail(h, CMPS_ERR_BAD_ARG, "cmps_psi_stream: state_in_dev is NULL exactly at the start of a stream (k0 == 0)");
-    if (forced > 0 && !audio_dev) return fail(h, CMPS_ERR_BAD_ARG, "cmps_psi_stream: forced > 0 needs audio_dev");
-    if (length > 0 && (!noise_dev || !out_dev)) return fail(h, CMPS_ERR_BAD_ARG, "cmps_psi_stream: length > 0 needs noise_dev and out_dev");
-    if (int c = sample_check_clips(h, "cmps_psi_stream", "n_audio", n_audio, n)) return c;
-    if (int c = sample_check_rows(h, "cmps_psi_stream", "k0 + forced + length + 1", (long long)k0 + forced + length)) return c;
-    const StreamDev ST{static_cast<const float*>(state_in_dev), static_cast<float*>(state_out_dev), k0, stream_rec_floats(h)};
-    return psi_sample_launch(h, "cmps_psi_stream", audio_dev, n_audio == 1 ? 0 : forced + 1, forced, noise_dev, n, length, out_dev, pred_dev,
-                             &ST, stream);
+    StreamDev ST;
+    SampleDev S;
+    if (int c = stream_args(h, "cmps_psi_stream", state_in_dev, state_out_dev, k0, audio_dev, n_audio, forced, noise_dev, length, n, out_dev, pred_dev,
+                            stream_rec_floats(h), ST, S))
+        return c;
+    return psi_sample_launch(h, "cmps_psi_stream", S, stream);
 }
 
 int cmps_psi_stream_score(cmps_handle_t h, const void* state_in_dev, void* state_out_dev, int k0, const float* audio_dev, int n_audio, int forced,
@@ -625,16 +630,15 @@ int cmps_psi_stream_score(cmps_handle_t h, const void* state_in_dev, void* state
     if (!h->params_set || h->legacy)
         return fail(h, CMPS_ERR_STATE, "cmps_psi_stream_score: call cmps_set_params first (not available in legacy mode)");
     if (n < 1 || forced < 1 || k0 < 0) return fail(h, CMPS_ERR_BAD_ARG, "cmps_psi_stream_score: need n >= 1, forced >= 1 and k0 >= 0");
-    if ((state_in_dev == nullptr) != (k0 == 0))
-        return fail(h, CMPS_ERR_BAD_ARG, "cmps_psi_stream_score: state_in_dev is NULL exactly at the start of a stream (k0 == 0)");
+    if (int c = stream_check_state(h, "cmps_psi_stream_score", state_in_dev, k0)) return c;
     if (!audio_dev) return fail(h, CMPS_ERR_BAD_ARG, "cmps_psi_stream_score: needs audio_dev");
     if (!loss_dev) return fail(h, CMPS_ERR_BAD_ARG, "cmps_psi_stream_score: needs loss_dev (the running loss per path)");
     if (int c = sample_check_clips(h, "cmps_psi_stream_score", "n_audio", n_audio, n)) return c;
     if (int c = sample_check_rows(h, "cmps_psi_stream_score", "k0 + forced + 1", (long long)k0 + forced)) return c;
     const StreamDev ST{static_cast<const float*>(state_in_dev), static_cast<float*>(state_out_dev), k0, stream_rec_floats(h)};
     const ScoreDev SC{nll_dev, loss_dev};
-    return psi_sample_launch(h, "cmps_psi_stream_score", audio_dev, n_audio == 1 ? 0 : forced + 1, forced, nullptr, n, 0, nullptr, pred_dev, &ST,
-                             stream, &SC);
+    const PrimeDev PR{audio_dev, n_audio == 1 ? 0 : forced + 1, forced, pred_dev};
+    return psi_sample_launch(h, "cmps_psi_stream_score", SampleDev{nullptr, n, 0, nullptr, PR, &ST, &SC}, stream);   // (every step is forced)
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -871,28 +875,30 @@ static int rho_stream_rec_floats(const cmps_handle_s* h) {
 }
 
 // What cmps_rho_sample, cmps_rho_sample_primed and cmps_rho_stream do behind their own argument checks: the workspace checks, the kernel
-// choice, the launch and the record for cmps_rho_states.  ST == nullptr and PR.prime == nullptr: unprimed; ST == nullptr: primed; else one
-// segment of a stream.  The scan has PR.PF + length steps.
-static int rho_sample_run(cmps_handle_t h, const char* who, const PrimeDev& PR, const StreamDev* ST, const float* noise_dev, int n, int length,
-                          float* out_dev, int save_states, void* stream) {
+// choice, the launch of one SampleDev and the record for cmps_rho_states.  The scan has S.PR.PF + S.length steps.
+static int rho_sample_run(cmps_handle_t h, const char* who, const SampleDev& S, int save_states, void* stream) {
     const std::string w(who);
-    const int steps = PR.PF + length;
+    const int n = S.n, steps = S.PR.PF + S.length;
     const bool mfma = rho_sampler_mfma(h);
+    const SampleMode mode = sample_mode(S);
+    if (mode == SAMPLE_SCORE) return fail_hip(h, hipErrorInvalidValue, who);      // (not reachable: no cmps_rho_stream_score; the tables below end at STREAM)
+    static const char* const names[2][3] = {{"k_sample_rho", "k_sample_rho_primed", "k_sample_rho_stream"},
+                                            {"k_sample_rho_mfma", "k_sample_rho_mfma_primed", "k_sample_rho_mfma_stream"}};   // [mfma][SampleMode]
+    static const char* const steps_name[3] = {"length", "(prime_T-1+length)", "(forced+length)"};
     // (only when the SAMPLER's three column arrays exceed the LDS: the workspace section exists from a smaller rank * D on, for the
     // reverse scan's four -- ADVICE r3)
     if (!mfma && rho_cols_spill(3, h->W.rank, h->P.D) && n > h->rho_B)
         return fail(h, CMPS_ERR_WORKSPACE, w + ": at this rank * D the columns live in the workspace: n must not exceed B_max");
     if (save_states && (!(h->rho_flags & CMPS_WS_TRAIN) || (size_t)n * steps > (size_t)h->rho_B * (h->rho_T - 1)))
-        return fail(h, CMPS_ERR_WORKSPACE, w + ": save_states needs a CMPS_WS_TRAIN rho workspace with B_max*(T-1) >= n*" +
-                                               (ST ? "(forced+length)" : PR.prime ? "(prime_T-1+length)" : "length"));
+        return fail(h, CMPS_ERR_WORKSPACE, w + ": save_states needs a CMPS_WS_TRAIN rho workspace with B_max*(T-1) >= n*" + steps_name[mode]);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    KBind kb(ST || PR.prime ? h : nullptr);                      // (cmps_rho_sample records no kernel events, as before)
-    KScope ks(ST ? (mfma ? "k_sample_rho_mfma_stream" : "k_sample_rho_stream") : (mfma ? "k_sample_rho_mfma_primed" : "k_sample_rho_primed"), s);
-    const hipError_t e = mfma ? launch_sample_rho_mfma(h->P, h->W, noise_dev, n, length, out_dev, save_states != 0, rank1_f16(h->rank1_mode), PR, ST, s)
-                              : launch_sample_rho(h->P, h->W, noise_dev, n, length, out_dev, save_states != 0, PR, ST, s);
+    KBind kb(mode != SAMPLE_PLAIN ? h : nullptr);                // (cmps_rho_sample records no kernel events, as before)
+    KScope ks(names[mfma][mode], s);
+    const hipError_t e = mfma ? launch_sample_rho_mfma(h->P, h->W, S, save_states != 0, rank1_f16(h->rank1_mode), s)
+                              : launch_sample_rho(h->P, h->W, S, save_states != 0, s);
     if (e != hipSuccess) return fail_hip(h, e, who);
     h->rho = Saved{save_states != 0, n, steps, nullptr, nullptr, mfma ? RHO_STASH_MFMA : RHO_STASH_BLOCK};   // (no reverse pass after a sampler)
-    h->rho.k0 = ST ? ST->k0 : 0;                                 // cmps_rho_states: the phases of the saved steps are ttab[k0 + k]
+    h->rho.k0 = S.ST ? S.ST->k0 : 0;                             // cmps_rho_states: the phases of the saved steps are ttab[k0 + k]
     return CMPS_OK;
 }
 
@@ -903,7 +909,7 @@ int cmps_rho_sample(cmps_handle_t h, const float* noise_dev, int n, int length, 
         return fail(h, CMPS_ERR_STATE, "cmps_rho_sample: call cmps_set_params and cmps_rho_set_state first");
     if (!noise_dev || !out_dev || n < 1 || length < 1) return fail(h, CMPS_ERR_BAD_ARG, "cmps_rho_sample: bad argument");
     if (length > h->L.N) return fail(h, CMPS_ERR_BAD_ARG, "cmps_rho_sample: length exceeds T - 1 of cmps_set_params");
-    return rho_sample_run(h, "cmps_rho_sample", PrimeDev{nullptr, 0, 0, nullptr}, nullptr, noise_dev, n, length, out_dev, save_states, stream);
+    return rho_sample_run(h, "cmps_rho_sample", SampleDev{noise_dev, n, length, out_dev, PrimeDev{}, nullptr, nullptr}, save_states, stream);
 }
 
 int cmps_rho_sample_primed(cmps_handle_t h, const float* prime_dev, int n_prime, int prime_T, const float* noise_dev, int n, int length,
@@ -911,14 +917,9 @@ int cmps_rho_sample_primed(cmps_handle_t h, const float* prime_dev, int n_prime,
     if (!h) return CMPS_ERR_BAD_ARG;
     if (!h->params_set || h->legacy || !h->rho_set)
         return fail(h, CMPS_ERR_STATE, "cmps_rho_sample_primed: call cmps_set_params and cmps_rho_set_state first (not available in legacy mode)");
-    if (!prime_dev || !noise_dev || !out_dev) return fail(h, CMPS_ERR_BAD_ARG, "cmps_rho_sample_primed: null pointer");
-    if (n < 1 || length < 1) return fail(h, CMPS_ERR_BAD_ARG, "cmps_rho_sample_primed: need n >= 1 and length >= 1");
-    if (prime_T < 2) return fail(h, CMPS_ERR_BAD_ARG, "cmps_rho_sample_primed: need prime_T >= 2 (one increment at least)");
-    if (int c = sample_check_clips(h, "cmps_rho_sample_primed", "n_prime", n_prime, n)) return c;
-    const int PF = prime_T - 1;                                  // teacher-forced steps
-    if (int c = sample_check_rows(h, "cmps_rho_sample_primed", "prime_T + length", (long long)PF + length)) return c;
-    return rho_sample_run(h, "cmps_rho_sample_primed", PrimeDev{prime_dev, n_prime == 1 ? 0 : prime_T, PF, pred_dev}, nullptr, noise_dev, n,
-                          length, out_dev, save_states, stream);
+    SampleDev S;
+    if (int c = primed_args(h, "cmps_rho_sample_primed", prime_dev, n_prime, prime_T, noise_dev, n, length, out_dev, pred_dev, S)) return c;
+    return rho_sample_run(h, "cmps_rho_sample_primed", S, save_states, stream);
 }
 
 size_t cmps_rho_stream_state_bytes(cmps_handle_t h, int n) {
@@ -931,17 +932,12 @@ int cmps_rho_stream(cmps_handle_t h, const void* state_in_dev, void* state_out_d
     if (!h) return CMPS_ERR_BAD_ARG;
     if (!h->params_set || h->legacy || !h->rho_set)
         return fail(h, CMPS_ERR_STATE, "cmps_rho_stream: call cmps_set_params and cmps_rho_set_state first (not available in legacy mode)");
-    if (n < 1 || forced < 0 || length < 0 || (long long)forced + length < 1 || k0 < 0)
-        return fail(h, CMPS_ERR_BAD_ARG, "cmps_rho_stream: need n >= 1, forced >= 0, length >= 0, forced + length >= 1 and k0 >= 0");
-    if ((state_in_dev == nullptr) != (k0 == 0))
-        return fail(h, CMPS_ERR_BAD_ARG, "cmps_rho_stream: state_in_dev is NULL exactly at the start of a stream (k0 == 0)");
-    if (forced > 0 && !audio_dev) return fail(h, CMPS_ERR_BAD_ARG, "cmps_rho_stream: forced > 0 needs audio_dev");
-    if (length > 0 && (!noise_dev || !out_dev)) return fail(h, CMPS_ERR_BAD_ARG, "cmps_rho_stream: length > 0 needs noise_dev and out_dev");
-    if (int c = sample_check_clips(h, "cmps_rho_stream", "n_audio", n_audio, n)) return c;
-    if (int c = sample_check_rows(h, "cmps_rho_stream", "k0 + forced + length + 1", (long long)k0 + forced + length)) return c;
-    const StreamDev ST{static_cast<const float*>(state_in_dev), static_cast<float*>(state_out_dev), k0, rho_stream_rec_floats(h)};
-    return rho_sample_run(h, "cmps_rho_stream", PrimeDev{audio_dev, n_audio == 1 ? 0 : forced + 1, forced, pred_dev}, &ST, noise_dev, n, length,
-                          out_dev, save_states, stream);
+    StreamDev ST;
+    SampleDev S;
+    if (int c = stream_args(h, "cmps_rho_stream", state_in_dev, state_out_dev, k0, audio_dev, n_audio, forced, noise_dev, length, n, out_dev, pred_dev,
+                            rho_stream_rec_floats(h), ST, S))
+        return c;
+    return rho_sample_run(h, "cmps_rho_stream", S, save_states, stream);
 }
 
 int cmps_rho_states(cmps_handle_t h, int B, int steps, float* rho_out_dev, float* purity_out_dev, void* stream) {

@@ -337,38 +337,63 @@ hipError_t launch_states_rho(const Dev& P, const RhoDev& W, int B, int steps, fl
                              hipStream_t s);
 hipError_t launch_update_ancilla_rho(const Dev& P, const float* rho_in, const float* signal, float t, int B,
                                      float* rho_out, hipStream_t s);
-// cmps_rho_sample_primed: PF = prime_T - 1 teacher-forced steps on prime[path * stride + k] (stride 0: one shared clip) in front of the
-// `length` sampled ones; pred [n][PF] may be null.  prime == nullptr: the unprimed sampler (cmps_rho_sample), which reads none of this
+// ---- the samplers: every launcher takes one SampleDev; PrimeDev, StreamDev and ScoreDev inside it are what the kernels take by value ----
+// PR (cmps_*_sample_primed): PF = prime_T - 1 teacher-forced steps on prime[path * stride + k] (stride 0: one shared clip) in front of the
+// `length` sampled ones; pred [n][PF] may be null.  ST (cmps_*_stream): one segment of a resumable scan -- the primed arguments with PF =
+// forced (either count may be 0, not both), on table rows k0 .. k0 + PF + length - 1; the state a kernel carries from one step into the
+// next is read from `in` (null: the start of a scan, psi_0 or the columns of cmps_rho_set_state) and written to `out` (null: not kept),
+// `rec` floats per path.  in == out is allowed: a path reads its record before it writes it.  SC (cmps_psi_stream_score): a stream
+// segment of PF forced steps that also gives the loss increment of every step.
+// Whoever fills the record zeroes what its mode does not use (unprimed: PR; scored: noise, length, out); a null ST / SC reaches the kernel as zeros.
 struct PrimeDev {
     const float* prime;
     int stride, PF;
     float* pred;
 };
-// cmps_psi_stream / cmps_rho_stream: one segment of a resumable scan.  The primed arguments with PF = forced (either count may be 0, not
-// both), on table rows k0 .. k0 + PF + length - 1; the state a kernel carries from one step into the next is read from `in` (null: the
-// start of a scan, psi_0 or the columns of cmps_rho_set_state) and written to `out` (null: not kept), `rec` floats per path.  in == out is
-// allowed: a path reads its record before it writes it.
 struct StreamDev {
     const float* in;
     float* out;
     int k0;
     int rec;
 };
+struct ScoreDev {
+    float* nll;       // every step's loss increment [path][step], or null
+    float* loss;      // the running loss per path: read when the segment resumes a scan (StreamDev::in set), written behind the last step
+};
+struct SampleDev {
+    const float* noise;     // [n][length]
+    int n, length;
+    float* out;             // [n][length]
+    PrimeDev PR;
+    const StreamDev* ST;    // null: not a stream segment
+    const ScoreDev* SC;     // null: not scored
+};
+inline StreamDev stream_of(const SampleDev& S) { return S.ST ? *S.ST : StreamDev{}; }
+inline ScoreDev score_of(const SampleDev& S) { return S.SC ? *S.SC : ScoreDev{}; }
+// The mode of a launch, stated once (ST first: a stream segment with forced == 0 has PR.prime == nullptr and is still SAMPLE_STREAM).  A
+// kernel's PRIMED, STREAM, SCORE (mode >= SAMPLE_PRIMED, >= SAMPLE_STREAM, == SAMPLE_SCORE) and its KScope name follow from it.  The RhoCMPS
+// kernels have no SCORE instance: their launchers return hipErrorInvalidValue.  dispatch_sample_mode: f(std::integral_constant<int, MODE>{})
+enum SampleMode { SAMPLE_PLAIN, SAMPLE_PRIMED, SAMPLE_STREAM, SAMPLE_SCORE };
+inline SampleMode sample_mode(const SampleDev& S) { return S.ST ? (S.SC ? SAMPLE_SCORE : SAMPLE_STREAM) : S.PR.prime ? SAMPLE_PRIMED : SAMPLE_PLAIN; }
+template <typename F>
+inline hipError_t dispatch_sample_mode(SampleMode mode, F&& f) {
+    if (mode == SAMPLE_SCORE) return f(std::integral_constant<int, SAMPLE_SCORE>{});
+    if (mode == SAMPLE_STREAM) return f(std::integral_constant<int, SAMPLE_STREAM>{});
+    if (mode == SAMPLE_PRIMED) return f(std::integral_constant<int, SAMPLE_PRIMED>{});
+    return f(std::integral_constant<int, SAMPLE_PLAIN>{});
+}
 // floats of one path's record of the RhoCMPS samplers, a multiple of 4: k_sample_rho_mfma the rows a < rank of U [rank][64], running sum |
 // k_sample_rho the columns S [rank][D] float2, running sum
 inline int stream_rec_rho_mfma(int rank) { return 64 * rank + 4; }
 inline int stream_rec_rho(int rank, int D) { return (2 * rank * D + 1 + 3) / 4 * 4; }
-// ST == nullptr: cmps_rho_sample / cmps_rho_sample_primed; else a stream segment (PR.prime may then be null: PR.PF == 0)
-hipError_t launch_sample_rho(const Dev& P, const RhoDev& W, const float* noise, int n, int length, float* out,
-                             bool save, const PrimeDev& PR, const StreamDev* ST, hipStream_t s);
+hipError_t launch_sample_rho(const Dev& P, const RhoDev& W, const SampleDev& S, bool save, hipStream_t s);
 hipError_t launch_fwd_legacy_wave(const Dev& P, const float* audio, float* loss, bool save, hipStream_t s);
 hipError_t launch_bwd_legacy_wave(const Dev& P, const float* audio, int rank1_mode, hipStream_t s);
 hipError_t launch_legacy_tables(const Dev& P, float2* psi0, float* dtk, float2* rho, hipStream_t s);
 hipError_t launch_fwd_rho_wave(const Dev& P, const RhoDev& W, const float* audio, float* loss, bool save, hipStream_t s);
 hipError_t launch_fwd_rho_mfma(const Dev& P, const RhoDev& W, const float* audio, float* loss, bool save, bool f16, bool grad1, hipStream_t s);
 hipError_t launch_bwd_rho_mfma(const Dev& P, const RhoDev& W, const float* audio, hipStream_t s);
-hipError_t launch_sample_rho_mfma(const Dev& P, const RhoDev& W, const float* noise, int n, int length, float* out, bool save,
-                                  bool f16, const PrimeDev& PR, const StreamDev* ST, hipStream_t s);
+hipError_t launch_sample_rho_mfma(const Dev& P, const RhoDev& W, const SampleDev& S, bool save, bool f16, hipStream_t s);
 hipError_t launch_bwd_rho_wave(const Dev& P, const RhoDev& W, const float* audio, hipStream_t s);
 hipError_t launch_prep(const Dev& P, const float* R_re, const float* R_im, const float* freqs,
                        const float* psi0_re, const float* psi0_im, float dt, bool rebuild_ttab,
@@ -408,40 +433,14 @@ hipError_t launch_pack_legacy(const Dev& P, const float* Rr, const float* Qre, c
 hipError_t launch_fwd_legacy(const Dev& P, const float* audio, float* loss, bool save, hipStream_t s);
 hipError_t launch_bwd_legacy(const Dev& P, const float* audio, hipStream_t s);
 hipError_t launch_finalize_legacy(const Dev& P, const float* loss, float* grad_out, hipStream_t s);
-hipError_t launch_sample_wave(const Dev& P, const float* noise, int n, int length, float* out, hipStream_t s);
-hipError_t launch_sample_wide(const Dev& P, const float* noise, int n, int length, float* out, hipStream_t s);
-hipError_t launch_sample_block(const Dev& P, const float* noise, int n, int length, float* out, hipStream_t s);
-// cmps_psi_sample_primed: PF = prime_T - 1 teacher-forced steps on prime[path * prime_stride + k] (prime_stride 0: one shared clip), then
-// `length` sampled steps; pred [n][PF] may be null
-hipError_t launch_sample_wave_primed(const Dev& P, const float* prime, int prime_stride, int PF, const float* noise, int n, int length,
-                                     float* out, float* pred, hipStream_t s);
-hipError_t launch_sample_wide_primed(const Dev& P, const float* prime, int prime_stride, int PF, const float* noise, int n, int length,
-                                     float* out, float* pred, hipStream_t s);
-hipError_t launch_sample_block_primed(const Dev& P, const float* prime, int prime_stride, int PF, const float* noise, int n, int length,
-                                      float* out, float* pred, hipStream_t s);
-// cmps_psi_stream: the primed arguments and a StreamDev (above)
-// floats of one path's record, a multiple of 4: wave u, |y|^2 partial per lane, running sum | wide ut [2 DP], |y|^2 partial per wave
-// [DP / 16], running sum | block u [2 D], running sum
+hipError_t launch_sample_wave(const Dev& P, const SampleDev& S, hipStream_t s);
+hipError_t launch_sample_wide(const Dev& P, const SampleDev& S, hipStream_t s);
+hipError_t launch_sample_block(const Dev& P, const SampleDev& S, hipStream_t s);
+// floats of one path's stream record (StreamDev::rec), a multiple of 4: wave u, |y|^2 partial per lane, running sum | wide ut [2 DP], |y|^2
+// partial per wave [DP / 16], running sum | block u [2 D], running sum
 constexpr int STREAM_REC_WAVE = 132;
 inline int stream_rec_wide(int DP) { return (2 * DP + DP / 16 + 1 + 3) / 4 * 4; }
 inline int stream_rec_block(int D) { return (2 * D + 1 + 3) / 4 * 4; }
-hipError_t launch_sample_wave_stream(const Dev& P, const StreamDev& ST, const float* audio, int audio_stride, int PF, const float* noise, int n,
-                                     int length, float* out, float* pred, hipStream_t s);
-hipError_t launch_sample_wide_stream(const Dev& P, const StreamDev& ST, const float* audio, int audio_stride, int PF, const float* noise, int n,
-                                     int length, float* out, float* pred, hipStream_t s);
-hipError_t launch_sample_block_stream(const Dev& P, const StreamDev& ST, const float* audio, int audio_stride, int PF, const float* noise, int n,
-                                      int length, float* out, float* pred, hipStream_t s);
-// cmps_psi_stream_score: a stream segment of PF forced steps that also gives the loss increment of every step
-struct ScoreDev {
-    float* nll;       // every step's loss increment [path][step], or null
-    float* loss;      // the running loss per path: read when the segment resumes a scan (StreamDev::in set), written behind the last step
-};
-hipError_t launch_sample_wave_score(const Dev& P, const StreamDev& ST, const ScoreDev& SC, const float* audio, int audio_stride, int PF, int n, float* pred,
-                                    hipStream_t s);
-hipError_t launch_sample_wide_score(const Dev& P, const StreamDev& ST, const ScoreDev& SC, const float* audio, int audio_stride, int PF, int n, float* pred,
-                                    hipStream_t s);
-hipError_t launch_sample_block_score(const Dev& P, const StreamDev& ST, const ScoreDev& SC, const float* audio, int audio_stride, int PF, int n, float* pred,
-                                     hipStream_t s);
 
 size_t apply_step_scratch_bytes(int D);
 hipError_t launch_apply_step(int D, bool apply, double inv_batch, double lr_t, double beta1, double beta2, double eps, double h_reg,

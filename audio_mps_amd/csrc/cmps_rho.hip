@@ -610,25 +610,21 @@ hipError_t launch_update_ancilla_rho(const Dev& P, const float* rho_in, const fl
     return hipGetLastError();
 }
 
-hipError_t launch_sample_rho(const Dev& P, const RhoDev& W, const float* noise, int n, int length, float* out,
-                             bool save, const PrimeDev& PR, const StreamDev* ST, hipStream_t s) {
+hipError_t launch_sample_rho(const Dev& P, const RhoDev& W, const SampleDev& S, bool save, hipStream_t s) {
     size_t shm;
-    float2* g = cols_if_needed(W, (size_t)3 * W.rank * P.D * sizeof(float2) + 128, shm, n);
+    float2* g = cols_if_needed(W, (size_t)3 * W.rank * P.D * sizeof(float2) + 128, shm, S.n);
     if (g == reinterpret_cast<float2*>(1)) return hipErrorInvalidValue;
     return dispatch_block_nt(P.D, [&](auto nt) {
-        constexpr int NT = decltype(nt)::value;
-        if (ST) {
-            const hipError_t e = lds_attr(k_sample_rho<NT, true, true>, shm);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL((k_sample_rho<NT, true, true>), dim3(n), dim3(NT), shm, s, P, W, noise, length, out, save ? 1 : 0, g, PR, *ST);
-            return hipGetLastError();
-        }
-        return dispatch_bool(PR.prime != nullptr, [&](auto pm) {
-            constexpr bool PM = decltype(pm)::value;
-            const hipError_t e = lds_attr(k_sample_rho<NT, PM>, shm);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL((k_sample_rho<NT, PM>), dim3(n), dim3(NT), shm, s, P, W, noise, length, out, save ? 1 : 0, g, PR, StreamDev{});
-            return hipGetLastError();
+        return dispatch_sample_mode(sample_mode(S), [&](auto mode) {
+            constexpr int NT = decltype(nt)::value, M = decltype(mode)::value;
+            if constexpr (M == SAMPLE_SCORE) return hipErrorInvalidValue;       // no SCORE instance (yet): a Rho score lands here
+            else {
+                const hipError_t e = lds_attr(k_sample_rho<NT, M >= SAMPLE_PRIMED, M >= SAMPLE_STREAM>, shm);
+                if (e != hipSuccess) return e;
+                hipLaunchKernelGGL((k_sample_rho<NT, M >= SAMPLE_PRIMED, M >= SAMPLE_STREAM>), dim3(S.n), dim3(NT), shm, s, P, W, S.noise, S.length, S.out,
+                                   save ? 1 : 0, g, S.PR, stream_of(S));
+                return hipGetLastError();
+            }
         });
     });
 }

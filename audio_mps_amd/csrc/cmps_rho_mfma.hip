@@ -824,20 +824,18 @@ hipError_t launch_fwd_rho_mfma(const Dev& P, const RhoDev& W, const float* audio
     return hipGetLastError();
 }
 
-hipError_t launch_sample_rho_mfma(const Dev& P, const RhoDev& W, const float* noise, int n, int length, float* out, bool save,
-                                  bool f16, const PrimeDev& PR, const StreamDev* ST, hipStream_t s) {
-    const unsigned nb = (unsigned)((n + WAVES - 1) / WAVES);
+hipError_t launch_sample_rho_mfma(const Dev& P, const RhoDev& W, const SampleDev& S, bool save, bool f16, hipStream_t s) {
+    const unsigned nb = (unsigned)((S.n + WAVES - 1) / WAVES);
     return dispatch_bool(save, [&](auto sv) {
         return dispatch_bool(f16, [&](auto hf) {
-            constexpr bool SV = decltype(sv)::value, HF = decltype(hf)::value;
-            if (ST) {
-                hipLaunchKernelGGL((k_sample_rho_mfma<SV, HF, true, true>), dim3(nb), dim3(64 * WAVES), 0, s, P, W, noise, n, length, out, PR, *ST);
-                return hipGetLastError();
-            }
-            return dispatch_bool(PR.prime != nullptr, [&](auto pm) {
-                hipLaunchKernelGGL((k_sample_rho_mfma<SV, HF, decltype(pm)::value>), dim3(nb), dim3(64 * WAVES), 0, s, P, W, noise, n, length, out,
-                                   PR, StreamDev{});
-                return hipGetLastError();
+            return dispatch_sample_mode(sample_mode(S), [&](auto mode) {
+                constexpr int M = decltype(mode)::value;
+                if constexpr (M == SAMPLE_SCORE) return hipErrorInvalidValue;   // no SCORE instance (yet): a Rho score lands here
+                else {
+                    hipLaunchKernelGGL((k_sample_rho_mfma<decltype(sv)::value, decltype(hf)::value, M >= SAMPLE_PRIMED, M >= SAMPLE_STREAM>), dim3(nb),
+                                       dim3(64 * WAVES), 0, s, P, W, S.noise, S.n, S.length, S.out, S.PR, stream_of(S));
+                    return hipGetLastError();
+                }
             });
         });
     });

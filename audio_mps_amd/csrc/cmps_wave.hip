@@ -803,33 +803,14 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_sample_wave(Dev P, const floa
     }
 }
 
-hipError_t launch_sample_wave(const Dev& P, const float* noise, int n, int length, float* out, hipStream_t s) {
-    const unsigned nb = (unsigned)((n + WAVES - 1) / WAVES);
-    hipLaunchKernelGGL(k_sample_wave<false>, dim3(nb), dim3(64 * WAVES), 0, s, P, noise, n, length, out, (const float*)nullptr, 0, 0, (float*)nullptr,
-                       StreamDev{}, ScoreDev{});
-    return hipGetLastError();
-}
-
-hipError_t launch_sample_wave_primed(const Dev& P, const float* prime, int prime_stride, int PF, const float* noise, int n, int length,
-                                     float* out, float* pred, hipStream_t s) {
-    const unsigned nb = (unsigned)((n + WAVES - 1) / WAVES);
-    hipLaunchKernelGGL(k_sample_wave<true>, dim3(nb), dim3(64 * WAVES), 0, s, P, noise, n, length, out, prime, prime_stride, PF, pred, StreamDev{}, ScoreDev{});
-    return hipGetLastError();
-}
-
-hipError_t launch_sample_wave_stream(const Dev& P, const StreamDev& ST, const float* audio, int audio_stride, int PF, const float* noise, int n,
-                                     int length, float* out, float* pred, hipStream_t s) {
-    const unsigned nb = (unsigned)((n + WAVES - 1) / WAVES);
-    hipLaunchKernelGGL((k_sample_wave<true, true>), dim3(nb), dim3(64 * WAVES), 0, s, P, noise, n, length, out, audio, audio_stride, PF, pred, ST, ScoreDev{});
-    return hipGetLastError();
-}
-
-hipError_t launch_sample_wave_score(const Dev& P, const StreamDev& ST, const ScoreDev& SC, const float* audio, int audio_stride, int PF, int n, float* pred,
-                                    hipStream_t s) {
-    const unsigned nb = (unsigned)((n + WAVES - 1) / WAVES);
-    hipLaunchKernelGGL((k_sample_wave<true, true, true>), dim3(nb), dim3(64 * WAVES), 0, s, P, (const float*)nullptr, n, 0, (float*)nullptr, audio,
-                       audio_stride, PF, pred, ST, SC);
-    return hipGetLastError();
+hipError_t launch_sample_wave(const Dev& P, const SampleDev& S, hipStream_t s) {
+    const unsigned nb = (unsigned)((S.n + WAVES - 1) / WAVES);
+    return dispatch_sample_mode(sample_mode(S), [&](auto mode) {
+        constexpr int M = decltype(mode)::value;
+        hipLaunchKernelGGL((k_sample_wave<M >= SAMPLE_PRIMED, M >= SAMPLE_STREAM, M == SAMPLE_SCORE>), dim3(nb), dim3(64 * WAVES), 0, s, P, S.noise, S.n,
+                           S.length, S.out, S.PR.prime, S.PR.stride, S.PR.PF, S.PR.pred, stream_of(S), score_of(S));
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_bwd_legacy_wave(const Dev& P, const float* audio, int rank1_mode, hipStream_t s) {

@@ -1404,44 +1404,15 @@ hipError_t launch_fwd_wide(const Dev& P, const float* audio, float* loss, bool s
     return dispatch_pd(P.DP, [&](auto pd) { return fwd_wide_t<decltype(pd)::value>(P, audio, loss, save, hy_f16, chain_mfma, s); });
 }
 
-hipError_t launch_sample_wide(const Dev& P, const float* noise, int n, int length, float* out, hipStream_t s) {
-    const unsigned nb = (unsigned)((n + 1) / 2);
+hipError_t launch_sample_wide(const Dev& P, const SampleDev& S, hipStream_t s) {
+    const unsigned nb = (unsigned)((S.n + 1) / 2);
     return dispatch_pd(P.DP, [&](auto pd) {
-        constexpr int PD = decltype(pd)::value;
-        hipLaunchKernelGGL((k_sample_wide<PD, false>), dim3(nb), dim3(4 * PD), 0, s, P, noise, n, length, out, (const float*)nullptr, 0, 0, (float*)nullptr,
-                           StreamDev{}, ScoreDev{});
-        return hipGetLastError();
-    });
-}
-
-hipError_t launch_sample_wide_primed(const Dev& P, const float* prime, int prime_stride, int PF, const float* noise, int n, int length,
-                                     float* out, float* pred, hipStream_t s) {
-    const unsigned nb = (unsigned)((n + 1) / 2);
-    return dispatch_pd(P.DP, [&](auto pd) {
-        constexpr int PD = decltype(pd)::value;
-        hipLaunchKernelGGL((k_sample_wide<PD, true>), dim3(nb), dim3(4 * PD), 0, s, P, noise, n, length, out, prime, prime_stride, PF, pred, StreamDev{}, ScoreDev{});
-        return hipGetLastError();
-    });
-}
-
-hipError_t launch_sample_wide_stream(const Dev& P, const StreamDev& ST, const float* audio, int audio_stride, int PF, const float* noise, int n,
-                                     int length, float* out, float* pred, hipStream_t s) {
-    const unsigned nb = (unsigned)((n + 1) / 2);
-    return dispatch_pd(P.DP, [&](auto pd) {
-        constexpr int PD = decltype(pd)::value;
-        hipLaunchKernelGGL((k_sample_wide<PD, true, true>), dim3(nb), dim3(4 * PD), 0, s, P, noise, n, length, out, audio, audio_stride, PF, pred, ST, ScoreDev{});
-        return hipGetLastError();
-    });
-}
-
-hipError_t launch_sample_wide_score(const Dev& P, const StreamDev& ST, const ScoreDev& SC, const float* audio, int audio_stride, int PF, int n, float* pred,
-                                    hipStream_t s) {
-    const unsigned nb = (unsigned)((n + 1) / 2);
-    return dispatch_pd(P.DP, [&](auto pd) {
-        constexpr int PD = decltype(pd)::value;
-        hipLaunchKernelGGL((k_sample_wide<PD, true, true, true>), dim3(nb), dim3(4 * PD), 0, s, P, (const float*)nullptr, n, 0, (float*)nullptr, audio,
-                           audio_stride, PF, pred, ST, SC);
-        return hipGetLastError();
+        return dispatch_sample_mode(sample_mode(S), [&](auto mode) {
+            constexpr int PD = decltype(pd)::value, M = decltype(mode)::value;
+            hipLaunchKernelGGL((k_sample_wide<PD, M >= SAMPLE_PRIMED, M >= SAMPLE_STREAM, M == SAMPLE_SCORE>), dim3(nb), dim3(4 * PD), 0, s, P, S.noise,
+                               S.n, S.length, S.out, S.PR.prime, S.PR.stride, S.PR.PF, S.PR.pred, stream_of(S), score_of(S));
+            return hipGetLastError();
+        });
     });
 }
 

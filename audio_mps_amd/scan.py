@@ -405,6 +405,18 @@ class HipScan:
             raise ValueError(f"invalid path count for a stream: n={n}" + hint)
         return torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
 
+    def _stream_paths(self, bytes_fn, state_in, state_out, n, n_audio) -> int:
+        """The path count of a segment (``n``, else a state tensor's, else the audio's rows), with the state tensors checked against it."""
+        if n is None:
+            st = state_out if state_out is not None else state_in
+            n = st.numel() // int(bytes_fn(self._h, 1)) if st is not None else n_audio
+        n = int(n)
+        for st in (state_in, state_out):
+            if st is not None and not (st.is_cuda and st.dtype == torch.uint8 and st.is_contiguous()
+                                       and st.numel() == int(bytes_fn(self._h, n))):
+                raise ValueError(f"a stream state must be the tensor stream_state({n}) returned")
+        return n
+
     def _stream_call(self, fn, bytes_fn, state_in, state_out, k0, audio, noise, want_pred, n, *flags):
         """One segment: the signal block [n_audio, forced + 1] and the noise [length, n] up, (out [n, length], pred [n, forced] or None)
         down.  `fn` / `bytes_fn` are cmps_{psi,rho}_stream / _stream_state_bytes, `flags` what `fn` takes behind pred_dev."""
@@ -421,14 +433,7 @@ class HipScan:
             if audio.ndim != 2 or audio.shape[1] < 1:
                 raise ValueError("audio must be [n_audio, forced + 1]")
             n_audio, forced = audio.shape[0], audio.shape[1] - 1
-        if n is None:
-            st = state_out if state_out is not None else state_in
-            n = st.numel() // int(bytes_fn(self._h, 1)) if st is not None else n_audio
-        n = int(n)
-        for st in (state_in, state_out):
-            if st is not None and not (st.is_cuda and st.dtype == torch.uint8 and st.is_contiguous()
-                                       and st.numel() == int(bytes_fn(self._h, n))):
-                raise ValueError(f"a stream state must be the tensor stream_state({n}) returned")
+        n = self._stream_paths(bytes_fn, state_in, state_out, n, n_audio)
         if forced > 0:
             d_audio = torch.from_numpy(audio).to(self.device)
         if length > 0:
@@ -467,14 +472,7 @@ class HipScan:
         if audio.ndim != 2 or audio.shape[1] < 2:
             raise ValueError("audio must be [n_audio, forced + 1] with forced >= 1")
         n_audio, forced = audio.shape[0], audio.shape[1] - 1
-        if n is None:
-            st = state_out if state_out is not None else state_in
-            n = st.numel() // int(self._lib.cmps_psi_stream_state_bytes(self._h, 1)) if st is not None else n_audio
-        n = int(n)
-        for st in (state_in, state_out):
-            if st is not None and not (st.is_cuda and st.dtype == torch.uint8 and st.is_contiguous()
-                                       and st.numel() == int(self._lib.cmps_psi_stream_state_bytes(self._h, n))):
-                raise ValueError(f"a stream state must be the tensor stream_state({n}) returned")
+        n = self._stream_paths(self._lib.cmps_psi_stream_state_bytes, state_in, state_out, n, n_audio)
         if loss is None:
             d_loss = torch.zeros(n, dtype=torch.float32, device=self.device)
         else:

@@ -43,17 +43,19 @@ class SampleStream:
         self.last_pred = None          # the predictions of the last score call
 
     # ------------------------------------------------------------------
-    def _launch(self, steps, audio, noise, want_pred):
+    def _launch(self, steps, entry, *args, **kw):
+        """One call of ``steps`` steps through ``entry`` (the stream's segment entry, or `score`'s): the bounds first -- a refused call
+        changes nothing -- then the entry on the stream's state and position, then the bookkeeping."""
         if self.position + steps > self.max_steps:
             raise ValueError(f"the stream was opened for max_steps={self.max_steps}: {self.position} taken, {steps} more asked for")
         if self.keep_states and steps > self.keep_states:
             raise ValueError(f"the stream was opened with keep_states={self.keep_states}: a call of {steps} steps does not fit")
-        keep = {"save_states": True} if self.keep_states else {}
-        out, pred = self._segment(self._state if self.position else None, self._state, self.position, audio, noise, want_pred,
-                                  n=self.num_paths, **keep)
+        if self.keep_states:
+            kw["save_states"] = True
+        res = entry(self._state if self.position else None, self._state, self.position, *args, n=self.num_paths, **kw)
         self.position += steps
         self._saved = steps if self.keep_states else None
-        return out, pred
+        return res
 
     def _kept(self, want_rho):
         if not self.keep_states:
@@ -104,13 +106,8 @@ class SampleStream:
         nll = np.empty((n, 0), dtype=np.float32)
         pred = np.empty((n, 0), dtype=np.float32)
         if steps:
-            if self.position + steps > self.max_steps:
-                raise ValueError(f"the stream was opened for max_steps={self.max_steps}: {self.position} taken, {steps} more asked for")
-            nll, total, pred = entry(self._state if self.position else None, self._state, self.position, np.ascontiguousarray(audio),
-                                     want_nll=True, want_pred=True, n=n, loss=self.total_nll)
+            nll, total, pred = self._launch(steps, entry, np.ascontiguousarray(audio), want_nll=True, want_pred=True, loss=self.total_nll)
             self.total_nll = np.asarray(total, dtype=np.float32)
-            self.position += steps
-            self._saved = None
         self.last_pred = pred
         self.last = np.array(np.broadcast_to(block[:, -1], (n,)), dtype=np.float32)
         self._level = None
@@ -127,7 +124,7 @@ class SampleStream:
         steps = audio.shape[1] - 1
         pred = np.empty((n, 0), dtype=np.float32)
         if steps:
-            _, pred = self._launch(steps, np.ascontiguousarray(audio), None, True)
+            _, pred = self._launch(steps, self._segment, np.ascontiguousarray(audio), None, True)
         self.last = np.array(np.broadcast_to(block[:, -1], (n,)), dtype=np.float32)
         self._level = None
         return pred
@@ -149,7 +146,7 @@ class SampleStream:
             raise ValueError(f"noise must be [{length}, {n}]")
         if self._level is None:
             self._level = np.zeros(n, dtype=np.float32) if self.last is None else self.last.copy()
-        out, _ = self._launch(length, None, noise, False)
+        out, _ = self._launch(length, self._segment, None, noise, False)
         wave = (self._level[:, None] + out / self._A).astype(np.float32)
         self.last = wave[:, -1].copy()
         return wave

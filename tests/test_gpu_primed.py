@@ -126,6 +126,26 @@ def test_shared_prime_equals_tiled_prime(D, P, length, n, variant):
     assert not np.array_equal(pred_p[0], pred_p[1])
 
 
+@pytest.mark.parametrize("D,variant", [(8, AUTO), (48, AUTO), (48, BLOCK)])
+def test_sample_kernel_names(D, variant):
+    """cmps_psi_sample and cmps_psi_sample_primed are each recorded once, under the family the variant resolves to and their own mode."""
+    n = 2
+    m = _model(D, n, variant)
+    be = m._get_backend()
+    be.set_params(m.effective_params(), n, 8, train=False)
+    family = {WAVE: "k_sample_wave", WIDE: "k_sample_wide", BLOCK: "k_sample_block"}[_expected_family(D, variant)]
+    rng = np.random.default_rng(D)
+    noise = (0.01 * rng.standard_normal((3, n))).astype(np.float32)
+    prime = (0.1 * rng.standard_normal((1, 4))).astype(np.float32)
+    be.kernel_events(True)
+    out = be.sample(noise)
+    times = be.kernel_times()
+    assert list(times) == [family] and times[family][1] == 1 and np.all(np.isfinite(out))
+    out_p = be.sample_primed(prime, noise)
+    times = be.kernel_times()
+    assert list(times) == [family + "_primed"] and times[family + "_primed"][1] == 1 and np.all(np.isfinite(out_p))
+
+
 def test_primed_error_returns():
     """(f) argument and call-order checks of the C entry."""
     from audio_mps_amd import _capi
