@@ -1,6 +1,7 @@
 // C ABI of libcmps.so (see include/cmps.h for the contract and the reference lines each entry replaces).
 #include "../../include/cmps.h"
 
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -639,6 +640,25 @@ int cmps_psi_stream_score(cmps_handle_t h, const void* state_in_dev, void* state
     const ScoreDev SC{nll_dev, loss_dev};
     const PrimeDev PR{audio_dev, n_audio == 1 ? 0 : forced + 1, forced, pred_dev};
     return psi_sample_launch(h, "cmps_psi_stream_score", SampleDev{nullptr, n, 0, nullptr, PR, &ST, &SC}, stream);   // (every step is forced)
+}
+
+// The samplers' noise drawn on the device: needs nothing of the handle but its error string and its kernel-event record
+int cmps_noise_fill(cmps_handle_t h, unsigned long long seed, unsigned long long first_step, unsigned first_path, int n, int length,
+                    float stddev, float* noise_dev, void* stream) {
+    if (!h) return CMPS_ERR_BAD_ARG;
+    if (!noise_dev) return fail(h, CMPS_ERR_BAD_ARG, "cmps_noise_fill: noise_dev is a null pointer");
+    if (n < 1 || length < 1) return fail(h, CMPS_ERR_BAD_ARG, "cmps_noise_fill: need n >= 1 and length >= 1");
+    if (!(stddev >= 0.0f) || !std::isfinite(stddev)) return fail(h, CMPS_ERR_BAD_ARG, "cmps_noise_fill: stddev must be finite and not negative");
+    if ((unsigned long long)first_path + (unsigned long long)n > (1ull << 32))
+        return fail(h, CMPS_ERR_BAD_ARG, "cmps_noise_fill: first_path + n exceeds 2^32 (a path is a 32-bit counter word)");
+    if (first_step + (unsigned long long)length < first_step)
+        return fail(h, CMPS_ERR_BAD_ARG, "cmps_noise_fill: first_step + length overflows 64 bits");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    KBind kb(h);
+    KScope ks("k_noise_philox", s);
+    const hipError_t e = launch_noise_philox(seed, first_step, first_path, n, length, stddev, noise_dev, s);
+    if (e != hipSuccess) return fail_hip(h, e, "cmps_noise_fill");
+    return CMPS_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------

@@ -436,6 +436,9 @@ hipError_t launch_finalize_legacy(const Dev& P, const float* loss, float* grad_o
 hipError_t launch_sample_wave(const Dev& P, const SampleDev& S, hipStream_t s);
 hipError_t launch_sample_wide(const Dev& P, const SampleDev& S, hipStream_t s);
 hipError_t launch_sample_block(const Dev& P, const SampleDev& S, hipStream_t s);
+// cmps_noise.hip: noise[b * length + j] = stddev * z(seed, first_path + b, first_step + j), the counter-based normals of include/cmps.h
+hipError_t launch_noise_philox(unsigned long long seed, unsigned long long first_step, unsigned first_path, int n, int length, float stddev,
+                               float* noise, hipStream_t s);
 // floats of one path's stream record (StreamDev::rec), a multiple of 4: wave u, |y|^2 partial per lane, running sum | wide ut [2 DP], |y|^2
 // partial per wave [DP / 16], running sum | block u [2 D], running sum
 constexpr int STREAM_REC_WAVE = 132;

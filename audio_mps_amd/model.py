@@ -236,12 +236,43 @@ class CMPS(_ScanModel):
         return EffectiveParams(R=self.R, freqs=self.freqs, psi0=psi0, A=float(self.A),
                                sigma=float(self.sigma), delta_t=float(self.delta_t))
 
-    def _noise(self, num_samples, length, temp, seed, noise):
+    @staticmethod
+    def _noise_seed(seed) -> int:
+        """The 64-bit seed of device-drawn noise: ``seed``, or (None) a fresh 63-bit one from the system's entropy."""
+        if seed is None:
+            return int(np.random.SeedSequence().entropy) & (2 ** 63 - 1)
+        seed = int(seed)
+        if not 0 <= seed < 2 ** 64:
+            raise ValueError("the seed of device-drawn noise must lie in [0, 2^64)")
+        return seed
+
+    def _device_noise_backend(self):
+        """The backend, if it can draw noise itself (HipScan.draw_noise, cmps_noise_fill); else device_noise=True is a ValueError."""
+        be = self._get_backend()
+        if not hasattr(be, "draw_noise"):
+            raise ValueError(f"device_noise=True needs a backend that draws noise on the device (draw_noise): {type(be).__name__} has none")
+        return be
+
+    @staticmethod
+    def _plan_shape(noise, length, n) -> dict:
+        """The ``length`` / ``n`` keywords a backend's sampler entry needs next to a NoisePlan; none next to an array, which brings its shape."""
+        if isinstance(noise, np.ndarray):
+            return {}
+        from .scan import NoisePlan
+        return {"length": int(length), "n": int(n)} if isinstance(noise, NoisePlan) else {}
+
+    def _noise(self, num_samples, length, temp, seed, noise, device_noise=False, first_step=0):
         """The sampler's Gaussian noise [length, num_samples] (stddev sigma * sqrt(temp * delta_t), model.py:246 / :88, 96, 106):
-        drawn on the host with a numpy Generator (``seed``), or ``noise`` as passed in, like the reference's tensor."""
+        drawn on the host with a numpy Generator (``seed``), or ``noise`` as passed in, like the reference's tensor.  With ``device_noise``
+        (and no ``noise``) nothing is drawn here: the return value is a NoisePlan(seed, first_step, stddev) the backend draws from on the
+        device, where it samples (cmps_noise_fill); ``first_step`` is the table row of the first sampled step."""
+        std = float(self.sigma) * math.sqrt(temp * float(self.delta_t))
+        if noise is None and device_noise:
+            from .scan import NoisePlan
+            self._device_noise_backend()
+            return NoisePlan(self._noise_seed(seed), int(first_step), std)
         if noise is None:
             rng = np.random.default_rng(seed)
-            std = float(self.sigma) * math.sqrt(temp * float(self.delta_t))
             noise = (std * rng.standard_normal((length, num_samples))).astype(np.float32)
         noise = np.asarray(noise, dtype=np.float32)
         if noise.shape != (length, num_samples):
@@ -249,8 +280,9 @@ class CMPS(_ScanModel):
         return noise
 
     # ---- primed sampling: units and shapes around the subclass's sample(prime=...) and its backend entry ----
-    def _sample_primed(self, be, prime, noise, want_pred):
-        """The backend's primed sampler for this model, (out, pred) with want_pred: HipScan.sample_primed / rho_sample_primed."""
+    def _sample_primed(self, be, prime, noise, want_pred, length=None, n=None):
+        """The backend's primed sampler for this model, (out, pred) with want_pred: HipScan.sample_primed / rho_sample_primed.  ``length``
+        and ``n`` are needed where ``noise`` is a NoisePlan."""
         raise NotImplementedError
 
     # ---- resumable sampling (audio_mps_amd/stream.py) ----
@@ -268,13 +300,14 @@ class CMPS(_ScanModel):
         """The backend as a stream needs it: T = max_steps + 1, one table row per step."""
         return self._prepare(num_paths, max_steps + 1, train=False)
 
-    def open_stream(self, num_paths, max_steps, temp=1, seed=None):
+    def open_stream(self, num_paths, max_steps, temp=1, seed=None, device_noise=False):
         """A resumable sampler of ``num_paths`` paths (no reference counterpart; audio_mps_amd/stream.py, cmps_psi_stream /
         cmps_rho_stream): follow an incoming signal block by block, generate in segments, or alternate.  Prepares the backend once with
         T = max_steps + 1 -- the only sizing decision, 8 DP bytes of phase table per step; running past ``max_steps`` raises ValueError.
-        The model's variables are read here: a stream keeps the parameters it was opened with."""
+        The model's variables are read here: a stream keeps the parameters it was opened with.  ``device_noise=True``: ``generate`` draws
+        its noise on the device from (``seed``, path, step) instead of a host Generator (SampleStream.generate)."""
         from .stream import SampleStream
-        return SampleStream(self, num_paths, max_steps, temp=temp, seed=seed)
+        return SampleStream(self, num_paths, max_steps, temp=temp, seed=seed, device_noise=device_noise)
 
     @staticmethod
     def _prime(prime, num_samples) -> np.ndarray:
@@ -290,12 +323,12 @@ class CMPS(_ScanModel):
             raise ValueError("prime needs two samples at least (one increment)")
         return np.ascontiguousarray(prime)
 
-    def continue_clip(self, prime, num_samples, length, temp=1, seed=None, noise=None) -> np.ndarray:
+    def continue_clip(self, prime, num_samples, length, temp=1, seed=None, noise=None, device_noise=False) -> np.ndarray:
         """The continuation of ``prime`` in the clip's own units, [num_samples, length]: the array to plot or write behind the clip.
         The model's waveform is A * (running sum of increments) and the data enter as increments / A (model.py:303, :175), so the
         sampled sum is divided by A and starts from the clip's last sample."""
         prime = self._prime(prime, num_samples)
-        out = self.sample(num_samples, length, temp=temp, seed=seed, noise=noise, prime=prime)
+        out = self.sample(num_samples, length, temp=temp, seed=seed, noise=noise, prime=prime, device_noise=device_noise)
         return (prime[..., -1:] + out / self.A).astype(np.float32)
 
     def predict_increments(self, data=None) -> np.ndarray:
@@ -424,27 +457,31 @@ class PsiCMPS(CMPS):
         be.forward(audio, save_for_bwd=True)
         return be.states()
 
-    def sample(self, num_samples, length, temp=1, seed=None, noise=None, prime=None, return_pred=False):
+    def sample(self, num_samples, length, temp=1, seed=None, noise=None, prime=None, return_pred=False, device_noise=False):
         """model.py:242-251: waveforms [num_samples, length] = A * running sum of the sampled increments.
         The Gaussian noise (stddev sigma * sqrt(temp * delta_t), model.py:246) is drawn on the host with a numpy
-        Generator (``seed``), or passed in as ``noise`` [length, num_samples] like the reference's tensor.
+        Generator (``seed``), or passed in as ``noise`` [length, num_samples] like the reference's tensor.  ``device_noise=True``
+        draws it on the device instead, where the reference draws it: counter-based normals of (``seed``, path, table row of the step)
+        (cmps_noise_fill; ``seed=None``: a fresh seed), so a primed sample and a stream that followed the same clip draw the same noise.
+        An explicit ``noise`` wins.
 
         ``prime`` (no reference counterpart): a clip [T'], [1, T'] (shared by all paths) or [num_samples, T'] the state is first
         teacher-forced on -- T' - 1 steps of _psi_update (model.py:269-274) on its increments -- before the ``length`` sampled
         steps follow in the same scan (cmps_psi_sample_primed).  The return value keeps the reference's convention: A * running
         sum of the SAMPLED increments, zero at the hand-over (``continue_clip`` returns the clip's own units).  ``return_pred``
         adds the model's expected increment of every forced step, [num_samples, T' - 1]."""
-        noise = self._noise(num_samples, length, temp, seed, noise)
         if prime is None:
             if return_pred:
                 raise ValueError("return_pred needs a prime: the predictions belong to the teacher-forced steps")
-            return self._prepare(num_samples, length + 1, train=False).sample(noise)
+            noise = self._noise(num_samples, length, temp, seed, noise, device_noise)
+            return self._prepare(num_samples, length + 1, train=False).sample(noise, **self._plan_shape(noise, length, num_samples))
         prime = self._prime(prime, num_samples)
+        noise = self._noise(num_samples, length, temp, seed, noise, device_noise, first_step=prime.shape[1] - 1)
         be = self._prepare(num_samples, prime.shape[1] + length, train=False)    # one table row per step, forced or sampled
-        return self._sample_primed(be, prime, noise, bool(return_pred))
+        return self._sample_primed(be, prime, noise, bool(return_pred), length, num_samples)
 
-    def _sample_primed(self, be, prime, noise, want_pred):
-        return be.sample_primed(prime, noise, want_pred=want_pred)
+    def _sample_primed(self, be, prime, noise, want_pred, length=None, n=None):
+        return be.sample_primed(prime, noise, want_pred=want_pred, **self._plan_shape(noise, length, n))
 
     def _stream_entries(self, be):
         return be.stream_state, be.stream
@@ -576,8 +613,8 @@ class RhoCMPS(CMPS):
         be.rho_forward(audio, save_for_bwd=True)
         return be.rho_states(B, T - 1, want_rho=True)
 
-    def _sample_primed(self, be, prime, noise, want_pred, save_states=False):
-        return be.rho_sample_primed(prime, noise, want_pred=want_pred, save_states=save_states)
+    def _sample_primed(self, be, prime, noise, want_pred, save_states=False, length=None, n=None):
+        return be.rho_sample_primed(prime, noise, want_pred=want_pred, save_states=save_states, **self._plan_shape(noise, length, n))
 
     def _stream_entries(self, be):
         return be.rho_stream_state, be.rho_stream
@@ -590,7 +627,7 @@ class RhoCMPS(CMPS):
         be.rho_set_state(self.columns(), num_paths, keep_states + 1, train=True)     # (its T is the stash's capacity, not the tables')
         return be
 
-    def open_stream(self, num_paths, max_steps, temp=1, seed=None, keep_states=0):
+    def open_stream(self, num_paths, max_steps, temp=1, seed=None, keep_states=0, device_noise=False):
         """CMPS.open_stream, from rho_0.  ``keep_states = S > 0`` also keeps the columns of every follow / generate call of at most S
         steps (a longer one raises ValueError), so that ``st.states()`` [num_paths, steps, D, D] and ``st.purity()`` [num_paths, steps]
         return the lab-frame rho and tr rho^2 after every step of the last call: rho along a run of any length from a stash that holds
@@ -599,37 +636,40 @@ class RhoCMPS(CMPS):
         keep_states = int(keep_states)
         if keep_states < 0:
             raise ValueError("keep_states must not be negative")
-        return SampleStream(self, num_paths, max_steps, temp=temp, seed=seed, keep_states=min(keep_states, int(max_steps)))
+        return SampleStream(self, num_paths, max_steps, temp=temp, seed=seed, keep_states=min(keep_states, int(max_steps)),
+                            device_noise=device_noise)
 
-    def _sample_scan(self, num_samples, length, temp, seed, noise, save_states, prime=None, want_pred=False):
+    def _sample_scan(self, num_samples, length, temp, seed, noise, save_states, prime=None, want_pred=False, device_noise=False):
         """(backend, what its sampler returned, steps of the scan): unprimed, or (``prime``) P = T' - 1 forced steps in front."""
-        noise = self._noise(num_samples, length, temp, seed, noise)
         if prime is None:
+            noise = self._noise(num_samples, length, temp, seed, noise, device_noise)
             be = self._prepare(num_samples, length + 1, train=save_states)
-            return be, be.rho_sample(noise, save_states=save_states), length
+            return be, be.rho_sample(noise, save_states=save_states, **self._plan_shape(noise, length, num_samples)), length
         prime = self._prime(prime, num_samples)
+        noise = self._noise(num_samples, length, temp, seed, noise, device_noise, first_step=prime.shape[1] - 1)
         be = self._prepare(num_samples, prime.shape[1] + length, train=save_states)      # one table row per step, forced or sampled
-        return be, self._sample_primed(be, prime, noise, want_pred, save_states), prime.shape[1] - 1 + length
+        return be, self._sample_primed(be, prime, noise, want_pred, save_states, length, num_samples), prime.shape[1] - 1 + length
 
-    def sample(self, num_samples, length, temp=1, seed=None, noise=None, prime=None, return_pred=False):
-        """model.py:103-116: waveforms [num_samples, length] = A * running sum of the sampled increments.
+    def sample(self, num_samples, length, temp=1, seed=None, noise=None, prime=None, return_pred=False, device_noise=False):
+        """model.py:103-116: waveforms [num_samples, length] = A * running sum of the sampled increments.  ``device_noise`` as in
+        PsiCMPS.sample: the noise is drawn on the device (cmps_noise_fill) unless ``noise`` is given.
 
         ``prime`` / ``return_pred`` as in PsiCMPS.sample: the state is first teacher-forced on the clip -- T' - 1 steps of _rho_update
         (model.py:144-150) on its increments -- and the ``length`` sampled steps follow in the same scan (cmps_rho_sample_primed);
         ``return_pred`` adds Re tr((Rt + Rt^dagger) rho) delta_t before every forced step, [num_samples, T' - 1]."""
         if prime is None and return_pred:
             raise ValueError("return_pred needs a prime: the predictions belong to the teacher-forced steps")
-        return self._sample_scan(num_samples, length, temp, seed, noise, False, prime, bool(return_pred))[1]
+        return self._sample_scan(num_samples, length, temp, seed, noise, False, prime, bool(return_pred), device_noise)[1]
 
-    def rho_evolve_with_sampling(self, num_samples, length, temp=1, seed=None, noise=None, prime=None) -> np.ndarray:
+    def rho_evolve_with_sampling(self, num_samples, length, temp=1, seed=None, noise=None, prime=None, device_noise=False) -> np.ndarray:
         """model.py:86-92: rho after every sampled step, [num_samples, length, D, D]; with ``prime`` [num_samples, P + length, D, D], the
         P = T' - 1 teacher-forced steps first."""
-        be, _, steps = self._sample_scan(num_samples, length, temp, seed, noise, True, prime)
+        be, _, steps = self._sample_scan(num_samples, length, temp, seed, noise, True, prime, device_noise=device_noise)
         return be.rho_states(num_samples, steps, want_rho=True)
 
-    def purity(self, num_samples, length, temp=1, seed=None, noise=None, prime=None) -> np.ndarray:
+    def purity(self, num_samples, length, temp=1, seed=None, noise=None, prime=None, device_noise=False) -> np.ndarray:
         """model.py:94-101: tr rho^2 along sampled paths, [num_samples, length]; with ``prime`` [num_samples, P + length], forced steps first."""
-        be, _, steps = self._sample_scan(num_samples, length, temp, seed, noise, True, prime)
+        be, _, steps = self._sample_scan(num_samples, length, temp, seed, noise, True, prime, device_noise=device_noise)
         return be.rho_states(num_samples, steps, want_rho=False, want_purity=True)
 
 

@@ -11,6 +11,8 @@ waveform is the clip followed by its continuation.  Writes ``sample_<i>.wav`` (1
 [-1, 1)) and ``samples.npy`` (float32 [num_samples, samples], unclipped) into --out_dir.
 ``--segment S`` runs the same job through a resumable stream (model.open_stream; cmps_psi_stream / cmps_rho_stream) in segments of S steps: the
 prime, if given, is followed, then the waveform is generated; the files and the return value are the same.
+``--device_noise`` (plain, --prime and --segment runs) draws the noise on the device instead of on the host (cmps_noise_fill): counter-based
+normals of (--seed, path, step), so --segment then changes no bit of the waveform however it cuts the run.
 ``--score FILE`` (PsiCMPS; a clip as --prime reads it) samples nothing: the clip is followed and scored through a stream
 (SampleStream.score; cmps_psi_stream_score), in segments of --segment steps when given.  Writes ``nll.npy`` (float32 [clips, T' - 1]: the
 negative log-likelihood of every sample, model.py:293-294) and ``pred.npy`` (the model's expected increments) into --out_dir and prints
@@ -88,6 +90,8 @@ def build_parser():
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--prime", default=None, metavar="FILE", help=".wav (16-bit mono) or .npy clip to continue")
     p.add_argument("--score", default=None, metavar="FILE", help=".wav (16-bit mono) or .npy clip to follow and score instead of sampling (PsiCMPS)")
+    p.add_argument("--device_noise", action="store_true", help="draw the noise on the device, from (--seed, path, step) (cmps_noise_fill), "
+                   "instead of a host Generator")
     p.add_argument("--segment", type=int, default=None, metavar="S", help="run through a resumable stream in segments of S steps")
     p.add_argument("--out_dir", default="./samples")
     p.add_argument("--kernel_variant", type=int, default=0, help="as in audio_mps_amd.train")
@@ -99,7 +103,7 @@ def _segmented(model, args, n, length):
     S = args.segment
     prime = None if args.prime is None else CMPS._prime(load_prime(args.prime, args.sample_rate), n)
     P = 0 if prime is None else prime.shape[1] - 1
-    st = model.open_stream(n, P + length, temp=args.temp, seed=args.seed)
+    st = model.open_stream(n, P + length, temp=args.temp, seed=args.seed, device_noise=args.device_noise)
     parts = []
     if prime is not None:
         parts.append(np.broadcast_to(prime, (n, prime.shape[1])))
@@ -162,6 +166,8 @@ def main(argv=None, backend=None):
     if args.segment is not None and args.segment < 1:
         raise ValueError("--segment must be positive")
     if args.score is not None:
+        if args.device_noise:
+            raise ValueError("--score follows and scores its clip and samples nothing: there is no noise for --device_noise to draw")
         if args.prime is not None:
             raise ValueError("--score follows and scores its clip and samples nothing: it does not go with --prime")
         if rho:
@@ -170,10 +176,10 @@ def main(argv=None, backend=None):
     if args.segment is not None:
         waves = _segmented(model, args, n, length)
     elif args.prime is None:
-        waves = model.sample(n, length, temp=args.temp, seed=args.seed) / model.A
+        waves = model.sample(n, length, temp=args.temp, seed=args.seed, device_noise=args.device_noise) / model.A
     else:
         prime = CMPS._prime(load_prime(args.prime, args.sample_rate), n)
-        cont = model.continue_clip(prime, n, length, temp=args.temp, seed=args.seed)
+        cont = model.continue_clip(prime, n, length, temp=args.temp, seed=args.seed, device_noise=args.device_noise)
         waves = np.concatenate([np.broadcast_to(prime, (n, prime.shape[1])), cont], axis=1)
     waves = np.ascontiguousarray(waves, dtype=np.float32)
     os.makedirs(args.out_dir, exist_ok=True)

@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -26,6 +26,15 @@ def _to_interleaved(z: np.ndarray, device) -> torch.Tensor:
 def _from_interleaved(t: torch.Tensor) -> np.ndarray:
     o = t.cpu().numpy()
     return (o[..., 0] + 1j * o[..., 1]).astype(np.complex64)
+
+
+class NoisePlan(NamedTuple):
+    """Noise to be drawn on the device instead of an array of it: what a sampler entry takes as ``noise`` next to ``length`` and ``n``.
+    Path b, sampled step j gets std * z(seed, b, first_step + j) of include/cmps.h (cmps_noise_fill); ``first_step`` is the table row of
+    the first sampled step: 0 for a plain sample, prime_T - 1 behind a prime, the stream's position in a segment."""
+    seed: int
+    first_step: int
+    std: float
 
 
 class HipScan:
@@ -116,7 +125,7 @@ class HipScan:
         return mode if mode in (_capi.CMPS_RANK1_EXACT_F32, _capi.CMPS_RANK1_BF16X2, _capi.CMPS_RANK1_F16X2) else _capi.CMPS_RANK1_BF16X3
 
     def kernel_events(self, on: bool):
-        """cmps_set_option(CMPS_OPT_KERNEL_EVENTS): bracket every kernel of forward() / backward() and of sample() / sample_primed() / stream() / stream_score() / rho_sample_primed() / rho_stream() with HIP
+        """cmps_set_option(CMPS_OPT_KERNEL_EVENTS): bracket every kernel of forward() / backward() and of sample() / sample_primed() / stream() / stream_score() / rho_sample_primed() / rho_stream() / draw_noise() with HIP
         events (a measurement aid, used by bench.py outside its timed region)."""
         _capi.check(self._h, self._lib.cmps_set_option(self._h, _capi.CMPS_OPT_KERNEL_EVENTS, 1 if on else 0))
 
@@ -347,11 +356,42 @@ class HipScan:
         _capi.check(self._h, fn(self._h, d_in.data_ptr(), d_sig.data_ptr(), float(t), x.shape[0], d_out.data_ptr(), self._stream()))
         return _from_interleaved(d_out)
 
-    def _sample(self, fn, noise: np.ndarray, *flags) -> np.ndarray:
-        """Pre-drawn noise [length, n] (the reference's layout) up, waveforms [n, length] down: `fn` is cmps_{psi,rho}_sample."""
-        noise = np.asarray(noise, dtype=np.float32)
-        length, n = noise.shape
-        d_noise = torch.from_numpy(np.ascontiguousarray(noise.T)).to(self.device)
+    def draw_noise(self, seed: int, first_step: int, n: int, length: int, std: float, first_path: int = 0) -> torch.Tensor:
+        """cmps_noise_fill: the samplers' noise drawn on the device, float32 [n, length] (the layout the sampler entries read), element
+        [b, j] = std * z(seed, first_path + b, first_step + j) of include/cmps.h.  No host copy, no synchronisation."""
+        n, length = int(n), int(length)
+        if n < 1 or length < 1:
+            raise ValueError("draw_noise needs n >= 1 and length >= 1")
+        out = torch.empty((n, length), dtype=torch.float32, device=self.device)
+        _capi.check(self._h, self._lib.cmps_noise_fill(self._h, int(seed), int(first_step), int(first_path), n, length, float(std),
+                                                       out.data_ptr(), self._stream()))
+        return out
+
+    def _device_noise(self, noise, length=None, n=None):
+        """What a sampler entry is handed as ``noise`` -> (device tensor [n, length], length, n).  A host array [length, n] (the reference's
+        layout) is transposed and uploaded; a device tensor [n, length] is used as it is; a NoisePlan is drawn by `draw_noise` for the
+        ``length`` and ``n`` given.  With an array, ``length`` and ``n`` default to its shape and must agree with it."""
+        if isinstance(noise, NoisePlan):
+            if length is None or n is None:
+                raise ValueError("a NoisePlan needs length and n: there is no array to take them from")
+            d_noise = self.draw_noise(noise.seed, noise.first_step, n, length, noise.std)
+        elif isinstance(noise, torch.Tensor):
+            if not (noise.is_cuda and noise.dtype == torch.float32 and noise.dim() == 2 and noise.is_contiguous()):
+                raise ValueError("device noise must be a contiguous float32 CUDA tensor [n, length]")
+            d_noise = noise
+        else:
+            noise = np.asarray(noise, dtype=np.float32)
+            if noise.ndim != 2:
+                raise ValueError("noise must be [length, n]")
+            d_noise = torch.from_numpy(np.array(noise.T, order="C")).to(self.device)    # (a copy: torch wants a writable array)
+        if (length is not None and int(length) != d_noise.shape[1]) or (n is not None and int(n) != d_noise.shape[0]):
+            raise ValueError(f"noise for {tuple(d_noise.shape)} (paths, steps) does not fit length={length}, n={n}")
+        return d_noise, int(d_noise.shape[1]), int(d_noise.shape[0])
+
+    def _sample(self, fn, noise, length, n, *flags) -> np.ndarray:
+        """Noise (`_device_noise`: pre-drawn [length, n] in the reference's layout, a device tensor, or a NoisePlan) in, waveforms
+        [n, length] down: `fn` is cmps_{psi,rho}_sample."""
+        d_noise, length, n = self._device_noise(noise, length, n)
         d_out = torch.empty((n, length), dtype=torch.float32, device=self.device)
         _capi.check(self._h, fn(self._h, d_noise.data_ptr(), n, length, d_out.data_ptr(), *flags, self._stream()))
         return d_out.cpu().numpy()
@@ -370,20 +410,20 @@ class HipScan:
         _capi.check(self._h, self._lib.cmps_psi_states(self._h, B, T, out.data_ptr(), self._stream()))
         return _from_interleaved(out)
 
-    def sample(self, noise: np.ndarray) -> np.ndarray:
-        """PsiCMPS.sample for pre-drawn noise [length, n] (the reference's layout) -> waveforms [n, length]."""
-        return self._sample(self._lib.cmps_psi_sample, noise)
+    def sample(self, noise, length: Optional[int] = None, n: Optional[int] = None) -> np.ndarray:
+        """PsiCMPS.sample for pre-drawn noise [length, n] (the reference's layout) -> waveforms [n, length].  ``noise`` may also be a device
+        tensor [n, length] or a NoisePlan with ``length`` and ``n`` (`_device_noise`); so for every sampler entry below."""
+        return self._sample(self._lib.cmps_psi_sample, noise, length, n)
 
-    def _sample_primed(self, fn, prime: np.ndarray, noise: np.ndarray, want_pred: bool, *flags):
-        """Clips [n_prime, prime_T] and pre-drawn noise [length, n] (the reference's layout) up, waveforms [n, length] and, with want_pred,
-        the forced steps' predictions [n, prime_T - 1] down: `fn` is cmps_{psi,rho}_sample_primed."""
+    def _sample_primed(self, fn, prime: np.ndarray, noise, length, n, want_pred: bool, *flags):
+        """Clips [n_prime, prime_T] up and the noise in (`_device_noise`), waveforms [n, length] and, with want_pred, the forced steps'
+        predictions [n, prime_T - 1] down: `fn` is cmps_{psi,rho}_sample_primed."""
         prime = np.array(prime, dtype=np.float32, order="C")          # (a copy: torch wants a writable array)
-        noise = np.asarray(noise, dtype=np.float32)
-        if prime.ndim != 2 or noise.ndim != 2:
-            raise ValueError("prime must be [n_prime, prime_T] and noise [length, n]")
-        (n_prime, prime_T), (length, n) = prime.shape, noise.shape
+        if prime.ndim != 2:
+            raise ValueError("prime must be [n_prime, prime_T]")
+        n_prime, prime_T = prime.shape
+        d_noise, length, n = self._device_noise(noise, length, n)
         d_prime = torch.from_numpy(prime).to(self.device)
-        d_noise = torch.from_numpy(np.array(noise.T, order="C")).to(self.device)
         d_out = torch.empty((n, length), dtype=torch.float32, device=self.device)
         d_pred = torch.empty((n, max(prime_T - 1, 0)), dtype=torch.float32, device=self.device) if want_pred else None
         _capi.check(self._h, fn(self._h, d_prime.data_ptr(), n_prime, prime_T, d_noise.data_ptr(), n, length, d_out.data_ptr(),
@@ -391,12 +431,12 @@ class HipScan:
         out = d_out.cpu().numpy()
         return (out, d_pred.cpu().numpy()) if want_pred else out
 
-    def sample_primed(self, prime: np.ndarray, noise: np.ndarray, want_pred: bool = False):
+    def sample_primed(self, prime: np.ndarray, noise, want_pred: bool = False, length: Optional[int] = None, n: Optional[int] = None):
         """cmps_psi_sample_primed: teacher-force the clips ``prime`` [n_prime, prime_T] (n_prime = n, or 1 for one clip shared by every
         path), then sample ``length`` steps with the pre-drawn ``noise`` [length, n] (the reference's layout, as `sample` takes it).
         Returns out [n, length] = A * running sum of the sampled increments (zero at the hand-over), or (out, pred [n, prime_T - 1])
         with want_pred: the model's expected increment of every forced step.  After set_params with T >= prime_T + length."""
-        return self._sample_primed(self._lib.cmps_psi_sample_primed, prime, noise, want_pred)
+        return self._sample_primed(self._lib.cmps_psi_sample_primed, prime, noise, length, n, want_pred)
 
     def _stream_state(self, bytes_fn, n: int, hint: str = "") -> torch.Tensor:
         """Device memory for the stream-state records of ``n`` paths: `bytes_fn` is cmps_{psi,rho}_stream_state_bytes."""
@@ -417,17 +457,17 @@ class HipScan:
                 raise ValueError(f"a stream state must be the tensor stream_state({n}) returned")
         return n
 
-    def _stream_call(self, fn, bytes_fn, state_in, state_out, k0, audio, noise, want_pred, n, *flags):
-        """One segment: the signal block [n_audio, forced + 1] and the noise [length, n] up, (out [n, length], pred [n, forced] or None)
-        down.  `fn` / `bytes_fn` are cmps_{psi,rho}_stream / _stream_state_bytes, `flags` what `fn` takes behind pred_dev."""
-        forced = length = 0
+    def _stream_call(self, fn, bytes_fn, state_in, state_out, k0, audio, noise, want_pred, n, length, *flags):
+        """One segment: the signal block [n_audio, forced + 1] up and the noise in (`_device_noise`; None: no sampled step), (out [n, length],
+        pred [n, forced] or None) down.  `fn` / `bytes_fn` are cmps_{psi,rho}_stream / _stream_state_bytes, `flags` what `fn` takes behind
+        pred_dev."""
+        forced = 0
         d_audio = d_noise = d_out = d_pred = None
         n_audio = 1
         if noise is not None:
-            noise = np.asarray(noise, dtype=np.float32)
-            if noise.ndim != 2:
-                raise ValueError("noise must be [length, n]")
-            length, n = noise.shape
+            d_noise, length, n = self._device_noise(noise, length, n)
+        else:
+            length = 0
         if audio is not None:
             audio = np.array(audio, dtype=np.float32, order="C")       # (a copy: torch wants a writable array)
             if audio.ndim != 2 or audio.shape[1] < 1:
@@ -436,8 +476,6 @@ class HipScan:
         n = self._stream_paths(bytes_fn, state_in, state_out, n, n_audio)
         if forced > 0:
             d_audio = torch.from_numpy(audio).to(self.device)
-        if length > 0:
-            d_noise = torch.from_numpy(np.array(noise.T, order="C")).to(self.device)
         d_out = torch.empty((n, length), dtype=torch.float32, device=self.device)
         if want_pred:
             d_pred = torch.empty((n, forced), dtype=torch.float32, device=self.device)
@@ -452,14 +490,14 @@ class HipScan:
         return self._stream_state(self._lib.cmps_psi_stream_state_bytes, n)
 
     def stream(self, state_in: Optional[torch.Tensor], state_out: Optional[torch.Tensor], k0: int, audio, noise, want_pred: bool = False,
-               n: Optional[int] = None):
+               n: Optional[int] = None, length: Optional[int] = None):
         """cmps_psi_stream, one segment of a resumable scan on table rows k0 ..: ``audio`` [n_audio, forced + 1] (n_audio = n, or 1: one
         signal shared by every path; its first column is the sample before the segment's first forced step) or None, then ``noise``
         [length, n] (the reference's layout) or None.  ``state_in`` is None exactly at k0 = 0, ``state_out`` may be None or ``state_in``
         (tensors of `stream_state`).  Returns (out [n, length], pred [n, forced] with want_pred, else None).  The path count is taken from
         the noise, else from a state tensor, else from ``n`` or the audio's rows."""
         return self._stream_call(self._lib.cmps_psi_stream, self._lib.cmps_psi_stream_state_bytes, state_in, state_out, k0, audio, noise,
-                                 want_pred, n)
+                                 want_pred, n, length)
 
     def stream_score(self, state_in: Optional[torch.Tensor], state_out: Optional[torch.Tensor], k0: int, audio, want_nll: bool = True,
                      want_pred: bool = False, n: Optional[int] = None, loss=None):
@@ -551,14 +589,15 @@ class HipScan:
         """RhoCMPS._update_ancilla_rho for a batch of matrices [B, D, D] (host in, host out)."""
         return self._ancilla(self._lib.cmps_rho_update_ancilla, "rho", rho, signal, t)
 
-    def rho_sample(self, noise: np.ndarray, save_states: bool = False) -> np.ndarray:
+    def rho_sample(self, noise, save_states: bool = False, length: Optional[int] = None, n: Optional[int] = None) -> np.ndarray:
         """RhoCMPS.sample for pre-drawn noise [length, n] -> waveforms [n, length]."""
-        return self._sample(self._lib.cmps_rho_sample, noise, 1 if save_states else 0)
+        return self._sample(self._lib.cmps_rho_sample, noise, length, n, 1 if save_states else 0)
 
-    def rho_sample_primed(self, prime: np.ndarray, noise: np.ndarray, want_pred: bool = False, save_states: bool = False):
+    def rho_sample_primed(self, prime: np.ndarray, noise, want_pred: bool = False, save_states: bool = False,
+                          length: Optional[int] = None, n: Optional[int] = None):
         """cmps_rho_sample_primed: `sample_primed` for RhoCMPS, from the columns of rho_set_state.  save_states keeps the columns of all
         prime_T - 1 + length steps for rho_states (a train=True rho workspace with T >= prime_T + length)."""
-        return self._sample_primed(self._lib.cmps_rho_sample_primed, prime, noise, want_pred, 1 if save_states else 0)
+        return self._sample_primed(self._lib.cmps_rho_sample_primed, prime, noise, length, n, want_pred, 1 if save_states else 0)
 
     def rho_stream_state(self, n: int) -> torch.Tensor:
         """`stream_state` for RhoCMPS (cmps_rho_stream_state_bytes): valid for this object's D and variant and the rank of rho_set_state,
@@ -566,12 +605,12 @@ class HipScan:
         return self._stream_state(self._lib.cmps_rho_stream_state_bytes, n, " (or rho_set_state has not been called)")
 
     def rho_stream(self, state_in: Optional[torch.Tensor], state_out: Optional[torch.Tensor], k0: int, audio, noise, want_pred: bool = False,
-                   n: Optional[int] = None, save_states: bool = False):
+                   n: Optional[int] = None, save_states: bool = False, length: Optional[int] = None):
         """cmps_rho_stream: `stream` for RhoCMPS, from the columns of rho_set_state (states of `rho_stream_state`).  save_states keeps the
         columns of this segment's steps for rho_states(n, forced + length): a train=True rho workspace whose T - 1 is at least that many
         steps; the rho workspace's T is a stash capacity only and may be smaller than set_params's."""
         return self._stream_call(self._lib.cmps_rho_stream, self._lib.cmps_rho_stream_state_bytes, state_in, state_out, k0, audio, noise,
-                                 want_pred, n, 1 if save_states else 0)
+                                 want_pred, n, length, 1 if save_states else 0)
 
     def rho_states(self, B: int, steps: int, want_rho: bool = True, want_purity: bool = False):
         """Lab-frame rho [B, steps, D, D] and/or purity [B, steps] of the last saved scan."""

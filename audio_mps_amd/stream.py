@@ -2,7 +2,9 @@
 
 The reference samples a whole waveform in one tf.scan (model.py:242-251) and has nothing that carries on.  A ``SampleStream`` keeps what
 the sampler kernel carries between two steps on the device, so a scan can be continued, can alternate between teacher-forced blocks
-(``follow``) and sampled ones (``generate``), and can follow only.  Cutting a run into segments changes no bit of it.
+(``follow``) and sampled ones (``generate``), and can follow only.  Cutting a run into segments changes no bit of it.  A stream opened
+with ``device_noise=True`` draws the noise of a generated step on the device, as a function of (seed, path, position) alone
+(cmps_noise_fill), instead of on the host.
 
     st = model.open_stream(num_paths=4, max_steps=3 * 16000, seed=0)
     pred = st.follow(block)             # [4, steps]: the model's expected increment before every followed sample
@@ -24,7 +26,7 @@ class SampleStream:
     """Returned by ``PsiCMPS.open_stream`` / ``RhoCMPS.open_stream``.  ``position`` is the number of steps taken (the next table row), ``max_steps`` the number the
     stream was sized for, ``last`` the last sample per path [num_paths] (None while the stream has seen no audio and generated nothing)."""
 
-    def __init__(self, model, num_paths: int, max_steps: int, temp=1, seed=None, keep_states: int = 0):
+    def __init__(self, model, num_paths: int, max_steps: int, temp=1, seed=None, keep_states: int = 0, device_noise: bool = False):
         if num_paths < 1 or max_steps < 1:
             raise ValueError("open_stream needs num_paths >= 1 and max_steps >= 1")
         self.num_paths, self.max_steps, self.keep_states = int(num_paths), int(max_steps), int(keep_states)
@@ -33,6 +35,11 @@ class SampleStream:
         self.last = None
         self._A = np.float32(model.A)
         self._std = float(model.sigma) * math.sqrt(temp * float(model.delta_t))      # CMPS._noise
+        self.device_noise = bool(device_noise)
+        self.noise_seed = None         # device noise: the seed every generated step's noise is a function of, with its path and position
+        if self.device_noise:
+            model._device_noise_backend()                                            # (ValueError before anything runs)
+            self.noise_seed = model._noise_seed(seed)
         self._rng = np.random.default_rng(seed)
         self._be = model._prepare_stream(self.num_paths, self.max_steps, self.keep_states)   # T = max_steps + 1: one table row per step
         new_state, self._segment = model._stream_entries(self._be)
@@ -133,20 +140,27 @@ class SampleStream:
         """Sample ``length`` steps: [num_paths, length] in the clip's own units = the level when the sampled run began (0 on a fresh
         stream, model.py:244; else the last followed sample) + the running sum of the sampled increments, which the kernel state
         carries, so consecutive calls continue one waveform.  The noise [length, num_paths] comes from the stream's own Generator
-        (stddev sigma sqrt(temp delta_t), as CMPS._noise), or is passed in."""
+        (stddev sigma sqrt(temp delta_t), as CMPS._noise), or is passed in.  A stream opened with ``device_noise=True`` draws it on the
+        device instead (cmps_noise_fill): step k of path b gets stddev * z(noise_seed, b, k), a function of the stream's position alone, so
+        how a run is cut into calls -- or into processes -- changes no bit of it."""
         length, n = int(length), self.num_paths
         if length < 1:
             raise ValueError("generate needs length >= 1")
         if self.position + length > self.max_steps:                  # (before the draw: a refused call leaves the Generator alone)
             raise ValueError(f"the stream was opened for max_steps={self.max_steps}: {self.position} taken, {length} more asked for")
-        if noise is None:
-            noise = (self._std * self._rng.standard_normal((length, n))).astype(np.float32)
-        noise = np.asarray(noise, dtype=np.float32)
-        if noise.shape != (length, n):
-            raise ValueError(f"noise must be [{length}, {n}]")
+        kw = {}
+        if noise is None and self.device_noise:
+            from .scan import NoisePlan
+            noise, kw = NoisePlan(self.noise_seed, self.position, self._std), {"length": length}
+        else:
+            if noise is None:
+                noise = (self._std * self._rng.standard_normal((length, n))).astype(np.float32)
+            noise = np.asarray(noise, dtype=np.float32)
+            if noise.shape != (length, n):
+                raise ValueError(f"noise must be [{length}, {n}]")
         if self._level is None:
             self._level = np.zeros(n, dtype=np.float32) if self.last is None else self.last.copy()
-        out, _ = self._launch(length, self._segment, None, noise, False)
+        out, _ = self._launch(length, self._segment, None, noise, False, **kw)
         wave = (self._level[:, None] + out / self._A).astype(np.float32)
         self.last = wave[:, -1].copy()
         return wave

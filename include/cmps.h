@@ -84,7 +84,7 @@ enum {
     CMPS_OPT_F16_SCALE_SHIFT = 4 /* DIAGNOSTIC, default 0: added to the exponent of every data-dependent fp16 scale of the wave reverse
                         * scan's F16X2 arithmetic (range -40 .. 40).  A positive value pushes the pieces out of fp16 range on purpose:
                         * how tests/test_gpu_parity.py provokes CMPS_ERR_F16_RANGE.  No reference counterpart. */,
-    CMPS_OPT_KERNEL_EVENTS = 2 /* 1: every kernel cmps_psi_loss_fwd / _bwd, cmps_psi_sample, cmps_psi_sample_primed, cmps_psi_stream, cmps_psi_stream_score, cmps_rho_sample_primed and cmps_rho_stream launch is bracketed by two HIP events on the caller's stream
+    CMPS_OPT_KERNEL_EVENTS = 2 /* 1: every kernel cmps_psi_loss_fwd / _bwd, cmps_psi_sample, cmps_psi_sample_primed, cmps_psi_stream, cmps_psi_stream_score, cmps_rho_sample_primed, cmps_rho_stream and cmps_noise_fill (as k_noise_philox) launch is bracketed by two HIP events on the caller's stream
                         * (read and reset with cmps_kernel_times); 0 (default): nothing is recorded.  A measurement aid -- the reference
                         * has no counterpart (no tracing / profiling hooks); bench.py uses it OUTSIDE its timed region to price
                         * each kernel of a multi-kernel family against the pipe it runs on */
@@ -503,6 +503,42 @@ int cmps_rho_apply_step(cmps_handle_t h, float* vars_dev, float* adam_m_dev, flo
                         int rank, double global_batch, double lr_t, double beta1, double beta2, double epsilon, double h_reg,
                         double r_reg, double c_r, double c_h, int with_reg, float* params_dev, float* phi_dev, float* losses_dev,
                         void* scratch_dev, void* stream);
+
+/*
+ * The samplers' Gaussian noise, drawn on the device.  Replaces: tf.random_normal([length, n], stddev = sigma * sqrt(temp * delta_t)) inside
+ * `sample` (model.py:246 / :88, 96, 106), for the noise_dev argument of cmps_psi_sample, _sample_primed, cmps_psi_stream, cmps_rho_sample,
+ * _sample_primed and cmps_rho_stream -- same layout, row-major [path][step]:
+ *   noise_dev[b * length + j] = stddev * z(seed, first_path + b, first_step + j)      (one float32 multiply), b < n, j < length.
+ * The generator is counter-based: z is a pure function of (seed, path, step), so cutting a run differently, resuming it in another process
+ * or sharding its paths gives the same noise without any generator state.  THE DEFINITION (normative; tests/_noise_ref.py restates it in
+ * numpy) for a 64-bit seed, a 32-bit path and a 64-bit step index s:
+ *   q = s >> 2,  r = s & 3
+ *   (x0, x1, x2, x3) = Philox4x32-10(counter = (q & 0xffffffff, q >> 32, path, 0), key = (seed & 0xffffffff, seed >> 32))
+ *     multipliers 0xD2511F53 (on counter word 0) and 0xCD9E8D57 (on word 2), key increments 0x9E3779B9 and 0xBB67AE85, ten rounds, in the
+ *     Random123 form: per round  (c0, c1, c2, c3) <- (hi(M1 c2) ^ c1 ^ k0,  lo(M1 c2),  hi(M0 c0) ^ c3 ^ k1,  lo(M0 c0)),  then the key is bumped.
+ *     Known answers (counter words, key words -> output):
+ *       00000000 x 4                        | 00000000 x 2        -> 6627e8d5 e169c58d bc57ac4c 9b00dbd8
+ *       ffffffff x 4                        | ffffffff x 2        -> 408f276d 41c83b0e a20bc7c6 6d5451fd
+ *       243f6a88 85a308d3 13198a2e 03707344 | a4093822 299f31d0   -> d16cfe09 94fdcceb 5001e420 24126ea1
+ *   for the pair j in {0, 1}:
+ *     a = x[2j] >> 8,      u = (a + 1) * 2^-24     in (0, 1]   (exact in float32)
+ *     c = x[2j+1] >> 8,    v = c * 2^-23           in [0, 2)   (exact in float32)
+ *     rad = sqrtf(-2 * logf(u));   z[2j] = rad * cospif(v),   z[2j+1] = rad * sinpif(v)        (float32; the accurate functions, not the
+ *     fast intrinsics: near u -> 1 the result is the small difference a fast logarithm gets wrong)
+ *   z(seed, path, s) = z[r].   |z| <= sqrt(48 ln 2) ~ 5.768, and u > 0: no Inf or NaN can arise.
+ * The integer part is bit-exact; the float part is within a few float32 roundings of the definition evaluated in double.
+ * first_step is THE TABLE ROW OF THE FIRST SAMPLED STEP: 0 for cmps_*_sample, prime_T - 1 behind a prime, k0 + forced in a stream segment
+ * -- so a primed sample and a follow-then-generate stream with the same seed draw the same noise.  first_path keeps the paths of a
+ * caller who shards them over processes distinct.
+ * Needs no cmps_set_params: it works on a fresh handle of any D and in legacy mode.  Asynchronous on `stream`; never synchronises,
+ * allocates nothing, reads no device memory and touches no element outside noise_dev[0 .. n * length).
+ * CMPS_ERR_BAD_ARG, each with a message: a null handle or noise_dev; n < 1 or length < 1; stddev negative or not finite;
+ * first_path + n > 2^32; first_step + length overflowing 64 bits.
+ * With CMPS_OPT_KERNEL_EVENTS the launch is recorded as k_noise_philox.
+ */
+int cmps_noise_fill(cmps_handle_t h, unsigned long long seed, unsigned long long first_step,
+                    unsigned first_path, int n, int length, float stddev,
+                    float* noise_dev, void* stream);
 
 /*
  * Host utility (no GPU involved): CRC-32C (Castagnoli, reflected polynomial 0x82F63B78) of `n` bytes, continuing from
