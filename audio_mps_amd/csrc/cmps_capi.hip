@@ -828,10 +828,14 @@ int cmps_rho_loss_fwd(cmps_handle_t h, const float* audio_dev, int B, int T, flo
     const bool f16 = rank1_f16(h->rank1_mode);
     hipStream_t s = static_cast<hipStream_t>(stream);
     KBind kb(h);
-    hipError_t e = wide ? launch_fwd_rho_wide(P, h->W, audio_dev, loss_dev, f16, s)
-                 : mfma ? launch_fwd_rho_mfma(P, h->W, audio_dev, loss_dev, save_for_bwd != 0, f16, !h->rho_virtual_bwd, s)
-                 : wave ? launch_fwd_rho_wave(P, h->W, audio_dev, loss_dev, save_for_bwd != 0, s)
-                        : launch_fwd_rho(P, h->W, audio_dev, loss_dev, save_for_bwd != 0, s);
+    hipError_t e;
+    if (wide) e = launch_fwd_rho_wide(P, h->W, audio_dev, loss_dev, f16, s);   // k_fwd_wide_rho, k_hy_wide, ... (scopes inside)
+    else {
+        KScope ks(mfma ? "k_fwd_rho_mfma" : wave ? "k_fwd_rho_wave" : "k_fwd_rho", s);
+        e = mfma ? launch_fwd_rho_mfma(P, h->W, audio_dev, loss_dev, save_for_bwd != 0, f16, !h->rho_virtual_bwd, s)
+          : wave ? launch_fwd_rho_wave(P, h->W, audio_dev, loss_dev, save_for_bwd != 0, s)
+                 : launch_fwd_rho(P, h->W, audio_dev, loss_dev, save_for_bwd != 0, s);
+    }
     if (e != hipSuccess) return fail_hip(h, e, "cmps_rho_loss_fwd");
     const bool save = save_for_bwd != 0;
     h->rho = Saved{save, B, T - 1, audio_dev, loss_dev, wide ? RHO_STASH_WIDE : mfma ? RHO_STASH_MFMA : wave ? RHO_STASH_WAVE : RHO_STASH_BLOCK,
