@@ -18,11 +18,23 @@
 // What the two kernels share (effective R, regulariser sums, column sums, c_r / c_h scaling, Adam, losses) is written once below.
 #include "cmps_internal.h"
 
+// numpy's rounding points means every product and sum rounds on its own.  hipcc contracts a * b + c into one fma by default, and HIP's
+// __fmul_rn / __fadd_rn / __fsub_rn are the plain operators compiled under the header's settings, which do not stop it: Adam's m and v
+// came out as v_fmac_f32 (one rounding where the host has two; hundreds of ulp of m where b1 m and (1 - b1) g cancel).  So: no
+// contraction anywhere in this file, the double expressions of the chain rule included, and the float32 rounding points are spelled
+// with the helpers below, whose operators are compiled under this pragma.
+#pragma clang fp contract(off)
+
 namespace cmps {
 
 namespace {
 
 constexpr int ONT = 1024;
+
+__device__ __forceinline__ float mul_rn(float a, float b) { return a * b; }
+__device__ __forceinline__ float add_rn(float a, float b) { return a + b; }
+__device__ __forceinline__ float sub_rn(float a, float b) { return a - b; }
+__device__ __forceinline__ float div_rn(float a, float b) { return a / b; }      // (hipcc's float32 division is correctly rounded)
 
 __device__ __forceinline__ double block_sum_d(double v, double* red) {
 #pragma unroll
@@ -38,19 +50,23 @@ __device__ __forceinline__ double block_sum_d(double v, double* red) {
 
 // effective R of model.py:36-42 from the raw variables, in the host's float32 rounding: Z = fl(c_r Rx) + i fl(c_r Ry), R[i][j] = Z[i][j] - Z[j][j]
 __device__ __forceinline__ float2 eff_R(const float* Rx, const float* Ry, int D, int i, int j, float c_r, bool scaled) {
-    const float zx = scaled ? __fmul_rn(c_r, Rx[i * D + j]) : Rx[i * D + j], zy = scaled ? __fmul_rn(c_r, Ry[i * D + j]) : Ry[i * D + j];
-    const float dx = scaled ? __fmul_rn(c_r, Rx[j * D + j]) : Rx[j * D + j], dy = scaled ? __fmul_rn(c_r, Ry[j * D + j]) : Ry[j * D + j];
-    return make_float2(__fsub_rn(zx, dx), __fsub_rn(zy, dy));
+    const float zx = scaled ? mul_rn(c_r, Rx[i * D + j]) : Rx[i * D + j], zy = scaled ? mul_rn(c_r, Ry[i * D + j]) : Ry[i * D + j];
+    const float dx = scaled ? mul_rn(c_r, Rx[j * D + j]) : Rx[j * D + j], dy = scaled ? mul_rn(c_r, Ry[j * D + j]) : Ry[j * D + j];
+    return make_float2(sub_rn(zx, dx), sub_rn(zy, dy));
 }
+
+// float32 square root rounded to nearest, as np.sqrt returns it.  (__fsqrt_rn is HIP's native v_sqrt_f32: 1 ulp, not correctly rounded;
+// the double root rounded once to float32 is -- 53 bits are more than twice 24 plus 2.)
+__device__ __forceinline__ float sqrt_rn(float x) { return (float)sqrt((double)x); }
 
 // tf.train.AdamOptimizer with numpy's float32 rounding points (audio_mps_amd/train.py::AdamOptimizer.apply_gradients)
 __device__ __forceinline__ void adam(float* var, float* m, float* v, int idx, float g, float lr_t, float b1, float omb1, float b2,
                                      float omb2, float eps) {
-    const float mn = __fadd_rn(__fmul_rn(b1, m[idx]), __fmul_rn(omb1, g));
-    const float vn = __fadd_rn(__fmul_rn(b2, v[idx]), __fmul_rn(__fmul_rn(omb2, g), g));
+    const float mn = add_rn(mul_rn(b1, m[idx]), mul_rn(omb1, g));
+    const float vn = add_rn(mul_rn(b2, v[idx]), mul_rn(mul_rn(omb2, g), g));
     m[idx] = mn;
     v[idx] = vn;
-    var[idx] = __fsub_rn(var[idx], __fdiv_rn(__fmul_rn(lr_t, mn), __fadd_rn(__fsqrt_rn(vn), eps)));
+    var[idx] = sub_rn(var[idx], div_rn(mul_rn(lr_t, mn), add_rn(sqrt_rn(vn), eps)));
 }
 
 struct OptArgs {
@@ -83,7 +99,7 @@ __device__ __forceinline__ bool skip_step(const OptArgs& a, const float* gs, int
 }
 
 __device__ __forceinline__ double eff_f(const OptArgs& a, const float* fr, int d) {
-    return a.scaled_h ? (double)__fmul_rn(a.c_h, fr[d]) : (double)fr[d];
+    return a.scaled_h ? (double)mul_rn(a.c_h, fr[d]) : (double)fr[d];
 }
 
 // regulariser terms on the CURRENT effective parameters (train.py:55-60): sf = sum freqs^2, sr = sum |R|^2
@@ -177,7 +193,7 @@ __device__ __forceinline__ void write_params_common(const OptArgs& a, const floa
     }
     if (t == 0) params[2 * DD + 3 * D] = vars[0];
 }
-__device__ __forceinline__ float eff_f32(const OptArgs& a, const float* fr, int d) { return a.scaled_h ? __fmul_rn(a.c_h, fr[d]) : fr[d]; }
+__device__ __forceinline__ float eff_f32(const OptArgs& a, const float* fr, int d) { return a.scaled_h ? mul_rn(a.c_h, fr[d]) : fr[d]; }
 
 __global__ __launch_bounds__(ONT) void k_apply_step(OptArgs a, float* __restrict__ vars, float* __restrict__ am, float* __restrict__ av,
                                                     const float* __restrict__ gs, float* __restrict__ params,
@@ -209,7 +225,7 @@ __global__ __launch_bounds__(ONT) void k_apply_step(OptArgs a, float* __restrict
         write_losses(a, gs, sf, sr, losses);
         step_common(a, vars, am, av, gs, colsum, reinterpret_cast<float*>(colsum + 2 * D));
         for (int d = t; d < D; d += ONT) {
-            const double f = a.scaled_h ? (double)__fmul_rn(a.c_h, fr[d]) : (double)fr[d];
+            const double f = a.scaled_h ? (double)mul_rn(a.c_h, fr[d]) : (double)fr[d];
             const double fb = (double)gs[2 * DD + d] * a.inv_batch + (a.with_reg ? 2.0 * a.h_reg * f : 0.0);
             const float gf = (float)((a.scaled_h ? (double)a.c_h : 1.0) * fb);
             const double bx = (double)gs[2 * DD + D + d] * a.inv_batch, by = (double)gs[2 * DD + 2 * D + d] * a.inv_batch;
@@ -230,10 +246,10 @@ __global__ __launch_bounds__(ONT) void k_apply_step(OptArgs a, float* __restrict
         ssf += ab * ab;
     }
     const float ss32 = (float)block_sum_d((double)ssf, red);
-    const float invn = __fdiv_rn(1.0f, __fsqrt_rn(fmaxf(ss32, 1e-12f)));
+    const float invn = div_rn(1.0f, sqrt_rn(fmaxf(ss32, 1e-12f)));
     for (int d = t; d < D; d += ONT) {
-        params[2 * DD + D + d] = __fmul_rn(px[d], invn);
-        params[2 * DD + 2 * D + d] = __fmul_rn(py[d], invn);
+        params[2 * DD + D + d] = mul_rn(px[d], invn);
+        params[2 * DD + 2 * D + d] = mul_rn(py[d], invn);
     }
 }
 

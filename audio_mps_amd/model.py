@@ -146,6 +146,7 @@ class CMPS(_ScanModel):
 
     def __init__(self, hparams, data_iterator=None, freqs_in=None, R_in=None, seed: int = 0):
         self._device_owner = None      # a Trainer whose device-resident optimiser state is newer than self._variables (see `variables`)
+        self._dirty_owner = None       # that Trainer again, held STRONGLY while its device state has steps the host copies lack
         self._backend = None           # the scan implementation (the subclasses' `backend` argument); None: a HipScan on first use
         self._last = None              # the flat gradient sums of the last loss_and_grads (host copy)
         self.hparams = hparams
@@ -196,7 +197,11 @@ class CMPS(_ScanModel):
         steps that changed them), so loss / sample / effective_params / summaries never see stale parameters.
         ASSIGNING an entry (``m.variables["Rx"] = ...``, ``m.variables["Rx"] *= c``) while a device-resident state is live brings that
         state back and drops it, so the Trainer's next step starts from the host values (ADVICE r4: such writes used to be ignored);
-        the Trainer is held by a weak reference."""
+        the Trainer is held by a weak reference -- and, only while it has device steps that have not come back (Trainer._dirty), by a
+        strong one as well (``_dirty_owner``, set by the device step, dropped by the sync, drop_device_state and restore): a Trainer that
+        goes out of scope in that state, e.g. inside a helper that returns the model alone, stays alive until this attribute has brought
+        its steps back instead of taking them with it (ADVICE: they used to be lost without notice).  The model <-> Trainer cycle of that
+        interval is the garbage collector's to break; a Trainer that is not dirty is still released at once."""
         owner = self._owner()
         if owner is not None:
             owner._lazy_sync()

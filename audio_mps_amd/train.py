@@ -186,6 +186,7 @@ class Trainer:
         self.opt.t += 1
         self._apply(flat, global_batch)
         self._dirty = True                                          # the host copies (model.variables, Adam slots) are stale now
+        m._dirty_owner = self                                       # ... and until they are synced the model keeps this Trainer alive
         self.global_step += 1
         out = {"global_step": self.global_step, "global_batch": int(global_batch), "losses_dev": st["losses"]}
         if sync:
@@ -202,6 +203,7 @@ class Trainer:
             self.sync_to_host()
             self._dev = None
             self._dirty = False
+            self._release()
 
     def sync_to_host(self):
         """Device-resident state -> model.variables and the host AdamOptimizer's slots (checkpoints, sampling, inspection)."""
@@ -219,6 +221,12 @@ class Trainer:
         for name, dst in (("vars", self.model._variables), ("m", self.opt.m), ("v", self.opt.v)):
             for k, a in layout.unpack(fields, self._dev[name].cpu().numpy()).items():
                 dst[k] = np.asarray(a, dtype=np.float32).copy()
+        self._release()
+
+    def _release(self):
+        """Not dirty any more: the model drops its strong reference to this Trainer (CMPS.variables; the weak one stays)."""
+        if self.model._dirty_owner is self:
+            self.model._dirty_owner = None
 
     # -- checkpoint / resume (train.py:93: save_checkpoint_secs=60, automatic restore from logdir) --
     def save(self, path: str):
@@ -241,6 +249,7 @@ class Trainer:
             self.global_step = int(z["global_step"])
         self._dev = None                                            # the device-resident copy is rebuilt from the restored state
         self._dirty = False
+        self._release()
         return True
 
 

@@ -255,3 +255,80 @@ def test_model_accessors_follow_the_device_resident_state():
     gc.collect()
     assert ref() is None and m_dev._owner() is None                # the model does not keep its Trainer (and the GPU buffers) alive
     assert np.all(np.isfinite(m_dev.variables["Rx"]))
+
+
+def _psi_pair(D, B, T, device_steps, seed=0, audio_seed=3):
+    """PsiCMPS trainers on the same data and initial variables, one per entry of `device_steps` (True: the device-resident step)."""
+    from audio_mps_amd import HParams, PsiCMPS
+    from audio_mps_amd.scan import HipScan
+    from audio_mps_amd.train import Trainer
+    hp = HParams(minibatch_size=B, bond_dim=D, learning_rate=0.01)
+    data = make_audio(B, T, hp.delta_t, audio_seed)
+    return [Trainer(PsiCMPS(hp, data_iterator=data, seed=seed, backend=HipScan(D)), hp, device_step=dev) for dev in device_steps]
+
+
+def _train_and_return_the_model(steps):
+    """What a helper of a training script does: build model and Trainer, step without syncing, hand back the model alone."""
+    (t,) = _psi_pair(8, 4, 120, (True,))
+    for _ in range(steps):
+        t.step(sync=False)
+    assert t._dirty
+    return t.model
+
+
+def test_collected_trainer_does_not_lose_steps():
+    """ADVICE (medium): model._device_owner is a weak reference, so a Trainer collected while its device state was newer than the host
+    copies used to take every step since the last sync with it -- the model then showed the values of step 0.  While it is dirty the
+    model now holds the Trainer strongly as well (CMPS.variables): after the helper has returned and a collection has run, the model
+    reads as that of a host-path trainer after the same 3 steps."""
+    import gc
+    m_dev = _train_and_return_the_model(3)
+    gc.collect()
+    (t_host,) = _psi_pair(8, 4, 120, (False,))
+    R0 = t_host.model.R.copy()
+    for _ in range(3):
+        t_host.step()
+    m_host = t_host.model
+    assert np.max(np.abs(m_host.R - R0)) > 1e-4                     # (the steps are visible at the bars below)
+    for k in ("A", "Rx", "Ry", "freqs", "psi_x", "psi_y"):
+        np.testing.assert_allclose(m_dev.variables[k], m_host.variables[k], rtol=2e-5, atol=2e-6, err_msg=k)
+    np.testing.assert_allclose(m_dev.R, m_host.R, rtol=2e-5, atol=2e-6)
+    np.testing.assert_allclose(m_dev.psi_0, m_host.psi_0, rtol=2e-5, atol=2e-6)
+    assert m_dev._dirty_owner is None                               # synced by the first read: the Trainer is released again
+    gc.collect()
+    assert m_dev._owner() is None
+
+
+@pytest.mark.parametrize("kind", ["psi", "rho"])
+def test_device_trainer_resumes_into_a_device_trainer(kind, tmp_path):
+    """5 device steps, save, then a NEW model and a NEW Trainer(device_step=True) restore and take 3 more: losses of steps 6-8, every
+    variable and both Adam slots are bit-identical to an uninterrupted 8-step device run (same kernels, same inputs, no atomics:
+    test_runs_are_bit_reproducible), and opt.t == global_step == 8.  PsiCMPS at D = 16, RhoCMPS at (8, 3); T = 120, B = 4."""
+    from audio_mps_amd import HParams, PsiCMPS, RhoCMPS
+    from audio_mps_amd.scan import HipScan
+    from audio_mps_amd.train import Trainer
+    D = 16 if kind == "psi" else 8
+    hp = HParams(minibatch_size=4, bond_dim=D, learning_rate=0.01, initial_rank=None if kind == "psi" else 3)
+    data = make_audio(4, 120, hp.delta_t, 3)
+    cls = PsiCMPS if kind == "psi" else RhoCMPS
+    make = lambda seed: Trainer(cls(hp, data_iterator=data, seed=seed, backend=HipScan(D)), hp, device_step=True)
+    whole, first = make(0), make(0)
+    want = [whole.step() for _ in range(8)]
+    for _ in range(5):
+        first.step(sync=False)
+    path = os.path.join(tmp_path, "model.ckpt.npz")
+    first.save(path)
+    second = make(1)                                                # other initial variables: everything must come from the file
+    assert second.restore(path) and second.global_step == 5 and second.opt.t == 5
+    got = [second.step() for _ in range(3)]
+    assert second._dev is not None and second.opt.t == second.global_step == 8 and whole.opt.t == whole.global_step == 8
+    for a, b in zip(got, want[5:]):
+        assert a["global_step"] == b["global_step"]
+        for k in ("model_loss", "total_loss"):
+            assert np.isfinite(a[k]) and np.float32(a[k]).tobytes() == np.float32(b[k]).tobytes(), (a, b)
+    assert len({w["total_loss"] for w in want}) == 8                # (the run moves: equal losses are not a constant's)
+    whole.sync_to_host()
+    second.sync_to_host()
+    for k in cls.VARIABLE_NAMES if kind == "rho" else ("A", "Rx", "Ry", "freqs", "psi_x", "psi_y"):
+        assert second.model.variables[k].tobytes() == whole.model.variables[k].tobytes(), k
+        assert second.opt.m[k].tobytes() == whole.opt.m[k].tobytes() and second.opt.v[k].tobytes() == whole.opt.v[k].tobytes(), k
