@@ -55,7 +55,7 @@ SYMBOLS = (
     "cmps_psi_sample_primed", "cmps_psi_stream_state_bytes", "cmps_psi_stream", "cmps_psi_stream_score",
     "cmps_legacy_set_params", "cmps_legacy_loss_fwd", "cmps_legacy_loss_bwd",
     "cmps_rho_workspace_bytes", "cmps_rho_set_state", "cmps_rho_loss_fwd", "cmps_rho_loss_bwd",
-    "cmps_rho_update_ancilla", "cmps_rho_sample", "cmps_rho_sample_primed", "cmps_rho_stream_state_bytes", "cmps_rho_stream", "cmps_rho_states",
+    "cmps_rho_update_ancilla", "cmps_rho_sample", "cmps_rho_sample_primed", "cmps_rho_stream_state_bytes", "cmps_rho_stream", "cmps_rho_stream_score", "cmps_rho_states",
     "cmps_rho_apply_step_scratch_bytes", "cmps_rho_apply_step", "cmps_noise_fill", "cmps_crc32c",
 )
 
@@ -143,6 +143,8 @@ def _declare(lib):
     lib.cmps_rho_stream_state_bytes.restype = c_size_t
     lib.cmps_rho_stream.argtypes = [vp, vp, vp, c_int, vp, c_int, c_int, vp, c_int, c_int, vp, vp, c_int, vp]
     lib.cmps_rho_stream.restype = c_int
+    lib.cmps_rho_stream_score.argtypes = [vp, vp, vp, c_int, vp, c_int, c_int, c_int, vp, vp, vp, c_int, vp]
+    lib.cmps_rho_stream_score.restype = c_int
     lib.cmps_rho_states.argtypes = [vp, c_int, c_int, vp, vp, vp]
     lib.cmps_rho_states.restype = c_int
     lib.cmps_rho_apply_step_scratch_bytes.argtypes = [c_int, c_int]

@@ -898,17 +898,17 @@ static int rho_stream_rec_floats(const cmps_handle_s* h) {
     return rho_sampler_mfma(h) ? stream_rec_rho_mfma(h->W.rank) : stream_rec_rho(h->W.rank, h->D);
 }
 
-// What cmps_rho_sample, cmps_rho_sample_primed and cmps_rho_stream do behind their own argument checks: the workspace checks, the kernel
-// choice, the launch of one SampleDev and the record for cmps_rho_states.  The scan has S.PR.PF + S.length steps.
+// What cmps_rho_sample, cmps_rho_sample_primed, cmps_rho_stream and cmps_rho_stream_score do behind their own argument checks: the
+// workspace checks, the kernel choice, the launch of one SampleDev and the record for cmps_rho_states.  The scan has S.PR.PF + S.length steps.
 static int rho_sample_run(cmps_handle_t h, const char* who, const SampleDev& S, int save_states, void* stream) {
     const std::string w(who);
     const int n = S.n, steps = S.PR.PF + S.length;
     const bool mfma = rho_sampler_mfma(h);
     const SampleMode mode = sample_mode(S);
-    if (mode == SAMPLE_SCORE) return fail_hip(h, hipErrorInvalidValue, who);      // (not reachable: no cmps_rho_stream_score; the tables below end at STREAM)
-    static const char* const names[2][3] = {{"k_sample_rho", "k_sample_rho_primed", "k_sample_rho_stream"},
-                                            {"k_sample_rho_mfma", "k_sample_rho_mfma_primed", "k_sample_rho_mfma_stream"}};   // [mfma][SampleMode]
-    static const char* const steps_name[3] = {"length", "(prime_T-1+length)", "(forced+length)"};
+    static const char* const names[2][4] = {{"k_sample_rho", "k_sample_rho_primed", "k_sample_rho_stream", "k_sample_rho_score"},
+                                            {"k_sample_rho_mfma", "k_sample_rho_mfma_primed", "k_sample_rho_mfma_stream",
+                                             "k_sample_rho_mfma_score"}};   // [mfma][SampleMode]
+    static const char* const steps_name[4] = {"length", "(prime_T-1+length)", "(forced+length)", "forced"};
     // (only when the SAMPLER's three column arrays exceed the LDS: the workspace section exists from a smaller rank * D on, for the
     // reverse scan's four -- ADVICE r3)
     if (!mfma && rho_cols_spill(3, h->W.rank, h->P.D) && n > h->rho_B)
@@ -962,6 +962,23 @@ int cmps_rho_stream(cmps_handle_t h, const void* state_in_dev, void* state_out_d
                             rho_stream_rec_floats(h), ST, S))
         return c;
     return rho_sample_run(h, "cmps_rho_stream", S, save_states, stream);
+}
+
+int cmps_rho_stream_score(cmps_handle_t h, const void* state_in_dev, void* state_out_dev, int k0, const float* audio_dev, int n_audio, int forced,
+                          int n, float* nll_dev, float* loss_dev, float* pred_dev, int save_states, void* stream) {
+    if (!h) return CMPS_ERR_BAD_ARG;
+    if (!h->params_set || h->legacy || !h->rho_set)
+        return fail(h, CMPS_ERR_STATE, "cmps_rho_stream_score: call cmps_set_params and cmps_rho_set_state first (not available in legacy mode)");
+    if (n < 1 || forced < 1 || k0 < 0) return fail(h, CMPS_ERR_BAD_ARG, "cmps_rho_stream_score: need n >= 1, forced >= 1 and k0 >= 0");
+    if (int c = stream_check_state(h, "cmps_rho_stream_score", state_in_dev, k0)) return c;
+    if (!audio_dev) return fail(h, CMPS_ERR_BAD_ARG, "cmps_rho_stream_score: needs audio_dev");
+    if (!loss_dev) return fail(h, CMPS_ERR_BAD_ARG, "cmps_rho_stream_score: needs loss_dev (the running loss per path)");
+    if (int c = sample_check_clips(h, "cmps_rho_stream_score", "n_audio", n_audio, n)) return c;
+    if (int c = sample_check_rows(h, "cmps_rho_stream_score", "k0 + forced + 1", (long long)k0 + forced)) return c;
+    const StreamDev ST{static_cast<const float*>(state_in_dev), static_cast<float*>(state_out_dev), k0, rho_stream_rec_floats(h)};
+    const ScoreDev SC{nll_dev, loss_dev};
+    const PrimeDev PR{audio_dev, n_audio == 1 ? 0 : forced + 1, forced, pred_dev};
+    return rho_sample_run(h, "cmps_rho_stream_score", SampleDev{nullptr, n, 0, nullptr, PR, &ST, &SC}, save_states, stream);   // (every step is forced)
 }
 
 int cmps_rho_states(cmps_handle_t h, int B, int steps, float* rho_out_dev, float* purity_out_dev, void* stream) {

@@ -342,7 +342,7 @@ hipError_t launch_update_ancilla_rho(const Dev& P, const float* rho_in, const fl
 // `length` sampled ones; pred [n][PF] may be null.  ST (cmps_*_stream): one segment of a resumable scan -- the primed arguments with PF =
 // forced (either count may be 0, not both), on table rows k0 .. k0 + PF + length - 1; the state a kernel carries from one step into the
 // next is read from `in` (null: the start of a scan, psi_0 or the columns of cmps_rho_set_state) and written to `out` (null: not kept),
-// `rec` floats per path.  in == out is allowed: a path reads its record before it writes it.  SC (cmps_psi_stream_score): a stream
+// `rec` floats per path.  in == out is allowed: a path reads its record before it writes it.  SC (cmps_{psi,rho}_stream_score): a stream
 // segment of PF forced steps that also gives the loss increment of every step.
 // Whoever fills the record zeroes what its mode does not use (unprimed: PR; scored: noise, length, out); a null ST / SC reaches the kernel as zeros.
 struct PrimeDev {
@@ -371,8 +371,8 @@ struct SampleDev {
 inline StreamDev stream_of(const SampleDev& S) { return S.ST ? *S.ST : StreamDev{}; }
 inline ScoreDev score_of(const SampleDev& S) { return S.SC ? *S.SC : ScoreDev{}; }
 // The mode of a launch, stated once (ST first: a stream segment with forced == 0 has PR.prime == nullptr and is still SAMPLE_STREAM).  A
-// kernel's PRIMED, STREAM, SCORE (mode >= SAMPLE_PRIMED, >= SAMPLE_STREAM, == SAMPLE_SCORE) and its KScope name follow from it.  The RhoCMPS
-// kernels have no SCORE instance: their launchers return hipErrorInvalidValue.  dispatch_sample_mode: f(std::integral_constant<int, MODE>{})
+// kernel's PRIMED, STREAM, SCORE (mode >= SAMPLE_PRIMED, >= SAMPLE_STREAM, == SAMPLE_SCORE) and its KScope name follow from it.
+// dispatch_sample_mode: f(std::integral_constant<int, MODE>{})
 enum SampleMode { SAMPLE_PLAIN, SAMPLE_PRIMED, SAMPLE_STREAM, SAMPLE_SCORE };
 inline SampleMode sample_mode(const SampleDev& S) { return S.ST ? (S.SC ? SAMPLE_SCORE : SAMPLE_STREAM) : S.PR.prime ? SAMPLE_PRIMED : SAMPLE_PLAIN; }
 template <typename F>

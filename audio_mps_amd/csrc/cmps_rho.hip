@@ -430,11 +430,20 @@ __global__ void k_update_ancilla_rho(Dev P, const float* __restrict__ rho_in, co
 // running sum come from the path's record when ST.in is set and go to it behind the last step when ST.out is.  Thread t moves the
 // components t of all columns, the ones it alone writes in a step.  The other instances ignore ST and are the kernels they were
 // (profiles/rho_stream_isa_identity.log).
+// SCORE (cmps_rho_stream_score): a stream segment of forced steps that also gives every step's loss increment (model.py:152-158, 169-170).
+// Behind the barrier that follows the update, when Wb holds all of y_a = u_a + Q u_a + s R u_a (un-normalised, frame of t_k), one more pass:
+// thread t forms (R y_a)[t] from RT for every column (four at a time) and sums Re(conj(y_a[t]) (R y_a)[t]); e' = 2 x the block's sum = Re tr((Rt +
+// Rt^dagger) rho'), z = (e' x) / A, lv = -log(1 + z) as in k_fwd_rho above.  The pass reads Wb across threads: nothing writes Wb between
+// that barrier and the one at the top of the next step (the rotation reads a thread's own components and writes S).  lv is added to the
+// running loss (SC.loss[b]: read on a resumed scan, written behind the last step) and stored to SC.nll[b][k] when set.  The columns, the
+// running sum, pred and the stash are untouched.  The other instances ignore SC and are the kernels they were
+// (profiles/rho_stream_score_isa_identity.log).
 // ------------------------------------------------------------------------------------------------
-template <int NT, bool PRIMED, bool STREAM = false>
+template <int NT, bool PRIMED, bool STREAM = false, bool SCORE = false>
 __global__ __launch_bounds__(NT) void k_sample_rho(Dev P, RhoDev W, const float* __restrict__ noise, int length,
-                                                   float* __restrict__ out, int save, float2* gcols, PrimeDev PR, StreamDev ST) {
+                                                   float* __restrict__ out, int save, float2* gcols, PrimeDev PR, StreamDev ST, ScoreDev SC) {
     static_assert(PRIMED || !STREAM, "a stream segment is a primed scan");
+    static_assert(STREAM || !SCORE, "a scored segment is a stream segment");
     extern __shared__ float2 sh[];
     const int D = P.D, DP = P.DP, r = W.rank, rD = r * D;
     float2* base = gcols ? gcols + (size_t)blockIdx.x * 4 * rD : sh;
@@ -457,6 +466,10 @@ __global__ __launch_bounds__(NT) void k_sample_rho(Dev P, RhoDev W, const float*
     } else {
         if (act)
             for (int a = 0; a < r; ++a) S[a * D + t] = W.phi0[a * DP + t];
+    }
+    [[maybe_unused]] float loss = 0.f;                              // SCORE: the path's running loss (model.py:155)
+    if constexpr (SCORE) {
+        if (rin) loss = SC.loss[b];
     }
     for (int k = 0; k < nsteps; ++k) {
         __syncthreads();
@@ -500,6 +513,37 @@ __global__ __launch_bounds__(NT) void k_sample_rho(Dev P, RhoDev W, const float*
         const float n = block_sum<NT>(pn, red);
         const float sc = sqrtf(1.0f / fmaxf(n, 1e-12f));                           // :165
         __syncthreads();
+        if constexpr (SCORE) {                                      // (every step of a scored segment is forced: inc is the clip's increment)
+            float ph = 0.f;
+            if (act) {
+                constexpr int CW = 4;                               // columns per chunk: one matrix element is loaded once for CW of them
+                for (int a0 = 0; a0 < r; a0 += CW) {
+                    const int na = (r - a0) < CW ? (r - a0) : CW;
+                    const float2* ya[CW];                           // a ragged last chunk repeats its last column: no branch inside the j loop
+#pragma unroll
+                    for (int c = 0; c < CW; ++c) ya[c] = Wb + (a0 + (c < na ? c : na - 1)) * D;
+                    float2 h[CW];
+#pragma unroll
+                    for (int c = 0; c < CW; ++c) h[c] = make_float2(0.f, 0.f);
+                    for (int j = 0; j < D; ++j) {
+                        const float2 m = P.RT[j * DP + t];
+#pragma unroll
+                        for (int c = 0; c < CW; ++c) h[c] = cfma(m, ya[c][j], h[c]);      // (R y_a)_t
+                    }
+#pragma unroll
+                    for (int c = 0; c < CW; ++c)
+                        if (c < na) {
+                            const float2 y = ya[c][t];
+                            ph += y.x * h[c].x + y.y * h[c].y;
+                        }
+                }
+            }
+            const float e2 = 2.0f * block_sum<NT>(ph, red);          // Re tr((Rt + Rt^dagger) rho'), :189-196 on the columns of :186
+            const float z = (e2 * inc) / dev_A(P);                   // :166
+            const float lv = -logf(1.0f + z);
+            loss += lv;                                              // :155
+            if (t == 0 && SC.nll) SC.nll[(size_t)b * PF + k] = lv;
+        }
         if (act) {
             const float2 rho = P.rho[(size_t)(STREAM ? ST.k0 + k : k) * DP + t];
             for (int a = 0; a < r; ++a) S[a * D + t] = cmul(rho, cscale(sc, Wb[a * D + t]));
@@ -512,6 +556,9 @@ __global__ __launch_bounds__(NT) void k_sample_rho(Dev P, RhoDev W, const float*
         } else {
             if (t == 0) out[(size_t)b * length + k] = dev_A(P) * samp;                  // :116
         }
+    }
+    if constexpr (SCORE) {
+        if (t == 0) SC.loss[b] = loss;
     }
     if constexpr (STREAM) {
         if (ST.out) {                                               // (in == out: thread t read these components before the first step)
@@ -617,14 +664,11 @@ hipError_t launch_sample_rho(const Dev& P, const RhoDev& W, const SampleDev& S, 
     return dispatch_block_nt(P.D, [&](auto nt) {
         return dispatch_sample_mode(sample_mode(S), [&](auto mode) {
             constexpr int NT = decltype(nt)::value, M = decltype(mode)::value;
-            if constexpr (M == SAMPLE_SCORE) return hipErrorInvalidValue;       // no SCORE instance (yet): a Rho score lands here
-            else {
-                const hipError_t e = lds_attr(k_sample_rho<NT, M >= SAMPLE_PRIMED, M >= SAMPLE_STREAM>, shm);
-                if (e != hipSuccess) return e;
-                hipLaunchKernelGGL((k_sample_rho<NT, M >= SAMPLE_PRIMED, M >= SAMPLE_STREAM>), dim3(S.n), dim3(NT), shm, s, P, W, S.noise, S.length, S.out,
-                                   save ? 1 : 0, g, S.PR, stream_of(S));
-                return hipGetLastError();
-            }
+            const hipError_t e = lds_attr(k_sample_rho<NT, M >= SAMPLE_PRIMED, M >= SAMPLE_STREAM, M == SAMPLE_SCORE>, shm);
+            if (e != hipSuccess) return e;
+            hipLaunchKernelGGL((k_sample_rho<NT, M >= SAMPLE_PRIMED, M >= SAMPLE_STREAM, M == SAMPLE_SCORE>), dim3(S.n), dim3(NT), shm, s, P, W, S.noise,
+                               S.length, S.out, save ? 1 : 0, g, S.PR, stream_of(S), score_of(S));
+            return hipGetLastError();
         });
     });
 }

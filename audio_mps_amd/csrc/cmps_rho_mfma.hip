@@ -618,11 +618,22 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_bwd_rho_mfma(Dev P, RhoDev W,
 // to it behind the last step when ST.out is.  The record holds the float32 rows themselves (the rows from rank on are zero and stay
 // zero), so the fp16 x 2 form needs no scale here either.  The other instances ignore ST and are the kernels they were
 // (profiles/rho_stream_isa_identity.log).
+// SCORE (cmps_rho_stream_score): a stream segment of forced steps that also gives the loss increment of every step (model.py:152-158,
+// 169-170).  Behind Y, before it is normalised and rotated, the wave writes Y to a second LDS row array and forms the third GEMM of the
+// step, H Y with H = R + R^dagger, the way k_fwd_rho_mfma does (pieces of W_H split once; fp16 x 2: H scaled by sH to 2^15, Y by sY to
+// 2^13, the sum unscaled by iYH): e' = sum Y . (H Y) = Re tr((Rt + Rt^dagger) rho') on the un-normalised columns, still in the frame of
+// t_k.  e' is parked one step per lane; behind the chunk z = (e' x) / A and lv = -log(1 + z) are formed for 64 steps at once and added to
+// the running loss in step order (the forward's order).  The forward takes sY from the loudest increment of the whole clip; a segment
+// must give the bits of the uncut run, so here sY comes from the step's own increment: rows of Y have norm <= 1 + |W_Q|_F + |s_k| |W_R|_F.
+// Nothing of this feeds U, the running sum, pred or the stash: they keep the stream instance's bits.  The running loss comes from
+// SC.loss[b] on a resumed scan (else 0) and goes back to it behind the last step; lv goes to SC.nll[b][k] when set.  The other instances
+// ignore SC, have no second row array, and are the kernels they were (profiles/rho_stream_score_isa_identity.log).
 // ------------------------------------------------------------------------------------------------
-template <bool SAVE, bool F16, bool PRIMED, bool STREAM = false>
+template <bool SAVE, bool F16, bool PRIMED, bool STREAM = false, bool SCORE = false>
 __global__ __launch_bounds__(64 * WAVES, 1) void k_sample_rho_mfma(Dev P, RhoDev W, const float* __restrict__ noise, int n_paths,
-                                                                   int length, float* __restrict__ out, PrimeDev PR, StreamDev ST) {
+                                                                   int length, float* __restrict__ out, PrimeDev PR, StreamDev ST, ScoreDev SC) {
     static_assert(PRIMED || !STREAM, "a stream segment is a primed scan");
+    static_assert(STREAM || !SCORE, "a scored segment is a stream segment");
     __shared__ __attribute__((aligned(16))) float Urow[WAVES][32 * RRLD];
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int b = blockIdx.x * WAVES + w;
@@ -633,17 +644,32 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_sample_rho_mfma(Dev P, RhoDev
     // pieces of the W forms of R and Q (bf16 x 3, or fp16 x 2 of the forms scaled to 2^15: both operands are constant, and U has
     // unit trace, so every scale is fixed before the first step): lane (col, hk) holds W[16 ks + 8 hk + e][32 t + col], e = 0..7
     unsigned RH[2][4][4], RM[F16 ? 1 : 2][4][4], RL[2][4][4], QH[2][4][4], QM[F16 ? 1 : 2][4][4], QL[2][4][4];
+    // SCORE: the pieces of the W form of H = R + R^dagger (fp16 x 2: scaled by sH), and the second row array
+    [[maybe_unused]] unsigned HH[SCORE ? 2 : 1][4][4], HM[SCORE && !F16 ? 2 : 1][4][4], HL[SCORE ? 2 : 1][4][4];
+    [[maybe_unused]] float sH = 1.f, nq = 0.f, nr = 0.f;
+    [[maybe_unused]] float* Y = nullptr;
+    if constexpr (SCORE) {
+        __shared__ __attribute__((aligned(16))) float Yrow[WAVES][32 * RRLD];
+        Y = &Yrow[w][0];
+    }
     float sR = 1.f, sQ = 1.f;
     if constexpr (F16) {
         float mr = 0.f, mq = 0.f;
+        [[maybe_unused]] float mh = 0.f;
         for (int idx = lane; idx < DPW * DPW; idx += 64) {
             const float2 rr = P.R[idx], qq = P.Q[idx];
             mr = fmaxf(mr, fmaxf(fabsf(rr.x), fabsf(rr.y)));
             mq = fmaxf(mq, fmaxf(fabsf(qq.x), fabsf(qq.y)));
+            if constexpr (SCORE) {
+                const float2 rt = P.RT[idx];                         // H[i][j] = R[i][j] + conj(R[j][i])
+                mh = fmaxf(mh, fmaxf(fabsf(rr.x + rt.x), fabsf(rr.y - rt.y)));
+            }
         }
         sR = pow2_below(max64(mr), 15);
         sQ = pow2_below(max64(mq), 15);
+        if constexpr (SCORE) sH = pow2_below(max64(mh), 15);
     }
+    [[maybe_unused]] float fq = 0.f, fr = 0.f;                       // SCORE, fp16 x 2: |W_Q|_F^2, |W_R|_F^2 for the bound behind sY
     constexpr float sU = 8192.f;
     const float iUR = F16 ? pow2_recip(sU) * pow2_recip(sR) : 1.f, iUQ = F16 ? pow2_recip(sU) * pow2_recip(sQ) : 1.f;
 #pragma unroll
@@ -668,7 +694,26 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_sample_rho_mfma(Dev P, RhoDev
                     split3_pk(wq[2 * e2], wq[2 * e2 + 1], QH[t][ks][e2], QM[t][ks][e2], QL[t][ks][e2]);
                 }
             }
+            if constexpr (SCORE) {
+                float wh[8];
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    const int m = 16 * ks + 8 * hk + e, jj = m >> 1, cp = m & 1;
+                    const float2 rij = P.R[ii * DPW + jj], rji = P.RT[ii * DPW + jj];
+                    wh[e] = wform(make_float2(rij.x + rji.x, rij.y - rji.y), cp, cc);      // (R + R^dagger)[ii][jj]
+                    if constexpr (F16) { fq = fmaf(wq[e], wq[e], fq); fr = fmaf(wr[e], wr[e], fr); }
+                }
+#pragma unroll
+                for (int e2 = 0; e2 < 4; ++e2) {
+                    if constexpr (F16) split2h(wh[2 * e2] * sH, wh[2 * e2 + 1] * sH, HH[t][ks][e2], HL[t][ks][e2]);
+                    else split3_pk(wh[2 * e2], wh[2 * e2 + 1], HH[t][ks][e2], HM[t][ks][e2], HL[t][ks][e2]);
+                }
+            }
         }
+    }
+    if constexpr (SCORE && F16) {
+        nq = 1.001f * sqrtf(sum64(fq));
+        nr = 1.001f * sqrtf(sum64(fr));
     }
     const float* rin = nullptr;                                      // (STREAM) this path's record to carry on from
     if constexpr (STREAM) rin = ST.in ? ST.in + (size_t)b * ST.rec : nullptr;
@@ -696,6 +741,12 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_sample_rho_mfma(Dev P, RhoDev
     if constexpr (STREAM) {
         if (rin) samp = rin[64 * r];
     }
+    [[maybe_unused]] float loss = 0.f;                               // SCORE: the path's running loss (model.py:155)
+    [[maybe_unused]] float* lrow = nullptr;
+    if constexpr (SCORE) {
+        if (rin) loss = SC.loss[b];
+        if (SC.nll) lrow = SC.nll + (size_t)b * PF;
+    }
     for (int kbeg = 0; kbeg < nsteps; kbeg += CH) {
         const int cnt = (nsteps - kbeg) < CH ? (nsteps - kbeg) : CH;
         float nzv;                                                   // what this lane's step is handed: its noise, or (PRIMED, below PF) the clip's increment
@@ -706,6 +757,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_sample_rho_mfma(Dev P, RhoDev
             nzv = kbeg + lane < length ? nrow[kbeg + lane] : 0.f;
         }
         float outv = 0.f;
+        [[maybe_unused]] float evec = 0.f;                           // SCORE: e' of this lane's step
         for (int kk = 0; kk < cnt; ++kk) {
             const int k = kbeg + kk;
             const size_t kt = STREAM ? (size_t)ST.k0 + k : (size_t)k;       // table row
@@ -775,6 +827,51 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_sample_rho_mfma(Dev P, RhoDev
             }
             const float n = sum64(accn);
             const float sc1 = sqrtf(1.0f / fmaxf(n, 1e-12f));        // :165
+            if constexpr (SCORE) {                                   // e' = sum Y . (H Y) on the un-normalised columns (model.py:152-158, 189-196)
+                __builtin_amdgcn_sched_barrier(0);                   // (the third GEMM starts behind the update, not among it: registers)
+#pragma unroll
+                for (int q = 0; q < 16; ++q) {
+                    const int row = (q & 3) + 8 * (q >> 2) + 4 * hk;
+                    Y[row * RRLD + col] = y0[q];
+                    Y[row * RRLD + 32 + col] = y1[q];
+                }
+                float sY = 1.f, iYH = 1.f;
+                if constexpr (F16) {
+                    sY = pow2_below(1.01f * (1.0f + nq + (1.001f * fabsf(s)) * nr), 13);
+                    iYH = pow2_recip(sY) * pow2_recip(sH);
+                }
+                v16f h0 = {}, h1 = {};
+#pragma unroll
+                for (int ks = 0; ks < 4; ++ks) {
+                    const float4 f0 = *reinterpret_cast<const float4*>(Y + col * RRLD + 16 * ks + 8 * hk);
+                    const float4 f1 = *reinterpret_cast<const float4*>(Y + col * RRLD + 16 * ks + 8 * hk + 4);
+                    unsigned AH[4], AM[4], AL[4];
+                    if constexpr (F16) {
+                        split2h(f0.x * sY, f0.y * sY, AH[0], AL[0]);
+                        split2h(f0.z * sY, f0.w * sY, AH[1], AL[1]);
+                        split2h(f1.x * sY, f1.y * sY, AH[2], AL[2]);
+                        split2h(f1.z * sY, f1.w * sY, AH[3], AL[3]);
+                        mfma3(h0, AH, AL, HH[0][ks], HL[0][ks]);
+                        mfma3(h1, AH, AL, HH[1][ks], HL[1][ks]);
+                    } else {
+                        split3_pk(f0.x, f0.y, AH[0], AM[0], AL[0]);
+                        split3_pk(f0.z, f0.w, AH[1], AM[1], AL[1]);
+                        split3_pk(f1.x, f1.y, AH[2], AM[2], AL[2]);
+                        split3_pk(f1.z, f1.w, AH[3], AM[3], AL[3]);
+                        mfma6(h0, AH, AM, AL, HH[0][ks], HM[0][ks], HL[0][ks]);
+                        mfma6(h1, AH, AM, AL, HH[1][ks], HM[1][ks], HL[1][ks]);
+                    }
+                }
+                float acch = 0.f;
+#pragma unroll
+                for (int q = 0; q < 16; ++q) {
+                    acch = fmaf(y0[q], h0[q], acch);
+                    acch = fmaf(y1[q], h1[q], acch);
+                }
+                const float e2 = F16 ? sum64(acch) * iYH : sum64(acch);
+                evec = lane == kk ? e2 : evec;
+                __builtin_amdgcn_sched_barrier(0);
+            }
             if (SAVE) {
                 float2* sbase = st + (size_t)k * r * 64 + lane;
 #pragma unroll
@@ -803,6 +900,15 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_sample_rho_mfma(Dev P, RhoDev
         } else {
             if (kbeg + lane < length) orow[kbeg + lane] = outv;
         }
+        if constexpr (SCORE) {                                       // (every step of a scored segment is forced: nzv is its increment)
+            const float z = (evec * nzv) / A;                        // model.py:166 operation order
+            const float lv = -logf(1.0f + z);
+            for (int j = 0; j < cnt; ++j) loss += rdlane(lv, j);     // :155, sequential in time
+            if (lrow && lane < cnt) lrow[kbeg + lane] = lv;
+        }
+    }
+    if constexpr (SCORE) {
+        if (lane == 0) SC.loss[b] = loss;
     }
     if constexpr (STREAM) {
         if (ST.out) {                                                // (in == out: this wave read its record before the first step)
@@ -830,12 +936,9 @@ hipError_t launch_sample_rho_mfma(const Dev& P, const RhoDev& W, const SampleDev
         return dispatch_bool(f16, [&](auto hf) {
             return dispatch_sample_mode(sample_mode(S), [&](auto mode) {
                 constexpr int M = decltype(mode)::value;
-                if constexpr (M == SAMPLE_SCORE) return hipErrorInvalidValue;   // no SCORE instance (yet): a Rho score lands here
-                else {
-                    hipLaunchKernelGGL((k_sample_rho_mfma<decltype(sv)::value, decltype(hf)::value, M >= SAMPLE_PRIMED, M >= SAMPLE_STREAM>), dim3(nb),
-                                       dim3(64 * WAVES), 0, s, P, W, S.noise, S.n, S.length, S.out, S.PR, stream_of(S));
-                    return hipGetLastError();
-                }
+                hipLaunchKernelGGL((k_sample_rho_mfma<decltype(sv)::value, decltype(hf)::value, M >= SAMPLE_PRIMED, M >= SAMPLE_STREAM, M == SAMPLE_SCORE>),
+                                   dim3(nb), dim3(64 * WAVES), 0, s, P, W, S.noise, S.n, S.length, S.out, S.PR, stream_of(S), score_of(S));
+                return hipGetLastError();
             });
         });
     });

@@ -297,9 +297,28 @@ class CMPS(_ScanModel):
         raise NotImplementedError
 
     def _stream_score_entry(self, be):
-        """The backend's scored segment entry for this model (HipScan.stream_score).  PsiCMPS only: cmps_rho_stream_score does not exist."""
-        raise ValueError(f"scoring a stream is PsiCMPS-only: {type(self).__name__} has no scored sampler (cmps_psi_stream_score has no "
-                         "RhoCMPS counterpart yet)")
+        """The backend's scored segment entry for this model: HipScan.stream_score, or rho_stream_score."""
+        raise NotImplementedError
+
+    def nll_per_step(self, data=None, segment=None) -> np.ndarray:
+        """The fold's increment of every step, [B, T - 1]: -log(1 + e' x / A) of model.py:276-282, 293-294 (RhoCMPS: :152-158,
+        169-170; the reference only returns their sum).  One scored stream over the batch (cmps_psi_stream_score / cmps_rho_stream_score), cut into segments of ``segment`` steps when given -- the
+        cut changes no bit.  Row sums are ``loss_per_clip`` to float32 rounding."""
+        data = self._batch(data)
+        if hasattr(data, "detach"):
+            data = data.detach().cpu().numpy()
+        data = np.asarray(data, dtype=np.float32)
+        if data.ndim != 2 or data.shape[1] < 2:
+            raise ValueError("data must be [B, T] with T >= 2")
+        B, N = data.shape[0], data.shape[1] - 1
+        S = N if segment is None else int(segment)
+        if S < 1:
+            raise ValueError("segment must be positive")
+        st = self.open_stream(B, N)
+        parts = [st.score(data[:, :S + 1])]                           # the anchor and S steps
+        for a in range(S + 1, N + 1, S):
+            parts.append(st.score(data[:, a:a + S]))
+        return np.concatenate(parts, axis=1)
 
     def _prepare_stream(self, num_paths, max_steps, keep_states=0):
         """The backend as a stream needs it: T = max_steps + 1, one table row per step."""
@@ -307,7 +326,7 @@ class CMPS(_ScanModel):
 
     def open_stream(self, num_paths, max_steps, temp=1, seed=None, device_noise=False):
         """A resumable sampler of ``num_paths`` paths (no reference counterpart; audio_mps_amd/stream.py, cmps_psi_stream /
-        cmps_rho_stream): follow an incoming signal block by block, generate in segments, or alternate.  Prepares the backend once with
+        cmps_rho_stream): follow (and score) an incoming signal block by block, generate in segments, or alternate.  Prepares the backend once with
         T = max_steps + 1 -- the only sizing decision, 8 DP bytes of phase table per step; running past ``max_steps`` raises ValueError.
         The model's variables are read here: a stream keeps the parameters it was opened with.  ``device_noise=True``: ``generate`` draws
         its noise on the device from (``seed``, path, step) instead of a host Generator (SampleStream.generate)."""
@@ -494,26 +513,6 @@ class PsiCMPS(CMPS):
     def _stream_score_entry(self, be):
         return be.stream_score
 
-    def nll_per_step(self, data=None, segment=None) -> np.ndarray:
-        """The fold's increment of every step, [B, T - 1]: -log(1 + e' x / A) of model.py:276-282, 293-294 (the reference only returns
-        their sum).  One scored stream over the batch (cmps_psi_stream_score), cut into segments of ``segment`` steps when given -- the
-        cut changes no bit.  Row sums are ``loss_per_clip`` to float32 rounding."""
-        data = self._batch(data)
-        if hasattr(data, "detach"):
-            data = data.detach().cpu().numpy()
-        data = np.asarray(data, dtype=np.float32)
-        if data.ndim != 2 or data.shape[1] < 2:
-            raise ValueError("data must be [B, T] with T >= 2")
-        B, N = data.shape[0], data.shape[1] - 1
-        S = N if segment is None else int(segment)
-        if S < 1:
-            raise ValueError("segment must be positive")
-        st = self.open_stream(B, N)
-        parts = [st.score(data[:, :S + 1])]                           # the anchor and S steps
-        for a in range(S + 1, N + 1, S):
-            parts.append(st.score(data[:, a:a + S]))
-        return np.concatenate(parts, axis=1)
-
 
 # --------------------------------------------------------------------------------------------------
 class RhoCMPS(CMPS):
@@ -623,6 +622,12 @@ class RhoCMPS(CMPS):
 
     def _stream_entries(self, be):
         return be.rho_stream_state, be.rho_stream
+
+    def _stream_score_entry(self, be):
+        entry = getattr(be, "rho_stream_score", None)
+        if entry is None:                                             # (as device_noise on a backend that cannot draw: said before anything runs)
+            raise ValueError(f"this backend scores PsiCMPS-only streams: {type(be).__name__} has no rho_stream_score (cmps_rho_stream_score)")
+        return entry
 
     def _prepare_stream(self, num_paths, max_steps, keep_states=0):
         if not keep_states:

@@ -13,9 +13,9 @@ waveform is the clip followed by its continuation.  Writes ``sample_<i>.wav`` (1
 prime, if given, is followed, then the waveform is generated; the files and the return value are the same.
 ``--device_noise`` (plain, --prime and --segment runs) draws the noise on the device instead of on the host (cmps_noise_fill): counter-based
 normals of (--seed, path, step), so --segment then changes no bit of the waveform however it cuts the run.
-``--score FILE`` (PsiCMPS; a clip as --prime reads it) samples nothing: the clip is followed and scored through a stream
-(SampleStream.score; cmps_psi_stream_score), in segments of --segment steps when given.  Writes ``nll.npy`` (float32 [clips, T' - 1]: the
-negative log-likelihood of every sample, model.py:293-294) and ``pred.npy`` (the model's expected increments) into --out_dir and prints
+``--score FILE`` (a clip as --prime reads it; either model) samples nothing: the clip is followed and scored through a stream
+(SampleStream.score; cmps_psi_stream_score / cmps_rho_stream_score), in segments of --segment steps when given.  Writes ``nll.npy`` (float32
+[clips, T' - 1]: the negative log-likelihood of every sample, model.py:293-294 / :166, 169-170) and ``pred.npy`` (the model's expected increments) into --out_dir and prints
 the total and the mean per sample; returns the nll array.
 Run:  python -m audio_mps_amd.sample --modeldir=LOGDIR --sample_duration=16000 --prime=clip.wav
 """
@@ -89,7 +89,7 @@ def build_parser():
     p.add_argument("--temp", type=float, default=1.0, help="noise temperature (model.py:246)")
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--prime", default=None, metavar="FILE", help=".wav (16-bit mono) or .npy clip to continue")
-    p.add_argument("--score", default=None, metavar="FILE", help=".wav (16-bit mono) or .npy clip to follow and score instead of sampling (PsiCMPS)")
+    p.add_argument("--score", default=None, metavar="FILE", help=".wav (16-bit mono) or .npy clip to follow and score instead of sampling (PsiCMPS or RhoCMPS)")
     p.add_argument("--device_noise", action="store_true", help="draw the noise on the device, from (--seed, path, step) (cmps_noise_fill), "
                    "instead of a host Generator")
     p.add_argument("--segment", type=int, default=None, metavar="S", help="run through a resumable stream in segments of S steps")
@@ -170,8 +170,7 @@ def main(argv=None, backend=None):
             raise ValueError("--score follows and scores its clip and samples nothing: there is no noise for --device_noise to draw")
         if args.prime is not None:
             raise ValueError("--score follows and scores its clip and samples nothing: it does not go with --prime")
-        if rho:
-            raise ValueError("--score needs a PsiCMPS checkpoint: scoring a stream is PsiCMPS-only (RhoCMPS has no scored sampler yet)")
+        model._stream_score_entry(model._get_backend())           # (a backend that cannot score this model says so before anything is written)
         return _scored(model, args)
     if args.segment is not None:
         waves = _segmented(model, args, n, length)

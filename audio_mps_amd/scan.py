@@ -125,7 +125,7 @@ class HipScan:
         return mode if mode in (_capi.CMPS_RANK1_EXACT_F32, _capi.CMPS_RANK1_BF16X2, _capi.CMPS_RANK1_F16X2) else _capi.CMPS_RANK1_BF16X3
 
     def kernel_events(self, on: bool):
-        """cmps_set_option(CMPS_OPT_KERNEL_EVENTS): bracket every kernel of forward() / backward() and of sample() / sample_primed() / stream() / stream_score() / rho_sample_primed() / rho_stream() / draw_noise() with HIP
+        """cmps_set_option(CMPS_OPT_KERNEL_EVENTS): bracket every kernel of forward() / backward() and of sample() / sample_primed() / stream() / stream_score() / rho_sample_primed() / rho_stream() / rho_stream_score() / draw_noise() with HIP
         events (a measurement aid, used by bench.py outside its timed region)."""
         _capi.check(self._h, self._lib.cmps_set_option(self._h, _capi.CMPS_OPT_KERNEL_EVENTS, 1 if on else 0))
 
@@ -499,18 +499,15 @@ class HipScan:
         return self._stream_call(self._lib.cmps_psi_stream, self._lib.cmps_psi_stream_state_bytes, state_in, state_out, k0, audio, noise,
                                  want_pred, n, length)
 
-    def stream_score(self, state_in: Optional[torch.Tensor], state_out: Optional[torch.Tensor], k0: int, audio, want_nll: bool = True,
-                     want_pred: bool = False, n: Optional[int] = None, loss=None):
-        """cmps_psi_stream_score, one scored segment of a resumable scan on table rows k0 ..: `stream`'s forced steps on ``audio``
-        [n_audio, forced + 1] (forced >= 1) that also give the loss increment of every step.  ``loss`` [n] is the running loss to
-        continue (not read at k0 = 0).  ``loss=None`` on a resumed segment (k0 > 0) starts the total again from zero: the caller keeps
-        the total, the state record does not.  Returns (nll [n, forced] with want_nll else None, the running loss [n] behind the
-        segment, pred [n, forced] with want_pred else None).  The states are `stream`'s: a scan may alternate between the two."""
+    def _stream_score_call(self, fn, bytes_fn, state_in, state_out, k0, audio, want_nll, want_pred, n, loss, *flags):
+        """One scored segment: the signal block [n_audio, forced + 1] and the running loss up, (nll [n, forced] or None, loss [n], pred
+        [n, forced] or None) down.  `fn` / `bytes_fn` are cmps_{psi,rho}_stream_score / _stream_state_bytes, `flags` what `fn` takes
+        behind pred_dev."""
         audio = np.array(audio, dtype=np.float32, order="C")           # (a copy: torch wants a writable array)
         if audio.ndim != 2 or audio.shape[1] < 2:
             raise ValueError("audio must be [n_audio, forced + 1] with forced >= 1")
         n_audio, forced = audio.shape[0], audio.shape[1] - 1
-        n = self._stream_paths(self._lib.cmps_psi_stream_state_bytes, state_in, state_out, n, n_audio)
+        n = self._stream_paths(bytes_fn, state_in, state_out, n, n_audio)
         if loss is None:
             d_loss = torch.zeros(n, dtype=torch.float32, device=self.device)
         else:
@@ -522,9 +519,19 @@ class HipScan:
         d_nll = torch.empty((n, forced), dtype=torch.float32, device=self.device) if want_nll else None
         d_pred = torch.empty((n, forced), dtype=torch.float32, device=self.device) if want_pred else None
         ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None   # noqa: E731
-        _capi.check(self._h, self._lib.cmps_psi_stream_score(self._h, ptr(state_in), ptr(state_out), int(k0), ptr(d_audio), n_audio, forced, n,
-                                                             ptr(d_nll), ptr(d_loss), ptr(d_pred), self._stream()))
+        _capi.check(self._h, fn(self._h, ptr(state_in), ptr(state_out), int(k0), ptr(d_audio), n_audio, forced, n, ptr(d_nll), ptr(d_loss),
+                                ptr(d_pred), *flags, self._stream()))
         return (d_nll.cpu().numpy() if want_nll else None), d_loss.cpu().numpy(), (d_pred.cpu().numpy() if want_pred else None)
+
+    def stream_score(self, state_in: Optional[torch.Tensor], state_out: Optional[torch.Tensor], k0: int, audio, want_nll: bool = True,
+                     want_pred: bool = False, n: Optional[int] = None, loss=None):
+        """cmps_psi_stream_score, one scored segment of a resumable scan on table rows k0 ..: `stream`'s forced steps on ``audio``
+        [n_audio, forced + 1] (forced >= 1) that also give the loss increment of every step.  ``loss`` [n] is the running loss to
+        continue (not read at k0 = 0).  ``loss=None`` on a resumed segment (k0 > 0) starts the total again from zero: the caller keeps
+        the total, the state record does not.  Returns (nll [n, forced] with want_nll else None, the running loss [n] behind the
+        segment, pred [n, forced] with want_pred else None).  The states are `stream`'s: a scan may alternate between the two."""
+        return self._stream_score_call(self._lib.cmps_psi_stream_score, self._lib.cmps_psi_stream_state_bytes, state_in, state_out, k0, audio,
+                                       want_nll, want_pred, n, loss)
 
     # ------------------------------------------------------------------
     # legacy AudioMPS arithmetic (SURVEY 8f rank 2)
@@ -611,6 +618,14 @@ class HipScan:
         steps; the rho workspace's T is a stash capacity only and may be smaller than set_params's."""
         return self._stream_call(self._lib.cmps_rho_stream, self._lib.cmps_rho_stream_state_bytes, state_in, state_out, k0, audio, noise,
                                  want_pred, n, length, 1 if save_states else 0)
+
+    def rho_stream_score(self, state_in: Optional[torch.Tensor], state_out: Optional[torch.Tensor], k0: int, audio, want_nll: bool = True,
+                         want_pred: bool = False, n: Optional[int] = None, loss=None, save_states: bool = False):
+        """cmps_rho_stream_score: `stream_score` for RhoCMPS, from the columns of rho_set_state (states of `rho_stream_state`, shared with
+        `rho_stream`: a scan may alternate between the two).  Returns (nll, loss, pred) as `stream_score` does.  save_states keeps the
+        columns of this segment's steps for rho_states(n, forced), as in `rho_stream`."""
+        return self._stream_score_call(self._lib.cmps_rho_stream_score, self._lib.cmps_rho_stream_state_bytes, state_in, state_out, k0, audio,
+                                       want_nll, want_pred, n, loss, 1 if save_states else 0)
 
     def rho_states(self, B: int, steps: int, want_rho: bool = True, want_purity: bool = False):
         """Lab-frame rho [B, steps, D, D] and/or purity [B, steps] of the last saved scan."""

@@ -1,4 +1,5 @@
-"""A resumable sampler for PsiCMPS and RhoCMPS: follow an incoming signal and generate audio in segments (cmps_psi_stream, cmps_rho_stream).
+"""A resumable sampler for PsiCMPS and RhoCMPS: follow and score an incoming signal and generate audio in segments (cmps_psi_stream,
+cmps_psi_stream_score, cmps_rho_stream, cmps_rho_stream_score).
 
 The reference samples a whole waveform in one tf.scan (model.py:242-251) and has nothing that carries on.  A ``SampleStream`` keeps what
 the sampler kernel carries between two steps on the device, so a scan can be continued, can alternate between teacher-forced blocks
@@ -8,12 +9,12 @@ with ``device_noise=True`` draws the noise of a generated step on the device, as
 
     st = model.open_stream(num_paths=4, max_steps=3 * 16000, seed=0)
     pred = st.follow(block)             # [4, steps]: the model's expected increment before every followed sample
-    nll = st.score(block2)              # [4, steps]: follow, and how likely every sample was (PsiCMPS); st.total_nll sums them
+    nll = st.score(block2)              # [4, steps]: follow, and how likely every sample was; st.total_nll sums them
     wave = st.generate(16000)           # [4, 16000] in the clip's own units, continuing the followed signal
     wave2 = st.generate(16000)          # ... and on from there
 
 A RhoCMPS stream opened with ``keep_states=S`` also returns rho and the purity after every step of the last call (``st.states()``,
-``st.purity()``), from a stash that holds S steps however long the run is.
+``st.purity()``), from a stash that holds S steps however long the run is -- behind a ``score`` call as behind a ``follow``.
 """
 from __future__ import annotations
 
@@ -72,11 +73,11 @@ class SampleStream:
         return self._be.rho_states(self.num_paths, self._saved, want_rho=want_rho, want_purity=not want_rho)
 
     def states(self) -> np.ndarray:
-        """Lab-frame rho after every step of the last follow / generate call, [num_paths, steps, D, D] (keep_states streams)."""
+        """Lab-frame rho after every step of the last follow / score / generate call, [num_paths, steps, D, D] (keep_states streams)."""
         return self._kept(True)
 
     def purity(self) -> np.ndarray:
-        """tr rho^2 after every step of the last follow / generate call, [num_paths, steps] (keep_states streams)."""
+        """tr rho^2 after every step of the last follow / score / generate call, [num_paths, steps] (keep_states streams)."""
         return self._kept(False)
 
     def _block(self, block) -> np.ndarray:
@@ -102,8 +103,9 @@ class SampleStream:
         return block, audio
 
     def score(self, block, anchor: bool = False) -> np.ndarray:
-        """``follow`` that also says how likely the block was (PsiCMPS; cmps_psi_stream_score): same arguments, anchoring rule and
-        bookkeeping, returns the negative log-likelihood of every step, [num_paths, steps] = -log(1 + e' x / A) of model.py:293-294,
+        """``follow`` that also says how likely the block was (cmps_psi_stream_score / cmps_rho_stream_score): same arguments, anchoring
+        rule and bookkeeping, returns the negative log-likelihood of every step, [num_paths, steps] = -log(1 + e' x / A) of
+        model.py:293-294 (RhoCMPS: :166, 169-170),
         and adds them to ``total_nll`` [num_paths] in step order (the fold carry of model.py:279; over a whole clip from a fresh
         stream: ``loss_per_clip``).  The predictions ``follow`` would have returned are in ``last_pred``.  Scoring changes nothing the
         stream carries: ``follow``, ``score`` and ``generate`` alternate freely, and unscored steps leave ``total_nll`` as it is."""

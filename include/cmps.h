@@ -84,7 +84,7 @@ enum {
     CMPS_OPT_F16_SCALE_SHIFT = 4 /* DIAGNOSTIC, default 0: added to the exponent of every data-dependent fp16 scale of the wave reverse
                         * scan's F16X2 arithmetic (range -40 .. 40).  A positive value pushes the pieces out of fp16 range on purpose:
                         * how tests/test_gpu_parity.py provokes CMPS_ERR_F16_RANGE.  No reference counterpart. */,
-    CMPS_OPT_KERNEL_EVENTS = 2 /* 1: every kernel cmps_psi_loss_fwd / _bwd, cmps_rho_loss_fwd / _bwd, cmps_psi_sample, cmps_psi_sample_primed, cmps_psi_stream, cmps_psi_stream_score, cmps_rho_sample_primed, cmps_rho_stream and cmps_noise_fill (as k_noise_philox) launch is bracketed by two HIP events on the caller's stream
+    CMPS_OPT_KERNEL_EVENTS = 2 /* 1: every kernel cmps_psi_loss_fwd / _bwd, cmps_rho_loss_fwd / _bwd, cmps_psi_sample, cmps_psi_sample_primed, cmps_psi_stream, cmps_psi_stream_score, cmps_rho_sample_primed, cmps_rho_stream, cmps_rho_stream_score and cmps_noise_fill (as k_noise_philox) launch is bracketed by two HIP events on the caller's stream
                         * (read and reset with cmps_kernel_times); 0 (default): nothing is recorded.  A measurement aid -- the reference
                         * has no counterpart (no tracing / profiling hooks); bench.py uses it OUTSIDE its timed region to price
                         * each kernel of a multi-kernel family against the pipe it runs on */
@@ -479,6 +479,34 @@ int cmps_rho_stream(cmps_handle_t h, const void* state_in_dev, void* state_out_d
                     const float* audio_dev, int n_audio, int forced,
                     const float* noise_dev, int length,
                     int n, float* out_dev, float* pred_dev, int save_states, void* stream);
+
+/*
+ * One scored segment of a resumable RhoCMPS scan: cmps_psi_stream_score for the density-matrix model.  `forced` >= 1 forced steps of
+ * cmps_rho_stream (length = 0, same conventions: audio_dev [n_audio, forced + 1] with the one-sample overlap, n_audio in {1, n},
+ * state_in_dev == NULL <=> k0 == 0, state_out_dev NULL or equal to state_in_dev, table rows k0 .. k0 + forced - 1, save_states as there)
+ * that also give the loss increment of every step (_rho_and_loss_update, model.py:152-158; _inc_loss_rho, :169-170), formed behind the
+ * update and before the normalisation:
+ *   step j:  y_a = u_a + Q u_a + s R u_a on the columns of the normalised rho, s = x_j / A, x_j = audio[b'][j + 1] - audio[b'][j];
+ *            e'  = Re tr((Rt + Rt^dagger) rho') = 2 sum_a Re(y_a^dagger R y_a) in float32 on the UN-normalised columns, in the frame of t_j;
+ *            z   = (e' * x_j) / A;   nll[b][j] = -logf(1.0f + z)   -- the operation order of cmps_rho_loss_fwd (model.py:166);
+ *            loss[b] += nll[b][j], sequentially in step order in float32 (model.py:155).
+ * The reference gives only the batch mean of the whole clip (_build_loss_rho, model.py:132-142); this entry gives every sample's share.
+ * Nothing of it feeds the chain: pred, the state record and the saved columns carry the bits cmps_rho_stream gives on the same steps,
+ * the record is the one cmps_rho_stream_state_bytes describes, and a stream may alternate between this entry and cmps_rho_stream freely.
+ * nll_dev [n * forced] row-major [path][step], or NULL.  loss_dev [n], required: the running loss lives with the caller, not in the
+ * record.  At the start of a stream (state_in_dev == NULL) it is not read and is written from 0; otherwise it is loaded once, continued,
+ * and stored once behind the last step.  pred_dev [n * forced] or NULL, as in cmps_rho_stream.  Cut anywhere, nll, loss, pred, the final
+ * record and the saved columns keep their bits; over a whole clip from k0 = 0 loss is the clip's cmps_rho_loss_fwd to rounding.  Where
+ * 1 + z <= 0 the NaN / Inf of the logarithm propagates into nll and loss, as in the loss entries.
+ * CMPS_ERR_BAD_ARG: cmps_rho_stream's (with length = 0), and forced < 1 or loss_dev == NULL; k0 + forced > T - 1 with a message naming
+ * the needed T >= k0 + forced + 1.  CMPS_ERR_STATE before cmps_set_params* or cmps_rho_set_state and in legacy mode.  CMPS_ERR_WORKSPACE
+ * as for cmps_rho_stream.
+ * Asynchronous on `stream`; never synchronises, allocates nothing.  The kernel is chosen as cmps_rho_sample chooses it; with
+ * CMPS_OPT_KERNEL_EVENTS the launch is recorded as k_sample_rho_mfma_score or k_sample_rho_score.
+ */
+int cmps_rho_stream_score(cmps_handle_t h, const void* state_in_dev, void* state_out_dev, int k0,
+                          const float* audio_dev, int n_audio, int forced, int n,
+                          float* nll_dev, float* loss_dev, float* pred_dev, int save_states, void* stream);
 
 /*
  * Replaces: the optimiser half of a RhoCMPS training step -- tf.train.AdamOptimizer(learning_rate).minimize(total_loss)
