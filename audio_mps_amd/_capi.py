@@ -56,7 +56,7 @@ SYMBOLS = (
     "cmps_legacy_set_params", "cmps_legacy_loss_fwd", "cmps_legacy_loss_bwd",
     "cmps_rho_workspace_bytes", "cmps_rho_set_state", "cmps_rho_loss_fwd", "cmps_rho_loss_bwd",
     "cmps_rho_update_ancilla", "cmps_rho_sample", "cmps_rho_sample_primed", "cmps_rho_stream_state_bytes", "cmps_rho_stream", "cmps_rho_stream_score", "cmps_rho_states",
-    "cmps_rho_apply_step_scratch_bytes", "cmps_rho_apply_step", "cmps_noise_fill", "cmps_crc32c",
+    "cmps_rho_apply_step_scratch_bytes", "cmps_rho_apply_step", "cmps_noise_fill", "cmps_batch_gather", "cmps_damped_sine_fill", "cmps_crc32c",
 )
 
 
@@ -154,6 +154,10 @@ def _declare(lib):
     lib.cmps_rho_apply_step.restype = c_int
     lib.cmps_noise_fill.argtypes = [vp, ctypes.c_ulonglong, ctypes.c_ulonglong, ctypes.c_uint, c_int, c_int, c_float, vp, vp]
     lib.cmps_noise_fill.restype = c_int
+    lib.cmps_batch_gather.argtypes = [vp, vp, ctypes.c_longlong, ctypes.c_longlong, vp, vp, c_int, c_int, vp, vp]
+    lib.cmps_batch_gather.restype = c_int
+    lib.cmps_damped_sine_fill.argtypes = [vp, ctypes.c_ulonglong, ctypes.c_ulonglong, c_int, c_int, c_double, vp, vp]
+    lib.cmps_damped_sine_fill.restype = c_int
     lib.cmps_crc32c.argtypes = [ctypes.c_char_p, c_size_t, ctypes.c_uint]
     lib.cmps_crc32c.restype = ctypes.c_uint
 

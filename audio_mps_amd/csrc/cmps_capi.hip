@@ -661,6 +661,43 @@ int cmps_noise_fill(cmps_handle_t h, unsigned long long seed, unsigned long long
     return CMPS_OK;
 }
 
+// The input of a training step produced on the device: like cmps_noise_fill, both need nothing of the handle but its error string and
+// its kernel-event record
+int cmps_batch_gather(cmps_handle_t h, const float* data_dev, long long n_clips, long long clip_len, const int* index_dev,
+                      const int* offset_dev, int B, int T, float* audio_dev, void* stream) {
+    if (!h) return CMPS_ERR_BAD_ARG;
+    if (!data_dev) return fail(h, CMPS_ERR_BAD_ARG, "cmps_batch_gather: data_dev is a null pointer");
+    if (!index_dev) return fail(h, CMPS_ERR_BAD_ARG, "cmps_batch_gather: index_dev is a null pointer");
+    if (!audio_dev) return fail(h, CMPS_ERR_BAD_ARG, "cmps_batch_gather: audio_dev is a null pointer");
+    if (B < 1 || T < 1) return fail(h, CMPS_ERR_BAD_ARG, "cmps_batch_gather: need B >= 1 and T >= 1");
+    if (n_clips < 1 || n_clips > 2147483647ll)
+        return fail(h, CMPS_ERR_BAD_ARG, "cmps_batch_gather: need 1 <= n_clips <= 2^31 - 1 (an index is a 32-bit int)");
+    if (clip_len < (long long)T) return fail(h, CMPS_ERR_BAD_ARG, "cmps_batch_gather: clip_len must be at least T");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    KBind kb(h);
+    KScope ks("k_batch_gather", s);
+    const hipError_t e = launch_batch_gather(data_dev, n_clips, clip_len, index_dev, offset_dev, B, T, audio_dev, s);
+    if (e != hipSuccess) return fail_hip(h, e, "cmps_batch_gather");
+    return CMPS_OK;
+}
+
+int cmps_damped_sine_fill(cmps_handle_t h, unsigned long long seed, unsigned long long first_clip, int B, int T, double delta_t,
+                          float* audio_dev, void* stream) {
+    if (!h) return CMPS_ERR_BAD_ARG;
+    if (!audio_dev) return fail(h, CMPS_ERR_BAD_ARG, "cmps_damped_sine_fill: audio_dev is a null pointer");
+    if (B < 1 || T < 1 || T > (1 << 24))
+        return fail(h, CMPS_ERR_BAD_ARG, "cmps_damped_sine_fill: need B >= 1 and 1 <= T <= 2^24 (beyond that a sample index is not exact in float32)");
+    if (!std::isfinite(delta_t) || !(delta_t > 0.0)) return fail(h, CMPS_ERR_BAD_ARG, "cmps_damped_sine_fill: delta_t must be finite and positive");
+    if (first_clip + (unsigned long long)B < first_clip)
+        return fail(h, CMPS_ERR_BAD_ARG, "cmps_damped_sine_fill: first_clip + B overflows 64 bits");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    KBind kb(h);
+    KScope ks("k_damped_sine", s);
+    const hipError_t e = launch_damped_sine(seed, first_clip, B, T, delta_t, audio_dev, s);
+    if (e != hipSuccess) return fail_hip(h, e, "cmps_damped_sine_fill");
+    return CMPS_OK;
+}
+
 // ---------------------------------------------------------------------------------------------------
 // legacy AudioMPS arithmetic
 // ---------------------------------------------------------------------------------------------------

@@ -439,6 +439,11 @@ hipError_t launch_sample_block(const Dev& P, const SampleDev& S, hipStream_t s);
 // cmps_noise.hip: noise[b * length + j] = stddev * z(seed, first_path + b, first_step + j), the counter-based normals of include/cmps.h
 hipError_t launch_noise_philox(unsigned long long seed, unsigned long long first_step, unsigned first_path, int n, int length, float stddev,
                                float* noise, hipStream_t s);
+// cmps_data.hip: audio[b * T + j] = data[index[b] * clip_len + offset[b] + j] (a row out of range: quiet NaNs), and clips first_clip ..
+// first_clip + B - 1 of the synthetic damped-sine sequence of include/cmps.h
+hipError_t launch_batch_gather(const float* data, long long n_clips, long long clip_len, const int* index, const int* offset, int B, int T,
+                               float* audio, hipStream_t s);
+hipError_t launch_damped_sine(unsigned long long seed, unsigned long long first_clip, int B, int T, double delta_t, float* audio, hipStream_t s);
 // floats of one path's stream record (StreamDev::rec), a multiple of 4: wave u, |y|^2 partial per lane, running sum | wide ut [2 DP], |y|^2
 // partial per wave [DP / 16], running sum | block u [2 D], running sum
 constexpr int STREAM_REC_WAVE = 132;

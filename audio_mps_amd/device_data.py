@@ -1,0 +1,175 @@
+"""The input of a training step produced on the device (``--device_data``): the batch no longer comes from the host every step.
+
+  ResidentDataset    a TFRecord dataset uploaded ONCE, [N, L] float32 in device memory; every batch is then a row gather
+                     (HipScan.gather_batch, cmps_batch_gather) driven by an index plan.  The plan is the reference's pipeline
+                     (data.py:37-40 batch -> shuffle(24) -> repeat; training_estimators.py:92 shuffle(24) -> repeat -> batch) run on
+                     clip INDICES: tfrecord._shuffle draws from its Generator by the buffer's length alone, so fed indices and the
+                     same seed it emits the positions of exactly the clips tfrecord.audio_batches emits -- the k-th batch holds the
+                     same bits.  A plan is uploaded an epoch at a time as one int32 tensor and sliced per step.
+  DampedSineSource   the reference's synthetic batch (data.py:8-22) generated where it is used (HipScan.damped_sine,
+                     cmps_damped_sine_fill): clip c of the run is a pure function of (seed, c, T, delta_t).
+
+Both need a backend that has the two methods; one without them (the stand-ins of the host tests) is a ValueError, as with draw_noise.
+"""
+from __future__ import annotations
+
+from typing import Optional, Tuple
+
+import numpy as np
+import torch
+
+from . import tfrecord
+
+UPLOAD_CLIPS_BYTES = 64 << 20          # from_tfrecord: host clips are uploaded in chunks of about this many bytes
+
+
+def _need(backend, method: str, what: str):
+    if not hasattr(backend, method):
+        raise ValueError(f"--device_data ({what}) needs a backend that produces the batch on the device ({method}): "
+                         f"{type(backend).__name__} has none")
+
+
+def _device(backend):
+    dev = getattr(backend, "device", None)
+    return dev if dev is not None else torch.device("cpu")
+
+
+class ResidentDataset:
+    """``clips`` [N, L] float32 (host array or tensor) held on the backend's device."""
+
+    def __init__(self, clips, backend):
+        _need(backend, "gather_batch", "ResidentDataset")
+        self.backend = backend
+        t = clips if isinstance(clips, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(clips, dtype=np.float32))
+        if t.dim() != 2 or t.shape[0] < 1 or t.shape[1] < 1:
+            raise ValueError("ResidentDataset needs clips [N, L] with N >= 1 and L >= 1")
+        self.clips = t.to(device=_device(backend), dtype=torch.float32).contiguous()
+
+    @property
+    def n_clips(self) -> int:
+        return int(self.clips.shape[0])
+
+    @property
+    def clip_len(self) -> int:
+        return int(self.clips.shape[1])
+
+    @classmethod
+    def from_tfrecord(cls, path: str, sample_duration: int, backend, verify: bool = False) -> "ResidentDataset":
+        """Reads the file once (tfrecord._audio_records: every record's "audio" must hold ``sample_duration`` values) and uploads it in
+        chunks; the chunks are joined on the device, so twice the dataset is allocated for a moment at the end."""
+        _need(backend, "gather_batch", "ResidentDataset")
+        dev = _device(backend)
+        per_chunk = max(1, UPLOAD_CLIPS_BYTES // (4 * int(sample_duration)))
+        chunks, cur = [], []
+
+        def flush():
+            if cur:
+                chunks.append(torch.from_numpy(np.stack(cur)).to(dev))
+                cur.clear()
+        for a in tfrecord._audio_records(path, int(sample_duration), verify):
+            cur.append(a)
+            if len(cur) == per_chunk:
+                flush()
+        flush()
+        if not chunks:
+            raise ValueError(f"{path}: no records")
+        return cls(chunks[0] if len(chunks) == 1 else torch.cat(chunks), backend)
+
+    def batches(self, minibatch_size: int, seed: int = 0, order: str = "data", shuffle_buffer: int = 24, crop: Optional[int] = None,
+                crop_seed: int = 0) -> "BatchStream":
+        """A callable returning the next batch as a device tensor, forever (see BatchStream).
+        order="data":       batch -> shuffle(shuffle_buffer) -> repeat   (over BATCHES; the short last batch of an epoch is kept)
+        order="estimator":  shuffle(shuffle_buffer) -> repeat -> batch
+        ``crop=T < L``: every clip of every batch is cut to T samples from a random start in [0, L - T], drawn from a Generator of its own
+        (``crop_seed``), so the order is the one without crops.  The reference has no crops."""
+        return BatchStream(self, minibatch_size, seed, order, shuffle_buffer, crop, crop_seed)
+
+
+class BatchStream:
+    """``stream()`` -> the next batch [B, T] on the device; ``stream(shard=(start, count))`` -> rows start .. start + count - 1 of that
+    batch (cut to its size) and nothing else gathered; ``stream.next_size`` is the size of the batch the next call returns (a rank needs
+    it to pick its shard of a short batch)."""
+
+    takes_shard = True             # (training_estimators.Estimator.train: hand this callable the rank's shard instead of slicing its result)
+
+    def __init__(self, dataset: ResidentDataset, minibatch_size: int, seed: int, order: str, shuffle_buffer: int, crop: Optional[int],
+                 crop_seed: int):
+        if order not in ("data", "estimator"):
+            raise ValueError(f"order must be 'data' or 'estimator', not {order!r}")
+        if int(minibatch_size) < 1 or int(shuffle_buffer) < 1:
+            raise ValueError("batches needs minibatch_size >= 1 and shuffle_buffer >= 1")
+        self.ds, self.mb, self.order, self.buffer = dataset, int(minibatch_size), order, int(shuffle_buffer)
+        L = dataset.clip_len
+        if crop is not None and not 1 <= int(crop) <= L:
+            raise ValueError(f"crop must lie in [1, {L}] (the clips' length), not {crop}")
+        self.T = L if crop is None else int(crop)
+        self._crop = crop is not None and self.T < L
+        self._rng = np.random.default_rng(seed)
+        self._crop_rng = np.random.default_rng(crop_seed)
+        self._plan = None              # int32 device tensor [2 if crops else 1, n]: the indices (and offsets) of the clips still to come
+        self._pos = 0                  # clips of _plan already handed out
+        self._sizes = []               # order="data": sizes of the planned batches still to come
+
+    # -- planning (host; one upload per epoch) ----------------------------------------------------
+    def _epoch(self):
+        """Plan one more epoch and append it to what is left of the current plan."""
+        N = self.ds.n_clips
+        if self.order == "data":
+            rows = [list(range(i, min(i + self.mb, N))) for i in range(0, N, self.mb)]
+            rows = list(tfrecord._shuffle(iter(rows), self.buffer, self._rng))
+            self._sizes += [len(r) for r in rows]
+            idx = np.array([i for r in rows for i in r], dtype=np.int32)
+        else:
+            idx = np.array(list(tfrecord._shuffle(iter(range(N)), self.buffer, self._rng)), dtype=np.int32)
+        plan = idx[None, :]
+        if self._crop:
+            off = self._crop_rng.integers(0, self.ds.clip_len - self.T + 1, size=idx.size).astype(np.int32)
+            plan = np.stack([idx, off])
+        new = torch.from_numpy(np.ascontiguousarray(plan)).to(self.ds.clips.device)
+        left = None if self._plan is None else self._plan[:, self._pos:]
+        self._plan = new if left is None or left.shape[1] == 0 else torch.cat([left, new], dim=1)     # (joined on the device)
+        self._pos = 0
+
+    def _planned(self) -> int:
+        return 0 if self._plan is None else int(self._plan.shape[1]) - self._pos
+
+    @property
+    def next_size(self) -> int:
+        if self.order == "estimator":
+            return self.mb
+        if not self._sizes:
+            self._epoch()
+        return self._sizes[0]
+
+    def __call__(self, shard: Optional[Tuple[int, int]] = None) -> torch.Tensor:
+        n = self.next_size
+        while self._planned() < n:
+            self._epoch()
+        if self.order == "data":
+            self._sizes.pop(0)
+        lo, hi = (0, n) if shard is None else (min(max(int(shard[0]), 0), n), min(max(int(shard[0]), 0) + max(int(shard[1]), 0), n))
+        at = self._pos
+        self._pos += n
+        if hi <= lo:
+            return torch.empty((0, self.T), dtype=torch.float32, device=self.ds.clips.device)
+        index = self._plan[0, at + lo:at + hi]
+        offset = self._plan[1, at + lo:at + hi] if self._crop else None
+        return self.ds.backend.gather_batch(self.ds.clips, index, offset, T=self.T)
+
+
+class DampedSineSource:
+    """The synthetic damped-sine batch of every step, generated on the device: step k of the run (k = the trainer's global_step, so a
+    restored run continues the sequence) holds clips k * minibatch_size .. (k + 1) * minibatch_size - 1 of the seed's sequence."""
+
+    def __init__(self, backend, minibatch_size: int, T: int, delta_t: float, seed: int = 0):
+        _need(backend, "damped_sine", "DampedSineSource")
+        if int(minibatch_size) < 1 or int(T) < 1:
+            raise ValueError("DampedSineSource needs minibatch_size >= 1 and T >= 1")
+        self.backend, self.mb, self.T, self.delta_t, self.seed = backend, int(minibatch_size), int(T), float(delta_t), int(seed)
+
+    def next(self, step: int, shard: Optional[Tuple[int, int]] = None) -> torch.Tensor:
+        """The batch of ``step``, or with ``shard=(start, count)`` rows start .. start + count - 1 of it, without generating the rest."""
+        start, count = (0, self.mb) if shard is None else (int(shard[0]), int(shard[1]))
+        if count < 1:
+            return torch.empty((0, self.T), dtype=torch.float32, device=_device(self.backend))
+        return self.backend.damped_sine(self.seed, int(step) * self.mb + start, count, self.T, self.delta_t)

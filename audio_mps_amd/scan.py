@@ -125,7 +125,7 @@ class HipScan:
         return mode if mode in (_capi.CMPS_RANK1_EXACT_F32, _capi.CMPS_RANK1_BF16X2, _capi.CMPS_RANK1_F16X2) else _capi.CMPS_RANK1_BF16X3
 
     def kernel_events(self, on: bool):
-        """cmps_set_option(CMPS_OPT_KERNEL_EVENTS): bracket every kernel of forward() / backward() and of sample() / sample_primed() / stream() / stream_score() / rho_sample_primed() / rho_stream() / rho_stream_score() / draw_noise() with HIP
+        """cmps_set_option(CMPS_OPT_KERNEL_EVENTS): bracket every kernel of forward() / backward() and of sample() / sample_primed() / stream() / stream_score() / rho_sample_primed() / rho_stream() / rho_stream_score() / draw_noise() / gather_batch() / damped_sine() with HIP
         events (a measurement aid, used by bench.py outside its timed region)."""
         _capi.check(self._h, self._lib.cmps_set_option(self._h, _capi.CMPS_OPT_KERNEL_EVENTS, 1 if on else 0))
 
@@ -365,6 +365,38 @@ class HipScan:
         out = torch.empty((n, length), dtype=torch.float32, device=self.device)
         _capi.check(self._h, self._lib.cmps_noise_fill(self._h, int(seed), int(first_step), int(first_path), n, length, float(std),
                                                        out.data_ptr(), self._stream()))
+        return out
+
+    def gather_batch(self, data: torch.Tensor, index: torch.Tensor, offset: Optional[torch.Tensor] = None, T: Optional[int] = None) -> torch.Tensor:
+        """cmps_batch_gather: a batch cut out of a dataset that lives on the device.  ``data`` float32 [N, L], ``index`` (and ``offset``,
+        default all zero) int32 [B], all contiguous on this device; returns float32 [B, T] (T defaults to L) with row b =
+        data[index[b], offset[b] : offset[b] + T] -- or T quiet NaNs where index[b] or offset[b] is out of range.  No host copy, no
+        synchronisation."""
+        def ok(t, dtype, dim):
+            return isinstance(t, torch.Tensor) and t.device == self.device and t.dtype == dtype and t.dim() == dim and t.is_contiguous()
+        if not ok(data, torch.float32, 2):
+            raise ValueError("gather_batch: data must be a contiguous float32 tensor [N, L] on the backend's device")
+        if not ok(index, torch.int32, 1) or (offset is not None and (not ok(offset, torch.int32, 1) or offset.shape != index.shape)):
+            raise ValueError("gather_batch: index (and offset) must be contiguous int32 tensors [B] on the backend's device")
+        N, L = int(data.shape[0]), int(data.shape[1])
+        B, T = int(index.shape[0]), L if T is None else int(T)
+        out = torch.empty((B, T), dtype=torch.float32, device=self.device)
+        if B == 0:
+            return out
+        _capi.check(self._h, self._lib.cmps_batch_gather(self._h, data.data_ptr(), N, L, index.data_ptr(),
+                                                         offset.data_ptr() if offset is not None else None, B, T, out.data_ptr(),
+                                                         self._stream()))
+        return out
+
+    def damped_sine(self, seed: int, first_clip: int, B: int, T: int, delta_t: float) -> torch.Tensor:
+        """cmps_damped_sine_fill: clips first_clip .. first_clip + B - 1 of the seed's synthetic damped-sine sequence (include/cmps.h),
+        float32 [B, T], generated on the device.  No host copy, no synchronisation."""
+        B, T = int(B), int(T)
+        if B < 1 or T < 1:
+            raise ValueError("damped_sine needs B >= 1 and T >= 1")
+        out = torch.empty((B, T), dtype=torch.float32, device=self.device)
+        _capi.check(self._h, self._lib.cmps_damped_sine_fill(self._h, int(seed), int(first_clip), B, T, float(delta_t), out.data_ptr(),
+                                                             self._stream()))
         return out
 
     def _device_noise(self, noise, length=None, n=None):

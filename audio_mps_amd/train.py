@@ -11,6 +11,8 @@ The TensorBoard summaries (train.py:62-85: scalars, audio, histogram, tfplot ima
 not part of the hot path; the scalar ones are returned by ``Trainer.step`` as a dict.
 Run:  python -m audio_mps_amd.train --dataset=damped_sine --hparams=bond_dim=32,minibatch_size=64
 (under torchrun for several GPUs: the batch is sharded over ranks, one RCCL all-reduce per step).
+``--device_data`` produces every batch on the device instead of on the host (audio_mps_amd/device_data.py): a TFRecord dataset is uploaded
+once and gathered from in the host pipeline's order, damped_sine is generated there.
 """
 from __future__ import annotations
 
@@ -274,7 +276,30 @@ def build_parser():
     p.add_argument("--host_optimizer", action="store_true",
                    help="chain rule and Adam in numpy on the host (the reference implementation of the optimiser half) instead of "
                         "the device-resident step (cmps_psi_apply_step / cmps_rho_apply_step)")
+    p.add_argument("--device_data", action="store_true",
+                   help="produce every batch on the device instead of on the host: damped_sine is generated there from (--seed, clip "
+                        "number) (cmps_damped_sine_fill: other clips than the host generator draws for the same seed), a TFRecord dataset "
+                        "is uploaded once and every batch gathered from it in the order of the host pipeline (cmps_batch_gather).  With "
+                        "more than one rank every rank holds the whole dataset and gathers its shard of the batch")
+    p.add_argument("--crop_duration", type=int, default=None,
+                   help="with --device_data and a TFRecord dataset: train on this many samples of every clip, cut from a random start "
+                        "(--sample_duration stays the length of the records)")
     return p
+
+
+def device_source(args, hp, backend):
+    """--device_data: (next_size, next_shard) of the run's input.  next_size(step) is the size of the global batch of ``step``,
+    next_shard(step, (start, count)) that rank's rows of it as a device tensor; the two are called in turn, once per step."""
+    from .device_data import DampedSineSource, ResidentDataset
+    if args.dataset == "damped_sine":
+        src = DampedSineSource(backend, hp.minibatch_size, args.sample_duration, hp.delta_t, seed=args.seed)
+        return (lambda step: hp.minibatch_size), src.next
+    path = os.path.join(str(args.datadir), f"{args.dataset}.tfrecords")
+    if not os.path.exists(path):
+        raise FileNotFoundError(f"{path} (the reference's data blobs are not distributed: .MISSING_LARGE_BLOBS)")
+    stream = ResidentDataset.from_tfrecord(path, args.sample_duration, backend).batches(
+        hp.minibatch_size, seed=args.seed, order="data", crop=args.crop_duration, crop_seed=args.seed)
+    return (lambda step: stream.next_size), (lambda step, shard: stream(shard=shard))
 
 
 def main(argv=None, backend=None):
@@ -284,6 +309,8 @@ def main(argv=None, backend=None):
     args = build_parser().parse_args(argv)
     hp = HParams(delta_t=1.0 / args.sample_rate, h_reg=200.0 / (math.pi * args.sample_rate) ** 2)  # train.py:41-43
     hp.parse(args.hparams)
+    if args.crop_duration is not None and (not args.device_data or args.dataset == "damped_sine"):
+        raise ValueError("--crop_duration needs --device_data and a TFRecord dataset (crops are cut by the device-side gather)")
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if backend is None:
         import torch
@@ -306,18 +333,25 @@ def main(argv=None, backend=None):
     last_save = time.time()
     # train.py:46-47: the input pipeline is built ONCE; for TFRecord datasets get_audio returns the one-shot iterator's
     # get_next (batch -> shuffle(24) -> repeat, data.py:37-40), for damped_sine every step draws fresh delays (data.py:15)
+    # --device_data: the same batches (TFRecords) / the device's own clips (damped_sine), produced on the device, a rank's shard only
+    on_device = device_source(args, hp, backend) if args.device_data else None
     source = get_audio(args.datadir, args.dataset, hp, args.sample_duration, seed=args.seed) \
-        if args.dataset != "damped_sine" else None
+        if args.dataset != "damped_sine" and on_device is None else None
     for it in range(args.max_steps):
-        if source is not None:
+        if on_device is not None:
+            n_full = int(on_device[0](trainer.global_step))
+        elif source is not None:
             full = source()
         else:
             full = get_audio(args.datadir, args.dataset, hp, args.sample_duration, seed=args.seed + trainer.global_step)
+        if on_device is None:
+            n_full = int(full.shape[0])
         # every rank reads the same global batch and keeps its shard (a short final batch of an epoch is sharded as it is)
-        s0, c0 = dp.shard(full.shape[0]) if full.shape[0] != hp.minibatch_size else (start, count)
+        s0, c0 = dp.shard(n_full) if n_full != hp.minibatch_size else (start, count)
+        shard = on_device[1](trainer.global_step, (s0, c0)) if on_device is not None else full[s0:s0 + c0]
         # the losses come to the host only on logging steps (the device-resident step needs no device -> host copy otherwise)
         log_now = (it % max(args.log_every, 1) == 0) or it == args.max_steps - 1
-        out = trainer.step(full[s0:s0 + c0], sync=log_now, global_batch=int(full.shape[0]))
+        out = trainer.step(shard, sync=log_now, global_batch=n_full)
         if dp.rank == 0:
             if log_now:
                 print(f"step {out['global_step']}: model_loss {out['model_loss']:.6f} total_loss {out['total_loss']:.6f}")

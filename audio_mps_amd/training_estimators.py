@@ -38,6 +38,11 @@ def build_parser():
     p.add_argument("--data_dir", default="")                       # :36-39 (a .tfrecords file)
     p.add_argument("--sample_duration", type=int, default=2 ** 16)  # FixedLenFeature([2 ** 16]) at :81
     p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--device_data", action="store_true",
+                   help="produce every batch on the device instead of on the host: the TFRecord file is uploaded once and every batch "
+                        "gathered from it in the order of the host pipeline (cmps_batch_gather); without --data_dir the synthetic clips "
+                        "are generated there (cmps_damped_sine_fill: other clips than the host generator draws for the same seed).  With "
+                        "more than one rank every rank holds the whole dataset and gathers its shard of the batch")
     return p
 
 
@@ -99,11 +104,18 @@ class Estimator:
     def train(self, input_fn: Callable[[], np.ndarray], steps: int):
         """model_fn in TRAIN mode, `steps` times (training_estimators.py:48-74, 114-115)."""
         start, count = None, None
+        takes_shard = getattr(input_fn, "takes_shard", False)       # a device-side input (--device_data) produces this rank's rows only
         for _ in range(steps):
-            batch = input_fn()
-            if start is None:
-                start, count = self.dp.shard(batch.shape[0])
-            flat, b_local = self.model.grad_sums(batch[start:start + count])
+            if takes_shard:
+                if start is None:
+                    start, count = self.dp.shard(int(self.params["batch_size"]))
+                local = input_fn(shard=(start, count))
+            else:
+                batch = input_fn()
+                if start is None:
+                    start, count = self.dp.shard(batch.shape[0])
+                local = batch[start:start + count]
+            flat, b_local = self.model.grad_sums(local)
             host, b_global = self.dp.allreduce_sums(flat, b_local)
             loss, grads = self.model.chain_rule(host, b_global, with_reg=False)     # :64, :68 minimise(loss)
             self.opt.apply_gradients(self.model.variables, grads)
@@ -114,6 +126,22 @@ class Estimator:
         return self
 
 
+def build_device_input_fns(backend, data_dir: str, batch_size: int, sample_duration: int, dt: float, seed: int = 0, first_step: int = 0):
+    """--device_data: the input of build_input_fns (or, without a dataset, the synthetic fixture) produced on the device.  The callable
+    takes ``shard=(start, count)`` and returns that rank's rows of the next batch (``takes_shard``, see Estimator.train)."""
+    from .device_data import DampedSineSource, ResidentDataset
+    if data_dir:
+        return ResidentDataset.from_tfrecord(data_dir, sample_duration, backend).batches(batch_size, seed=seed, order="estimator")
+    src = DampedSineSource(backend, batch_size, sample_duration, dt, seed=seed)
+    state = {"step": int(first_step)}                               # (a restored run continues the sequence from its global_step)
+
+    def train_input_fn(shard=None):
+        state["step"] += 1
+        return src.next(state["step"] - 1, shard)
+    train_input_fn.takes_shard = True
+    return train_input_fn
+
+
 def main(argv=None):
     import torch
     args = build_parser().parse_args(argv)
@@ -121,7 +149,12 @@ def main(argv=None):
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     torch.cuda.set_device(local_rank)
     dp = DataParallel(device=torch.device("cuda", local_rank))
-    if args.data_dir:
+    estimator = Estimator(params, model_dir=args.model_dir, save_checkpoints_steps=args.viz_steps, dp=dp,
+                          model_kw={"seed": args.seed})
+    if args.device_data:
+        train_input_fn = build_device_input_fns(estimator.model._get_backend(), args.data_dir, args.batch_size, args.sample_duration,
+                                                args.dt, seed=args.seed, first_step=estimator.global_step)
+    elif args.data_dir:
         train_input_fn = build_input_fns(args.data_dir, args.batch_size, args.sample_duration, seed=args.seed)
     else:   # no dataset given: the reference's synthetic fixture (data.py:8-22), so that the script runs anywhere
         from .data import damped_sine
@@ -130,8 +163,6 @@ def main(argv=None):
         def train_input_fn():
             state["i"] += 1
             return damped_sine(args.batch_size, args.sample_duration, args.dt, seed=args.seed + state["i"])
-    estimator = Estimator(params, model_dir=args.model_dir, save_checkpoints_steps=args.viz_steps, dp=dp,
-                          model_kw={"seed": args.seed})
     for _ in range(args.max_steps // args.viz_steps):                               # :114-115
         estimator.train(train_input_fn, steps=args.viz_steps)
         if dp.rank == 0:

@@ -84,7 +84,7 @@ enum {
     CMPS_OPT_F16_SCALE_SHIFT = 4 /* DIAGNOSTIC, default 0: added to the exponent of every data-dependent fp16 scale of the wave reverse
                         * scan's F16X2 arithmetic (range -40 .. 40).  A positive value pushes the pieces out of fp16 range on purpose:
                         * how tests/test_gpu_parity.py provokes CMPS_ERR_F16_RANGE.  No reference counterpart. */,
-    CMPS_OPT_KERNEL_EVENTS = 2 /* 1: every kernel cmps_psi_loss_fwd / _bwd, cmps_rho_loss_fwd / _bwd, cmps_psi_sample, cmps_psi_sample_primed, cmps_psi_stream, cmps_psi_stream_score, cmps_rho_sample_primed, cmps_rho_stream, cmps_rho_stream_score and cmps_noise_fill (as k_noise_philox) launch is bracketed by two HIP events on the caller's stream
+    CMPS_OPT_KERNEL_EVENTS = 2 /* 1: every kernel cmps_psi_loss_fwd / _bwd, cmps_rho_loss_fwd / _bwd, cmps_psi_sample, cmps_psi_sample_primed, cmps_psi_stream, cmps_psi_stream_score, cmps_rho_sample_primed, cmps_rho_stream, cmps_rho_stream_score, cmps_noise_fill (as k_noise_philox), cmps_batch_gather (as k_batch_gather) and cmps_damped_sine_fill (as k_damped_sine) launch is bracketed by two HIP events on the caller's stream
                         * (read and reset with cmps_kernel_times); 0 (default): nothing is recorded.  A measurement aid -- the reference
                         * has no counterpart (no tracing / profiling hooks); bench.py uses it OUTSIDE its timed region to price
                         * each kernel of a multi-kernel family against the pipe it runs on */
@@ -567,6 +567,51 @@ int cmps_rho_apply_step(cmps_handle_t h, float* vars_dev, float* adam_m_dev, flo
 int cmps_noise_fill(cmps_handle_t h, unsigned long long seed, unsigned long long first_step,
                     unsigned first_path, int n, int length, float stddev,
                     float* noise_dev, void* stream);
+
+/*
+ * A training batch cut out of a dataset that is already in device memory.  Replaces: audio_dataset.batch(...) ... get_next()
+ * (data.py:37-43), whose order the caller plans on clip indices (audio_mps_amd/device_data.py).
+ *   data_dev  [n_clips * clip_len] float32, row-major [clip][sample];  index_dev [B] int;  offset_dev [B] int, or NULL for all zero;
+ *   audio_dev[b * T + j] = data_dev[index[b] * clip_len + offset[b] + j],   b < B, j < T      (all address arithmetic in 64 bits).
+ * THE ROW GUARD: a row whose index[b] lies outside [0, n_clips) or whose offset[b] lies outside [0, clip_len - T] is written as T quiet
+ * NaNs (0x7fc00000) and nothing is read for it -- a bad plan is memory-safe and loud (the loss turns NaN); the other rows are unaffected.
+ * Only rows named by a valid index are read, and of those only the T samples copied.
+ * Every pointer needs 4-byte alignment only.  Needs no cmps_set_params: it works on a fresh handle of any D and in legacy mode.
+ * Asynchronous on `stream`; never synchronises, allocates nothing and touches no element outside audio_dev[0 .. B * T).
+ * CMPS_ERR_BAD_ARG, each with a message, the first failing check speaking: a null handle, data_dev, index_dev or audio_dev; B < 1 or T < 1;
+ * n_clips < 1 or n_clips > 2^31 - 1; clip_len < T.
+ * With CMPS_OPT_KERNEL_EVENTS the launch is recorded as k_batch_gather.
+ */
+int cmps_batch_gather(cmps_handle_t h, const float* data_dev, long long n_clips, long long clip_len,
+                      const int* index_dev, const int* offset_dev, int B, int T,
+                      float* audio_dev, void* stream);
+
+/*
+ * The synthetic training batch, generated where it is used.  Replaces: the damped_sine branch of get_audio (data.py:8-22): a 261.6 Hz sine
+ * that starts after a Gamma(2)-distributed delay and decays with a time constant of 0.1 s.  Row b of audio_dev [B * T] is clip
+ * c = first_clip + b, a pure function of (seed, c, T, delta_t): a caller who fills clips [start, start + count) of a global batch gets exactly
+ * those rows of the whole batch without generating the rest, and a resumed run continues the sequence without generator state.
+ * THE DEFINITION (normative; tests/_data_ref.py restates it in numpy), fl32(x) = x rounded to float32, every operation in float32:
+ *   (x0, x1, ., .) = Philox4x32-10(counter = (c & 0xffffffff, c >> 32, 0, 1), key = (seed & 0xffffffff, seed >> 32))     as in cmps_noise_fill;
+ *     counter word 3 = 1 keeps these draws apart from the noise's, which use 0
+ *   u_i = ((x_i >> 8) + 1) * 2^-24     in (0, 1]   (exact in float32)
+ *   delay = fl32(T / 200.0) * (-(logf(u0) + logf(u1)))       a Gamma(2, scale = delay_time / 2) draw with delay_time = T / 100
+ *                                                            (data.py:13, 15), as the sum of two exponentials;  0 <= delay < 0.1664 T
+ *   for sample j:  t = ((float)j - delay) * fl32(delta_t)
+ *                  audio[b * T + j] = ((0.5f * (sign(t) + 1.0f)) * sinf(fl32(2 pi 261.6) * t)) * expf(-t / fl32(0.1))
+ *     a product, in this order, as the reference writes it (data.py:19-22), with sign(0) = 0; the accurate logf / sinf / expf, not the fast
+ *     intrinsics (the sine's argument reaches thousands of radians).
+ * The Philox integers are bit-exact; the float part is within a few float32 roundings of the definition evaluated in double.  As in the
+ * reference, the samples before the onset are the product 0 * expf(-t / 0.1) with t < 0: exactly zero while 0.1664 T delta_t stays below
+ * 8.8 s (expf finite), which every clip shorter than 53 s does.
+ * Needs no cmps_set_params: it works on a fresh handle of any D and in legacy mode.  Asynchronous on `stream`; never synchronises, allocates
+ * nothing, reads no device memory and touches no element outside audio_dev[0 .. B * T).
+ * CMPS_ERR_BAD_ARG, each with a message, the first failing check speaking: a null handle or audio_dev; B < 1, T < 1 or T > 2^24 (beyond that
+ * (float)j is not exact); delta_t not finite or <= 0; first_clip + B overflowing 64 bits.
+ * With CMPS_OPT_KERNEL_EVENTS the launch is recorded as k_damped_sine.
+ */
+int cmps_damped_sine_fill(cmps_handle_t h, unsigned long long seed, unsigned long long first_clip,
+                          int B, int T, double delta_t, float* audio_dev, void* stream);
 
 /*
  * Host utility (no GPU involved): CRC-32C (Castagnoli, reflected polynomial 0x82F63B78) of `n` bytes, continuing from
