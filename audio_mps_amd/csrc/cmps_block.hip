@@ -333,6 +333,12 @@ __global__ void k_states(Dev P, float* __restrict__ psi_out) {
         } else if (P.stash_layout == STASH_WAVE32) {   // 32-row wave layout: 64 (y[n], (H y)[n]) pairs, n = 2 i + {re, im}
             const float* r = P.hst + row * 128;
             y = make_float2(r[4 * i], r[4 * i + 2]);
+        } else if (P.stash_layout == STASH_WAVE32N) {  // the same positions hold yhat = y / sqrt(max(n, 1e-12)); n_k from the scalar rows [B][NC][2][64]
+            const float* r = P.hst + row * 128;
+            const int b = (int)(row / N), NC = (N + 63) / 64;
+            const float nk = P.scal[((size_t)b * NC + (k >> 6)) * 128 + (k & 63)];
+            const float nrm = sqrtf(fmaxf(nk, 1e-12f));
+            y = make_float2(r[4 * i] * nrm, r[4 * i + 2] * nrm);
         } else if (P.stash_layout == STASH_WIDE) {
             // wide variant (cmps_wide.hip): per pair and step [y | H y][wave][lane], lane = 8 q + i, q = (row half, component, clip)
             const int b = (int)(row / N);

@@ -98,6 +98,16 @@ int wave_rank1(int mode) {
 }
 // the same option where there is only an fp16 and a bf16 form (loss products, samplers, the legacy gradient GEMM): true for two fp16 pieces
 bool rank1_f16(int mode) { return mode == CMPS_RANK1_DEFAULT || mode == CMPS_RANK1_F16X2; }
+// whether the 32-row family's reverse scan of this handle is the two-wave kernel (k_bwd_wave2w: F16X2 sums only)
+bool bwd_two_wave(const cmps_handle_s* h) { return h->bwd_waves == 2 && rank1_f16(h->rank1_mode) && h->f16_shift == 0; }
+// Diagnostic builds only (-DCMPS_DIAG -DCMPS_DIAG_YHY_ROWS, scripts/ablate.py): the forward keeps writing (y, H y) rows, so the two-wave
+// reverse scan runs its (y, H y) instance -- the behaviour before the normalised rows, for A/B timing.
+#if defined(CMPS_DIAG) && defined(CMPS_DIAG_YHY_ROWS)
+#undef CMPS_DIAG_YHY_ROWS
+#define CMPS_DIAG_YHY_ROWS 1
+#else
+#define CMPS_DIAG_YHY_ROWS 0
+#endif
 // ... and as the wide kernels' gradient GEMM takes it: -2 two fp16 pieces, 2 two bf16 pieces, 3 three bf16 pieces
 int rank1_wide_pieces(int mode) { return rank1_f16(mode) ? -2 : mode == CMPS_RANK1_BF16X2 ? 2 : 3; }
 
@@ -257,6 +267,7 @@ int cmps_set_option(cmps_handle_t h, int option, int value) {
         if (!value && h->ktimer) { ktimer_free(h->ktimer); h->ktimer = nullptr; }
         return CMPS_OK;
     }
+    if (option == CMPS_OPT_SAVED_ROWS) return fail(h, CMPS_ERR_BAD_ARG, "cmps_set_option: CMPS_OPT_SAVED_ROWS is read-only");
     return fail(h, CMPS_ERR_BAD_ARG, "cmps_set_option: unknown option");
 }
 
@@ -268,6 +279,7 @@ int cmps_get_option(cmps_handle_t h, int option) {
     if (option == CMPS_OPT_F16_SCALE_SHIFT) return h->f16_shift;
     if (option == CMPS_OPT_BWD_WAVES) return h->bwd_waves;
     if (option == CMPS_OPT_RHO_BWD) return h->rho_virtual_bwd ? CMPS_RHO_BWD_VIRTUAL : CMPS_RHO_BWD_GEMM;
+    if (option == CMPS_OPT_SAVED_ROWS) return h->main.valid && h->main.layout == STASH_WAVE32N ? 1 : 0;
     return -1;
 }
 
@@ -406,18 +418,21 @@ int cmps_psi_loss_fwd(cmps_handle_t h, const float* audio_dev, int B, int T, flo
     const int family = variant == CMPS_VARIANT_WAVE && h->D <= 16 ? STASH_WAVE16 : wave ? STASH_WAVE32
                      : variant == CMPS_VARIANT_PAIR ? STASH_PAIR : variant == CMPS_VARIANT_WIDE ? STASH_WIDE : STASH_BLOCK;
     const bool save = save_for_bwd != 0, f16 = rank1_f16(h->rank1_mode);
+    // The rows of the 32-row family are written normalised (STASH_WAVE32N) when the reverse pass of this handle will be k_bwd_wave2w:
+    // decided from the options NOW and recorded; cmps_psi_loss_bwd follows the record.
+    const bool norm_rows = save && family == STASH_WAVE32 && bwd_two_wave(h) && !CMPS_DIAG_YHY_ROWS;
     hipError_t e;
     switch (family) {
     case STASH_WAVE16: { KScope ks("k_fwd_wave16", s); e = launch_fwd_wave16(P, audio_dev, loss_dev, save, s); } break;
     // the loss product's pieces follow CMPS_OPT_RANK1 like the reverse scan's rank-1 sums: two fp16 pieces for F16X2 / DEFAULT
-    case STASH_WAVE32: { KScope ks("k_fwd_wave2", s); e = launch_fwd_wave2(P, audio_dev, loss_dev, save, f16, s); } break;
+    case STASH_WAVE32: { KScope ks("k_fwd_wave2", s); e = launch_fwd_wave2(P, audio_dev, loss_dev, save, f16, norm_rows, s); } break;
     case STASH_PAIR: { KScope ks("k_fwd_pair", s); e = launch_fwd_pair(P, audio_dev, loss_dev, save, s); } break;
     // k_fwd_wide, k_hy_wide, k_loss_wide (scopes inside); the loss product's pieces follow CMPS_OPT_RANK1 like the gradient GEMM's
     case STASH_WIDE: e = launch_fwd_wide(P, audio_dev, loss_dev, save, f16, h->wide_chain != CMPS_WIDE_CHAIN_VALU, s); break;
     default: { KScope ks("k_fwd_block", s); e = launch_fwd_block(P, audio_dev, loss_dev, save, s); } break;
     }
     if (e != hipSuccess) return fail_hip(h, e, "cmps_psi_loss_fwd");
-    h->main = Saved{save, B, T - 1, audio_dev, loss_dev, family};
+    h->main = Saved{save, B, T - 1, audio_dev, loss_dev, norm_rows ? (int)STASH_WAVE32N : family};
     return CMPS_OK;
 }
 
@@ -458,10 +473,12 @@ int cmps_psi_loss_bwd(cmps_handle_t h, const float* audio_dev, int B, int T, flo
         if (e != hipSuccess) return fail_hip(h, e, "cmps_psi_loss_bwd (wide reduce)");
         return CMPS_OK;
     }
-    const bool w16 = layout == STASH_WAVE16, wave = w16 || layout == STASH_WAVE32;
+    const bool w16 = layout == STASH_WAVE16, norm_rows = layout == STASH_WAVE32N, wave = w16 || layout == STASH_WAVE32 || norm_rows;
     hipError_t e;
     {
-        const bool two = wave && !w16 && h->bwd_waves == 2 && rank1_f16(h->rank1_mode) && h->f16_shift == 0;
+        // normalised rows have one reader, k_bwd_wave2w (the forward wrote them for it): options that changed since the forward do not
+        // move the reverse pass of THAT forward to a kernel that would misread them
+        const bool two = norm_rows || (wave && !w16 && bwd_two_wave(h));
         KScope ks(!wave ? "k_bwd_block" : w16 ? "k_bwd_wave16" : two ? "k_bwd_wave2w" : "k_bwd_wave", s);
         e = !wave ? launch_bwd_block(P, audio_dev, s) : w16 ? launch_bwd_wave16(P, audio_dev, s)
           : two ? launch_bwd_wave2w(P, audio_dev, s) : launch_bwd_wave(P, audio_dev, wave_rank1(h->rank1_mode), s);

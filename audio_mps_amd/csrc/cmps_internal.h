@@ -137,6 +137,8 @@ enum StashLayout : int {
     STASH_PAIR = 2,      // pair rows (cmps_pair.hip)
     STASH_WAVE32 = 3,    // hst rows of (y[n], (H y)[n]) pairs, n = 2 i + {re, im} (cmps_wave2.hip)
     STASH_WIDE = 4,      // wide rows (cmps_wide.hip): [pair][step][y | H y][wave][lane] float
+    STASH_WAVE32N = 5,   // hst rows of (yhat[n], p[n]) pairs in STASH_WAVE32's positions: yhat_k = y_k / sqrt(max(n_k, 1e-12)), p_k = 2 ebar_k (H y_k)
+                         // (cmps_wave2.hip, for k_bwd_wave2w alone; n_k in the scalar rows turns yhat back into y, H y is not recoverable)
 };
 
 // Device-side view handed to the kernels by value.
@@ -404,7 +406,7 @@ hipError_t launch_fwd_block(const Dev& P, const float* audio, float* loss, bool 
 hipError_t launch_bwd_block(const Dev& P, const float* audio, hipStream_t s);
 hipError_t launch_bwd_wave(const Dev& P, const float* audio, int rank1_mode, hipStream_t s);
 hipError_t launch_bwd_wave2w(const Dev& P, const float* audio, hipStream_t s);    // cmps_wave_bwd2.hip: two waves per clip (F16X2 sums)
-hipError_t launch_fwd_wave2(const Dev& P, const float* audio, float* loss, bool save, bool hf16, hipStream_t s);
+hipError_t launch_fwd_wave2(const Dev& P, const float* audio, float* loss, bool save, bool hf16, bool norm_rows, hipStream_t s);
 hipError_t launch_fwd_wave16(const Dev& P, const float* audio, float* loss, bool save, hipStream_t s);
 hipError_t launch_bwd_wave16(const Dev& P, const float* audio, hipStream_t s);
 hipError_t launch_fwd_pair(const Dev& P, const float* audio, float* loss, bool save, hipStream_t s);

@@ -25,7 +25,8 @@
 // Synchronisation is two LDS counters per clip and NO barrier: the ring holds two chunks; the loss wave starts chunk
 // c when prod >= c + 1, the chain wave starts chunk c (c >= 2) when cons >= c - 1.  LDS operations of one wave
 // complete in order, so a counter write issued after the chunk's data is visible after it.
-// Same arithmetic as k_fwd_wave (cmps_wave.hip) up to rounding, same stash layouts; the reverse sweep is unchanged.  Since round 6 the chain
+// Same arithmetic as k_fwd_wave (cmps_wave.hip) up to rounding, same stash layouts (plus the normalised rows of the NORM instance, below:
+// what the two-wave reverse scan reads by default).  Since round 6 the chain
 // carries the UN-normalised state z_k and the loss wave normalises the rows it reads.
 #include "cmps_wave_util.h"
 
@@ -116,7 +117,11 @@ __device__ __forceinline__ void lds_wait_hi_t_after(v4f (&o)[8], v2f& t, v2f& de
 // pieces per operand and three products (hi hi + hi lo + lo hi on v_mfma_f32_32x32x16_f16) instead of three bf16 pieces and six: the
 // arithmetic of the wide family's k_hy_wide<f16x2>.  Scales: W from its largest entry (below 2^15), the chunk's y rows from
 // the guaranteed bound |y_k|_2 <= 1 + |Q|_F + max_chunk |s_k| |R|_F (below 2^14); one exact multiply takes them out of the accumulators.
-template <bool SAVE, bool LEGACY = false, bool HF16 = false>
+// NORM (with SAVE, PsiCMPS arithmetic): the stash rows are written NORMALISED for the two-wave reverse scan (STASH_WAVE32N,
+// cmps_wave_bwd2.hip): (yhat_k[n], p_k[n]) with yhat_k = y_k inv_k, inv_k = rsq_newton(max(n_k, 1e-12)), p_k = 2 ebar_k (H y_k),
+// ebar_k = -(x_k / A) / (1 + z_k) -- three multiplies per component and step that the reverse CHAIN wave would otherwise issue, done here
+// where the most issue slots are free.  The rows are stored behind the e_k column sums and the per-chunk scalar stage (2 ebar_k needs e_k).
+template <bool SAVE, bool LEGACY = false, bool HF16 = false, bool NORM = false>
 __global__ __launch_bounds__(128 * WAVES, 1) void k_fwd_wave2(Dev P, const float* __restrict__ audio,
                                                               float* __restrict__ loss_out) {
     // rho rows of the chain wave's chunk, two buffers (round 5): the next chunk's rows are fetched in two halves of 16 rows and committed
@@ -486,40 +491,41 @@ __global__ __launch_bounds__(128 * WAVES, 1) void k_fwd_wave2(Dev P, const float
 #pragma unroll
             for (int r = 0; r < 16; ++r) pn[r] = yc0[r] * yc0[r] + yc1[r] * yc1[r];
         }
-        if (SAVE) {
-            // Stash row (kbeg + step) = 64 pairs (y[n], (H y)[n]) = 512 contiguous bytes.  Register r holds step s0 = (r & 3) +
-            // 8 (r >> 2) in lanes 0-31 and step s0 + 4 in lanes 32-63, for n = 0..31 (tile 0) and n = 32..63 (tile 1): one
-            // v_permlane32_swap between the two tiles puts ALL of row s0 into one register and all of row s0 + 4 into the
-            // other, so every store instruction writes one whole row (lane = n).
-            // A full chunk (all but a clip's last): address = uniform base (SGPR pair, one per eight rows: the immediate reaches 4095) + this
-            // lane's 8 bytes (one VGPR for the whole kernel) + the row's immediate -- no 64-bit VALU address arithmetic and no per-row test.
-            // (Stores by asm: dwordx2 data has no write-after-store hazard; nothing in this kernel reads the rows back.)
-            char* cbase = reinterpret_cast<char*>(st + (size_t)kbeg * 64);
-            const unsigned loff = (unsigned)lane * 8u;
-            if (cnt == CH2) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int s0 = (r & 3) + 8 * (r >> 2);
-                    const auto ys = __builtin_amdgcn_permlane32_swap(__float_as_uint(yc0[r]), __float_as_uint(yc1[r]), false, false);
-                    const auto hs = __builtin_amdgcn_permlane32_swap(__float_as_uint(acc0[r]), __float_as_uint(acc1[r]), false, false);
-                    const v2f lo = mk2(__uint_as_float(ys[0]), __uint_as_float(hs[0])), hi = mk2(__uint_as_float(ys[1]), __uint_as_float(hs[1]));
-                    const char* q0 = cbase + (s0 >> 3) * 4096;              // rows 8 q .. 8 q + 7
-                    asm volatile("global_store_dwordx2 %0, %1, %2 offset:%3" :: "v"(loff), "v"(lo), "s"(q0), "n"((s0 & 7) * 512) : "memory");
-                    asm volatile("global_store_dwordx2 %0, %1, %2 offset:%3" :: "v"(loff), "v"(hi), "s"(q0), "n"(((s0 + 4) & 7) * 512) : "memory");
-                }
-            } else {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int s0 = (r & 3) + 8 * (r >> 2);
-                    const auto ys = __builtin_amdgcn_permlane32_swap(__float_as_uint(yc0[r]), __float_as_uint(yc1[r]), false, false);
-                    const auto hs = __builtin_amdgcn_permlane32_swap(__float_as_uint(acc0[r]), __float_as_uint(acc1[r]), false, false);
-                    if (s0 < cnt)
-                        *reinterpret_cast<float2*>(cbase + s0 * 512 + loff) = make_float2(__uint_as_float(ys[0]), __uint_as_float(hs[0]));
-                    if (s0 + 4 < cnt)
-                        *reinterpret_cast<float2*>(cbase + (s0 + 4) * 512 + loff) = make_float2(__uint_as_float(ys[1]), __uint_as_float(hs[1]));
-                }
+        // (a macro, not a lambda: the (y, H y) instances keep the instruction stream they had)
+        // Stash row (kbeg + step) = 64 pairs (y[n], (H y)[n]) = 512 contiguous bytes.  Register r holds step s0 = (r & 3) +
+        // 8 (r >> 2) in lanes 0-31 and step s0 + 4 in lanes 32-63, for n = 0..31 (tile 0) and n = 32..63 (tile 1): one
+        // v_permlane32_swap between the two tiles puts ALL of row s0 into one register and all of row s0 + 4 into the
+        // other, so every store instruction writes one whole row (lane = n).
+        // A full chunk (all but a clip's last): address = uniform base (SGPR pair, one per eight rows: the immediate reaches 4095) + this
+        // lane's 8 bytes (one VGPR for the whole kernel) + the row's immediate -- no 64-bit VALU address arithmetic and no per-row test.
+        // (Stores by asm: dwordx2 data has no write-after-store hazard; nothing in this kernel reads the rows back.)
+#define FWD2_STORE_ROWS                                                                                                                             \
+            char* cbase = reinterpret_cast<char*>(st + (size_t)kbeg * 64);                                                                          \
+            const unsigned loff = (unsigned)lane * 8u;                                                                                              \
+            if (cnt == CH2) {                                                                                                                       \
+                _Pragma("unroll")                                                                                                                   \
+                for (int r = 0; r < 16; ++r) {                                                                                                      \
+                    const int s0 = (r & 3) + 8 * (r >> 2);                                                                                          \
+                    const auto ys = __builtin_amdgcn_permlane32_swap(__float_as_uint(yc0[r]), __float_as_uint(yc1[r]), false, false);               \
+                    const auto hs = __builtin_amdgcn_permlane32_swap(__float_as_uint(acc0[r]), __float_as_uint(acc1[r]), false, false);             \
+                    const v2f lo = mk2(__uint_as_float(ys[0]), __uint_as_float(hs[0])), hi = mk2(__uint_as_float(ys[1]), __uint_as_float(hs[1]));   \
+                    const char* q0 = cbase + (s0 >> 3) * 4096;                                                                                      \
+                    asm volatile("global_store_dwordx2 %0, %1, %2 offset:%3" :: "v"(loff), "v"(lo), "s"(q0), "n"((s0 & 7) * 512) : "memory");       \
+                    asm volatile("global_store_dwordx2 %0, %1, %2 offset:%3" :: "v"(loff), "v"(hi), "s"(q0), "n"(((s0 + 4) & 7) * 512) : "memory"); \
+                }                                                                                                                                   \
+            } else {                                                                                                                                \
+                _Pragma("unroll")                                                                                                                   \
+                for (int r = 0; r < 16; ++r) {                                                                                                      \
+                    const int s0 = (r & 3) + 8 * (r >> 2);                                                                                          \
+                    const auto ys = __builtin_amdgcn_permlane32_swap(__float_as_uint(yc0[r]), __float_as_uint(yc1[r]), false, false);               \
+                    const auto hs = __builtin_amdgcn_permlane32_swap(__float_as_uint(acc0[r]), __float_as_uint(acc1[r]), false, false);             \
+                    if (s0 < cnt)                                                                                                                   \
+                        *reinterpret_cast<float2*>(cbase + s0 * 512 + loff) = make_float2(__uint_as_float(ys[0]), __uint_as_float(hs[0]));          \
+                    if (s0 + 4 < cnt)                                                                                                               \
+                        *reinterpret_cast<float2*>(cbase + (s0 + 4) * 512 + loff) = make_float2(__uint_as_float(ys[1]), __uint_as_float(hs[1]));    \
+                }                                                                                                                                   \
             }
-        }
+        if (SAVE && !NORM) { FWD2_STORE_ROWS }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         flag_store(aCons, c + 1, lane);                                // every ring read has landed: the half is free
         // e_k = sum_n y_k[n] (H y_k)[n]: transpose the per-column products through LDS, then lane (k, hh) sums columns
@@ -563,6 +569,34 @@ __global__ __launch_bounds__(128 * WAVES, 1) void k_fwd_wave2(Dev P, const float
         } else {
             const float z = (evec * incv) / A;                         // model.py:294 operation order
             lv = -logf(1.0f + z);
+            if constexpr (SAVE && NORM) {
+                // the per-row factors in the reverse scan's own operations (cmps_wave_bwd2.hip::scal_commit), so that yhat and p are
+                // bit for bit what its pre stage formed from (y, H y) rows; to the C/D-layout registers the way c_k went: an LDS row each
+                // (cst is free since the y rows were formed, pe since the column sums were read) and one 16-byte read per four steps
+                const float invk = rsq_newton(fmaxf(nk, 1e-12f));
+                const float zbar = -1.0f / (1.0f + z);
+                const float tev = 2.0f * (zbar * incv / A);
+                __builtin_amdgcn_wave_barrier();
+                if (lane < CH2) { cst[w][lane] = invk; pew[lane] = tev; }
+                __builtin_amdgcn_wave_barrier();
+#pragma unroll
+                for (int g4 = 0; g4 < 4; ++g4) {
+                    const float4 ig = *reinterpret_cast<const float4*>(&cst[w][8 * g4 + 4 * chk]);
+                    const float4 tg = *reinterpret_cast<const float4*>(&pew[8 * g4 + 4 * chk]);
+                    const v2f i01 = mk2(ig.x, ig.y), i23 = mk2(ig.z, ig.w), t01 = mk2(tg.x, tg.y), t23 = mk2(tg.z, tg.w);
+#pragma unroll
+                    for (int q = 0; q < 4; q += 2) {
+                        const int r = 4 * g4 + q;
+                        const v2f iv = q ? i23 : i01, tv = q ? t23 : t01;
+                        const v2f a = mk2(yc0[r], yc0[r + 1]) * iv, b2 = mk2(yc1[r], yc1[r + 1]) * iv;
+                        const v2f p0 = mk2(acc0[r], acc0[r + 1]) * tv, p1 = mk2(acc1[r], acc1[r + 1]) * tv;
+                        yc0[r] = a.x; yc0[r + 1] = a.y; yc1[r] = b2.x; yc1[r + 1] = b2.y;
+                        acc0[r] = p0.x; acc0[r + 1] = p0.y; acc1[r] = p1.x; acc1[r + 1] = p1.y;
+                    }
+                }
+                __builtin_amdgcn_wave_barrier();
+                FWD2_STORE_ROWS
+            }
         }
         if (cnt == CH2) {                                              // model.py:279: sequential in time.  A full chunk unrolled: the lane
 #pragma unroll                                                         // selects are immediates (v_readlane + v_add per step; the counted loop
@@ -575,11 +609,18 @@ __global__ __launch_bounds__(128 * WAVES, 1) void k_fwd_wave2(Dev P, const float
             sc[(size_t)(c >> 1) * 128 + 64 + (c & 1) * CH2 + lane] = evec;
         }
     }
+#undef FWD2_STORE_ROWS
     if (lane == 0) loss_out[b] = loss;
 }
 
-hipError_t launch_fwd_wave2(const Dev& P, const float* audio, float* loss, bool save, bool hf16, hipStream_t s) {
+// norm_rows: write STASH_WAVE32N rows (the caller asks for them only with save and hf16: the two-wave reverse scan's settings)
+hipError_t launch_fwd_wave2(const Dev& P, const float* audio, float* loss, bool save, bool hf16, bool norm_rows, hipStream_t s) {
     const unsigned nb = (unsigned)((P.B + WAVES - 1) / WAVES);
+    if (norm_rows) {
+        if (!save || !hf16) return hipErrorInvalidValue;
+        hipLaunchKernelGGL((k_fwd_wave2<true, false, true, true>), dim3(nb), dim3(128 * WAVES), 0, s, P, audio, loss);
+        return hipGetLastError();
+    }
     return dispatch_bool(save, [&](auto sv) {
         return dispatch_bool(hf16, [&](auto hf) {
             hipLaunchKernelGGL((k_fwd_wave2<decltype(sv)::value, false, decltype(hf)::value>), dim3(nb), dim3(128 * WAVES), 0, s, P, audio, loss);

@@ -22,6 +22,9 @@
 // Arithmetic: the chain is k_bwd_wave's instruction for instruction; the sums are the F16X2 form (three products per pair, fp32
 // accumulate), with scales that differ from k_bwd_wave<3>'s by powers of two only where both are in range -- same accuracy class
 // (tests/test_gpu_parity.py::test_two_wave_reverse_scan_*).  PsiCMPS arithmetic only (no legacy mode); RhoCMPS virtual clips are supported.
+// Two instances: on (y, H y) rows (RhoCMPS virtual clips; a PsiCMPS forward saved under other settings) the chain is k_bwd_wave's
+// instruction for instruction; on the forward's NORMALISED rows (STASH_WAVE32N, the PsiCMPS default) the pre stage and the serial tail
+// are shorter -- same algebra, rounding points moved (tests/test_gpu_norm_stash.py).
 #include "cmps_wave_util.h"
 
 namespace cmps {
@@ -33,6 +36,7 @@ struct Pre2 {
     v2f rho;
     v2f sd;                                    // (s_k, dt_k): kept as a pair so that v_pk_fma can read s from its low half
     float inv, ten, rad;
+    float q;                                   // normalised rows: q_k (the radial term's factor, see scal_commit)
 };
 
 constexpr int RING_SLOT = 256;                 // bytes: one value of one step, 64 lanes
@@ -53,6 +57,24 @@ __device__ __forceinline__ void swap_fill(float& a, float& b, v2f& m0, v2f r0, v
         "v_permlane32_swap_b32 %0, %1"
         : "+v"(a), "+v"(b), "=&v"(m0), "=&v"(m1) : "v"(r0), "v"(q0), "v"(r1), "v"(q1), "v"(s2));
 }
+// The pre stage's reads on NORMALISED rows: the lane's own (yhat, p) pair, the partner component's yhat (the neighbouring pair of the
+// staged row: no lane exchange), rho, and the step's ONE 16-byte scalar row.  Four LDS operations, as own_issue: the counted waits of
+// the step are the same numbers.
+__device__ __forceinline__ void own_issue_n(unsigned ay, unsigned ap, unsigned ar, unsigned as, v2f& yh, float& part, v2f& t, v4f& c0) {
+    asm volatile("ds_read_b64 %0, %4\n\tds_read_b32 %1, %5\n\tds_read_b64 %2, %6\n\tds_read_b128 %3, %7"
+                 : "=&v"(yh), "=&v"(part), "=&v"(t), "=&v"(c0) : "v"(ay), "v"(ap), "v"(ar), "v"(as) : "memory");
+}
+template <int OY, int OR, int OS>
+__device__ __forceinline__ void own_issue_n_off(unsigned ay, unsigned ap, unsigned ar, unsigned as, v2f& yh, float& part, v2f& t, v4f& c0) {
+    asm volatile("ds_read_b64 %0, %4 offset:%8\n\tds_read_b32 %1, %5 offset:%8\n\tds_read_b64 %2, %6 offset:%9\n\t"
+                 "ds_read_b128 %3, %7 offset:%10"
+                 : "=&v"(yh), "=&v"(part), "=&v"(t), "=&v"(c0) : "v"(ay), "v"(ap), "v"(ar), "v"(as), "n"(OY), "n"(OR), "n"(OS)
+                 : "memory");
+}
+template <int N>
+__device__ __forceinline__ void lds_wait_own_n(v2f& yh, float& part, v2f& t, v4f& c0) {
+    asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(yh), "+v"(part), "+v"(t), "+v"(c0) : "n"(N) : "memory");
+}
 template <int OFF>
 __device__ __forceinline__ void ring_write(unsigned addr, float v) {
     asm volatile("ds_write_b32 %0, %1 offset:%2" : : "v"(addr), "v"(v), "n"(OFF) : "memory");
@@ -69,6 +91,9 @@ __device__ __forceinline__ float wave_max(float x) {       // max over the 64 la
 
 }  // namespace
 
+// NORM: the stash rows are the forward's normalised rows (STASH_WAVE32N: (yhat_k[n], p_k[n]) pairs, cmps_wave2.hip) and the chain wave's
+// pre stage and serial tail take their short form (make_pre, chain_step); else (y, H y) rows (PsiCMPS on other settings, RhoCMPS).
+template <bool NORM = false>
 __global__ __launch_bounds__(128 * WAVES, 1) void k_bwd_wave2w(Dev P, const float* __restrict__ audio) {
     __shared__ __attribute__((aligned(16))) float4 stY[WAVES][CHB * 32];   // stashed (y, H y) rows of the staged chunk
     __shared__ __attribute__((aligned(16))) float4 stR[WAVES][CHB * 16];   // rho rows
@@ -114,12 +139,15 @@ __global__ __launch_bounds__(128 * WAVES, 1) void k_bwd_wave2w(Dev P, const floa
         }
         const unsigned aBw = lds_addr(&bcB[w][0]) + i * 8 + h * 4, aBr = lds_addr(&bcB[w][0]) + h * 128;
         const unsigned aYown = lds_addr(&stY[w][0]) + (2 * i + h) * 8;   // stash rows: 64 (y[n], (H y)[n]) pairs, n = 2 i + {re, im}
+        const unsigned aYpart = lds_addr(&stY[w][0]) + (2 * i + (1 - h)) * 8;   // NORM: the pair of the partner component, n ^ 1
+        const unsigned sgn_h = hb ? 0x80000000u : 0u;                       // NORM: osig = the partner's value with the sign of the half
         const unsigned aRho = lds_addr(&stR[w][0]) + i * 8;
         const unsigned aScl = lds_addr(&scl[w][0]);
         const float4* rho4 = reinterpret_cast<const float4*>(P.rho);
         const float4* sty4 = reinterpret_cast<const float4*>(P.hst + ((size_t)bc * N * vr + av) * 128);
         float facc = 0.f, accS = 0.f, accA = 0.f;
         float ra0 = 0.f, ra1 = 0.f, rdt = 0.f, rnv = 1.f, rev = 0.f;   // raw prefetched values of the next chunk
+        float rad_above = 0.f;                        // NORM: rad of the lowest step of the scalar chunk above (no step N: 0)
         // staging by OCTETS (two waves share the SIMD's registers: 256 each): while the chain works through rows 8 q .. 8 q + 7 of the staged
         // chunk, the same eight rows of the chunk below wait in 24 registers and take over the slots when the octet is done
         v4f so4[4], so2[2];
@@ -174,8 +202,22 @@ __global__ __launch_bounds__(128 * WAVES, 1) void k_bwd_wave2w(Dev P, const floa
             const float zbar = -1.0f / (1.0f + z);
             const float ebar = zbar * inc / A;
             const float tev = 2.0f * ebar;
+            if constexpr (NORM) {
+                // ONE 16-byte row per step, (s_k, dt_k, +-inv_k, q_k).  The radial term of ybar_k, rad_{k+1} [n_k > 1e-12] inv_k yhat_k, has
+                // rad_{k+1} = 2 ebar_{k+1} e_{k+1} a step early, so its factor q_k = rad_{k+1} [n_k > 1e-12] inv_k is formed here, once per 64
+                // steps and lane-parallel (rad of step 64 (c + 1) comes from the chunk above, committed before this one).  The sign of the
+                // inv entry carries [n_k > 1e-12] for the steps that take the explicit projection (chain_step reads |inv|: a source modifier).
+                const float radv = tev * ev;
+                float radn = __shfl_down(radv, 1, 64);
+                if (lane == CH - 1) radn = rad_above;
+                if (idx + 1 >= N) radn = 0.f;                                      // (rows above N - 1 hold whatever the workspace held)
+                rad_above = rdlane(radv, 0);
+                const bool ok = nv > 1e-12f;
+                scl[w][lane] = make_float4(sv, rdt, ok ? invv : -invv, ok ? radn * invv : 0.f);
+            } else {
             scl[w][2 * lane] = make_float4(sv, rdt, invv, tev * nv);
             scl[w][2 * lane + 1] = make_float4(tev, invokv, tev * ev, 0.f);
+            }
             sct[w][c & 1][lane] = make_float2(sv, tev * nv);      // what the gradient wave needs of the row (it may lag two octets behind)
             if (idx < N) accA += zbar * ex;
         };
@@ -203,6 +245,23 @@ __global__ __launch_bounds__(128 * WAVES, 1) void k_bwd_wave2w(Dev P, const floa
             return S;
         };
 
+        // The same on normalised rows: yhat and p = 2 ebar (H y) are the loaded values, the partner component comes from LDS, the radial term
+        // is folded into t = p - q yhat.  4 VALU: t, the signed partner, two for un.
+        auto make_pre_n = [&](v2f yh2, float part, v2f rho, v4f c0) -> Pre2 {
+            Pre2 S;
+            S.rho = rho;
+            S.sd = __builtin_shufflevector(c0, c0, 0, 1);
+            S.inv = c0.z;
+            S.q = c0.w;
+            S.yh = yh2.x;
+            S.pre = __builtin_fmaf(-S.q, yh2.x, yh2.y);
+            S.yho = __uint_as_float(__float_as_uint(part) ^ sgn_h);
+            // Re / Im of rho yhat for this half: cmul2's low half with its roundings (the product, then one FMA) -- only that half is
+            // used, and written out it needs no (yhat, osig) register pair
+            S.un = __builtin_fmaf(-S.yho, rho.y, S.yh * rho.x);
+            return S;
+        };
+
         const int hl = (N - 1) / CHB;
 #pragma unroll 1
         for (int q = 0; q < 4; ++q) { octet_load(hl, q); octet_commit(q); }      // the top chunk (row (N - 1) & 31 feeds the first pre stage)
@@ -211,8 +270,14 @@ __global__ __launch_bounds__(128 * WAVES, 1) void k_bwd_wave2w(Dev P, const floa
         v4f qc[8];
         v2f yh_j, rho_j;
         v4f c0_j, c1_j;
+        float part_j;                                 // NORM: the partner component's yhat of the row being read
         Pre2 S;
-        {
+        if constexpr (NORM) {
+            const int jr = (N - 1) & (CHB - 1), jc = (N - 1) & (CH - 1);
+            own_issue_n(aYown + jr * 512, aYpart + jr * 512, aRho + jr * 256, aScl + jc * 16, yh_j, part_j, rho_j, c0_j);
+            lds_wait_own_n<0>(yh_j, part_j, rho_j, c0_j);
+            S = make_pre_n(yh_j, part_j, rho_j, c0_j);
+        } else {
             const int jr = (N - 1) & (CHB - 1), jc = (N - 1) & (CH - 1);
             own_issue(aYown + jr * 512, aRho + jr * 256, aScl + jc * 32, yh_j, rho_j, c0_j, c1_j);
             lds_wait_own<0>(yh_j, rho_j, c0_j, c1_j);
@@ -235,29 +300,46 @@ __global__ __launch_bounds__(128 * WAVES, 1) void k_bwd_wave2w(Dev P, const floa
             facc += S.sd.y * (go * S.un);
             const v2f yhbp = cmul2_conj_b(mk2(g, go), S.rho);              // conj(rho_k) g
             const float yhb = yhbp.x;
+            float ybar;
+            if constexpr (NORM) {
+                // ybar = yhb inv + (p - rad_{k+1} [n > 1e-12] inv yhat): ONE instruction on the chain (t = S.pre is the pre stage's)
+                ybar = __builtin_fmaf(yhb, __builtin_fabsf(S.inv), S.pre);
+                if (exact) {                                               // the explicit projection: the wave sum in rad_{k+1}'s place
+                    asm volatile("" ::: "memory");
+                    const float dsum = sum64(S.yh * yhb);
+                    const float okinv = S.inv > 0.f ? S.inv : 0.f;
+                    ybar = __builtin_fmaf(__builtin_fmaf(-okinv, dsum, S.q), S.yh, ybar);
+                }
+            } else {
             float dot = rad_next;
             if (exact) {                                                   // (a real branch: see k_bwd_wave)
                 asm volatile("" ::: "memory");
                 dot = sum64(S.yhp * yhb);
             }
             rad_next = S.rad;
-            const float ybar = (yhb - dot * S.yhp) * S.inv + S.pre;
+            ybar = (yhb - dot * S.yhp) * S.inv + S.pre;
+            }
             bcast_issue(aBw, aBr, ybar, qc);                               // 9 ops
-            {   // M_k = Q + s_k R^dagger, in the shadow of the broadcast (entries 10, 11: inside this step's pre stage, make_pre; the last MT: in
-                // the tail of the step before)
+            {   // M_k = Q + s_k R^dagger, in the shadow of the broadcast (entries 10, 11: inside this step's pre stage, make_pre -- on
+                // normalised rows there is no lane exchange to hide them in, they are formed here; the last MT: in the tail of the step before)
                 const v2f s2 = mk2(S.sd.x, S.sd.x);
 #pragma unroll
-                for (int m = 0; m < 16 - MT - 2; ++m) MM[m] = __builtin_elementwise_fma(MRd[m], s2, MQ[m]);
+                for (int m = 0; m < (NORM ? 16 - MT : 16 - MT - 2); ++m) MM[m] = __builtin_elementwise_fma(MRd[m], s2, MQ[m]);
             }
             Pre2 Sn = S;
-            if constexpr (!decltype(have_pre)::value) {                     // no pre stage to carry entries 10, 11 (step 0)
+            if constexpr (!NORM && !decltype(have_pre)::value) {            // no pre stage to carry entries 10, 11 (step 0)
                 const v2f s2 = mk2(S.sd.x, S.sd.x);
                 MM[10] = __builtin_elementwise_fma(MRd[10], s2, MQ[10]);
                 MM[11] = __builtin_elementwise_fma(MRd[11], s2, MQ[11]);
             }
             if constexpr (decltype(have_pre)::value) {
-                lds_wait_own<9>(yh_j, rho_j, c0_j, c1_j);
-                Sn = make_pre(yh_j, rho_j, c0_j, c1_j, S.sd);
+                if constexpr (NORM) {
+                    lds_wait_own_n<9>(yh_j, part_j, rho_j, c0_j);
+                    Sn = make_pre_n(yh_j, part_j, rho_j, c0_j);
+                } else {
+                    lds_wait_own<9>(yh_j, rho_j, c0_j, c1_j);
+                    Sn = make_pre(yh_j, rho_j, c0_j, c1_j, S.sd);
+                }
                 uk = Sn.un;
             }
             // the gradient wave's operands of this step (behind the broadcast: the counted waits below only get stricter)
@@ -332,7 +414,8 @@ __global__ __launch_bounds__(128 * WAVES, 1) void k_bwd_wave2w(Dev P, const floa
                 int t = 8 - u_top;
                 for (; j >= jlo && (j & 7) != 7; --j, ++t) {
                     const int jr = j & (CHB - 1), jc = j & (CH - 1);
-                    own_issue(aYown + jr * 512, aRho + jr * 256, aScl + jc * 32, yh_j, rho_j, c0_j, c1_j);
+                    if constexpr (NORM) own_issue_n(aYown + jr * 512, aYpart + jr * 512, aRho + jr * 256, aScl + jc * 16, yh_j, part_j, rho_j, c0_j);
+                    else own_issue(aYown + jr * 512, aRho + jr * 256, aScl + jc * 32, yh_j, rho_j, c0_j, c1_j);
                     S = chain_step(S, 0.f, std::true_type{}, proj_ok && j == jhi, ab + t * RING_SLOT, std::integral_constant<int, 0>{});
                 }
                 if (hh > 0) octet_commit(q);
@@ -342,7 +425,8 @@ __global__ __launch_bounds__(128 * WAVES, 1) void k_bwd_wave2w(Dev P, const floa
 #define BWD2_STEP8(PQ)                                                                                         \
             {                                                                                                 \
                 if ((PQ) == 3) peek_cons();                                                                                \
-                own_issue_off<(PQ) * 512, (PQ) * 256, (PQ) * 32>(aYo8, aRo8, aSo8, yh_j, rho_j, c0_j, c1_j);  \
+                if constexpr (NORM) own_issue_n_off<(PQ) * 512, (PQ) * 256, (PQ) * 16>(aYo8, aPo8, aRo8, aSo8, yh_j, part_j, rho_j, c0_j);   \
+                else own_issue_off<(PQ) * 512, (PQ) * 256, (PQ) * 32>(aYo8, aRo8, aSo8, yh_j, rho_j, c0_j, c1_j);  \
                 S = chain_step(S, 0.f, std::true_type{}, (PQ) == 7 && proj_ok && j == jhi, ab8, std::integral_constant<int, (7 - (PQ)) * RING_SLOT>{}); \
             }
             for (; j >= jlo; j -= 8) {
@@ -351,7 +435,8 @@ __global__ __launch_bounds__(128 * WAVES, 1) void k_bwd_wave2w(Dev P, const floa
                 wait_free(oct);
                 const unsigned ab8 = half_base(oct);
                 const unsigned aYo8 = aYown + ((j - 7) & (CHB - 1)) * 512, aRo8 = aRho + ((j - 7) & (CHB - 1)) * 256;
-                const unsigned aSo8 = aScl + ((j - 7) & (CH - 1)) * 32;
+                const unsigned aSo8 = aScl + ((j - 7) & (CH - 1)) * (NORM ? 16 : 32);
+                const unsigned aPo8 = aYpart + ((j - 7) & (CHB - 1)) * 512;       // (NORM only)
                 BWD2_STEP8(7) BWD2_STEP8(6) BWD2_STEP8(5) BWD2_STEP8(4) BWD2_STEP8(3) BWD2_STEP8(2) BWD2_STEP8(1) BWD2_STEP8(0)
                 if (hh > 0) octet_commit_below(q);
                 publish();
@@ -505,9 +590,11 @@ __global__ __launch_bounds__(128 * WAVES, 1) void k_bwd_wave2w(Dev P, const floa
     }
 }
 
+// (the row kind is the saved-forward record's: P.stash_layout)
 hipError_t launch_bwd_wave2w(const Dev& P, const float* audio, hipStream_t s) {
     const unsigned nb = (unsigned)((P.B + WAVES - 1) / WAVES);
-    hipLaunchKernelGGL(k_bwd_wave2w, dim3(nb), dim3(128 * WAVES), 0, s, P, audio);
+    if (P.stash_layout == STASH_WAVE32N) hipLaunchKernelGGL(k_bwd_wave2w<true>, dim3(nb), dim3(128 * WAVES), 0, s, P, audio);
+    else hipLaunchKernelGGL(k_bwd_wave2w<false>, dim3(nb), dim3(128 * WAVES), 0, s, P, audio);
     return hipGetLastError();
 }
 

@@ -80,7 +80,14 @@ enum {
                         * SIMD, a chain wave and a gradient wave (k_bwd_wave2w, cmps_wave_bwd2.hip); 1 = one wavefront per clip (k_bwd_wave,
                         * the round-4 kernel: the A/B setting).  Same float32 tolerances; every other CMPS_OPT_RANK1 value, a non-zero
                         * CMPS_OPT_F16_SCALE_SHIFT and the legacy mode run one wavefront whatever this says; the RhoCMPS reverse sweep on virtual clips
-                        * (CMPS_OPT_RHO_BWD) follows it */,
+                        * (CMPS_OPT_RHO_BWD) follows it.
+                        * The SAVED FORWARD is tied to the reverse kernel it was written for: when cmps_psi_loss_fwd(save_for_bwd = 1) runs
+                        * with the settings of k_bwd_wave2w (17 <= D <= 32 or CMPS_VARIANT_WAVE32, this option 2, F16X2 / DEFAULT sums, no
+                        * scale shift), its stash rows are written normalised, (yhat_k, 2 ebar_k H y_k) instead of (y_k, H y_k), and the
+                        * cmps_psi_loss_bwd of that forward runs k_bwd_wave2w whatever this option, CMPS_OPT_RANK1 and
+                        * CMPS_OPT_F16_SCALE_SHIFT say by then: they take effect with the next forward.  cmps_psi_states reads either kind. */,
+    CMPS_OPT_SAVED_ROWS = 7 /* READ-ONLY (cmps_get_option): 1 when the main workspace holds a saved pure-state forward with normalised stash
+                        * rows (see CMPS_OPT_BWD_WAVES), else 0 */,
     CMPS_OPT_F16_SCALE_SHIFT = 4 /* DIAGNOSTIC, default 0: added to the exponent of every data-dependent fp16 scale of the wave reverse
                         * scan's F16X2 arithmetic (range -40 .. 40).  A positive value pushes the pieces out of fp16 range on purpose:
                         * how tests/test_gpu_parity.py provokes CMPS_ERR_F16_RANGE.  No reference counterpart. */,
@@ -219,7 +226,9 @@ int cmps_psi_apply_step(cmps_handle_t h, float* vars_dev, float* adam_m_dev, flo
  * (:293-294), _expectation (:319-325), _normalize_psi (:327-334) per step.
  * audio_dev [B*T] row-major float32 clips (the `data_iterator` tensor);  loss_dev [B] receives the
  * per-clip loss (the fold carry); PsiCMPS.loss is its mean (model.py:267).
- * save_for_bwd != 0 stashes the per-step un-normalised state in the workspace (needs CMPS_WS_TRAIN).
+ * save_for_bwd != 0 stashes the per-step state in the workspace (needs CMPS_WS_TRAIN): un-normalised, or -- in the form the two-wave
+ * reverse scan reads -- normalised; which one is chosen from the handle's options at THIS call and recorded with the saved forward
+ * (CMPS_OPT_BWD_WAVES, CMPS_OPT_SAVED_ROWS).  cmps_psi_loss_bwd and cmps_psi_states follow the record.
  */
 int cmps_psi_loss_fwd(cmps_handle_t h, const float* audio_dev, int B, int T, float* loss_dev,
                       int save_for_bwd, void* stream);

@@ -4,7 +4,8 @@
 usage: ablate.py [--shape D T B ROUNDS VARIANT] name=-DFLAG[,-DFLAG...] ...
   e.g. ablate.py base= no_mfma=-DPABL_NO_MFMA --shape 128 16000 512 2 3
 Every build gets -DCMPS_DIAG; known switches (all inert without it): CMPS_DIAG_NO_LOSS / CMPS_DIAG_NO_CHAIN (cmps_wave2.hip:
-only the chain wave / only the loss wave of the forward runs), PABL_NO_MFMA / PABL_NO_BARRIER / PABL_TIMING (s_memtime stamps
+only the chain wave / only the loss wave of the forward runs), CMPS_DIAG_YHY_ROWS (cmps_capi.hip: the 32-row forward keeps writing
+(y, H y) rows, so the two-wave reverse scan runs its (y, H y) instance -- the A/B of the normalised rows; results are right), PABL_NO_MFMA / PABL_NO_BARRIER / PABL_TIMING (s_memtime stamps
 inside the pair scans, printed per launch) (cmps_pair.hip; round 4 dropped NO_REDUCE, NO_EXPORT*, NO_STASHREAD and HALF_READS with
 the code they switched).  tests/test_capi_load.py compiles each of them so that they cannot rot.
 Runs on the GPU box (hipcc is available there); libraries go to gpurun_out/.
