@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Robustness sweep on the GPU by hand: `python scripts/random_sweep.py SEED [family ...]` runs tests/_sweep.py with the full draw
-counts (the test module tests/test_gpu_sweep.py runs fixed seeds with fewer draws and asserts the bars) and prints the worst case per
+counts (the test modules tests/test_gpu_sweep.py and tests/test_gpu_sweep_stream.py run fixed seeds with fewer draws and assert the bars)
+and prints the worst case per
 family and quantity, the time per family, and every record above its bar."""
 import os
 import sys

@@ -1,6 +1,7 @@
 """Random robustness sweep: random shapes, parameter scales, amplitudes and sampling rates through every kernel family against
-the oracles.  Shared by `tests/test_gpu_sweep.py` (fixed seeds, asserted bars: what the driver runs) and
-`scripts/random_sweep.py` (any seed, prints the worst case per family).
+the oracles.  Shared by `tests/test_gpu_sweep.py` (the loss and gradient families) and `tests/test_gpu_sweep_stream.py` (the sampler, stream
+and score families) -- fixed seeds, asserted bars: what the driver runs -- and `scripts/random_sweep.py` (any seed, prints the worst case
+per family).
 
 Why it is a test: rounds 2-3 were green with a wrong `Qbar` in `k_bwd_wave` (a VALU write one wait state in front of
 the MFMA that read it) because no fixed test made Q = -(dt sigma^2 / 2) R^dagger R (/root/reference/model.py:312)
@@ -15,14 +16,34 @@ A batch for which grad_sums took the fp16-range fallback (BF16X3 / VALU re-run) 
 there to stress the fp16 scales, and the re-run would otherwise stand in for the kernel under test."""
 from __future__ import annotations
 
+import dataclasses
+
 import numpy as np
 
 from oracle import cmps_oracle as O, c_oracle as C
 from _util import make_audio, c_oracle_run, grad_sums_and_fallbacks, rel_inf, oracle_hparams, oracle_variables
+import _score_ref as SC
+import _rho_score_ref as RS
+from _score_ref import SCORE, FOLLOW, SAMPLE
 
 LOSS_BAR, GRAD_BAR = 1e-5, 1e-4
 PAIR_LOSS_BAR, PAIR_GRAD_BAR = 3e-4, 2e-3          # tests/test_gpu_pair.py, vs oracle.psi_bf16_scan
-DEFAULT_COUNTS = {"psi": 60, "wide": 16, "step": 8, "pair": 14, "rho": 34, "legacy": 10}
+DEFAULT_COUNTS = {"psi": 60, "wide": 16, "step": 8, "pair": 14, "rho": 34, "legacy": 10, "psi_stream": 60, "rho_stream": 40}
+
+# The stream families (psi_stream, rho_stream: the samplers, the resumable stream, its score mode, the saved RhoCMPS states) keep three
+# things apart: draw_*(rng, it) -> case and check_*(case, result, ref32, ref64) -> records need numpy and the oracle only, so
+# tests/test_sweep_stream_host.py can show on the CPU that the checks catch a wrong step; run_*_hip(case) -> result is the kernels.  Every
+# check is against the float64 reference; its bar is the floor of the fixed tests plus their factor 4 on the float32 reference's own distance
+# from float64.  Factor and floors are those of the headers of the fixed tests, quoted here once:
+STREAM_FACTOR = 4.0                       # test_gpu_primed.py: "the kernels sum in another order than numpy (factor 4)"
+PSI_OUT_FLOOR = 2e-5                      # test_gpu_primed.py OUT_RTOL, x max(1, max |out|)
+PSI_PRED_FLOOR = 2e-6                     # test_gpu_primed.py, x max |pred|: "the accuracy tests' own"
+NLL_FLOOR = 2.0 ** -22                    # test_gpu_stream_score.py: "two roundings of 1 + z at 1"
+RHO_OUT_FLOOR = 2e-4                      # test_gpu_rho_primed.py OUT_RTOL, x max |out|
+RHO_PRODUCT_FLOOR = 8.0 * 2.0 ** -22      # test_gpu_rho_primed.py: x |R|_F delta_t for pred; test_gpu_rho_stream_score.py: x |R|_F max|x| / A for nll
+RHO_STATE_FLOOR = 2e-4                    # test_gpu_rho_stream.py: rel_inf(rho), x max |rho|
+PURITY_RTOL, PURITY_ATOL = 2e-4, 1e-6     # test_gpu_rho_stream.py
+AUTO, BLOCK, BF16X3 = 0, 1, 2             # CMPS_VARIANT_AUTO, CMPS_VARIANT_BLOCK; CMPS_OPT_RANK1 = BF16X3
 
 
 def _loss_err(per, ref):
@@ -205,7 +226,309 @@ def sweep_legacy(rng, n, out):
         out.append(("legacy", "grad", max(rel_inf(grads["R"], ref["gR"]), rel_inf(grads["H"], ref["gH"])), GRAD_BAR, (D, T, B)))
 
 
-FAMILIES = {"psi": sweep_psi, "wide": sweep_wide, "step": sweep_step, "pair": sweep_pair, "rho": sweep_rho, "legacy": sweep_legacy}
+# ---------------------------------------------------------------------------------------------------
+# the sampler, stream and score kernels: random plans of scored, followed and sampled segments
+# ---------------------------------------------------------------------------------------------------
+def _draw_plan(rng, cap=None):
+    """1-5 segments of kind score, follow or sample; each step count from {1, 2, U[1, 40), U[60, 70), U[1, 140)} (single steps, both sides
+    of the kernels' 64-step chunk), at most `cap`; a forced segment behind the first is anchored at random."""
+    plan = []
+    for s in range(int(rng.integers(1, 6))):
+        kind = (SCORE, FOLLOW, SAMPLE)[int(rng.integers(3))]
+        steps = (1, 2, int(rng.integers(1, 40)), int(rng.integers(60, 70)), int(rng.integers(1, 140)))[int(rng.integers(5))]
+        anchored = bool(rng.integers(2)) and kind != SAMPLE and s > 0
+        plan.append((kind, steps if cap is None else min(steps, cap), anchored))
+    return plan
+
+
+def _draw_inputs(rng, hp, plan, n, n_audio, amp, temp, silent):
+    """(clip [n_audio, columns] = O.damped_sine x amp, its first third silent with `silent`, or None without forced steps;
+    noise [sampled, n] = O.sample_noise at `temp`, or None without sampled steps)."""
+    S, F, L, _ = SC.plan_counts(plan)
+    clip = noise = None
+    seed = int(rng.integers(2 ** 31))
+    if S + F:
+        cols = SC.clip_columns(plan)
+        clip = (O.damped_sine(n_audio, cols, hp.delta_t, seed=seed) * np.float32(amp)).astype(np.float32)
+        if silent and S + F > 40:
+            clip[:, : cols // 3] = 0.0                       # increments exactly zero
+    if L:
+        noise = O.sample_noise(hp, n, L, temp=temp, seed=seed + 1)
+    return clip, noise
+
+
+def _plan_text(plan):
+    return " ".join(f"{kind[:2]}{steps}{'a' if anchored else ''}" for kind, steps, anchored in plan)
+
+
+def draw_psi_stream(rng, it):
+    """Draw `it` of the psi_stream family (numpy only): the ranges of sweep_psi / sweep_wide, a plan, its clip and its noise."""
+    D = int(rng.integers(33, 129)) if it % 3 == 2 else int(rng.integers(1, 33))
+    variant = BLOCK if int(rng.integers(4)) == 0 else AUTO
+    n = int(rng.integers(1, 7))
+    n_audio = 1 if int(rng.integers(4)) == 0 else n         # one clip shared by every path
+    sigma = float(10 ** rng.uniform(-4, 0))
+    rs = float(10 ** (rng.uniform(-1.5, 0) if D <= 32 else rng.uniform(-1.5, -0.3)))
+    A = float(10 ** rng.uniform(0, 2))
+    amp = float(10 ** rng.uniform(-3, 0.3))
+    delta_t = float(10 ** rng.uniform(-5, -3.5)) if it % 4 == 1 else 1.0 / 16000      # 3 kHz ... 100 kHz, as sweep_psi
+    temp = float(rng.uniform(0.1, 1.5))
+    plan = _draw_plan(rng)
+    hp = O.HParams(minibatch_size=n, bond_dim=D, delta_t=delta_t, sigma=sigma, A=A)
+    var = O.init_variables(hp, seed=int(rng.integers(2 ** 31)))
+    var.Rx, var.Ry = var.Rx * np.float32(rs), var.Ry * np.float32(rs)
+    clip, noise = _draw_inputs(rng, hp, plan, n, n_audio, amp, temp, silent=it % 3 == 0)
+    cfg = (it, D, n, n_audio, variant, round(sigma, 5), round(rs, 3), round(A, 2), round(amp, 4), float(f"{delta_t:.3g}"), round(temp, 2),
+           _plan_text(plan))
+    return dict(family="psi_stream", hparams=hp, variables=var, plan=plan, clip=clip, noise=noise, n=n, n_audio=n_audio, variant=variant,
+                options={}, cfg=cfg)
+
+
+def draw_rho_stream(rng, it):
+    """Draw `it` of the rho_stream family (numpy only): three draws of four in the row-array kernel's range with sweep_rho's scales of R and
+    of the clip, the fourth in the general kernel's (32 < D <= 128, segments of at most 30 steps: the reference keeps n x steps x D^2
+    states)."""
+    big = it % 4 == 3
+    if big:
+        D = int(rng.integers(33, 129)); rank = int(rng.integers(1, min(D, 40) + 1)); rs = 0.4
+    else:
+        D = int(rng.integers(2, 33)); rank = int(rng.integers(1, D + 1)); rs = float(10 ** rng.uniform(-2.5, 0.2))
+    rank1 = BF16X3 if not big and int(rng.integers(4)) == 0 else None
+    variant = BLOCK if int(rng.integers(4)) == 0 else AUTO
+    n = int(rng.integers(1, 5))
+    n_audio = 1 if int(rng.integers(4)) == 0 else n
+    sigma = float(10 ** rng.uniform(-4, -0.3))
+    A = float(10 ** rng.uniform(0, 2))
+    amp = float(10 ** rng.uniform(-3, 0.7))
+    delta_t = float(10 ** rng.uniform(-5, -3.5)) if int(rng.integers(4)) == 0 else 1.0 / 16000      # (drawn: `it % 4` picks the kernel here)
+    temp = float(rng.uniform(0.1, 1.5))
+    plan = _draw_plan(rng, cap=30 if big else None)
+    hp = O.HParams(minibatch_size=n, bond_dim=D, delta_t=delta_t, sigma=sigma, A=A, initial_rank=rank)
+    seed = int(rng.integers(2 ** 31))
+    var = O.init_variables(hp, seed=seed)
+    var.Rx, var.Ry = var.Rx * np.float32(rs), var.Ry * np.float32(rs)
+    var.psi_x, var.psi_y = np.zeros(D, np.float32), np.zeros(D, np.float32)          # (RhoCMPS has none)
+    Wx, Wy = O.rho_init_W(hp, seed=seed)
+    clip, noise = _draw_inputs(rng, hp, plan, n, n_audio, amp, temp, silent=False)
+    cfg = (it, D, rank, n, n_audio, variant, rank1, round(sigma, 5), round(rs, 4), round(A, 2), round(amp, 4), float(f"{delta_t:.3g}"),
+           round(temp, 2), _plan_text(plan))
+    return dict(family="rho_stream", hparams=hp, variables=var, Wx=Wx, Wy=Wy, plan=plan, clip=clip, noise=noise, n=n, n_audio=n_audio,
+                variant=variant, options={"rank1": rank1}, cfg=cfg)
+
+
+def reference_psi_stream(case, dtype):
+    """SC.score_reference on the draw's own hparams and variables: dict(nll, total, pred, out)."""
+    with np.errstate(all="ignore"):
+        nll, total, pred, out, _ = SC.score_reference(case["hparams"], case["variables"], case["plan"], case["clip"], case["noise"], dtype,
+                                                      n=case["n"])
+    return dict(nll=nll, total=total, pred=pred, out=out)
+
+
+def reference_rho_stream(case, dtype):
+    """RS.rho_score_reference on the draw's own hparams and variables: dict(nll, total, pred, out, rho, purity)."""
+    with np.errstate(all="ignore"):
+        nll, total, pred, out, rho, purity, _ = RS.rho_score_reference(case["hparams"], case["variables"], case["Wx"], case["Wy"],
+                                                                       case["plan"], case["clip"], case["noise"], dtype, n=case["n"])
+    return dict(nll=nll, total=total, pred=pred, out=out, rho=rho, purity=purity)
+
+
+def all_finite(res):
+    return all(np.all(np.isfinite(v)) for v in res.values() if isinstance(v, np.ndarray))
+
+
+def _amax(a):
+    return float(np.max(np.abs(a))) if np.size(a) else 0.0
+
+
+def _dist(a, b):
+    """max |a - b| in double precision (NaN if either holds one)."""
+    wide = np.complex128 if np.iscomplexobj(b) else np.float64
+    return _amax(np.asarray(a, dtype=wide) - np.asarray(b, dtype=wide))
+
+
+def _is_primed_plan(plan):
+    """One followed segment, then one sampled one: what cmps_{psi,rho}_sample_primed runs in one call."""
+    return [seg[0] for seg in plan] == [FOLLOW, SAMPLE]
+
+
+def _forced_increments(case):
+    """The clip increments the plan's forced steps read [n_audio, scored + followed]."""
+    cols, c = [], 0
+    for kind, skip in SC.expand(case["plan"]):
+        if kind != SAMPLE:
+            c += skip
+            cols.append(c)
+            c += 1
+    clip = np.asarray(case["clip"], dtype=np.float64)
+    return clip[:, [c + 1 for c in cols]] - clip[:, cols]
+
+
+def _stream_records(case, res, r32, r64, floors):
+    """The records every stream family shares: each quantity's distance from the float64 reference against STREAM_FACTOR x the float32
+    reference's own distance plus the family's floor `floors[quantity]`; the totals relative to max(|l|, 1); finiteness."""
+    fam, cfg = case["family"], case["cfg"]
+    S = SC.plan_counts(case["plan"])[0]
+    rec = [(fam, "finite", float(sum(int(np.sum(~np.isfinite(v))) for v in res.values() if isinstance(v, np.ndarray))), 0.0, cfg)]
+    for what in ("out", "pred", "nll"):
+        if r64[what].size:
+            assert res[what].shape == r64[what].shape, (fam, what, res[what].shape, r64[what].shape, cfg)
+            rec.append((fam, what, _dist(res[what], r64[what]), STREAM_FACTOR * _dist(r32[what], r64[what]) + floors[what], cfg))
+    if S:
+        scale = np.maximum(np.abs(r64["total"]), 1.0)
+        own = _amax((r32["total"].astype(np.float64) - r64["total"]) / scale)
+        rec.append((fam, "total", _amax((res["total"].astype(np.float64) - r64["total"]) / scale), max(LOSS_BAR, STREAM_FACTOR * own), cfg))
+    return rec
+
+
+def check_psi_stream(case, res, r32, r64):
+    """Records of one psi_stream draw: `res` (dict(nll, total, pred, out) and, from the kernels, "primed") against the references."""
+    floors = {"out": PSI_OUT_FLOOR * max(1.0, _amax(r64["out"])), "pred": PSI_PRED_FLOOR * _amax(r64["pred"]), "nll": NLL_FLOOR}
+    rec = _stream_records(case, res, r32, r64, floors)
+    if res.get("primed") is not None:                    # tests/test_gpu_stream.py::test_one_call_equals_the_existing_entries, of the pair
+        out_p, pred_p = res["primed"]
+        rec.append(("psi_stream", "primed out", _dist(out_p, res["out"]), PSI_OUT_FLOOR * max(1.0, _amax(r32["out"])), case["cfg"]))
+        rec.append(("psi_stream", "primed pred", _dist(pred_p, res["pred"]),
+                    STREAM_FACTOR * _dist(r32["pred"], r64["pred"]) + PSI_PRED_FLOOR * _amax(r64["pred"]), case["cfg"]))
+    return rec
+
+
+def check_rho_stream(case, res, r32, r64):
+    """Records of one rho_stream draw: `res` (dict(nll, total, pred, out, rho, purity) and, from the kernels, "primed")."""
+    hp, cfg = case["hparams"], case["cfg"]
+    R_fro = float(np.linalg.norm(O.effective_params(hp, case["variables"].astype(np.float64), "f64")[0]))
+    product = RHO_PRODUCT_FLOOR * R_fro                  # the split arithmetics' product error on e at unit trace
+    x_max = _amax(_forced_increments(case)) if r64["pred"].size else 0.0
+    floors = {"out": RHO_OUT_FLOOR * _amax(r64["out"]), "pred": product * hp.delta_t,
+              "nll": NLL_FLOOR + product * x_max / float(case["variables"].A)}
+    rec = _stream_records(case, res, r32, r64, floors)
+    rec.append(("rho_stream", "rho", _dist(res["rho"], r64["rho"]),
+                STREAM_FACTOR * _dist(r32["rho"], r64["rho"]) + RHO_STATE_FLOOR * _amax(r64["rho"]), cfg))
+    allowed = STREAM_FACTOR * _dist(r32["purity"], r64["purity"]) + PURITY_ATOL + PURITY_RTOL * np.abs(r64["purity"])
+    rec.append(("rho_stream", "purity", _amax((res["purity"].astype(np.float64) - r64["purity"]) / allowed), 1.0, cfg))      # (in units of its bar)
+    if res.get("primed") is not None:                    # tests/test_gpu_rho_stream.py::test_one_call_against_the_existing_entries
+        out_p, pred_p = res["primed"]
+        rec.append(("rho_stream", "primed out", _dist(out_p, res["out"]), RHO_OUT_FLOOR * _amax(r32["out"]), cfg))
+        rec.append(("rho_stream", "primed pred", _dist(pred_p, res["pred"]),
+                    STREAM_FACTOR * _dist(r32["pred"], r64["pred"]) + product * hp.delta_t, cfg))
+    return rec
+
+
+def _segments(plan):
+    """(kind, steps, first clip column or None, first noise row or None, k0) of every segment: the clip cursor of tests/_score_ref.py -- an
+    anchored segment starts one column further on, without a step."""
+    c = l0 = k0 = 0
+    for seg in plan:
+        kind, steps, anchored = SC._seg(seg)
+        if kind == SAMPLE:
+            yield kind, steps, None, l0, k0
+            l0 += steps
+        else:
+            c += anchored
+            yield kind, steps, c, None, k0
+            c += steps
+        k0 += steps
+
+
+def _gather(parts, n):
+    return np.concatenate([np.empty((n, 0), np.float32)] + parts, axis=1)
+
+
+def _running_loss(plan, n):
+    """The running loss handed to the first scored segment: not read at k0 = 0 (the NaN pattern proves it), zero behind unscored steps."""
+    return np.full(n, np.nan if plan[0][0] == SCORE else 0.0, np.float32)
+
+
+def run_psi_stream_hip(case):
+    """The plan call by call through HipScan: stream_score for a scored segment, stream with audio for a followed one, stream with noise
+    for a sampled one; the state alternates between two records.  A [follow, sample] plan also goes through sample_primed ("primed")."""
+    from audio_mps_amd import HParams, PsiCMPS
+    from audio_mps_amd.scan import HipScan
+    hp, var, plan, clip, noise, n = (case[k] for k in ("hparams", "variables", "plan", "clip", "noise", "n"))
+    m = PsiCMPS(HParams(**dataclasses.asdict(hp)), seed=0, backend=HipScan(hp.bond_dim, variant=case["variant"]))
+    for k in O.Variables.NAMES:
+        m.variables[k] = np.array(getattr(var, k), dtype=np.float32)
+    be = m._get_backend()
+    be.set_params(m.effective_params(), n, sum(SC.plan_counts(plan)[:3]) + 1, train=False)
+    states = [be.stream_state(n), be.stream_state(n)]
+    cur, loss = None, _running_loss(plan, n)
+    nll, pred, out = [], [], []
+    for idx, (kind, steps, c, l0, k0) in enumerate(_segments(plan)):
+        nxt = states[idx % 2]
+        if kind == SCORE:
+            a, loss, p = be.stream_score(cur, nxt, k0, clip[:, c:c + steps + 1], want_nll=True, want_pred=True, n=n, loss=loss)
+            nll.append(a)
+            pred.append(p)
+        elif kind == FOLLOW:
+            pred.append(be.stream(cur, nxt, k0, clip[:, c:c + steps + 1], None, True, n=n)[1])
+        else:
+            out.append(be.stream(cur, nxt, k0, None, noise[l0:l0 + steps], False, n=n)[0])
+        cur = nxt
+    res = dict(nll=_gather(nll, n), total=loss, pred=_gather(pred, n), out=_gather(out, n))
+    if _is_primed_plan(plan):
+        res["primed"] = be.sample_primed(clip, noise, want_pred=True)
+    return res
+
+
+def run_rho_stream_hip(case):
+    """run_psi_stream_hip for RhoCMPS: rho_stream_score / rho_stream with save_states, and rho_states behind every call."""
+    from audio_mps_amd import HParams, RhoCMPS
+    from audio_mps_amd.scan import HipScan
+    hp, var, plan, clip, noise, n = (case[k] for k in ("hparams", "variables", "plan", "clip", "noise", "n"))
+    D = hp.bond_dim
+    m = RhoCMPS(HParams(**dataclasses.asdict(hp)), seed=0, backend=HipScan(D, variant=case["variant"], rank1=case["options"]["rank1"]))
+    for k, v in (("A", var.A), ("Rx", var.Rx), ("Ry", var.Ry), ("freqs", var.freqs), ("Wx", case["Wx"]), ("Wy", case["Wy"])):
+        m.variables[k] = np.array(v, dtype=np.float32)
+    be = m._get_backend()
+    total = sum(SC.plan_counts(plan)[:3])
+    be.set_params(m.effective_params(), n, total + 1, train=False)
+    be.rho_set_state(m.columns(), n, max(seg[1] for seg in plan) + 1, train=True)       # (stash rows for the longest call only)
+    states = [be.rho_stream_state(n), be.rho_stream_state(n)]
+    cur, loss = None, _running_loss(plan, n)
+    nll, pred, out, rho, pur = [], [], [], [], []
+    for idx, (kind, steps, c, l0, k0) in enumerate(_segments(plan)):
+        nxt = states[idx % 2]
+        if kind == SCORE:
+            a, loss, p = be.rho_stream_score(cur, nxt, k0, clip[:, c:c + steps + 1], want_nll=True, want_pred=True, n=n, loss=loss,
+                                             save_states=True)
+            nll.append(a)
+            pred.append(p)
+        elif kind == FOLLOW:
+            pred.append(be.rho_stream(cur, nxt, k0, clip[:, c:c + steps + 1], None, True, n=n, save_states=True)[1])
+        else:
+            out.append(be.rho_stream(cur, nxt, k0, None, noise[l0:l0 + steps], False, n=n, save_states=True)[0])
+        r, p = be.rho_states(n, steps, want_rho=True, want_purity=True)
+        rho.append(r)
+        pur.append(p)
+        cur = nxt
+    res = dict(nll=_gather(nll, n), total=loss, pred=_gather(pred, n), out=_gather(out, n), rho=np.concatenate(rho, axis=1),
+               purity=np.concatenate(pur, axis=1))
+    if _is_primed_plan(plan):
+        be.rho_set_state(m.columns(), n, total + 1, train=False)
+        res["primed"] = be.rho_sample_primed(clip, noise, want_pred=True)
+    return res
+
+
+def _sweep_stream(draw, reference, run, check, rng, n, out):
+    for it in range(n):
+        case = draw(rng, it)
+        r32, r64 = reference(case, "f32"), reference(case, "f64")
+        if not (all_finite(r32) and all_finite(r64)):
+            continue                                       # (1 + z <= 0 somewhere: the model itself diverges on this draw, as in sweep_psi)
+        out += check(case, run(case), r32, r64)
+
+
+def sweep_psi_stream(rng, n, out):
+    """k_sample_wave / k_sample_wide / k_sample_block in their stream, score and primed modes vs the plan composition (tests/_score_ref.py)."""
+    _sweep_stream(draw_psi_stream, reference_psi_stream, run_psi_stream_hip, check_psi_stream, rng, n, out)
+
+
+def sweep_rho_stream(rng, n, out):
+    """k_sample_rho_mfma / k_sample_rho in the same modes, k_states_rho behind them, vs tests/_rho_score_ref.py."""
+    _sweep_stream(draw_rho_stream, reference_rho_stream, run_rho_stream_hip, check_rho_stream, rng, n, out)
+
+
+FAMILIES = {"psi": sweep_psi, "wide": sweep_wide, "step": sweep_step, "pair": sweep_pair, "rho": sweep_rho, "legacy": sweep_legacy,
+            "psi_stream": sweep_psi_stream, "rho_stream": sweep_rho_stream}
 
 
 def run_sweep(seed, counts=None, families=None):
