@@ -5,6 +5,8 @@ from __future__ import annotations
 import ctypes
 import os
 
+import numpy as np
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CMPS_LIB") or os.path.join(_HERE, "lib", "libcmps.so")   # CMPS_LIB: diagnostic builds
 
@@ -57,8 +59,14 @@ SYMBOLS = (
     "cmps_legacy_set_params", "cmps_legacy_loss_fwd", "cmps_legacy_loss_bwd",
     "cmps_rho_workspace_bytes", "cmps_rho_set_state", "cmps_rho_loss_fwd", "cmps_rho_loss_bwd",
     "cmps_rho_update_ancilla", "cmps_rho_sample", "cmps_rho_sample_primed", "cmps_rho_stream_state_bytes", "cmps_rho_stream", "cmps_rho_stream_score", "cmps_rho_states",
-    "cmps_rho_apply_step_scratch_bytes", "cmps_rho_apply_step", "cmps_noise_fill", "cmps_batch_gather", "cmps_damped_sine_fill", "cmps_crc32c",
+    "cmps_rho_apply_step_scratch_bytes", "cmps_rho_apply_step", "cmps_noise_fill", "cmps_batch_gather", "cmps_batch_gather_i16", "cmps_loss_stats", "cmps_damped_sine_fill", "cmps_crc32c",
 )
+
+
+# the 64-byte record of cmps_loss_stats (include/cmps.h: cmps_loss_stats_rec), little-endian
+LOSS_STATS = np.dtype([("sum", "<f8"), ("sumsq", "<f8"), ("n_finite", "<i8"), ("n_nonfinite", "<i8"), ("argmin", "<i8"), ("argmax", "<i8"),
+                       ("first_nonfinite", "<i8"), ("min", "<f4"), ("max", "<f4")])
+assert LOSS_STATS.itemsize == 64
 
 
 class CmpsError(RuntimeError):
@@ -157,6 +165,10 @@ def _declare(lib):
     lib.cmps_noise_fill.restype = c_int
     lib.cmps_batch_gather.argtypes = [vp, vp, ctypes.c_longlong, ctypes.c_longlong, vp, vp, c_int, c_int, vp, vp]
     lib.cmps_batch_gather.restype = c_int
+    lib.cmps_batch_gather_i16.argtypes = [vp, vp, ctypes.c_longlong, ctypes.c_longlong, vp, vp, c_int, c_int, c_float, vp, vp]
+    lib.cmps_batch_gather_i16.restype = c_int
+    lib.cmps_loss_stats.argtypes = [vp, vp, c_int, ctypes.c_longlong, c_int, vp, vp]
+    lib.cmps_loss_stats.restype = c_int
     lib.cmps_damped_sine_fill.argtypes = [vp, ctypes.c_ulonglong, ctypes.c_ulonglong, c_int, c_int, c_double, vp, vp]
     lib.cmps_damped_sine_fill.restype = c_int
     lib.cmps_crc32c.argtypes = [ctypes.c_char_p, c_size_t, ctypes.c_uint]

@@ -698,6 +698,42 @@ int cmps_batch_gather(cmps_handle_t h, const float* data_dev, long long n_clips,
     return CMPS_OK;
 }
 
+int cmps_batch_gather_i16(cmps_handle_t h, const short* data_dev, long long n_clips, long long clip_len, const int* index_dev,
+                          const int* offset_dev, int B, int T, float scale, float* audio_dev, void* stream) {
+    if (!h) return CMPS_ERR_BAD_ARG;
+    if (!data_dev) return fail(h, CMPS_ERR_BAD_ARG, "cmps_batch_gather_i16: data_dev is a null pointer");
+    if (!index_dev) return fail(h, CMPS_ERR_BAD_ARG, "cmps_batch_gather_i16: index_dev is a null pointer");
+    if (!audio_dev) return fail(h, CMPS_ERR_BAD_ARG, "cmps_batch_gather_i16: audio_dev is a null pointer");
+    if (B < 1 || T < 1) return fail(h, CMPS_ERR_BAD_ARG, "cmps_batch_gather_i16: need B >= 1 and T >= 1");
+    if (n_clips < 1 || n_clips > 2147483647ll)
+        return fail(h, CMPS_ERR_BAD_ARG, "cmps_batch_gather_i16: need 1 <= n_clips <= 2^31 - 1 (an index is a 32-bit int)");
+    if (clip_len < (long long)T) return fail(h, CMPS_ERR_BAD_ARG, "cmps_batch_gather_i16: clip_len must be at least T");
+    if (!std::isfinite(scale) || !(scale > 0.0f)) return fail(h, CMPS_ERR_BAD_ARG, "cmps_batch_gather_i16: scale must be finite and positive");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    KBind kb(h);
+    KScope ks("k_batch_gather_i16", s);
+    const hipError_t e = launch_batch_gather_i16(data_dev, n_clips, clip_len, index_dev, offset_dev, B, T, scale, audio_dev, s);
+    if (e != hipSuccess) return fail_hip(h, e, "cmps_batch_gather_i16");
+    return CMPS_OK;
+}
+
+// The per-clip losses of an evaluation pass folded into one record on the device: needs nothing of the handle either
+int cmps_loss_stats(cmps_handle_t h, const float* loss_dev, int B, long long first_id, int reset, void* stats_dev, void* stream) {
+    if (!h) return CMPS_ERR_BAD_ARG;
+    if (!loss_dev) return fail(h, CMPS_ERR_BAD_ARG, "cmps_loss_stats: loss_dev is a null pointer");
+    if (!stats_dev) return fail(h, CMPS_ERR_BAD_ARG, "cmps_loss_stats: stats_dev is a null pointer");
+    if (((uintptr_t)stats_dev & 7) != 0) return fail(h, CMPS_ERR_BAD_ARG, "cmps_loss_stats: stats_dev must be 8-byte aligned");
+    if (B < 1) return fail(h, CMPS_ERR_BAD_ARG, "cmps_loss_stats: need B >= 1");
+    if (first_id < 0 || first_id > 9223372036854775807ll - (long long)B)
+        return fail(h, CMPS_ERR_BAD_ARG, "cmps_loss_stats: need first_id >= 0 and first_id + B below 2^63 (an id is a signed 64-bit integer)");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    KBind kb(h);
+    KScope ks("k_loss_stats", s);
+    const hipError_t e = launch_loss_stats(loss_dev, B, first_id, reset, stats_dev, s);
+    if (e != hipSuccess) return fail_hip(h, e, "cmps_loss_stats");
+    return CMPS_OK;
+}
+
 int cmps_damped_sine_fill(cmps_handle_t h, unsigned long long seed, unsigned long long first_clip, int B, int T, double delta_t,
                           float* audio_dev, void* stream) {
     if (!h) return CMPS_ERR_BAD_ARG;

@@ -446,6 +446,11 @@ hipError_t launch_noise_philox(unsigned long long seed, unsigned long long first
 hipError_t launch_batch_gather(const float* data, long long n_clips, long long clip_len, const int* index, const int* offset, int B, int T,
                                float* audio, hipStream_t s);
 hipError_t launch_damped_sine(unsigned long long seed, unsigned long long first_clip, int B, int T, double delta_t, float* audio, hipStream_t s);
+// ... and the gather out of an int16 dataset: audio[b * T + j] = (float)data[...] * scale
+hipError_t launch_batch_gather_i16(const short* data, long long n_clips, long long clip_len, const int* index, const int* offset, int B, int T,
+                                   float scale, float* audio, hipStream_t s);
+// cmps_eval.hip: loss[0 .. B), clip ids first_id + b, folded into the 64-byte record of include/cmps.h (reset: in place of what it held)
+hipError_t launch_loss_stats(const float* loss, int B, long long first_id, int reset, void* stats, hipStream_t s);
 // floats of one path's stream record (StreamDev::rec), a multiple of 4: wave u, |y|^2 partial per lane, running sum | wide ut [2 DP], |y|^2
 // partial per wave [DP / 16], running sum | block u [2 D], running sum
 constexpr int STREAM_REC_WAVE = 132;

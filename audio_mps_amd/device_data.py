@@ -1,6 +1,7 @@
 """The input of a training step produced on the device (``--device_data``): the batch no longer comes from the host every step.
 
-  ResidentDataset    a TFRecord dataset uploaded ONCE, [N, L] float32 in device memory; every batch is then a row gather
+  ResidentDataset    a TFRecord dataset uploaded ONCE, [N, L] float32 (or, for 16-bit PCM data, int16: storage=) in device memory; every
+                     batch is then a row gather
                      (HipScan.gather_batch, cmps_batch_gather) driven by an index plan.  The plan is the reference's pipeline
                      (data.py:37-40 batch -> shuffle(24) -> repeat; training_estimators.py:92 shuffle(24) -> repeat -> batch) run on
                      clip INDICES: tfrecord._shuffle draws from its Generator by the buffer's length alone, so fed indices and the
@@ -34,16 +35,52 @@ def _device(backend):
     return dev if dev is not None else torch.device("cpu")
 
 
-class ResidentDataset:
-    """``clips`` [N, L] float32 (host array or tensor) held on the backend's device."""
+PCM_SCALE = 2.0 ** -15                 # int16 storage: sample = i * 2^-15, the float32 value of 16-bit PCM (x = i / 32768)
+STORAGES = ("float32", "int16", "auto")
 
-    def __init__(self, clips, backend):
+
+def _as_pcm16(t: torch.Tensor):
+    """``t`` float32 [n, L] -> (int16 tensor i with float32(i) * 2^-15 equal to ``t`` BIT FOR BIT, None), or (None, flat position of the
+    first sample no i in [-32768, 32767] reproduces): a sample off the grid, one outside [-1, 1 - 2^-15], a NaN -- or a -0.0, which would
+    come back as +0.0."""
+    i = torch.nan_to_num(t * 32768.0, nan=0.0, posinf=32767.0, neginf=-32768.0).clamp_(-32768.0, 32767.0).to(torch.int16)
+    bad = (i.to(torch.float32) * PCM_SCALE).view(torch.int32) != t.view(torch.int32)
+    if bool(bad.any()):
+        return None, int(torch.nonzero(bad.reshape(-1))[0])
+    return i, None
+
+
+def _not_pcm16(first_clip: int, flat: int, L: int, value) -> ValueError:
+    return ValueError(f"storage='int16' needs every sample to equal i * 2^-15 bit for bit with i in [-32768, 32767]: clip "
+                      f"{first_clip + flat // L}, sample {flat % L} holds {float(value)!r}")
+
+
+class ResidentDataset:
+    """``clips`` [N, L] float32 (host array or tensor) held on the backend's device.  ``storage``: "float32" (the default) holds them as
+    they are; "int16" holds 16-bit PCM data as int16, half the memory, widened by the gather (cmps_batch_gather_i16) without changing a bit
+    of any batch -- allowed only where i * 2^-15 reproduces every sample bit for bit, else a ValueError naming the first offending clip and
+    sample; "auto" takes int16 where that holds and float32 otherwise.  (An int16 tensor is taken as PCM as it is.)"""
+
+    def __init__(self, clips, backend, storage: str = "float32"):
         _need(backend, "gather_batch", "ResidentDataset")
+        if storage not in STORAGES:
+            raise ValueError(f"storage must be one of {STORAGES}, not {storage!r}")
         self.backend = backend
-        t = clips if isinstance(clips, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(clips, dtype=np.float32))
+        t = clips if isinstance(clips, torch.Tensor) else torch.from_numpy(
+            np.ascontiguousarray(clips, dtype=None if np.asarray(clips).dtype == np.int16 else np.float32))
         if t.dim() != 2 or t.shape[0] < 1 or t.shape[1] < 1:
             raise ValueError("ResidentDataset needs clips [N, L] with N >= 1 and L >= 1")
-        self.clips = t.to(device=_device(backend), dtype=torch.float32).contiguous()
+        if t.dtype == torch.int16:
+            if storage == "float32":
+                t = t.to(torch.float32) * PCM_SCALE
+        else:
+            t = t.to(dtype=torch.float32)
+            if storage != "float32":
+                i, bad = _as_pcm16(t.contiguous())
+                if i is None and storage == "int16":
+                    raise _not_pcm16(0, bad, int(t.shape[1]), t.reshape(-1)[bad])
+                t = t if i is None else i
+        self.clips = t.to(device=_device(backend)).contiguous()
 
     @property
     def n_clips(self) -> int:
@@ -53,27 +90,74 @@ class ResidentDataset:
     def clip_len(self) -> int:
         return int(self.clips.shape[1])
 
+    @property
+    def storage(self) -> str:
+        """"int16" or "float32": how the clips are held."""
+        return "int16" if self.clips.dtype == torch.int16 else "float32"
+
+    @property
+    def nbytes(self) -> int:
+        """Device memory the clips occupy."""
+        return int(self.clips.numel() * self.clips.element_size())
+
+    def gather(self, index: torch.Tensor, offset: Optional[torch.Tensor] = None, T: Optional[int] = None) -> torch.Tensor:
+        """Rows ``index`` (cut at ``offset``, to ``T`` samples) as a float32 batch on the device, from either storage."""
+        if self.clips.dtype == torch.int16:
+            return self.backend.gather_batch(self.clips, index, offset, T=T, scale=PCM_SCALE)
+        return self.backend.gather_batch(self.clips, index, offset, T=T)
+
     @classmethod
-    def from_tfrecord(cls, path: str, sample_duration: int, backend, verify: bool = False) -> "ResidentDataset":
+    def from_tfrecord(cls, path: str, sample_duration: int, backend, verify: bool = False, storage: str = "float32") -> "ResidentDataset":
         """Reads the file once (tfrecord._audio_records: every record's "audio" must hold ``sample_duration`` values) and uploads it in
-        chunks; the chunks are joined on the device, so twice the dataset is allocated for a moment at the end."""
+        chunks; the chunks are joined on the device, so twice the dataset is allocated for a moment at the end.  ``storage`` is decided
+        and converted per chunk, on the host, so an int16 dataset is uploaded as int16; the first chunk that fails under "auto" converts
+        the chunks already stored back to float32, once."""
         _need(backend, "gather_batch", "ResidentDataset")
+        if storage not in STORAGES:
+            raise ValueError(f"storage must be one of {STORAGES}, not {storage!r}")
         dev = _device(backend)
-        per_chunk = max(1, UPLOAD_CLIPS_BYTES // (4 * int(sample_duration)))
+        L = int(sample_duration)
+        per_chunk = max(1, UPLOAD_CLIPS_BYTES // (4 * L))
         chunks, cur = [], []
+        state = {"pcm": storage != "float32", "seen": 0}
 
         def flush():
-            if cur:
-                chunks.append(torch.from_numpy(np.stack(cur)).to(dev))
-                cur.clear()
-        for a in tfrecord._audio_records(path, int(sample_duration), verify):
+            if not cur:
+                return
+            t = torch.from_numpy(np.stack(cur))
+            if state["pcm"]:
+                i, bad = _as_pcm16(t)
+                if i is None and storage == "int16":
+                    raise _not_pcm16(state["seen"], bad, L, t.reshape(-1)[bad])
+                if i is None:                                   # "auto": float32 from here on, and for what is already there
+                    state["pcm"] = False
+                    chunks[:] = [c.to(torch.float32) * PCM_SCALE for c in chunks]
+                else:
+                    t = i
+            chunks.append(t.to(dev))
+            state["seen"] += len(cur)
+            cur.clear()
+        for a in tfrecord._audio_records(path, L, verify):
             cur.append(a)
             if len(cur) == per_chunk:
                 flush()
         flush()
         if not chunks:
             raise ValueError(f"{path}: no records")
-        return cls(chunks[0] if len(chunks) == 1 else torch.cat(chunks), backend)
+        return cls(chunks[0] if len(chunks) == 1 else torch.cat(chunks), backend, storage="int16" if state["pcm"] else "float32")
+
+    def ordered(self, minibatch_size: int, T: Optional[int] = None):
+        """Every clip once, in file order: yields (first_id, batch [B, T] on the device) with B = ``minibatch_size`` but for the short last
+        batch, which is kept.  ``T < L`` takes the first T samples of every clip.  The plan (the clip numbers) is uploaded once."""
+        mb, N, L = int(minibatch_size), self.n_clips, self.clip_len
+        if mb < 1:
+            raise ValueError("ordered needs minibatch_size >= 1")
+        T = L if T is None else int(T)
+        if not 1 <= T <= L:
+            raise ValueError(f"T must lie in [1, {L}] (the clips' length), not {T}")
+        plan = torch.arange(N, dtype=torch.int32).to(self.clips.device)
+        for first in range(0, N, mb):
+            yield first, self.gather(plan[first:first + mb], None, T)
 
     def batches(self, minibatch_size: int, seed: int = 0, order: str = "data", shuffle_buffer: int = 24, crop: Optional[int] = None,
                 crop_seed: int = 0) -> "BatchStream":
@@ -154,7 +238,7 @@ class BatchStream:
             return torch.empty((0, self.T), dtype=torch.float32, device=self.ds.clips.device)
         index = self._plan[0, at + lo:at + hi]
         offset = self._plan[1, at + lo:at + hi] if self._crop else None
-        return self.ds.backend.gather_batch(self.ds.clips, index, offset, T=self.T)
+        return self.ds.gather(index, offset, self.T)
 
 
 class DampedSineSource:

@@ -1,0 +1,140 @@
+"""Held-out evaluation: the loss of a model over a dataset it has not seen, reduced on the device.
+
+  reference          training_estimators.py:70-74   eval_metric_ops={"loss": tf.metrics.mean(loss)} -- declared, never run
+  evaluate(...)      a pass over a ResidentDataset in file order (ResidentDataset.ordered): every batch runs the model's own forward scan
+                     (what loss_per_clip runs: cmps_psi_loss_fwd / cmps_rho_loss_fwd / cmps_legacy_loss_fwd), its per-clip losses are folded
+                     into one 64-byte record where they are (HipScan.loss_stats, cmps_loss_stats), and the record is downloaded ONCE at the
+                     end -- not one download per batch, as model.loss_per_clip makes.
+  EvalResult         the mean the reference declares, and what a bare mean hides: how many clips came out non-finite (1 + z <= 0,
+                     model.py:294) and which was the first, the worst and the best clip, the spread.
+
+A clip's id is its position in the dataset's file.  Needs a backend with loss_stats; one without it (the stand-ins of the host tests that
+lack it) is a ValueError, as with draw_noise and gather_batch.
+Run:  python -m audio_mps_amd.evaluate --modeldir=LOGDIR --datadir=DIR --dataset=nsynth_valid --sample_duration=16000 --storage=auto
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import math
+import os
+from dataclasses import dataclass, fields
+from typing import Callable, Optional
+
+import numpy as np
+
+
+@dataclass
+class EvalResult:
+    mean: float                    # sum / n_finite: the mean loss per clip over the finite ones (NaN while there is none)
+    per_sample: float              # mean / (T - 1): per scored sample, the figure that compares runs of different T
+    std: float                     # unbiased standard deviation of the finite losses (0 below two of them)
+    sem: float                     # std / sqrt(n_finite)
+    n_clips: int                   # clips evaluated, finite or not
+    n_nonfinite: int
+    first_nonfinite: int           # id of the first clip whose loss is NaN or +-Inf, -1 when there is none
+    min: float
+    max: float
+    argmin: int                    # id of the clip with the smallest finite loss (lowest id on ties), -1 when there is none
+    argmax: int
+    T: int
+    losses: Optional[np.ndarray] = None        # keep_losses: float32 [n_clips], in the dataset's order
+
+    @classmethod
+    def from_stats(cls, stats: dict, T: int, losses: Optional[np.ndarray] = None) -> "EvalResult":
+        """From the record of cmps_loss_stats (HipScan.read_stats).  The variance is (sumsq - sum^2 / n) / (n - 1) in float64, clamped at 0
+        (the difference of two rounded sums can come out a hair negative for equal losses)."""
+        n, s, q = int(stats["n_finite"]), float(stats["sum"]), float(stats["sumsq"])
+        mean = s / n if n else float("nan")
+        var = max((q - s * s / n) / (n - 1), 0.0) if n > 1 else 0.0
+        std = math.sqrt(var)
+        return cls(mean=mean, per_sample=mean / (T - 1) if T > 1 else float("nan"), std=std, sem=std / math.sqrt(n) if n else float("nan"),
+                   n_clips=n + int(stats["n_nonfinite"]), n_nonfinite=int(stats["n_nonfinite"]), first_nonfinite=int(stats["first_nonfinite"]),
+                   min=float(stats["min"]), max=float(stats["max"]), argmin=int(stats["argmin"]), argmax=int(stats["argmax"]), T=int(T),
+                   losses=losses)
+
+    def scalars(self) -> dict:
+        """Everything but ``losses``, as JSON takes it."""
+        return {f.name: getattr(self, f.name) for f in fields(self) if f.name != "losses"}
+
+
+def _need_stats(backend):
+    if not (hasattr(backend, "loss_stats") and hasattr(backend, "read_stats")):
+        raise ValueError(f"evaluate needs a backend that reduces the per-clip losses on the device (loss_stats): {type(backend).__name__} "
+                         "has none")
+
+
+def run_pass(batches, forward: Callable, backend, T: int, keep_losses: bool = False) -> EvalResult:
+    """The loop of `evaluate` over ``batches`` (an iterable of (first_id, batch)) with ``forward(batch)`` -> per-clip losses on the device:
+    one loss_stats per batch, ONE download at the end (two with keep_losses: the record and the concatenated losses)."""
+    import torch
+    _need_stats(backend)
+    stats, kept = None, []
+    for first_id, batch in batches:
+        loss = forward(batch)
+        stats = backend.loss_stats(loss, first_id, stats, reset=stats is None)
+        if keep_losses:
+            kept.append(loss.clone())              # (the backend's loss tensor is overwritten by the next forward)
+    if stats is None:
+        raise ValueError("evaluate: the dataset yielded no batch")
+    losses = torch.cat(kept).cpu().numpy() if keep_losses else None
+    return EvalResult.from_stats(backend.read_stats(stats), T, losses)
+
+
+def evaluate(model, dataset, minibatch_size: int, T: Optional[int] = None, keep_losses: bool = False) -> EvalResult:
+    """The model's loss over every clip of ``dataset`` (a ResidentDataset of either storage) once, in file order, in batches of
+    ``minibatch_size`` (the short last batch included); ``T < L`` scores the first T samples of every clip.  The parameters are uploaded
+    once, every batch then costs a gather, the forward scan and the 64-byte update; ``keep_losses`` also brings the per-clip losses back."""
+    T = dataset.clip_len if T is None else int(T)
+    if T < 2:
+        raise ValueError("evaluate needs T >= 2 (one increment)")
+    be = model._get_backend()
+    _need_stats(be)
+    B_max = min(int(minibatch_size), dataset.n_clips)
+    be = model._prepare(B_max, T, train=False)
+    fwd = model._forward_entry(be)
+    return run_pass(dataset.ordered(minibatch_size, T), lambda batch: fwd(batch, save_for_bwd=False), be, T, keep_losses)
+
+
+def build_parser():
+    p = argparse.ArgumentParser(description="Evaluate a trained PsiCMPS or RhoCMPS on a held-out TFRecord dataset (MI355X)")
+    p.add_argument("--modeldir", default="./data", help="directory holding model.ckpt.npz, or a checkpoint file (either model)")
+    p.add_argument("--datadir", default="./data")
+    p.add_argument("--dataset", required=True, help="NAME of NAME.tfrecords in --datadir")
+    p.add_argument("--sample_duration", type=int, default=2 ** 16, help="samples per record; the model scores all of them")
+    p.add_argument("--sample_rate", type=int, default=16000)
+    p.add_argument("--minibatch_size", type=int, default=64)
+    p.add_argument("--storage", default="auto", choices=["float32", "int16", "auto"],
+                   help="how the dataset is held on the device: int16 halves the memory of 16-bit PCM data without changing a bit")
+    p.add_argument("--per_clip", default=None, metavar="OUT.npy", help="also write the per-clip losses, float32 [clips], in file order")
+    p.add_argument("--hparams", default="", help="as for training (r_reg, h_reg, sigma, delta_t must be the training run's)")
+    p.add_argument("--kernel_variant", type=int, default=0, help="as in audio_mps_amd.train")
+    p.add_argument("--json", action="store_true", help="print the result as one JSON line as well")
+    return p
+
+
+def main(argv=None, backend=None) -> EvalResult:
+    """``backend``: a scan backend to use instead of HipScan (CPU tests of the host logic inject one)."""
+    from .device_data import ResidentDataset
+    from .sample import build_model, load_variables
+    args = build_parser().parse_args(argv)
+    if args.sample_duration < 2 or args.minibatch_size < 1:
+        raise ValueError("--sample_duration must be at least 2 and --minibatch_size positive")
+    model = build_model(load_variables(args.modeldir), args.sample_rate, args.hparams, args.kernel_variant, 0, backend)
+    path = os.path.join(str(args.datadir), f"{args.dataset}.tfrecords")
+    if not os.path.exists(path):
+        raise FileNotFoundError(path)
+    ds = ResidentDataset.from_tfrecord(path, args.sample_duration, model._get_backend(), storage=args.storage)
+    res = evaluate(model, ds, args.minibatch_size, keep_losses=args.per_clip is not None)
+    if args.per_clip is not None:
+        np.save(args.per_clip, res.losses)
+    print(f"eval {args.dataset}: loss={res.mean:.6f} per_sample={res.per_sample:.6g} std={res.std:.6g} sem={res.sem:.6g} "
+          f"clips={res.n_clips} nonfinite={res.n_nonfinite} min={res.min:.6g} (clip {res.argmin}) max={res.max:.6g} (clip {res.argmax}) "
+          f"storage={ds.storage}")
+    if args.json:
+        print(json.dumps({"dataset": args.dataset, "storage": ds.storage, **res.scalars()}))
+    return res
+
+
+if __name__ == "__main__":
+    main()

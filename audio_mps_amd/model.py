@@ -84,7 +84,8 @@ def _normalize_psi_host(p: np.ndarray) -> np.ndarray:
 # --------------------------------------------------------------------------------------------------
 class _ScanModel:
     """What every model class needs to run a scan on its backend.  Expects ``bond_d``, ``data_iterator``, ``_backend``, ``_last`` and
-    the subclass's ``_prepare(B, T, train)`` (upload the parameters, return the backend), ``grad_sums`` and ``chain_rule``."""
+    the subclass's ``_prepare(B, T, train)`` (upload the parameters, return the backend), ``_forward_entry(be)`` (the backend's forward
+    scan for this model), ``grad_sums`` and ``chain_rule``."""
 
     def _get_backend(self):
         if self._backend is None:
@@ -115,6 +116,12 @@ class _ScanModel:
         audio = self._to_device(self._batch(data))
         B, T = audio.shape
         return self._prepare(B, T, train), audio, B, T
+
+    def loss_per_clip_dev(self, data=None):
+        """``loss_per_clip`` left where the scan wrote it: the backend's per-clip loss tensor [B] (forward only; the next forward
+        overwrites it).  What an evaluation pass reduces on the device (audio_mps_amd/evaluate.py)."""
+        be, audio, _, _ = self._scan(data, train=False)
+        return self._forward_entry(be)(audio, save_for_bwd=False)
 
     def loss_and_grads(self, data=None, with_reg: bool = False):
         """(loss, {variable: gradient}) of mean_b loss_b (+ train.py's regularisers if with_reg): what
@@ -434,8 +441,10 @@ class PsiCMPS(CMPS):
     # ---- the hot path ----
     def loss_per_clip(self, data=None) -> np.ndarray:
         """The fold carry ``loss`` [B] of model.py:265-266 (forward only)."""
-        be, audio, _, _ = self._scan(data, train=False)
-        return be.forward(audio, save_for_bwd=False).detach().cpu().numpy()
+        return self.loss_per_clip_dev(data).detach().cpu().numpy()
+
+    def _forward_entry(self, be):
+        return be.forward
 
     def flat_size(self) -> int:
         """Length of the buffer grad_sums() returns (cmps_psi_loss_bwd's layout): what an empty shard adds to the all-reduce as zeros."""
@@ -574,8 +583,10 @@ class RhoCMPS(CMPS):
 
     # ---- the scan ----
     def loss_per_clip(self, data=None) -> np.ndarray:
-        be, audio, _, _ = self._scan(data, train=False)
-        return be.rho_forward(audio, save_for_bwd=False).detach().cpu().numpy()
+        return self.loss_per_clip_dev(data).detach().cpu().numpy()
+
+    def _forward_entry(self, be):
+        return be.rho_forward
 
     def flat_size(self) -> int:
         """Length of the buffer grad_sums() returns: the pure-state layout followed by the 2 rank D column cotangents
@@ -723,8 +734,10 @@ class LegacyAudioMPS(_ScanModel):
         return be
 
     def loss_per_clip(self, data=None) -> np.ndarray:
-        be, audio, _, _ = self._scan(data, train=False)
-        return be.legacy_forward(audio).detach().cpu().numpy()
+        return self.loss_per_clip_dev(data).detach().cpu().numpy()
+
+    def _forward_entry(self, be):
+        return be.legacy_forward
 
     @property
     def loss(self) -> np.float32:

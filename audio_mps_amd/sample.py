@@ -138,30 +138,36 @@ def _scored(model, args):
     return nll
 
 
+def build_model(variables: dict, sample_rate: int, hparams: str = "", kernel_variant: int = 0, seed: int = 0, backend=None):
+    """The model a checkpoint's ``variables`` (load_variables) belong to, holding them: RhoCMPS where they include Wx / Wy, else PsiCMPS;
+    bond_dim and initial_rank are read from their shapes, the other hyper-parameters are train.main's defaults overridden by ``hparams``."""
+    rho = "Wx" in variables and "Wy" in variables             # a RhoCMPS checkpoint (train.py --mps_model rho_mps)
+    if not rho and "psi_x" not in variables:
+        raise ValueError("the checkpoint holds neither psi_x (PsiCMPS) nor Wx / Wy (RhoCMPS)")
+    hp = HParams(delta_t=1.0 / sample_rate, h_reg=200.0 / (math.pi * sample_rate) ** 2)       # train.py:41-43
+    if rho:
+        hp.initial_rank, hp.bond_dim = (int(x) for x in variables["Wx"].shape)
+    else:
+        hp.bond_dim = int(variables["psi_x"].shape[0])
+    hp.parse(hparams)
+    if backend is None:
+        from .scan import HipScan
+        backend = HipScan(hp.bond_dim, variant=kernel_variant)
+    model = (RhoCMPS if rho else PsiCMPS)(hp, seed=seed, backend=backend)
+    for k in model.variables:
+        if variables[k].shape != model.variables[k].shape:
+            raise ValueError(f"checkpoint variable {k} has shape {variables[k].shape}, bond_dim={hp.bond_dim} needs {model.variables[k].shape}")
+        model.variables[k] = variables[k]
+    return model
+
+
 def main(argv=None, backend=None):
     """Returns the waveforms [num_samples, samples] it wrote.  ``backend``: a scan backend to use instead of HipScan (CPU tests of the
     host logic inject one; the product always builds a HipScan and fails loudly without a GPU)."""
     args = build_parser().parse_args(argv)
     if args.sample_duration < 1 or args.num_samples < 1:
         raise ValueError("--sample_duration and --num_samples must be positive")
-    variables = load_variables(args.modeldir)
-    rho = "Wx" in variables and "Wy" in variables             # a RhoCMPS checkpoint (train.py --mps_model rho_mps)
-    if not rho and "psi_x" not in variables:
-        raise ValueError("the checkpoint holds neither psi_x (PsiCMPS) nor Wx / Wy (RhoCMPS)")
-    hp = HParams(delta_t=1.0 / args.sample_rate, h_reg=200.0 / (math.pi * args.sample_rate) ** 2)       # train.py:41-43
-    if rho:
-        hp.initial_rank, hp.bond_dim = (int(x) for x in variables["Wx"].shape)
-    else:
-        hp.bond_dim = int(variables["psi_x"].shape[0])
-    hp.parse(args.hparams)
-    if backend is None:
-        from .scan import HipScan
-        backend = HipScan(hp.bond_dim, variant=args.kernel_variant)
-    model = (RhoCMPS if rho else PsiCMPS)(hp, seed=args.seed, backend=backend)
-    for k in model.variables:
-        if variables[k].shape != model.variables[k].shape:
-            raise ValueError(f"checkpoint variable {k} has shape {variables[k].shape}, bond_dim={hp.bond_dim} needs {model.variables[k].shape}")
-        model.variables[k] = variables[k]
+    model = build_model(load_variables(args.modeldir), args.sample_rate, args.hparams, args.kernel_variant, args.seed, backend)
     n, length = args.num_samples, args.sample_duration
     if args.segment is not None and args.segment < 1:
         raise ValueError("--segment must be positive")

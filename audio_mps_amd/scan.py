@@ -125,7 +125,7 @@ class HipScan:
         return mode if mode in (_capi.CMPS_RANK1_EXACT_F32, _capi.CMPS_RANK1_BF16X2, _capi.CMPS_RANK1_F16X2) else _capi.CMPS_RANK1_BF16X3
 
     def kernel_events(self, on: bool):
-        """cmps_set_option(CMPS_OPT_KERNEL_EVENTS): bracket every kernel of forward() / backward() and of sample() / sample_primed() / stream() / stream_score() / rho_sample_primed() / rho_stream() / rho_stream_score() / draw_noise() / gather_batch() / damped_sine() with HIP
+        """cmps_set_option(CMPS_OPT_KERNEL_EVENTS): bracket every kernel of forward() / backward() and of sample() / sample_primed() / stream() / stream_score() / rho_sample_primed() / rho_stream() / rho_stream_score() / draw_noise() / gather_batch() / loss_stats() / damped_sine() with HIP
         events (a measurement aid, used by bench.py outside its timed region)."""
         _capi.check(self._h, self._lib.cmps_set_option(self._h, _capi.CMPS_OPT_KERNEL_EVENTS, 1 if on else 0))
 
@@ -367,15 +367,17 @@ class HipScan:
                                                        out.data_ptr(), self._stream()))
         return out
 
-    def gather_batch(self, data: torch.Tensor, index: torch.Tensor, offset: Optional[torch.Tensor] = None, T: Optional[int] = None) -> torch.Tensor:
+    def gather_batch(self, data: torch.Tensor, index: torch.Tensor, offset: Optional[torch.Tensor] = None, T: Optional[int] = None,
+                     scale: float = 2.0 ** -15) -> torch.Tensor:
         """cmps_batch_gather: a batch cut out of a dataset that lives on the device.  ``data`` float32 [N, L], ``index`` (and ``offset``,
         default all zero) int32 [B], all contiguous on this device; returns float32 [B, T] (T defaults to L) with row b =
         data[index[b], offset[b] : offset[b] + T] -- or T quiet NaNs where index[b] or offset[b] is out of range.  No host copy, no
-        synchronisation."""
+        synchronisation.  ``data`` int16 [N, L] goes to cmps_batch_gather_i16 instead: row b = float32(data[...]) * ``scale``."""
         def ok(t, dtype, dim):
             return isinstance(t, torch.Tensor) and t.device == self.device and t.dtype == dtype and t.dim() == dim and t.is_contiguous()
-        if not ok(data, torch.float32, 2):
-            raise ValueError("gather_batch: data must be a contiguous float32 tensor [N, L] on the backend's device")
+        i16 = isinstance(data, torch.Tensor) and data.dtype == torch.int16
+        if not ok(data, torch.int16 if i16 else torch.float32, 2):
+            raise ValueError("gather_batch: data must be a contiguous float32 or int16 tensor [N, L] on the backend's device")
         if not ok(index, torch.int32, 1) or (offset is not None and (not ok(offset, torch.int32, 1) or offset.shape != index.shape)):
             raise ValueError("gather_batch: index (and offset) must be contiguous int32 tensors [B] on the backend's device")
         N, L = int(data.shape[0]), int(data.shape[1])
@@ -383,10 +385,36 @@ class HipScan:
         out = torch.empty((B, T), dtype=torch.float32, device=self.device)
         if B == 0:
             return out
-        _capi.check(self._h, self._lib.cmps_batch_gather(self._h, data.data_ptr(), N, L, index.data_ptr(),
-                                                         offset.data_ptr() if offset is not None else None, B, T, out.data_ptr(),
-                                                         self._stream()))
+        off_ptr = offset.data_ptr() if offset is not None else None
+        if i16:
+            _capi.check(self._h, self._lib.cmps_batch_gather_i16(self._h, data.data_ptr(), N, L, index.data_ptr(), off_ptr, B, T,
+                                                                 float(scale), out.data_ptr(), self._stream()))
+        else:
+            _capi.check(self._h, self._lib.cmps_batch_gather(self._h, data.data_ptr(), N, L, index.data_ptr(), off_ptr, B, T,
+                                                             out.data_ptr(), self._stream()))
         return out
+
+    def loss_stats(self, loss: torch.Tensor, first_id: int, stats: Optional[torch.Tensor] = None, reset: bool = False) -> torch.Tensor:
+        """cmps_loss_stats: fold the per-clip losses ``loss`` [B] (float32, on this device; clip ids first_id .. first_id + B - 1) into the
+        64-byte record ``stats`` (a uint8 device tensor this method allocates -- and resets -- when None) and return it.  No host copy, no
+        synchronisation: read_stats is the download."""
+        if not (isinstance(loss, torch.Tensor) and loss.device == self.device and loss.dtype == torch.float32 and loss.dim() == 1
+                and loss.is_contiguous() and loss.numel() >= 1):
+            raise ValueError("loss_stats: loss must be a contiguous float32 tensor [B], B >= 1, on the backend's device")
+        if stats is None:
+            stats, reset = torch.empty(64, dtype=torch.uint8, device=self.device), True
+        elif not (isinstance(stats, torch.Tensor) and stats.device == self.device and stats.dtype == torch.uint8 and stats.numel() == 64
+                  and stats.is_contiguous()):
+            raise ValueError("loss_stats: stats must be a contiguous uint8 tensor of 64 bytes on the backend's device")
+        _capi.check(self._h, self._lib.cmps_loss_stats(self._h, loss.data_ptr(), int(loss.numel()), int(first_id), 1 if reset else 0,
+                                                       stats.data_ptr(), self._stream()))
+        return stats
+
+    @staticmethod
+    def read_stats(stats: torch.Tensor) -> dict:
+        """The record of loss_stats as a dict of Python numbers (_capi.LOSS_STATS's fields): the one device -> host copy of an evaluation."""
+        rec = stats.cpu().numpy().view(_capi.LOSS_STATS)[0]
+        return {k: (float(rec[k]) if _capi.LOSS_STATS[k].kind == "f" else int(rec[k])) for k in _capi.LOSS_STATS.names}
 
     def damped_sine(self, seed: int, first_clip: int, B: int, T: int, delta_t: float) -> torch.Tensor:
         """cmps_damped_sine_fill: clips first_clip .. first_clip + B - 1 of the seed's synthetic damped-sine sequence (include/cmps.h),

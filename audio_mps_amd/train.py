@@ -13,10 +13,13 @@ Run:  python -m audio_mps_amd.train --dataset=damped_sine --hparams=bond_dim=32,
 (under torchrun for several GPUs: the batch is sharded over ranks, one RCCL all-reduce per step).
 ``--device_data`` produces every batch on the device instead of on the host (audio_mps_amd/device_data.py): a TFRecord dataset is uploaded
 once and gathered from in the host pipeline's order, damped_sine is generated there.
+``--eval_dataset NAME --eval_every N`` evaluates a held-out set every N steps and after the last one (Trainer.evaluate,
+audio_mps_amd/evaluate.py): a line on the console, a JSON line in {logdir}/eval.jsonl, and model.best.ckpt.npz when the mean improves.
 """
 from __future__ import annotations
 
 import argparse
+import json
 import math
 import os
 import time
@@ -230,6 +233,32 @@ class Trainer:
         if self.model._dirty_owner is self:
             self.model._dirty_owner = None
 
+    # -- held-out evaluation ------------------------------------------------------------------------
+    def evaluate(self, dataset, minibatch_size: Optional[int] = None, T: Optional[int] = None, keep_losses: bool = False):
+        """The current parameters' loss over every clip of ``dataset`` (a ResidentDataset; audio_mps_amd/evaluate.py): an EvalResult.
+        Under ``device_step`` the parameters are the device-resident ones (the buffers cmps_*_apply_step wrote), read where they are.
+        Training is left untouched: the pass runs forward scans only, writes no variable and no Adam slot, and every training step
+        configures the backend for itself (set_params* with its own shape), so the steps after an evaluation are bit for bit those of a
+        run without it.  With several ranks every rank evaluates the whole dataset: nothing is communicated."""
+        from .evaluate import _need_stats, run_pass
+        m = self.model
+        be = m._get_backend()
+        _need_stats(be)
+        mb = int(minibatch_size) if minibatch_size else int(self.hparams.minibatch_size)
+        T = dataset.clip_len if T is None else int(T)
+        if T < 2 or mb < 1:
+            raise ValueError("evaluate needs T >= 2 and minibatch_size >= 1")
+        B_max = min(mb, dataset.n_clips)
+        if self.device_step:
+            st, rank = self._device_state(), self._rank()
+            be.set_params_dev(st["params"], m.sigma, m.delta_t, B_max, T, train=False)
+            if rank:
+                be.rho_set_state_dev(st["phi"], rank, B_max, T, train=False)
+        else:
+            be = m._prepare(B_max, T, train=False)
+        fwd = m._forward_entry(be)
+        return run_pass(dataset.ordered(mb, T), lambda batch: fwd(batch, save_for_bwd=False), be, T, keep_losses)
+
     # -- checkpoint / resume (train.py:93: save_checkpoint_secs=60, automatic restore from logdir) --
     def save(self, path: str):
         self.sync_to_host()
@@ -284,7 +313,58 @@ def build_parser():
     p.add_argument("--crop_duration", type=int, default=None,
                    help="with --device_data and a TFRecord dataset: train on this many samples of every clip, cut from a random start "
                         "(--sample_duration stays the length of the records)")
+    p.add_argument("--eval_dataset", default=None, metavar="NAME",
+                   help="held-out evaluation (audio_mps_amd/evaluate.py): NAME.tfrecords in --datadir, uploaded once and held on the "
+                        "device; 'damped_sine' instead evaluates clips [0, --eval_clips) of seed --seed + 1 of the device's synthetic "
+                        "sequence (cmps_damped_sine_fill).  With several ranks every rank evaluates the whole set; rank 0 writes")
+    p.add_argument("--eval_every", type=int, default=0, help="evaluate every N steps (0: off); also after the last step")
+    p.add_argument("--eval_clips", type=int, default=256, help="clips of the synthetic held-out set (--eval_dataset damped_sine)")
+    p.add_argument("--eval_minibatch", type=int, default=None, help="clips per evaluation batch (default: minibatch_size)")
+    p.add_argument("--eval_storage", default="float32", choices=["float32", "int16", "auto"],
+                   help="how a TFRecord held-out set is held on the device (int16: half the memory for 16-bit PCM data, the same bits)")
     return p
+
+
+def eval_dataset(args, hp, backend):
+    """--eval_dataset: the held-out set as a ResidentDataset on the backend's device."""
+    from .device_data import ResidentDataset, _need
+    if args.eval_dataset == "damped_sine":
+        _need(backend, "damped_sine", "--eval_dataset damped_sine")
+        if args.eval_clips < 1:
+            raise ValueError("--eval_clips must be positive")
+        return ResidentDataset(backend.damped_sine(args.seed + 1, 0, args.eval_clips, args.sample_duration, hp.delta_t), backend)
+    path = os.path.join(str(args.datadir), f"{args.eval_dataset}.tfrecords")
+    if not os.path.exists(path):
+        raise FileNotFoundError(path)
+    return ResidentDataset.from_tfrecord(path, args.sample_duration, backend, storage=args.eval_storage)
+
+
+class EvalLog:
+    """What train.main does with an evaluation: a line on the console, a JSON line appended to {logdir}/eval.jsonl, and
+    {logdir}/model.best.ckpt.npz whenever the mean improves with no non-finite clip (rank 0 only; the best so far survives a restart
+    through eval.jsonl)."""
+
+    def __init__(self, logdir: str, write: bool):
+        self.path, self.best_path, self.write = os.path.join(logdir, "eval.jsonl"), os.path.join(logdir, "model.best.ckpt.npz"), write
+        self.best = math.inf
+        if write and os.path.exists(self.path):
+            with open(self.path) as f:
+                for line in f:
+                    rec = json.loads(line)
+                    if rec.get("n_nonfinite") == 0 and rec.get("mean") is not None and rec["mean"] < self.best:
+                        self.best = float(rec["mean"])
+
+    def __call__(self, trainer, res):
+        if not self.write:
+            return
+        print(f"eval step={trainer.global_step} loss={res.mean:.6f} per_sample={res.per_sample:.6g} clips={res.n_clips} "
+              f"nonfinite={res.n_nonfinite}")
+        os.makedirs(os.path.dirname(self.path) or ".", exist_ok=True)
+        with open(self.path, "a") as f:
+            f.write(json.dumps({"global_step": trainer.global_step, **res.scalars()}) + "\n")
+        if res.n_nonfinite == 0 and res.mean < self.best:
+            self.best = res.mean
+            trainer.save(self.best_path)
 
 
 def device_source(args, hp, backend):
@@ -331,6 +411,8 @@ def main(argv=None, backend=None):
     if trainer.restore(ckpt) and dp.rank == 0:
         print(f"Restoring parameters from {ckpt} (global_step {trainer.global_step})")
     last_save = time.time()
+    held_out = eval_dataset(args, hp, backend) if args.eval_dataset else None
+    eval_log = EvalLog(logdir, dp.rank == 0)
     # train.py:46-47: the input pipeline is built ONCE; for TFRecord datasets get_audio returns the one-shot iterator's
     # get_next (batch -> shuffle(24) -> repeat, data.py:37-40), for damped_sine every step draws fresh delays (data.py:15)
     # --device_data: the same batches (TFRecords) / the device's own clips (damped_sine), produced on the device, a rank's shard only
@@ -358,6 +440,8 @@ def main(argv=None, backend=None):
             if time.time() - last_save > args.save_checkpoint_secs or it == args.max_steps - 1:
                 trainer.save(ckpt)
                 last_save = time.time()
+        if held_out is not None and ((args.eval_every > 0 and trainer.global_step % args.eval_every == 0) or it == args.max_steps - 1):
+            eval_log(trainer, trainer.evaluate(held_out, args.eval_minibatch))
     dp.close()
     return trainer
 

@@ -64,7 +64,8 @@ def build_input_fns(data_dir: str, batch_size: int, sample_duration: int = 2 ** 
 
 
 class Estimator:
-    """The part of tf.estimator.Estimator this script uses: train(input_fn, steps) with checkpoints in model_dir."""
+    """The part of tf.estimator.Estimator this script uses: train(input_fn, steps) with checkpoints in model_dir, and the
+    evaluate(input_fn, steps) its model_fn declares metrics for."""
 
     def __init__(self, params: dict, model_dir: Optional[str] = None, save_checkpoints_steps: int = 1,
                  dp: Optional[DataParallel] = None, model_kw: Optional[dict] = None):
@@ -124,6 +125,28 @@ class Estimator:
             if self.model_dir and self.dp.rank == 0 and self.global_step % self.save_checkpoints_steps == 0:
                 self._save()
         return self
+
+
+    def evaluate(self, input_fn: Callable[[], np.ndarray], steps: int) -> dict:
+        """model_fn in EVAL mode, `steps` times (training_estimators.py:70-74: eval_metric_ops={"loss": tf.metrics.mean(loss)}): the streaming
+        mean of the batch means over `steps` batches of equal size, that is the mean over all their clips -- accumulated on the device
+        (cmps_loss_stats) and downloaded once.  As with tf.metrics.mean, one non-finite clip makes it NaN.  Every rank evaluates every
+        batch; the variables and the optimiser are not touched."""
+        from .evaluate import _need_stats
+        be = self.model._get_backend()
+        _need_stats(be)
+        takes_shard = getattr(input_fn, "takes_shard", False)
+        stats, seen = None, 0
+        for _ in range(int(steps)):
+            batch = input_fn(shard=(0, int(self.params["batch_size"]))) if takes_shard else input_fn()
+            loss = self.model.loss_per_clip_dev(batch)
+            stats = be.loss_stats(loss, seen, stats, reset=stats is None)
+            seen += int(loss.shape[0])
+        if stats is None:
+            raise ValueError("evaluate needs steps >= 1")
+        s = be.read_stats(stats)
+        loss = s["sum"] / s["n_finite"] if s["n_nonfinite"] == 0 else float("nan")
+        return {"loss": float(loss), "global_step": self.global_step}
 
 
 def build_device_input_fns(backend, data_dir: str, batch_size: int, sample_duration: int, dt: float, seed: int = 0, first_step: int = 0):

@@ -91,7 +91,7 @@ enum {
     CMPS_OPT_F16_SCALE_SHIFT = 4 /* DIAGNOSTIC, default 0: added to the exponent of every data-dependent fp16 scale of the wave reverse
                         * scan's F16X2 arithmetic (range -40 .. 40).  A positive value pushes the pieces out of fp16 range on purpose:
                         * how tests/test_gpu_parity.py provokes CMPS_ERR_F16_RANGE.  No reference counterpart. */,
-    CMPS_OPT_KERNEL_EVENTS = 2 /* 1: every kernel cmps_psi_loss_fwd / _bwd, cmps_rho_loss_fwd / _bwd, cmps_psi_sample, cmps_psi_sample_primed, cmps_psi_stream, cmps_psi_stream_score, cmps_rho_sample_primed, cmps_rho_stream, cmps_rho_stream_score, cmps_noise_fill (as k_noise_philox), cmps_batch_gather (as k_batch_gather) and cmps_damped_sine_fill (as k_damped_sine) launch is bracketed by two HIP events on the caller's stream
+    CMPS_OPT_KERNEL_EVENTS = 2 /* 1: every kernel cmps_psi_loss_fwd / _bwd, cmps_rho_loss_fwd / _bwd, cmps_psi_sample, cmps_psi_sample_primed, cmps_psi_stream, cmps_psi_stream_score, cmps_rho_sample_primed, cmps_rho_stream, cmps_rho_stream_score, cmps_noise_fill (as k_noise_philox), cmps_batch_gather (as k_batch_gather), cmps_batch_gather_i16 (as k_batch_gather_i16), cmps_loss_stats (as k_loss_stats) and cmps_damped_sine_fill (as k_damped_sine) launch is bracketed by two HIP events on the caller's stream
                         * (read and reset with cmps_kernel_times); 0 (default): nothing is recorded.  A measurement aid -- the reference
                         * has no counterpart (no tracing / profiling hooks); bench.py uses it OUTSIDE its timed region to price
                         * each kernel of a multi-kernel family against the pipe it runs on */
@@ -594,6 +594,60 @@ int cmps_noise_fill(cmps_handle_t h, unsigned long long seed, unsigned long long
 int cmps_batch_gather(cmps_handle_t h, const float* data_dev, long long n_clips, long long clip_len,
                       const int* index_dev, const int* offset_dev, int B, int T,
                       float* audio_dev, void* stream);
+
+/*
+ * cmps_batch_gather out of a dataset held as int16 (16-bit PCM, x = i / 32768: half the memory of float32), widened on the way:
+ *   data_dev  [n_clips * clip_len] int16, row-major [clip][sample];  index_dev, offset_dev, audio_dev as in cmps_batch_gather;
+ *   audio_dev[b * T + j] = (float)data_dev[index[b] * clip_len + offset[b] + j] * scale,   b < B, j < T
+ * -- an exact integer-to-float conversion followed by ONE float32 multiply, so with scale = 2^-15 a batch holds the bits of the float32
+ * dataset i * 2^-15.  THE ROW GUARD, the address arithmetic, the argument checks, their order and their messages are cmps_batch_gather's: a
+ * row out of range is written as T quiet NaNs (0x7fc00000) and nothing is read for it; only rows named by a valid index are read, and of those
+ * only the T samples copied -- EXCEPT that a read may reach the aligned dword that contains the row's first or last copied sample, that is at
+ * most 2 bytes before the first and 2 bytes behind the last, and never outside data_dev[0 .. n_clips * clip_len): the first and last
+ * element of the buffer are not overshot by a byte.
+ * data_dev needs 2-byte alignment only, index_dev, offset_dev and audio_dev 4-byte alignment.  Needs no cmps_set_params: it works on a fresh
+ * handle of any D and in legacy mode.  Asynchronous on `stream`; never synchronises, allocates nothing and touches no element outside
+ * audio_dev[0 .. B * T).
+ * CMPS_ERR_BAD_ARG, each with a message, the first failing check speaking: a null handle, data_dev, index_dev or audio_dev; B < 1 or T < 1;
+ * n_clips < 1 or n_clips > 2^31 - 1; clip_len < T; and last, scale not finite or <= 0.
+ * With CMPS_OPT_KERNEL_EVENTS the launch is recorded as k_batch_gather_i16.
+ */
+int cmps_batch_gather_i16(cmps_handle_t h, const short* data_dev, long long n_clips, long long clip_len,
+                          const int* index_dev, const int* offset_dev, int B, int T, float scale,
+                          float* audio_dev, void* stream);
+
+/*
+ * The per-clip losses of an evaluation pass reduced on the device: loss_dev[0 .. B), the losses of the clips first_id .. first_id + B - 1
+ * (the id of loss_dev[b] is first_id + b), are folded into ONE 64-byte record in caller-owned device memory, so that a pass over a whole
+ * dataset downloads 64 bytes once.  Replaces: eval_metric_ops={"loss": tf.metrics.mean(loss)} (training_estimators.py:70-74), and says what a
+ * bare mean hides.  THE RECORD (normative; little-endian, 8-byte aligned; cmps_loss_stats_rec below):
+ *   offset  type       field
+ *        0  double     sum              of the finite losses
+ *        8  double     sumsq            of the finite losses, each squared in double (exact for a float32)
+ *       16  long long  n_finite
+ *       24  long long  n_nonfinite      NaN, +Inf, -Inf
+ *       32  long long  argmin           id of the smallest finite loss, the lowest id on ties; -1 while there is none
+ *       40  long long  argmax           likewise for the largest
+ *       48  long long  first_nonfinite  the lowest id of a non-finite loss; -1 while there is none
+ *       56  float      min              the loss at argmin (+Inf while n_finite == 0)
+ *       60  float      max              the loss at argmax (-Inf while n_finite == 0)
+ * reset != 0 ignores what the record held (no memset is needed before the first call); reset == 0 continues it.  A non-finite value enters
+ * nothing but n_nonfinite and first_nonfinite.  No atomics: one workgroup, a fixed assignment of elements to threads and a fixed reduction
+ * tree, and the update is ordered by the stream -- the same sequence of calls gives the same bits on every run.  sum and sumsq are
+ * accumulated in double in that fixed order: within n_finite * 2^-53 * sum |x| of the exact sums.
+ * Needs no cmps_set_params: it works on a fresh handle of any D and in legacy mode.  Asynchronous on `stream`; never synchronises, allocates
+ * nothing, reads loss_dev[0 .. B) and touches only the 64 bytes of the record.
+ * CMPS_ERR_BAD_ARG, each with a message, the first failing check speaking: a null handle; a null loss_dev; a null stats_dev or one that is
+ * not 8-byte aligned; B < 1; first_id < 0 or first_id + B > 2^63 - 1.
+ * With CMPS_OPT_KERNEL_EVENTS the launch is recorded as k_loss_stats.
+ */
+typedef struct cmps_loss_stats_rec {
+    double sum, sumsq;
+    long long n_finite, n_nonfinite, argmin, argmax, first_nonfinite;
+    float min, max;
+} cmps_loss_stats_rec;
+int cmps_loss_stats(cmps_handle_t h, const float* loss_dev, int B, long long first_id,
+                    int reset, void* stats_dev, void* stream);
 
 /*
  * The synthetic training batch, generated where it is used.  Replaces: the damped_sine branch of get_audio (data.py:8-22): a 261.6 Hz sine
