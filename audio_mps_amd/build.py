@@ -16,7 +16,7 @@ SOURCES = ["cmps_capi.hip", "cmps_prep.hip", "cmps_opt.hip", "cmps_block.hip", "
 # per-source flags: the pair kernels place plain VALU between MFMAs themselves (cmps_pair.hip::mfma_valu_pipeline); the compiler's
 # SLP packing into v_pk_* (expensive beside MFMAs, and a v_mov shuffle per operand) is switched off there
 EXTRA_FLAGS = {"cmps_pair.hip": ["-fno-slp-vectorize"]}
-HEADERS = ["cmps_internal.h", "cmps_lane_util.h", "cmps_block_util.h", "cmps_wave_util.h", "cmps_grad_gemm.h", "cmps_philox.h", os.path.join("..", "..", "include", "cmps.h")]
+HEADERS = ["cmps_internal.h", "cmps_stash_layout.h", "cmps_stash_layout_check.h", "cmps_lane_util.h", "cmps_block_util.h", "cmps_wave_util.h", "cmps_grad_gemm.h", "cmps_philox.h", os.path.join("..", "..", "include", "cmps.h")]
 
 
 def _hipcc() -> str:

@@ -327,31 +327,27 @@ __global__ void k_states(Dev P, float* __restrict__ psi_out) {
     const bool act = i < D;
     float2 y = make_float2(0.f, 0.f);
     if (act) {
-        if (P.stash_layout == STASH_WAVE16) {   // 16-row wave layout: 64 lanes x (y own, H y own); re on lane i, im on lane i + 32
-            const float* r = P.hst + row * 128;
-            y = make_float2(r[2 * i], r[2 * (i + 32)]);
-        } else if (P.stash_layout == STASH_WAVE32) {   // 32-row wave layout: 64 (y[n], (H y)[n]) pairs, n = 2 i + {re, im}
-            const float* r = P.hst + row * 128;
-            y = make_float2(r[4 * i], r[4 * i + 2]);
-        } else if (P.stash_layout == STASH_WAVE32N) {  // the same positions hold yhat = y / sqrt(max(n, 1e-12)); n_k from the scalar rows [B][NC][2][64]
-            const float* r = P.hst + row * 128;
-            const int b = (int)(row / N), NC = (N + 63) / 64;
-            const float nk = P.scal[((size_t)b * NC + (k >> 6)) * 128 + (k & 63)];
+        // every layout's positions: cmps_stash_layout.h
+        const int b = (int)(row / N), cl = b & 1;
+        const size_t pair = b >> 1;
+        const float* st = reinterpret_cast<const float*>(P.stash);
+        const float* r = P.hst + wave_row(b, N, k);
+        if (P.stash_layout == STASH_WAVE16) {
+            y = make_float2(r[wave16_pos(i, 0, 0)], r[wave16_pos(i, 1, 0)]);
+        } else if (P.stash_layout == STASH_WAVE32) {
+            y = make_float2(r[wave32_pos(i, 0, 0)], r[wave32_pos(i, 1, 0)]);
+        } else if (P.stash_layout == STASH_WAVE32N) {  // the rows hold yhat = y / sqrt(max(n, 1e-12)); n_k from the scalar rows
+            const float nk = P.scal[scal_off(b, (int)scal_chunks(N), 0) + scal_n(k / SCAL_STEPS, k % SCAL_STEPS)];
             const float nrm = sqrtf(fmaxf(nk, 1e-12f));
-            y = make_float2(r[4 * i] * nrm, r[4 * i + 2] * nrm);
+            y = make_float2(r[wave32_pos(i, 0, 0)] * nrm, r[wave32_pos(i, 1, 0)] * nrm);
         } else if (P.stash_layout == STASH_WIDE) {
-            // wide variant (cmps_wide.hip): per pair and step [y | H y][wave][lane], lane = 8 q + i, q = (row half, component, clip)
-            const int b = (int)(row / N);
-            const float* r = reinterpret_cast<const float*>(P.stash) + (((size_t)(b >> 1) * N + k) * 2) * 4 * DP
-                             + (i >> 4) * 64 + (i & 7) + 8 * (((i >> 3) & 1) * 4 + (b & 1));
-            y = make_float2(r[0], r[16]);
+            const float* v = st + wide_stash_vec(DP, pair, N, k, 0);
+            y = make_float2(v[wide_pos(i, 0, cl)], v[wide_pos(i, 1, cl)]);
         } else if (P.stash_layout == STASH_PAIR) {
-            // pair variant (cmps_pair.hip): per pair and step [y | H y][clip][re | im][DP] float32
-            const int b = (int)(row / N);
-            const float* r = reinterpret_cast<const float*>(P.stash) + ((((size_t)(b >> 1) * N + k) * 2 + 0) * 2 + (b & 1)) * 2 * DP;
-            y = make_float2(r[i], r[DP + i]);
+            const float* v = st + wide_stash_vec(DP, pair, N, k, 0);
+            y = make_float2(v[pair_pos(DP, i, 0, cl)], v[pair_pos(DP, i, 1, cl)]);
         } else {
-            y = P.stash[row * DP + i];
+            y = P.stash[block_row_pair(b, N, k, DP) + i];
         }
     }
     float n = act ? (y.x * y.x + y.y * y.y) : 0.f;

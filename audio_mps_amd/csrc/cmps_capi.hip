@@ -9,6 +9,7 @@
 #include <string>
 
 #include "cmps_internal.h"
+#include "cmps_stash_layout_check.h"   // compile-time checks of the stash, ybar-row and scalar-row layouts (this host pass only)
 
 using namespace cmps;
 

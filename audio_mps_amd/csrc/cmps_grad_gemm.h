@@ -109,8 +109,8 @@ __global__ __launch_bounds__(2 * PD, 1) void k_grad_gemm(Dev P, const float* __r
     // ---- build role: this thread = both components of one (row, clip); sixteen lanes = eight rows x two clips (128 contiguous
     //      bytes of an operand array per ds_write_b64) ----
     const int prow = 8 * (tid >> 4) + (tid & 7), pclip = (tid >> 3) & 1;
-    const float* stf = reinterpret_cast<const float*>(P.stash) + (size_t)blockIdx.x * N * (8 * PD);   // uniform bases
-    const float* ybs = reinterpret_cast<const float*>(P.gops) + (size_t)blockIdx.x * N * (4 * PD);
+    const float* stf = reinterpret_cast<const float*>(P.stash) + (size_t)blockIdx.x * N * stash_step_floats(PD);   // uniform bases
+    const float* ybs = reinterpret_cast<const float*>(P.gops) + (size_t)blockIdx.x * N * ybar_step_floats(PD);
     float2 ps0 = P.phi0 ? P.phi0[(size_t)((2 * blockIdx.x + pclip) % P.phi_rank) * PD + prow] : P.psi0[prow];   // (RhoCMPS: the column's phi_a)
     // ---- MFMA role: wave w owns the 32-row block w of Re Rbar, Im Rbar, Re Qbar, Im Qbar ----
     const int mr = lane & 31, mh = lane >> 5;
@@ -125,9 +125,9 @@ __global__ __launch_bounds__(2 * PD, 1) void k_grad_gemm(Dev P, const float* __r
             const int idx = e >> 1, cl = e & 1;
             if (cl && !two) continue;
             const float* xr = audio + (size_t)(cl ? b1 : b0) * T;
-            const float* sc = P.scal + ((size_t)(cl ? b1 : b0) * NC + idx / CH) * 128;
+            const float* sc = P.scal + scal_off(cl ? b1 : b0, NC, idx / CH);
             const float inc = (idx + 1 < T ? xr[idx + 1] : 0.f) - xr[idx];
-            const float nv = sc[idx & (CH - 1)], ev = sc[64 + (idx & (CH - 1))];
+            const float nv = sc[idx & (CH - 1)], ev = sc[SCAL_E + (idx & (CH - 1))];
             if constexpr (LEGACY) {                               // |psi_k| = 1
                 m_s = fmaxf(m_s, fabsf(P.dt * inc));
                 m_t = fmaxf(m_t, fabsf(2.0f * (ev - inc)));
@@ -174,10 +174,10 @@ __global__ __launch_bounds__(2 * PD, 1) void k_grad_gemm(Dev P, const float* __r
             const int st = tid >> 1, cl = tid & 1, idx = cj * CH + st;
             const bool in = idx < N;
             const float* xr = audio + (size_t)(cl ? b1 : b0) * T;
-            const float* sc = P.scal + ((size_t)(cl ? b1 : b0) * NC + cj) * 128;
+            const float* sc = P.scal + scal_off(cl ? b1 : b0, NC, cj);
             const float x0 = idx < T ? xr[idx] : 0.f, x1 = idx + 1 < T ? xr[idx + 1] : 0.f;
             const float inc = x1 - x0;
-            const float nv = in ? sc[st] : 1.f, ev = in ? sc[64 + st] : 0.f;
+            const float nv = in ? sc[st] : 1.f, ev = in ? sc[SCAL_E + st] : 0.f;
             const float z = (ev * inc) / A;
             const float zbar = -1.0f / (1.0f + z);
             const bool on = in && (cl == 0 || two);
@@ -195,18 +195,18 @@ __global__ __launch_bounds__(2 * PD, 1) void k_grad_gemm(Dev P, const float* __r
     // select.
     float rY[2][GU + 1], rYB[2][GU];                              // [component][step]
     float2 rRH[GU];
-    const auto rs_y = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(stf - 8 * PD), 0, (N + 1) * (8 * PD * 4), 0x00020000);
-    const auto rs_b = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(ybs), 0, N * (4 * PD * 4), 0x00020000);
+    const auto rs_y = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(stf - stash_step_floats(PD)), 0, (N + 1) * stash_step_bytes(PD), 0x00020000);
+    const auto rs_b = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(ybs), 0, N * ybar_step_bytes(PD), 0x00020000);
     const auto rs_r = __builtin_amdgcn_make_buffer_rsrc(const_cast<float2*>(P.rho - PD), 0, (N + 2) * (PD * 8), 0x00020000);
     const int voff_y0 = ROWS::y_off(tid, 0) * 4, voff_y1 = ROWS::y_off(tid, 1) * 4;
     const int voff_b0 = ROWS::yb_off(tid, 0) * 4, voff_b1 = ROWS::yb_off(tid, 1) * 4, voff_r = prow * 8;
     auto load_y = [&](int kb, int c, int j) {
         const int row = (kb - 1 + j) < N ? (kb - 1 + j) : N - 1;
-        rY[c][j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_y, c ? voff_y1 : voff_y0, (row + 1) * (8 * PD * 4), 0));
+        rY[c][j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_y, c ? voff_y1 : voff_y0, (row + 1) * stash_step_bytes(PD), 0));
     };
     auto load_yb = [&](int kb, int c, int j) {
         const int row = (kb + j) < N ? (kb + j) : N - 1;
-        rYB[c][j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_b, c ? voff_b1 : voff_b0, row * (4 * PD * 4), 0));
+        rYB[c][j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_b, c ? voff_b1 : voff_b0, row * ybar_step_bytes(PD), 0));
     };
     auto load_rho = [&](int kb, int j) {
         const int row = (kb - 1 + j) < N ? (kb - 1 + j) : N;

@@ -8,6 +8,8 @@
 #include <utility>
 #include <vector>
 
+#include "cmps_stash_layout.h"
+
 namespace cmps {
 
 // ---------------------------------------------------------------------------------------------
@@ -39,7 +41,8 @@ struct KScope {
 
 
 // ---------------------------------------------------------------------------------------------
-// Workspace layout (all offsets in bytes from the workspace base, every section 256-B aligned).
+// Workspace layout (all offsets in bytes from the workspace base, every section 256-B aligned).  The positions inside the stash, the
+// scalar rows and the ybar rows, and the bytes of those sections, are stated in cmps_stash_layout.h.
 //
 //   mats     : R [D][D] float2 | RT [D][D] float2 (RT[j][i] = R[i][j]) | Q [D][D] float2
 //              (Q = -(dt sigma^2 / 2) R^dagger R, Hermitian) | psi0 [D] float2 | freqs [D] float | qflag (|Q|_F <= 2^-19)
@@ -67,19 +70,17 @@ struct Layout {
     size_t slab_floats;  // psi_slab_floats(DP)
 };
 
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+constexpr size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
-inline int padded_D(int D) { return (D + 31) / 32 * 32; }   // zero padding to the next multiple of 32 (32, 64, 96, 128)
+constexpr int padded_D(int D) { return (D + 31) / 32 * 32; }   // zero padding to the next multiple of 32 (32, 64, 96, 128)
 
 constexpr int WS_TRAIN = 1;   // CMPS_WS_TRAIN (include/cmps.h): the workspace has the stash, the slabs and the reduction buffers
 // floats of a pure-state gradient slab: Rbar and Qbar as re | im planes [DP][DP], then f | psi0bar_re | psi0bar_im [DP] each, A, one spare
-inline size_t psi_slab_floats(size_t DP) { return 4 * DP * DP + 3 * DP + 2; }
+constexpr size_t psi_slab_floats(size_t DP) { return 4 * DP * DP + 3 * DP + 2; }
 // bytes of a `sums` section for slabs of `slab` floats: the reduced slab (padded to the next 64 floats) + [32][slab] double first-pass partials
-inline size_t sums_bytes(size_t slab) { return (slab + 64) * sizeof(float) + 32 * slab * sizeof(double); }
-// bytes of a `scal` section: per clip and 64-step chunk two rows of 64 floats, one step per lane
-inline size_t scal_bytes(size_t B, size_t N) { return B * ((N + 63) / 64) * 128 * sizeof(float); }
+constexpr size_t sums_bytes(size_t slab) { return (slab + 64) * sizeof(float) + 32 * slab * sizeof(double); }
 
-inline Layout make_layout(int D, int B, int T, int flags) {
+constexpr Layout make_layout(int D, int B, int T, int flags) {
     Layout L{};
     L.D = D; L.B = B; L.T = T; L.N = T - 1; L.flags = flags;
     // one layout serves both variants: tables are sized for the larger stride
@@ -108,38 +109,23 @@ inline Layout make_layout(int D, int B, int T, int flags) {
     L.off_status = o;
     if (flags & WS_TRAIN) {
         // the two variants never run on the same stash: their layouts share one region
-        // D > 32: the pair kernels (D = 128) keep (y, H y) per step, 16 B per component; the block kernels use half of it
-        size_t stash_bytes = D > 32 ? (size_t)((B + 1) / 2 * 2) * N * DP * sizeof(float2) * 2   // whole pairs
-                                    : (size_t)B * N * DP * sizeof(float2);
-        if (D <= 32 && stash_bytes < (size_t)B * N * 128 * sizeof(float)) stash_bytes = (size_t)B * N * 128 * sizeof(float);
         L.off_hst = L.off_stash;
-        o = align256(o + stash_bytes);
+        o = align256(o + psi_stash_bytes(D, DP, B, N));
         L.off_scal = o;  o = align256(o + scal_bytes(B, N));
         L.off_slabs = o; o = align256(o + (size_t)B * L.slab_floats * sizeof(float));
         L.off_sums = o;  o = align256(o + sums_bytes(L.slab_floats));
         L.off_gops = o;
         // ybar rows: exactly [pairs][N][4 DP] floats (k_grad_gemm clamps every row it requests to the pair's range and its buffer
         // descriptors end at the last row; round 3's 32 rows of slack behind the section had no reader left -- ADVICE r3)
-        if (D > 32) o = align256(o + (size_t)((B + 1) / 2) * N * 4 * DP * sizeof(float));
+        if (D > 32) o = align256(o + wide_ybar_bytes(pairs_of(B), N, DP));
         // max |ybar| per pair (wide reverse scan -> the gradient GEMM's fp16 operand scale, CMPS_RANK1_F16X2)
         L.off_opmax = o;
-        if (D > 32) o = align256(o + (size_t)((B + 1) / 2) * sizeof(float));
+        if (D > 32) o = align256(o + pairs_of(B) * sizeof(float));
         L.off_status = o; o = align256(o + 2 * sizeof(unsigned));
     }
     L.total = o;
     return L;
 }
-
-// Which family's forward wrote the stash (Dev::stash_layout): plain ints, so that the field and the kernels' comparisons stay what they were
-enum StashLayout : int {
-    STASH_BLOCK = 0,     // stash [B][N][DP] float2 (cmps_block.hip)
-    STASH_WAVE16 = 1,    // hst rows in lane order (cmps_wave16.hip)
-    STASH_PAIR = 2,      // pair rows (cmps_pair.hip)
-    STASH_WAVE32 = 3,    // hst rows of (y[n], (H y)[n]) pairs, n = 2 i + {re, im} (cmps_wave2.hip)
-    STASH_WIDE = 4,      // wide rows (cmps_wide.hip): [pair][step][y | H y][wave][lane] float
-    STASH_WAVE32N = 5,   // hst rows of (yhat[n], p[n]) pairs in STASH_WAVE32's positions: yhat_k = y_k / sqrt(max(n_k, 1e-12)), p_k = 2 ebar_k (H y_k)
-                         // (cmps_wave2.hip, for k_bwd_wave2w alone; n_k in the scalar rows turns yhat back into y, H y is not recoverable)
-};
 
 // Device-side view handed to the kernels by value.
 struct Dev {
@@ -196,11 +182,11 @@ struct RhoLayout {
 };
 
 // RhoCMPS on the wide kernels: every pair of columns of a clip is one broadcast vector in LDS, two buffers (cmps_wide.hip::k_fwd_wide_rho)
-inline size_t rho_wide_lds(int D, int rank) {
+constexpr size_t rho_wide_lds(int D, int rank) {
     const size_t PD = (size_t)padded_D(D), vr = (size_t)((rank + 1) / 2 * 2);
     return 2 * (vr / 2) * (8 * (PD / 8 + 1)) * 16 + 2 * (PD / 16) * sizeof(float) + 64;
 }
-inline bool rho_wide_ok(int D, int rank, int flags) { return D > 32 && D <= 128 && (flags & WS_TRAIN) && rho_wide_lds(D, rank) <= 120 * 1024; }
+constexpr bool rho_wide_ok(int D, int rank, int flags) { return D > 32 && D <= 128 && (flags & WS_TRAIN) && rho_wide_lds(D, rank) <= 120 * 1024; }
 
 // rank * D above which the block kernels' column arrays (4 rank D complex numbers in the reverse scan) no longer fit into 160 KB of
 // LDS and live in the workspace instead (RhoDev::cols): the reference's default rank = D (model.py:62-65) from D = 72 upwards
@@ -212,7 +198,7 @@ constexpr size_t RHO_LDS_COLS_MAX = 5000;
 constexpr size_t RHO_LDS_MAX = 160 * 1024;
 inline bool rho_cols_spill(int arrays, int rank, int D) { return (size_t)arrays * rank * D * sizeof(float2) + 128 > RHO_LDS_MAX; }
 
-inline RhoLayout make_rho_layout(int D, int rank, int B, int T, int flags) {
+constexpr RhoLayout make_rho_layout(int D, int rank, int B, int T, int flags) {
     RhoLayout L{};
     const size_t DP = (size_t)padded_D(D), N = (size_t)(T - 1), r = (size_t)rank;
     L.rank = rank;
@@ -221,8 +207,7 @@ inline RhoLayout make_rho_layout(int D, int rank, int B, int T, int flags) {
     L.off_phi0 = o; o = align256(o + r * DP * sizeof(float2));
     L.off_stash = L.off_scal = L.off_slabs = L.off_sums = o;
     if (flags & WS_TRAIN) {
-        // D <= 32: the wave kernels keep (y_a own, (H y_a) own) per lane, 512 B per column and step
-        L.off_stash = o; o = align256(o + (size_t)B * N * r * DP * sizeof(float2) * (D <= 32 ? 2 : 1));
+        L.off_stash = o; o = align256(o + rho_stash_bytes(D, DP, B, N, r));
         L.off_scal = o;  o = align256(o + scal_bytes(B, N));
         L.off_slabs = o; o = align256(o + (size_t)B * L.slab_floats * sizeof(float));
         L.off_sums = o;  o = align256(o + sums_bytes(L.slab_floats));
@@ -244,8 +229,8 @@ inline RhoLayout make_rho_layout(int D, int rank, int B, int T, int flags) {
         L.vrank = (int)vr;
         L.vslab_floats = psi_slab_floats(DP);
         L.off_vphi = o;   o = align256(o + vr * DP * sizeof(float2));
-        L.off_vstash = o; o = align256(o + vp * N * 8 * DP * sizeof(float));         // [virtual pair][step][y | H y][4 DP]
-        L.off_vgops = o;  o = align256(o + vp * N * 4 * DP * sizeof(float));         // ybar rows
+        L.off_vstash = o; o = align256(o + wide_stash_bytes(vp, N, DP));             // [virtual pair][step][y | H y][4 DP]
+        L.off_vgops = o;  o = align256(o + wide_ybar_bytes(vp, N, DP));              // ybar rows
         L.off_vopmax = o; o = align256(o + vp * sizeof(float));
         L.off_vscal = o;  o = align256(o + scal_bytes(vB, N));                       // (|y|^2 of the clip, e of the clip) per virtual clip
         L.off_rscal = o;  o = align256(o + scal_bytes(B, N));                        // the same per real clip
@@ -257,14 +242,6 @@ inline RhoLayout make_rho_layout(int D, int rank, int B, int T, int flags) {
     L.total = o;
     return L;
 }
-
-// Which forward (or sampler) wrote the rho stash (RhoDev::stash_layout)
-enum RhoStashLayout : int {
-    RHO_STASH_BLOCK = 0,   // [B][N][rank][DP] float2 (cmps_rho.hip)
-    RHO_STASH_WAVE = 1,    // [B][N][rank][64] (y own, H y own) (cmps_rho_wave.hip)
-    RHO_STASH_MFMA = 2,    // [B][N][rank][64] pairs (y[n], (H y)[n]), n = 2 i + {re, im} (cmps_rho_mfma.hip)
-    RHO_STASH_WIDE = 3,    // the wide kernels' rows, one vector per PAIR of columns: vstash [(b vrank + a) / 2][N][y | H y][4 DP] (cmps_wide.hip)
-};
 
 struct RhoDev {
     int rank;

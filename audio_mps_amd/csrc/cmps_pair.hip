@@ -440,12 +440,6 @@ struct FwdRing {
     __attribute__((aligned(16))) float sinc[2][2][PCH];                // [chunk parity][clip][step]: s_k = x_k / A of a 64-step chunk (loss wave 0 -> chain waves)
 };
 
-// float index of (pair, step, y / H y, clip, component, row) in the pair stash
-template <int PD>
-__device__ __forceinline__ size_t pair_stash_index(size_t pair, int N, int step, int yh, int clip, int comp, int row) {
-    return (((((pair * N + step) * 2 + yh) * 2 + clip) * 2 + comp) * PD) + row;
-}
-
 }  // namespace
 
 template <int PD, bool SAVE>
@@ -639,7 +633,7 @@ __global__ __launch_bounds__(4 * PD, 1) void k_fwd_pair(Dev P, const float* __re
     const int ob1 = FwdRing<PD>::brow(clip, comp) * BROW + 16 * hk, ob2 = FwdRing<PD>::brow(clip, comp ? 0 : 2) * BROW + 16 * hk;
     const int of = (clip * 2 + comp) * FROW + (32 * w + 4 * hk) * 4;
     float* stash = reinterpret_cast<float*>(P.stash);
-    float* sc_c = SAVE ? P.scal + ((size_t)(clip ? b1 : b0) * NC) * 128 : nullptr;
+    float* sc_c = SAVE ? P.scal + ((size_t)(clip ? b1 : b0) * NC) * SCAL_ROW : nullptr;
     const float* xr_c = clip ? xr1 : xr0;
     const bool clip_live = clip == 0 || two;
     float loss0 = 0.f, loss1 = 0.f;
@@ -700,7 +694,7 @@ __global__ __launch_bounds__(4 * PD, 1) void k_fwd_pair(Dev P, const float* __re
                     const bool in = step_e < N;                                                                            \
                     const float lv = in ? -logf(1.0f + (e * (xp1 - xp0)) / A) : 0.f;  /* model.py:294 operation order */    \
                     if (SAVE && w == 0 && lane < 2 * FB && in && clip_live)                                                 \
-                        sc_c[(size_t)(step_e / PCH) * 128 + 64 + (step_e & (PCH - 1))] = e;                               \
+                        sc_c[(size_t)(step_e / PCH) * SCAL_ROW + SCAL_E + (step_e & (PCH - 1))] = e;                        \
                     _Pragma("unroll") for (int jj = 0; jj < FB; ++jj) {  /* model.py:279: sequential in time */             \
                         loss0 += rdlane(lv, 2 * jj);                                                                          \
                         loss1 += rdlane(lv, 2 * jj + 1);                                                                      \
@@ -715,7 +709,7 @@ __global__ __launch_bounds__(4 * PD, 1) void k_fwd_pair(Dev P, const float* __re
                     *reinterpret_cast<v4f*>(yp + 8 * g) = yv[g];                                                            \
                 }                                                                                                          \
                 if ((J) == 4 && SAVE && step_b < N && w == 0 && lane < 2 * FB && clip_live)                                 \
-                    sc_c[(size_t)(step_b / PCH) * 128 + (step_b & (PCH - 1))] = sum_waves<PWV>(&RG.nrm[(pb & 1) * FB + sb][clip][0]); \
+                    sc_c[(size_t)(step_b / PCH) * SCAL_ROW + (step_b & (PCH - 1))] = sum_waves<PWV>(&RG.nrm[(pb & 1) * FB + sb][clip][0]); \
                 v4u bvs[(KT + FB - 1) / FB];                                                                                \
                 _Pragma("unroll") for (int t = (J) * KT / FB; t < ((J) + 1) * KT / FB; ++t)                                \
                     bvs[t - (J) * KT / FB] = PAIR_LOSS_BV(bslot + (t < KS ? ob1 : ob2) + 32 * (t < KS ? t : t - KS));      \
@@ -859,11 +853,6 @@ __device__ __forceinline__ void rd128(unsigned addr, V& v) {
     asm volatile("ds_read_b128 %0, %1 offset:%2" : "=&v"(v) : "v"(addr), "n"(OFF) : "memory");
 }
 
-// float offset of (row, component, clip) inside a vector of the wide family's stash (cmps_wide.hip: lane order of its chain kernels)
-__device__ __forceinline__ int wide_pos(int row, int comp, int clip) {
-    return 64 * (row >> 4) + 8 * (4 * ((row >> 3) & 1) + 2 * comp + clip) + (row & 7);
-}
-
 }  // namespace
 
 // QLITE: the instance for |Q|_F <= 2^-19 (train.py's sigma = 1e-4 puts Q = -(dt sigma^2 / 2) R^dagger R near 1e-12): Q enters with its
@@ -947,7 +936,7 @@ __global__ __launch_bounds__(2 * PD, 1) void k_fwd_chain16(Dev P, const float* _
     v2f ua = odd ? v2f{pa.y, pa.x} : v2f{pa.x, pa.y}, ub = odd ? v2f{pb.y, pb.x} : v2f{pb.x, pb.y};
     float sv0 = 0.f, sv1 = 0.f;
     float nbuf0 = 0.f, nbuf1 = 0.f;                                   // wave 0: |y_k|^2 of the current 64-step chunk, lane <-> step
-    float* stash = reinterpret_cast<float*>(P.stash) + (size_t)blockIdx.x * N * (8 * PD) + wide_pos(ia, odd ? 1 : 0, q);
+    float* stash = reinterpret_cast<float*>(P.stash) + (size_t)blockIdx.x * N * stash_step_floats(PD) + wide_pos(ia, odd ? 1 : 0, q);
     v4u o0, o1;                                                        // the wave's own K-steps: [K half] (both pieces stacked in the A rows)
     float n0p = 1.f, n1p = 1.f;                                       // |y|^2 of both clips as the last step's tail read them
     // |y_kn|^2 rows of the scalar stash (wave 0; lane <-> step, one row of 64 steps per chunk), a step late and off the chain's tail
@@ -957,8 +946,8 @@ __global__ __launch_bounds__(2 * PD, 1) void k_fwd_chain16(Dev P, const float* _
         if ((kn & (PCH - 1)) == PCH - 1 || kn == N - 1) {
             const int c = kn / PCH;
             if (c * PCH + lane_c < N) {
-                P.scal[((size_t)b0 * NC + c) * 128 + lane_c] = nbuf0;
-                if (two) P.scal[((size_t)b1 * NC + c) * 128 + lane_c] = nbuf1;
+                P.scal[((size_t)b0 * NC + c) * SCAL_ROW + lane_c] = nbuf0;
+                if (two) P.scal[((size_t)b1 * NC + c) * SCAL_ROW + lane_c] = nbuf1;
             }
         }
     };
@@ -1052,7 +1041,7 @@ __global__ __launch_bounds__(2 * PD, 1) void k_fwd_chain16(Dev P, const float* _
         rd_own<(p ^ 1) * 2 * VEC>(g.lo[0], g.hi[0], o0, o1);          /* (same wave, in order: no wait between store and read) */ \
         nn = row_sum16(nn);                                                                                                \
         if (lane_c == 0 || lane_c == 32) L.nrm[p ^ 1][q][w] = nn;                                                          \
-        if (k < N) *reinterpret_cast<float2*>(stash + (size_t)k * (8 * PD)) = make_float2(ya.x, yb.x);                      \
+        if (k < N) *reinterpret_cast<float2*>(stash + (size_t)k * stash_step_floats(PD)) = make_float2(ya.x, yb.x);        \
         n0p = n0; n1p = n1;                                            /* |y_{k-1}|^2: booked behind the MFMAs of the next step */ \
         C16_STAMP_DEP(4, nn)                                                                                               \
         lds_barrier();                                                                                                     \
@@ -1155,12 +1144,12 @@ __global__ __launch_bounds__(2 * PD, 1) void k_bwd_pair(Dev P, const float* __re
     const float wq = (q == 0 || two) ? 1.f : 0.f;                      // weight of this lane's clip (0: the repeated clip)
     const float* xr0 = audio + (size_t)b0 * T;
     const float* xr1 = audio + (size_t)b1 * T;
-    const float* sc0 = P.scal + ((size_t)b0 * NC) * 128;
-    const float* sc1 = P.scal + ((size_t)b1 * NC) * 128;
+    const float* sc0 = P.scal + ((size_t)b0 * NC) * SCAL_ROW;
+    const float* sc1 = P.scal + ((size_t)b1 * NC) * SCAL_ROW;
     const float* stf = reinterpret_cast<const float*>(P.stash);
     const int NBLK = (N + GB - 1) / GB;
     // ybar_k of this lane: rows ia, ia + 1 (8 contiguous bytes) of component (c & 1), clip q
-    float* ybar_base = reinterpret_cast<float*>(P.gops) + ((size_t)blockIdx.x * N * 4 + (q * 2 + (odd ? 1 : 0))) * PD + ia;
+    float* ybar_base = reinterpret_cast<float*>(P.gops) + ((size_t)blockIdx.x * N * 4 + (q * 2 + (odd ? 1 : 0))) * PD + ia;   // pair_ybar_index<PD>(pair, N, 0, q, odd, ia)
     const float A = dev_A(P);
     const float sgn = odd ? 1.f : -1.f;                                // (rho x)_own = rho_re x_own + sgn rho_im x_partner
 
@@ -1176,8 +1165,8 @@ __global__ __launch_bounds__(2 * PD, 1) void k_bwd_pair(Dev P, const float* __re
             const float* sc = qq ? sc1 : sc0;
             const float x0 = idx < T ? xr[idx] : 0.f, x1 = idx + 1 < T ? xr[idx + 1] : 0.f;
             const float inc = x1 - x0;
-            const float nv = in ? sc[(size_t)cj * 128 + lane] : 1.f;
-            const float ev = in ? sc[(size_t)cj * 128 + 64 + lane] : 0.f;
+            const float nv = in ? sc[(size_t)cj * SCAL_ROW + lane] : 1.f;
+            const float ev = in ? sc[(size_t)cj * SCAL_ROW + SCAL_E + lane] : 0.f;
             const float ex = ev * inc;                                 // model.py:294 operation order
             const float z = ex / A;
             const float zbar = -1.0f / (1.0f + z);
@@ -1307,7 +1296,7 @@ __global__ __launch_bounds__(2 * PD, 1) void k_bwd_pair(Dev P, const float* __re
         float pyba, pybb;                                                                                                          \
         const float una_ = una, unb_ = unb;                          /* u_{k+1}: the pieces below overwrite una .. only at the step's end */ \
         if constexpr (!PAIR_NO_PIECES) {                                                                                           \
-            *reinterpret_cast<float2*>(ybar_base + (size_t)k * (4 * PD)) = make_float2(yba, ybb);    /* for the gradient GEMM */   \
+            *reinterpret_cast<float2*>(ybar_base + (size_t)k * ybar_step_floats(PD)) = make_float2(yba, ybb);    /* for the gradient GEMM */ \
             facca += S1.z * (pga * una - ga * puna);                  /* the frequency gradient (meaningful in the Re lanes) */    \
             faccb += S1.z * (pgb * unb - gb * punb);                                                                               \
         } else { pyba = yba; pybb = ybb; }                                                                                         \
@@ -1528,12 +1517,12 @@ __global__ __launch_bounds__(2 * PD, 1) void k_bwd_chain16(Dev P, const float* _
     const float wq = (q == 0 || two) ? 1.f : 0.f;
     const float* xr0 = audio + (size_t)b0 * T;
     const float* xr1 = audio + (size_t)b1 * T;
-    const float* sc0 = P.scal + ((size_t)b0 * NC) * 128;
-    const float* sc1 = P.scal + ((size_t)b1 * NC) * 128;
+    const float* sc0 = P.scal + ((size_t)b0 * NC) * SCAL_ROW;
+    const float* sc1 = P.scal + ((size_t)b1 * NC) * SCAL_ROW;
     const int wpos = wide_pos(ia, odd ? 1 : 0, q);
     // rows through buffer instructions: descriptor + SGPR row offset + this lane's loop-invariant offset (no address arithmetic on the VALU)
-    const auto rs_st = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<float*>(P.stash) + (size_t)blockIdx.x * N * (8 * PD), 0, N * (8 * PD * 4), 0x00020000);
-    const auto rs_yb = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<float*>(P.gops) + (size_t)blockIdx.x * N * (4 * PD), 0, N * (4 * PD * 4), 0x00020000);
+    const auto rs_st = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<float*>(P.stash) + (size_t)blockIdx.x * N * stash_step_floats(PD), 0, N * stash_step_bytes(PD), 0x00020000);
+    const auto rs_yb = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<float*>(P.gops) + (size_t)blockIdx.x * N * ybar_step_floats(PD), 0, N * ybar_step_bytes(PD), 0x00020000);
     const int voff = wpos * 4;
     const float sgn = odd ? 1.f : -1.f;
 
@@ -1551,8 +1540,8 @@ __global__ __launch_bounds__(2 * PD, 1) void k_bwd_chain16(Dev P, const float* _
             const float* sc = qq ? sc1 : sc0;
             const float x0 = idx < T ? xr[idx] : 0.f, x1 = idx + 1 < T ? xr[idx + 1] : 0.f;
             const float inc = x1 - x0;
-            const float nv = in ? sc[(size_t)cj * 128 + lane] : 1.f;
-            const float ev = in ? sc[(size_t)cj * 128 + 64 + lane] : 0.f;
+            const float nv = in ? sc[(size_t)cj * SCAL_ROW + lane] : 1.f;
+            const float ev = in ? sc[(size_t)cj * SCAL_ROW + SCAL_E + lane] : 0.f;
             const float ex = ev * inc;
             const float z = ex / A;
             const float zbar = -1.0f / (1.0f + z);
@@ -1599,8 +1588,8 @@ __global__ __launch_bounds__(2 * PD, 1) void k_bwd_chain16(Dev P, const float* _
     auto tab_row = [&](int k, int half) { return TB.row[w][(k / PCH) & 1][k & (PCH - 1)][q][half]; };
     auto row_at = [&](int k) {
         const int kc = k > 0 ? k : 0;
-        const v2u y = __builtin_amdgcn_raw_buffer_load_b64(rs_st, voff, kc * (8 * PD * 4), 0);
-        const v2u h = __builtin_amdgcn_raw_buffer_load_b64(rs_st, voff + 4 * PD * 4, kc * (8 * PD * 4), 0);
+        const v2u y = __builtin_amdgcn_raw_buffer_load_b64(rs_st, voff, kc * stash_step_bytes(PD), 0);
+        const v2u h = __builtin_amdgcn_raw_buffer_load_b64(rs_st, voff + vec_floats(PD) * 4, kc * stash_step_bytes(PD), 0);
         return make_float4(__uint_as_float(y.x), __uint_as_float(y.y), __uint_as_float(h.x), __uint_as_float(h.y));
     };
     float4 ring0, ring1, ring2, ring3, ring4, ring5, ring6, ring7;
@@ -1673,7 +1662,7 @@ __global__ __launch_bounds__(2 * PD, 1) void k_bwd_chain16(Dev P, const float* _
         __builtin_amdgcn_sched_barrier(0);                                                                                         \
         C16_STAMP(1)                                                                                                               \
         /* ---- behind the stores: ybar out (for the gradient GEMM) ---- */                                                        \
-        __builtin_amdgcn_raw_buffer_store_b64(v2u{__float_as_uint(yba), __float_as_uint(ybb)}, rs_yb, voff, k * (4 * PD * 4), 0);   \
+        __builtin_amdgcn_raw_buffer_store_b64(v2u{__float_as_uint(yba), __float_as_uint(ybb)}, rs_yb, voff, k * ybar_step_bytes(PD), 0); \
         const v2f una_ = una, unb_ = unb, ga_ = ga, gb_ = gb;                                                                       \
         unsigned mbits = max(__float_as_uint(yba) & 0x7FFFFFFFu, __float_as_uint(ybb) & 0x7FFFFFFFu);     /* max |ybar| as float bits */ \
         __builtin_amdgcn_sched_barrier(0);                                                                                         \
@@ -1882,7 +1871,7 @@ namespace cmps {
 // ------------------------------------------------------------------------------------------------
 template <int PD>
 struct PairRows {
-    static __device__ __forceinline__ int y_off(int tid, int c) { return ((((tid >> 3) & 1) * 2 + c) * PD) + 8 * (tid >> 4) + (tid & 7); }
+    static __device__ __forceinline__ int y_off(int tid, int c) { return ((((tid >> 3) & 1) * 2 + c) * PD) + 8 * (tid >> 4) + (tid & 7); }   // pair_pos_thread(PD, tid, c)
     static __device__ __forceinline__ int yb_off(int tid, int c) { return y_off(tid, c); }
     static __device__ __forceinline__ float rsq(float m) { return 1.0f / sqrtf(m); }
 };

@@ -40,7 +40,7 @@ __global__ __launch_bounds__(NT) void k_fwd_rho(Dev P, RhoDev W, const float* __
     const int DPT = (NT == 64 || D <= 64) ? 64 : 128, tt = t & (DPT - 1), grp = t / DPT, NG = NT / DPT;
     const bool mact = tt < D;
     const float* xrow = audio + (size_t)b * P.T;
-    float2* st = save ? W.stash + (size_t)b * N * r * DP : nullptr;
+    float2* st = save ? W.stash + block_row_pair(b, N, 0, DP, r) : nullptr;
     if (act)
         for (int a = 0; a < r; ++a) cur[a * D + t] = W.phi0[a * DP + t];
     float loss = 0.f;
@@ -72,7 +72,7 @@ __global__ __launch_bounds__(NT) void k_fwd_rho(Dev P, RhoDev W, const float* __
                         const float2 u = cur[a * D + tt];
                         const float2 y = make_float2(u.x + q[c].x + s * v[c].x, u.y + q[c].y + s * v[c].y);   // column of U rho U^dagger, :186
                         nxt[a * D + tt] = y;
-                        if (save) st[((size_t)k * r + a) * DP + tt] = y;
+                        if (save) st[block_row_pair(0, N, k, DP, r, a) + tt] = y;
                     }
             }
         }
@@ -135,7 +135,7 @@ __global__ __launch_bounds__(NT) void k_bwd_rho(Dev P, RhoDev W, const float* __
     const int DPT = (NT == 64 || D <= 64) ? 64 : 128, tt = t & (DPT - 1), grp = t / DPT, NG = NT / DPT;   // the mat-vecs: as in k_fwd_rho
     const bool mact = tt < D;
     const float* xrow = audio + (size_t)b * P.T;
-    const float2* st = W.stash + (size_t)b * N * r * DP;
+    const float2* st = W.stash + (size_t)b * N * r * DP;   // block_row_pair(b, N, 0, DP, r): a call moves this kernel's instructions
     const float2 zero = make_float2(0.f, 0.f);
     float2 Rb[EPT], Qb[EPT];
 #pragma unroll
@@ -329,17 +329,17 @@ __global__ __launch_bounds__(256) void k_states_rho(Dev P, RhoDev W, int steps, 
     float* red = reinterpret_cast<float*>(ph + D);
     const size_t row = blockIdx.x;                          // b * steps + k
     const int k = (int)(row % steps), t = threadIdx.x;
-    const float2* st = W.stash + row * r * DP;
-    const float* stw = reinterpret_cast<const float*>(W.stash) + row * r * 128;   // wave layout: [rank][64] (y own, H y own)
-    auto ldY = [&](int a, int d) {
-        if (W.stash_layout == RHO_STASH_WIDE) {                          // the wide kernels' rows (cmps_wide.hip): one vector per pair of columns, lane order
-            const size_t vp = ((row / steps) * W.vrank + a) >> 1;
-            const float* base = W.vstash + ((vp * steps + k) * 2) * (size_t)(4 * DP);
-            const int p0 = 64 * (d >> 4) + 8 * ((((d & 15) >> 3) << 2) | (a & 1)) + (d & 7);
-            return make_float2(base[p0], base[p0 + 16]);    // component bit = q bit 1 = + 16 lanes
+    const int b = (int)(row / steps);
+    const float2* st = W.stash + block_row_pair(b, steps, k, DP, r);
+    const float* stw = reinterpret_cast<const float*>(W.stash) + wave_row(b, steps, k, r);   // wave and MFMA layouts: one wave row per column
+    auto ldY = [&](int a, int d) {                          // every layout's positions: cmps_stash_layout.h
+        if (W.stash_layout == RHO_STASH_WIDE) {             // the wide kernels' rows: one vector per pair of columns
+            const float* v = W.vstash + wide_stash_vec(DP, rho_wide_pair(b, W.vrank, a), steps, k, 0);
+            return make_float2(v[wide_pos(d, 0, rho_wide_clip(a))], v[wide_pos(d, 1, rho_wide_clip(a))]);
         }
-        return W.stash_layout == RHO_STASH_WAVE ? make_float2(stw[(a * 64 + d) * 2], stw[(a * 64 + d + 32) * 2])
-             : W.stash_layout == RHO_STASH_MFMA ? make_float2(stw[(a * 64 + 2 * d) * 2], stw[(a * 64 + 2 * d + 1) * 2]) : st[a * DP + d];
+        const float* w = stw + a * WAVE_ROW;
+        return W.stash_layout == RHO_STASH_WAVE ? make_float2(w[wave16_pos(d, 0, 0)], w[wave16_pos(d, 1, 0)])
+             : W.stash_layout == RHO_STASH_MFMA ? make_float2(w[wave32_pos(d, 0, 0)], w[wave32_pos(d, 1, 0)]) : st[a * DP + d];
     };
     float pn = 0.f;
     for (int idx = t; idx < r * D; idx += 256) {
@@ -455,7 +455,7 @@ __global__ __launch_bounds__(NT) void k_sample_rho(Dev P, RhoDev W, const float*
     const bool act = t < D;
     const int PF = PRIMED ? PR.PF : 0, nsteps = PF + length;        // (unprimed: nsteps = length)
     const float* prow = PRIMED ? PR.prime + (size_t)b * PR.stride : nullptr;      // (stride 0: one clip shared by all paths)
-    float2* st = save ? W.stash + (size_t)b * nsteps * r * DP : nullptr;
+    float2* st = save ? W.stash + block_row_pair(b, nsteps, 0, DP, r) : nullptr;
     float samp = 0.f;
     const float2* rin = nullptr;                                    // (STREAM) this path's record to carry on from
     if constexpr (STREAM) rin = ST.in ? reinterpret_cast<const float2*>(ST.in + (size_t)b * ST.rec) : nullptr;
@@ -507,7 +507,7 @@ __global__ __launch_bounds__(NT) void k_sample_rho(Dev P, RhoDev W, const float*
                 const float2 y = make_float2(w.x + s * v.x, w.y + s * v.y);
                 Wb[a * D + t] = y;
                 pn += y.x * y.x + y.y * y.y;
-                if (save) st[((size_t)k * r + a) * DP + t] = y;
+                if (save) st[block_row_pair(0, nsteps, k, DP, r, a) + t] = y;
             }
         }
         const float n = block_sum<NT>(pn, red);

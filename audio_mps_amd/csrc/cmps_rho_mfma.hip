@@ -161,8 +161,8 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_fwd_rho_mfma(Dev P, RhoDev W,
         U[a * RRLD + lane] = v;
     }
     const float* xrow = audio + (size_t)b * T;
-    float2* st = SAVE ? reinterpret_cast<float2*>(W.stash) + (size_t)b * N * r * 64 : nullptr;
-    float* sc = SAVE ? W.scal + (size_t)b * NC * 128 : nullptr;
+    float2* st = SAVE ? reinterpret_cast<float2*>(W.stash) + (size_t)b * N * r * WAVE_ROW_PAIRS : nullptr;
+    float* sc = SAVE ? W.scal + scal_off(b, NC, 0) : nullptr;
     const float A = dev_A(P);
     const float sgn = (col & 1) ? 1.f : -1.f;                  // Im lanes add rho_y * partner, Re lanes subtract it
     // the part of the gradient that needs no cotangent: P1 = sum_k 2 ebar_k Y^T Y (real form of sum_k 2 ebar_k sum_a y_a y_a^dagger),
@@ -270,14 +270,14 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_fwd_rho_mfma(Dev P, RhoDev W,
             if (SAVE) {
                 // register q holds row s0 = (q & 3) + 8 (q >> 2) in lanes 0-31 and row s0 + 4 in lanes 32-63, for the two tiles:
                 // one v_permlane32_swap between the tiles puts a whole 512-B row into each store
-                float2* sbase = st + (size_t)k * r * 64 + lane;
+                float2* sbase = st + (size_t)k * r * WAVE_ROW_PAIRS + lane;
 #pragma unroll
                 for (int q = 0; q < 16; ++q) {
                     const int s0 = (q & 3) + 8 * (q >> 2);
                     const auto ys = __builtin_amdgcn_permlane32_swap(__float_as_uint(y0[q]), __float_as_uint(y1[q]), false, false);
                     const auto hs = __builtin_amdgcn_permlane32_swap(__float_as_uint(h0[q]), __float_as_uint(h1[q]), false, false);
-                    if (s0 < r) sbase[(size_t)s0 * 64] = make_float2(__uint_as_float(ys[0]), __uint_as_float(hs[0]));
-                    if (s0 + 4 < r) sbase[(size_t)(s0 + 4) * 64] = make_float2(__uint_as_float(ys[1]), __uint_as_float(hs[1]));
+                    if (s0 < r) sbase[(size_t)s0 * WAVE_ROW_PAIRS] = make_float2(__uint_as_float(ys[0]), __uint_as_float(hs[0]));
+                    if (s0 + 4 < r) sbase[(size_t)(s0 + 4) * WAVE_ROW_PAIRS] = make_float2(__uint_as_float(ys[1]), __uint_as_float(hs[1]));
                 }
             }
             if (SAVE && GRAD1) {
@@ -336,8 +336,8 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_fwd_rho_mfma(Dev P, RhoDev W,
         const float lv = -logf(1.0f + z);
         for (int j = 0; j < cnt; ++j) loss += rdlane(lv, j);     // :155, sequential in time
         if (SAVE) {
-            sc[(size_t)c * 128 + lane] = nvec;
-            sc[(size_t)c * 128 + 64 + lane] = evec;
+            sc[(size_t)c * SCAL_ROW + lane] = nvec;
+            sc[(size_t)c * SCAL_ROW + SCAL_E + lane] = evec;
         }
     }
     if (lane == 0) loss_out[b] = loss;
@@ -384,8 +384,8 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_bwd_rho_mfma(Dev P, RhoDev W,
     const int N = P.N, T = P.T, NC = (N + CH - 1) / CH, r = W.rank;
     float* Bw = &Brow[w][0];
     const float* xrow = audio + (size_t)b * T;
-    const float2* st = reinterpret_cast<const float2*>(W.stash) + (size_t)b * N * r * 64;
-    const float* sc = W.scal + (size_t)b * NC * 128;
+    const float2* st = reinterpret_cast<const float2*>(W.stash) + (size_t)b * N * r * WAVE_ROW_PAIRS;
+    const float* sc = W.scal + scal_off(b, NC, 0);
     const float A = dev_A(P);
     const float sgn = (col & 1) ? 1.f : -1.f;        // rotation by rho: own*rho_x + sgn*partner*rho_y (conj: -sgn)
     // rows of this lane: a(q) = (q & 3) + 8 (q >> 2) + 4 hk
@@ -396,7 +396,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_bwd_rho_mfma(Dev P, RhoDev W,
             const int a = (q & 3) + 8 * (q >> 2) + 4 * hk;
             float t0 = 0.f, t1 = 0.f;
             if (a < r) {
-                const float* row = reinterpret_cast<const float*>(st + ((size_t)k * r + a) * 64) + sel;
+                const float* row = reinterpret_cast<const float*>(st + ((size_t)k * r + a) * WAVE_ROW_PAIRS) + sel;
                 t0 = row[2 * col];
                 t1 = row[2 * (32 + col)];
             }
@@ -420,8 +420,8 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_bwd_rho_mfma(Dev P, RhoDev W,
         const int idx = kbeg + lane;
         const float x0 = idx < T ? xrow[idx] : 0.f, x1 = idx + 1 < T ? xrow[idx + 1] : 0.f;
         const float incv = x1 - x0;
-        const float nv = idx < N ? sc[(size_t)c * 128 + lane] : 1.f;
-        const float ev = idx < N ? sc[(size_t)c * 128 + 64 + lane] : 0.f;
+        const float nv = idx < N ? sc[(size_t)c * SCAL_ROW + lane] : 1.f;
+        const float ev = idx < N ? sc[(size_t)c * SCAL_ROW + SCAL_E + lane] : 0.f;
         const float invv = sqrtf(1.0f / fmaxf(nv, 1e-12f));
         const float okv = nv > 1e-12f ? 1.f : 0.f;
         const float exv = ev * incv;
@@ -431,7 +431,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_bwd_rho_mfma(Dev P, RhoDev W,
         const float sv = incv / A;
         const float dtv = idx < N ? P.dtk[idx] : 0.f;
         if (idx < N) accA += zbv * (-exv / (A * A));
-        const float nbelow = kbeg > 0 ? sc[(size_t)(c - 1) * 128 + 63] : 1.f;          // tr rho' of the step below the chunk
+        const float nbelow = kbeg > 0 ? sc[(size_t)(c - 1) * SCAL_ROW + SCAL_STEPS - 1] : 1.f;          // tr rho' of the step below the chunk
         const float invbelow = sqrtf(1.0f / fmaxf(nbelow, 1e-12f));
         for (int kk = cnt - 1; kk >= 0; --kk) {
             const int k = kbeg + kk;
@@ -734,7 +734,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_sample_rho_mfma(Dev P, RhoDev
     const int PF = PRIMED ? PR.PF : 0, nsteps = PF + length;        // (unprimed: nsteps = length)
     const float* prow = PRIMED ? PR.prime + (size_t)b * PR.stride : nullptr;      // (stride 0: one clip shared by all paths)
     float* drow = PRIMED && PR.pred ? PR.pred + (size_t)b * PF : nullptr;
-    float2* st = SAVE ? reinterpret_cast<float2*>(W.stash) + (size_t)b * nsteps * r * 64 : nullptr;
+    float2* st = SAVE ? reinterpret_cast<float2*>(W.stash) + (size_t)b * nsteps * r * WAVE_ROW_PAIRS : nullptr;
     const float A = dev_A(P);
     const float sgn = (col & 1) ? 1.f : -1.f;                        // Im lanes add rho_y * partner, Re lanes subtract it
     float samp = 0.f;
@@ -873,13 +873,13 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_sample_rho_mfma(Dev P, RhoDev
                 __builtin_amdgcn_sched_barrier(0);
             }
             if (SAVE) {
-                float2* sbase = st + (size_t)k * r * 64 + lane;
+                float2* sbase = st + (size_t)k * r * WAVE_ROW_PAIRS + lane;
 #pragma unroll
                 for (int q = 0; q < 16; ++q) {
                     const int s0 = (q & 3) + 8 * (q >> 2);
                     const auto ys = __builtin_amdgcn_permlane32_swap(__float_as_uint(y0[q]), __float_as_uint(y1[q]), false, false);
-                    if (s0 < r) sbase[(size_t)s0 * 64] = make_float2(__uint_as_float(ys[0]), 0.f);
-                    if (s0 + 4 < r) sbase[(size_t)(s0 + 4) * 64] = make_float2(__uint_as_float(ys[1]), 0.f);
+                    if (s0 < r) sbase[(size_t)s0 * WAVE_ROW_PAIRS] = make_float2(__uint_as_float(ys[0]), 0.f);
+                    if (s0 + 4 < r) sbase[(size_t)(s0 + 4) * WAVE_ROW_PAIRS] = make_float2(__uint_as_float(ys[1]), 0.f);
                 }
             }
 #pragma unroll

@@ -54,8 +54,8 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_fwd_rho_wave(Dev P, RhoDev W,
     const unsigned aUw = lds_addr(&bcU[w][0]) + i * 8 + h * 4, aUr = lds_addr(&bcU[w][0]) + h * 128;
     const float4* rho4 = reinterpret_cast<const float4*>(P.rho);
     const float* xrow = audio + (size_t)b * T;
-    float2* st = SAVE ? reinterpret_cast<float2*>(W.stash) + (size_t)b * N * r * 64 + lane : nullptr;
-    float* sc = SAVE ? W.scal + (size_t)b * NC * 128 : nullptr;
+    float2* st = SAVE ? reinterpret_cast<float2*>(W.stash) + wave_clip_pair(b, N, r) + lane : nullptr;
+    float* sc = SAVE ? W.scal + scal_off(b, NC, 0) : nullptr;
     const float A = dev_A(P);
     for (int a = 0; a < r; ++a) {
         const float2 p = W.phi0[a * DPW + i];
@@ -90,7 +90,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_fwd_rho_wave(Dev P, RhoDev W,
                 const v2f ah = mv1(MH, q);
                 const float hs = swap32_add(ah.x, ah.y);            // ((Rt + Rt^dagger) y_a), :193-194
                 acce += y * hs;
-                if (SAVE) st[((size_t)(kbeg + kk) * r + a) * 64] = make_float2(y, hs);
+                if (SAVE) st[((size_t)(kbeg + kk) * r + a) * WAVE_ROW_PAIRS] = make_float2(y, hs);
             }
             const float n = sum64(accn);                         // tr rho', :200
             const float e = sum64(acce);                         // Re tr(x rho'), :195-196
@@ -110,8 +110,8 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_fwd_rho_wave(Dev P, RhoDev W,
         const float lv = -logf(1.0f + z);
         for (int j = 0; j < cnt; ++j) loss += rdlane(lv, j);     // :155, sequential in time
         if (SAVE) {
-            sc[(size_t)c * 128 + lane] = nvec;
-            sc[(size_t)c * 128 + 64 + lane] = evec;
+            sc[(size_t)c * SCAL_ROW + lane] = nvec;
+            sc[(size_t)c * SCAL_ROW + SCAL_E + lane] = evec;
         }
     }
     if (lane == 0) loss_out[b] = loss;
@@ -140,8 +140,8 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_bwd_rho_wave(Dev P, RhoDev W,
     const float* xrow = audio + (size_t)b * T;
     // stash rows of 64 pairs (y, H y): in lane order (RHO_STASH_WAVE, k_fwd_rho_wave) or per real component n = 2 i + {re, im}
     // (RHO_STASH_MFMA, k_fwd_rho_mfma)
-    const float2* st = reinterpret_cast<const float2*>(W.stash) + (size_t)b * N * r * 64 + (W.stash_layout == RHO_STASH_MFMA ? 2 * i + h : lane);
-    const float* sc = W.scal + (size_t)b * NC * 128;
+    const float2* st = reinterpret_cast<const float2*>(W.stash) + wave_clip_pair(b, N, r) + (W.stash_layout == RHO_STASH_MFMA ? 2 * i + h : lane);
+    const float* sc = W.scal + scal_off(b, NC, 0);
     const float A = dev_A(P);
     for (int a = 0; a < r; ++a) G[w][a][lane] = 0.f;
     v16f Rre = {}, Rim = {}, Qre = {}, Qim = {};
@@ -157,8 +157,8 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_bwd_rho_wave(Dev P, RhoDev W,
         const int idx = kbeg + lane;
         const float x0 = idx < T ? xrow[idx] : 0.f, x1 = idx + 1 < T ? xrow[idx + 1] : 0.f;
         const float incv = x1 - x0;
-        const float nv = idx < N ? sc[(size_t)c * 128 + lane] : 1.f;
-        const float ev = idx < N ? sc[(size_t)c * 128 + 64 + lane] : 0.f;
+        const float nv = idx < N ? sc[(size_t)c * SCAL_ROW + lane] : 1.f;
+        const float ev = idx < N ? sc[(size_t)c * SCAL_ROW + SCAL_E + lane] : 0.f;
         const float invv = sqrtf(1.0f / fmaxf(nv, 1e-12f));
         const float okv = nv > 1e-12f ? 1.f : 0.f;
         const float exv = ev * incv;
@@ -168,7 +168,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_bwd_rho_wave(Dev P, RhoDev W,
         const float sv = incv / A;
         const float dtv = idx < N ? P.dtk[idx] : 0.f;
         if (idx < N) accA += zbv * (-exv / (A * A));
-        const float nbelow = kbeg > 0 ? sc[(size_t)(c - 1) * 128 + 63] : 1.f;          // tr rho' of the step below the chunk
+        const float nbelow = kbeg > 0 ? sc[(size_t)(c - 1) * SCAL_ROW + SCAL_STEPS - 1] : 1.f;          // tr rho' of the step below the chunk
         const float invbelow = sqrtf(1.0f / fmaxf(nbelow, 1e-12f));
         for (int kk = cnt - 1; kk >= 0; --kk) {
             const int k = kbeg + kk;
@@ -181,7 +181,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_bwd_rho_wave(Dev P, RhoDev W,
             // ---- pass 1: yhb_a and the joint projection ----
             float accd = 0.f;
             for (int a = 0; a < r; ++a) {
-                const float2 row = st[((size_t)k * r + a) * 64];
+                const float2 row = st[((size_t)k * r + a) * WAVE_ROW_PAIRS];
                 const float yh = row.x * inv;
                 const float g = G[w][a][lane];
                 const float go = osig_of(g, hb);
@@ -195,7 +195,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_bwd_rho_wave(Dev P, RhoDev W,
             const float dot = sum64(accd);
             // ---- pass 2 ----
             for (int a = 0; a < r; ++a) {
-                const float2 row = st[((size_t)k * r + a) * 64];
+                const float2 row = st[((size_t)k * r + a) * WAVE_ROW_PAIRS];
                 const float y = row.x, hy = row.y;
                 const float yh = y * inv;
                 const float yhb = Tb[w][a][lane];
@@ -208,7 +208,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_bwd_rho_wave(Dev P, RhoDev W,
                 // u_a(k) = rho_{k-1} y_a(k-1) / sqrt(tr)  (the initial column at k = 0)
                 float uk, uko;
                 if (k > 0) {
-                    const float yp = st[((size_t)(k - 1) * r + a) * 64].x * invp;
+                    const float yp = st[((size_t)(k - 1) * r + a) * WAVE_ROW_PAIRS].x * invp;
                     const v2f t = cmul2(mk2(yp, osig_of(yp, hb)), rhop);
                     uk = t.x;
                     uko = t.y;

@@ -129,7 +129,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_bwd_wave(Dev P, const float* 
     // column's rows in the [clip][step][column] stash of k_fwd_rho_mfma (the same 512-B row format), phi_av as the initial vector
     const int vr = P.phi0 ? P.phi_rank : 1;
     const int bc = b / vr, av = b - bc * vr;
-    const float4* sty4 = reinterpret_cast<const float4*>(P.hst + ((size_t)bc * N * vr + av) * 128);
+    const float4* sty4 = reinterpret_cast<const float4*>(P.hst + wave_row(bc, N, 0, vr, av));
     const float* xrow = audio + (size_t)bc * T;
     const float* sc = P.scal + scal_off(bc, NC, 0);
     const float A = dev_A(P);
@@ -149,8 +149,8 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_bwd_wave(Dev P, const float* 
         ra0 = idx < T ? xrow[idx] : 0.f;
         ra1 = idx + 1 < T ? xrow[idx + 1] : 0.f;
         rdt = P.dtk[idx];                 // padded to N + 64 entries
-        rnv = sc[(size_t)c * 128 + lane];
-        rev = sc[(size_t)c * 128 + 64 + lane];
+        rnv = sc[scal_n(c, lane)];
+        rev = sc[scal_e(c, lane)];
     };
     float te_above = 0.f;             // LEGACY: te of the first step of the chunk above (no step N: 0)
     auto scal_commit = [&](int c) {

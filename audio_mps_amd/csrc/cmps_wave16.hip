@@ -240,7 +240,7 @@ __global__ __launch_bounds__(128, 1) void k_fwd_wave16(Dev P, const float* __res
                 xsq = y * y;
                 if (kk > 0 || c > 0) nvec = (lane == ((kk - 1) & (CH16 - 1))) ? nprev : nvec;
                 if (SAVE && kk == 0 && c > 0 && lane < CH16) {
-                    sc[(size_t)((c - 1) >> 1) * 128 + ((c - 1) & 1) * CH16 + lane] = nvec;
+                    sc[(size_t)((c - 1) >> 1) * SCAL_ROW + ((c - 1) & 1) * CH16 + lane] = nvec;
                 }
                 W16_STAMP(tC, xsq)
 #if W16_ON
@@ -273,7 +273,7 @@ __global__ __launch_bounds__(128, 1) void k_fwd_wave16(Dev P, const float* __res
             const float nlast = 0.5f * sum64(xsq);
             const int cl = NC2 - 1;
             nvec = (lane == ((N - 1) & (CH16 - 1))) ? nlast : nvec;
-            if (lane < CH16) sc[(size_t)(cl >> 1) * 128 + (cl & 1) * CH16 + lane] = nvec;
+            if (lane < CH16) sc[(size_t)(cl >> 1) * SCAL_ROW + (cl & 1) * CH16 + lane] = nvec;
         }
         return;
     }
@@ -288,7 +288,7 @@ __global__ __launch_bounds__(128, 1) void k_fwd_wave16(Dev P, const float* __res
     }
     const unsigned aYr = aRing + q * 32, aYo = aRing + i * 8 + hq * 4;
     const unsigned aPEw = lds_addr(&pe[0]) + lane * (PE16_LD * 4);
-    float2* st = SAVE ? reinterpret_cast<float2*>(P.hst + (size_t)b * N * 128) + lane : nullptr;
+    float2* st = SAVE ? reinterpret_cast<float2*>(P.hst + (size_t)b * N * WAVE_ROW) + lane : nullptr;
     float loss = 0.f;
     v4f qa[2], qb[2];
     float ya = 0.f, yb = 0.f;
@@ -311,7 +311,7 @@ __global__ __launch_bounds__(128, 1) void k_fwd_wave16(Dev P, const float* __res
             const v2f ah = mv16(MH, Q);                                                                \
             const float hs = combine16(ah.x, ah.y);                                                    \
             lds_write32(aPEw + kk_ * 4, Y * hs);                                                       \
-            if (SAVE) st[(size_t)(kbeg + kk_) * 64] = make_float2(Y, hs);                              \
+            if (SAVE) st[(size_t)(kbeg + kk_) * WAVE_ROW_PAIRS] = make_float2(Y, hs);                  \
         }
         for (int kk = 0; kk < cnt; kk += 2) {
             LOSS16_STEP(kk, qa, ya, qb, yb)
@@ -341,7 +341,7 @@ __global__ __launch_bounds__(128, 1) void k_fwd_wave16(Dev P, const float* __res
         const float z = (evec * incv) / A;                             // model.py:294 operation order
         const float lv = -logf(1.0f + z);
         for (int j = 0; j < cnt; ++j) loss += rdlane(lv, j);           // model.py:279: sequential in time
-        if (SAVE && lane < CH16) sc[(size_t)(c >> 1) * 128 + 64 + (c & 1) * CH16 + lane] = evec;
+        if (SAVE && lane < CH16) sc[(size_t)(c >> 1) * SCAL_ROW + SCAL_E + (c & 1) * CH16 + lane] = evec;
     }
     if (lane == 0) loss_out[b] = loss;
 }
@@ -384,7 +384,7 @@ __global__ __launch_bounds__(128, 1) void k_bwd_wave16(Dev P, const float* __res
         const unsigned aRho = lds_addr(&stR[0]) + i * 8;
         const unsigned aScl = lds_addr(&scl[0]);
         const float4* rho4 = reinterpret_cast<const float4*>(P.rho);
-        const float4* sty4 = reinterpret_cast<const float4*>(P.hst + (size_t)b * N * 128);
+        const float4* sty4 = reinterpret_cast<const float4*>(P.hst + (size_t)b * N * WAVE_ROW);
         float facc = 0.f, accS = 0.f, accA = 0.f;
         float ra0 = 0.f, ra1 = 0.f, rdt = 0.f, rnv = 1.f, rev = 0.f;
         v4f sry[4], srr[2];
@@ -393,8 +393,8 @@ __global__ __launch_bounds__(128, 1) void k_bwd_wave16(Dev P, const float* __res
             ra0 = idx < T ? xrow[idx] : 0.f;
             ra1 = idx + 1 < T ? xrow[idx + 1] : 0.f;
             rdt = P.dtk[idx];
-            rnv = sc[(size_t)c * 128 + lane];
-            rev = sc[(size_t)c * 128 + 64 + lane];
+            rnv = sc[(size_t)c * SCAL_ROW + lane];
+            rev = sc[(size_t)c * SCAL_ROW + SCAL_E + lane];
         };
         auto scal_commit = [&](int c) {
             const int idx = c * CH + lane;
@@ -604,8 +604,8 @@ __global__ __launch_bounds__(128, 1) void k_bwd_wave16(Dev P, const float* __res
             const int idx = c * CH + lane;
             ra0 = idx < T ? xrow[idx] : 0.f;
             ra1 = idx + 1 < T ? xrow[idx + 1] : 0.f;
-            rnv = sc[(size_t)c * 128 + lane];
-            rev = sc[(size_t)c * 128 + 64 + lane];
+            rnv = sc[(size_t)c * SCAL_ROW + lane];
+            rev = sc[(size_t)c * SCAL_ROW + SCAL_E + lane];
         };
         auto scal_commit = [&](int c) {
             const int idx = c * CH + lane;

@@ -358,7 +358,7 @@ __global__ __launch_bounds__(128 * WAVES, 1) void k_fwd_wave2(Dev P, const float
     const int crow = lane & 31, chk = lane >> 5;
     const float* ringw = &ring[w][0][0];
     float* pew = &pe[w][0];
-    float2* st = SAVE ? reinterpret_cast<float2*>(P.hst + (size_t)b * N * 128) : nullptr;   // rows of 64 (y[n], (H y)[n]) pairs
+    float2* st = SAVE ? reinterpret_cast<float2*>(P.hst + (size_t)b * N * WAVE_ROW) : nullptr;   // rows of 64 (y[n], (H y)[n]) pairs
     float loss = 0.f;
     float f_below = 2.0f * P.R[0].x, n_below = 1.f;                    // LEGACY: y^dagger H y and |y|^2 of the step below the chunk (psi_0 = e_0)
     float m_below = 1.f, g_carry = 1.f;                                // |z|^2 of the step below the chunk (|psi_0|^2 = 1), g of the chunk's first step
@@ -500,7 +500,7 @@ __global__ __launch_bounds__(128 * WAVES, 1) void k_fwd_wave2(Dev P, const float
         // lane's 8 bytes (one VGPR for the whole kernel) + the row's immediate -- no 64-bit VALU address arithmetic and no per-row test.
         // (Stores by asm: dwordx2 data has no write-after-store hazard; nothing in this kernel reads the rows back.)
 #define FWD2_STORE_ROWS                                                                                                                             \
-            char* cbase = reinterpret_cast<char*>(st + (size_t)kbeg * 64);                                                                          \
+            char* cbase = reinterpret_cast<char*>(st + (size_t)kbeg * WAVE_ROW_PAIRS);                                                              \
             const unsigned loff = (unsigned)lane * 8u;                                                                                              \
             if (cnt == CH2) {                                                                                                                       \
                 _Pragma("unroll")                                                                                                                   \
@@ -605,8 +605,8 @@ __global__ __launch_bounds__(128 * WAVES, 1) void k_fwd_wave2(Dev P, const float
             for (int j = 0; j < cnt; ++j) loss += rdlane(lv, j);
         }
         if (SAVE && lane < CH2) {
-            sc[(size_t)(c >> 1) * 128 + (c & 1) * CH2 + lane] = nk;                // n_k = |y_k|^2
-            sc[(size_t)(c >> 1) * 128 + 64 + (c & 1) * CH2 + lane] = evec;
+            sc[(size_t)(c >> 1) * SCAL_ROW + (c & 1) * CH2 + lane] = nk;                // n_k = |y_k|^2
+            sc[(size_t)(c >> 1) * SCAL_ROW + SCAL_E + (c & 1) * CH2 + lane] = evec;
         }
     }
 #undef FWD2_STORE_ROWS

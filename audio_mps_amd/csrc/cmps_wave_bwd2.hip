@@ -144,7 +144,7 @@ __global__ __launch_bounds__(128 * WAVES, 1) void k_bwd_wave2w(Dev P, const floa
         const unsigned aRho = lds_addr(&stR[w][0]) + i * 8;
         const unsigned aScl = lds_addr(&scl[w][0]);
         const float4* rho4 = reinterpret_cast<const float4*>(P.rho);
-        const float4* sty4 = reinterpret_cast<const float4*>(P.hst + ((size_t)bc * N * vr + av) * 128);
+        const float4* sty4 = reinterpret_cast<const float4*>(P.hst + wave_row(bc, N, 0, vr, av));
         float facc = 0.f, accS = 0.f, accA = 0.f;
         float ra0 = 0.f, ra1 = 0.f, rdt = 0.f, rnv = 1.f, rev = 0.f;   // raw prefetched values of the next chunk
         float rad_above = 0.f;                        // NORM: rad of the lowest step of the scalar chunk above (no step N: 0)
@@ -163,7 +163,7 @@ __global__ __launch_bounds__(128 * WAVES, 1) void k_bwd_wave2w(Dev P, const floa
         auto octet_load_below = [&](int hh, int q) {
             if (vr == 1) {
                 const int row0 = __builtin_amdgcn_readfirstlane(hh * CHB + 8 * q);
-                const float4* py = sty4 + (size_t)row0 * 32;
+                const float4* py = sty4 + (size_t)row0 * WAVE_ROW_QUADS;
                 const float4* pr = rho4 + (size_t)row0 * 16;
                 asm volatile("global_load_dwordx4 %0, %6, %7\n\tglobal_load_dwordx4 %1, %6, %7 offset:1024\n\t"
                              "global_load_dwordx4 %2, %6, %7 offset:2048\n\tglobal_load_dwordx4 %3, %6, %7 offset:3072\n\t"
@@ -187,8 +187,8 @@ __global__ __launch_bounds__(128 * WAVES, 1) void k_bwd_wave2w(Dev P, const floa
             ra0 = idx < T ? xrow[idx] : 0.f;
             ra1 = idx + 1 < T ? xrow[idx + 1] : 0.f;
             rdt = P.dtk[idx];                 // padded to N + 64 entries
-            rnv = sc[(size_t)c * 128 + lane];
-            rev = sc[(size_t)c * 128 + 64 + lane];
+            rnv = sc[scal_n(c, lane)];
+            rev = sc[scal_e(c, lane)];
         };
         auto scal_commit = [&](int c) {
             const int idx = c * CH + lane;

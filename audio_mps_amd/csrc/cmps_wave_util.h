@@ -291,7 +291,7 @@ __device__ __forceinline__ void stage_load512(const float4* __restrict__ tab, in
         const int e = q * 64 + lane;
         int row = row0 + (e >> 5);
         row = row < max_row ? row : max_row;
-        const float4 t = tab[(size_t)row * stride * 32 + (e & 31)];
+        const float4 t = tab[(size_t)row * stride * WAVE_ROW_QUADS + (e & 31)];
         r[q] = v4f{t.x, t.y, t.z, t.w};
     }
 }
@@ -309,9 +309,6 @@ __device__ __forceinline__ void stagger(int w) {
     if (wu & 1) __builtin_amdgcn_s_sleep(4);
     if (wu & 2) { __builtin_amdgcn_s_sleep(4); __builtin_amdgcn_s_sleep(4); }
 }
-
-// per-chunk scalar stash: [B][NC][2][64] floats: n_k (true |y_k|^2), e_k, one step per lane
-__device__ __forceinline__ size_t scal_off(int b, int NC, int c) { return ((size_t)b * NC + c) * 128; }
 
 }  // namespace
 

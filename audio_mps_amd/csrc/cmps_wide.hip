@@ -143,20 +143,11 @@ struct WideGeom {
     static constexpr size_t FWD_LDS = ((size_t)NW * KC * 64 + 4 * VEC4) * 16 + 2 * 2 * NW * 2 * 4;     // loss in the kernel
     static constexpr size_t FWD_LDS_CHAIN = ((size_t)2 * VEC4) * 16 + 2 * NW * 2 * 4;                     // chain only (SAVE)
 };
-// float4 index (and float offset inside it) of this lane's own value in a broadcast vector
+// float4 index (and float offset inside it) of this lane's own value in a broadcast vector in LDS
 template <int PD>
 __device__ __forceinline__ int vec_float_index(int row, int comp, int clip) {
     constexpr int KC = WideGeom<PD>::KC, VSL = WideGeom<PD>::VSL;
     return ((row / KC) * VSL + row % KC) * 4 + comp * 2 + clip;
-}
-// float offset of the vector (pair, step, y / H y) in the stash
-template <int PD>
-__device__ __forceinline__ size_t wide_stash_vec(size_t pair, int N, int step, int yh) {
-    return ((pair * N + step) * 2 + yh) * (size_t)(4 * PD);
-}
-template <int PD>
-__device__ __forceinline__ size_t wide_ybar_vec(size_t pair, int N, int step) {
-    return (pair * N + step) * (size_t)(4 * PD);
 }
 
 
@@ -279,7 +270,7 @@ __global__ __launch_bounds__(4 * PD) void k_fwd_wide(Dev P, const float* __restr
         // y_{k-1} goes out HERE, in front of the rho load: vector-memory operations retire in order, so waiting for rho_{k+1} at the
         // top of the next step then only waits for operations a full step old (with the store behind the load, every step waited
         // for its predecessor's store to be acknowledged)
-        if (SAVE && k >= 1) stash[wide_stash_vec<PD>(blockIdx.x, N, k - 1, 0) + pos] = yprev;
+        if (SAVE && k >= 1) stash[wide_stash_vec(PD, blockIdx.x, N, k - 1, 0) + pos] = yprev;
         if (k + 1 < N) rho_next = P.rho[(size_t)(k + 1) * PD + row];
         // |y_{k-1}|^2 of both clips (published before the barrier of the previous iteration)
         float n0 = 1.f, n1 = 1.f;
@@ -324,14 +315,14 @@ __global__ __launch_bounds__(4 * PD) void k_fwd_wide(Dev P, const float* __restr
                 const float hy = reduce_slices(hRe0, hIm0, hRe1, hIm1, clip1);
                 const float ep = clip_wave_sum(yprev * hy);
                 if (i == 0 && q < 2) ee[((p ^ 1) * NW + w) * 2 + clip] = ep;
-                if (SAVE) stash[wide_stash_vec<PD>(blockIdx.x, N, k - 1, 1) + pos] = hy;
+                if (SAVE) stash[wide_stash_vec(PD, blockIdx.x, N, k - 1, 1) + pos] = hy;
             }
             yprev = y;
         } else if (lossmv) {                                      // k == N: the last loss product
             const float hy = reduce_slices(hRe0, hIm0, hRe1, hIm1, clip1);
             const float ep = clip_wave_sum(yprev * hy);
             if (i == 0 && q < 2) ee[((p ^ 1) * NW + w) * 2 + clip] = ep;
-            if (SAVE) stash[wide_stash_vec<PD>(blockIdx.x, N, k - 1, 1) + pos] = hy;
+            if (SAVE) stash[wide_stash_vec(PD, blockIdx.x, N, k - 1, 1) + pos] = hy;
         }
         if (w == 0 && LOSS) {                                     // bookkeeping: e_{k-2}, |y_{k-1}|^2, the loss (sequential float32)
             if (k >= 2) {
@@ -375,8 +366,8 @@ __global__ __launch_bounds__(4 * PD) void k_fwd_wide(Dev P, const float* __restr
             if ((kn & (WCH - 1)) == WCH - 1 || kn == N - 1) {
                 const int c = kn / WCH;
                 if (c * WCH + lane < N) {
-                    P.scal[((size_t)b0 * NC + c) * 128 + lane] = nbuf0;
-                    if (two) P.scal[((size_t)b1 * NC + c) * 128 + lane] = nbuf1;
+                    P.scal[scal_off(b0, NC, c) + lane] = nbuf0;
+                    if (two) P.scal[scal_off(b1, NC, c) + lane] = nbuf1;
                 }
             }
         }
@@ -474,7 +465,7 @@ __global__ __launch_bounds__(4 * PD) void k_fwd_wide_rho(Dev P, const float* __r
                 const float acc = reduce_slices(cRe0, cIm0, cRe1, cIm1, clip1);
                 const float y = inv * (ut + acc);
                 nacc = fmaf(y, y, nacc);
-                stash[wide_stash_vec<PD>((size_t)b * npairs + cp, N, k, 0) + pos] = y;
+                stash[wide_stash_vec(PD, (size_t)b * npairs + cp, N, k, 0) + pos] = y;
                 const float py = partner16(y, im_lane);
                 reinterpret_cast<float*>(uvec + ((size_t)(p ^ 1) * npairs + cp) * VEC4)[own_f] =
                     rho_k.x * y + (im_lane ? rho_k.y : -rho_k.y) * py;       // ut_{k+1} = rho_k y_k (un-normalised)
@@ -488,7 +479,7 @@ __global__ __launch_bounds__(4 * PD) void k_fwd_wide_rho(Dev P, const float* __r
             if (lane == (kn & (WCH - 1))) nbuf = n;
             if ((kn & (WCH - 1)) == WCH - 1 || kn == N - 1) {
                 const int c = kn / WCH;
-                if (c * WCH + lane < N) rscal[((size_t)b * NC + c) * 128 + lane] = nbuf;
+                if (c * WCH + lane < N) rscal[scal_off(b, NC, c) + lane] = nbuf;
             }
         }
         wide_barrier();
@@ -503,16 +494,16 @@ __global__ void k_rho_expand_audio(const float* __restrict__ audio, float* __res
 }
 // the clip's |y|^2 rows -> every virtual clip's rows (k_hy_wide scales its fp16 pieces from them: |y_a|^2 <= tr rho')
 __global__ void k_rho_spread_n(const float* __restrict__ rscal, float* __restrict__ vscal, int NC, int vrank) {
-    const size_t v = blockIdx.x, c = blockIdx.y;
-    vscal[(v * NC + c) * 128 + threadIdx.x] = rscal[((v / vrank) * NC + c) * 128 + threadIdx.x];
+    const int v = blockIdx.x, c = blockIdx.y;
+    vscal[scal_off(v, NC, c) + threadIdx.x] = rscal[scal_off(v / vrank, NC, c) + threadIdx.x];
 }
 // e = sum over the clip's columns of y_a^dagger H y_a (fixed order), to the clip's row and back to every column's row
 __global__ void k_rho_merge_e(float* __restrict__ rscal, float* __restrict__ vscal, int NC, int vrank) {
-    const size_t b = blockIdx.x, c = blockIdx.y;
+    const int b = blockIdx.x, c = blockIdx.y;
     float e = 0.f;
-    for (int a = 0; a < vrank; ++a) e += vscal[((b * vrank + a) * NC + c) * 128 + 64 + threadIdx.x];
-    rscal[(b * NC + c) * 128 + 64 + threadIdx.x] = e;
-    for (int a = 0; a < vrank; ++a) vscal[((b * vrank + a) * NC + c) * 128 + 64 + threadIdx.x] = e;
+    for (int a = 0; a < vrank; ++a) e += vscal[scal_off(b * vrank + a, NC, c) + SCAL_E + threadIdx.x];
+    rscal[scal_off(b, NC, c) + SCAL_E + threadIdx.x] = e;
+    for (int a = 0; a < vrank; ++a) vscal[scal_off(b * vrank + a, NC, c) + SCAL_E + threadIdx.x] = e;
 }
 // zero-padded copy of the columns: [rank][DP] -> [vrank][DP]
 __global__ void k_rho_pad_phi(const float2* __restrict__ phi0, float2* __restrict__ vphi, int rank, int vrank, int DP) {
@@ -830,7 +821,7 @@ __global__ __launch_bounds__(2 * PD, 1) void k_hy_wide(Dev P) {
         }
         for (int e = tid; e < 2 * (k_hi - k_lo); e += 2 * PD) {   // |y_k|^2 of the workgroup's steps (written by k_fwd_wide)
             const int k = k_lo + (e >> 1);
-            mN = fmaxf(mN, P.scal[((size_t)((e & 1) ? b1 : b0) * NC + k / WCH) * 128 + (k & (WCH - 1))]);
+            mN = fmaxf(mN, P.scal[scal_off((e & 1) ? b1 : b0, NC, k / WCH) + (k & (WCH - 1))]);
         }
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) {
@@ -896,16 +887,16 @@ __global__ __launch_bounds__(2 * PD, 1) void k_hy_wide(Dev P) {
     const int prow = 16 * (ppos >> 6) + 8 * (pq >> 2) + pi;      // even; the second position is row prow + 1
     // buffer descriptors (SGPR row offset + a loop-invariant lane offset; a store to be dropped gets a lane offset beyond the
     // descriptor's range instead of a branch): the pair's stash rows, and the scalar stash
-    float* pair_rows = stash + wide_stash_vec<PD>(blockIdx.x, N, 0, 0);
-    const auto rs_st = __builtin_amdgcn_make_buffer_rsrc(pair_rows, 0, N * (8 * PD * 4), 0x00020000);
-    const auto rs_sc = __builtin_amdgcn_make_buffer_rsrc(P.scal, 0, (int)((size_t)P.B * NC * 128 * 4), 0x00020000);
-    const int voff_y = ppos * 4, voff_h = (4 * PD + ppos) * 4;
+    float* pair_rows = stash + wide_stash_vec(PD, blockIdx.x, N, 0, 0);
+    const auto rs_st = __builtin_amdgcn_make_buffer_rsrc(pair_rows, 0, N * stash_step_bytes(PD), 0x00020000);
+    const auto rs_sc = __builtin_amdgcn_make_buffer_rsrc(P.scal, 0, (int)((size_t)P.B * NC * SCAL_ROW * 4), 0x00020000);
+    const int voff_y = ppos * 4, voff_h = (vec_floats(PD) + ppos) * 4;
 
     // rows of a unit (steps k_lo + 8 u ..).  Unclamped loads: rows a few steps above the pair's range lie inside the caller's
     // workspace, and every value derived from them is discarded by a select.
     float2 Y[HU];
     auto fetch_row = [&](int u, int j) {                          // (rows past the pair's last one read as zero: the descriptor's range)
-        Y[j] = __builtin_bit_cast(float2, __builtin_amdgcn_raw_buffer_load_b64(rs_st, voff_y, (k_lo + HU * u + j) * (8 * PD * 4), 0));
+        Y[j] = __builtin_bit_cast(float2, __builtin_amdgcn_raw_buffer_load_b64(rs_st, voff_y, (k_lo + HU * u + j) * stash_step_bytes(PD), 0));
     };
     // step j of unit u -> bf16 pieces (buffer u & 1) + float32 row (buffer u % 3); three parts
     unsigned sh[3];
@@ -975,14 +966,14 @@ __global__ __launch_bounds__(2 * PD, 1) void k_hy_wide(Dev P) {
                     const float2 v = *reinterpret_cast<const float2*>(&hb[hy_slot((j * 2 + pclip) * 2 + pcomp) * FROW + prow]);
                     const bool ok = u >= 2 && kw + j < k_hi;
                     __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(v2u, v), rs_st, ok ? voff_h : 0x7fffffff,
-                                                          ok ? (kw + j) * (8 * PD * 4) : 0, 0);
+                                                          ok ? (kw + j) * stash_step_bytes(PD) : 0, 0);
                 } else {
                     const int j = (tid >> 1) & 7, cl = tid & 1, k = kw + j;
                     float e = 0.f;
 #pragma unroll
                     for (int ww = 0; ww < PWV; ++ww) e += eacc[(PAR * PWV + ww) * 16 + (tid & 15)];
                     const bool ok = tid < 16 && u >= 2 && k < k_hi && (cl == 0 || two);
-                    const int so = (int)((((size_t)(cl ? b1 : b0) * NC + (ok ? k / WCH : 0)) * 128 + 64 + (k & (WCH - 1))) * 4);
+                    const int so = (int)((scal_off(cl ? b1 : b0, NC, ok ? k / WCH : 0) + SCAL_E + (k & (WCH - 1))) * 4);
                     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, e), rs_sc, ok ? so : 0x7fffffff, 0, 0);
                 }
             } else if constexpr (I < S_P0) {                      // unit u - 1: H y = acc0 +- acc1, e partial, float32 rows into hf
@@ -1065,10 +1056,10 @@ __global__ __launch_bounds__(64) void k_loss_wide(Dev P, const float* __restrict
     const int b = blockIdx.x, lane = threadIdx.x;
     const int N = P.N, NC = (N + WCH - 1) / WCH;
     const float* xr = audio + (size_t)b * P.T;
-    float* sc = P.scal + (size_t)b * NC * 128;
+    float* sc = P.scal + (size_t)b * NC * SCAL_ROW;
     const float A = dev_A(P);
     float loss = 0.f;
-    float en = lane < N ? sc[64 + lane] : 0.f, x0n = lane < N ? xr[lane] : 0.f, x1n = lane < N ? xr[lane + 1] : 0.f;
+    float en = lane < N ? sc[SCAL_E + lane] : 0.f, x0n = lane < N ? xr[lane] : 0.f, x1n = lane < N ? xr[lane + 1] : 0.f;
     float nn = (LEGACY && lane < N) ? sc[lane] : 1.f;
     float f_below = LEGACY ? 2.0f * P.R[0].x : 0.f, n_below = 1.f;     // LEGACY: y^dagger H y and |y|^2 of the step below the chunk (psi_0 = e_0)
     for (int c = 0; c < NC; ++c) {
@@ -1077,8 +1068,8 @@ __global__ __launch_bounds__(64) void k_loss_wide(Dev P, const float* __restrict
         const bool in = c * WCH + lane < N;
         const int idx = (c + 1) * WCH + lane;
         if (c + 1 < NC) {
-            en = idx < N ? sc[(size_t)(c + 1) * 128 + 64 + lane] : 0.f;
-            if (LEGACY) nn = idx < N ? sc[(size_t)(c + 1) * 128 + lane] : 1.f;
+            en = idx < N ? sc[(size_t)(c + 1) * SCAL_ROW + SCAL_E + lane] : 0.f;
+            if (LEGACY) nn = idx < N ? sc[(size_t)(c + 1) * SCAL_ROW + lane] : 1.f;
             x0n = idx < N ? xr[idx] : 0.f;
             x1n = idx < N ? xr[idx + 1] : 0.f;
         }
@@ -1092,7 +1083,7 @@ __global__ __launch_bounds__(64) void k_loss_wide(Dev P, const float* __restrict
             n_below = rdlane(nv, WCH - 1);
             const float invb = 1.0f / sqrtf(fmaxf(nb, 1e-12f));       // graph.pbtxt:14350-14594
             e = (fb * invb) * invb;
-            if (in) sc[(size_t)c * 128 + 64 + lane] = e;
+            if (in) sc[(size_t)c * SCAL_ROW + SCAL_E + lane] = e;
             const float d = inc - e;
             lv = in ? d * d / 2.0f : 0.f;
         } else {
@@ -1133,8 +1124,8 @@ __global__ __launch_bounds__(4 * PD) void k_bwd_wide(Dev P, const float* __restr
     const float wq = (!clip1 || two) ? 1.f : 0.f;                 // weight of this lane's clip (0: the repeated clip)
     const float* xr0 = audio + (size_t)b0 * T;
     const float* xr1 = audio + (size_t)b1 * T;
-    const float* sc0 = P.scal + ((size_t)b0 * NC) * 128;
-    const float* sc1 = P.scal + ((size_t)b1 * NC) * 128;
+    const float* sc0 = P.scal + scal_off(b0, NC, 0);
+    const float* sc1 = P.scal + scal_off(b1, NC, 0);
     const float A = dev_A(P);
     const float sgn = im_lane ? 1.f : -1.f;                       // (rho x)_own = rho_re x_own + sgn rho_im x_partner
 
@@ -1172,8 +1163,8 @@ __global__ __launch_bounds__(4 * PD) void k_bwd_wide(Dev P, const float* __restr
             const float* xr = qq ? xr1 : xr0;
             const float* sc = qq ? sc1 : sc0;
             const float x0 = idx < T ? xr[idx] : 0.f, x1 = idx + 1 < T ? xr[idx + 1] : 0.f;
-            const float nv = in ? sc[(size_t)cj * 128 + lane] : 1.f;
-            const float ev = in ? sc[(size_t)cj * 128 + 64 + lane] : 0.f;
+            const float nv = in ? sc[scal_n(cj, lane)] : 1.f;
+            const float ev = in ? sc[scal_e(cj, lane)] : 0.f;
             StepScal r;
             if constexpr (LEGACY) {
                 const float inc = x1 - x0;
@@ -1206,11 +1197,11 @@ __global__ __launch_bounds__(4 * PD) void k_bwd_wide(Dev P, const float* __restr
     struct Row { float y, yp, h; };
     auto row_at = [&](int k) {
         const int kc = k > 0 ? k : 0;
-        const float* base = stf + wide_stash_vec<PD>(blockIdx.x, N, kc, 0);
+        const float* base = stf + wide_stash_vec(PD, blockIdx.x, N, kc, 0);
         Row r;
         r.y = base[pos];
         r.yp = base[pos ^ 16];
-        r.h = base[4 * PD + pos];
+        r.h = base[vec_floats(PD) + pos];
         return r;
     };
     auto rho_row = [&](int k) { return P.rho[(size_t)(k > 0 ? k : 0) * PD + row]; };
@@ -1242,7 +1233,7 @@ __global__ __launch_bounds__(4 * PD) void k_bwd_wide(Dev P, const float* __restr
         const float hb = rh.x * g - sgn * rh.y * pg;              // conj(rho_k) g
         const float yb = fmaf(hb, S0.y, c3);
         reinterpret_cast<float*>(vec[p])[own_f] = yb;
-        ybs[wide_ybar_vec<PD>(blockIdx.x, N, k) + pos] = yb;
+        ybs[wide_ybar_vec(PD, blockIdx.x, N, k) + pos] = yb;
         ymx = fmaxf(ymx, fabsf(yb));
         wide_barrier();
         const int kl = k & (WCH - 1);
@@ -1329,7 +1320,7 @@ __global__ __launch_bounds__(4 * PD) void k_bwd_wide(Dev P, const float* __restr
 // ------------------------------------------------------------------------------------------------------------------------
 template <int PD>
 struct WideRows {
-    static __device__ __forceinline__ int y_off(int tid, int c) { return (((tid >> 4) << 5) | (tid & 15)) + 16 * c; }
+    static __device__ __forceinline__ int y_off(int tid, int c) { return wide_pos_thread(tid, c); }
     static __device__ __forceinline__ int yb_off(int tid, int c) { return y_off(tid, c); }
     static __device__ __forceinline__ float rsq(float m) { return rsq_newton(m); }
 };
