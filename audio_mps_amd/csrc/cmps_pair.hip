@@ -873,11 +873,12 @@ __global__ __launch_bounds__(2 * PD, 1) void k_fwd_chain16(Dev P, const float* _
     const float A = dev_A(P);
     if ((*P.qflag != 0u) != QLITE) return;        // the other instance's case (decided once per parameter set: k_qflag)
 
-    // ---- operand scales: max |R|, max |Q|, Frobenius norms, max |s| over the pair's clips ----
-    float sR, sQ, sV;
+    // ---- operand scales: max |R|, max |Q|, Frobenius norms; max |s| of EACH clip: a clip's vector images are scaled by its own sV, so
+    // that a clip with a wild increment (sV down to 2^-60) cannot flush its pair-mate's fp16 pieces to zero ----
+    float sR, sQ, sV0, sV1;
     {
         const int row0 = 32 * w + (lane & 31), c0 = (lane >> 5) * (PD / 2);
-        float mR = 0.f, mQ = 0.f, fR = 0.f, fQ = 0.f, ms = 0.f;
+        float mR = 0.f, mQ = 0.f, fR = 0.f, fQ = 0.f, ms0 = 0.f, ms1 = 0.f;
         for (int c = 0; c < PD / 2; ++c) {
             const float2 r = P.R[(size_t)row0 * PD + c0 + c], qq = P.Q[(size_t)row0 * PD + c0 + c];
             mR = fmaxf(mR, fmaxf(fabsf(r.x), fabsf(r.y)));
@@ -886,29 +887,30 @@ __global__ __launch_bounds__(2 * PD, 1) void k_fwd_chain16(Dev P, const float* _
             fQ += qq.x * qq.x + qq.y * qq.y;
         }
         for (int idx = threadIdx.x; idx < N; idx += 2 * PD) {
-            ms = fmaxf(ms, fabsf((xr0[idx + 1] - xr0[idx]) / A));
-            ms = fmaxf(ms, fabsf((xr1[idx + 1] - xr1[idx]) / A));
+            ms0 = fmaxf(ms0, fabsf((xr0[idx + 1] - xr0[idx]) / A));
+            ms1 = fmaxf(ms1, fabsf((xr1[idx + 1] - xr1[idx]) / A));
         }
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) {
-            mR = fmaxf(mR, __shfl_xor(mR, off, 64)); mQ = fmaxf(mQ, __shfl_xor(mQ, off, 64)); ms = fmaxf(ms, __shfl_xor(ms, off, 64));
+            mR = fmaxf(mR, __shfl_xor(mR, off, 64)); mQ = fmaxf(mQ, __shfl_xor(mQ, off, 64));
+            ms0 = fmaxf(ms0, __shfl_xor(ms0, off, 64)); ms1 = fmaxf(ms1, __shfl_xor(ms1, off, 64));
             fR += __shfl_xor(fR, off, 64); fQ += __shfl_xor(fQ, off, 64);
         }
-        if (lane == 0) { L.red[w][0] = mR; L.red[w][1] = mQ; L.red[w][2] = ms; L.nrm[0][0][w] = fR; L.nrm[0][1][w] = fQ; }
+        if (lane == 0) { L.red[w][0] = mR; L.red[w][1] = mQ; L.red[w][2] = ms0; L.red[w][3] = ms1; L.nrm[0][0][w] = fR; L.nrm[0][1][w] = fQ; }
         __syncthreads();
-        mR = mQ = ms = fR = fQ = 0.f;
+        mR = mQ = ms0 = ms1 = fR = fQ = 0.f;
 #pragma unroll
         for (int ww = 0; ww < PWV; ++ww) {
-            mR = fmaxf(mR, L.red[ww][0]); mQ = fmaxf(mQ, L.red[ww][1]); ms = fmaxf(ms, L.red[ww][2]);
+            mR = fmaxf(mR, L.red[ww][0]); mQ = fmaxf(mQ, L.red[ww][1]); ms0 = fmaxf(ms0, L.red[ww][2]); ms1 = fmaxf(ms1, L.red[ww][3]);
             fR += L.nrm[0][0][ww]; fQ += L.nrm[0][1][ww];
         }
         __syncthreads();
         auto uni = [](float x) { return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(x))); };
         sR = uni(pow2_below(mR, 15));
         sQ = uni(pow2_below(mQ, 15));
-        sV = uni(pow2_below(1.01f * (1.0f + sqrtf(fQ) + ms * sqrtf(fR)), 13));
+        sV0 = uni(pow2_below(1.01f * (1.0f + sqrtf(fQ) + ms0 * sqrtf(fR)), 13));
+        sV1 = uni(pow2_below(1.01f * (1.0f + sqrtf(fQ) + ms1 * sqrtf(fR)), 13));
     }
-    const float iRV = (1.0f / sR) * (1.0f / sV), iQV = (1.0f / sQ) * (1.0f / sV);    // exact: powers of two
 
     v4u FRh[PD / 8], FRl[PD / 8], FQh[PD / 8], FQl[QLITE ? 1 : PD / 8];
     {
@@ -930,6 +932,8 @@ __global__ __launch_bounds__(2 * PD, 1) void k_fwd_chain16(Dev P, const float* _
     const int q = g.q, ia = g.ia, ib = g.ib;
     const bool odd = g.odd;
     const float sg = odd ? 1.f : -1.f;
+    const float sV = q ? sV1 : sV0;                                   // this lane's clip
+    const float iRV = (1.0f / sR) * (1.0f / sV), iQV = (1.0f / sQ) * (1.0f / sV);    // exact: powers of two
     const unsigned a_nrm = lds_addr_of(&L.nrm[0][0][0]);             // + 32 parity: (clip 0 row, clip 1 row)
     const unsigned a_rho = lds_addr_of(&RS.row[0][0][ia]);            // + 8 PD (32 buffer + row)
     const float2 pa = P.psi0[ia], pb = P.psi0[ib];

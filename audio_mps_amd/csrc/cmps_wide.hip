@@ -782,7 +782,8 @@ __device__ __forceinline__ constexpr int hy_slot(int row) { return 8 * (row >> 3
 // accumulator of that half (out = acc0 +- acc1 per column form), not to the operand reads.
 // F16 (CMPS_RANK1_F16X2 / DEFAULT): two fp16 pieces per operand instead of three bf16 ones and three products instead of six, as in
 // k_grad_gemm (cmps_grad_gemm.h): H is scaled by a power of two from its largest entry, the y rows of the workgroup's 512 steps from
-// their largest |y|^2 (the chain kernel's scalar stash); the product is unscaled where it leaves the accumulators.
+// their largest |y|^2 (the chain kernel's scalar stash), each clip of the pair by its own (a clip whose |y|^2 ran away cannot flush its
+// pair-mate's pieces to zero); the product is unscaled where it leaves the accumulators.
 template <int PD, bool F16>
 __global__ __launch_bounds__(2 * PD, 1) void k_hy_wide(Dev P) {
     using HG = HyGeom<PD>;
@@ -810,10 +811,10 @@ __global__ __launch_bounds__(2 * PD, 1) void k_hy_wide(Dev P) {
 
     // ---- A operand: row 32 w + mr of [H_re | -H_im], K values 16 t + 8 mh .. + 7, three bf16 pieces (two fp16 pieces) ----
     s16x8 Ah[KT], Am[F16 ? 1 : KT], Al[KT];
-    float sH = 1.f, sB = 1.f;
+    float sH = 1.f, sB0 = 1.f, sB1 = 1.f;                         // sB: per clip of the pair
     if constexpr (F16) {
         const int row = 32 * w + mr;
-        float mH = 0.f, mN = 1.f;
+        float mH = 0.f, mN0 = 1.f, mN1 = 1.f;
         for (int e = 0; e < PD / 2; ++e) {                        // this lane's half of its row of H
             const int j = mh * (PD / 2) + e;
             const float2 r = P.R[(size_t)row * PD + j], rt = P.RT[(size_t)row * PD + j];
@@ -821,21 +822,24 @@ __global__ __launch_bounds__(2 * PD, 1) void k_hy_wide(Dev P) {
         }
         for (int e = tid; e < 2 * (k_hi - k_lo); e += 2 * PD) {   // |y_k|^2 of the workgroup's steps (written by k_fwd_wide)
             const int k = k_lo + (e >> 1);
-            mN = fmaxf(mN, P.scal[scal_off((e & 1) ? b1 : b0, NC, k / WCH) + (k & (WCH - 1))]);
+            const float n2 = P.scal[scal_off((e & 1) ? b1 : b0, NC, k / WCH) + (k & (WCH - 1))];
+            if (e & 1) mN1 = fmaxf(mN1, n2); else mN0 = fmaxf(mN0, n2);
         }
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) {
             mH = fmaxf(mH, __shfl_xor(mH, off, 64));
-            mN = fmaxf(mN, __shfl_xor(mN, off, 64));
+            mN0 = fmaxf(mN0, __shfl_xor(mN0, off, 64));
+            mN1 = fmaxf(mN1, __shfl_xor(mN1, off, 64));
         }
-        if (lane == 0) { eacc[2 * w] = mH; eacc[2 * w + 1] = mN; }
+        if (lane == 0) { eacc[3 * w] = mH; eacc[3 * w + 1] = mN0; eacc[3 * w + 2] = mN1; }
         __syncthreads();
 #pragma unroll
-        for (int ww = 0; ww < PWV; ++ww) { mH = fmaxf(mH, eacc[2 * ww]); mN = fmaxf(mN, eacc[2 * ww + 1]); }
+        for (int ww = 0; ww < PWV; ++ww) { mH = fmaxf(mH, eacc[3 * ww]); mN0 = fmaxf(mN0, eacc[3 * ww + 1]); mN1 = fmaxf(mN1, eacc[3 * ww + 2]); }
         __syncthreads();
         auto uni = [](float x) { return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(x))); };
         sH = uni(pow2_below(mH, 15));
-        sB = uni(pow2_below(sqrtf(mN), 13));
+        sB0 = uni(pow2_below(sqrtf(mN0), 13));
+        sB1 = uni(pow2_below(sqrtf(mN1), 13));
 #pragma unroll
         for (int t = 0; t < KT; ++t) {
             unsigned ph[4], pl[4];
@@ -891,6 +895,7 @@ __global__ __launch_bounds__(2 * PD, 1) void k_hy_wide(Dev P) {
     const auto rs_st = __builtin_amdgcn_make_buffer_rsrc(pair_rows, 0, N * stash_step_bytes(PD), 0x00020000);
     const auto rs_sc = __builtin_amdgcn_make_buffer_rsrc(P.scal, 0, (int)((size_t)P.B * NC * SCAL_ROW * 4), 0x00020000);
     const int voff_y = ppos * 4, voff_h = (vec_floats(PD) + ppos) * 4;
+    const float sB = pclip ? sB1 : sB0;                           // the clip whose rows this thread builds
 
     // rows of a unit (steps k_lo + 8 u ..).  Unclamped loads: rows a few steps above the pair's range lie inside the caller's
     // workspace, and every value derived from them is discarded by a select.
@@ -937,7 +942,7 @@ __global__ __launch_bounds__(2 * PD, 1) void k_hy_wide(Dev P) {
     v16f acc0[2], acc1[2];                                         // [unit parity]: K half 0 (H_re), K half 1 (-H_im)
     float ep_run = 0.f;
     float4 hv = make_float4(0.f, 0.f, 0.f, 0.f);
-    const float usc = (1.0f / sH) * (1.0f / sB), usgn = sgn * usc;   // exact powers of two (1 without the fp16 scales)
+    const float usc = (1.0f / sH) * (1.0f / (cc ? sB1 : sB0)), usgn = sgn * usc;   // exact powers of two (1 without the fp16 scales); the clip of this lane's column
     auto run_unit = [&](auto par_c, auto mac_c, int u, int u3) {
         constexpr int PAR = decltype(par_c)::value;
         constexpr bool MAC = decltype(mac_c)::value;

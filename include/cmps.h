@@ -11,7 +11,10 @@
  *
  * Every function returns CMPS_OK (0) or a CMPS_ERR_* code; cmps_last_error(h) gives the message.
  * NaN / Inf in the loss is NOT an error at this boundary (it propagates, as in the reference where
- * only tests/test_model.py:113 looks at it).
+ * only tests/test_model.py:113 looks at it) -- into the loss of THAT clip: the forward entries (cmps_psi_loss_fwd with either value
+ * of save_for_bwd, cmps_legacy_loss_fwd, cmps_rho_loss_fwd, the scored streams) keep the clips of a batch apart, also where one
+ * workgroup runs several of them; a clip with a NaN, an Inf or a sample of 2^40 leaves the losses of the others where the clean batch
+ * has them (tests/test_gpu_wild_clip.py).  The gradient sums of such a batch are non-finite by definition.
  */
 #ifndef CMPS_H_
 #define CMPS_H_
@@ -111,7 +114,8 @@ enum {
  *   wave reverse scan, 17 <= D <= 32 (PsiCMPS)    yes        yes     yes     scales per eight-step octet    F16X2
  *   wave reverse scan in legacy AudioMPS mode     yes        yes     yes     runs BF16X3                    BF16X3
  *   wave kernels, D <= 16                         always exact fp32 MFMAs (the option is ignored)
- *   wide kernels' GEMMs (H y, gradient), D > 32   runs BF16X3  yes   yes     scales per pair of clips       F16X2
+ *   wide kernels' H y GEMM (forward), D > 32      runs BF16X3  yes   yes     scales per clip                F16X2
+ *   wide kernels' gradient GEMM, D > 32           runs BF16X3  yes   yes     scales per pair of clips       F16X2
  *   RhoCMPS row-array GEMM forward and sampler    runs BF16X3 (every value but F16X2 / DEFAULT)  scales per clip / fixed   F16X2
  *   RhoCMPS reverse scan, pair (bf16) kernels     the option is ignored
  * The fp16 scales follow guaranteed bounds; should one ever be violated the pieces overflow to Inf and the gradient
@@ -140,6 +144,7 @@ enum {
     CMPS_WIDE_CHAIN_MFMA_FWD = 2,  /* the forward as MFMA below, the reverse scan as VALU (k_bwd_wide): for A/B measurements */
     CMPS_WIDE_CHAIN_MFMA = 1    /* (a new handle's setting) k_fwd_chain16 / k_bwd_chain16: the correction (Q + s R) u as power-of-two scaled fp16 x 2 split operands on
                                  * v_mfma_f32_16x16x32_f16 (three products, fp32 accumulate: the accuracy class of CMPS_RANK1_F16X2);
+                                 * the forward scales each clip's vector from that clip's own largest |s| (the matrices' scales are shared);
                                  * identity part and everything behind the mat-vec in float32 */
 };
 
