@@ -87,6 +87,46 @@ __device__ __forceinline__ void mv1r_hi(const v2f (&M)[16], const v4f (&q)[8], v
           "v"(lo2(q[7])), "v"(hi2(q[7])));
 }
 #undef DPPADD
+// The serial tail of a chain step on ROTATED PARTIALS.  The mat-vec leaves in lane (i, h) the plain complex partial sum
+// am = (M u)_i over K-half h.  The identity term joins it in the lane's own slot, G = am + mask u (mask = (1, 0) in half 0, (0, 1) in
+// half 1: one packed FMA, behind the chain so that the 32 small products are not accumulated onto an O(1) seed); then
+//     z_i     = G(half 0) + G(half 1)              -> split layout by ONE exchange + add   (the ring row)
+//     rho z_i = G rho (half 0) + G rho (half 1)    -> split layout by ONE exchange + add   (the next broadcast)
+// because the rotation is linear: it is applied to the partial pair of each lane, an ordinary complex product, BEFORE the halves are
+// combined.  The two exchanges are independent of each other, and the state's path holds one of them where it held two (combine, then
+// the partner component for the rotation), no select and no copies.
+// v_permlane32_swap_b32 needs two wait states behind the VALU writes of its operands; each exchange's are the other path's work:
+//     1 G  = v_pk_fma      2 Gr = v_pk_mul      3 Gr = v_pk_fma      4 swap G (written by 1: 2, 3 between)      5 z = v_add
+//     6 swap Gr (written by 3: 4, 5 between)      7 ring write of z      8 u = v_add      9.. the broadcast of u
+// ONE statement, the ring write and the broadcast (bcast_issue_tab_off, cmps_wave_util.h) included: hipcc pads a statement whose operands
+// the statement before wrote with an s_nop, and it cannot see the distances above.  The exchange names the HALVES of the pairs G and Gr,
+// which an operand cannot, so the two pairs are the fixed registers v[250:253], declared clobbered (the chain wave has them to spare).
+// Outputs as bcast_issue_tab_off's, valid only after a matching lds_wait*; ROFF / TOFF: compile-time offsets on the ring / table address.
+template <int ROFF, int TOFF>
+__device__ __forceinline__ void rot_tail_bcast(v2f am, float u, v2f mask, unsigned ring, unsigned wr, unsigned rd, unsigned tab,
+                                               float& z, float& un, v4f (&o)[8], v2f& rho) {
+    const v2f u2 = __builtin_shufflevector(mk2(u, 0.f), mk2(u, 0.f), 0, -1);   // only the low half is read: the high half is left undefined
+    // (rho: this step's entry in, the next step's out, in place: a second variable would be copied into the first at a loop's back-edge,
+    // in front of the counted wait -- see bcast_issue_tab_sync, cmps_wave_util.h)
+    asm volatile("v_pk_fma_f32 v[250:251], %12, %13, %11 op_sel_hi:[1,0,1]\n\t"
+                 "v_pk_mul_f32 v[252:253], v[250:251], %8 op_sel:[0,0] op_sel_hi:[1,0]\n\t"
+                 "v_pk_fma_f32 v[252:253], v[250:251], %8, v[252:253] op_sel:[1,1,0] op_sel_hi:[0,1,1] neg_lo:[1,0,0]\n\t"
+                 "v_permlane32_swap_b32 v250, v251\n\t"
+                 "v_add_f32 %9, v250, v251\n\t"
+                 "v_permlane32_swap_b32 v252, v253\n\t"
+                 "ds_write_b32 %14, %9 offset:%18\n\t"
+                 "v_add_f32 %10, v252, v253\n\t"
+                 "ds_write_b32 %15, %10\n\t"
+                 "ds_read_b128 %0, %16\n\tds_read_b128 %1, %16 offset:16\n\t"
+                 "ds_read_b128 %2, %16 offset:32\n\tds_read_b128 %3, %16 offset:48\n\t"
+                 "ds_read_b128 %4, %16 offset:64\n\tds_read_b128 %5, %16 offset:80\n\t"
+                 "ds_read_b128 %6, %16 offset:96\n\tds_read_b128 %7, %16 offset:112\n\t"
+                 "ds_read_b64 %8, %17 offset:%19"
+                 : "=&v"(o[0]), "=&v"(o[1]), "=&v"(o[2]), "=&v"(o[3]), "=&v"(o[4]), "=&v"(o[5]), "=&v"(o[6]), "=&v"(o[7]),
+                   "+v"(rho), "=&v"(z), "=&v"(un)
+                 : "v"(am), "v"(mask), "v"(u2), "v"(ring), "v"(wr), "v"(rd), "v"(tab), "n"(ROFF), "n"(TOFF)
+                 : "memory", "v250", "v251", "v252", "v253");
+}
 // wait for the second half of a broadcast; `dep` ties the wait behind the first FMA block (a plain asm statement the
 // scheduler would otherwise be free to sink below this volatile one)
 template <int N>
@@ -175,6 +215,7 @@ __global__ __launch_bounds__(128 * WAVES, 1) void k_fwd_wave2(Dev P, const float
         float xa1 = lane + 1 < T ? xrow[lane + 1] : 0.f;
         const float2 p0 = P.psi0[i];
         float u = hb ? p0.y : p0.x;
+        const v2f hmask = hb ? mk2(0.f, 1.f) : mk2(1.f, 0.f);          // the lane's own slot of a complex partial (rot_tail)
         v4f qu[8];
         v2f rho;
         // The normalisation is linear, so the chain does not apply it at all: it carries the un-normalised product
@@ -215,14 +256,11 @@ __global__ __launch_bounds__(128 * WAVES, 1) void k_fwd_wave2(Dev P, const float
                 mv1_lo(MM, qu, am);                                                                           \
                 lds_wait_hi_t_after<0>(qu, rho, am);                                                          \
                 mv1_hi(MM, qu, am);                                                                           \
-                const float y = u + swapadd_after_asm(am.x, am.y);        /* z_k */                           \
-                lds_write32(ay, y);                                                                           \
-                ay += RROWB;                                                                                  \
-                const float yo = osig_of(y, hb);                                                              \
-                const v2f un = cmul2(mk2(y, yo), rho);                    /* rho_k y_k, normalised next step */ \
-                u = un.x;                                                                                     \
                 const int kn = kk_ + 1 < CH2 ? kk_ + 1 : 0;               /* chunk end: a dummy, retired below */ \
-                bcast_issue_tab(aUw, aUr, u, aRho + kn * 256, qu, rho);                                       \
+                float y, un;                                              /* z_k -> ring row; rho_k z_k -> broadcast */ \
+                rot_tail_bcast<0, 0>(am, u, hmask, ay, aUw, aUr, aRho + kn * 256, y, un, qu, rho);            \
+                ay += RROWB;                                                                                  \
+                u = un;                                                                                       \
                 FORM_M(rdlane(sv, kn))                                    /* in the shadow of the broadcast */ \
             }
             // a full chunk runs unrolled with compile-time step numbers: every LDS offset is an immediate, the lane selects of
@@ -240,12 +278,14 @@ __global__ __launch_bounds__(128 * WAVES, 1) void k_fwd_wave2(Dev P, const float
                     lds_wait_hi_t_after<0>(qu, rho, am);                                                      \
                     mv1_hi(MM, qu, am);                                                                       \
                 }                                                                                             \
-                const float y = u + swapadd_after_asm(am.x, am.y);                                            \
-                lds_write32_imm<(KK) * RROWB>(ay, y);                                                         \
-                const float yo = osig_of(y, hb);                                                              \
-                const v2f un = cmul2(mk2(y, yo), rho);                                                        \
-                u = un.x;                                                                                     \
-                bcast_issue_tab_off<(((KK) + 1) & (CH2 - 1)) * 256>(aUw, aUr, u, aRho, qu, rho);              \
+                float y, un;                                                                                  \
+                if constexpr ((KK) == CH2 - 1) {                          /* chunk end: the table read is a dummy, retired below. */ \
+                    v2f rend = rho;                                       /* Into a register of its own: written into rho it would be */ \
+                    rot_tail_bcast<(KK) * RROWB, 0>(am, u, hmask, ay, aUw, aUr, aRho, y, un, qu, rend);   /* copied where the two chunk */ \
+                } else {                                                  /* paths join, in front of the wait */ \
+                    rot_tail_bcast<(KK) * RROWB, ((KK) + 1) * 256>(am, u, hmask, ay, aUw, aUr, aRho, y, un, qu, rho); \
+                }                                                                                             \
+                u = un;                                                                                       \
                 FORM_M(rdlane(sv, ((KK) + 1) & (CH2 - 1)))                                                    \
                 if constexpr ((KK) == CH2 - 3) xsq = y * y;                                                   \
             }
