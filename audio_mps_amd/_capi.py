@@ -60,6 +60,8 @@ SYMBOLS = (
     "cmps_rho_workspace_bytes", "cmps_rho_set_state", "cmps_rho_loss_fwd", "cmps_rho_loss_bwd",
     "cmps_rho_update_ancilla", "cmps_rho_sample", "cmps_rho_sample_primed", "cmps_rho_stream_state_bytes", "cmps_rho_stream", "cmps_rho_stream_score", "cmps_rho_states",
     "cmps_rho_apply_step_scratch_bytes", "cmps_rho_apply_step", "cmps_noise_fill", "cmps_batch_gather", "cmps_batch_gather_i16", "cmps_loss_stats", "cmps_damped_sine_fill", "cmps_crc32c",
+    "cmps_bank_workspace_bytes", "cmps_bank_set_params_dev", "cmps_bank_loss_fwd", "cmps_bank_loss_bwd", "cmps_bank_apply_step_scratch_bytes",
+    "cmps_bank_apply_step", "cmps_bank_grad_status",
 )
 
 
@@ -173,6 +175,21 @@ def _declare(lib):
     lib.cmps_damped_sine_fill.restype = c_int
     lib.cmps_crc32c.argtypes = [ctypes.c_char_p, c_size_t, ctypes.c_uint]
     lib.cmps_crc32c.restype = ctypes.c_uint
+    lib.cmps_bank_workspace_bytes.argtypes = [c_int, c_int, c_int, c_int, c_int]
+    lib.cmps_bank_workspace_bytes.restype = c_size_t
+    lib.cmps_bank_set_params_dev.argtypes = [vp, c_int, vp, c_double, c_double, c_int, c_int, c_int, vp, c_size_t, vp]
+    lib.cmps_bank_set_params_dev.restype = c_int
+    lib.cmps_bank_loss_fwd.argtypes = [vp, vp, c_int, c_int, c_int, vp, c_int, vp]
+    lib.cmps_bank_loss_fwd.restype = c_int
+    lib.cmps_bank_loss_bwd.argtypes = [vp, vp, c_int, c_int, c_int, vp, vp]
+    lib.cmps_bank_loss_bwd.restype = c_int
+    lib.cmps_bank_apply_step_scratch_bytes.argtypes = [c_int, c_int]
+    lib.cmps_bank_apply_step_scratch_bytes.restype = c_size_t
+    lib.cmps_bank_apply_step.argtypes = [vp, c_int, vp, vp, vp, vp, c_double, c_double, c_double, c_double, c_double, c_double, vp, c_int,
+                                         vp, vp, vp, vp]
+    lib.cmps_bank_apply_step.restype = c_int
+    lib.cmps_bank_grad_status.argtypes = [vp, ctypes.POINTER(c_int), ctypes.POINTER(c_int), vp]
+    lib.cmps_bank_grad_status.restype = c_int
 
 
 _lib = None

@@ -1,0 +1,291 @@
+"""Many models at once: a bank of M same-shape PsiCMPS models that train in one kernel launch per stage.
+
+  reference          a sweep is a Python loop over models: a grid over --hparams (train.py:31) at minibatch_size = 8, bond_dim = 8
+                     (train.py:41), several seeds of the random initialisation (model.py:36-50), one model per pitch (reader.py:9-66)
+  PsiBank            M PsiCMPS models of one D, each initialised exactly as PsiCMPS(hparams_m, seed=seed_m)
+  BankTrainer        one optimiser step of every member: cmps_bank_set_params_dev, cmps_bank_loss_fwd / _bwd, cmps_bank_apply_step --
+                     the plain kernels with a member grid dimension, so member m gets bit for bit what Trainer(device_step=True) gives
+                     model m alone.  On a backend without the bank entries the trainer loops over plain steps of its members.
+
+Common to a bank: bond_dim, minibatch_size, sigma, delta_t, A, Adam's betas and epsilon.  Free per member: seed, learning_rate, h_reg, r_reg
+and the data.  A member is sampled, scored, evaluated or saved on its own by taking it out as an ordinary model: ``BankTrainer.member(m)``.
+"""
+from __future__ import annotations
+
+import json
+import math
+import os
+import weakref
+from dataclasses import replace
+from typing import List, Optional, Sequence
+
+import numpy as np
+
+from . import layout
+from .model import HParams, PsiCMPS
+from .parallel import DataParallel
+from .train import Trainer
+
+MEMBER_KEYS = ("seed", "learning_rate", "h_reg", "r_reg")
+
+
+class PsiBank:
+    """``members``: a list of dicts overriding ``seed``, ``learning_rate``, ``h_reg``, ``r_reg`` of ``hparams`` (any other key is a
+    ValueError naming it).  ``models[m]`` is PsiCMPS(hparams_m, seed=seed_m); all of them share one backend."""
+
+    def __init__(self, hparams: HParams, members: Sequence[dict], backend=None):
+        if len(members) < 1:
+            raise ValueError("a bank needs at least one member")
+        self.hparams = hparams
+        self.overrides: List[dict] = []
+        for m, ov in enumerate(members):
+            ov = dict(ov)
+            for key in ov:
+                if key not in MEMBER_KEYS:
+                    raise ValueError(f"member {m}: '{key}' cannot differ inside a bank (free per member: {', '.join(MEMBER_KEYS)})")
+            self.overrides.append(ov)
+        self.member_hparams = [replace(hparams, **{k: float(v) for k, v in ov.items() if k != "seed"}) for ov in self.overrides]
+        self.seeds = [int(ov.get("seed", 0)) for ov in self.overrides]
+        if backend is None:
+            from .scan import HipScan       # raises if libcmps.so or the GPU is missing: no fallback
+            backend = HipScan(int(hparams.bond_dim))
+        self.backend = backend
+        self.models = [PsiCMPS(hp, seed=seed, backend=backend) for hp, seed in zip(self.member_hparams, self.seeds)]
+
+    def __len__(self) -> int:
+        return len(self.models)
+
+    @property
+    def bond_d(self) -> int:
+        return int(self.hparams.bond_dim)
+
+
+class BankTrainer:
+    """One optimiser step of every member of a PsiBank per ``step``.  Every member keeps an ordinary Trainer (its model, its Adam slots,
+    its checkpoint format); on a backend with the bank entries (HipScan) variables, Adam slots and effective parameters of all members
+    live on the device as [M, ...] arrays between steps and come back with ``sync_to_host`` (``member`` and ``save`` do so).  While that
+    state is live the bank is every member model's device owner, as a Trainer(device_step=True) is its model's (CMPS.variables): reading
+    ``bank.models[m].variables`` brings the state back first, and assigning an entry brings it back and drops it, so the next step starts
+    from the host values of every member."""
+
+    def __init__(self, bank: PsiBank, dp: Optional[DataParallel] = None):
+        if dp is not None and dp.world_size > 1:
+            raise ValueError("BankTrainer: multi-rank training of a bank is not supported (world size must be 1)")
+        self.bank = bank
+        be = bank.backend
+        self.native = all(hasattr(be, name) for name in ("bank_set_params_dev", "bank_forward", "bank_backward", "bank_apply_step"))
+        plain_device = type(be).__name__ == "HipScan"
+        self.trainers = [Trainer(model, hp, device_step=plain_device and not self.native)
+                         for model, hp in zip(bank.models, bank.member_hparams)]
+        self.global_step = 0
+        self.last = None              # the last synchronised step's per-member losses: {"model_loss": [M], "total_loss": [M]}
+        self._dev = None
+        self._dirty = False
+        self._syncing_back = False    # (read by the members' variables dicts; sync_to_host writes past them)
+
+    def __len__(self) -> int:
+        return len(self.trainers)
+
+    # -- the members' device owner (the interface CMPS.variables and its dict use of a Trainer) -------
+    def _own(self, dirty: bool):
+        for tr in self.trainers:
+            tr.model._device_owner = weakref.ref(self)
+            if dirty:
+                tr.model._dirty_owner = self      # a bank that goes out of scope with steps the host lacks stays alive until they are back
+
+    def _release(self):
+        for tr in self.trainers:
+            if tr.model._dirty_owner is self:
+                tr.model._dirty_owner = None
+
+    def _lazy_sync(self):
+        self.sync_to_host()
+
+    def drop_device_state(self):
+        """Bring the device-resident state back and forget it: the next step uploads variables and Adam slots from the host again."""
+        if self._dev is not None:
+            self.sync_to_host()
+            self._dev = None
+
+    # -- device-resident state of the native path ---------------------------------------------------
+    def _device_state(self):
+        if self._dev is None:
+            import torch
+            be, D = self.bank.backend, self.bank.bond_d
+            fields = layout.var_fields(D, 0)
+
+            def packed(get):
+                rows = []
+                for tr in self.trainers:
+                    variables = tr.model.variables
+                    zeros = {k: np.zeros_like(variables[k]) for k in layout.var_order(0)}
+                    rows.append(layout.pack(fields, {**zeros, **get(tr)}))
+                return torch.from_numpy(np.stack(rows)).to(be.device)
+
+            M = len(self.trainers)
+            st = {"vars": packed(lambda tr: tr.model.variables), "m": packed(lambda tr: tr.opt.m), "v": packed(lambda tr: tr.opt.v)}
+            st["params"] = torch.empty((M, layout.size(layout.param_fields(D, with_A=True))), dtype=torch.float32, device=be.device)
+            st["losses"] = torch.zeros((M, 2), dtype=torch.float32, device=be.device)
+            hyper = np.array([[tr.opt.lr, tr.model.h_reg, tr.model.r_reg, float(tr.model._c_r), float(tr.model._c_h)] for tr in self.trainers],
+                             dtype=np.float64)
+            st["hyper"] = torch.from_numpy(hyper).to(be.device)       # uploaded once: the device forms lr_t itself
+            self._dev = st
+            self._dirty = False
+            self._own(dirty=False)
+            self._apply(None, 1)                                      # effective parameters of the current variables
+        return self._dev
+
+    def _apply(self, grad_sums, global_batch):
+        st, o = self._dev, self.trainers[0].opt
+        t = max(o.t, 1)
+        self.bank.backend.bank_apply_step(st["vars"], st["m"], st["v"], grad_sums, global_batch, math.sqrt(1.0 - o.b2 ** t), 1.0 - o.b1 ** t,
+                                          o.b1, o.b2, o.eps, st["hyper"], True, st["params"], st["losses"])
+
+    def sync_to_host(self):
+        """Device-resident state -> every member's model.variables and Adam slots."""
+        if self._dev is None or not self._dirty:
+            return
+        fields = layout.var_fields(self.bank.bond_d, 0)
+        host = {name: self._dev[name].cpu().numpy() for name in ("vars", "m", "v")}
+        for m, tr in enumerate(self.trainers):
+            for name, dst in (("vars", tr.model._variables), ("m", tr.opt.m), ("v", tr.opt.v)):
+                for k, a in layout.unpack(fields, host[name][m]).items():
+                    dict.__setitem__(dst, k, np.asarray(a, dtype=np.float32).copy())
+        self._dirty = False
+        self._release()
+
+    # -- one step -------------------------------------------------------------------------------------
+    def step(self, data, sync: bool = True) -> dict:
+        """``data`` [B, T] (one batch shared by every member) or [M, B, T] (one per member).  Returns per-member ``model_loss`` and
+        ``total_loss`` ([M] arrays), or -- ``sync=False`` -- ``losses_dev`` [M, 2] where the step left it."""
+        M = len(self.trainers)
+        nd = data.dim() if hasattr(data, "dim") else np.ndim(data)
+        if nd not in (2, 3) or (nd == 3 and len(data) != M):
+            raise ValueError(f"data must be [B, T] or [M, B, T] with M = {M}")
+        if self.native:
+            out = self._step_native(data)
+        else:
+            recs = [tr.step(data if nd == 2 else data[m], sync=True) for m, tr in enumerate(self.trainers)]
+            out = {"losses_dev": np.array([[r["model_loss"], r["total_loss"]] for r in recs], dtype=np.float32)}
+        self.global_step += 1
+        out["global_step"] = self.global_step
+        if sync:
+            lo = out.pop("losses_dev")
+            lo = lo.cpu().numpy() if hasattr(lo, "cpu") else lo
+            out.update(model_loss=lo[:, 0].copy(), total_loss=lo[:, 1].copy())
+            self.last = out
+        return out
+
+    def _step_native(self, data):
+        be, m0 = self.bank.backend, self.bank.models[0]
+        st = self._device_state()
+        audio = m0._to_device(data)
+        B, T = audio.shape[-2:]
+        be.bank_set_params_dev(st["params"], m0.sigma, m0.delta_t, int(B), int(T), train=True)
+        be.bank_forward(audio, save_for_bwd=True)
+        flat = be.bank_backward()
+        for tr in self.trainers:
+            tr.opt.t += 1
+            tr.global_step += 1
+        self._apply(flat, int(B))
+        self._dirty = True
+        self._own(dirty=True)         # (again every step: a plain Trainer of a member taken out in between has made itself the owner)
+        return {"losses_dev": st["losses"]}
+
+    def best(self) -> int:
+        """The member with the lowest last ``model_loss`` among the finite ones."""
+        if self.last is None:
+            raise RuntimeError("best() needs a synchronised step first")
+        loss = np.asarray(self.last["model_loss"], dtype=np.float64)
+        if not np.isfinite(loss).any():
+            raise RuntimeError("best(): no member has a finite loss")
+        return int(np.argmin(np.where(np.isfinite(loss), loss, np.inf)))
+
+    def member(self, m: int) -> PsiCMPS:
+        """Member ``m`` as an ordinary PsiCMPS holding its current variables: sample, open_stream, evaluate and save work on it as on any
+        model (its scans reconfigure the shared backend; the next bank step configures it again)."""
+        self.sync_to_host()
+        return self.trainers[m].model
+
+    # -- held-out evaluation ------------------------------------------------------------------------------
+    def evaluate(self, dataset, minibatch_size: Optional[int] = None, T: Optional[int] = None, keep_losses: bool = False):
+        """Every member's loss over every clip of ``dataset`` (a ResidentDataset): a list of EvalResult.  The batches are shared; the bank
+        forward scores them for all members at once and cmps_loss_stats folds every member's row into its own record."""
+        if not self.native:
+            return [tr.evaluate(dataset, minibatch_size, T, keep_losses) for tr in self.trainers]
+        import torch
+        from .evaluate import EvalResult, _need_stats
+        be, m0 = self.bank.backend, self.bank.models[0]
+        _need_stats(be)
+        mb = int(minibatch_size) if minibatch_size else int(self.bank.hparams.minibatch_size)
+        T = dataset.clip_len if T is None else int(T)
+        if T < 2 or mb < 1:
+            raise ValueError("evaluate needs T >= 2 and minibatch_size >= 1")
+        st = self._device_state()
+        be.bank_set_params_dev(st["params"], m0.sigma, m0.delta_t, min(mb, dataset.n_clips), T, train=False)
+        M = len(self.trainers)
+        stats, kept = [None] * M, [[] for _ in range(M)]
+        for first_id, batch in dataset.ordered(mb, T):
+            loss = be.bank_forward(batch, save_for_bwd=False)
+            for m in range(M):
+                stats[m] = be.loss_stats(loss[m], first_id, stats[m], reset=stats[m] is None)
+                if keep_losses:
+                    kept[m].append(loss[m])
+        if stats[0] is None:
+            raise ValueError("evaluate: the dataset yielded no batch")
+        return [EvalResult.from_stats(be.read_stats(stats[m]), T, torch.cat(kept[m]).cpu().numpy() if keep_losses else None) for m in range(M)]
+
+    # -- checkpoints: model.<m>.ckpt.npz in the format of Trainer.save, bank.json with the members' overrides -----------
+    @staticmethod
+    def member_path(directory: str, m: int) -> str:
+        return os.path.join(directory, f"model.{m}.ckpt.npz")
+
+    def save(self, directory: str):
+        self.sync_to_host()
+        os.makedirs(directory, exist_ok=True)
+        for m, tr in enumerate(self.trainers):
+            tr.save(self.member_path(directory, m))
+        meta = {"members": self.bank.overrides, "adam_step": int(self.trainers[0].opt.t), "global_step": int(self.global_step)}
+        tmp = os.path.join(directory, "bank.json.tmp")
+        with open(tmp, "w") as f:
+            json.dump(meta, f)
+        os.replace(tmp, os.path.join(directory, "bank.json"))
+
+    def restore(self, directory: str) -> bool:
+        path = os.path.join(directory, "bank.json")
+        if not os.path.exists(path):
+            return False
+        with open(path) as f:
+            meta = json.load(f)
+        if meta["members"] != json.loads(json.dumps(self.bank.overrides)):
+            raise ValueError(f"{path} was written by a bank of other members: {meta['members']}")
+        self.drop_device_state()      # the device-resident copy is rebuilt from the restored state
+        for m, tr in enumerate(self.trainers):
+            if not tr.restore(self.member_path(directory, m)):
+                raise FileNotFoundError(self.member_path(directory, m))
+        self.global_step = int(meta["global_step"])
+        return True
+
+
+def parse_bank_hparams(spec: str) -> List[dict]:
+    """``--bank_hparams "learning_rate=1e-3,3e-3;r_reg=0.1,1"`` -> the Cartesian grid as member overrides, the first name varying slowest:
+    [{lr 1e-3, r_reg 0.1}, {lr 1e-3, r_reg 1}, {lr 3e-3, r_reg 0.1}, {lr 3e-3, r_reg 1}]."""
+    grid: List[dict] = [{}]
+    for item in spec.split(";"):
+        if not item.strip():
+            continue
+        name, _, values = item.partition("=")
+        name = name.strip()
+        if name not in MEMBER_KEYS or name == "seed":
+            raise ValueError(f"--bank_hparams: '{name}' cannot differ inside a bank (learning_rate, h_reg, r_reg)")
+        vals = [float(v) for v in values.split(",") if v.strip()]
+        if not vals:
+            raise ValueError(f"--bank_hparams: no values for '{name}'")
+        grid = [{**g, name: v} for g in grid for v in vals]
+    return grid
+
+
+def bank_members(seed: int, n_seeds: int, spec: str) -> List[dict]:
+    """The members of ``--bank N --bank_hparams SPEC``: every seed of seed .. seed + N - 1 once per grid point (grid point varying slowest)."""
+    grid = parse_bank_hparams(spec) if spec else [{}]
+    return [{**g, "seed": seed + s} for g in grid for s in range(max(int(n_seeds), 1))]

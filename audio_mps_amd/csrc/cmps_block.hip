@@ -17,8 +17,11 @@ namespace cmps {
 // forward
 // ------------------------------------------------------------------------------------------------
 template <int NT>
-__global__ __launch_bounds__(NT) void k_fwd_block(Dev P, const float* __restrict__ audio,
+__global__ __launch_bounds__(NT) void k_fwd_block(Dev Pk, const float* __restrict__ audio,
                                                   float* __restrict__ loss_out, int save) {
+    const Dev P = bank_view(Pk, blockIdx.y);      // the member's workspace (a plain launch: Pk itself)
+    audio += blockIdx.y * P.bank_audio;
+    loss_out += blockIdx.y * P.bank_loss;
     extern __shared__ float2 sh[];
     const int D = P.D, DP = P.DP, N = P.N;
     float2* su = sh;
@@ -77,7 +80,9 @@ __global__ __launch_bounds__(NT) void k_fwd_block(Dev P, const float* __restrict
 //   g       = ybar + Q ybar + s d
 // ------------------------------------------------------------------------------------------------
 template <int NT, int EPT>
-__global__ __launch_bounds__(NT) void k_bwd_block(Dev P, const float* __restrict__ audio) {
+__global__ __launch_bounds__(NT) void k_bwd_block(Dev Pk, const float* __restrict__ audio) {
+    const Dev P = bank_view(Pk, blockIdx.y);      // the member's workspace (a plain launch: Pk itself)
+    audio += blockIdx.y * P.bank_audio;
     extern __shared__ float2 sh[];
     const int D = P.D, DP = P.DP, N = P.N;
     float2* sy = sh;            // y_k
@@ -199,7 +204,10 @@ __global__ __launch_bounds__(NT) void k_bwd_block(Dev P, const float* __restrict
 // ------------------------------------------------------------------------------------------------
 // two passes, fixed summation order (deterministic): RPART row-groups of clips, then the groups
 constexpr int RPART = 32;
-__global__ void k_reduce_slabs(Dev P, float* __restrict__ part) {
+// (a bank: member = blockIdx.z here, blockIdx.y in the two kernels behind it; `part` and `sums` lie in the member's workspace)
+__global__ void k_reduce_slabs(Dev Pk, float* __restrict__ part) {
+    const Dev P = bank_view(Pk, blockIdx.z);
+    part = bank_shift(part, blockIdx.z * P.bank_stride);
     const size_t col = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (col >= P.slab_floats) return;
     const int g = blockIdx.y;
@@ -210,7 +218,10 @@ __global__ void k_reduce_slabs(Dev P, float* __restrict__ part) {
     for (int b = b0; b < b1; ++b) acc += (double)P.slabs[(size_t)b * P.slab_floats + col];
     reinterpret_cast<double*>(part)[(size_t)g * P.slab_floats + col] = acc;
 }
-__global__ void k_reduce_parts(Dev P, const float* __restrict__ part, float* __restrict__ sums) {
+__global__ void k_reduce_parts(Dev Pk, const float* __restrict__ part, float* __restrict__ sums) {
+    const Dev& P = Pk;
+    part = bank_shift(part, blockIdx.y * P.bank_stride);
+    sums = bank_shift(sums, blockIdx.y * P.bank_stride);
     const size_t col = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (col >= P.slab_floats) return;
     double acc = 0.0;
@@ -218,8 +229,12 @@ __global__ void k_reduce_parts(Dev P, const float* __restrict__ part, float* __r
     sums[col] = (float)acc;
 }
 
-__global__ void k_finalize(Dev P, const float* __restrict__ sums, const float* __restrict__ loss,
+__global__ void k_finalize(Dev Pk, const float* __restrict__ sums, const float* __restrict__ loss,
                            float* __restrict__ grad_out) {
+    const Dev P = bank_view(Pk, blockIdx.y);
+    sums = bank_shift(sums, blockIdx.y * P.bank_stride);
+    loss += blockIdx.y * P.bank_loss;
+    grad_out += blockIdx.y * P.bank_grad;
     const int D = P.D, DP = P.DP, DD = DP * DP;
     const int tid = blockIdx.x * blockDim.x + threadIdx.x;
     const int nthreads = gridDim.x * blockDim.x;
@@ -481,29 +496,29 @@ __global__ __launch_bounds__(NT) void k_sample_block(Dev P, const float* __restr
 // ------------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------------
-hipError_t launch_fwd_block(const Dev& P, const float* audio, float* loss, bool save, hipStream_t s) {
+hipError_t launch_fwd_block(const Dev& P, const float* audio, float* loss, bool save, hipStream_t s, int M) {
     const size_t shm = (size_t)2 * P.D * sizeof(float2) + 64;
     return dispatch_block_nt(P.D, [&](auto nt) {
         constexpr int NT = decltype(nt)::value;
-        hipLaunchKernelGGL(k_fwd_block<NT>, dim3(P.B), dim3(NT), shm, s, P, audio, loss, save ? 1 : 0);
+        hipLaunchKernelGGL(k_fwd_block<NT>, dim3(P.B, M), dim3(NT), shm, s, P, audio, loss, save ? 1 : 0);
         return hipGetLastError();
     });
 }
 
-hipError_t launch_bwd_block(const Dev& P, const float* audio, hipStream_t s) {
+hipError_t launch_bwd_block(const Dev& P, const float* audio, hipStream_t s, int M) {
     const size_t shm = (size_t)3 * P.D * sizeof(float2) + 128;
     return dispatch_block_bwd(P.D, [&](auto nt) {
         constexpr int NT = decltype(nt)::value;
-        hipLaunchKernelGGL((k_bwd_block<NT, BLOCK_EPT>), dim3(P.B), dim3(NT), shm, s, P, audio);
+        hipLaunchKernelGGL((k_bwd_block<NT, BLOCK_EPT>), dim3(P.B, M), dim3(NT), shm, s, P, audio);
         return hipGetLastError();
     });
 }
 
-hipError_t launch_reduce_only(const Dev& P, hipStream_t s) {
+hipError_t launch_reduce_only(const Dev& P, hipStream_t s, int M) {
     const unsigned nb = (unsigned)((P.slab_floats + 255) / 256);
     float* part = P.sums + ((P.slab_floats + 63) / 64) * 64;          // RPART x slab doubles behind the sums
-    hipLaunchKernelGGL(k_reduce_slabs, dim3(nb, RPART), dim3(256), 0, s, P, part);
-    hipLaunchKernelGGL(k_reduce_parts, dim3(nb), dim3(256), 0, s, P, (const float*)part, P.sums);
+    hipLaunchKernelGGL(k_reduce_slabs, dim3(nb, RPART, M), dim3(256), 0, s, P, part);
+    hipLaunchKernelGGL(k_reduce_parts, dim3(nb, M), dim3(256), 0, s, P, (const float*)part, P.sums);
     return hipGetLastError();
 }
 
@@ -514,15 +529,15 @@ static unsigned finalize_blocks(const Dev& P) {
     return nb < 8 ? 8 : nb;
 }
 
-hipError_t launch_reduce_finalize(const Dev& P, const float* loss, float* grad_out, hipStream_t s) {
-    const hipError_t e = launch_reduce_only(P, s);     // its hipGetLastError() has consumed the launch status
+hipError_t launch_reduce_finalize(const Dev& P, const float* loss, float* grad_out, hipStream_t s, int M) {
+    const hipError_t e = launch_reduce_only(P, s, M);     // its hipGetLastError() has consumed the launch status
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_finalize, dim3(finalize_blocks(P)), dim3(256), 0, s, P, (const float*)P.sums, loss, grad_out);
+    hipLaunchKernelGGL(k_finalize, dim3(finalize_blocks(P), M), dim3(256), 0, s, P, (const float*)P.sums, loss, grad_out);
     return hipGetLastError();
 }
 
-hipError_t launch_finalize_only(const Dev& P, const float* loss, float* grad_out, hipStream_t s) {
-    hipLaunchKernelGGL(k_finalize, dim3(finalize_blocks(P)), dim3(256), 0, s, P, (const float*)P.sums, loss, grad_out);
+hipError_t launch_finalize_only(const Dev& P, const float* loss, float* grad_out, hipStream_t s, int M) {
+    hipLaunchKernelGGL(k_finalize, dim3(finalize_blocks(P), M), dim3(256), 0, s, P, (const float*)P.sums, loss, grad_out);
     return hipGetLastError();
 }
 

@@ -26,6 +26,7 @@ struct Saved {
     bool bwd_ok = false;           // rho: written by cmps_rho_loss_fwd (not by the sampler), a reverse pass may follow
     bool grad1 = false;            // rho: the GEMM forward accumulated RhoDev::p1
     int k0 = 0;                    // rho: the table row of the first saved step (a cmps_rho_stream segment; else 0)
+    int M = 0, n_audio = 0;        // main: written by cmps_bank_loss_fwd for M members from n_audio batches (0: a plain forward)
 };
 
 struct cmps_handle_s {
@@ -38,6 +39,7 @@ struct cmps_handle_s {
     bool rho_virtual_bwd = true;   // CMPS_OPT_RHO_BWD: the RhoCMPS GEMM forward's reverse sweep on virtual clips of k_bwd_wave (else k_bwd_rho_mfma)
     bool params_set = false;
     bool legacy = false;       // the tables currently hold the legacy AudioMPS arithmetic (cmps_legacy_set_params)
+    int bank_M = 0;            // > 0: the workspace holds the tables of a bank of bank_M members (cmps_bank_set_params_dev); 0: plain mode
     Saved main, rho;           // the stash of the main workspace (cmps_psi_* / cmps_legacy_* entries) and of the rho workspace
     Layout L{};
     Dev P{};                   // (stash_layout stays 0 here: main_dev() fills it from `main` for the kernels that read the stash)
@@ -182,6 +184,12 @@ int check_bwd(cmps_handle_t h, const char* who, bool ready, const char* fwd, con
     if (B != S.B || T != S.steps + 1 || audio != S.audio) return fail(h, CMPS_ERR_STATE, w + ": audio / B / T differ from the forward call");
     return CMPS_OK;
 }
+// What every plain entry outside a bank's scope (samplers, streams, state read-outs, ancilla updates, cmps_rho_set_state,
+// cmps_psi_grad_status) answers while the workspace holds a bank: its tables would be member 0's alone.  A member is taken out as a plain model.
+int check_not_bank(cmps_handle_t h, const char* who) {
+    if (!h->bank_M) return CMPS_OK;
+    return fail(h, CMPS_ERR_STATE, std::string(who) + ": the handle holds a bank (cmps_bank_set_params_dev); call cmps_set_params for one model first");
+}
 
 // the end of a reverse pass whose slabs hold one PAIR of clips each (pair and wide kernels): reduce over (B + 1) / 2 slabs, closing terms
 hipError_t reduce_pairs_finalize(Dev P, int abar_fix, const float* loss, float* grad_out, hipStream_t s) {
@@ -292,23 +300,28 @@ size_t cmps_workspace_bytes(int D, int B, int T, int flags) {
 static int set_params_impl(cmps_handle_t h, const float* R_re_dev, const float* R_im_dev,
                            const float* freqs_dev, const float* psi0_re_dev, const float* psi0_im_dev,
                            float A, const float* A_dev, double sigma, double delta_t, int T, int B_max, int flags,
-                           void* workspace_dev, size_t workspace_bytes, void* stream) {
+                           void* workspace_dev, size_t workspace_bytes, void* stream, int M = 0) {
+    const std::string w(M > 0 ? "cmps_bank_set_params_dev" : "cmps_set_params");     // the entry that speaks in the messages
+    // M > 0 (cmps_bank_set_params_dev, which has checked its own arguments): the parameter pointers are member 0's, member m's lie
+    // m (2 D^2 + 3 D + 1) floats behind them, and member m's workspace is the plain layout at byte m * L.total
     if (!h) return CMPS_ERR_BAD_ARG;
     if (!R_re_dev || !R_im_dev || !freqs_dev || !psi0_re_dev || !psi0_im_dev)
-        return fail(h, CMPS_ERR_BAD_ARG, "cmps_set_params: null parameter pointer");
-    if (T < 2 || B_max < 1) return fail(h, CMPS_ERR_BAD_ARG, "cmps_set_params: need T >= 2 and B_max >= 1");
-    if (!workspace_dev) return fail(h, CMPS_ERR_WORKSPACE, "cmps_set_params: null workspace");
+        return fail(h, CMPS_ERR_BAD_ARG, w + ": null parameter pointer");
+    if (T < 2 || B_max < 1) return fail(h, CMPS_ERR_BAD_ARG, w + ": need T >= 2 and B_max >= 1");
+    if (!workspace_dev) return fail(h, CMPS_ERR_WORKSPACE, w + ": null workspace");
     // the cached time table is trusted only when the caller says the workspace is untouched (and never with CMPS_WS_FRESH)
     const bool fresh = (flags & CMPS_WS_FRESH) != 0 || (flags & CMPS_WS_REUSE_TABLES) == 0;
     flags &= ~(CMPS_WS_FRESH | CMPS_WS_REUSE_TABLES);
     Layout L = make_layout(h->D, B_max, T, flags);
-    if (workspace_bytes < L.total) {
+    const size_t members = M > 0 ? (size_t)M : 1, n_par = 2 * (size_t)h->D * h->D + 3 * (size_t)h->D + 1;
+    if (workspace_bytes < members * L.total) {
         char buf[160];
-        snprintf(buf, sizeof buf, "cmps_set_params: workspace has %zu bytes, needs %zu", workspace_bytes, L.total);
+        snprintf(buf, sizeof buf, "%s: workspace has %zu bytes, needs %zu", w.c_str(), workspace_bytes,
+                 members * L.total);
         return fail(h, CMPS_ERR_WORKSPACE, buf);
     }
     if (((uintptr_t)workspace_dev & 255) != 0)
-        return fail(h, CMPS_ERR_WORKSPACE, "cmps_set_params: workspace must be 256-byte aligned");
+        return fail(h, CMPS_ERR_WORKSPACE, w + ": workspace must be 256-byte aligned");
     char* ws = static_cast<char*>(workspace_dev);
     Dev P = bind_workspace(L, ws);
     P.ttab = reinterpret_cast<float*>(ws + L.off_ttab);
@@ -319,25 +332,31 @@ static int set_params_impl(cmps_handle_t h, const float* R_re_dev, const float* 
     P.c_half = (float)(-delta_t * sigma * sigma) / 2.0f;
     const float dt = (float)delta_t;  // model.py:16
     P.dt = dt;
-    const bool rebuild = fresh || !(h->tt_ws == ws && h->tt_N == L.N && h->tt_dt == dt);
+    if (M > 0) { P.bank_stride = L.total; P.bank_adev = n_par; }
+    // (a bank's members each have a time table: another member count, or a change between bank and plain mode, moves or adds tables)
+    const bool rebuild = fresh || h->bank_M != M || (M > 0 && h->P.bank_stride != L.total) || !(h->tt_ws == ws && h->tt_N == L.N && h->tt_dt == dt);
     hipError_t e = launch_prep(P, R_re_dev, R_im_dev, freqs_dev, psi0_re_dev, psi0_im_dev, dt, rebuild,
                                const_cast<float*>(P.ttab), const_cast<float*>(P.dtk),
                                const_cast<float2*>(P.R), const_cast<float2*>(P.RT),
                                const_cast<float2*>(P.Q), const_cast<float2*>(P.psi0),
                                const_cast<float*>(P.freqs), const_cast<float2*>(P.rho),
-                               reinterpret_cast<double2*>(ws + L.off_rfix), static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return fail_hip(h, e, "cmps_set_params");
+                               reinterpret_cast<double2*>(ws + L.off_rfix), static_cast<hipStream_t>(stream), (int)members, M > 0 ? n_par : 0);
+    if (e != hipSuccess) return fail_hip(h, e, w.c_str());
     // a workspace this handle cannot vouch for, or flag words that moved: the layout puts them behind the stash and the slabs, so with
     // CMPS_WS_REUSE_TABLES and another T, B_max or TRAIN flag (or after the legacy mode) their address holds something else -- the flag
     // words start at zero
-    if (P.status && (fresh || h->ws != ws || h->legacy || !h->params_set || h->P.status != P.status)) {
-        e = hipMemsetAsync(P.status, 0, 2 * sizeof(unsigned), static_cast<hipStream_t>(stream));
-        if (e != hipSuccess) return fail_hip(h, e, "cmps_set_params (status words)");
+    if (P.status && (fresh || h->ws != ws || h->legacy || !h->params_set || h->P.status != P.status || h->bank_M != M ||
+                     h->P.bank_stride != P.bank_stride)) {
+        // (every member's pair of words, one workspace apart: one strided fill)
+        e = M > 0 ? hipMemset2DAsync(P.status, L.total, 0, 2 * sizeof(unsigned), members, static_cast<hipStream_t>(stream))
+                  : hipMemsetAsync(P.status, 0, 2 * sizeof(unsigned), static_cast<hipStream_t>(stream));
+        if (e != hipSuccess) return fail_hip(h, e, (w + " (status words)").c_str());
     }
     h->tt_ws = ws; h->tt_N = L.N; h->tt_dt = dt;
     h->L = L; h->P = P; h->ws = ws;
     h->params_set = true;
     h->legacy = false;
+    h->bank_M = M;
     h->main.valid = false;
     h->rho_set = false;               // the columns of rho_0 are handed over again after every parameter change
     h->rho.valid = false;
@@ -404,13 +423,13 @@ int cmps_rho_apply_step(cmps_handle_t h, float* vars_dev, float* adam_m_dev, flo
     return CMPS_OK;
 }
 
-int cmps_psi_loss_fwd(cmps_handle_t h, const float* audio_dev, int B, int T, float* loss_dev,
-                      int save_for_bwd, void* stream) {
-    if (!h) return CMPS_ERR_BAD_ARG;
-    if (const int rc = check_fwd(h, "cmps_psi_loss_fwd", h->params_set && !h->legacy, "cmps_set_params", audio_dev, loss_dev, B, T,
-                                 h->L.T, h->L.B, save_for_bwd, h->L.flags)) return rc;
+// cmps_psi_loss_fwd (M = 0) and cmps_bank_loss_fwd (M members, n_audio batches) behind their argument checks
+static int psi_fwd_run(cmps_handle_t h, const char* who, int M, int n_audio, const float* audio_dev, int B, int T, float* loss_dev,
+                       int save_for_bwd, void* stream) {
     Dev P = h->P;
     P.B = B;
+    const int Mk = M > 0 ? M : 1;
+    if (M > 0) { P.bank_audio = n_audio == 1 ? 0 : (size_t)B * T; P.bank_loss = (size_t)B; }
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int variant = resolve_variant(h);
     KBind kb(h);
@@ -424,24 +443,38 @@ int cmps_psi_loss_fwd(cmps_handle_t h, const float* audio_dev, int B, int T, flo
     const bool norm_rows = save && family == STASH_WAVE32 && bwd_two_wave(h) && !CMPS_DIAG_YHY_ROWS;
     hipError_t e;
     switch (family) {
-    case STASH_WAVE16: { KScope ks("k_fwd_wave16", s); e = launch_fwd_wave16(P, audio_dev, loss_dev, save, s); } break;
+    case STASH_WAVE16: { KScope ks("k_fwd_wave16", s); e = launch_fwd_wave16(P, audio_dev, loss_dev, save, s, Mk); } break;
     // the loss product's pieces follow CMPS_OPT_RANK1 like the reverse scan's rank-1 sums: two fp16 pieces for F16X2 / DEFAULT
-    case STASH_WAVE32: { KScope ks("k_fwd_wave2", s); e = launch_fwd_wave2(P, audio_dev, loss_dev, save, f16, norm_rows, s); } break;
+    case STASH_WAVE32: { KScope ks("k_fwd_wave2", s); e = launch_fwd_wave2(P, audio_dev, loss_dev, save, f16, norm_rows, s, Mk); } break;
     case STASH_PAIR: { KScope ks("k_fwd_pair", s); e = launch_fwd_pair(P, audio_dev, loss_dev, save, s); } break;
     // k_fwd_wide, k_hy_wide, k_loss_wide (scopes inside); the loss product's pieces follow CMPS_OPT_RANK1 like the gradient GEMM's
     case STASH_WIDE: e = launch_fwd_wide(P, audio_dev, loss_dev, save, f16, h->wide_chain != CMPS_WIDE_CHAIN_VALU, s); break;
-    default: { KScope ks("k_fwd_block", s); e = launch_fwd_block(P, audio_dev, loss_dev, save, s); } break;
+    default: { KScope ks("k_fwd_block", s); e = launch_fwd_block(P, audio_dev, loss_dev, save, s, Mk); } break;
     }
-    if (e != hipSuccess) return fail_hip(h, e, "cmps_psi_loss_fwd");
+    if (e != hipSuccess) return fail_hip(h, e, who);
     h->main = Saved{save, B, T - 1, audio_dev, loss_dev, norm_rows ? (int)STASH_WAVE32N : family};
+    h->main.M = M; h->main.n_audio = M > 0 ? n_audio : 0;
     return CMPS_OK;
 }
 
-int cmps_psi_loss_bwd(cmps_handle_t h, const float* audio_dev, int B, int T, float* grad_dev, void* stream) {
+int cmps_psi_loss_fwd(cmps_handle_t h, const float* audio_dev, int B, int T, float* loss_dev,
+                      int save_for_bwd, void* stream) {
     if (!h) return CMPS_ERR_BAD_ARG;
-    if (const int rc = check_bwd(h, "cmps_psi_loss_bwd", h->params_set && !h->legacy, "cmps_psi_loss_fwd", h->main, audio_dev, grad_dev, B, T))
-        return rc;
+    if (const int rc = check_fwd(h, "cmps_psi_loss_fwd", h->params_set && !h->legacy && !h->bank_M, "cmps_set_params", audio_dev, loss_dev, B, T,
+                                 h->L.T, h->L.B, save_for_bwd, h->L.flags)) return rc;
+    return psi_fwd_run(h, "cmps_psi_loss_fwd", 0, 0, audio_dev, B, T, loss_dev, save_for_bwd, stream);
+}
+
+// cmps_psi_loss_bwd (M = 0) and cmps_bank_loss_bwd behind their argument checks
+static int psi_bwd_run(cmps_handle_t h, const char* who, int M, int n_audio, const float* audio_dev, int B, int T, float* grad_dev, void* stream) {
+    const auto failed = [&](hipError_t e, const char* stage) { return fail_hip(h, e, (std::string(who) + stage).c_str()); };
     Dev P = main_dev(h, B);
+    const int Mk = M > 0 ? M : 1;
+    if (M > 0) {
+        P.bank_audio = n_audio == 1 ? 0 : (size_t)B * T;
+        P.bank_loss = (size_t)B;
+        P.bank_grad = 2 * (size_t)h->D * h->D + 3 * (size_t)h->D + 2;
+    }
     P.f16_shift = h->f16_shift;
     hipStream_t s = static_cast<hipStream_t>(stream);
     // the reverse kernels belong to the family whose forward wrote the stash
@@ -453,9 +486,9 @@ int cmps_psi_loss_bwd(cmps_handle_t h, const float* audio_dev, int B, int T, flo
         hipError_t e;
         { KScope ks("k_bwd_pair", s); e = launch_bwd_pair(P, audio_dev, s); }
         if (e == hipSuccess) { KScope ks("k_grad_gemm<1>", s); e = launch_grad_pair(P, audio_dev, s); }
-        if (e != hipSuccess) return fail_hip(h, e, "cmps_psi_loss_bwd (pair scan)");
+        if (e != hipSuccess) return failed(e, " (pair scan)");
         e = reduce_pairs_finalize(P, 0, loss, grad_dev, s);
-        if (e != hipSuccess) return fail_hip(h, e, "cmps_psi_loss_bwd (pair reduce)");
+        if (e != hipSuccess) return failed(e, " (pair reduce)");
         return CMPS_OK;
     }
     if (layout == STASH_WIDE) {
@@ -468,10 +501,10 @@ int cmps_psi_loss_bwd(cmps_handle_t h, const float* audio_dev, int B, int T, flo
             KScope ks(pieces == -2 ? "k_grad_gemm<f16x2>" : pieces == 2 ? "k_grad_gemm<2>" : "k_grad_gemm<3>", s);
             e = launch_grad_wide(P, audio_dev, pieces, s);
         }
-        if (e != hipSuccess) return fail_hip(h, e, "cmps_psi_loss_bwd (wide scan)");
+        if (e != hipSuccess) return failed(e, " (wide scan)");
         // abar_fix: the merged mat-vec, k_finalize removes the Q part of sum Re(u^dagger (Q + s R^dagger) ybar)
         e = reduce_pairs_finalize(P, 1, loss, grad_dev, s);
-        if (e != hipSuccess) return fail_hip(h, e, "cmps_psi_loss_bwd (wide reduce)");
+        if (e != hipSuccess) return failed(e, " (wide reduce)");
         return CMPS_OK;
     }
     const bool w16 = layout == STASH_WAVE16, norm_rows = layout == STASH_WAVE32N, wave = w16 || layout == STASH_WAVE32 || norm_rows;
@@ -481,19 +514,28 @@ int cmps_psi_loss_bwd(cmps_handle_t h, const float* audio_dev, int B, int T, flo
         // move the reverse pass of THAT forward to a kernel that would misread them
         const bool two = norm_rows || (wave && !w16 && bwd_two_wave(h));
         KScope ks(!wave ? "k_bwd_block" : w16 ? "k_bwd_wave16" : two ? "k_bwd_wave2w" : "k_bwd_wave", s);
-        e = !wave ? launch_bwd_block(P, audio_dev, s) : w16 ? launch_bwd_wave16(P, audio_dev, s)
-          : two ? launch_bwd_wave2w(P, audio_dev, s) : launch_bwd_wave(P, audio_dev, wave_rank1(h->rank1_mode), s);
+        e = !wave ? launch_bwd_block(P, audio_dev, s, Mk) : w16 ? launch_bwd_wave16(P, audio_dev, s, Mk)
+          : two ? launch_bwd_wave2w(P, audio_dev, s, Mk) : launch_bwd_wave(P, audio_dev, wave_rank1(h->rank1_mode), s);
     }
-    if (e != hipSuccess) return fail_hip(h, e, "cmps_psi_loss_bwd (scan)");
+    if (e != hipSuccess) return failed(e, " (scan)");
     P.abar_fix = wave ? 1 : 0;
     KScope ks("reduce + finalize", s);
-    e = launch_reduce_finalize(P, loss, grad_dev, s);
-    if (e != hipSuccess) return fail_hip(h, e, "cmps_psi_loss_bwd (reduce)");
+    e = launch_reduce_finalize(P, loss, grad_dev, s, Mk);
+    if (e != hipSuccess) return failed(e, " (reduce)");
     return CMPS_OK;
+}
+
+int cmps_psi_loss_bwd(cmps_handle_t h, const float* audio_dev, int B, int T, float* grad_dev, void* stream) {
+    if (!h) return CMPS_ERR_BAD_ARG;
+    if (const int rc = check_bwd(h, "cmps_psi_loss_bwd", h->params_set && !h->legacy && !h->bank_M && h->main.M == 0, "cmps_psi_loss_fwd", h->main,
+                                 audio_dev, grad_dev, B, T))
+        return rc;
+    return psi_bwd_run(h, "cmps_psi_loss_bwd", 0, 0, audio_dev, B, T, grad_dev, stream);
 }
 
 int cmps_psi_grad_status(cmps_handle_t h, int* sticky_out, void* stream) {
     if (!h) return CMPS_ERR_BAD_ARG;
+    if (const int rc = check_not_bank(h, "cmps_psi_grad_status")) return rc;
     if (sticky_out) *sticky_out = 0;
     if (!h->params_set || h->legacy || !h->P.status)
         return fail(h, CMPS_ERR_STATE, "cmps_psi_grad_status: needs cmps_set_params with a CMPS_WS_TRAIN workspace");
@@ -512,9 +554,122 @@ int cmps_psi_grad_status(cmps_handle_t h, int* sticky_out, void* stream) {
     return CMPS_OK;
 }
 
+// ---- model bank: M same-shape PsiCMPS models per launch (include/cmps.h) ----
+
+constexpr int BANK_MAX = 1024;
+
+// What every bank entry that launches scans refuses before it looks at its arguments: the kernel families without a member dimension
+// (wide / pair: AUTO above D = 32), the legacy tables, and the options that would select the one-wave k_bwd_wave or change its scales.
+static int bank_check_mode(cmps_handle_t h, const char* who, bool tables) {
+    const std::string w(who);
+    if (h->D > 32 && resolve_variant(h) != CMPS_VARIANT_BLOCK)
+        return fail(h, CMPS_ERR_UNSUPPORTED_D, w + ": a bank above D = 32 needs CMPS_VARIANT_BLOCK (the wide and pair kernels have no member dimension)");
+    if (tables && h->legacy) return fail(h, CMPS_ERR_STATE, w + ": not available in legacy mode");
+    if (h->rank1_mode != CMPS_RANK1_DEFAULT || h->bwd_waves != 2 || h->f16_shift != 0)
+        return fail(h, CMPS_ERR_STATE, w + ": a bank runs with the default CMPS_OPT_RANK1, CMPS_OPT_BWD_WAVES and CMPS_OPT_F16_SCALE_SHIFT only");
+    return CMPS_OK;
+}
+static int bank_check_M(cmps_handle_t h, const char* who, int M) {
+    if (M < 1 || M > BANK_MAX) return fail(h, CMPS_ERR_BAD_ARG, std::string(who) + ": M outside [1, 1024]");
+    return CMPS_OK;
+}
+static int bank_check_shape(cmps_handle_t h, const char* who, int M, int B, int T) {
+    const std::string w(who);
+    if (B < 1 || T < 2) return fail(h, CMPS_ERR_BAD_ARG, w + ": need B >= 1 and T >= 2");
+    if ((unsigned long long)M * (unsigned long long)B * (unsigned long long)T > 0x7fffffffull)
+        return fail(h, CMPS_ERR_BAD_ARG, w + ": M * B * T overflows");
+    return CMPS_OK;
+}
+
+size_t cmps_bank_workspace_bytes(int D, int M, int B, int T, int flags) {
+    if (M < 1 || M > BANK_MAX) return 0;
+    return (size_t)M * cmps_workspace_bytes(D, B, T, flags);
+}
+
+int cmps_bank_set_params_dev(cmps_handle_t h, int M, const float* params_dev, double sigma, double delta_t, int T, int B_max, int flags,
+                             void* workspace_dev, size_t workspace_bytes, void* stream) {
+    const char* who = "cmps_bank_set_params_dev";
+    if (!h) return CMPS_ERR_BAD_ARG;
+    if (const int rc = bank_check_mode(h, who, false)) return rc;
+    if (!params_dev) return fail(h, CMPS_ERR_BAD_ARG, std::string(who) + ": null parameter buffer");
+    if (const int rc = bank_check_M(h, who, M)) return rc;
+    if (const int rc = bank_check_shape(h, who, M, B_max, T)) return rc;
+    if (!workspace_dev) return fail(h, CMPS_ERR_WORKSPACE, std::string(who) + ": null workspace");
+    const size_t DD = (size_t)h->D * h->D, D = (size_t)h->D;
+    return set_params_impl(h, params_dev, params_dev + DD, params_dev + 2 * DD, params_dev + 2 * DD + D, params_dev + 2 * DD + 2 * D,
+                           0.f, params_dev + 2 * DD + 3 * D, sigma, delta_t, T, B_max, flags, workspace_dev, workspace_bytes, stream, M);
+}
+
+int cmps_bank_loss_fwd(cmps_handle_t h, const float* audio_dev, int n_audio, int B, int T, float* loss_dev, int save_for_bwd, void* stream) {
+    const char* who = "cmps_bank_loss_fwd";
+    if (!h) return CMPS_ERR_BAD_ARG;
+    if (const int rc = bank_check_mode(h, who, true)) return rc;
+    if (const int rc = check_fwd(h, who, h->params_set && !h->legacy && h->bank_M > 0, "cmps_bank_set_params_dev", audio_dev, loss_dev, B, T,
+                                 h->L.T, h->L.B, save_for_bwd, h->L.flags)) return rc;
+    if (n_audio != 1 && n_audio != h->bank_M) return fail(h, CMPS_ERR_BAD_ARG, std::string(who) + ": n_audio must be 1 (one shared batch) or M");
+    return psi_fwd_run(h, who, h->bank_M, n_audio, audio_dev, B, T, loss_dev, save_for_bwd, stream);
+}
+
+int cmps_bank_loss_bwd(cmps_handle_t h, const float* audio_dev, int n_audio, int B, int T, float* grad_dev, void* stream) {
+    const char* who = "cmps_bank_loss_bwd";
+    if (!h) return CMPS_ERR_BAD_ARG;
+    if (const int rc = bank_check_mode(h, who, true)) return rc;
+    const bool ready = h->params_set && !h->legacy && h->bank_M > 0 && h->main.M == h->bank_M;
+    if (const int rc = check_bwd(h, who, ready, "cmps_bank_loss_fwd", h->main, audio_dev, grad_dev, B, T)) return rc;
+    if (n_audio != h->main.n_audio) return fail(h, CMPS_ERR_STATE, std::string(who) + ": n_audio differs from the forward call");
+    return psi_bwd_run(h, who, h->bank_M, n_audio, audio_dev, B, T, grad_dev, stream);
+}
+
+size_t cmps_bank_apply_step_scratch_bytes(int D, int M) {
+    return (M < 1 || M > BANK_MAX) ? 0 : (size_t)M * cmps_apply_step_scratch_bytes(D);
+}
+
+int cmps_bank_apply_step(cmps_handle_t h, int M, float* vars_dev, float* adam_m_dev, float* adam_v_dev, const float* grad_sums_dev,
+                         double global_batch, double bias_num, double bias_den, double beta1, double beta2, double epsilon,
+                         const double* hyper_dev, int with_reg, float* params_dev, float* losses_dev, void* scratch_dev, void* stream) {
+    const std::string w("cmps_bank_apply_step");
+    if (!h) return CMPS_ERR_BAD_ARG;
+    if (!vars_dev || !params_dev || !hyper_dev) return fail(h, CMPS_ERR_BAD_ARG, w + ": null variable / parameter / hyper-parameter buffer");
+    if (const int rc = bank_check_M(h, "cmps_bank_apply_step", M)) return rc;
+    const bool apply = grad_sums_dev != nullptr;
+    if (apply && (!adam_m_dev || !adam_v_dev || !losses_dev || !scratch_dev || !(global_batch > 0.0)))
+        return fail(h, CMPS_ERR_BAD_ARG, w + ": an update needs the Adam slots, losses_dev, scratch_dev and a positive batch");
+    if (((uintptr_t)scratch_dev & 7) != 0) return fail(h, CMPS_ERR_BAD_ARG, w + ": scratch_dev must be 8-byte aligned");
+    if (((uintptr_t)hyper_dev & 7) != 0) return fail(h, CMPS_ERR_BAD_ARG, w + ": hyper_dev must be 8-byte aligned");
+    const hipError_t e = launch_bank_apply_step(h->D, M, apply, apply ? 1.0 / global_batch : 0.0, bias_num, bias_den, beta1, beta2, epsilon,
+                                                hyper_dev, with_reg != 0, vars_dev, adam_m_dev, adam_v_dev, grad_sums_dev, params_dev,
+                                                losses_dev, static_cast<double*>(scratch_dev), static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail_hip(h, e, "cmps_bank_apply_step");
+    return CMPS_OK;
+}
+
+int cmps_bank_grad_status(cmps_handle_t h, int* codes_out, int* sticky_out, void* stream) {
+    const std::string w("cmps_bank_grad_status");
+    if (!h) return CMPS_ERR_BAD_ARG;
+    if (!codes_out) return fail(h, CMPS_ERR_BAD_ARG, w + ": null codes_out");
+    if (!h->params_set || h->legacy || h->bank_M < 1 || !h->P.status)
+        return fail(h, CMPS_ERR_STATE, w + ": needs cmps_bank_set_params_dev with a CMPS_WS_TRAIN workspace");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int M = h->bank_M;
+    std::vector<unsigned> words(2 * (size_t)M, 0u);
+    // the members' pairs of words lie one workspace apart: one strided copy, then the sticky words restart with one strided fill
+    hipError_t e = hipMemcpy2DAsync(words.data(), 2 * sizeof(unsigned), h->P.status, h->P.bank_stride, 2 * sizeof(unsigned), (size_t)M,
+                                    hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemset2DAsync(h->P.status + 1, h->P.bank_stride, 0, sizeof(unsigned), (size_t)M, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return fail_hip(h, e, "cmps_bank_grad_status");
+    for (int m = 0; m < M; ++m) {
+        const unsigned now = words[2 * m];
+        codes_out[m] = ((now & 1u) && !(now & 2u)) ? CMPS_ERR_F16_RANGE : CMPS_OK;
+        if (sticky_out) sticky_out[m] = (int)words[2 * m + 1];
+    }
+    return CMPS_OK;
+}
+
 int cmps_psi_update_ancilla(cmps_handle_t h, const float* psi_in_dev, const float* signal_dev, float t,
                             int B, float* psi_out_dev, void* stream) {
     if (!h) return CMPS_ERR_BAD_ARG;
+    if (const int rc = check_not_bank(h, "cmps_psi_update_ancilla")) return rc;
     if (!h->params_set) return fail(h, CMPS_ERR_STATE, "cmps_psi_update_ancilla: call cmps_set_params first");
     if (!psi_in_dev || !signal_dev || !psi_out_dev || B < 1)
         return fail(h, CMPS_ERR_BAD_ARG, "cmps_psi_update_ancilla: bad argument");
@@ -526,9 +681,10 @@ int cmps_psi_update_ancilla(cmps_handle_t h, const float* psi_in_dev, const floa
 
 int cmps_psi_states(cmps_handle_t h, int B, int T, float* psi_out_dev, void* stream) {
     if (!h) return CMPS_ERR_BAD_ARG;
+    if (const int rc = check_not_bank(h, "cmps_psi_states")) return rc;
     if (h->legacy)               // (k_states rotates into the lab frame with freqs and the time table; neither exists after cmps_legacy_set_params)
         return fail(h, CMPS_ERR_STATE, "cmps_psi_states: not available in legacy mode (no time table for the lab-frame phases)");
-    if (!h->params_set || !h->main.valid)
+    if (!h->params_set || !h->main.valid || h->main.M != 0)
         return fail(h, CMPS_ERR_STATE, "cmps_psi_states: needs cmps_psi_loss_fwd(save_for_bwd=1) first");
     if (!psi_out_dev || B != h->main.B || T != h->main.steps + 1)
         return fail(h, CMPS_ERR_BAD_ARG, "cmps_psi_states: bad argument");
@@ -607,6 +763,7 @@ static int psi_sample_launch(cmps_handle_t h, const char* who, const SampleDev& 
 
 int cmps_psi_sample(cmps_handle_t h, const float* noise_dev, int n, int length, float* out_dev, void* stream) {
     if (!h) return CMPS_ERR_BAD_ARG;
+    if (const int rc = check_not_bank(h, "cmps_psi_sample")) return rc;
     if (!h->params_set) return fail(h, CMPS_ERR_STATE, "cmps_psi_sample: call cmps_set_params first");
     if (!noise_dev || !out_dev || n < 1 || length < 1)
         return fail(h, CMPS_ERR_BAD_ARG, "cmps_psi_sample: bad argument");
@@ -618,6 +775,7 @@ int cmps_psi_sample(cmps_handle_t h, const float* noise_dev, int n, int length, 
 int cmps_psi_sample_primed(cmps_handle_t h, const float* prime_dev, int n_prime, int prime_T, const float* noise_dev, int n, int length,
                            float* out_dev, float* pred_dev, void* stream) {
     if (!h) return CMPS_ERR_BAD_ARG;
+    if (const int rc = check_not_bank(h, "cmps_psi_sample_primed")) return rc;
     if (!h->params_set || h->legacy)       // (the legacy tables carry no rotation and another step: nothing here would mean PsiCMPS.sample)
         return fail(h, CMPS_ERR_STATE, "cmps_psi_sample_primed: call cmps_set_params first (not available in legacy mode)");
     SampleDev S;
@@ -633,6 +791,7 @@ size_t cmps_psi_stream_state_bytes(cmps_handle_t h, int n) {
 int cmps_psi_stream(cmps_handle_t h, const void* state_in_dev, void* state_out_dev, int k0, const float* audio_dev, int n_audio, int forced,
                     const float* noise_dev, int length, int n, float* out_dev, float* pred_dev, void* stream) {
     if (!h) return CMPS_ERR_BAD_ARG;
+    if (const int rc = check_not_bank(h, "cmps_psi_stream")) return rc;
     if (!h->params_set || h->legacy)
         return fail(h, CMPS_ERR_STATE, "cmps_psi_stream: call cmps_set_params first (not available in legacy mode)");
     StreamDev ST;
@@ -646,6 +805,7 @@ int cmps_psi_stream(cmps_handle_t h, const void* state_in_dev, void* state_out_d
 int cmps_psi_stream_score(cmps_handle_t h, const void* state_in_dev, void* state_out_dev, int k0, const float* audio_dev, int n_audio, int forced,
                           int n, float* nll_dev, float* loss_dev, float* pred_dev, void* stream) {
     if (!h) return CMPS_ERR_BAD_ARG;
+    if (const int rc = check_not_bank(h, "cmps_psi_stream_score")) return rc;
     if (!h->params_set || h->legacy)
         return fail(h, CMPS_ERR_STATE, "cmps_psi_stream_score: call cmps_set_params first (not available in legacy mode)");
     if (n < 1 || forced < 1 || k0 < 0) return fail(h, CMPS_ERR_BAD_ARG, "cmps_psi_stream_score: need n >= 1, forced >= 1 and k0 >= 0");
@@ -781,6 +941,7 @@ int cmps_legacy_set_params(cmps_handle_t h, const float* R_dev, const float* Q_r
     h->tt_ws = nullptr;               // the time table of the PsiCMPS mode is no longer valid for this workspace
     h->params_set = true;
     h->legacy = true;
+    h->bank_M = 0;
     h->main.valid = false;
     h->rho_set = false;
     return CMPS_OK;
@@ -846,6 +1007,7 @@ size_t cmps_rho_workspace_bytes(int D, int rank, int B, int T, int flags) {
 int cmps_rho_set_state(cmps_handle_t h, const float* phi_re_dev, const float* phi_im_dev, int rank, int T, int B_max,
                        int flags, void* rho_workspace_dev, size_t rho_workspace_bytes, void* stream) {
     if (!h) return CMPS_ERR_BAD_ARG;
+    if (const int rc = check_not_bank(h, "cmps_rho_set_state")) return rc;
     if (!h->params_set || h->legacy) return fail(h, CMPS_ERR_STATE, "cmps_rho_set_state: call cmps_set_params first");
     if (!phi_re_dev || !phi_im_dev || rank < 1 || B_max < 1 || T < 2)
         return fail(h, CMPS_ERR_BAD_ARG, "cmps_rho_set_state: bad argument");
@@ -972,6 +1134,7 @@ int cmps_rho_loss_bwd(cmps_handle_t h, const float* audio_dev, int B, int T, flo
 int cmps_rho_update_ancilla(cmps_handle_t h, const float* rho_in_dev, const float* signal_dev, float t, int B,
                             float* rho_out_dev, void* stream) {
     if (!h) return CMPS_ERR_BAD_ARG;
+    if (const int rc = check_not_bank(h, "cmps_rho_update_ancilla")) return rc;
     if (!h->params_set || h->legacy) return fail(h, CMPS_ERR_STATE, "cmps_rho_update_ancilla: call cmps_set_params first");
     if (!rho_in_dev || !signal_dev || !rho_out_dev || B < 1 || rho_in_dev == rho_out_dev)
         return fail(h, CMPS_ERR_BAD_ARG, "cmps_rho_update_ancilla: bad argument");

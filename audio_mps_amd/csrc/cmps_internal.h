@@ -163,7 +163,36 @@ struct Dev {
     int f16_shift;       // CMPS_OPT_F16_SCALE_SHIFT (diagnostic, 0): added to the exponent of the wave reverse scan's data-dependent fp16 scales
     int abar_fix;        // 1: the slabs' Abar holds -(sum_k Re(u^dagger (Q + s R^dagger) ybar)) / A (k_bwd_wave's merged mat-vec);
                          //    k_finalize adds Re sum_ij Q_ij Qbar_ji / A from the reduced Qbar
+    // A bank of M same-shape models in one launch (cmps_bank_*): member m's workspace is the plain layout `bank_stride` bytes behind
+    // member m - 1's, and the caller's buffers are rows of one array per member.  A plain launch has every stride 0 and one member.
+    size_t bank_stride;  // bytes between two members' workspaces (M > 1: make_layout(...).total)
+    size_t bank_audio;   // floats between two members' audio (B T; 0: one batch shared by every member)
+    size_t bank_loss;    // floats between two members' per-clip losses (B)
+    size_t bank_grad;    // floats between two members' gradient sums (2 D^2 + 3 D + 2)
+    size_t bank_adev;    // floats between two members' effective parameters (2 D^2 + 3 D + 1): what Adev moves by
 };
+
+// p moved forward by `bytes` (a member's section of a bank's workspace)
+template <typename T>
+__host__ __device__ __forceinline__ T* bank_shift(T* p, size_t bytes) {
+    using C = std::conditional_t<std::is_const<T>::value, const char, char>;
+    return reinterpret_cast<T*>(reinterpret_cast<C*>(p) + bytes);
+}
+// The Dev of member `member` of a bank: every workspace pointer moved by member * bank_stride, Adev by member * bank_adev floats.  The
+// kernels take it once at entry with member = blockIdx.y (wave-uniform: scalar arithmetic in front of the role split); nothing behind
+// the entry knows about banks.  Stride 0 / member 0 (every plain launch) is the Dev as it was handed in.  Sections a workspace does
+// not have (null: FWD_ONLY workspaces) and an unset Adev stay null.
+__host__ __device__ __forceinline__ Dev bank_view(Dev P, unsigned member) {
+    const size_t o = (size_t)member * P.bank_stride;
+    P.R = bank_shift(P.R, o); P.RT = bank_shift(P.RT, o); P.Q = bank_shift(P.Q, o); P.QT = bank_shift(P.QT, o);
+    P.psi0 = bank_shift(P.psi0, o); P.freqs = bank_shift(P.freqs, o); P.qflag = bank_shift(P.qflag, o);
+    P.ttab = bank_shift(P.ttab, o); P.dtk = bank_shift(P.dtk, o); P.rho = bank_shift(P.rho, o);
+    P.stash = bank_shift(P.stash, o); P.hst = bank_shift(P.hst, o); P.scal = bank_shift(P.scal, o);
+    P.slabs = bank_shift(P.slabs, o); P.sums = bank_shift(P.sums, o);
+    if (P.status) P.status = bank_shift(P.status, o);
+    if (P.Adev) P.Adev += (size_t)member * P.bank_adev;
+    return P;
+}
 
 // ---------------------------------------------------------------------------------------------
 // RhoCMPS (cmps_rho.hip): its own caller-provided workspace next to the main one.
@@ -377,15 +406,16 @@ hipError_t launch_bwd_rho_wave(const Dev& P, const RhoDev& W, const float* audio
 hipError_t launch_prep(const Dev& P, const float* R_re, const float* R_im, const float* freqs,
                        const float* psi0_re, const float* psi0_im, float dt, bool rebuild_ttab,
                        float* ttab, float* dtk, float2* R, float2* RT, float2* Q, float2* psi0,
-                       float* freqs_out, float2* rho, double2* rfix, hipStream_t s);
+                       float* freqs_out, float2* rho, double2* rfix, hipStream_t s, int M = 1, size_t par_stride = 0);
 
-hipError_t launch_fwd_block(const Dev& P, const float* audio, float* loss, bool save, hipStream_t s);
-hipError_t launch_bwd_block(const Dev& P, const float* audio, hipStream_t s);
+// (M: the members of a bank, the kernels' second grid dimension -- Dev::bank_*; the plain entry points launch one)
+hipError_t launch_fwd_block(const Dev& P, const float* audio, float* loss, bool save, hipStream_t s, int M = 1);
+hipError_t launch_bwd_block(const Dev& P, const float* audio, hipStream_t s, int M = 1);
 hipError_t launch_bwd_wave(const Dev& P, const float* audio, int rank1_mode, hipStream_t s);
-hipError_t launch_bwd_wave2w(const Dev& P, const float* audio, hipStream_t s);    // cmps_wave_bwd2.hip: two waves per clip (F16X2 sums)
-hipError_t launch_fwd_wave2(const Dev& P, const float* audio, float* loss, bool save, bool hf16, bool norm_rows, hipStream_t s);
-hipError_t launch_fwd_wave16(const Dev& P, const float* audio, float* loss, bool save, hipStream_t s);
-hipError_t launch_bwd_wave16(const Dev& P, const float* audio, hipStream_t s);
+hipError_t launch_bwd_wave2w(const Dev& P, const float* audio, hipStream_t s, int M = 1);    // cmps_wave_bwd2.hip: two waves per clip (F16X2 sums)
+hipError_t launch_fwd_wave2(const Dev& P, const float* audio, float* loss, bool save, bool hf16, bool norm_rows, hipStream_t s, int M = 1);
+hipError_t launch_fwd_wave16(const Dev& P, const float* audio, float* loss, bool save, hipStream_t s, int M = 1);
+hipError_t launch_bwd_wave16(const Dev& P, const float* audio, hipStream_t s, int M = 1);
 hipError_t launch_fwd_pair(const Dev& P, const float* audio, float* loss, bool save, hipStream_t s);
 hipError_t launch_bwd_pair(const Dev& P, const float* audio, hipStream_t s);
 hipError_t launch_grad_pair(const Dev& P, const float* audio, hipStream_t s);
@@ -401,12 +431,12 @@ hipError_t launch_fwd_chain16(const Dev& P, const float* audio, hipStream_t s);
 hipError_t launch_bwd_chain16(const Dev& P, const float* audio, hipStream_t s);    // cmps_pair.hip: the wide family's chain on the matrix cores
 hipError_t launch_bwd_wide(const Dev& P, const float* audio, hipStream_t s);
 hipError_t launch_grad_wide(const Dev& P, const float* audio, int pieces, hipStream_t s);
-hipError_t launch_finalize_only(const Dev& P, const float* loss, float* grad_out, hipStream_t s);
-hipError_t launch_reduce_finalize(const Dev& P, const float* loss, float* grad_out, hipStream_t s);
+hipError_t launch_finalize_only(const Dev& P, const float* loss, float* grad_out, hipStream_t s, int M = 1);
+hipError_t launch_reduce_finalize(const Dev& P, const float* loss, float* grad_out, hipStream_t s, int M = 1);
 hipError_t launch_update_ancilla(const Dev& P, const float* psi_in, const float* signal, float t,
                                  int B, float* psi_out, hipStream_t s);
 hipError_t launch_states(const Dev& P, int B, float* psi_out, hipStream_t s);
-hipError_t launch_reduce_only(const Dev& P, hipStream_t s);
+hipError_t launch_reduce_only(const Dev& P, hipStream_t s, int M = 1);
 hipError_t launch_pack_legacy(const Dev& P, const float* Rr, const float* Qre, const float* Qim, float2* R,
                               float2* RT, float2* Q, float2* QT, hipStream_t s);
 hipError_t launch_fwd_legacy(const Dev& P, const float* audio, float* loss, bool save, hipStream_t s);
@@ -438,6 +468,10 @@ size_t apply_step_scratch_bytes(int D);
 hipError_t launch_apply_step(int D, bool apply, double inv_batch, double lr_t, double beta1, double beta2, double eps, double h_reg,
                              double r_reg, double c_r, double c_h, bool with_reg, float* vars, float* am, float* av,
                              const float* grad_sums, float* params_out, float* losses_out, double* scratch, hipStream_t s);
+// cmps_bank_apply_step: M members' steps in one launch; hyper [M][5] = (learning_rate, h_reg, r_reg, c_r, c_h) per member, on the device
+hipError_t launch_bank_apply_step(int D, int M, bool apply, double inv_batch, double bias_num, double bias_den, double beta1, double beta2,
+                                  double eps, const double* hyper, bool with_reg, float* vars, float* am, float* av, const float* grad_sums,
+                                  float* params_out, float* losses_out, double* scratch, hipStream_t s);
 // cmps_rho_apply_step: the same step for RhoCMPS's variables (Wx, Wy [rank, D] in place of psi_x, psi_y); phi_out = the next columns
 size_t rho_apply_step_scratch_bytes(int D, int rank);
 hipError_t launch_rho_apply_step(int D, int rank, bool apply, double inv_batch, double lr_t, double beta1, double beta2, double eps,

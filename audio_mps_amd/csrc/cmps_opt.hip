@@ -195,10 +195,40 @@ __device__ __forceinline__ void write_params_common(const OptArgs& a, const floa
 }
 __device__ __forceinline__ float eff_f32(const OptArgs& a, const float* fr, int d) { return a.scaled_h ? mul_rn(a.c_h, fr[d]) : fr[d]; }
 
-__global__ __launch_bounds__(ONT) void k_apply_step(OptArgs a, float* __restrict__ vars, float* __restrict__ am, float* __restrict__ av,
+// A bank (cmps_bank_apply_step): one workgroup per member, member = blockIdx.x.  Its buffers are row `member` of the callers' arrays
+// (BankArgs: floats, for the scratch doubles, between two rows) and what is free per member comes from hyper[member] = (learning_rate,
+// h_reg, r_reg, c_r, c_h); lr_t = (learning_rate * bias_num) / bias_den in double, the host's `lr * sqrt(1 - b2^t) / (1 - b1^t)` to
+// the bit (audio_mps_amd/train.py::Trainer._apply).  The plain step is the instance BANK = false: it sees its arguments as before (the
+// per-member values pass through the vector unit, which costs the bank instance two vector registers the plain one does not pay).
+struct BankArgs {
+    const double* hyper;          // [M][5] (the plain step: unused)
+    double bias_num, bias_den;
+    size_t n_vars, n_grad, n_scratch;
+};
+
+template <bool BANK>
+__global__ __launch_bounds__(ONT) void k_apply_step(OptArgs a, BankArgs k, float* __restrict__ vars, float* __restrict__ am, float* __restrict__ av,
                                                     const float* __restrict__ gs, float* __restrict__ params,
                                                     float* __restrict__ losses, double* __restrict__ colsum) {
     __shared__ double red[ONT / 64];
+    if constexpr (BANK) {
+        const size_t m = blockIdx.x;
+        const double* hy = k.hyper + 5 * m;
+        // (workgroup-uniform values that the vector unit computes: back into scalar registers, where the plain step's arguments live)
+        auto uni = [](float x) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(x))); };
+        a.lr_t = uni((float)((hy[0] * k.bias_num) / k.bias_den));
+        auto uni_d = [](double x) {
+            return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(x)), __builtin_amdgcn_readfirstlane(__double2loint(x)));
+        };
+        a.h_reg = uni_d(hy[1]); a.r_reg = uni_d(hy[2]);
+        a.c_r = uni((float)hy[3]); a.c_h = uni((float)hy[4]);
+        a.scaled_r = __builtin_amdgcn_readfirstlane(hy[3] != 1.0 ? 1 : 0); a.scaled_h = __builtin_amdgcn_readfirstlane(hy[4] != 1.0 ? 1 : 0);
+    }
+    {   // (the plain step: one workgroup, strides 0; without an update the null buffers are moved and never read)
+        const size_t m = blockIdx.x;
+        vars += m * k.n_vars; params += m * k.n_vars; am += m * k.n_vars; av += m * k.n_vars;
+        gs += m * k.n_grad; losses += 2 * m; colsum += m * k.n_scratch;
+    }
     const int D = a.D, DD = D * D, t = threadIdx.x;
     float* Rx = vars + 1;
     float* Ry = Rx + DD;
@@ -345,7 +375,17 @@ hipError_t launch_apply_step(int D, bool apply, double inv_batch, double lr_t, d
                              double r_reg, double c_r, double c_h, bool with_reg, float* vars, float* am, float* av,
                              const float* grad_sums, float* params_out, float* losses_out, double* scratch, hipStream_t s) {
     const OptArgs a = opt_args(D, 0, apply, inv_batch, lr_t, beta1, beta2, eps, h_reg, r_reg, c_r, c_h, with_reg);
-    hipLaunchKernelGGL(k_apply_step, dim3(1), dim3(ONT), 0, s, a, vars, am, av, grad_sums, params_out, losses_out, scratch);
+    hipLaunchKernelGGL(k_apply_step<false>, dim3(1), dim3(ONT), 0, s, a, BankArgs{}, vars, am, av, grad_sums, params_out, losses_out, scratch);
+    return hipGetLastError();
+}
+
+hipError_t launch_bank_apply_step(int D, int M, bool apply, double inv_batch, double bias_num, double bias_den, double beta1, double beta2,
+                                  double eps, const double* hyper, bool with_reg, float* vars, float* am, float* av, const float* grad_sums,
+                                  float* params_out, float* losses_out, double* scratch, hipStream_t s) {
+    const OptArgs a = opt_args(D, 0, apply, inv_batch, 0.0, beta1, beta2, eps, 0.0, 0.0, 1.0, 1.0, with_reg);     // (k_apply_step fills the per-member ones)
+    const size_t DD = (size_t)D * D;
+    const BankArgs k{hyper, bias_num, bias_den, 2 * DD + 3 * D + 1, 2 * DD + 3 * D + 2, apply_step_scratch_bytes(D) / sizeof(double)};
+    hipLaunchKernelGGL(k_apply_step<true>, dim3(M), dim3(ONT), 0, s, a, k, vars, am, av, grad_sums, params_out, losses_out, scratch);
     return hipGetLastError();
 }
 

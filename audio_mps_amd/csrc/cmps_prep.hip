@@ -5,9 +5,13 @@
 
 namespace cmps {
 
+// A bank (cmps_bank_set_params_dev) builds every member's tables in one launch: member = blockIdx.y, whose workspace lies `ws` bytes
+// and whose parameters `par` floats behind its predecessor's.  A plain launch has one member and both strides 0.
+
 // t_0 = 0; t_{k+1} = fl32(t_k + dt), strictly sequential (one lane).  dtk[k] = t_k - t_{k+1} is exact.
-__global__ void k_ttable(float dt, int N, float* __restrict__ ttab, float* __restrict__ dtk) {
+__global__ void k_ttable(float dt, int N, float* __restrict__ ttab, float* __restrict__ dtk, size_t ws) {
     if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    ttab = bank_shift(ttab, blockIdx.y * ws); dtk = bank_shift(dtk, blockIdx.y * ws);
     float t = 0.0f;
     for (int k = 0; k <= N; ++k) {
         ttab[k] = t;
@@ -24,8 +28,13 @@ __global__ void k_pack(int D, int DP, const float* __restrict__ R_re, const floa
                        const float* __restrict__ freqs, const float* __restrict__ psi0_re,
                        const float* __restrict__ psi0_im, float c_half, float2* __restrict__ R,
                        float2* __restrict__ RT, float2* __restrict__ Q, float2* __restrict__ psi0,
-                       float* __restrict__ freqs_out) {
+                       float* __restrict__ freqs_out, size_t ws, size_t par) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    {
+        const size_t po = blockIdx.y * par, wo = blockIdx.y * ws;
+        R_re += po; R_im += po; freqs += po; psi0_re += po; psi0_im += po;
+        R = bank_shift(R, wo); RT = bank_shift(RT, wo); Q = bank_shift(Q, wo); psi0 = bank_shift(psi0, wo); freqs_out = bank_shift(freqs_out, wo);
+    }
     if (idx < DP * DP) {
         const int i = idx / DP, j = idx % DP;
         float2 r = make_float2(0.f, 0.f), rt = make_float2(0.f, 0.f), q = make_float2(0.f, 0.f);
@@ -67,8 +76,12 @@ __global__ void k_pack(int D, int DP, const float* __restrict__ R_re, const floa
 // pass 1: one thread per (chunk, d): raw entries, the exact product of the chunk's entries but the last,
 //         and the target accumulated rotation at the end of the chunk.
 __global__ void k_rho_raw(int D, int DP, int N, const float* __restrict__ freqs, const float* __restrict__ ttab,
-                          float2* __restrict__ rho, double2* __restrict__ prod, double2* __restrict__ target) {
+                          float2* __restrict__ rho, double2* __restrict__ prod, double2* __restrict__ target, size_t ws) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    {
+        const size_t wo = blockIdx.y * ws;
+        freqs = bank_shift(freqs, wo); ttab = bank_shift(ttab, wo); rho = bank_shift(rho, wo); prod = bank_shift(prod, wo); target = bank_shift(target, wo);
+    }
     const int NC = (N + 63) / 64;
     if (idx >= NC * DP) return;
     const int c = idx / DP, d = idx % DP;
@@ -99,8 +112,9 @@ __global__ void k_rho_raw(int D, int DP, int N, const float* __restrict__ freqs,
 }
 // pass 2: one thread per d, sequential over chunks (a few hundred iterations of double arithmetic).
 __global__ void k_rho_fix(int DP, int N, float2* __restrict__ rho, const double2* __restrict__ prod,
-                          const double2* __restrict__ target) {
+                          const double2* __restrict__ target, size_t ws) {
     const int d = blockIdx.x * blockDim.x + threadIdx.x;
+    rho = bank_shift(rho, blockIdx.y * ws); prod = bank_shift(prod, blockIdx.y * ws); target = bank_shift(target, blockIdx.y * ws);
     if (d >= DP) return;
     const int NC = (N + 63) / 64;
     double ar = 1.0, ai = 0.0;   // exact accumulated rotation of the float32 table so far
@@ -144,7 +158,8 @@ __global__ void k_rho_fix(int DP, int N, float2* __restrict__ rho, const double2
 // |Q|_F <= 2^-19 ?  Decided ONCE per parameter set, here; both chain kernels of the wide family (k_fwd_chain16 / k_bwd_chain16 have an
 // instance for either case) read the word.  Rounds 4's kernels each recomputed the norm in their prologue and compared it with the
 // threshold themselves: two separately compiled sums at a boundary can disagree, and then both instances run, or neither.
-__global__ void k_qflag(int DP, const float2* __restrict__ Q, unsigned* __restrict__ flag) {
+__global__ void k_qflag(int DP, const float2* __restrict__ Q, unsigned* __restrict__ flag, size_t ws) {
+    Q = bank_shift(Q, blockIdx.y * ws); flag = bank_shift(flag, blockIdx.y * ws);
     __shared__ double red[4];
     double f = 0.0;
     for (int idx = threadIdx.x; idx < DP * DP; idx += 256) f += (double)Q[idx].x * Q[idx].x + (double)Q[idx].y * Q[idx].y;
@@ -158,21 +173,22 @@ __global__ void k_qflag(int DP, const float2* __restrict__ Q, unsigned* __restri
 hipError_t launch_prep(const Dev& P, const float* R_re, const float* R_im, const float* freqs,
                        const float* psi0_re, const float* psi0_im, float dt, bool rebuild_ttab,
                        float* ttab, float* dtk, float2* R, float2* RT, float2* Q, float2* psi0,
-                       float* freqs_out, float2* rho, double2* rfix, hipStream_t s) {
-    if (rebuild_ttab) hipLaunchKernelGGL(k_ttable, dim3(1), dim3(64), 0, s, dt, P.N, ttab, dtk);
+                       float* freqs_out, float2* rho, double2* rfix, hipStream_t s, int M, size_t par) {
+    const size_t ws = P.bank_stride;
+    if (rebuild_ttab) hipLaunchKernelGGL(k_ttable, dim3(1, M), dim3(64), 0, s, dt, P.N, ttab, dtk, ws);
     const int n = P.DP * P.DP;
-    hipLaunchKernelGGL(k_pack, dim3((n + 255) / 256), dim3(256), 0, s, P.D, P.DP, R_re, R_im, freqs,
-                       psi0_re, psi0_im, P.c_half, R, RT, Q, psi0, freqs_out);
+    hipLaunchKernelGGL(k_pack, dim3((n + 255) / 256, M), dim3(256), 0, s, P.D, P.DP, R_re, R_im, freqs,
+                       psi0_re, psi0_im, P.c_half, R, RT, Q, psi0, freqs_out, ws, par);
     if (P.D > 32 && P.qflag)
-        hipLaunchKernelGGL(k_qflag, dim3(1), dim3(256), 0, s, P.DP, (const float2*)Q, const_cast<unsigned*>(P.qflag));
+        hipLaunchKernelGGL(k_qflag, dim3(1, M), dim3(256), 0, s, P.DP, (const float2*)Q, const_cast<unsigned*>(P.qflag), ws);
     const int NC = (P.N + 63) / 64;
     const int m = NC * P.DP;
     double2* prod = rfix;
     double2* target = rfix + m;
-    hipLaunchKernelGGL(k_rho_raw, dim3((unsigned)((m + 63) / 64)), dim3(64), 0, s, P.D, P.DP, P.N,
-                       (const float*)freqs_out, (const float*)ttab, rho, prod, target);
-    hipLaunchKernelGGL(k_rho_fix, dim3((unsigned)((P.DP + 63) / 64)), dim3(64), 0, s, P.DP, P.N, rho,
-                       (const double2*)prod, (const double2*)target);
+    hipLaunchKernelGGL(k_rho_raw, dim3((unsigned)((m + 63) / 64), M), dim3(64), 0, s, P.D, P.DP, P.N,
+                       (const float*)freqs_out, (const float*)ttab, rho, prod, target, ws);
+    hipLaunchKernelGGL(k_rho_fix, dim3((unsigned)((P.DP + 63) / 64), M), dim3(64), 0, s, P.DP, P.N, rho,
+                       (const double2*)prod, (const double2*)target, ws);
     return hipGetLastError();
 }
 

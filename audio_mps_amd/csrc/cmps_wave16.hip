@@ -149,7 +149,10 @@ struct Pre16 {
 // forward
 // ------------------------------------------------------------------------------------------------
 template <bool SAVE>
-__global__ __launch_bounds__(128, 1) void k_fwd_wave16(Dev P, const float* __restrict__ audio, float* __restrict__ loss_out) {
+__global__ __launch_bounds__(128, 1) void k_fwd_wave16(Dev Pk, const float* __restrict__ audio, float* __restrict__ loss_out) {
+    const Dev P = bank_view(Pk, blockIdx.y);                               // the member's workspace (a plain launch: Pk itself)
+    audio += blockIdx.y * P.bank_audio;
+    loss_out += blockIdx.y * P.bank_loss;
     __shared__ __attribute__((aligned(16))) float4 stR[CH16 * 8];          // rho rows (16 entries) of the chain wave's chunk
     __shared__ __attribute__((aligned(16))) float2 bcU[D16];
     __shared__ __attribute__((aligned(16))) float2 ring[RING16][D16];      // y_k, interleaved (re, im) per component
@@ -349,7 +352,9 @@ __global__ __launch_bounds__(128, 1) void k_fwd_wave16(Dev P, const float* __res
 // ------------------------------------------------------------------------------------------------
 // reverse
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(128, 1) void k_bwd_wave16(Dev P, const float* __restrict__ audio) {
+__global__ __launch_bounds__(128, 1) void k_bwd_wave16(Dev Pk, const float* __restrict__ audio) {
+    const Dev P = bank_view(Pk, blockIdx.y);                               // the member's workspace (a plain launch: Pk itself)
+    audio += blockIdx.y * P.bank_audio;
     __shared__ __attribute__((aligned(16))) float4 stY[CS16 * 32];         // stashed (y, H y) rows of the staged chunk
     __shared__ __attribute__((aligned(16))) float4 stR[CS16 * 16];         // rho rows (full 256-B rows)
     __shared__ __attribute__((aligned(16))) float4 scl[CH * 2];            // per-step scalars, one 32-B row per step
@@ -673,16 +678,16 @@ __global__ __launch_bounds__(128, 1) void k_bwd_wave16(Dev P, const float* __res
     }
 }
 
-hipError_t launch_fwd_wave16(const Dev& P, const float* audio, float* loss, bool save, hipStream_t s) {
+hipError_t launch_fwd_wave16(const Dev& P, const float* audio, float* loss, bool save, hipStream_t s, int M) {
     if (save)
-        hipLaunchKernelGGL(k_fwd_wave16<true>, dim3(P.B), dim3(128), 0, s, P, audio, loss);
+        hipLaunchKernelGGL(k_fwd_wave16<true>, dim3(P.B, M), dim3(128), 0, s, P, audio, loss);
     else
-        hipLaunchKernelGGL(k_fwd_wave16<false>, dim3(P.B), dim3(128), 0, s, P, audio, loss);
+        hipLaunchKernelGGL(k_fwd_wave16<false>, dim3(P.B, M), dim3(128), 0, s, P, audio, loss);
     return hipGetLastError();
 }
 
-hipError_t launch_bwd_wave16(const Dev& P, const float* audio, hipStream_t s) {
-    hipLaunchKernelGGL(k_bwd_wave16, dim3(P.B), dim3(128), 0, s, P, audio);
+hipError_t launch_bwd_wave16(const Dev& P, const float* audio, hipStream_t s, int M) {
+    hipLaunchKernelGGL(k_bwd_wave16, dim3(P.B, M), dim3(128), 0, s, P, audio);
     return hipGetLastError();
 }
 

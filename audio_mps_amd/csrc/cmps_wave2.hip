@@ -162,8 +162,11 @@ __device__ __forceinline__ void lds_wait_hi_t_after(v4f (&o)[8], v2f& t, v2f& de
 // ebar_k = -(x_k / A) / (1 + z_k) -- three multiplies per component and step that the reverse CHAIN wave would otherwise issue, done here
 // where the most issue slots are free.  The rows are stored behind the e_k column sums and the per-chunk scalar stage (2 ebar_k needs e_k).
 template <bool SAVE, bool LEGACY = false, bool HF16 = false, bool NORM = false>
-__global__ __launch_bounds__(128 * WAVES, 1) void k_fwd_wave2(Dev P, const float* __restrict__ audio,
+__global__ __launch_bounds__(128 * WAVES, 1) void k_fwd_wave2(Dev Pk, const float* __restrict__ audio,
                                                               float* __restrict__ loss_out) {
+    const Dev P = bank_view(Pk, blockIdx.y);                               // the member's workspace (a plain launch: Pk itself)
+    audio += blockIdx.y * P.bank_audio;
+    loss_out += blockIdx.y * P.bank_loss;
     // rho rows of the chain wave's chunk, two buffers (round 5): the next chunk's rows are fetched in two halves of 16 rows and committed
     // into the OTHER buffer while the current one is being read, so only 16 registers ride through the chunk instead of 32 -- with 32
     // hipcc spilled four of them to scratch memory and reloaded them behind an s_waitcnt vmcnt(0) at every chunk end (ISA of round 4)
@@ -654,16 +657,16 @@ __global__ __launch_bounds__(128 * WAVES, 1) void k_fwd_wave2(Dev P, const float
 }
 
 // norm_rows: write STASH_WAVE32N rows (the caller asks for them only with save and hf16: the two-wave reverse scan's settings)
-hipError_t launch_fwd_wave2(const Dev& P, const float* audio, float* loss, bool save, bool hf16, bool norm_rows, hipStream_t s) {
+hipError_t launch_fwd_wave2(const Dev& P, const float* audio, float* loss, bool save, bool hf16, bool norm_rows, hipStream_t s, int M) {
     const unsigned nb = (unsigned)((P.B + WAVES - 1) / WAVES);
     if (norm_rows) {
         if (!save || !hf16) return hipErrorInvalidValue;
-        hipLaunchKernelGGL((k_fwd_wave2<true, false, true, true>), dim3(nb), dim3(128 * WAVES), 0, s, P, audio, loss);
+        hipLaunchKernelGGL((k_fwd_wave2<true, false, true, true>), dim3(nb, M), dim3(128 * WAVES), 0, s, P, audio, loss);
         return hipGetLastError();
     }
     return dispatch_bool(save, [&](auto sv) {
         return dispatch_bool(hf16, [&](auto hf) {
-            hipLaunchKernelGGL((k_fwd_wave2<decltype(sv)::value, false, decltype(hf)::value>), dim3(nb), dim3(128 * WAVES), 0, s, P, audio, loss);
+            hipLaunchKernelGGL((k_fwd_wave2<decltype(sv)::value, false, decltype(hf)::value>), dim3(nb, M), dim3(128 * WAVES), 0, s, P, audio, loss);
             return hipGetLastError();
         });
     });

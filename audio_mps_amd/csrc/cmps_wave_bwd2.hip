@@ -94,7 +94,9 @@ __device__ __forceinline__ float wave_max(float x) {       // max over the 64 la
 // NORM: the stash rows are the forward's normalised rows (STASH_WAVE32N: (yhat_k[n], p_k[n]) pairs, cmps_wave2.hip) and the chain wave's
 // pre stage and serial tail take their short form (make_pre, chain_step); else (y, H y) rows (PsiCMPS on other settings, RhoCMPS).
 template <bool NORM = false>
-__global__ __launch_bounds__(128 * WAVES, 1) void k_bwd_wave2w(Dev P, const float* __restrict__ audio) {
+__global__ __launch_bounds__(128 * WAVES, 1) void k_bwd_wave2w(Dev Pk, const float* __restrict__ audio) {
+    const Dev P = bank_view(Pk, blockIdx.y);                               // the member's workspace (a plain launch: Pk itself)
+    audio += blockIdx.y * P.bank_audio;
     __shared__ __attribute__((aligned(16))) float4 stY[WAVES][CHB * 32];   // stashed (y, H y) rows of the staged chunk
     __shared__ __attribute__((aligned(16))) float4 stR[WAVES][CHB * 16];   // rho rows
     __shared__ __attribute__((aligned(16))) float4 scl[WAVES][CH * 2];     // per-step scalars, one 32-B row per step
@@ -591,10 +593,10 @@ __global__ __launch_bounds__(128 * WAVES, 1) void k_bwd_wave2w(Dev P, const floa
 }
 
 // (the row kind is the saved-forward record's: P.stash_layout)
-hipError_t launch_bwd_wave2w(const Dev& P, const float* audio, hipStream_t s) {
+hipError_t launch_bwd_wave2w(const Dev& P, const float* audio, hipStream_t s, int M) {
     const unsigned nb = (unsigned)((P.B + WAVES - 1) / WAVES);
-    if (P.stash_layout == STASH_WAVE32N) hipLaunchKernelGGL(k_bwd_wave2w<true>, dim3(nb), dim3(128 * WAVES), 0, s, P, audio);
-    else hipLaunchKernelGGL(k_bwd_wave2w<false>, dim3(nb), dim3(128 * WAVES), 0, s, P, audio);
+    if (P.stash_layout == STASH_WAVE32N) hipLaunchKernelGGL(k_bwd_wave2w<true>, dim3(nb, M), dim3(128 * WAVES), 0, s, P, audio);
+    else hipLaunchKernelGGL(k_bwd_wave2w<false>, dim3(nb, M), dim3(128 * WAVES), 0, s, P, audio);
     return hipGetLastError();
 }
 

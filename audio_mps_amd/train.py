@@ -15,6 +15,9 @@ Run:  python -m audio_mps_amd.train --dataset=damped_sine --hparams=bond_dim=32,
 once and gathered from in the host pipeline's order, damped_sine is generated there.
 ``--eval_dataset NAME --eval_every N`` evaluates a held-out set every N steps and after the last one (Trainer.evaluate,
 audio_mps_amd/evaluate.py): a line on the console, a JSON line in {logdir}/eval.jsonl, and model.best.ckpt.npz when the mean improves.
+``--bank N`` and ``--bank_hparams "learning_rate=1e-3,3e-3;r_reg=0.1,1"`` train many PsiCMPS models at once (audio_mps_amd/bank.py): N seeds,
+the Cartesian grid, or every seed once per grid point; one kernel launch per stage serves all of them, every member sees the same batch,
+and the checkpoints are {logdir}/model.<m>.ckpt.npz (each loads in audio_mps_amd.sample / .evaluate) next to bank.json.
 """
 from __future__ import annotations
 
@@ -320,6 +323,12 @@ def build_parser():
     p.add_argument("--eval_every", type=int, default=0, help="evaluate every N steps (0: off); also after the last step")
     p.add_argument("--eval_clips", type=int, default=256, help="clips of the synthetic held-out set (--eval_dataset damped_sine)")
     p.add_argument("--eval_minibatch", type=int, default=None, help="clips per evaluation batch (default: minibatch_size)")
+    p.add_argument("--bank", type=int, default=0, metavar="N",
+                   help="train N PsiCMPS models at once, seeds --seed .. --seed + N - 1 (audio_mps_amd/bank.py); every member trains on the "
+                        "same batch")
+    p.add_argument("--bank_hparams", default="", metavar="SPEC",
+                   help="train the Cartesian grid of 'learning_rate=1e-3,3e-3;r_reg=0.1,1' (learning_rate, h_reg, r_reg) at once; with --bank "
+                        "every seed runs once per grid point")
     p.add_argument("--eval_storage", default="float32", choices=["float32", "int16", "auto"],
                    help="how a TFRecord held-out set is held on the device (int16: half the memory for 16-bit PCM data, the same bits)")
     return p
@@ -402,6 +411,8 @@ def main(argv=None, backend=None):
     else:
         dp = DataParallel(backend="gloo")
     start, count = dp.shard(hp.minibatch_size)
+    if args.bank or args.bank_hparams:
+        return bank_main(args, hp, backend, dp)
     cls = RhoCMPS if args.mps_model == "rho_mps" else PsiCMPS                                   # train.py:50-53
     model = cls(hp, seed=args.seed, backend=backend)
     device_step = (not args.host_optimizer and type(backend).__name__ == "HipScan")
@@ -444,6 +455,57 @@ def main(argv=None, backend=None):
             eval_log(trainer, trainer.evaluate(held_out, args.eval_minibatch))
     dp.close()
     return trainer
+
+
+def bank_main(args, hp, backend, dp):
+    """``--bank`` / ``--bank_hparams``: the loop of ``main`` for a BankTrainer.  One batch per step, shared by every member."""
+    from .bank import BankTrainer, PsiBank, bank_members
+    from .data import get_audio
+    if args.mps_model != "psi_mps":
+        raise ValueError("--bank trains PsiCMPS models (--mps_model psi_mps)")
+    if args.bank < 0:
+        raise ValueError("--bank must not be negative (0: one seed per point of --bank_hparams)")
+    # what the loop below does not do is refused, not ignored
+    if args.eval_dataset or args.eval_every or args.eval_minibatch is not None:
+        raise ValueError("--bank does not evaluate while it trains (--eval_dataset, --eval_every, --eval_minibatch): run "
+                         "python -m audio_mps_amd.evaluate on a member's model.<m>.ckpt.npz, or BankTrainer.evaluate")
+    if args.host_optimizer:
+        raise ValueError("--bank runs the device-resident optimiser step of every member (cmps_bank_apply_step): no --host_optimizer")
+    members = bank_members(args.seed, args.bank, args.bank_hparams)
+    trainer = BankTrainer(PsiBank(hp, members, backend=backend), dp)
+    logdir = f"{args.logdir}/{args.dataset}/{hp.bond_dim}_{hp.delta_t}_{hp.minibatch_size}"    # train.py:94
+    if trainer.restore(logdir):
+        print(f"Restoring {len(trainer)} members from {logdir} (global_step {trainer.global_step})")
+    last_save = time.time()
+    on_device = device_source(args, hp, backend) if args.device_data else None
+    source = get_audio(args.datadir, args.dataset, hp, args.sample_duration, seed=args.seed) \
+        if args.dataset != "damped_sine" and on_device is None else None
+    for it in range(args.max_steps):
+        if on_device is not None:
+            batch = on_device[1](trainer.global_step, (0, int(on_device[0](trainer.global_step))))
+        elif source is not None:
+            batch = source()
+        else:
+            batch = get_audio(args.datadir, args.dataset, hp, args.sample_duration, seed=args.seed + trainer.global_step)
+        log_now = (it % max(args.log_every, 1) == 0) or it == args.max_steps - 1
+        out = trainer.step(batch, sync=log_now)
+        if log_now:
+            print(bank_log_line(out))
+        if time.time() - last_save > args.save_checkpoint_secs or it == args.max_steps - 1:
+            trainer.save(logdir)
+            last_save = time.time()
+    dp.close()
+    return trainer
+
+
+def bank_log_line(out) -> str:
+    """The log line of a bank step: best, median and worst member loss among the finite ones, and how many are not."""
+    loss = np.asarray(out["model_loss"], dtype=np.float64)
+    fin = np.sort(loss[np.isfinite(loss)])
+    if fin.size == 0:
+        return f"step {out['global_step']}: members {loss.size} nonfinite {loss.size}"
+    return (f"step {out['global_step']}: members {loss.size} best {fin[0]:.6f} (member {int(np.nanargmin(np.where(np.isfinite(loss), loss, np.nan)))}) "
+            f"median {float(np.median(fin)):.6f} worst {fin[-1]:.6f} nonfinite {loss.size - fin.size}")
 
 
 if __name__ == "__main__":

@@ -263,6 +263,68 @@ int cmps_psi_loss_bwd(cmps_handle_t h, const float* audio_dev, int B, int T, flo
 int cmps_psi_grad_status(cmps_handle_t h, int* sticky_out, void* stream);
 
 /*
+ * ---- Model bank: M PsiCMPS models of one shape per kernel launch ----
+ * Replaces: the Python loop over models that a sweep of the reference is -- a grid over --hparams (train.py:31) at its own settings
+ * minibatch_size = 8, bond_dim = 8 (train.py:41), several seeds of the random initialisation, one model per pitch or instrument
+ * (reader.py:9-66).  Every scan here is bound by its serial chain, so M members cost about the time of one.  D, B, T, sigma, delta_t,
+ * Adam's betas and epsilon and with_reg are common to a bank; the variables, learning_rate, h_reg, r_reg (with c_r, c_h) and the data
+ * are free per member.  Member m computes, bit for bit, what the plain entry computes for model m alone: the kernels are the plain
+ * ones with a second grid dimension, each member working in its own workspace.
+ *
+ * Kernel families: D <= 16, 17 <= D <= 32 with the default options under CMPS_VARIANT_AUTO / WAVE, and CMPS_VARIANT_BLOCK at every D.
+ * Errors of every cmps_bank_* entry that launches scans: CMPS_ERR_UNSUPPORTED_D for D > 32 without CMPS_VARIANT_BLOCK (a bank above
+ * D = 32 needs CMPS_VARIANT_BLOCK); CMPS_ERR_STATE in legacy mode or with a non-default CMPS_OPT_RANK1, CMPS_OPT_BWD_WAVES or
+ * CMPS_OPT_F16_SCALE_SHIFT; CMPS_ERR_BAD_ARG (the message starts with the entry's name) for null pointers, M outside [1, 1024],
+ * B < 1, T < 2, M B T beyond 2^31 - 1, n_audio not in {1, M}; CMPS_ERR_WORKSPACE for a workspace smaller than
+ * cmps_bank_workspace_bytes.  All of them are returned before the device is touched.  Every entry is asynchronous on `stream`, never
+ * synchronises (cmps_bank_grad_status excepted, like cmps_psi_grad_status), allocates nothing and touches nothing outside the
+ * stated extents.
+ *
+ * cmps_bank_workspace_bytes = M * cmps_workspace_bytes(D, B, T, flags): member m's workspace is the plain layout at byte m * that.
+ */
+size_t cmps_bank_workspace_bytes(int D, int M, int B, int T, int flags);
+
+/*
+ * Mirrors cmps_set_params_dev for M members: params_dev [M][2 D^2 + 3 D + 1], the buffer cmps_bank_apply_step writes; member m's A is
+ * read from its row by the scan kernels.  Every member gets its own tables (the time table is built M times in parallel);
+ * CMPS_WS_REUSE_TABLES as in cmps_set_params.  Puts the handle into bank mode; a plain cmps_set_params* puts it back.  In bank mode
+ * the plain entries that read the tables of ONE model -- cmps_psi_loss_fwd / _bwd, cmps_psi_grad_status, cmps_psi_states,
+ * cmps_psi_update_ancilla, cmps_psi_sample*, cmps_psi_stream*, cmps_rho_set_state, cmps_rho_update_ancilla -- return CMPS_ERR_STATE.
+ */
+int cmps_bank_set_params_dev(cmps_handle_t h, int M, const float* params_dev, double sigma, double delta_t, int T, int B_max, int flags,
+                             void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/*
+ * Mirror cmps_psi_loss_fwd / cmps_psi_loss_bwd.  audio_dev [n_audio][B][T]: n_audio = 1 is one batch shared by every member (a sweep
+ * over seeds or hyper-parameters, train.py:31), n_audio = M one batch per member (a model per pitch, reader.py:9-66).
+ * loss_dev [M][B], grad_dev [M][2 D^2 + 3 D + 2].  The saved-forward record of the handle is one record for the whole bank:
+ * cmps_bank_loss_bwd without a matching cmps_bank_loss_fwd(save_for_bwd = 1) of the same audio, n_audio, B, T is CMPS_ERR_STATE, and
+ * so is a plain cmps_psi_loss_bwd after a bank forward or a bank reverse pass after a plain forward.
+ */
+int cmps_bank_loss_fwd(cmps_handle_t h, const float* audio_dev, int n_audio, int B, int T, float* loss_dev, int save_for_bwd, void* stream);
+int cmps_bank_loss_bwd(cmps_handle_t h, const float* audio_dev, int n_audio, int B, int T, float* grad_dev, void* stream);
+
+/*
+ * Mirrors cmps_psi_apply_step (train.py:55-60, 88-89), one workgroup per member.  vars_dev, adam_m_dev, adam_v_dev, params_dev
+ * [M][2 D^2 + 3 D + 1]; grad_sums_dev [M][2 D^2 + 3 D + 2] or NULL (only params_dev is computed); losses_dev [M][2];
+ * scratch_dev cmps_bank_apply_step_scratch_bytes(D, M) = M * cmps_apply_step_scratch_bytes(D) bytes, 8-byte aligned.
+ * hyper_dev [M][5] doubles on the device, 8-byte aligned: learning_rate, h_reg, r_reg, c_r, c_h of every member.  The device forms
+ * lr_t = (learning_rate * bias_num) / bias_den in double with bias_num = sqrt(1 - beta2^t), bias_den = 1 - beta1^t -- the value a
+ * host computes for cmps_psi_apply_step, to the bit -- so hyper_dev is uploaded once per run.  The skipped step (a non-finite gradient
+ * next to a finite loss) is per member: that member's variables and Adam slots stay as they are, its losses_dev[1] is NaN.
+ */
+size_t cmps_bank_apply_step_scratch_bytes(int D, int M);
+int cmps_bank_apply_step(cmps_handle_t h, int M, float* vars_dev, float* adam_m_dev, float* adam_v_dev, const float* grad_sums_dev,
+                         double global_batch, double bias_num, double bias_den, double beta1, double beta2, double epsilon,
+                         const double* hyper_dev, int with_reg, float* params_dev, float* losses_dev, void* scratch_dev, void* stream);
+
+/*
+ * Mirrors cmps_psi_grad_status per member: codes_out [M] receives CMPS_OK or CMPS_ERR_F16_RANGE, sticky_out [M] (may be NULL) the OR
+ * of every member's flag words since the previous call.  Waits for `stream`.  Returns CMPS_OK when the words were read.
+ */
+int cmps_bank_grad_status(cmps_handle_t h, int* codes_out, int* sticky_out, void* stream);
+
+/*
  * Replaces: PsiCMPS._update_ancilla_psi (model.py:300-317), one step in the lab frame.
  * psi_in_dev / psi_out_dev [B*D*2] interleaved (re, im); signal_dev [B]; t = time of the step.
  */
