@@ -1,8 +1,10 @@
-"""Many models at once: a bank of M same-shape PsiCMPS models that train in one kernel launch per stage.
+"""Many models at once: a bank of M same-shape PsiCMPS (or RhoCMPS) models that train in one kernel launch per stage.
 
   reference          a sweep is a Python loop over models: a grid over --hparams (train.py:31) at minibatch_size = 8, bond_dim = 8
                      (train.py:41), several seeds of the random initialisation (model.py:36-50), one model per pitch (reader.py:9-66)
   PsiBank            M PsiCMPS models of one D, each initialised exactly as PsiCMPS(hparams_m, seed=seed_m)
+  RhoBank            the same for the reference's other model (train.py:18-20, 50-53): M RhoCMPS models of one D and one initial_rank;
+                     the device path uses cmps_rho_bank_* (D <= 32, 3 <= rank <= 32)
   BankTrainer        one optimiser step of every member: cmps_bank_set_params_dev, cmps_bank_loss_fwd / _bwd, cmps_bank_apply_step --
                      the plain kernels with a member grid dimension, so member m gets bit for bit what Trainer(device_step=True) gives
                      model m alone.  On a backend without the bank entries the trainer loops over plain steps of its members.
@@ -22,7 +24,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from . import layout
-from .model import HParams, PsiCMPS
+from .model import HParams, PsiCMPS, RhoCMPS
 from .parallel import DataParallel
 from .train import Trainer
 
@@ -32,6 +34,10 @@ MEMBER_KEYS = ("seed", "learning_rate", "h_reg", "r_reg")
 class PsiBank:
     """``members``: a list of dicts overriding ``seed``, ``learning_rate``, ``h_reg``, ``r_reg`` of ``hparams`` (any other key is a
     ValueError naming it).  ``models[m]`` is PsiCMPS(hparams_m, seed=seed_m); all of them share one backend."""
+
+    MODEL = PsiCMPS
+    MODEL_NAME = "psi_mps"        # --mps_model (train.py:18-20); written into a Rho bank's bank.json
+    rank = 0                      # columns of rho_0 (RhoBank); 0: pure states
 
     def __init__(self, hparams: HParams, members: Sequence[dict], backend=None):
         if len(members) < 1:
@@ -50,7 +56,7 @@ class PsiBank:
             from .scan import HipScan       # raises if libcmps.so or the GPU is missing: no fallback
             backend = HipScan(int(hparams.bond_dim))
         self.backend = backend
-        self.models = [PsiCMPS(hp, seed=seed, backend=backend) for hp, seed in zip(self.member_hparams, self.seeds)]
+        self.models = [self.MODEL(hp, seed=seed, backend=backend) for hp, seed in zip(self.member_hparams, self.seeds)]
 
     def __len__(self) -> int:
         return len(self.models)
@@ -60,8 +66,21 @@ class PsiBank:
         return int(self.hparams.bond_dim)
 
 
+class RhoBank(PsiBank):
+    """``models[m]`` is RhoCMPS(hparams_m, seed=seed_m); ``hparams.initial_rank`` (None: bond_dim) is common to the bank."""
+    MODEL = RhoCMPS
+    MODEL_NAME = "rho_mps"
+
+    def __init__(self, hparams: HParams, members: Sequence[dict], backend=None):
+        super().__init__(hparams, members, backend)
+        self.rank = int(self.models[0].rank_rho_0)
+
+
+RHO_BANK_ENTRIES = ("rho_bank_set_state_dev", "rho_bank_forward", "rho_bank_backward", "rho_bank_apply_step")
+
+
 class BankTrainer:
-    """One optimiser step of every member of a PsiBank per ``step``.  Every member keeps an ordinary Trainer (its model, its Adam slots,
+    """One optimiser step of every member of a PsiBank or RhoBank per ``step``.  Every member keeps an ordinary Trainer (its model, its Adam slots,
     its checkpoint format); on a backend with the bank entries (HipScan) variables, Adam slots and effective parameters of all members
     live on the device as [M, ...] arrays between steps and come back with ``sync_to_host`` (``member`` and ``save`` do so).  While that
     state is live the bank is every member model's device owner, as a Trainer(device_step=True) is its model's (CMPS.variables): reading
@@ -73,7 +92,9 @@ class BankTrainer:
             raise ValueError("BankTrainer: multi-rank training of a bank is not supported (world size must be 1)")
         self.bank = bank
         be = bank.backend
-        self.native = all(hasattr(be, name) for name in ("bank_set_params_dev", "bank_forward", "bank_backward", "bank_apply_step"))
+        self.rank = int(bank.rank)    # 0: PsiCMPS members; else the columns of every RhoCMPS member (selects the layouts and the rho_bank_* entries)
+        entries = RHO_BANK_ENTRIES if self.rank else ("bank_set_params_dev", "bank_forward", "bank_backward", "bank_apply_step")
+        self.native = all(hasattr(be, name) for name in entries)
         plain_device = type(be).__name__ == "HipScan"
         self.trainers = [Trainer(model, hp, device_step=plain_device and not self.native)
                          for model, hp in zip(bank.models, bank.member_hparams)]
@@ -111,14 +132,14 @@ class BankTrainer:
     def _device_state(self):
         if self._dev is None:
             import torch
-            be, D = self.bank.backend, self.bank.bond_d
-            fields = layout.var_fields(D, 0)
+            be, D, rank = self.bank.backend, self.bank.bond_d, self.rank
+            fields = layout.var_fields(D, rank)
 
             def packed(get):
                 rows = []
                 for tr in self.trainers:
                     variables = tr.model.variables
-                    zeros = {k: np.zeros_like(variables[k]) for k in layout.var_order(0)}
+                    zeros = {k: np.zeros_like(variables[k]) for k in layout.var_order(rank)}
                     rows.append(layout.pack(fields, {**zeros, **get(tr)}))
                 return torch.from_numpy(np.stack(rows)).to(be.device)
 
@@ -126,6 +147,8 @@ class BankTrainer:
             st = {"vars": packed(lambda tr: tr.model.variables), "m": packed(lambda tr: tr.opt.m), "v": packed(lambda tr: tr.opt.v)}
             st["params"] = torch.empty((M, layout.size(layout.param_fields(D, with_A=True))), dtype=torch.float32, device=be.device)
             st["losses"] = torch.zeros((M, 2), dtype=torch.float32, device=be.device)
+            if rank:
+                st["phi"] = torch.empty((M, layout.size(layout.phi_fields(D, rank))), dtype=torch.float32, device=be.device)
             hyper = np.array([[tr.opt.lr, tr.model.h_reg, tr.model.r_reg, float(tr.model._c_r), float(tr.model._c_h)] for tr in self.trainers],
                              dtype=np.float64)
             st["hyper"] = torch.from_numpy(hyper).to(be.device)       # uploaded once: the device forms lr_t itself
@@ -138,14 +161,19 @@ class BankTrainer:
     def _apply(self, grad_sums, global_batch):
         st, o = self._dev, self.trainers[0].opt
         t = max(o.t, 1)
-        self.bank.backend.bank_apply_step(st["vars"], st["m"], st["v"], grad_sums, global_batch, math.sqrt(1.0 - o.b2 ** t), 1.0 - o.b1 ** t,
-                                          o.b1, o.b2, o.eps, st["hyper"], True, st["params"], st["losses"])
+        be, bias = self.bank.backend, (math.sqrt(1.0 - o.b2 ** t), 1.0 - o.b1 ** t)
+        if self.rank:
+            be.rho_bank_apply_step(st["vars"], st["m"], st["v"], grad_sums, self.rank, global_batch, *bias, o.b1, o.b2, o.eps, st["hyper"], True,
+                                   st["params"], st["phi"], st["losses"])
+        else:
+            be.bank_apply_step(st["vars"], st["m"], st["v"], grad_sums, global_batch, *bias, o.b1, o.b2, o.eps, st["hyper"], True, st["params"],
+                               st["losses"])
 
     def sync_to_host(self):
         """Device-resident state -> every member's model.variables and Adam slots."""
         if self._dev is None or not self._dirty:
             return
-        fields = layout.var_fields(self.bank.bond_d, 0)
+        fields = layout.var_fields(self.bank.bond_d, self.rank)
         host = {name: self._dev[name].cpu().numpy() for name in ("vars", "m", "v")}
         for m, tr in enumerate(self.trainers):
             for name, dst in (("vars", tr.model._variables), ("m", tr.opt.m), ("v", tr.opt.v)):
@@ -181,9 +209,14 @@ class BankTrainer:
         st = self._device_state()
         audio = m0._to_device(data)
         B, T = audio.shape[-2:]
-        be.bank_set_params_dev(st["params"], m0.sigma, m0.delta_t, int(B), int(T), train=True)
-        be.bank_forward(audio, save_for_bwd=True)
-        flat = be.bank_backward()
+        if self.rank:
+            be.rho_bank_set_state_dev(st["params"], st["phi"], self.rank, m0.sigma, m0.delta_t, int(B), int(T), train=True)
+            be.rho_bank_forward(audio, save_for_bwd=True)
+            flat = be.rho_bank_backward()
+        else:
+            be.bank_set_params_dev(st["params"], m0.sigma, m0.delta_t, int(B), int(T), train=True)
+            be.bank_forward(audio, save_for_bwd=True)
+            flat = be.bank_backward()
         for tr in self.trainers:
             tr.opt.t += 1
             tr.global_step += 1
@@ -201,8 +234,8 @@ class BankTrainer:
             raise RuntimeError("best(): no member has a finite loss")
         return int(np.argmin(np.where(np.isfinite(loss), loss, np.inf)))
 
-    def member(self, m: int) -> PsiCMPS:
-        """Member ``m`` as an ordinary PsiCMPS holding its current variables: sample, open_stream, evaluate and save work on it as on any
+    def member(self, m: int):
+        """Member ``m`` as an ordinary PsiCMPS (RhoBank: RhoCMPS) holding its current variables: sample, open_stream, evaluate and save work on it as on any
         model (its scans reconfigure the shared backend; the next bank step configures it again)."""
         self.sync_to_host()
         return self.trainers[m].model
@@ -222,11 +255,15 @@ class BankTrainer:
         if T < 2 or mb < 1:
             raise ValueError("evaluate needs T >= 2 and minibatch_size >= 1")
         st = self._device_state()
-        be.bank_set_params_dev(st["params"], m0.sigma, m0.delta_t, min(mb, dataset.n_clips), T, train=False)
+        if self.rank:
+            be.rho_bank_set_state_dev(st["params"], st["phi"], self.rank, m0.sigma, m0.delta_t, min(mb, dataset.n_clips), T, train=False)
+        else:
+            be.bank_set_params_dev(st["params"], m0.sigma, m0.delta_t, min(mb, dataset.n_clips), T, train=False)
+        forward = be.rho_bank_forward if self.rank else be.bank_forward
         M = len(self.trainers)
         stats, kept = [None] * M, [[] for _ in range(M)]
         for first_id, batch in dataset.ordered(mb, T):
-            loss = be.bank_forward(batch, save_for_bwd=False)
+            loss = forward(batch, save_for_bwd=False)
             for m in range(M):
                 stats[m] = be.loss_stats(loss[m], first_id, stats[m], reset=stats[m] is None)
                 if keep_losses:
@@ -246,6 +283,8 @@ class BankTrainer:
         for m, tr in enumerate(self.trainers):
             tr.save(self.member_path(directory, m))
         meta = {"members": self.bank.overrides, "adam_step": int(self.trainers[0].opt.t), "global_step": int(self.global_step)}
+        if self.rank:                 # (a PsiCMPS bank's file stays as it was)
+            meta["model"] = self.bank.MODEL_NAME
         tmp = os.path.join(directory, "bank.json.tmp")
         with open(tmp, "w") as f:
             json.dump(meta, f)
@@ -257,6 +296,8 @@ class BankTrainer:
             return False
         with open(path) as f:
             meta = json.load(f)
+        if meta.get("model", PsiBank.MODEL_NAME) != self.bank.MODEL_NAME:
+            raise ValueError(f"{path} was written by a bank of {meta.get('model', PsiBank.MODEL_NAME)} models, this bank holds {self.bank.MODEL_NAME}")
         if meta["members"] != json.loads(json.dumps(self.bank.overrides)):
             raise ValueError(f"{path} was written by a bank of other members: {meta['members']}")
         self.drop_device_state()      # the device-resident copy is rebuilt from the restored state

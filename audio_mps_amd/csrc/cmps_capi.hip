@@ -26,7 +26,7 @@ struct Saved {
     bool bwd_ok = false;           // rho: written by cmps_rho_loss_fwd (not by the sampler), a reverse pass may follow
     bool grad1 = false;            // rho: the GEMM forward accumulated RhoDev::p1
     int k0 = 0;                    // rho: the table row of the first saved step (a cmps_rho_stream segment; else 0)
-    int M = 0, n_audio = 0;        // main: written by cmps_bank_loss_fwd for M members from n_audio batches (0: a plain forward)
+    int M = 0, n_audio = 0;        // written by cmps_bank_loss_fwd (main) / cmps_rho_bank_loss_fwd (rho) for M members from n_audio batches (0: a plain forward)
 };
 
 struct cmps_handle_s {
@@ -40,6 +40,8 @@ struct cmps_handle_s {
     bool params_set = false;
     bool legacy = false;       // the tables currently hold the legacy AudioMPS arithmetic (cmps_legacy_set_params)
     int bank_M = 0;            // > 0: the workspace holds the tables of a bank of bank_M members (cmps_bank_set_params_dev); 0: plain mode
+    bool bank_rho = false;     // with bank_M > 0: a bank of RhoCMPS models (cmps_rho_bank_set_state_dev) -- every member's region is the main layout
+                               // (tables only) followed by the rho layout, W is member 0's; rho_set stays false, so the plain rho entries refuse
     Saved main, rho;           // the stash of the main workspace (cmps_psi_* / cmps_legacy_* entries) and of the rho workspace
     Layout L{};
     Dev P{};                   // (stash_layout stays 0 here: main_dev() fills it from `main` for the kernels that read the stash)
@@ -151,6 +153,41 @@ Dev bind_workspace(const Layout& L, char* ws) {
     return P;
 }
 
+// The sections of a rho workspace as the kernels see them (cmps_rho_set_state; cmps_rho_bank_set_state_dev: member 0's)
+RhoDev bind_rho_workspace(int D, const RhoLayout& RL, char* ws, int flags, int B_max) {
+    const size_t rD = (size_t)RL.rank * D;
+    RhoDev W{};
+    W.rank = RL.rank;
+    W.phi0 = reinterpret_cast<float2*>(ws + RL.off_phi0);
+    const bool train = (flags & CMPS_WS_TRAIN) != 0;
+    W.stash = train ? reinterpret_cast<float2*>(ws + RL.off_stash) : nullptr;
+    W.scal = train ? reinterpret_cast<float*>(ws + RL.off_scal) : nullptr;
+    W.p1 = (train && D <= 32) ? reinterpret_cast<float*>(ws + RL.off_p1) : nullptr;
+    W.stash_layout = RHO_STASH_BLOCK;                            // (stays: rho_dev() fills it from the record for the kernels that read the stash)
+    W.cols = rD > RHO_LDS_COLS_MAX ? reinterpret_cast<float2*>(ws + RL.off_cols) : nullptr;
+    W.cols_blocks = B_max;
+    W.slabs = train ? reinterpret_cast<float*>(ws + RL.off_slabs) : nullptr;
+    W.sums = train ? reinterpret_cast<float*>(ws + RL.off_sums) : nullptr;
+    W.slab_floats = RL.slab_floats;
+    W.wslabs = (train && D <= 32) ? reinterpret_cast<float*>(ws + RL.off_wslabs) : nullptr;
+    W.wsums = (train && D <= 32) ? reinterpret_cast<float*>(ws + RL.off_wsums) : nullptr;
+    W.vrank = RL.vrank;                                          // > 0: the sections of the wide (virtual-clip) path exist
+    if (RL.vrank) {
+        W.vphi = reinterpret_cast<float2*>(ws + RL.off_vphi);
+        W.vstash = reinterpret_cast<float*>(ws + RL.off_vstash);
+        W.vgops = reinterpret_cast<float*>(ws + RL.off_vgops);
+        W.vopmax = reinterpret_cast<float*>(ws + RL.off_vopmax);
+        W.vscal = reinterpret_cast<float*>(ws + RL.off_vscal);
+        W.rscal = reinterpret_cast<float*>(ws + RL.off_rscal);
+        W.vslabs = reinterpret_cast<float*>(ws + RL.off_vslabs);
+        W.vsums = reinterpret_cast<float*>(ws + RL.off_vsums);
+        W.vaudio = reinterpret_cast<float*>(ws + RL.off_vaudio);
+        W.gphi = reinterpret_cast<float*>(ws + RL.off_gphi);
+        W.vslab_floats = RL.vslab_floats;
+    }
+    return W;
+}
+
 // The Dev / RhoDev of a call that reads a stash: B clips, the layout from the workspace's record
 Dev main_dev(const cmps_handle_s* h, int B) {
     Dev P = h->P;
@@ -188,7 +225,7 @@ int check_bwd(cmps_handle_t h, const char* who, bool ready, const char* fwd, con
 // cmps_psi_grad_status) answers while the workspace holds a bank: its tables would be member 0's alone.  A member is taken out as a plain model.
 int check_not_bank(cmps_handle_t h, const char* who) {
     if (!h->bank_M) return CMPS_OK;
-    return fail(h, CMPS_ERR_STATE, std::string(who) + ": the handle holds a bank (cmps_bank_set_params_dev); call cmps_set_params for one model first");
+    return fail(h, CMPS_ERR_STATE, std::string(who) + ": the handle holds a bank (cmps_bank_set_params_dev / cmps_rho_bank_set_state_dev); call cmps_set_params for one model first");
 }
 
 // the end of a reverse pass whose slabs hold one PAIR of clips each (pair and wide kernels): reduce over (B + 1) / 2 slabs, closing terms
@@ -300,10 +337,13 @@ size_t cmps_workspace_bytes(int D, int B, int T, int flags) {
 static int set_params_impl(cmps_handle_t h, const float* R_re_dev, const float* R_im_dev,
                            const float* freqs_dev, const float* psi0_re_dev, const float* psi0_im_dev,
                            float A, const float* A_dev, double sigma, double delta_t, int T, int B_max, int flags,
-                           void* workspace_dev, size_t workspace_bytes, void* stream, int M = 0) {
-    const std::string w(M > 0 ? "cmps_bank_set_params_dev" : "cmps_set_params");     // the entry that speaks in the messages
+                           void* workspace_dev, size_t workspace_bytes, void* stream, int M = 0, size_t rho_bytes = 0) {
+    // the entry that speaks in the messages
+    const std::string w(rho_bytes ? "cmps_rho_bank_set_state_dev" : M > 0 ? "cmps_bank_set_params_dev" : "cmps_set_params");
     // M > 0 (cmps_bank_set_params_dev, which has checked its own arguments): the parameter pointers are member 0's, member m's lie
-    // m (2 D^2 + 3 D + 1) floats behind them, and member m's workspace is the plain layout at byte m * L.total
+    // m (2 D^2 + 3 D + 1) floats behind them, and member m's workspace is the plain layout at byte m * L.total.
+    // rho_bytes > 0 (cmps_rho_bank_set_state_dev, with the flags of a tables-only main layout): every member's rho layout of that many
+    // bytes follows its main layout, and the stride is their sum.
     if (!h) return CMPS_ERR_BAD_ARG;
     if (!R_re_dev || !R_im_dev || !freqs_dev || !psi0_re_dev || !psi0_im_dev)
         return fail(h, CMPS_ERR_BAD_ARG, w + ": null parameter pointer");
@@ -314,10 +354,11 @@ static int set_params_impl(cmps_handle_t h, const float* R_re_dev, const float* 
     flags &= ~(CMPS_WS_FRESH | CMPS_WS_REUSE_TABLES);
     Layout L = make_layout(h->D, B_max, T, flags);
     const size_t members = M > 0 ? (size_t)M : 1, n_par = 2 * (size_t)h->D * h->D + 3 * (size_t)h->D + 1;
-    if (workspace_bytes < members * L.total) {
+    const size_t stride = L.total + rho_bytes;
+    if (workspace_bytes < members * stride) {
         char buf[160];
         snprintf(buf, sizeof buf, "%s: workspace has %zu bytes, needs %zu", w.c_str(), workspace_bytes,
-                 members * L.total);
+                 members * stride);
         return fail(h, CMPS_ERR_WORKSPACE, buf);
     }
     if (((uintptr_t)workspace_dev & 255) != 0)
@@ -332,9 +373,9 @@ static int set_params_impl(cmps_handle_t h, const float* R_re_dev, const float* 
     P.c_half = (float)(-delta_t * sigma * sigma) / 2.0f;
     const float dt = (float)delta_t;  // model.py:16
     P.dt = dt;
-    if (M > 0) { P.bank_stride = L.total; P.bank_adev = n_par; }
+    if (M > 0) { P.bank_stride = stride; P.bank_adev = n_par; }
     // (a bank's members each have a time table: another member count, or a change between bank and plain mode, moves or adds tables)
-    const bool rebuild = fresh || h->bank_M != M || (M > 0 && h->P.bank_stride != L.total) || !(h->tt_ws == ws && h->tt_N == L.N && h->tt_dt == dt);
+    const bool rebuild = fresh || h->bank_M != M || (M > 0 && h->P.bank_stride != stride) || !(h->tt_ws == ws && h->tt_N == L.N && h->tt_dt == dt);
     hipError_t e = launch_prep(P, R_re_dev, R_im_dev, freqs_dev, psi0_re_dev, psi0_im_dev, dt, rebuild,
                                const_cast<float*>(P.ttab), const_cast<float*>(P.dtk),
                                const_cast<float2*>(P.R), const_cast<float2*>(P.RT),
@@ -348,7 +389,7 @@ static int set_params_impl(cmps_handle_t h, const float* R_re_dev, const float* 
     if (P.status && (fresh || h->ws != ws || h->legacy || !h->params_set || h->P.status != P.status || h->bank_M != M ||
                      h->P.bank_stride != P.bank_stride)) {
         // (every member's pair of words, one workspace apart: one strided fill)
-        e = M > 0 ? hipMemset2DAsync(P.status, L.total, 0, 2 * sizeof(unsigned), members, static_cast<hipStream_t>(stream))
+        e = M > 0 ? hipMemset2DAsync(P.status, stride, 0, 2 * sizeof(unsigned), members, static_cast<hipStream_t>(stream))
                   : hipMemsetAsync(P.status, 0, 2 * sizeof(unsigned), static_cast<hipStream_t>(stream));
         if (e != hipSuccess) return fail_hip(h, e, (w + " (status words)").c_str());
     }
@@ -357,6 +398,7 @@ static int set_params_impl(cmps_handle_t h, const float* R_re_dev, const float* 
     h->params_set = true;
     h->legacy = false;
     h->bank_M = M;
+    h->bank_rho = false;              // (cmps_rho_bank_set_state_dev sets it once the columns are packed)
     h->main.valid = false;
     h->rho_set = false;               // the columns of rho_0 are handed over again after every parameter change
     h->rho.valid = false;
@@ -604,7 +646,7 @@ int cmps_bank_loss_fwd(cmps_handle_t h, const float* audio_dev, int n_audio, int
     const char* who = "cmps_bank_loss_fwd";
     if (!h) return CMPS_ERR_BAD_ARG;
     if (const int rc = bank_check_mode(h, who, true)) return rc;
-    if (const int rc = check_fwd(h, who, h->params_set && !h->legacy && h->bank_M > 0, "cmps_bank_set_params_dev", audio_dev, loss_dev, B, T,
+    if (const int rc = check_fwd(h, who, h->params_set && !h->legacy && h->bank_M > 0 && !h->bank_rho, "cmps_bank_set_params_dev", audio_dev, loss_dev, B, T,
                                  h->L.T, h->L.B, save_for_bwd, h->L.flags)) return rc;
     if (n_audio != 1 && n_audio != h->bank_M) return fail(h, CMPS_ERR_BAD_ARG, std::string(who) + ": n_audio must be 1 (one shared batch) or M");
     return psi_fwd_run(h, who, h->bank_M, n_audio, audio_dev, B, T, loss_dev, save_for_bwd, stream);
@@ -614,7 +656,7 @@ int cmps_bank_loss_bwd(cmps_handle_t h, const float* audio_dev, int n_audio, int
     const char* who = "cmps_bank_loss_bwd";
     if (!h) return CMPS_ERR_BAD_ARG;
     if (const int rc = bank_check_mode(h, who, true)) return rc;
-    const bool ready = h->params_set && !h->legacy && h->bank_M > 0 && h->main.M == h->bank_M;
+    const bool ready = h->params_set && !h->legacy && h->bank_M > 0 && !h->bank_rho && h->main.M == h->bank_M;
     if (const int rc = check_bwd(h, who, ready, "cmps_bank_loss_fwd", h->main, audio_dev, grad_dev, B, T)) return rc;
     if (n_audio != h->main.n_audio) return fail(h, CMPS_ERR_STATE, std::string(who) + ": n_audio differs from the forward call");
     return psi_bwd_run(h, who, h->bank_M, n_audio, audio_dev, B, T, grad_dev, stream);
@@ -647,7 +689,7 @@ int cmps_bank_grad_status(cmps_handle_t h, int* codes_out, int* sticky_out, void
     const std::string w("cmps_bank_grad_status");
     if (!h) return CMPS_ERR_BAD_ARG;
     if (!codes_out) return fail(h, CMPS_ERR_BAD_ARG, w + ": null codes_out");
-    if (!h->params_set || h->legacy || h->bank_M < 1 || !h->P.status)
+    if (!h->params_set || h->legacy || h->bank_M < 1 || h->bank_rho || !h->P.status)
         return fail(h, CMPS_ERR_STATE, w + ": needs cmps_bank_set_params_dev with a CMPS_WS_TRAIN workspace");
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int M = h->bank_M;
@@ -942,6 +984,7 @@ int cmps_legacy_set_params(cmps_handle_t h, const float* R_dev, const float* Q_r
     h->params_set = true;
     h->legacy = true;
     h->bank_M = 0;
+    h->bank_rho = false;
     h->main.valid = false;
     h->rho_set = false;
     return CMPS_OK;
@@ -1013,7 +1056,6 @@ int cmps_rho_set_state(cmps_handle_t h, const float* phi_re_dev, const float* ph
         return fail(h, CMPS_ERR_BAD_ARG, "cmps_rho_set_state: bad argument");
     if (T > h->L.T) return fail(h, CMPS_ERR_BAD_ARG, "cmps_rho_set_state: T exceeds T of cmps_set_params (the per-step tables)");
     if (rank > 128) return fail(h, CMPS_ERR_UNSUPPORTED_D, "cmps_rho_set_state: rank above 128");
-    const size_t rD = (size_t)rank * h->D;
     if (!rho_workspace_dev) return fail(h, CMPS_ERR_WORKSPACE, "cmps_rho_set_state: null workspace");
     if (((uintptr_t)rho_workspace_dev & 255) != 0)
         return fail(h, CMPS_ERR_WORKSPACE, "cmps_rho_set_state: workspace must be 256-byte aligned");
@@ -1024,35 +1066,7 @@ int cmps_rho_set_state(cmps_handle_t h, const float* phi_re_dev, const float* ph
         return fail(h, CMPS_ERR_WORKSPACE, buf);
     }
     char* ws = static_cast<char*>(rho_workspace_dev);
-    RhoDev W{};
-    W.rank = rank;
-    W.phi0 = reinterpret_cast<float2*>(ws + RL.off_phi0);
-    const bool train = (flags & CMPS_WS_TRAIN) != 0;
-    W.stash = train ? reinterpret_cast<float2*>(ws + RL.off_stash) : nullptr;
-    W.scal = train ? reinterpret_cast<float*>(ws + RL.off_scal) : nullptr;
-    W.p1 = (train && h->D <= 32) ? reinterpret_cast<float*>(ws + RL.off_p1) : nullptr;
-    W.stash_layout = RHO_STASH_BLOCK;                            // (stays: rho_dev() fills it from the record for the kernels that read the stash)
-    W.cols = rD > RHO_LDS_COLS_MAX ? reinterpret_cast<float2*>(ws + RL.off_cols) : nullptr;
-    W.cols_blocks = B_max;
-    W.slabs = train ? reinterpret_cast<float*>(ws + RL.off_slabs) : nullptr;
-    W.sums = train ? reinterpret_cast<float*>(ws + RL.off_sums) : nullptr;
-    W.slab_floats = RL.slab_floats;
-    W.wslabs = (train && h->D <= 32) ? reinterpret_cast<float*>(ws + RL.off_wslabs) : nullptr;
-    W.wsums = (train && h->D <= 32) ? reinterpret_cast<float*>(ws + RL.off_wsums) : nullptr;
-    W.vrank = RL.vrank;                                          // > 0: the sections of the wide (virtual-clip) path exist
-    if (RL.vrank) {
-        W.vphi = reinterpret_cast<float2*>(ws + RL.off_vphi);
-        W.vstash = reinterpret_cast<float*>(ws + RL.off_vstash);
-        W.vgops = reinterpret_cast<float*>(ws + RL.off_vgops);
-        W.vopmax = reinterpret_cast<float*>(ws + RL.off_vopmax);
-        W.vscal = reinterpret_cast<float*>(ws + RL.off_vscal);
-        W.rscal = reinterpret_cast<float*>(ws + RL.off_rscal);
-        W.vslabs = reinterpret_cast<float*>(ws + RL.off_vslabs);
-        W.vsums = reinterpret_cast<float*>(ws + RL.off_vsums);
-        W.vaudio = reinterpret_cast<float*>(ws + RL.off_vaudio);
-        W.gphi = reinterpret_cast<float*>(ws + RL.off_gphi);
-        W.vslab_floats = RL.vslab_floats;
-    }
+    const RhoDev W = bind_rho_workspace(h->D, RL, ws, flags, B_max);
     hipError_t e = launch_pack_phi(h->P, W, phi_re_dev, phi_im_dev, static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return fail_hip(h, e, "cmps_rho_set_state");
     h->RL = RL; h->W = W;
@@ -1128,6 +1142,140 @@ int cmps_rho_loss_bwd(cmps_handle_t h, const float* audio_dev, int B, int T, flo
     e = launch_reduce_finalize(P, loss, grad_dev, s);
     if (e == hipSuccess) e = launch_finalize_rho(P, W, grad_dev, s);
     if (e != hipSuccess) return fail_hip(h, e, "cmps_rho_loss_bwd (reduce)");
+    return CMPS_OK;
+}
+
+// ---- model bank of RhoCMPS members (include/cmps.h): the kernel set a plain handle picks at D <= 32, 3 <= rank <= 32 ----
+
+constexpr int RHO_BANK_RANK_MIN = 3, RHO_BANK_RANK_MAX = 32, RHO_BANK_D_MAX = 32;
+static bool rho_bank_shape_ok(int D, int rank) {
+    return D >= 1 && D <= RHO_BANK_D_MAX && rank >= RHO_BANK_RANK_MIN && rank <= RHO_BANK_RANK_MAX;
+}
+// What every cmps_rho_bank_* entry that launches scans refuses before it looks at its other arguments: the shapes and the settings whose
+// kernels have no member dimension (the block and wide families, the column-by-column wave kernels of CMPS_VARIANT_WAVE32 and of
+// rank <= 2, k_bwd_rho_mfma, the one-wave k_bwd_wave)
+static int rho_bank_check_mode(cmps_handle_t h, const char* who, int rank) {
+    const std::string w(who);
+    if (!rho_bank_shape_ok(h->D, rank))
+        return fail(h, CMPS_ERR_UNSUPPORTED_D, w + ": a RhoCMPS bank needs D <= 32 and 3 <= rank <= 32");
+    if (h->variant_req != CMPS_VARIANT_AUTO && h->variant_req != CMPS_VARIANT_WAVE)
+        return fail(h, CMPS_ERR_STATE, w + ": a RhoCMPS bank runs under CMPS_VARIANT_AUTO or CMPS_VARIANT_WAVE only");
+    if (!h->rho_virtual_bwd || h->rank1_mode != CMPS_RANK1_DEFAULT || h->bwd_waves != 2 || h->f16_shift != 0)
+        return fail(h, CMPS_ERR_STATE, w + ": a RhoCMPS bank runs with the default CMPS_OPT_RHO_BWD, CMPS_OPT_RANK1, CMPS_OPT_BWD_WAVES and "
+                                           "CMPS_OPT_F16_SCALE_SHIFT only");
+    return CMPS_OK;
+}
+
+size_t cmps_rho_bank_workspace_bytes(int D, int rank, int M, int B, int T, int flags) {
+    if (M < 1 || M > BANK_MAX || !rho_bank_shape_ok(D, rank)) return 0;
+    flags &= ~(CMPS_WS_FRESH | CMPS_WS_REUSE_TABLES);
+    const size_t a = cmps_workspace_bytes(D, B, T, CMPS_WS_FWD_ONLY), b = cmps_rho_workspace_bytes(D, rank, B, T, flags);
+    return (a && b) ? (size_t)M * (a + b) : 0;
+}
+
+int cmps_rho_bank_set_state_dev(cmps_handle_t h, int M, const float* params_dev, const float* phi_dev, int rank, double sigma, double delta_t,
+                                int T, int B_max, int flags, void* workspace_dev, size_t workspace_bytes, void* stream) {
+    const char* who = "cmps_rho_bank_set_state_dev";
+    const std::string w(who);
+    if (!h) return CMPS_ERR_BAD_ARG;
+    if (const int rc = rho_bank_check_mode(h, who, rank)) return rc;
+    if (!params_dev || !phi_dev) return fail(h, CMPS_ERR_BAD_ARG, w + ": null parameter / column buffer");
+    if (const int rc = bank_check_M(h, who, M)) return rc;
+    if (B_max < 1 || T < 2) return fail(h, CMPS_ERR_BAD_ARG, w + ": need B_max >= 1 and T >= 2");
+    if ((unsigned long long)M * (unsigned long long)B_max * (unsigned long long)rank * (unsigned long long)T > 0x7fffffffull)
+        return fail(h, CMPS_ERR_BAD_ARG, w + ": M * B_max * rank * T overflows");
+    if (!workspace_dev) return fail(h, CMPS_ERR_WORKSPACE, w + ": null workspace");
+    const int rflags = flags & ~(CMPS_WS_FRESH | CMPS_WS_REUSE_TABLES);
+    const RhoLayout RL = make_rho_layout(h->D, rank, B_max, T, rflags);
+    const size_t DD = (size_t)h->D * h->D, D = (size_t)h->D;
+    // every member's tables (the main layout without its training sections), the size and alignment checks of the whole workspace
+    if (const int rc = set_params_impl(h, params_dev, params_dev + DD, params_dev + 2 * DD, params_dev + 2 * DD + D, params_dev + 2 * DD + 2 * D,
+                                       0.f, params_dev + 2 * DD + 3 * D, sigma, delta_t, T, B_max, flags & ~CMPS_WS_TRAIN, workspace_dev,
+                                       workspace_bytes, stream, M, RL.total)) return rc;
+    // member 0's rho sections lie behind its main layout; rho_bank_view / bank_view / bank_view_phi move them by the one stride
+    const RhoDev W = bind_rho_workspace(h->D, RL, h->ws + h->L.total, rflags, B_max);
+    const hipError_t e = launch_pack_phi(h->P, W, phi_dev, phi_dev + (size_t)rank * D, static_cast<hipStream_t>(stream), M);
+    if (e != hipSuccess) { h->params_set = false; return fail_hip(h, e, who); }
+    h->RL = RL; h->W = W;
+    h->rho_B = B_max; h->rho_T = T; h->rho_flags = rflags;
+    h->bank_rho = true;
+    h->rho.valid = h->rho.bwd_ok = false;
+    return CMPS_OK;
+}
+
+int cmps_rho_bank_loss_fwd(cmps_handle_t h, const float* audio_dev, int n_audio, int B, int T, float* loss_dev, int save_for_bwd, void* stream) {
+    const char* who = "cmps_rho_bank_loss_fwd";
+    if (!h) return CMPS_ERR_BAD_ARG;
+    const bool ready = h->params_set && h->bank_M > 0 && h->bank_rho;
+    if (ready) if (const int rc = rho_bank_check_mode(h, who, h->W.rank)) return rc;
+    if (const int rc = check_fwd(h, who, ready, "cmps_rho_bank_set_state_dev", audio_dev, loss_dev, B, T, h->rho_T, h->rho_B, save_for_bwd,
+                                 h->rho_flags)) return rc;
+    const int M = h->bank_M;
+    if (n_audio != 1 && n_audio != M) return fail(h, CMPS_ERR_BAD_ARG, std::string(who) + ": n_audio must be 1 (one shared batch) or M");
+    Dev P = h->P;
+    P.B = B;
+    P.bank_audio = n_audio == 1 ? 0 : (size_t)B * T; P.bank_loss = (size_t)B;
+    const bool save = save_for_bwd != 0;
+    const bool mfma = h->W.rank > (save ? 2 : 8);                  // as cmps_rho_loss_fwd chooses with the virtual-clip reverse sweep
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    KBind kb(h);
+    hipError_t e;
+    {
+        KScope ks(mfma ? "k_fwd_rho_mfma" : "k_fwd_rho_wave", s);
+        e = mfma ? launch_fwd_rho_mfma(P, h->W, audio_dev, loss_dev, save, rank1_f16(h->rank1_mode), false, s, M)
+                 : launch_fwd_rho_wave(P, h->W, audio_dev, loss_dev, save, s, M);
+    }
+    if (e != hipSuccess) return fail_hip(h, e, who);
+    h->rho = Saved{save, B, T - 1, audio_dev, loss_dev, mfma ? RHO_STASH_MFMA : RHO_STASH_WAVE, save, false};
+    h->rho.M = M; h->rho.n_audio = n_audio;
+    return CMPS_OK;
+}
+
+int cmps_rho_bank_loss_bwd(cmps_handle_t h, const float* audio_dev, int n_audio, int B, int T, float* grad_dev, void* stream) {
+    const char* who = "cmps_rho_bank_loss_bwd";
+    if (!h) return CMPS_ERR_BAD_ARG;
+    const bool ready = h->params_set && h->bank_M > 0 && h->bank_rho && h->rho.bwd_ok && h->rho.M == h->bank_M;
+    if (ready) if (const int rc = rho_bank_check_mode(h, who, h->W.rank)) return rc;
+    if (const int rc = check_bwd(h, who, ready, "cmps_rho_bank_loss_fwd", h->rho, audio_dev, grad_dev, B, T)) return rc;
+    if (n_audio != h->rho.n_audio) return fail(h, CMPS_ERR_STATE, std::string(who) + ": n_audio differs from the forward call");
+    const int M = h->bank_M, rank = h->W.rank;
+    Dev P = h->P;
+    P.B = B;
+    P.bank_audio = n_audio == 1 ? 0 : (size_t)B * T; P.bank_loss = (size_t)B;
+    P.bank_grad = 2 * (size_t)h->D * h->D + 3 * (size_t)h->D + 2 + 2 * (size_t)rank * h->D;
+    KBind kb(h);
+    // (a saved bank forward wrote RHO_STASH_MFMA rows: rank >= 3)
+    const hipError_t e = launch_bwd_rho_virtual_wave(P, rho_dev(h), audio_dev, h->rho.loss, grad_dev, wave_rank1(h->rank1_mode), h->bwd_waves,
+                                                     static_cast<hipStream_t>(stream), M);
+    if (e != hipSuccess) return fail_hip(h, e, (std::string(who) + " (virtual clips)").c_str());
+    return CMPS_OK;
+}
+
+size_t cmps_rho_bank_apply_step_scratch_bytes(int D, int rank, int M) {
+    return (M < 1 || M > BANK_MAX || !rho_bank_shape_ok(D, rank)) ? 0 : (size_t)M * cmps_rho_apply_step_scratch_bytes(D, rank);
+}
+
+int cmps_rho_bank_apply_step(cmps_handle_t h, int M, float* vars_dev, float* adam_m_dev, float* adam_v_dev, const float* grad_sums_dev, int rank,
+                             double global_batch, double bias_num, double bias_den, double beta1, double beta2, double epsilon,
+                             const double* hyper_dev, int with_reg, float* params_dev, float* phi_dev, float* losses_dev, void* scratch_dev,
+                             void* stream) {
+    const char* who = "cmps_rho_bank_apply_step";
+    const std::string w(who);
+    if (!h) return CMPS_ERR_BAD_ARG;
+    if (!rho_bank_shape_ok(h->D, rank)) return fail(h, CMPS_ERR_UNSUPPORTED_D, w + ": a RhoCMPS bank needs D <= 32 and 3 <= rank <= 32");
+    if (!vars_dev || !params_dev || !phi_dev || !hyper_dev)
+        return fail(h, CMPS_ERR_BAD_ARG, w + ": null variable / parameter / column / hyper-parameter buffer");
+    if (const int rc = bank_check_M(h, who, M)) return rc;
+    const bool apply = grad_sums_dev != nullptr;
+    if (apply && (!adam_m_dev || !adam_v_dev || !losses_dev || !scratch_dev || !(global_batch > 0.0)))
+        return fail(h, CMPS_ERR_BAD_ARG, w + ": an update needs the Adam slots, losses_dev, scratch_dev and a positive batch");
+    if (((uintptr_t)scratch_dev & 7) != 0) return fail(h, CMPS_ERR_BAD_ARG, w + ": scratch_dev must be 8-byte aligned");
+    if (((uintptr_t)hyper_dev & 7) != 0) return fail(h, CMPS_ERR_BAD_ARG, w + ": hyper_dev must be 8-byte aligned");
+    const hipError_t e = launch_rho_bank_apply_step(h->D, rank, M, apply, apply ? 1.0 / global_batch : 0.0, bias_num, bias_den, beta1, beta2,
+                                                    epsilon, hyper_dev, with_reg != 0, vars_dev, adam_m_dev, adam_v_dev, grad_sums_dev,
+                                                    params_dev, phi_dev, losses_dev, static_cast<double*>(scratch_dev),
+                                                    static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail_hip(h, e, who);
     return CMPS_OK;
 }
 

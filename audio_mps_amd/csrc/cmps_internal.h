@@ -291,6 +291,35 @@ struct RhoDev {
     size_t slab_floats;
 };
 
+// bank_view for the one kernel instance that reads Dev::phi0, k_bwd_wave2w<false> on RhoCMPS's virtual clips: the columns lie in the
+// member's region too and move with it (null, a pure-state model: stays null).  Kept out of bank_view itself: with the move inside it
+// the compiler laid out k_bwd_wave2w<true>, the flagship's reverse scan, which never has columns, differently, and bench.py's bwd_ms
+// rose by 0.6 % in six interleaved A/B runs; this way that instance's code is the parent's, byte for byte.
+__host__ __device__ __forceinline__ Dev bank_view_phi(Dev P, unsigned member) {
+    const float2* phi0 = P.phi0 ? bank_shift(P.phi0, (size_t)member * P.bank_stride) : nullptr;
+    P = bank_view(P, member);
+    P.phi0 = phi0;
+    return P;
+}
+
+// A bank of RhoCMPS models (cmps_rho_bank_*) has ONE workspace: member m's region is the plain main layout (tables only) followed by
+// the plain rho layout, Dev::bank_stride bytes behind member m - 1's, so that the virtual-clip reverse sweep's Dev -- which takes
+// R, Q, rho, the time tables and Adev from the main part and the stash, the scalars, the slabs and phi0 from the rho part -- moves
+// by the one stride bank_view knows.  The RhoDev of a member: every section moved by `bytes` = member * Dev::bank_stride; sections
+// a workspace does not have stay null.  (`cols` is null in a bank's scope, rank * D <= 1024; the wide path's v* sections do not exist
+// at D <= 32.)  0 bytes (every plain launch) is the RhoDev as it was handed in.
+__host__ __device__ __forceinline__ RhoDev rho_bank_view(RhoDev W, size_t bytes) {
+    W.phi0 = bank_shift(W.phi0, bytes);
+    if (W.stash) W.stash = bank_shift(W.stash, bytes);
+    if (W.scal) W.scal = bank_shift(W.scal, bytes);
+    if (W.p1) W.p1 = bank_shift(W.p1, bytes);
+    if (W.slabs) W.slabs = bank_shift(W.slabs, bytes);
+    if (W.sums) W.sums = bank_shift(W.sums, bytes);
+    if (W.wslabs) W.wslabs = bank_shift(W.wslabs, bytes);
+    if (W.wsums) W.wsums = bank_shift(W.wsums, bytes);
+    return W;
+}
+
 // ---- host-side dispatch of a run-time value to a template argument, written once for every launcher ----
 // f(std::integral_constant<int, PD>{}) for the padded bond dimension of the MFMA / wide kernels (64, 96 or 128)
 template <typename F>
@@ -337,7 +366,8 @@ inline hipError_t lds_attr(K kernel, size_t shm) {
 inline int round_up64(int d) { return (d + 63) / 64 * 64; }   // whole waves for d threads
 
 // ---- launchers (each returns the hipError_t of its launches) ----
-hipError_t launch_pack_phi(const Dev& P, const RhoDev& W, const float* re, const float* im, hipStream_t s);
+// (M > 1, cmps_rho_bank_set_state_dev: member m's columns lie 2 rank D floats behind member m - 1's, its phi0 P.bank_stride bytes)
+hipError_t launch_pack_phi(const Dev& P, const RhoDev& W, const float* re, const float* im, hipStream_t s, int M = 1);
 hipError_t launch_fwd_rho(const Dev& P, const RhoDev& W, const float* audio, float* loss, bool save, hipStream_t s);
 hipError_t launch_bwd_rho(const Dev& P, const RhoDev& W, const float* audio, hipStream_t s);
 hipError_t launch_finalize_rho(const Dev& P, const RhoDev& W, float* grad_out, hipStream_t s);
@@ -398,8 +428,9 @@ hipError_t launch_sample_rho(const Dev& P, const RhoDev& W, const SampleDev& S, 
 hipError_t launch_fwd_legacy_wave(const Dev& P, const float* audio, float* loss, bool save, hipStream_t s);
 hipError_t launch_bwd_legacy_wave(const Dev& P, const float* audio, int rank1_mode, hipStream_t s);
 hipError_t launch_legacy_tables(const Dev& P, float2* psi0, float* dtk, float2* rho, hipStream_t s);
-hipError_t launch_fwd_rho_wave(const Dev& P, const RhoDev& W, const float* audio, float* loss, bool save, hipStream_t s);
-hipError_t launch_fwd_rho_mfma(const Dev& P, const RhoDev& W, const float* audio, float* loss, bool save, bool f16, bool grad1, hipStream_t s);
+hipError_t launch_fwd_rho_wave(const Dev& P, const RhoDev& W, const float* audio, float* loss, bool save, hipStream_t s, int M = 1);
+hipError_t launch_fwd_rho_mfma(const Dev& P, const RhoDev& W, const float* audio, float* loss, bool save, bool f16, bool grad1, hipStream_t s,
+                               int M = 1);
 hipError_t launch_bwd_rho_mfma(const Dev& P, const RhoDev& W, const float* audio, hipStream_t s);
 hipError_t launch_sample_rho_mfma(const Dev& P, const RhoDev& W, const SampleDev& S, bool save, bool f16, hipStream_t s);
 hipError_t launch_bwd_rho_wave(const Dev& P, const RhoDev& W, const float* audio, hipStream_t s);
@@ -424,7 +455,7 @@ hipError_t launch_fwd_wide_legacy(const Dev& P, const float* audio, float* loss,
 hipError_t launch_bwd_wide_legacy(const Dev& P, const float* audio, hipStream_t s);
 hipError_t launch_grad_wide_legacy(const Dev& P, const float* audio, bool f16, hipStream_t s);
 hipError_t launch_bwd_rho_virtual_wave(const Dev& P, const RhoDev& W, const float* audio, const float* loss, float* grad_out, int rank1_mode, int bwd_waves,
-                                       hipStream_t s);
+                                       hipStream_t s, int M = 1);
 hipError_t launch_fwd_rho_wide(const Dev& P, const RhoDev& W, const float* audio, float* loss, bool hy_f16, hipStream_t s);
 hipError_t launch_bwd_rho_wide(const Dev& P, const RhoDev& W, const float* loss, float* grad_out, int pieces, hipStream_t s);
 hipError_t launch_fwd_chain16(const Dev& P, const float* audio, hipStream_t s);
@@ -478,6 +509,11 @@ hipError_t launch_rho_apply_step(int D, int rank, bool apply, double inv_batch, 
                                  double h_reg, double r_reg, double c_r, double c_h, bool with_reg, float* vars, float* am, float* av,
                                  const float* grad_sums, float* params_out, float* phi_out, float* losses_out, double* scratch,
                                  hipStream_t s);
+// cmps_rho_bank_apply_step: M members' RhoCMPS steps in one launch; hyper as for launch_bank_apply_step
+hipError_t launch_rho_bank_apply_step(int D, int rank, int M, bool apply, double inv_batch, double bias_num, double bias_den, double beta1,
+                                      double beta2, double eps, const double* hyper, bool with_reg, float* vars, float* am, float* av,
+                                      const float* grad_sums, float* params_out, float* phi_out, float* losses_out, double* scratch,
+                                      hipStream_t s);
 
 // model.A (model.py:19) as the kernels see it: a launch argument, or -- device-resident training -- a word of device memory
 __device__ __forceinline__ float dev_A(const Dev& P) { return P.Adev ? *P.Adev : P.A; }

@@ -285,11 +285,36 @@ __global__ __launch_bounds__(ONT) void k_apply_step(OptArgs a, BankArgs k, float
 
 // RhoCMPS (audio_mps_amd/model.py::RhoCMPS.chain_rule, ::columns): the variables end in Wx, Wy [rank, D], the gradient sums in the
 // column cotangents phibar_re, phibar_im [rank, D] (cmps_rho_loss_bwd); phi_out = the columns of the (updated) W.
-__global__ __launch_bounds__(ONT) void k_rho_apply_step(OptArgs a, float* __restrict__ vars, float* __restrict__ am,
+// A bank (cmps_rho_bank_apply_step): one workgroup per member, as k_apply_step<BANK> -- the per-member values from hyper[member], the
+// buffers row `member` of the callers' arrays (RhoBankArgs: floats, for the scratch doubles, between two rows).
+struct RhoBankArgs {
+    const double* hyper;          // [M][5] (the plain step: unused)
+    double bias_num, bias_den;
+    size_t n_vars, n_params, n_phi, n_grad, n_scratch;
+};
+
+template <bool BANK>
+__global__ __launch_bounds__(ONT) void k_rho_apply_step(OptArgs a, RhoBankArgs k, float* __restrict__ vars, float* __restrict__ am,
                                                         float* __restrict__ av, const float* __restrict__ gs,
                                                         float* __restrict__ params, float* __restrict__ phi_out,
                                                         float* __restrict__ losses, double* __restrict__ colsum) {
     __shared__ double red[ONT / 64];
+    if constexpr (BANK) {
+        const size_t m = blockIdx.x;
+        const double* hy = k.hyper + 5 * m;
+        // (workgroup-uniform values that the vector unit computes: back into scalar registers, where the plain step's arguments live)
+        auto uni = [](float x) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(x))); };
+        a.lr_t = uni((float)((hy[0] * k.bias_num) / k.bias_den));
+        auto uni_d = [](double x) {
+            return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(x)), __builtin_amdgcn_readfirstlane(__double2loint(x)));
+        };
+        a.h_reg = uni_d(hy[1]); a.r_reg = uni_d(hy[2]);
+        a.c_r = uni((float)hy[3]); a.c_h = uni((float)hy[4]);
+        a.scaled_r = __builtin_amdgcn_readfirstlane(hy[3] != 1.0 ? 1 : 0); a.scaled_h = __builtin_amdgcn_readfirstlane(hy[4] != 1.0 ? 1 : 0);
+        // (without an update the null buffers are moved and never read)
+        vars += m * k.n_vars; am += m * k.n_vars; av += m * k.n_vars; params += m * k.n_params; phi_out += m * k.n_phi;
+        gs += m * k.n_grad; losses += 2 * m; colsum += m * k.n_scratch;
+    }
     const int D = a.D, DD = D * D, RD = a.rank * D, t = threadIdx.x;
     float* Rx = vars + 1;
     float* Ry = Rx + DD;
@@ -394,7 +419,20 @@ hipError_t launch_rho_apply_step(int D, int rank, bool apply, double inv_batch, 
                                  const float* grad_sums, float* params_out, float* phi_out, float* losses_out, double* scratch,
                                  hipStream_t s) {
     const OptArgs a = opt_args(D, rank, apply, inv_batch, lr_t, beta1, beta2, eps, h_reg, r_reg, c_r, c_h, with_reg);
-    hipLaunchKernelGGL(k_rho_apply_step, dim3(1), dim3(ONT), 0, s, a, vars, am, av, grad_sums, params_out, phi_out, losses_out, scratch);
+    hipLaunchKernelGGL(k_rho_apply_step<false>, dim3(1), dim3(ONT), 0, s, a, RhoBankArgs{}, vars, am, av, grad_sums, params_out, phi_out, losses_out,
+                       scratch);
+    return hipGetLastError();
+}
+
+hipError_t launch_rho_bank_apply_step(int D, int rank, int M, bool apply, double inv_batch, double bias_num, double bias_den, double beta1,
+                                      double beta2, double eps, const double* hyper, bool with_reg, float* vars, float* am, float* av,
+                                      const float* grad_sums, float* params_out, float* phi_out, float* losses_out, double* scratch,
+                                      hipStream_t s) {
+    const OptArgs a = opt_args(D, rank, apply, inv_batch, 0.0, beta1, beta2, eps, 0.0, 0.0, 1.0, 1.0, with_reg);  // (the kernel fills the per-member ones)
+    const size_t DD = (size_t)D * D, RD = (size_t)rank * D;
+    const RhoBankArgs k{hyper, bias_num, bias_den, 1 + 2 * DD + D + 2 * RD, 2 * DD + 3 * D + 1, 2 * RD, 2 * DD + 3 * D + 2 + 2 * RD,
+                        rho_apply_step_scratch_bytes(D, rank) / sizeof(double)};
+    hipLaunchKernelGGL(k_rho_apply_step<true>, dim3(M), dim3(ONT), 0, s, a, k, vars, am, av, grad_sums, params_out, phi_out, losses_out, scratch);
     return hipGetLastError();
 }
 

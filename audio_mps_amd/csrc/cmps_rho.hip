@@ -570,10 +570,13 @@ __global__ __launch_bounds__(NT) void k_sample_rho(Dev P, RhoDev W, const float*
     }
 }
 
-// pack the r initial columns into the DP-strided table
+// pack the r initial columns into the DP-strided table (a bank: member = blockIdx.y, whose columns lie 2 r D floats and whose table
+// `ws` bytes behind its predecessor's; a plain launch has one member)
 __global__ void k_pack_phi(int D, int DP, int r, const float* __restrict__ re, const float* __restrict__ im,
-                           float2* __restrict__ phi0) {
+                           float2* __restrict__ phi0, size_t ws) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    re += (size_t)blockIdx.y * 2 * r * D; im += (size_t)blockIdx.y * 2 * r * D;
+    phi0 = bank_shift(phi0, blockIdx.y * ws);
     if (idx >= r * DP) return;
     const int a = idx / DP, d = idx % DP;
     phi0[idx] = d < D ? make_float2(re[a * D + d], im[a * D + d]) : make_float2(0.f, 0.f);
@@ -582,10 +585,10 @@ __global__ void k_pack_phi(int D, int DP, int r, const float* __restrict__ re, c
 // ------------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------------
-hipError_t launch_pack_phi(const Dev& P, const RhoDev& W, const float* re, const float* im, hipStream_t s) {
+hipError_t launch_pack_phi(const Dev& P, const RhoDev& W, const float* re, const float* im, hipStream_t s, int M) {
     const int n = W.rank * P.DP;
-    hipLaunchKernelGGL(k_pack_phi, dim3((n + 255) / 256), dim3(256), 0, s, P.D, P.DP, W.rank, re, im,
-                       const_cast<float2*>(W.phi0));
+    hipLaunchKernelGGL(k_pack_phi, dim3((n + 255) / 256, M), dim3(256), 0, s, P.D, P.DP, W.rank, re, im,
+                       const_cast<float2*>(W.phi0), P.bank_stride);
     return hipGetLastError();
 }
 

@@ -78,8 +78,12 @@ __device__ __forceinline__ float dpp_nb(float x) { return dpp_mov<0xB1>(x); }   
 // GRAD1: also accumulate the forward's part of Rbar, sum_k 2 ebar_k Y^T Y (RhoDev::p1), which k_bwd_rho_mfma adds to its own sums; the
 // virtual-clip reverse sweep (round 5, k_bwd_wave per column: cmps_rho_wave.hip) forms all three rank-1 sums itself and runs without it
 template <bool SAVE, bool F16, bool GRAD1 = true>
-__global__ __launch_bounds__(64 * WAVES, 1) void k_fwd_rho_mfma(Dev P, RhoDev W, const float* __restrict__ audio,
+__global__ __launch_bounds__(64 * WAVES, 1) void k_fwd_rho_mfma(Dev Pk, RhoDev Wk, const float* __restrict__ audio,
                                                                 float* __restrict__ loss_out) {
+    const Dev P = bank_view(Pk, blockIdx.y);                               // the member's region (a plain launch: Pk and Wk themselves)
+    const RhoDev W = rho_bank_view(Wk, blockIdx.y * P.bank_stride);
+    audio += blockIdx.y * P.bank_audio;
+    loss_out += blockIdx.y * P.bank_loss;
     __shared__ __attribute__((aligned(16))) float Urow[WAVES][32 * RRLD];
     __shared__ __attribute__((aligned(16))) float Yrow[WAVES][32 * RRLD];
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -919,14 +923,15 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_sample_rho_mfma(Dev P, RhoDev
     }
 }
 
-hipError_t launch_fwd_rho_mfma(const Dev& P, const RhoDev& W, const float* audio, float* loss, bool save, bool f16, bool grad1, hipStream_t s) {
+hipError_t launch_fwd_rho_mfma(const Dev& P, const RhoDev& W, const float* audio, float* loss, bool save, bool f16, bool grad1, hipStream_t s,
+                               int M) {
     const unsigned nb = (unsigned)((P.B + WAVES - 1) / WAVES);
-    if (save && f16 && grad1) hipLaunchKernelGGL((k_fwd_rho_mfma<true, true, true>), dim3(nb), dim3(64 * WAVES), 0, s, P, W, audio, loss);
-    else if (save && f16) hipLaunchKernelGGL((k_fwd_rho_mfma<true, true, false>), dim3(nb), dim3(64 * WAVES), 0, s, P, W, audio, loss);
-    else if (save && grad1) hipLaunchKernelGGL((k_fwd_rho_mfma<true, false, true>), dim3(nb), dim3(64 * WAVES), 0, s, P, W, audio, loss);
-    else if (save) hipLaunchKernelGGL((k_fwd_rho_mfma<true, false, false>), dim3(nb), dim3(64 * WAVES), 0, s, P, W, audio, loss);
-    else if (f16) hipLaunchKernelGGL((k_fwd_rho_mfma<false, true>), dim3(nb), dim3(64 * WAVES), 0, s, P, W, audio, loss);
-    else hipLaunchKernelGGL((k_fwd_rho_mfma<false, false>), dim3(nb), dim3(64 * WAVES), 0, s, P, W, audio, loss);
+    if (save && f16 && grad1) hipLaunchKernelGGL((k_fwd_rho_mfma<true, true, true>), dim3(nb, M), dim3(64 * WAVES), 0, s, P, W, audio, loss);
+    else if (save && f16) hipLaunchKernelGGL((k_fwd_rho_mfma<true, true, false>), dim3(nb, M), dim3(64 * WAVES), 0, s, P, W, audio, loss);
+    else if (save && grad1) hipLaunchKernelGGL((k_fwd_rho_mfma<true, false, true>), dim3(nb, M), dim3(64 * WAVES), 0, s, P, W, audio, loss);
+    else if (save) hipLaunchKernelGGL((k_fwd_rho_mfma<true, false, false>), dim3(nb, M), dim3(64 * WAVES), 0, s, P, W, audio, loss);
+    else if (f16) hipLaunchKernelGGL((k_fwd_rho_mfma<false, true>), dim3(nb, M), dim3(64 * WAVES), 0, s, P, W, audio, loss);
+    else hipLaunchKernelGGL((k_fwd_rho_mfma<false, false>), dim3(nb, M), dim3(64 * WAVES), 0, s, P, W, audio, loss);
     return hipGetLastError();
 }
 

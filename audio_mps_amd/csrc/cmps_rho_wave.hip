@@ -31,8 +31,12 @@ __device__ __forceinline__ void bcast(unsigned wr, unsigned rd, float mine, v4f 
 
 // per-chunk scalar stash of the rho path: [B][NC][2][64] floats: tr rho'_k and e_k, one step per lane
 template <bool SAVE>
-__global__ __launch_bounds__(64 * WAVES, 1) void k_fwd_rho_wave(Dev P, RhoDev W, const float* __restrict__ audio,
+__global__ __launch_bounds__(64 * WAVES, 1) void k_fwd_rho_wave(Dev Pk, RhoDev Wk, const float* __restrict__ audio,
                                                                 float* __restrict__ loss_out) {
+    const Dev P = bank_view(Pk, blockIdx.y);                               // the member's region (a plain launch: Pk and Wk themselves)
+    const RhoDev W = rho_bank_view(Wk, blockIdx.y * P.bank_stride);
+    audio += blockIdx.y * P.bank_audio;
+    loss_out += blockIdx.y * P.bank_loss;
     __shared__ __attribute__((aligned(16))) float4 stR[WAVES][CH * 16];
     __shared__ __attribute__((aligned(16))) float2 bcU[WAVES][DPW];
     __shared__ float S[WAVES][RMAX][64];        // column states u_a (split layout)
@@ -254,12 +258,12 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_bwd_rho_wave(Dev P, RhoDev W,
     if (lane == 0) slab[4 * DD + 3 * DPW] = sumA - sumS / (A * A);
 }
 
-hipError_t launch_fwd_rho_wave(const Dev& P, const RhoDev& W, const float* audio, float* loss, bool save, hipStream_t s) {
+hipError_t launch_fwd_rho_wave(const Dev& P, const RhoDev& W, const float* audio, float* loss, bool save, hipStream_t s, int M) {
     const unsigned nb = (unsigned)((P.B + WAVES - 1) / WAVES);
     if (save)
-        hipLaunchKernelGGL(k_fwd_rho_wave<true>, dim3(nb), dim3(64 * WAVES), 0, s, P, W, audio, loss);
+        hipLaunchKernelGGL(k_fwd_rho_wave<true>, dim3(nb, M), dim3(64 * WAVES), 0, s, P, W, audio, loss);
     else
-        hipLaunchKernelGGL(k_fwd_rho_wave<false>, dim3(nb), dim3(64 * WAVES), 0, s, P, W, audio, loss);
+        hipLaunchKernelGGL(k_fwd_rho_wave<false>, dim3(nb, M), dim3(64 * WAVES), 0, s, P, W, audio, loss);
     return hipGetLastError();
 }
 
@@ -277,8 +281,11 @@ hipError_t launch_bwd_rho_wave(const Dev& P, const RhoDev& W, const float* audio
 // run in the CMPS_OPT_RANK1 arithmetic (fp16 x 2 by default).  k_bwd_rho_mfma (bf16 x 3, the same cost at every rank) stays behind
 // CMPS_VARIANT_WAVE32 ... it also needs the forward's part of Rbar (RhoDev::p1), which this path ignores: k_bwd_wave forms all three sums.
 // ------------------------------------------------------------------------------------------------
+// (a bank: member = blockIdx.y; its slabs lie `ws` bytes, its gradient sums `gstride` floats behind its predecessor's)
 __global__ void k_rho_phi_from_slabs(const float* __restrict__ slabs, size_t slab_floats, int B, int rank, int D, int DP,
-                                     float* __restrict__ grad_out) {
+                                     float* __restrict__ grad_out, size_t ws, size_t gstride) {
+    slabs = bank_shift(slabs, blockIdx.y * ws);
+    grad_out += blockIdx.y * gstride;
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     const int DD = DP * DP, G = 2 * D * D + 3 * D + 2;
     if (idx < 2 * D) grad_out[2 * D * D + D + idx] = 0.f;           // the pure-state layout's psi_0 entries: unused here (include/cmps.h)
@@ -295,7 +302,9 @@ __global__ void k_rho_phi_from_slabs(const float* __restrict__ slabs, size_t sla
 }
 
 hipError_t launch_bwd_rho_virtual_wave(const Dev& P, const RhoDev& W, const float* audio, const float* loss, float* grad_out, int rank1_mode,
-                                       int bwd_waves, hipStream_t s) {
+                                       int bwd_waves, hipStream_t s, int M) {
+    // (M > 1, cmps_rho_bank_loss_bwd: P carries the member strides, and every pointer below lies in member 0's region of the one
+    // workspace -- bank_view / bank_view_phi move them all by the one stride; the one-wave k_bwd_wave has no member dimension and is never asked for)
     Dev V = P;
     V.B = P.B * W.rank;
     V.hst = reinterpret_cast<float*>(W.stash);
@@ -311,19 +320,19 @@ hipError_t launch_bwd_rho_virtual_wave(const Dev& P, const RhoDev& W, const floa
     V.status = nullptr;
     hipError_t e;
     const bool two = bwd_waves == 2 && rank1_mode == 3 && P.f16_shift == 0;      // 3 = CMPS_RANK1_F16X2: as cmps_psi_loss_bwd chooses
-    { KScope ks(two ? "k_bwd_wave2w" : "k_bwd_wave", s); e = two ? launch_bwd_wave2w(V, audio, s) : launch_bwd_wave(V, audio, rank1_mode, s); }
+    { KScope ks(two ? "k_bwd_wave2w" : "k_bwd_wave", s); e = two ? launch_bwd_wave2w(V, audio, s, M) : launch_bwd_wave(V, audio, rank1_mode, s); }
     if (e != hipSuccess) return e;
     KScope ks("reduce + finalize", s);
-    e = launch_reduce_only(V, s);
+    e = launch_reduce_only(V, s, M);
     if (e != hipSuccess) return e;
     Dev F = V;
     F.B = P.B;                                                   // the loss sum runs over the real clips
     F.abar_fix = 1;
-    e = launch_finalize_only(F, loss, grad_out, s);
+    e = launch_finalize_only(F, loss, grad_out, s, M);
     if (e != hipSuccess) return e;
     const int n = W.rank * P.D > 2 * P.D ? W.rank * P.D : 2 * P.D;
-    hipLaunchKernelGGL(k_rho_phi_from_slabs, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const float*)W.wslabs, V.slab_floats, P.B,
-                       W.rank, P.D, P.DP, grad_out);
+    hipLaunchKernelGGL(k_rho_phi_from_slabs, dim3((unsigned)((n + 255) / 256), M), dim3(256), 0, s, (const float*)W.wslabs, V.slab_floats, P.B,
+                       W.rank, P.D, P.DP, grad_out, P.bank_stride, P.bank_grad);
     return hipGetLastError();
 }
 

@@ -95,7 +95,8 @@ __device__ __forceinline__ float wave_max(float x) {       // max over the 64 la
 // pre stage and serial tail take their short form (make_pre, chain_step); else (y, H y) rows (PsiCMPS on other settings, RhoCMPS).
 template <bool NORM = false>
 __global__ __launch_bounds__(128 * WAVES, 1) void k_bwd_wave2w(Dev Pk, const float* __restrict__ audio) {
-    const Dev P = bank_view(Pk, blockIdx.y);                               // the member's workspace (a plain launch: Pk itself)
+    // the member's workspace (a plain launch: Pk itself); the (y, H y) instance also serves RhoCMPS's virtual clips, whose columns move along
+    const Dev P = NORM ? bank_view(Pk, blockIdx.y) : bank_view_phi(Pk, blockIdx.y);
     audio += blockIdx.y * P.bank_audio;
     __shared__ __attribute__((aligned(16))) float4 stY[WAVES][CHB * 32];   // stashed (y, H y) rows of the staged chunk
     __shared__ __attribute__((aligned(16))) float4 stR[WAVES][CHB * 16];   // rho rows

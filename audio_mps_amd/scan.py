@@ -329,6 +329,93 @@ class HipScan:
         _capi.check(self._h, self._lib.cmps_bank_grad_status(self._h, codes, sticky, self._stream()))
         return [int(c) for c in codes], [int(x) for x in sticky]
 
+    # ------------------------------------------------------------------
+    # Model bank of RhoCMPS members (cmps_rho_bank_*): ONE workspace, every member's main layout (tables only) followed by its rho layout.
+    def rho_bank_workspace_bytes(self, rank: int, M: int, B: int, T: int, train: bool) -> int:
+        return int(self._lib.cmps_rho_bank_workspace_bytes(self.D, int(rank), int(M), B, T, self._ws_flags(train)))
+
+    def rho_bank_set_state_dev(self, params: torch.Tensor, phi: torch.Tensor, rank: int, sigma: float, delta_t: float, B: int, T: int,
+                               train: bool = True):
+        """cmps_rho_bank_set_state_dev: ``params`` [M, 2 D^2 + 3 D + 1] and ``phi`` [M, 2 rank D], the buffers rho_bank_apply_step wrote."""
+        rank = int(rank)
+        if not (params.is_cuda and params.dtype == torch.float32 and params.dim() == 2 and params.shape[1] == self._n_params + 1
+                and params.is_contiguous()):
+            raise ValueError("params must be a contiguous float32 CUDA tensor [M, 2 D^2 + 3 D + 1]")
+        M = int(params.shape[0])
+        if not (phi.is_cuda and phi.dtype == torch.float32 and tuple(phi.shape) == (M, 2 * rank * self.D) and phi.is_contiguous()):
+            raise ValueError("phi must be a contiguous float32 CUDA tensor [M, 2 rank D]")
+        key = ("rho_bank", M, rank, B, T, train)
+        if self._ws_key["main"] != key:
+            nbytes = self.rho_bank_workspace_bytes(rank, M, B, T, train)
+            if nbytes == 0:
+                raise ValueError(f"invalid shape for a RhoCMPS bank: D={self.D}, rank={rank}, M={M}, B={B}, T={T}")
+            self._ws["main"] = None
+            self._ws["main"] = torch.empty(nbytes + 256, dtype=torch.uint8, device=self.device)
+            self._ws_key["main"] = key
+            self._ws_fresh = True
+        ws = self._ws["main"]
+        flags = self._ws_flags(train, self._ws_fresh)
+        self._ws_fresh = False
+        _capi.check(self._h, self._lib.cmps_rho_bank_set_state_dev(
+            self._h, M, params.data_ptr(), phi.data_ptr(), rank, float(sigma), float(delta_t), int(T), int(B), flags,
+            (ws.data_ptr() + 255) // 256 * 256, ws.numel() - 256, self._stream()))
+        self._B, self._T, self._mode, self._bank_M, self._rho_bank_rank = B, T, "rho_bank", M, rank
+        self._rho_rank = 0            # (the plain rho state is gone: rho_forward() asks for rho_set_state again)
+
+    def _rho_bank_audio(self, audio: torch.Tensor):
+        M = getattr(self, "_bank_M", 0)
+        if self._mode != "rho_bank" or not M:
+            raise RuntimeError("rho_bank_forward() needs rho_bank_set_state_dev() first")
+        if not (isinstance(audio, torch.Tensor) and audio.is_cuda and audio.dtype == torch.float32 and audio.dim() in (2, 3)
+                and audio.is_contiguous()):
+            raise ValueError("audio must be a contiguous float32 CUDA tensor [B, T] (shared) or [M, B, T]")
+        n_audio = 1 if audio.dim() == 2 else int(audio.shape[0])
+        B, T = audio.shape[-2:]
+        if n_audio not in (1, M) or T != self._T or B > self._B:
+            raise ValueError(f"audio shape {tuple(audio.shape)} does not fit the bank (M={M}, B={self._B}, T={self._T})")
+        return M, n_audio, int(B), int(T)
+
+    def rho_bank_forward(self, audio: torch.Tensor, save_for_bwd: bool = False) -> torch.Tensor:
+        """cmps_rho_bank_loss_fwd: per-clip losses [M, B] for ``audio`` [B, T] (one batch shared by every member) or [M, B, T]."""
+        M, n_audio, B, T = self._rho_bank_audio(audio)
+        loss = torch.empty((M, B), dtype=torch.float32, device=self.device)
+        _capi.check(self._h, self._lib.cmps_rho_bank_loss_fwd(self._h, audio.data_ptr(), n_audio, B, T, loss.data_ptr(),
+                                                              1 if save_for_bwd else 0, self._stream()))
+        self._rho_bank_saved = (audio, loss, n_audio)    # (kept alive: the reverse pass reads both)
+        return loss
+
+    def rho_bank_backward(self) -> torch.Tensor:
+        """cmps_rho_bank_loss_bwd after rho_bank_forward(save_for_bwd=True): gradient sums [M, 2 D^2 + 3 D + 2 + 2 rank D]."""
+        saved = getattr(self, "_rho_bank_saved", None)
+        if saved is None or self._mode != "rho_bank":
+            raise RuntimeError("rho_bank_backward() needs rho_bank_forward(save_for_bwd=True) first")
+        audio, _, n_audio = saved
+        B, T = audio.shape[-2:]
+        grad = torch.empty((self._bank_M, grad_size(self.D, self._rho_bank_rank)), dtype=torch.float32, device=self.device)
+        _capi.check(self._h, self._lib.cmps_rho_bank_loss_bwd(self._h, audio.data_ptr(), n_audio, int(B), int(T), grad.data_ptr(),
+                                                              self._stream()))
+        return grad
+
+    def rho_bank_apply_step(self, vars_: torch.Tensor, m: torch.Tensor, v: torch.Tensor, grad_sums: Optional[torch.Tensor], rank: int,
+                            global_batch: int, bias_num: float, bias_den: float, beta1: float, beta2: float, eps: float,
+                            hyper: torch.Tensor, with_reg: bool, params: torch.Tensor, phi: torch.Tensor, losses: torch.Tensor):
+        """cmps_rho_bank_apply_step: every member's optimiser step; ``hyper`` [M, 5] float64 on the device as for bank_apply_step."""
+        M, rank = int(vars_.shape[0]), int(rank)
+        if not (hyper.is_cuda and hyper.dtype == torch.float64 and tuple(hyper.shape) == (M, 5) and hyper.is_contiguous()):
+            raise ValueError("hyper must be a contiguous float64 CUDA tensor [M, 5]")
+        if tuple(phi.shape) != (M, 2 * rank * self.D) or tuple(params.shape) != (M, self._n_params + 1):
+            raise ValueError("phi must be [M, 2 rank D] and params [M, 2 D^2 + 3 D + 1]")
+        scratch = getattr(self, "_rho_bank_scratch", None)
+        n = int(self._lib.cmps_rho_bank_apply_step_scratch_bytes(self.D, rank, M))
+        if n == 0:
+            raise ValueError(f"invalid shape for a RhoCMPS bank's optimiser step: D={self.D}, rank={rank}, M={M}")
+        if scratch is None or scratch.numel() * 8 < n:
+            scratch = self._rho_bank_scratch = torch.empty((n + 7) // 8, dtype=torch.float64, device=self.device)
+        _capi.check(self._h, self._lib.cmps_rho_bank_apply_step(
+            self._h, M, vars_.data_ptr(), m.data_ptr(), v.data_ptr(), grad_sums.data_ptr() if grad_sums is not None else None, rank,
+            float(max(global_batch, 1)), float(bias_num), float(bias_den), float(beta1), float(beta2), float(eps), hyper.data_ptr(),
+            1 if with_reg else 0, params.data_ptr(), phi.data_ptr(), losses.data_ptr(), scratch.data_ptr(), self._stream()))
+
     def _check_audio(self, audio: torch.Tensor):
         if not (isinstance(audio, torch.Tensor) and audio.is_cuda and audio.dtype == torch.float32
                 and audio.dim() == 2 and audio.is_contiguous()):

@@ -15,7 +15,7 @@ Run:  python -m audio_mps_amd.train --dataset=damped_sine --hparams=bond_dim=32,
 once and gathered from in the host pipeline's order, damped_sine is generated there.
 ``--eval_dataset NAME --eval_every N`` evaluates a held-out set every N steps and after the last one (Trainer.evaluate,
 audio_mps_amd/evaluate.py): a line on the console, a JSON line in {logdir}/eval.jsonl, and model.best.ckpt.npz when the mean improves.
-``--bank N`` and ``--bank_hparams "learning_rate=1e-3,3e-3;r_reg=0.1,1"`` train many PsiCMPS models at once (audio_mps_amd/bank.py): N seeds,
+``--bank N`` and ``--bank_hparams "learning_rate=1e-3,3e-3;r_reg=0.1,1"`` train many models of --mps_model at once (audio_mps_amd/bank.py): N seeds,
 the Cartesian grid, or every seed once per grid point; one kernel launch per stage serves all of them, every member sees the same batch,
 and the checkpoints are {logdir}/model.<m>.ckpt.npz (each loads in audio_mps_amd.sample / .evaluate) next to bank.json.
 """
@@ -324,7 +324,7 @@ def build_parser():
     p.add_argument("--eval_clips", type=int, default=256, help="clips of the synthetic held-out set (--eval_dataset damped_sine)")
     p.add_argument("--eval_minibatch", type=int, default=None, help="clips per evaluation batch (default: minibatch_size)")
     p.add_argument("--bank", type=int, default=0, metavar="N",
-                   help="train N PsiCMPS models at once, seeds --seed .. --seed + N - 1 (audio_mps_amd/bank.py); every member trains on the "
+                   help="train N models of --mps_model at once, seeds --seed .. --seed + N - 1 (audio_mps_amd/bank.py); every member trains on the "
                         "same batch")
     p.add_argument("--bank_hparams", default="", metavar="SPEC",
                    help="train the Cartesian grid of 'learning_rate=1e-3,3e-3;r_reg=0.1,1' (learning_rate, h_reg, r_reg) at once; with --bank "
@@ -459,10 +459,12 @@ def main(argv=None, backend=None):
 
 def bank_main(args, hp, backend, dp):
     """``--bank`` / ``--bank_hparams``: the loop of ``main`` for a BankTrainer.  One batch per step, shared by every member."""
-    from .bank import BankTrainer, PsiBank, bank_members
+    from .bank import RHO_BANK_ENTRIES, BankTrainer, PsiBank, RhoBank, bank_members
     from .data import get_audio
-    if args.mps_model != "psi_mps":
-        raise ValueError("--bank trains PsiCMPS models (--mps_model psi_mps)")
+    rho = args.mps_model == "rho_mps"                                                        # train.py:18-20, 50-53
+    if rho and backend is not None and not all(hasattr(backend, name) for name in RHO_BANK_ENTRIES):
+        raise ValueError("--bank --mps_model rho_mps needs a backend with the cmps_rho_bank_* entries (HipScan): this one "
+                         f"({type(backend).__name__}) has none, and a loop of plain RhoCMPS trainers is what --bank is there to replace")
     if args.bank < 0:
         raise ValueError("--bank must not be negative (0: one seed per point of --bank_hparams)")
     # what the loop below does not do is refused, not ignored
@@ -472,7 +474,7 @@ def bank_main(args, hp, backend, dp):
     if args.host_optimizer:
         raise ValueError("--bank runs the device-resident optimiser step of every member (cmps_bank_apply_step): no --host_optimizer")
     members = bank_members(args.seed, args.bank, args.bank_hparams)
-    trainer = BankTrainer(PsiBank(hp, members, backend=backend), dp)
+    trainer = BankTrainer((RhoBank if rho else PsiBank)(hp, members, backend=backend), dp)
     logdir = f"{args.logdir}/{args.dataset}/{hp.bond_dim}_{hp.delta_t}_{hp.minibatch_size}"    # train.py:94
     if trainer.restore(logdir):
         print(f"Restoring {len(trainer)} members from {logdir} (global_step {trainer.global_step})")

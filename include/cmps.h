@@ -609,6 +609,67 @@ int cmps_rho_apply_step(cmps_handle_t h, float* vars_dev, float* adam_m_dev, flo
                         void* scratch_dev, void* stream);
 
 /*
+ * ---- Model bank: M RhoCMPS models of one shape per kernel launch ----
+ * Replaces: the Python loop over models of a sweep with --mps_model rho_mps -- the reference offers psi_mps and rho_mps side by side
+ * (train.py:18-20, 50-53) at minibatch_size = 8, bond_dim = 8 (train.py:41), where one RhoCMPS model (model.py:55-203) occupies 8 of
+ * the 1024 SIMDs in its forward and is bound by its serial chain whatever the rank.  As for the PsiCMPS bank (cmps_bank_* above): D,
+ * rank, B, T, sigma, delta_t, Adam's betas and epsilon and with_reg are common to a bank; the variables, learning_rate, h_reg, r_reg
+ * (with c_r, c_h) and the data are free per member, and member m computes, bit for bit, what the plain cmps_rho_* entries compute for
+ * model m alone: the kernels are the plain ones with a second grid dimension.
+ *
+ * Scope: D <= 32 and 3 <= rank <= 32 under CMPS_VARIANT_AUTO or CMPS_VARIANT_WAVE with the default CMPS_OPT_RHO_BWD (VIRTUAL),
+ * CMPS_OPT_RANK1, CMPS_OPT_BWD_WAVES and CMPS_OPT_F16_SCALE_SHIFT -- the kernel set a plain handle picks there: k_fwd_rho_mfma (forward
+ * with save_for_bwd = 0 at rank <= 8: k_fwd_rho_wave), k_bwd_wave2w on B rank virtual clips, the slab reduction, k_finalize and
+ * k_rho_phi_from_slabs.  Out of scope and refused: rank <= 2, D > 32 and rank > 32 (the block and wide families), CMPS_VARIANT_BLOCK /
+ * WAVE32, k_bwd_rho_mfma (CMPS_OPT_RHO_BWD = GEMM) and every other non-default option.  There are no multi-rank banks, no bank samplers or
+ * streams (take a member out as a plain model) and no status words (RhoCMPS has none).
+ * Errors, all returned before the device is touched, every message starting with the entry's name: CMPS_ERR_UNSUPPORTED_D for D or rank
+ * outside the scope; CMPS_ERR_STATE for another variant or a non-default option (checked at the forward and the reverse call too);
+ * CMPS_ERR_BAD_ARG for null pointers, M outside [1, 1024], n_audio not in {1, M}, B < 1, T < 2, M B rank T beyond 2^31 - 1;
+ * CMPS_ERR_WORKSPACE for a null, unaligned (256 bytes) or too small workspace.  Every entry is asynchronous on `stream`, allocates
+ * nothing and touches nothing outside the stated extents.
+ *
+ * One workspace, one stride: a RhoCMPS bank does not take a main and a rho workspace but ONE, in which member m's region is the plain
+ * main layout (tables only: CMPS_WS_FWD_ONLY) followed by the plain rho layout, at byte m * (their sum).
+ * cmps_rho_bank_workspace_bytes = M * (cmps_workspace_bytes(D, B, T, CMPS_WS_FWD_ONLY) + cmps_rho_workspace_bytes(D, rank, B, T, flags));
+ * 0 for M outside [1, 1024], D or rank outside the scope, B < 1 or T < 2.
+ */
+size_t cmps_rho_bank_workspace_bytes(int D, int rank, int M, int B, int T, int flags);
+
+/*
+ * cmps_bank_set_params_dev plus cmps_rho_set_state for every member: params_dev [M][2 D^2 + 3 D + 1] and phi_dev [M][2 rank D] (phi_re
+ * [rank][D], then phi_im), the buffers cmps_rho_bank_apply_step writes.  flags: CMPS_WS_TRAIN for the rho part, CMPS_WS_REUSE_TABLES as
+ * in cmps_bank_set_params_dev.  Puts the handle into the rho-bank mode: every plain one-model entry and the PsiCMPS bank's
+ * cmps_bank_loss_fwd / _bwd / _grad_status return CMPS_ERR_STATE, and cmps_rho_bank_loss_* return CMPS_ERR_STATE in every other mode.
+ * A plain cmps_set_params* puts the handle back.
+ */
+int cmps_rho_bank_set_state_dev(cmps_handle_t h, int M, const float* params_dev, const float* phi_dev, int rank, double sigma, double delta_t,
+                                int T, int B_max, int flags, void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/*
+ * Mirror cmps_rho_loss_fwd / cmps_rho_loss_bwd.  audio_dev [n_audio][B][T] with n_audio = 1 (one batch shared by every member) or M;
+ * loss_dev [M][B]; grad_dev [M][2 D^2 + 3 D + 2 + 2 rank D] (the layout of cmps_rho_loss_bwd per member).  One saved-forward record
+ * for the whole bank: cmps_rho_bank_loss_bwd without a matching cmps_rho_bank_loss_fwd(save_for_bwd = 1) of the same audio, n_audio,
+ * B, T is CMPS_ERR_STATE.
+ */
+int cmps_rho_bank_loss_fwd(cmps_handle_t h, const float* audio_dev, int n_audio, int B, int T, float* loss_dev, int save_for_bwd, void* stream);
+int cmps_rho_bank_loss_bwd(cmps_handle_t h, const float* audio_dev, int n_audio, int B, int T, float* grad_dev, void* stream);
+
+/*
+ * Mirrors cmps_rho_apply_step, one workgroup per member (train.py:55-60, 88-89).  vars_dev, adam_m_dev, adam_v_dev
+ * [M][1 + 2 D^2 + D + 2 rank D]; params_dev [M][2 D^2 + 3 D + 1]; phi_dev [M][2 rank D]; grad_sums_dev [M][2 D^2 + 3 D + 2 + 2 rank D] or
+ * NULL (only params_dev and phi_dev are computed); losses_dev [M][2]; scratch_dev cmps_rho_bank_apply_step_scratch_bytes(D, rank, M) =
+ * M * cmps_rho_apply_step_scratch_bytes(D, rank) bytes (0 outside the scope), 8-byte aligned.  hyper_dev [M][5] doubles as in
+ * cmps_bank_apply_step; lr_t = (learning_rate * bias_num) / bias_den is formed in double on the device.  The skipped step (a non-finite
+ * gradient next to a finite loss) is per member.
+ */
+size_t cmps_rho_bank_apply_step_scratch_bytes(int D, int rank, int M);
+int cmps_rho_bank_apply_step(cmps_handle_t h, int M, float* vars_dev, float* adam_m_dev, float* adam_v_dev, const float* grad_sums_dev, int rank,
+                             double global_batch, double bias_num, double bias_den, double beta1, double beta2, double epsilon,
+                             const double* hyper_dev, int with_reg, float* params_dev, float* phi_dev, float* losses_dev, void* scratch_dev,
+                             void* stream);
+
+/*
  * The samplers' Gaussian noise, drawn on the device.  Replaces: tf.random_normal([length, n], stddev = sigma * sqrt(temp * delta_t)) inside
  * `sample` (model.py:246 / :88, 96, 106), for the noise_dev argument of cmps_psi_sample, _sample_primed, cmps_psi_stream, cmps_rho_sample,
  * _sample_primed and cmps_rho_stream -- same layout, row-major [path][step]:
