@@ -61,7 +61,7 @@ SYMBOLS = (
     "cmps_rho_update_ancilla", "cmps_rho_sample", "cmps_rho_sample_primed", "cmps_rho_stream_state_bytes", "cmps_rho_stream", "cmps_rho_stream_score", "cmps_rho_states",
     "cmps_rho_apply_step_scratch_bytes", "cmps_rho_apply_step", "cmps_noise_fill", "cmps_batch_gather", "cmps_batch_gather_i16", "cmps_loss_stats", "cmps_damped_sine_fill", "cmps_crc32c",
     "cmps_bank_workspace_bytes", "cmps_bank_set_params_dev", "cmps_bank_loss_fwd", "cmps_bank_loss_bwd", "cmps_bank_apply_step_scratch_bytes",
-    "cmps_bank_apply_step", "cmps_bank_grad_status",
+    "cmps_bank_apply_step", "cmps_bank_grad_status", "cmps_bank_stream_state_bytes", "cmps_bank_stream", "cmps_bank_stream_score",
     "cmps_rho_bank_workspace_bytes", "cmps_rho_bank_set_state_dev", "cmps_rho_bank_loss_fwd", "cmps_rho_bank_loss_bwd",
     "cmps_rho_bank_apply_step_scratch_bytes", "cmps_rho_bank_apply_step",
 )
@@ -192,6 +192,12 @@ def _declare(lib):
     lib.cmps_bank_apply_step.restype = c_int
     lib.cmps_bank_grad_status.argtypes = [vp, ctypes.POINTER(c_int), ctypes.POINTER(c_int), vp]
     lib.cmps_bank_grad_status.restype = c_int
+    lib.cmps_bank_stream_state_bytes.argtypes = [vp, c_int]
+    lib.cmps_bank_stream_state_bytes.restype = c_size_t
+    lib.cmps_bank_stream.argtypes = [vp, vp, vp, c_int, vp, c_int, c_int, vp, c_int, c_int, c_int, vp, vp, vp]
+    lib.cmps_bank_stream.restype = c_int
+    lib.cmps_bank_stream_score.argtypes = [vp, vp, vp, c_int, vp, c_int, c_int, c_int, vp, vp, vp, vp]
+    lib.cmps_bank_stream_score.restype = c_int
     lib.cmps_rho_bank_workspace_bytes.argtypes = [c_int, c_int, c_int, c_int, c_int, c_int]
     lib.cmps_rho_bank_workspace_bytes.restype = c_size_t
     lib.cmps_rho_bank_set_state_dev.argtypes = [vp, c_int, vp, vp, c_int, c_double, c_double, c_int, c_int, c_int, vp, c_size_t, vp]

@@ -10,7 +10,9 @@
                      model m alone.  On a backend without the bank entries the trainer loops over plain steps of its members.
 
 Common to a bank: bond_dim, minibatch_size, sigma, delta_t, A, Adam's betas and epsilon.  Free per member: seed, learning_rate, h_reg, r_reg
-and the data.  A member is sampled, scored, evaluated or saved on its own by taking it out as an ordinary model: ``BankTrainer.member(m)``.
+and the data.  Every member is sampled, followed and scored at once through ``PsiBank.open_stream`` (a BankStream: cmps_bank_stream*),
+``PsiBank.sample``, ``nll_per_step`` and ``classify``; for everything else a member is taken out as an ordinary model:
+``BankTrainer.member(m)``.
 """
 from __future__ import annotations
 
@@ -65,6 +67,61 @@ class PsiBank:
     def bond_d(self) -> int:
         return int(self.hparams.bond_dim)
 
+    # -- every member at once: stream, sample, score (cmps_bank_stream*) ---------------------------------
+    def stream_backend(self):
+        """A new backend of the bank's kind, D and variant: what a stream of the bank runs on."""
+        be = self.backend
+        if type(be).__name__ == "HipScan":
+            return type(be)(self.bond_d, device=be.device, variant=be.variant)
+        return type(be)(self.bond_d)
+
+    def open_stream(self, num_paths, max_steps, temp=1, seed=None, device_noise=False, independent_noise=False):
+        """``PsiCMPS.open_stream`` for every member at once: a BankStream (audio_mps_amd/stream.py) of ``num_paths`` paths per member.
+        It runs on a backend of its own, so it never disturbs a trainer's workspace on the bank's shared one, and keeps the parameters
+        the members have now.  By default member m, path b hears the noise ``models[m].open_stream(num_paths, ..., seed=seed)`` would
+        give path b; ``independent_noise=True`` numbers the paths globally (g = m num_paths + b)."""
+        from .stream import BankStream
+        return BankStream(self, num_paths, max_steps, temp=temp, seed=seed, device_noise=device_noise, independent_noise=independent_noise)
+
+    def sample(self, n, length, temp=1, seed=None, prime=None, device_noise=False) -> np.ndarray:
+        """``PsiCMPS.sample`` of every member, [M, n, length] in the reference's convention (A * running sum of the sampled increments,
+        zero at the hand-over behind a ``prime`` [T'], [1, T'] or [n, T']).  Every member hears the same noise."""
+        steps = 0 if prime is None else PsiCMPS._prime(prime, n).shape[1] - 1
+        st = self.open_stream(n, steps + int(length), temp=temp, seed=seed, device_noise=device_noise)
+        if prime is not None:
+            st.follow(PsiCMPS._prime(prime, n))
+        st.generate(length)
+        return st._raw
+
+    def nll_per_step(self, clips, segment=None) -> np.ndarray:
+        """``PsiCMPS.nll_per_step`` under every member, [M, B, T - 1]: one scored bank stream over ``clips`` [B, T], in segments of
+        ``segment`` steps when given (the cut changes no bit)."""
+        return self._scored(clips, segment)[0]
+
+    def classify(self, clips):
+        """M per-class generative models are a classifier: (best [B], total_nll [M, B]) -- the member under which each clip of ``clips``
+        [B, T] is the most likely, and every member's loss of every clip."""
+        _, st = self._scored(clips, None)
+        return st.best(), st.total_nll
+
+    def _scored(self, clips, segment):
+        if hasattr(clips, "detach"):
+            clips = clips.detach().cpu().numpy()
+        clips = np.asarray(clips, dtype=np.float32)
+        if clips.ndim == 1:
+            clips = clips[None, :]
+        if clips.ndim != 2 or clips.shape[1] < 2:
+            raise ValueError("clips must be [B, T] with T >= 2")
+        B, N = clips.shape[0], clips.shape[1] - 1
+        S = N if segment is None else int(segment)
+        if S < 1:
+            raise ValueError("segment must be positive")
+        st = self.open_stream(B, N)
+        parts = [st.score(clips[:, :S + 1])]                          # the anchor and S steps
+        for a in range(S + 1, N + 1, S):
+            parts.append(st.score(clips[:, a:a + S]))
+        return np.concatenate(parts, axis=-1), st
+
 
 class RhoBank(PsiBank):
     """``models[m]`` is RhoCMPS(hparams_m, seed=seed_m); ``hparams.initial_rank`` (None: bond_dim) is common to the bank."""
@@ -74,6 +131,10 @@ class RhoBank(PsiBank):
     def __init__(self, hparams: HParams, members: Sequence[dict], backend=None):
         super().__init__(hparams, members, backend)
         self.rank = int(self.models[0].rank_rho_0)
+
+    def open_stream(self, *args, **kwargs):
+        raise ValueError("open_stream: a bank's streams (sample, nll_per_step, classify) are built for PsiCMPS banks only; take a RhoCMPS "
+                         "member out with BankTrainer.member(m) and stream it alone")
 
 
 RHO_BANK_ENTRIES = ("rho_bank_set_state_dev", "rho_bank_forward", "rho_bank_backward", "rho_bank_apply_step")
@@ -239,6 +300,11 @@ class BankTrainer:
         model (its scans reconfigure the shared backend; the next bank step configures it again)."""
         self.sync_to_host()
         return self.trainers[m].model
+
+    def open_stream(self, num_paths, max_steps, temp=1, seed=None, device_noise=False, independent_noise=False):
+        """``PsiBank.open_stream`` on the members' current variables: the device-resident state comes back first."""
+        self.sync_to_host()
+        return self.bank.open_stream(num_paths, max_steps, temp=temp, seed=seed, device_noise=device_noise, independent_noise=independent_noise)
 
     # -- held-out evaluation ------------------------------------------------------------------------------
     def evaluate(self, dataset, minibatch_size: Optional[int] = None, T: Optional[int] = None, keep_losses: bool = False):

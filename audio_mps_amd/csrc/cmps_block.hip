@@ -398,17 +398,28 @@ __global__ void k_states(Dev P, float* __restrict__ psi_out) {
 // k_fwd_block above; lv is added to the running loss (SC.loss[b]: read on a resumed scan, written behind the last step) and stored to
 // SC.nll[b][k] when set.  u and the running sum are untouched.  The other instances are the kernels they were
 // (profiles/stream_score_isa_identity.log).
-template <int NT, bool PRIMED, bool STREAM = false, bool SCORE = false>
-__global__ __launch_bounds__(NT) void k_sample_block(Dev P, const float* __restrict__ noise, int length, float* __restrict__ out,
+// BANK (cmps_bank_stream, cmps_bank_stream_score): member m = blockIdx.y of a bank runs the STREAM / SCORE instance on its own tables, as
+// in k_sample_wave (cmps_wave.hip): what a path writes or carries is indexed by the global path g = m gridDim.x + b, the audio and the
+// noise by the path b behind the member's MB.audio / MB.noise floats (0: shared).  The plain instances ignore MB and are the kernels they
+// were (profiles/bank_stream_isa_identity.log).
+template <int NT, bool PRIMED, bool STREAM = false, bool SCORE = false, bool BANK = false>
+__global__ __launch_bounds__(NT) void k_sample_block(Dev Pk, const float* __restrict__ noise, int length, float* __restrict__ out,
                                                      const float* __restrict__ prime, int prime_stride, int PF, float* __restrict__ pred,
-                                                     StreamDev ST, ScoreDev SC) {
+                                                     StreamDev ST, ScoreDev SC, MemberDev MB) {
     static_assert(PRIMED || !STREAM, "a stream segment is a primed scan");
     static_assert(STREAM || !SCORE, "a scored segment is a stream segment");
+    static_assert(STREAM || !BANK, "a bank launch is a stream segment");
+    const Dev P = member_view<BANK>(Pk);                 // the member's workspace (a plain instance: Pk itself)
     extern __shared__ float2 sh[];
     const int D = P.D, DP = P.DP;
     float2* su = sh;
     float* red = reinterpret_cast<float*>(sh + (SCORE ? 2 * D : D));   // (SCORE: y_k sits at sh + D)
     const int b = blockIdx.x, t = threadIdx.x;
+    const size_t g = member_path<BANK>((int)gridDim.x, b);                        // the path among all members' (a plain instance: b)
+    if constexpr (BANK) {
+        noise += blockIdx.y * MB.noise;
+        prime += blockIdx.y * MB.audio;
+    }
     const bool act = t < D;
     float2 u = act ? P.psi0[t] : make_float2(0.f, 0.f);
     float samp = 0.f;
@@ -416,14 +427,14 @@ __global__ __launch_bounds__(NT) void k_sample_block(Dev P, const float* __restr
     const float* prow = PRIMED ? prime + (size_t)b * prime_stride : nullptr;      // (prime_stride 0: one clip shared by all paths)
     if constexpr (STREAM) {
         if (ST.in) {
-            const float* rec = ST.in + (size_t)b * ST.rec;
+            const float* rec = ST.in + g * ST.rec;
             if (act) u = make_float2(rec[2 * t], rec[2 * t + 1]);
             samp = rec[2 * D];
         }
     }
     [[maybe_unused]] float loss = 0.f;                                            // SCORE: the path's running loss (model.py:279)
     if constexpr (SCORE) {
-        if (ST.in) loss = SC.loss[b];
+        if (ST.in) loss = SC.loss[g];
     }
     for (int k = 0; k < nsteps; ++k) {
         if (act) su[t] = u;
@@ -469,12 +480,12 @@ __global__ __launch_bounds__(NT) void k_sample_block(Dev P, const float* __restr
             const float z = (e2 * xs) / dev_A(P);                                          // :294
             const float lv = -logf(1.0f + z);
             loss += lv;                                                                    // :279
-            if (t == 0 && SC.nll) SC.nll[(size_t)b * PF + k] = lv;
+            if (t == 0 && SC.nll) SC.nll[g * PF + k] = lv;
         }
         if constexpr (PRIMED) {
             if (t == 0) {
-                if (!forced) out[(size_t)b * length + (k - PF)] = dev_A(P) * samp;
-                else if (pred) pred[(size_t)b * PF + k] = e * P.dt;
+                if (!forced) out[g * length + (k - PF)] = dev_A(P) * samp;
+                else if (pred) pred[g * PF + k] = e * P.dt;
             }
         } else {
             if (t == 0) out[(size_t)b * length + k] = dev_A(P) * samp;                          // :251
@@ -482,11 +493,11 @@ __global__ __launch_bounds__(NT) void k_sample_block(Dev P, const float* __restr
         __syncthreads();
     }
     if constexpr (SCORE) {
-        if (t == 0) SC.loss[b] = loss;
+        if (t == 0) SC.loss[g] = loss;
     }
     if constexpr (STREAM) {
         if (ST.out) {
-            float* rec = ST.out + (size_t)b * ST.rec;
+            float* rec = ST.out + g * ST.rec;
             if (act) { rec[2 * t] = u.x; rec[2 * t + 1] = u.y; }
             if (t == 0) rec[2 * D] = samp;
         }
@@ -553,9 +564,13 @@ hipError_t launch_sample_block(const Dev& P, const SampleDev& S, hipStream_t s) 
         return dispatch_sample_mode(sample_mode(S), [&](auto mode) {
             constexpr int NT = decltype(nt)::value, M = decltype(mode)::value;
             const size_t shm = (size_t)(M == SAMPLE_SCORE ? 2 : 1) * P.D * sizeof(float2) + 64;      // (SCORE: y_k behind u)
-            hipLaunchKernelGGL((k_sample_block<NT, M >= SAMPLE_PRIMED, M >= SAMPLE_STREAM, M == SAMPLE_SCORE>), dim3(S.n), dim3(NT), shm, s, P, S.noise,
-                               S.length, S.out, S.PR.prime, S.PR.stride, S.PR.PF, S.PR.pred, stream_of(S), score_of(S));
-            return hipGetLastError();
+            return dispatch_bool(S.MB.M > 0, [&](auto bank) {
+                constexpr bool BANK = decltype(bank)::value && M >= SAMPLE_STREAM;   // (cmps_bank_stream*: stream segments only)
+                hipLaunchKernelGGL((k_sample_block<NT, M >= SAMPLE_PRIMED, M >= SAMPLE_STREAM, M == SAMPLE_SCORE, BANK>), dim3(S.n, BANK ? S.MB.M : 1),
+                                   dim3(NT), shm, s, P, S.noise, S.length, S.out, S.PR.prime, S.PR.stride, S.PR.PF, S.PR.pred, stream_of(S),
+                                   score_of(S), S.MB);
+                return hipGetLastError();
+            });
         });
     });
 }

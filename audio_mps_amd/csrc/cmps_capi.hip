@@ -862,6 +862,82 @@ int cmps_psi_stream_score(cmps_handle_t h, const void* state_in_dev, void* state
     return psi_sample_launch(h, "cmps_psi_stream_score", SampleDev{nullptr, n, 0, nullptr, PR, &ST, &SC}, stream);   // (every step is forced)
 }
 
+// ---- a bank's streams: the STREAM / SCORE instances with the members as a second grid dimension (include/cmps.h) ----
+// What cmps_bank_stream and cmps_bank_stream_score refuse before they look at their arguments
+static int bank_stream_check_mode(cmps_handle_t h, const char* who) {
+    if (!h->params_set || h->legacy || h->bank_M < 1 || h->bank_rho)
+        return fail(h, CMPS_ERR_STATE, std::string(who) + ": needs a PsiCMPS bank (call cmps_bank_set_params_dev first)");
+    if (const int rc = bank_check_mode(h, who, true)) return rc;
+    if (sampler_family(h) == SAMPLER_WIDE)               // (a variant set behind cmps_bank_set_params_dev)
+        return fail(h, CMPS_ERR_STATE, std::string(who) + ": a bank samples with the wave and block kernels only");
+    return CMPS_OK;
+}
+// rows of an array a bank's members may share: `choices` names the allowed counts in the caller's terms
+static int bank_check_rows(cmps_handle_t h, const char* who, const char* name, const char* choices, long long rows, bool shared_ok, int n) {
+    const long long Mn = (long long)h->bank_M * n;
+    if ((shared_ok && rows == 1) || rows == n || rows == Mn) return CMPS_OK;
+    return fail(h, CMPS_ERR_BAD_ARG, std::string(who) + ": " + name + " must be " + choices);
+}
+// M n (forced + length): every index into the caller's arrays fits 31 bits (n >= 1, forced + length >= 1 checked)
+static int bank_check_extent(cmps_handle_t h, const char* who, int n, long long steps) {
+    if ((unsigned long long)h->bank_M * (unsigned long long)n * (unsigned long long)steps <= 0x7fffffffull) return CMPS_OK;
+    return fail(h, CMPS_ERR_BAD_ARG, std::string(who) + ": M * n * (forced + length) exceeds 2^31 - 1");
+}
+// floats between two members' rows of an array with `rows` rows of `row` floats (1 or n rows: shared, 0)
+static size_t bank_member_stride(const cmps_handle_s* h, long long rows, int n, size_t row) {
+    return (h->bank_M > 1 && rows == (long long)h->bank_M * n) ? (size_t)n * row : 0;
+}
+
+size_t cmps_bank_stream_state_bytes(cmps_handle_t h, int n) {
+    if (!h || n < 1 || !h->params_set || h->legacy || h->bank_M < 1 || h->bank_rho) return 0;
+    return (size_t)h->bank_M * (size_t)n * stream_rec_floats(h) * sizeof(float);
+}
+
+int cmps_bank_stream(cmps_handle_t h, const void* state_in_dev, void* state_out_dev, int k0, const float* audio_dev, int n_audio, int forced,
+                     const float* noise_dev, int n_noise, int length, int n, float* out_dev, float* pred_dev, void* stream) {
+    const char* who = "cmps_bank_stream";
+    if (!h) return CMPS_ERR_BAD_ARG;
+    if (const int rc = bank_stream_check_mode(h, who)) return rc;
+    const std::string w(who);
+    if (n < 1 || forced < 0 || length < 0 || (long long)forced + length < 1 || k0 < 0)
+        return fail(h, CMPS_ERR_BAD_ARG, w + ": need n >= 1, forced >= 0, length >= 0, forced + length >= 1 and k0 >= 0");
+    if (int c = stream_check_state(h, who, state_in_dev, k0)) return c;
+    if (forced > 0 && !audio_dev) return fail(h, CMPS_ERR_BAD_ARG, w + ": forced > 0 needs audio_dev");
+    if (length > 0 && (!noise_dev || !out_dev)) return fail(h, CMPS_ERR_BAD_ARG, w + ": length > 0 needs noise_dev and out_dev");
+    if (int c = bank_check_rows(h, who, "n_audio", "1 (one signal for every path of every member), n (shared by the members) or M * n", n_audio, true, n))
+        return c;
+    if (length > 0)
+        if (int c = bank_check_rows(h, who, "n_noise", "n (every member hears the same noise) or M * n", n_noise, false, n)) return c;
+    if (int c = bank_check_extent(h, who, n, (long long)forced + length)) return c;
+    if (int c = sample_check_rows(h, who, "k0 + forced + length + 1", (long long)k0 + forced + length)) return c;
+    const StreamDev ST{static_cast<const float*>(state_in_dev), static_cast<float*>(state_out_dev), k0, stream_rec_floats(h)};
+    SampleDev S{noise_dev, n, length, out_dev, PrimeDev{audio_dev, n_audio == 1 ? 0 : forced + 1, forced, pred_dev}, &ST, nullptr};
+    S.MB = MemberDev{h->bank_M, audio_dev ? bank_member_stride(h, n_audio, n, (size_t)forced + 1) : 0,
+                     length > 0 ? bank_member_stride(h, n_noise, n, (size_t)length) : 0};
+    return psi_sample_launch(h, who, S, stream);
+}
+
+int cmps_bank_stream_score(cmps_handle_t h, const void* state_in_dev, void* state_out_dev, int k0, const float* audio_dev, int n_audio, int forced,
+                           int n, float* nll_dev, float* loss_dev, float* pred_dev, void* stream) {
+    const char* who = "cmps_bank_stream_score";
+    if (!h) return CMPS_ERR_BAD_ARG;
+    if (const int rc = bank_stream_check_mode(h, who)) return rc;
+    const std::string w(who);
+    if (n < 1 || forced < 1 || k0 < 0) return fail(h, CMPS_ERR_BAD_ARG, w + ": need n >= 1, forced >= 1 and k0 >= 0");
+    if (int c = stream_check_state(h, who, state_in_dev, k0)) return c;
+    if (!audio_dev) return fail(h, CMPS_ERR_BAD_ARG, w + ": needs audio_dev");
+    if (!loss_dev) return fail(h, CMPS_ERR_BAD_ARG, w + ": needs loss_dev (the running loss per member and path)");
+    if (int c = bank_check_rows(h, who, "n_audio", "1 (one signal for every path of every member), n (shared by the members) or M * n", n_audio, true, n))
+        return c;
+    if (int c = bank_check_extent(h, who, n, forced)) return c;
+    if (int c = sample_check_rows(h, who, "k0 + forced + 1", (long long)k0 + forced)) return c;
+    const StreamDev ST{static_cast<const float*>(state_in_dev), static_cast<float*>(state_out_dev), k0, stream_rec_floats(h)};
+    const ScoreDev SC{nll_dev, loss_dev};
+    SampleDev S{nullptr, n, 0, nullptr, PrimeDev{audio_dev, n_audio == 1 ? 0 : forced + 1, forced, pred_dev}, &ST, &SC};   // (every step is forced)
+    S.MB = MemberDev{h->bank_M, bank_member_stride(h, n_audio, n, (size_t)forced + 1), 0};
+    return psi_sample_launch(h, who, S, stream);
+}
+
 // The samplers' noise drawn on the device: needs nothing of the handle but its error string and its kernel-event record
 int cmps_noise_fill(cmps_handle_t h, unsigned long long seed, unsigned long long first_step, unsigned first_path, int n, int length,
                     float stddev, float* noise_dev, void* stream) {

@@ -398,6 +398,13 @@ struct ScoreDev {
     float* nll;       // every step's loss increment [path][step], or null
     float* loss;      // the running loss per path: read when the segment resumes a scan (StreamDev::in set), written behind the last step
 };
+// MB (cmps_bank_stream*): the launch runs M members of a bank, member m = blockIdx.y on bank_view(P, m), n paths each.  What a path writes
+// or carries (out, pred, nll, the running loss, the state records) is one array over the global paths g = m n + b; the audio and the noise
+// of member m lie `audio` / `noise` floats behind member m - 1's (0: every member reads the same rows).  M = 0: a plain launch.
+struct MemberDev {
+    int M = 0;
+    size_t audio = 0, noise = 0;
+};
 struct SampleDev {
     const float* noise;     // [n][length]
     int n, length;
@@ -405,7 +412,20 @@ struct SampleDev {
     PrimeDev PR;
     const StreamDev* ST;    // null: not a stream segment
     const ScoreDev* SC;     // null: not scored
+    MemberDev MB{};         // M == 0: not a bank's launch
 };
+// What the BANK instances of the sampler kernels take at entry: the member's Dev and the global number of path b of n (the plain instances:
+// the Dev and the path as they were handed in, no code)
+template <bool BANK>
+__device__ __forceinline__ Dev member_view(const Dev& P) {
+    if constexpr (BANK) return bank_view(P, blockIdx.y);
+    else return P;
+}
+template <bool BANK>
+__device__ __forceinline__ size_t member_path(int n, int b) {
+    if constexpr (BANK) return (size_t)blockIdx.y * (size_t)n + (size_t)b;
+    else return (size_t)b;
+}
 inline StreamDev stream_of(const SampleDev& S) { return S.ST ? *S.ST : StreamDev{}; }
 inline ScoreDev score_of(const SampleDev& S) { return S.SC ? *S.SC : ScoreDev{}; }
 // The mode of a launch, stated once (ST first: a stream segment with forced == 0 has PR.prime == nullptr and is still SAMPLE_STREAM).  A

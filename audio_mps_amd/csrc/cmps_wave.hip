@@ -674,12 +674,20 @@ __device__ __forceinline__ void mv2r_hi(const v2f (&MA)[16], const v2f (&MB)[16]
 // or the running sum: they keep the stream instance's bits.  The running loss comes from SC.loss[b] on a resumed scan (else 0) and goes
 // back to it behind the last step; lv goes to SC.nll[b][k] when set.  The other instances are the kernels they were
 // (profiles/stream_score_isa_identity.log).
-template <bool PRIMED, bool STREAM = false, bool SCORE = false>
-__global__ __launch_bounds__(64 * WAVES, 1) void k_sample_wave(Dev P, const float* __restrict__ noise, int n_paths, int length,
+// BANK (cmps_bank_stream, cmps_bank_stream_score): member m = blockIdx.y of a bank runs the STREAM / SCORE instance on its own tables.  The
+// member takes its Dev once at entry; behind it only the rows of the caller's arrays differ: everything a path writes or carries (out, pred,
+// nll, the running loss, the state records) is indexed by the global path g = m n_paths + b, the audio and the noise by the path b behind
+// the member's MB.audio / MB.noise floats (0: shared by every member).  The last workgroup's idle waves return per member.  The plain
+// instances ignore MB and are the kernels they were (profiles/bank_stream_isa_identity.log).
+template <bool PRIMED, bool STREAM = false, bool SCORE = false, bool BANK = false>
+__global__ __launch_bounds__(64 * WAVES, 1) void k_sample_wave(Dev Pk, const float* __restrict__ noise, int n_paths, int length,
                                                                float* __restrict__ out, const float* __restrict__ prime,
-                                                               int prime_stride, int PF, float* __restrict__ pred, StreamDev ST, ScoreDev SC) {
+                                                               int prime_stride, int PF, float* __restrict__ pred, StreamDev ST, ScoreDev SC,
+                                                               MemberDev MB) {
     static_assert(PRIMED || !STREAM, "a stream segment is a primed scan");
     static_assert(STREAM || !SCORE, "a scored segment is a stream segment");
+    static_assert(STREAM || !BANK, "a bank launch is a stream segment");
+    const Dev P = member_view<BANK>(Pk);                 // the member's workspace (a plain instance: Pk itself)
     __shared__ __attribute__((aligned(16))) float4 stR[WAVES][CH * 16];
     __shared__ __attribute__((aligned(16))) float2 bcU[WAVES][DPW];
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -687,6 +695,11 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_sample_wave(Dev P, const floa
     const bool hb = h != 0;
     const int b = blockIdx.x * WAVES + w;
     if (b >= n_paths) return;
+    const size_t g = member_path<BANK>(n_paths, b);      // the path among all members' (a plain instance: b)
+    if constexpr (BANK) {
+        noise += blockIdx.y * MB.noise;
+        prime += blockIdx.y * MB.audio;
+    }
     const int N = PRIMED ? PF + length : length, NC = (N + CH - 1) / CH;
     v2f MR[16], MQ[16];
 #pragma unroll
@@ -698,9 +711,9 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_sample_wave(Dev P, const floa
     const unsigned aRho = lds_addr(&stR[w][0]) + i * 8;
     const float4* rho4 = reinterpret_cast<const float4*>(P.rho);
     const float* nrow = noise + (size_t)b * length;
-    float* orow = out + (size_t)b * length;
+    float* orow = out + g * length;
     const float* prow = PRIMED ? prime + (size_t)b * prime_stride : nullptr;      // (prime_stride 0: one clip shared by all paths)
-    float* drow = PRIMED && pred ? pred + (size_t)b * PF : nullptr;
+    float* drow = PRIMED && pred ? pred + g * PF : nullptr;
     const float A = dev_A(P), dt = P.dt;
     const float2 p0 = P.psi0[i];
     float u = hb ? p0.y : p0.x;
@@ -708,7 +721,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_sample_wave(Dev P, const floa
     float samp = 0.f;                                    // model.py:244 batch_zeros
     if constexpr (STREAM) {
         if (ST.in) {                                     // resume: the values the loop below left behind the previous segment's last step
-            const float* rec = ST.in + (size_t)b * ST.rec;
+            const float* rec = ST.in + g * ST.rec;
             u = rec[lane];
             xsq = rec[64 + lane];
             samp = rec[128];
@@ -717,8 +730,8 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_sample_wave(Dev P, const floa
     [[maybe_unused]] float loss = 0.f;                   // SCORE: the path's running loss (model.py:279)
     [[maybe_unused]] float* lrow = nullptr;
     if constexpr (SCORE) {
-        if (ST.in) loss = SC.loss[b];
-        if (SC.nll) lrow = SC.nll + (size_t)b * PF;
+        if (ST.in) loss = SC.loss[g];
+        if (SC.nll) lrow = SC.nll + g * PF;
     }
     v4f sr[16], qu[8];
     v2f rho;
@@ -791,11 +804,11 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_sample_wave(Dev P, const floa
         }
     }
     if constexpr (SCORE) {
-        if (lane == 0) SC.loss[b] = loss;
+        if (lane == 0) SC.loss[g] = loss;
     }
     if constexpr (STREAM) {
         if (ST.out) {
-            float* rec = ST.out + (size_t)b * ST.rec;
+            float* rec = ST.out + g * ST.rec;
             rec[lane] = u;
             rec[64 + lane] = xsq;
             if (lane == 0) rec[128] = samp;
@@ -807,9 +820,13 @@ hipError_t launch_sample_wave(const Dev& P, const SampleDev& S, hipStream_t s) {
     const unsigned nb = (unsigned)((S.n + WAVES - 1) / WAVES);
     return dispatch_sample_mode(sample_mode(S), [&](auto mode) {
         constexpr int M = decltype(mode)::value;
-        hipLaunchKernelGGL((k_sample_wave<M >= SAMPLE_PRIMED, M >= SAMPLE_STREAM, M == SAMPLE_SCORE>), dim3(nb), dim3(64 * WAVES), 0, s, P, S.noise, S.n,
-                           S.length, S.out, S.PR.prime, S.PR.stride, S.PR.PF, S.PR.pred, stream_of(S), score_of(S));
-        return hipGetLastError();
+        return dispatch_bool(S.MB.M > 0, [&](auto bank) {
+            constexpr bool BANK = decltype(bank)::value && M >= SAMPLE_STREAM;       // (cmps_bank_stream*: stream segments only)
+            hipLaunchKernelGGL((k_sample_wave<M >= SAMPLE_PRIMED, M >= SAMPLE_STREAM, M == SAMPLE_SCORE, BANK>), dim3(nb, BANK ? S.MB.M : 1),
+                               dim3(64 * WAVES), 0, s, P, S.noise, S.n, S.length, S.out, S.PR.prime, S.PR.stride, S.PR.PF, S.PR.pred, stream_of(S),
+                               score_of(S), S.MB);
+            return hipGetLastError();
+        });
     });
 }
 

@@ -17,6 +17,10 @@ normals of (--seed, path, step), so --segment then changes no bit of the wavefor
 (SampleStream.score; cmps_psi_stream_score / cmps_rho_stream_score), in segments of --segment steps when given.  Writes ``nll.npy`` (float32
 [clips, T' - 1]: the negative log-likelihood of every sample, model.py:293-294 / :166, 169-170) and ``pred.npy`` (the model's expected increments) into --out_dir and prints
 the total and the mean per sample; returns the nll array.
+``--bankdir DIR`` (a directory BankTrainer.save wrote: bank.json + model.<m>.ckpt.npz, PsiCMPS members) does the same with every member
+of the bank at once (PsiBank.open_stream; cmps_bank_stream / cmps_bank_stream_score), every member hearing the same noise: sampling writes
+``sample_m<m>_<i>.wav`` and ``samples.npy`` [M, num_samples, samples]; --prime continues one clip with every member; --score writes
+``nll.npy`` ([M, T' - 1] for one clip, else [M, clips, T' - 1]) and ``pred.npy`` and prints one line per member and the best member.
 Run:  python -m audio_mps_amd.sample --modeldir=LOGDIR --sample_duration=16000 --prime=clip.wav
 """
 from __future__ import annotations
@@ -93,6 +97,8 @@ def build_parser():
     p.add_argument("--device_noise", action="store_true", help="draw the noise on the device, from (--seed, path, step) (cmps_noise_fill), "
                    "instead of a host Generator")
     p.add_argument("--segment", type=int, default=None, metavar="S", help="run through a resumable stream in segments of S steps")
+    p.add_argument("--bankdir", default=None, metavar="DIR", help="a directory BankTrainer.save wrote (bank.json + model.<m>.ckpt.npz): sample, "
+                   "continue or score with every member of a PsiCMPS bank at once, instead of --modeldir")
     p.add_argument("--out_dir", default="./samples")
     p.add_argument("--kernel_variant", type=int, default=0, help="as in audio_mps_amd.train")
     return p
@@ -161,12 +167,100 @@ def build_model(variables: dict, sample_rate: int, hparams: str = "", kernel_var
     return model
 
 
+def load_bank(bankdir: str, sample_rate: int, hparams: str = "", kernel_variant: int = 0, backend=None):
+    """The PsiBank a directory written by BankTrainer.save holds, every member with its checkpoint's variables."""
+    import json
+    from .bank import BankTrainer, PsiBank
+    path = os.path.join(bankdir, "bank.json")
+    if not os.path.exists(path):
+        raise FileNotFoundError(f"no bank at {path} (--bankdir: a directory BankTrainer.save wrote)")
+    with open(path) as f:
+        meta = json.load(f)
+    if meta.get("model", PsiBank.MODEL_NAME) != PsiBank.MODEL_NAME:
+        raise ValueError(f"{path} was written by a bank of {meta['model']} models: --bankdir samples and scores PsiCMPS banks only "
+                         f"(take a member's checkpoint with --modeldir)")
+    variables = [load_variables(BankTrainer.member_path(bankdir, m)) for m in range(len(meta["members"]))]
+    if any("psi_x" not in v for v in variables):
+        raise ValueError(f"{bankdir}: a member's checkpoint holds no psi_x (PsiCMPS)")
+    hp = HParams(delta_t=1.0 / sample_rate, h_reg=200.0 / (math.pi * sample_rate) ** 2)       # train.py:41-43
+    hp.bond_dim = int(variables[0]["psi_x"].shape[0])
+    hp.parse(hparams)
+    if backend is None:
+        from .scan import HipScan
+        backend = HipScan(hp.bond_dim, variant=kernel_variant)
+    bank = PsiBank(hp, meta["members"], backend=backend)
+    for m, (model, var) in enumerate(zip(bank.models, variables)):
+        for k in model.variables:
+            if var[k].shape != model.variables[k].shape:
+                raise ValueError(f"member {m}: checkpoint variable {k} has shape {var[k].shape}, bond_dim={hp.bond_dim} needs {model.variables[k].shape}")
+            model.variables[k] = var[k]
+    return bank
+
+
+def _bank_main(args, backend):
+    """--bankdir: `main`'s three jobs with every member of a bank at once, through one BankStream."""
+    bank = load_bank(args.bankdir, args.sample_rate, args.hparams, args.kernel_variant, backend)
+    M, n, length = len(bank), args.num_samples, args.sample_duration
+    os.makedirs(args.out_dir, exist_ok=True)
+    if args.score is not None:
+        clip = load_prime(args.score, args.sample_rate)
+        clip = clip[None, :] if clip.ndim == 1 else clip
+        if clip.ndim != 2 or clip.shape[1] < 2:
+            raise ValueError(f"--score {args.score}: need [T'] or [n, T'] with two samples at least (one increment), not {clip.shape}")
+        n, N = clip.shape[0], clip.shape[1] - 1
+        S = N if args.segment is None else args.segment
+        st = bank.open_stream(n, N)
+        nll, pred = [st.score(clip[:, :S + 1])], [st.last_pred]   # the anchor and S steps
+        for a in range(S + 1, N + 1, S):
+            nll.append(st.score(clip[:, a:a + S]))
+            pred.append(st.last_pred)
+        one = (lambda x: x[:, 0]) if n == 1 else (lambda x: x)
+        nll = np.ascontiguousarray(one(np.concatenate(nll, axis=-1)), dtype=np.float32)
+        pred = np.ascontiguousarray(one(np.concatenate(pred, axis=-1)), dtype=np.float32)
+        np.save(os.path.join(args.out_dir, "nll.npy"), nll)
+        np.save(os.path.join(args.out_dir, "pred.npy"), pred)
+        totals = np.sum(st.total_nll, axis=1, dtype=np.float64)
+        for m in range(M):
+            print(f"member {m}: total nll {totals[m]:.6g}, mean per sample {totals[m] / (n * N):.6g}, {bank.overrides[m]}")
+        best = int(np.argmin(np.where(np.isfinite(totals), totals, np.inf)))
+        print(f"best member {best} of {M} over {n} clip(s) of {N} steps; wrote nll.npy and pred.npy to {args.out_dir}")
+        return nll
+    prime = None if args.prime is None else CMPS._prime(load_prime(args.prime, args.sample_rate), n)
+    P = 0 if prime is None else prime.shape[1] - 1
+    S = max(P, length) if args.segment is None else args.segment
+    st = bank.open_stream(n, P + length, temp=args.temp, seed=args.seed, device_noise=args.device_noise)
+    parts = []
+    if prime is not None:
+        parts.append(np.broadcast_to(prime, (M, n, prime.shape[1])))
+        st.follow(prime[:, :S + 1])                               # the anchor and S steps
+        for a in range(S + 1, P + 1, S):
+            st.follow(prime[:, a:a + S])
+    for a in range(0, length, S):
+        parts.append(st.generate(min(S, length - a)))
+    waves = np.ascontiguousarray(np.concatenate(parts, axis=-1), dtype=np.float32)
+    np.save(os.path.join(args.out_dir, "samples.npy"), waves)
+    for m in range(M):
+        for i in range(n):
+            write_wav(os.path.join(args.out_dir, f"sample_m{m}_{i}.wav"), waves[m, i], args.sample_rate)
+    print(f"wrote {M} x {n} waveform(s) of {waves.shape[-1]} samples to {args.out_dir}")
+    return waves
+
+
 def main(argv=None, backend=None):
     """Returns the waveforms [num_samples, samples] it wrote.  ``backend``: a scan backend to use instead of HipScan (CPU tests of the
     host logic inject one; the product always builds a HipScan and fails loudly without a GPU)."""
+    import sys
     args = build_parser().parse_args(argv)
     if args.sample_duration < 1 or args.num_samples < 1:
         raise ValueError("--sample_duration and --num_samples must be positive")
+    if args.bankdir is not None:
+        if any(a == "--modeldir" or a.startswith("--modeldir=") for a in (sys.argv[1:] if argv is None else argv)):
+            raise ValueError("--bankdir and --modeldir do not go together: a bank's members are read from --bankdir")
+        if args.segment is not None and args.segment < 1:
+            raise ValueError("--segment must be positive")
+        if args.score is not None and (args.device_noise or args.prime is not None):
+            raise ValueError("--score follows and scores its clip and samples nothing: it goes with neither --device_noise nor --prime")
+        return _bank_main(args, backend)
     model = build_model(load_variables(args.modeldir), args.sample_rate, args.hparams, args.kernel_variant, args.seed, backend)
     n, length = args.num_samples, args.sample_duration
     if args.segment is not None and args.segment < 1:

@@ -767,6 +767,85 @@ class HipScan:
                                        want_nll, want_pred, n, loss)
 
     # ------------------------------------------------------------------
+    # A bank's streams (cmps_bank_stream*): `stream` / `stream_score` with a leading member axis on everything a path writes or carries
+    def bank_set_params(self, members, B: int, T: int, train: bool = False):
+        """cmps_bank_set_params_dev from host values: ``members`` is a list of EffectiveParams of one sigma and delta_t (A per member)."""
+        fields = layout.param_fields(self.D, with_A=True)
+        rows = [layout.pack(fields, {**layout.split("R", p.R), "freqs": p.freqs, **layout.split("psi0", p.psi0), "A": p.A}) for p in members]
+        self._bank_params = torch.from_numpy(np.stack(rows)).to(self.device)           # (kept alive: the scans read A from it)
+        self.bank_set_params_dev(self._bank_params, members[0].sigma, members[0].delta_t, B, T, train=train)
+
+    def _bank_M_or_raise(self, what: str) -> int:
+        M = getattr(self, "_bank_M", 0)
+        if self._mode != "bank" or not M:
+            raise RuntimeError(f"{what}() needs bank_set_params_dev() first")
+        return M
+
+    def bank_stream_state(self, n: int) -> torch.Tensor:
+        """Device memory for the stream-state records of ``n`` paths of every member (cmps_bank_stream_state_bytes)."""
+        self._bank_M_or_raise("bank_stream_state")
+        return self._stream_state(self._lib.cmps_bank_stream_state_bytes, n, " (or the handle holds no PsiCMPS bank)")
+
+    def _bank_audio_block(self, audio, M: int, n: int, least: int):
+        """A signal block [n_audio, forced + 1] with n_audio in {1, n, M n} -> (device tensor or None, n_audio, forced)."""
+        audio = np.array(audio, dtype=np.float32, order="C")            # (a copy: torch wants a writable array)
+        if audio.ndim != 2 or audio.shape[1] < least or audio.shape[0] not in (1, n, M * n):
+            raise ValueError(f"audio must be [n_audio, forced + 1] with n_audio in (1, {n}, {M * n}) and forced >= {least - 1}")
+        forced = audio.shape[1] - 1
+        return (torch.from_numpy(audio).to(self.device) if forced > 0 else None), audio.shape[0], forced
+
+    def bank_stream(self, state_in: Optional[torch.Tensor], state_out: Optional[torch.Tensor], k0: int, audio, noise, want_pred: bool = False,
+                    n: Optional[int] = None, length: Optional[int] = None, n_noise: Optional[int] = None):
+        """cmps_bank_stream: `stream` for every member of the bank at once.  ``audio`` [n_audio, forced + 1] with n_audio = 1 (one signal for
+        everybody), n (one per path, shared by the members) or M n, or None; ``noise`` [length, n_noise] (the reference's layout), a device
+        tensor [n_noise, length] or a NoisePlan -- drawn by ONE cmps_noise_fill over ``n_noise`` paths from path 0 -- with n_noise = n
+        (every member hears the same noise) or M n, or None.  ``n`` is required.  Returns (out [M, n, length], pred [M, n, forced] with
+        want_pred, else None)."""
+        M, n = self._bank_M_or_raise("bank_stream"), int(n)
+        self._stream_paths(self._lib.cmps_bank_stream_state_bytes, state_in, state_out, n, n)
+        d_audio = d_noise = d_pred = None
+        n_audio, forced, rows = 1, 0, n
+        if noise is not None:
+            if n_noise is None and isinstance(noise, NoisePlan):
+                n_noise = n                                                   # (an array brings its own path count)
+            d_noise, length, rows = self._device_noise(noise, length, n_noise)
+            if rows not in (n, M * n):
+                raise ValueError(f"noise for {rows} paths fits neither n = {n} nor M n = {M * n}")
+        else:
+            length = 0
+        if audio is not None:
+            d_audio, n_audio, forced = self._bank_audio_block(audio, M, n, 1)
+        d_out = torch.empty((M, n, length), dtype=torch.float32, device=self.device)
+        if want_pred:
+            d_pred = torch.empty((M, n, forced), dtype=torch.float32, device=self.device)
+        ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None   # noqa: E731
+        _capi.check(self._h, self._lib.cmps_bank_stream(self._h, ptr(state_in), ptr(state_out), int(k0), ptr(d_audio), n_audio, forced,
+                                                        ptr(d_noise), rows, length, n, ptr(d_out), ptr(d_pred), self._stream()))
+        return d_out.cpu().numpy(), (d_pred.cpu().numpy() if want_pred else None)
+
+    def bank_stream_score(self, state_in: Optional[torch.Tensor], state_out: Optional[torch.Tensor], k0: int, audio, want_nll: bool = True,
+                          want_pred: bool = False, n: Optional[int] = None, loss=None):
+        """cmps_bank_stream_score: `stream_score` for every member of the bank at once; ``audio`` as in `bank_stream` (forced >= 1), ``loss``
+        [M, n] the running loss to continue.  Returns (nll [M, n, forced] with want_nll else None, the running loss [M, n], pred
+        [M, n, forced] with want_pred else None)."""
+        M, n = self._bank_M_or_raise("bank_stream_score"), int(n)
+        self._stream_paths(self._lib.cmps_bank_stream_state_bytes, state_in, state_out, n, n)
+        d_audio, n_audio, forced = self._bank_audio_block(audio, M, n, 2)
+        if loss is None:
+            d_loss = torch.zeros((M, n), dtype=torch.float32, device=self.device)
+        else:
+            loss = np.array(loss, dtype=np.float32, order="C")
+            if loss.shape != (M, n):
+                raise ValueError(f"loss must be [{M}, {n}]")
+            d_loss = torch.from_numpy(loss).to(self.device)
+        d_nll = torch.empty((M, n, forced), dtype=torch.float32, device=self.device) if want_nll else None
+        d_pred = torch.empty((M, n, forced), dtype=torch.float32, device=self.device) if want_pred else None
+        ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None   # noqa: E731
+        _capi.check(self._h, self._lib.cmps_bank_stream_score(self._h, ptr(state_in), ptr(state_out), int(k0), ptr(d_audio), n_audio, forced, n,
+                                                              ptr(d_nll), ptr(d_loss), ptr(d_pred), self._stream()))
+        return (d_nll.cpu().numpy() if want_nll else None), d_loss.cpu().numpy(), (d_pred.cpu().numpy() if want_pred else None)
+
+    # ------------------------------------------------------------------
     # legacy AudioMPS arithmetic (SURVEY 8f rank 2)
     # ------------------------------------------------------------------
     def legacy_set_params(self, R: np.ndarray, Q: np.ndarray, delta_t: float, B: int, T: int, train: bool = True):

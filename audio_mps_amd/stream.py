@@ -15,6 +15,9 @@ with ``device_noise=True`` draws the noise of a generated step on the device, as
 
 A RhoCMPS stream opened with ``keep_states=S`` also returns rho and the purity after every step of the last call (``st.states()``,
 ``st.purity()``), from a stash that holds S steps however long the run is -- behind a ``score`` call as behind a ``follow``.
+
+A ``BankStream`` (``PsiBank.open_stream``; cmps_bank_stream, cmps_bank_stream_score) is the same stream for every member of a PsiCMPS bank
+at once: results [M, num_paths, steps], ``total_nll`` [M, num_paths], ``ranking()`` and ``best()`` -- M models along one signal.
 """
 from __future__ import annotations
 
@@ -34,7 +37,8 @@ class SampleStream:
         self._saved = None             # steps of the last call whose columns the backend kept (keep_states)
         self.position = 0
         self.last = None
-        self._A = np.float32(model.A)
+        self._shape = self._path_shape(model)   # of everything the stream keeps per path: (num_paths,); a BankStream: (M, num_paths)
+        self._A = self._scale(model)
         self._std = float(model.sigma) * math.sqrt(temp * float(model.delta_t))      # CMPS._noise
         self.device_noise = bool(device_noise)
         self.noise_seed = None         # device noise: the seed every generated step's noise is a function of, with its path and position
@@ -46,9 +50,17 @@ class SampleStream:
         new_state, self._segment = model._stream_entries(self._be)
         self._state = new_state(self.num_paths)
         self._level = None             # inside a sampled run: the level it began at
+        self._raw = None               # the last generate call as the entry returned it (PsiBank.sample)
         self._model = model
-        self.total_nll = np.zeros(self.num_paths, dtype=np.float32)   # the fold carry of the scored steps so far (model.py:279)
+        self.total_nll = np.zeros(self._shape, dtype=np.float32)      # the fold carry of the scored steps so far (model.py:279)
         self.last_pred = None          # the predictions of the last score call
+
+    def _path_shape(self, model):
+        return (self.num_paths,)
+
+    def _scale(self, model):
+        """model.A as the waveforms are divided by it"""
+        return np.float32(model.A)
 
     # ------------------------------------------------------------------
     def _launch(self, steps, entry, *args, **kw):
@@ -93,14 +105,21 @@ class SampleStream:
     def _anchored(self, block, anchor):
         """(block, the audio of a forced call [n_audio, steps + 1]): the block behind the sample it continues from, follow's rule."""
         block = self._block(block)
-        n = self.num_paths
         if anchor or self.last is None:
             audio = block
-        elif block.shape[0] == 1 and np.all(self.last == self.last[0]):
-            audio = np.concatenate([self.last[:1, None], block], axis=1)
         else:
-            audio = np.concatenate([self.last[:, None], np.broadcast_to(block, (n, block.shape[1]))], axis=1)
+            audio = self._behind_last(block)
         return block, audio
+
+    def _behind_last(self, block):
+        """The block behind the stream's last samples: shared by every path while they are all equal, else one row per path."""
+        if block.shape[0] == 1 and np.all(self.last == self.last[0]):
+            return np.concatenate([self.last[:1, None], block], axis=1)
+        return np.concatenate([self.last[:, None], np.broadcast_to(block, (self.num_paths, block.shape[1]))], axis=1)
+
+    def _rows(self, audio):
+        """A forced call's audio as the entry takes it: [n_audio, steps + 1]."""
+        return np.ascontiguousarray(audio)
 
     def score(self, block, anchor: bool = False) -> np.ndarray:
         """``follow`` that also says how likely the block was (cmps_psi_stream_score / cmps_rho_stream_score): same arguments, anchoring
@@ -111,14 +130,14 @@ class SampleStream:
         stream carries: ``follow``, ``score`` and ``generate`` alternate freely, and unscored steps leave ``total_nll`` as it is."""
         entry = self._model._stream_score_entry(self._be)
         block, audio = self._anchored(block, anchor)
-        n, steps = self.num_paths, audio.shape[1] - 1
-        nll = np.empty((n, 0), dtype=np.float32)
-        pred = np.empty((n, 0), dtype=np.float32)
+        steps = audio.shape[-1] - 1
+        nll = np.empty(self._shape + (0,), dtype=np.float32)
+        pred = np.empty(self._shape + (0,), dtype=np.float32)
         if steps:
-            nll, total, pred = self._launch(steps, entry, np.ascontiguousarray(audio), want_nll=True, want_pred=True, loss=self.total_nll)
+            nll, total, pred = self._launch(steps, entry, self._rows(audio), want_nll=True, want_pred=True, loss=self.total_nll)
             self.total_nll = np.asarray(total, dtype=np.float32)
         self.last_pred = pred
-        self.last = np.array(np.broadcast_to(block[:, -1], (n,)), dtype=np.float32)
+        self.last = np.array(np.broadcast_to(block[..., -1], self._shape), dtype=np.float32)
         self._level = None
         return nll
 
@@ -129,12 +148,11 @@ class SampleStream:
         (to resume behind a generated gap without showing the model the jump).  Returns the model's expected increment before every
         step, [num_paths, steps]."""
         block, audio = self._anchored(block, anchor)
-        n = self.num_paths
-        steps = audio.shape[1] - 1
-        pred = np.empty((n, 0), dtype=np.float32)
+        steps = audio.shape[-1] - 1
+        pred = np.empty(self._shape + (0,), dtype=np.float32)
         if steps:
-            _, pred = self._launch(steps, self._segment, np.ascontiguousarray(audio), None, True)
-        self.last = np.array(np.broadcast_to(block[:, -1], (n,)), dtype=np.float32)
+            _, pred = self._launch(steps, self._segment, self._rows(audio), None, True)
+        self.last = np.array(np.broadcast_to(block[..., -1], self._shape), dtype=np.float32)
         self._level = None
         return pred
 
@@ -145,7 +163,7 @@ class SampleStream:
         (stddev sigma sqrt(temp delta_t), as CMPS._noise), or is passed in.  A stream opened with ``device_noise=True`` draws it on the
         device instead (cmps_noise_fill): step k of path b gets stddev * z(noise_seed, b, k), a function of the stream's position alone, so
         how a run is cut into calls -- or into processes -- changes no bit of it."""
-        length, n = int(length), self.num_paths
+        length, n = int(length), self._noise_paths()
         if length < 1:
             raise ValueError("generate needs length >= 1")
         if self.position + length > self.max_steps:                  # (before the draw: a refused call leaves the Generator alone)
@@ -153,7 +171,7 @@ class SampleStream:
         kw = {}
         if noise is None and self.device_noise:
             from .scan import NoisePlan
-            noise, kw = NoisePlan(self.noise_seed, self.position, self._std), {"length": length}
+            noise, kw = NoisePlan(self.noise_seed, self.position, self._std), {"length": length, **self._plan_kw()}
         else:
             if noise is None:
                 noise = (self._std * self._rng.standard_normal((length, n))).astype(np.float32)
@@ -161,11 +179,20 @@ class SampleStream:
             if noise.shape != (length, n):
                 raise ValueError(f"noise must be [{length}, {n}]")
         if self._level is None:
-            self._level = np.zeros(n, dtype=np.float32) if self.last is None else self.last.copy()
+            self._level = np.zeros(self._shape, dtype=np.float32) if self.last is None else self.last.copy()
         out, _ = self._launch(length, self._segment, None, noise, False, **kw)
-        wave = (self._level[:, None] + out / self._A).astype(np.float32)
-        self.last = wave[:, -1].copy()
+        self._raw = out                # A * running sum of the sampled increments: the reference's convention (model.py:251)
+        wave = (self._level[..., None] + out / self._A).astype(np.float32)
+        self.last = wave[..., -1].copy()
         return wave
+
+    def _noise_paths(self) -> int:
+        """Columns of a generate call's noise"""
+        return self.num_paths
+
+    def _plan_kw(self) -> dict:
+        """What the segment entry needs next to a NoisePlan besides ``length``"""
+        return {}
 
     def fill_gaps(self, clip, known) -> np.ndarray:
         """``clip`` [T] or [num_paths, T] with a boolean mask ``known`` [T]: runs of True are followed, runs of False generated, and each
@@ -173,14 +200,142 @@ class SampleStream:
         waveform in the gaps."""
         clip = self._block(clip)
         known = np.asarray(known, dtype=bool)
-        if known.shape != (clip.shape[1],):
-            raise ValueError(f"known must be a boolean mask [{clip.shape[1]}]")
-        T, n = clip.shape[1], self.num_paths
-        wave = np.array(np.broadcast_to(clip, (n, T)), dtype=np.float32)
+        if known.shape != (clip.shape[-1],):
+            raise ValueError(f"known must be a boolean mask [{clip.shape[-1]}]")
+        T = clip.shape[-1]
+        wave = np.array(np.broadcast_to(clip, self._shape + (T,)), dtype=np.float32)
         edges = [0] + [k for k in range(1, T) if known[k] != known[k - 1]] + [T]
         for a, b in zip(edges[:-1], edges[1:]):
             if known[a]:
-                self.follow(clip[:, a:b], anchor=a > 0)
+                self.follow(clip[..., a:b], anchor=a > 0)
             else:
-                wave[:, a:b] = self.generate(b - a)
+                wave[..., a:b] = self.generate(b - a)
         return wave
+
+
+class _MemberLoop:
+    """The three bank entries of HipScan (bank_stream_state, bank_stream, bank_stream_score) for a backend that lacks them: a loop over
+    one plain backend per member, as BankTrainer loops over plain steps.  A state is the list of the members' states."""
+
+    def __init__(self, backends):
+        self.backends = list(backends)
+
+    def bank_set_params(self, members, B, T, train=False):
+        for be, p in zip(self.backends, members):
+            be.set_params(p, B, T, train=train)
+
+    def bank_stream_state(self, n):
+        return [be.stream_state(n) for be in self.backends]
+
+    def _member(self, rows, m, n, axis):
+        """Member m's rows of an array shared by the members (1 or n rows) or holding M n"""
+        if rows is None or rows.shape[axis] in (1, n) and len(self.backends) * n != rows.shape[axis]:
+            return rows
+        return np.take(rows, range(m * n, (m + 1) * n), axis=axis)
+
+    def bank_stream(self, state_in, state_out, k0, audio, noise, want_pred=False, n=None):
+        audio = None if audio is None else np.asarray(audio, dtype=np.float32)
+        noise = None if noise is None else np.asarray(noise, dtype=np.float32)
+        res = [be.stream(None if state_in is None else state_in[m], None if state_out is None else state_out[m], k0,
+                         self._member(audio, m, n, 0), self._member(noise, m, n, 1), want_pred, n=n) for m, be in enumerate(self.backends)]
+        return np.stack([r[0] for r in res]), (np.stack([r[1] for r in res]) if want_pred else None)
+
+    def bank_stream_score(self, state_in, state_out, k0, audio, want_nll=True, want_pred=False, n=None, loss=None):
+        audio = np.asarray(audio, dtype=np.float32)
+        res = [be.stream_score(None if state_in is None else state_in[m], None if state_out is None else state_out[m], k0,
+                               self._member(audio, m, n, 0), want_nll, want_pred, n=n, loss=None if loss is None else loss[m])
+               for m, be in enumerate(self.backends)]
+        pick = lambda i, want: np.stack([r[i] for r in res]) if want else None   # noqa: E731
+        return pick(0, want_nll), np.stack([r[1] for r in res]), pick(2, want_pred)
+
+
+class _BankScan:
+    """What SampleStream asks of its model, answered by a PsiBank: the members' effective parameters as they are when the stream is opened,
+    on a backend of the stream's own."""
+
+    def __init__(self, bank):
+        self.members = [m.effective_params() for m in bank.models]
+        m0 = bank.models[0]
+        self.sigma, self.delta_t = m0.sigma, m0.delta_t
+        self._noise_seed = m0._noise_seed
+        self.backend = bank.stream_backend()
+        if not hasattr(self.backend, "bank_stream"):
+            self.backend = _MemberLoop([self.backend] + [bank.stream_backend() for _ in self.members[1:]])
+
+    def __len__(self):
+        return len(self.members)
+
+    def _device_noise_backend(self):
+        if not hasattr(self.backend, "draw_noise"):
+            raise ValueError("device_noise=True needs a backend that draws noise on the device (draw_noise): the bank's has none")
+        return self.backend
+
+    def _prepare_stream(self, num_paths, max_steps, keep_states=0):
+        self.backend.bank_set_params(self.members, num_paths, max_steps + 1, train=False)
+        return self.backend
+
+    def _stream_entries(self, be):
+        return be.bank_stream_state, be.bank_stream
+
+    def _stream_score_entry(self, be):
+        return be.bank_stream_score
+
+
+class BankStream(SampleStream):
+    """Returned by ``PsiBank.open_stream`` / ``BankTrainer.open_stream``: a SampleStream of every member at once (cmps_bank_stream,
+    cmps_bank_stream_score).  Everything carries a leading member axis -- results [M, num_paths, steps], ``last`` and ``total_nll``
+    [M, num_paths] -- and a block may be [m] / [1, m] (one signal for everybody), [num_paths, m] (shared by the members) or
+    [M, num_paths, m].  Member m, path b gets the noise ``member(m).open_stream(num_paths, ..., seed=seed)`` would give path b, so what
+    differs between two members' samples is the model and not the draw; ``independent_noise=True`` numbers the paths globally instead
+    (g = m num_paths + b).  On a backend without the bank entries the stream loops over plain streams of its members."""
+
+    def __init__(self, bank, num_paths: int, max_steps: int, temp=1, seed=None, device_noise: bool = False, independent_noise: bool = False):
+        self.independent_noise = bool(independent_noise)
+        super().__init__(_BankScan(bank), num_paths, max_steps, temp=temp, seed=seed, device_noise=device_noise)
+        self.native = not isinstance(self._be, _MemberLoop)
+
+    def __len__(self) -> int:
+        return self._shape[0]
+
+    def _path_shape(self, model):
+        return (len(model), self.num_paths)
+
+    def _scale(self, model):
+        return np.array([p.A for p in model.members], dtype=np.float32)[:, None, None]
+
+    def _block(self, block) -> np.ndarray:
+        if hasattr(block, "detach"):
+            block = block.detach().cpu().numpy()
+        block = np.asarray(block, dtype=np.float32)
+        if block.ndim == 1:
+            block = block[None, :]
+        M, n = self._shape
+        if not (block.ndim == 2 and block.shape[0] in (1, n) or block.shape[:-1] == (M, n)) or block.shape[-1] < 1:
+            raise ValueError(f"a block must be [m], [1, m], [{n}, m] or [{M}, {n}, m] with m >= 1, not {block.shape}")
+        return block
+
+    def _behind_last(self, block):
+        M, n = self._shape
+        m = block.shape[-1]
+        if block.ndim == 2 and np.all(self.last == self.last[0]):       # the members agree: the audio stays shared between them
+            if block.shape[0] == 1 and np.all(self.last[0] == self.last[0, 0]):
+                return np.concatenate([self.last[0, :1, None], block], axis=1)
+            return np.concatenate([self.last[0][:, None], np.broadcast_to(block, (n, m))], axis=1)
+        return np.concatenate([self.last[..., None], np.broadcast_to(block, (M, n, m))], axis=-1)
+
+    def _rows(self, audio):
+        return np.ascontiguousarray(audio.reshape(-1, audio.shape[-1]))
+
+    def _noise_paths(self) -> int:
+        return self._shape[0] * self.num_paths if self.independent_noise else self.num_paths
+
+    def _plan_kw(self) -> dict:
+        return {"n_noise": self._noise_paths()}
+
+    def ranking(self) -> np.ndarray:
+        """Per path, the members ordered by ``total_nll``, the most likely first: [M, num_paths] (a stable sort; NaN last)."""
+        return np.argsort(self.total_nll, axis=0, kind="stable")
+
+    def best(self) -> np.ndarray:
+        """Per path, the member under which the scored samples so far were the most likely: [num_paths], the classifier's answer."""
+        return self.ranking()[0]

@@ -290,6 +290,8 @@ size_t cmps_bank_workspace_bytes(int D, int M, int B, int T, int flags);
  * CMPS_WS_REUSE_TABLES as in cmps_set_params.  Puts the handle into bank mode; a plain cmps_set_params* puts it back.  In bank mode
  * the plain entries that read the tables of ONE model -- cmps_psi_loss_fwd / _bwd, cmps_psi_grad_status, cmps_psi_states,
  * cmps_psi_update_ancilla, cmps_psi_sample*, cmps_psi_stream*, cmps_rho_set_state, cmps_rho_update_ancilla -- return CMPS_ERR_STATE.
+ * Sampling, following and scoring with every member at once are cmps_bank_stream / cmps_bank_stream_score below (a plain or a primed
+ * sample of a bank is a stream from k0 = 0); the state read-outs and the ancilla updates need a member taken out as a plain model.
  */
 int cmps_bank_set_params_dev(cmps_handle_t h, int M, const float* params_dev, double sigma, double delta_t, int T, int B_max, int flags,
                              void* workspace_dev, size_t workspace_bytes, void* stream);
@@ -323,6 +325,48 @@ int cmps_bank_apply_step(cmps_handle_t h, int M, float* vars_dev, float* adam_m_
  * of every member's flag words since the previous call.  Waits for `stream`.  Returns CMPS_OK when the words were read.
  */
 int cmps_bank_grad_status(cmps_handle_t h, int* codes_out, int* sticky_out, void* stream);
+
+/*
+ * ---- Model bank: stream, sample and score with M PsiCMPS models per launch ----
+ * Replaces: the Python loop over a trained bank's members that listening to a sweep (the samples of every member, as the reference's
+ * summaries give them for one model: model.sample(3, sample_duration), train.py:82-85) or classifying with one model per pitch or
+ * instrument (reader.py:9-66: follow one signal with all M, compare the per-sample surprise) is.  The samplers are bound by their
+ * serial chain as the training scans are, and n = 3 paths of one model are three wavefronts.
+ *
+ * cmps_bank_stream / cmps_bank_stream_score are cmps_psi_stream / cmps_psi_stream_score (below: every convention of the segment, the
+ * one-sample overlap of the audio, the state rule, the exact cut, the running loss) with the members as a second grid dimension of
+ * the same kernels: member m runs n paths on its own tables, and the caller's arrays are indexed by the global path g = m * n + b.
+ *   out_dev, noise_dev (n_noise == M * n)   [M][n][length]
+ *   pred_dev, nll_dev                       [M][n][forced]
+ *   loss_dev                                [M][n]
+ *   state_in_dev, state_out_dev             [M][n] records: cmps_bank_stream_state_bytes(h, n) = M * n records of the handle's sampler
+ *                                           family (0 for a null handle, n < 1, and outside PsiCMPS bank mode)
+ *   audio_dev                               [n_audio][forced + 1], n_audio in {1, n, M * n}: one signal for every path of every member
+ *                                           (the classifier), one per path shared by the members, or one per member and path
+ *   noise_dev                               [n_noise][length], n_noise in {n, M * n}: every member hears the same noise -- what differs
+ *                                           between two members' samples is then the model and not the draw -- or every global path
+ *                                           its own (n_noise is not looked at when length == 0)
+ * The promise: member m's slices of out, pred, nll, loss and the state records hold, bit for bit, what cmps_psi_stream /
+ * cmps_psi_stream_score give on a plain handle set to model m (cmps_set_params_dev on row m of params_dev) with the same T, fed member
+ * m's audio and noise rows.  A cut changes no bit, as for the plain stream.
+ * The handle must be in PsiCMPS bank mode (after cmps_bank_set_params_dev), otherwise CMPS_ERR_STATE: plain mode, legacy mode, a
+ * RhoCMPS bank, before any set_params.  The kernel families are the bank's: k_sample_wave for D <= 32 under CMPS_VARIANT_AUTO / WAVE,
+ * k_sample_block under CMPS_VARIANT_BLOCK at every D <= 128 (cmps_bank_*'s own mode errors apply).
+ * CMPS_ERR_BAD_ARG: n_audio not in {1, n, M * n}; n_noise not in {n, M * n} when length > 0; M * n * (forced + length) beyond 2^31 - 1;
+ * and everything the plain entries refuse (state_in_dev NULL <=> k0 == 0, the table rows with a message naming the needed T, null
+ * pointers, the counts).  Every message starts with the entry's name and is returned before the device is touched.
+ * Asynchronous on `stream`; never synchronises, allocates nothing, touches nothing outside the stated extents.  With
+ * CMPS_OPT_KERNEL_EVENTS the launch is recorded under the plain entries' names: k_sample_wave_stream, k_sample_wave_score,
+ * k_sample_block_stream, k_sample_block_score.
+ */
+size_t cmps_bank_stream_state_bytes(cmps_handle_t h, int n);
+int cmps_bank_stream(cmps_handle_t h, const void* state_in_dev, void* state_out_dev, int k0,
+                     const float* audio_dev, int n_audio, int forced,
+                     const float* noise_dev, int n_noise, int length,
+                     int n, float* out_dev, float* pred_dev, void* stream);
+int cmps_bank_stream_score(cmps_handle_t h, const void* state_in_dev, void* state_out_dev, int k0,
+                           const float* audio_dev, int n_audio, int forced, int n,
+                           float* nll_dev, float* loss_dev, float* pred_dev, void* stream);
 
 /*
  * Replaces: PsiCMPS._update_ancilla_psi (model.py:300-317), one step in the lab frame.
