@@ -156,6 +156,15 @@ class BankTrainer:
         self.rank = int(bank.rank)    # 0: PsiCMPS members; else the columns of every RhoCMPS member (selects the layouts and the rho_bank_* entries)
         entries = RHO_BANK_ENTRIES if self.rank else ("bank_set_params_dev", "bank_forward", "bank_backward", "bank_apply_step")
         self.native = all(hasattr(be, name) for name in entries)
+        if self.native:               # the backend's operations of this kind of bank, bound once: every call below goes through them
+            setter, self._forward, self._backward, apply_step = (getattr(be, name) for name in entries)
+            m0, r = bank.models[0], self.rank
+            if r:
+                self._configure = lambda st, B, T, train: setter(st["params"], st["phi"], r, m0.sigma, m0.delta_t, B, T, train=train)
+                self._apply_step = lambda st, grad, *a: apply_step(st["vars"], st["m"], st["v"], grad, r, *a, st["params"], st["phi"], st["losses"])
+            else:
+                self._configure = lambda st, B, T, train: setter(st["params"], m0.sigma, m0.delta_t, B, T, train=train)
+                self._apply_step = lambda st, grad, *a: apply_step(st["vars"], st["m"], st["v"], grad, *a, st["params"], st["losses"])
         plain_device = type(be).__name__ == "HipScan"
         self.trainers = [Trainer(model, hp, device_step=plain_device and not self.native)
                          for model, hp in zip(bank.models, bank.member_hparams)]
@@ -222,13 +231,7 @@ class BankTrainer:
     def _apply(self, grad_sums, global_batch):
         st, o = self._dev, self.trainers[0].opt
         t = max(o.t, 1)
-        be, bias = self.bank.backend, (math.sqrt(1.0 - o.b2 ** t), 1.0 - o.b1 ** t)
-        if self.rank:
-            be.rho_bank_apply_step(st["vars"], st["m"], st["v"], grad_sums, self.rank, global_batch, *bias, o.b1, o.b2, o.eps, st["hyper"], True,
-                                   st["params"], st["phi"], st["losses"])
-        else:
-            be.bank_apply_step(st["vars"], st["m"], st["v"], grad_sums, global_batch, *bias, o.b1, o.b2, o.eps, st["hyper"], True, st["params"],
-                               st["losses"])
+        self._apply_step(st, grad_sums, global_batch, math.sqrt(1.0 - o.b2 ** t), 1.0 - o.b1 ** t, o.b1, o.b2, o.eps, st["hyper"], True)
 
     def sync_to_host(self):
         """Device-resident state -> every member's model.variables and Adam slots."""
@@ -266,18 +269,12 @@ class BankTrainer:
         return out
 
     def _step_native(self, data):
-        be, m0 = self.bank.backend, self.bank.models[0]
         st = self._device_state()
-        audio = m0._to_device(data)
+        audio = self.bank.models[0]._to_device(data)
         B, T = audio.shape[-2:]
-        if self.rank:
-            be.rho_bank_set_state_dev(st["params"], st["phi"], self.rank, m0.sigma, m0.delta_t, int(B), int(T), train=True)
-            be.rho_bank_forward(audio, save_for_bwd=True)
-            flat = be.rho_bank_backward()
-        else:
-            be.bank_set_params_dev(st["params"], m0.sigma, m0.delta_t, int(B), int(T), train=True)
-            be.bank_forward(audio, save_for_bwd=True)
-            flat = be.bank_backward()
+        self._configure(st, int(B), int(T), True)
+        self._forward(audio, save_for_bwd=True)
+        flat = self._backward()
         for tr in self.trainers:
             tr.opt.t += 1
             tr.global_step += 1
@@ -314,22 +311,18 @@ class BankTrainer:
             return [tr.evaluate(dataset, minibatch_size, T, keep_losses) for tr in self.trainers]
         import torch
         from .evaluate import EvalResult, _need_stats
-        be, m0 = self.bank.backend, self.bank.models[0]
+        be = self.bank.backend
         _need_stats(be)
         mb = int(minibatch_size) if minibatch_size else int(self.bank.hparams.minibatch_size)
         T = dataset.clip_len if T is None else int(T)
         if T < 2 or mb < 1:
             raise ValueError("evaluate needs T >= 2 and minibatch_size >= 1")
         st = self._device_state()
-        if self.rank:
-            be.rho_bank_set_state_dev(st["params"], st["phi"], self.rank, m0.sigma, m0.delta_t, min(mb, dataset.n_clips), T, train=False)
-        else:
-            be.bank_set_params_dev(st["params"], m0.sigma, m0.delta_t, min(mb, dataset.n_clips), T, train=False)
-        forward = be.rho_bank_forward if self.rank else be.bank_forward
+        self._configure(st, min(mb, dataset.n_clips), T, False)
         M = len(self.trainers)
         stats, kept = [None] * M, [[] for _ in range(M)]
         for first_id, batch in dataset.ordered(mb, T):
-            loss = forward(batch, save_for_bwd=False)
+            loss = self._forward(batch, save_for_bwd=False)
             for m in range(M):
                 stats[m] = be.loss_stats(loss[m], first_id, stats[m], reset=stats[m] is None)
                 if keep_losses:

@@ -221,6 +221,22 @@ int check_bwd(cmps_handle_t h, const char* who, bool ready, const char* fwd, con
     if (B != S.B || T != S.steps + 1 || audio != S.audio) return fail(h, CMPS_ERR_STATE, w + ": audio / B / T differ from the forward call");
     return CMPS_OK;
 }
+// What the four *_apply_step entries ask of an update (grad_sums non-null) and of their double-precision buffers (hyper: the bank entries')
+int check_apply_step(cmps_handle_t h, const char* who, const float* grad_sums, const float* adam_m, const float* adam_v, const float* losses,
+                     const void* scratch, double global_batch, const double* hyper = nullptr) {
+    const std::string w(who);
+    if (grad_sums && (!adam_m || !adam_v || !losses || !scratch || !(global_batch > 0.0)))
+        return fail(h, CMPS_ERR_BAD_ARG, w + ": an update needs the Adam slots, losses_dev, scratch_dev and a positive batch");
+    if (((uintptr_t)scratch & 7) != 0) return fail(h, CMPS_ERR_BAD_ARG, w + ": scratch_dev must be 8-byte aligned");
+    if (((uintptr_t)hyper & 7) != 0) return fail(h, CMPS_ERR_BAD_ARG, w + ": hyper_dev must be 8-byte aligned");
+    return CMPS_OK;
+}
+// The member strides of a bank launch, in floats: between two members' batches (0: one shared batch), loss rows and gradient rows
+void bank_strides(Dev& P, int n_audio, int B, int T, size_t grad = 0) {
+    P.bank_audio = n_audio == 1 ? 0 : (size_t)B * T;
+    P.bank_loss = (size_t)B;
+    P.bank_grad = grad;                  // (a forward: 0, the value h->P holds anyway; no forward kernel reads it)
+}
 // What every plain entry outside a bank's scope (samplers, streams, state read-outs, ancilla updates, cmps_rho_set_state,
 // cmps_psi_grad_status) answers while the workspace holds a bank: its tables would be member 0's alone.  A member is taken out as a plain model.
 int check_not_bank(cmps_handle_t h, const char* who) {
@@ -413,13 +429,19 @@ int cmps_set_params(cmps_handle_t h, const float* R_re_dev, const float* R_im_de
                            workspace_dev, workspace_bytes, stream);
 }
 
+// set_params_impl on the packed buffer R_re | R_im | freqs | psi0_re | psi0_im | A that the apply-step entries write (a bank's: member 0's row)
+static int set_params_packed(cmps_handle_t h, const float* params_dev, double sigma, double delta_t, int T, int B_max, int flags,
+                             void* workspace_dev, size_t workspace_bytes, void* stream, int M = 0, size_t rho_bytes = 0) {
+    const size_t DD = (size_t)h->D * h->D, D = (size_t)h->D;
+    return set_params_impl(h, params_dev, params_dev + DD, params_dev + 2 * DD, params_dev + 2 * DD + D, params_dev + 2 * DD + 2 * D,
+                           0.f, params_dev + 2 * DD + 3 * D, sigma, delta_t, T, B_max, flags, workspace_dev, workspace_bytes, stream, M, rho_bytes);
+}
+
 int cmps_set_params_dev(cmps_handle_t h, const float* params_dev, double sigma, double delta_t, int T, int B_max, int flags,
                         void* workspace_dev, size_t workspace_bytes, void* stream) {
     if (!h) return CMPS_ERR_BAD_ARG;
     if (!params_dev) return fail(h, CMPS_ERR_BAD_ARG, "cmps_set_params_dev: null parameter buffer");
-    const size_t DD = (size_t)h->D * h->D, D = (size_t)h->D;
-    return set_params_impl(h, params_dev, params_dev + DD, params_dev + 2 * DD, params_dev + 2 * DD + D, params_dev + 2 * DD + 2 * D,
-                           0.f, params_dev + 2 * DD + 3 * D, sigma, delta_t, T, B_max, flags, workspace_dev, workspace_bytes, stream);
+    return set_params_packed(h, params_dev, sigma, delta_t, T, B_max, flags, workspace_dev, workspace_bytes, stream);
 }
 
 size_t cmps_apply_step_scratch_bytes(int D) { return (D < 1 || D > 128) ? 0 : apply_step_scratch_bytes(D); }
@@ -430,10 +452,8 @@ int cmps_psi_apply_step(cmps_handle_t h, float* vars_dev, float* adam_m_dev, flo
                         void* stream) {
     if (!h) return CMPS_ERR_BAD_ARG;
     if (!vars_dev || !params_dev) return fail(h, CMPS_ERR_BAD_ARG, "cmps_psi_apply_step: null variable / parameter buffer");
+    if (const int rc = check_apply_step(h, "cmps_psi_apply_step", grad_sums_dev, adam_m_dev, adam_v_dev, losses_dev, scratch_dev, global_batch)) return rc;
     const bool apply = grad_sums_dev != nullptr;
-    if (apply && (!adam_m_dev || !adam_v_dev || !losses_dev || !scratch_dev || !(global_batch > 0.0)))
-        return fail(h, CMPS_ERR_BAD_ARG, "cmps_psi_apply_step: an update needs the Adam slots, losses_dev, scratch_dev and a positive batch");
-    if (((uintptr_t)scratch_dev & 7) != 0) return fail(h, CMPS_ERR_BAD_ARG, "cmps_psi_apply_step: scratch_dev must be 8-byte aligned");
     const hipError_t e = launch_apply_step(h->D, apply, apply ? 1.0 / global_batch : 0.0, lr_t, beta1, beta2, epsilon, h_reg, r_reg, c_r,
                                            c_h, with_reg != 0, vars_dev, adam_m_dev, adam_v_dev, grad_sums_dev, params_dev, losses_dev,
                                            static_cast<double*>(scratch_dev), static_cast<hipStream_t>(stream));
@@ -453,10 +473,8 @@ int cmps_rho_apply_step(cmps_handle_t h, float* vars_dev, float* adam_m_dev, flo
     if (!vars_dev || !params_dev || !phi_dev)
         return fail(h, CMPS_ERR_BAD_ARG, "cmps_rho_apply_step: null variable / parameter / column buffer");
     if (rank < 1 || rank > 128) return fail(h, CMPS_ERR_BAD_ARG, "cmps_rho_apply_step: rank outside [1, 128]");
+    if (const int rc = check_apply_step(h, "cmps_rho_apply_step", grad_sums_dev, adam_m_dev, adam_v_dev, losses_dev, scratch_dev, global_batch)) return rc;
     const bool apply = grad_sums_dev != nullptr;
-    if (apply && (!adam_m_dev || !adam_v_dev || !losses_dev || !scratch_dev || !(global_batch > 0.0)))
-        return fail(h, CMPS_ERR_BAD_ARG, "cmps_rho_apply_step: an update needs the Adam slots, losses_dev, scratch_dev and a positive batch");
-    if (((uintptr_t)scratch_dev & 7) != 0) return fail(h, CMPS_ERR_BAD_ARG, "cmps_rho_apply_step: scratch_dev must be 8-byte aligned");
     const hipError_t e = launch_rho_apply_step(h->D, rank, apply, apply ? 1.0 / global_batch : 0.0, lr_t, beta1, beta2, epsilon, h_reg,
                                                r_reg, c_r, c_h, with_reg != 0, vars_dev, adam_m_dev, adam_v_dev, grad_sums_dev,
                                                params_dev, phi_dev, losses_dev, static_cast<double*>(scratch_dev),
@@ -471,7 +489,7 @@ static int psi_fwd_run(cmps_handle_t h, const char* who, int M, int n_audio, con
     Dev P = h->P;
     P.B = B;
     const int Mk = M > 0 ? M : 1;
-    if (M > 0) { P.bank_audio = n_audio == 1 ? 0 : (size_t)B * T; P.bank_loss = (size_t)B; }
+    if (M > 0) bank_strides(P, n_audio, B, T);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int variant = resolve_variant(h);
     KBind kb(h);
@@ -512,11 +530,7 @@ static int psi_bwd_run(cmps_handle_t h, const char* who, int M, int n_audio, con
     const auto failed = [&](hipError_t e, const char* stage) { return fail_hip(h, e, (std::string(who) + stage).c_str()); };
     Dev P = main_dev(h, B);
     const int Mk = M > 0 ? M : 1;
-    if (M > 0) {
-        P.bank_audio = n_audio == 1 ? 0 : (size_t)B * T;
-        P.bank_loss = (size_t)B;
-        P.bank_grad = 2 * (size_t)h->D * h->D + 3 * (size_t)h->D + 2;
-    }
+    if (M > 0) bank_strides(P, n_audio, B, T, 2 * (size_t)h->D * h->D + 3 * (size_t)h->D + 2);
     P.f16_shift = h->f16_shift;
     hipStream_t s = static_cast<hipStream_t>(stream);
     // the reverse kernels belong to the family whose forward wrote the stash
@@ -637,9 +651,7 @@ int cmps_bank_set_params_dev(cmps_handle_t h, int M, const float* params_dev, do
     if (const int rc = bank_check_M(h, who, M)) return rc;
     if (const int rc = bank_check_shape(h, who, M, B_max, T)) return rc;
     if (!workspace_dev) return fail(h, CMPS_ERR_WORKSPACE, std::string(who) + ": null workspace");
-    const size_t DD = (size_t)h->D * h->D, D = (size_t)h->D;
-    return set_params_impl(h, params_dev, params_dev + DD, params_dev + 2 * DD, params_dev + 2 * DD + D, params_dev + 2 * DD + 2 * D,
-                           0.f, params_dev + 2 * DD + 3 * D, sigma, delta_t, T, B_max, flags, workspace_dev, workspace_bytes, stream, M);
+    return set_params_packed(h, params_dev, sigma, delta_t, T, B_max, flags, workspace_dev, workspace_bytes, stream, M);
 }
 
 int cmps_bank_loss_fwd(cmps_handle_t h, const float* audio_dev, int n_audio, int B, int T, float* loss_dev, int save_for_bwd, void* stream) {
@@ -669,15 +681,12 @@ size_t cmps_bank_apply_step_scratch_bytes(int D, int M) {
 int cmps_bank_apply_step(cmps_handle_t h, int M, float* vars_dev, float* adam_m_dev, float* adam_v_dev, const float* grad_sums_dev,
                          double global_batch, double bias_num, double bias_den, double beta1, double beta2, double epsilon,
                          const double* hyper_dev, int with_reg, float* params_dev, float* losses_dev, void* scratch_dev, void* stream) {
-    const std::string w("cmps_bank_apply_step");
+    const char* who = "cmps_bank_apply_step";
     if (!h) return CMPS_ERR_BAD_ARG;
-    if (!vars_dev || !params_dev || !hyper_dev) return fail(h, CMPS_ERR_BAD_ARG, w + ": null variable / parameter / hyper-parameter buffer");
-    if (const int rc = bank_check_M(h, "cmps_bank_apply_step", M)) return rc;
+    if (!vars_dev || !params_dev || !hyper_dev) return fail(h, CMPS_ERR_BAD_ARG, std::string(who) + ": null variable / parameter / hyper-parameter buffer");
+    if (const int rc = bank_check_M(h, who, M)) return rc;
+    if (const int rc = check_apply_step(h, who, grad_sums_dev, adam_m_dev, adam_v_dev, losses_dev, scratch_dev, global_batch, hyper_dev)) return rc;
     const bool apply = grad_sums_dev != nullptr;
-    if (apply && (!adam_m_dev || !adam_v_dev || !losses_dev || !scratch_dev || !(global_batch > 0.0)))
-        return fail(h, CMPS_ERR_BAD_ARG, w + ": an update needs the Adam slots, losses_dev, scratch_dev and a positive batch");
-    if (((uintptr_t)scratch_dev & 7) != 0) return fail(h, CMPS_ERR_BAD_ARG, w + ": scratch_dev must be 8-byte aligned");
-    if (((uintptr_t)hyper_dev & 7) != 0) return fail(h, CMPS_ERR_BAD_ARG, w + ": hyper_dev must be 8-byte aligned");
     const hipError_t e = launch_bank_apply_step(h->D, M, apply, apply ? 1.0 / global_batch : 0.0, bias_num, bias_den, beta1, beta2, epsilon,
                                                 hyper_dev, with_reg != 0, vars_dev, adam_m_dev, adam_v_dev, grad_sums_dev, params_dev,
                                                 losses_dev, static_cast<double*>(scratch_dev), static_cast<hipStream_t>(stream));
@@ -768,24 +777,51 @@ static int primed_args(cmps_handle_t h, const char* who, const float* prime_dev,
     S = SampleDev{noise_dev, n, length, out_dev, PrimeDev{prime_dev, n_prime == 1 ? 0 : prime_T, PF, pred_dev}, nullptr, nullptr};
     return CMPS_OK;
 }
-// The same for cmps_{psi,rho}_stream (`rec`: floats of one state record); ST is the caller's, S points to it.  cmps_psi_stream_score, whose
-// messages and stricter lines are its own, shares the state rule
+// The launch record of one stream segment: S points to ST and, when the segment is scored, to SC (so a StreamCall is filled where it stands)
+struct StreamCall {
+    StreamDev ST{};
+    ScoreDev SC{};
+    SampleDev S{};
+};
+// A stream entry's rule for the row counts of its arrays: the signal's n_audio and the noise's n_noise (n where the segment samples
+// nothing), for n paths and `steps` steps.  plain_rows is a plain handle's, bank_rows a bank's
+using RowRule = int (*)(cmps_handle_t h, const char* who, int n_audio, int n_noise, int n, long long steps);
+static int plain_rows(cmps_handle_t h, const char* who, int n_audio, int, int n, long long) { return sample_check_clips(h, who, "n_audio", n_audio, n); }
 static int stream_check_state(cmps_handle_t h, const char* who, const void* state_in_dev, int k0) {
     if ((state_in_dev == nullptr) == (k0 == 0)) return CMPS_OK;
     return fail(h, CMPS_ERR_BAD_ARG, std::string(who) + ": state_in_dev is NULL exactly at the start of a stream (k0 == 0)");
 }
+// What cmps_{psi,rho,bank}_stream check behind their state check, and the launch record of the call (`rec`: floats of one state record).
+// The caller brings what a bank changes: the rule for the row counts, with the noise's rows, and the member strides.
 static int stream_args(cmps_handle_t h, const char* who, const void* state_in_dev, void* state_out_dev, int k0, const float* audio_dev, int n_audio,
-                       int forced, const float* noise_dev, int length, int n, float* out_dev, float* pred_dev, int rec, StreamDev& ST, SampleDev& S) {
+                       int forced, const float* noise_dev, int n_noise, int length, int n, float* out_dev, float* pred_dev, int rec, RowRule rows,
+                       const MemberDev& MB, StreamCall& C) {
     const std::string w(who);
     if (n < 1 || forced < 0 || length < 0 || (long long)forced + length < 1 || k0 < 0)
         return fail(h, CMPS_ERR_BAD_ARG, w + ": need n >= 1, forced >= 0, length >= 0, forced + length >= 1 and k0 >= 0");
     if (int c = stream_check_state(h, who, state_in_dev, k0)) return c;
     if (forced > 0 && !audio_dev) return fail(h, CMPS_ERR_BAD_ARG, w + ": forced > 0 needs audio_dev");
     if (length > 0 && (!noise_dev || !out_dev)) return fail(h, CMPS_ERR_BAD_ARG, w + ": length > 0 needs noise_dev and out_dev");
-    if (int c = sample_check_clips(h, who, "n_audio", n_audio, n)) return c;
+    if (int c = rows(h, who, n_audio, length > 0 ? n_noise : n, n, (long long)forced + length)) return c;
     if (int c = sample_check_rows(h, who, "k0 + forced + length + 1", (long long)k0 + forced + length)) return c;
-    ST = StreamDev{static_cast<const float*>(state_in_dev), static_cast<float*>(state_out_dev), k0, rec};
-    S = SampleDev{noise_dev, n, length, out_dev, PrimeDev{audio_dev, n_audio == 1 ? 0 : forced + 1, forced, pred_dev}, &ST, nullptr};
+    C.ST = StreamDev{static_cast<const float*>(state_in_dev), static_cast<float*>(state_out_dev), k0, rec};
+    C.S = SampleDev{noise_dev, n, length, out_dev, PrimeDev{audio_dev, n_audio == 1 ? 0 : forced + 1, forced, pred_dev}, &C.ST, nullptr, MB};
+    return CMPS_OK;
+}
+// The same for the three *_stream_score entries, whose every step is forced: `per` ends the sentence on what loss_dev holds one value for
+static int score_args(cmps_handle_t h, const char* who, const void* state_in_dev, void* state_out_dev, int k0, const float* audio_dev, int n_audio,
+                      int forced, int n, float* nll_dev, float* loss_dev, float* pred_dev, int rec, const char* per, RowRule rows,
+                      const MemberDev& MB, StreamCall& C) {
+    const std::string w(who);
+    if (n < 1 || forced < 1 || k0 < 0) return fail(h, CMPS_ERR_BAD_ARG, w + ": need n >= 1, forced >= 1 and k0 >= 0");
+    if (int c = stream_check_state(h, who, state_in_dev, k0)) return c;
+    if (!audio_dev) return fail(h, CMPS_ERR_BAD_ARG, w + ": needs audio_dev");
+    if (!loss_dev) return fail(h, CMPS_ERR_BAD_ARG, w + ": needs loss_dev (the running loss per " + per + ")");
+    if (int c = rows(h, who, n_audio, n, n, forced)) return c;
+    if (int c = sample_check_rows(h, who, "k0 + forced + 1", (long long)k0 + forced)) return c;
+    C.ST = StreamDev{static_cast<const float*>(state_in_dev), static_cast<float*>(state_out_dev), k0, rec};
+    C.SC = ScoreDev{nll_dev, loss_dev};
+    C.S = SampleDev{nullptr, n, 0, nullptr, PrimeDev{audio_dev, n_audio == 1 ? 0 : forced + 1, forced, pred_dev}, &C.ST, &C.SC, MB};
     return CMPS_OK;
 }
 // The kernel choice and the launch of one SampleDev
@@ -836,12 +872,11 @@ int cmps_psi_stream(cmps_handle_t h, const void* state_in_dev, void* state_out_d
     if (const int rc = check_not_bank(h, "cmps_psi_stream")) return rc;
     if (!h->params_set || h->legacy)
         return fail(h, CMPS_ERR_STATE, "cmps_psi_stream: call cmps_set_params first (not available in legacy mode)");
-    StreamDev ST;
-    SampleDev S;
-    if (int c = stream_args(h, "cmps_psi_stream", state_in_dev, state_out_dev, k0, audio_dev, n_audio, forced, noise_dev, length, n, out_dev, pred_dev,
-                            stream_rec_floats(h), ST, S))
+    StreamCall C;
+    if (int c = stream_args(h, "cmps_psi_stream", state_in_dev, state_out_dev, k0, audio_dev, n_audio, forced, noise_dev, n, length, n, out_dev, pred_dev,
+                            stream_rec_floats(h), plain_rows, MemberDev{}, C))
         return c;
-    return psi_sample_launch(h, "cmps_psi_stream", S, stream);
+    return psi_sample_launch(h, "cmps_psi_stream", C.S, stream);
 }
 
 int cmps_psi_stream_score(cmps_handle_t h, const void* state_in_dev, void* state_out_dev, int k0, const float* audio_dev, int n_audio, int forced,
@@ -850,16 +885,11 @@ int cmps_psi_stream_score(cmps_handle_t h, const void* state_in_dev, void* state
     if (const int rc = check_not_bank(h, "cmps_psi_stream_score")) return rc;
     if (!h->params_set || h->legacy)
         return fail(h, CMPS_ERR_STATE, "cmps_psi_stream_score: call cmps_set_params first (not available in legacy mode)");
-    if (n < 1 || forced < 1 || k0 < 0) return fail(h, CMPS_ERR_BAD_ARG, "cmps_psi_stream_score: need n >= 1, forced >= 1 and k0 >= 0");
-    if (int c = stream_check_state(h, "cmps_psi_stream_score", state_in_dev, k0)) return c;
-    if (!audio_dev) return fail(h, CMPS_ERR_BAD_ARG, "cmps_psi_stream_score: needs audio_dev");
-    if (!loss_dev) return fail(h, CMPS_ERR_BAD_ARG, "cmps_psi_stream_score: needs loss_dev (the running loss per path)");
-    if (int c = sample_check_clips(h, "cmps_psi_stream_score", "n_audio", n_audio, n)) return c;
-    if (int c = sample_check_rows(h, "cmps_psi_stream_score", "k0 + forced + 1", (long long)k0 + forced)) return c;
-    const StreamDev ST{static_cast<const float*>(state_in_dev), static_cast<float*>(state_out_dev), k0, stream_rec_floats(h)};
-    const ScoreDev SC{nll_dev, loss_dev};
-    const PrimeDev PR{audio_dev, n_audio == 1 ? 0 : forced + 1, forced, pred_dev};
-    return psi_sample_launch(h, "cmps_psi_stream_score", SampleDev{nullptr, n, 0, nullptr, PR, &ST, &SC}, stream);   // (every step is forced)
+    StreamCall C;
+    if (int c = score_args(h, "cmps_psi_stream_score", state_in_dev, state_out_dev, k0, audio_dev, n_audio, forced, n, nll_dev, loss_dev, pred_dev,
+                           stream_rec_floats(h), "path", plain_rows, MemberDev{}, C))
+        return c;
+    return psi_sample_launch(h, "cmps_psi_stream_score", C.S, stream);
 }
 
 // ---- a bank's streams: the STREAM / SCORE instances with the members as a second grid dimension (include/cmps.h) ----
@@ -872,16 +902,16 @@ static int bank_stream_check_mode(cmps_handle_t h, const char* who) {
         return fail(h, CMPS_ERR_STATE, std::string(who) + ": a bank samples with the wave and block kernels only");
     return CMPS_OK;
 }
-// rows of an array a bank's members may share: `choices` names the allowed counts in the caller's terms
-static int bank_check_rows(cmps_handle_t h, const char* who, const char* name, const char* choices, long long rows, bool shared_ok, int n) {
+// The RowRule of a bank's streams: arrays the members may share, then M n `steps` (= forced + length): every index into the caller's
+// arrays fits 31 bits (n >= 1 and steps >= 1 are checked before)
+static int bank_rows(cmps_handle_t h, const char* who, int n_audio, int n_noise, int n, long long steps) {
+    const std::string w(who);
     const long long Mn = (long long)h->bank_M * n;
-    if ((shared_ok && rows == 1) || rows == n || rows == Mn) return CMPS_OK;
-    return fail(h, CMPS_ERR_BAD_ARG, std::string(who) + ": " + name + " must be " + choices);
-}
-// M n (forced + length): every index into the caller's arrays fits 31 bits (n >= 1, forced + length >= 1 checked)
-static int bank_check_extent(cmps_handle_t h, const char* who, int n, long long steps) {
-    if ((unsigned long long)h->bank_M * (unsigned long long)n * (unsigned long long)steps <= 0x7fffffffull) return CMPS_OK;
-    return fail(h, CMPS_ERR_BAD_ARG, std::string(who) + ": M * n * (forced + length) exceeds 2^31 - 1");
+    if (n_audio != 1 && n_audio != n && n_audio != Mn)
+        return fail(h, CMPS_ERR_BAD_ARG, w + ": n_audio must be 1 (one signal for every path of every member), n (shared by the members) or M * n");
+    if (n_noise != n && n_noise != Mn) return fail(h, CMPS_ERR_BAD_ARG, w + ": n_noise must be n (every member hears the same noise) or M * n");
+    if ((unsigned long long)Mn * (unsigned long long)steps > 0x7fffffffull) return fail(h, CMPS_ERR_BAD_ARG, w + ": M * n * (forced + length) exceeds 2^31 - 1");
+    return CMPS_OK;
 }
 // floats between two members' rows of an array with `rows` rows of `row` floats (1 or n rows: shared, 0)
 static size_t bank_member_stride(const cmps_handle_s* h, long long rows, int n, size_t row) {
@@ -898,23 +928,13 @@ int cmps_bank_stream(cmps_handle_t h, const void* state_in_dev, void* state_out_
     const char* who = "cmps_bank_stream";
     if (!h) return CMPS_ERR_BAD_ARG;
     if (const int rc = bank_stream_check_mode(h, who)) return rc;
-    const std::string w(who);
-    if (n < 1 || forced < 0 || length < 0 || (long long)forced + length < 1 || k0 < 0)
-        return fail(h, CMPS_ERR_BAD_ARG, w + ": need n >= 1, forced >= 0, length >= 0, forced + length >= 1 and k0 >= 0");
-    if (int c = stream_check_state(h, who, state_in_dev, k0)) return c;
-    if (forced > 0 && !audio_dev) return fail(h, CMPS_ERR_BAD_ARG, w + ": forced > 0 needs audio_dev");
-    if (length > 0 && (!noise_dev || !out_dev)) return fail(h, CMPS_ERR_BAD_ARG, w + ": length > 0 needs noise_dev and out_dev");
-    if (int c = bank_check_rows(h, who, "n_audio", "1 (one signal for every path of every member), n (shared by the members) or M * n", n_audio, true, n))
+    const MemberDev MB{h->bank_M, audio_dev ? bank_member_stride(h, n_audio, n, (size_t)forced + 1) : 0,
+                       length > 0 ? bank_member_stride(h, n_noise, n, (size_t)length) : 0};
+    StreamCall C;
+    if (int c = stream_args(h, who, state_in_dev, state_out_dev, k0, audio_dev, n_audio, forced, noise_dev, n_noise, length, n, out_dev, pred_dev,
+                            stream_rec_floats(h), bank_rows, MB, C))
         return c;
-    if (length > 0)
-        if (int c = bank_check_rows(h, who, "n_noise", "n (every member hears the same noise) or M * n", n_noise, false, n)) return c;
-    if (int c = bank_check_extent(h, who, n, (long long)forced + length)) return c;
-    if (int c = sample_check_rows(h, who, "k0 + forced + length + 1", (long long)k0 + forced + length)) return c;
-    const StreamDev ST{static_cast<const float*>(state_in_dev), static_cast<float*>(state_out_dev), k0, stream_rec_floats(h)};
-    SampleDev S{noise_dev, n, length, out_dev, PrimeDev{audio_dev, n_audio == 1 ? 0 : forced + 1, forced, pred_dev}, &ST, nullptr};
-    S.MB = MemberDev{h->bank_M, audio_dev ? bank_member_stride(h, n_audio, n, (size_t)forced + 1) : 0,
-                     length > 0 ? bank_member_stride(h, n_noise, n, (size_t)length) : 0};
-    return psi_sample_launch(h, who, S, stream);
+    return psi_sample_launch(h, who, C.S, stream);
 }
 
 int cmps_bank_stream_score(cmps_handle_t h, const void* state_in_dev, void* state_out_dev, int k0, const float* audio_dev, int n_audio, int forced,
@@ -922,20 +942,12 @@ int cmps_bank_stream_score(cmps_handle_t h, const void* state_in_dev, void* stat
     const char* who = "cmps_bank_stream_score";
     if (!h) return CMPS_ERR_BAD_ARG;
     if (const int rc = bank_stream_check_mode(h, who)) return rc;
-    const std::string w(who);
-    if (n < 1 || forced < 1 || k0 < 0) return fail(h, CMPS_ERR_BAD_ARG, w + ": need n >= 1, forced >= 1 and k0 >= 0");
-    if (int c = stream_check_state(h, who, state_in_dev, k0)) return c;
-    if (!audio_dev) return fail(h, CMPS_ERR_BAD_ARG, w + ": needs audio_dev");
-    if (!loss_dev) return fail(h, CMPS_ERR_BAD_ARG, w + ": needs loss_dev (the running loss per member and path)");
-    if (int c = bank_check_rows(h, who, "n_audio", "1 (one signal for every path of every member), n (shared by the members) or M * n", n_audio, true, n))
+    StreamCall C;
+    if (int c = score_args(h, who, state_in_dev, state_out_dev, k0, audio_dev, n_audio, forced, n, nll_dev, loss_dev, pred_dev, stream_rec_floats(h),
+                           "member and path", bank_rows,
+                           MemberDev{h->bank_M, bank_member_stride(h, n_audio, n, (size_t)forced + 1), 0}, C))
         return c;
-    if (int c = bank_check_extent(h, who, n, forced)) return c;
-    if (int c = sample_check_rows(h, who, "k0 + forced + 1", (long long)k0 + forced)) return c;
-    const StreamDev ST{static_cast<const float*>(state_in_dev), static_cast<float*>(state_out_dev), k0, stream_rec_floats(h)};
-    const ScoreDev SC{nll_dev, loss_dev};
-    SampleDev S{nullptr, n, 0, nullptr, PrimeDev{audio_dev, n_audio == 1 ? 0 : forced + 1, forced, pred_dev}, &ST, &SC};   // (every step is forced)
-    S.MB = MemberDev{h->bank_M, bank_member_stride(h, n_audio, n, (size_t)forced + 1), 0};
-    return psi_sample_launch(h, who, S, stream);
+    return psi_sample_launch(h, who, C.S, stream);
 }
 
 // The samplers' noise drawn on the device: needs nothing of the handle but its error string and its kernel-event record
@@ -1263,14 +1275,12 @@ int cmps_rho_bank_set_state_dev(cmps_handle_t h, int M, const float* params_dev,
     if (!workspace_dev) return fail(h, CMPS_ERR_WORKSPACE, w + ": null workspace");
     const int rflags = flags & ~(CMPS_WS_FRESH | CMPS_WS_REUSE_TABLES);
     const RhoLayout RL = make_rho_layout(h->D, rank, B_max, T, rflags);
-    const size_t DD = (size_t)h->D * h->D, D = (size_t)h->D;
     // every member's tables (the main layout without its training sections), the size and alignment checks of the whole workspace
-    if (const int rc = set_params_impl(h, params_dev, params_dev + DD, params_dev + 2 * DD, params_dev + 2 * DD + D, params_dev + 2 * DD + 2 * D,
-                                       0.f, params_dev + 2 * DD + 3 * D, sigma, delta_t, T, B_max, flags & ~CMPS_WS_TRAIN, workspace_dev,
-                                       workspace_bytes, stream, M, RL.total)) return rc;
+    if (const int rc = set_params_packed(h, params_dev, sigma, delta_t, T, B_max, flags & ~CMPS_WS_TRAIN, workspace_dev, workspace_bytes, stream, M,
+                                         RL.total)) return rc;
     // member 0's rho sections lie behind its main layout; rho_bank_view / bank_view / bank_view_phi move them by the one stride
     const RhoDev W = bind_rho_workspace(h->D, RL, h->ws + h->L.total, rflags, B_max);
-    const hipError_t e = launch_pack_phi(h->P, W, phi_dev, phi_dev + (size_t)rank * D, static_cast<hipStream_t>(stream), M);
+    const hipError_t e = launch_pack_phi(h->P, W, phi_dev, phi_dev + (size_t)rank * h->D, static_cast<hipStream_t>(stream), M);
     if (e != hipSuccess) { h->params_set = false; return fail_hip(h, e, who); }
     h->RL = RL; h->W = W;
     h->rho_B = B_max; h->rho_T = T; h->rho_flags = rflags;
@@ -1290,7 +1300,7 @@ int cmps_rho_bank_loss_fwd(cmps_handle_t h, const float* audio_dev, int n_audio,
     if (n_audio != 1 && n_audio != M) return fail(h, CMPS_ERR_BAD_ARG, std::string(who) + ": n_audio must be 1 (one shared batch) or M");
     Dev P = h->P;
     P.B = B;
-    P.bank_audio = n_audio == 1 ? 0 : (size_t)B * T; P.bank_loss = (size_t)B;
+    bank_strides(P, n_audio, B, T);
     const bool save = save_for_bwd != 0;
     const bool mfma = h->W.rank > (save ? 2 : 8);                  // as cmps_rho_loss_fwd chooses with the virtual-clip reverse sweep
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -1317,8 +1327,7 @@ int cmps_rho_bank_loss_bwd(cmps_handle_t h, const float* audio_dev, int n_audio,
     const int M = h->bank_M, rank = h->W.rank;
     Dev P = h->P;
     P.B = B;
-    P.bank_audio = n_audio == 1 ? 0 : (size_t)B * T; P.bank_loss = (size_t)B;
-    P.bank_grad = 2 * (size_t)h->D * h->D + 3 * (size_t)h->D + 2 + 2 * (size_t)rank * h->D;
+    bank_strides(P, n_audio, B, T, 2 * (size_t)h->D * h->D + 3 * (size_t)h->D + 2 + 2 * (size_t)rank * h->D);
     KBind kb(h);
     // (a saved bank forward wrote RHO_STASH_MFMA rows: rank >= 3)
     const hipError_t e = launch_bwd_rho_virtual_wave(P, rho_dev(h), audio_dev, h->rho.loss, grad_dev, wave_rank1(h->rank1_mode), h->bwd_waves,
@@ -1336,17 +1345,13 @@ int cmps_rho_bank_apply_step(cmps_handle_t h, int M, float* vars_dev, float* ada
                              const double* hyper_dev, int with_reg, float* params_dev, float* phi_dev, float* losses_dev, void* scratch_dev,
                              void* stream) {
     const char* who = "cmps_rho_bank_apply_step";
-    const std::string w(who);
     if (!h) return CMPS_ERR_BAD_ARG;
-    if (!rho_bank_shape_ok(h->D, rank)) return fail(h, CMPS_ERR_UNSUPPORTED_D, w + ": a RhoCMPS bank needs D <= 32 and 3 <= rank <= 32");
+    if (!rho_bank_shape_ok(h->D, rank)) return fail(h, CMPS_ERR_UNSUPPORTED_D, std::string(who) + ": a RhoCMPS bank needs D <= 32 and 3 <= rank <= 32");
     if (!vars_dev || !params_dev || !phi_dev || !hyper_dev)
-        return fail(h, CMPS_ERR_BAD_ARG, w + ": null variable / parameter / column / hyper-parameter buffer");
+        return fail(h, CMPS_ERR_BAD_ARG, std::string(who) + ": null variable / parameter / column / hyper-parameter buffer");
     if (const int rc = bank_check_M(h, who, M)) return rc;
+    if (const int rc = check_apply_step(h, who, grad_sums_dev, adam_m_dev, adam_v_dev, losses_dev, scratch_dev, global_batch, hyper_dev)) return rc;
     const bool apply = grad_sums_dev != nullptr;
-    if (apply && (!adam_m_dev || !adam_v_dev || !losses_dev || !scratch_dev || !(global_batch > 0.0)))
-        return fail(h, CMPS_ERR_BAD_ARG, w + ": an update needs the Adam slots, losses_dev, scratch_dev and a positive batch");
-    if (((uintptr_t)scratch_dev & 7) != 0) return fail(h, CMPS_ERR_BAD_ARG, w + ": scratch_dev must be 8-byte aligned");
-    if (((uintptr_t)hyper_dev & 7) != 0) return fail(h, CMPS_ERR_BAD_ARG, w + ": hyper_dev must be 8-byte aligned");
     const hipError_t e = launch_rho_bank_apply_step(h->D, rank, M, apply, apply ? 1.0 / global_batch : 0.0, bias_num, bias_den, beta1, beta2,
                                                     epsilon, hyper_dev, with_reg != 0, vars_dev, adam_m_dev, adam_v_dev, grad_sums_dev,
                                                     params_dev, phi_dev, losses_dev, static_cast<double*>(scratch_dev),
@@ -1434,12 +1439,11 @@ int cmps_rho_stream(cmps_handle_t h, const void* state_in_dev, void* state_out_d
     if (!h) return CMPS_ERR_BAD_ARG;
     if (!h->params_set || h->legacy || !h->rho_set)
         return fail(h, CMPS_ERR_STATE, "cmps_rho_stream: call cmps_set_params and cmps_rho_set_state first (not available in legacy mode)");
-    StreamDev ST;
-    SampleDev S;
-    if (int c = stream_args(h, "cmps_rho_stream", state_in_dev, state_out_dev, k0, audio_dev, n_audio, forced, noise_dev, length, n, out_dev, pred_dev,
-                            rho_stream_rec_floats(h), ST, S))
+    StreamCall C;
+    if (int c = stream_args(h, "cmps_rho_stream", state_in_dev, state_out_dev, k0, audio_dev, n_audio, forced, noise_dev, n, length, n, out_dev, pred_dev,
+                            rho_stream_rec_floats(h), plain_rows, MemberDev{}, C))
         return c;
-    return rho_sample_run(h, "cmps_rho_stream", S, save_states, stream);
+    return rho_sample_run(h, "cmps_rho_stream", C.S, save_states, stream);
 }
 
 int cmps_rho_stream_score(cmps_handle_t h, const void* state_in_dev, void* state_out_dev, int k0, const float* audio_dev, int n_audio, int forced,
@@ -1447,16 +1451,11 @@ int cmps_rho_stream_score(cmps_handle_t h, const void* state_in_dev, void* state
     if (!h) return CMPS_ERR_BAD_ARG;
     if (!h->params_set || h->legacy || !h->rho_set)
         return fail(h, CMPS_ERR_STATE, "cmps_rho_stream_score: call cmps_set_params and cmps_rho_set_state first (not available in legacy mode)");
-    if (n < 1 || forced < 1 || k0 < 0) return fail(h, CMPS_ERR_BAD_ARG, "cmps_rho_stream_score: need n >= 1, forced >= 1 and k0 >= 0");
-    if (int c = stream_check_state(h, "cmps_rho_stream_score", state_in_dev, k0)) return c;
-    if (!audio_dev) return fail(h, CMPS_ERR_BAD_ARG, "cmps_rho_stream_score: needs audio_dev");
-    if (!loss_dev) return fail(h, CMPS_ERR_BAD_ARG, "cmps_rho_stream_score: needs loss_dev (the running loss per path)");
-    if (int c = sample_check_clips(h, "cmps_rho_stream_score", "n_audio", n_audio, n)) return c;
-    if (int c = sample_check_rows(h, "cmps_rho_stream_score", "k0 + forced + 1", (long long)k0 + forced)) return c;
-    const StreamDev ST{static_cast<const float*>(state_in_dev), static_cast<float*>(state_out_dev), k0, rho_stream_rec_floats(h)};
-    const ScoreDev SC{nll_dev, loss_dev};
-    const PrimeDev PR{audio_dev, n_audio == 1 ? 0 : forced + 1, forced, pred_dev};
-    return rho_sample_run(h, "cmps_rho_stream_score", SampleDev{nullptr, n, 0, nullptr, PR, &ST, &SC}, save_states, stream);   // (every step is forced)
+    StreamCall C;
+    if (int c = score_args(h, "cmps_rho_stream_score", state_in_dev, state_out_dev, k0, audio_dev, n_audio, forced, n, nll_dev, loss_dev, pred_dev,
+                           rho_stream_rec_floats(h), "path", plain_rows, MemberDev{}, C))
+        return c;
+    return rho_sample_run(h, "cmps_rho_stream_score", C.S, save_states, stream);
 }
 
 int cmps_rho_states(cmps_handle_t h, int B, int steps, float* rho_out_dev, float* purity_out_dev, void* stream) {

@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+from dataclasses import dataclass
 from typing import NamedTuple, Optional
 
 import numpy as np
@@ -37,6 +38,25 @@ class NoisePlan(NamedTuple):
     std: float
 
 
+def _ptr(t: Optional[torch.Tensor]):
+    """The address of a device tensor as an entry takes it: NULL for None and for a tensor without elements."""
+    return t.data_ptr() if t is not None and t.numel() else None
+
+
+BANK_SETTER = {"bank": "bank_set_params_dev", "rho_bank": "rho_bank_set_state_dev"}      # kind of a bank -> the method that configures it
+
+
+@dataclass
+class _Bank:
+    """The bank a HipScan holds (``kind`` None: none).  Every set_params* replaces it, so what a mode kept alive goes with the mode."""
+    kind: Optional[str] = None                # a key of BANK_SETTER
+    M: int = 0
+    rank: int = 0                             # columns of every member's rho_0 ("rho_bank"; else 0)
+    saved: Optional[tuple] = None             # the last forward's (audio, loss, n_audio): the reverse pass reads both tensors
+    params: Optional[torch.Tensor] = None     # the rows bank_set_params uploaded: the scans read A from them
+    scratch: Optional[torch.Tensor] = None    # of the apply-step entries; sized by (D, rank, M) alone, so it is handed on from mode to mode
+
+
 class HipScan:
     """The MI355X backend: per-clip loss and parameter-gradient sums for a batch resident on the GPU."""
 
@@ -60,7 +80,8 @@ class HipScan:
             self.set_rank1(rank1)
         if os.environ.get("CMPS_BWD_WAVES"):            # diagnostic (like CMPS_LIB): A/B of the one- and two-wave reverse scans without code changes
             _capi.check(self._h, self._lib.cmps_set_option(self._h, _capi.CMPS_OPT_BWD_WAVES, int(os.environ["CMPS_BWD_WAVES"])))
-        self._mode = "psi"            # which arithmetic the handle was last configured for: set_params* -> "psi", legacy_set_params -> "legacy"
+        self._mode = "psi"            # which arithmetic the handle was last configured for: set_params* -> "psi", legacy_set_params -> "legacy",
+        self._bank = _Bank()          # the bank setters -> their kind, with the bank's record (`_configured`)
         self._ws = {"main": None, "rho": None}        # caller-owned workspaces of the C ABI, keyed by the shape they were sized for
         self._ws_key = {"main": None, "rho": None}
         self._ws_fresh = False        # the main workspace was (re)allocated since the last set_params*: its cached tables are gone
@@ -154,30 +175,47 @@ class HipScan:
     def workspace_bytes(self, B: int, T: int, train: bool) -> int:
         return int(self._lib.cmps_workspace_bytes(self.D, B, T, self._ws_flags(train)))
 
-    def _workspace(self, B: int, T: int, train: bool, rank: Optional[int] = None):
-        """(256-byte aligned address, usable bytes) of the main workspace (rank None) or of the rho workspace of `rank` columns,
-        (re)allocated when the shape it was sized for changes."""
-        which, key = ("main" if rank is None else "rho"), (rank, B, T, train)
+    def _alloc(self, which: str, key: tuple, sized):
+        """(256-byte aligned address, usable bytes) of workspace `which` ("main" / "rho"), (re)allocated when `key`, the kind and shape it
+        was sized for, changes.  Only then is `sized()` asked for (the bytes the C ABI wants, what they are for): 0 bytes is the ABI's
+        answer to an invalid shape."""
         if self._ws_key[which] != key:
-            nbytes = self.workspace_bytes(B, T, train) if rank is None else \
-                int(self._lib.cmps_rho_workspace_bytes(self.D, rank, B, T, self._ws_flags(train)))
+            nbytes, what = sized()
             if nbytes == 0:
-                what = "scan" if rank is None else f"rho scan (rank={rank})"
-                raise ValueError(f"invalid shape for the {what}: D={self.D}, B={B}, T={T}")
+                raise ValueError(f"invalid shape for {what}")
             self._ws[which] = None        # (free before allocating)
             self._ws[which] = torch.empty(nbytes + 256, dtype=torch.uint8, device=self.device)
             self._ws_key[which] = key
-            if rank is None:
+            if which == "main":
                 self._ws_fresh = True     # the allocator may hand back the old address: the cached tables are gone
         ws = self._ws[which]
         return (ws.data_ptr() + 255) // 256 * 256, ws.numel() - 256
 
-    def _psi_workspace(self, B: int, T: int, train: bool):
-        """set_params*: (flags, address, bytes) of the main workspace, as the C ABI takes them."""
-        ws_ptr, ws_bytes = self._workspace(B, T, train)
-        flags = self._ws_flags(train, self._ws_fresh)
+    def _main_workspace(self, key: tuple, sized, reuse: bool = True):
+        """set_params* and the bank setters: (flags, address, bytes) of the main workspace, as the C ABI takes them.  `key` ends with the
+        train flag.  A reallocated workspace is fresh; one this object has not touched since its last set_params* reuses its tables.
+        reuse=False (legacy_set_params, which rebuilds every table): fresh flags, and a reallocation stays noted for the next set_params*."""
+        ws_ptr, ws_bytes = self._alloc("main", key, sized)
+        if not reuse:
+            return self._ws_flags(key[-1]), ws_ptr, ws_bytes
+        flags = self._ws_flags(key[-1], self._ws_fresh)
         self._ws_fresh = False
         return flags, ws_ptr, ws_bytes
+
+    def _psi_workspace(self, B: int, T: int, train: bool, reuse: bool = True):
+        """set_params* of one model: (flags, address, bytes) of the main workspace, as the C ABI takes them."""
+        return self._main_workspace((None, B, T, train), lambda: (self.workspace_bytes(B, T, train), f"the scan: D={self.D}, B={B}, T={T}"), reuse)
+
+    def _rho_workspace(self, B: int, T: int, train: bool, rank: int):
+        """rho_set_state*: (address, bytes) of the rho workspace of `rank` columns."""
+        return self._alloc("rho", (rank, B, T, train), lambda: (int(self._lib.cmps_rho_workspace_bytes(self.D, rank, B, T, self._ws_flags(train))),
+                                                                f"the rho scan (rank={rank}): D={self.D}, B={B}, T={T}"))
+
+    def _configured(self, B: int, T: int, mode: str, M: int = 0, rank: int = 0):
+        """What every set_params* ends with: the shape and the arithmetic the handle now holds, and the record of the bank it holds (M
+        members; none outside the bank modes).  The batch and the parameter rows a mode kept alive are released when it is left."""
+        self._B, self._T, self._mode = B, T, mode
+        self._bank = _Bank(mode if M else None, M, rank, scratch=self._bank.scratch)
 
     def _upload(self, fields, values):
         """Pack `values` as the layout `fields` -> (device tensor, address of every field)."""
@@ -200,7 +238,7 @@ class HipScan:
         _capi.check(self._h, self._lib.cmps_set_params(
             self._h, *layout.pointers(self._param_buf.data_ptr(), fields), float(p.A), float(p.sigma), float(p.delta_t), int(T), int(B),
             *self._psi_workspace(B, T, train), self._stream()))
-        self._B, self._T, self._mode = B, T, "psi"
+        self._configured(B, T, "psi")
 
     def set_params_dev(self, params: torch.Tensor, sigma: float, delta_t: float, B: int, T: int, train: bool = True):
         """cmps_set_params_dev: the effective parameters (A included) are read from the device buffer `params`
@@ -209,7 +247,7 @@ class HipScan:
             raise ValueError("params must be a float32 CUDA tensor of 2 D^2 + 3 D + 1 elements")
         _capi.check(self._h, self._lib.cmps_set_params_dev(self._h, params.data_ptr(), float(sigma), float(delta_t), int(T), int(B),
                                                            *self._psi_workspace(B, T, train), self._stream()))
-        self._B, self._T, self._mode = B, T, "psi"
+        self._configured(B, T, "psi")
 
     def apply_step(self, vars_: torch.Tensor, m: torch.Tensor, v: torch.Tensor, grad_sums: Optional[torch.Tensor], global_batch: int,
                    lr_t: float, beta1: float, beta2: float, eps: float, h_reg: float, r_reg: float, c_r: float, c_h: float,
@@ -254,27 +292,21 @@ class HipScan:
                 and params.is_contiguous()):
             raise ValueError("params must be a contiguous float32 CUDA tensor [M, 2 D^2 + 3 D + 1]")
         M = int(params.shape[0])
-        key = ("bank", M, B, T, train)
-        if self._ws_key["main"] != key:
-            nbytes = self.bank_workspace_bytes(M, B, T, train)
-            if nbytes == 0:
-                raise ValueError(f"invalid shape for a bank: D={self.D}, M={M}, B={B}, T={T}")
-            self._ws["main"] = None
-            self._ws["main"] = torch.empty(nbytes + 256, dtype=torch.uint8, device=self.device)
-            self._ws_key["main"] = key
-            self._ws_fresh = True
-        ws = self._ws["main"]
-        flags = self._ws_flags(train, self._ws_fresh)
-        self._ws_fresh = False
-        _capi.check(self._h, self._lib.cmps_bank_set_params_dev(
-            self._h, M, params.data_ptr(), float(sigma), float(delta_t), int(T), int(B), flags, (ws.data_ptr() + 255) // 256 * 256,
-            ws.numel() - 256, self._stream()))
-        self._B, self._T, self._mode, self._bank_M = B, T, "bank", M
+        ws = self._main_workspace(("bank", M, B, T, train),
+                                  lambda: (self.bank_workspace_bytes(M, B, T, train), f"a bank: D={self.D}, M={M}, B={B}, T={T}"))
+        _capi.check(self._h, self._lib.cmps_bank_set_params_dev(self._h, M, params.data_ptr(), float(sigma), float(delta_t), int(T), int(B), *ws,
+                                                                self._stream()))
+        self._configured(B, T, "bank", M)
 
-    def _bank_audio(self, audio: torch.Tensor):
-        M = getattr(self, "_bank_M", 0)
-        if self._mode != "bank" or not M:
-            raise RuntimeError("bank_forward() needs bank_set_params_dev() first")
+    # The drivers of both kinds of bank (`kind`: a key of BANK_SETTER, also the prefix of the public methods' names)
+    def _bank_of(self, kind: str, what: str) -> _Bank:
+        """The record of the bank of `kind` this handle holds; without one, the RuntimeError of the method `what`."""
+        if self._bank.kind != kind:
+            raise RuntimeError(f"{what}() needs {BANK_SETTER[kind]}() first")
+        return self._bank
+
+    def _bank_audio(self, M: int, audio: torch.Tensor):
+        """A bank's batch [B, T] (shared) or [M, B, T] -> (n_audio, B, T) as the scan entries take them."""
         if not (isinstance(audio, torch.Tensor) and audio.is_cuda and audio.dtype == torch.float32 and audio.dim() in (2, 3)
                 and audio.is_contiguous()):
             raise ValueError("audio must be a contiguous float32 CUDA tensor [B, T] (shared) or [M, B, T]")
@@ -282,49 +314,65 @@ class HipScan:
         B, T = audio.shape[-2:]
         if n_audio not in (1, M) or T != self._T or B > self._B:
             raise ValueError(f"audio shape {tuple(audio.shape)} does not fit the bank (M={M}, B={self._B}, T={self._T})")
-        return M, n_audio, int(B), int(T)
+        return n_audio, int(B), int(T)
+
+    def _bank_forward(self, kind: str, fn, audio: torch.Tensor, save_for_bwd: bool) -> torch.Tensor:
+        """The one forward driver of a bank: `fn` is cmps_{bank,rho_bank}_loss_fwd.  Returns the per-clip losses [M, B]."""
+        bank = self._bank_of(kind, kind + "_forward")
+        n_audio, B, T = self._bank_audio(bank.M, audio)
+        loss = torch.empty((bank.M, B), dtype=torch.float32, device=self.device)
+        _capi.check(self._h, fn(self._h, audio.data_ptr(), n_audio, B, T, loss.data_ptr(), 1 if save_for_bwd else 0, self._stream()))
+        bank.saved = (audio, loss, n_audio)
+        return loss
+
+    def _bank_backward(self, kind: str, fn) -> torch.Tensor:
+        """The one backward driver of a bank: `fn` is cmps_{bank,rho_bank}_loss_bwd.  Returns the gradient sums, one row per member."""
+        bank = self._bank
+        if bank.kind != kind or bank.saved is None:
+            raise RuntimeError(f"{kind}_backward() needs {kind}_forward(save_for_bwd=True) first")
+        audio, _, n_audio = bank.saved
+        B, T = audio.shape[-2:]
+        grad = torch.empty((bank.M, grad_size(self.D, bank.rank)), dtype=torch.float32, device=self.device)
+        _capi.check(self._h, fn(self._h, audio.data_ptr(), n_audio, int(B), int(T), grad.data_ptr(), self._stream()))
+        return grad
+
+    def _bank_apply_step(self, fn, n_scratch: int, vars_, m, v, grad_sums, rank: tuple, global_batch, bias_num, bias_den, beta1, beta2, eps,
+                         hyper, with_reg, outs: tuple):
+        """The one apply-step driver of a bank: `fn` is cmps_{bank,rho_bank}_apply_step, `n_scratch` its scratch bytes, `rank` what it
+        takes behind grad_sums_dev (nothing, or the rank), `outs` the buffers it writes, in its order."""
+        bank = self._bank
+        if bank.scratch is None or bank.scratch.numel() * 8 < n_scratch:
+            bank.scratch = torch.empty((n_scratch + 7) // 8, dtype=torch.float64, device=self.device)
+        _capi.check(self._h, fn(
+            self._h, int(vars_.shape[0]), vars_.data_ptr(), m.data_ptr(), v.data_ptr(), grad_sums.data_ptr() if grad_sums is not None else None,
+            *rank, float(max(global_batch, 1)), float(bias_num), float(bias_den), float(beta1), float(beta2), float(eps), hyper.data_ptr(),
+            1 if with_reg else 0, *(t.data_ptr() for t in outs), bank.scratch.data_ptr(), self._stream()))
+
+    @staticmethod
+    def _check_hyper(hyper: torch.Tensor, M: int):
+        if not (hyper.is_cuda and hyper.dtype == torch.float64 and tuple(hyper.shape) == (M, 5) and hyper.is_contiguous()):
+            raise ValueError("hyper must be a contiguous float64 CUDA tensor [M, 5]")
 
     def bank_forward(self, audio: torch.Tensor, save_for_bwd: bool = False) -> torch.Tensor:
         """cmps_bank_loss_fwd: per-clip losses [M, B] for ``audio`` [B, T] (one batch shared by every member) or [M, B, T]."""
-        M, n_audio, B, T = self._bank_audio(audio)
-        loss = torch.empty((M, B), dtype=torch.float32, device=self.device)
-        _capi.check(self._h, self._lib.cmps_bank_loss_fwd(self._h, audio.data_ptr(), n_audio, B, T, loss.data_ptr(),
-                                                          1 if save_for_bwd else 0, self._stream()))
-        self._bank_saved = (audio, loss, n_audio)        # (kept alive: the reverse pass reads both)
-        return loss
+        return self._bank_forward("bank", self._lib.cmps_bank_loss_fwd, audio, save_for_bwd)
 
     def bank_backward(self) -> torch.Tensor:
         """cmps_bank_loss_bwd after bank_forward(save_for_bwd=True): gradient sums [M, 2 D^2 + 3 D + 2]."""
-        saved = getattr(self, "_bank_saved", None)
-        if saved is None:
-            raise RuntimeError("bank_backward() needs bank_forward(save_for_bwd=True) first")
-        audio, _, n_audio = saved
-        B, T = audio.shape[-2:]
-        grad = torch.empty((self._bank_M, grad_size(self.D)), dtype=torch.float32, device=self.device)
-        _capi.check(self._h, self._lib.cmps_bank_loss_bwd(self._h, audio.data_ptr(), n_audio, int(B), int(T), grad.data_ptr(), self._stream()))
-        return grad
+        return self._bank_backward("bank", self._lib.cmps_bank_loss_bwd)
 
     def bank_apply_step(self, vars_: torch.Tensor, m: torch.Tensor, v: torch.Tensor, grad_sums: Optional[torch.Tensor], global_batch: int,
                         bias_num: float, bias_den: float, beta1: float, beta2: float, eps: float, hyper: torch.Tensor, with_reg: bool,
                         params: torch.Tensor, losses: torch.Tensor):
         """cmps_bank_apply_step: every member's optimiser step; ``hyper`` [M, 5] float64 on the device (learning_rate, h_reg, r_reg, c_r, c_h)."""
         M = int(vars_.shape[0])
-        if not (hyper.is_cuda and hyper.dtype == torch.float64 and tuple(hyper.shape) == (M, 5) and hyper.is_contiguous()):
-            raise ValueError("hyper must be a contiguous float64 CUDA tensor [M, 5]")
-        scratch = getattr(self, "_bank_scratch", None)
-        n = int(self._lib.cmps_bank_apply_step_scratch_bytes(self.D, M))
-        if scratch is None or scratch.numel() * 8 < n:
-            scratch = self._bank_scratch = torch.empty((n + 7) // 8, dtype=torch.float64, device=self.device)
-        _capi.check(self._h, self._lib.cmps_bank_apply_step(
-            self._h, M, vars_.data_ptr(), m.data_ptr(), v.data_ptr(), grad_sums.data_ptr() if grad_sums is not None else None,
-            float(max(global_batch, 1)), float(bias_num), float(bias_den), float(beta1), float(beta2), float(eps), hyper.data_ptr(),
-            1 if with_reg else 0, params.data_ptr(), losses.data_ptr(), scratch.data_ptr(), self._stream()))
+        self._check_hyper(hyper, M)
+        self._bank_apply_step(self._lib.cmps_bank_apply_step, int(self._lib.cmps_bank_apply_step_scratch_bytes(self.D, M)), vars_, m, v,
+                              grad_sums, (), global_batch, bias_num, bias_den, beta1, beta2, eps, hyper, with_reg, (params, losses))
 
     def bank_grad_status(self):
         """cmps_bank_grad_status: (codes [M], sticky flags [M]).  Waits for the stream."""
-        M = getattr(self, "_bank_M", 0)
-        if self._mode != "bank" or not M:
-            raise RuntimeError("bank_grad_status() needs bank_set_params_dev() first")
+        M = self._bank_of("bank", "bank_grad_status").M
         codes, sticky = (ctypes.c_int * M)(), (ctypes.c_int * M)()
         _capi.check(self._h, self._lib.cmps_bank_grad_status(self._h, codes, sticky, self._stream()))
         return [int(c) for c in codes], [int(x) for x in sticky]
@@ -344,77 +392,34 @@ class HipScan:
         M = int(params.shape[0])
         if not (phi.is_cuda and phi.dtype == torch.float32 and tuple(phi.shape) == (M, 2 * rank * self.D) and phi.is_contiguous()):
             raise ValueError("phi must be a contiguous float32 CUDA tensor [M, 2 rank D]")
-        key = ("rho_bank", M, rank, B, T, train)
-        if self._ws_key["main"] != key:
-            nbytes = self.rho_bank_workspace_bytes(rank, M, B, T, train)
-            if nbytes == 0:
-                raise ValueError(f"invalid shape for a RhoCMPS bank: D={self.D}, rank={rank}, M={M}, B={B}, T={T}")
-            self._ws["main"] = None
-            self._ws["main"] = torch.empty(nbytes + 256, dtype=torch.uint8, device=self.device)
-            self._ws_key["main"] = key
-            self._ws_fresh = True
-        ws = self._ws["main"]
-        flags = self._ws_flags(train, self._ws_fresh)
-        self._ws_fresh = False
-        _capi.check(self._h, self._lib.cmps_rho_bank_set_state_dev(
-            self._h, M, params.data_ptr(), phi.data_ptr(), rank, float(sigma), float(delta_t), int(T), int(B), flags,
-            (ws.data_ptr() + 255) // 256 * 256, ws.numel() - 256, self._stream()))
-        self._B, self._T, self._mode, self._bank_M, self._rho_bank_rank = B, T, "rho_bank", M, rank
+        ws = self._main_workspace(("rho_bank", M, rank, B, T, train), lambda: (self.rho_bank_workspace_bytes(rank, M, B, T, train),
+                                                                                f"a RhoCMPS bank: D={self.D}, rank={rank}, M={M}, B={B}, T={T}"))
+        _capi.check(self._h, self._lib.cmps_rho_bank_set_state_dev(self._h, M, params.data_ptr(), phi.data_ptr(), rank, float(sigma), float(delta_t),
+                                                                   int(T), int(B), *ws, self._stream()))
+        self._configured(B, T, "rho_bank", M, rank)
         self._rho_rank = 0            # (the plain rho state is gone: rho_forward() asks for rho_set_state again)
-
-    def _rho_bank_audio(self, audio: torch.Tensor):
-        M = getattr(self, "_bank_M", 0)
-        if self._mode != "rho_bank" or not M:
-            raise RuntimeError("rho_bank_forward() needs rho_bank_set_state_dev() first")
-        if not (isinstance(audio, torch.Tensor) and audio.is_cuda and audio.dtype == torch.float32 and audio.dim() in (2, 3)
-                and audio.is_contiguous()):
-            raise ValueError("audio must be a contiguous float32 CUDA tensor [B, T] (shared) or [M, B, T]")
-        n_audio = 1 if audio.dim() == 2 else int(audio.shape[0])
-        B, T = audio.shape[-2:]
-        if n_audio not in (1, M) or T != self._T or B > self._B:
-            raise ValueError(f"audio shape {tuple(audio.shape)} does not fit the bank (M={M}, B={self._B}, T={self._T})")
-        return M, n_audio, int(B), int(T)
 
     def rho_bank_forward(self, audio: torch.Tensor, save_for_bwd: bool = False) -> torch.Tensor:
         """cmps_rho_bank_loss_fwd: per-clip losses [M, B] for ``audio`` [B, T] (one batch shared by every member) or [M, B, T]."""
-        M, n_audio, B, T = self._rho_bank_audio(audio)
-        loss = torch.empty((M, B), dtype=torch.float32, device=self.device)
-        _capi.check(self._h, self._lib.cmps_rho_bank_loss_fwd(self._h, audio.data_ptr(), n_audio, B, T, loss.data_ptr(),
-                                                              1 if save_for_bwd else 0, self._stream()))
-        self._rho_bank_saved = (audio, loss, n_audio)    # (kept alive: the reverse pass reads both)
-        return loss
+        return self._bank_forward("rho_bank", self._lib.cmps_rho_bank_loss_fwd, audio, save_for_bwd)
 
     def rho_bank_backward(self) -> torch.Tensor:
         """cmps_rho_bank_loss_bwd after rho_bank_forward(save_for_bwd=True): gradient sums [M, 2 D^2 + 3 D + 2 + 2 rank D]."""
-        saved = getattr(self, "_rho_bank_saved", None)
-        if saved is None or self._mode != "rho_bank":
-            raise RuntimeError("rho_bank_backward() needs rho_bank_forward(save_for_bwd=True) first")
-        audio, _, n_audio = saved
-        B, T = audio.shape[-2:]
-        grad = torch.empty((self._bank_M, grad_size(self.D, self._rho_bank_rank)), dtype=torch.float32, device=self.device)
-        _capi.check(self._h, self._lib.cmps_rho_bank_loss_bwd(self._h, audio.data_ptr(), n_audio, int(B), int(T), grad.data_ptr(),
-                                                              self._stream()))
-        return grad
+        return self._bank_backward("rho_bank", self._lib.cmps_rho_bank_loss_bwd)
 
     def rho_bank_apply_step(self, vars_: torch.Tensor, m: torch.Tensor, v: torch.Tensor, grad_sums: Optional[torch.Tensor], rank: int,
                             global_batch: int, bias_num: float, bias_den: float, beta1: float, beta2: float, eps: float,
                             hyper: torch.Tensor, with_reg: bool, params: torch.Tensor, phi: torch.Tensor, losses: torch.Tensor):
         """cmps_rho_bank_apply_step: every member's optimiser step; ``hyper`` [M, 5] float64 on the device as for bank_apply_step."""
         M, rank = int(vars_.shape[0]), int(rank)
-        if not (hyper.is_cuda and hyper.dtype == torch.float64 and tuple(hyper.shape) == (M, 5) and hyper.is_contiguous()):
-            raise ValueError("hyper must be a contiguous float64 CUDA tensor [M, 5]")
+        self._check_hyper(hyper, M)
         if tuple(phi.shape) != (M, 2 * rank * self.D) or tuple(params.shape) != (M, self._n_params + 1):
             raise ValueError("phi must be [M, 2 rank D] and params [M, 2 D^2 + 3 D + 1]")
-        scratch = getattr(self, "_rho_bank_scratch", None)
         n = int(self._lib.cmps_rho_bank_apply_step_scratch_bytes(self.D, rank, M))
         if n == 0:
             raise ValueError(f"invalid shape for a RhoCMPS bank's optimiser step: D={self.D}, rank={rank}, M={M}")
-        if scratch is None or scratch.numel() * 8 < n:
-            scratch = self._rho_bank_scratch = torch.empty((n + 7) // 8, dtype=torch.float64, device=self.device)
-        _capi.check(self._h, self._lib.cmps_rho_bank_apply_step(
-            self._h, M, vars_.data_ptr(), m.data_ptr(), v.data_ptr(), grad_sums.data_ptr() if grad_sums is not None else None, rank,
-            float(max(global_batch, 1)), float(bias_num), float(bias_den), float(beta1), float(beta2), float(eps), hyper.data_ptr(),
-            1 if with_reg else 0, params.data_ptr(), phi.data_ptr(), losses.data_ptr(), scratch.data_ptr(), self._stream()))
+        self._bank_apply_step(self._lib.cmps_rho_bank_apply_step, n, vars_, m, v, grad_sums, (rank,), global_batch, bias_num, bias_den, beta1,
+                              beta2, eps, hyper, with_reg, (params, phi, losses))
 
     def _check_audio(self, audio: torch.Tensor):
         if not (isinstance(audio, torch.Tensor) and audio.is_cuda and audio.dtype == torch.float32
@@ -690,32 +695,48 @@ class HipScan:
                 raise ValueError(f"a stream state must be the tensor stream_state({n}) returned")
         return n
 
+    def _audio_block(self, audio, least: int, rows: Optional[tuple] = None, need: str = ""):
+        """A signal block [n_audio, forced + 1] of at least `least` columns (and, given `rows`, of one of these row counts) -> (device
+        tensor, or None where no step is forced; n_audio; forced).  `need` is how the caller's error message names these conditions."""
+        audio = np.array(audio, dtype=np.float32, order="C")           # (a copy: torch wants a writable array)
+        if audio.ndim != 2 or audio.shape[1] < least or (rows is not None and audio.shape[0] not in rows):
+            raise ValueError("audio must be [n_audio, forced + 1]" + need)
+        forced = audio.shape[1] - 1
+        return (torch.from_numpy(audio).to(self.device) if forced > 0 else None), audio.shape[0], forced
+
+    def _running_loss(self, loss, shape: tuple) -> torch.Tensor:
+        """The running loss of a scored stream on the device: zeros for None, else the host array of `shape`."""
+        if loss is None:
+            return torch.zeros(shape, dtype=torch.float32, device=self.device)
+        loss = np.array(loss, dtype=np.float32, order="C")
+        if loss.shape != shape:
+            raise ValueError(f"loss must be {list(shape)}")
+        return torch.from_numpy(loss).to(self.device)
+
+    def _stream_launch(self, fn, state_in, state_out, k0, block, noise_args, n, length, want_pred, lead, *flags):
+        """One segment behind its checks, for the paths of one model (`lead` = ()) or of every member of a bank ((M,)): (out lead + [n,
+        length], pred lead + [n, forced] or None) down.  `fn` is cmps_{psi,rho,bank}_stream, `block` what `_audio_block` returned,
+        `noise_args` what `fn` takes between forced and n, `flags` what it takes behind pred_dev."""
+        d_audio, n_audio, forced = block
+        d_out = torch.empty(lead + (n, length), dtype=torch.float32, device=self.device)
+        d_pred = torch.empty(lead + (n, forced), dtype=torch.float32, device=self.device) if want_pred else None
+        _capi.check(self._h, fn(self._h, _ptr(state_in), _ptr(state_out), int(k0), _ptr(d_audio), n_audio, forced, *noise_args, n, _ptr(d_out),
+                                _ptr(d_pred), *flags, self._stream()))
+        return d_out.cpu().numpy(), (d_pred.cpu().numpy() if want_pred else None)
+
     def _stream_call(self, fn, bytes_fn, state_in, state_out, k0, audio, noise, want_pred, n, length, *flags):
-        """One segment: the signal block [n_audio, forced + 1] up and the noise in (`_device_noise`; None: no sampled step), (out [n, length],
-        pred [n, forced] or None) down.  `fn` / `bytes_fn` are cmps_{psi,rho}_stream / _stream_state_bytes, `flags` what `fn` takes behind
-        pred_dev."""
-        forced = 0
-        d_audio = d_noise = d_out = d_pred = None
-        n_audio = 1
+        """One segment of one model: the signal block [n_audio, forced + 1] up and the noise in (`_device_noise`; None: no sampled step),
+        (out [n, length], pred [n, forced] or None) down.  `fn` / `bytes_fn` are cmps_{psi,rho}_stream / _stream_state_bytes, `flags` what
+        `fn` takes behind pred_dev."""
+        d_noise, block = None, (None, 1, 0)
         if noise is not None:
             d_noise, length, n = self._device_noise(noise, length, n)
         else:
             length = 0
         if audio is not None:
-            audio = np.array(audio, dtype=np.float32, order="C")       # (a copy: torch wants a writable array)
-            if audio.ndim != 2 or audio.shape[1] < 1:
-                raise ValueError("audio must be [n_audio, forced + 1]")
-            n_audio, forced = audio.shape[0], audio.shape[1] - 1
-        n = self._stream_paths(bytes_fn, state_in, state_out, n, n_audio)
-        if forced > 0:
-            d_audio = torch.from_numpy(audio).to(self.device)
-        d_out = torch.empty((n, length), dtype=torch.float32, device=self.device)
-        if want_pred:
-            d_pred = torch.empty((n, forced), dtype=torch.float32, device=self.device)
-        ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None   # noqa: E731
-        _capi.check(self._h, fn(self._h, ptr(state_in), ptr(state_out), int(k0), ptr(d_audio), n_audio, forced, ptr(d_noise), length, n,
-                                ptr(d_out), ptr(d_pred), *flags, self._stream()))
-        return d_out.cpu().numpy(), (d_pred.cpu().numpy() if want_pred else None)
+            block = self._audio_block(audio, 1)
+        n = self._stream_paths(bytes_fn, state_in, state_out, n, block[1])
+        return self._stream_launch(fn, state_in, state_out, k0, block, (_ptr(d_noise), length), n, length, want_pred, (), *flags)
 
     def stream_state(self, n: int) -> torch.Tensor:
         """Device memory for the stream-state records of ``n`` paths (cmps_psi_stream_state_bytes): opaque bytes, valid for this
@@ -732,29 +753,25 @@ class HipScan:
         return self._stream_call(self._lib.cmps_psi_stream, self._lib.cmps_psi_stream_state_bytes, state_in, state_out, k0, audio, noise,
                                  want_pred, n, length)
 
-    def _stream_score_call(self, fn, bytes_fn, state_in, state_out, k0, audio, want_nll, want_pred, n, loss, *flags):
-        """One scored segment: the signal block [n_audio, forced + 1] and the running loss up, (nll [n, forced] or None, loss [n], pred
-        [n, forced] or None) down.  `fn` / `bytes_fn` are cmps_{psi,rho}_stream_score / _stream_state_bytes, `flags` what `fn` takes
-        behind pred_dev."""
-        audio = np.array(audio, dtype=np.float32, order="C")           # (a copy: torch wants a writable array)
-        if audio.ndim != 2 or audio.shape[1] < 2:
-            raise ValueError("audio must be [n_audio, forced + 1] with forced >= 1")
-        n_audio, forced = audio.shape[0], audio.shape[1] - 1
-        n = self._stream_paths(bytes_fn, state_in, state_out, n, n_audio)
-        if loss is None:
-            d_loss = torch.zeros(n, dtype=torch.float32, device=self.device)
-        else:
-            loss = np.array(loss, dtype=np.float32, order="C")
-            if loss.shape != (n,):
-                raise ValueError(f"loss must be [{n}]")
-            d_loss = torch.from_numpy(loss).to(self.device)
-        d_audio = torch.from_numpy(audio).to(self.device)
-        d_nll = torch.empty((n, forced), dtype=torch.float32, device=self.device) if want_nll else None
-        d_pred = torch.empty((n, forced), dtype=torch.float32, device=self.device) if want_pred else None
-        ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None   # noqa: E731
-        _capi.check(self._h, fn(self._h, ptr(state_in), ptr(state_out), int(k0), ptr(d_audio), n_audio, forced, n, ptr(d_nll), ptr(d_loss),
-                                ptr(d_pred), *flags, self._stream()))
+    def _score_launch(self, fn, state_in, state_out, k0, block, want_nll, want_pred, n, loss, lead, *flags):
+        """One scored segment behind its checks, for the paths of one model (`lead` = ()) or of every member of a bank ((M,)): the running
+        loss up, (nll lead + [n, forced] or None, loss lead + [n], pred lead + [n, forced] or None) down.  `fn` is
+        cmps_{psi,rho,bank}_stream_score, `block` what `_audio_block` returned, `flags` what `fn` takes behind pred_dev."""
+        d_audio, n_audio, forced = block
+        d_loss = self._running_loss(loss, lead + (n,))
+        d_nll = torch.empty(lead + (n, forced), dtype=torch.float32, device=self.device) if want_nll else None
+        d_pred = torch.empty(lead + (n, forced), dtype=torch.float32, device=self.device) if want_pred else None
+        _capi.check(self._h, fn(self._h, _ptr(state_in), _ptr(state_out), int(k0), _ptr(d_audio), n_audio, forced, n, _ptr(d_nll), _ptr(d_loss),
+                                _ptr(d_pred), *flags, self._stream()))
         return (d_nll.cpu().numpy() if want_nll else None), d_loss.cpu().numpy(), (d_pred.cpu().numpy() if want_pred else None)
+
+    def _stream_score_call(self, fn, bytes_fn, state_in, state_out, k0, audio, want_nll, want_pred, n, loss, *flags):
+        """One scored segment of one model: the signal block [n_audio, forced + 1] and the running loss up, (nll [n, forced] or None, loss
+        [n], pred [n, forced] or None) down.  `fn` / `bytes_fn` are cmps_{psi,rho}_stream_score / _stream_state_bytes, `flags` what `fn`
+        takes behind pred_dev."""
+        block = self._audio_block(audio, 2, need=" with forced >= 1")
+        n = self._stream_paths(bytes_fn, state_in, state_out, n, block[1])
+        return self._score_launch(fn, state_in, state_out, k0, block, want_nll, want_pred, n, loss, (), *flags)
 
     def stream_score(self, state_in: Optional[torch.Tensor], state_out: Optional[torch.Tensor], k0: int, audio, want_nll: bool = True,
                      want_pred: bool = False, n: Optional[int] = None, loss=None):
@@ -772,27 +789,14 @@ class HipScan:
         """cmps_bank_set_params_dev from host values: ``members`` is a list of EffectiveParams of one sigma and delta_t (A per member)."""
         fields = layout.param_fields(self.D, with_A=True)
         rows = [layout.pack(fields, {**layout.split("R", p.R), "freqs": p.freqs, **layout.split("psi0", p.psi0), "A": p.A}) for p in members]
-        self._bank_params = torch.from_numpy(np.stack(rows)).to(self.device)           # (kept alive: the scans read A from it)
-        self.bank_set_params_dev(self._bank_params, members[0].sigma, members[0].delta_t, B, T, train=train)
-
-    def _bank_M_or_raise(self, what: str) -> int:
-        M = getattr(self, "_bank_M", 0)
-        if self._mode != "bank" or not M:
-            raise RuntimeError(f"{what}() needs bank_set_params_dev() first")
-        return M
+        params = torch.from_numpy(np.stack(rows)).to(self.device)
+        self.bank_set_params_dev(params, members[0].sigma, members[0].delta_t, B, T, train=train)
+        self._bank.params = params
 
     def bank_stream_state(self, n: int) -> torch.Tensor:
         """Device memory for the stream-state records of ``n`` paths of every member (cmps_bank_stream_state_bytes)."""
-        self._bank_M_or_raise("bank_stream_state")
+        self._bank_of("bank", "bank_stream_state")
         return self._stream_state(self._lib.cmps_bank_stream_state_bytes, n, " (or the handle holds no PsiCMPS bank)")
-
-    def _bank_audio_block(self, audio, M: int, n: int, least: int):
-        """A signal block [n_audio, forced + 1] with n_audio in {1, n, M n} -> (device tensor or None, n_audio, forced)."""
-        audio = np.array(audio, dtype=np.float32, order="C")            # (a copy: torch wants a writable array)
-        if audio.ndim != 2 or audio.shape[1] < least or audio.shape[0] not in (1, n, M * n):
-            raise ValueError(f"audio must be [n_audio, forced + 1] with n_audio in (1, {n}, {M * n}) and forced >= {least - 1}")
-        forced = audio.shape[1] - 1
-        return (torch.from_numpy(audio).to(self.device) if forced > 0 else None), audio.shape[0], forced
 
     def bank_stream(self, state_in: Optional[torch.Tensor], state_out: Optional[torch.Tensor], k0: int, audio, noise, want_pred: bool = False,
                     n: Optional[int] = None, length: Optional[int] = None, n_noise: Optional[int] = None):
@@ -801,10 +805,9 @@ class HipScan:
         tensor [n_noise, length] or a NoisePlan -- drawn by ONE cmps_noise_fill over ``n_noise`` paths from path 0 -- with n_noise = n
         (every member hears the same noise) or M n, or None.  ``n`` is required.  Returns (out [M, n, length], pred [M, n, forced] with
         want_pred, else None)."""
-        M, n = self._bank_M_or_raise("bank_stream"), int(n)
+        M, n = self._bank_of("bank", "bank_stream").M, int(n)
         self._stream_paths(self._lib.cmps_bank_stream_state_bytes, state_in, state_out, n, n)
-        d_audio = d_noise = d_pred = None
-        n_audio, forced, rows = 1, 0, n
+        d_noise, rows, block = None, n, (None, 1, 0)
         if noise is not None:
             if n_noise is None and isinstance(noise, NoisePlan):
                 n_noise = n                                                   # (an array brings its own path count)
@@ -814,36 +817,19 @@ class HipScan:
         else:
             length = 0
         if audio is not None:
-            d_audio, n_audio, forced = self._bank_audio_block(audio, M, n, 1)
-        d_out = torch.empty((M, n, length), dtype=torch.float32, device=self.device)
-        if want_pred:
-            d_pred = torch.empty((M, n, forced), dtype=torch.float32, device=self.device)
-        ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None   # noqa: E731
-        _capi.check(self._h, self._lib.cmps_bank_stream(self._h, ptr(state_in), ptr(state_out), int(k0), ptr(d_audio), n_audio, forced,
-                                                        ptr(d_noise), rows, length, n, ptr(d_out), ptr(d_pred), self._stream()))
-        return d_out.cpu().numpy(), (d_pred.cpu().numpy() if want_pred else None)
+            block = self._audio_block(audio, 1, (1, n, M * n), f" with n_audio in (1, {n}, {M * n}) and forced >= 0")
+        return self._stream_launch(self._lib.cmps_bank_stream, state_in, state_out, k0, block, (_ptr(d_noise), rows, length), n, length, want_pred,
+                                   (M,))
 
     def bank_stream_score(self, state_in: Optional[torch.Tensor], state_out: Optional[torch.Tensor], k0: int, audio, want_nll: bool = True,
                           want_pred: bool = False, n: Optional[int] = None, loss=None):
         """cmps_bank_stream_score: `stream_score` for every member of the bank at once; ``audio`` as in `bank_stream` (forced >= 1), ``loss``
         [M, n] the running loss to continue.  Returns (nll [M, n, forced] with want_nll else None, the running loss [M, n], pred
         [M, n, forced] with want_pred else None)."""
-        M, n = self._bank_M_or_raise("bank_stream_score"), int(n)
+        M, n = self._bank_of("bank", "bank_stream_score").M, int(n)
         self._stream_paths(self._lib.cmps_bank_stream_state_bytes, state_in, state_out, n, n)
-        d_audio, n_audio, forced = self._bank_audio_block(audio, M, n, 2)
-        if loss is None:
-            d_loss = torch.zeros((M, n), dtype=torch.float32, device=self.device)
-        else:
-            loss = np.array(loss, dtype=np.float32, order="C")
-            if loss.shape != (M, n):
-                raise ValueError(f"loss must be [{M}, {n}]")
-            d_loss = torch.from_numpy(loss).to(self.device)
-        d_nll = torch.empty((M, n, forced), dtype=torch.float32, device=self.device) if want_nll else None
-        d_pred = torch.empty((M, n, forced), dtype=torch.float32, device=self.device) if want_pred else None
-        ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None   # noqa: E731
-        _capi.check(self._h, self._lib.cmps_bank_stream_score(self._h, ptr(state_in), ptr(state_out), int(k0), ptr(d_audio), n_audio, forced, n,
-                                                              ptr(d_nll), ptr(d_loss), ptr(d_pred), self._stream()))
-        return (d_nll.cpu().numpy() if want_nll else None), d_loss.cpu().numpy(), (d_pred.cpu().numpy() if want_pred else None)
+        block = self._audio_block(audio, 2, (1, n, M * n), f" with n_audio in (1, {n}, {M * n}) and forced >= 1")
+        return self._score_launch(self._lib.cmps_bank_stream_score, state_in, state_out, k0, block, want_nll, want_pred, n, loss, (M,))
 
     # ------------------------------------------------------------------
     # legacy AudioMPS arithmetic (SURVEY 8f rank 2)
@@ -851,8 +837,8 @@ class HipScan:
     def legacy_set_params(self, R: np.ndarray, Q: np.ndarray, delta_t: float, B: int, T: int, train: bool = True):
         self._legacy_buf, ptrs = self._upload(layout.legacy_param_fields(self.D), {"R": R, **layout.split("Q", Q)})
         _capi.check(self._h, self._lib.cmps_legacy_set_params(
-            self._h, *ptrs, float(delta_t), int(T), int(B), self._ws_flags(train), *self._workspace(B, T, train), self._stream()))
-        self._B, self._T, self._mode = B, T, "legacy"
+            self._h, *ptrs, float(delta_t), int(T), int(B), *self._psi_workspace(B, T, train, reuse=False), self._stream()))
+        self._configured(B, T, "legacy")
 
     def legacy_forward(self, audio: torch.Tensor, save_for_bwd: bool = False) -> torch.Tensor:
         return self._forward(self._lib.cmps_legacy_loss_fwd, audio, save_for_bwd)
@@ -874,7 +860,7 @@ class HipScan:
         r, D = phi.shape
         if D != self.D:
             raise ValueError("phi has the wrong bond dimension")
-        ws_ptr, ws_bytes = self._workspace(B, T, train, rank=r)
+        ws_ptr, ws_bytes = self._rho_workspace(B, T, train, r)
         self._phi_buf, ptrs = self._upload(layout.phi_fields(D, r), layout.split("phi", phi))
         _capi.check(self._h, self._lib.cmps_rho_set_state(
             self._h, *ptrs, r, int(T), int(B), self._ws_flags(train), ws_ptr, ws_bytes, self._stream()))
@@ -886,7 +872,7 @@ class HipScan:
         r, D = int(rank), self.D
         if not (phi.is_cuda and phi.dtype == torch.float32 and phi.is_contiguous() and phi.numel() == 2 * r * D):
             raise ValueError("phi must be a contiguous float32 CUDA tensor of 2 rank D elements")
-        ws_ptr, ws_bytes = self._workspace(B, T, train, rank=r)
+        ws_ptr, ws_bytes = self._rho_workspace(B, T, train, r)
         self._phi_buf = phi
         _capi.check(self._h, self._lib.cmps_rho_set_state(
             self._h, *layout.pointers(phi.data_ptr(), layout.phi_fields(D, r)), r, int(T), int(B), self._ws_flags(train), ws_ptr, ws_bytes,

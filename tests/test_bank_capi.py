@@ -140,3 +140,70 @@ def test_non_default_options_are_refused(hip_lib, D, variant, option, value):
         assert msg.startswith("cmps_bank_loss_bwd:") and "CMPS_OPT_RANK1" in msg and "CMPS_OPT_BWD_WAVES" in msg
     finally:
         lib.cmps_destroy(h)
+
+
+# Every refusal of the four *_apply_step entries, in the order their checks fire: (arguments that differ from a good call, code, message
+# behind "<entry>: ").  None needs a configured handle, and none touches the device: a launch on these fake pointers would come back as
+# CMPS_ERR_HIP, so the code also says that no kernel ran.
+_ADAM = "an update needs the Adam slots, losses_dev, scratch_dev and a positive batch"
+_SCRATCH, _HYPER, _M = "scratch_dev must be 8-byte aligned", "hyper_dev must be 8-byte aligned", "M outside [1, 1024]"
+_UPDATE = [(dict(m=None), _ADAM), (dict(v=None), _ADAM), (dict(losses=None), _ADAM), (dict(scratch=None), _ADAM), (dict(batch=0.0), _ADAM),
+           (dict(batch=float("nan")), _ADAM), (dict(scratch=PTR4 + 4), _SCRATCH), (dict(grad=None, scratch=PTR4 + 4), _SCRATCH)]
+_BANK_UPDATE = _UPDATE + [(dict(hyper=PTR2 + 4), _HYPER), (dict(grad=None, hyper=PTR2 + 4), _HYPER)]
+APPLY_REFUSALS = {
+    "cmps_psi_apply_step": [(dict(vars_=None), "null variable / parameter buffer"), (dict(params=None), "null variable / parameter buffer")] + _UPDATE + [
+        # the first failing check speaks
+        (dict(vars_=None, m=None, scratch=PTR4 + 4), "null variable / parameter buffer"), (dict(m=None, scratch=PTR4 + 4), _ADAM)],
+    "cmps_rho_apply_step": [(dict(vars_=None), "null variable / parameter / column buffer"), (dict(params=None), "null variable / parameter / column buffer"),
+                            (dict(phi=None), "null variable / parameter / column buffer"), (dict(rank=0), "rank outside [1, 128]"),
+                            (dict(rank=129), "rank outside [1, 128]")] + _UPDATE + [
+        (dict(phi=None, rank=0, m=None), "null variable / parameter / column buffer"), (dict(rank=0, m=None, scratch=PTR4 + 4), "rank outside [1, 128]"),
+        (dict(m=None, scratch=PTR4 + 4), _ADAM)],
+    "cmps_bank_apply_step": [(dict(vars_=None), "null variable / parameter / hyper-parameter buffer"),
+                             (dict(params=None), "null variable / parameter / hyper-parameter buffer"),
+                             (dict(hyper=None), "null variable / parameter / hyper-parameter buffer"), (dict(M=0), _M), (dict(M=1025), _M)] + _BANK_UPDATE + [
+        (dict(hyper=None, M=0, m=None), "null variable / parameter / hyper-parameter buffer"), (dict(M=0, m=None, scratch=PTR4 + 4), _M),
+        (dict(m=None, scratch=PTR4 + 4, hyper=PTR2 + 4), _ADAM), (dict(scratch=PTR4 + 4, hyper=PTR2 + 4), _SCRATCH)],
+    "cmps_rho_bank_apply_step": [(dict(rank=2), "a RhoCMPS bank needs D <= 32 and 3 <= rank <= 32"), (dict(rank=33), "a RhoCMPS bank needs D <= 32 and 3 <= rank <= 32"),
+                                 (dict(vars_=None), "null variable / parameter / column / hyper-parameter buffer"),
+                                 (dict(params=None), "null variable / parameter / column / hyper-parameter buffer"),
+                                 (dict(phi=None), "null variable / parameter / column / hyper-parameter buffer"),
+                                 (dict(hyper=None), "null variable / parameter / column / hyper-parameter buffer"), (dict(M=0), _M),
+                                 (dict(M=1025), _M)] + _BANK_UPDATE + [
+        (dict(rank=2, vars_=None, M=0), "a RhoCMPS bank needs D <= 32 and 3 <= rank <= 32"),
+        (dict(phi=None, M=0, m=None), "null variable / parameter / column / hyper-parameter buffer"), (dict(M=0, m=None, scratch=PTR4 + 4), _M),
+        (dict(m=None, scratch=PTR4 + 4, hyper=PTR2 + 4), _ADAM), (dict(scratch=PTR4 + 4, hyper=PTR2 + 4), _SCRATCH)],
+}
+
+
+def _apply_step(lib, h, entry, M=2, rank=3, vars_=PTR, m=PTR, v=PTR, grad=PTR, batch=2.0, hyper=PTR2, params=PTR3, phi=PTR3, losses=PTR3, scratch=PTR4):
+    adam = (0.9, 0.999, 1e-8)
+    if entry == "cmps_psi_apply_step":
+        return lib.cmps_psi_apply_step(h, vars_, m, v, grad, batch, 1e-3, *adam, 0.0, 0.0, 1.0, 1.0, 1, params, losses, scratch, None)
+    if entry == "cmps_rho_apply_step":
+        return lib.cmps_rho_apply_step(h, vars_, m, v, grad, rank, batch, 1e-3, *adam, 0.0, 0.0, 1.0, 1.0, 1, params, phi, losses, scratch, None)
+    if entry == "cmps_bank_apply_step":
+        return lib.cmps_bank_apply_step(h, M, vars_, m, v, grad, batch, 1.0, 1.0, *adam, hyper, 1, params, losses, scratch, None)
+    return lib.cmps_rho_bank_apply_step(h, M, vars_, m, v, grad, rank, batch, 1.0, 1.0, *adam, hyper, 1, params, phi, losses, scratch, None)
+
+
+@pytest.mark.parametrize("entry", sorted(APPLY_REFUSALS))
+def test_every_refusal_of_the_apply_step_entries(hip_lib, entry):
+    from audio_mps_amd import _capi
+    lib = hip_lib
+    assert _apply_step(lib, None, entry) == _capi.CMPS_ERR_BAD_ARG
+    h = _handle(lib, 4)
+    try:
+        for kw, text in APPLY_REFUSALS[entry]:
+            want = _capi.CMPS_ERR_UNSUPPORTED_D if text.startswith("a RhoCMPS bank") else _capi.CMPS_ERR_BAD_ARG
+            code = _apply_step(lib, h, entry, **kw)
+            assert (code, lib.cmps_last_error(h).decode()) == (want, f"{entry}: {text}"), kw
+    finally:
+        lib.cmps_destroy(h)
+    if entry == "cmps_rho_bank_apply_step":                      # the shape rule reads the handle's D as well
+        h = _handle(lib, 33, 1)
+        try:
+            assert _apply_step(lib, h, entry) == _capi.CMPS_ERR_UNSUPPORTED_D
+            assert lib.cmps_last_error(h).decode() == "cmps_rho_bank_apply_step: a RhoCMPS bank needs D <= 32 and 3 <= rank <= 32"
+        finally:
+            lib.cmps_destroy(h)
