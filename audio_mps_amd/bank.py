@@ -19,15 +19,14 @@ from __future__ import annotations
 import json
 import math
 import os
-import weakref
 from dataclasses import replace
 from typing import List, Optional, Sequence
 
 import numpy as np
 
-from . import layout
 from .model import HParams, PsiCMPS, RhoCMPS
 from .parallel import DataParallel
+from .resident import ResidentState
 from .train import Trainer
 
 MEMBER_KEYS = ("seed", "learning_rate", "h_reg", "r_reg")
@@ -140,13 +139,15 @@ class RhoBank(PsiBank):
 RHO_BANK_ENTRIES = ("rho_bank_set_state_dev", "rho_bank_forward", "rho_bank_backward", "rho_bank_apply_step")
 
 
-class BankTrainer:
+class BankTrainer(ResidentState):
     """One optimiser step of every member of a PsiBank or RhoBank per ``step``.  Every member keeps an ordinary Trainer (its model, its Adam slots,
     its checkpoint format); on a backend with the bank entries (HipScan) variables, Adam slots and effective parameters of all members
     live on the device as [M, ...] arrays between steps and come back with ``sync_to_host`` (``member`` and ``save`` do so).  While that
-    state is live the bank is every member model's device owner, as a Trainer(device_step=True) is its model's (CMPS.variables): reading
-    ``bank.models[m].variables`` brings the state back first, and assigning an entry brings it back and drops it, so the next step starts
-    from the host values of every member."""
+    state is live the bank is every member model's device owner by the protocol a Trainer(device_step=True) follows (ResidentState,
+    audio_mps_amd/resident.py): reading ``bank.models[m].variables`` brings the state back first, and assigning an entry brings it back
+    and drops it, so the next step starts from the host values of every member."""
+
+    STACKED = True                # (SYNC_CLEAN stays off: sync_to_host() without a step since the last one touches no member)
 
     def __init__(self, bank: PsiBank, dp: Optional[DataParallel] = None):
         if dp is not None and dp.world_size > 1:
@@ -170,61 +171,19 @@ class BankTrainer:
                          for model, hp in zip(bank.models, bank.member_hparams)]
         self.global_step = 0
         self.last = None              # the last synchronised step's per-member losses: {"model_loss": [M], "total_loss": [M]}
-        self._dev = None
-        self._dirty = False
-        self._syncing_back = False    # (read by the members' variables dicts; sync_to_host writes past them)
+        self._resident([(tr.model, tr.opt) for tr in self.trainers], bank.bond_d, self.rank)
 
     def __len__(self) -> int:
         return len(self.trainers)
 
-    # -- the members' device owner (the interface CMPS.variables and its dict use of a Trainer) -------
-    def _own(self, dirty: bool):
-        for tr in self.trainers:
-            tr.model._device_owner = weakref.ref(self)
-            if dirty:
-                tr.model._dirty_owner = self      # a bank that goes out of scope with steps the host lacks stays alive until they are back
-
-    def _release(self):
-        for tr in self.trainers:
-            if tr.model._dirty_owner is self:
-                tr.model._dirty_owner = None
-
-    def _lazy_sync(self):
-        self.sync_to_host()
-
-    def drop_device_state(self):
-        """Bring the device-resident state back and forget it: the next step uploads variables and Adam slots from the host again."""
-        if self._dev is not None:
-            self.sync_to_host()
-            self._dev = None
-
-    # -- device-resident state of the native path ---------------------------------------------------
+    # -- device-resident state of the native path ([M, ...] rows of ResidentState's tensors, and "hyper") ---------------
     def _device_state(self):
         if self._dev is None:
             import torch
-            be, D, rank = self.bank.backend, self.bank.bond_d, self.rank
-            fields = layout.var_fields(D, rank)
-
-            def packed(get):
-                rows = []
-                for tr in self.trainers:
-                    variables = tr.model.variables
-                    zeros = {k: np.zeros_like(variables[k]) for k in layout.var_order(rank)}
-                    rows.append(layout.pack(fields, {**zeros, **get(tr)}))
-                return torch.from_numpy(np.stack(rows)).to(be.device)
-
-            M = len(self.trainers)
-            st = {"vars": packed(lambda tr: tr.model.variables), "m": packed(lambda tr: tr.opt.m), "v": packed(lambda tr: tr.opt.v)}
-            st["params"] = torch.empty((M, layout.size(layout.param_fields(D, with_A=True))), dtype=torch.float32, device=be.device)
-            st["losses"] = torch.zeros((M, 2), dtype=torch.float32, device=be.device)
-            if rank:
-                st["phi"] = torch.empty((M, layout.size(layout.phi_fields(D, rank))), dtype=torch.float32, device=be.device)
+            be = self.bank.backend
             hyper = np.array([[tr.opt.lr, tr.model.h_reg, tr.model.r_reg, float(tr.model._c_r), float(tr.model._c_h)] for tr in self.trainers],
                              dtype=np.float64)
-            st["hyper"] = torch.from_numpy(hyper).to(be.device)       # uploaded once: the device forms lr_t itself
-            self._dev = st
-            self._dirty = False
-            self._own(dirty=False)
+            self._upload(be.device)["hyper"] = torch.from_numpy(hyper).to(be.device)       # uploaded once: the device forms lr_t itself
             self._apply(None, 1)                                      # effective parameters of the current variables
         return self._dev
 
@@ -232,19 +191,6 @@ class BankTrainer:
         st, o = self._dev, self.trainers[0].opt
         t = max(o.t, 1)
         self._apply_step(st, grad_sums, global_batch, math.sqrt(1.0 - o.b2 ** t), 1.0 - o.b1 ** t, o.b1, o.b2, o.eps, st["hyper"], True)
-
-    def sync_to_host(self):
-        """Device-resident state -> every member's model.variables and Adam slots."""
-        if self._dev is None or not self._dirty:
-            return
-        fields = layout.var_fields(self.bank.bond_d, self.rank)
-        host = {name: self._dev[name].cpu().numpy() for name in ("vars", "m", "v")}
-        for m, tr in enumerate(self.trainers):
-            for name, dst in (("vars", tr.model._variables), ("m", tr.opt.m), ("v", tr.opt.v)):
-                for k, a in layout.unpack(fields, host[name][m]).items():
-                    dict.__setitem__(dst, k, np.asarray(a, dtype=np.float32).copy())
-        self._dirty = False
-        self._release()
 
     # -- one step -------------------------------------------------------------------------------------
     def step(self, data, sync: bool = True) -> dict:
@@ -279,8 +225,7 @@ class BankTrainer:
             tr.opt.t += 1
             tr.global_step += 1
         self._apply(flat, int(B))
-        self._dirty = True
-        self._own(dirty=True)         # (again every step: a plain Trainer of a member taken out in between has made itself the owner)
+        self._mark_dirty()
         return {"losses_dev": st["losses"]}
 
     def best(self) -> int:
@@ -310,15 +255,11 @@ class BankTrainer:
         if not self.native:
             return [tr.evaluate(dataset, minibatch_size, T, keep_losses) for tr in self.trainers]
         import torch
-        from .evaluate import EvalResult, _need_stats
+        from .evaluate import EvalResult, pass_shape
         be = self.bank.backend
-        _need_stats(be)
-        mb = int(minibatch_size) if minibatch_size else int(self.bank.hparams.minibatch_size)
-        T = dataset.clip_len if T is None else int(T)
-        if T < 2 or mb < 1:
-            raise ValueError("evaluate needs T >= 2 and minibatch_size >= 1")
+        mb, T, B_max = pass_shape(be, dataset, minibatch_size, self.bank.hparams.minibatch_size, T)
         st = self._device_state()
-        self._configure(st, min(mb, dataset.n_clips), T, False)
+        self._configure(st, B_max, T, False)
         M = len(self.trainers)
         stats, kept = [None] * M, [[] for _ in range(M)]
         for first_id, batch in dataset.ordered(mb, T):

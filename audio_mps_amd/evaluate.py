@@ -64,6 +64,16 @@ def _need_stats(backend):
                          "has none")
 
 
+def pass_shape(backend, dataset, minibatch_size, default_minibatch, T):
+    """(clips per batch, T, largest batch) of a trainer's ``evaluate``: ``minibatch_size`` None or 0 is the training one, ``T`` None the clips' length."""
+    _need_stats(backend)
+    mb = int(minibatch_size) if minibatch_size else int(default_minibatch)
+    T = dataset.clip_len if T is None else int(T)
+    if T < 2 or mb < 1:
+        raise ValueError("evaluate needs T >= 2 and minibatch_size >= 1")
+    return mb, T, min(mb, dataset.n_clips)
+
+
 def run_pass(batches, forward: Callable, backend, T: int, keep_losses: bool = False) -> EvalResult:
     """The loop of `evaluate` over ``batches`` (an iterable of (first_id, batch)) with ``forward(batch)`` -> per-clip losses on the device:
     one loss_stats per batch, ONE download at the end (two with keep_losses: the record and the concatenated losses)."""

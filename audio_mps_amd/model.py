@@ -141,8 +141,8 @@ class _VarDict(dict):
 
     def __setitem__(self, key, value):
         owner = self._model._owner()
-        if owner is not None and owner._dev is not None and not owner._syncing_back:
-            owner.drop_device_state()              # device -> host for everything else, then forget the device copy
+        if owner is not None:
+            owner.drop_device_state()              # device -> host for everything else, then forget the device copy (if one is live)
         super().__setitem__(key, value)
 
 
@@ -152,8 +152,8 @@ class CMPS(_ScanModel):
     ``self.A``, ``self.sigma`` are the attributes train.py:55-75 reads."""
 
     def __init__(self, hparams, data_iterator=None, freqs_in=None, R_in=None, seed: int = 0):
-        self._device_owner = None      # a Trainer whose device-resident optimiser state is newer than self._variables (see `variables`)
-        self._dirty_owner = None       # that Trainer again, held STRONGLY while its device state has steps the host copies lack
+        self._device_owner = None      # weak reference to the ResidentState (Trainer, BankTrainer) that holds a device copy of self._variables
+        self._dirty_owner = None       # that owner again, held STRONGLY while its device state has steps the host copies lack
         self._backend = None           # the scan implementation (the subclasses' `backend` argument); None: a HipScan on first use
         self._last = None              # the flat gradient sums of the last loss_and_grads (host copy)
         self.hparams = hparams
@@ -199,16 +199,16 @@ class CMPS(_ScanModel):
 
     @property
     def variables(self) -> Dict[str, np.ndarray]:
-        """The raw trainable variables (host copies).  While a Trainer runs the device-resident optimiser step the current values
-        live on the GPU; reading this attribute then brings them back first (Trainer._lazy_sync: one device -> host copy, only after
-        steps that changed them), so loss / sample / effective_params / summaries never see stale parameters.
-        ASSIGNING an entry (``m.variables["Rx"] = ...``, ``m.variables["Rx"] *= c``) while a device-resident state is live brings that
-        state back and drops it, so the Trainer's next step starts from the host values (ADVICE r4: such writes used to be ignored);
-        the Trainer is held by a weak reference -- and, only while it has device steps that have not come back (Trainer._dirty), by a
-        strong one as well (``_dirty_owner``, set by the device step, dropped by the sync, drop_device_state and restore): a Trainer that
-        goes out of scope in that state, e.g. inside a helper that returns the model alone, stays alive until this attribute has brought
-        its steps back instead of taking them with it (ADVICE: they used to be lost without notice).  The model <-> Trainer cycle of that
-        interval is the garbage collector's to break; a Trainer that is not dirty is still released at once."""
+        """The raw trainable variables (host copies).  While a Trainer or a BankTrainer runs the device-resident optimiser step the
+        current values live on the GPU; reading this attribute then brings them back first (ResidentState._lazy_sync,
+        audio_mps_amd/resident.py: one device -> host copy, only after steps that changed them), so loss / sample / effective_params /
+        summaries never see stale parameters.  ASSIGNING an entry (``m.variables["Rx"] = ...``, ``m.variables["Rx"] *= c``)
+        while a device-resident state is live brings that state back and drops it (drop_device_state), so the owner's next step starts
+        from the host values (such writes used to be ignored).  The owner is held by a weak reference and, only while it has
+        device steps that have not come back, by a strong one as well (``_dirty_owner``): an owner that goes out of scope in that state,
+        e.g. inside a helper that returns the model alone, stays alive until this attribute has brought its steps back instead of taking
+        them with it (ADVICE: they used to be lost without notice).  The model <-> owner cycle of that interval is the garbage
+        collector's to break; an owner that is not dirty is still released at once."""
         owner = self._owner()
         if owner is not None:
             owner._lazy_sync()

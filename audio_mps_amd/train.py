@@ -26,7 +26,6 @@ import json
 import math
 import os
 import time
-import weakref
 from collections import deque
 from typing import Dict, Optional
 
@@ -36,6 +35,7 @@ from . import layout
 from .layout import VAR_ORDER  # noqa: F401  (bench.py imports it from here)
 from .model import HParams, PsiCMPS, RhoCMPS
 from .parallel import DataParallel
+from .resident import ResidentState
 
 
 class AdamOptimizer:
@@ -70,7 +70,7 @@ class AdamOptimizer:
         self.v = {k[2:]: np.asarray(v) for k, v in sd.items() if k.startswith("v/")}
 
 
-class Trainer:
+class Trainer(ResidentState):
     """One optimiser step = parameter tables, forward scan, reverse scan, (all-reduce), chain rule, Adam.
 
     ``device_step=False``: the gradient sums come to the host, chain rule (model.chain_rule) and Adam (AdamOptimizer) run in
@@ -79,9 +79,11 @@ class Trainer:
     columns of rho_0 as well) live on the GPU and cmps_psi_apply_step / cmps_rho_apply_step does the optimiser half there; a step
     issues no device -> host copy.  ``step`` then returns the
     losses as a 2-element device tensor under "losses_dev" unless ``sync=True``; ``sync_to_host()`` brings variables and
-    Adam state back (checkpoints, sampling, inspection)."""
+    Adam state back (checkpoints, sampling, inspection).  That state, its upload and download and the model's way to it (reading
+    model.variables syncs, assigning an entry drops it) are ResidentState's (audio_mps_amd/resident.py)."""
 
     HISTORY = 4096                # step records kept (a long run must not grow without bound)
+    SYNC_CLEAN = True             # sync_to_host() after a synced step, or before any, still copies (save: explicit zero Adam slots)
 
     def __init__(self, model: PsiCMPS, hparams: HParams, dp: Optional[DataParallel] = None, device_step: bool = False):
         self.model = model
@@ -91,10 +93,7 @@ class Trainer:
         self.global_step = 0
         self.history = deque(maxlen=self.HISTORY)   # the dict of every step (the scalar summaries of train.py:62-66)
         self.device_step = bool(device_step)
-        self._dev = None              # device-resident step: {"vars", "m", "v", "params", "losses"} (RhoCMPS: + "phi") device tensors (_device_state)
-        self._dirty = False           # a device step has run since the last sync: the host copies are stale
-        self._syncing = False         # inside _lazy_sync (sync_to_host reads model.variables, which calls _lazy_sync)
-        self._syncing_back = False    # inside sync_to_host: assigning model.variables must not drop the state being read
+        self._resident([(model, self.opt)], model.bond_d, self._rank())    # _dev: flat "vars", "m", "v", "params", "losses" (RhoCMPS: + "phi")
         if self.device_step and not isinstance(model, (PsiCMPS, RhoCMPS)):
             raise ValueError("device_step: the device-resident optimiser step exists for PsiCMPS or RhoCMPS")
 
@@ -132,31 +131,9 @@ class Trainer:
 
     def _device_state(self):
         if self._dev is None:
-            import torch
-            be = self.model._get_backend()
-            D, rank, variables = self.model.bond_d, self._rank(), self.model.variables
-            fields = layout.var_fields(D, rank)
-            zeros = {k: np.zeros_like(variables[k]) for k in layout.var_order(rank)}     # (a missing Adam slot starts at zero)
-            st = {slot: torch.from_numpy(layout.pack(fields, {**zeros, **src})).to(be.device)
-                  for slot, src in (("vars", variables), ("m", self.opt.m), ("v", self.opt.v))}
-            st["params"] = torch.empty(layout.size(layout.param_fields(D, with_A=True)), dtype=torch.float32, device=be.device)
-            st["losses"] = torch.zeros(2, dtype=torch.float32, device=be.device)
-            if rank:
-                st["phi"] = torch.empty(layout.size(layout.phi_fields(D, rank)), dtype=torch.float32, device=be.device)
-            self._dev = st
-            self._dirty = False
-            self.model._device_owner = weakref.ref(self)           # model.variables now syncs lazily from the device state
+            self._upload(self.model._get_backend().device)
             self._apply(None, 1)                                   # effective parameters of the current variables
         return self._dev
-
-    def _lazy_sync(self):
-        """Called by model.variables: device state -> host copies if a device step has run since the last sync."""
-        if self._dev is not None and self._dirty and not self._syncing:
-            self._syncing = True
-            try:
-                self.sync_to_host()
-            finally:
-                self._syncing = False
 
     def _apply(self, grad_sums, global_batch):
         st, m, o = self._dev, self.model, self.opt
@@ -193,8 +170,7 @@ class Trainer:
         self.dp.allreduce_device(flat)
         self.opt.t += 1
         self._apply(flat, global_batch)
-        self._dirty = True                                          # the host copies (model.variables, Adam slots) are stale now
-        m._dirty_owner = self                                       # ... and until they are synced the model keeps this Trainer alive
+        self._mark_dirty()                                          # the host copies (model.variables, Adam slots) are stale now
         self.global_step += 1
         out = {"global_step": self.global_step, "global_batch": int(global_batch), "losses_dev": st["losses"]}
         if sync:
@@ -204,38 +180,6 @@ class Trainer:
             self.history.append(out)
         return out
 
-    def drop_device_state(self):
-        """Bring the device-resident state back and forget it: the next device step re-uploads variables and Adam slots from the host
-        (called when model.variables is assigned to while the state is live)."""
-        if self._dev is not None:
-            self.sync_to_host()
-            self._dev = None
-            self._dirty = False
-            self._release()
-
-    def sync_to_host(self):
-        """Device-resident state -> model.variables and the host AdamOptimizer's slots (checkpoints, sampling, inspection)."""
-        if self._dev is None:
-            return
-        self._syncing_back = True              # (the assignments below must not drop the state they are reading)
-        try:
-            self._sync_to_host()
-        finally:
-            self._syncing_back = False
-
-    def _sync_to_host(self):
-        fields = layout.var_fields(self.model.bond_d, self._rank())
-        self._dirty = False
-        for name, dst in (("vars", self.model._variables), ("m", self.opt.m), ("v", self.opt.v)):
-            for k, a in layout.unpack(fields, self._dev[name].cpu().numpy()).items():
-                dst[k] = np.asarray(a, dtype=np.float32).copy()
-        self._release()
-
-    def _release(self):
-        """Not dirty any more: the model drops its strong reference to this Trainer (CMPS.variables; the weak one stays)."""
-        if self.model._dirty_owner is self:
-            self.model._dirty_owner = None
-
     # -- held-out evaluation ------------------------------------------------------------------------
     def evaluate(self, dataset, minibatch_size: Optional[int] = None, T: Optional[int] = None, keep_losses: bool = False):
         """The current parameters' loss over every clip of ``dataset`` (a ResidentDataset; audio_mps_amd/evaluate.py): an EvalResult.
@@ -243,15 +187,10 @@ class Trainer:
         Training is left untouched: the pass runs forward scans only, writes no variable and no Adam slot, and every training step
         configures the backend for itself (set_params* with its own shape), so the steps after an evaluation are bit for bit those of a
         run without it.  With several ranks every rank evaluates the whole dataset: nothing is communicated."""
-        from .evaluate import _need_stats, run_pass
+        from .evaluate import pass_shape, run_pass
         m = self.model
         be = m._get_backend()
-        _need_stats(be)
-        mb = int(minibatch_size) if minibatch_size else int(self.hparams.minibatch_size)
-        T = dataset.clip_len if T is None else int(T)
-        if T < 2 or mb < 1:
-            raise ValueError("evaluate needs T >= 2 and minibatch_size >= 1")
-        B_max = min(mb, dataset.n_clips)
+        mb, T, B_max = pass_shape(be, dataset, minibatch_size, self.hparams.minibatch_size, T)
         if self.device_step:
             st, rank = self._device_state(), self._rank()
             be.set_params_dev(st["params"], m.sigma, m.delta_t, B_max, T, train=False)
@@ -281,9 +220,7 @@ class Trainer:
                 self.model.variables[k] = np.asarray(z[f"model/{k}"], dtype=np.float32)
             self.opt.load_state_dict({k[5:]: z[k] for k in z.files if k.startswith("adam/")})
             self.global_step = int(z["global_step"])
-        self._dev = None                                            # the device-resident copy is rebuilt from the restored state
-        self._dirty = False
-        self._release()
+        self._forget()                                              # the device-resident copy is rebuilt from the restored state
         return True
 
 
@@ -391,10 +328,30 @@ def device_source(args, hp, backend):
     return (lambda step: stream.next_size), (lambda step, shard: stream(shard=shard))
 
 
+def step_input(args, hp, backend):
+    """The run's input, built ONCE (train.py:46-47): ``batch(step, shard)`` -> (size n of the global batch of ``step``, its rows
+    ``shard(n) = (start, count)``; default: all of them).  For TFRecord datasets get_audio returns the one-shot iterator's get_next
+    (batch -> shuffle(24) -> repeat, data.py:37-40), for damped_sine every step draws fresh delays (data.py:15); --device_data: the same
+    batches (TFRecords) / the device's own clips (damped_sine), produced on the device, the asked rows only."""
+    from .data import get_audio
+    on_device = device_source(args, hp, backend) if args.device_data else None
+    source = get_audio(args.datadir, args.dataset, hp, args.sample_duration, seed=args.seed) \
+        if args.dataset != "damped_sine" and on_device is None else None
+
+    def batch(step, shard=lambda n: (0, n)):
+        if on_device is not None:
+            n = int(on_device[0](step))
+            return n, on_device[1](step, shard(n))
+        full = source() if source is not None else get_audio(args.datadir, args.dataset, hp, args.sample_duration, seed=args.seed + step)
+        n = int(full.shape[0])
+        s0, c0 = shard(n)
+        return n, full[s0:s0 + c0]
+    return batch
+
+
 def main(argv=None, backend=None):
     """``backend``: a scan backend to use instead of HipScan (CPU tests of the host logic inject one; the product
     always builds a HipScan and fails loudly without a GPU)."""
-    from .data import get_audio
     args = build_parser().parse_args(argv)
     hp = HParams(delta_t=1.0 / args.sample_rate, h_reg=200.0 / (math.pi * args.sample_rate) ** 2)  # train.py:41-43
     hp.parse(args.hparams)
@@ -424,24 +381,10 @@ def main(argv=None, backend=None):
     last_save = time.time()
     held_out = eval_dataset(args, hp, backend) if args.eval_dataset else None
     eval_log = EvalLog(logdir, dp.rank == 0)
-    # train.py:46-47: the input pipeline is built ONCE; for TFRecord datasets get_audio returns the one-shot iterator's
-    # get_next (batch -> shuffle(24) -> repeat, data.py:37-40), for damped_sine every step draws fresh delays (data.py:15)
-    # --device_data: the same batches (TFRecords) / the device's own clips (damped_sine), produced on the device, a rank's shard only
-    on_device = device_source(args, hp, backend) if args.device_data else None
-    source = get_audio(args.datadir, args.dataset, hp, args.sample_duration, seed=args.seed) \
-        if args.dataset != "damped_sine" and on_device is None else None
+    batch = step_input(args, hp, backend)
     for it in range(args.max_steps):
-        if on_device is not None:
-            n_full = int(on_device[0](trainer.global_step))
-        elif source is not None:
-            full = source()
-        else:
-            full = get_audio(args.datadir, args.dataset, hp, args.sample_duration, seed=args.seed + trainer.global_step)
-        if on_device is None:
-            n_full = int(full.shape[0])
         # every rank reads the same global batch and keeps its shard (a short final batch of an epoch is sharded as it is)
-        s0, c0 = dp.shard(n_full) if n_full != hp.minibatch_size else (start, count)
-        shard = on_device[1](trainer.global_step, (s0, c0)) if on_device is not None else full[s0:s0 + c0]
+        n_full, shard = batch(trainer.global_step, lambda n: dp.shard(n) if n != hp.minibatch_size else (start, count))
         # the losses come to the host only on logging steps (the device-resident step needs no device -> host copy otherwise)
         log_now = (it % max(args.log_every, 1) == 0) or it == args.max_steps - 1
         out = trainer.step(shard, sync=log_now, global_batch=n_full)
@@ -460,7 +403,6 @@ def main(argv=None, backend=None):
 def bank_main(args, hp, backend, dp):
     """``--bank`` / ``--bank_hparams``: the loop of ``main`` for a BankTrainer.  One batch per step, shared by every member."""
     from .bank import RHO_BANK_ENTRIES, BankTrainer, PsiBank, RhoBank, bank_members
-    from .data import get_audio
     rho = args.mps_model == "rho_mps"                                                        # train.py:18-20, 50-53
     if rho and backend is not None and not all(hasattr(backend, name) for name in RHO_BANK_ENTRIES):
         raise ValueError("--bank --mps_model rho_mps needs a backend with the cmps_rho_bank_* entries (HipScan): this one "
@@ -479,18 +421,10 @@ def bank_main(args, hp, backend, dp):
     if trainer.restore(logdir):
         print(f"Restoring {len(trainer)} members from {logdir} (global_step {trainer.global_step})")
     last_save = time.time()
-    on_device = device_source(args, hp, backend) if args.device_data else None
-    source = get_audio(args.datadir, args.dataset, hp, args.sample_duration, seed=args.seed) \
-        if args.dataset != "damped_sine" and on_device is None else None
+    batch = step_input(args, hp, backend)
     for it in range(args.max_steps):
-        if on_device is not None:
-            batch = on_device[1](trainer.global_step, (0, int(on_device[0](trainer.global_step))))
-        elif source is not None:
-            batch = source()
-        else:
-            batch = get_audio(args.datadir, args.dataset, hp, args.sample_duration, seed=args.seed + trainer.global_step)
         log_now = (it % max(args.log_every, 1) == 0) or it == args.max_steps - 1
-        out = trainer.step(batch, sync=log_now)
+        out = trainer.step(batch(trainer.global_step)[1], sync=log_now)
         if log_now:
             print(bank_log_line(out))
         if time.time() - last_save > args.save_checkpoint_secs or it == args.max_steps - 1:
