@@ -64,6 +64,7 @@ SYMBOLS = (
     "cmps_bank_apply_step", "cmps_bank_grad_status", "cmps_bank_stream_state_bytes", "cmps_bank_stream", "cmps_bank_stream_score",
     "cmps_rho_bank_workspace_bytes", "cmps_rho_bank_set_state_dev", "cmps_rho_bank_loss_fwd", "cmps_rho_bank_loss_bwd",
     "cmps_rho_bank_apply_step_scratch_bytes", "cmps_rho_bank_apply_step",
+    "cmps_rho_bank_stream_state_bytes", "cmps_rho_bank_stream", "cmps_rho_bank_stream_score",
 )
 
 
@@ -211,6 +212,12 @@ def _declare(lib):
     lib.cmps_rho_bank_apply_step.argtypes = [vp, c_int, vp, vp, vp, vp, c_int, c_double, c_double, c_double, c_double, c_double, c_double, vp,
                                              c_int, vp, vp, vp, vp, vp]
     lib.cmps_rho_bank_apply_step.restype = c_int
+    lib.cmps_rho_bank_stream_state_bytes.argtypes = [vp, c_int]
+    lib.cmps_rho_bank_stream_state_bytes.restype = c_size_t
+    lib.cmps_rho_bank_stream.argtypes = [vp, vp, vp, c_int, vp, c_int, c_int, vp, c_int, c_int, c_int, vp, vp, vp]
+    lib.cmps_rho_bank_stream.restype = c_int
+    lib.cmps_rho_bank_stream_score.argtypes = [vp, vp, vp, c_int, vp, c_int, c_int, c_int, vp, vp, vp, vp]
+    lib.cmps_rho_bank_stream_score.restype = c_int
 
 
 _lib = None

@@ -10,8 +10,8 @@
                      model m alone.  On a backend without the bank entries the trainer loops over plain steps of its members.
 
 Common to a bank: bond_dim, minibatch_size, sigma, delta_t, A, Adam's betas and epsilon.  Free per member: seed, learning_rate, h_reg, r_reg
-and the data.  Every member is sampled, followed and scored at once through ``PsiBank.open_stream`` (a BankStream: cmps_bank_stream*),
-``PsiBank.sample``, ``nll_per_step`` and ``classify``; for everything else a member is taken out as an ordinary model:
+and the data.  Every member is sampled, followed and scored at once through ``open_stream`` (a BankStream: cmps_bank_stream*; a RhoBank:
+cmps_rho_bank_stream*), ``sample``, ``nll_per_step`` and ``classify``; for everything else a member is taken out as an ordinary model:
 ``BankTrainer.member(m)``.
 """
 from __future__ import annotations
@@ -66,7 +66,7 @@ class PsiBank:
     def bond_d(self) -> int:
         return int(self.hparams.bond_dim)
 
-    # -- every member at once: stream, sample, score (cmps_bank_stream*) ---------------------------------
+    # -- every member at once: stream, sample, score (cmps_bank_stream*, cmps_rho_bank_stream*) ---------------------------------
     def stream_backend(self):
         """A new backend of the bank's kind, D and variant: what a stream of the bank runs on."""
         be = self.backend
@@ -75,20 +75,20 @@ class PsiBank:
         return type(be)(self.bond_d)
 
     def open_stream(self, num_paths, max_steps, temp=1, seed=None, device_noise=False, independent_noise=False):
-        """``PsiCMPS.open_stream`` for every member at once: a BankStream (audio_mps_amd/stream.py) of ``num_paths`` paths per member.
-        It runs on a backend of its own, so it never disturbs a trainer's workspace on the bank's shared one, and keeps the parameters
+        """``PsiCMPS.open_stream`` (RhoBank: ``RhoCMPS.open_stream`` without keep_states) for every member at once: a BankStream
+        (audio_mps_amd/stream.py) of ``num_paths`` paths per member.  It runs on a backend of its own, so it never disturbs a trainer's workspace on the bank's shared one, and keeps the parameters
         the members have now.  By default member m, path b hears the noise ``models[m].open_stream(num_paths, ..., seed=seed)`` would
         give path b; ``independent_noise=True`` numbers the paths globally (g = m num_paths + b)."""
         from .stream import BankStream
         return BankStream(self, num_paths, max_steps, temp=temp, seed=seed, device_noise=device_noise, independent_noise=independent_noise)
 
     def sample(self, n, length, temp=1, seed=None, prime=None, device_noise=False) -> np.ndarray:
-        """``PsiCMPS.sample`` of every member, [M, n, length] in the reference's convention (A * running sum of the sampled increments,
-        zero at the hand-over behind a ``prime`` [T'], [1, T'] or [n, T']).  Every member hears the same noise."""
-        steps = 0 if prime is None else PsiCMPS._prime(prime, n).shape[1] - 1
+        """``PsiCMPS.sample`` (RhoBank: ``RhoCMPS.sample``) of every member, [M, n, length] in the reference's convention (A * running sum
+        of the sampled increments, zero at the hand-over behind a ``prime`` [T'], [1, T'] or [n, T']).  Every member hears the same noise."""
+        steps = 0 if prime is None else self.MODEL._prime(prime, n).shape[1] - 1
         st = self.open_stream(n, steps + int(length), temp=temp, seed=seed, device_noise=device_noise)
         if prime is not None:
-            st.follow(PsiCMPS._prime(prime, n))
+            st.follow(self.MODEL._prime(prime, n))
         st.generate(length)
         return st._raw
 
@@ -130,10 +130,6 @@ class RhoBank(PsiBank):
     def __init__(self, hparams: HParams, members: Sequence[dict], backend=None):
         super().__init__(hparams, members, backend)
         self.rank = int(self.models[0].rank_rho_0)
-
-    def open_stream(self, *args, **kwargs):
-        raise ValueError("open_stream: a bank's streams (sample, nll_per_step, classify) are built for PsiCMPS banks only; take a RhoCMPS "
-                         "member out with BankTrainer.member(m) and stream it alone")
 
 
 RHO_BANK_ENTRIES = ("rho_bank_set_state_dev", "rho_bank_forward", "rho_bank_backward", "rho_bank_apply_step")

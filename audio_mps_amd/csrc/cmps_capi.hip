@@ -1404,6 +1404,7 @@ static int rho_sample_run(cmps_handle_t h, const char* who, const SampleDev& S, 
     const hipError_t e = mfma ? launch_sample_rho_mfma(h->P, h->W, S, save_states != 0, rank1_f16(h->rank1_mode), s)
                               : launch_sample_rho(h->P, h->W, S, save_states != 0, s);
     if (e != hipSuccess) return fail_hip(h, e, who);
+    if (S.MB.M > 0) return CMPS_OK;                              // (a bank's segment wrote no stash: a saved cmps_rho_bank_loss_fwd stays what it was)
     h->rho = Saved{save_states != 0, n, steps, nullptr, nullptr, mfma ? RHO_STASH_MFMA : RHO_STASH_BLOCK};   // (no reverse pass after a sampler)
     h->rho.k0 = S.ST ? S.ST->k0 : 0;                             // cmps_rho_states: the phases of the saved steps are ttab[k0 + k]
     return CMPS_OK;
@@ -1456,6 +1457,47 @@ int cmps_rho_stream_score(cmps_handle_t h, const void* state_in_dev, void* state
                            rho_stream_rec_floats(h), "path", plain_rows, MemberDev{}, C))
         return c;
     return rho_sample_run(h, "cmps_rho_stream_score", C.S, save_states, stream);
+}
+
+// ---- a RhoCMPS bank's streams: k_sample_rho_mfma's STREAM / SCORE instances with the members as a second grid dimension (include/cmps.h) ----
+static bool rho_bank_mode(const cmps_handle_s* h) { return h->params_set && !h->legacy && h->bank_M > 0 && h->bank_rho; }
+// What cmps_rho_bank_stream and cmps_rho_bank_stream_score refuse before they look at their arguments
+static int rho_bank_stream_check_mode(cmps_handle_t h, const char* who) {
+    if (!rho_bank_mode(h)) return fail(h, CMPS_ERR_STATE, std::string(who) + ": needs a RhoCMPS bank (call cmps_rho_bank_set_state_dev first)");
+    if (const int rc = rho_bank_check_mode(h, who, h->W.rank)) return rc;        // (a variant or an option set behind cmps_rho_bank_set_state_dev)
+    return CMPS_OK;
+}
+
+size_t cmps_rho_bank_stream_state_bytes(cmps_handle_t h, int n) {
+    if (!h || n < 1 || !rho_bank_mode(h)) return 0;
+    return (size_t)h->bank_M * (size_t)n * stream_rec_rho_mfma(h->W.rank) * sizeof(float);
+}
+
+int cmps_rho_bank_stream(cmps_handle_t h, const void* state_in_dev, void* state_out_dev, int k0, const float* audio_dev, int n_audio, int forced,
+                         const float* noise_dev, int n_noise, int length, int n, float* out_dev, float* pred_dev, void* stream) {
+    const char* who = "cmps_rho_bank_stream";
+    if (!h) return CMPS_ERR_BAD_ARG;
+    if (const int rc = rho_bank_stream_check_mode(h, who)) return rc;
+    const MemberDev MB{h->bank_M, audio_dev ? bank_member_stride(h, n_audio, n, (size_t)forced + 1) : 0,
+                       length > 0 ? bank_member_stride(h, n_noise, n, (size_t)length) : 0};
+    StreamCall C;
+    if (int c = stream_args(h, who, state_in_dev, state_out_dev, k0, audio_dev, n_audio, forced, noise_dev, n_noise, length, n, out_dev, pred_dev,
+                            stream_rec_rho_mfma(h->W.rank), bank_rows, MB, C))
+        return c;
+    return rho_sample_run(h, who, C.S, 0, stream);
+}
+
+int cmps_rho_bank_stream_score(cmps_handle_t h, const void* state_in_dev, void* state_out_dev, int k0, const float* audio_dev, int n_audio,
+                               int forced, int n, float* nll_dev, float* loss_dev, float* pred_dev, void* stream) {
+    const char* who = "cmps_rho_bank_stream_score";
+    if (!h) return CMPS_ERR_BAD_ARG;
+    if (const int rc = rho_bank_stream_check_mode(h, who)) return rc;
+    StreamCall C;
+    if (int c = score_args(h, who, state_in_dev, state_out_dev, k0, audio_dev, n_audio, forced, n, nll_dev, loss_dev, pred_dev,
+                           stream_rec_rho_mfma(h->W.rank), "member and path", bank_rows,
+                           MemberDev{h->bank_M, bank_member_stride(h, n_audio, n, (size_t)forced + 1), 0}, C))
+        return c;
+    return rho_sample_run(h, who, C.S, 0, stream);
 }
 
 int cmps_rho_states(cmps_handle_t h, int B, int steps, float* rho_out_dev, float* purity_out_dev, void* stream) {

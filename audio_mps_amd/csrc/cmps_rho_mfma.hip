@@ -632,16 +632,35 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_bwd_rho_mfma(Dev P, RhoDev W,
 // Nothing of this feeds U, the running sum, pred or the stash: they keep the stream instance's bits.  The running loss comes from
 // SC.loss[b] on a resumed scan (else 0) and goes back to it behind the last step; lv goes to SC.nll[b][k] when set.  The other instances
 // ignore SC, have no second row array, and are the kernels they were (profiles/rho_stream_score_isa_identity.log).
+// BANK (cmps_rho_bank_stream, cmps_rho_bank_stream_score): member m = blockIdx.y of a RhoCMPS bank runs the STREAM / SCORE instance on
+// its own tables.  The member takes its Dev and its RhoDev once at entry (R, Q, RT, the time table, Adev, phi0); behind it only the rows
+// of the caller's arrays differ: everything a path writes or carries (out, pred, nll, the running loss, the state records) is indexed by
+// the global path g = m n_paths + b, the audio and the noise by the path b behind the member's MB.audio / MB.noise floats (0: shared by
+// every member).  The last workgroup's idle waves return per member.  A bank keeps no stash (SAVE = false) and runs the default fp16 x 2
+// arithmetic only.  The plain instances ignore MB and are the kernels they were (profiles/rho_bank_stream_isa_identity.log).
 // ------------------------------------------------------------------------------------------------
-template <bool SAVE, bool F16, bool PRIMED, bool STREAM = false, bool SCORE = false>
+template <bool SAVE, bool F16, bool PRIMED, bool STREAM = false, bool SCORE = false, bool BANK = false>
 __global__ __launch_bounds__(64 * WAVES, 1) void k_sample_rho_mfma(Dev P, RhoDev W, const float* __restrict__ noise, int n_paths,
-                                                                   int length, float* __restrict__ out, PrimeDev PR, StreamDev ST, ScoreDev SC) {
+                                                                   int length, float* __restrict__ out, PrimeDev PR, StreamDev ST, ScoreDev SC,
+                                                                   MemberDev MB) {
     static_assert(PRIMED || !STREAM, "a stream segment is a primed scan");
     static_assert(STREAM || !SCORE, "a scored segment is a stream segment");
+    static_assert(STREAM || !BANK, "a bank launch is a stream segment");
+    static_assert(!BANK || (!SAVE && F16), "a bank keeps no stash and runs the default arithmetic");
+    if constexpr (BANK) {                                            // the member's tables (a plain instance: no code, P and W as handed in)
+        P = member_view<BANK>(P);
+        W = rho_bank_view(W, blockIdx.y * P.bank_stride);
+    }
     __shared__ __attribute__((aligned(16))) float Urow[WAVES][32 * RRLD];
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int b = blockIdx.x * WAVES + w;
     if (b >= n_paths) return;
+    // the path among all members' (a plain instance: (size_t)b where it stood, so that the plain kernels stay what they were)
+    const auto g = [&] { return member_path<BANK>(n_paths, b); };
+    if constexpr (BANK) {
+        noise += blockIdx.y * MB.noise;
+        PR.prime += blockIdx.y * MB.audio;
+    }
     const int r = W.rank;
     const int col = lane & 31, hk = lane >> 5;
     float* U = &Urow[w][0];
@@ -720,7 +739,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_sample_rho_mfma(Dev P, RhoDev
         nr = 1.001f * sqrtf(sum64(fr));
     }
     const float* rin = nullptr;                                      // (STREAM) this path's record to carry on from
-    if constexpr (STREAM) rin = ST.in ? ST.in + (size_t)b * ST.rec : nullptr;
+    if constexpr (STREAM) rin = ST.in ? ST.in + g() * ST.rec : nullptr;
     for (int a = 0; a < 32; ++a) {                                   // rows a < rank of U = phi_a (model.py:127-136), the rest zero
         float v = 0.f;
         if (a < r) {
@@ -734,10 +753,10 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_sample_rho_mfma(Dev P, RhoDev
         U[a * RRLD + lane] = v;
     }
     const float* nrow = noise + (size_t)b * length;
-    float* orow = out + (size_t)b * length;
+    float* orow = out + g() * length;
     const int PF = PRIMED ? PR.PF : 0, nsteps = PF + length;        // (unprimed: nsteps = length)
     const float* prow = PRIMED ? PR.prime + (size_t)b * PR.stride : nullptr;      // (stride 0: one clip shared by all paths)
-    float* drow = PRIMED && PR.pred ? PR.pred + (size_t)b * PF : nullptr;
+    float* drow = PRIMED && PR.pred ? PR.pred + g() * PF : nullptr;
     float2* st = SAVE ? reinterpret_cast<float2*>(W.stash) + (size_t)b * nsteps * r * WAVE_ROW_PAIRS : nullptr;
     const float A = dev_A(P);
     const float sgn = (col & 1) ? 1.f : -1.f;                        // Im lanes add rho_y * partner, Re lanes subtract it
@@ -748,8 +767,8 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_sample_rho_mfma(Dev P, RhoDev
     [[maybe_unused]] float loss = 0.f;                               // SCORE: the path's running loss (model.py:155)
     [[maybe_unused]] float* lrow = nullptr;
     if constexpr (SCORE) {
-        if (rin) loss = SC.loss[b];
-        if (SC.nll) lrow = SC.nll + (size_t)b * PF;
+        if (rin) loss = SC.loss[g()];
+        if (SC.nll) lrow = SC.nll + g() * PF;
     }
     for (int kbeg = 0; kbeg < nsteps; kbeg += CH) {
         const int cnt = (nsteps - kbeg) < CH ? (nsteps - kbeg) : CH;
@@ -912,11 +931,11 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_sample_rho_mfma(Dev P, RhoDev
         }
     }
     if constexpr (SCORE) {
-        if (lane == 0) SC.loss[b] = loss;
+        if (lane == 0) SC.loss[g()] = loss;
     }
     if constexpr (STREAM) {
         if (ST.out) {                                                // (in == out: this wave read its record before the first step)
-            float* rec = ST.out + (size_t)b * ST.rec;
+            float* rec = ST.out + g() * ST.rec;
             for (int a = 0; a < r; ++a) rec[a * 64 + lane] = U[a * RRLD + lane];
             if (lane == 0) rec[64 * r] = samp;
         }
@@ -941,9 +960,16 @@ hipError_t launch_sample_rho_mfma(const Dev& P, const RhoDev& W, const SampleDev
         return dispatch_bool(f16, [&](auto hf) {
             return dispatch_sample_mode(sample_mode(S), [&](auto mode) {
                 constexpr int M = decltype(mode)::value;
-                hipLaunchKernelGGL((k_sample_rho_mfma<decltype(sv)::value, decltype(hf)::value, M >= SAMPLE_PRIMED, M >= SAMPLE_STREAM, M == SAMPLE_SCORE>),
-                                   dim3(nb), dim3(64 * WAVES), 0, s, P, W, S.noise, S.n, S.length, S.out, S.PR, stream_of(S), score_of(S));
-                return hipGetLastError();
+                constexpr bool SV = decltype(sv)::value, HF = decltype(hf)::value;
+                return dispatch_bool(S.MB.M > 0, [&](auto bank) {
+                    // (cmps_rho_bank_stream*: stream segments without a stash, in the default arithmetic; nothing else has a BANK instance)
+                    constexpr bool BANK = decltype(bank)::value && M >= SAMPLE_STREAM && !SV && HF;
+                    if (decltype(bank)::value && !BANK) return hipErrorInvalidValue;
+                    hipLaunchKernelGGL((k_sample_rho_mfma<SV, HF, M >= SAMPLE_PRIMED, M >= SAMPLE_STREAM, M == SAMPLE_SCORE, BANK>),
+                                       dim3(nb, BANK ? S.MB.M : 1), dim3(64 * WAVES), 0, s, P, W, S.noise, S.n, S.length, S.out, S.PR,
+                                       stream_of(S), score_of(S), S.MB);
+                    return hipGetLastError();
+                });
             });
         });
     });

@@ -17,8 +17,9 @@ normals of (--seed, path, step), so --segment then changes no bit of the wavefor
 (SampleStream.score; cmps_psi_stream_score / cmps_rho_stream_score), in segments of --segment steps when given.  Writes ``nll.npy`` (float32
 [clips, T' - 1]: the negative log-likelihood of every sample, model.py:293-294 / :166, 169-170) and ``pred.npy`` (the model's expected increments) into --out_dir and prints
 the total and the mean per sample; returns the nll array.
-``--bankdir DIR`` (a directory BankTrainer.save wrote: bank.json + model.<m>.ckpt.npz, PsiCMPS members) does the same with every member
-of the bank at once (PsiBank.open_stream; cmps_bank_stream / cmps_bank_stream_score), every member hearing the same noise: sampling writes
+``--bankdir DIR`` (a directory BankTrainer.save wrote: bank.json + model.<m>.ckpt.npz; PsiCMPS members, or RhoCMPS members where bank.json says
+rho_mps) does the same with every member of the bank at once (PsiBank.open_stream / RhoBank.open_stream; cmps_bank_stream* /
+cmps_rho_bank_stream*), every member hearing the same noise: sampling writes
 ``sample_m<m>_<i>.wav`` and ``samples.npy`` [M, num_samples, samples]; --prime continues one clip with every member; --score writes
 ``nll.npy`` ([M, T' - 1] for one clip, else [M, clips, T' - 1]) and ``pred.npy`` and prints one line per member and the best member.
 Run:  python -m audio_mps_amd.sample --modeldir=LOGDIR --sample_duration=16000 --prime=clip.wav
@@ -98,7 +99,7 @@ def build_parser():
                    "instead of a host Generator")
     p.add_argument("--segment", type=int, default=None, metavar="S", help="run through a resumable stream in segments of S steps")
     p.add_argument("--bankdir", default=None, metavar="DIR", help="a directory BankTrainer.save wrote (bank.json + model.<m>.ckpt.npz): sample, "
-                   "continue or score with every member of a PsiCMPS bank at once, instead of --modeldir")
+                   "continue or score with every member of a PsiCMPS or RhoCMPS bank at once, instead of --modeldir")
     p.add_argument("--out_dir", default="./samples")
     p.add_argument("--kernel_variant", type=int, default=0, help="as in audio_mps_amd.train")
     return p
@@ -168,27 +169,36 @@ def build_model(variables: dict, sample_rate: int, hparams: str = "", kernel_var
 
 
 def load_bank(bankdir: str, sample_rate: int, hparams: str = "", kernel_variant: int = 0, backend=None):
-    """The PsiBank a directory written by BankTrainer.save holds, every member with its checkpoint's variables."""
+    """The PsiBank (a bank.json of rho_mps: the RhoBank) a directory written by BankTrainer.save holds, every member with its checkpoint's
+    variables; bond_dim (and initial_rank) are read from their shapes, as `build_model` does."""
     import json
-    from .bank import BankTrainer, PsiBank
+    from .bank import BankTrainer, PsiBank, RhoBank
     path = os.path.join(bankdir, "bank.json")
     if not os.path.exists(path):
         raise FileNotFoundError(f"no bank at {path} (--bankdir: a directory BankTrainer.save wrote)")
     with open(path) as f:
         meta = json.load(f)
-    if meta.get("model", PsiBank.MODEL_NAME) != PsiBank.MODEL_NAME:
-        raise ValueError(f"{path} was written by a bank of {meta['model']} models: --bankdir samples and scores PsiCMPS banks only "
-                         f"(take a member's checkpoint with --modeldir)")
+    name = meta.get("model", PsiBank.MODEL_NAME)
+    if name not in (PsiBank.MODEL_NAME, RhoBank.MODEL_NAME):
+        raise ValueError(f"{path} was written by a bank of {name} models: --bankdir knows {PsiBank.MODEL_NAME} and {RhoBank.MODEL_NAME}")
+    rho = name == RhoBank.MODEL_NAME
     variables = [load_variables(BankTrainer.member_path(bankdir, m)) for m in range(len(meta["members"]))]
-    if any("psi_x" not in v for v in variables):
-        raise ValueError(f"{bankdir}: a member's checkpoint holds no psi_x (PsiCMPS)")
     hp = HParams(delta_t=1.0 / sample_rate, h_reg=200.0 / (math.pi * sample_rate) ** 2)       # train.py:41-43
-    hp.bond_dim = int(variables[0]["psi_x"].shape[0])
+    if rho:
+        if any("Wx" not in v or "Wy" not in v for v in variables):
+            raise ValueError(f"{bankdir}: bank.json says {name}, but a member's checkpoint holds no Wx / Wy (RhoCMPS)")
+        hp.initial_rank, hp.bond_dim = (int(x) for x in variables[0]["Wx"].shape)
+    else:
+        if any("psi_x" not in v for v in variables):
+            raise ValueError(f"{bankdir}: a member's checkpoint holds no psi_x (PsiCMPS)")
+        hp.bond_dim = int(variables[0]["psi_x"].shape[0])
     hp.parse(hparams)
     if backend is None:
         from .scan import HipScan
         backend = HipScan(hp.bond_dim, variant=kernel_variant)
-    bank = PsiBank(hp, meta["members"], backend=backend)
+    if rho and not (hasattr(backend, "rho_bank_stream") or hasattr(backend, "rho_stream")):
+        raise ValueError(f"{path} holds a bank of {name} models: {type(backend).__name__} has neither rho_bank_stream nor rho_stream")
+    bank = (RhoBank if rho else PsiBank)(hp, meta["members"], backend=backend)
     for m, (model, var) in enumerate(zip(bank.models, variables)):
         for k in model.variables:
             if var[k].shape != model.variables[k].shape:

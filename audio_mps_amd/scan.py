@@ -53,7 +53,7 @@ class _Bank:
     M: int = 0
     rank: int = 0                             # columns of every member's rho_0 ("rho_bank"; else 0)
     saved: Optional[tuple] = None             # the last forward's (audio, loss, n_audio): the reverse pass reads both tensors
-    params: Optional[torch.Tensor] = None     # the rows bank_set_params uploaded: the scans read A from them
+    params: Optional[object] = None           # the rows bank_set_params / rho_bank_set_state uploaded: the scans read A from them
     scratch: Optional[torch.Tensor] = None    # of the apply-step entries; sized by (D, rank, M) alone, so it is handed on from mode to mode
 
 
@@ -784,29 +784,46 @@ class HipScan:
                                        want_nll, want_pred, n, loss)
 
     # ------------------------------------------------------------------
-    # A bank's streams (cmps_bank_stream*): `stream` / `stream_score` with a leading member axis on everything a path writes or carries
+    # A bank's streams (cmps_bank_stream*, cmps_rho_bank_stream*): `stream` / `stream_score` with a leading member axis on everything a
+    # path writes or carries.  One driver per operation; `kind` is a key of BANK_SETTER and the prefix of the public methods' names.
+    @staticmethod
+    def _param_rows(D: int, members) -> np.ndarray:
+        fields = layout.param_fields(D, with_A=True)
+        return np.stack([layout.pack(fields, {**layout.split("R", p.R), "freqs": p.freqs, **layout.split("psi0", p.psi0), "A": p.A})
+                         for p in members])
+
     def bank_set_params(self, members, B: int, T: int, train: bool = False):
         """cmps_bank_set_params_dev from host values: ``members`` is a list of EffectiveParams of one sigma and delta_t (A per member)."""
-        fields = layout.param_fields(self.D, with_A=True)
-        rows = [layout.pack(fields, {**layout.split("R", p.R), "freqs": p.freqs, **layout.split("psi0", p.psi0), "A": p.A}) for p in members]
-        params = torch.from_numpy(np.stack(rows)).to(self.device)
+        params = torch.from_numpy(self._param_rows(self.D, members)).to(self.device)
         self.bank_set_params_dev(params, members[0].sigma, members[0].delta_t, B, T, train=train)
         self._bank.params = params
 
-    def bank_stream_state(self, n: int) -> torch.Tensor:
-        """Device memory for the stream-state records of ``n`` paths of every member (cmps_bank_stream_state_bytes)."""
-        self._bank_of("bank", "bank_stream_state")
-        return self._stream_state(self._lib.cmps_bank_stream_state_bytes, n, " (or the handle holds no PsiCMPS bank)")
+    def rho_bank_set_state(self, members, columns, B: int, T: int, train: bool = False):
+        """cmps_rho_bank_set_state_dev from host values: ``members`` as for `bank_set_params` (psi0 is not read by a RhoCMPS scan),
+        ``columns`` every member's phi [rank, D] complex (rho_0 = sum_a phi_a phi_a^dagger), one rank for all."""
+        columns = [np.asarray(c) for c in columns]
+        rank = columns[0].shape[0]
+        if len(columns) != len(members) or any(c.shape != (rank, self.D) for c in columns):
+            raise ValueError("columns must be one [rank, D] array per member, of one rank")
+        fields = layout.phi_fields(self.D, rank)
+        params = torch.from_numpy(self._param_rows(self.D, members)).to(self.device)
+        phi = torch.from_numpy(np.stack([layout.pack(fields, layout.split("phi", c)) for c in columns])).to(self.device)
+        self.rho_bank_set_state_dev(params, phi, rank, members[0].sigma, members[0].delta_t, B, T, train=train)
+        self._bank.params = (params, phi)
 
-    def bank_stream(self, state_in: Optional[torch.Tensor], state_out: Optional[torch.Tensor], k0: int, audio, noise, want_pred: bool = False,
-                    n: Optional[int] = None, length: Optional[int] = None, n_noise: Optional[int] = None):
-        """cmps_bank_stream: `stream` for every member of the bank at once.  ``audio`` [n_audio, forced + 1] with n_audio = 1 (one signal for
-        everybody), n (one per path, shared by the members) or M n, or None; ``noise`` [length, n_noise] (the reference's layout), a device
-        tensor [n_noise, length] or a NoisePlan -- drawn by ONE cmps_noise_fill over ``n_noise`` paths from path 0 -- with n_noise = n
-        (every member hears the same noise) or M n, or None.  ``n`` is required.  Returns (out [M, n, length], pred [M, n, forced] with
-        want_pred, else None)."""
-        M, n = self._bank_of("bank", "bank_stream").M, int(n)
-        self._stream_paths(self._lib.cmps_bank_stream_state_bytes, state_in, state_out, n, n)
+    def _bank_stream_entries(self, kind: str):
+        """(cmps_*_stream_state_bytes, cmps_*_stream, cmps_*_stream_score) of a bank of `kind`"""
+        pre = "cmps_bank_stream" if kind == "bank" else "cmps_rho_bank_stream"
+        return getattr(self._lib, pre + "_state_bytes"), getattr(self._lib, pre), getattr(self._lib, pre + "_score")
+
+    def _bank_stream_state(self, kind: str, n: int) -> torch.Tensor:
+        self._bank_of(kind, kind + "_stream_state")
+        return self._stream_state(self._bank_stream_entries(kind)[0], n, f" (or the handle holds no {'PsiCMPS' if kind == 'bank' else 'RhoCMPS'} bank)")
+
+    def _bank_stream(self, kind: str, state_in, state_out, k0, audio, noise, want_pred, n, length, n_noise):
+        bytes_fn, fn, _ = self._bank_stream_entries(kind)
+        M, n = self._bank_of(kind, kind + "_stream").M, int(n)
+        self._stream_paths(bytes_fn, state_in, state_out, n, n)
         d_noise, rows, block = None, n, (None, 1, 0)
         if noise is not None:
             if n_noise is None and isinstance(noise, NoisePlan):
@@ -818,18 +835,48 @@ class HipScan:
             length = 0
         if audio is not None:
             block = self._audio_block(audio, 1, (1, n, M * n), f" with n_audio in (1, {n}, {M * n}) and forced >= 0")
-        return self._stream_launch(self._lib.cmps_bank_stream, state_in, state_out, k0, block, (_ptr(d_noise), rows, length), n, length, want_pred,
-                                   (M,))
+        return self._stream_launch(fn, state_in, state_out, k0, block, (_ptr(d_noise), rows, length), n, length, want_pred, (M,))
+
+    def _bank_stream_score(self, kind: str, state_in, state_out, k0, audio, want_nll, want_pred, n, loss):
+        bytes_fn, _, fn = self._bank_stream_entries(kind)
+        M, n = self._bank_of(kind, kind + "_stream_score").M, int(n)
+        self._stream_paths(bytes_fn, state_in, state_out, n, n)
+        block = self._audio_block(audio, 2, (1, n, M * n), f" with n_audio in (1, {n}, {M * n}) and forced >= 1")
+        return self._score_launch(fn, state_in, state_out, k0, block, want_nll, want_pred, n, loss, (M,))
+
+    def bank_stream_state(self, n: int) -> torch.Tensor:
+        """Device memory for the stream-state records of ``n`` paths of every member (cmps_bank_stream_state_bytes)."""
+        return self._bank_stream_state("bank", n)
+
+    def bank_stream(self, state_in: Optional[torch.Tensor], state_out: Optional[torch.Tensor], k0: int, audio, noise, want_pred: bool = False,
+                    n: Optional[int] = None, length: Optional[int] = None, n_noise: Optional[int] = None):
+        """cmps_bank_stream: `stream` for every member of the bank at once.  ``audio`` [n_audio, forced + 1] with n_audio = 1 (one signal for
+        everybody), n (one per path, shared by the members) or M n, or None; ``noise`` [length, n_noise] (the reference's layout), a device
+        tensor [n_noise, length] or a NoisePlan -- drawn by ONE cmps_noise_fill over ``n_noise`` paths from path 0 -- with n_noise = n
+        (every member hears the same noise) or M n, or None.  ``n`` is required.  Returns (out [M, n, length], pred [M, n, forced] with
+        want_pred, else None)."""
+        return self._bank_stream("bank", state_in, state_out, k0, audio, noise, want_pred, n, length, n_noise)
 
     def bank_stream_score(self, state_in: Optional[torch.Tensor], state_out: Optional[torch.Tensor], k0: int, audio, want_nll: bool = True,
                           want_pred: bool = False, n: Optional[int] = None, loss=None):
         """cmps_bank_stream_score: `stream_score` for every member of the bank at once; ``audio`` as in `bank_stream` (forced >= 1), ``loss``
         [M, n] the running loss to continue.  Returns (nll [M, n, forced] with want_nll else None, the running loss [M, n], pred
         [M, n, forced] with want_pred else None)."""
-        M, n = self._bank_of("bank", "bank_stream_score").M, int(n)
-        self._stream_paths(self._lib.cmps_bank_stream_state_bytes, state_in, state_out, n, n)
-        block = self._audio_block(audio, 2, (1, n, M * n), f" with n_audio in (1, {n}, {M * n}) and forced >= 1")
-        return self._score_launch(self._lib.cmps_bank_stream_score, state_in, state_out, k0, block, want_nll, want_pred, n, loss, (M,))
+        return self._bank_stream_score("bank", state_in, state_out, k0, audio, want_nll, want_pred, n, loss)
+
+    def rho_bank_stream_state(self, n: int) -> torch.Tensor:
+        """`bank_stream_state` for a RhoCMPS bank (cmps_rho_bank_stream_state_bytes)."""
+        return self._bank_stream_state("rho_bank", n)
+
+    def rho_bank_stream(self, state_in: Optional[torch.Tensor], state_out: Optional[torch.Tensor], k0: int, audio, noise,
+                        want_pred: bool = False, n: Optional[int] = None, length: Optional[int] = None, n_noise: Optional[int] = None):
+        """cmps_rho_bank_stream: `bank_stream` for a RhoCMPS bank (after rho_bank_set_state*), every argument and result as there."""
+        return self._bank_stream("rho_bank", state_in, state_out, k0, audio, noise, want_pred, n, length, n_noise)
+
+    def rho_bank_stream_score(self, state_in: Optional[torch.Tensor], state_out: Optional[torch.Tensor], k0: int, audio, want_nll: bool = True,
+                              want_pred: bool = False, n: Optional[int] = None, loss=None):
+        """cmps_rho_bank_stream_score: `bank_stream_score` for a RhoCMPS bank, every argument and result as there."""
+        return self._bank_stream_score("rho_bank", state_in, state_out, k0, audio, want_nll, want_pred, n, loss)
 
     # ------------------------------------------------------------------
     # legacy AudioMPS arithmetic (SURVEY 8f rank 2)

@@ -16,8 +16,9 @@ with ``device_noise=True`` draws the noise of a generated step on the device, as
 A RhoCMPS stream opened with ``keep_states=S`` also returns rho and the purity after every step of the last call (``st.states()``,
 ``st.purity()``), from a stash that holds S steps however long the run is -- behind a ``score`` call as behind a ``follow``.
 
-A ``BankStream`` (``PsiBank.open_stream``; cmps_bank_stream, cmps_bank_stream_score) is the same stream for every member of a PsiCMPS bank
-at once: results [M, num_paths, steps], ``total_nll`` [M, num_paths], ``ranking()`` and ``best()`` -- M models along one signal.
+A ``BankStream`` (``PsiBank.open_stream`` / ``RhoBank.open_stream``; cmps_bank_stream, cmps_bank_stream_score, cmps_rho_bank_stream,
+cmps_rho_bank_stream_score) is the same stream for every member of a bank at once: results [M, num_paths, steps], ``total_nll``
+[M, num_paths], ``ranking()`` and ``best()`` -- M models along one signal.
 """
 from __future__ import annotations
 
@@ -214,8 +215,9 @@ class SampleStream:
 
 
 class _MemberLoop:
-    """The three bank entries of HipScan (bank_stream_state, bank_stream, bank_stream_score) for a backend that lacks them: a loop over
-    one plain backend per member, as BankTrainer loops over plain steps.  A state is the list of the members' states."""
+    """The bank entries of HipScan (bank_stream_state, bank_stream, bank_stream_score and their rho_bank_* counterparts) for a backend that
+    lacks them: a loop over one plain backend per member, as BankTrainer loops over plain steps.  A state is the list of the members'
+    states."""
 
     def __init__(self, backends):
         self.backends = list(backends)
@@ -224,8 +226,10 @@ class _MemberLoop:
         for be, p in zip(self.backends, members):
             be.set_params(p, B, T, train=train)
 
-    def bank_stream_state(self, n):
-        return [be.stream_state(n) for be in self.backends]
+    def rho_bank_set_state(self, members, columns, B, T, train=False):
+        for be, p, phi in zip(self.backends, members, columns):
+            be.set_params(p, B, T, train=False)
+            be.rho_set_state(phi, B, T, train=train)
 
     def _member(self, rows, m, n, axis):
         """Member m's rows of an array shared by the members (1 or n rows) or holding M n"""
@@ -233,33 +237,61 @@ class _MemberLoop:
             return rows
         return np.take(rows, range(m * n, (m + 1) * n), axis=axis)
 
-    def bank_stream(self, state_in, state_out, k0, audio, noise, want_pred=False, n=None):
+    # one loop per operation; `pre` is "" (PsiCMPS members: stream_state, stream, stream_score) or "rho_"
+    def _state(self, pre, n):
+        return [getattr(be, pre + "stream_state")(n) for be in self.backends]
+
+    def _stream(self, pre, state_in, state_out, k0, audio, noise, want_pred=False, n=None):
         audio = None if audio is None else np.asarray(audio, dtype=np.float32)
         noise = None if noise is None else np.asarray(noise, dtype=np.float32)
-        res = [be.stream(None if state_in is None else state_in[m], None if state_out is None else state_out[m], k0,
-                         self._member(audio, m, n, 0), self._member(noise, m, n, 1), want_pred, n=n) for m, be in enumerate(self.backends)]
+        res = [getattr(be, pre + "stream")(None if state_in is None else state_in[m], None if state_out is None else state_out[m], k0,
+                                           self._member(audio, m, n, 0), self._member(noise, m, n, 1), want_pred, n=n)
+               for m, be in enumerate(self.backends)]
         return np.stack([r[0] for r in res]), (np.stack([r[1] for r in res]) if want_pred else None)
 
-    def bank_stream_score(self, state_in, state_out, k0, audio, want_nll=True, want_pred=False, n=None, loss=None):
+    def _score(self, pre, state_in, state_out, k0, audio, want_nll=True, want_pred=False, n=None, loss=None):
         audio = np.asarray(audio, dtype=np.float32)
-        res = [be.stream_score(None if state_in is None else state_in[m], None if state_out is None else state_out[m], k0,
-                               self._member(audio, m, n, 0), want_nll, want_pred, n=n, loss=None if loss is None else loss[m])
+        res = [getattr(be, pre + "stream_score")(None if state_in is None else state_in[m], None if state_out is None else state_out[m], k0,
+                                                 self._member(audio, m, n, 0), want_nll, want_pred, n=n, loss=None if loss is None else loss[m])
                for m, be in enumerate(self.backends)]
         pick = lambda i, want: np.stack([r[i] for r in res]) if want else None   # noqa: E731
         return pick(0, want_nll), np.stack([r[1] for r in res]), pick(2, want_pred)
 
+    def bank_stream_state(self, n):
+        return self._state("", n)
+
+    def bank_stream(self, *args, **kw):
+        return self._stream("", *args, **kw)
+
+    def bank_stream_score(self, *args, **kw):
+        return self._score("", *args, **kw)
+
+    def rho_bank_stream_state(self, n):
+        return self._state("rho_", n)
+
+    def rho_bank_stream(self, *args, **kw):
+        return self._stream("rho_", *args, **kw)
+
+    def rho_bank_stream_score(self, *args, **kw):
+        return self._score("rho_", *args, **kw)
+
 
 class _BankScan:
-    """What SampleStream asks of its model, answered by a PsiBank: the members' effective parameters as they are when the stream is opened,
-    on a backend of the stream's own."""
+    """What SampleStream asks of its model, answered by a PsiBank or a RhoBank: the members' effective parameters (RhoBank: and their
+    columns of rho_0) as they are when the stream is opened, on a backend of the stream's own."""
 
     def __init__(self, bank):
         self.members = [m.effective_params() for m in bank.models]
+        self.columns = [m.columns() for m in bank.models] if bank.rank else None
+        self._pre = "rho_bank_" if bank.rank else "bank_"            # the backend's entries of this kind of bank
         m0 = bank.models[0]
         self.sigma, self.delta_t = m0.sigma, m0.delta_t
         self._noise_seed = m0._noise_seed
         self.backend = bank.stream_backend()
-        if not hasattr(self.backend, "bank_stream"):
+        if not hasattr(self.backend, self._pre + "stream"):
+            if bank.rank and not hasattr(self.backend, "rho_stream"):
+                raise ValueError(f"open_stream: this backend streams PsiCMPS banks only: {type(self.backend).__name__} has neither "
+                                 "rho_bank_stream nor rho_stream (cmps_rho_bank_stream, cmps_rho_stream)")
             self.backend = _MemberLoop([self.backend] + [bank.stream_backend() for _ in self.members[1:]])
 
     def __len__(self):
@@ -271,19 +303,25 @@ class _BankScan:
         return self.backend
 
     def _prepare_stream(self, num_paths, max_steps, keep_states=0):
-        self.backend.bank_set_params(self.members, num_paths, max_steps + 1, train=False)
+        if self.columns is None:
+            self.backend.bank_set_params(self.members, num_paths, max_steps + 1, train=False)
+        else:
+            self.backend.rho_bank_set_state(self.members, self.columns, num_paths, max_steps + 1, train=False)
         return self.backend
 
     def _stream_entries(self, be):
-        return be.bank_stream_state, be.bank_stream
+        return getattr(be, self._pre + "stream_state"), getattr(be, self._pre + "stream")
 
     def _stream_score_entry(self, be):
-        return be.bank_stream_score
+        if self.columns is not None and isinstance(be, _MemberLoop) and not hasattr(be.backends[0], "rho_stream_score"):
+            raise ValueError(f"this backend scores PsiCMPS-only streams: {type(be.backends[0]).__name__} has no rho_stream_score "
+                             "(cmps_rho_stream_score)")       # (as RhoCMPS._stream_score_entry: said before anything runs)
+        return getattr(be, self._pre + "stream_score")
 
 
 class BankStream(SampleStream):
-    """Returned by ``PsiBank.open_stream`` / ``BankTrainer.open_stream``: a SampleStream of every member at once (cmps_bank_stream,
-    cmps_bank_stream_score).  Everything carries a leading member axis -- results [M, num_paths, steps], ``last`` and ``total_nll``
+    """Returned by ``PsiBank.open_stream`` / ``RhoBank.open_stream`` / ``BankTrainer.open_stream``: a SampleStream of every member at once
+    (cmps_bank_stream, cmps_bank_stream_score; a RhoBank: cmps_rho_bank_stream, cmps_rho_bank_stream_score).  Everything carries a leading member axis -- results [M, num_paths, steps], ``last`` and ``total_nll``
     [M, num_paths] -- and a block may be [m] / [1, m] (one signal for everybody), [num_paths, m] (shared by the members) or
     [M, num_paths, m].  Member m, path b gets the noise ``member(m).open_stream(num_paths, ..., seed=seed)`` would give path b, so what
     differs between two members' samples is the model and not the draw; ``independent_noise=True`` numbers the paths globally instead

@@ -665,8 +665,9 @@ int cmps_rho_apply_step(cmps_handle_t h, float* vars_dev, float* adam_m_dev, flo
  * CMPS_OPT_RANK1, CMPS_OPT_BWD_WAVES and CMPS_OPT_F16_SCALE_SHIFT -- the kernel set a plain handle picks there: k_fwd_rho_mfma (forward
  * with save_for_bwd = 0 at rank <= 8: k_fwd_rho_wave), k_bwd_wave2w on B rank virtual clips, the slab reduction, k_finalize and
  * k_rho_phi_from_slabs.  Out of scope and refused: rank <= 2, D > 32 and rank > 32 (the block and wide families), CMPS_VARIANT_BLOCK /
- * WAVE32, k_bwd_rho_mfma (CMPS_OPT_RHO_BWD = GEMM) and every other non-default option.  There are no multi-rank banks, no bank samplers or
- * streams (take a member out as a plain model) and no status words (RhoCMPS has none).
+ * WAVE32, k_bwd_rho_mfma (CMPS_OPT_RHO_BWD = GEMM) and every other non-default option.  There are no multi-rank banks and no status
+ * words (RhoCMPS has none).  Sampling, following and scoring with every member at once are cmps_rho_bank_stream /
+ * cmps_rho_bank_stream_score below; the state read-outs (cmps_rho_states, save_states) need a member taken out as a plain model.
  * Errors, all returned before the device is touched, every message starting with the entry's name: CMPS_ERR_UNSUPPORTED_D for D or rank
  * outside the scope; CMPS_ERR_STATE for another variant or a non-default option (checked at the forward and the reverse call too);
  * CMPS_ERR_BAD_ARG for null pointers, M outside [1, 1024], n_audio not in {1, M}, B < 1, T < 2, M B rank T beyond 2^31 - 1;
@@ -712,6 +713,48 @@ int cmps_rho_bank_apply_step(cmps_handle_t h, int M, float* vars_dev, float* ada
                              double global_batch, double bias_num, double bias_den, double beta1, double beta2, double epsilon,
                              const double* hyper_dev, int with_reg, float* params_dev, float* phi_dev, float* losses_dev, void* scratch_dev,
                              void* stream);
+
+/*
+ * ---- Model bank: stream, sample and score with M RhoCMPS models per launch ----
+ * Replaces: the Python loop of M plain cmps_rho_stream* handles over a trained RhoCMPS bank's members (the samples of every member,
+ * model.sample(3, sample_duration), train.py:82-85; one model per class following one signal, reader.py:9-66).  k_sample_rho_mfma puts
+ * one path on one wavefront and is bound by its serial chain: n = 3 paths of one model are three wavefronts.
+ *
+ * cmps_rho_bank_stream / cmps_rho_bank_stream_score are cmps_rho_stream / cmps_rho_stream_score (above: every convention of the segment,
+ * the one-sample overlap of the audio, the state rule, the exact cut, the running loss) without save_states, with the members as a
+ * second grid dimension of the same kernel; the argument lists and the array shapes are those of cmps_bank_stream / _score:
+ *   out_dev, noise_dev (n_noise == M * n)   [M][n][length]
+ *   pred_dev, nll_dev                       [M][n][forced]
+ *   loss_dev                                [M][n]
+ *   state_in_dev, state_out_dev             [M][n] records: cmps_rho_bank_stream_state_bytes(h, n) = M * cmps_rho_stream_state_bytes of
+ *                                           a plain handle of the same D and rank (records of 64 rank + 4 floats; 0 for a null handle,
+ *                                           n < 1, and outside RhoCMPS bank mode)
+ *   audio_dev                               [n_audio][forced + 1], n_audio in {1, n, M * n}
+ *   noise_dev                               [n_noise][length], n_noise in {n, M * n} (not looked at when length == 0)
+ * The promise: member m's slices of out, pred, nll, loss and the state records hold, bit for bit, what cmps_rho_stream /
+ * cmps_rho_stream_score give on a plain handle set to model m with the same T -- cmps_set_params_dev on row m of params_dev, then
+ * cmps_rho_set_state on member m's columns (phi_dev + m * 2 rank D: phi_re, then phi_im) -- fed member m's audio and noise rows.  A cut
+ * changes no bit, as for the plain stream.
+ * Scope: the RhoCMPS bank's own (D <= 32, 3 <= rank <= 32, CMPS_VARIANT_AUTO / WAVE, default options), where a plain handle picks
+ * k_sample_rho_mfma too.  There is no save_states: a bank has one T, the table length, and no separate stash capacity; a member taken
+ * out as a plain model keeps cmps_rho_states.  A saved cmps_rho_bank_loss_fwd stays valid across these calls (they write no stash).
+ * CMPS_ERR_STATE outside RhoCMPS bank mode (before any set_params, plain mode, legacy mode, a PsiCMPS bank) and for a variant or a
+ * non-default option set behind cmps_rho_bank_set_state_dev; the plain cmps_rho_stream* entries return CMPS_ERR_STATE in bank mode, and
+ * cmps_bank_stream* (the PsiCMPS bank's) refuse a RhoCMPS bank.  CMPS_ERR_BAD_ARG: n_audio not in {1, n, M * n}; n_noise not in
+ * {n, M * n} when length > 0; M * n * (forced + length) beyond 2^31 - 1; and everything the plain entries refuse (state_in_dev NULL <=>
+ * k0 == 0, the table rows with a message naming the needed T, null pointers, the counts).  Every message starts with the entry's name
+ * and is returned before the device is touched.
+ * Asynchronous on `stream`; never synchronises, allocates nothing, touches nothing outside the stated extents.  With
+ * CMPS_OPT_KERNEL_EVENTS the launch is recorded under the plain entries' names: k_sample_rho_mfma_stream, k_sample_rho_mfma_score.
+ */
+size_t cmps_rho_bank_stream_state_bytes(cmps_handle_t h, int n);
+int cmps_rho_bank_stream(cmps_handle_t h, const void* state_in_dev, void* state_out_dev, int k0,
+                         const float* audio_dev, int n_audio, int forced,
+                         const float* noise_dev, int n_noise, int length,
+                         int n, float* out_dev, float* pred_dev, void* stream);
+int cmps_rho_bank_stream_score(cmps_handle_t h, const void* state_in_dev, void* state_out_dev, int k0,
+                               const float* audio_dev, int n_audio, int forced, int n,
+                               float* nll_dev, float* loss_dev, float* pred_dev, void* stream);
 
 /*
  * The samplers' Gaussian noise, drawn on the device.  Replaces: tf.random_normal([length, n], stddev = sigma * sqrt(temp * delta_t)) inside
