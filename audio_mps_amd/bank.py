@@ -9,6 +9,10 @@
                      the plain kernels with a member grid dimension, so member m gets bit for bit what Trainer(device_step=True) gives
                      model m alone.  On a backend without the bank entries the trainer loops over plain steps of its members.
 
+  class bank         ``classes=[...]``: member m models the clips labelled classes[m] (a model per pitch).  It trains on
+                     ResidentDataset.class_batches ([M, B, T], one batch per member) and is judged as a classifier by
+                     ``BankTrainer.evaluate_classifier`` (cmps_bank_classify_stats: accuracy, cross-entropy, confusion matrix).
+
 Common to a bank: bond_dim, minibatch_size, sigma, delta_t, A, Adam's betas and epsilon.  Free per member: seed, learning_rate, h_reg, r_reg
 and the data.  Every member is sampled, followed and scored at once through ``open_stream`` (a BankStream: cmps_bank_stream*; a RhoBank:
 cmps_rho_bank_stream*), ``sample``, ``nll_per_step`` and ``classify``; for everything else a member is taken out as an ordinary model:
@@ -40,9 +44,14 @@ class PsiBank:
     MODEL_NAME = "psi_mps"        # --mps_model (train.py:18-20); written into a Rho bank's bank.json
     rank = 0                      # columns of rho_0 (RhoBank); 0: pure states
 
-    def __init__(self, hparams: HParams, members: Sequence[dict], backend=None):
+    def __init__(self, hparams: HParams, members: Sequence[dict], backend=None, classes: Optional[Sequence] = None,
+                 label_key: Optional[str] = None):
         if len(members) < 1:
             raise ValueError("a bank needs at least one member")
+        self.classes = None if classes is None else [c if isinstance(c, str) else int(c) for c in classes]     # member m models classes[m]
+        self.label_key = label_key          # the TFRecord feature the classes are values of (bank.json keeps it for evaluate / sample)
+        if self.classes is not None and (len(self.classes) != len(members) or len(set(self.classes)) != len(self.classes)):
+            raise ValueError(f"a class bank needs one distinct class per member: {len(members)} members, classes {self.classes}")
         self.hparams = hparams
         self.overrides: List[dict] = []
         for m, ov in enumerate(members):
@@ -65,6 +74,15 @@ class PsiBank:
     @property
     def bond_d(self) -> int:
         return int(self.hparams.bond_dim)
+
+    def member_of(self, label) -> int:
+        """The member that models class ``label`` of a class bank."""
+        if self.classes is None:
+            raise ValueError("member_of: this bank has no classes")
+        label = label if isinstance(label, str) else int(label)
+        if label not in self.classes:
+            raise ValueError(f"member_of: no member models class {label!r} (classes: {self.classes})")
+        return self.classes.index(label)
 
     # -- every member at once: stream, sample, score (cmps_bank_stream*, cmps_rho_bank_stream*) ---------------------------------
     def stream_backend(self):
@@ -127,8 +145,9 @@ class RhoBank(PsiBank):
     MODEL = RhoCMPS
     MODEL_NAME = "rho_mps"
 
-    def __init__(self, hparams: HParams, members: Sequence[dict], backend=None):
-        super().__init__(hparams, members, backend)
+    def __init__(self, hparams: HParams, members: Sequence[dict], backend=None, classes: Optional[Sequence] = None,
+                 label_key: Optional[str] = None):
+        super().__init__(hparams, members, backend, classes, label_key)
         self.rank = int(self.models[0].rank_rho_0)
 
 
@@ -268,6 +287,42 @@ class BankTrainer(ResidentState):
             raise ValueError("evaluate: the dataset yielded no batch")
         return [EvalResult.from_stats(be.read_stats(stats[m]), T, torch.cat(kept[m]).cpu().numpy() if keep_losses else None) for m in range(M)]
 
+    def evaluate_classifier(self, dataset, minibatch_size: Optional[int] = None, T: Optional[int] = None, keep_best: bool = False):
+        """The class bank judged as a classifier over every clip of ``dataset`` (a ResidentDataset; its labels, where it has some, are
+        looked up in ``bank.classes``): a ClassifierResult.  One pass of ``dataset.ordered``: the batches are shared, every batch costs ONE
+        bank forward and ONE cmps_bank_classify_stats launch, and the record comes back ONCE at the end (``keep_best``: and with it
+        every clip's decision, ``result.best`` [n_clips], -1 where no member gave a finite loss)."""
+        import torch
+        from .evaluate import ClassifierResult, pass_shape
+        be = self.bank.backend
+        if self.bank.classes is None:
+            raise ValueError("evaluate_classifier needs a class bank (PsiBank / RhoBank(..., classes=))")
+        if not (hasattr(be, "classify_stats") and hasattr(be, "read_classify_stats")):
+            raise ValueError("evaluate_classifier needs a backend that judges the members' losses on the device (classify_stats): "
+                             f"{type(be).__name__} has none")
+        mb, T, B_max = pass_shape(be, dataset, minibatch_size, self.bank.hparams.minibatch_size, T)
+        M = len(self.trainers)
+        if self.native:
+            self._configure(self._device_state(), B_max, T, False)
+            forward = lambda batch: self._forward(batch, save_for_bwd=False)                        # noqa: E731
+        else:
+            def forward(batch):
+                rows = []
+                for tr in self.trainers:
+                    rows.append(tr.model._forward_entry(tr.model._prepare(B_max, T, train=False))(batch, save_for_bwd=False).clone())
+                return torch.stack(rows)
+        labels = dataset.class_index(self.bank.classes) if dataset.labels is not None else None
+        best = torch.empty(dataset.n_clips, dtype=torch.int32, device=dataset.clips.device) if keep_best else None
+        stats = None
+        for first_id, batch in dataset.ordered(mb, T):
+            loss = forward(batch)
+            B = int(loss.shape[1])
+            stats = be.classify_stats(loss, None if labels is None else labels[first_id:first_id + B], first_id, stats, reset=stats is None,
+                                      best=None if best is None else best[first_id:first_id + B])
+        if stats is None:
+            raise ValueError("evaluate_classifier: the dataset yielded no batch")
+        return ClassifierResult.from_stats(be.read_classify_stats(stats, M), self.bank.classes, T, best.cpu().numpy() if keep_best else None)
+
     # -- checkpoints: model.<m>.ckpt.npz in the format of Trainer.save, bank.json with the members' overrides -----------
     @staticmethod
     def member_path(directory: str, m: int) -> str:
@@ -281,6 +336,8 @@ class BankTrainer(ResidentState):
         meta = {"members": self.bank.overrides, "adam_step": int(self.trainers[0].opt.t), "global_step": int(self.global_step)}
         if self.rank:                 # (a PsiCMPS bank's file stays as it was)
             meta["model"] = self.bank.MODEL_NAME
+        if self.bank.classes is not None:     # (and so does the file of a bank without classes)
+            meta["label_key"], meta["classes"] = self.bank.label_key, self.bank.classes
         tmp = os.path.join(directory, "bank.json.tmp")
         with open(tmp, "w") as f:
             json.dump(meta, f)
@@ -296,6 +353,8 @@ class BankTrainer(ResidentState):
             raise ValueError(f"{path} was written by a bank of {meta.get('model', PsiBank.MODEL_NAME)} models, this bank holds {self.bank.MODEL_NAME}")
         if meta["members"] != json.loads(json.dumps(self.bank.overrides)):
             raise ValueError(f"{path} was written by a bank of other members: {meta['members']}")
+        if meta.get("classes") != self.bank.classes:
+            raise ValueError(f"{path} was written by a bank of classes {meta.get('classes')}, this bank's are {self.bank.classes}")
         self.drop_device_state()      # the device-resident copy is rebuilt from the restored state
         for m, tr in enumerate(self.trainers):
             if not tr.restore(self.member_path(directory, m)):

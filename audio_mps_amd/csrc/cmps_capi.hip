@@ -1025,6 +1025,32 @@ int cmps_loss_stats(cmps_handle_t h, const float* loss_dev, int B, long long fir
     return CMPS_OK;
 }
 
+// The [M][B] losses of a bank forward judged as a classifier, folded into one record on the device: needs nothing of the handle either
+size_t cmps_bank_classify_stats_bytes(int M) {
+    if (M < 1 || M > CLASSIFY_MAX_M) return 0;
+    return CLASSIFY_HEAD_BYTES + sizeof(long long) * ((size_t)M * (size_t)M + (size_t)M);
+}
+
+int cmps_bank_classify_stats(cmps_handle_t h, const float* loss_dev, int M, int B, long long ld, const int* label_dev, long long first_id,
+                             int reset, void* stats_dev, int* best_dev, void* stream) {
+    if (!h) return CMPS_ERR_BAD_ARG;
+    if (!loss_dev) return fail(h, CMPS_ERR_BAD_ARG, "cmps_bank_classify_stats: loss_dev is a null pointer");
+    if (!stats_dev) return fail(h, CMPS_ERR_BAD_ARG, "cmps_bank_classify_stats: stats_dev is a null pointer");
+    if (((uintptr_t)stats_dev & 7) != 0) return fail(h, CMPS_ERR_BAD_ARG, "cmps_bank_classify_stats: stats_dev must be 8-byte aligned");
+    if (M < 1 || M > CLASSIFY_MAX_M) return fail(h, CMPS_ERR_BAD_ARG, "cmps_bank_classify_stats: need 1 <= M <= 1024");
+    if (B < 1) return fail(h, CMPS_ERR_BAD_ARG, "cmps_bank_classify_stats: need B >= 1");
+    if (ld < (long long)B) return fail(h, CMPS_ERR_BAD_ARG, "cmps_bank_classify_stats: ld must be at least B");
+    if (first_id < 0 || first_id > 9223372036854775807ll - (long long)B)
+        return fail(h, CMPS_ERR_BAD_ARG,
+                    "cmps_bank_classify_stats: need first_id >= 0 and first_id + B below 2^63 (an id is a signed 64-bit integer)");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    KBind kb(h);
+    KScope ks("k_classify_stats", s);
+    const hipError_t e = launch_classify_stats(loss_dev, M, B, ld, label_dev, first_id, reset, stats_dev, best_dev, s);
+    if (e != hipSuccess) return fail_hip(h, e, "cmps_bank_classify_stats");
+    return CMPS_OK;
+}
+
 int cmps_damped_sine_fill(cmps_handle_t h, unsigned long long seed, unsigned long long first_clip, int B, int T, double delta_t,
                           float* audio_dev, void* stream) {
     if (!h) return CMPS_ERR_BAD_ARG;

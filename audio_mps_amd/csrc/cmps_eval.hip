@@ -10,6 +10,7 @@
 // what the record held (reset == 0) or in its place, and writes it with plain stores.  Assignment and tree are fixed, and the update is
 // ordered by the stream, so the same sequence of calls gives the same bits on every run.  A batch is a few thousand floats: one workgroup
 // reads it in a few microseconds, and more of them would need the second pass or the atomics this kernel does without.
+// k_classify_stats (cmps_bank_classify_stats), further down: the [M][B] losses of a bank of one model per class judged as a classifier.
 #include "cmps_internal.h"
 
 namespace cmps {
@@ -85,11 +86,125 @@ __global__ __launch_bounds__(STATS_NT) void k_loss_stats(const float* __restrict
     }
 }
 
+// k_classify_stats (cmps_bank_classify_stats): the [M][B] losses of a bank forward judged as a classifier, into the record of include/cmps.h
+// (tests/_classify_ref.py restates it).  ONE workgroup of STATS_NT threads, as k_loss_stats: thread t takes clips t, t + STATS_NT, ... in that
+// order and walks the M losses of each (loss[m * ld + b]: neighbouring threads read neighbouring floats, every load of a member's row is
+// coalesced); its two double sums and seven integers go through the same binary tree in LDS, and thread 0 merges the result behind (or in
+// place of) the header.  The confusion matrix and unlabelled_best are integer counts: every thread adds its own clips with vector atomic
+// adds -- an integer sum does not depend on the order -- after all threads have zeroed them where reset says so.
+struct alignas(8) ClassifyHead {       // the header of the record of include/cmps.h (cmps_bank_classify_stats), field for field
+    double sum_xent, sum_margin;
+    long long n_decided, n_undecided, n_unlabelled, n_correct, n_xent, n_margin, first_undecided;
+};
+static_assert(sizeof(ClassifyHead) == 72, "the header of cmps_bank_classify_stats is 72 bytes");
+
+__device__ __forceinline__ void classify_merge(ClassifyHead& a, const ClassifyHead& b) {
+    a.sum_xent += b.sum_xent;
+    a.sum_margin += b.sum_margin;
+    a.n_decided += b.n_decided;
+    a.n_undecided += b.n_undecided;
+    a.n_unlabelled += b.n_unlabelled;
+    a.n_correct += b.n_correct;
+    a.n_xent += b.n_xent;
+    a.n_margin += b.n_margin;
+    if (b.first_undecided >= 0 && (a.first_undecided < 0 || b.first_undecided < a.first_undecided)) a.first_undecided = b.first_undecided;
+}
+
+__device__ __forceinline__ bool is_finite_f32(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
+
+// grid 1
+__global__ __launch_bounds__(STATS_NT) void k_classify_stats(const float* __restrict__ loss, int M, int B, long long ld,
+                                                             const int* __restrict__ label, long long first_id, int reset,
+                                                             ClassifyHead* __restrict__ head, int* __restrict__ best_out) {
+    __shared__ ClassifyHead part[STATS_NT];
+    const int tid = threadIdx.x;
+    unsigned long long* confusion = reinterpret_cast<unsigned long long*>(head + 1);          // [M][M], then unlabelled_best [M]
+    unsigned long long* unlabelled_best = confusion + (size_t)M * (size_t)M;
+    if (reset) {
+        const size_t n = (size_t)M * (size_t)M + (size_t)M;
+        for (size_t i = tid; i < n; i += STATS_NT) confusion[i] = 0ull;
+        __threadfence();              // the zeros are in place before any thread of the workgroup adds to them
+        __syncthreads();
+    }
+    ClassifyHead r{0.0, 0.0, 0ll, 0ll, 0ll, 0ll, 0ll, 0ll, -1ll};
+    for (int b = tid; b < B; b += STATS_NT) {
+        const float* col = loss + b;
+        float l1 = __uint_as_float(0x7f800000u), l2 = l1;                                     // smallest and second-smallest finite loss
+        int best = -1, n_finite = 0;
+#pragma unroll 8
+        for (int m = 0; m < M; ++m) {
+            const float x = col[(long long)m * ld];
+            if (is_finite_f32(x)) {
+                ++n_finite;
+                if (x < l1) { l2 = l1; l1 = x; best = m; }                                    // (strict: the lowest m keeps a tie)
+                else if (x < l2) l2 = x;
+            }
+        }
+        if (best_out) best_out[b] = best;
+        if (n_finite == 0) {
+            r.n_undecided += 1;
+            if (r.first_undecided < 0) r.first_undecided = first_id + (long long)b;           // (a thread's ids arrive in increasing order)
+            continue;
+        }
+        r.n_decided += 1;
+        if (n_finite >= 2) {
+            r.sum_margin += (double)l2 - (double)l1;
+            r.n_margin += 1;
+        }
+        const int y = label ? label[b] : -1;
+        if (y < 0 || y >= M) {
+            r.n_unlabelled += 1;
+            atomicAdd(unlabelled_best + best, 1ull);
+            continue;
+        }
+        atomicAdd(confusion + (size_t)y * (size_t)M + (size_t)best, 1ull);
+        if (y == best) r.n_correct += 1;
+        const float xl = col[(long long)y * ld];
+        if (!is_finite_f32(xl)) continue;
+        double S = 0.0;                                                                       // sum over the finite members, in member order,
+#pragma unroll 4
+        for (int m = 0; m < M; ++m) {                                                         // of exp(-(loss_m - min)): 1 <= S <= M
+            const float x = col[(long long)m * ld];
+            if (is_finite_f32(x)) S += exp(-((double)x - (double)l1));
+        }
+        r.sum_xent += ((double)xl - (double)l1) + log(S);
+        r.n_xent += 1;
+    }
+    part[tid] = r;
+    __syncthreads();
+    for (int w = STATS_NT / 2; w >= 1; w >>= 1) {
+        if (tid < w) {
+            ClassifyHead a = part[tid];
+            classify_merge(a, part[tid + w]);
+            part[tid] = a;
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        ClassifyHead total = part[0];
+        if (!reset) {
+            ClassifyHead before = *head;
+            classify_merge(before, total);
+            total = before;
+        }
+        *head = total;
+    }
+}
+
 }  // namespace
 
 // The caller (cmps_loss_stats) has checked: B >= 1, first_id >= 0, first_id + B representable, stats 8-byte aligned
 hipError_t launch_loss_stats(const float* loss, int B, long long first_id, int reset, void* stats, hipStream_t s) {
     hipLaunchKernelGGL(k_loss_stats, dim3(1), dim3(STATS_NT), 0, s, loss, B, first_id, reset, static_cast<LossStats*>(stats));
+    return hipGetLastError();
+}
+
+// The caller (cmps_bank_classify_stats) has checked: 1 <= M <= 1024, B >= 1, ld >= B, first_id >= 0, first_id + B representable, stats
+// 8-byte aligned and of cmps_bank_classify_stats_bytes(M) bytes; label and best may be null
+hipError_t launch_classify_stats(const float* loss, int M, int B, long long ld, const int* label, long long first_id, int reset, void* stats,
+                                 int* best, hipStream_t s) {
+    hipLaunchKernelGGL(k_classify_stats, dim3(1), dim3(STATS_NT), 0, s, loss, M, B, ld, label, first_id, reset,
+                       static_cast<ClassifyHead*>(stats), best);
     return hipGetLastError();
 }
 

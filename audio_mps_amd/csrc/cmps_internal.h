@@ -509,6 +509,11 @@ hipError_t launch_batch_gather_i16(const short* data, long long n_clips, long lo
                                    float scale, float* audio, hipStream_t s);
 // cmps_eval.hip: loss[0 .. B), clip ids first_id + b, folded into the 64-byte record of include/cmps.h (reset: in place of what it held)
 hipError_t launch_loss_stats(const float* loss, int B, long long first_id, int reset, void* stats, hipStream_t s);
+// ... and loss[m * ld + b] of a bank forward judged as a classifier, into the record of cmps_bank_classify_stats (best[b]: the decision)
+constexpr int CLASSIFY_MAX_M = 1024;
+constexpr size_t CLASSIFY_HEAD_BYTES = 72;
+hipError_t launch_classify_stats(const float* loss, int M, int B, long long ld, const int* label, long long first_id, int reset, void* stats,
+                                 int* best, hipStream_t s);
 // floats of one path's stream record (StreamDev::rec), a multiple of 4: wave u, |y|^2 partial per lane, running sum | wide ut [2 DP], |y|^2
 // partial per wave [DP / 16], running sum | block u [2 D], running sum
 constexpr int STREAM_REC_WAVE = 132;

@@ -7,6 +7,8 @@
                      clip INDICES: tfrecord._shuffle draws from its Generator by the buffer's length alone, so fed indices and the
                      same seed it emits the positions of exactly the clips tfrecord.audio_batches emits -- the k-th batch holds the
                      same bits.  A plan is uploaded an epoch at a time as one int32 tensor and sliced per step.
+  ClassBatches       a labelled ResidentDataset (labels=, from_tfrecord(label_key=)) read as one stream per class, the reference's
+                     per-pitch input (reader.py:22-40), for a bank of one model per class: [M, B, T] per step from ONE gather of M B rows.
   DampedSineSource   the reference's synthetic batch (data.py:8-22) generated where it is used (HipScan.damped_sine,
                      cmps_damped_sine_fill): clip c of the run is a pure function of (seed, c, T, delta_t).
 
@@ -14,6 +16,8 @@ Both need a backend that has the two methods; one without them (the stand-ins of
 """
 from __future__ import annotations
 
+import threading
+import time
 from typing import Optional, Tuple
 
 import numpy as np
@@ -61,7 +65,7 @@ class ResidentDataset:
     of any batch -- allowed only where i * 2^-15 reproduces every sample bit for bit, else a ValueError naming the first offending clip and
     sample; "auto" takes int16 where that holds and float32 otherwise.  (An int16 tensor is taken as PCM as it is.)"""
 
-    def __init__(self, clips, backend, storage: str = "float32"):
+    def __init__(self, clips, backend, storage: str = "float32", labels=None):
         _need(backend, "gather_batch", "ResidentDataset")
         if storage not in STORAGES:
             raise ValueError(f"storage must be one of {STORAGES}, not {storage!r}")
@@ -81,6 +85,13 @@ class ResidentDataset:
                     raise _not_pcm16(0, bad, int(t.shape[1]), t.reshape(-1)[bad])
                 t = t if i is None else i
         self.clips = t.to(device=_device(backend)).contiguous()
+        self.labels = None             # with labels: a host array [n_clips], int64 or object (str), one label per clip
+        if labels is not None:
+            lab = np.asarray(labels)
+            lab = lab.astype(np.int64) if lab.dtype.kind in "iu" else np.array([str(x) for x in lab.reshape(-1)], dtype=object).reshape(lab.shape)
+            if lab.shape != (int(t.shape[0]),):
+                raise ValueError(f"labels must hold one label per clip ([{int(t.shape[0])}]), not {lab.shape}")
+            self.labels = lab
 
     @property
     def n_clips(self) -> int:
@@ -107,11 +118,13 @@ class ResidentDataset:
         return self.backend.gather_batch(self.clips, index, offset, T=T)
 
     @classmethod
-    def from_tfrecord(cls, path: str, sample_duration: int, backend, verify: bool = False, storage: str = "float32") -> "ResidentDataset":
+    def from_tfrecord(cls, path: str, sample_duration: int, backend, verify: bool = False, storage: str = "float32",
+                      label_key: Optional[str] = None) -> "ResidentDataset":
         """Reads the file once (tfrecord._audio_records: every record's "audio" must hold ``sample_duration`` values) and uploads it in
         chunks; the chunks are joined on the device, so twice the dataset is allocated for a moment at the end.  ``storage`` is decided
         and converted per chunk, on the host, so an int16 dataset is uploaded as int16; the first chunk that fails under "auto" converts
-        the chunks already stored back to float32, once."""
+        the chunks already stored back to float32, once.  ``label_key``: also keep every record's label (tfrecord.labelled_records) as
+        ``dataset.labels``."""
         _need(backend, "gather_batch", "ResidentDataset")
         if storage not in STORAGES:
             raise ValueError(f"storage must be one of {STORAGES}, not {storage!r}")
@@ -137,14 +150,20 @@ class ResidentDataset:
             chunks.append(t.to(dev))
             state["seen"] += len(cur)
             cur.clear()
-        for a in tfrecord._audio_records(path, L, verify):
+        labels = None if label_key is None else []
+        records = tfrecord._audio_records(path, L, verify) if label_key is None else tfrecord.labelled_records(path, L, label_key, verify)
+        for a in records:
+            if labels is not None:
+                a, label = a
+                labels.append(label)
             cur.append(a)
             if len(cur) == per_chunk:
                 flush()
         flush()
         if not chunks:
             raise ValueError(f"{path}: no records")
-        return cls(chunks[0] if len(chunks) == 1 else torch.cat(chunks), backend, storage="int16" if state["pcm"] else "float32")
+        return cls(chunks[0] if len(chunks) == 1 else torch.cat(chunks), backend, storage="int16" if state["pcm"] else "float32",
+                   labels=labels)
 
     def ordered(self, minibatch_size: int, T: Optional[int] = None):
         """Every clip once, in file order: yields (first_id, batch [B, T] on the device) with B = ``minibatch_size`` but for the short last
@@ -158,6 +177,24 @@ class ResidentDataset:
         plan = torch.arange(N, dtype=torch.int32).to(self.clips.device)
         for first in range(0, N, mb):
             yield first, self.gather(plan[first:first + mb], None, T)
+
+    def class_positions(self, classes) -> np.ndarray:
+        """Host int32 [n_clips]: each clip's position in ``classes``, -1 where its label is not among them."""
+        if self.labels is None:
+            raise ValueError("the dataset holds no labels (ResidentDataset(..., labels=) or from_tfrecord(..., label_key=))")
+        classes = list(classes)
+        if len(set(classes)) != len(classes):
+            raise ValueError(f"classes must be distinct: {classes}")
+        where = {(int(c) if self.labels.dtype != object else str(c)): m for m, c in enumerate(classes)}
+        return np.array([where.get(int(x) if self.labels.dtype != object else x, -1) for x in self.labels], dtype=np.int32)
+
+    def class_index(self, classes) -> torch.Tensor:
+        """``class_positions`` on the device: what cmps_bank_classify_stats reads as a clip's label."""
+        return torch.from_numpy(self.class_positions(classes)).to(self.clips.device)
+
+    def class_batches(self, classes, minibatch_size: int, seed: int = 0, shuffle_buffer: int = 24, crop: Optional[int] = None) -> "ClassBatches":
+        """A callable returning the next [M, B, T] batch, one [B, T] batch per class of ``classes``, forever (see ClassBatches)."""
+        return ClassBatches(self, classes, minibatch_size, seed, shuffle_buffer, crop)
 
     def batches(self, minibatch_size: int, seed: int = 0, order: str = "data", shuffle_buffer: int = 24, crop: Optional[int] = None,
                 crop_seed: int = 0) -> "BatchStream":
@@ -195,9 +232,9 @@ class BatchStream:
         self._sizes = []               # order="data": sizes of the planned batches still to come
 
     # -- planning (host; one upload per epoch) ----------------------------------------------------
-    def _epoch(self):
-        """Plan one more epoch and append it to what is left of the current plan."""
-        N = self.ds.n_clips
+    def _plan_epoch(self, N: int) -> np.ndarray:
+        """One more epoch over clips 0 .. N - 1, on the host: int32 [2 if crops else 1, n] -- the clip of every row to come, in order, and
+        its crop offset.  Draws from the stream's two Generators, so successive calls continue the sequence."""
         if self.order == "data":
             rows = [list(range(i, min(i + self.mb, N))) for i in range(0, N, self.mb)]
             rows = list(tfrecord._shuffle(iter(rows), self.buffer, self._rng))
@@ -209,6 +246,11 @@ class BatchStream:
         if self._crop:
             off = self._crop_rng.integers(0, self.ds.clip_len - self.T + 1, size=idx.size).astype(np.int32)
             plan = np.stack([idx, off])
+        return plan
+
+    def _epoch(self):
+        """Plan one more epoch and append it to what is left of the current plan."""
+        plan = self._plan_epoch(self.ds.n_clips)
         new = torch.from_numpy(np.ascontiguousarray(plan)).to(self.ds.clips.device)
         left = None if self._plan is None else self._plan[:, self._pos:]
         self._plan = new if left is None or left.shape[1] == 0 else torch.cat([left, new], dim=1)     # (joined on the device)
@@ -239,6 +281,103 @@ class BatchStream:
         index = self._plan[0, at + lo:at + hi]
         offset = self._plan[1, at + lo:at + hi] if self._crop else None
         return self.ds.gather(index, offset, self.T)
+
+
+class _ClassPlanner(BatchStream):
+    """The plan of ONE class of a ClassBatches, kept on the host: BatchStream's own epochs (order="estimator") over the class's clips
+    0 .. n - 1, translated to their positions ``ids`` in the whole dataset.  Never gathers."""
+
+    def __init__(self, dataset: ResidentDataset, ids: np.ndarray, minibatch_size: int, seed: int, shuffle_buffer: int, crop: Optional[int]):
+        super().__init__(dataset, minibatch_size, seed, "estimator", shuffle_buffer, crop, seed)
+        self.ids = np.asarray(ids, dtype=np.int32)
+        self._host = np.zeros((2 if self._crop else 1, 0), dtype=np.int32)
+
+    def take(self, n: int) -> np.ndarray:
+        """The next ``n`` rows of the class's stream: int32 [2 if crops else 1, n] (dataset clip, crop offset)."""
+        while self._host.shape[1] < n:
+            plan = self._plan_epoch(int(self.ids.size)).copy()
+            plan[0] = self.ids[plan[0]]
+            self._host = np.concatenate([self._host, plan], axis=1)
+        out, self._host = self._host[:, :n], self._host[:, n:]
+        return out
+
+
+class ClassBatches:
+    """``stream()`` -> the next [M, B, T] batch on the device, one [B, T] batch per class of ``classes``: the reference's per-pitch input
+    (reader.py:22-40: filter -> shuffle -> repeat -> batch) for every class at once.  Member m's k-th batch is bit for bit the k-th batch of
+    ``ResidentDataset(clips[ids_m]).batches(B, seed=seed + m, order="estimator", shuffle_buffer=..., crop=..., crop_seed=seed + m)`` with
+    ids_m the clips of class m in file order -- the order in which a class smaller than B still gives full batches.  One step is ONE
+    gather of M B rows out of the whole dataset; the rows (and crop offsets) of ``PLAN_STEPS`` steps are planned on the host, one planner
+    per class because the classes run out of epoch at different steps, and uploaded as one block, so most steps copy nothing to the device."""
+
+    PLAN_STEPS = 256
+
+    def __init__(self, dataset: ResidentDataset, classes, minibatch_size: int, seed: int = 0, shuffle_buffer: int = 24,
+                 crop: Optional[int] = None):
+        if dataset.labels is None:
+            raise ValueError("class_batches needs a dataset with labels (ResidentDataset(..., labels=) or from_tfrecord(..., label_key=))")
+        self.ds, self.classes, self.mb = dataset, list(classes), int(minibatch_size)
+        if not self.classes:
+            raise ValueError("class_batches needs at least one class")
+        index = dataset.class_positions(self.classes)
+        self.planners = []
+        for m, c in enumerate(self.classes):
+            ids = np.flatnonzero(index == m)
+            if ids.size == 0:
+                raise ValueError(f"class_batches: class {c!r} has no clip in the dataset")
+            self.planners.append(_ClassPlanner(dataset, ids, self.mb, int(seed) + m, shuffle_buffer, crop))
+        self.T, self._crop = self.planners[0].T, self.planners[0]._crop
+        self._block = None             # int32 device tensor [2 if crops else 1, steps, M * B]: the rows of the steps still to come
+        self._at = 0                   # steps of _block already handed out
+        self.uploads = 0               # blocks uploaded so far
+        self._ahead = None             # (worker thread, [its block or its exception]): the block behind the current one
+
+    def __len__(self) -> int:
+        return len(self.classes)
+
+    def _plan_block(self, steps: int, pause=lambda: None) -> np.ndarray:
+        """int32 [2 if crops else 1, steps, M * B]: step k's rows, class after class.  ``pause()`` is called after every class (the
+        worker yields the interpreter to the training loop there)."""
+        per_class = []                                                                         # each [rows, steps * B]
+        for p in self.planners:
+            per_class.append(p.take(steps * self.mb))
+            pause()
+        rows = per_class[0].shape[0]
+        return np.ascontiguousarray(np.stack([c.reshape(rows, steps, self.mb) for c in per_class], axis=2).reshape(rows, steps, -1))
+
+    def _plan_ahead(self):
+        """Start planning the next block on a worker thread: M B shuffle draws per step are host work of the order of a tenth of a
+        training step, done while the device works through the current block.  One worker at a time, joined before its block is used, so
+        the planners' Generators are drawn from in the same order as without it."""
+        box = []
+
+        def work():
+            try:
+                box.append(self._plan_block(self.PLAN_STEPS, pause=lambda: time.sleep(0)))
+            except BaseException as e:                                                  # re-raised by the caller's thread
+                box.append(e)
+        worker = threading.Thread(target=work, name="ClassBatches-plan", daemon=True)
+        worker.start()
+        self._ahead = (worker, box)
+
+    def _next_block(self) -> np.ndarray:
+        if self._ahead is None:
+            self._plan_ahead()
+        worker, box = self._ahead
+        worker.join()
+        self._ahead = None
+        if isinstance(box[0], BaseException):
+            raise box[0]
+        return box[0]
+
+    def __call__(self) -> torch.Tensor:
+        if self._block is None or self._at == self._block.shape[1]:
+            self._block = torch.from_numpy(self._next_block()).to(self.ds.clips.device)
+            self._at, self.uploads = 0, self.uploads + 1
+            self._plan_ahead()
+        k, self._at = self._at, self._at + 1
+        out = self.ds.gather(self._block[0, k], self._block[1, k] if self._crop else None, self.T)
+        return out.view(len(self.classes), self.mb, self.T)
 
 
 class DampedSineSource:

@@ -58,6 +58,55 @@ class EvalResult:
         return {f.name: getattr(self, f.name) for f in fields(self) if f.name != "losses"}
 
 
+@dataclass
+class ClassifierResult:
+    """A class bank judged as a classifier (BankTrainer.evaluate_classifier), from the record of cmps_bank_classify_stats."""
+    accuracy: float                # n_correct / n_labelled: over the decided clips with a label among the classes (NaN without any)
+    cross_entropy: float           # sum_xent / n_xent: mean -log p(label | clip) under a uniform prior (NaN while n_xent == 0)
+    mean_margin: float             # sum_margin / n_margin: mean gap between the best and the second-best member's loss
+    n_clips: int                   # clips evaluated: decided + undecided
+    n_labelled: int                # decided clips whose label is one of the bank's classes: the confusion matrix's total
+    n_correct: int
+    n_undecided: int               # clips under which no member's loss was finite
+    n_unlabelled: int              # decided clips without a label among the classes
+    first_undecided: int           # id of the first undecided clip, -1 when there is none
+    n_xent: int
+    n_margin: int
+    T: int
+    classes: list
+    confusion: np.ndarray          # int64 [M, M]: row = the clip's class, column = the member that won it
+    recall: np.ndarray             # float64 [M]: confusion[m, m] / confusion[m].sum() (NaN for a class without a decided clip)
+    unlabelled_best: np.ndarray    # int64 [M]: the decided unlabelled clips by the member that won them
+    best: Optional[np.ndarray] = None          # keep_best: int32 [n_clips], the winning member of every clip, -1 for undecided
+
+    @classmethod
+    def from_stats(cls, stats: dict, classes, T: int, best: Optional[np.ndarray] = None) -> "ClassifierResult":
+        conf = np.asarray(stats["confusion"], dtype=np.int64)
+        rows = conf.sum(axis=1)
+        n_lab = int(conf.sum())
+        nan = float("nan")
+        with np.errstate(invalid="ignore", divide="ignore"):
+            recall = np.where(rows > 0, np.diagonal(conf) / np.maximum(rows, 1), np.nan).astype(np.float64)
+        return cls(accuracy=int(stats["n_correct"]) / n_lab if n_lab else nan,
+                   cross_entropy=float(stats["sum_xent"]) / int(stats["n_xent"]) if stats["n_xent"] else nan,
+                   mean_margin=float(stats["sum_margin"]) / int(stats["n_margin"]) if stats["n_margin"] else nan,
+                   n_clips=int(stats["n_decided"]) + int(stats["n_undecided"]), n_labelled=n_lab, n_correct=int(stats["n_correct"]),
+                   n_undecided=int(stats["n_undecided"]), n_unlabelled=int(stats["n_unlabelled"]),
+                   first_undecided=int(stats["first_undecided"]), n_xent=int(stats["n_xent"]), n_margin=int(stats["n_margin"]), T=int(T),
+                   classes=list(classes), confusion=conf, recall=recall,
+                   unlabelled_best=np.asarray(stats["unlabelled_best"], dtype=np.int64), best=best)
+
+    def scalars(self) -> dict:
+        """The figures and the per-class recall, as a JSON line takes them (the matrix and ``best`` are files of their own)."""
+        out = {f.name: getattr(self, f.name) for f in fields(self) if f.name not in ("confusion", "recall", "unlabelled_best", "best")}
+        out["recall"] = [None if np.isnan(r) else float(r) for r in self.recall]
+        return out
+
+    def line(self) -> str:
+        return (f"accuracy={self.accuracy:.4f} xent={self.cross_entropy:.6g} margin={self.mean_margin:.6g} clips={self.n_clips} "
+                f"undecided={self.n_undecided}")
+
+
 def _need_stats(backend):
     if not (hasattr(backend, "loss_stats") and hasattr(backend, "read_stats")):
         raise ValueError(f"evaluate needs a backend that reduces the per-clip losses on the device (loss_stats): {type(backend).__name__} "
@@ -120,7 +169,36 @@ def build_parser():
     p.add_argument("--hparams", default="", help="as for training (r_reg, h_reg, sigma, delta_t must be the training run's)")
     p.add_argument("--kernel_variant", type=int, default=0, help="as in audio_mps_amd.train")
     p.add_argument("--json", action="store_true", help="print the result as one JSON line as well")
+    p.add_argument("--bankdir", default=None, metavar="DIR",
+                   help="instead of --modeldir: a class bank that train --bank_by saved (bank.json with its classes + model.<m>.ckpt.npz, "
+                        "either model), judged as a classifier on the dataset's labels; --per_clip then writes every clip's winning member "
+                        "(int32, -1: undecided)")
+    p.add_argument("--confusion", default=None, metavar="OUT.npy", help="with --bankdir: write the confusion matrix, int64 [M, M] "
+                   "(row = the clip's class, column = the member that won it)")
     return p
+
+
+def bank_main(args, backend=None) -> ClassifierResult:
+    """``--bankdir``: a saved class bank judged on a labelled TFRecord file (BankTrainer.evaluate_classifier)."""
+    from .bank import BankTrainer
+    from .device_data import ResidentDataset
+    from .sample import load_bank
+    bank = load_bank(args.bankdir, args.sample_rate, args.hparams, args.kernel_variant, backend)
+    if bank.classes is None or bank.label_key is None:
+        raise ValueError(f"{args.bankdir} holds a bank without classes: --bankdir judges what train --bank_by saved")
+    path = os.path.join(str(args.datadir), f"{args.dataset}.tfrecords")
+    if not os.path.exists(path):
+        raise FileNotFoundError(path)
+    ds = ResidentDataset.from_tfrecord(path, args.sample_duration, bank.backend, storage=args.storage, label_key=bank.label_key)
+    res = BankTrainer(bank).evaluate_classifier(ds, args.minibatch_size, keep_best=args.per_clip is not None)
+    if args.per_clip is not None:
+        np.save(args.per_clip, res.best)
+    if args.confusion is not None:
+        np.save(args.confusion, res.confusion)
+    print(f"eval {args.dataset}: {res.line()} classes={len(res.classes)} unlabelled={res.n_unlabelled} storage={ds.storage}")
+    if args.json:
+        print(json.dumps({"dataset": args.dataset, "storage": ds.storage, **res.scalars()}))
+    return res
 
 
 def main(argv=None, backend=None) -> EvalResult:
@@ -130,6 +208,10 @@ def main(argv=None, backend=None) -> EvalResult:
     args = build_parser().parse_args(argv)
     if args.sample_duration < 2 or args.minibatch_size < 1:
         raise ValueError("--sample_duration must be at least 2 and --minibatch_size positive")
+    if args.bankdir is not None:
+        return bank_main(args, backend)
+    if args.confusion is not None:
+        raise ValueError("--confusion is a class bank's (--bankdir)")
     model = build_model(load_variables(args.modeldir), args.sample_rate, args.hparams, args.kernel_variant, 0, backend)
     path = os.path.join(str(args.datadir), f"{args.dataset}.tfrecords")
     if not os.path.exists(path):

@@ -198,7 +198,7 @@ def load_bank(bankdir: str, sample_rate: int, hparams: str = "", kernel_variant:
         backend = HipScan(hp.bond_dim, variant=kernel_variant)
     if rho and not (hasattr(backend, "rho_bank_stream") or hasattr(backend, "rho_stream")):
         raise ValueError(f"{path} holds a bank of {name} models: {type(backend).__name__} has neither rho_bank_stream nor rho_stream")
-    bank = (RhoBank if rho else PsiBank)(hp, meta["members"], backend=backend)
+    bank = (RhoBank if rho else PsiBank)(hp, meta["members"], backend=backend, classes=meta.get("classes"), label_key=meta.get("label_key"))
     for m, (model, var) in enumerate(zip(bank.models, variables)):
         for k in model.variables:
             if var[k].shape != model.variables[k].shape:
@@ -230,10 +230,11 @@ def _bank_main(args, backend):
         np.save(os.path.join(args.out_dir, "nll.npy"), nll)
         np.save(os.path.join(args.out_dir, "pred.npy"), pred)
         totals = np.sum(st.total_nll, axis=1, dtype=np.float64)
+        named = (lambda m: f" (class {bank.classes[m]!r})") if bank.classes is not None else (lambda m: "")     # a class bank names its classes
         for m in range(M):
-            print(f"member {m}: total nll {totals[m]:.6g}, mean per sample {totals[m] / (n * N):.6g}, {bank.overrides[m]}")
+            print(f"member {m}{named(m)}: total nll {totals[m]:.6g}, mean per sample {totals[m] / (n * N):.6g}, {bank.overrides[m]}")
         best = int(np.argmin(np.where(np.isfinite(totals), totals, np.inf)))
-        print(f"best member {best} of {M} over {n} clip(s) of {N} steps; wrote nll.npy and pred.npy to {args.out_dir}")
+        print(f"best member {best}{named(best)} of {M} over {n} clip(s) of {N} steps; wrote nll.npy and pred.npy to {args.out_dir}")
         return nll
     prime = None if args.prime is None else CMPS._prime(load_prime(args.prime, args.sample_rate), n)
     P = 0 if prime is None else prime.shape[1] - 1

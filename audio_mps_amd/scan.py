@@ -146,7 +146,7 @@ class HipScan:
         return mode if mode in (_capi.CMPS_RANK1_EXACT_F32, _capi.CMPS_RANK1_BF16X2, _capi.CMPS_RANK1_F16X2) else _capi.CMPS_RANK1_BF16X3
 
     def kernel_events(self, on: bool):
-        """cmps_set_option(CMPS_OPT_KERNEL_EVENTS): bracket every kernel of forward() / backward() and of sample() / sample_primed() / stream() / stream_score() / rho_sample_primed() / rho_stream() / rho_stream_score() / draw_noise() / gather_batch() / loss_stats() / damped_sine() with HIP
+        """cmps_set_option(CMPS_OPT_KERNEL_EVENTS): bracket every kernel of forward() / backward() and of sample() / sample_primed() / stream() / stream_score() / rho_sample_primed() / rho_stream() / rho_stream_score() / draw_noise() / gather_batch() / loss_stats() / classify_stats() / damped_sine() with HIP
         events (a measurement aid, used by bench.py outside its timed region)."""
         _capi.check(self._h, self._lib.cmps_set_option(self._h, _capi.CMPS_OPT_KERNEL_EVENTS, 1 if on else 0))
 
@@ -593,6 +593,46 @@ class HipScan:
         """The record of loss_stats as a dict of Python numbers (_capi.LOSS_STATS's fields): the one device -> host copy of an evaluation."""
         rec = stats.cpu().numpy().view(_capi.LOSS_STATS)[0]
         return {k: (float(rec[k]) if _capi.LOSS_STATS[k].kind == "f" else int(rec[k])) for k in _capi.LOSS_STATS.names}
+
+    def classify_stats(self, loss: torch.Tensor, labels: Optional[torch.Tensor], first_id: int, stats: Optional[torch.Tensor] = None,
+                       reset: bool = False, best: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """cmps_bank_classify_stats: judge the losses ``loss`` [M, B] of a bank forward over one shared batch (float32 on this device, rows
+        contiguous; clip ids first_id .. first_id + B - 1) as a classifier and fold the result into the record ``stats`` (a uint8 device
+        tensor of cmps_bank_classify_stats_bytes(M) bytes this method allocates -- and resets -- when None), which it returns.
+        ``labels``: int32 [B] on this device, the member each clip belongs to (outside [0, M): unlabelled), or None for no labels;
+        ``best``: int32 [B] to receive each clip's decision.  No host copy, no synchronisation: read_classify_stats is the download."""
+        def on_dev(t, dtype, dim):
+            return isinstance(t, torch.Tensor) and t.device == self.device and t.dtype == dtype and t.dim() == dim
+        if not (on_dev(loss, torch.float32, 2) and loss.shape[0] >= 1 and loss.shape[1] >= 1 and loss.stride(1) == 1
+                and (loss.shape[0] == 1 or loss.stride(0) >= loss.shape[1])):
+            raise ValueError("classify_stats: loss must be a float32 tensor [M, B] with contiguous rows, M >= 1 and B >= 1, on the backend's "
+                             "device")
+        M, B = int(loss.shape[0]), int(loss.shape[1])
+        ld = int(loss.stride(0)) if M > 1 else B
+        for name, t in (("labels", labels), ("best", best)):
+            if t is not None and not (on_dev(t, torch.int32, 1) and t.is_contiguous() and int(t.numel()) == B):
+                raise ValueError(f"classify_stats: {name} must be a contiguous int32 tensor [B] on the backend's device")
+        nbytes = int(self._lib.cmps_bank_classify_stats_bytes(M))
+        if nbytes == 0:
+            raise ValueError(f"classify_stats: a record holds 1 .. {_capi.CLASSIFY_MAX_M} members, not {M}")
+        if stats is None:
+            stats, reset = torch.empty(nbytes, dtype=torch.uint8, device=self.device), True
+        elif not (on_dev(stats, torch.uint8, 1) and stats.numel() == nbytes and stats.is_contiguous()):
+            raise ValueError(f"classify_stats: stats must be a contiguous uint8 tensor of {nbytes} bytes on the backend's device")
+        _capi.check(self._h, self._lib.cmps_bank_classify_stats(
+            self._h, loss.data_ptr(), M, B, ld, labels.data_ptr() if labels is not None else None, int(first_id), 1 if reset else 0,
+            stats.data_ptr(), best.data_ptr() if best is not None else None, self._stream()))
+        return stats
+
+    @staticmethod
+    def read_classify_stats(stats: torch.Tensor, M: int) -> dict:
+        """The record of classify_stats: the header's fields as Python numbers (_capi.CLASSIFY_HEAD), ``confusion`` [M, M] and
+        ``unlabelled_best`` [M] as int64 arrays.  The one device -> host copy of a classifier evaluation."""
+        rec = stats.cpu().numpy().view(_capi.classify_stats_dtype(M))[0]
+        head = _capi.CLASSIFY_HEAD
+        out = {k: (float(rec["head"][k]) if head[k].kind == "f" else int(rec["head"][k])) for k in head.names}
+        out["confusion"], out["unlabelled_best"] = rec["confusion"].copy(), rec["unlabelled_best"].copy()
+        return out
 
     def damped_sine(self, seed: int, first_clip: int, B: int, T: int, delta_t: float) -> torch.Tensor:
         """cmps_damped_sine_fill: clips first_clip .. first_clip + B - 1 of the seed's synthetic damped-sine sequence (include/cmps.h),

@@ -205,18 +205,34 @@ def parse_example(data: bytes) -> Dict[str, np.ndarray]:
     return out
 
 
-def make_example(audio: np.ndarray) -> bytes:
-    """Serialised Example with one float_list feature "audio" (make-small-dataset.py:24-32)."""
+def _as_list(v) -> list:
+    return list(v) if isinstance(v, (list, tuple, np.ndarray)) else [v]
+
+
+def make_example(audio: np.ndarray, int64_features: Optional[dict] = None, bytes_features: Optional[dict] = None) -> bytes:
+    """Serialised Example with one float_list feature "audio" (make-small-dataset.py:24-32) and, behind it, the extra features given:
+    ``int64_features`` {name: int or list of ints} as Int64List (packed varints, as TensorFlow writes them), ``bytes_features``
+    {name: bytes / str (utf-8) or a list of them} as BytesList -- what NSynth's records carry next to the audio (pitch,
+    instrument_family_str).  With neither, the bytes are what they always were."""
     vals = np.ascontiguousarray(audio, dtype="<f4").tobytes()
     float_list = _enc_ld(1, vals)
     feature = _enc_ld(2, float_list)
-    entry = _enc_ld(1, b"audio") + _enc_ld(2, feature)
-    features = _enc_ld(1, entry)
+    features = _enc_ld(1, _enc_ld(1, b"audio") + _enc_ld(2, feature))
+    for name, v in (int64_features or {}).items():
+        packed = b"".join(_enc_varint(int(x) & 0xFFFFFFFFFFFFFFFF) for x in _as_list(v))
+        features += _enc_ld(1, _enc_ld(1, name.encode("utf-8")) + _enc_ld(2, _enc_ld(3, _enc_ld(1, packed))))
+    for name, v in (bytes_features or {}).items():
+        items = b"".join(_enc_ld(1, x.encode("utf-8") if isinstance(x, str) else bytes(x)) for x in _as_list(v))
+        features += _enc_ld(1, _enc_ld(1, name.encode("utf-8")) + _enc_ld(2, _enc_ld(1, items)))
     return _enc_ld(1, features)
 
 
-def write_audio_tfrecord(path: str, clips) -> None:
-    write_records(path, (make_example(c) for c in clips))
+def write_audio_tfrecord(path: str, clips, int64_features: Optional[dict] = None, bytes_features: Optional[dict] = None) -> None:
+    """One record per clip.  ``int64_features`` / ``bytes_features``: {name: a sequence with one entry per clip}, written next to
+    "audio" (make_example)."""
+    def extra(table, i):
+        return None if not table else {name: column[i] for name, column in table.items()}
+    write_records(path, (make_example(c, extra(int64_features, i), extra(bytes_features, i)) for i, c in enumerate(clips)))
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -246,6 +262,30 @@ def _audio_records(path: str, length: int, verify: bool) -> Iterator[np.ndarray]
         if a.shape[0] != length:          # FixedLenFeature([length]) rejects other sizes (data.py:32)
             raise ValueError(f"{path}: 'audio' has {a.shape[0]} values, FixedLenFeature expects {length}")
         yield a
+
+
+def labelled_records(path: str, length: int, label_key: str, verify: bool = False):
+    """Yields (audio float32 [length], label) per record: the label is the single value of feature ``label_key`` -- an int for an
+    Int64List (NSynth's "pitch", reader.py:22-40 filters on it), a str for a BytesList ("instrument_family_str", decoded as utf-8).  A record
+    without the key, or with other than exactly one value under it, is a ValueError naming the record."""
+    for n, rec in enumerate(read_records(path, verify=verify)):
+        ex = parse_example(rec)
+        if "audio" not in ex:
+            raise KeyError(f"{path}: record without an 'audio' feature")
+        a = np.asarray(ex["audio"], dtype=np.float32)
+        if a.shape[0] != length:
+            raise ValueError(f"{path}: 'audio' has {a.shape[0]} values, FixedLenFeature expects {length}")
+        if label_key not in ex:
+            raise ValueError(f"{path}: record {n} has no feature '{label_key}'")
+        v = ex[label_key]
+        if len(v) != 1:
+            raise ValueError(f"{path}: record {n} holds {len(v)} values under '{label_key}', a label is exactly one")
+        if isinstance(v, list):
+            yield a, v[0].decode("utf-8")
+        elif isinstance(v, np.ndarray) and v.dtype == np.int64:
+            yield a, int(v[0])
+        else:
+            raise ValueError(f"{path}: record {n}: feature '{label_key}' is a FloatList, a label is an Int64List or a BytesList")
 
 
 def audio_batches(path: str, minibatch_size: int, sample_duration: int, seed: int = 0, shuffle_buffer: int = 24,

@@ -266,6 +266,13 @@ def build_parser():
     p.add_argument("--bank_hparams", default="", metavar="SPEC",
                    help="train the Cartesian grid of 'learning_rate=1e-3,3e-3;r_reg=0.1,1' (learning_rate, h_reg, r_reg) at once; with --bank "
                         "every seed runs once per grid point")
+    p.add_argument("--bank_by", default=None, metavar="KEY",
+                   help="train one model per class at once (reader.py:9-66: a model per pitch): KEY is the TFRecord feature that labels "
+                        "every record (an Int64List such as pitch, a BytesList such as instrument_family_str); member m, seed --seed + m, "
+                        "trains on the clips of class m only.  Needs --device_data and a TFRecord dataset; with --eval_dataset the bank is "
+                        "judged as a classifier on the held-out file (BankTrainer.evaluate_classifier)")
+    p.add_argument("--bank_classes", default=None, metavar="A,B,C",
+                   help="with --bank_by: the classes, in member order (default: the sorted distinct labels of the dataset)")
     p.add_argument("--eval_storage", default="float32", choices=["float32", "int16", "auto"],
                    help="how a TFRecord held-out set is held on the device (int16: half the memory for 16-bit PCM data, the same bits)")
     return p
@@ -368,6 +375,10 @@ def main(argv=None, backend=None):
     else:
         dp = DataParallel(backend="gloo")
     start, count = dp.shard(hp.minibatch_size)
+    if args.bank_classes is not None and args.bank_by is None:
+        raise ValueError("--bank_classes names the classes of --bank_by KEY: it needs that flag")
+    if args.bank_by is not None:
+        return class_bank_main(args, hp, backend, dp)
     if args.bank or args.bank_hparams:
         return bank_main(args, hp, backend, dp)
     cls = RhoCMPS if args.mps_model == "rho_mps" else PsiCMPS                                   # train.py:50-53
@@ -430,6 +441,70 @@ def bank_main(args, hp, backend, dp):
         if time.time() - last_save > args.save_checkpoint_secs or it == args.max_steps - 1:
             trainer.save(logdir)
             last_save = time.time()
+    dp.close()
+    return trainer
+
+
+def parse_classes(spec: str, labels: np.ndarray) -> list:
+    """``--bank_classes a,b,c`` as values of the dataset's labels: ints where those are ints."""
+    items = [s.strip() for s in spec.split(",") if s.strip()]
+    if not items:
+        raise ValueError("--bank_classes names no class")
+    return items if labels.dtype == object else [int(s) for s in items]
+
+
+def class_bank_main(args, hp, backend, dp):
+    """``--bank_by KEY``: a labelled TFRecord dataset trained as one model per class, every member on the clips of its own class
+    (ResidentDataset.class_batches: one gather of M B rows per step), and -- with --eval_dataset -- judged as a classifier on a held-out
+    file while it trains (BankTrainer.evaluate_classifier: one forward and one reduction per batch, one download per pass)."""
+    from .bank import RHO_BANK_ENTRIES, BankTrainer, PsiBank, RhoBank
+    from .device_data import ResidentDataset
+    rho = args.mps_model == "rho_mps"
+    if args.bank or args.bank_hparams:
+        raise ValueError("--bank_by makes one member per class, seeds --seed + m: it does not go with --bank N or --bank_hparams")
+    if not args.device_data or args.dataset == "damped_sine":
+        raise ValueError("--bank_by needs --device_data and a TFRecord dataset: the classes are the values of a feature of its records, "
+                         "and every member's batch is gathered from the resident dataset (damped_sine has no labels)")
+    if args.host_optimizer:
+        raise ValueError("--bank_by runs the device-resident optimiser step of every member (cmps_bank_apply_step): no --host_optimizer")
+    if rho and not all(hasattr(backend, name) for name in RHO_BANK_ENTRIES):
+        raise ValueError("--bank_by --mps_model rho_mps needs a backend with the cmps_rho_bank_* entries (HipScan): this one "
+                         f"({type(backend).__name__}) has none")
+    if args.eval_dataset == "damped_sine":
+        raise ValueError("--bank_by judges the bank on a labelled TFRecord file: --eval_dataset damped_sine has no labels")
+    if (args.eval_every or args.eval_minibatch is not None) and not args.eval_dataset:
+        raise ValueError("--eval_every and --eval_minibatch need --eval_dataset")
+
+    def resident(name, storage):
+        path = os.path.join(str(args.datadir), f"{name}.tfrecords")
+        if not os.path.exists(path):
+            raise FileNotFoundError(path)
+        return ResidentDataset.from_tfrecord(path, args.sample_duration, backend, storage=storage, label_key=args.bank_by)
+    data = resident(args.dataset, "float32")
+    classes = parse_classes(args.bank_classes, data.labels) if args.bank_classes is not None else sorted(set(data.labels.tolist()))
+    bank = (RhoBank if rho else PsiBank)(hp, [{"seed": args.seed + m} for m in range(len(classes))], backend=backend, classes=classes,
+                                         label_key=args.bank_by)
+    trainer = BankTrainer(bank, dp)
+    logdir = f"{args.logdir}/{args.dataset}/{hp.bond_dim}_{hp.delta_t}_{hp.minibatch_size}"    # train.py:94
+    if trainer.restore(logdir):
+        print(f"Restoring {len(trainer)} members from {logdir} (global_step {trainer.global_step})")
+    stream = data.class_batches(classes, hp.minibatch_size, seed=args.seed, crop=args.crop_duration)
+    held_out = resident(args.eval_dataset, args.eval_storage) if args.eval_dataset else None
+    last_save = time.time()
+    for it in range(args.max_steps):
+        log_now = (it % max(args.log_every, 1) == 0) or it == args.max_steps - 1
+        out = trainer.step(stream(), sync=log_now)
+        if log_now:
+            print(bank_log_line(out))
+        if time.time() - last_save > args.save_checkpoint_secs or it == args.max_steps - 1:
+            trainer.save(logdir)
+            last_save = time.time()
+        if held_out is not None and ((args.eval_every > 0 and trainer.global_step % args.eval_every == 0) or it == args.max_steps - 1):
+            res = trainer.evaluate_classifier(held_out, args.eval_minibatch)
+            print(f"eval step={trainer.global_step} {res.line()}")
+            os.makedirs(logdir, exist_ok=True)
+            with open(os.path.join(logdir, "eval.jsonl"), "a") as f:
+                f.write(json.dumps({"global_step": trainer.global_step, **res.scalars()}) + "\n")
     dp.close()
     return trainer
 

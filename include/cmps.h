@@ -94,7 +94,7 @@ enum {
     CMPS_OPT_F16_SCALE_SHIFT = 4 /* DIAGNOSTIC, default 0: added to the exponent of every data-dependent fp16 scale of the wave reverse
                         * scan's F16X2 arithmetic (range -40 .. 40).  A positive value pushes the pieces out of fp16 range on purpose:
                         * how tests/test_gpu_parity.py provokes CMPS_ERR_F16_RANGE.  No reference counterpart. */,
-    CMPS_OPT_KERNEL_EVENTS = 2 /* 1: every kernel cmps_psi_loss_fwd / _bwd, cmps_rho_loss_fwd / _bwd, cmps_psi_sample, cmps_psi_sample_primed, cmps_psi_stream, cmps_psi_stream_score, cmps_rho_sample_primed, cmps_rho_stream, cmps_rho_stream_score, cmps_noise_fill (as k_noise_philox), cmps_batch_gather (as k_batch_gather), cmps_batch_gather_i16 (as k_batch_gather_i16), cmps_loss_stats (as k_loss_stats) and cmps_damped_sine_fill (as k_damped_sine) launch is bracketed by two HIP events on the caller's stream
+    CMPS_OPT_KERNEL_EVENTS = 2 /* 1: every kernel cmps_psi_loss_fwd / _bwd, cmps_rho_loss_fwd / _bwd, cmps_psi_sample, cmps_psi_sample_primed, cmps_psi_stream, cmps_psi_stream_score, cmps_rho_sample_primed, cmps_rho_stream, cmps_rho_stream_score, cmps_noise_fill (as k_noise_philox), cmps_batch_gather (as k_batch_gather), cmps_batch_gather_i16 (as k_batch_gather_i16), cmps_loss_stats (as k_loss_stats), cmps_bank_classify_stats (as k_classify_stats) and cmps_damped_sine_fill (as k_damped_sine) launch is bracketed by two HIP events on the caller's stream
                         * (read and reset with cmps_kernel_times); 0 (default): nothing is recorded.  A measurement aid -- the reference
                         * has no counterpart (no tracing / profiling hooks); bench.py uses it OUTSIDE its timed region to price
                         * each kernel of a multi-kernel family against the pipe it runs on */
@@ -863,6 +863,56 @@ typedef struct cmps_loss_stats_rec {
 } cmps_loss_stats_rec;
 int cmps_loss_stats(cmps_handle_t h, const float* loss_dev, int B, long long first_id,
                     int reset, void* stats_dev, void* stream);
+
+/*
+ * A bank of one model per class judged as a classifier, on the device: loss_dev[m * ld + b] (ld >= B) is the [M][B] output of
+ * cmps_bank_loss_fwd / cmps_rho_bank_loss_fwd over ONE shared batch, the loss of clip first_id + b under member m; label_dev[b] is the
+ * member that clip belongs to (a value outside [0, M): unlabelled; label_dev == NULL: every clip unlabelled); best_dev is [B] int or NULL.
+ * Replaces: nothing -- the reference trains a model per pitch (reader.py:9-66) and never judges them against each other.
+ * PER CLIP (normative; tests/_classify_ref.py restates it in numpy).  A NaN or +-Inf loss makes that member ABSENT for that clip.
+ *   best    the present member with the smallest loss (float32 compare; the lowest m on ties), written to best_dev[b].  No present member:
+ *           the clip is UNDECIDED, best = -1, and it enters n_undecided and first_undecided and nothing else.
+ *   margin  (second-smallest present loss) - (smallest), each widened to double first; over decided clips with at least two present members.
+ *   xent    -log p(label | clip), p = softmax(-loss) over the present members (a uniform prior), over labelled clips whose own member is
+ *           present:  xent = (loss[label] - lmin) + log(sum_m exp(-(loss[m] - lmin))),  lmin the smallest present loss, everything in double,
+ *           the sum in member order.  xent >= 0.
+ * THE RECORD (normative; little-endian, 8-byte aligned): the 72-byte header cmps_bank_classify_head below, then the counts
+ *   offset  type       field
+ *        0  double     sum_xent         over the n_xent clips
+ *        8  double     sum_margin       over the n_margin clips
+ *       16  long long  n_decided        clips with a best member, labelled or not
+ *       24  long long  n_undecided
+ *       32  long long  n_unlabelled     decided clips without a label in [0, M)
+ *       40  long long  n_correct        labelled decided clips with best == label
+ *       48  long long  n_xent
+ *       56  long long  n_margin
+ *       64  long long  first_undecided  the lowest id of an undecided clip; -1 while there is none
+ *       72  long long  confusion[M][M]  row = label, column = best: the labelled decided clips
+ *   72 + 8 M M  long long  unlabelled_best[M]   the decided unlabelled clips by best
+ * cmps_bank_classify_stats_bytes(M) = 72 + 8 M M + 8 M is the record's size; 0 for M outside [1, 1024].
+ * reset != 0 ignores what the record held (no memset is needed before the first call); reset == 0 continues it.  One workgroup, a fixed
+ * assignment of clips to threads and a fixed reduction tree for the header, and the update is ordered by the stream; the confusion counts
+ * are integer atomic adds, whose sum does not depend on the order -- the same sequence of calls gives the same bits on every run.
+ * ROUNDING.  With L = max |present loss|, u = 2^-53, and exp and log of the device within 4 ulp in double (HIP documents 1 ulp for both;
+ * OpenCL's bound is 3): a clip's xent is within u (1.4 M + 78 + 4 L) of exact arithmetic on the float32 losses -- the sum of at most M
+ * terms in (0, 1], the log of a number in [1, M], and two differences of numbers of size L -- and a margin within u |margin|.  Summed in
+ * double in any order:
+ *   |sum_xent   - exact| <= 2^-52 n_xent   (M + 40 + 2 L + sum of the exact xent)
+ *   |sum_margin - exact| <= 2^-52 n_margin (sum of the exact margins)
+ * Needs no cmps_set_params: it works on a fresh handle of any D and in legacy mode.  Asynchronous on `stream`; never synchronises, allocates
+ * nothing, reads loss_dev[m * ld + b] for m < M, b < B and label_dev[0 .. B) only, and writes only the record and best_dev[0 .. B).
+ * CMPS_ERR_BAD_ARG, each with a message, the first failing check speaking: a null handle; a null loss_dev; a null stats_dev or one that is
+ * not 8-byte aligned; M outside [1, 1024]; B < 1; ld < B; first_id < 0 or first_id + B > 2^63 - 1.
+ * With CMPS_OPT_KERNEL_EVENTS the launch is recorded as k_classify_stats.
+ */
+typedef struct cmps_bank_classify_head {
+    double sum_xent, sum_margin;
+    long long n_decided, n_undecided, n_unlabelled, n_correct, n_xent, n_margin, first_undecided;
+} cmps_bank_classify_head;
+size_t cmps_bank_classify_stats_bytes(int M);
+int cmps_bank_classify_stats(cmps_handle_t h, const float* loss_dev, int M, int B, long long ld,
+                             const int* label_dev, long long first_id, int reset,
+                             void* stats_dev, int* best_dev, void* stream);
 
 /*
  * The synthetic training batch, generated where it is used.  Replaces: the damped_sine branch of get_audio (data.py:8-22): a 261.6 Hz sine
