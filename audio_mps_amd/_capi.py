@@ -60,7 +60,7 @@ SYMBOLS = (
     "cmps_rho_workspace_bytes", "cmps_rho_set_state", "cmps_rho_loss_fwd", "cmps_rho_loss_bwd",
     "cmps_rho_update_ancilla", "cmps_rho_sample", "cmps_rho_sample_primed", "cmps_rho_stream_state_bytes", "cmps_rho_stream", "cmps_rho_stream_score", "cmps_rho_states",
     "cmps_rho_apply_step_scratch_bytes", "cmps_rho_apply_step", "cmps_noise_fill", "cmps_batch_gather", "cmps_batch_gather_i16", "cmps_loss_stats", "cmps_damped_sine_fill", "cmps_crc32c",
-    "cmps_bank_classify_stats_bytes", "cmps_bank_classify_stats",
+    "cmps_bank_classify_stats_bytes", "cmps_bank_classify_stats", "cmps_bank_classify_weights", "cmps_bank_loss_bwd_weighted",
     "cmps_bank_workspace_bytes", "cmps_bank_set_params_dev", "cmps_bank_loss_fwd", "cmps_bank_loss_bwd", "cmps_bank_apply_step_scratch_bytes",
     "cmps_bank_apply_step", "cmps_bank_grad_status", "cmps_bank_stream_state_bytes", "cmps_bank_stream", "cmps_bank_stream_score",
     "cmps_rho_bank_workspace_bytes", "cmps_rho_bank_set_state_dev", "cmps_rho_bank_loss_fwd", "cmps_rho_bank_loss_bwd",
@@ -80,6 +80,11 @@ CLASSIFY_HEAD = np.dtype([("sum_xent", "<f8"), ("sum_margin", "<f8"), ("n_decide
                           ("n_correct", "<i8"), ("n_xent", "<i8"), ("n_margin", "<i8"), ("first_undecided", "<i8")])
 assert CLASSIFY_HEAD.itemsize == 72
 CLASSIFY_MAX_M = 1024
+
+# the 40-byte record of cmps_bank_classify_weights (include/cmps.h: cmps_bank_classify_weights_rec), little-endian
+CLASSIFY_WEIGHTS_REC = np.dtype([("sum_xent", "<f8"), ("sum_own_loss", "<f8"), ("n_used", "<i8"), ("n_unlabelled", "<i8"),
+                                 ("n_own_absent", "<i8")])
+assert CLASSIFY_WEIGHTS_REC.itemsize == 40
 
 
 def classify_stats_dtype(M: int) -> np.dtype:
@@ -194,6 +199,11 @@ def _declare(lib):
     lib.cmps_bank_classify_stats_bytes.restype = c_size_t
     lib.cmps_bank_classify_stats.argtypes = [vp, vp, c_int, c_int, ctypes.c_longlong, vp, ctypes.c_longlong, c_int, vp, vp, vp]
     lib.cmps_bank_classify_stats.restype = c_int
+    lib.cmps_bank_classify_weights.argtypes = [vp, vp, c_int, c_int, ctypes.c_longlong, vp, c_double, c_double, c_double, c_int, vp,
+                                               ctypes.c_longlong, vp, vp]
+    lib.cmps_bank_classify_weights.restype = c_int
+    lib.cmps_bank_loss_bwd_weighted.argtypes = [vp, vp, c_int, c_int, c_int, vp, ctypes.c_longlong, vp, vp]
+    lib.cmps_bank_loss_bwd_weighted.restype = c_int
     lib.cmps_damped_sine_fill.argtypes = [vp, ctypes.c_ulonglong, ctypes.c_ulonglong, c_int, c_int, c_double, vp, vp]
     lib.cmps_damped_sine_fill.restype = c_int
     lib.cmps_crc32c.argtypes = [ctypes.c_char_p, c_size_t, ctypes.c_uint]

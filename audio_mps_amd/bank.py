@@ -12,6 +12,8 @@
   class bank         ``classes=[...]``: member m models the clips labelled classes[m] (a model per pitch).  It trains on
                      ResidentDataset.class_batches ([M, B, T], one batch per member) and is judged as a classifier by
                      ``BankTrainer.evaluate_classifier`` (cmps_bank_classify_stats: accuracy, cross-entropy, confusion matrix).
+                     ``BankTrainer.step_classifier`` trains its members against each other on ONE shared labelled batch
+                     (ResidentDataset.labelled_batches; cmps_bank_classify_weights, cmps_bank_loss_bwd_weighted; PsiCMPS members).
 
 Common to a bank: bond_dim, minibatch_size, sigma, delta_t, A, Adam's betas and epsilon.  Free per member: seed, learning_rate, h_reg, r_reg
 and the data.  Every member is sampled, followed and scored at once through ``open_stream`` (a BankStream: cmps_bank_stream*; a RhoBank:
@@ -185,7 +187,8 @@ class BankTrainer(ResidentState):
         self.trainers = [Trainer(model, hp, device_step=plain_device and not self.native)
                          for model, hp in zip(bank.models, bank.member_hparams)]
         self.global_step = 0
-        self.last = None              # the last synchronised step's per-member losses: {"model_loss": [M], "total_loss": [M]}
+        self.objective = None         # a dict the caller sets for a run that is not generative (train --bank_objective): kept in bank.json
+        self.last = None            # the last synchronised step's per-member losses: {"model_loss": [M], "total_loss": [M]}
         self._resident([(tr.model, tr.opt) for tr in self.trainers], bank.bond_d, self.rank)
 
     def __len__(self) -> int:
@@ -242,6 +245,58 @@ class BankTrainer(ResidentState):
         self._apply(flat, int(B))
         self._mark_dirty()
         return {"losses_dev": st["losses"]}
+
+    def step_classifier(self, data, labels, gen_weight: float = 0.0, disc_weight: float = 1.0, temperature: float = 1.0,
+                        sync: bool = True) -> dict:
+        """One step of a class bank trained as a classifier: ``data`` [B, T], ONE batch shared by every member, and ``labels`` [B], the
+        member each clip belongs to (``dataset.class_index(bank.classes)``; outside [0, M): the clip is skipped).  Every member descends
+        sum_b (gen_weight * loss[label_b, b] + disc_weight * xent_b) / B with p(m | clip) = softmax(-loss / temperature), the objective
+        of cmps_bank_classify_weights: a shared-batch forward, the weights, cmps_bank_loss_bwd_weighted and the optimiser step of
+        ``step``.  Returns what ``step`` returns -- ``model_loss`` [M] is each member's weighted loss sum / B -- and ``xent`` (the mean over
+        the used clips), ``used``, ``unlabelled`` and ``own_absent``; with ``sync=False`` ``losses_dev`` and ``record_dev`` instead."""
+        import torch
+        be = self.bank.backend
+        if self.bank.classes is None:
+            raise ValueError("step_classifier needs a class bank (PsiBank(..., classes=))")
+        if self.rank:
+            raise ValueError("step_classifier: a RhoBank has no weighted reverse pass (cmps_bank_loss_bwd_weighted is for PsiCMPS members)")
+        if not (self.native and hasattr(be, "classify_weights")):
+            raise ValueError("step_classifier needs the backend's bank entries and classify_weights (the native path): "
+                             f"{type(be).__name__} has none")
+        if not (temperature > 0.0 and math.isfinite(temperature)):
+            raise ValueError("step_classifier: temperature must be finite and positive")
+        nd = data.dim() if hasattr(data, "dim") else np.ndim(data)
+        if nd != 2:
+            raise ValueError("step_classifier: data must be [B, T], one batch shared by every member")
+        st = self._device_state()
+        audio = self.bank.models[0]._to_device(data)
+        B, T = audio.shape[-2:]
+        if not isinstance(labels, torch.Tensor):
+            labels = torch.from_numpy(np.ascontiguousarray(labels, dtype=np.int32))
+        labels = labels.to(device=audio.device, dtype=torch.int32).contiguous()
+        if labels.dim() != 1 or int(labels.numel()) != int(B):
+            raise ValueError(f"step_classifier: labels must be [B] with B = {int(B)}")
+        self._configure(st, int(B), int(T), True)
+        loss = self._forward(audio, save_for_bwd=True)
+        weights, record = be.classify_weights(loss, labels, 1.0 / float(temperature), float(gen_weight), float(disc_weight))
+        flat = self._backward(weights=weights)
+        for tr in self.trainers:
+            tr.opt.t += 1
+            tr.global_step += 1
+        self._apply(flat, int(B))
+        self._mark_dirty()
+        self.global_step += 1
+        out = {"global_step": self.global_step}
+        if not sync:
+            out.update(losses_dev=st["losses"], record_dev=record)
+            return out
+        lo = st["losses"].cpu().numpy()
+        rec = be.read_classify_weights_record(record)
+        out.update(model_loss=lo[:, 0].copy(), total_loss=lo[:, 1].copy(),
+                   xent=rec["sum_xent"] / rec["n_used"] if rec["n_used"] else float("nan"),
+                   used=rec["n_used"], unlabelled=rec["n_unlabelled"], own_absent=rec["n_own_absent"])
+        self.last = out
+        return out
 
     def best(self) -> int:
         """The member with the lowest last ``model_loss`` among the finite ones."""
@@ -338,6 +393,8 @@ class BankTrainer(ResidentState):
             meta["model"] = self.bank.MODEL_NAME
         if self.bank.classes is not None:     # (and so does the file of a bank without classes)
             meta["label_key"], meta["classes"] = self.bank.label_key, self.bank.classes
+        if self.objective is not None:        # (and of a generatively trained one)
+            meta["objective"] = self.objective
         tmp = os.path.join(directory, "bank.json.tmp")
         with open(tmp, "w") as f:
             json.dump(meta, f)

@@ -205,7 +205,11 @@ __global__ __launch_bounds__(NT) void k_bwd_block(Dev Pk, const float* __restric
 // two passes, fixed summation order (deterministic): RPART row-groups of clips, then the groups
 constexpr int RPART = 32;
 // (a bank: member = blockIdx.z here, blockIdx.y in the two kernels behind it; `part` and `sums` lie in the member's workspace)
-__global__ void k_reduce_slabs(Dev Pk, float* __restrict__ part) {
+// WEIGHTED (cmps_bank_loss_bwd_weighted): clip b of member z enters with the cotangent weight[z * ldw + b], the product of two float32
+// values exact in double; a clip whose weight is exactly 0 is not read at all (the branch is uniform: b and z are), so that a diverged
+// clip's or an absent member's NaN slab cannot reach the sum.  Same groups, same order.
+template <bool WEIGHTED>
+__device__ __forceinline__ void reduce_slabs_body(const Dev& Pk, float* __restrict__ part, const float* __restrict__ weight, long long ldw) {
     const Dev P = bank_view(Pk, blockIdx.z);
     part = bank_shift(part, blockIdx.z * P.bank_stride);
     const size_t col = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -215,8 +219,20 @@ __global__ void k_reduce_slabs(Dev Pk, float* __restrict__ part) {
     const int per = (P.B + RPART - 1) / RPART;
     const int b0 = g * per, b1 = (b0 + per < P.B) ? b0 + per : P.B;
     double acc = 0.0;
-    for (int b = b0; b < b1; ++b) acc += (double)P.slabs[(size_t)b * P.slab_floats + col];
+    if constexpr (WEIGHTED) {
+        const float* wrow = weight + (long long)blockIdx.z * ldw;
+        for (int b = b0; b < b1; ++b) {
+            const float w = wrow[b];
+            if (w != 0.f) acc += (double)w * (double)P.slabs[(size_t)b * P.slab_floats + col];
+        }
+    } else {
+        for (int b = b0; b < b1; ++b) acc += (double)P.slabs[(size_t)b * P.slab_floats + col];
+    }
     reinterpret_cast<double*>(part)[(size_t)g * P.slab_floats + col] = acc;
+}
+__global__ void k_reduce_slabs(Dev Pk, float* __restrict__ part) { reduce_slabs_body<false>(Pk, part, nullptr, 0); }
+__global__ void k_reduce_slabs_weighted(Dev Pk, float* __restrict__ part, const float* __restrict__ weight, long long ldw) {
+    reduce_slabs_body<true>(Pk, part, weight, ldw);
 }
 __global__ void k_reduce_parts(Dev Pk, const float* __restrict__ part, float* __restrict__ sums) {
     const Dev& P = Pk;
@@ -229,8 +245,12 @@ __global__ void k_reduce_parts(Dev Pk, const float* __restrict__ part, float* __
     sums[col] = (float)acc;
 }
 
+// WEIGHTED: the closing terms are linear in the reduced sums, so only the last element differs -- sum_b weight[y * ldw + b] loss_b over the
+// clips with a weight other than 0, in loss_sum_wave's order.  (A template instance, not a shared body behind two kernels: inlined into
+// a wrapper the plain kernel compiled to other instructions; <false> keeps the parent's, scripts/isa_identity.py --kernels.)
+template <bool WEIGHTED>
 __global__ void k_finalize(Dev Pk, const float* __restrict__ sums, const float* __restrict__ loss,
-                           float* __restrict__ grad_out) {
+                           float* __restrict__ grad_out, const float* __restrict__ weight, long long ldw) {
     const Dev P = bank_view(Pk, blockIdx.y);
     sums = bank_shift(sums, blockIdx.y * P.bank_stride);
     loss += blockIdx.y * P.bank_loss;
@@ -291,7 +311,19 @@ __global__ void k_finalize(Dev Pk, const float* __restrict__ sums, const float* 
         }
     }
     if (blockIdx.x == 0 && threadIdx.x < 64) {      // sum_b loss_b: one wave, strided partials then a fixed-order tree
-        const double ls = loss_sum_wave(loss, P.B);
+        double ls;
+        if constexpr (WEIGHTED) {
+            const float* wrow = weight + (long long)blockIdx.y * ldw;
+            ls = 0.0;
+            for (int b = threadIdx.x; b < P.B; b += 64) {
+                const float w = wrow[b];
+                if (w != 0.f) ls += (double)w * (double)loss[b];
+            }
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) ls += __shfl_xor(ls, off, 64);
+        } else {
+            ls = loss_sum_wave(loss, P.B);
+        }
         if (threadIdx.x == 0) {
             grad_out[2 * D * D + 3 * D + 1] = (float)ls;
             if (!isfinite((float)ls)) flag(2u);
@@ -543,12 +575,27 @@ static unsigned finalize_blocks(const Dev& P) {
 hipError_t launch_reduce_finalize(const Dev& P, const float* loss, float* grad_out, hipStream_t s, int M) {
     const hipError_t e = launch_reduce_only(P, s, M);     // its hipGetLastError() has consumed the launch status
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_finalize, dim3(finalize_blocks(P), M), dim3(256), 0, s, P, (const float*)P.sums, loss, grad_out);
+    hipLaunchKernelGGL(k_finalize<false>, dim3(finalize_blocks(P), M), dim3(256), 0, s, P, (const float*)P.sums, loss, grad_out,
+                       (const float*)nullptr, 0ll);
+    return hipGetLastError();
+}
+
+// cmps_bank_loss_bwd_weighted: launch_reduce_finalize with the [M][B] cotangents `weight` (rows ldw floats apart)
+hipError_t launch_reduce_finalize_weighted(const Dev& P, const float* loss, float* grad_out, const float* weight, long long ldw,
+                                           hipStream_t s, int M) {
+    const unsigned nb = (unsigned)((P.slab_floats + 255) / 256);
+    float* part = P.sums + ((P.slab_floats + 63) / 64) * 64;          // RPART x slab doubles behind the sums
+    hipLaunchKernelGGL(k_reduce_slabs_weighted, dim3(nb, RPART, M), dim3(256), 0, s, P, part, weight, ldw);
+    hipLaunchKernelGGL(k_reduce_parts, dim3(nb, M), dim3(256), 0, s, P, (const float*)part, P.sums);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_finalize<true>, dim3(finalize_blocks(P), M), dim3(256), 0, s, P, (const float*)P.sums, loss, grad_out, weight, ldw);
     return hipGetLastError();
 }
 
 hipError_t launch_finalize_only(const Dev& P, const float* loss, float* grad_out, hipStream_t s, int M) {
-    hipLaunchKernelGGL(k_finalize, dim3(finalize_blocks(P), M), dim3(256), 0, s, P, (const float*)P.sums, loss, grad_out);
+    hipLaunchKernelGGL(k_finalize<false>, dim3(finalize_blocks(P), M), dim3(256), 0, s, P, (const float*)P.sums, loss, grad_out,
+                       (const float*)nullptr, 0ll);
     return hipGetLastError();
 }
 

@@ -526,7 +526,9 @@ int cmps_psi_loss_fwd(cmps_handle_t h, const float* audio_dev, int B, int T, flo
 }
 
 // cmps_psi_loss_bwd (M = 0) and cmps_bank_loss_bwd behind their argument checks
-static int psi_bwd_run(cmps_handle_t h, const char* who, int M, int n_audio, const float* audio_dev, int B, int T, float* grad_dev, void* stream) {
+// (weight non-null, cmps_bank_loss_bwd_weighted: the same reverse scan, the cross-clip reduction weighted by weight[m * ldw + b])
+static int psi_bwd_run(cmps_handle_t h, const char* who, int M, int n_audio, const float* audio_dev, int B, int T, float* grad_dev, void* stream,
+                       const float* weight = nullptr, long long ldw = 0) {
     const auto failed = [&](hipError_t e, const char* stage) { return fail_hip(h, e, (std::string(who) + stage).c_str()); };
     Dev P = main_dev(h, B);
     const int Mk = M > 0 ? M : 1;
@@ -575,8 +577,8 @@ static int psi_bwd_run(cmps_handle_t h, const char* who, int M, int n_audio, con
     }
     if (e != hipSuccess) return failed(e, " (scan)");
     P.abar_fix = wave ? 1 : 0;
-    KScope ks("reduce + finalize", s);
-    e = launch_reduce_finalize(P, loss, grad_dev, s, Mk);
+    KScope ks(weight ? "reduce + finalize (weighted)" : "reduce + finalize", s);
+    e = weight ? launch_reduce_finalize_weighted(P, loss, grad_dev, weight, ldw, s, Mk) : launch_reduce_finalize(P, loss, grad_dev, s, Mk);
     if (e != hipSuccess) return failed(e, " (reduce)");
     return CMPS_OK;
 }
@@ -672,6 +674,23 @@ int cmps_bank_loss_bwd(cmps_handle_t h, const float* audio_dev, int n_audio, int
     if (const int rc = check_bwd(h, who, ready, "cmps_bank_loss_fwd", h->main, audio_dev, grad_dev, B, T)) return rc;
     if (n_audio != h->main.n_audio) return fail(h, CMPS_ERR_STATE, std::string(who) + ": n_audio differs from the forward call");
     return psi_bwd_run(h, who, h->bank_M, n_audio, audio_dev, B, T, grad_dev, stream);
+}
+
+// cmps_bank_loss_bwd with a cotangent per clip and member.  Its own two checks come first, so that they answer on any handle; then
+// cmps_bank_loss_bwd's.  PsiCMPS banks only: a RhoCMPS bank's reverse pass runs `rank` virtual clips per clip and closes with kernels of its own.
+int cmps_bank_loss_bwd_weighted(cmps_handle_t h, const float* audio_dev, int n_audio, int B, int T, const float* weight_dev, long long ldw,
+                                float* grad_dev, void* stream) {
+    const char* who = "cmps_bank_loss_bwd_weighted";
+    if (!h) return CMPS_ERR_BAD_ARG;
+    if (!weight_dev) return fail(h, CMPS_ERR_BAD_ARG, std::string(who) + ": weight_dev is a null pointer");
+    if (ldw < (long long)B) return fail(h, CMPS_ERR_BAD_ARG, std::string(who) + ": ldw must be at least B");
+    if (const int rc = bank_check_mode(h, who, true)) return rc;
+    if (h->bank_M > 0 && h->bank_rho)
+        return fail(h, CMPS_ERR_STATE, std::string(who) + ": the handle holds a RhoCMPS bank; the weighted reverse pass is for PsiCMPS banks (cmps_bank_set_params_dev)");
+    const bool ready = h->params_set && !h->legacy && h->bank_M > 0 && h->main.M == h->bank_M;
+    if (const int rc = check_bwd(h, who, ready, "cmps_bank_loss_fwd", h->main, audio_dev, grad_dev, B, T)) return rc;
+    if (n_audio != h->main.n_audio) return fail(h, CMPS_ERR_STATE, std::string(who) + ": n_audio differs from the forward call");
+    return psi_bwd_run(h, who, h->bank_M, n_audio, audio_dev, B, T, grad_dev, stream, weight_dev, ldw);
 }
 
 size_t cmps_bank_apply_step_scratch_bytes(int D, int M) {
@@ -1048,6 +1067,33 @@ int cmps_bank_classify_stats(cmps_handle_t h, const float* loss_dev, int M, int 
     KScope ks("k_classify_stats", s);
     const hipError_t e = launch_classify_stats(loss_dev, M, B, ld, label_dev, first_id, reset, stats_dev, best_dev, s);
     if (e != hipSuccess) return fail_hip(h, e, "cmps_bank_classify_stats");
+    return CMPS_OK;
+}
+
+// ... and turned into the cotangents of a cross-entropy step: needs nothing of the handle either
+int cmps_bank_classify_weights(cmps_handle_t h, const float* loss_dev, int M, int B, long long ld, const int* label_dev, double inv_temp,
+                               double gen_weight, double disc_weight, int reset, float* weight_dev, long long ldw, void* record_dev,
+                               void* stream) {
+    const std::string w("cmps_bank_classify_weights");
+    if (!h) return CMPS_ERR_BAD_ARG;
+    if (!loss_dev) return fail(h, CMPS_ERR_BAD_ARG, w + ": loss_dev is a null pointer");
+    if (!label_dev) return fail(h, CMPS_ERR_BAD_ARG, w + ": label_dev is a null pointer");
+    if (!weight_dev) return fail(h, CMPS_ERR_BAD_ARG, w + ": weight_dev is a null pointer");
+    if (!record_dev) return fail(h, CMPS_ERR_BAD_ARG, w + ": record_dev is a null pointer");
+    if (((uintptr_t)record_dev & 7) != 0) return fail(h, CMPS_ERR_BAD_ARG, w + ": record_dev must be 8-byte aligned");
+    if (M < 1 || M > CLASSIFY_MAX_M) return fail(h, CMPS_ERR_BAD_ARG, w + ": need 1 <= M <= 1024");
+    if (B < 1) return fail(h, CMPS_ERR_BAD_ARG, w + ": need B >= 1");
+    if (ld < (long long)B) return fail(h, CMPS_ERR_BAD_ARG, w + ": ld must be at least B");
+    if (ldw < (long long)B) return fail(h, CMPS_ERR_BAD_ARG, w + ": ldw must be at least B");
+    if (!std::isfinite(inv_temp) || !(inv_temp > 0.0)) return fail(h, CMPS_ERR_BAD_ARG, w + ": inv_temp must be finite and positive");
+    if (!std::isfinite(gen_weight) || gen_weight < 0.0) return fail(h, CMPS_ERR_BAD_ARG, w + ": gen_weight must be finite and not negative");
+    if (!std::isfinite(disc_weight) || disc_weight < 0.0) return fail(h, CMPS_ERR_BAD_ARG, w + ": disc_weight must be finite and not negative");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    KBind kb(h);
+    KScope ks("k_classify_weights", s);
+    const hipError_t e = launch_classify_weights(loss_dev, M, B, ld, label_dev, inv_temp, gen_weight, disc_weight, reset, weight_dev, ldw,
+                                                 record_dev, s);
+    if (e != hipSuccess) return fail_hip(h, e, "cmps_bank_classify_weights");
     return CMPS_OK;
 }
 

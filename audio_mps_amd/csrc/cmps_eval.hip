@@ -11,6 +11,7 @@
 // ordered by the stream, so the same sequence of calls gives the same bits on every run.  A batch is a few thousand floats: one workgroup
 // reads it in a few microseconds, and more of them would need the second pass or the atomics this kernel does without.
 // k_classify_stats (cmps_bank_classify_stats), further down: the [M][B] losses of a bank of one model per class judged as a classifier.
+// k_classify_weights (cmps_bank_classify_weights), last: the same losses turned into the per-clip, per-member cotangents of a cross-entropy step.
 #include "cmps_internal.h"
 
 namespace cmps {
@@ -191,6 +192,94 @@ __global__ __launch_bounds__(STATS_NT) void k_classify_stats(const float* __rest
     }
 }
 
+// k_classify_weights (cmps_bank_classify_weights): the same [M][B] losses and the labels turned into the [M][B] cotangents of the
+// cross-entropy objective of include/cmps.h (tests/_disc_ref.py restates it), w[m][b] = d J_b / d loss[m][b] with
+// J_b = alpha loss[y][b] + beta xent_b, and into a 40-byte record.  ONE workgroup of STATS_NT threads, as k_classify_stats: thread t takes
+// clips t, t + STATS_NT, ... in that order and walks the M losses of each three times (smallest present loss; S; the weights), every
+// pass's loads and the stores coalesced over neighbouring clips.  Every weight[m * ldw + b], m < M, b < B, is written exactly once, a
+// skipped clip's and an absent member's with +0.  The record's two double sums and three counts go through the binary tree in LDS.
+struct alignas(8) ClassifyWeightsRec {   // the record of include/cmps.h (cmps_bank_classify_weights), field for field
+    double sum_xent, sum_own_loss;
+    long long n_used, n_unlabelled, n_own_absent;
+};
+static_assert(sizeof(ClassifyWeightsRec) == 40, "the record of cmps_bank_classify_weights is 40 bytes");
+
+__device__ __forceinline__ void weights_merge(ClassifyWeightsRec& a, const ClassifyWeightsRec& b) {
+    a.sum_xent += b.sum_xent;
+    a.sum_own_loss += b.sum_own_loss;
+    a.n_used += b.n_used;
+    a.n_unlabelled += b.n_unlabelled;
+    a.n_own_absent += b.n_own_absent;
+}
+
+// grid 1
+__global__ __launch_bounds__(STATS_NT) void k_classify_weights(const float* __restrict__ loss, int M, int B, long long ld,
+                                                               const int* __restrict__ label, double kappa, double alpha, double beta,
+                                                               int reset, float* __restrict__ weight, long long ldw,
+                                                               ClassifyWeightsRec* __restrict__ rec) {
+    __shared__ ClassifyWeightsRec part[STATS_NT];
+    const int tid = threadIdx.x;
+    const double bk = beta * kappa;
+    ClassifyWeightsRec r{0.0, 0.0, 0ll, 0ll, 0ll};
+    for (int b = tid; b < B; b += STATS_NT) {
+        const float* col = loss + b;
+        float* wcol = weight + b;
+        const int y = label[b];
+        const bool labelled = y >= 0 && y < M;
+        const float xl = labelled ? col[(long long)y * ld] : 0.f;
+        if (!labelled || !is_finite_f32(xl)) {                                                // skipped: every weight of the clip is +0
+            if (!labelled) r.n_unlabelled += 1; else r.n_own_absent += 1;
+            for (int m = 0; m < M; ++m) wcol[(long long)m * ldw] = 0.f;
+            continue;
+        }
+        float l1 = xl;                                                                        // smallest present loss (the own one is present)
+#pragma unroll 8
+        for (int m = 0; m < M; ++m) {
+            const float x = col[(long long)m * ld];
+            if (is_finite_f32(x) && x < l1) l1 = x;
+        }
+        double S = 0.0;                                                                       // in member order: 1 <= S <= M
+#pragma unroll 4
+        for (int m = 0; m < M; ++m) {
+            const float x = col[(long long)m * ld];
+            if (is_finite_f32(x)) S += exp(-(kappa * ((double)x - (double)l1)));
+        }
+#pragma unroll 4
+        for (int m = 0; m < M; ++m) {
+            const float x = col[(long long)m * ld];
+            float w = 0.f;
+            if (is_finite_f32(x)) {
+                const double d = m == y ? 1.0 : 0.0;
+                const double p = exp(-(kappa * ((double)x - (double)l1))) / S;
+                w = (float)(alpha * d + bk * (d - p));
+            }
+            wcol[(long long)m * ldw] = w;
+        }
+        r.sum_xent += kappa * ((double)xl - (double)l1) + log(S);
+        r.sum_own_loss += (double)xl;
+        r.n_used += 1;
+    }
+    part[tid] = r;
+    __syncthreads();
+    for (int w = STATS_NT / 2; w >= 1; w >>= 1) {
+        if (tid < w) {
+            ClassifyWeightsRec a = part[tid];
+            weights_merge(a, part[tid + w]);
+            part[tid] = a;
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        ClassifyWeightsRec total = part[0];
+        if (!reset) {
+            ClassifyWeightsRec before = *rec;
+            weights_merge(before, total);
+            total = before;
+        }
+        *rec = total;
+    }
+}
+
 }  // namespace
 
 // The caller (cmps_loss_stats) has checked: B >= 1, first_id >= 0, first_id + B representable, stats 8-byte aligned
@@ -205,6 +294,15 @@ hipError_t launch_classify_stats(const float* loss, int M, int B, long long ld, 
                                  int* best, hipStream_t s) {
     hipLaunchKernelGGL(k_classify_stats, dim3(1), dim3(STATS_NT), 0, s, loss, M, B, ld, label, first_id, reset,
                        static_cast<ClassifyHead*>(stats), best);
+    return hipGetLastError();
+}
+
+// The caller (cmps_bank_classify_weights) has checked: 1 <= M <= 1024, B >= 1, ld >= B, ldw >= B, inv_temp finite and > 0, the two weights
+// finite and >= 0, record 8-byte aligned and of 40 bytes; no pointer is null
+hipError_t launch_classify_weights(const float* loss, int M, int B, long long ld, const int* label, double inv_temp, double gen_weight,
+                                   double disc_weight, int reset, float* weight, long long ldw, void* record, hipStream_t s) {
+    hipLaunchKernelGGL(k_classify_weights, dim3(1), dim3(STATS_NT), 0, s, loss, M, B, ld, label, inv_temp, gen_weight, disc_weight, reset,
+                       weight, ldw, static_cast<ClassifyWeightsRec*>(record));
     return hipGetLastError();
 }
 

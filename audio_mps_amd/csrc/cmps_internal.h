@@ -484,6 +484,8 @@ hipError_t launch_bwd_wide(const Dev& P, const float* audio, hipStream_t s);
 hipError_t launch_grad_wide(const Dev& P, const float* audio, int pieces, hipStream_t s);
 hipError_t launch_finalize_only(const Dev& P, const float* loss, float* grad_out, hipStream_t s, int M = 1);
 hipError_t launch_reduce_finalize(const Dev& P, const float* loss, float* grad_out, hipStream_t s, int M = 1);
+hipError_t launch_reduce_finalize_weighted(const Dev& P, const float* loss, float* grad_out, const float* weight, long long ldw,
+                                           hipStream_t s, int M);
 hipError_t launch_update_ancilla(const Dev& P, const float* psi_in, const float* signal, float t,
                                  int B, float* psi_out, hipStream_t s);
 hipError_t launch_states(const Dev& P, int B, float* psi_out, hipStream_t s);
@@ -514,6 +516,9 @@ constexpr int CLASSIFY_MAX_M = 1024;
 constexpr size_t CLASSIFY_HEAD_BYTES = 72;
 hipError_t launch_classify_stats(const float* loss, int M, int B, long long ld, const int* label, long long first_id, int reset, void* stats,
                                  int* best, hipStream_t s);
+// ... and turned into weight[m * ldw + b], the cotangents of the cross-entropy objective of cmps_bank_classify_weights, and its 40-byte record
+hipError_t launch_classify_weights(const float* loss, int M, int B, long long ld, const int* label, double inv_temp, double gen_weight,
+                                   double disc_weight, int reset, float* weight, long long ldw, void* record, hipStream_t s);
 // floats of one path's stream record (StreamDev::rec), a multiple of 4: wave u, |y|^2 partial per lane, running sum | wide ut [2 DP], |y|^2
 // partial per wave [DP / 16], running sum | block u [2 D], running sum
 constexpr int STREAM_REC_WAVE = 132;

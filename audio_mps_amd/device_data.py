@@ -9,6 +9,8 @@
                      same bits.  A plan is uploaded an epoch at a time as one int32 tensor and sliced per step.
   ClassBatches       a labelled ResidentDataset (labels=, from_tfrecord(label_key=)) read as one stream per class, the reference's
                      per-pitch input (reader.py:22-40), for a bank of one model per class: [M, B, T] per step from ONE gather of M B rows.
+  LabelledBatches    the batches of a plain BatchStream over a labelled ResidentDataset together with the labels of exactly their rows
+                     (BatchStream.last_index): the ONE shared batch of a class bank trained as a classifier.
   DampedSineSource   the reference's synthetic batch (data.py:8-22) generated where it is used (HipScan.damped_sine,
                      cmps_damped_sine_fill): clip c of the run is a pure function of (seed, c, T, delta_t).
 
@@ -205,6 +207,13 @@ class ResidentDataset:
         (``crop_seed``), so the order is the one without crops.  The reference has no crops."""
         return BatchStream(self, minibatch_size, seed, order, shuffle_buffer, crop, crop_seed)
 
+    def labelled_batches(self, classes, minibatch_size: int, seed: int = 0, order: str = "data", shuffle_buffer: int = 24,
+                         crop: Optional[int] = None, crop_seed: int = 0) -> "LabelledBatches":
+        """A callable returning the next (batch [B, T], labels [B] int32 on the device), forever: the batches of ``batches(...)`` with the
+        same arguments, bit for bit, and of exactly those rows ``class_index(classes)`` -- the shared batch of a class bank trained as a
+        classifier (BankTrainer.step_classifier)."""
+        return LabelledBatches(self, classes, self.batches(minibatch_size, seed, order, shuffle_buffer, crop, crop_seed))
+
 
 class BatchStream:
     """``stream()`` -> the next batch [B, T] on the device; ``stream(shard=(start, count))`` -> rows start .. start + count - 1 of that
@@ -230,6 +239,7 @@ class BatchStream:
         self._plan = None              # int32 device tensor [2 if crops else 1, n]: the indices (and offsets) of the clips still to come
         self._pos = 0                  # clips of _plan already handed out
         self._sizes = []               # order="data": sizes of the planned batches still to come
+        self.last_index = None         # int32 device tensor: the dataset rows of the batch (or shard) the last call returned
 
     # -- planning (host; one upload per epoch) ----------------------------------------------------
     def _plan_epoch(self, N: int) -> np.ndarray:
@@ -276,11 +286,30 @@ class BatchStream:
         lo, hi = (0, n) if shard is None else (min(max(int(shard[0]), 0), n), min(max(int(shard[0]), 0) + max(int(shard[1]), 0), n))
         at = self._pos
         self._pos += n
+        self.last_index = self._plan[0, at + lo:at + hi]       # (a view of the plan: nothing is drawn or copied for it)
         if hi <= lo:
             return torch.empty((0, self.T), dtype=torch.float32, device=self.ds.clips.device)
-        index = self._plan[0, at + lo:at + hi]
+        index = self.last_index
         offset = self._plan[1, at + lo:at + hi] if self._crop else None
         return self.ds.gather(index, offset, self.T)
+
+
+class LabelledBatches:
+    """``stream()`` -> (the next batch of ``stream``, a BatchStream, and its rows' positions in ``classes``: int32 [B] on the device, -1
+    for a label that is not among them).  The labels are uploaded once; a step is the stream's gather and one index_select."""
+
+    def __init__(self, dataset: ResidentDataset, classes, stream: BatchStream):
+        self.ds, self.classes, self.stream = dataset, list(classes), stream
+        self.labels = dataset.class_index(self.classes)
+        self.T = stream.T
+
+    @property
+    def next_size(self) -> int:
+        return self.stream.next_size
+
+    def __call__(self):
+        batch = self.stream()
+        return batch, self.labels.index_select(0, self.stream.last_index.to(torch.int64))
 
 
 class _ClassPlanner(BatchStream):

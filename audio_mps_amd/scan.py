@@ -146,7 +146,7 @@ class HipScan:
         return mode if mode in (_capi.CMPS_RANK1_EXACT_F32, _capi.CMPS_RANK1_BF16X2, _capi.CMPS_RANK1_F16X2) else _capi.CMPS_RANK1_BF16X3
 
     def kernel_events(self, on: bool):
-        """cmps_set_option(CMPS_OPT_KERNEL_EVENTS): bracket every kernel of forward() / backward() and of sample() / sample_primed() / stream() / stream_score() / rho_sample_primed() / rho_stream() / rho_stream_score() / draw_noise() / gather_batch() / loss_stats() / classify_stats() / damped_sine() with HIP
+        """cmps_set_option(CMPS_OPT_KERNEL_EVENTS): bracket every kernel of forward() / backward() and of sample() / sample_primed() / stream() / stream_score() / rho_sample_primed() / rho_stream() / rho_stream_score() / draw_noise() / gather_batch() / loss_stats() / classify_stats() / classify_weights() / damped_sine() with HIP
         events (a measurement aid, used by bench.py outside its timed region)."""
         _capi.check(self._h, self._lib.cmps_set_option(self._h, _capi.CMPS_OPT_KERNEL_EVENTS, 1 if on else 0))
 
@@ -357,9 +357,25 @@ class HipScan:
         """cmps_bank_loss_fwd: per-clip losses [M, B] for ``audio`` [B, T] (one batch shared by every member) or [M, B, T]."""
         return self._bank_forward("bank", self._lib.cmps_bank_loss_fwd, audio, save_for_bwd)
 
-    def bank_backward(self) -> torch.Tensor:
-        """cmps_bank_loss_bwd after bank_forward(save_for_bwd=True): gradient sums [M, 2 D^2 + 3 D + 2]."""
-        return self._bank_backward("bank", self._lib.cmps_bank_loss_bwd)
+    def bank_backward(self, weights: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """cmps_bank_loss_bwd after bank_forward(save_for_bwd=True): gradient sums [M, 2 D^2 + 3 D + 2].  With ``weights`` (float32
+        [M, B] on this device, rows contiguous; classify_weights' output) cmps_bank_loss_bwd_weighted: member m's row is the gradient of
+        sum_b weights[m, b] * loss[m, b], its last element that sum."""
+        if weights is None:
+            return self._bank_backward("bank", self._lib.cmps_bank_loss_bwd)
+        saved = self._bank.saved if self._bank.kind == "bank" else None
+        M, B = (self._bank.M, int(saved[0].shape[-2])) if saved is not None else (-1, -1)
+        if not (isinstance(weights, torch.Tensor) and weights.device == self.device and weights.dtype == torch.float32 and weights.dim() == 2
+                and weights.stride(1) == 1 and (weights.shape[0] == 1 or weights.stride(0) >= weights.shape[1])):
+            raise ValueError("bank_backward: weights must be a float32 tensor [M, B] with contiguous rows on the backend's device")
+        if saved is not None and tuple(weights.shape) != (M, B):
+            raise ValueError(f"bank_backward: weights of shape {tuple(weights.shape)} do not fit the forward's losses [{M}, {B}]")
+        ldw = int(weights.stride(0)) if weights.shape[0] > 1 else int(weights.shape[1])
+        w_ptr = weights.data_ptr()
+
+        def weighted(h, audio, n_audio, B_, T_, grad, stream):
+            return self._lib.cmps_bank_loss_bwd_weighted(h, audio, n_audio, B_, T_, w_ptr, ldw, grad, stream)
+        return self._bank_backward("bank", weighted)
 
     def bank_apply_step(self, vars_: torch.Tensor, m: torch.Tensor, v: torch.Tensor, grad_sums: Optional[torch.Tensor], global_batch: int,
                         bias_num: float, bias_den: float, beta1: float, beta2: float, eps: float, hyper: torch.Tensor, with_reg: bool,
@@ -633,6 +649,47 @@ class HipScan:
         out = {k: (float(rec["head"][k]) if head[k].kind == "f" else int(rec["head"][k])) for k in head.names}
         out["confusion"], out["unlabelled_best"] = rec["confusion"].copy(), rec["unlabelled_best"].copy()
         return out
+
+    def classify_weights(self, loss: torch.Tensor, labels: torch.Tensor, inv_temp: float, gen_weight: float, disc_weight: float,
+                         weights: Optional[torch.Tensor] = None, record: Optional[torch.Tensor] = None, reset: bool = True):
+        """cmps_bank_classify_weights: turn the losses ``loss`` [M, B] of a bank forward over one shared batch and the ``labels`` (int32
+        [B] on this device) into the cotangents of the cross-entropy objective of include/cmps.h, ``weights`` [M, B] (float32, rows
+        contiguous; allocated when None), and fold the batch into the 40-byte ``record`` (uint8 on this device; allocated -- and reset --
+        when None).  Returns (weights, record).  No host copy, no synchronisation: read_classify_weights_record is the download."""
+        def on_dev(t, dtype, dim):
+            return isinstance(t, torch.Tensor) and t.device == self.device and t.dtype == dtype and t.dim() == dim
+
+        def rows(t):
+            return on_dev(t, torch.float32, 2) and t.shape[0] >= 1 and t.shape[1] >= 1 and t.stride(1) == 1 and (
+                t.shape[0] == 1 or t.stride(0) >= t.shape[1])
+        if not rows(loss):
+            raise ValueError("classify_weights: loss must be a float32 tensor [M, B] with contiguous rows, M >= 1 and B >= 1, on the "
+                             "backend's device")
+        M, B = int(loss.shape[0]), int(loss.shape[1])
+        if not 1 <= M <= _capi.CLASSIFY_MAX_M:
+            raise ValueError(f"classify_weights: a bank holds 1 .. {_capi.CLASSIFY_MAX_M} members, not {M}")
+        if not (on_dev(labels, torch.int32, 1) and labels.is_contiguous() and int(labels.numel()) == B):
+            raise ValueError("classify_weights: labels must be a contiguous int32 tensor [B] on the backend's device")
+        if weights is None:
+            weights = torch.empty((M, B), dtype=torch.float32, device=self.device)
+        elif not (rows(weights) and tuple(weights.shape) == (M, B)):
+            raise ValueError("classify_weights: weights must be a float32 tensor [M, B] with contiguous rows on the backend's device")
+        if record is None:
+            record, reset = torch.empty(_capi.CLASSIFY_WEIGHTS_REC.itemsize, dtype=torch.uint8, device=self.device), True
+        elif not (on_dev(record, torch.uint8, 1) and record.numel() == _capi.CLASSIFY_WEIGHTS_REC.itemsize and record.is_contiguous()):
+            raise ValueError("classify_weights: record must be a contiguous uint8 tensor of 40 bytes on the backend's device")
+        _capi.check(self._h, self._lib.cmps_bank_classify_weights(
+            self._h, loss.data_ptr(), M, B, int(loss.stride(0)) if M > 1 else B, labels.data_ptr(), float(inv_temp), float(gen_weight),
+            float(disc_weight), 1 if reset else 0, weights.data_ptr(), int(weights.stride(0)) if M > 1 else B, record.data_ptr(),
+            self._stream()))
+        return weights, record
+
+    @staticmethod
+    def read_classify_weights_record(record: torch.Tensor) -> dict:
+        """The record of classify_weights as a dict of Python numbers (_capi.CLASSIFY_WEIGHTS_REC's fields): one 40-byte download."""
+        dt = _capi.CLASSIFY_WEIGHTS_REC
+        rec = record.cpu().numpy().view(dt)[0]
+        return {k: (float(rec[k]) if dt[k].kind == "f" else int(rec[k])) for k in dt.names}
 
     def damped_sine(self, seed: int, first_clip: int, B: int, T: int, delta_t: float) -> torch.Tensor:
         """cmps_damped_sine_fill: clips first_clip .. first_clip + B - 1 of the seed's synthetic damped-sine sequence (include/cmps.h),

@@ -273,6 +273,17 @@ def build_parser():
                         "judged as a classifier on the held-out file (BankTrainer.evaluate_classifier)")
     p.add_argument("--bank_classes", default=None, metavar="A,B,C",
                    help="with --bank_by: the classes, in member order (default: the sorted distinct labels of the dataset)")
+    p.add_argument("--bank_objective", default="generative", choices=["generative", "discriminative"],
+                   help="with --bank_by: generative (default) trains member m on the clips of class m alone; discriminative trains the "
+                        "members against each other on ONE shared labelled batch per step (BankTrainer.step_classifier: every member "
+                        "descends gen_weight * loss[own] + disc_weight * cross-entropy of softmax(-loss / temperature)).  No --mps_model rho_mps")
+    p.add_argument("--disc_weight", type=float, default=1.0, help="--bank_objective discriminative: weight of the cross-entropy")
+    p.add_argument("--gen_weight", type=float, default=0.0, help="--bank_objective discriminative: weight of the own member's loss")
+    p.add_argument("--disc_temperature", type=float, default=1.0,
+                   help="--bank_objective discriminative: temperature of the softmax over the members' losses.  A per-clip loss is a sum "
+                        "over sample_duration - 1 samples, so differences between members are of that order: a temperature of that order "
+                        "(e.g. sample_duration) keeps the softmax from saturating where the members' losses differ by that much; where "
+                        "they differ by a few nats (README, \"Class banks\") such a temperature flattens it instead")
     p.add_argument("--eval_storage", default="float32", choices=["float32", "int16", "auto"],
                    help="how a TFRecord held-out set is held on the device (int16: half the memory for 16-bit PCM data, the same bits)")
     return p
@@ -377,6 +388,11 @@ def main(argv=None, backend=None):
     start, count = dp.shard(hp.minibatch_size)
     if args.bank_classes is not None and args.bank_by is None:
         raise ValueError("--bank_classes names the classes of --bank_by KEY: it needs that flag")
+    disc_flags = (args.disc_weight, args.gen_weight, args.disc_temperature) != (1.0, 0.0, 1.0)
+    if args.bank_objective == "discriminative" and args.bank_by is None:
+        raise ValueError("--bank_objective discriminative trains the members of a class bank against each other: it needs --bank_by KEY")
+    if args.bank_objective != "discriminative" and disc_flags:
+        raise ValueError("--disc_weight, --gen_weight and --disc_temperature belong to --bank_objective discriminative")
     if args.bank_by is not None:
         return class_bank_main(args, hp, backend, dp)
     if args.bank or args.bank_hparams:
@@ -467,6 +483,15 @@ def class_bank_main(args, hp, backend, dp):
                          "and every member's batch is gathered from the resident dataset (damped_sine has no labels)")
     if args.host_optimizer:
         raise ValueError("--bank_by runs the device-resident optimiser step of every member (cmps_bank_apply_step): no --host_optimizer")
+    disc = args.bank_objective == "discriminative"
+    if disc and rho:
+        raise ValueError("--bank_objective discriminative trains PsiCMPS members (cmps_bank_loss_bwd_weighted): no --mps_model rho_mps")
+    if disc and not (args.disc_weight >= 0.0 and args.gen_weight >= 0.0 and args.disc_temperature > 0.0
+                     and all(math.isfinite(x) for x in (args.disc_weight, args.gen_weight, args.disc_temperature))):
+        raise ValueError("--bank_objective discriminative needs finite --disc_weight >= 0, --gen_weight >= 0 and --disc_temperature > 0")
+    if disc and not hasattr(backend, "classify_weights"):
+        raise ValueError("--bank_objective discriminative needs a backend with cmps_bank_classify_weights and the weighted reverse pass "
+                         f"(HipScan): this one ({type(backend).__name__}) has none")
     if rho and not all(hasattr(backend, name) for name in RHO_BANK_ENTRIES):
         raise ValueError("--bank_by --mps_model rho_mps needs a backend with the cmps_rho_bank_* entries (HipScan): this one "
                          f"({type(backend).__name__}) has none")
@@ -488,14 +513,25 @@ def class_bank_main(args, hp, backend, dp):
     logdir = f"{args.logdir}/{args.dataset}/{hp.bond_dim}_{hp.delta_t}_{hp.minibatch_size}"    # train.py:94
     if trainer.restore(logdir):
         print(f"Restoring {len(trainer)} members from {logdir} (global_step {trainer.global_step})")
-    stream = data.class_batches(classes, hp.minibatch_size, seed=args.seed, crop=args.crop_duration)
+    if disc:        # one shared labelled batch per step, the members trained against each other (bank.json records the objective)
+        trainer.objective = {"name": "discriminative", "disc_weight": args.disc_weight, "gen_weight": args.gen_weight,
+                             "temperature": args.disc_temperature}
+        stream = data.labelled_batches(classes, hp.minibatch_size, seed=args.seed, order="estimator", crop=args.crop_duration,
+                                       crop_seed=args.seed)           # (shuffle -> repeat -> batch: every batch is full, as class_batches')
+    else:
+        stream = data.class_batches(classes, hp.minibatch_size, seed=args.seed, crop=args.crop_duration)
     held_out = resident(args.eval_dataset, args.eval_storage) if args.eval_dataset else None
     last_save = time.time()
     for it in range(args.max_steps):
         log_now = (it % max(args.log_every, 1) == 0) or it == args.max_steps - 1
-        out = trainer.step(stream(), sync=log_now)
+        if disc:
+            batch, labels = stream()
+            out = trainer.step_classifier(batch, labels, gen_weight=args.gen_weight, disc_weight=args.disc_weight,
+                                          temperature=args.disc_temperature, sync=log_now)
+        else:
+            out = trainer.step(stream(), sync=log_now)
         if log_now:
-            print(bank_log_line(out))
+            print(bank_log_line(out) + (f" xent={out['xent']:.6f} used={out['used']}" if disc else ""))
         if time.time() - last_save > args.save_checkpoint_secs or it == args.max_steps - 1:
             trainer.save(logdir)
             last_save = time.time()

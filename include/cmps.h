@@ -94,7 +94,7 @@ enum {
     CMPS_OPT_F16_SCALE_SHIFT = 4 /* DIAGNOSTIC, default 0: added to the exponent of every data-dependent fp16 scale of the wave reverse
                         * scan's F16X2 arithmetic (range -40 .. 40).  A positive value pushes the pieces out of fp16 range on purpose:
                         * how tests/test_gpu_parity.py provokes CMPS_ERR_F16_RANGE.  No reference counterpart. */,
-    CMPS_OPT_KERNEL_EVENTS = 2 /* 1: every kernel cmps_psi_loss_fwd / _bwd, cmps_rho_loss_fwd / _bwd, cmps_psi_sample, cmps_psi_sample_primed, cmps_psi_stream, cmps_psi_stream_score, cmps_rho_sample_primed, cmps_rho_stream, cmps_rho_stream_score, cmps_noise_fill (as k_noise_philox), cmps_batch_gather (as k_batch_gather), cmps_batch_gather_i16 (as k_batch_gather_i16), cmps_loss_stats (as k_loss_stats), cmps_bank_classify_stats (as k_classify_stats) and cmps_damped_sine_fill (as k_damped_sine) launch is bracketed by two HIP events on the caller's stream
+    CMPS_OPT_KERNEL_EVENTS = 2 /* 1: every kernel cmps_psi_loss_fwd / _bwd, cmps_rho_loss_fwd / _bwd, cmps_psi_sample, cmps_psi_sample_primed, cmps_psi_stream, cmps_psi_stream_score, cmps_rho_sample_primed, cmps_rho_stream, cmps_rho_stream_score, cmps_noise_fill (as k_noise_philox), cmps_batch_gather (as k_batch_gather), cmps_batch_gather_i16 (as k_batch_gather_i16), cmps_loss_stats (as k_loss_stats), cmps_bank_classify_stats (as k_classify_stats), cmps_bank_classify_weights (as k_classify_weights), cmps_bank_loss_bwd_weighted (the scan of cmps_bank_loss_bwd, then "reduce + finalize (weighted)") and cmps_damped_sine_fill (as k_damped_sine) launch is bracketed by two HIP events on the caller's stream
                         * (read and reset with cmps_kernel_times); 0 (default): nothing is recorded.  A measurement aid -- the reference
                         * has no counterpart (no tracing / profiling hooks); bench.py uses it OUTSIDE its timed region to price
                         * each kernel of a multi-kernel family against the pipe it runs on */
@@ -305,6 +305,22 @@ int cmps_bank_set_params_dev(cmps_handle_t h, int M, const float* params_dev, do
  */
 int cmps_bank_loss_fwd(cmps_handle_t h, const float* audio_dev, int n_audio, int B, int T, float* loss_dev, int save_for_bwd, void* stream);
 int cmps_bank_loss_bwd(cmps_handle_t h, const float* audio_dev, int n_audio, int B, int T, float* grad_dev, void* stream);
+
+/*
+ * cmps_bank_loss_bwd with a cotangent per clip and member: member m's grad_dev row is the gradient of sum_b w[m][b] loss[m][b] with
+ * w[m][b] = weight_dev[m * ldw + b] (ldw >= B; the output of cmps_bank_classify_weights, or any float32 values), and its last element
+ * is that weighted sum itself.  Every family a bank may use writes one gradient slab per clip and member, linear in the cotangent of
+ * that clip's loss, and so are the closing terms: the reverse scan is cmps_bank_loss_bwd's, kernel for kernel, and only the cross-clip
+ * reduction and the loss sum differ.  They accumulate (double)w * (double)value -- a product of two float32 values is exact in
+ * double -- in the plain reduction's fixed order (groups of clips, then the groups).  A clip whose weight is exactly 0 (either sign) is
+ * not read at all, neither its slab nor its loss: a diverged clip, or a member absent for a clip, cannot reach the sums or the words of
+ * cmps_bank_grad_status.  Weights of all 1.0f give cmps_bank_loss_bwd's grad_dev bit for bit.
+ * Preconditions, errors and the saved-forward record are cmps_bank_loss_bwd's; in addition a null weight_dev or ldw < B is
+ * CMPS_ERR_BAD_ARG (these two are checked first, on any handle), and a RhoCMPS bank is refused with CMPS_ERR_STATE and a message: its
+ * reverse pass runs `rank` virtual clips per clip and closes with kernels of its own.  Reads weight_dev[m * ldw + b], m < M, b < B only.
+ */
+int cmps_bank_loss_bwd_weighted(cmps_handle_t h, const float* audio_dev, int n_audio, int B, int T, const float* weight_dev, long long ldw,
+                                float* grad_dev, void* stream);
 
 /*
  * Mirrors cmps_psi_apply_step (train.py:55-60, 88-89), one workgroup per member.  vars_dev, adam_m_dev, adam_v_dev, params_dev
@@ -913,6 +929,61 @@ size_t cmps_bank_classify_stats_bytes(int M);
 int cmps_bank_classify_stats(cmps_handle_t h, const float* loss_dev, int M, int B, long long ld,
                              const int* label_dev, long long first_id, int reset,
                              void* stats_dev, int* best_dev, void* stream);
+
+/*
+ * The same [M][B] losses and labels turned into the cotangents of a cross-entropy training step, on the device: the members of a class bank
+ * trained AGAINST each other.  loss_dev[m * ld + b] (ld >= B) as above, the output of cmps_bank_loss_fwd(save_for_bwd = 1) over ONE shared
+ * batch; label_dev[b] the member clip b belongs to; weight_dev[m * ldw + b] (ldw >= B) receives the weights cmps_bank_loss_bwd_weighted takes.
+ * Replaces: nothing -- the reference trains a model per pitch (reader.py:9-66), each on its own clips alone.
+ * THE OBJECTIVE (normative; tests/_disc_ref.py restates it in numpy).  inv_temp = kappa > 0, gen_weight = alpha >= 0, disc_weight = beta >= 0,
+ * doubles.  Per clip b, with l_m = loss_dev[m * ld + b], y = label_dev[b], and a NaN or +-Inf loss making that member ABSENT for that clip:
+ *   SKIPPED  y outside [0, M): every weight of the clip is +0 and it counts in n_unlabelled.  Else member y absent: every weight of the clip
+ *            is +0 and it counts in n_own_absent.  A skipped clip enters nothing else.
+ *   USED     every other clip.  With lmin the smallest present loss, everything in double, the sums in member order:
+ *              S      = sum over the present m of exp(-kappa (l_m - lmin))                         1 <= S <= M
+ *              p_m    = exp(-kappa (l_m - lmin)) / S
+ *              xent   = kappa (l_y - lmin) + log S                                                 >= 0
+ *              w[m][b] = float32(alpha [m == y] + beta kappa ([m == y] - p_m))   for a present m;   +0 for an absent m
+ *            w[m][b] is d J_b / d l_m of J_b = alpha l_y + beta xent_b: the gradient of sum_b J_b with respect to member m's parameters is
+ *            the gradient of sum_b w[m][b] loss[m][b], which cmps_bank_loss_bwd_weighted computes.  With kappa = 1 the xent is exactly the
+ *            one of cmps_bank_classify_stats.
+ * THE RECORD (normative; little-endian, 8-byte aligned; cmps_bank_classify_weights_rec below), 40 bytes:
+ *   offset  type       field
+ *        0  double     sum_xent         over the used clips
+ *        8  double     sum_own_loss     sum of l_y over the used clips
+ *       16  long long  n_used
+ *       24  long long  n_unlabelled
+ *       32  long long  n_own_absent
+ * reset != 0 ignores what the record held (no memset is needed before the first call); reset == 0 continues it.  One workgroup, a fixed
+ * assignment of clips to threads, a fixed reduction tree for the record, no floating-point atomics, and the update is ordered by the
+ * stream -- the same sequence of calls gives the same bits on every run.
+ * ROUNDING.  u = 2^-53, L = max |present loss|, exp and log of the device within 4 ulp = 8 u in double (as for cmps_bank_classify_stats).
+ * The argument a = kappa (l_m - lmin) >= 0 carries two roundings, |da| <= 2 u a, so the computed e_m = exp(-a) is within
+ * u e_m (8 + 2 a) <= u (8 e_m + 0.74) of the exact one (a exp(-a) <= 1 / e).  S, a sum of at most M such terms with S >= 1, is within
+ * u S (1.74 M + 7) of exact; p_m = e_m / S <= 1 within u (0.74 + p_m (1.74 M + 16)) <= u (1.74 M + 17).  [m == y] - p_m, the product
+ * beta kappa, the product of the two and the sum with alpha add four roundings of numbers no larger than alpha + beta kappa.  The result is
+ * rounded to float32 once (a subnormal result to within 2^-150):
+ *   |w[m][b] - exact| <= 2^-24 |exact| + 2^-52 (alpha + beta kappa) (M + 16) + 2^-149
+ * and two evaluations that each meet this bound -- the device's and a float64 restatement -- differ by at most twice it.
+ * A clip's xent: the argument's two roundings (2 u kappa |l_y - lmin| <= 4 u kappa L), log S within u (1.74 M + 7) + 8 u log M
+ * <= u (1.74 M + 63), one sum: within u (2 M + 64 + 4 kappa L + xent).  Summed in double in any order:
+ *   |sum_xent     - exact| <= 2^-52 n_used (M + 32 + 2 kappa L + sum of the exact xent)
+ *   |sum_own_loss - exact| <= 2^-53 n_used (sum of |l_y|)
+ * Needs no cmps_set_params: it works on a fresh handle of any D and in legacy mode.  Asynchronous on `stream`; never synchronises, allocates
+ * nothing, reads loss_dev[m * ld + b] for m < M, b < B and label_dev[0 .. B) only, and writes exactly weight_dev[m * ldw + b] for m < M,
+ * b < B and the 40 bytes of the record.
+ * CMPS_ERR_BAD_ARG, each with a message, the first failing check speaking: a null handle; a null loss_dev; a null label_dev; a null
+ * weight_dev; a null record_dev or one that is not 8-byte aligned; M outside [1, 1024]; B < 1; ld < B; ldw < B; inv_temp not finite or
+ * <= 0; gen_weight not finite or < 0; disc_weight not finite or < 0.
+ * With CMPS_OPT_KERNEL_EVENTS the launch is recorded as k_classify_weights.
+ */
+typedef struct cmps_bank_classify_weights_rec {
+    double sum_xent, sum_own_loss;
+    long long n_used, n_unlabelled, n_own_absent;
+} cmps_bank_classify_weights_rec;
+int cmps_bank_classify_weights(cmps_handle_t h, const float* loss_dev, int M, int B, long long ld, const int* label_dev, double inv_temp,
+                               double gen_weight, double disc_weight, int reset, float* weight_dev, long long ldw, void* record_dev,
+                               void* stream);
 
 /*
  * The synthetic training batch, generated where it is used.  Replaces: the damped_sine branch of get_audio (data.py:8-22): a 261.6 Hz sine

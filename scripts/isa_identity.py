@@ -12,7 +12,9 @@ code only, expects every row "identical".  Needs hipcc, no GPU.  --keep DIR leav
 --kernels REGEX adds one row per kernel whose (mangled) symbol matches, in the translation units that differ: the kernel's body
 (its label to its end label) and its .amdhsa_kernel descriptor block, compared as text with the kernel's own symbol and the
 function index of its labels normalised -- for a change that adds kernels or instances to a file and must leave the existing ones
-alone.  Kernels are paired by demangled name, trailing template arguments `false` dropped."""
+alone.  Kernels are paired by demangled name, trailing template arguments `false` dropped.  "same instructions": only directives
+differ (the kernel-argument segment grew, the kernel moved to a template instance's section) and, where the segment grew by g bytes,
+scalar loads of hidden kernel arguments that moved g bytes with it; each such line is printed."""
 import argparse
 import hashlib
 import importlib.util
@@ -69,6 +71,7 @@ def kernel_key(sym):
     if not filt:
         raise RuntimeError("--kernels needs c++filt (or llvm-cxxfilt) to pair the kernels of the two trees")
     name = subprocess.run([filt, sym], stdout=subprocess.PIPE, text=True, check=True).stdout.strip()
+    name = name.replace("(anonymous namespace)", "{anonymous}")          # (its parenthesis is not the argument list's)
     name = re.sub(r"^void ", "", name.split("(")[0]).replace(" ", "")
     args = [x for x in re.sub(r"^[^<]*<?|>$", "", name).split(",") if x] if "<" in name else []
     while args and args[-1] == "false":
@@ -138,13 +141,24 @@ def main():
                     lp, lc = tp.split("\n"), tc.split("\n")
                     if len(lp) == len(lc):
                         extra = [(x.strip(), y.strip()) for x, y in zip(lp, lc) if x != y]
-                        if all(re.match(r"\.(amdhsa_kernarg_size|text|section)\b", x) and re.match(r"\.(amdhsa_kernarg_size|text|section)\b", y) for x, y in extra):
+                        directive = r"\.(amdhsa_kernarg_size|text|section)\b"
+                        # a kernel-argument segment that grew by g bytes moves the 256 bytes of hidden arguments behind it by g: a scalar
+                        # load from the kernarg pointer s[0:1] at an offset inside the parent's hidden block, the same load g bytes further
+                        # on in the change, is the same instruction reading the same hidden argument
+                        size = [int(m.group(1)) if m else 0 for m in (re.search(r"\.amdhsa_kernarg_size (\d+)", t) for t in (tp, tc))]
+                        load = r"(s_load_dword\w* s\S+ s\[0:1\], )(0x[0-9a-f]+)$"
+
+                        def moved(x, y):
+                            mx, my = re.match(load, x), re.match(load, y)
+                            return bool(mx and my and mx.group(1) == my.group(1) and int(mx.group(2), 16) >= size[0] - 256
+                                        and int(my.group(2), 16) - int(mx.group(2), 16) == size[1] - size[0] != 0)
+                        if all((re.match(directive, x) and re.match(directive, y)) or moved(x, y) for x, y in extra):
                             verdict = "same instructions"
                 ktotal += tp is not None
                 ksame += verdict in ("identical", "same instructions")
                 print(f"{lab:20s} {tp.count(chr(10)) if tp else 0:8d} {tc.count(chr(10)) if tc else 0:8d}  {verdict:22s} {key}")
                 for x, y in sorted(set(extra)) if verdict == "same instructions" else []:
-                    print(f"{'':40s}    directive: {x}  ->  {y}")
+                    print(f"{'':40s}    {'directive' if x.startswith('.') else 'hidden argument'}: {x}  ->  {y}")
         print(f"\n{ksame} of {ktotal} kernels of the parent with identical instructions")
         return 0 if ksame == ktotal else 1
     return 0 if same == len(todo) else 1

@@ -16,7 +16,8 @@ rows = []
 for line in out.splitlines():
     m = re.search(r"remark: .*?Function Name: (\S+)", line) or re.search(r"Name: (\S+) \[", line)
     if m:
-        cur = {"name": subprocess.run(["c++filt", m.group(1)], capture_output=True, text=True).stdout.strip().split("(")[0]}
+        name = subprocess.run(["c++filt", m.group(1)], capture_output=True, text=True).stdout.strip()
+        cur = {"name": name.replace("(anonymous namespace)::", "").split("(")[0]}
         rows.append(cur)
         continue
     m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[bytes/(?:lane|block)\])?(?: \[waves/SIMD\])?: (\d+)", line)
