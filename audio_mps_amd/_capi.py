@@ -60,7 +60,7 @@ SYMBOLS = (
     "cmps_rho_workspace_bytes", "cmps_rho_set_state", "cmps_rho_loss_fwd", "cmps_rho_loss_bwd",
     "cmps_rho_update_ancilla", "cmps_rho_sample", "cmps_rho_sample_primed", "cmps_rho_stream_state_bytes", "cmps_rho_stream", "cmps_rho_stream_score", "cmps_rho_states",
     "cmps_rho_apply_step_scratch_bytes", "cmps_rho_apply_step", "cmps_noise_fill", "cmps_batch_gather", "cmps_batch_gather_i16", "cmps_loss_stats", "cmps_damped_sine_fill", "cmps_crc32c",
-    "cmps_bank_classify_stats_bytes", "cmps_bank_classify_stats", "cmps_bank_classify_weights", "cmps_bank_loss_bwd_weighted",
+    "cmps_bank_classify_stats_bytes", "cmps_bank_classify_stats", "cmps_bank_classify_weights", "cmps_bank_posterior", "cmps_bank_loss_bwd_weighted",
     "cmps_bank_workspace_bytes", "cmps_bank_set_params_dev", "cmps_bank_loss_fwd", "cmps_bank_loss_bwd", "cmps_bank_apply_step_scratch_bytes",
     "cmps_bank_apply_step", "cmps_bank_grad_status", "cmps_bank_stream_state_bytes", "cmps_bank_stream", "cmps_bank_stream_score",
     "cmps_rho_bank_workspace_bytes", "cmps_rho_bank_set_state_dev", "cmps_rho_bank_loss_fwd", "cmps_rho_bank_loss_bwd",
@@ -85,6 +85,10 @@ CLASSIFY_MAX_M = 1024
 CLASSIFY_WEIGHTS_REC = np.dtype([("sum_xent", "<f8"), ("sum_own_loss", "<f8"), ("n_used", "<i8"), ("n_unlabelled", "<i8"),
                                  ("n_own_absent", "<i8")])
 assert CLASSIFY_WEIGHTS_REC.itemsize == 40
+
+# the 16-byte decision record of cmps_bank_posterior (include/cmps.h: cmps_bank_decision), little-endian, one per path
+DECISION_REC = np.dtype([("step", "<i8"), ("member", "<i4"), ("reserved", "<i4")])
+assert DECISION_REC.itemsize == 16
 
 
 def classify_stats_dtype(M: int) -> np.dtype:
@@ -202,6 +206,9 @@ def _declare(lib):
     lib.cmps_bank_classify_weights.argtypes = [vp, vp, c_int, c_int, ctypes.c_longlong, vp, c_double, c_double, c_double, c_int, vp,
                                                ctypes.c_longlong, vp, vp]
     lib.cmps_bank_classify_weights.restype = c_int
+    lib.cmps_bank_posterior.argtypes = [vp, vp, c_int, c_int, c_int, vp, vp, c_double, vp, vp, vp, vp, c_double, ctypes.c_longlong, c_int, vp,
+                                        vp]
+    lib.cmps_bank_posterior.restype = c_int
     lib.cmps_bank_loss_bwd_weighted.argtypes = [vp, vp, c_int, c_int, c_int, vp, ctypes.c_longlong, vp, vp]
     lib.cmps_bank_loss_bwd_weighted.restype = c_int
     lib.cmps_damped_sine_fill.argtypes = [vp, ctypes.c_ulonglong, ctypes.c_ulonglong, c_int, c_int, c_double, vp, vp]

@@ -51,6 +51,7 @@ class PsiBank:
         if len(members) < 1:
             raise ValueError("a bank needs at least one member")
         self.classes = None if classes is None else [c if isinstance(c, str) else int(c) for c in classes]     # member m models classes[m]
+        self.class_counts = None            # clips per class of the training set, where somebody counted them (bank.json keeps them)
         self.label_key = label_key          # the TFRecord feature the classes are values of (bank.json keeps it for evaluate / sample)
         if self.classes is not None and (len(self.classes) != len(members) or len(set(self.classes)) != len(self.classes)):
             raise ValueError(f"a class bank needs one distinct class per member: {len(members)} members, classes {self.classes}")
@@ -94,13 +95,16 @@ class PsiBank:
             return type(be)(self.bond_d, device=be.device, variant=be.variant)
         return type(be)(self.bond_d)
 
-    def open_stream(self, num_paths, max_steps, temp=1, seed=None, device_noise=False, independent_noise=False):
+    def open_stream(self, num_paths, max_steps, temp=1, seed=None, device_noise=False, independent_noise=False, prior=None,
+                    temperature=1.0, threshold=None):
         """``PsiCMPS.open_stream`` (RhoBank: ``RhoCMPS.open_stream`` without keep_states) for every member at once: a BankStream
         (audio_mps_amd/stream.py) of ``num_paths`` paths per member.  It runs on a backend of its own, so it never disturbs a trainer's workspace on the bank's shared one, and keeps the parameters
         the members have now.  By default member m, path b hears the noise ``models[m].open_stream(num_paths, ..., seed=seed)`` would
-        give path b; ``independent_noise=True`` numbers the paths globally (g = m num_paths + b)."""
+        give path b; ``independent_noise=True`` numbers the paths globally (g = m num_paths + b).  ``prior`` ([M] probabilities, normalised
+        here; None: uniform), ``temperature`` and ``threshold`` are what the stream's ``score_posterior`` judges the members with."""
         from .stream import BankStream
-        return BankStream(self, num_paths, max_steps, temp=temp, seed=seed, device_noise=device_noise, independent_noise=independent_noise)
+        return BankStream(self, num_paths, max_steps, temp=temp, seed=seed, device_noise=device_noise, independent_noise=independent_noise,
+                          prior=prior, temperature=temperature, threshold=threshold)
 
     def sample(self, n, length, temp=1, seed=None, prime=None, device_noise=False) -> np.ndarray:
         """``PsiCMPS.sample`` (RhoBank: ``RhoCMPS.sample``) of every member, [M, n, length] in the reference's convention (A * running sum
@@ -123,7 +127,22 @@ class PsiBank:
         _, st = self._scored(clips, None)
         return st.best(), st.total_nll
 
-    def _scored(self, clips, segment):
+    def posterior_trace(self, clips, prior=None, temperature=1.0, threshold=None, segment=None, want_post=False):
+        """``classify`` after every sample: one scored bank stream with one path per clip of ``clips`` [B, T], judged by
+        ``BankStream.score_posterior`` in segments of ``segment`` steps when given (the cut changes no bit).  Returns a PosteriorTrace:
+        ``best``, ``conf`` [B, T - 1] (``post`` [M, B, T - 1] with want_post) and ``decided_at``, ``decided_as`` [B] -- the step, counted
+        from 0, at which the best member's probability first reached ``threshold``, and that member; -1 for a clip that never got there."""
+        clips, S = self._clips(clips, segment)
+        B, N = clips.shape[0], clips.shape[1] - 1
+        st = self.open_stream(B, N, prior=prior, temperature=temperature, threshold=threshold)
+        parts = [st.score_posterior(clips[:, :S + 1], want_post=want_post)]
+        for a in range(S + 1, N + 1, S):
+            parts.append(st.score_posterior(clips[:, a:a + S], want_post=want_post))
+        from .stream import PosteriorTrace
+        cat = lambda key: np.concatenate([getattr(p, key) for p in parts], axis=-1)                 # noqa: E731
+        return PosteriorTrace(cat("best"), cat("conf"), cat("post") if want_post else None, None, parts[-1].decided_at, parts[-1].decided_as)
+
+    def _clips(self, clips, segment):
         if hasattr(clips, "detach"):
             clips = clips.detach().cpu().numpy()
         clips = np.asarray(clips, dtype=np.float32)
@@ -131,10 +150,14 @@ class PsiBank:
             clips = clips[None, :]
         if clips.ndim != 2 or clips.shape[1] < 2:
             raise ValueError("clips must be [B, T] with T >= 2")
-        B, N = clips.shape[0], clips.shape[1] - 1
-        S = N if segment is None else int(segment)
+        S = clips.shape[1] - 1 if segment is None else int(segment)
         if S < 1:
             raise ValueError("segment must be positive")
+        return clips, S
+
+    def _scored(self, clips, segment):
+        clips, S = self._clips(clips, segment)
+        B, N = clips.shape[0], clips.shape[1] - 1
         st = self.open_stream(B, N)
         parts = [st.score(clips[:, :S + 1])]                          # the anchor and S steps
         for a in range(S + 1, N + 1, S):
@@ -313,10 +336,12 @@ class BankTrainer(ResidentState):
         self.sync_to_host()
         return self.trainers[m].model
 
-    def open_stream(self, num_paths, max_steps, temp=1, seed=None, device_noise=False, independent_noise=False):
+    def open_stream(self, num_paths, max_steps, temp=1, seed=None, device_noise=False, independent_noise=False, prior=None,
+                    temperature=1.0, threshold=None):
         """``PsiBank.open_stream`` on the members' current variables: the device-resident state comes back first."""
         self.sync_to_host()
-        return self.bank.open_stream(num_paths, max_steps, temp=temp, seed=seed, device_noise=device_noise, independent_noise=independent_noise)
+        return self.bank.open_stream(num_paths, max_steps, temp=temp, seed=seed, device_noise=device_noise, independent_noise=independent_noise,
+                                     prior=prior, temperature=temperature, threshold=threshold)
 
     # -- held-out evaluation ------------------------------------------------------------------------------
     def evaluate(self, dataset, minibatch_size: Optional[int] = None, T: Optional[int] = None, keep_losses: bool = False):
@@ -393,6 +418,8 @@ class BankTrainer(ResidentState):
             meta["model"] = self.bank.MODEL_NAME
         if self.bank.classes is not None:     # (and so does the file of a bank without classes)
             meta["label_key"], meta["classes"] = self.bank.label_key, self.bank.classes
+        if getattr(self.bank, "class_counts", None) is not None:      # clips per class of the training set: an empirical prior
+            meta["class_counts"] = [int(c) for c in self.bank.class_counts]
         if self.objective is not None:        # (and of a generatively trained one)
             meta["objective"] = self.objective
         tmp = os.path.join(directory, "bank.json.tmp")

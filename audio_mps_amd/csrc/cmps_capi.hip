@@ -1097,6 +1097,37 @@ int cmps_bank_classify_weights(cmps_handle_t h, const float* loss_dev, int M, in
     return CMPS_OK;
 }
 
+// The per-step losses of a scored bank stream folded into the posterior over the members after every step: needs nothing of the handle either
+int cmps_bank_posterior(cmps_handle_t h, const float* nll_dev, int M, int n, int steps, const float* total_in_dev, const double* log_prior_dev,
+                        double inv_temp, float* total_out_dev, float* post_dev, int* best_dev, float* conf_dev, double threshold,
+                        long long first_step, int reset, void* decision_dev, void* stream) {
+    const std::string w("cmps_bank_posterior");
+    if (!h) return CMPS_ERR_BAD_ARG;
+    if (!nll_dev) return fail(h, CMPS_ERR_BAD_ARG, w + ": nll_dev is a null pointer");
+    if (M < 1 || M > CLASSIFY_MAX_M) return fail(h, CMPS_ERR_BAD_ARG, w + ": need 1 <= M <= 1024");
+    if (n < 1) return fail(h, CMPS_ERR_BAD_ARG, w + ": need n >= 1");
+    if (steps < 1) return fail(h, CMPS_ERR_BAD_ARG, w + ": need steps >= 1");
+    if ((long long)M * (long long)n > 2147483647ll / (long long)steps)
+        return fail(h, CMPS_ERR_BAD_ARG, w + ": need M * n * steps <= 2^31 - 1");
+    if (!std::isfinite(inv_temp) || !(inv_temp > 0.0)) return fail(h, CMPS_ERR_BAD_ARG, w + ": inv_temp must be finite and positive");
+    if (((uintptr_t)log_prior_dev & 7) != 0) return fail(h, CMPS_ERR_BAD_ARG, w + ": log_prior_dev must be 8-byte aligned");
+    if (((uintptr_t)decision_dev & 7) != 0) return fail(h, CMPS_ERR_BAD_ARG, w + ": decision_dev must be 8-byte aligned");
+    if (decision_dev) {
+        if (!std::isfinite(threshold) || !(threshold > 0.0) || threshold > 1.0)
+            return fail(h, CMPS_ERR_BAD_ARG, w + ": threshold must lie in (0, 1] where decision_dev is given");
+        if (first_step < 0 || first_step > 9223372036854775807ll - (long long)steps)
+            return fail(h, CMPS_ERR_BAD_ARG,
+                        w + ": need first_step >= 0 and first_step + steps below 2^63 (a step is a signed 64-bit integer)");
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    KBind kb(h);
+    KScope ks("k_bank_posterior", s);
+    const hipError_t e = launch_bank_posterior(nll_dev, M, n, steps, total_in_dev, log_prior_dev, inv_temp, total_out_dev, post_dev, best_dev,
+                                               conf_dev, threshold, first_step, reset, decision_dev, s);
+    if (e != hipSuccess) return fail_hip(h, e, "cmps_bank_posterior");
+    return CMPS_OK;
+}
+
 int cmps_damped_sine_fill(cmps_handle_t h, unsigned long long seed, unsigned long long first_clip, int B, int T, double delta_t,
                           float* audio_dev, void* stream) {
     if (!h) return CMPS_ERR_BAD_ARG;

@@ -11,7 +11,8 @@
 // ordered by the stream, so the same sequence of calls gives the same bits on every run.  A batch is a few thousand floats: one workgroup
 // reads it in a few microseconds, and more of them would need the second pass or the atomics this kernel does without.
 // k_classify_stats (cmps_bank_classify_stats), further down: the [M][B] losses of a bank of one model per class judged as a classifier.
-// k_classify_weights (cmps_bank_classify_weights), last: the same losses turned into the per-clip, per-member cotangents of a cross-entropy step.
+// k_classify_weights (cmps_bank_classify_weights), behind it: the same losses turned into the per-clip, per-member cotangents of a cross-entropy step.
+// k_bank_posterior (cmps_bank_posterior), last: the per-step losses of a scored bank stream folded into a posterior over the members after every step.
 #include "cmps_internal.h"
 
 namespace cmps {
@@ -280,6 +281,178 @@ __global__ __launch_bounds__(STATS_NT) void k_classify_weights(const float* __re
     }
 }
 
+// k_bank_posterior (cmps_bank_posterior): the per-step losses nll[M][n][steps] of a scored bank stream folded into the running totals and,
+// after EVERY step, the posterior over the members, the best member, its probability and the first step at which the bank was sure
+// (include/cmps.h states it; tests/_posterior_ref.py restates it).  Two shapes of work: per row (m, g) a chain of `steps` dependent float32
+// additions -- the fold of the score kernels, bit for bit, so no tree scan -- and per (g, k) a soft-max over the M members in double.
+// ONE workgroup of POST_NT threads per path g; the steps go by in chunks of C (64; 32 above 512 members, where the tile has to fit the LDS):
+//   load    thread (part, k) = (t / C, t % C) holds step k of the rows part, part + P, ... (P = POST_NT / C) of the chunk in R registers --
+//           every load is C consecutive floats of one row -- and puts them into tile[m][C + 1]; the NEXT chunk's loads are issued right
+//           behind, so they are in flight while this chunk is folded and judged (R = the rows a thread holds, a template parameter)
+//   fold    thread t walks rows t, t + POST_NT, ... of the tile with the total in a register and leaves the running totals in place
+//           (the odd row pitch spreads the lanes of a wave over the banks)
+//   judge   thread (part, k) takes step k and the members part, part + P, ...: the smallest a and its member, then the sum of
+//           exp(-(a - amin)), each merged over the P parts through LDS in part order; post, best and conf from there
+//   decide  wave 0 holds the path's decision record in registers: one ballot over the chunk's steps, the lowest set bit is the first
+// nll is read once, the only scratch is LDS, nothing is atomic, and the assignment of work to threads is fixed: the same bits on every run.
+constexpr int POST_NT = 512;
+constexpr int POST_ROWS = CLASSIFY_MAX_M / POST_NT;      // rows of the tile a thread folds, at most
+
+struct alignas(8) BankDecision {       // the record of include/cmps.h (cmps_bank_decision), field for field
+    long long step;
+    int member, reserved;
+};
+static_assert(sizeof(BankDecision) == 16, "the record of cmps_bank_posterior is 16 bytes");
+
+// grid n; dynamic LDS posterior_lds_bytes(M, C); R > 0: M <= R * POST_NT / C, the next chunk prefetched; R == 0: any M, no prefetch
+template <int C, int R>
+__global__ __launch_bounds__(POST_NT) void k_bank_posterior(const float* __restrict__ nll, int M, int n, int steps, const float* total_in,
+                                                            const double* __restrict__ log_prior, double kappa, float* total_out,
+                                                            float* __restrict__ post, int* __restrict__ best_out,
+                                                            float* __restrict__ conf_out, double threshold, long long first_step, int reset,
+                                                            BankDecision* __restrict__ decision) {
+    constexpr int P = POST_NT / C, LD = C + 1;
+    extern __shared__ __attribute__((aligned(8))) unsigned char post_lds[];
+    __shared__ double s_min[POST_NT], s_sum[POST_NT];
+    __shared__ int s_arg[POST_NT];
+    double* lp = reinterpret_cast<double*>(post_lds);                                        // [M]
+    float* tile = reinterpret_cast<float*>(lp + M);                                           // [M][LD]
+    const int tid = threadIdx.x, k = tid % C, part = tid / C;
+    const size_t g = blockIdx.x;
+    const double inf = __longlong_as_double(0x7ff0000000000000ll);
+    for (int m = tid; m < M; m += POST_NT) lp[m] = log_prior ? log_prior[m] : 0.0;
+    float tot[POST_ROWS];
+#pragma unroll
+    for (int j = 0; j < POST_ROWS; ++j) {
+        const int m = tid + j * POST_NT;
+        tot[j] = (m < M && total_in) ? total_in[(size_t)m * n + g] : 0.f;
+    }
+    long long d_step = -1ll;                                                                  // (wave 0: the path's record)
+    int d_member = -1, d_reserved = 0;
+    if (decision && !reset && tid < 64) {
+        const BankDecision r = decision[g];
+        d_step = r.step, d_member = r.member, d_reserved = r.reserved;
+    }
+    float pre[R > 0 ? R : 1];                                                                 // this thread's part of the chunk to come
+    auto fetch = [&](int k0) {
+        const bool in = k0 + k < steps;
+#pragma unroll
+        for (int i = 0; i < R; ++i) {
+            const int m = part + i * P;
+            pre[i] = (in && m < M) ? nll[((size_t)m * n + g) * steps + k0 + k] : 0.f;
+        }
+    };
+    fetch(0);
+    for (int k0 = 0; k0 < steps; k0 += C) {
+        const int len = steps - k0 < C ? steps - k0 : C;
+        if constexpr (R > 0) {
+            if (k < len) {
+#pragma unroll
+                for (int i = 0; i < R; ++i) {
+                    const int m = part + i * P;
+                    if (m < M) tile[m * LD + k] = pre[i];
+                }
+            }
+            if (k0 + C < steps) fetch(k0 + C);     // in flight while this chunk is folded and judged
+        } else if (k < len) {                      // R == 0, the banks too wide to hold a chunk in registers: dozens of loads a thread anyway
+#pragma unroll 8
+            for (int m = part; m < M; m += P) tile[m * LD + k] = nll[((size_t)m * n + g) * steps + k0 + k];
+        }
+        __syncthreads();                          // (also: lp is in place before the first chunk is judged)
+#pragma unroll
+        for (int j = 0; j < POST_ROWS; ++j) {
+            const int m = tid + j * POST_NT;
+            if (m < M) {
+                float* row = tile + m * LD;
+                float c = tot[j];
+                if (len == C) {                   // a whole chunk: the offsets are constants, the row's reads go out ahead of the chain
+#pragma unroll
+                    for (int i = 0; i < C; ++i) {
+                        c += row[i];              // ONE float32 addition per step, in step order
+                        row[i] = c;
+                    }
+                } else {
+#pragma unroll 8
+                    for (int i = 0; i < len; ++i) {
+                        c += row[i];
+                        row[i] = c;
+                    }
+                }
+                tot[j] = c;
+            }
+        }
+        __syncthreads();
+        double amin = inf;
+        int arg = -1;
+        if (k < len)
+            for (int m = part; m < M; m += P) {
+                const float c = tile[m * LD + k];
+                if (is_finite_f32(c)) {
+                    const double a = kappa * (double)c - lp[m];
+                    if (a < amin) { amin = a; arg = m; }          // (strict, m ascending: the lowest m keeps a tie; a = +inf never wins)
+                }
+            }
+        s_min[tid] = amin;
+        s_arg[tid] = arg;
+        __syncthreads();
+        amin = inf, arg = -1;
+#pragma unroll
+        for (int p = 0; p < P; ++p) {
+            const double a = s_min[p * C + k];
+            const int r = s_arg[p * C + k];
+            if (r >= 0 && (arg < 0 || a < amin || (a == amin && r < arg))) { amin = a; arg = r; }
+        }
+        double S = 0.0;
+        if (k < len && arg >= 0) {
+#pragma unroll 4
+            for (int m = part; m < M; m += P) {   // (no branch around the exp: the members' terms can overlap; exp(-inf) = +0)
+                const float c = tile[m * LD + k];
+                S += exp(is_finite_f32(c) ? -((kappa * (double)c - lp[m]) - amin) : -inf);
+            }
+        }
+        s_sum[tid] = S;
+        __syncthreads();
+        S = 0.0;
+#pragma unroll
+        for (int p = 0; p < P; ++p) S += s_sum[p * C + k];
+        const double inv_S = arg >= 0 ? 1.0 / S : 0.0;
+        if (k < len) {
+            const size_t at = g * steps + k0 + k;
+            if (post)
+                for (int m = part; m < M; m += P) {
+                    const float c = tile[m * LD + k];
+                    float p = 0.f;
+                    if (arg >= 0 && is_finite_f32(c)) p = (float)(exp(-((kappa * (double)c - lp[m]) - amin)) / S);
+                    post[(size_t)m * n * steps + at] = p;
+                }
+            if (part == 0) {
+                if (best_out) best_out[at] = arg;
+                if (conf_out) conf_out[at] = (float)inv_S;
+            }
+        }
+        if (decision && tid < 64) {                // part 0 sits in wave 0's lanes 0 .. C - 1: lane k is step k0 + k
+            const unsigned long long sure = __ballot(part == 0 && k < len && arg >= 0 && inv_S >= threshold);
+            if (d_step < 0 && sure != 0ull) {
+                const int first = __ffsll((long long)sure) - 1;
+                d_step = first_step + (long long)(k0 + first);
+                d_member = __shfl(arg, first);
+            }
+        }
+        if (post) __syncthreads();                // post was the tile's last reader; without it the barrier behind the partial sums was,
+                                                  // and the three arrays are rewritten only behind two barriers of the next chunk
+    }
+    if (total_out) {
+#pragma unroll
+        for (int j = 0; j < POST_ROWS; ++j) {
+            const int m = tid + j * POST_NT;
+            if (m < M) total_out[(size_t)m * n + g] = tot[j];
+        }
+    }
+    if (decision && tid == 0) decision[g] = BankDecision{d_step, d_member, d_reserved};
+}
+
+inline size_t posterior_lds_bytes(int M, int C) { return (size_t)M * (sizeof(double) + sizeof(float) * (size_t)(C + 1)); }
+
 }  // namespace
 
 // The caller (cmps_loss_stats) has checked: B >= 1, first_id >= 0, first_id + B representable, stats 8-byte aligned
@@ -304,6 +477,28 @@ hipError_t launch_classify_weights(const float* loss, int M, int B, long long ld
     hipLaunchKernelGGL(k_classify_weights, dim3(1), dim3(STATS_NT), 0, s, loss, M, B, ld, label, inv_temp, gen_weight, disc_weight, reset,
                        weight, ldw, static_cast<ClassifyWeightsRec*>(record));
     return hipGetLastError();
+}
+
+// The caller (cmps_bank_posterior) has checked: 1 <= M <= 1024, n >= 1, steps >= 1, M n steps <= 2^31 - 1, inv_temp finite and > 0,
+// log_prior and decision 8-byte aligned, and with a decision: threshold in (0, 1], first_step >= 0, first_step + steps representable;
+// every pointer but nll may be null
+hipError_t launch_bank_posterior(const float* nll, int M, int n, int steps, const float* total_in, const double* log_prior, double inv_temp,
+                                 float* total_out, float* post, int* best, float* conf, double threshold, long long first_step, int reset,
+                                 void* decision, hipStream_t s) {
+    auto go = [&](auto kernel, int C) -> hipError_t {
+        const size_t shm = posterior_lds_bytes(M, C);
+        const hipError_t e = lds_attr(kernel, shm);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(kernel, dim3(n), dim3(POST_NT), shm, s, nll, M, n, steps, total_in, log_prior, inv_temp, total_out, post, best,
+                           conf, threshold, first_step, reset, static_cast<BankDecision*>(decision));
+        return hipGetLastError();
+    };
+    // R: the rows of a chunk a thread holds, M <= R POST_NT / C; beyond 256 members a chunk does not fit the registers (R = 0)
+    if (M <= 64) return go(k_bank_posterior<64, 8>, 64);
+    if (M <= 128) return go(k_bank_posterior<64, 16>, 64);
+    if (M <= POSTERIOR_PREFETCH_M) return go(k_bank_posterior<64, 32>, 64);
+    if (M <= POSTERIOR_WIDE_M) return go(k_bank_posterior<64, 0>, 64);
+    return go(k_bank_posterior<32, 0>, 32);
 }
 
 }  // namespace cmps

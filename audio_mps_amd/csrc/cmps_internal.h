@@ -519,6 +519,13 @@ hipError_t launch_classify_stats(const float* loss, int M, int B, long long ld, 
 // ... and turned into weight[m * ldw + b], the cotangents of the cross-entropy objective of cmps_bank_classify_weights, and its 40-byte record
 hipError_t launch_classify_weights(const float* loss, int M, int B, long long ld, const int* label, double inv_temp, double gen_weight,
                                    double disc_weight, int reset, float* weight, long long ldw, void* record, hipStream_t s);
+// ... and nll[(m * n + g) * steps + k] of a scored bank stream folded into running totals and the posterior over the members after every
+// step (cmps_bank_posterior); a bank of more than POSTERIOR_WIDE_M members goes by in chunks of 32 steps instead of 64
+constexpr int POSTERIOR_WIDE_M = 512;
+constexpr int POSTERIOR_PREFETCH_M = 256;      // up to here a thread holds the next chunk's loads in registers while it works on this one
+hipError_t launch_bank_posterior(const float* nll, int M, int n, int steps, const float* total_in, const double* log_prior, double inv_temp,
+                                 float* total_out, float* post, int* best, float* conf, double threshold, long long first_step, int reset,
+                                 void* decision, hipStream_t s);
 // floats of one path's stream record (StreamDev::rec), a multiple of 4: wave u, |y|^2 partial per lane, running sum | wide ut [2 DP], |y|^2
 // partial per wave [DP / 16], running sum | block u [2 D], running sum
 constexpr int STREAM_REC_WAVE = 132;

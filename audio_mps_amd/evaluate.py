@@ -175,7 +175,67 @@ def build_parser():
                         "(int32, -1: undecided)")
     p.add_argument("--confusion", default=None, metavar="OUT.npy", help="with --bankdir: write the confusion matrix, int64 [M, M] "
                    "(row = the clip's class, column = the member that won it)")
+    p.add_argument("--listen", action="store_true", help="with --bankdir: judge the bank as a STREAMING classifier (cmps_bank_posterior): "
+                   "how many samples it hears before it is sure, and whether it is right then")
+    p.add_argument("--threshold", type=float, default=0.99, metavar="P", help="with --listen: sure means the best member's posterior "
+                   "probability reached P")
+    p.add_argument("--temperature", type=float, default=1.0, help="with --listen: the members' total losses are divided by it")
+    p.add_argument("--prior", default=None, metavar="P0,P1,...|empirical", help="with --listen: the members' prior probabilities, or "
+                   "'empirical': the class counts bank.json holds (default: uniform)")
+    p.add_argument("--listen_curve", default=None, metavar="OUT.npy", help="with --listen: write the accuracy of the best member after "
+                   "every sample, float64 [steps]")
     return p
+
+
+LISTEN_FRACTIONS = ((1, 16), (1, 8), (1, 4), (1, 2), (1, 1))
+
+
+def listen_main(args, backend=None) -> dict:
+    """``--bankdir --listen``: one pass of the dataset through ``bank.posterior_trace``, a batch of clips per scored bank stream.  Per batch
+    ``best`` [B, steps] and the decisions come down once; the accuracy after every sample is counted here from ``best``."""
+    from .device_data import ResidentDataset
+    from .sample import load_bank, parse_prior
+    bank = load_bank(args.bankdir, args.sample_rate, args.hparams, args.kernel_variant, backend)
+    if bank.classes is None or bank.label_key is None:
+        raise ValueError(f"{args.bankdir} holds a bank without classes: --bankdir judges what train --bank_by saved")
+    prior = parse_prior(args.prior, bank, args.bankdir)
+    path = os.path.join(str(args.datadir), f"{args.dataset}.tfrecords")
+    if not os.path.exists(path):
+        raise FileNotFoundError(path)
+    ds = ResidentDataset.from_tfrecord(path, args.sample_duration, bank.backend, storage=args.storage, label_key=bank.label_key)
+    labels = ds.class_positions(bank.classes)
+    steps = ds.clip_len - 1
+    right = np.zeros(steps, dtype=np.int64)                              # labelled clips whose best member after step k is their own
+    at, as_, n_lab = [], [], 0
+    for first_id, batch in ds.ordered(args.minibatch_size):
+        tr = bank.posterior_trace(batch, prior=prior, temperature=args.temperature, threshold=args.threshold)
+        y = labels[first_id:first_id + tr.best.shape[0]]
+        known = y >= 0
+        right += np.sum(tr.best[known] == y[known, None], axis=0)
+        n_lab += int(known.sum())
+        at.append(tr.decided_at)
+        as_.append(tr.decided_as)
+    if not at:
+        raise ValueError("evaluate --listen: the dataset yielded no batch")
+    at, as_ = np.concatenate(at), np.concatenate(as_)
+    known, decided = labels[:len(at)] >= 0, at >= 0
+    both = known & decided
+    curve = right / max(n_lab, 1)
+    res = {"clips": int(len(at)), "labelled": n_lab, "threshold": float(args.threshold), "temperature": float(args.temperature),
+           "decided": float(decided.mean()), "mean_decision_sample": float(at[decided].mean()) if decided.any() else None,
+           "median_decision_sample": float(np.median(at[decided])) if decided.any() else None,
+           "accuracy_at_decision": float(np.mean(as_[both] == labels[:len(at)][both])) if both.any() else None,
+           "accuracy_after": {f"{a}/{b}": float(curve[max(steps * a // b, 1) - 1]) for a, b in LISTEN_FRACTIONS}}
+    if args.listen_curve is not None:
+        np.save(args.listen_curve, curve)
+    fmt = lambda x: "-" if x is None else f"{x:.6g}"                       # noqa: E731
+    print(f"listen {args.dataset}: decided={res['decided']:.4f} mean_sample={fmt(res['mean_decision_sample'])} "
+          f"median_sample={fmt(res['median_decision_sample'])} accuracy_at_decision={fmt(res['accuracy_at_decision'])} "
+          + " ".join(f"acc@{k}={v:.4f}" for k, v in res["accuracy_after"].items())
+          + f" clips={res['clips']} threshold={args.threshold:g} temperature={args.temperature:g} storage={ds.storage}")
+    if args.json:
+        print(json.dumps({"dataset": args.dataset, "storage": ds.storage, **res}))
+    return res
 
 
 def bank_main(args, backend=None) -> ClassifierResult:
@@ -208,6 +268,12 @@ def main(argv=None, backend=None) -> EvalResult:
     args = build_parser().parse_args(argv)
     if args.sample_duration < 2 or args.minibatch_size < 1:
         raise ValueError("--sample_duration must be at least 2 and --minibatch_size positive")
+    if args.listen:
+        if args.bankdir is None:
+            raise ValueError("--listen judges a class bank: it needs --bankdir")
+        if not (0.0 < args.threshold <= 1.0 and args.temperature > 0.0):
+            raise ValueError("--listen needs --threshold in (0, 1] and --temperature > 0")
+        return listen_main(args, backend)
     if args.bankdir is not None:
         return bank_main(args, backend)
     if args.confusion is not None:

@@ -20,7 +20,9 @@ the total and the mean per sample; returns the nll array.
 ``--bankdir DIR`` (a directory BankTrainer.save wrote: bank.json + model.<m>.ckpt.npz; PsiCMPS members, or RhoCMPS members where bank.json says
 rho_mps) does the same with every member of the bank at once (PsiBank.open_stream / RhoBank.open_stream; cmps_bank_stream* /
 cmps_rho_bank_stream*), every member hearing the same noise: sampling writes
-``sample_m<m>_<i>.wav`` and ``samples.npy`` [M, num_samples, samples]; --prime continues one clip with every member; --score writes
+``sample_m<m>_<i>.wav`` and ``samples.npy`` [M, num_samples, samples]; --prime continues one clip with every member; --score --posterior
+judges the members as a classifier after every sample of the clip (``posterior.npy`` [M, steps], ``best.npy``, ``conf.npy``; --prior,
+--temperature, --threshold); --score writes
 ``nll.npy`` ([M, T' - 1] for one clip, else [M, clips, T' - 1]) and ``pred.npy`` and prints one line per member and the best member.
 Run:  python -m audio_mps_amd.sample --modeldir=LOGDIR --sample_duration=16000 --prime=clip.wav
 """
@@ -100,6 +102,13 @@ def build_parser():
     p.add_argument("--segment", type=int, default=None, metavar="S", help="run through a resumable stream in segments of S steps")
     p.add_argument("--bankdir", default=None, metavar="DIR", help="a directory BankTrainer.save wrote (bank.json + model.<m>.ckpt.npz): sample, "
                    "continue or score with every member of a PsiCMPS or RhoCMPS bank at once, instead of --modeldir")
+    p.add_argument("--posterior", action="store_true", help="with --bankdir --score: judge the members as a classifier after every sample "
+                   "(cmps_bank_posterior); writes posterior.npy, best.npy and conf.npy instead of nll.npy and pred.npy")
+    p.add_argument("--prior", default=None, metavar="P0,P1,...|empirical", help="with --posterior: the members' prior probabilities, or "
+                   "'empirical': the class counts bank.json holds (default: uniform)")
+    p.add_argument("--temperature", type=float, default=1.0, help="with --posterior: the members' total losses are divided by it")
+    p.add_argument("--threshold", type=float, default=None, metavar="P", help="with --posterior: report the first sample at which the best "
+                   "member's probability reached P")
     p.add_argument("--out_dir", default="./samples")
     p.add_argument("--kernel_variant", type=int, default=0, help="as in audio_mps_amd.train")
     return p
@@ -199,12 +208,55 @@ def load_bank(bankdir: str, sample_rate: int, hparams: str = "", kernel_variant:
     if rho and not (hasattr(backend, "rho_bank_stream") or hasattr(backend, "rho_stream")):
         raise ValueError(f"{path} holds a bank of {name} models: {type(backend).__name__} has neither rho_bank_stream nor rho_stream")
     bank = (RhoBank if rho else PsiBank)(hp, meta["members"], backend=backend, classes=meta.get("classes"), label_key=meta.get("label_key"))
+    bank.class_counts = meta.get("class_counts")                  # clips per class of the training set, where the trainer recorded them
     for m, (model, var) in enumerate(zip(bank.models, variables)):
         for k in model.variables:
             if var[k].shape != model.variables[k].shape:
                 raise ValueError(f"member {m}: checkpoint variable {k} has shape {var[k].shape}, bond_dim={hp.bond_dim} needs {model.variables[k].shape}")
             model.variables[k] = var[k]
     return bank
+
+
+def parse_prior(spec, bank, where: str = ""):
+    """--prior: None (uniform), "empirical" (the class counts the bank's bank.json holds) or "p0,p1,..." -> [M] floats or None."""
+    if spec is None:
+        return None
+    if spec == "empirical":
+        counts = getattr(bank, "class_counts", None)
+        if counts is None:
+            raise ValueError(f"--prior empirical: {where or 'the bank'} holds no class counts (bank.json of a bank trained with --bank_by)")
+        return [float(c) for c in counts]
+    prior = [float(x) for x in spec.split(",")]
+    if len(prior) != len(bank):
+        raise ValueError(f"--prior names {len(prior)} probabilities, the bank has {len(bank)} members")
+    return prior
+
+
+def _bank_posterior(bank, args, clip):
+    """--bankdir --score --posterior: the clip followed by every member and judged after every sample (BankStream.score_posterior)."""
+    M, n, N = len(bank), clip.shape[0], clip.shape[1] - 1
+    tr = bank.posterior_trace(clip, prior=parse_prior(args.prior, bank, args.bankdir), temperature=args.temperature, threshold=args.threshold,
+                              segment=args.segment, want_post=True)
+    one = (lambda x, lead: x[:, 0] if lead else x[0]) if n == 1 else (lambda x, lead: x)
+    post = np.ascontiguousarray(one(tr.post, True), dtype=np.float32)
+    np.save(os.path.join(args.out_dir, "posterior.npy"), post)
+    np.save(os.path.join(args.out_dir, "best.npy"), np.ascontiguousarray(one(tr.best, False)))
+    np.save(os.path.join(args.out_dir, "conf.npy"), np.ascontiguousarray(one(tr.conf, False)))
+    named = (lambda m: f" (class {bank.classes[m]!r})") if bank.classes is not None else (lambda m: "")
+    for m in range(M):
+        print(f"member {m}{named(m)}: final posterior " + " ".join(f"{tr.post[m, i, -1]:.6g}" for i in range(n)))
+    for i in range(n):
+        b = int(tr.best[i, -1])
+        head = f"clip {i}: final best " + (f"member {b}{named(b)}, probability {tr.conf[i, -1]:.6g}" if b >= 0 else "nobody (no finite loss)")
+        if args.threshold is None:
+            print(head)
+        elif tr.decided_at[i] < 0:
+            print(f"{head}; undecided (never reached {args.threshold:g})")
+        else:
+            a = int(tr.decided_as[i])
+            print(f"{head}; decided at sample {int(tr.decided_at[i])} as member {a}{named(a)}")
+    print(f"judged {n} clip(s) of {N} steps under {M} members; wrote posterior.npy, best.npy and conf.npy to {args.out_dir}")
+    return post
 
 
 def _bank_main(args, backend):
@@ -217,6 +269,8 @@ def _bank_main(args, backend):
         clip = clip[None, :] if clip.ndim == 1 else clip
         if clip.ndim != 2 or clip.shape[1] < 2:
             raise ValueError(f"--score {args.score}: need [T'] or [n, T'] with two samples at least (one increment), not {clip.shape}")
+        if args.posterior:
+            return _bank_posterior(bank, args, clip)
         n, N = clip.shape[0], clip.shape[1] - 1
         S = N if args.segment is None else args.segment
         st = bank.open_stream(n, N)
@@ -264,6 +318,10 @@ def main(argv=None, backend=None):
     args = build_parser().parse_args(argv)
     if args.sample_duration < 1 or args.num_samples < 1:
         raise ValueError("--sample_duration and --num_samples must be positive")
+    if args.posterior and (args.bankdir is None or args.score is None):
+        raise ValueError("--posterior judges the members of a bank along a clip: it needs --bankdir and --score")
+    if not args.posterior and (args.prior is not None or args.threshold is not None or args.temperature != 1.0):
+        raise ValueError("--prior, --temperature and --threshold belong to --posterior")
     if args.bankdir is not None:
         if any(a == "--modeldir" or a.startswith("--modeldir=") for a in (sys.argv[1:] if argv is None else argv)):
             raise ValueError("--bankdir and --modeldir do not go together: a bank's members are read from --bankdir")

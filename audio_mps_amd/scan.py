@@ -146,7 +146,7 @@ class HipScan:
         return mode if mode in (_capi.CMPS_RANK1_EXACT_F32, _capi.CMPS_RANK1_BF16X2, _capi.CMPS_RANK1_F16X2) else _capi.CMPS_RANK1_BF16X3
 
     def kernel_events(self, on: bool):
-        """cmps_set_option(CMPS_OPT_KERNEL_EVENTS): bracket every kernel of forward() / backward() and of sample() / sample_primed() / stream() / stream_score() / rho_sample_primed() / rho_stream() / rho_stream_score() / draw_noise() / gather_batch() / loss_stats() / classify_stats() / classify_weights() / damped_sine() with HIP
+        """cmps_set_option(CMPS_OPT_KERNEL_EVENTS): bracket every kernel of forward() / backward() and of sample() / sample_primed() / stream() / stream_score() / rho_sample_primed() / rho_stream() / rho_stream_score() / draw_noise() / gather_batch() / loss_stats() / classify_stats() / classify_weights() / bank_posterior() / damped_sine() with HIP
         events (a measurement aid, used by bench.py outside its timed region)."""
         _capi.check(self._h, self._lib.cmps_set_option(self._h, _capi.CMPS_OPT_KERNEL_EVENTS, 1 if on else 0))
 
@@ -691,6 +691,55 @@ class HipScan:
         rec = record.cpu().numpy().view(dt)[0]
         return {k: (float(rec[k]) if dt[k].kind == "f" else int(rec[k])) for k in dt.names}
 
+    def log_prior_tensor(self, log_prior) -> Optional[torch.Tensor]:
+        """A log prior [M] (finite or -inf) as `bank_posterior` takes it: float64 on this device.  None stays None (a uniform prior)."""
+        if log_prior is None or isinstance(log_prior, torch.Tensor):
+            return log_prior
+        return torch.from_numpy(np.array(log_prior, dtype=np.float64, order="C")).to(self.device)
+
+    def bank_posterior(self, nll: torch.Tensor, total_in: Optional[torch.Tensor] = None, log_prior: Optional[torch.Tensor] = None,
+                       inv_temp: float = 1.0, threshold: Optional[float] = None, first_step: int = 0,
+                       decision: Optional[torch.Tensor] = None, want_post: bool = False) -> dict:
+        """cmps_bank_posterior: the per-step losses ``nll`` [M, n, steps] of a scored bank stream (float32, contiguous, on this device)
+        folded into the running totals and, after every step, the posterior over the members.  ``total_in`` [M, n] float32 or None (zeros),
+        ``log_prior`` [M] float64 or None (uniform).  With a ``threshold`` the first step at which the best member's probability reached
+        it is kept per path in ``decision`` (a uint8 tensor of 16 n bytes, _capi.DECISION_REC; None: a fresh one), numbered from
+        ``first_step``.  Returns {"total": [M, n], "best": int32 [n, steps], "conf": [n, steps], "post": [M, n, steps] with want_post else
+        None, "decision": the records (new memory, continued from ``decision``) or None}, all on the device; "pack" is the one uint8
+        tensor the small results are views of, in the order and sizes of "pack_sizes" (records, total, best, conf).  No host copy, no
+        synchronisation."""
+        def on_dev(t, dtype, shape):
+            return isinstance(t, torch.Tensor) and t.is_cuda and t.device == self.device and t.dtype == dtype and t.is_contiguous() \
+                and tuple(t.shape) == shape
+
+        if not (isinstance(nll, torch.Tensor) and nll.dim() == 3 and on_dev(nll, torch.float32, tuple(nll.shape)) and nll.numel() >= 1):
+            raise ValueError("bank_posterior: nll must be a contiguous float32 tensor [M, n, steps] with M, n, steps >= 1 on the backend's device")
+        M, n, steps = (int(x) for x in nll.shape)
+        if M > _capi.CLASSIFY_MAX_M:
+            raise ValueError(f"bank_posterior: a bank holds 1 .. {_capi.CLASSIFY_MAX_M} members, not {M}")
+        if total_in is not None and not on_dev(total_in, torch.float32, (M, n)):
+            raise ValueError(f"bank_posterior: total_in must be a contiguous float32 tensor [{M}, {n}] on the backend's device")
+        if log_prior is not None and not on_dev(log_prior, torch.float64, (M,)):
+            raise ValueError(f"bank_posterior: log_prior must be a contiguous float64 tensor [{M}] on the backend's device")
+        if threshold is None and decision is not None:
+            raise ValueError("bank_posterior: decision records need a threshold")
+        if decision is not None and not on_dev(decision, torch.uint8, (16 * n,)):
+            raise ValueError(f"bank_posterior: decision must be a contiguous uint8 tensor of {16 * n} bytes on the backend's device")
+        # one allocation for everything small, so that a caller who wants it on the host downloads once: records | total | best | conf
+        sizes = (16 * n if threshold is not None else 0, 4 * M * n, 4 * n * steps, 4 * n * steps)
+        pack = torch.empty(sum(sizes), dtype=torch.uint8, device=self.device)
+        rec, b_total, b_best, b_conf = torch.split(pack, sizes)
+        total, best, conf = b_total.view(torch.float32).view(M, n), b_best.view(torch.int32).view(n, steps), b_conf.view(torch.float32).view(n, steps)
+        if threshold is None:
+            rec = None
+        elif decision is not None:
+            rec.copy_(decision)                                        # continued where the caller's records are, in the new allocation
+        post = torch.empty((M, n, steps), dtype=torch.float32, device=self.device) if want_post else None
+        _capi.check(self._h, self._lib.cmps_bank_posterior(
+            self._h, _ptr(nll), M, n, steps, _ptr(total_in), _ptr(log_prior), float(inv_temp), _ptr(total), _ptr(post), _ptr(best), _ptr(conf),
+            0.0 if threshold is None else float(threshold), int(first_step), int(decision is None), _ptr(rec), self._stream()))
+        return {"total": total, "best": best, "conf": conf, "post": post, "decision": rec, "pack": pack, "pack_sizes": sizes}
+
     def damped_sine(self, seed: int, first_clip: int, B: int, T: int, delta_t: float) -> torch.Tensor:
         """cmps_damped_sine_fill: clips first_clip .. first_clip + B - 1 of the seed's synthetic damped-sine sequence (include/cmps.h),
         float32 [B, T], generated on the device.  No host copy, no synchronisation."""
@@ -805,6 +854,10 @@ class HipScan:
         """The running loss of a scored stream on the device: zeros for None, else the host array of `shape`."""
         if loss is None:
             return torch.zeros(shape, dtype=torch.float32, device=self.device)
+        if isinstance(loss, torch.Tensor):                             # (already there: the entry updates it in place)
+            if not (loss.device == self.device and loss.dtype == torch.float32 and loss.is_contiguous() and tuple(loss.shape) == shape):
+                raise ValueError(f"loss must be {list(shape)}")
+            return loss
         loss = np.array(loss, dtype=np.float32, order="C")
         if loss.shape != shape:
             raise ValueError(f"loss must be {list(shape)}")
@@ -854,13 +907,18 @@ class HipScan:
         """One scored segment behind its checks, for the paths of one model (`lead` = ()) or of every member of a bank ((M,)): the running
         loss up, (nll lead + [n, forced] or None, loss lead + [n], pred lead + [n, forced] or None) down.  `fn` is
         cmps_{psi,rho,bank}_stream_score, `block` what `_audio_block` returned, `flags` what `fn` takes behind pred_dev."""
+        d_nll, d_loss, d_pred = self._score_device(fn, state_in, state_out, k0, block, want_nll, want_pred, n, loss, lead, *flags)
+        return (d_nll.cpu().numpy() if want_nll else None), d_loss.cpu().numpy(), (d_pred.cpu().numpy() if want_pred else None)
+
+    def _score_device(self, fn, state_in, state_out, k0, block, want_nll, want_pred, n, loss, lead, *flags):
+        """`_score_launch` up to the downloads: (nll or None, the running loss behind the segment, pred or None) on the device."""
         d_audio, n_audio, forced = block
         d_loss = self._running_loss(loss, lead + (n,))
         d_nll = torch.empty(lead + (n, forced), dtype=torch.float32, device=self.device) if want_nll else None
         d_pred = torch.empty(lead + (n, forced), dtype=torch.float32, device=self.device) if want_pred else None
         _capi.check(self._h, fn(self._h, _ptr(state_in), _ptr(state_out), int(k0), _ptr(d_audio), n_audio, forced, n, _ptr(d_nll), _ptr(d_loss),
                                 _ptr(d_pred), *flags, self._stream()))
-        return (d_nll.cpu().numpy() if want_nll else None), d_loss.cpu().numpy(), (d_pred.cpu().numpy() if want_pred else None)
+        return d_nll, d_loss, d_pred
 
     def _stream_score_call(self, fn, bytes_fn, state_in, state_out, k0, audio, want_nll, want_pred, n, loss, *flags):
         """One scored segment of one model: the signal block [n_audio, forced + 1] and the running loss up, (nll [n, forced] or None, loss
@@ -940,6 +998,48 @@ class HipScan:
         self._stream_paths(bytes_fn, state_in, state_out, n, n)
         block = self._audio_block(audio, 2, (1, n, M * n), f" with n_audio in (1, {n}, {M * n}) and forced >= 1")
         return self._score_launch(fn, state_in, state_out, k0, block, want_nll, want_pred, n, loss, (M,))
+
+    def _bank_stream_posterior(self, kind: str, state_in, state_out, k0, audio, n, loss, log_prior, inv_temp, threshold, decision, want_post,
+                               want_nll, want_pred):
+        """The scored segment of `_bank_stream_score` with nll kept on the device, then `bank_posterior` on it."""
+        bytes_fn, _, fn = self._bank_stream_entries(kind)
+        M, n = self._bank_of(kind, kind + "_stream_posterior").M, int(n)
+        self._stream_paths(bytes_fn, state_in, state_out, n, n)
+        block = self._audio_block(audio, 2, (1, n, M * n), f" with n_audio in (1, {n}, {M * n}) and forced >= 1")
+        d_before = self._running_loss(loss, (M, n))
+        d_nll, d_loss, d_pred = self._score_device(fn, state_in, state_out, k0, block, True, bool(want_pred), n, d_before.clone(), (M,))
+        res = self.bank_posterior(d_nll, d_before, self.log_prior_tensor(log_prior), inv_temp, threshold, int(k0), decision, want_post)
+        pred = None
+        if want_pred == "lazy":
+            pred = lambda: d_pred.cpu().numpy()                                        # noqa: E731
+        elif want_pred:
+            pred = d_pred.cpu().numpy()
+        forced = block[2]
+        h_rec, h_total, h_best, h_conf = np.split(res["pack"].cpu().numpy(), np.cumsum(res["pack_sizes"])[:-1])       # ONE download
+        return {"best": h_best.view(np.int32).reshape(n, forced), "conf": h_conf.view(np.float32).reshape(n, forced),
+                "loss": h_total.view(np.float32).reshape(M, n), "decision": h_rec.view(_capi.DECISION_REC) if h_rec.size else None,
+                "carry": res["decision"], "post": res["post"].cpu().numpy() if want_post else None,
+                "nll": d_nll.cpu().numpy() if want_nll else None, "pred": pred}
+
+    def bank_stream_posterior(self, state_in: Optional[torch.Tensor], state_out: Optional[torch.Tensor], k0: int, audio,
+                              n: Optional[int] = None, loss=None, log_prior=None, inv_temp: float = 1.0, threshold: Optional[float] = None,
+                              decision: Optional[torch.Tensor] = None, want_post: bool = False, want_nll: bool = False, want_pred=False) -> dict:
+        """cmps_bank_stream_score, then cmps_bank_posterior on its nll where it lies: `bank_stream_score`'s segment judged as a classifier
+        after every step.  ``loss`` [M, n] is the running loss to continue, ``log_prior`` [M] (host values or `log_prior_tensor`'s) or None,
+        ``decision`` the "carry" of the previous segment's result or None (fresh records).  Only what is asked for comes down: {"best"
+        int32 [n, forced], "conf" [n, forced], "loss" [M, n] behind the segment, "decision" (_capi.DECISION_REC [n], steps numbered
+        from k0) or None without a threshold, "carry" (the records on the device), "post" / "nll" [M, n, forced] and "pred" on request,
+        else None; want_pred="lazy": a function that downloads it}."""
+        return self._bank_stream_posterior("bank", state_in, state_out, k0, audio, n, loss, log_prior, inv_temp, threshold, decision, want_post,
+                                           want_nll, want_pred)
+
+    def rho_bank_stream_posterior(self, state_in: Optional[torch.Tensor], state_out: Optional[torch.Tensor], k0: int, audio,
+                                  n: Optional[int] = None, loss=None, log_prior=None, inv_temp: float = 1.0,
+                                  threshold: Optional[float] = None, decision: Optional[torch.Tensor] = None, want_post: bool = False,
+                                  want_nll: bool = False, want_pred=False) -> dict:
+        """`bank_stream_posterior` for a RhoCMPS bank (cmps_rho_bank_stream_score, then cmps_bank_posterior)."""
+        return self._bank_stream_posterior("rho_bank", state_in, state_out, k0, audio, n, loss, log_prior, inv_temp, threshold, decision,
+                                           want_post, want_nll, want_pred)
 
     def bank_stream_state(self, n: int) -> torch.Tensor:
         """Device memory for the stream-state records of ``n`` paths of every member (cmps_bank_stream_state_bytes)."""

@@ -18,11 +18,14 @@ A RhoCMPS stream opened with ``keep_states=S`` also returns rho and the purity a
 
 A ``BankStream`` (``PsiBank.open_stream`` / ``RhoBank.open_stream``; cmps_bank_stream, cmps_bank_stream_score, cmps_rho_bank_stream,
 cmps_rho_bank_stream_score) is the same stream for every member of a bank at once: results [M, num_paths, steps], ``total_nll``
-[M, num_paths], ``ranking()`` and ``best()`` -- M models along one signal.
+[M, num_paths], ``ranking()`` and ``best()`` -- M models along one signal.  ``score_posterior`` (cmps_bank_posterior) is ``score`` judged as a
+classifier after every sample: the most probable member and its probability per step, and the step at which the bank was first sure.
 """
 from __future__ import annotations
 
 import math
+from dataclasses import dataclass
+from typing import Optional
 
 import numpy as np
 
@@ -318,6 +321,39 @@ class _BankScan:
                              "(cmps_rho_stream_score)")       # (as RhoCMPS._stream_score_entry: said before anything runs)
         return getattr(be, self._pre + "stream_score")
 
+    def _stream_posterior_entry(self, be):
+        name = self._pre + "stream_posterior"
+        if not hasattr(be, name):
+            inner = be.backends[0] if isinstance(be, _MemberLoop) else be
+            raise ValueError(f"score_posterior needs a backend that folds the members' losses on the device: {type(inner).__name__} has no "
+                             f"{name} (cmps_bank_posterior)")
+        return getattr(be, name)
+
+
+@dataclass
+class PosteriorTrace:
+    """What ``BankStream.score_posterior`` and ``PsiBank.posterior_trace`` return: per path and scored step the most probable member
+    ``best`` [n, steps] (int32, -1 where no member has a finite total) and its posterior probability ``conf`` [n, steps]; on request the
+    whole posterior ``post`` [M, n, steps] and the members' ``nll`` [M, n, steps]; ``decided_at`` / ``decided_as`` [n]: the stream position
+    of the first step at which ``conf`` reached the threshold and the member it was then, -1 while undecided (or without a threshold)."""
+    best: np.ndarray
+    conf: np.ndarray
+    post: Optional[np.ndarray] = None
+    nll: Optional[np.ndarray] = None
+    decided_at: Optional[np.ndarray] = None
+    decided_as: Optional[np.ndarray] = None
+
+
+def log_prior_of(prior, M: int):
+    """``prior`` [M] probabilities (any positive scale; a zero: that member never wins) -> their normalised log, float64; None stays None."""
+    if prior is None:
+        return None
+    p = np.asarray(prior, dtype=np.float64)
+    if p.shape != (M,) or not np.all(np.isfinite(p)) or np.any(p < 0) or not p.sum() > 0:
+        raise ValueError(f"prior must be [{M}] finite probabilities, none negative and not all zero")
+    with np.errstate(divide="ignore"):
+        return np.log(p / p.sum())
+
 
 class BankStream(SampleStream):
     """Returned by ``PsiBank.open_stream`` / ``RhoBank.open_stream`` / ``BankTrainer.open_stream``: a SampleStream of every member at once
@@ -327,10 +363,24 @@ class BankStream(SampleStream):
     differs between two members' samples is the model and not the draw; ``independent_noise=True`` numbers the paths globally instead
     (g = m num_paths + b).  On a backend without the bank entries the stream loops over plain streams of its members."""
 
-    def __init__(self, bank, num_paths: int, max_steps: int, temp=1, seed=None, device_noise: bool = False, independent_noise: bool = False):
+    def __init__(self, bank, num_paths: int, max_steps: int, temp=1, seed=None, device_noise: bool = False, independent_noise: bool = False,
+                 prior=None, temperature: float = 1.0, threshold: Optional[float] = None):
         self.independent_noise = bool(independent_noise)
+        log_prior = log_prior_of(prior, len(bank))
+        if not (math.isfinite(temperature) and temperature > 0):
+            raise ValueError("open_stream: temperature must be finite and positive")
+        if threshold is not None and not 0.0 < float(threshold) <= 1.0:
+            raise ValueError("open_stream: threshold must lie in (0, 1]")
+        self._pred = None              # last_pred: the host array, or what downloads it when somebody asks
         super().__init__(_BankScan(bank), num_paths, max_steps, temp=temp, seed=seed, device_noise=device_noise)
         self.native = not isinstance(self._be, _MemberLoop)
+        self.temperature, self.threshold = float(temperature), None if threshold is None else float(threshold)
+        self.log_prior = log_prior     # [M] float64 or None (uniform): what score_posterior weighs the members with
+        up = getattr(self._be, "log_prior_tensor", None)
+        self._log_prior_be = up(log_prior) if up is not None else log_prior          # (goes up once)
+        self._decision = None          # the backend's decision records, carried from one score_posterior call to the next
+        self.decided_at = np.full(self.num_paths, -1, dtype=np.int64)                 # the position of the first sure step per path
+        self.decided_as = np.full(self.num_paths, -1, dtype=np.int32)                 # ... and the member it was sure of
 
     def __len__(self) -> int:
         return self._shape[0]
@@ -369,6 +419,49 @@ class BankStream(SampleStream):
 
     def _plan_kw(self) -> dict:
         return {"n_noise": self._noise_paths()}
+
+    @property
+    def last_pred(self):
+        """The predictions of the last score / score_posterior call (score_posterior: downloaded when first read)."""
+        if callable(self._pred):
+            self._pred = self._pred()
+        return self._pred
+
+    @last_pred.setter
+    def last_pred(self, value):
+        self._pred = value
+
+    def score_posterior(self, block, anchor: bool = False, want_post: bool = False, want_nll: bool = False) -> PosteriorTrace:
+        """``score`` judged as a classifier after every sample (cmps_bank_stream_score / cmps_rho_bank_stream_score, then
+        cmps_bank_posterior on the losses where they lie): same arguments, anchoring rule and bookkeeping -- state, ``position``,
+        ``last``, ``last_pred`` and ``total_nll`` end up as ``score`` leaves them, bit for bit -- but what comes back is a PosteriorTrace:
+        per path and step the member that is the most probable given everything scored so far, and its probability, under the stream's
+        ``prior`` and ``temperature`` (p_m proportional to prior_m exp(-total_nll_m / temperature)).  A stream opened with a ``threshold``
+        also keeps, across calls, the position of the first step at which that probability reached it (``decided_at`` [num_paths], -1
+        while undecided) and the member it was (``decided_as``).  The members' per-step losses stay on the device unless ``want_nll``."""
+        entry = self._model._stream_posterior_entry(self._be)
+        block, audio = self._anchored(block, anchor)
+        steps = audio.shape[-1] - 1
+        M, n = self._shape
+        trace = PosteriorTrace(np.empty((n, 0), np.int32), np.empty((n, 0), np.float32),
+                               np.empty((M, n, 0), np.float32) if want_post else None, np.empty((M, n, 0), np.float32) if want_nll else None)
+        pred = np.empty(self._shape + (0,), dtype=np.float32)
+        if steps:
+            res = self._launch(steps, entry, self._rows(audio), loss=self.total_nll, log_prior=self._log_prior_be,
+                               inv_temp=1.0 / self.temperature, threshold=self.threshold, decision=self._decision, want_post=want_post,
+                               want_nll=want_nll, want_pred="lazy")
+            self.total_nll = np.asarray(res["loss"], dtype=np.float32)
+            pred = res["pred"]
+            if self.threshold is not None:
+                self._decision = res["carry"]
+                self.decided_at = np.array(res["decision"]["step"], dtype=np.int64)
+                self.decided_as = np.array(res["decision"]["member"], dtype=np.int32)
+            trace = PosteriorTrace(res["best"], res["conf"], res["post"], res["nll"])
+        self.last_pred = pred
+        self.last = np.array(np.broadcast_to(block[..., -1], self._shape), dtype=np.float32)
+        self._level = None
+        trace.decided_at, trace.decided_as = self.decided_at.copy(), self.decided_as.copy()
+        return trace
 
     def ranking(self) -> np.ndarray:
         """Per path, the members ordered by ``total_nll``, the most likely first: [M, num_paths] (a stable sort; NaN last)."""

@@ -509,6 +509,8 @@ def class_bank_main(args, hp, backend, dp):
     classes = parse_classes(args.bank_classes, data.labels) if args.bank_classes is not None else sorted(set(data.labels.tolist()))
     bank = (RhoBank if rho else PsiBank)(hp, [{"seed": args.seed + m} for m in range(len(classes))], backend=backend, classes=classes,
                                          label_key=args.bank_by)
+    at = data.class_positions(classes)
+    bank.class_counts = np.bincount(at[at >= 0], minlength=len(classes)).tolist()   # bank.json keeps them: sample / evaluate --prior empirical
     trainer = BankTrainer(bank, dp)
     logdir = f"{args.logdir}/{args.dataset}/{hp.bond_dim}_{hp.delta_t}_{hp.minibatch_size}"    # train.py:94
     if trainer.restore(logdir):

@@ -94,7 +94,7 @@ enum {
     CMPS_OPT_F16_SCALE_SHIFT = 4 /* DIAGNOSTIC, default 0: added to the exponent of every data-dependent fp16 scale of the wave reverse
                         * scan's F16X2 arithmetic (range -40 .. 40).  A positive value pushes the pieces out of fp16 range on purpose:
                         * how tests/test_gpu_parity.py provokes CMPS_ERR_F16_RANGE.  No reference counterpart. */,
-    CMPS_OPT_KERNEL_EVENTS = 2 /* 1: every kernel cmps_psi_loss_fwd / _bwd, cmps_rho_loss_fwd / _bwd, cmps_psi_sample, cmps_psi_sample_primed, cmps_psi_stream, cmps_psi_stream_score, cmps_rho_sample_primed, cmps_rho_stream, cmps_rho_stream_score, cmps_noise_fill (as k_noise_philox), cmps_batch_gather (as k_batch_gather), cmps_batch_gather_i16 (as k_batch_gather_i16), cmps_loss_stats (as k_loss_stats), cmps_bank_classify_stats (as k_classify_stats), cmps_bank_classify_weights (as k_classify_weights), cmps_bank_loss_bwd_weighted (the scan of cmps_bank_loss_bwd, then "reduce + finalize (weighted)") and cmps_damped_sine_fill (as k_damped_sine) launch is bracketed by two HIP events on the caller's stream
+    CMPS_OPT_KERNEL_EVENTS = 2 /* 1: every kernel cmps_psi_loss_fwd / _bwd, cmps_rho_loss_fwd / _bwd, cmps_psi_sample, cmps_psi_sample_primed, cmps_psi_stream, cmps_psi_stream_score, cmps_rho_sample_primed, cmps_rho_stream, cmps_rho_stream_score, cmps_noise_fill (as k_noise_philox), cmps_batch_gather (as k_batch_gather), cmps_batch_gather_i16 (as k_batch_gather_i16), cmps_loss_stats (as k_loss_stats), cmps_bank_classify_stats (as k_classify_stats), cmps_bank_classify_weights (as k_classify_weights), cmps_bank_posterior (as k_bank_posterior), cmps_bank_loss_bwd_weighted (the scan of cmps_bank_loss_bwd, then "reduce + finalize (weighted)") and cmps_damped_sine_fill (as k_damped_sine) launch is bracketed by two HIP events on the caller's stream
                         * (read and reset with cmps_kernel_times); 0 (default): nothing is recorded.  A measurement aid -- the reference
                         * has no counterpart (no tracing / profiling hooks); bench.py uses it OUTSIDE its timed region to price
                         * each kernel of a multi-kernel family against the pipe it runs on */
@@ -984,6 +984,71 @@ typedef struct cmps_bank_classify_weights_rec {
 int cmps_bank_classify_weights(cmps_handle_t h, const float* loss_dev, int M, int B, long long ld, const int* label_dev, double inv_temp,
                                double gen_weight, double disc_weight, int reset, float* weight_dev, long long ldw, void* record_dev,
                                void* stream);
+
+/*
+ * A bank followed along a signal judged as a classifier AFTER EVERY SAMPLE, on the device: nll_dev [M][n][steps], contiguous, is what
+ * cmps_bank_stream_score / cmps_rho_bank_stream_score wrote for one segment -- the loss increment of step k of path g under member m at
+ * nll_dev[(m * n + g) * steps + k] -- and this entry folds it into the running totals and, per path and step, the posterior over the
+ * members, the most probable member, its probability, and the first step at which that probability reached a threshold.
+ * Replaces: nothing -- the reference scores one model along one clip (model.py:279, 293-294) and never weighs models against each other.
+ *   total_in_dev  [M][n] the running totals before the segment, or NULL: every total starts at 0.f (a stream at k0 == 0)
+ *   log_prior_dev [M] doubles, 8-byte aligned, or NULL: a uniform prior (log prior 0 for every member).  An entry is finite or -inf; it need
+ *                 not be normalised (a common shift changes nothing).  NaN and +inf entries give unspecified values, within the extents.
+ *   inv_temp      kappa > 0
+ *   total_out_dev [M][n], post_dev [M][n][steps], best_dev [n][steps] int, conf_dev [n][steps]: each may be NULL and is then not written;
+ *                 total_out_dev may equal total_in_dev
+ *   decision_dev  [n] records cmps_bank_decision (16 bytes each, 8-byte aligned), or NULL; threshold, first_step and reset are read only
+ *                 with a record
+ * THE DEFINITION (normative; tests/_posterior_ref.py restates it in numpy).  Per member m and path g:
+ *   c_m(-1) = total_in[m][g] (or 0.f);  c_m(k) = c_m(k - 1) + nll[m][g][k]: ONE float32 addition per step, in step order -- the fold
+ *   every score kernel performs on its running loss.  total_out[m][g] = c_m(steps - 1) is therefore, bit for bit, the loss_dev the score
+ *   call of the same segment wrote, and cutting a run into calls (total_out of one as total_in of the next) changes no bit of anything.
+ *   Member m is ABSENT at step k of path g when c_m(k) is NaN or +-Inf; the total being a running sum, it stays absent from there on.
+ * Per (g, k), over the present members, in double:
+ *   a_m  = kappa (double)c_m(k) - log_prior[m]
+ *   amin = the smallest a_m
+ *   S    = sum over the present m of exp(-(a_m - amin))                                          1 <= S <= M
+ *   p_m  = exp(-(a_m - amin)) / S
+ *   post[m][g][k] = float32(p_m) for a present m, +0 for an absent one
+ *   best[g][k]    = the present m with the smallest a_m (a double compare; the lowest m on ties);  conf[g][k] = float32(1 / S) = p_best
+ *   No member present: best = -1, conf = +0, every post = +0.
+ *   A member with log prior -inf has a_m = +inf: it never wins and its p is 0; it is present only in the sense that its total is finite.
+ *   A step at which every present member has log prior -inf is a step with no member present.
+ * THE DECISION.  decision_dev[g] = {step, member, reserved} holds the FIRST step at which the bank was sure.  reset != 0 ignores what the
+ * record held and starts from {-1, -1, 0} (no memset is needed before the first call); reset == 0 continues it.  A record with step >= 0
+ * is left as it is.  Otherwise the first k of this call with 1 / S >= threshold -- compared in double, before the rounding to float32 --
+ * sets step = first_step + k and member = best[g][k]; later dips below the threshold change nothing.
+ * ROUNDING.  u = 2^-53, A' = max over the present m with a finite log prior of (kappa |c_m| + |log_prior_m|), exp of the device within 4 ulp = 8 u in double (as
+ * for cmps_bank_classify_stats).  a_m carries two roundings of numbers no larger than A' (one where the compiler fuses them), amin the
+ * same, and their difference d = a_m - amin >= 0 one more: |dd| <= u (4 A' + d).  e_m = exp(-d) <= 1 is then within
+ * u (e_m (8 + 4 A') + 0.37) of the exact one (d exp(-d) <= 1 / e), whatever shift stands in for amin -- the soft-max does not depend on
+ * it.  S, a sum of at most M such terms in any order with S >= 1, is within u S (1.37 M + 8 + 4 A') of exact; p_m = e_m / S <= 1 and
+ * 1 / S within u (1.37 M + 18 + 8 A').  The result is rounded to float32 once (a subnormal result to within 2^-150):
+ *   |post[m][g][k] - exact| <= 2^-24 |exact| + 2^-52 (M + 16 + 4 A') + 2^-149          and the same for conf[g][k]
+ * where "exact" is exact arithmetic on the float32 totals c_m(k), which every evaluation shares bit for bit.  Two evaluations that each
+ * meet this bound -- the device's and a float64 restatement -- differ by at most twice it.  best and the decision are exact compares of
+ * rounded doubles: two evaluations agree on them wherever the runner-up's a is not within that error of the best's and 1 / S not within
+ * it of the threshold.
+ * One workgroup per path, a fixed assignment of members and steps to threads, fixed merge orders, no atomics, and nll_dev is read once:
+ * the same call gives the same bits on every run.
+ * Needs no cmps_set_params: it works on a fresh handle of any D, in legacy mode and for either kind of bank.  Asynchronous on `stream`;
+ * never synchronises, allocates nothing, uses no global scratch, reads nll_dev[0 .. M n steps), total_in_dev[0 .. M n),
+ * log_prior_dev[0 .. M) and (reset == 0) decision_dev[0 .. n) only, and writes only the stated extents of the outputs that are not NULL.
+ * CMPS_ERR_BAD_ARG, each with a message that starts with the entry's name, the first failing check speaking, before the device is
+ * touched: a null handle; a null nll_dev; M outside [1, 1024]; n < 1; steps < 1; M n steps > 2^31 - 1; inv_temp not finite or <= 0;
+ * log_prior_dev not 8-byte aligned; decision_dev not 8-byte aligned; with a decision_dev: threshold not finite or outside (0, 1];
+ * first_step < 0 or first_step + steps > 2^63 - 1.
+ * With CMPS_OPT_KERNEL_EVENTS the launch is recorded as k_bank_posterior.
+ */
+typedef struct cmps_bank_decision {
+    long long step;      /* first_step + k of the first sure step; -1 while undecided */
+    int member;          /* best at that step; -1 while undecided */
+    int reserved;        /* 0 */
+} cmps_bank_decision;
+int cmps_bank_posterior(cmps_handle_t h, const float* nll_dev, int M, int n, int steps,
+                        const float* total_in_dev, const double* log_prior_dev, double inv_temp,
+                        float* total_out_dev, float* post_dev, int* best_dev, float* conf_dev,
+                        double threshold, long long first_step, int reset, void* decision_dev, void* stream);
 
 /*
  * The synthetic training batch, generated where it is used.  Replaces: the damped_sine branch of get_audio (data.py:8-22): a 261.6 Hz sine
