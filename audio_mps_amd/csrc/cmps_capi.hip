@@ -29,6 +29,12 @@ struct Saved {
     int M = 0, n_audio = 0;        // written by cmps_bank_loss_fwd (main) / cmps_rho_bank_loss_fwd (rho) for M members from n_audio batches (0: a plain forward)
 };
 
+// What a handle is configured for: nothing yet (or a setter failed half-way), one PsiCMPS model (cmps_set_params*; the RhoCMPS entries
+// after cmps_rho_set_state on top of it), the legacy AudioMPS arithmetic (cmps_legacy_set_params), a bank of PsiCMPS models
+// (cmps_bank_set_params_dev), or a bank of RhoCMPS models (cmps_rho_bank_set_state_dev: every member's region is the main layout, tables
+// only, followed by the rho layout; W is member 0's)
+enum Mode { MODE_NONE, MODE_PSI, MODE_LEGACY, MODE_PSI_BANK, MODE_RHO_BANK };
+
 struct cmps_handle_s {
     int D = 0;
     int variant_req = CMPS_VARIANT_AUTO;
@@ -37,11 +43,10 @@ struct cmps_handle_s {
     int f16_shift = 0;         // CMPS_OPT_F16_SCALE_SHIFT (diagnostic)
     int bwd_waves = 2;             // CMPS_OPT_BWD_WAVES
     bool rho_virtual_bwd = true;   // CMPS_OPT_RHO_BWD: the RhoCMPS GEMM forward's reverse sweep on virtual clips of k_bwd_wave (else k_bwd_rho_mfma)
-    bool params_set = false;
-    bool legacy = false;       // the tables currently hold the legacy AudioMPS arithmetic (cmps_legacy_set_params)
-    int bank_M = 0;            // > 0: the workspace holds the tables of a bank of bank_M members (cmps_bank_set_params_dev); 0: plain mode
-    bool bank_rho = false;     // with bank_M > 0: a bank of RhoCMPS models (cmps_rho_bank_set_state_dev) -- every member's region is the main layout
-                               // (tables only) followed by the rho layout, W is member 0's; rho_set stays false, so the plain rho entries refuse
+    // What the tables of the workspace hold, and so which entries may run.  Two invariants, kept by every setter (the four that install a
+    // mode, cmps_rho_set_state and unconfigure()):  bank_M > 0 exactly in the two bank modes;  rho_set only in MODE_PSI.
+    Mode mode = MODE_NONE;
+    int bank_M = 0;            // the members of the bank (cmps_bank_set_params_dev / cmps_rho_bank_set_state_dev)
     Saved main, rho;           // the stash of the main workspace (cmps_psi_* / cmps_legacy_* entries) and of the rho workspace
     Layout L{};
     Dev P{};                   // (stash_layout stays 0 here: main_dev() fills it from `main` for the kernels that read the stash)
@@ -201,12 +206,30 @@ RhoDev rho_dev(const cmps_handle_s* h) {
     return W;
 }
 
-// The argument checks of every *_loss_fwd entry (h non-null): `ready` is the entry's call-order condition, T_set / B_max / ws_flags what
-// `setter` was given.  CMPS_OK, or the code to return with the message set.
-int check_fwd(cmps_handle_t h, const char* who, bool ready, const char* setter, const void* audio, const void* loss, int B, int T,
+// The one call-order check: entry `who` runs in the modes of the set `accepted` (bits 1 << Mode), and only where `also` holds (what the
+// entry needs beside the mode: cmps_rho_set_state, a saved forward, a CMPS_WS_TRAIN workspace).  Otherwise the message is `who` and the
+// refusal (in up to three pieces, so that an accepted call builds no string).
+constexpr unsigned in(Mode m) { return 1u << m; }
+constexpr unsigned BANKS = in(MODE_PSI_BANK) | in(MODE_RHO_BANK);
+int need_mode(cmps_handle_t h, const char* who, unsigned accepted, bool also, const char* refusal, const char* r2 = "", const char* r3 = "") {
+    if ((accepted & in(h->mode)) && also) return CMPS_OK;
+    return fail(h, CMPS_ERR_STATE, std::string(who) + refusal + r2 + r3);
+}
+// What a setter leaves behind when a launch fails after it has begun to overwrite the tables
+void unconfigure(cmps_handle_t h) {
+    h->mode = MODE_NONE;
+    h->bank_M = 0;
+    h->rho_set = false;
+    h->main.valid = h->rho.valid = false;
+    h->tt_ws = nullptr;                  // (the time table may be half written)
+}
+
+// The argument checks of every *_loss_fwd entry (h non-null): `modes` and `also` are the entry's call-order condition (need_mode),
+// T_set / B_max / ws_flags what `setter` was given.  CMPS_OK, or the code to return with the message set.
+int check_fwd(cmps_handle_t h, const char* who, unsigned modes, bool also, const char* setter, const void* audio, const void* loss, int B, int T,
               int T_set, int B_max, int save, int ws_flags) {
     const std::string w(who);
-    if (!ready) return fail(h, CMPS_ERR_STATE, w + ": call " + setter + " first");
+    if (const int rc = need_mode(h, who, modes, also, ": call ", setter, " first")) return rc;
     if (!audio || !loss) return fail(h, CMPS_ERR_BAD_ARG, w + ": null pointer");
     if (T != T_set) return fail(h, CMPS_ERR_BAD_ARG, w + ": T differs from " + setter);
     if (B < 1 || B > B_max) return fail(h, CMPS_ERR_BAD_ARG, w + ": B outside [1, B_max] of " + setter);
@@ -214,9 +237,10 @@ int check_fwd(cmps_handle_t h, const char* who, bool ready, const char* setter, 
     return CMPS_OK;
 }
 // ... and of every *_loss_bwd entry, against the record S of the forward `fwd` it follows
-int check_bwd(cmps_handle_t h, const char* who, bool ready, const char* fwd, const Saved& S, const void* audio, const void* grad, int B, int T) {
+int check_bwd(cmps_handle_t h, const char* who, unsigned modes, bool also, const char* fwd, const Saved& S, const void* audio, const void* grad,
+              int B, int T) {
     const std::string w(who);
-    if (!ready || !S.valid) return fail(h, CMPS_ERR_STATE, w + ": needs " + fwd + "(save_for_bwd=1) first");
+    if (const int rc = need_mode(h, who, modes, also && S.valid, ": needs ", fwd, "(save_for_bwd=1) first")) return rc;
     if (!audio || !grad) return fail(h, CMPS_ERR_BAD_ARG, w + ": null pointer");
     if (B != S.B || T != S.steps + 1 || audio != S.audio) return fail(h, CMPS_ERR_STATE, w + ": audio / B / T differ from the forward call");
     return CMPS_OK;
@@ -240,8 +264,51 @@ void bank_strides(Dev& P, int n_audio, int B, int T, size_t grad = 0) {
 // What every plain entry outside a bank's scope (samplers, streams, state read-outs, ancilla updates, cmps_rho_set_state,
 // cmps_psi_grad_status) answers while the workspace holds a bank: its tables would be member 0's alone.  A member is taken out as a plain model.
 int check_not_bank(cmps_handle_t h, const char* who) {
-    if (!h->bank_M) return CMPS_OK;
-    return fail(h, CMPS_ERR_STATE, std::string(who) + ": the handle holds a bank (cmps_bank_set_params_dev / cmps_rho_bank_set_state_dev); call cmps_set_params for one model first");
+    return need_mode(h, who, ~BANKS, true, ": the handle holds a bank (cmps_bank_set_params_dev / cmps_rho_bank_set_state_dev); call cmps_set_params for one model first");
+}
+// ... and then its own call-order check
+int need_plain(cmps_handle_t h, const char* who, unsigned accepted, bool also, const char* refusal) {
+    if (const int rc = check_not_bank(h, who)) return rc;
+    return need_mode(h, who, accepted, also, refusal);
+}
+
+// The small argument checks of the entries that need nothing of the handle but its error string: chained, the first that fails speaks
+// (CMPS_ERR_BAD_ARG, in rc), the ones behind it do nothing; a passing check builds no string
+struct Args {
+    cmps_handle_t h;
+    const char* who;
+    int rc = CMPS_OK;
+    Args& need(bool ok, std::initializer_list<const char*> sentence) {
+        if (rc || ok) return *this;
+        std::string msg = std::string(who) + ": ";
+        for (const char* piece : sentence) msg += piece;
+        rc = fail(h, CMPS_ERR_BAD_ARG, msg);
+        return *this;
+    }
+    Args& need(bool ok, const char* sentence) { return need(ok, {sentence}); }
+    Args& ptr(const char* name, const void* p) { return need(p != nullptr, {name, " is a null pointer"}); }
+    Args& align8(const char* name, const void* p) { return need(((uintptr_t)p & 7) == 0, {name, " must be 8-byte aligned"}); }
+    Args& min1(const char* name, long long v) { return need(v >= 1, {"need ", name, " >= 1"}); }
+    Args& members(int M) { return need(M >= 1 && M <= CLASSIFY_MAX_M, "need 1 <= M <= 1024"); }
+    Args& ld(const char* name, long long ld, int B) { return need(ld >= (long long)B, {name, " must be at least B"}); }
+    Args& positive(const char* name, double v) { return need(std::isfinite(v) && v > 0.0, {name, " must be finite and positive"}); }
+    Args& not_negative(const char* name, double v) { return need(std::isfinite(v) && v >= 0.0, {name, " must be finite and not negative"}); }
+    // `count` consecutive ids or steps from `first` on stay below 2^63 (`a_thing`: "an id", "a step"; count >= 1 was checked before)
+    Args& range63(const char* first_name, long long first, const char* count_name, long long count, const char* a_thing) {
+        return need(rc || (first >= 0 && first <= 9223372036854775807ll - count),
+                    {"need ", first_name, " >= 0 and ", first_name, " + ", count_name, " below 2^63 (", a_thing, " is a signed 64-bit integer)"});
+    }
+};
+
+// The tail of an entry that is one launch: bind the handle's kernel-event record, time the launch under the name `kernel`, and turn a HIP
+// error into the entry's code and message (`where` names the entry)
+template <class Launch>
+int run_kernel(cmps_handle_t h, const char* where, const char* kernel, void* stream, Launch&& launch) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    KBind kb(h);
+    KScope ks(kernel, s);
+    const hipError_t e = launch(s);
+    return e == hipSuccess ? CMPS_OK : fail_hip(h, e, where);
 }
 
 // the end of a reverse pass whose slabs hold one PAIR of clips each (pair and wide kernels): reduce over (B + 1) / 2 slabs, closing terms
@@ -353,13 +420,13 @@ size_t cmps_workspace_bytes(int D, int B, int T, int flags) {
 static int set_params_impl(cmps_handle_t h, const float* R_re_dev, const float* R_im_dev,
                            const float* freqs_dev, const float* psi0_re_dev, const float* psi0_im_dev,
                            float A, const float* A_dev, double sigma, double delta_t, int T, int B_max, int flags,
-                           void* workspace_dev, size_t workspace_bytes, void* stream, int M = 0, size_t rho_bytes = 0) {
-    // the entry that speaks in the messages
-    const std::string w(rho_bytes ? "cmps_rho_bank_set_state_dev" : M > 0 ? "cmps_bank_set_params_dev" : "cmps_set_params");
-    // M > 0 (cmps_bank_set_params_dev, which has checked its own arguments): the parameter pointers are member 0's, member m's lie
-    // m (2 D^2 + 3 D + 1) floats behind them, and member m's workspace is the plain layout at byte m * L.total.
-    // rho_bytes > 0 (cmps_rho_bank_set_state_dev, with the flags of a tables-only main layout): every member's rho layout of that many
-    // bytes follows its main layout, and the stride is their sum.
+                           void* workspace_dev, size_t workspace_bytes, void* stream, Mode mode = MODE_PSI, int M = 0, size_t rho_bytes = 0) {
+    // `mode` is what the call installs; the entry of that mode speaks in the messages
+    const std::string w(mode == MODE_RHO_BANK ? "cmps_rho_bank_set_state_dev" : mode == MODE_PSI_BANK ? "cmps_bank_set_params_dev" : "cmps_set_params");
+    // MODE_PSI_BANK (cmps_bank_set_params_dev, which has checked its own arguments): M > 0, the parameter pointers are member 0's, member
+    // m's lie m (2 D^2 + 3 D + 1) floats behind them, and member m's workspace is the plain layout at byte m * L.total.
+    // MODE_RHO_BANK (cmps_rho_bank_set_state_dev, with the flags of a tables-only main layout): every member's rho layout of rho_bytes
+    // bytes follows its main layout, and the stride is their sum; the caller packs the columns and fills W.
     if (!h) return CMPS_ERR_BAD_ARG;
     if (!R_re_dev || !R_im_dev || !freqs_dev || !psi0_re_dev || !psi0_im_dev)
         return fail(h, CMPS_ERR_BAD_ARG, w + ": null parameter pointer");
@@ -390,31 +457,29 @@ static int set_params_impl(cmps_handle_t h, const float* R_re_dev, const float* 
     const float dt = (float)delta_t;  // model.py:16
     P.dt = dt;
     if (M > 0) { P.bank_stride = stride; P.bank_adev = n_par; }
-    // (a bank's members each have a time table: another member count, or a change between bank and plain mode, moves or adds tables)
-    const bool rebuild = fresh || h->bank_M != M || (M > 0 && h->P.bank_stride != stride) || !(h->tt_ws == ws && h->tt_N == L.N && h->tt_dt == dt);
+    // (a bank's members each have a time table: another member count or stride, or a change between bank and plain mode, moves or adds tables)
+    const bool regrouped = h->bank_M != M || h->P.bank_stride != P.bank_stride;
+    const bool rebuild = fresh || regrouped || !(h->tt_ws == ws && h->tt_N == L.N && h->tt_dt == dt);
     hipError_t e = launch_prep(P, R_re_dev, R_im_dev, freqs_dev, psi0_re_dev, psi0_im_dev, dt, rebuild,
                                const_cast<float*>(P.ttab), const_cast<float*>(P.dtk),
                                const_cast<float2*>(P.R), const_cast<float2*>(P.RT),
                                const_cast<float2*>(P.Q), const_cast<float2*>(P.psi0),
                                const_cast<float*>(P.freqs), const_cast<float2*>(P.rho),
                                reinterpret_cast<double2*>(ws + L.off_rfix), static_cast<hipStream_t>(stream), (int)members, M > 0 ? n_par : 0);
-    if (e != hipSuccess) return fail_hip(h, e, w.c_str());
+    if (e != hipSuccess) { unconfigure(h); return fail_hip(h, e, w.c_str()); }
     // a workspace this handle cannot vouch for, or flag words that moved: the layout puts them behind the stash and the slabs, so with
-    // CMPS_WS_REUSE_TABLES and another T, B_max or TRAIN flag (or after the legacy mode) their address holds something else -- the flag
+    // CMPS_WS_REUSE_TABLES and another T, B_max or TRAIN flag (or after another mode) their address holds something else -- the flag
     // words start at zero
-    if (P.status && (fresh || h->ws != ws || h->legacy || !h->params_set || h->P.status != P.status || h->bank_M != M ||
-                     h->P.bank_stride != P.bank_stride)) {
+    if (P.status && (fresh || h->ws != ws || h->mode != mode || regrouped || h->P.status != P.status)) {
         // (every member's pair of words, one workspace apart: one strided fill)
         e = M > 0 ? hipMemset2DAsync(P.status, stride, 0, 2 * sizeof(unsigned), members, static_cast<hipStream_t>(stream))
                   : hipMemsetAsync(P.status, 0, 2 * sizeof(unsigned), static_cast<hipStream_t>(stream));
-        if (e != hipSuccess) return fail_hip(h, e, (w + " (status words)").c_str());
+        if (e != hipSuccess) { unconfigure(h); return fail_hip(h, e, (w + " (status words)").c_str()); }
     }
     h->tt_ws = ws; h->tt_N = L.N; h->tt_dt = dt;
     h->L = L; h->P = P; h->ws = ws;
-    h->params_set = true;
-    h->legacy = false;
+    h->mode = mode;
     h->bank_M = M;
-    h->bank_rho = false;              // (cmps_rho_bank_set_state_dev sets it once the columns are packed)
     h->main.valid = false;
     h->rho_set = false;               // the columns of rho_0 are handed over again after every parameter change
     h->rho.valid = false;
@@ -431,10 +496,11 @@ int cmps_set_params(cmps_handle_t h, const float* R_re_dev, const float* R_im_de
 
 // set_params_impl on the packed buffer R_re | R_im | freqs | psi0_re | psi0_im | A that the apply-step entries write (a bank's: member 0's row)
 static int set_params_packed(cmps_handle_t h, const float* params_dev, double sigma, double delta_t, int T, int B_max, int flags,
-                             void* workspace_dev, size_t workspace_bytes, void* stream, int M = 0, size_t rho_bytes = 0) {
+                             void* workspace_dev, size_t workspace_bytes, void* stream, Mode mode = MODE_PSI, int M = 0, size_t rho_bytes = 0) {
     const size_t DD = (size_t)h->D * h->D, D = (size_t)h->D;
     return set_params_impl(h, params_dev, params_dev + DD, params_dev + 2 * DD, params_dev + 2 * DD + D, params_dev + 2 * DD + 2 * D,
-                           0.f, params_dev + 2 * DD + 3 * D, sigma, delta_t, T, B_max, flags, workspace_dev, workspace_bytes, stream, M, rho_bytes);
+                           0.f, params_dev + 2 * DD + 3 * D, sigma, delta_t, T, B_max, flags, workspace_dev, workspace_bytes, stream, mode, M,
+                           rho_bytes);
 }
 
 int cmps_set_params_dev(cmps_handle_t h, const float* params_dev, double sigma, double delta_t, int T, int B_max, int flags,
@@ -520,8 +586,8 @@ static int psi_fwd_run(cmps_handle_t h, const char* who, int M, int n_audio, con
 int cmps_psi_loss_fwd(cmps_handle_t h, const float* audio_dev, int B, int T, float* loss_dev,
                       int save_for_bwd, void* stream) {
     if (!h) return CMPS_ERR_BAD_ARG;
-    if (const int rc = check_fwd(h, "cmps_psi_loss_fwd", h->params_set && !h->legacy && !h->bank_M, "cmps_set_params", audio_dev, loss_dev, B, T,
-                                 h->L.T, h->L.B, save_for_bwd, h->L.flags)) return rc;
+    if (const int rc = check_fwd(h, "cmps_psi_loss_fwd", in(MODE_PSI), true, "cmps_set_params", audio_dev, loss_dev, B, T, h->L.T, h->L.B,
+                                 save_for_bwd, h->L.flags)) return rc;
     return psi_fwd_run(h, "cmps_psi_loss_fwd", 0, 0, audio_dev, B, T, loss_dev, save_for_bwd, stream);
 }
 
@@ -585,8 +651,7 @@ static int psi_bwd_run(cmps_handle_t h, const char* who, int M, int n_audio, con
 
 int cmps_psi_loss_bwd(cmps_handle_t h, const float* audio_dev, int B, int T, float* grad_dev, void* stream) {
     if (!h) return CMPS_ERR_BAD_ARG;
-    if (const int rc = check_bwd(h, "cmps_psi_loss_bwd", h->params_set && !h->legacy && !h->bank_M && h->main.M == 0, "cmps_psi_loss_fwd", h->main,
-                                 audio_dev, grad_dev, B, T))
+    if (const int rc = check_bwd(h, "cmps_psi_loss_bwd", in(MODE_PSI), h->main.M == 0, "cmps_psi_loss_fwd", h->main, audio_dev, grad_dev, B, T))
         return rc;
     return psi_bwd_run(h, "cmps_psi_loss_bwd", 0, 0, audio_dev, B, T, grad_dev, stream);
 }
@@ -595,8 +660,8 @@ int cmps_psi_grad_status(cmps_handle_t h, int* sticky_out, void* stream) {
     if (!h) return CMPS_ERR_BAD_ARG;
     if (const int rc = check_not_bank(h, "cmps_psi_grad_status")) return rc;
     if (sticky_out) *sticky_out = 0;
-    if (!h->params_set || h->legacy || !h->P.status)
-        return fail(h, CMPS_ERR_STATE, "cmps_psi_grad_status: needs cmps_set_params with a CMPS_WS_TRAIN workspace");
+    if (const int rc = need_mode(h, "cmps_psi_grad_status", in(MODE_PSI), h->P.status != nullptr, ": needs cmps_set_params with a CMPS_WS_TRAIN workspace"))
+        return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     unsigned words[2] = {0u, 0u};
     hipError_t e = hipMemcpyAsync(words, h->P.status, sizeof words, hipMemcpyDeviceToHost, s);
@@ -622,7 +687,7 @@ static int bank_check_mode(cmps_handle_t h, const char* who, bool tables) {
     const std::string w(who);
     if (h->D > 32 && resolve_variant(h) != CMPS_VARIANT_BLOCK)
         return fail(h, CMPS_ERR_UNSUPPORTED_D, w + ": a bank above D = 32 needs CMPS_VARIANT_BLOCK (the wide and pair kernels have no member dimension)");
-    if (tables && h->legacy) return fail(h, CMPS_ERR_STATE, w + ": not available in legacy mode");
+    if (tables) if (const int rc = need_mode(h, who, ~in(MODE_LEGACY), true, ": not available in legacy mode")) return rc;
     if (h->rank1_mode != CMPS_RANK1_DEFAULT || h->bwd_waves != 2 || h->f16_shift != 0)
         return fail(h, CMPS_ERR_STATE, w + ": a bank runs with the default CMPS_OPT_RANK1, CMPS_OPT_BWD_WAVES and CMPS_OPT_F16_SCALE_SHIFT only");
     return CMPS_OK;
@@ -653,15 +718,15 @@ int cmps_bank_set_params_dev(cmps_handle_t h, int M, const float* params_dev, do
     if (const int rc = bank_check_M(h, who, M)) return rc;
     if (const int rc = bank_check_shape(h, who, M, B_max, T)) return rc;
     if (!workspace_dev) return fail(h, CMPS_ERR_WORKSPACE, std::string(who) + ": null workspace");
-    return set_params_packed(h, params_dev, sigma, delta_t, T, B_max, flags, workspace_dev, workspace_bytes, stream, M);
+    return set_params_packed(h, params_dev, sigma, delta_t, T, B_max, flags, workspace_dev, workspace_bytes, stream, MODE_PSI_BANK, M);
 }
 
 int cmps_bank_loss_fwd(cmps_handle_t h, const float* audio_dev, int n_audio, int B, int T, float* loss_dev, int save_for_bwd, void* stream) {
     const char* who = "cmps_bank_loss_fwd";
     if (!h) return CMPS_ERR_BAD_ARG;
     if (const int rc = bank_check_mode(h, who, true)) return rc;
-    if (const int rc = check_fwd(h, who, h->params_set && !h->legacy && h->bank_M > 0 && !h->bank_rho, "cmps_bank_set_params_dev", audio_dev, loss_dev, B, T,
-                                 h->L.T, h->L.B, save_for_bwd, h->L.flags)) return rc;
+    if (const int rc = check_fwd(h, who, in(MODE_PSI_BANK), true, "cmps_bank_set_params_dev", audio_dev, loss_dev, B, T, h->L.T, h->L.B,
+                                 save_for_bwd, h->L.flags)) return rc;
     if (n_audio != 1 && n_audio != h->bank_M) return fail(h, CMPS_ERR_BAD_ARG, std::string(who) + ": n_audio must be 1 (one shared batch) or M");
     return psi_fwd_run(h, who, h->bank_M, n_audio, audio_dev, B, T, loss_dev, save_for_bwd, stream);
 }
@@ -670,8 +735,7 @@ int cmps_bank_loss_bwd(cmps_handle_t h, const float* audio_dev, int n_audio, int
     const char* who = "cmps_bank_loss_bwd";
     if (!h) return CMPS_ERR_BAD_ARG;
     if (const int rc = bank_check_mode(h, who, true)) return rc;
-    const bool ready = h->params_set && !h->legacy && h->bank_M > 0 && !h->bank_rho && h->main.M == h->bank_M;
-    if (const int rc = check_bwd(h, who, ready, "cmps_bank_loss_fwd", h->main, audio_dev, grad_dev, B, T)) return rc;
+    if (const int rc = check_bwd(h, who, in(MODE_PSI_BANK), h->main.M == h->bank_M, "cmps_bank_loss_fwd", h->main, audio_dev, grad_dev, B, T)) return rc;
     if (n_audio != h->main.n_audio) return fail(h, CMPS_ERR_STATE, std::string(who) + ": n_audio differs from the forward call");
     return psi_bwd_run(h, who, h->bank_M, n_audio, audio_dev, B, T, grad_dev, stream);
 }
@@ -682,13 +746,11 @@ int cmps_bank_loss_bwd_weighted(cmps_handle_t h, const float* audio_dev, int n_a
                                 float* grad_dev, void* stream) {
     const char* who = "cmps_bank_loss_bwd_weighted";
     if (!h) return CMPS_ERR_BAD_ARG;
-    if (!weight_dev) return fail(h, CMPS_ERR_BAD_ARG, std::string(who) + ": weight_dev is a null pointer");
-    if (ldw < (long long)B) return fail(h, CMPS_ERR_BAD_ARG, std::string(who) + ": ldw must be at least B");
+    if (const int rc = Args{h, who}.ptr("weight_dev", weight_dev).ld("ldw", ldw, B).rc) return rc;
     if (const int rc = bank_check_mode(h, who, true)) return rc;
-    if (h->bank_M > 0 && h->bank_rho)
-        return fail(h, CMPS_ERR_STATE, std::string(who) + ": the handle holds a RhoCMPS bank; the weighted reverse pass is for PsiCMPS banks (cmps_bank_set_params_dev)");
-    const bool ready = h->params_set && !h->legacy && h->bank_M > 0 && h->main.M == h->bank_M;
-    if (const int rc = check_bwd(h, who, ready, "cmps_bank_loss_fwd", h->main, audio_dev, grad_dev, B, T)) return rc;
+    if (const int rc = need_mode(h, who, ~in(MODE_RHO_BANK), true,
+                                 ": the handle holds a RhoCMPS bank; the weighted reverse pass is for PsiCMPS banks (cmps_bank_set_params_dev)")) return rc;
+    if (const int rc = check_bwd(h, who, in(MODE_PSI_BANK), h->main.M == h->bank_M, "cmps_bank_loss_fwd", h->main, audio_dev, grad_dev, B, T)) return rc;
     if (n_audio != h->main.n_audio) return fail(h, CMPS_ERR_STATE, std::string(who) + ": n_audio differs from the forward call");
     return psi_bwd_run(h, who, h->bank_M, n_audio, audio_dev, B, T, grad_dev, stream, weight_dev, ldw);
 }
@@ -714,11 +776,11 @@ int cmps_bank_apply_step(cmps_handle_t h, int M, float* vars_dev, float* adam_m_
 }
 
 int cmps_bank_grad_status(cmps_handle_t h, int* codes_out, int* sticky_out, void* stream) {
-    const std::string w("cmps_bank_grad_status");
+    const char* who = "cmps_bank_grad_status";
     if (!h) return CMPS_ERR_BAD_ARG;
-    if (!codes_out) return fail(h, CMPS_ERR_BAD_ARG, w + ": null codes_out");
-    if (!h->params_set || h->legacy || h->bank_M < 1 || h->bank_rho || !h->P.status)
-        return fail(h, CMPS_ERR_STATE, w + ": needs cmps_bank_set_params_dev with a CMPS_WS_TRAIN workspace");
+    if (!codes_out) return fail(h, CMPS_ERR_BAD_ARG, std::string(who) + ": null codes_out");
+    if (const int rc = need_mode(h, who, in(MODE_PSI_BANK), h->P.status != nullptr, ": needs cmps_bank_set_params_dev with a CMPS_WS_TRAIN workspace"))
+        return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int M = h->bank_M;
     std::vector<unsigned> words(2 * (size_t)M, 0u);
@@ -739,8 +801,7 @@ int cmps_bank_grad_status(cmps_handle_t h, int* codes_out, int* sticky_out, void
 int cmps_psi_update_ancilla(cmps_handle_t h, const float* psi_in_dev, const float* signal_dev, float t,
                             int B, float* psi_out_dev, void* stream) {
     if (!h) return CMPS_ERR_BAD_ARG;
-    if (const int rc = check_not_bank(h, "cmps_psi_update_ancilla")) return rc;
-    if (!h->params_set) return fail(h, CMPS_ERR_STATE, "cmps_psi_update_ancilla: call cmps_set_params first");
+    if (const int rc = need_plain(h, "cmps_psi_update_ancilla", in(MODE_PSI) | in(MODE_LEGACY), true, ": call cmps_set_params first")) return rc;
     if (!psi_in_dev || !signal_dev || !psi_out_dev || B < 1)
         return fail(h, CMPS_ERR_BAD_ARG, "cmps_psi_update_ancilla: bad argument");
     hipError_t e = launch_update_ancilla(h->P, psi_in_dev, signal_dev, t, B, psi_out_dev,
@@ -752,10 +813,11 @@ int cmps_psi_update_ancilla(cmps_handle_t h, const float* psi_in_dev, const floa
 int cmps_psi_states(cmps_handle_t h, int B, int T, float* psi_out_dev, void* stream) {
     if (!h) return CMPS_ERR_BAD_ARG;
     if (const int rc = check_not_bank(h, "cmps_psi_states")) return rc;
-    if (h->legacy)               // (k_states rotates into the lab frame with freqs and the time table; neither exists after cmps_legacy_set_params)
-        return fail(h, CMPS_ERR_STATE, "cmps_psi_states: not available in legacy mode (no time table for the lab-frame phases)");
-    if (!h->params_set || !h->main.valid || h->main.M != 0)
-        return fail(h, CMPS_ERR_STATE, "cmps_psi_states: needs cmps_psi_loss_fwd(save_for_bwd=1) first");
+    // (k_states rotates into the lab frame with freqs and the time table; neither exists after cmps_legacy_set_params)
+    if (const int rc = need_mode(h, "cmps_psi_states", ~in(MODE_LEGACY), true, ": not available in legacy mode (no time table for the lab-frame phases)"))
+        return rc;
+    if (const int rc = need_mode(h, "cmps_psi_states", in(MODE_PSI), h->main.valid && h->main.M == 0, ": needs cmps_psi_loss_fwd(save_for_bwd=1) first"))
+        return rc;
     if (!psi_out_dev || B != h->main.B || T != h->main.steps + 1)
         return fail(h, CMPS_ERR_BAD_ARG, "cmps_psi_states: bad argument");
     hipError_t e = launch_states(main_dev(h, B), B, psi_out_dev, static_cast<hipStream_t>(stream));
@@ -845,23 +907,19 @@ static int score_args(cmps_handle_t h, const char* who, const void* state_in_dev
 }
 // The kernel choice and the launch of one SampleDev
 static int psi_sample_launch(cmps_handle_t h, const char* who, const SampleDev& S, void* stream) {
-    hipStream_t s = static_cast<hipStream_t>(stream);
     const int family = sampler_family(h);
     static const char* const names[3][4] = {{"k_sample_block", "k_sample_block_primed", "k_sample_block_stream", "k_sample_block_score"},
                                             {"k_sample_wave", "k_sample_wave_primed", "k_sample_wave_stream", "k_sample_wave_score"},
                                             {"k_sample_wide", "k_sample_wide_primed", "k_sample_wide_stream", "k_sample_wide_score"}};   // [family][SampleMode]
-    KBind kb(h);
-    KScope ks(names[family][sample_mode(S)], s);
-    const hipError_t e = family == SAMPLER_WAVE ? launch_sample_wave(h->P, S, s)
-                       : family == SAMPLER_WIDE ? launch_sample_wide(h->P, S, s) : launch_sample_block(h->P, S, s);
-    if (e != hipSuccess) return fail_hip(h, e, who);
-    return CMPS_OK;
+    return run_kernel(h, who, names[family][sample_mode(S)], stream, [&](hipStream_t s) {
+        return family == SAMPLER_WAVE ? launch_sample_wave(h->P, S, s)
+             : family == SAMPLER_WIDE ? launch_sample_wide(h->P, S, s) : launch_sample_block(h->P, S, s);
+    });
 }
 
 int cmps_psi_sample(cmps_handle_t h, const float* noise_dev, int n, int length, float* out_dev, void* stream) {
     if (!h) return CMPS_ERR_BAD_ARG;
-    if (const int rc = check_not_bank(h, "cmps_psi_sample")) return rc;
-    if (!h->params_set) return fail(h, CMPS_ERR_STATE, "cmps_psi_sample: call cmps_set_params first");
+    if (const int rc = need_plain(h, "cmps_psi_sample", in(MODE_PSI) | in(MODE_LEGACY), true, ": call cmps_set_params first")) return rc;
     if (!noise_dev || !out_dev || n < 1 || length < 1)
         return fail(h, CMPS_ERR_BAD_ARG, "cmps_psi_sample: bad argument");
     if (length > h->L.N)
@@ -872,9 +930,8 @@ int cmps_psi_sample(cmps_handle_t h, const float* noise_dev, int n, int length, 
 int cmps_psi_sample_primed(cmps_handle_t h, const float* prime_dev, int n_prime, int prime_T, const float* noise_dev, int n, int length,
                            float* out_dev, float* pred_dev, void* stream) {
     if (!h) return CMPS_ERR_BAD_ARG;
-    if (const int rc = check_not_bank(h, "cmps_psi_sample_primed")) return rc;
-    if (!h->params_set || h->legacy)       // (the legacy tables carry no rotation and another step: nothing here would mean PsiCMPS.sample)
-        return fail(h, CMPS_ERR_STATE, "cmps_psi_sample_primed: call cmps_set_params first (not available in legacy mode)");
+    // (the legacy tables carry no rotation and another step: nothing here would mean PsiCMPS.sample)
+    if (const int rc = need_plain(h, "cmps_psi_sample_primed", in(MODE_PSI), true, ": call cmps_set_params first (not available in legacy mode)")) return rc;
     SampleDev S;
     if (int c = primed_args(h, "cmps_psi_sample_primed", prime_dev, n_prime, prime_T, noise_dev, n, length, out_dev, pred_dev, S)) return c;
     return psi_sample_launch(h, "cmps_psi_sample_primed", S, stream);
@@ -888,9 +945,7 @@ size_t cmps_psi_stream_state_bytes(cmps_handle_t h, int n) {
 int cmps_psi_stream(cmps_handle_t h, const void* state_in_dev, void* state_out_dev, int k0, const float* audio_dev, int n_audio, int forced,
                     const float* noise_dev, int length, int n, float* out_dev, float* pred_dev, void* stream) {
     if (!h) return CMPS_ERR_BAD_ARG;
-    if (const int rc = check_not_bank(h, "cmps_psi_stream")) return rc;
-    if (!h->params_set || h->legacy)
-        return fail(h, CMPS_ERR_STATE, "cmps_psi_stream: call cmps_set_params first (not available in legacy mode)");
+    if (const int rc = need_plain(h, "cmps_psi_stream", in(MODE_PSI), true, ": call cmps_set_params first (not available in legacy mode)")) return rc;
     StreamCall C;
     if (int c = stream_args(h, "cmps_psi_stream", state_in_dev, state_out_dev, k0, audio_dev, n_audio, forced, noise_dev, n, length, n, out_dev, pred_dev,
                             stream_rec_floats(h), plain_rows, MemberDev{}, C))
@@ -901,9 +956,7 @@ int cmps_psi_stream(cmps_handle_t h, const void* state_in_dev, void* state_out_d
 int cmps_psi_stream_score(cmps_handle_t h, const void* state_in_dev, void* state_out_dev, int k0, const float* audio_dev, int n_audio, int forced,
                           int n, float* nll_dev, float* loss_dev, float* pred_dev, void* stream) {
     if (!h) return CMPS_ERR_BAD_ARG;
-    if (const int rc = check_not_bank(h, "cmps_psi_stream_score")) return rc;
-    if (!h->params_set || h->legacy)
-        return fail(h, CMPS_ERR_STATE, "cmps_psi_stream_score: call cmps_set_params first (not available in legacy mode)");
+    if (const int rc = need_plain(h, "cmps_psi_stream_score", in(MODE_PSI), true, ": call cmps_set_params first (not available in legacy mode)")) return rc;
     StreamCall C;
     if (int c = score_args(h, "cmps_psi_stream_score", state_in_dev, state_out_dev, k0, audio_dev, n_audio, forced, n, nll_dev, loss_dev, pred_dev,
                            stream_rec_floats(h), "path", plain_rows, MemberDev{}, C))
@@ -914,8 +967,7 @@ int cmps_psi_stream_score(cmps_handle_t h, const void* state_in_dev, void* state
 // ---- a bank's streams: the STREAM / SCORE instances with the members as a second grid dimension (include/cmps.h) ----
 // What cmps_bank_stream and cmps_bank_stream_score refuse before they look at their arguments
 static int bank_stream_check_mode(cmps_handle_t h, const char* who) {
-    if (!h->params_set || h->legacy || h->bank_M < 1 || h->bank_rho)
-        return fail(h, CMPS_ERR_STATE, std::string(who) + ": needs a PsiCMPS bank (call cmps_bank_set_params_dev first)");
+    if (const int rc = need_mode(h, who, in(MODE_PSI_BANK), true, ": needs a PsiCMPS bank (call cmps_bank_set_params_dev first)")) return rc;
     if (const int rc = bank_check_mode(h, who, true)) return rc;
     if (sampler_family(h) == SAMPLER_WIDE)               // (a variant set behind cmps_bank_set_params_dev)
         return fail(h, CMPS_ERR_STATE, std::string(who) + ": a bank samples with the wave and block kernels only");
@@ -938,7 +990,7 @@ static size_t bank_member_stride(const cmps_handle_s* h, long long rows, int n, 
 }
 
 size_t cmps_bank_stream_state_bytes(cmps_handle_t h, int n) {
-    if (!h || n < 1 || !h->params_set || h->legacy || h->bank_M < 1 || h->bank_rho) return 0;
+    if (!h || n < 1 || h->mode != MODE_PSI_BANK) return 0;
     return (size_t)h->bank_M * (size_t)n * stream_rec_floats(h) * sizeof(float);
 }
 
@@ -972,76 +1024,53 @@ int cmps_bank_stream_score(cmps_handle_t h, const void* state_in_dev, void* stat
 // The samplers' noise drawn on the device: needs nothing of the handle but its error string and its kernel-event record
 int cmps_noise_fill(cmps_handle_t h, unsigned long long seed, unsigned long long first_step, unsigned first_path, int n, int length,
                     float stddev, float* noise_dev, void* stream) {
+    const char* who = "cmps_noise_fill";
     if (!h) return CMPS_ERR_BAD_ARG;
-    if (!noise_dev) return fail(h, CMPS_ERR_BAD_ARG, "cmps_noise_fill: noise_dev is a null pointer");
-    if (n < 1 || length < 1) return fail(h, CMPS_ERR_BAD_ARG, "cmps_noise_fill: need n >= 1 and length >= 1");
-    if (!(stddev >= 0.0f) || !std::isfinite(stddev)) return fail(h, CMPS_ERR_BAD_ARG, "cmps_noise_fill: stddev must be finite and not negative");
-    if ((unsigned long long)first_path + (unsigned long long)n > (1ull << 32))
-        return fail(h, CMPS_ERR_BAD_ARG, "cmps_noise_fill: first_path + n exceeds 2^32 (a path is a 32-bit counter word)");
-    if (first_step + (unsigned long long)length < first_step)
-        return fail(h, CMPS_ERR_BAD_ARG, "cmps_noise_fill: first_step + length overflows 64 bits");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    KBind kb(h);
-    KScope ks("k_noise_philox", s);
-    const hipError_t e = launch_noise_philox(seed, first_step, first_path, n, length, stddev, noise_dev, s);
-    if (e != hipSuccess) return fail_hip(h, e, "cmps_noise_fill");
-    return CMPS_OK;
+    if (const int rc = Args{h, who}.ptr("noise_dev", noise_dev).need(n >= 1 && length >= 1, "need n >= 1 and length >= 1")
+                           .not_negative("stddev", stddev)
+                           .need((unsigned long long)first_path + (unsigned long long)n <= (1ull << 32),
+                                 "first_path + n exceeds 2^32 (a path is a 32-bit counter word)")
+                           .need(first_step + (unsigned long long)length >= first_step, "first_step + length overflows 64 bits").rc) return rc;
+    return run_kernel(h, who, "k_noise_philox", stream,
+                      [&](hipStream_t s) { return launch_noise_philox(seed, first_step, first_path, n, length, stddev, noise_dev, s); });
 }
 
 // The input of a training step produced on the device: like cmps_noise_fill, both need nothing of the handle but its error string and
 // its kernel-event record
+static Args gather_args(cmps_handle_t h, const char* who, const void* data_dev, long long n_clips, long long clip_len, const int* index_dev, int B, int T,
+                        const float* audio_dev) {
+    return Args{h, who}.ptr("data_dev", data_dev).ptr("index_dev", index_dev).ptr("audio_dev", audio_dev)
+        .need(B >= 1 && T >= 1, "need B >= 1 and T >= 1")
+        .need(n_clips >= 1 && n_clips <= 2147483647ll, "need 1 <= n_clips <= 2^31 - 1 (an index is a 32-bit int)")
+        .need(clip_len >= (long long)T, "clip_len must be at least T");
+}
+
 int cmps_batch_gather(cmps_handle_t h, const float* data_dev, long long n_clips, long long clip_len, const int* index_dev,
                       const int* offset_dev, int B, int T, float* audio_dev, void* stream) {
+    const char* who = "cmps_batch_gather";
     if (!h) return CMPS_ERR_BAD_ARG;
-    if (!data_dev) return fail(h, CMPS_ERR_BAD_ARG, "cmps_batch_gather: data_dev is a null pointer");
-    if (!index_dev) return fail(h, CMPS_ERR_BAD_ARG, "cmps_batch_gather: index_dev is a null pointer");
-    if (!audio_dev) return fail(h, CMPS_ERR_BAD_ARG, "cmps_batch_gather: audio_dev is a null pointer");
-    if (B < 1 || T < 1) return fail(h, CMPS_ERR_BAD_ARG, "cmps_batch_gather: need B >= 1 and T >= 1");
-    if (n_clips < 1 || n_clips > 2147483647ll)
-        return fail(h, CMPS_ERR_BAD_ARG, "cmps_batch_gather: need 1 <= n_clips <= 2^31 - 1 (an index is a 32-bit int)");
-    if (clip_len < (long long)T) return fail(h, CMPS_ERR_BAD_ARG, "cmps_batch_gather: clip_len must be at least T");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    KBind kb(h);
-    KScope ks("k_batch_gather", s);
-    const hipError_t e = launch_batch_gather(data_dev, n_clips, clip_len, index_dev, offset_dev, B, T, audio_dev, s);
-    if (e != hipSuccess) return fail_hip(h, e, "cmps_batch_gather");
-    return CMPS_OK;
+    if (const int rc = gather_args(h, who, data_dev, n_clips, clip_len, index_dev, B, T, audio_dev).rc) return rc;
+    return run_kernel(h, who, "k_batch_gather", stream,
+                      [&](hipStream_t s) { return launch_batch_gather(data_dev, n_clips, clip_len, index_dev, offset_dev, B, T, audio_dev, s); });
 }
 
 int cmps_batch_gather_i16(cmps_handle_t h, const short* data_dev, long long n_clips, long long clip_len, const int* index_dev,
                           const int* offset_dev, int B, int T, float scale, float* audio_dev, void* stream) {
+    const char* who = "cmps_batch_gather_i16";
     if (!h) return CMPS_ERR_BAD_ARG;
-    if (!data_dev) return fail(h, CMPS_ERR_BAD_ARG, "cmps_batch_gather_i16: data_dev is a null pointer");
-    if (!index_dev) return fail(h, CMPS_ERR_BAD_ARG, "cmps_batch_gather_i16: index_dev is a null pointer");
-    if (!audio_dev) return fail(h, CMPS_ERR_BAD_ARG, "cmps_batch_gather_i16: audio_dev is a null pointer");
-    if (B < 1 || T < 1) return fail(h, CMPS_ERR_BAD_ARG, "cmps_batch_gather_i16: need B >= 1 and T >= 1");
-    if (n_clips < 1 || n_clips > 2147483647ll)
-        return fail(h, CMPS_ERR_BAD_ARG, "cmps_batch_gather_i16: need 1 <= n_clips <= 2^31 - 1 (an index is a 32-bit int)");
-    if (clip_len < (long long)T) return fail(h, CMPS_ERR_BAD_ARG, "cmps_batch_gather_i16: clip_len must be at least T");
-    if (!std::isfinite(scale) || !(scale > 0.0f)) return fail(h, CMPS_ERR_BAD_ARG, "cmps_batch_gather_i16: scale must be finite and positive");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    KBind kb(h);
-    KScope ks("k_batch_gather_i16", s);
-    const hipError_t e = launch_batch_gather_i16(data_dev, n_clips, clip_len, index_dev, offset_dev, B, T, scale, audio_dev, s);
-    if (e != hipSuccess) return fail_hip(h, e, "cmps_batch_gather_i16");
-    return CMPS_OK;
+    if (const int rc = gather_args(h, who, data_dev, n_clips, clip_len, index_dev, B, T, audio_dev).positive("scale", scale).rc) return rc;
+    return run_kernel(h, who, "k_batch_gather_i16", stream, [&](hipStream_t s) {
+        return launch_batch_gather_i16(data_dev, n_clips, clip_len, index_dev, offset_dev, B, T, scale, audio_dev, s);
+    });
 }
 
 // The per-clip losses of an evaluation pass folded into one record on the device: needs nothing of the handle either
 int cmps_loss_stats(cmps_handle_t h, const float* loss_dev, int B, long long first_id, int reset, void* stats_dev, void* stream) {
+    const char* who = "cmps_loss_stats";
     if (!h) return CMPS_ERR_BAD_ARG;
-    if (!loss_dev) return fail(h, CMPS_ERR_BAD_ARG, "cmps_loss_stats: loss_dev is a null pointer");
-    if (!stats_dev) return fail(h, CMPS_ERR_BAD_ARG, "cmps_loss_stats: stats_dev is a null pointer");
-    if (((uintptr_t)stats_dev & 7) != 0) return fail(h, CMPS_ERR_BAD_ARG, "cmps_loss_stats: stats_dev must be 8-byte aligned");
-    if (B < 1) return fail(h, CMPS_ERR_BAD_ARG, "cmps_loss_stats: need B >= 1");
-    if (first_id < 0 || first_id > 9223372036854775807ll - (long long)B)
-        return fail(h, CMPS_ERR_BAD_ARG, "cmps_loss_stats: need first_id >= 0 and first_id + B below 2^63 (an id is a signed 64-bit integer)");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    KBind kb(h);
-    KScope ks("k_loss_stats", s);
-    const hipError_t e = launch_loss_stats(loss_dev, B, first_id, reset, stats_dev, s);
-    if (e != hipSuccess) return fail_hip(h, e, "cmps_loss_stats");
-    return CMPS_OK;
+    if (const int rc = Args{h, who}.ptr("loss_dev", loss_dev).ptr("stats_dev", stats_dev).align8("stats_dev", stats_dev).min1("B", B)
+                           .range63("first_id", first_id, "B", B, "an id").rc) return rc;
+    return run_kernel(h, who, "k_loss_stats", stream, [&](hipStream_t s) { return launch_loss_stats(loss_dev, B, first_id, reset, stats_dev, s); });
 }
 
 // The [M][B] losses of a bank forward judged as a classifier, folded into one record on the device: needs nothing of the handle either
@@ -1052,97 +1081,59 @@ size_t cmps_bank_classify_stats_bytes(int M) {
 
 int cmps_bank_classify_stats(cmps_handle_t h, const float* loss_dev, int M, int B, long long ld, const int* label_dev, long long first_id,
                              int reset, void* stats_dev, int* best_dev, void* stream) {
+    const char* who = "cmps_bank_classify_stats";
     if (!h) return CMPS_ERR_BAD_ARG;
-    if (!loss_dev) return fail(h, CMPS_ERR_BAD_ARG, "cmps_bank_classify_stats: loss_dev is a null pointer");
-    if (!stats_dev) return fail(h, CMPS_ERR_BAD_ARG, "cmps_bank_classify_stats: stats_dev is a null pointer");
-    if (((uintptr_t)stats_dev & 7) != 0) return fail(h, CMPS_ERR_BAD_ARG, "cmps_bank_classify_stats: stats_dev must be 8-byte aligned");
-    if (M < 1 || M > CLASSIFY_MAX_M) return fail(h, CMPS_ERR_BAD_ARG, "cmps_bank_classify_stats: need 1 <= M <= 1024");
-    if (B < 1) return fail(h, CMPS_ERR_BAD_ARG, "cmps_bank_classify_stats: need B >= 1");
-    if (ld < (long long)B) return fail(h, CMPS_ERR_BAD_ARG, "cmps_bank_classify_stats: ld must be at least B");
-    if (first_id < 0 || first_id > 9223372036854775807ll - (long long)B)
-        return fail(h, CMPS_ERR_BAD_ARG,
-                    "cmps_bank_classify_stats: need first_id >= 0 and first_id + B below 2^63 (an id is a signed 64-bit integer)");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    KBind kb(h);
-    KScope ks("k_classify_stats", s);
-    const hipError_t e = launch_classify_stats(loss_dev, M, B, ld, label_dev, first_id, reset, stats_dev, best_dev, s);
-    if (e != hipSuccess) return fail_hip(h, e, "cmps_bank_classify_stats");
-    return CMPS_OK;
+    if (const int rc = Args{h, who}.ptr("loss_dev", loss_dev).ptr("stats_dev", stats_dev).align8("stats_dev", stats_dev).members(M).min1("B", B)
+                           .ld("ld", ld, B).range63("first_id", first_id, "B", B, "an id").rc) return rc;
+    return run_kernel(h, who, "k_classify_stats", stream, [&](hipStream_t s) {
+        return launch_classify_stats(loss_dev, M, B, ld, label_dev, first_id, reset, stats_dev, best_dev, s);
+    });
 }
 
 // ... and turned into the cotangents of a cross-entropy step: needs nothing of the handle either
 int cmps_bank_classify_weights(cmps_handle_t h, const float* loss_dev, int M, int B, long long ld, const int* label_dev, double inv_temp,
                                double gen_weight, double disc_weight, int reset, float* weight_dev, long long ldw, void* record_dev,
                                void* stream) {
-    const std::string w("cmps_bank_classify_weights");
+    const char* who = "cmps_bank_classify_weights";
     if (!h) return CMPS_ERR_BAD_ARG;
-    if (!loss_dev) return fail(h, CMPS_ERR_BAD_ARG, w + ": loss_dev is a null pointer");
-    if (!label_dev) return fail(h, CMPS_ERR_BAD_ARG, w + ": label_dev is a null pointer");
-    if (!weight_dev) return fail(h, CMPS_ERR_BAD_ARG, w + ": weight_dev is a null pointer");
-    if (!record_dev) return fail(h, CMPS_ERR_BAD_ARG, w + ": record_dev is a null pointer");
-    if (((uintptr_t)record_dev & 7) != 0) return fail(h, CMPS_ERR_BAD_ARG, w + ": record_dev must be 8-byte aligned");
-    if (M < 1 || M > CLASSIFY_MAX_M) return fail(h, CMPS_ERR_BAD_ARG, w + ": need 1 <= M <= 1024");
-    if (B < 1) return fail(h, CMPS_ERR_BAD_ARG, w + ": need B >= 1");
-    if (ld < (long long)B) return fail(h, CMPS_ERR_BAD_ARG, w + ": ld must be at least B");
-    if (ldw < (long long)B) return fail(h, CMPS_ERR_BAD_ARG, w + ": ldw must be at least B");
-    if (!std::isfinite(inv_temp) || !(inv_temp > 0.0)) return fail(h, CMPS_ERR_BAD_ARG, w + ": inv_temp must be finite and positive");
-    if (!std::isfinite(gen_weight) || gen_weight < 0.0) return fail(h, CMPS_ERR_BAD_ARG, w + ": gen_weight must be finite and not negative");
-    if (!std::isfinite(disc_weight) || disc_weight < 0.0) return fail(h, CMPS_ERR_BAD_ARG, w + ": disc_weight must be finite and not negative");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    KBind kb(h);
-    KScope ks("k_classify_weights", s);
-    const hipError_t e = launch_classify_weights(loss_dev, M, B, ld, label_dev, inv_temp, gen_weight, disc_weight, reset, weight_dev, ldw,
-                                                 record_dev, s);
-    if (e != hipSuccess) return fail_hip(h, e, "cmps_bank_classify_weights");
-    return CMPS_OK;
+    if (const int rc = Args{h, who}.ptr("loss_dev", loss_dev).ptr("label_dev", label_dev).ptr("weight_dev", weight_dev).ptr("record_dev", record_dev)
+                           .align8("record_dev", record_dev).members(M).min1("B", B).ld("ld", ld, B).ld("ldw", ldw, B)
+                           .positive("inv_temp", inv_temp).not_negative("gen_weight", gen_weight).not_negative("disc_weight", disc_weight).rc)
+        return rc;
+    return run_kernel(h, who, "k_classify_weights", stream, [&](hipStream_t s) {
+        return launch_classify_weights(loss_dev, M, B, ld, label_dev, inv_temp, gen_weight, disc_weight, reset, weight_dev, ldw, record_dev, s);
+    });
 }
 
 // The per-step losses of a scored bank stream folded into the posterior over the members after every step: needs nothing of the handle either
 int cmps_bank_posterior(cmps_handle_t h, const float* nll_dev, int M, int n, int steps, const float* total_in_dev, const double* log_prior_dev,
                         double inv_temp, float* total_out_dev, float* post_dev, int* best_dev, float* conf_dev, double threshold,
                         long long first_step, int reset, void* decision_dev, void* stream) {
-    const std::string w("cmps_bank_posterior");
+    const char* who = "cmps_bank_posterior";
     if (!h) return CMPS_ERR_BAD_ARG;
-    if (!nll_dev) return fail(h, CMPS_ERR_BAD_ARG, w + ": nll_dev is a null pointer");
-    if (M < 1 || M > CLASSIFY_MAX_M) return fail(h, CMPS_ERR_BAD_ARG, w + ": need 1 <= M <= 1024");
-    if (n < 1) return fail(h, CMPS_ERR_BAD_ARG, w + ": need n >= 1");
-    if (steps < 1) return fail(h, CMPS_ERR_BAD_ARG, w + ": need steps >= 1");
-    if ((long long)M * (long long)n > 2147483647ll / (long long)steps)
-        return fail(h, CMPS_ERR_BAD_ARG, w + ": need M * n * steps <= 2^31 - 1");
-    if (!std::isfinite(inv_temp) || !(inv_temp > 0.0)) return fail(h, CMPS_ERR_BAD_ARG, w + ": inv_temp must be finite and positive");
-    if (((uintptr_t)log_prior_dev & 7) != 0) return fail(h, CMPS_ERR_BAD_ARG, w + ": log_prior_dev must be 8-byte aligned");
-    if (((uintptr_t)decision_dev & 7) != 0) return fail(h, CMPS_ERR_BAD_ARG, w + ": decision_dev must be 8-byte aligned");
-    if (decision_dev) {
-        if (!std::isfinite(threshold) || !(threshold > 0.0) || threshold > 1.0)
-            return fail(h, CMPS_ERR_BAD_ARG, w + ": threshold must lie in (0, 1] where decision_dev is given");
-        if (first_step < 0 || first_step > 9223372036854775807ll - (long long)steps)
-            return fail(h, CMPS_ERR_BAD_ARG,
-                        w + ": need first_step >= 0 and first_step + steps below 2^63 (a step is a signed 64-bit integer)");
-    }
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    KBind kb(h);
-    KScope ks("k_bank_posterior", s);
-    const hipError_t e = launch_bank_posterior(nll_dev, M, n, steps, total_in_dev, log_prior_dev, inv_temp, total_out_dev, post_dev, best_dev,
-                                               conf_dev, threshold, first_step, reset, decision_dev, s);
-    if (e != hipSuccess) return fail_hip(h, e, "cmps_bank_posterior");
-    return CMPS_OK;
+    Args a{h, who};
+    a.ptr("nll_dev", nll_dev).members(M).min1("n", n).min1("steps", steps);
+    a.need(a.rc || (long long)M * (long long)n <= 2147483647ll / (long long)steps, "need M * n * steps <= 2^31 - 1")
+        .positive("inv_temp", inv_temp).align8("log_prior_dev", log_prior_dev).align8("decision_dev", decision_dev);
+    if (decision_dev)
+        a.need(std::isfinite(threshold) && threshold > 0.0 && threshold <= 1.0, "threshold must lie in (0, 1] where decision_dev is given")
+            .range63("first_step", first_step, "steps", steps, "a step");
+    if (a.rc) return a.rc;
+    return run_kernel(h, who, "k_bank_posterior", stream, [&](hipStream_t s) {
+        return launch_bank_posterior(nll_dev, M, n, steps, total_in_dev, log_prior_dev, inv_temp, total_out_dev, post_dev, best_dev, conf_dev,
+                                     threshold, first_step, reset, decision_dev, s);
+    });
 }
 
 int cmps_damped_sine_fill(cmps_handle_t h, unsigned long long seed, unsigned long long first_clip, int B, int T, double delta_t,
                           float* audio_dev, void* stream) {
+    const char* who = "cmps_damped_sine_fill";
     if (!h) return CMPS_ERR_BAD_ARG;
-    if (!audio_dev) return fail(h, CMPS_ERR_BAD_ARG, "cmps_damped_sine_fill: audio_dev is a null pointer");
-    if (B < 1 || T < 1 || T > (1 << 24))
-        return fail(h, CMPS_ERR_BAD_ARG, "cmps_damped_sine_fill: need B >= 1 and 1 <= T <= 2^24 (beyond that a sample index is not exact in float32)");
-    if (!std::isfinite(delta_t) || !(delta_t > 0.0)) return fail(h, CMPS_ERR_BAD_ARG, "cmps_damped_sine_fill: delta_t must be finite and positive");
-    if (first_clip + (unsigned long long)B < first_clip)
-        return fail(h, CMPS_ERR_BAD_ARG, "cmps_damped_sine_fill: first_clip + B overflows 64 bits");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    KBind kb(h);
-    KScope ks("k_damped_sine", s);
-    const hipError_t e = launch_damped_sine(seed, first_clip, B, T, delta_t, audio_dev, s);
-    if (e != hipSuccess) return fail_hip(h, e, "cmps_damped_sine_fill");
-    return CMPS_OK;
+    if (const int rc = Args{h, who}.ptr("audio_dev", audio_dev)
+                           .need(B >= 1 && T >= 1 && T <= (1 << 24), "need B >= 1 and 1 <= T <= 2^24 (beyond that a sample index is not exact in float32)")
+                           .positive("delta_t", delta_t)
+                           .need(first_clip + (unsigned long long)B >= first_clip, "first_clip + B overflows 64 bits").rc) return rc;
+    return run_kernel(h, who, "k_damped_sine", stream, [&](hipStream_t s) { return launch_damped_sine(seed, first_clip, B, T, delta_t, audio_dev, s); });
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -1169,13 +1160,11 @@ int cmps_legacy_set_params(cmps_handle_t h, const float* R_dev, const float* Q_r
                                       const_cast<float2*>(P.Q), const_cast<float2*>(P.QT), static_cast<hipStream_t>(stream));
     if (e == hipSuccess) e = launch_legacy_tables(P, const_cast<float2*>(P.psi0), const_cast<float*>(P.dtk), const_cast<float2*>(P.rho),
                                                   static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return fail_hip(h, e, "cmps_legacy_set_params");
+    if (e != hipSuccess) { unconfigure(h); return fail_hip(h, e, "cmps_legacy_set_params"); }
     h->L = L; h->P = P; h->ws = ws;
     h->tt_ws = nullptr;               // the time table of the PsiCMPS mode is no longer valid for this workspace
-    h->params_set = true;
-    h->legacy = true;
+    h->mode = MODE_LEGACY;
     h->bank_M = 0;
-    h->bank_rho = false;
     h->main.valid = false;
     h->rho_set = false;
     return CMPS_OK;
@@ -1184,8 +1173,8 @@ int cmps_legacy_set_params(cmps_handle_t h, const float* R_dev, const float* Q_r
 int cmps_legacy_loss_fwd(cmps_handle_t h, const float* audio_dev, int B, int T, float* loss_dev, int save_for_bwd,
                          void* stream) {
     if (!h) return CMPS_ERR_BAD_ARG;
-    if (const int rc = check_fwd(h, "cmps_legacy_loss_fwd", h->params_set && h->legacy, "cmps_legacy_set_params", audio_dev, loss_dev, B, T,
-                                 h->L.T, h->L.B, save_for_bwd, h->L.flags)) return rc;
+    if (const int rc = check_fwd(h, "cmps_legacy_loss_fwd", in(MODE_LEGACY), true, "cmps_legacy_set_params", audio_dev, loss_dev, B, T, h->L.T, h->L.B,
+                                 save_for_bwd, h->L.flags)) return rc;
     Dev P = h->P;
     P.B = B;
     // D <= 32: the pure-state wave kernels in LEGACY mode (cmps_wave2.hip, cmps_wave.hip); above: the wide kernels in LEGACY mode
@@ -1205,7 +1194,7 @@ int cmps_legacy_loss_fwd(cmps_handle_t h, const float* audio_dev, int B, int T, 
 
 int cmps_legacy_loss_bwd(cmps_handle_t h, const float* audio_dev, int B, int T, float* grad_dev, void* stream) {
     if (!h) return CMPS_ERR_BAD_ARG;
-    if (const int rc = check_bwd(h, "cmps_legacy_loss_bwd", h->params_set && h->legacy, "cmps_legacy_loss_fwd", h->main, audio_dev, grad_dev, B, T))
+    if (const int rc = check_bwd(h, "cmps_legacy_loss_bwd", in(MODE_LEGACY), true, "cmps_legacy_loss_fwd", h->main, audio_dev, grad_dev, B, T))
         return rc;
     Dev P = main_dev(h, B);
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -1241,8 +1230,7 @@ size_t cmps_rho_workspace_bytes(int D, int rank, int B, int T, int flags) {
 int cmps_rho_set_state(cmps_handle_t h, const float* phi_re_dev, const float* phi_im_dev, int rank, int T, int B_max,
                        int flags, void* rho_workspace_dev, size_t rho_workspace_bytes, void* stream) {
     if (!h) return CMPS_ERR_BAD_ARG;
-    if (const int rc = check_not_bank(h, "cmps_rho_set_state")) return rc;
-    if (!h->params_set || h->legacy) return fail(h, CMPS_ERR_STATE, "cmps_rho_set_state: call cmps_set_params first");
+    if (const int rc = need_plain(h, "cmps_rho_set_state", in(MODE_PSI), true, ": call cmps_set_params first")) return rc;
     if (!phi_re_dev || !phi_im_dev || rank < 1 || B_max < 1 || T < 2)
         return fail(h, CMPS_ERR_BAD_ARG, "cmps_rho_set_state: bad argument");
     if (T > h->L.T) return fail(h, CMPS_ERR_BAD_ARG, "cmps_rho_set_state: T exceeds T of cmps_set_params (the per-step tables)");
@@ -1267,13 +1255,14 @@ int cmps_rho_set_state(cmps_handle_t h, const float* phi_re_dev, const float* ph
     return CMPS_OK;
 }
 
-int cmps_rho_loss_fwd(cmps_handle_t h, const float* audio_dev, int B, int T, float* loss_dev, int save_for_bwd,
-                      void* stream) {
-    if (!h) return CMPS_ERR_BAD_ARG;
-    if (const int rc = check_fwd(h, "cmps_rho_loss_fwd", h->params_set && !h->legacy && h->rho_set, "cmps_rho_set_state (after cmps_set_params)",
-                                 audio_dev, loss_dev, B, T, h->rho_T, h->rho_B, save_for_bwd, h->rho_flags)) return rc;
+// cmps_rho_loss_fwd (M = 0) and cmps_rho_bank_loss_fwd (M members, n_audio batches) behind their argument checks.  A bank comes here under
+// the conditions of rho_bank_check_mode only, where the choice below is the wave family with the virtual-clip reverse sweep, never wide.
+static int rho_fwd_run(cmps_handle_t h, const char* who, int M, int n_audio, const float* audio_dev, int B, int T, float* loss_dev, int save_for_bwd,
+                       void* stream) {
     Dev P = h->P;
-    P.B = B; P.T = T; P.N = T - 1;
+    P.B = B; P.T = T; P.N = T - 1;                               // (a bank's rho workspace has the T of its tables: the values h->P holds)
+    const int Mk = M > 0 ? M : 1;
+    if (M > 0) bank_strides(P, n_audio, B, T);
     // D <= 32 (and rank <= 32): one wavefront per clip, unless the block variant was asked for -- the forward as row-array
     // GEMMs on the matrix cores (cmps_rho_mfma.hip); CMPS_VARIANT_WAVE32 keeps the column-by-column kernel (cross-check)
     const bool wave = h->D <= 32 && h->W.rank <= 32 && h->variant_req != CMPS_VARIANT_BLOCK;
@@ -1283,57 +1272,72 @@ int cmps_rho_loss_fwd(cmps_handle_t h, const float* audio_dev, int B, int T, flo
     // 32 < D <= 128, training forward (round 5): the columns as virtual clips of the wide kernels (cmps_wide.hip), when the rho workspace
     // has the sections for it (cmps_rho_workspace_bytes: CMPS_WS_TRAIN and the column vectors fit the LDS); else the general kernels
     const bool wide = h->D > 32 && h->W.vrank > 0 && save_for_bwd != 0 && h->variant_req != CMPS_VARIANT_BLOCK;
-    const bool f16 = rank1_f16(h->rank1_mode);
+    const bool save = save_for_bwd != 0, f16 = rank1_f16(h->rank1_mode);
     hipStream_t s = static_cast<hipStream_t>(stream);
     KBind kb(h);
     hipError_t e;
     if (wide) e = launch_fwd_rho_wide(P, h->W, audio_dev, loss_dev, f16, s);   // k_fwd_wide_rho, k_hy_wide, ... (scopes inside)
     else {
         KScope ks(mfma ? "k_fwd_rho_mfma" : wave ? "k_fwd_rho_wave" : "k_fwd_rho", s);
-        e = mfma ? launch_fwd_rho_mfma(P, h->W, audio_dev, loss_dev, save_for_bwd != 0, f16, !h->rho_virtual_bwd, s)
-          : wave ? launch_fwd_rho_wave(P, h->W, audio_dev, loss_dev, save_for_bwd != 0, s)
-                 : launch_fwd_rho(P, h->W, audio_dev, loss_dev, save_for_bwd != 0, s);
+        e = mfma ? launch_fwd_rho_mfma(P, h->W, audio_dev, loss_dev, save, f16, !h->rho_virtual_bwd, s, Mk)
+          : wave ? launch_fwd_rho_wave(P, h->W, audio_dev, loss_dev, save, s, Mk)
+                 : launch_fwd_rho(P, h->W, audio_dev, loss_dev, save, s);
     }
-    if (e != hipSuccess) return fail_hip(h, e, "cmps_rho_loss_fwd");
-    const bool save = save_for_bwd != 0;
+    if (e != hipSuccess) return fail_hip(h, e, who);
     h->rho = Saved{save, B, T - 1, audio_dev, loss_dev, wide ? RHO_STASH_WIDE : mfma ? RHO_STASH_MFMA : wave ? RHO_STASH_WAVE : RHO_STASH_BLOCK,
                    save, mfma && !h->rho_virtual_bwd};      // grad1: the forward's part of Rbar exists (k_bwd_rho_mfma needs it)
+    h->rho.M = M; h->rho.n_audio = M > 0 ? n_audio : 0;
+    return CMPS_OK;
+}
+
+int cmps_rho_loss_fwd(cmps_handle_t h, const float* audio_dev, int B, int T, float* loss_dev, int save_for_bwd,
+                      void* stream) {
+    if (!h) return CMPS_ERR_BAD_ARG;
+    if (const int rc = check_fwd(h, "cmps_rho_loss_fwd", in(MODE_PSI), h->rho_set, "cmps_rho_set_state (after cmps_set_params)", audio_dev, loss_dev, B, T,
+                                 h->rho_T, h->rho_B, save_for_bwd, h->rho_flags)) return rc;
+    return rho_fwd_run(h, "cmps_rho_loss_fwd", 0, 0, audio_dev, B, T, loss_dev, save_for_bwd, stream);
+}
+
+// cmps_rho_loss_bwd (M = 0) and cmps_rho_bank_loss_bwd behind their argument checks.  A saved bank forward wrote RHO_STASH_MFMA rows
+// (rank >= 3) and rho_bank_check_mode holds, so a bank takes the virtual-clip branch.
+static int rho_bwd_run(cmps_handle_t h, const char* who, int M, int n_audio, const float* audio_dev, int B, int T, float* grad_dev, void* stream) {
+    const auto failed = [&](hipError_t e, const char* stage) { return fail_hip(h, e, (std::string(who) + stage).c_str()); };
+    Dev P = h->P;
+    P.B = B; P.T = T; P.N = T - 1;
+    const RhoDev W = rho_dev(h);
+    if (M > 0) bank_strides(P, n_audio, B, T, 2 * (size_t)h->D * h->D + 3 * (size_t)h->D + 2 + 2 * (size_t)W.rank * h->D);
+    const int layout = h->rho.layout;
+    float* const loss = h->rho.loss;
+    // the reduction runs on the rho slabs (launch_bwd_rho_virtual_wave reads none of the three: it points its own copy at W.wslabs / W.wsums)
+    P.slabs = W.slabs; P.sums = W.sums; P.slab_floats = W.slab_floats;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    KBind kb(h);
+    if (layout == RHO_STASH_WIDE) {                                 // the wide kernels on virtual clips: reverse chain, GEMM, reduction, closing terms
+        const hipError_t ew = launch_bwd_rho_wide(P, W, loss, grad_dev, rank1_wide_pieces(h->rank1_mode), s);
+        return ew == hipSuccess ? CMPS_OK : failed(ew, " (wide)");
+    }
+    if (layout == RHO_STASH_MFMA && !h->rho_virtual_bwd && !h->rho.grad1)
+        return fail(h, CMPS_ERR_STATE, std::string(who) + ": CMPS_OPT_RHO_BWD changed between the forward and the reverse call");
+    if (layout == RHO_STASH_MFMA && h->rho_virtual_bwd) {
+        // the row-array forward's rows through the pure-state wave reverse scan, one virtual clip per column (cmps_rho_wave.hip)
+        const hipError_t ew = launch_bwd_rho_virtual_wave(P, W, audio_dev, loss, grad_dev, wave_rank1(h->rank1_mode), h->bwd_waves, s, M > 0 ? M : 1);
+        return ew == hipSuccess ? CMPS_OK : failed(ew, " (virtual clips)");
+    }
+    hipError_t e = layout == RHO_STASH_MFMA ? launch_bwd_rho_mfma(P, W, audio_dev, s)
+                 : layout == RHO_STASH_WAVE ? launch_bwd_rho_wave(P, W, audio_dev, s) : launch_bwd_rho(P, W, audio_dev, s);
+    if (e != hipSuccess) return failed(e, " (scan)");
+    P.abar_fix = layout == RHO_STASH_MFMA ? 1 : 0;   // the MFMA scan sums Re(u^dagger (Q + s R^dagger) ybar); k_finalize removes the Q part
+    e = launch_reduce_finalize(P, loss, grad_dev, s);
+    if (e == hipSuccess) e = launch_finalize_rho(P, W, grad_dev, s);
+    if (e != hipSuccess) return failed(e, " (reduce)");
     return CMPS_OK;
 }
 
 int cmps_rho_loss_bwd(cmps_handle_t h, const float* audio_dev, int B, int T, float* grad_dev, void* stream) {
     if (!h) return CMPS_ERR_BAD_ARG;
-    if (const int rc = check_bwd(h, "cmps_rho_loss_bwd", h->params_set && h->rho_set && h->rho.bwd_ok, "cmps_rho_loss_fwd", h->rho, audio_dev, grad_dev,
-                                 B, T)) return rc;
-    Dev P = h->P;
-    P.B = B; P.T = T; P.N = T - 1;
-    const RhoDev W = rho_dev(h);
-    const int layout = h->rho.layout;
-    float* const loss = h->rho.loss;
-    P.slabs = W.slabs; P.sums = W.sums; P.slab_floats = W.slab_floats;   // the reduction runs on the rho slabs
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    KBind kb(h);
-    if (layout == RHO_STASH_WIDE) {                                 // the wide kernels on virtual clips: reverse chain, GEMM, reduction, closing terms
-        const hipError_t ew = launch_bwd_rho_wide(P, W, loss, grad_dev, rank1_wide_pieces(h->rank1_mode), s);
-        if (ew != hipSuccess) return fail_hip(h, ew, "cmps_rho_loss_bwd (wide)");
-        return CMPS_OK;
-    }
-    if (layout == RHO_STASH_MFMA && !h->rho_virtual_bwd && !h->rho.grad1)
-        return fail(h, CMPS_ERR_STATE, "cmps_rho_loss_bwd: CMPS_OPT_RHO_BWD changed between the forward and the reverse call");
-    if (layout == RHO_STASH_MFMA && h->rho_virtual_bwd) {
-        // the row-array forward's rows through the pure-state wave reverse scan, one virtual clip per column (cmps_rho_wave.hip)
-        const hipError_t ew = launch_bwd_rho_virtual_wave(P, W, audio_dev, loss, grad_dev, wave_rank1(h->rank1_mode), h->bwd_waves, s);
-        if (ew != hipSuccess) return fail_hip(h, ew, "cmps_rho_loss_bwd (virtual clips)");
-        return CMPS_OK;
-    }
-    hipError_t e = layout == RHO_STASH_MFMA ? launch_bwd_rho_mfma(P, W, audio_dev, s)
-                 : layout == RHO_STASH_WAVE ? launch_bwd_rho_wave(P, W, audio_dev, s) : launch_bwd_rho(P, W, audio_dev, s);
-    if (e != hipSuccess) return fail_hip(h, e, "cmps_rho_loss_bwd (scan)");
-    P.abar_fix = layout == RHO_STASH_MFMA ? 1 : 0;   // the MFMA scan sums Re(u^dagger (Q + s R^dagger) ybar); k_finalize removes the Q part
-    e = launch_reduce_finalize(P, loss, grad_dev, s);
-    if (e == hipSuccess) e = launch_finalize_rho(P, W, grad_dev, s);
-    if (e != hipSuccess) return fail_hip(h, e, "cmps_rho_loss_bwd (reduce)");
-    return CMPS_OK;
+    if (const int rc = check_bwd(h, "cmps_rho_loss_bwd", in(MODE_PSI), h->rho_set && h->rho.bwd_ok, "cmps_rho_loss_fwd", h->rho, audio_dev, grad_dev, B, T))
+        return rc;
+    return rho_bwd_run(h, "cmps_rho_loss_bwd", 0, 0, audio_dev, B, T, grad_dev, stream);
 }
 
 // ---- model bank of RhoCMPS members (include/cmps.h): the kernel set a plain handle picks at D <= 32, 3 <= rank <= 32 ----
@@ -1379,15 +1383,14 @@ int cmps_rho_bank_set_state_dev(cmps_handle_t h, int M, const float* params_dev,
     const int rflags = flags & ~(CMPS_WS_FRESH | CMPS_WS_REUSE_TABLES);
     const RhoLayout RL = make_rho_layout(h->D, rank, B_max, T, rflags);
     // every member's tables (the main layout without its training sections), the size and alignment checks of the whole workspace
-    if (const int rc = set_params_packed(h, params_dev, sigma, delta_t, T, B_max, flags & ~CMPS_WS_TRAIN, workspace_dev, workspace_bytes, stream, M,
-                                         RL.total)) return rc;
+    if (const int rc = set_params_packed(h, params_dev, sigma, delta_t, T, B_max, flags & ~CMPS_WS_TRAIN, workspace_dev, workspace_bytes, stream,
+                                         MODE_RHO_BANK, M, RL.total)) return rc;
     // member 0's rho sections lie behind its main layout; rho_bank_view / bank_view / bank_view_phi move them by the one stride
     const RhoDev W = bind_rho_workspace(h->D, RL, h->ws + h->L.total, rflags, B_max);
     const hipError_t e = launch_pack_phi(h->P, W, phi_dev, phi_dev + (size_t)rank * h->D, static_cast<hipStream_t>(stream), M);
-    if (e != hipSuccess) { h->params_set = false; return fail_hip(h, e, who); }
+    if (e != hipSuccess) { unconfigure(h); return fail_hip(h, e, who); }
     h->RL = RL; h->W = W;
     h->rho_B = B_max; h->rho_T = T; h->rho_flags = rflags;
-    h->bank_rho = true;
     h->rho.valid = h->rho.bwd_ok = false;
     return CMPS_OK;
 }
@@ -1395,48 +1398,21 @@ int cmps_rho_bank_set_state_dev(cmps_handle_t h, int M, const float* params_dev,
 int cmps_rho_bank_loss_fwd(cmps_handle_t h, const float* audio_dev, int n_audio, int B, int T, float* loss_dev, int save_for_bwd, void* stream) {
     const char* who = "cmps_rho_bank_loss_fwd";
     if (!h) return CMPS_ERR_BAD_ARG;
-    const bool ready = h->params_set && h->bank_M > 0 && h->bank_rho;
-    if (ready) if (const int rc = rho_bank_check_mode(h, who, h->W.rank)) return rc;
-    if (const int rc = check_fwd(h, who, ready, "cmps_rho_bank_set_state_dev", audio_dev, loss_dev, B, T, h->rho_T, h->rho_B, save_for_bwd,
-                                 h->rho_flags)) return rc;
-    const int M = h->bank_M;
-    if (n_audio != 1 && n_audio != M) return fail(h, CMPS_ERR_BAD_ARG, std::string(who) + ": n_audio must be 1 (one shared batch) or M");
-    Dev P = h->P;
-    P.B = B;
-    bank_strides(P, n_audio, B, T);
-    const bool save = save_for_bwd != 0;
-    const bool mfma = h->W.rank > (save ? 2 : 8);                  // as cmps_rho_loss_fwd chooses with the virtual-clip reverse sweep
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    KBind kb(h);
-    hipError_t e;
-    {
-        KScope ks(mfma ? "k_fwd_rho_mfma" : "k_fwd_rho_wave", s);
-        e = mfma ? launch_fwd_rho_mfma(P, h->W, audio_dev, loss_dev, save, rank1_f16(h->rank1_mode), false, s, M)
-                 : launch_fwd_rho_wave(P, h->W, audio_dev, loss_dev, save, s, M);
-    }
-    if (e != hipSuccess) return fail_hip(h, e, who);
-    h->rho = Saved{save, B, T - 1, audio_dev, loss_dev, mfma ? RHO_STASH_MFMA : RHO_STASH_WAVE, save, false};
-    h->rho.M = M; h->rho.n_audio = n_audio;
-    return CMPS_OK;
+    if (h->mode == MODE_RHO_BANK) if (const int rc = rho_bank_check_mode(h, who, h->W.rank)) return rc;
+    if (const int rc = check_fwd(h, who, in(MODE_RHO_BANK), true, "cmps_rho_bank_set_state_dev", audio_dev, loss_dev, B, T, h->rho_T, h->rho_B,
+                                 save_for_bwd, h->rho_flags)) return rc;
+    if (n_audio != 1 && n_audio != h->bank_M) return fail(h, CMPS_ERR_BAD_ARG, std::string(who) + ": n_audio must be 1 (one shared batch) or M");
+    return rho_fwd_run(h, who, h->bank_M, n_audio, audio_dev, B, T, loss_dev, save_for_bwd, stream);
 }
 
 int cmps_rho_bank_loss_bwd(cmps_handle_t h, const float* audio_dev, int n_audio, int B, int T, float* grad_dev, void* stream) {
     const char* who = "cmps_rho_bank_loss_bwd";
     if (!h) return CMPS_ERR_BAD_ARG;
-    const bool ready = h->params_set && h->bank_M > 0 && h->bank_rho && h->rho.bwd_ok && h->rho.M == h->bank_M;
-    if (ready) if (const int rc = rho_bank_check_mode(h, who, h->W.rank)) return rc;
-    if (const int rc = check_bwd(h, who, ready, "cmps_rho_bank_loss_fwd", h->rho, audio_dev, grad_dev, B, T)) return rc;
+    const bool saved = h->rho.bwd_ok && h->rho.M == h->bank_M;     // (the options are judged only where a reverse pass could run)
+    if (h->mode == MODE_RHO_BANK && saved) if (const int rc = rho_bank_check_mode(h, who, h->W.rank)) return rc;
+    if (const int rc = check_bwd(h, who, in(MODE_RHO_BANK), saved, "cmps_rho_bank_loss_fwd", h->rho, audio_dev, grad_dev, B, T)) return rc;
     if (n_audio != h->rho.n_audio) return fail(h, CMPS_ERR_STATE, std::string(who) + ": n_audio differs from the forward call");
-    const int M = h->bank_M, rank = h->W.rank;
-    Dev P = h->P;
-    P.B = B;
-    bank_strides(P, n_audio, B, T, 2 * (size_t)h->D * h->D + 3 * (size_t)h->D + 2 + 2 * (size_t)rank * h->D);
-    KBind kb(h);
-    // (a saved bank forward wrote RHO_STASH_MFMA rows: rank >= 3)
-    const hipError_t e = launch_bwd_rho_virtual_wave(P, rho_dev(h), audio_dev, h->rho.loss, grad_dev, wave_rank1(h->rank1_mode), h->bwd_waves,
-                                                     static_cast<hipStream_t>(stream), M);
-    if (e != hipSuccess) return fail_hip(h, e, (std::string(who) + " (virtual clips)").c_str());
-    return CMPS_OK;
+    return rho_bwd_run(h, who, h->bank_M, n_audio, audio_dev, B, T, grad_dev, stream);
 }
 
 size_t cmps_rho_bank_apply_step_scratch_bytes(int D, int rank, int M) {
@@ -1466,8 +1442,7 @@ int cmps_rho_bank_apply_step(cmps_handle_t h, int M, float* vars_dev, float* ada
 int cmps_rho_update_ancilla(cmps_handle_t h, const float* rho_in_dev, const float* signal_dev, float t, int B,
                             float* rho_out_dev, void* stream) {
     if (!h) return CMPS_ERR_BAD_ARG;
-    if (const int rc = check_not_bank(h, "cmps_rho_update_ancilla")) return rc;
-    if (!h->params_set || h->legacy) return fail(h, CMPS_ERR_STATE, "cmps_rho_update_ancilla: call cmps_set_params first");
+    if (const int rc = need_plain(h, "cmps_rho_update_ancilla", in(MODE_PSI), true, ": call cmps_set_params first")) return rc;
     if (!rho_in_dev || !signal_dev || !rho_out_dev || B < 1 || rho_in_dev == rho_out_dev)
         return fail(h, CMPS_ERR_BAD_ARG, "cmps_rho_update_ancilla: bad argument");
     hipError_t e = launch_update_ancilla_rho(h->P, rho_in_dev, signal_dev, t, B, rho_out_dev, static_cast<hipStream_t>(stream));
@@ -1516,8 +1491,7 @@ static int rho_sample_run(cmps_handle_t h, const char* who, const SampleDev& S, 
 int cmps_rho_sample(cmps_handle_t h, const float* noise_dev, int n, int length, float* out_dev, int save_states,
                     void* stream) {
     if (!h) return CMPS_ERR_BAD_ARG;
-    if (!h->params_set || h->legacy || !h->rho_set)
-        return fail(h, CMPS_ERR_STATE, "cmps_rho_sample: call cmps_set_params and cmps_rho_set_state first");
+    if (const int rc = need_mode(h, "cmps_rho_sample", in(MODE_PSI), h->rho_set, ": call cmps_set_params and cmps_rho_set_state first")) return rc;
     if (!noise_dev || !out_dev || n < 1 || length < 1) return fail(h, CMPS_ERR_BAD_ARG, "cmps_rho_sample: bad argument");
     if (length > h->L.N) return fail(h, CMPS_ERR_BAD_ARG, "cmps_rho_sample: length exceeds T - 1 of cmps_set_params");
     return rho_sample_run(h, "cmps_rho_sample", SampleDev{noise_dev, n, length, out_dev, PrimeDev{}, nullptr, nullptr}, save_states, stream);
@@ -1526,23 +1500,23 @@ int cmps_rho_sample(cmps_handle_t h, const float* noise_dev, int n, int length, 
 int cmps_rho_sample_primed(cmps_handle_t h, const float* prime_dev, int n_prime, int prime_T, const float* noise_dev, int n, int length,
                            float* out_dev, float* pred_dev, int save_states, void* stream) {
     if (!h) return CMPS_ERR_BAD_ARG;
-    if (!h->params_set || h->legacy || !h->rho_set)
-        return fail(h, CMPS_ERR_STATE, "cmps_rho_sample_primed: call cmps_set_params and cmps_rho_set_state first (not available in legacy mode)");
+    if (const int rc = need_mode(h, "cmps_rho_sample_primed", in(MODE_PSI), h->rho_set,
+                                 ": call cmps_set_params and cmps_rho_set_state first (not available in legacy mode)")) return rc;
     SampleDev S;
     if (int c = primed_args(h, "cmps_rho_sample_primed", prime_dev, n_prime, prime_T, noise_dev, n, length, out_dev, pred_dev, S)) return c;
     return rho_sample_run(h, "cmps_rho_sample_primed", S, save_states, stream);
 }
 
 size_t cmps_rho_stream_state_bytes(cmps_handle_t h, int n) {
-    if (!h || n < 1 || !h->rho_set) return 0;
+    if (!h || n < 1 || h->mode != MODE_PSI || !h->rho_set) return 0;
     return (size_t)n * rho_stream_rec_floats(h) * sizeof(float);
 }
 
 int cmps_rho_stream(cmps_handle_t h, const void* state_in_dev, void* state_out_dev, int k0, const float* audio_dev, int n_audio, int forced,
                     const float* noise_dev, int length, int n, float* out_dev, float* pred_dev, int save_states, void* stream) {
     if (!h) return CMPS_ERR_BAD_ARG;
-    if (!h->params_set || h->legacy || !h->rho_set)
-        return fail(h, CMPS_ERR_STATE, "cmps_rho_stream: call cmps_set_params and cmps_rho_set_state first (not available in legacy mode)");
+    if (const int rc = need_mode(h, "cmps_rho_stream", in(MODE_PSI), h->rho_set,
+                                 ": call cmps_set_params and cmps_rho_set_state first (not available in legacy mode)")) return rc;
     StreamCall C;
     if (int c = stream_args(h, "cmps_rho_stream", state_in_dev, state_out_dev, k0, audio_dev, n_audio, forced, noise_dev, n, length, n, out_dev, pred_dev,
                             rho_stream_rec_floats(h), plain_rows, MemberDev{}, C))
@@ -1553,8 +1527,8 @@ int cmps_rho_stream(cmps_handle_t h, const void* state_in_dev, void* state_out_d
 int cmps_rho_stream_score(cmps_handle_t h, const void* state_in_dev, void* state_out_dev, int k0, const float* audio_dev, int n_audio, int forced,
                           int n, float* nll_dev, float* loss_dev, float* pred_dev, int save_states, void* stream) {
     if (!h) return CMPS_ERR_BAD_ARG;
-    if (!h->params_set || h->legacy || !h->rho_set)
-        return fail(h, CMPS_ERR_STATE, "cmps_rho_stream_score: call cmps_set_params and cmps_rho_set_state first (not available in legacy mode)");
+    if (const int rc = need_mode(h, "cmps_rho_stream_score", in(MODE_PSI), h->rho_set,
+                                 ": call cmps_set_params and cmps_rho_set_state first (not available in legacy mode)")) return rc;
     StreamCall C;
     if (int c = score_args(h, "cmps_rho_stream_score", state_in_dev, state_out_dev, k0, audio_dev, n_audio, forced, n, nll_dev, loss_dev, pred_dev,
                            rho_stream_rec_floats(h), "path", plain_rows, MemberDev{}, C))
@@ -1563,16 +1537,15 @@ int cmps_rho_stream_score(cmps_handle_t h, const void* state_in_dev, void* state
 }
 
 // ---- a RhoCMPS bank's streams: k_sample_rho_mfma's STREAM / SCORE instances with the members as a second grid dimension (include/cmps.h) ----
-static bool rho_bank_mode(const cmps_handle_s* h) { return h->params_set && !h->legacy && h->bank_M > 0 && h->bank_rho; }
 // What cmps_rho_bank_stream and cmps_rho_bank_stream_score refuse before they look at their arguments
 static int rho_bank_stream_check_mode(cmps_handle_t h, const char* who) {
-    if (!rho_bank_mode(h)) return fail(h, CMPS_ERR_STATE, std::string(who) + ": needs a RhoCMPS bank (call cmps_rho_bank_set_state_dev first)");
+    if (const int rc = need_mode(h, who, in(MODE_RHO_BANK), true, ": needs a RhoCMPS bank (call cmps_rho_bank_set_state_dev first)")) return rc;
     if (const int rc = rho_bank_check_mode(h, who, h->W.rank)) return rc;        // (a variant or an option set behind cmps_rho_bank_set_state_dev)
     return CMPS_OK;
 }
 
 size_t cmps_rho_bank_stream_state_bytes(cmps_handle_t h, int n) {
-    if (!h || n < 1 || !rho_bank_mode(h)) return 0;
+    if (!h || n < 1 || h->mode != MODE_RHO_BANK) return 0;
     return (size_t)h->bank_M * (size_t)n * stream_rec_rho_mfma(h->W.rank) * sizeof(float);
 }
 
@@ -1605,8 +1578,8 @@ int cmps_rho_bank_stream_score(cmps_handle_t h, const void* state_in_dev, void* 
 
 int cmps_rho_states(cmps_handle_t h, int B, int steps, float* rho_out_dev, float* purity_out_dev, void* stream) {
     if (!h) return CMPS_ERR_BAD_ARG;
-    if (!h->params_set || !h->rho_set || !h->rho.valid)
-        return fail(h, CMPS_ERR_STATE, "cmps_rho_states: needs cmps_rho_loss_fwd(save_for_bwd=1) or cmps_rho_sample(save_states=1) first");
+    if (const int rc = need_mode(h, "cmps_rho_states", in(MODE_PSI), h->rho_set && h->rho.valid,
+                                 ": needs cmps_rho_loss_fwd(save_for_bwd=1) or cmps_rho_sample(save_states=1) first")) return rc;
     if (B != h->rho.B || steps != h->rho.steps || (!rho_out_dev && !purity_out_dev))
         return fail(h, CMPS_ERR_BAD_ARG, "cmps_rho_states: bad argument");
     Dev P = h->P;

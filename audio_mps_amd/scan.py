@@ -38,6 +38,29 @@ class NoisePlan(NamedTuple):
     std: float
 
 
+def _is_tensor(t, device, dtype, shape, rows: bool = False) -> bool:
+    """The one argument check of the backend: ``t`` is a tensor of ``dtype`` on ``device`` (None: on any CUDA device) of the rank
+    ``shape`` (an int) or the shape ``shape`` (a tuple, None for any extent), and contiguous -- or, with ``rows``, a matrix whose rows
+    are contiguous (a row stride of its own is allowed)."""
+    if not (isinstance(t, torch.Tensor) and t.dtype == dtype and (t.is_cuda if device is None else t.device == device)):
+        return False
+    if isinstance(shape, int):
+        shape = (None,) * shape
+    if t.dim() != len(shape) or any(want is not None and want != have for want, have in zip(shape, t.shape)):
+        return False
+    if rows:
+        return t.dim() == 2 and t.stride(1) == 1 and (t.shape[0] == 1 or t.stride(0) >= t.shape[1])
+    return t.is_contiguous()
+
+
+def _read_record(record: torch.Tensor, dtype: np.dtype, head: Optional[str] = None):
+    """The one device -> host copy of a record: (its scalar fields -- those of the field ``head``, if given -- as Python numbers, the
+    numpy record)."""
+    rec = record.cpu().numpy().view(dtype)[0]
+    scalars = rec if head is None else rec[head]
+    return {k: (float(scalars[k]) if scalars.dtype[k].kind == "f" else int(scalars[k])) for k in scalars.dtype.names}, rec
+
+
 def _ptr(t: Optional[torch.Tensor]):
     """The address of a device tensor as an entry takes it: NULL for None and for a tensor without elements."""
     return t.data_ptr() if t is not None and t.numel() else None
@@ -288,8 +311,7 @@ class HipScan:
 
     def bank_set_params_dev(self, params: torch.Tensor, sigma: float, delta_t: float, B: int, T: int, train: bool = True):
         """cmps_bank_set_params_dev: ``params`` [M, 2 D^2 + 3 D + 1], the buffer bank_apply_step wrote; every member's tables are rebuilt."""
-        if not (params.is_cuda and params.dtype == torch.float32 and params.dim() == 2 and params.shape[1] == self._n_params + 1
-                and params.is_contiguous()):
+        if not _is_tensor(params, None, torch.float32, (None, self._n_params + 1)):
             raise ValueError("params must be a contiguous float32 CUDA tensor [M, 2 D^2 + 3 D + 1]")
         M = int(params.shape[0])
         ws = self._main_workspace(("bank", M, B, T, train),
@@ -307,8 +329,7 @@ class HipScan:
 
     def _bank_audio(self, M: int, audio: torch.Tensor):
         """A bank's batch [B, T] (shared) or [M, B, T] -> (n_audio, B, T) as the scan entries take them."""
-        if not (isinstance(audio, torch.Tensor) and audio.is_cuda and audio.dtype == torch.float32 and audio.dim() in (2, 3)
-                and audio.is_contiguous()):
+        if not (_is_tensor(audio, None, torch.float32, 2) or _is_tensor(audio, None, torch.float32, 3)):
             raise ValueError("audio must be a contiguous float32 CUDA tensor [B, T] (shared) or [M, B, T]")
         n_audio = 1 if audio.dim() == 2 else int(audio.shape[0])
         B, T = audio.shape[-2:]
@@ -350,7 +371,7 @@ class HipScan:
 
     @staticmethod
     def _check_hyper(hyper: torch.Tensor, M: int):
-        if not (hyper.is_cuda and hyper.dtype == torch.float64 and tuple(hyper.shape) == (M, 5) and hyper.is_contiguous()):
+        if not _is_tensor(hyper, None, torch.float64, (M, 5)):
             raise ValueError("hyper must be a contiguous float64 CUDA tensor [M, 5]")
 
     def bank_forward(self, audio: torch.Tensor, save_for_bwd: bool = False) -> torch.Tensor:
@@ -365,8 +386,7 @@ class HipScan:
             return self._bank_backward("bank", self._lib.cmps_bank_loss_bwd)
         saved = self._bank.saved if self._bank.kind == "bank" else None
         M, B = (self._bank.M, int(saved[0].shape[-2])) if saved is not None else (-1, -1)
-        if not (isinstance(weights, torch.Tensor) and weights.device == self.device and weights.dtype == torch.float32 and weights.dim() == 2
-                and weights.stride(1) == 1 and (weights.shape[0] == 1 or weights.stride(0) >= weights.shape[1])):
+        if not _is_tensor(weights, self.device, torch.float32, 2, rows=True):
             raise ValueError("bank_backward: weights must be a float32 tensor [M, B] with contiguous rows on the backend's device")
         if saved is not None and tuple(weights.shape) != (M, B):
             raise ValueError(f"bank_backward: weights of shape {tuple(weights.shape)} do not fit the forward's losses [{M}, {B}]")
@@ -402,11 +422,10 @@ class HipScan:
                                train: bool = True):
         """cmps_rho_bank_set_state_dev: ``params`` [M, 2 D^2 + 3 D + 1] and ``phi`` [M, 2 rank D], the buffers rho_bank_apply_step wrote."""
         rank = int(rank)
-        if not (params.is_cuda and params.dtype == torch.float32 and params.dim() == 2 and params.shape[1] == self._n_params + 1
-                and params.is_contiguous()):
+        if not _is_tensor(params, None, torch.float32, (None, self._n_params + 1)):
             raise ValueError("params must be a contiguous float32 CUDA tensor [M, 2 D^2 + 3 D + 1]")
         M = int(params.shape[0])
-        if not (phi.is_cuda and phi.dtype == torch.float32 and tuple(phi.shape) == (M, 2 * rank * self.D) and phi.is_contiguous()):
+        if not _is_tensor(phi, None, torch.float32, (M, 2 * rank * self.D)):
             raise ValueError("phi must be a contiguous float32 CUDA tensor [M, 2 rank D]")
         ws = self._main_workspace(("rho_bank", M, rank, B, T, train), lambda: (self.rho_bank_workspace_bytes(rank, M, B, T, train),
                                                                                 f"a RhoCMPS bank: D={self.D}, rank={rank}, M={M}, B={B}, T={T}"))
@@ -438,8 +457,7 @@ class HipScan:
                               beta2, eps, hyper, with_reg, (params, phi, losses))
 
     def _check_audio(self, audio: torch.Tensor):
-        if not (isinstance(audio, torch.Tensor) and audio.is_cuda and audio.dtype == torch.float32
-                and audio.dim() == 2 and audio.is_contiguous()):
+        if not _is_tensor(audio, None, torch.float32, 2):
             raise ValueError("audio must be a contiguous float32 CUDA tensor [B, T]")
         B, T = audio.shape
         if T != self._T or B > self._B:
@@ -567,12 +585,10 @@ class HipScan:
         default all zero) int32 [B], all contiguous on this device; returns float32 [B, T] (T defaults to L) with row b =
         data[index[b], offset[b] : offset[b] + T] -- or T quiet NaNs where index[b] or offset[b] is out of range.  No host copy, no
         synchronisation.  ``data`` int16 [N, L] goes to cmps_batch_gather_i16 instead: row b = float32(data[...]) * ``scale``."""
-        def ok(t, dtype, dim):
-            return isinstance(t, torch.Tensor) and t.device == self.device and t.dtype == dtype and t.dim() == dim and t.is_contiguous()
         i16 = isinstance(data, torch.Tensor) and data.dtype == torch.int16
-        if not ok(data, torch.int16 if i16 else torch.float32, 2):
+        if not _is_tensor(data, self.device, torch.int16 if i16 else torch.float32, 2):
             raise ValueError("gather_batch: data must be a contiguous float32 or int16 tensor [N, L] on the backend's device")
-        if not ok(index, torch.int32, 1) or (offset is not None and (not ok(offset, torch.int32, 1) or offset.shape != index.shape)):
+        if not _is_tensor(index, self.device, torch.int32, 1) or (offset is not None and not _is_tensor(offset, self.device, torch.int32, tuple(index.shape))):
             raise ValueError("gather_batch: index (and offset) must be contiguous int32 tensors [B] on the backend's device")
         N, L = int(data.shape[0]), int(data.shape[1])
         B, T = int(index.shape[0]), L if T is None else int(T)
@@ -592,23 +608,25 @@ class HipScan:
         """cmps_loss_stats: fold the per-clip losses ``loss`` [B] (float32, on this device; clip ids first_id .. first_id + B - 1) into the
         64-byte record ``stats`` (a uint8 device tensor this method allocates -- and resets -- when None) and return it.  No host copy, no
         synchronisation: read_stats is the download."""
-        if not (isinstance(loss, torch.Tensor) and loss.device == self.device and loss.dtype == torch.float32 and loss.dim() == 1
-                and loss.is_contiguous() and loss.numel() >= 1):
+        if not (_is_tensor(loss, self.device, torch.float32, 1) and loss.numel() >= 1):
             raise ValueError("loss_stats: loss must be a contiguous float32 tensor [B], B >= 1, on the backend's device")
-        if stats is None:
-            stats, reset = torch.empty(64, dtype=torch.uint8, device=self.device), True
-        elif not (isinstance(stats, torch.Tensor) and stats.device == self.device and stats.dtype == torch.uint8 and stats.numel() == 64
-                  and stats.is_contiguous()):
-            raise ValueError("loss_stats: stats must be a contiguous uint8 tensor of 64 bytes on the backend's device")
+        stats, reset = self._record(stats, 64, reset, "loss_stats: stats")
         _capi.check(self._h, self._lib.cmps_loss_stats(self._h, loss.data_ptr(), int(loss.numel()), int(first_id), 1 if reset else 0,
                                                        stats.data_ptr(), self._stream()))
         return stats
 
+    def _record(self, record: Optional[torch.Tensor], nbytes: int, reset: bool, what: str):
+        """A device record of ``nbytes`` bytes and whether the entry resets it: a new one (reset), or the caller's, checked."""
+        if record is None:
+            return torch.empty(nbytes, dtype=torch.uint8, device=self.device), True
+        if not _is_tensor(record, self.device, torch.uint8, (nbytes,)):
+            raise ValueError(f"{what} must be a contiguous uint8 tensor of {nbytes} bytes on the backend's device")
+        return record, reset
+
     @staticmethod
     def read_stats(stats: torch.Tensor) -> dict:
         """The record of loss_stats as a dict of Python numbers (_capi.LOSS_STATS's fields): the one device -> host copy of an evaluation."""
-        rec = stats.cpu().numpy().view(_capi.LOSS_STATS)[0]
-        return {k: (float(rec[k]) if _capi.LOSS_STATS[k].kind == "f" else int(rec[k])) for k in _capi.LOSS_STATS.names}
+        return _read_record(stats, _capi.LOSS_STATS)[0]
 
     def classify_stats(self, loss: torch.Tensor, labels: Optional[torch.Tensor], first_id: int, stats: Optional[torch.Tensor] = None,
                        reset: bool = False, best: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -617,24 +635,18 @@ class HipScan:
         tensor of cmps_bank_classify_stats_bytes(M) bytes this method allocates -- and resets -- when None), which it returns.
         ``labels``: int32 [B] on this device, the member each clip belongs to (outside [0, M): unlabelled), or None for no labels;
         ``best``: int32 [B] to receive each clip's decision.  No host copy, no synchronisation: read_classify_stats is the download."""
-        def on_dev(t, dtype, dim):
-            return isinstance(t, torch.Tensor) and t.device == self.device and t.dtype == dtype and t.dim() == dim
-        if not (on_dev(loss, torch.float32, 2) and loss.shape[0] >= 1 and loss.shape[1] >= 1 and loss.stride(1) == 1
-                and (loss.shape[0] == 1 or loss.stride(0) >= loss.shape[1])):
+        if not (_is_tensor(loss, self.device, torch.float32, 2, rows=True) and loss.numel() >= 1):
             raise ValueError("classify_stats: loss must be a float32 tensor [M, B] with contiguous rows, M >= 1 and B >= 1, on the backend's "
                              "device")
         M, B = int(loss.shape[0]), int(loss.shape[1])
         ld = int(loss.stride(0)) if M > 1 else B
         for name, t in (("labels", labels), ("best", best)):
-            if t is not None and not (on_dev(t, torch.int32, 1) and t.is_contiguous() and int(t.numel()) == B):
+            if t is not None and not _is_tensor(t, self.device, torch.int32, (B,)):
                 raise ValueError(f"classify_stats: {name} must be a contiguous int32 tensor [B] on the backend's device")
         nbytes = int(self._lib.cmps_bank_classify_stats_bytes(M))
         if nbytes == 0:
             raise ValueError(f"classify_stats: a record holds 1 .. {_capi.CLASSIFY_MAX_M} members, not {M}")
-        if stats is None:
-            stats, reset = torch.empty(nbytes, dtype=torch.uint8, device=self.device), True
-        elif not (on_dev(stats, torch.uint8, 1) and stats.numel() == nbytes and stats.is_contiguous()):
-            raise ValueError(f"classify_stats: stats must be a contiguous uint8 tensor of {nbytes} bytes on the backend's device")
+        stats, reset = self._record(stats, nbytes, reset, "classify_stats: stats")
         _capi.check(self._h, self._lib.cmps_bank_classify_stats(
             self._h, loss.data_ptr(), M, B, ld, labels.data_ptr() if labels is not None else None, int(first_id), 1 if reset else 0,
             stats.data_ptr(), best.data_ptr() if best is not None else None, self._stream()))
@@ -644,9 +656,7 @@ class HipScan:
     def read_classify_stats(stats: torch.Tensor, M: int) -> dict:
         """The record of classify_stats: the header's fields as Python numbers (_capi.CLASSIFY_HEAD), ``confusion`` [M, M] and
         ``unlabelled_best`` [M] as int64 arrays.  The one device -> host copy of a classifier evaluation."""
-        rec = stats.cpu().numpy().view(_capi.classify_stats_dtype(M))[0]
-        head = _capi.CLASSIFY_HEAD
-        out = {k: (float(rec["head"][k]) if head[k].kind == "f" else int(rec["head"][k])) for k in head.names}
+        out, rec = _read_record(stats, _capi.classify_stats_dtype(M), "head")
         out["confusion"], out["unlabelled_best"] = rec["confusion"].copy(), rec["unlabelled_best"].copy()
         return out
 
@@ -656,28 +666,19 @@ class HipScan:
         [B] on this device) into the cotangents of the cross-entropy objective of include/cmps.h, ``weights`` [M, B] (float32, rows
         contiguous; allocated when None), and fold the batch into the 40-byte ``record`` (uint8 on this device; allocated -- and reset --
         when None).  Returns (weights, record).  No host copy, no synchronisation: read_classify_weights_record is the download."""
-        def on_dev(t, dtype, dim):
-            return isinstance(t, torch.Tensor) and t.device == self.device and t.dtype == dtype and t.dim() == dim
-
-        def rows(t):
-            return on_dev(t, torch.float32, 2) and t.shape[0] >= 1 and t.shape[1] >= 1 and t.stride(1) == 1 and (
-                t.shape[0] == 1 or t.stride(0) >= t.shape[1])
-        if not rows(loss):
+        if not (_is_tensor(loss, self.device, torch.float32, 2, rows=True) and loss.numel() >= 1):
             raise ValueError("classify_weights: loss must be a float32 tensor [M, B] with contiguous rows, M >= 1 and B >= 1, on the "
                              "backend's device")
         M, B = int(loss.shape[0]), int(loss.shape[1])
         if not 1 <= M <= _capi.CLASSIFY_MAX_M:
             raise ValueError(f"classify_weights: a bank holds 1 .. {_capi.CLASSIFY_MAX_M} members, not {M}")
-        if not (on_dev(labels, torch.int32, 1) and labels.is_contiguous() and int(labels.numel()) == B):
+        if not _is_tensor(labels, self.device, torch.int32, (B,)):
             raise ValueError("classify_weights: labels must be a contiguous int32 tensor [B] on the backend's device")
         if weights is None:
             weights = torch.empty((M, B), dtype=torch.float32, device=self.device)
-        elif not (rows(weights) and tuple(weights.shape) == (M, B)):
+        elif not _is_tensor(weights, self.device, torch.float32, (M, B), rows=True):
             raise ValueError("classify_weights: weights must be a float32 tensor [M, B] with contiguous rows on the backend's device")
-        if record is None:
-            record, reset = torch.empty(_capi.CLASSIFY_WEIGHTS_REC.itemsize, dtype=torch.uint8, device=self.device), True
-        elif not (on_dev(record, torch.uint8, 1) and record.numel() == _capi.CLASSIFY_WEIGHTS_REC.itemsize and record.is_contiguous()):
-            raise ValueError("classify_weights: record must be a contiguous uint8 tensor of 40 bytes on the backend's device")
+        record, reset = self._record(record, _capi.CLASSIFY_WEIGHTS_REC.itemsize, reset, "classify_weights: record")
         _capi.check(self._h, self._lib.cmps_bank_classify_weights(
             self._h, loss.data_ptr(), M, B, int(loss.stride(0)) if M > 1 else B, labels.data_ptr(), float(inv_temp), float(gen_weight),
             float(disc_weight), 1 if reset else 0, weights.data_ptr(), int(weights.stride(0)) if M > 1 else B, record.data_ptr(),
@@ -687,9 +688,7 @@ class HipScan:
     @staticmethod
     def read_classify_weights_record(record: torch.Tensor) -> dict:
         """The record of classify_weights as a dict of Python numbers (_capi.CLASSIFY_WEIGHTS_REC's fields): one 40-byte download."""
-        dt = _capi.CLASSIFY_WEIGHTS_REC
-        rec = record.cpu().numpy().view(dt)[0]
-        return {k: (float(rec[k]) if dt[k].kind == "f" else int(rec[k])) for k in dt.names}
+        return _read_record(record, _capi.CLASSIFY_WEIGHTS_REC)[0]
 
     def log_prior_tensor(self, log_prior) -> Optional[torch.Tensor]:
         """A log prior [M] (finite or -inf) as `bank_posterior` takes it: float64 on this device.  None stays None (a uniform prior)."""
@@ -708,22 +707,18 @@ class HipScan:
         None, "decision": the records (new memory, continued from ``decision``) or None}, all on the device; "pack" is the one uint8
         tensor the small results are views of, in the order and sizes of "pack_sizes" (records, total, best, conf).  No host copy, no
         synchronisation."""
-        def on_dev(t, dtype, shape):
-            return isinstance(t, torch.Tensor) and t.is_cuda and t.device == self.device and t.dtype == dtype and t.is_contiguous() \
-                and tuple(t.shape) == shape
-
-        if not (isinstance(nll, torch.Tensor) and nll.dim() == 3 and on_dev(nll, torch.float32, tuple(nll.shape)) and nll.numel() >= 1):
+        if not (_is_tensor(nll, self.device, torch.float32, 3) and nll.numel() >= 1):
             raise ValueError("bank_posterior: nll must be a contiguous float32 tensor [M, n, steps] with M, n, steps >= 1 on the backend's device")
         M, n, steps = (int(x) for x in nll.shape)
         if M > _capi.CLASSIFY_MAX_M:
             raise ValueError(f"bank_posterior: a bank holds 1 .. {_capi.CLASSIFY_MAX_M} members, not {M}")
-        if total_in is not None and not on_dev(total_in, torch.float32, (M, n)):
+        if total_in is not None and not _is_tensor(total_in, self.device, torch.float32, (M, n)):
             raise ValueError(f"bank_posterior: total_in must be a contiguous float32 tensor [{M}, {n}] on the backend's device")
-        if log_prior is not None and not on_dev(log_prior, torch.float64, (M,)):
+        if log_prior is not None and not _is_tensor(log_prior, self.device, torch.float64, (M,)):
             raise ValueError(f"bank_posterior: log_prior must be a contiguous float64 tensor [{M}] on the backend's device")
         if threshold is None and decision is not None:
             raise ValueError("bank_posterior: decision records need a threshold")
-        if decision is not None and not on_dev(decision, torch.uint8, (16 * n,)):
+        if decision is not None and not _is_tensor(decision, self.device, torch.uint8, (16 * n,)):
             raise ValueError(f"bank_posterior: decision must be a contiguous uint8 tensor of {16 * n} bytes on the backend's device")
         # one allocation for everything small, so that a caller who wants it on the host downloads once: records | total | best | conf
         sizes = (16 * n if threshold is not None else 0, 4 * M * n, 4 * n * steps, 4 * n * steps)
@@ -760,7 +755,7 @@ class HipScan:
                 raise ValueError("a NoisePlan needs length and n: there is no array to take them from")
             d_noise = self.draw_noise(noise.seed, noise.first_step, n, length, noise.std)
         elif isinstance(noise, torch.Tensor):
-            if not (noise.is_cuda and noise.dtype == torch.float32 and noise.dim() == 2 and noise.is_contiguous()):
+            if not _is_tensor(noise, None, torch.float32, 2):
                 raise ValueError("device noise must be a contiguous float32 CUDA tensor [n, length]")
             d_noise = noise
         else:
@@ -855,7 +850,7 @@ class HipScan:
         if loss is None:
             return torch.zeros(shape, dtype=torch.float32, device=self.device)
         if isinstance(loss, torch.Tensor):                             # (already there: the entry updates it in place)
-            if not (loss.device == self.device and loss.dtype == torch.float32 and loss.is_contiguous() and tuple(loss.shape) == shape):
+            if not _is_tensor(loss, self.device, torch.float32, shape):
                 raise ValueError(f"loss must be {list(shape)}")
             return loss
         loss = np.array(loss, dtype=np.float32, order="C")
