@@ -61,6 +61,7 @@ SYMBOLS = (
     "cmps_rho_update_ancilla", "cmps_rho_sample", "cmps_rho_sample_primed", "cmps_rho_stream_state_bytes", "cmps_rho_stream", "cmps_rho_stream_score", "cmps_rho_states",
     "cmps_rho_apply_step_scratch_bytes", "cmps_rho_apply_step", "cmps_noise_fill", "cmps_batch_gather", "cmps_batch_gather_i16", "cmps_loss_stats", "cmps_damped_sine_fill", "cmps_crc32c",
     "cmps_bank_classify_stats_bytes", "cmps_bank_classify_stats", "cmps_bank_classify_weights", "cmps_bank_posterior", "cmps_bank_loss_bwd_weighted",
+    "cmps_bank_calibrate_scratch_bytes", "cmps_bank_calibrate",
     "cmps_bank_workspace_bytes", "cmps_bank_set_params_dev", "cmps_bank_loss_fwd", "cmps_bank_loss_bwd", "cmps_bank_apply_step_scratch_bytes",
     "cmps_bank_apply_step", "cmps_bank_grad_status", "cmps_bank_stream_state_bytes", "cmps_bank_stream", "cmps_bank_stream_score",
     "cmps_rho_bank_workspace_bytes", "cmps_rho_bank_set_state_dev", "cmps_rho_bank_loss_fwd", "cmps_rho_bank_loss_bwd",
@@ -89,6 +90,15 @@ assert CLASSIFY_WEIGHTS_REC.itemsize == 40
 # the 16-byte decision record of cmps_bank_posterior (include/cmps.h: cmps_bank_decision), little-endian, one per path
 DECISION_REC = np.dtype([("step", "<i8"), ("member", "<i4"), ("reserved", "<i4")])
 assert DECISION_REC.itemsize == 16
+
+# cmps_bank_calibrate: the bits of `fit`, the record's flags and its 80 bytes (include/cmps.h: cmps_bank_calibrate_rec), little-endian
+CMPS_CALIB_TEMPERATURE = 1
+CMPS_CALIB_PRIOR = 2
+CALIB_CONVERGED, CALIB_AT_KAPPA_MIN, CALIB_AT_KAPPA_MAX, CALIB_NO_DATA, CALIB_MAX_ITER = 1, 2, 4, 8, 16
+CALIB_REC = np.dtype([("xent_start", "<f8"), ("xent_end", "<f8"), ("g_logk", "<f8"), ("resid_prior", "<f8"), ("curvature", "<f8"),
+                      ("n_used", "<i8"), ("n_unlabelled", "<i8"), ("n_own_absent", "<i8"), ("passes", "<i4"), ("flags", "<i4"),
+                      ("n_unfitted", "<i4"), ("reserved", "<i4")])
+assert CALIB_REC.itemsize == 80
 
 
 def classify_stats_dtype(M: int) -> np.dtype:
@@ -209,6 +219,11 @@ def _declare(lib):
     lib.cmps_bank_posterior.argtypes = [vp, vp, c_int, c_int, c_int, vp, vp, c_double, vp, vp, vp, vp, c_double, ctypes.c_longlong, c_int, vp,
                                         vp]
     lib.cmps_bank_posterior.restype = c_int
+    lib.cmps_bank_calibrate_scratch_bytes.argtypes = [c_int, ctypes.c_longlong]
+    lib.cmps_bank_calibrate_scratch_bytes.restype = c_size_t
+    lib.cmps_bank_calibrate.argtypes = [vp, vp, c_int, ctypes.c_longlong, ctypes.c_longlong, vp, c_int, c_int, c_double, c_double, c_double,
+                                        vp, vp, vp, c_size_t, vp]
+    lib.cmps_bank_calibrate.restype = c_int
     lib.cmps_bank_loss_bwd_weighted.argtypes = [vp, vp, c_int, c_int, c_int, vp, ctypes.c_longlong, vp, vp]
     lib.cmps_bank_loss_bwd_weighted.restype = c_int
     lib.cmps_damped_sine_fill.argtypes = [vp, ctypes.c_ulonglong, ctypes.c_ulonglong, c_int, c_int, c_double, vp, vp]

@@ -25,7 +25,7 @@ from __future__ import annotations
 import json
 import math
 import os
-from dataclasses import replace
+from dataclasses import dataclass, fields, replace
 from typing import List, Optional, Sequence
 
 import numpy as np
@@ -36,6 +36,59 @@ from .resident import ResidentState
 from .train import Trainer
 
 MEMBER_KEYS = ("seed", "learning_rate", "h_reg", "r_reg")
+CALIBRATION_FITS = {"temperature": 1, "prior": 2, "both": 3}        # cmps_bank_calibrate's `fit` bits
+CALIBRATION_KEYS = ("temperature", "log_prior", "fit", "dataset", "clips", "T", "xent_before", "xent_after")     # bank.json's "calibration"
+
+
+@dataclass
+class CalibrationResult:
+    """A temperature and a prior fitted on held-out clips (BankTrainer.calibrate), from theta and the record of cmps_bank_calibrate."""
+    temperature: float             # 1 / kappa
+    prior: np.ndarray              # float64 [M]: exp(log_prior - logsumexp(log_prior))
+    log_prior: np.ndarray          # float64 [M]: c as the device left it (never shifted there)
+    xent_before: float             # the held-out cross-entropy at the start values
+    xent_after: float              # ... and at the returned ones: never above xent_before
+    converged: bool
+    at_bound: bool                 # the temperature sits on kappa_min or kappa_max, with the gradient pushing outwards
+    unfitted: list                 # the classes without a used held-out clip: their prior kept its start value
+    passes: int
+    n_used: int
+    n_unlabelled: int
+    n_own_absent: int
+    T: int                         # a temperature fitted on whole clips of T samples belongs to that T
+    fit: str = "temperature"
+
+    def line(self) -> str:
+        return (f"temperature={self.temperature:.6g} xent_before={self.xent_before:.6g} xent_after={self.xent_after:.6g} "
+                f"converged={self.converged} passes={self.passes} unfitted={len(self.unfitted)}")
+
+    def scalars(self) -> dict:
+        out = {f.name: getattr(self, f.name) for f in fields(self) if f.name not in ("prior", "log_prior")}
+        out["prior"], out["log_prior"] = [float(p) for p in self.prior], log_prior_json(self.log_prior)
+        return out
+
+    def meta(self, dataset: Optional[str] = None) -> dict:
+        """What bank.json keeps under "calibration"."""
+        return {"temperature": float(self.temperature), "log_prior": log_prior_json(self.log_prior), "fit": self.fit, "dataset": dataset,
+                "clips": int(self.n_used), "T": int(self.T), "xent_before": float(self.xent_before), "xent_after": float(self.xent_after)}
+
+
+def log_prior_json(log_prior) -> list:
+    """A log prior as bank.json and a JSON line hold it: floats, and null for -inf (a prior of zero), which JSON has no number for."""
+    return [None if c == -math.inf else float(c) for c in np.asarray(log_prior, dtype=np.float64)]
+
+
+def log_prior_array(values) -> np.ndarray:
+    """`log_prior_json` read back (an array passes through): float64 [M] with -inf for null."""
+    return np.array([-math.inf if c is None else float(c) for c in values], dtype=np.float64)
+
+
+def normalised_prior(log_prior) -> np.ndarray:
+    """exp(c - logsumexp c) of a log prior whose entries are finite or -inf (null: -inf)."""
+    c = log_prior_array(log_prior)
+    top = np.max(c)
+    w = np.exp(c - top)
+    return w / np.sum(w)
 
 
 class PsiBank:
@@ -211,6 +264,7 @@ class BankTrainer(ResidentState):
                          for model, hp in zip(bank.models, bank.member_hparams)]
         self.global_step = 0
         self.objective = None         # a dict the caller sets for a run that is not generative (train --bank_objective): kept in bank.json
+        self.calibration = None       # a dict (CALIBRATION_KEYS) once `calibrate` ran or `restore` found one: kept in bank.json
         self.last = None            # the last synchronised step's per-member losses: {"model_loss": [M], "total_loss": [M]}
         self._resident([(tr.model, tr.opt) for tr in self.trainers], bank.bond_d, self.rank)
 
@@ -403,6 +457,116 @@ class BankTrainer(ResidentState):
             raise ValueError("evaluate_classifier: the dataset yielded no batch")
         return ClassifierResult.from_stats(be.read_classify_stats(stats, M), self.bank.classes, T, best.cpu().numpy() if keep_best else None)
 
+    def _heldout_losses(self, dataset, minibatch_size, T, who):
+        """`evaluate_classifier`'s ordered pass with every batch's [M][B] losses kept side by side on the device: (loss [M, N], labels
+        [N] int32, the labels on the host, T).  Forward scans only: no optimiser state, no Adam step and no random stream is touched."""
+        import torch
+        from .evaluate import pass_shape
+        be = self.bank.backend
+        if self.bank.classes is None:
+            raise ValueError(f"{who} needs a class bank (PsiBank / RhoBank(..., classes=))")
+        if not (hasattr(be, "bank_calibrate") and hasattr(be, "read_calibrate_record")):
+            raise ValueError(f"{who} needs a backend that fits on the device (bank_calibrate): {type(be).__name__} has none")
+        if dataset.labels is None:
+            raise ValueError(f"{who}: the dataset has no labels")
+        mb, T, B_max = pass_shape(be, dataset, minibatch_size, self.bank.hparams.minibatch_size, T)
+        M = len(self.trainers)
+        if self.native:
+            self._configure(self._device_state(), B_max, T, False)
+            forward = lambda batch: self._forward(batch, save_for_bwd=False)                        # noqa: E731
+        else:
+            def forward(batch):
+                rows = [tr.model._forward_entry(tr.model._prepare(B_max, T, train=False))(batch, save_for_bwd=False).clone() for tr in self.trainers]
+                return torch.stack(rows)
+        host_labels = dataset.class_positions(self.bank.classes)
+        labels = torch.from_numpy(host_labels).to(dataset.clips.device)
+        kept = None
+        for first_id, batch in dataset.ordered(mb, T):
+            loss = forward(batch)
+            if kept is None:
+                kept = torch.empty((M, int(dataset.n_clips)), dtype=torch.float32, device=loss.device)
+            kept[:, first_id:first_id + int(loss.shape[1])].copy_(loss)                             # device to device
+        if kept is None:
+            raise ValueError(f"{who}: the dataset yielded no batch")
+        return kept, labels, host_labels, T
+
+    def _start_prior(self, prior, who):
+        """``prior``: None (uniform), "empirical" (the bank's class counts) or [M] probabilities -> the log prior [M] (finite or -inf)."""
+        M = len(self.trainers)
+        if prior is None:
+            return np.zeros(M, dtype=np.float64)
+        if isinstance(prior, str):
+            if prior != "empirical":
+                raise ValueError(f"{who}: prior is None, 'empirical' or {M} probabilities, not {prior!r}")
+            prior = getattr(self.bank, "class_counts", None)
+            if prior is None:
+                raise ValueError(f"{who}: prior='empirical' needs the bank's class counts (a bank trained by class)")
+        p = np.asarray(prior, dtype=np.float64).reshape(-1)
+        if p.shape != (M,) or not np.all(np.isfinite(p)) or np.any(p < 0.0) or not np.sum(p) > 0.0:
+            raise ValueError(f"{who}: prior must be {M} finite probabilities, none negative and not all zero")
+        with np.errstate(divide="ignore"):
+            return np.log(p / np.sum(p))
+
+    def calibrate(self, dataset, minibatch_size: Optional[int] = None, T: Optional[int] = None, fit: str = "temperature",
+                  temperature: float = 1.0, prior=None, tol: float = 1e-9, max_iter: int = 200, kappa_min: float = 1e-6,
+                  kappa_max: float = 1e6) -> CalibrationResult:
+        """Fit the temperature and (or) the prior of p_m ~ prior_m exp(-loss_m / temperature) on every labelled clip of ``dataset`` (a
+        ResidentDataset of HELD-OUT clips): `evaluate_classifier`'s ordered pass with the [M][B] losses of every batch copied into one
+        resident [M][N] tensor, then ONE cmps_bank_calibrate call and ONE download (a second one, of the own members' losses, only where a class
+        lost its last clip to a non-finite loss and ``unfitted`` has to name it).  ``fit``: "temperature", "prior" or "both";
+        ``temperature`` and ``prior`` (None: uniform, "empirical": the class counts, or [M] probabilities) are the start.  The result is
+        kept in ``self.calibration`` (and by ``save`` in bank.json).  Like `evaluate_classifier` it runs forward scans only: the training
+        steps after it are bit for bit those of a run without it."""
+        if fit not in CALIBRATION_FITS:
+            raise ValueError(f"calibrate: fit is one of {', '.join(CALIBRATION_FITS)}, not {fit!r}")
+        res = self._calibrate(dataset, minibatch_size, T, CALIBRATION_FITS[fit], fit, temperature, prior, tol, max_iter, kappa_min, kappa_max,
+                              "calibrate")
+        self.calibration = res.meta()
+        return res
+
+    def cross_entropy(self, dataset, temperature: float = 1.0, prior=None, minibatch_size: Optional[int] = None, T: Optional[int] = None,
+                      log_prior=None) -> float:
+        """The held-out cross-entropy of the bank under a GIVEN temperature and prior: `calibrate`'s pass and cmps_bank_calibrate with
+        zero iterations (cmps_bank_classify_stats knows temperature 1 and the uniform prior only).  ``log_prior`` ([M], finite or -inf)
+        instead of ``prior`` is taken as it is: a saved calibration's."""
+        if log_prior is not None:
+            if prior is not None:
+                raise ValueError("cross_entropy: give prior or log_prior, not both")
+            log_prior = log_prior_array(log_prior).reshape(-1)
+            if log_prior.shape != (len(self.trainers),) or np.any(np.isnan(log_prior)) or np.any(log_prior == np.inf):
+                raise ValueError(f"cross_entropy: log_prior must be {len(self.trainers)} values, each finite or -inf")
+        return self._calibrate(dataset, minibatch_size, T, 0, "none", temperature, prior, 1e-9, 0, 1e-6, 1e6, "cross_entropy",
+                               log_prior).xent_before
+
+    def _calibrate(self, dataset, minibatch_size, T, fit_bits, fit, temperature, prior, tol, max_iter, kappa_min, kappa_max, who,
+                   log_prior=None):
+        import torch
+        if not (math.isfinite(temperature) and temperature > 0.0):
+            raise ValueError(f"{who}: temperature must be finite and positive")
+        c0 = self._start_prior(prior, who) if log_prior is None else log_prior
+        loss, labels, host_labels, T = self._heldout_losses(dataset, minibatch_size, T, who)
+        known = host_labels >= 0
+        counts = np.bincount(host_labels[known], minlength=len(self.trainers))
+        if np.any((counts > 0) & (np.asarray(c0) == -math.inf)):     # its clips would have probability zero: the cross-entropy is +inf
+            zero = [self.bank.classes[m] for m in range(len(counts)) if counts[m] > 0 and c0[m] == -math.inf]
+            raise ValueError(f"{who}: the prior is zero for {zero}, of which the dataset holds clips")
+        be, M = self.bank.backend, len(self.trainers)
+        theta, rec = be.read_calibrate_record(be.bank_calibrate(loss, labels, fit_bits, 1.0 / float(temperature), c0, tol, max_iter, kappa_min,
+                                                                kappa_max))
+        if rec["flags"] & 8:
+            raise ValueError(f"{who}: no clip of the dataset carries a label of the bank's classes with a finite loss under its own member "
+                             f"({rec['n_unlabelled']} unlabelled, {rec['n_own_absent']} with the own member absent)")
+        # the classes without a used clip, from the labels the host holds; where a class lost its last clip to a non-finite loss of its
+        # own member (the device counted more unfitted members than the labels show) the own losses come down too, a second download
+        if rec["n_own_absent"] and int(np.sum(counts == 0)) != rec["n_unfitted"]:     # a class lost its last clip to a non-finite loss: look
+            own = loss[labels.clamp(min=0).to(torch.int64), torch.arange(loss.shape[1], device=loss.device)].cpu().numpy()
+            counts = np.bincount(host_labels[known & np.isfinite(own)], minlength=M)
+        unfitted = [self.bank.classes[m] for m in range(M) if counts[m] == 0]
+        return CalibrationResult(temperature=1.0 / float(theta[0]), prior=normalised_prior(theta[1:]), log_prior=theta[1:].copy(),
+                                 xent_before=rec["xent_start"], xent_after=rec["xent_end"], converged=bool(rec["flags"] & 1),
+                                 at_bound=bool(rec["flags"] & 6), unfitted=unfitted, passes=rec["passes"], n_used=rec["n_used"],
+                                 n_unlabelled=rec["n_unlabelled"], n_own_absent=rec["n_own_absent"], T=int(T), fit=fit)
+
     # -- checkpoints: model.<m>.ckpt.npz in the format of Trainer.save, bank.json with the members' overrides -----------
     @staticmethod
     def member_path(directory: str, m: int) -> str:
@@ -422,6 +586,8 @@ class BankTrainer(ResidentState):
             meta["class_counts"] = [int(c) for c in self.bank.class_counts]
         if self.objective is not None:        # (and of a generatively trained one)
             meta["objective"] = self.objective
+        if self.calibration is not None:      # (and of a bank nobody calibrated)
+            meta["calibration"] = self.calibration
         tmp = os.path.join(directory, "bank.json.tmp")
         with open(tmp, "w") as f:
             json.dump(meta, f)
@@ -444,6 +610,7 @@ class BankTrainer(ResidentState):
             if not tr.restore(self.member_path(directory, m)):
                 raise FileNotFoundError(self.member_path(directory, m))
         self.global_step = int(meta["global_step"])
+        self.calibration = meta.get("calibration")
         return True
 
 

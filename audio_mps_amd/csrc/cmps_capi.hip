@@ -1125,6 +1125,47 @@ int cmps_bank_posterior(cmps_handle_t h, const float* nll_dev, int M, int n, int
     });
 }
 
+// The [M][N] losses of a held-out set fitted for the temperature and the prior: needs nothing of the handle either.  max_iter + 1 pairs of
+// launches go out without a look at the device; the pairs behind the one that finishes leave at their first branch
+size_t cmps_bank_calibrate_scratch_bytes(int M, long long N) {
+    if (M < 1 || M > CLASSIFY_MAX_M || N < 1 || N > (1ll << 62) / (long long)M) return 0;
+    return calib_scratch_bytes(M, N);
+}
+
+int cmps_bank_calibrate(cmps_handle_t h, const float* loss_dev, int M, long long N, long long ld, const int* label_dev, int fit, int max_iter,
+                        double tol, double kappa_min, double kappa_max, double* theta_dev, void* record_dev, void* scratch_dev,
+                        size_t scratch_bytes, void* stream) {
+    const char* who = "cmps_bank_calibrate";
+    if (!h) return CMPS_ERR_BAD_ARG;
+    Args a{h, who};
+    a.ptr("loss_dev", loss_dev).ptr("label_dev", label_dev).ptr("theta_dev", theta_dev).align8("theta_dev", theta_dev)
+        .ptr("record_dev", record_dev).align8("record_dev", record_dev).ptr("scratch_dev", scratch_dev).align8("scratch_dev", scratch_dev)
+        .members(M);
+    a.need(a.rc || (N >= 1 && ld <= (1ll << 62) / (long long)M), "need N >= 1 and M * ld <= 2^62")
+        .need(ld >= N, "ld must be at least N")
+        .need(fit >= 0 && fit <= 3, "fit is a set of CMPS_CALIB_TEMPERATURE | CMPS_CALIB_PRIOR: 0 .. 3")
+        .need(max_iter >= 0 && max_iter <= 10000, "need 0 <= max_iter <= 10000")
+        .positive("tol", tol).positive("kappa_min", kappa_min)
+        .need(std::isfinite(kappa_max) && kappa_max >= kappa_min, "kappa_max must be finite and at least kappa_min");
+    a.need(a.rc || scratch_bytes >= calib_scratch_bytes(M, N), "scratch_bytes is below cmps_bank_calibrate_scratch_bytes(M, N)");
+    if (a.rc) return a.rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    KBind kb(h);
+    for (int i = 0; i <= max_iter; ++i) {
+        hipError_t e;
+        {
+            KScope ks("k_calib_pass", s);
+            e = launch_calib_pass(loss_dev, M, N, ld, label_dev, theta_dev, scratch_dev, i == 0, s);
+        }
+        if (e == hipSuccess) {
+            KScope ks("k_calib_update", s);
+            e = launch_calib_update(theta_dev, record_dev, scratch_dev, M, N, fit, max_iter, tol, kappa_min, kappa_max, i == 0, s);
+        }
+        if (e != hipSuccess) return fail_hip(h, e, who);
+    }
+    return CMPS_OK;
+}
+
 int cmps_damped_sine_fill(cmps_handle_t h, unsigned long long seed, unsigned long long first_clip, int B, int T, double delta_t,
                           float* audio_dev, void* stream) {
     const char* who = "cmps_damped_sine_fill";

@@ -12,7 +12,8 @@
 // reads it in a few microseconds, and more of them would need the second pass or the atomics this kernel does without.
 // k_classify_stats (cmps_bank_classify_stats), further down: the [M][B] losses of a bank of one model per class judged as a classifier.
 // k_classify_weights (cmps_bank_classify_weights), behind it: the same losses turned into the per-clip, per-member cotangents of a cross-entropy step.
-// k_bank_posterior (cmps_bank_posterior), last: the per-step losses of a scored bank stream folded into a posterior over the members after every step.
+// k_bank_posterior (cmps_bank_posterior), behind that: the per-step losses of a scored bank stream folded into a posterior over the members after every step.
+// k_calib_pass, k_calib_update (cmps_bank_calibrate), last: the [M][N] losses of a held-out set fitted for the temperature and the prior.
 #include "cmps_internal.h"
 
 namespace cmps {
@@ -453,7 +454,334 @@ __global__ __launch_bounds__(POST_NT) void k_bank_posterior(const float* __restr
 
 inline size_t posterior_lds_bytes(int M, int C) { return (size_t)M * (sizeof(double) + sizeof(float) * (size_t)(C + 1)); }
 
+// k_calib_pass, k_calib_update (cmps_bank_calibrate): the temperature and the prior of a class bank fitted on the [M][N] losses of a held-out
+// set where they lie (include/cmps.h states the model, the objective and the contract; tests/_calib_ref.py restates them).  One iteration
+// is two launches, so an iteration boundary is a kernel boundary and no workgroup ever waits for another:
+//   k_calib_pass    G = calib_groups(N) workgroups of ONE wave; workgroup w takes the tiles w, w + G, ... of CALIB_TILE consecutive clips,
+//                   thread t clip t of the tile, and walks the M losses of its clip (loss[m * ld + b]: the lanes read consecutive floats):
+//                   smallest present loss; smallest a; S and the two moments; then, CALIB_TILE members at a time, p_m into a tile in LDS
+//                   that thread j walks for member j in clip order and adds to the workgroup's q[m].  J, g, h and the three counts go
+//                   through a binary tree in LDS; n_m is an integer count (LDS integer adds: no order to depend on).  The workgroup's sums
+//                   go to its own row of the scratch buffer.
+//   k_calib_update  ONE workgroup: adds the G rows in row order (thread per quantity, thread per member), takes the maximum residual through
+//                   a tree, and thread 0 decides: converged, out of iterations, a kappa step or a prior sweep.  The state of the solver
+//                   (CalibState), the best theta seen and a `done` word live at the head of the scratch buffer.
+// The entry enqueues max_iter + 1 such pairs without looking; once `done` is set every later launch leaves at its first branch.  The
+// assignment of clips to threads and every order of summation are fixed: the same call gives the same bits on every run.
+constexpr int CALIB_TILE = 64;         // clips of a tile = threads of a pass workgroup = members of a p-tile
+constexpr int CALIB_MAX_G = 1024;      // workgroups of a pass, at most: the update kernel adds that many rows per quantity
+constexpr int CALIB_UPD_NT = 256;
+constexpr int CALIB_UPD_ROWS = CLASSIFY_MAX_M / CALIB_UPD_NT;
+constexpr int CALIB_ROW_HEAD = 8;      // 8-byte words of a row before q[M] and n_m[M]: J, g, h sums, n_used, n_unlabelled, n_own_absent, 2 spare
+
+struct alignas(8) CalibRec {           // the record of include/cmps.h (cmps_bank_calibrate_rec), field for field
+    double xent_start, xent_end, g_logk, resid_prior, curvature;
+    long long n_used, n_unlabelled, n_own_absent;
+    int passes, flags, n_unfitted, reserved;
+};
+static_assert(sizeof(CalibRec) == 80, "the record of cmps_bank_calibrate is 80 bytes");
+
+struct alignas(8) CalibState {         // the head of the scratch buffer: what one update launch leaves for the next
+    int done, iter, last, lo_known, hi_known, have_best, spare0, spare1;
+    double lo, hi;                     // the sign bracket of g in kappa: g(lo) < 0 < g(hi) where the end is known, else the box's end
+    double best_J, best_g, best_h, best_resid, xent_start;
+    double spare[5];
+};
+static_assert(sizeof(CalibState) == 128, "the solver state is 128 bytes");
+constexpr int CALIB_STEP_KAPPA = 1, CALIB_STEP_PRIOR = 2;                                      // CalibState::last
+constexpr int CALIB_DO_SAVE = 1, CALIB_DO_SWEEP = 2, CALIB_DO_RESTORE = 4;                      // what thread 0 asks of the workgroup
+constexpr int CALIB_CONVERGED = 1, CALIB_AT_MIN = 2, CALIB_AT_MAX = 4, CALIB_NO_DATA = 8, CALIB_MAX_ITER = 16;
+
+__host__ __device__ inline int calib_groups(long long N) {
+    const long long tiles = (N + CALIB_TILE - 1) / CALIB_TILE;
+    return (int)(tiles < CALIB_MAX_G ? tiles : CALIB_MAX_G);
+}
+// scratch: CalibState | best theta [1 + M] | rows [G][CALIB_ROW_HEAD + 2 M], everything in 8-byte words
+__host__ __device__ inline size_t calib_row_words(int M) { return (size_t)CALIB_ROW_HEAD + 2 * (size_t)M; }
+
+// grid G
+__global__ __launch_bounds__(CALIB_TILE) void k_calib_pass(const float* __restrict__ loss, int M, long long N, long long ld,
+                                                           const int* __restrict__ label, const double* __restrict__ theta,
+                                                           unsigned char* __restrict__ scratch, int first) {
+    if (!first && reinterpret_cast<const CalibState*>(scratch)->done) return;
+    __shared__ double ptile[CALIB_TILE][CALIB_TILE + 1];
+    __shared__ double qacc[CLASSIFY_MAX_M];
+    __shared__ unsigned long long cnt[CLASSIFY_MAX_M];
+    __shared__ double red[3][CALIB_TILE];
+    __shared__ long long redn[3][CALIB_TILE];
+    const int tid = threadIdx.x;
+    const double kappa = theta[0];
+    const double* c = theta + 1;
+    const double inf = __longlong_as_double(0x7ff0000000000000ll);
+    for (int m = tid; m < M; m += CALIB_TILE) { qacc[m] = 0.0; cnt[m] = 0ull; }
+    __syncthreads();
+    double sJ = 0.0, sg = 0.0, sh = 0.0;
+    long long n_used = 0, n_unl = 0, n_abs = 0;
+    const long long tiles = (N + CALIB_TILE - 1) / CALIB_TILE;
+    for (long long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        const long long b = tile * CALIB_TILE + tid;
+        const float* col = loss + b;
+        bool used = false;
+        int y = -1;
+        float l1 = 0.f;
+        double amin = 0.0, inv_S = 0.0;
+        if (b < N) {
+            y = label[b];
+            const bool labelled = y >= 0 && y < M;
+            const float xl = labelled ? col[(long long)y * ld] : 0.f;
+            if (!labelled) n_unl += 1;
+            else if (!is_finite_f32(xl)) n_abs += 1;
+            else {
+                used = true;
+                l1 = xl;                                                                      // smallest present loss (the own one is present)
+#pragma unroll 8
+                for (int m = 0; m < M; ++m) {
+                    const float x = col[(long long)m * ld];
+                    if (is_finite_f32(x) && x < l1) l1 = x;
+                }
+                amin = inf;
+#pragma unroll 4
+                for (int m = 0; m < M; ++m) {
+                    const float x = col[(long long)m * ld];
+                    if (is_finite_f32(x)) {
+                        const double a = kappa * ((double)x - (double)l1) - c[m];
+                        if (a < amin) amin = a;
+                    }
+                }
+                double S = 0.0, S1 = 0.0, S2 = 0.0;                                           // in member order
+#pragma unroll 4
+                for (int m = 0; m < M; ++m) {
+                    const float x = col[(long long)m * ld];
+                    if (is_finite_f32(x)) {
+                        const double d = (double)x - (double)l1;
+                        const double e = exp(-((kappa * d - c[m]) - amin));
+                        S += e;
+                        S1 += e * d;
+                        S2 += e * (d * d);
+                    }
+                }
+                inv_S = 1.0 / S;
+                const double dy = (double)xl - (double)l1;
+                const double E = S1 * inv_S;
+                sJ += ((kappa * dy - c[y]) - amin) + log(S);
+                sg += dy - E;
+                sh += S2 * inv_S - E * E;
+                n_used += 1;
+                atomicAdd(cnt + y, 1ull);
+            }
+        }
+        for (int m0 = 0; m0 < M; m0 += CALIB_TILE) {                                          // (uniform: every thread meets the barriers)
+            const int len = M - m0 < CALIB_TILE ? M - m0 : CALIB_TILE;
+            for (int j = 0; j < len; ++j) {
+                double p = 0.0;
+                if (used) {
+                    const float x = col[(long long)(m0 + j) * ld];
+                    if (is_finite_f32(x)) p = exp(-((kappa * ((double)x - (double)l1) - c[m0 + j]) - amin)) * inv_S;
+                }
+                ptile[j][tid] = p;
+            }
+            __syncthreads();
+            if (tid < len) {
+                double s = 0.0;
+#pragma unroll 8
+                for (int i = 0; i < CALIB_TILE; ++i) s += ptile[tid][i];                      // in clip order
+                qacc[m0 + tid] += s;                                                          // in tile order
+            }
+            __syncthreads();
+        }
+    }
+    red[0][tid] = sJ, red[1][tid] = sg, red[2][tid] = sh;
+    redn[0][tid] = n_used, redn[1][tid] = n_unl, redn[2][tid] = n_abs;
+    __syncthreads();
+    for (int w = CALIB_TILE / 2; w >= 1; w >>= 1) {
+        if (tid < w) {
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+                red[i][tid] += red[i][tid + w];
+                redn[i][tid] += redn[i][tid + w];
+            }
+        }
+        __syncthreads();
+    }
+    unsigned long long* row = reinterpret_cast<unsigned long long*>(scratch + sizeof(CalibState)) + (size_t)(1 + M) +
+                              (size_t)blockIdx.x * calib_row_words(M);
+    if (tid < 3) {
+        reinterpret_cast<double*>(row)[tid] = red[tid][0];
+        reinterpret_cast<long long*>(row)[3 + tid] = redn[tid][0];
+    }
+    for (int m = tid; m < M; m += CALIB_TILE) {
+        reinterpret_cast<double*>(row)[CALIB_ROW_HEAD + m] = qacc[m];
+        row[CALIB_ROW_HEAD + M + m] = cnt[m];
+    }
+}
+
+// grid 1
+__global__ __launch_bounds__(CALIB_UPD_NT) void k_calib_update(double* __restrict__ theta, CalibRec* __restrict__ rec,
+                                                               unsigned char* __restrict__ scratch, int M, int G, int fit, int max_iter,
+                                                               double tol, double kmin, double kmax, int first) {
+    CalibState* st = reinterpret_cast<CalibState*>(scratch);
+    if (!first && st->done) return;
+    __shared__ double s_sum[3];
+    __shared__ long long s_cnt[3];
+    __shared__ double s_res[CALIB_UPD_NT];
+    __shared__ int s_unf[CALIB_UPD_NT];
+    __shared__ int s_do;
+    const int tid = threadIdx.x;
+    double* best = reinterpret_cast<double*>(scratch + sizeof(CalibState));                   // [1 + M]
+    const unsigned long long* rows = reinterpret_cast<const unsigned long long*>(best + 1 + M);
+    const size_t W = calib_row_words(M);
+    if (tid < 3) {
+        double s = 0.0;
+        for (int g = 0; g < G; ++g) s += reinterpret_cast<const double*>(rows + (size_t)g * W)[tid];          // in row order
+        s_sum[tid] = s;
+    } else if (tid < 6) {
+        long long s = 0;
+        for (int g = 0; g < G; ++g) s += reinterpret_cast<const long long*>(rows + (size_t)g * W)[tid];
+        s_cnt[tid - 3] = s;
+    }
+    __syncthreads();
+    const long long n = s_cnt[0];
+    const double inv_n = n > 0 ? 1.0 / (double)n : 0.0;
+    double qv[CALIB_UPD_ROWS], nv[CALIB_UPD_ROWS];
+    double res = 0.0;
+    int unf = 0;
+#pragma unroll
+    for (int j = 0; j < CALIB_UPD_ROWS; ++j) {
+        const int m = tid + j * CALIB_UPD_NT;
+        qv[j] = nv[j] = 0.0;
+        if (m < M) {
+            double q = 0.0;
+            unsigned long long k = 0ull;
+            for (int g = 0; g < G; ++g) {
+                const unsigned long long* row = rows + (size_t)g * W;
+                q += reinterpret_cast<const double*>(row)[CALIB_ROW_HEAD + m];
+                k += row[CALIB_ROW_HEAD + M + m];
+            }
+            qv[j] = q, nv[j] = (double)k;
+            if (k == 0ull) unf += 1;
+            else res = fmax(res, fabs(q - (double)k) * inv_n);
+        }
+    }
+    s_res[tid] = res;
+    s_unf[tid] = unf;
+    __syncthreads();
+    for (int w = CALIB_UPD_NT / 2; w >= 1; w >>= 1) {
+        if (tid < w) {
+            s_res[tid] = fmax(s_res[tid], s_res[tid + w]);
+            s_unf[tid] += s_unf[tid + w];
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        const bool fit_t = (fit & 1) != 0, fit_p = (fit & 2) != 0;
+        const double inf = __longlong_as_double(0x7ff0000000000000ll);
+        int act = 0;
+        double kappa = theta[0];
+        const int it = first ? 0 : st->iter;
+        if (first) {
+            st->last = 0, st->lo_known = st->hi_known = st->have_best = 0, st->spare0 = st->spare1 = 0;
+            st->lo = kmin, st->hi = kmax;
+            st->best_J = st->best_g = st->best_h = st->best_resid = st->xent_start = 0.0;
+        }
+        const double J = s_sum[0] * inv_n, g = s_sum[1] * inv_n, h = s_sum[2] * inv_n;
+        const double resid = fit_p ? s_res[0] : 0.0;
+        CalibRec r{0.0, 0.0, 0.0, 0.0, 0.0, n, s_cnt[1], s_cnt[2], it + 1, 0, s_unf[0], 0};
+        bool finish = false;
+        if (n == 0) {
+            r.flags = CALIB_NO_DATA;
+            finish = true;
+        } else {
+            if (it == 0 && fit_t && max_iter > 0 && !(kappa >= kmin && kappa <= kmax)) {
+                kappa = kappa > kmax ? kmax : kmin;                                           // a start outside the box (or a NaN) is put on it:
+                theta[0] = kappa;                                                             // the fit, and xent_start, begin there
+            } else {
+                if (!st->have_best) st->xent_start = J;                                       // (the first theta inside the box)
+                const bool is_best = !st->have_best || J < st->best_J || st->best_J != st->best_J;
+                if (is_best) {
+                    st->have_best = 1;
+                    st->best_J = J, st->best_g = g, st->best_h = h, st->best_resid = resid;
+                    best[0] = kappa;
+                    act |= CALIB_DO_SAVE;
+                }
+                const bool out_min = fit_t && kappa == kmin && g > 0.0, out_max = fit_t && kappa == kmax && g < 0.0;
+                const bool temp_ok = !fit_t || fabs(kappa * g) <= tol || out_min || out_max;
+                const bool prior_ok = !fit_p || resid <= tol;
+                const bool conv = temp_ok && prior_ok;
+                if (conv && J <= st->xent_start) {
+                    r.flags = CALIB_CONVERGED | (out_min ? CALIB_AT_MIN : 0) | (out_max ? CALIB_AT_MAX : 0);
+                    r.xent_end = J, r.g_logk = kappa * g, r.resid_prior = resid, r.curvature = h;
+                    finish = true;
+                } else if (conv || it >= max_iter) {                                          // the best theta seen, the one with the lowest J
+                    const double bk = best[0], bg = st->best_g;
+                    r.flags = CALIB_MAX_ITER | (fit_t && bk == kmin && bg > 0.0 ? CALIB_AT_MIN : 0) | (fit_t && bk == kmax && bg < 0.0 ? CALIB_AT_MAX : 0);
+                    r.xent_end = st->best_J, r.g_logk = bk * bg, r.resid_prior = st->best_resid, r.curvature = st->best_h;
+                    if (!is_best) {
+                        act |= CALIB_DO_RESTORE;
+                        if (fit_t) theta[0] = bk;
+                    }
+                    finish = true;
+                } else if (fit_t && !temp_ok && (!fit_p || prior_ok || st->last != CALIB_STEP_KAPPA)) {
+                    // a Newton step on g, at most a factor 8 in kappa, kept inside the sign bracket: an end whose sign is not known is
+                    // the box's and is tried itself, a known one sends the step to the middle of the bracket in log kappa
+                    if (g < 0.0) { st->lo = kappa; st->lo_known = 1; } else { st->hi = kappa; st->hi_known = 1; }
+                    double cand = h > 0.0 ? kappa - g / h : (g < 0.0 ? inf : -inf);
+                    if (!(cand < kappa * 8.0)) cand = kappa * 8.0;
+                    if (!(cand > kappa * 0.125)) cand = kappa * 0.125;
+                    if (cand >= st->hi) cand = st->hi_known ? sqrt(st->lo * st->hi) : st->hi;
+                    else if (cand <= st->lo) cand = st->lo_known ? sqrt(st->lo * st->hi) : st->lo;
+                    theta[0] = cand;
+                    st->last = CALIB_STEP_KAPPA;
+                } else {                                                                      // c moves: the bracket is opened again
+                    act |= CALIB_DO_SWEEP;
+                    st->last = CALIB_STEP_PRIOR;
+                    st->lo = kmin, st->hi = kmax, st->lo_known = st->hi_known = 0;
+                }
+            }
+        }
+        st->iter = it + 1;
+        st->done = finish ? 1 : 0;
+        if (finish) {
+            if (n > 0) r.xent_start = st->xent_start;
+            *rec = r;
+        }
+        s_do = act;
+    }
+    __syncthreads();
+    const int act = s_do;
+    if (act == 0) return;
+#pragma unroll
+    for (int j = 0; j < CALIB_UPD_ROWS; ++j) {
+        const int m = tid + j * CALIB_UPD_NT;
+        if (m >= M) continue;
+        if (act & CALIB_DO_SAVE) best[1 + m] = theta[1 + m];
+        if (nv[j] == 0.0) continue;                                                           // an unfitted member keeps its bits
+        if (act & CALIB_DO_SWEEP) theta[1 + m] += qv[j] > 0.0 ? log(nv[j] / qv[j]) : 700.0;   // (q_m == 0: every own p underflowed)
+        if ((act & CALIB_DO_RESTORE) && (fit & 2)) theta[1 + m] = best[1 + m];
+    }
+}
+
 }  // namespace
+
+size_t calib_scratch_bytes(int M, long long N) {
+    return sizeof(CalibState) + sizeof(double) * ((size_t)(1 + M) + (size_t)calib_groups(N) * calib_row_words(M));
+}
+
+// The caller (cmps_bank_calibrate) has checked: 1 <= M <= 1024, N >= 1, ld >= N, M ld <= 2^62, fit in [0, 3], tol and the box finite and
+// positive, theta, record and scratch 8-byte aligned and the scratch of calib_scratch_bytes(M, N) bytes; no pointer is null.  `first`: the
+// first pair of a call, which reads nothing of what the scratch held
+hipError_t launch_calib_pass(const float* loss, int M, long long N, long long ld, const int* label, const double* theta, void* scratch,
+                             int first, hipStream_t s) {
+    hipLaunchKernelGGL(k_calib_pass, dim3(calib_groups(N)), dim3(CALIB_TILE), 0, s, loss, M, N, ld, label, theta,
+                       static_cast<unsigned char*>(scratch), first);
+    return hipGetLastError();
+}
+
+hipError_t launch_calib_update(double* theta, void* record, void* scratch, int M, long long N, int fit, int max_iter, double tol,
+                               double kappa_min, double kappa_max, int first, hipStream_t s) {
+    hipLaunchKernelGGL(k_calib_update, dim3(1), dim3(CALIB_UPD_NT), 0, s, theta, static_cast<CalibRec*>(record),
+                       static_cast<unsigned char*>(scratch), M, calib_groups(N), fit, max_iter, tol, kappa_min, kappa_max, first);
+    return hipGetLastError();
+}
 
 // The caller (cmps_loss_stats) has checked: B >= 1, first_id >= 0, first_id + B representable, stats 8-byte aligned
 hipError_t launch_loss_stats(const float* loss, int B, long long first_id, int reset, void* stats, hipStream_t s) {

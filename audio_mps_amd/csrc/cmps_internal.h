@@ -526,6 +526,13 @@ constexpr int POSTERIOR_PREFETCH_M = 256;      // up to here a thread holds the 
 hipError_t launch_bank_posterior(const float* nll, int M, int n, int steps, const float* total_in, const double* log_prior, double inv_temp,
                                  float* total_out, float* post, int* best, float* conf, double threshold, long long first_step, int reset,
                                  void* decision, hipStream_t s);
+// ... and the [M][N] losses of a held-out set fitted for the temperature and the prior (cmps_bank_calibrate): one iteration is a pass over
+// the clips (many workgroups, their sums into rows of the scratch buffer) and an update (one workgroup: adds the rows, decides, moves theta)
+size_t calib_scratch_bytes(int M, long long N);
+hipError_t launch_calib_pass(const float* loss, int M, long long N, long long ld, const int* label, const double* theta, void* scratch,
+                             int first, hipStream_t s);
+hipError_t launch_calib_update(double* theta, void* record, void* scratch, int M, long long N, int fit, int max_iter, double tol,
+                               double kappa_min, double kappa_max, int first, hipStream_t s);
 // floats of one path's stream record (StreamDev::rec), a multiple of 4: wave u, |y|^2 partial per lane, running sum | wide ut [2 DP], |y|^2
 // partial per wave [DP / 16], running sum | block u [2 D], running sum
 constexpr int STREAM_REC_WAVE = 132;

@@ -182,6 +182,12 @@ def build_parser():
     p.add_argument("--temperature", type=float, default=1.0, help="with --listen: the members' total losses are divided by it")
     p.add_argument("--prior", default=None, metavar="P0,P1,...|empirical", help="with --listen: the members' prior probabilities, or "
                    "'empirical': the class counts bank.json holds (default: uniform)")
+    p.add_argument("--calibrate", default=None, choices=["temperature", "prior", "both"],
+                   help="with --bankdir: fit the temperature and (or) the prior of p_m ~ prior_m exp(-loss_m / temperature) on this dataset's "
+                        "labelled clips (cmps_bank_calibrate), from --temperature and --prior as the start; the dataset should be held out")
+    p.add_argument("--save_calibration", action="store_true", help="with --calibrate: write the fit into bank.json of --bankdir")
+    p.add_argument("--calibrated", action="store_true", help="with --bankdir: take temperature and prior from the calibration bank.json "
+                   "holds, instead of --temperature and --prior; without --listen also report the cross-entropy under them, xent_calibrated")
     p.add_argument("--listen_curve", default=None, metavar="OUT.npy", help="with --listen: write the accuracy of the best member after "
                    "every sample, float64 [steps]")
     return p
@@ -198,7 +204,11 @@ def listen_main(args, backend=None) -> dict:
     bank = load_bank(args.bankdir, args.sample_rate, args.hparams, args.kernel_variant, backend)
     if bank.classes is None or bank.label_key is None:
         raise ValueError(f"{args.bankdir} holds a bank without classes: --bankdir judges what train --bank_by saved")
-    prior = parse_prior(args.prior, bank, args.bankdir)
+    if args.calibrated:
+        from .sample import saved_calibration
+        args.temperature, prior = saved_calibration(bank, args.bankdir, args.temperature, args.prior)
+    else:
+        prior = parse_prior(args.prior, bank, args.bankdir)
     path = os.path.join(str(args.datadir), f"{args.dataset}.tfrecords")
     if not os.path.exists(path):
         raise FileNotFoundError(path)
@@ -249,16 +259,49 @@ def bank_main(args, backend=None) -> ClassifierResult:
     path = os.path.join(str(args.datadir), f"{args.dataset}.tfrecords")
     if not os.path.exists(path):
         raise FileNotFoundError(path)
+    if args.calibrated:
+        from .sample import saved_calibration
+        saved_calibration(bank, args.bankdir)              # (a bank.json without a calibration: a ValueError before anything is scored)
     ds = ResidentDataset.from_tfrecord(path, args.sample_duration, bank.backend, storage=args.storage, label_key=bank.label_key)
-    res = BankTrainer(bank).evaluate_classifier(ds, args.minibatch_size, keep_best=args.per_clip is not None)
+    trainer = BankTrainer(bank)
+    res = trainer.evaluate_classifier(ds, args.minibatch_size, keep_best=args.per_clip is not None)
     if args.per_clip is not None:
         np.save(args.per_clip, res.best)
     if args.confusion is not None:
         np.save(args.confusion, res.confusion)
     print(f"eval {args.dataset}: {res.line()} classes={len(res.classes)} unlabelled={res.n_unlabelled} storage={ds.storage}")
+    extra = {}
+    if args.calibrated:
+        cal = bank.calibration
+        extra["xent_calibrated"] = trainer.cross_entropy(ds, cal["temperature"], minibatch_size=args.minibatch_size, log_prior=cal["log_prior"])
+        print(f"calibrated {args.dataset}: xent_calibrated={extra['xent_calibrated']:.6g} temperature={cal['temperature']:.6g} "
+              f"(fitted on {cal['dataset']}, {cal['clips']} clips of T={cal['T']})")
+    if args.calibrate is not None:
+        from .sample import parse_prior
+        cal = trainer.calibrate(ds, args.minibatch_size, fit=args.calibrate, temperature=args.temperature,
+                                prior=parse_prior(args.prior, bank, args.bankdir))
+        print(f"calibration {cal.line()}")
+        for m, c in enumerate(res.classes):
+            print(f"class {c!r}: prior {cal.prior[m]:.6g}" + (" (no held-out clip: not fitted)" if c in cal.unfitted else ""))
+        extra["calibration"] = cal.scalars()
+        if args.save_calibration:
+            save_calibration(args.bankdir, cal.meta(args.dataset))
     if args.json:
-        print(json.dumps({"dataset": args.dataset, "storage": ds.storage, **res.scalars()}))
+        print(json.dumps({"dataset": args.dataset, "storage": ds.storage, **res.scalars(), **extra}))
     return res
+
+
+def save_calibration(bankdir: str, calibration: dict):
+    """Rewrite bank.json of ``bankdir`` with ``calibration`` under "calibration" and every other key as it was: a temporary file, then
+    os.replace, as BankTrainer.save writes it."""
+    path = os.path.join(bankdir, "bank.json")
+    with open(path) as f:
+        meta = json.load(f)
+    meta["calibration"] = calibration
+    tmp = os.path.join(bankdir, "bank.json.tmp")
+    with open(tmp, "w") as f:
+        json.dump(meta, f)
+    os.replace(tmp, path)
 
 
 def main(argv=None, backend=None) -> EvalResult:
@@ -268,6 +311,16 @@ def main(argv=None, backend=None) -> EvalResult:
     args = build_parser().parse_args(argv)
     if args.sample_duration < 2 or args.minibatch_size < 1:
         raise ValueError("--sample_duration must be at least 2 and --minibatch_size positive")
+    if (args.calibrate is not None or args.calibrated or args.save_calibration) and args.bankdir is None:
+        raise ValueError("--calibrate, --save_calibration and --calibrated are a class bank's: they need --bankdir")
+    if args.save_calibration and args.calibrate is None:
+        raise ValueError("--save_calibration saves what --calibrate fitted: it needs --calibrate")
+    if args.calibrated and (args.temperature != 1.0 or args.prior is not None):
+        raise ValueError("--calibrated takes temperature and prior from bank.json: it goes with neither --temperature nor --prior")
+    if args.calibrated and args.calibrate is not None:
+        raise ValueError("--calibrated uses a saved calibration and --calibrate fits a new one: one at a time")
+    if args.calibrate is not None and (args.listen or not args.temperature > 0.0):
+        raise ValueError("--calibrate fits on whole clips: it does not go with --listen, and its start --temperature must be positive")
     if args.listen:
         if args.bankdir is None:
             raise ValueError("--listen judges a class bank: it needs --bankdir")

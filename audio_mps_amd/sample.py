@@ -109,6 +109,8 @@ def build_parser():
     p.add_argument("--temperature", type=float, default=1.0, help="with --posterior: the members' total losses are divided by it")
     p.add_argument("--threshold", type=float, default=None, metavar="P", help="with --posterior: report the first sample at which the best "
                    "member's probability reached P")
+    p.add_argument("--calibrated", action="store_true", help="with --posterior: take temperature and prior from the calibration "
+                   "bank.json holds (evaluate --calibrate ... --save_calibration), instead of --temperature and --prior")
     p.add_argument("--out_dir", default="./samples")
     p.add_argument("--kernel_variant", type=int, default=0, help="as in audio_mps_amd.train")
     return p
@@ -209,6 +211,7 @@ def load_bank(bankdir: str, sample_rate: int, hparams: str = "", kernel_variant:
         raise ValueError(f"{path} holds a bank of {name} models: {type(backend).__name__} has neither rho_bank_stream nor rho_stream")
     bank = (RhoBank if rho else PsiBank)(hp, meta["members"], backend=backend, classes=meta.get("classes"), label_key=meta.get("label_key"))
     bank.class_counts = meta.get("class_counts")                  # clips per class of the training set, where the trainer recorded them
+    bank.calibration = meta.get("calibration")                    # a fitted temperature and log prior, where somebody calibrated the bank
     for m, (model, var) in enumerate(zip(bank.models, variables)):
         for k in model.variables:
             if var[k].shape != model.variables[k].shape:
@@ -232,11 +235,28 @@ def parse_prior(spec, bank, where: str = ""):
     return prior
 
 
+def saved_calibration(bank, where: str, temperature: float = 1.0, prior=None):
+    """--calibrated: (temperature, prior [M]) of the calibration bank.json holds (evaluate --calibrate ... --save_calibration), the prior
+    normalised as exp(c - logsumexp c).  It stands in for --temperature and --prior, so neither may be given beside it."""
+    from .bank import normalised_prior
+    if temperature != 1.0 or prior is not None:
+        raise ValueError("--calibrated takes temperature and prior from bank.json: it goes with neither --temperature nor --prior")
+    cal = getattr(bank, "calibration", None)
+    if cal is None:
+        raise ValueError(f"--calibrated: {where} holds no calibration (evaluate --bankdir ... --calibrate ... --save_calibration writes one)")
+    if len(cal["log_prior"]) != len(bank):
+        raise ValueError(f"--calibrated: the calibration of {where} names {len(cal['log_prior'])} members, the bank has {len(bank)}")
+    return float(cal["temperature"]), [float(p) for p in normalised_prior(cal["log_prior"])]
+
+
 def _bank_posterior(bank, args, clip):
     """--bankdir --score --posterior: the clip followed by every member and judged after every sample (BankStream.score_posterior)."""
     M, n, N = len(bank), clip.shape[0], clip.shape[1] - 1
-    tr = bank.posterior_trace(clip, prior=parse_prior(args.prior, bank, args.bankdir), temperature=args.temperature, threshold=args.threshold,
-                              segment=args.segment, want_post=True)
+    if args.calibrated:
+        temperature, prior = saved_calibration(bank, args.bankdir, args.temperature, args.prior)
+    else:
+        temperature, prior = args.temperature, parse_prior(args.prior, bank, args.bankdir)
+    tr = bank.posterior_trace(clip, prior=prior, temperature=temperature, threshold=args.threshold, segment=args.segment, want_post=True)
     one = (lambda x, lead: x[:, 0] if lead else x[0]) if n == 1 else (lambda x, lead: x)
     post = np.ascontiguousarray(one(tr.post, True), dtype=np.float32)
     np.save(os.path.join(args.out_dir, "posterior.npy"), post)
@@ -322,6 +342,10 @@ def main(argv=None, backend=None):
         raise ValueError("--posterior judges the members of a bank along a clip: it needs --bankdir and --score")
     if not args.posterior and (args.prior is not None or args.threshold is not None or args.temperature != 1.0):
         raise ValueError("--prior, --temperature and --threshold belong to --posterior")
+    if args.calibrated and not args.posterior:
+        raise ValueError("--calibrated belongs to --posterior: it stands in for --temperature and --prior")
+    if args.calibrated and (args.temperature != 1.0 or args.prior is not None):
+        raise ValueError("--calibrated takes temperature and prior from bank.json: it goes with neither --temperature nor --prior")
     if args.bankdir is not None:
         if any(a == "--modeldir" or a.startswith("--modeldir=") for a in (sys.argv[1:] if argv is None else argv)):
             raise ValueError("--bankdir and --modeldir do not go together: a bank's members are read from --bankdir")

@@ -169,7 +169,7 @@ class HipScan:
         return mode if mode in (_capi.CMPS_RANK1_EXACT_F32, _capi.CMPS_RANK1_BF16X2, _capi.CMPS_RANK1_F16X2) else _capi.CMPS_RANK1_BF16X3
 
     def kernel_events(self, on: bool):
-        """cmps_set_option(CMPS_OPT_KERNEL_EVENTS): bracket every kernel of forward() / backward() and of sample() / sample_primed() / stream() / stream_score() / rho_sample_primed() / rho_stream() / rho_stream_score() / draw_noise() / gather_batch() / loss_stats() / classify_stats() / classify_weights() / bank_posterior() / damped_sine() with HIP
+        """cmps_set_option(CMPS_OPT_KERNEL_EVENTS): bracket every kernel of forward() / backward() and of sample() / sample_primed() / stream() / stream_score() / rho_sample_primed() / rho_stream() / rho_stream_score() / draw_noise() / gather_batch() / loss_stats() / classify_stats() / classify_weights() / bank_posterior() / bank_calibrate() / damped_sine() with HIP
         events (a measurement aid, used by bench.py outside its timed region)."""
         _capi.check(self._h, self._lib.cmps_set_option(self._h, _capi.CMPS_OPT_KERNEL_EVENTS, 1 if on else 0))
 
@@ -689,6 +689,42 @@ class HipScan:
     def read_classify_weights_record(record: torch.Tensor) -> dict:
         """The record of classify_weights as a dict of Python numbers (_capi.CLASSIFY_WEIGHTS_REC's fields): one 40-byte download."""
         return _read_record(record, _capi.CLASSIFY_WEIGHTS_REC)[0]
+
+    def bank_calibrate(self, loss: torch.Tensor, labels: torch.Tensor, fit: int, kappa: float, log_prior=None, tol: float = 1e-9,
+                       max_iter: int = 200, kappa_min: float = 1e-6, kappa_max: float = 1e6) -> torch.Tensor:
+        """cmps_bank_calibrate: fit the inverse temperature and (or) the log prior of a class bank on the held-out losses ``loss`` [M, N]
+        (float32 on this device, rows contiguous) and ``labels`` (int32 [N] on this device), from the start ``kappa`` and ``log_prior``
+        ([M] floats, finite or -inf; None: zeros).  ``fit``: a set of _capi.CMPS_CALIB_TEMPERATURE | _capi.CMPS_CALIB_PRIOR; 0 (or
+        max_iter = 0) evaluates the cross-entropy under the given values.  Returns ONE uint8 device tensor, theta [1 + M] doubles with
+        the 80-byte record behind it: read_calibrate_record is the one download.  No host copy of the losses, no synchronisation."""
+        if not (_is_tensor(loss, self.device, torch.float32, 2, rows=True) and loss.numel() >= 1):
+            raise ValueError("bank_calibrate: loss must be a float32 tensor [M, N] with contiguous rows, M >= 1 and N >= 1, on the "
+                             "backend's device")
+        M, N = int(loss.shape[0]), int(loss.shape[1])
+        if not 1 <= M <= _capi.CLASSIFY_MAX_M:
+            raise ValueError(f"bank_calibrate: a bank holds 1 .. {_capi.CLASSIFY_MAX_M} members, not {M}")
+        if not _is_tensor(labels, self.device, torch.int32, (N,)):
+            raise ValueError("bank_calibrate: labels must be a contiguous int32 tensor [N] on the backend's device")
+        theta = np.zeros(1 + M, dtype=np.float64)
+        theta[0] = float(kappa)
+        if log_prior is not None:
+            theta[1:] = np.asarray(log_prior, dtype=np.float64).reshape(M)
+        out = torch.empty(8 * (1 + M) + _capi.CALIB_REC.itemsize, dtype=torch.uint8, device=self.device)
+        out[:8 * (1 + M)].copy_(torch.from_numpy(theta.view(np.uint8)))
+        nbytes = int(self._lib.cmps_bank_calibrate_scratch_bytes(M, N))
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        _capi.check(self._h, self._lib.cmps_bank_calibrate(
+            self._h, loss.data_ptr(), M, N, int(loss.stride(0)) if M > 1 else N, labels.data_ptr(), int(fit), int(max_iter), float(tol),
+            float(kappa_min), float(kappa_max), out.data_ptr(), out.data_ptr() + 8 * (1 + M), scratch.data_ptr(), nbytes, self._stream()))
+        return out
+
+    @staticmethod
+    def read_calibrate_record(out: torch.Tensor) -> tuple:
+        """What bank_calibrate returned, downloaded once: (theta [1 + M] float64, the record as a dict of Python numbers)."""
+        raw = out.cpu().numpy()
+        split = raw.size - _capi.CALIB_REC.itemsize
+        rec = raw[split:].view(_capi.CALIB_REC)[0]
+        return raw[:split].view(np.float64).copy(), {k: (float(rec[k]) if rec.dtype[k].kind == "f" else int(rec[k])) for k in rec.dtype.names}
 
     def log_prior_tensor(self, log_prior) -> Optional[torch.Tensor]:
         """A log prior [M] (finite or -inf) as `bank_posterior` takes it: float64 on this device.  None stays None (a uniform prior)."""

@@ -94,7 +94,7 @@ enum {
     CMPS_OPT_F16_SCALE_SHIFT = 4 /* DIAGNOSTIC, default 0: added to the exponent of every data-dependent fp16 scale of the wave reverse
                         * scan's F16X2 arithmetic (range -40 .. 40).  A positive value pushes the pieces out of fp16 range on purpose:
                         * how tests/test_gpu_parity.py provokes CMPS_ERR_F16_RANGE.  No reference counterpart. */,
-    CMPS_OPT_KERNEL_EVENTS = 2 /* 1: every kernel cmps_psi_loss_fwd / _bwd, cmps_rho_loss_fwd / _bwd, cmps_psi_sample, cmps_psi_sample_primed, cmps_psi_stream, cmps_psi_stream_score, cmps_rho_sample_primed, cmps_rho_stream, cmps_rho_stream_score, cmps_noise_fill (as k_noise_philox), cmps_batch_gather (as k_batch_gather), cmps_batch_gather_i16 (as k_batch_gather_i16), cmps_loss_stats (as k_loss_stats), cmps_bank_classify_stats (as k_classify_stats), cmps_bank_classify_weights (as k_classify_weights), cmps_bank_posterior (as k_bank_posterior), cmps_bank_loss_bwd_weighted (the scan of cmps_bank_loss_bwd, then "reduce + finalize (weighted)") and cmps_damped_sine_fill (as k_damped_sine) launch is bracketed by two HIP events on the caller's stream
+    CMPS_OPT_KERNEL_EVENTS = 2 /* 1: every kernel cmps_psi_loss_fwd / _bwd, cmps_rho_loss_fwd / _bwd, cmps_psi_sample, cmps_psi_sample_primed, cmps_psi_stream, cmps_psi_stream_score, cmps_rho_sample_primed, cmps_rho_stream, cmps_rho_stream_score, cmps_noise_fill (as k_noise_philox), cmps_batch_gather (as k_batch_gather), cmps_batch_gather_i16 (as k_batch_gather_i16), cmps_loss_stats (as k_loss_stats), cmps_bank_classify_stats (as k_classify_stats), cmps_bank_classify_weights (as k_classify_weights), cmps_bank_posterior (as k_bank_posterior), cmps_bank_calibrate (as k_calib_pass and k_calib_update, one pair per iteration), cmps_bank_loss_bwd_weighted (the scan of cmps_bank_loss_bwd, then "reduce + finalize (weighted)") and cmps_damped_sine_fill (as k_damped_sine) launch is bracketed by two HIP events on the caller's stream
                         * (read and reset with cmps_kernel_times); 0 (default): nothing is recorded.  A measurement aid -- the reference
                         * has no counterpart (no tracing / profiling hooks); bench.py uses it OUTSIDE its timed region to price
                         * each kernel of a multi-kernel family against the pipe it runs on */
@@ -1049,6 +1049,114 @@ int cmps_bank_posterior(cmps_handle_t h, const float* nll_dev, int M, int n, int
                         const float* total_in_dev, const double* log_prior_dev, double inv_temp,
                         float* total_out_dev, float* post_dev, int* best_dev, float* conf_dev,
                         double threshold, long long first_step, int reset, void* decision_dev, void* stream);
+
+/*
+ * The temperature and the prior of a class bank FITTED on held-out losses, on the device: loss_dev[m * ld + b] (ld >= N) holds the [M][N]
+ * losses of N held-out clips under the M members -- the outputs of cmps_bank_loss_fwd / cmps_rho_bank_loss_fwd over the batches of a
+ * held-out set, kept side by side -- and label_dev[b] the member clip b belongs to.  The bank answers with
+ * p_m ~ prior_m exp(-loss_m / temperature); this entry finds the temperature and (or) the prior under which the held-out labels are the
+ * most likely.  With max_iter == 0 or fit == 0 it evaluates the held-out cross-entropy under the GIVEN temperature and prior.
+ * Replaces: nothing -- the reference trains a model per pitch (reader.py:9-66) and never judges them against each other.
+ * THE MODEL AND THE OBJECTIVE (normative; tests/_calib_ref.py restates them in numpy).  l[m][b] = loss_dev[m * ld + b], y_b = label_dev[b].
+ * theta = (kappa, c_0 .. c_{M-1}) in double: kappa = 1 / temperature > 0, c_m = log prior_m up to a common shift.  A NaN or +-Inf loss
+ * makes that member ABSENT for that clip.
+ *   SKIPPED  y_b outside [0, M): counted in n_unlabelled.  Else member y_b absent: counted in n_own_absent.  A skipped clip enters nothing
+ *            else (the rules and counters of cmps_bank_classify_weights).
+ *   USED     every other clip; n of them, n_m with label m.  With lmin_b the smallest present loss, everything in double, the sums in
+ *            member order:
+ *              a_m    = kappa (l_m - lmin_b) - c_m,  amin = the smallest a_m  (the shift of the exponentials, as in cmps_bank_posterior)
+ *              S      = sum over the present m of exp(-(a_m - amin))                               1 <= S <= M
+ *              p_m    = exp(-(a_m - amin)) / S
+ *              xent_b = (a_y - amin) + log S
+ *              E_b    = sum_m p_m (l_m - lmin_b),   V_b = sum_m p_m (l_m - lmin_b)^2 - E_b^2
+ *   Over the used clips:
+ *              J(theta) = (1 / n) sum_b xent_b                                   the objective, convex in theta
+ *              g = dJ / dkappa   = (1 / n) sum_b ((l_y - lmin_b) - E_b)         monotone in kappa
+ *              h = d2J / dkappa2 = (1 / n) sum_b V_b  >= 0
+ *              q_m = sum_b p_m(b),  so  dJ / dc_m = (q_m - n_m) / n
+ * THE FIT.  fit is a set of bits.  With CMPS_CALIB_TEMPERATURE kappa moves inside [kappa_min, kappa_max] towards the root of g: a Newton
+ * step on g of at most a factor 8 in kappa, kept inside a sign bracket and sent to the bracket's middle in log kappa when it leaves it.
+ * With CMPS_CALIB_PRIOR every member with n_m > 0 takes the iterative-scaling step c_m += log(n_m / q_m) (generalised iterative scaling
+ * for one-hot features: its auxiliary bound separates per coordinate, so J never rises); a member with n_m == 0 is UNFITTED and its c_m
+ * keeps its input bits.  With both, kappa steps and prior sweeps alternate (whichever of the two has met its test stands back), and the
+ * bracket is opened again whenever c has moved.  c is never shifted on the device: the host normalises it for display.  The iterates are
+ * not normative; the properties below are.
+ *   theta_dev   [1 + M] doubles, 8-byte aligned: in the start, out the fit.  A start kappa outside the box cannot be refused without a
+ *               download: where the temperature is fitted and max_iter > 0 the first update puts it on the nearer bound (a NaN on
+ *               kappa_min).  That counts as a pass, and the theta with kappa on the box is then "the input theta" of the record and
+ *               of the properties: xent_start is J there.  A c_m is finite or -inf (a prior of zero); a used clip whose OWN member has
+ *               c = -inf has probability zero, J is +inf (NaN where no present member of a clip has a finite c) and theta, the record
+ *               and the flags are unspecified, within the extents -- the host layer refuses such a prior.
+ *   record_dev  80 bytes, 8-byte aligned (cmps_bank_calibrate_rec below); written once, when the fit finishes
+ *   scratch_dev cmps_bank_calibrate_scratch_bytes(M, N) bytes, 8-byte aligned; may hold anything before the call; 0 for M outside
+ *               [1, 1024], N < 1 or M N beyond 2^62
+ * THE RECORD (normative; little-endian, 8-byte aligned):
+ *   offset  type       field
+ *        0  double     xent_start     J at the input theta (kappa put on the box first where it lay outside: see theta_dev)
+ *        8  double     xent_end       J at the returned theta
+ *       16  double     g_logk         kappa g at the returned theta
+ *       24  double     resid_prior    max over the fitted m of |q_m - n_m| / n at the returned theta; 0 when the prior is not fitted
+ *       32  double     curvature      h at the returned theta
+ *       40  long long  n_used
+ *       48  long long  n_unlabelled
+ *       56  long long  n_own_absent
+ *       64  int        passes         evaluations of J made
+ *       68  int        flags          1 CONVERGED, 2 AT_KAPPA_MIN, 4 AT_KAPPA_MAX, 8 NO_DATA, 16 MAX_ITER
+ *       72  int        n_unfitted     members with n_m == 0
+ *       76  int        reserved       0
+ * PROPERTIES.
+ *   1  CONVERGED means that at ONE pass, at the returned theta: |kappa g| <= tol, or kappa sits on a bound of the box with g pushing
+ *      outwards (the bound's flag is then set as well); and, with the prior fitted, resid_prior <= tol.  Otherwise MAX_ITER is set and the
+ *      theta with the lowest J of all passes is returned, with the record's figures from that pass.
+ *   2  xent_end <= xent_start (a converged theta whose J came out above xent_start by rounding is given up for the best one, under
+ *      MAX_ITER).  With fit == 0 or max_iter == 0: theta keeps its bits, xent_end == xent_start, passes == 1.
+ *   3  Without CMPS_CALIB_PRIOR every c_m keeps its bits, without CMPS_CALIB_TEMPERATURE kappa keeps its bits, an unfitted member always
+ *      keeps its bits, kappa stays inside [kappa_min, kappa_max], and where g == 0 (all present losses of every clip equal) kappa keeps its
+ *      start value.
+ *   4  n_used == 0: NO_DATA, theta untouched, both xents 0, passes == 1.
+ * A FINITE OPTIMUM needs clips that are wrong and more clips than fitted parameters.  An unfitted member with a finite c_m keeps a share
+ * of every clip's probability that no finite c of the others takes away: with the prior fitted J then has no minimum, the fitted c_m
+ * grow without bound (the residual falls like 1 / passes) and the fit ends with MAX_ITER at the best theta.  c_m = -inf, a prior of zero,
+ * is carried through as a member that never wins (a_m = +inf, p_m = 0) and keeps its bits like any unfitted member's.
+ * HOW IT RUNS.  One iteration is two launches: k_calib_pass, many workgroups over the clips, each leaving its sums of J, g, h and q[M] in
+ * double in a row of scratch_dev; k_calib_update, one workgroup that adds the rows in row order, decides, moves theta and keeps the solver's
+ * state, the best theta and a `done` word in scratch_dev.  The entry enqueues max_iter + 1 such pairs without looking; once `done` is set
+ * the later launches leave at their first, uniform branch.  No cooperative launch, no workgroup waits for another, no floating-point
+ * atomics (n_m is an integer count); the assignment of clips to threads and every order of summation are fixed: the same call gives the
+ * same bits on every run.
+ * ROUNDING.  u = 2^-53, exp and log of the device within 4 ulp = 8 u in double (as for cmps_bank_classify_stats).  At a theta, with
+ * D = the largest (l_m - lmin_b) over the present members of the used clips and A = kappa D + max_m |c_m|:  d = l_m - lmin_b carries one
+ * rounding, a_m two more, each of a number no larger than A, and so does amin: t = a_m - amin >= 0 has |dt| <= u (6 A + t), and
+ * e_m = exp(-t) <= 1 is within u (e_m (8 + 6 A) + 0.37) of exact (t exp(-t) <= 1 / e).  S, a sum of at most M such terms with S >= 1, is
+ * within u S (1.37 M + 8 + 6 A); p_m within u (1.37 M + 18 + 12 A); log S within u (1.37 M + 8 + 6 A) + 8 u log M, so a clip's xent
+ * within u (1.37 M + 64 + 12 A + 2 xent).  sum_m e_m d_m <= S D is within u S D (1.37 M + 10 + 6 A), E_b within u D (3 M + 24 + 12 A), and
+ * (l_y - lmin_b) - E_b, of size at most D, within u D (3 M + 27 + 12 A).  A mean of n terms summed in double in any order adds
+ * n u (mean of the absolute terms):
+ *   eps_J = 2^-52 (M + 32 + 6 A + (n / 2 + 2) J)                  bounds |J_device - J_exact|
+ *   eps_g = 2^-52 D (1.5 M + 14 + 6 A + n / 2)                    bounds |g_device - g_exact|
+ *   eps_q = 2^-52 n (0.7 M + 9 + 6 A + n / 2)                     bounds |q_m device - q_m exact|;  resid_prior within eps_q / n
+ * where "exact" is exact arithmetic on the float32 losses and the doubles of theta.
+ * Needs no cmps_set_params: it works on a fresh handle of any D, in legacy mode and for either kind of bank.  Asynchronous on `stream`;
+ * never synchronises, allocates nothing, reads loss_dev[m * ld + b] for m < M, b < N and label_dev[0 .. N) only, and writes only
+ * theta_dev[0 .. 1 + M), the record and the scratch.
+ * CMPS_ERR_BAD_ARG, each with a message that starts with the entry's name, the first failing check speaking, before the device is
+ * touched: a null handle; a null loss_dev; a null label_dev; a null theta_dev or one that is not 8-byte aligned; the same for record_dev;
+ * the same for scratch_dev; M outside [1, 1024]; N < 1 or M ld beyond 2^62; ld < N; fit outside [0, 3]; max_iter outside [0, 10000]; tol
+ * not finite or <= 0; kappa_min not finite or <= 0; kappa_max not finite or < kappa_min; scratch_bytes below
+ * cmps_bank_calibrate_scratch_bytes(M, N).
+ * With CMPS_OPT_KERNEL_EVENTS the launches are recorded as k_calib_pass and k_calib_update.
+ */
+enum { CMPS_CALIB_TEMPERATURE = 1, CMPS_CALIB_PRIOR = 2 };            /* `fit` is a bit set; 0 = evaluate only */
+enum { CMPS_CALIB_CONVERGED = 1, CMPS_CALIB_AT_KAPPA_MIN = 2, CMPS_CALIB_AT_KAPPA_MAX = 4, CMPS_CALIB_NO_DATA = 8, CMPS_CALIB_MAX_ITER = 16 };
+typedef struct cmps_bank_calibrate_rec {
+    double xent_start, xent_end, g_logk, resid_prior, curvature;
+    long long n_used, n_unlabelled, n_own_absent;
+    int passes, flags, n_unfitted, reserved;
+} cmps_bank_calibrate_rec;
+size_t cmps_bank_calibrate_scratch_bytes(int M, long long N);
+int cmps_bank_calibrate(cmps_handle_t h, const float* loss_dev, int M, long long N, long long ld, const int* label_dev,
+                        int fit, int max_iter, double tol, double kappa_min, double kappa_max,
+                        double* theta_dev, void* record_dev, void* scratch_dev, size_t scratch_bytes, void* stream);
 
 /*
  * The synthetic training batch, generated where it is used.  Replaces: the damped_sine branch of get_audio (data.py:8-22): a 261.6 Hz sine
