@@ -19,6 +19,12 @@
 // Every wait loop is bounded (a wave that never sees its partner's counter gives up and finishes: wrong numbers, never a hang).
 // The first octet is padded in FRONT with zeros when (N - 1) & 7 steps sit above the first aligned octet, step 0 gets an octet of its own
 // (seven zero slots behind it): zero operands add nothing.
+// Loop structure of the chain wave: a loop over the 32-step staged chunks from the top one down; inside it
+//   a full chunk with a chunk below it, on normalised rows of a PsiCMPS stash: four octets unrolled with compile-time step numbers (every
+//     LDS offset an immediate, the ring-half and scalar-chunk parities settled per chunk, the serial tail one asm statement: DESIGN 4.2c);
+//   otherwise the steps above the first aligned octet one by one, then a loop over the aligned octets, eight steps unrolled
+//     (the top chunk, chunk 0, RhoCMPS virtual clips, every chunk of the (y, H y) instance);
+// then step 0.  All of them run chain_step: one statement of the arithmetic.
 // Arithmetic: the chain is k_bwd_wave's instruction for instruction; the sums are the F16X2 form (three products per pair, fp32
 // accumulate), with scales that differ from k_bwd_wave<3>'s by powers of two only where both are in range -- same accuracy class
 // (tests/test_gpu_parity.py::test_two_wave_reverse_scan_*).  PsiCMPS arithmetic only (no legacy mode); RhoCMPS virtual clips are supported.
@@ -57,6 +63,30 @@ __device__ __forceinline__ void swap_fill(float& a, float& b, v2f& m0, v2f r0, v
         "v_permlane32_swap_b32 %0, %1"
         : "+v"(a), "+v"(b), "=&v"(m0), "=&v"(m1) : "v"(r0), "v"(q0), "v"(r1), "v"(q1), "v"(s2));
 }
+// The serial tail of a step on normalised rows as ONE statement (the forward's rot_tail_bcast, cmps_wave2.hip): both lane exchanges with
+// their two fills each, md = sx + sy, g = ybar + md and the two selects behind the second exchange.  Written in C++ the exchanges cost
+// four copies per step: one half of the mat-vec result in front of the first, g twice in front of the second (the exchange overwrites both
+// its operands and g has to survive), g once more into the pair the next step's complex product reads.  Here the mat-vec result arrives in
+// v[254:255] and is exchanged in place, g is ADDED twice (the same sum, the same bits) and comes back out of the exchanged pair by a
+// select -- after the exchange a = (g.lo | g.lo), b = (g.hi | g.hi), so g = hb ? b : a and osig = hb ? -a : b.  Same operations on the
+// same values as swap_fill + the C++ between; `hmask`: the lanes of the upper half.
+__device__ __forceinline__ void chain_tail_n(v2f am, float ybar, unsigned long long hmask, float& md, float& g, float& go,
+                                             v2f& m0, v2f r0, v2f q0, v2f& m1, v2f r1, v2f q1, v2f& m2, v2f r2, v2f q2, v2f& m3, v2f r3, v2f q3,
+                                             v2f s2) {
+    asm("v_pk_fma_f32 %3, %8, %16, %9 op_sel_hi:[1,0,1]\n\t"
+        "v_pk_fma_f32 %4, %10, %16, %11 op_sel_hi:[1,0,1]\n\t"
+        "v_permlane32_swap_b32 v254, v255\n\t"
+        "v_add_f32 %0, v254, v255\n\t"
+        "v_add_f32 v254, %17, %0\n\t"
+        "v_add_f32 v255, %17, %0\n\t"
+        "v_pk_fma_f32 %5, %12, %16, %13 op_sel_hi:[1,0,1]\n\t"
+        "v_pk_fma_f32 %6, %14, %16, %15 op_sel_hi:[1,0,1]\n\t"
+        "v_permlane32_swap_b32 v254, v255\n\t"
+        "v_cndmask_b32_e64 %1, v254, v255, %18\n\t"
+        "v_cndmask_b32_e64 %2, v255, -v254, %18"
+        : "=&v"(md), "=&v"(g), "=&v"(go), "=&v"(m0), "=&v"(m1), "=&v"(m2), "=&v"(m3), "+{v[254:255]}"(am)
+        : "v"(r0), "v"(q0), "v"(r1), "v"(q1), "v"(r2), "v"(q2), "v"(r3), "v"(q3), "v"(s2), "v"(ybar), "s"(hmask));
+}
 // The pre stage's reads on NORMALISED rows: the lane's own (yhat, p) pair, the partner component's yhat (the neighbouring pair of the
 // staged row: no lane exchange), rho, and the step's ONE 16-byte scalar row.  Four LDS operations, as own_issue: the counted waits of
 // the step are the same numbers.
@@ -78,6 +108,12 @@ __device__ __forceinline__ void lds_wait_own_n(v2f& yh, float& part, v2f& t, v4f
 template <int OFF>
 __device__ __forceinline__ void ring_write(unsigned addr, float v) {
     asm volatile("ds_write_b32 %0, %1 offset:%2" : : "v"(addr), "v"(v), "n"(OFF) : "memory");
+}
+// a * b + c with the product rounded (two instructions), whatever the contraction setting and whether or not the vectoriser pairs two steps:
+// the chain's running sums on normalised rows state their roundings, so every path through the scan gives the same bits for the same step
+__device__ __forceinline__ float mul_add_rounded(float a, float b, float c) {
+#pragma clang fp contract(off)
+    return a * b + c;
 }
 __device__ __forceinline__ float wave_max(float x) {       // max over the 64 lanes (x >= 0), uniform; DPP as sum64 (cmps_wave_util.h)
     asm("s_nop 1\n\tv_max_f32_dpp %0, %0, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
@@ -144,6 +180,7 @@ __global__ __launch_bounds__(128 * WAVES, 1) void k_bwd_wave2w(Dev Pk, const flo
         const unsigned aYown = lds_addr(&stY[w][0]) + (2 * i + h) * 8;   // stash rows: 64 (y[n], (H y)[n]) pairs, n = 2 i + {re, im}
         const unsigned aYpart = lds_addr(&stY[w][0]) + (2 * i + (1 - h)) * 8;   // NORM: the pair of the partner component, n ^ 1
         const unsigned sgn_h = hb ? 0x80000000u : 0u;                       // NORM: osig = the partner's value with the sign of the half
+        const unsigned long long hmask = __builtin_amdgcn_ballot_w64(hb);   // NORM: the upper half's lanes (chain_tail_n's selects)
         const unsigned aRho = lds_addr(&stR[w][0]) + i * 8;
         const unsigned aScl = lds_addr(&scl[w][0]);
         const float4* rho4 = reinterpret_cast<const float4*>(P.rho);
@@ -176,6 +213,14 @@ __global__ __launch_bounds__(128 * WAVES, 1) void k_bwd_wave2w(Dev Pk, const flo
             } else {
                 octet_load(hh, q);
             }
+        };
+        // the same six loads from bases the caller keeps (the full-chunk path: one constant increment per octet, no row arithmetic)
+        auto octet_load_at = [&](const float4* py, const float4* pr) {
+            asm volatile("global_load_dwordx4 %0, %6, %7\n\tglobal_load_dwordx4 %1, %6, %7 offset:1024\n\t"
+                         "global_load_dwordx4 %2, %6, %7 offset:2048\n\tglobal_load_dwordx4 %3, %6, %7 offset:3072\n\t"
+                         "global_load_dwordx4 %4, %6, %8\n\tglobal_load_dwordx4 %5, %6, %8 offset:1024"
+                         : "=&v"(so4[0]), "=&v"(so4[1]), "=&v"(so4[2]), "=&v"(so4[3]), "=&v"(so2[0]), "=&v"(so2[1])
+                         : "v"(so_lane16), "s"(py), "s"(pr) : "memory");
         };
         auto octet_commit = [&](int q) {
             stage_commit<4>(&stY[w][q * 256], lane, so4);
@@ -300,9 +345,17 @@ __global__ __launch_bounds__(128 * WAVES, 1) void k_bwd_wave2w(Dev Pk, const flo
         // ring slot `aslot` (an LDS address with the value / slot offsets folded in by the caller)
         auto chain_step = [&](const Pre2& S, float uk, auto have_pre, bool exact, unsigned aslot, auto slot_off) -> Pre2 {
             constexpr int SO = decltype(slot_off)::value;        // constant part of the slot address (the aligned octets: the whole slot)
+            if constexpr (NORM) facc = __builtin_fmaf(S.sd.y, go * S.un, facc);
+            else
             facc += S.sd.y * (go * S.un);
-            const v2f yhbp = cmul2_conj_b(mk2(g, go), S.rho);              // conj(rho_k) g
-            const float yhb = yhbp.x;
+            float yhb;                                                     // conj(rho_k) g, this half's component
+            if constexpr (NORM) {
+                // cmul2_conj_b's low half with its roundings (the product, then one FMA): g and osig need not sit in a register pair
+                yhb = __builtin_fmaf(go, S.rho.y, g * S.rho.x);
+            } else {
+                const v2f yhbp = cmul2_conj_b(mk2(g, go), S.rho);
+                yhb = yhbp.x;
+            }
             float ybar;
             if constexpr (NORM) {
                 // ybar = yhb inv + (p - rad_{k+1} [n > 1e-12] inv yhat): ONE instruction on the chain (t = S.pre is the pre stage's)
@@ -323,6 +376,9 @@ __global__ __launch_bounds__(128 * WAVES, 1) void k_bwd_wave2w(Dev Pk, const flo
             ybar = (yhb - dot * S.yhp) * S.inv + S.pre;
             }
             bcast_issue(aBw, aBr, ybar, qc);                               // 9 ops
+            // the two running sums are up to date here, in the shadow of the broadcast (no instruction): left alone, the scheduler
+            // gathers a whole unrolled chunk's updates at its end and spills their operands on the way
+            if constexpr (NORM) asm volatile("" : "+v"(facc), "+v"(accS));
             {   // M_k = Q + s_k R^dagger, in the shadow of the broadcast (entries 10, 11: inside this step's pre stage, make_pre -- on
                 // normalised rows there is no lane exchange to hide them in, they are formed here; the last MT: in the tail of the step before)
                 const v2f s2 = mk2(S.sd.x, S.sd.x);
@@ -357,6 +413,14 @@ __global__ __launch_bounds__(128 * WAVES, 1) void k_bwd_wave2w(Dev Pk, const flo
             // the tail is one dependency chain with two lane exchanges in it (VALU write -> permlane read: wait states the compiler fills
             // with s_nop): MT entries of the NEXT step's matrix go there (the mat-vec above has consumed this step's)
             const v2f sn2 = __builtin_shufflevector(c0_j, c0_j, 0, 1);     // (s, dtk) of the next step's row: only the low half is read
+            if constexpr (NORM) {
+                float md;
+                chain_tail_n(am, ybar, hmask, md, g, go, MM[12], MRd[12], MQ[12], MM[13], MRd[13], MQ[13], MM[14], MRd[14], MQ[14],
+                             MM[15], MRd[15], MQ[15], sn2);
+                // (the product is rounded in the scan's steps and fused in step 0, as this sum has always been evaluated)
+                accS = decltype(have_pre)::value ? mul_add_rounded(md, uk, accS) : __builtin_fmaf(md, uk, accS);
+                return Sn;
+            }
             float sx = am.x, sy = am.y;                                    // swap32_add (cmps_lane_util.h)
             swap_fill(sx, sy, MM[12], MRd[12], MQ[12], MM[13], MRd[13], MQ[13], sn2);
             const float md = sx + sy;
@@ -408,6 +472,43 @@ __global__ __launch_bounds__(128 * WAVES, 1) void k_bwd_wave2w(Dev Pk, const flo
             const int jhi = (N - 2) < (jlo + CHB - 1) ? (N - 2) : (jlo + CHB - 1);
             const bool new_scal = (hh & 1) == 0 && hh > 0;
             if (new_scal) scal_load((hh >> 1) - 1);
+            if constexpr (NORM) {
+                // A full chunk with a chunk below it, PsiCMPS stash: the 32 steps unrolled with compile-time step numbers (the forward's
+                // CHAIN_STEPC).  Row, partner-row, rho-row, scalar-row, ring-slot and commit offsets are immediates on bases that live in
+                // registers for the whole kernel; what a chunk does not know at compile time is settled once in front of it:
+                //   the ring half of its first octet (an unaligned top octet shifts it): two bases, the octets alternate between them;
+                //   the half of the 64 scalar rows it reads (hh & 1): one base in a VGPR, so that no step moves it there;
+                //   the explicit projection: the chunk's first step, one branch.
+                // Per octet stay the six loads of the rows below (one constant step down two scalar bases), the look at the consumer
+                // count, the commit and the publish.  The arithmetic is chain_step's: the same statements on the same values.
+                if (hh > 0 && vr == 1 && jhi == jlo + CHB - 1) {
+                    const unsigned abE = half_base(oct), abO = half_base(oct + 1);
+                    unsigned aSclC;
+                    asm volatile("v_mov_b32 %0, %1" : "=v"(aSclC) : "s"(aScl + (unsigned)(hh & 1) * (CHB * 16)));
+                    const float4* pyC = sty4 + (size_t)(jlo - CHB) * WAVE_ROW_QUADS;
+                    const float4* prC = rho4 + (size_t)(jlo - CHB) * 16;
+#define BWD2_CSTEP(Q, PQ, EX, AB)                                                                                    \
+                    {                                                                                                 \
+                        if ((PQ) == 3) peek_cons();                                                                   \
+                        own_issue_n_off<(8 * (Q) + (PQ)) * 512, (8 * (Q) + (PQ)) * 256, (8 * (Q) + (PQ)) * 16>(aYown, aYpart, aRho, aSclC, yh_j, part_j, rho_j, c0_j); \
+                        S = chain_step(S, 0.f, std::true_type{}, EX, AB, std::integral_constant<int, (7 - (PQ)) * RING_SLOT>{}); \
+                    }
+#define BWD2_COCTET(Q, EX, AB)                                                                                        \
+                    {                                                                                                 \
+                        octet_load_at(pyC + (Q) * 8 * WAVE_ROW_QUADS, prC + (Q) * 8 * 16);                            \
+                        wait_free(oct);                                                                               \
+                        BWD2_CSTEP(Q, 7, EX, AB) BWD2_CSTEP(Q, 6, false, AB) BWD2_CSTEP(Q, 5, false, AB) BWD2_CSTEP(Q, 4, false, AB) \
+                        BWD2_CSTEP(Q, 3, false, AB) BWD2_CSTEP(Q, 2, false, AB) BWD2_CSTEP(Q, 1, false, AB) BWD2_CSTEP(Q, 0, false, AB) \
+                        octet_commit_below(Q);                                                                        \
+                        publish();                                                                                    \
+                    }
+                    BWD2_COCTET(3, proj_ok, abE) BWD2_COCTET(2, false, abO) BWD2_COCTET(1, false, abE) BWD2_COCTET(0, false, abO)
+#undef BWD2_COCTET
+#undef BWD2_CSTEP
+                    if (new_scal) scal_commit((hh >> 1) - 1);
+                    continue;
+                }
+            }
             int j = jhi;
             // steps above the first aligned octet (top chunk only): slots 8 - u_top .. 7 of octet 0; they are one whole octet of rows
             if (j >= jlo && (j & 7) != 7) {
