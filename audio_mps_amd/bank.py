@@ -32,6 +32,7 @@ import numpy as np
 
 from .model import HParams, PsiCMPS, RhoCMPS
 from .parallel import DataParallel
+from .prior import log_prior_array, log_prior_json, log_prior_of, normalised_prior     # noqa: F401  (normalised_prior: imported from here)
 from .resident import ResidentState
 from .train import Trainer
 
@@ -71,24 +72,6 @@ class CalibrationResult:
         """What bank.json keeps under "calibration"."""
         return {"temperature": float(self.temperature), "log_prior": log_prior_json(self.log_prior), "fit": self.fit, "dataset": dataset,
                 "clips": int(self.n_used), "T": int(self.T), "xent_before": float(self.xent_before), "xent_after": float(self.xent_after)}
-
-
-def log_prior_json(log_prior) -> list:
-    """A log prior as bank.json and a JSON line hold it: floats, and null for -inf (a prior of zero), which JSON has no number for."""
-    return [None if c == -math.inf else float(c) for c in np.asarray(log_prior, dtype=np.float64)]
-
-
-def log_prior_array(values) -> np.ndarray:
-    """`log_prior_json` read back (an array passes through): float64 [M] with -inf for null."""
-    return np.array([-math.inf if c is None else float(c) for c in values], dtype=np.float64)
-
-
-def normalised_prior(log_prior) -> np.ndarray:
-    """exp(c - logsumexp c) of a log prior whose entries are finite or -inf (null: -inf)."""
-    c = log_prior_array(log_prior)
-    top = np.max(c)
-    w = np.exp(c - top)
-    return w / np.sum(w)
 
 
 class PsiBank:
@@ -172,12 +155,12 @@ class PsiBank:
     def nll_per_step(self, clips, segment=None) -> np.ndarray:
         """``PsiCMPS.nll_per_step`` under every member, [M, B, T - 1]: one scored bank stream over ``clips`` [B, T], in segments of
         ``segment`` steps when given (the cut changes no bit)."""
-        return self._scored(clips, segment)[0]
+        return self._scored(clips, segment, "nll_per_step")[0]
 
     def classify(self, clips):
         """M per-class generative models are a classifier: (best [B], total_nll [M, B]) -- the member under which each clip of ``clips``
         [B, T] is the most likely, and every member's loss of every clip."""
-        _, st = self._scored(clips, None)
+        _, st = self._scored(clips, None, "classify")
         return st.best(), st.total_nll
 
     def posterior_trace(self, clips, prior=None, temperature=1.0, threshold=None, segment=None, want_post=False):
@@ -185,37 +168,22 @@ class PsiBank:
         ``BankStream.score_posterior`` in segments of ``segment`` steps when given (the cut changes no bit).  Returns a PosteriorTrace:
         ``best``, ``conf`` [B, T - 1] (``post`` [M, B, T - 1] with want_post) and ``decided_at``, ``decided_as`` [B] -- the step, counted
         from 0, at which the best member's probability first reached ``threshold``, and that member; -1 for a clip that never got there."""
-        clips, S = self._clips(clips, segment)
+        from .stream import PosteriorTrace, as_clips, segments
+        clips = as_clips(clips, "posterior_trace")
         B, N = clips.shape[0], clips.shape[1] - 1
+        cuts = segments(N, segment)
         st = self.open_stream(B, N, prior=prior, temperature=temperature, threshold=threshold)
-        parts = [st.score_posterior(clips[:, :S + 1], want_post=want_post)]
-        for a in range(S + 1, N + 1, S):
-            parts.append(st.score_posterior(clips[:, a:a + S], want_post=want_post))
-        from .stream import PosteriorTrace
+        parts = [st.score_posterior(clips[:, lo:hi], want_post=want_post) for lo, hi in cuts]
         cat = lambda key: np.concatenate([getattr(p, key) for p in parts], axis=-1)                 # noqa: E731
         return PosteriorTrace(cat("best"), cat("conf"), cat("post") if want_post else None, None, parts[-1].decided_at, parts[-1].decided_as)
 
-    def _clips(self, clips, segment):
-        if hasattr(clips, "detach"):
-            clips = clips.detach().cpu().numpy()
-        clips = np.asarray(clips, dtype=np.float32)
-        if clips.ndim == 1:
-            clips = clips[None, :]
-        if clips.ndim != 2 or clips.shape[1] < 2:
-            raise ValueError("clips must be [B, T] with T >= 2")
-        S = clips.shape[1] - 1 if segment is None else int(segment)
-        if S < 1:
-            raise ValueError("segment must be positive")
-        return clips, S
-
-    def _scored(self, clips, segment):
-        clips, S = self._clips(clips, segment)
+    def _scored(self, clips, segment, who):
+        from .stream import as_clips, segments
+        clips = as_clips(clips, who)
         B, N = clips.shape[0], clips.shape[1] - 1
+        cuts = segments(N, segment)
         st = self.open_stream(B, N)
-        parts = [st.score(clips[:, :S + 1])]                          # the anchor and S steps
-        for a in range(S + 1, N + 1, S):
-            parts.append(st.score(clips[:, a:a + S]))
-        return np.concatenate(parts, axis=-1), st
+        return np.concatenate([st.score(clips[:, lo:hi]) for lo, hi in cuts], axis=-1), st
 
 
 class RhoBank(PsiBank):
@@ -316,12 +284,17 @@ class BankTrainer(ResidentState):
         self._configure(st, int(B), int(T), True)
         self._forward(audio, save_for_bwd=True)
         flat = self._backward()
+        self._finish_step(flat, int(B))
+        return {"losses_dev": st["losses"]}
+
+    def _finish_step(self, grad_sums, B):
+        """The optimiser tail of a native step: every member's Adam step and step count advance, the device applies the step, and the
+        resident state is newer than the host's."""
         for tr in self.trainers:
             tr.opt.t += 1
             tr.global_step += 1
-        self._apply(flat, int(B))
+        self._apply(grad_sums, B)
         self._mark_dirty()
-        return {"losses_dev": st["losses"]}
 
     def step_classifier(self, data, labels, gen_weight: float = 0.0, disc_weight: float = 1.0, temperature: float = 1.0,
                         sync: bool = True) -> dict:
@@ -357,11 +330,7 @@ class BankTrainer(ResidentState):
         loss = self._forward(audio, save_for_bwd=True)
         weights, record = be.classify_weights(loss, labels, 1.0 / float(temperature), float(gen_weight), float(disc_weight))
         flat = self._backward(weights=weights)
-        for tr in self.trainers:
-            tr.opt.t += 1
-            tr.global_step += 1
-        self._apply(flat, int(B))
-        self._mark_dirty()
+        self._finish_step(flat, int(B))
         self.global_step += 1
         out = {"global_step": self.global_step}
         if not sync:
@@ -398,27 +367,44 @@ class BankTrainer(ResidentState):
                                      prior=prior, temperature=temperature, threshold=threshold)
 
     # -- held-out evaluation ------------------------------------------------------------------------------
+    def _heldout_pass(self, dataset, minibatch_size, T, who):
+        """One ordered pass over ``dataset`` (a ResidentDataset) with one bank forward per shared batch: (T, an iterator of (first_id,
+        loss [M, B]) on the device).  The backend is configured here, once, for the largest batch; a backend without the bank entries
+        runs its members one after the other.  Forward scans only: no optimiser state, no Adam step and no random stream is touched."""
+        import torch
+        from .evaluate import pass_shape
+        mb, T, B_max = pass_shape(self.bank.backend, dataset, minibatch_size, self.bank.hparams.minibatch_size, T)
+        if self.native:
+            self._configure(self._device_state(), B_max, T, False)
+            forward = lambda batch: self._forward(batch, save_for_bwd=False)                        # noqa: E731
+        else:
+            def forward(batch):
+                rows = [tr.model._forward_entry(tr.model._prepare(B_max, T, train=False))(batch, save_for_bwd=False).clone() for tr in self.trainers]
+                return torch.stack(rows)
+
+        def batches():
+            first_id = None
+            for first_id, batch in dataset.ordered(mb, T):
+                yield first_id, forward(batch)
+            if first_id is None:
+                raise ValueError(f"{who}: the dataset yielded no batch")
+        return T, batches()
+
     def evaluate(self, dataset, minibatch_size: Optional[int] = None, T: Optional[int] = None, keep_losses: bool = False):
         """Every member's loss over every clip of ``dataset`` (a ResidentDataset): a list of EvalResult.  The batches are shared; the bank
         forward scores them for all members at once and cmps_loss_stats folds every member's row into its own record."""
         if not self.native:
             return [tr.evaluate(dataset, minibatch_size, T, keep_losses) for tr in self.trainers]
         import torch
-        from .evaluate import EvalResult, pass_shape
-        be = self.bank.backend
-        mb, T, B_max = pass_shape(be, dataset, minibatch_size, self.bank.hparams.minibatch_size, T)
-        st = self._device_state()
-        self._configure(st, B_max, T, False)
-        M = len(self.trainers)
+        from .evaluate import EvalResult
+        be, M = self.bank.backend, len(self.trainers)
+        T, batches = self._heldout_pass(dataset, minibatch_size, T, "evaluate")
         stats, kept = [None] * M, [[] for _ in range(M)]
-        for first_id, batch in dataset.ordered(mb, T):
-            loss = self._forward(batch, save_for_bwd=False)
+        for first_id, loss in batches:
             for m in range(M):
                 stats[m] = be.loss_stats(loss[m], first_id, stats[m], reset=stats[m] is None)
                 if keep_losses:
                     kept[m].append(loss[m])
-        if stats[0] is None:
-            raise ValueError("evaluate: the dataset yielded no batch")
         return [EvalResult.from_stats(be.read_stats(stats[m]), T, torch.cat(kept[m]).cpu().numpy() if keep_losses else None) for m in range(M)]
 
     def evaluate_classifier(self, dataset, minibatch_size: Optional[int] = None, T: Optional[int] = None, keep_best: bool = False):
@@ -427,41 +413,28 @@ class BankTrainer(ResidentState):
         bank forward and ONE cmps_bank_classify_stats launch, and the record comes back ONCE at the end (``keep_best``: and with it
         every clip's decision, ``result.best`` [n_clips], -1 where no member gave a finite loss)."""
         import torch
-        from .evaluate import ClassifierResult, pass_shape
+        from .evaluate import ClassifierResult
         be = self.bank.backend
         if self.bank.classes is None:
             raise ValueError("evaluate_classifier needs a class bank (PsiBank / RhoBank(..., classes=))")
         if not (hasattr(be, "classify_stats") and hasattr(be, "read_classify_stats")):
             raise ValueError("evaluate_classifier needs a backend that judges the members' losses on the device (classify_stats): "
                              f"{type(be).__name__} has none")
-        mb, T, B_max = pass_shape(be, dataset, minibatch_size, self.bank.hparams.minibatch_size, T)
-        M = len(self.trainers)
-        if self.native:
-            self._configure(self._device_state(), B_max, T, False)
-            forward = lambda batch: self._forward(batch, save_for_bwd=False)                        # noqa: E731
-        else:
-            def forward(batch):
-                rows = []
-                for tr in self.trainers:
-                    rows.append(tr.model._forward_entry(tr.model._prepare(B_max, T, train=False))(batch, save_for_bwd=False).clone())
-                return torch.stack(rows)
+        T, batches = self._heldout_pass(dataset, minibatch_size, T, "evaluate_classifier")
         labels = dataset.class_index(self.bank.classes) if dataset.labels is not None else None
         best = torch.empty(dataset.n_clips, dtype=torch.int32, device=dataset.clips.device) if keep_best else None
         stats = None
-        for first_id, batch in dataset.ordered(mb, T):
-            loss = forward(batch)
+        for first_id, loss in batches:
             B = int(loss.shape[1])
             stats = be.classify_stats(loss, None if labels is None else labels[first_id:first_id + B], first_id, stats, reset=stats is None,
                                       best=None if best is None else best[first_id:first_id + B])
-        if stats is None:
-            raise ValueError("evaluate_classifier: the dataset yielded no batch")
-        return ClassifierResult.from_stats(be.read_classify_stats(stats, M), self.bank.classes, T, best.cpu().numpy() if keep_best else None)
+        return ClassifierResult.from_stats(be.read_classify_stats(stats, len(self.trainers)), self.bank.classes, T,
+                                           best.cpu().numpy() if keep_best else None)
 
     def _heldout_losses(self, dataset, minibatch_size, T, who):
         """`evaluate_classifier`'s ordered pass with every batch's [M][B] losses kept side by side on the device: (loss [M, N], labels
-        [N] int32, the labels on the host, T).  Forward scans only: no optimiser state, no Adam step and no random stream is touched."""
+        [N] int32, the labels on the host, T)."""
         import torch
-        from .evaluate import pass_shape
         be = self.bank.backend
         if self.bank.classes is None:
             raise ValueError(f"{who} needs a class bank (PsiBank / RhoBank(..., classes=))")
@@ -469,43 +442,15 @@ class BankTrainer(ResidentState):
             raise ValueError(f"{who} needs a backend that fits on the device (bank_calibrate): {type(be).__name__} has none")
         if dataset.labels is None:
             raise ValueError(f"{who}: the dataset has no labels")
-        mb, T, B_max = pass_shape(be, dataset, minibatch_size, self.bank.hparams.minibatch_size, T)
-        M = len(self.trainers)
-        if self.native:
-            self._configure(self._device_state(), B_max, T, False)
-            forward = lambda batch: self._forward(batch, save_for_bwd=False)                        # noqa: E731
-        else:
-            def forward(batch):
-                rows = [tr.model._forward_entry(tr.model._prepare(B_max, T, train=False))(batch, save_for_bwd=False).clone() for tr in self.trainers]
-                return torch.stack(rows)
+        T, batches = self._heldout_pass(dataset, minibatch_size, T, who)
         host_labels = dataset.class_positions(self.bank.classes)
         labels = torch.from_numpy(host_labels).to(dataset.clips.device)
         kept = None
-        for first_id, batch in dataset.ordered(mb, T):
-            loss = forward(batch)
+        for first_id, loss in batches:
             if kept is None:
-                kept = torch.empty((M, int(dataset.n_clips)), dtype=torch.float32, device=loss.device)
+                kept = torch.empty((len(self.trainers), int(dataset.n_clips)), dtype=torch.float32, device=loss.device)
             kept[:, first_id:first_id + int(loss.shape[1])].copy_(loss)                             # device to device
-        if kept is None:
-            raise ValueError(f"{who}: the dataset yielded no batch")
         return kept, labels, host_labels, T
-
-    def _start_prior(self, prior, who):
-        """``prior``: None (uniform), "empirical" (the bank's class counts) or [M] probabilities -> the log prior [M] (finite or -inf)."""
-        M = len(self.trainers)
-        if prior is None:
-            return np.zeros(M, dtype=np.float64)
-        if isinstance(prior, str):
-            if prior != "empirical":
-                raise ValueError(f"{who}: prior is None, 'empirical' or {M} probabilities, not {prior!r}")
-            prior = getattr(self.bank, "class_counts", None)
-            if prior is None:
-                raise ValueError(f"{who}: prior='empirical' needs the bank's class counts (a bank trained by class)")
-        p = np.asarray(prior, dtype=np.float64).reshape(-1)
-        if p.shape != (M,) or not np.all(np.isfinite(p)) or np.any(p < 0.0) or not np.sum(p) > 0.0:
-            raise ValueError(f"{who}: prior must be {M} finite probabilities, none negative and not all zero")
-        with np.errstate(divide="ignore"):
-            return np.log(p / np.sum(p))
 
     def calibrate(self, dataset, minibatch_size: Optional[int] = None, T: Optional[int] = None, fit: str = "temperature",
                   temperature: float = 1.0, prior=None, tol: float = 1e-9, max_iter: int = 200, kappa_min: float = 1e-6,
@@ -543,7 +488,9 @@ class BankTrainer(ResidentState):
         import torch
         if not (math.isfinite(temperature) and temperature > 0.0):
             raise ValueError(f"{who}: temperature must be finite and positive")
-        c0 = self._start_prior(prior, who) if log_prior is None else log_prior
+        if log_prior is None:
+            log_prior = log_prior_of(prior, len(self.trainers), self.bank.class_counts, who)
+        c0 = np.zeros(len(self.trainers), dtype=np.float64) if log_prior is None else log_prior             # (None: uniform)
         loss, labels, host_labels, T = self._heldout_losses(dataset, minibatch_size, T, who)
         known = host_labels >= 0
         counts = np.bincount(host_labels[known], minlength=len(self.trainers))

@@ -196,23 +196,27 @@ def build_parser():
 LISTEN_FRACTIONS = ((1, 16), (1, 8), (1, 4), (1, 2), (1, 1))
 
 
-def listen_main(args, backend=None) -> dict:
-    """``--bankdir --listen``: one pass of the dataset through ``bank.posterior_trace``, a batch of clips per scored bank stream.  Per batch
-    ``best`` [B, steps] and the decisions come down once; the accuracy after every sample is counted here from ``best``."""
+def _bank_and_dataset(args, backend):
+    """(bank, load) of ``--bankdir``: the saved class bank, and ``load()`` -> the TFRecord file it is judged on as a ResidentDataset labelled
+    by the bank's label key.  The file is only looked for here: a caller refuses what it can tell from the bank before it reads the file."""
     from .device_data import ResidentDataset
-    from .sample import load_bank, parse_prior
+    from .sample import load_bank
     bank = load_bank(args.bankdir, args.sample_rate, args.hparams, args.kernel_variant, backend)
     if bank.classes is None or bank.label_key is None:
         raise ValueError(f"{args.bankdir} holds a bank without classes: --bankdir judges what train --bank_by saved")
-    if args.calibrated:
-        from .sample import saved_calibration
-        args.temperature, prior = saved_calibration(bank, args.bankdir, args.temperature, args.prior)
-    else:
-        prior = parse_prior(args.prior, bank, args.bankdir)
     path = os.path.join(str(args.datadir), f"{args.dataset}.tfrecords")
     if not os.path.exists(path):
         raise FileNotFoundError(path)
-    ds = ResidentDataset.from_tfrecord(path, args.sample_duration, bank.backend, storage=args.storage, label_key=bank.label_key)
+    return bank, lambda: ResidentDataset.from_tfrecord(path, args.sample_duration, bank.backend, storage=args.storage, label_key=bank.label_key)
+
+
+def listen_main(args, backend=None) -> dict:
+    """``--bankdir --listen``: one pass of the dataset through ``bank.posterior_trace``, a batch of clips per scored bank stream.  Per batch
+    ``best`` [B, steps] and the decisions come down once; the accuracy after every sample is counted here from ``best``."""
+    from .sample import posterior_settings
+    bank, load = _bank_and_dataset(args, backend)
+    args.temperature, prior = posterior_settings(bank, args)
+    ds = load()
     labels = ds.class_positions(bank.classes)
     steps = ds.clip_len - 1
     right = np.zeros(steps, dtype=np.int64)                              # labelled clips whose best member after step k is their own
@@ -251,18 +255,11 @@ def listen_main(args, backend=None) -> dict:
 def bank_main(args, backend=None) -> ClassifierResult:
     """``--bankdir``: a saved class bank judged on a labelled TFRecord file (BankTrainer.evaluate_classifier)."""
     from .bank import BankTrainer
-    from .device_data import ResidentDataset
-    from .sample import load_bank
-    bank = load_bank(args.bankdir, args.sample_rate, args.hparams, args.kernel_variant, backend)
-    if bank.classes is None or bank.label_key is None:
-        raise ValueError(f"{args.bankdir} holds a bank without classes: --bankdir judges what train --bank_by saved")
-    path = os.path.join(str(args.datadir), f"{args.dataset}.tfrecords")
-    if not os.path.exists(path):
-        raise FileNotFoundError(path)
+    from .sample import parse_prior, saved_calibration
+    bank, load = _bank_and_dataset(args, backend)
     if args.calibrated:
-        from .sample import saved_calibration
         saved_calibration(bank, args.bankdir)              # (a bank.json without a calibration: a ValueError before anything is scored)
-    ds = ResidentDataset.from_tfrecord(path, args.sample_duration, bank.backend, storage=args.storage, label_key=bank.label_key)
+    ds = load()
     trainer = BankTrainer(bank)
     res = trainer.evaluate_classifier(ds, args.minibatch_size, keep_best=args.per_clip is not None)
     if args.per_clip is not None:
@@ -277,7 +274,6 @@ def bank_main(args, backend=None) -> ClassifierResult:
         print(f"calibrated {args.dataset}: xent_calibrated={extra['xent_calibrated']:.6g} temperature={cal['temperature']:.6g} "
               f"(fitted on {cal['dataset']}, {cal['clips']} clips of T={cal['T']})")
     if args.calibrate is not None:
-        from .sample import parse_prior
         cal = trainer.calibrate(ds, args.minibatch_size, fit=args.calibrate, temperature=args.temperature,
                                 prior=parse_prior(args.prior, bank, args.bankdir))
         print(f"calibration {cal.line()}")

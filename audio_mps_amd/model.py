@@ -311,21 +311,12 @@ class CMPS(_ScanModel):
         """The fold's increment of every step, [B, T - 1]: -log(1 + e' x / A) of model.py:276-282, 293-294 (RhoCMPS: :152-158,
         169-170; the reference only returns their sum).  One scored stream over the batch (cmps_psi_stream_score / cmps_rho_stream_score), cut into segments of ``segment`` steps when given -- the
         cut changes no bit.  Row sums are ``loss_per_clip`` to float32 rounding."""
-        data = self._batch(data)
-        if hasattr(data, "detach"):
-            data = data.detach().cpu().numpy()
-        data = np.asarray(data, dtype=np.float32)
-        if data.ndim != 2 or data.shape[1] < 2:
-            raise ValueError("data must be [B, T] with T >= 2")
+        from .stream import as_clips, segments
+        data = as_clips(self._batch(data), "nll_per_step")
         B, N = data.shape[0], data.shape[1] - 1
-        S = N if segment is None else int(segment)
-        if S < 1:
-            raise ValueError("segment must be positive")
+        cuts = segments(N, segment)
         st = self.open_stream(B, N)
-        parts = [st.score(data[:, :S + 1])]                           # the anchor and S steps
-        for a in range(S + 1, N + 1, S):
-            parts.append(st.score(data[:, a:a + S]))
-        return np.concatenate(parts, axis=1)
+        return np.concatenate([st.score(data[:, lo:hi]) for lo, hi in cuts], axis=1)
 
     def _prepare_stream(self, num_paths, max_steps, keep_states=0):
         """The backend as a stream needs it: T = max_steps + 1, one table row per step."""
@@ -343,16 +334,11 @@ class CMPS(_ScanModel):
     @staticmethod
     def _prime(prime, num_samples) -> np.ndarray:
         """A prime as the backend takes it: float32 [1, T'] (shared by every path) or [num_samples, T'], T' >= 2."""
-        if hasattr(prime, "detach"):
-            prime = prime.detach().cpu().numpy()
-        prime = np.asarray(prime, dtype=np.float32)
-        if prime.ndim == 1:
-            prime = prime[None, :]
-        if prime.ndim != 2 or prime.shape[0] not in (1, num_samples):
+        from .stream import as_clips
+        prime = as_clips(prime, "prime")
+        if prime.shape[0] not in (1, num_samples):
             raise ValueError(f"prime must be [T'], [1, T'] or [{num_samples}, T'], not {prime.shape}")
-        if prime.shape[1] < 2:
-            raise ValueError("prime needs two samples at least (one increment)")
-        return np.ascontiguousarray(prime)
+        return prime
 
     def continue_clip(self, prime, num_samples, length, temp=1, seed=None, noise=None, device_noise=False) -> np.ndarray:
         """The continuation of ``prime`` in the clip's own units, [num_samples, length]: the array to plot or write behind the clip.

@@ -36,6 +36,8 @@ import wave
 import numpy as np
 
 from .model import CMPS, HParams, PsiCMPS, RhoCMPS
+from .prior import log_prior_of, normalised_prior
+from .stream import as_clips, segments
 
 CKPT_NAME = "model.ckpt.npz"          # what train.main saves into its logdir
 
@@ -125,9 +127,8 @@ def _segmented(model, args, n, length):
     parts = []
     if prime is not None:
         parts.append(np.broadcast_to(prime, (n, prime.shape[1])))
-        st.follow(prime[:, :S + 1])                               # the anchor and S steps
-        for a in range(S + 1, P + 1, S):
-            st.follow(prime[:, a:a + S])
+        for lo, hi in segments(P, S):
+            st.follow(prime[:, lo:hi])
     for a in range(0, length, S):
         parts.append(st.generate(min(S, length - a)))
     return np.concatenate(parts, axis=1)
@@ -135,24 +136,27 @@ def _segmented(model, args, n, length):
 
 def _scored(model, args):
     """--score: the clip followed and scored through a SampleStream, whole or in segments of --segment steps; writes nll.npy / pred.npy."""
-    clip = load_prime(args.score, args.sample_rate)
-    clip = clip[None, :] if clip.ndim == 1 else clip
-    if clip.ndim != 2 or clip.shape[1] < 2:
-        raise ValueError(f"--score {args.score}: need [T'] or [n, T'] with two samples at least (one increment), not {clip.shape}")
+    clip = as_clips(load_prime(args.score, args.sample_rate), f"--score {args.score}")
     n, N = clip.shape[0], clip.shape[1] - 1
-    S = N if args.segment is None else args.segment
     st = model.open_stream(n, N)
-    nll, pred = [st.score(clip[:, :S + 1])], [st.last_pred]       # the anchor and S steps
-    for a in range(S + 1, N + 1, S):
-        nll.append(st.score(clip[:, a:a + S]))
+    nll = _save_scored(st, clip, args)
+    total = float(np.sum(st.total_nll, dtype=np.float64))
+    print(f"scored {n} clip(s) of {N} steps: total nll {total:.6g}, mean per sample {total / (n * N):.6g}; wrote nll.npy and pred.npy to {args.out_dir}")
+    return nll
+
+
+def _save_scored(st, clip, args, one=lambda x: x):
+    """The job of --score for one model and for a bank: ``clip`` [n, T'] followed and scored through the fresh stream ``st``, whole or
+    in segments of --segment steps, then nll.npy and pred.npy written (a bank with a single clip drops the clip axis through ``one``).
+    Returns the nll array; the totals are in ``st.total_nll``."""
+    nll, pred = [], []
+    for lo, hi in segments(clip.shape[1] - 1, args.segment):
+        nll.append(st.score(clip[:, lo:hi]))
         pred.append(st.last_pred)
-    nll = np.ascontiguousarray(np.concatenate(nll, axis=1), dtype=np.float32)
-    pred = np.ascontiguousarray(np.concatenate(pred, axis=1), dtype=np.float32)
+    nll, pred = (np.ascontiguousarray(one(np.concatenate(x, axis=-1)), dtype=np.float32) for x in (nll, pred))
     os.makedirs(args.out_dir, exist_ok=True)
     np.save(os.path.join(args.out_dir, "nll.npy"), nll)
     np.save(os.path.join(args.out_dir, "pred.npy"), pred)
-    total = float(np.sum(st.total_nll, dtype=np.float64))
-    print(f"scored {n} clip(s) of {N} steps: total nll {total:.6g}, mean per sample {total / (n * N):.6g}; wrote nll.npy and pred.npy to {args.out_dir}")
     return nll
 
 
@@ -221,24 +225,18 @@ def load_bank(bankdir: str, sample_rate: int, hparams: str = "", kernel_variant:
 
 
 def parse_prior(spec, bank, where: str = ""):
-    """--prior: None (uniform), "empirical" (the class counts the bank's bank.json holds) or "p0,p1,..." -> [M] floats or None."""
-    if spec is None:
-        return None
-    if spec == "empirical":
-        counts = getattr(bank, "class_counts", None)
-        if counts is None:
-            raise ValueError(f"--prior empirical: {where or 'the bank'} holds no class counts (bank.json of a bank trained with --bank_by)")
-        return [float(c) for c in counts]
-    prior = [float(x) for x in spec.split(",")]
-    if len(prior) != len(bank):
-        raise ValueError(f"--prior names {len(prior)} probabilities, the bank has {len(bank)} members")
+    """--prior: None (uniform) and "empirical" as they are (prior.log_prior_of knows both), "p0,p1,..." -> [M] floats.  What comes back
+    is a prior the bank takes: a wrong one is refused here, before anything is loaded or scored."""
+    prior = spec if spec is None or spec == "empirical" else [float(x) for x in spec.split(",")]
+    if isinstance(prior, list) and len(prior) != len(bank):
+        raise ValueError(f"--prior names {len(prior)} probabilities, {where or 'the bank'} has {len(bank)} members")
+    log_prior_of(prior, len(bank), bank.class_counts, f"--prior {spec}")
     return prior
 
 
 def saved_calibration(bank, where: str, temperature: float = 1.0, prior=None):
     """--calibrated: (temperature, prior [M]) of the calibration bank.json holds (evaluate --calibrate ... --save_calibration), the prior
     normalised as exp(c - logsumexp c).  It stands in for --temperature and --prior, so neither may be given beside it."""
-    from .bank import normalised_prior
     if temperature != 1.0 or prior is not None:
         raise ValueError("--calibrated takes temperature and prior from bank.json: it goes with neither --temperature nor --prior")
     cal = getattr(bank, "calibration", None)
@@ -249,13 +247,18 @@ def saved_calibration(bank, where: str, temperature: float = 1.0, prior=None):
     return float(cal["temperature"]), [float(p) for p in normalised_prior(cal["log_prior"])]
 
 
+def posterior_settings(bank, args):
+    """(temperature, prior) a posterior over the members is judged with: the calibration bank.json holds (--calibrated), else --temperature
+    and --prior."""
+    if args.calibrated:
+        return saved_calibration(bank, args.bankdir, args.temperature, args.prior)
+    return args.temperature, parse_prior(args.prior, bank, args.bankdir)
+
+
 def _bank_posterior(bank, args, clip):
     """--bankdir --score --posterior: the clip followed by every member and judged after every sample (BankStream.score_posterior)."""
     M, n, N = len(bank), clip.shape[0], clip.shape[1] - 1
-    if args.calibrated:
-        temperature, prior = saved_calibration(bank, args.bankdir, args.temperature, args.prior)
-    else:
-        temperature, prior = args.temperature, parse_prior(args.prior, bank, args.bankdir)
+    temperature, prior = posterior_settings(bank, args)
     tr = bank.posterior_trace(clip, prior=prior, temperature=temperature, threshold=args.threshold, segment=args.segment, want_post=True)
     one = (lambda x, lead: x[:, 0] if lead else x[0]) if n == 1 else (lambda x, lead: x)
     post = np.ascontiguousarray(one(tr.post, True), dtype=np.float32)
@@ -285,24 +288,12 @@ def _bank_main(args, backend):
     M, n, length = len(bank), args.num_samples, args.sample_duration
     os.makedirs(args.out_dir, exist_ok=True)
     if args.score is not None:
-        clip = load_prime(args.score, args.sample_rate)
-        clip = clip[None, :] if clip.ndim == 1 else clip
-        if clip.ndim != 2 or clip.shape[1] < 2:
-            raise ValueError(f"--score {args.score}: need [T'] or [n, T'] with two samples at least (one increment), not {clip.shape}")
+        clip = as_clips(load_prime(args.score, args.sample_rate), f"--score {args.score}")
         if args.posterior:
             return _bank_posterior(bank, args, clip)
         n, N = clip.shape[0], clip.shape[1] - 1
-        S = N if args.segment is None else args.segment
         st = bank.open_stream(n, N)
-        nll, pred = [st.score(clip[:, :S + 1])], [st.last_pred]   # the anchor and S steps
-        for a in range(S + 1, N + 1, S):
-            nll.append(st.score(clip[:, a:a + S]))
-            pred.append(st.last_pred)
-        one = (lambda x: x[:, 0]) if n == 1 else (lambda x: x)
-        nll = np.ascontiguousarray(one(np.concatenate(nll, axis=-1)), dtype=np.float32)
-        pred = np.ascontiguousarray(one(np.concatenate(pred, axis=-1)), dtype=np.float32)
-        np.save(os.path.join(args.out_dir, "nll.npy"), nll)
-        np.save(os.path.join(args.out_dir, "pred.npy"), pred)
+        nll = _save_scored(st, clip, args, (lambda x: x[:, 0]) if n == 1 else (lambda x: x))
         totals = np.sum(st.total_nll, axis=1, dtype=np.float64)
         named = (lambda m: f" (class {bank.classes[m]!r})") if bank.classes is not None else (lambda m: "")     # a class bank names its classes
         for m in range(M):
@@ -317,9 +308,8 @@ def _bank_main(args, backend):
     parts = []
     if prime is not None:
         parts.append(np.broadcast_to(prime, (M, n, prime.shape[1])))
-        st.follow(prime[:, :S + 1])                               # the anchor and S steps
-        for a in range(S + 1, P + 1, S):
-            st.follow(prime[:, a:a + S])
+        for lo, hi in segments(P, S):
+            st.follow(prime[:, lo:hi])
     for a in range(0, length, S):
         parts.append(st.generate(min(S, length - a)))
     waves = np.ascontiguousarray(np.concatenate(parts, axis=-1), dtype=np.float32)

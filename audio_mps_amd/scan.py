@@ -623,6 +623,20 @@ class HipScan:
             raise ValueError(f"{what} must be a contiguous uint8 tensor of {nbytes} bytes on the backend's device")
         return record, reset
 
+    def _member_losses(self, loss, who: str, what: str = "loss"):
+        """(M, B, ld) of ``loss`` [M, B], every member's value of every clip as the classifier entries take it: float32 on this device,
+        rows contiguous ``ld`` floats apart, 1 <= M <= CLASSIFY_MAX_M and B >= 1."""
+        if not (_is_tensor(loss, self.device, torch.float32, 2, rows=True) and loss.numel() >= 1):
+            raise ValueError(f"{who}: {what} must be a float32 tensor [M, B] with contiguous rows, M >= 1 and B >= 1, on the backend's device")
+        M, B = int(loss.shape[0]), int(loss.shape[1])
+        if M > _capi.CLASSIFY_MAX_M:
+            raise ValueError(f"{who}: a bank holds 1 .. {_capi.CLASSIFY_MAX_M} members, not {M}")
+        return M, B, int(loss.stride(0)) if M > 1 else B
+
+    def _clip_labels(self, labels, B: int, who: str, what: str = "labels"):
+        if not _is_tensor(labels, self.device, torch.int32, (B,)):
+            raise ValueError(f"{who}: {what} must be a contiguous int32 tensor [B] on the backend's device")
+
     @staticmethod
     def read_stats(stats: torch.Tensor) -> dict:
         """The record of loss_stats as a dict of Python numbers (_capi.LOSS_STATS's fields): the one device -> host copy of an evaluation."""
@@ -635,18 +649,11 @@ class HipScan:
         tensor of cmps_bank_classify_stats_bytes(M) bytes this method allocates -- and resets -- when None), which it returns.
         ``labels``: int32 [B] on this device, the member each clip belongs to (outside [0, M): unlabelled), or None for no labels;
         ``best``: int32 [B] to receive each clip's decision.  No host copy, no synchronisation: read_classify_stats is the download."""
-        if not (_is_tensor(loss, self.device, torch.float32, 2, rows=True) and loss.numel() >= 1):
-            raise ValueError("classify_stats: loss must be a float32 tensor [M, B] with contiguous rows, M >= 1 and B >= 1, on the backend's "
-                             "device")
-        M, B = int(loss.shape[0]), int(loss.shape[1])
-        ld = int(loss.stride(0)) if M > 1 else B
+        M, B, ld = self._member_losses(loss, "classify_stats")
         for name, t in (("labels", labels), ("best", best)):
-            if t is not None and not _is_tensor(t, self.device, torch.int32, (B,)):
-                raise ValueError(f"classify_stats: {name} must be a contiguous int32 tensor [B] on the backend's device")
-        nbytes = int(self._lib.cmps_bank_classify_stats_bytes(M))
-        if nbytes == 0:
-            raise ValueError(f"classify_stats: a record holds 1 .. {_capi.CLASSIFY_MAX_M} members, not {M}")
-        stats, reset = self._record(stats, nbytes, reset, "classify_stats: stats")
+            if t is not None:
+                self._clip_labels(t, B, "classify_stats", name)
+        stats, reset = self._record(stats, int(self._lib.cmps_bank_classify_stats_bytes(M)), reset, "classify_stats: stats")
         _capi.check(self._h, self._lib.cmps_bank_classify_stats(
             self._h, loss.data_ptr(), M, B, ld, labels.data_ptr() if labels is not None else None, int(first_id), 1 if reset else 0,
             stats.data_ptr(), best.data_ptr() if best is not None else None, self._stream()))
@@ -666,23 +673,18 @@ class HipScan:
         [B] on this device) into the cotangents of the cross-entropy objective of include/cmps.h, ``weights`` [M, B] (float32, rows
         contiguous; allocated when None), and fold the batch into the 40-byte ``record`` (uint8 on this device; allocated -- and reset --
         when None).  Returns (weights, record).  No host copy, no synchronisation: read_classify_weights_record is the download."""
-        if not (_is_tensor(loss, self.device, torch.float32, 2, rows=True) and loss.numel() >= 1):
-            raise ValueError("classify_weights: loss must be a float32 tensor [M, B] with contiguous rows, M >= 1 and B >= 1, on the "
-                             "backend's device")
-        M, B = int(loss.shape[0]), int(loss.shape[1])
-        if not 1 <= M <= _capi.CLASSIFY_MAX_M:
-            raise ValueError(f"classify_weights: a bank holds 1 .. {_capi.CLASSIFY_MAX_M} members, not {M}")
-        if not _is_tensor(labels, self.device, torch.int32, (B,)):
-            raise ValueError("classify_weights: labels must be a contiguous int32 tensor [B] on the backend's device")
+        M, B, ld = self._member_losses(loss, "classify_weights")
+        self._clip_labels(labels, B, "classify_weights")
         if weights is None:
-            weights = torch.empty((M, B), dtype=torch.float32, device=self.device)
-        elif not _is_tensor(weights, self.device, torch.float32, (M, B), rows=True):
-            raise ValueError("classify_weights: weights must be a float32 tensor [M, B] with contiguous rows on the backend's device")
+            weights, ldw = torch.empty((M, B), dtype=torch.float32, device=self.device), B
+        else:
+            Mw, Bw, ldw = self._member_losses(weights, "classify_weights", "weights")
+            if (Mw, Bw) != (M, B):
+                raise ValueError(f"classify_weights: weights must be [{M}, {B}] as loss is, not {list(weights.shape)}")
         record, reset = self._record(record, _capi.CLASSIFY_WEIGHTS_REC.itemsize, reset, "classify_weights: record")
         _capi.check(self._h, self._lib.cmps_bank_classify_weights(
-            self._h, loss.data_ptr(), M, B, int(loss.stride(0)) if M > 1 else B, labels.data_ptr(), float(inv_temp), float(gen_weight),
-            float(disc_weight), 1 if reset else 0, weights.data_ptr(), int(weights.stride(0)) if M > 1 else B, record.data_ptr(),
-            self._stream()))
+            self._h, loss.data_ptr(), M, B, ld, labels.data_ptr(), float(inv_temp), float(gen_weight), float(disc_weight),
+            1 if reset else 0, weights.data_ptr(), ldw, record.data_ptr(), self._stream()))
         return weights, record
 
     @staticmethod
@@ -697,14 +699,8 @@ class HipScan:
         ([M] floats, finite or -inf; None: zeros).  ``fit``: a set of _capi.CMPS_CALIB_TEMPERATURE | _capi.CMPS_CALIB_PRIOR; 0 (or
         max_iter = 0) evaluates the cross-entropy under the given values.  Returns ONE uint8 device tensor, theta [1 + M] doubles with
         the 80-byte record behind it: read_calibrate_record is the one download.  No host copy of the losses, no synchronisation."""
-        if not (_is_tensor(loss, self.device, torch.float32, 2, rows=True) and loss.numel() >= 1):
-            raise ValueError("bank_calibrate: loss must be a float32 tensor [M, N] with contiguous rows, M >= 1 and N >= 1, on the "
-                             "backend's device")
-        M, N = int(loss.shape[0]), int(loss.shape[1])
-        if not 1 <= M <= _capi.CLASSIFY_MAX_M:
-            raise ValueError(f"bank_calibrate: a bank holds 1 .. {_capi.CLASSIFY_MAX_M} members, not {M}")
-        if not _is_tensor(labels, self.device, torch.int32, (N,)):
-            raise ValueError("bank_calibrate: labels must be a contiguous int32 tensor [N] on the backend's device")
+        M, N, ld = self._member_losses(loss, "bank_calibrate")
+        self._clip_labels(labels, N, "bank_calibrate")
         theta = np.zeros(1 + M, dtype=np.float64)
         theta[0] = float(kappa)
         if log_prior is not None:
@@ -714,7 +710,7 @@ class HipScan:
         nbytes = int(self._lib.cmps_bank_calibrate_scratch_bytes(M, N))
         scratch = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         _capi.check(self._h, self._lib.cmps_bank_calibrate(
-            self._h, loss.data_ptr(), M, N, int(loss.stride(0)) if M > 1 else N, labels.data_ptr(), int(fit), int(max_iter), float(tol),
+            self._h, loss.data_ptr(), M, N, ld, labels.data_ptr(), int(fit), int(max_iter), float(tol),
             float(kappa_min), float(kappa_max), out.data_ptr(), out.data_ptr() + 8 * (1 + M), scratch.data_ptr(), nbytes, self._stream()))
         return out
 

@@ -29,6 +29,30 @@ from typing import Optional
 
 import numpy as np
 
+from .prior import log_prior_of
+
+
+def segments(N: int, S: Optional[int] = None) -> list:
+    """The column slices (lo, hi) of a clip of ``N`` steps ([n, N + 1]) followed in segments of ``S`` steps (None: whole): the anchor and S
+    steps, (0, S + 1), then S steps at a time, (a, a + S) for a = S + 1, 2 S + 1, ... <= N.  The last slice may reach past the clip.
+    A list, built at once, so that a caller who cuts before it opens its stream has a bad ``S`` refused before anything is opened."""
+    S = int(N) if S is None else int(S)
+    if S < 1:
+        raise ValueError("segment must be positive")
+    return [(0, S + 1)] + [(a, a + S) for a in range(S + 1, int(N) + 1, S)]
+
+
+def as_clips(clips, who: str) -> np.ndarray:
+    """``clips`` ([T'] or [n, T']; a torch tensor or an array) as a stream follows them: contiguous float32 [n, T'] with T' >= 2."""
+    if hasattr(clips, "detach"):
+        clips = clips.detach().cpu().numpy()
+    clips = np.asarray(clips, dtype=np.float32)
+    if clips.ndim == 1:
+        clips = clips[None, :]
+    if clips.ndim != 2 or clips.shape[1] < 2:
+        raise ValueError(f"{who}: need [T'] or [n, T'] with two samples at least (one increment), not {clips.shape}")
+    return np.ascontiguousarray(clips)
+
 
 class SampleStream:
     """Returned by ``PsiCMPS.open_stream`` / ``RhoCMPS.open_stream``.  ``position`` is the number of steps taken (the next table row), ``max_steps`` the number the
@@ -344,17 +368,6 @@ class PosteriorTrace:
     decided_as: Optional[np.ndarray] = None
 
 
-def log_prior_of(prior, M: int):
-    """``prior`` [M] probabilities (any positive scale; a zero: that member never wins) -> their normalised log, float64; None stays None."""
-    if prior is None:
-        return None
-    p = np.asarray(prior, dtype=np.float64)
-    if p.shape != (M,) or not np.all(np.isfinite(p)) or np.any(p < 0) or not p.sum() > 0:
-        raise ValueError(f"prior must be [{M}] finite probabilities, none negative and not all zero")
-    with np.errstate(divide="ignore"):
-        return np.log(p / p.sum())
-
-
 class BankStream(SampleStream):
     """Returned by ``PsiBank.open_stream`` / ``RhoBank.open_stream`` / ``BankTrainer.open_stream``: a SampleStream of every member at once
     (cmps_bank_stream, cmps_bank_stream_score; a RhoBank: cmps_rho_bank_stream, cmps_rho_bank_stream_score).  Everything carries a leading member axis -- results [M, num_paths, steps], ``last`` and ``total_nll``
@@ -366,7 +379,7 @@ class BankStream(SampleStream):
     def __init__(self, bank, num_paths: int, max_steps: int, temp=1, seed=None, device_noise: bool = False, independent_noise: bool = False,
                  prior=None, temperature: float = 1.0, threshold: Optional[float] = None):
         self.independent_noise = bool(independent_noise)
-        log_prior = log_prior_of(prior, len(bank))
+        log_prior = log_prior_of(prior, len(bank), bank.class_counts, "open_stream")
         if not (math.isfinite(temperature) and temperature > 0):
             raise ValueError("open_stream: temperature must be finite and positive")
         if threshold is not None and not 0.0 < float(threshold) <= 1.0:

@@ -176,6 +176,37 @@ def test_calibrate_and_cross_entropy_on_a_stand_in_backend():
         BankTrainer(PsiBank(hparams(), [{"seed": 1}], backend=be)).calibrate(ds, 5)
 
 
+def test_every_held_out_pass_starts_afresh():
+    """One trainer judged and then calibrated gives what two fresh trainers give, bit for bit: a pass carries nothing over to the next.
+    A dataset without a batch is refused by every caller, in its own name.  The stand-in has no bank entries, so this is the pass with the
+    member-loop forward, and `evaluate` is every member's Trainer.evaluate; the native fold is the GPU tests'."""
+    from audio_mps_amd.bank import BankTrainer
+    from audio_mps_amd.device_data import ResidentDataset
+    clips = quiet(12, T)
+
+    def fresh():
+        be = Backend()
+        return be, BankTrainer(class_bank(be=be)), ResidentDataset(clips, be, labels=LABELS)
+
+    def same(a, b):
+        return set(a) == set(b) and all(np.array_equal(np.asarray(a[k]), np.asarray(b[k]), equal_nan=not isinstance(a[k], (list, str))) for k in a)
+    be, bt, ds = fresh()
+    judged, fitted = bt.evaluate_classifier(ds, 5, keep_best=True), bt.calibrate(ds, 5, fit="both")
+    be1, bt1, ds1 = fresh()
+    be2, bt2, ds2 = fresh()
+    alone, fit_alone = bt1.evaluate_classifier(ds1, 5, keep_best=True), bt2.calibrate(ds2, 5, fit="both")
+    assert same(judged.scalars(), alone.scalars()) and np.array_equal(judged.confusion, alone.confusion)
+    assert np.array_equal(judged.best, alone.best) and np.array_equal(judged.unlabelled_best, alone.unlabelled_best)
+    assert same(fitted.scalars(), fit_alone.scalars())
+    assert np.array_equal(be.calib_calls[-1]["loss"].view(np.uint32), be2.calib_calls[-1]["loss"].view(np.uint32))
+    assert [r.scalars() for r in bt.evaluate(ds, 5)] == [r.scalars() for r in bt1.evaluate(ds1, 5)]
+    ds.ordered = lambda minibatch_size, T=None: iter(())
+    for who, call in (("evaluate", bt.evaluate), ("evaluate_classifier", bt.evaluate_classifier), ("calibrate", bt.calibrate),
+                      ("cross_entropy", bt.cross_entropy)):
+        with pytest.raises(ValueError, match=f"^{who}: the dataset yielded no batch"):
+            call(ds, minibatch_size=5)
+
+
 def test_bank_json_round_trip(tmp_path):
     from audio_mps_amd.bank import BankTrainer
     from audio_mps_amd.device_data import ResidentDataset

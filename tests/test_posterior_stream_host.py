@@ -107,6 +107,13 @@ def test_refusals():
         st.score_posterior(_clip(N_PATHS, 12, seed=1))
     assert st.position == 0 and not getattr(st._be, "posterior_calls", [])
     assert np.array_equal(log_prior_of([2, 0, 6], 3), [np.log(0.25), -np.inf, np.log(0.75)]) and log_prior_of(None, 3) is None
+    assert np.array_equal(log_prior_of("empirical", 3, class_counts=[2, 0, 6]), log_prior_of([2, 0, 6], 3))
+    assert np.array_equal(log_prior_of([[2, 0, 6]], 3), log_prior_of([2, 0, 6], 3))      # flattened, as calibrate always took a prior
+    with pytest.raises(ValueError, match="listen: .*class counts"):
+        log_prior_of("empirical", 3, who="listen")
+    for bad in ([2, 6], [2, 0, 6, 1], [2, -1, 6], [2, float("nan"), 6], [0, 0, 0], "uniform"):
+        with pytest.raises(ValueError, match="prior"):
+            log_prior_of(bad, 3, class_counts=[2, 0, 6])
 
 
 def test_posterior_trace_is_classify_after_every_sample():

@@ -312,3 +312,20 @@ def test_sample_main_score_refuses_a_rho_checkpoint(tmp_path):
     with pytest.raises(ValueError, match="PsiCMPS-only"):
         S.main(["--modeldir", ckdir, "--score", npy, "--out_dir", os.path.join(tmp_path, "o")], backend=OracleBackend(D))
     assert not os.path.exists(os.path.join(tmp_path, "o"))
+
+
+@pytest.mark.parametrize("N,S", [(1, None), (1, 1), (5, 1), (5, 2), (5, 5), (5, 8)])
+def test_segments_cut_a_clip_as_the_written_out_loops_did(N, S):
+    from audio_mps_amd.stream import segments
+    cols = np.arange(N + 1)
+    step = N if S is None else S
+    old = [cols[:step + 1]] + [cols[a:a + step] for a in range(step + 1, N + 1, step)]     # "the anchor and S steps", then S steps at a time
+    cuts = list(segments(N, S))
+    got = [cols[lo:hi] for lo, hi in cuts]
+    assert len(got) == len(old) and all(np.array_equal(g, o) for g, o in zip(got, old))
+    assert np.array_equal(np.concatenate(got), cols) and all(len(g) >= 1 for g in got)
+    assert cuts[0][0] == 0 and len(got[0]) == min(step + 1, N + 1)
+    assert all(lo == before[1] for before, (lo, _) in zip(cuts[:-1], cuts[1:]))
+    for bad in (0, -3):
+        with pytest.raises(ValueError):
+            list(segments(N, bad))
